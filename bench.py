@@ -8,11 +8,31 @@
 One "step" = zero_grad -> 3 passes -> 3 losses -> backward -> (grad all-reduce) -> Adam on a synthetic batch that is
 resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up (--warmup steps), times --steps steps and reports them (`value` steps/s, `ms_per_step`).  The
+last timed step restarts from the seeded initial state (parameters, BatchNorm statistics, Adam moments and step count; the
+copies back are timed with it, once per run: 38 / 170 / 103 us of GPU time for the default MultiMNIST / CelebA / COCO
+configurations on an MI355X, i.e. 38/N us per step of an N-step run): the step's float atomics round differently from run
+to run, and the state after many steps would carry that.  So what the last step computes, `final_losses` and the dump, is one training step from
+the initial weights on the fixed batch, the same in every run and for every --steps / --warmup.
+  --dump-outputs DIR  after the timed steps, writes what the last timed step computed as DIR/<name>.npy (float32): `losses`
+                   (loss_1..3), `loss_parts` (mean BCE, mean NLL, KL sum per pass), `grads` (the step's flat gradient),
+                   `exp_avg` / `exp_avg_sq` (Adam's moments after the step) and `bn_stats` (BatchNorm running statistics).
+                   Not the parameters after Adam: its first update is lr x sign(g), and a gradient element near zero whose
+                   rounding crosses zero moves by 2 lr from run to run (tests/test_gpu_bench_restore.py checks them, with
+                   that tolerance, against a fresh engine's first step).
+                   An array of more than DUMP_MAX_ELEMS elements is replaced by a fixed seeded sample of that many
+                   (`<name>_sample`).  Inputs, initial weights and dropout seeds are fixed: equal arguments, equal inputs.
+  --full           also measures everything else below (extra steps and replays after the timed region, CPU baseline).
+
 The JSON line carries, next to the contract fields:
   step_mfma_frac   reference FLOP count (FlopCounterMode on the reference) x steps/s / dense bf16 MFMA peak
+  step_hbm_frac    algorithmic bytes per step (SURVEY 8d: 0.59 GB at B=256) x steps/s / 8 TB/s
+  with_loader      (--loader) the same steps fed by data.DeviceBatcher
+and with --full:
   executed_flops_per_step  GEMM FLOPs this engine actually enqueues per step (encoder passes deduplicated, zero-padded taps
                    included; counted by the launchers), and step_mfma_frac_executed on that count
-  step_hbm_frac    algorithmic bytes per step (SURVEY 8d: 0.59 GB at B=256) x steps/s / 8 TB/s
+  ms_per_step_p10_p50_p90  HIP events around single steps
+  cpu_baseline     the oracle timed on this host's cores (not with --no-cpu-baseline)
   roofline         the GEMM kernel FAMILY with the largest GPU-time share of the step, measured IN THE STEP: every launch of 20
                    extra steps carries its own HIP start/stop events (mmvae_debug_probe); achieved = sum of the family's
                    ALGORITHMIC FLOPs / sum of the durations of ALL its launches, with the other streams' kernels running beside
@@ -52,6 +72,7 @@ ALGO_BYTES_PER_SAMPLE = {"multimnist": 0.59e9 / 256}          # 0.59 
 PEAK_BF16_TFLOPS = 2500.0           # dense bf16 MFMA peak, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
 DEFAULT_BATCH = {"multimnist": 256, "celeba": 512, "coco": 128}
+DUMP_MAX_ELEMS = 4 << 20            # --dump-outputs: per array (16 MB of float32), a dump stays below 64 MB in all
 
 
 def synthetic_batch(B, seed):
@@ -278,6 +299,41 @@ def roofline_entry(eng, call, layer, kernel, B, D):
     return e
 
 
+def training_state(eng):
+    """Every device buffer a training step reads that an earlier step wrote: parameters, BatchNorm statistics, Adam moments and
+    step counter, gradients (packed copies included) and loss sums."""
+    st = eng.state
+    return [st.params, st.bn_stats, st.bn_nbt, st.grads, st.gpk, st.gpk_vec, eng.exp_avg, eng.exp_avg_sq, eng.adam_state, eng.sums]
+
+
+def restore_training_state(eng, saved):
+    """Back to `saved` (copies of training_state(eng)), on the current stream.  The packed bf16 weights are then refreshed as after
+    an optimizer update (_after_update: by the next step's own prologue where the family folds the refresh into it)."""
+    for dst, src in zip(training_state(eng), saved):
+        dst.copy_(src)
+    eng._after_update()
+
+
+def step_outputs(out, eng):
+    """What the last step handed its caller, copied to the host before any further step overwrites it: the losses and their parts
+    (core.StepOutputs), the step's gradient, Adam's moments after the step and the BatchNorm running statistics."""
+    arrays = {"losses": out.losses(), "loss_parts": torch.stack(out.parts()), "grads": eng.state.grads,
+              "exp_avg": eng.exp_avg, "exp_avg_sq": eng.exp_avg_sq, "bn_stats": eng.state.bn_stats}
+    torch.cuda.synchronize()
+    return {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+
+
+def dump_outputs(outdir, arrays):
+    """DIR/<name>.npy in float32; an array above DUMP_MAX_ELEMS elements becomes a fixed seeded sample (<name>_sample.npy)."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -294,7 +350,14 @@ def main():
                     help="also time the step fed by data.DeviceBatcher (pinned uint8 pixels + second modality, double-buffered async H2D, "
                          "u8->f32 on the device) inside the timed loop: reported as `with_loader` next to the resident-input `value`")
     ap.add_argument("--no-probe", action="store_true", help="skip the in-step kernel timing (roofline falls back to the whole step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also count the executed FLOPs and, after the timed steps, measure the per-step distribution, the in-step kernel "
+                         "timing and rooflines, and the CPU baseline (off: the run does only what `value` and `ms_per_step` need)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = args.workload
 
     rank = int(os.environ.get("RANK", "0"))
@@ -352,6 +415,9 @@ def main():
     dp.broadcast_flat(state.params)
     dp.broadcast_flat(state.bn_stats)
     a_d, b_d = a.to(dev).contiguous(), b.to(dev).contiguous()
+    # The step accumulates with float atomics, so the state after many steps carries their rounding and differs from run to
+    # run.  The last timed step restarts from this seeded initial state: what it computes depends on the arguments alone.
+    initial = [t.clone() for t in training_state(eng)]
 
     use_graph = args.graph and world == 1
     if use_graph:
@@ -367,16 +433,15 @@ def main():
     for _ in range(args.warmup):
         run()
     torch.cuda.synchronize()
-    call("mmvae_debug_flops", 1)
-    eng(a_d, b_d)                                         # (eagerly, also with --graph: a replay does not pass through the launchers)
-    executed = call("mmvae_debug_flops", 1)               # GEMM FLOPs one step enqueues (host-side count)
     import gc
     gc.collect()
     gc.disable()            # a generational collection in the enqueue thread stalls the GPU for milliseconds
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         out = run()
+    restore_training_state(eng, initial)                  # (device copies, once per run)
+    out = run()
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
@@ -387,6 +452,8 @@ def main():
         dt = float(t.item())
     losses = out.losses().cpu().numpy().tolist()
     steps_per_s = args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(out, eng))
 
     result = {
         "metric": metric,
@@ -399,8 +466,6 @@ def main():
                    "parallelism": "dp%d" % world, "hip_graph": use_graph, "optimizer": "adam",
                    "mfma": "bf16 in / fp32 acc; fp32 master weights, BN stats, PoE/KL/BCE/NLL, Adam"},
         "final_losses": losses,
-        "executed_flops_per_step": executed,
-        "step_mfma_frac_executed": steps_per_s * executed / (PEAK_BF16_TFLOPS * 1e12),
     }
     if FLOP_PER_SAMPLE[wl]:
         result["reference_flops_per_step"] = B * FLOP_PER_SAMPLE[wl]
@@ -452,20 +517,29 @@ def main():
                                  "loader": "data.DeviceBatcher: %d-batch host dataset, gather into pinned staging on a worker thread, async H2D on a "
                                            "copy stream, u8->f32 on the device, four slots, slot reuse paced on the worker thread" % nb_ds}
 
-    # ---- per-step distribution: HIP events around single steps, outside the timed region
-    n_ev = min(100, args.steps)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
-    evs[0].record()
-    for i in range(n_ev):
-        run()
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_ev))
-    result["ms_per_step_p10_p50_p90"] = [per[int(0.1 * (n_ev - 1))], per[(n_ev - 1) // 2], per[int(0.9 * (n_ev - 1))]]
+    # ---- --full: everything else, after the timed steps (and after --dump-outputs has taken its copy)
+    rows = []
+    if args.full:
+        call("mmvae_debug_flops", 1)
+        eng(a_d, b_d)                                     # (eagerly, also with --graph: a replay does not pass through the launchers)
+        executed = call("mmvae_debug_flops", 1)           # GEMM FLOPs one step enqueues (host-side count)
+        result["executed_flops_per_step"] = executed
+        result["step_mfma_frac_executed"] = steps_per_s * executed / (PEAK_BF16_TFLOPS * 1e12)
 
-    # in-step kernel timing: EVERY rank runs the probed steps (they contain the gradient exchange), rank 0 reports
-    rows = [] if (args.no_probe or use_graph) else probe_steps(call, run, 20)
-    if rank == 0:
+        # ---- per-step distribution: HIP events around single steps, outside the timed region
+        n_ev = min(100, args.steps)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
+        evs[0].record()
+        for i in range(n_ev):
+            run()
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_ev))
+        result["ms_per_step_p10_p50_p90"] = [per[int(0.1 * (n_ev - 1))], per[(n_ev - 1) // 2], per[int(0.9 * (n_ev - 1))]]
+
+        # in-step kernel timing: EVERY rank runs the probed steps (they contain the gradient exchange), rank 0 reports
+        rows = [] if (args.no_probe or use_graph) else probe_steps(call, run, 20)
+    if rank == 0 and args.full:
         if rows:
             result["kernels_in_step"] = kernels_in_step(rows)
         fam_us, fam_fl = {}, {}
@@ -519,6 +593,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(wl, B, D, a, b)
             result["speedup_vs_cpu_baseline"] = steps_per_s / result["cpu_baseline"]["value"]
+    if rank == 0:
         print(json.dumps(result))
     if world > 1:
         import torch.distributed as dist

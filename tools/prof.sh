@@ -1,5 +1,6 @@
 #!/bin/bash
 # usage: tools/prof.sh <tag>   (run on the GPU box via gpurun)
+root=$(cd "$(dirname "$0")/.." && pwd); out=${PROF_OUT:-$root/prof_out}; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_$1 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-probe > $GRAFT_REPO_ROOT/gpurun_out/prof_$1.log 2>&1
-cd $GRAFT_REPO_ROOT && python3 tools/trace_step.py gpurun_out/prof_$1 > gpurun_out/prof_$1.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$1 -- python3 $root/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-probe > $out/prof_$1.log 2>&1
+python3 $root/tools/trace_step.py $out/prof_$1 > $out/prof_$1.txt

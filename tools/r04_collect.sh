@@ -6,12 +6,12 @@ O=gpurun_out/r04; mkdir -p $O
 parts=${@:-bench layers prof pmc}
 for part in $parts; do case $part in
 bench)
-  python bench.py > $O/bench_multimnist.json 2> $O/bench_multimnist.err || { tail -5 $O/bench_multimnist.err; exit 1; }
-  python bench.py --loader --no-cpu-baseline --no-probe --steps 500 > $O/bench_multimnist_loader.json 2>/dev/null || exit 1
-  python bench.py --workload celeba --no-cpu-baseline > $O/bench_celeba.json 2>/dev/null || exit 1
-  python bench.py --workload coco --loader --no-cpu-baseline > $O/bench_coco.json 2>/dev/null || exit 1
-  python bench.py --workload coco --batch 1024 --steps 40 --warmup 5 --no-cpu-baseline --no-probe > $O/bench_coco_b1024.json 2>/dev/null || exit 1
-  python bench.py --graph --no-cpu-baseline --no-probe --steps 500 > $O/bench_multimnist_graph.json 2>/dev/null || exit 1
+  python bench.py --full > $O/bench_multimnist.json 2> $O/bench_multimnist.err || { tail -5 $O/bench_multimnist.err; exit 1; }
+  python bench.py --full --loader --no-cpu-baseline --no-probe --steps 500 > $O/bench_multimnist_loader.json 2>/dev/null || exit 1
+  python bench.py --full --workload celeba --no-cpu-baseline > $O/bench_celeba.json 2>/dev/null || exit 1
+  python bench.py --full --workload coco --loader --no-cpu-baseline > $O/bench_coco.json 2>/dev/null || exit 1
+  python bench.py --full --workload coco --batch 1024 --steps 40 --warmup 5 --no-cpu-baseline --no-probe > $O/bench_coco_b1024.json 2>/dev/null || exit 1
+  python bench.py --full --graph --no-cpu-baseline --no-probe --steps 500 > $O/bench_multimnist_graph.json 2>/dev/null || exit 1
   python tools/dp_overhead.py 300 packed dp 2>&1 | grep "ms/step" > $O/dp_world1.txt || exit 1
   python tools/host_time.py 2>&1 | grep -v amdgpu > $O/host_time.txt
   echo benches done;;
@@ -22,9 +22,10 @@ layers)
   WR_TS=1 python tools/wgrad_check.py 256 dec_convT3_wgrad dec_convT2_wgrad enc_conv2_wgrad enc_conv3_wgrad dec_convT1_wgrad enc_conv4_wgrad 2>&1 | grep -v amdgpu > $O/wgrad_ring_check.txt || exit 1
   echo layer bench done;;
 prof)
-  bash tools/prof.sh r4mm && cp gpurun_out/prof_r4mm/*/*kernel_stats.csv $O/multimnist_kernel_stats.csv && cp gpurun_out/prof_r4mm.txt $O/multimnist_step_timeline.txt || exit 1
-  bash tools/prof_bench.sh r4ca celeba --steps 20 --warmup 3 --no-probe && cp gpurun_out/prof_r4ca/*/*kernel_stats.csv $O/celeba_kernel_stats.csv && cp gpurun_out/prof_r4ca.txt $O/celeba_step_timeline.txt || exit 1
-  bash tools/prof_bench.sh r4co coco --steps 12 --warmup 3 --no-probe && cp gpurun_out/prof_r4co/*/*kernel_stats.csv $O/coco_b128_kernel_stats.csv && cp gpurun_out/prof_r4co.txt $O/coco_b128_step_timeline.txt || exit 1
+  P=${PROF_OUT:-prof_out}             # where tools/prof*.sh write
+  bash tools/prof.sh r4mm && cp $P/prof_r4mm/*/*kernel_stats.csv $O/multimnist_kernel_stats.csv && cp $P/prof_r4mm.txt $O/multimnist_step_timeline.txt || exit 1
+  bash tools/prof_bench.sh r4ca celeba --steps 20 --warmup 3 --no-probe && cp $P/prof_r4ca/*/*kernel_stats.csv $O/celeba_kernel_stats.csv && cp $P/prof_r4ca.txt $O/celeba_step_timeline.txt || exit 1
+  bash tools/prof_bench.sh r4co coco --steps 12 --warmup 3 --no-probe && cp $P/prof_r4co/*/*kernel_stats.csv $O/coco_b128_kernel_stats.csv && cp $P/prof_r4co.txt $O/coco_b128_step_timeline.txt || exit 1
   echo profiles done;;
 pmc)
   bash tools/pmc.sh r4 multimnist --no-probe > $O/pmc.log 2>&1; cp gpurun_out/pmc_r4.txt $O/multimnist_pmc_summary.txt 2>/dev/null; cp gpurun_out/pmc_r4/sq_counters.csv $O/multimnist_sq_counters.csv 2>/dev/null; cp gpurun_out/pmc_r4/traffic.json $O/multimnist_pmc_traffic_by_kernel.json 2>/dev/null
