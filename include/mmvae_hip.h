@@ -147,6 +147,14 @@ int mmvae_mm_text_decoder_fwd(mmvae_mm_t*, void* ws, size_t ws_bytes, const floa
 int mmvae_mm_text_decoder_bwd(mmvae_mm_t*, void* ws, size_t ws_bytes, const float* z, const uint8_t* keep,
                               const long long* force_tokens, const float* words, const long long* tokens,
                               const float* d_words, float* dz, void* stream);
+/* Importance-weighted evaluation (the scoring step between mmvae_iw_particles and mmvae_iw_accumulate): eval-mode decoders on the
+ * B*K particle rows z [B][K][n_latents] of a plan created with at least B*K rows; writes log p(x|z) [B*K] (sum over the 2500
+ * pixels of x*l - softplus(l), l the pre-sigmoid logit: not clamped like the training BCE) and the text decoder's greedy
+ * log-softmax outputs words [B*K][4][12].  image [B][1][50][50] are the examples the rows belong to (row b*K + k: example b).
+ * No backward activations are kept; the BatchNorm running statistics are not touched.  Workspace: mmvae_mm_iw_workspace_bytes. */
+size_t mmvae_mm_iw_workspace_bytes(const mmvae_mm_t*);
+int mmvae_mm_iw_score(mmvae_mm_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K, float* loglik_x,
+                      float* words, void* stream);
 /* Runs one named GEMM of the step `iters` times on the workspace contents of the last step (profiling aid). */
 int mmvae_mm_bench_layer(mmvae_mm_t*, void* ws, size_t ws_bytes, const char* layer, int iters, void* stream);
 double mmvae_mm_layer_flops(const mmvae_mm_t*, const char* layer);        /* executed: 2*rows*N*K, zero-padded taps included */
@@ -387,6 +395,22 @@ int mmvae_bce_bwd(const float* p, const float* target, long long n, float coef, 
 /* F.nll_loss on log-probs [rows][classes] (multimnist/train.py:79) */
 int mmvae_nll_fwd(const float* logp, const long long* target, int rows, int classes, float* out_sum, void* stream);
 int mmvae_nll_bwd(const long long* target, int rows, int classes, float coef, const float* gscale, float* d_logp, void* stream);
+/* Importance-sampled marginal log-likelihood, model-family independent part.  Particle rows are example-major (row b*K + k).
+ * particles: z [B][K][D] = mu + exp(logvar/2) * eps and log_ratio [B][K] = log p(z) - log q(z) (standard normal prior,
+ *   q = N(mu, exp(logvar)), D <= 128); eps is Philox keyed by (seed, first_row + b, first_particle + k, dimension) only -- a particle
+ *   does not depend on the batch or the chunk it is drawn in -- unless eps_or_null ([B][K][D], test hook) is given.
+ * state: [B][3][4] floats per (example, target x / y / xy): running max of log w, sum exp(log w - max), sum exp(2 (log w - max)),
+ *   sum of the target's log-likelihood; iw_init empties it, every iw_accumulate merges one chunk of K particles into it.
+ * accumulate: log p(x|z) = loglik_x [B*K]; log p(y|z) = sum over t < T of words[row][t][targets[b][t]] (words [B*K][T][V],
+ *   targets [B][T] int64, clamped to [0, V)); log w = log-likelihood + log_ratio.  log_w_out_or_null: [B][K][3] log w of the call.
+ * finalize: out [B][8] = log p^(x), log p^(y), log p^(x,y) (logsumexp - log K_total), ESS x / y / xy ((sum w)^2 / sum w^2),
+ *   mean -log p(x|z), mean -log p(y|z) over the K_total particles. */
+int mmvae_iw_particles(const float* mu, const float* logvar, int B, int D, int K, long long first_row, long long first_particle,
+                       unsigned long long seed, const float* eps_or_null, float* z_out, float* log_ratio_out, void* stream);
+int mmvae_iw_init(float* state, int B, void* stream);
+int mmvae_iw_accumulate(const float* loglik_x, const float* words, const long long* targets, int T, int V, const float* log_ratio,
+                        int B, int K, float* state, float* log_w_out_or_null, void* stream);
+int mmvae_iw_finalize(const float* state, int B, long long K_total, float* out, void* stream);
 /* counter-based RNG (Philox4x32-10) */
 int mmvae_normal(float* out, long long n, unsigned long long seed, const long long* step_counter, unsigned stream_id, void* stream);
 int mmvae_keep_mask(uint8_t* out, long long n, float p, unsigned long long seed, const long long* step_counter,

@@ -131,6 +131,8 @@ SIGNATURES = {
     "mmvae_mm_image_encoder_fwd": (_I, [_P, _P, _SZ, _P, _P, _P, _I, _P, _P]),
     "mmvae_mm_image_encoder_bwd": (_I, [_P, _P, _SZ, _P, _P, _P, _P]),
     "mmvae_mm_image_decoder_fwd": (_I, [_P, _P, _SZ, _P, _I, _P, _P]),
+    "mmvae_mm_iw_workspace_bytes": (_SZ, [_P]),
+    "mmvae_mm_iw_score": (_I, [_P, _P, _SZ, _P, _P, _I, _I, _P, _P, _P]),
     "mmvae_mm_image_decoder_bwd": (_I, [_P, _P, _SZ, _P, _P, _P, _P]),
     "mmvae_mm_text_encoder_fwd": (_I, [_P, _P, _SZ, _P, _P, _P]),
     "mmvae_mm_text_encoder_bwd": (_I, [_P, _P, _SZ, _P, _P, _P]),
@@ -153,6 +155,10 @@ SIGNATURES = {
     "mmvae_bce_bwd": (_I, [_P, _P, _LL, _F, _P, _P, _P]),
     "mmvae_nll_fwd": (_I, [_P, _P, _I, _I, _P, _P]),
     "mmvae_nll_bwd": (_I, [_P, _I, _I, _F, _P, _P, _P]),
+    "mmvae_iw_particles": (_I, [_P, _P, _I, _I, _I, _LL, _LL, _ULL, _P, _P, _P, _P]),
+    "mmvae_iw_init": (_I, [_P, _I, _P]),
+    "mmvae_iw_accumulate": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "mmvae_iw_finalize": (_I, [_P, _I, _LL, _P, _P]),
     "mmvae_normal": (_I, [_P, _LL, _ULL, _P, _U, _P]),
     "mmvae_keep_mask": (_I, [_P, _LL, _F, _ULL, _P, _U, _P]),
     "mmvae_mse_fwd": (_I, [_P, _P, _LL, _P, _P]),

@@ -5,6 +5,7 @@
 #include "celeba.h"
 #include "coco.h"
 #include "plan_base.h"
+#include "iw.h"
 #include <cstring>
 #include <exception>
 
@@ -254,6 +255,13 @@ int mmvae_mm_text_decoder_bwd(mmvae_mm_t* p, void* ws, size_t wsb, const float* 
     return mm_text_decoder_bwd(p, ws, wsb, z, keep, force_tokens, words, tokens, d_words, dz, S(stream));
     API_GUARD_END
 }
+size_t mmvae_mm_iw_workspace_bytes(const mmvae_mm_t* p) { return mm_module_workspace_bytes(p); }
+int mmvae_mm_iw_score(mmvae_mm_t* p, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x,
+                      float* words, void* stream) {
+    API_GUARD_BEGIN
+    return mm_iw_score(p, ws, wsb, z, image, B, K, loglik_x, words, S(stream));
+    API_GUARD_END
+}
 int mmvae_mm_bench_layer(mmvae_mm_t* p, void* ws, size_t wsb, const char* layer, int iters, void* stream) {
     API_GUARD_BEGIN
     return mm_bench_layer(p, ws, wsb, layer, iters, S(stream));
@@ -458,6 +466,16 @@ int mmvae_bce_fwd(const float* p, const float* t, long long n, float* out, void*
 int mmvae_bce_bwd(const float* p, const float* t, long long n, float coef, const float* gs, float* dp, void* s) { return launch_bce_bwd(p, t, n, coef, gs, dp, S(s)); }
 int mmvae_nll_fwd(const float* lp, const long long* tg, int rows, int classes, float* out, void* s) { return launch_nll_fwd(lp, tg, rows, classes, out, S(s)); }
 int mmvae_nll_bwd(const long long* tg, int rows, int classes, float coef, const float* gs, float* dlp, void* s) { return launch_nll_bwd(tg, rows, classes, coef, gs, dlp, S(s)); }
+int mmvae_iw_particles(const float* mu, const float* lv, int B, int D, int K, long long first_row, long long first_particle,
+                       unsigned long long seed, const float* eps, float* z, float* log_ratio, void* s) {
+    return launch_iw_particles(mu, lv, B, D, K, first_row, first_particle, seed, eps, z, log_ratio, S(s));
+}
+int mmvae_iw_init(float* state, int B, void* s) { return launch_iw_init(state, B, S(s)); }
+int mmvae_iw_accumulate(const float* lx, const float* words, const long long* targets, int T, int V, const float* log_ratio, int B, int K,
+                        float* state, float* log_w, void* s) {
+    return launch_iw_accumulate(lx, words, targets, T, V, log_ratio, B, K, state, log_w, S(s));
+}
+int mmvae_iw_finalize(const float* state, int B, long long K_total, float* out, void* s) { return launch_iw_finalize(state, B, K_total, out, S(s)); }
 int mmvae_normal(float* out, long long n, unsigned long long seed, const long long* ctr, unsigned sid, void* s) { return launch_normal(out, n, seed, ctr, sid, S(s)); }
 int mmvae_keep_mask(uint8_t* out, long long n, float p, unsigned long long seed, const long long* ctr, unsigned sid, void* s) {
     return launch_keep_mask(out, n, p, seed, ctr, sid, S(s));

@@ -40,6 +40,8 @@ __device__ __forceinline__ bf16x8 tr_pair_d(const char* a0, const char* a1) {
     return u.v;
 }
 
+// IW: the importance-weighted evaluation form (DecLastFusedArgs::loglik): forward only, one log p(x|z) per image, no other output
+template <bool IW>
 __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const A_s = smem + DL_OFF_A;
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
         bn_channel_tables(f, g, tid, aff, mr);
         aff_s[tid] = aff; mr_s[tid] = mr;
     }
-    if (blockIdx.x == 0 && blockIdx.y == 0) {                // the tables backward reads + running statistics: once
+    if (!IW && blockIdx.x == 0 && blockIdx.y == 0) {         // the tables backward reads + running statistics: once
         for (int i = tid; i < f.G * DL_C; i += DL_NTHR) {
             float2 aff, mr;
             bn_channel_tables(f, i / DL_C, i % DL_C, aff, mr);
@@ -84,7 +86,8 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
         const i32x4c z = {0, 0, 0, 0};
         for (int i = tid * 16; i < (DL_ROWS - DL_NPIX) * DL_AP; i += DL_NTHR * 16)      // padding pixel rows of A
             *reinterpret_cast<i32x4c*>(A_s + DL_NPIX * DL_AP + i) = z;
-        for (int i = tid; i < DL_DLW * DL_DLW; i += DL_NTHR) dl_s[i] = 0.f;
+        if (!IW)
+            for (int i = tid; i < DL_DLW * DL_DLW; i += DL_NTHR) dl_s[i] = 0.f;
     }
     // weight fragments (fp32 (32, 1, 4, 4) -> bf16): forward B[k = ch][j = tap] for the two k-steps, input gradient B[k = tap][j = ch]
     bf16x8 wf[2], wd;
@@ -129,6 +132,36 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
         }
     }
     __syncthreads();
+    if constexpr (IW) {
+        // ---- log p(x|z) = sum over pixels of t*l - softplus(l) in fp32 from the logit l (not clamped like the BCE below);
+        //      the target is the image of the example this particle row belongs to
+        const float* const timg = a.target + (long long)(n / a.rows_per_target) * (DL_OH * DL_OW);
+        float ll = 0.f;
+        for (int o = tid; o < DL_OH * DL_OW; o += DL_NTHR) {
+            const int oy = o / DL_OW, ox = o - oy * DL_OW;
+            const int kh0 = (oy + 1) & 1, kw0 = (ox + 1) & 1;
+            const int iy0 = (oy + 1 - kh0) >> 1, ix0 = (ox + 1 - kw0) >> 1;
+            float acc = 0.f;
+#pragma unroll
+            for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+                for (int tx = 0; tx < 2; ++tx) {
+                    const int iy = iy0 - ty, ix = ix0 - tx;
+                    if ((unsigned)iy < (unsigned)DL_IH && (unsigned)ix < (unsigned)DL_IW)
+                        acc += P_s[(iy * DL_IW + ix) * 16 + (kh0 + 2 * ty) * 4 + kw0 + 2 * tx];
+                }
+            ll += timg[o] * acc - (fmaxf(acc, 0.f) + log1pf(expf(-fabsf(acc))));
+        }
+        ll = wave_sum(ll);
+        if (lane == 0) part[wave] = ll;
+        __syncthreads();
+        if (tid == 0) {
+            float s = 0.f;
+            for (int w = 0; w < DL_WAVES; ++w) s += part[w];
+            a.loglik[n] = s;
+        }
+        return;
+    }
     // ---- logits by overlap-add, sigmoid, BCE and its gradient
     float loss = 0.f;
     for (int o = tid; o < DL_OH * DL_OW; o += DL_NTHR) {
@@ -593,8 +626,15 @@ bool dec_last_mfma_applies(const DecLastFusedArgs& a) {
 }
 int launch_dec_last_mfma(const DecLastFusedArgs& a, hipStream_t s) {
     static std::atomic<unsigned> attr_set{0};
-    if (mmvae_first_use_on_device(attr_set))
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_last_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS);   // (+ 32 B static)
-    MMVAE_LAUNCH(dec_last_mfma_kernel, dim3(a.B, a.G), dim3(DL_NTHR), DL_LDS, s, a);
+    if (mmvae_first_use_on_device(attr_set)) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_last_mfma_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS);   // (+ 32 B static)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_last_mfma_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS);
+    }
+    if (a.loglik) {
+        MMVAE_REQUIRE(a.target && a.rows_per_target >= 1 && a.bwd_groups == 0 && !a.fin.training, "dec_last_mfma: importance-weighted form arguments");
+        MMVAE_LAUNCH(dec_last_mfma_kernel<true>, dim3(a.B, a.G), dim3(DL_NTHR), DL_LDS, s, a);
+        return mmvae_check_launch("dec_last_mfma_iw");
+    }
+    MMVAE_LAUNCH(dec_last_mfma_kernel<false>, dim3(a.B, a.G), dim3(DL_NTHR), DL_LDS, s, a);
     return mmvae_check_launch("dec_last_mfma");
 }

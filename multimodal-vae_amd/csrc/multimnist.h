@@ -76,6 +76,9 @@ int mm_text_decoder_fwd(MMPlan*, void* ws, size_t wsb, const float* z, int train
                         const long long* force_tokens, float* words, long long* tokens, hipStream_t);
 int mm_text_decoder_bwd(MMPlan*, void* ws, size_t wsb, const float* z, const uint8_t* keep, const long long* force_tokens,
                         const float* words, const long long* tokens, const float* d_words, float* dz, hipStream_t);
+// importance-weighted evaluation: z [B][K][D] (B*K <= plan rows), image [B][1][50][50] -> loglik_x [B*K], words [B*K][4][12]
+int mm_iw_score(MMPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
+                hipStream_t);
 int mm_unpack_grads(MMPlan*, hipStream_t);
 // makes `s` wait until the early gradient part of the last dp_split step is complete in the flat gradient buffer
 int mm_wait_early_grads(MMPlan*, hipStream_t s);

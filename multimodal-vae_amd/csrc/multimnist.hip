@@ -557,6 +557,7 @@ int fused_tail(MMPlan& P, int groups, int training, const ConvTLastFwdArgs* last
     x.target = last->target; x.logits = last->logits; x.recon = last->recon; x.dlogit = nullptr;
     for (int k = 0; k < 4; ++k) x.coef[k] = last->coef[k];
     x.loss_sum = last->loss_sum;
+    if (last->loglik) { x.loglik = last->loglik; x.rows_per_target = last->rows_per_target; x.B = last->rows; }
     if (x.bwd_groups > 0) {
         const int chunks = x.bwd_groups * B * (dec_last_mfma_applies(x) ? 1 : dec_last_fused_strips(25));
         x.wslab = P.slab.take((size_t)chunks * 32 * 16);
@@ -1233,6 +1234,29 @@ int mm_text_decoder_bwd(MMPlan* P, void* ws, size_t wsb, const float* z, const u
     a.force_tokens = force_tokens; a.words = const_cast<float*>(words); a.tokens_out = const_cast<long long*>(tokens);
     MMVAE_TRY(txt_dec_bwd(*P, a, d_words, dz, s));
     return mm_unpack_grads(P, s);
+}
+
+// ---------------------------------------------------------------- importance-weighted evaluation (iw.h)
+// Eval-mode decoders on the B*K particle rows z [B][K][D]: the image decoder ends in the scoring form of the fused tail (one
+// log p(x|z) per row, against the row's own example), the text decoder writes its greedy log-softmax outputs.  No backward
+// activations are kept and the BatchNorm running statistics are not touched.
+int mm_iw_score(MMPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
+                hipStream_t s) {
+    MMVAE_REQUIRE(P && z && image && loglik_x && words, "mmvae_mm_iw_score: null argument");
+    MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B,
+                  "mmvae_mm_iw_score: %d examples x %d particles exceed the plan's %d rows", B, K, P->B);
+    MMVAE_TRY(use_ws(P, ws, wsb));
+    MMPlan::W& w = P->w;
+    const int rows = B * K;
+    MMVAE_TRY(launch_fill_zero(w.zero_begin, w.zero_bytes, s));
+    hipLaunchKernelGGL(cast_z_kernel, dim3(ceil_div(rows * P->ldz, 256)), dim3(256), 0, s, z, rows, P->D, w.z_bf, P->ldz);
+    MMVAE_TRY(mmvae_check_launch("cast_z"));
+    ConvTLastFwdArgs last{};
+    last.target = image; last.loglik = loglik_x; last.rows_per_target = K; last.rows = rows;
+    MMVAE_TRY(dec_fwd(*P, 1, 0, &last, s, -1, 0));
+    TextDecArgs a = td_args(*P, z, 1, false);
+    a.R = rows; a.words = words;
+    return launch_text_decoder_fwd(a, s);
 }
 
 // ---------------------------------------------------------------- profiling aid: replay one GEMM of the step

@@ -13,6 +13,8 @@ struct ConvTLastFwdArgs {
     float* dlogit;           // coef[g] * dBCE/dlogit or null
     float coef[4];
     float* loss_sum;         // [MMVAE_LOSS_SLOTS][16]: slot row, column g += BCE sums, or null
+    // importance-weighted evaluation (fused tail only, DecLastFusedArgs::loglik): the first `rows` rows are scored
+    float* loglik = nullptr; int rows_per_target = 1; int rows = 0;
 };
 int launch_convt_last_fwd(const ConvTLastFwdArgs& a, hipStream_t s);
 
@@ -50,6 +52,10 @@ struct DecLastFusedArgs {
     bf16* db;                // out NHWC [G*B][IH][IW][Cin]
     float2* red;             // [fin.G][MMVAE_STAT_SLOTS][Cin] += (sum db, sum db*xhat)
     float* wslab;            // [bwd_groups*B*strips][Cin][16]: per-workgroup weight-gradient partials (plain stores)
+    // importance-weighted evaluation (dec_last_mfma only, eval mode, no backward): image n gets loglik[n] = log p(x|z) against
+    // target image n / rows_per_target; nothing else is written (no logits, probabilities, BCE sums or BatchNorm tables)
+    float* loglik = nullptr;
+    int rows_per_target = 1;
 };
 int dec_last_fused_strips(int IH);
 // matrix-core form (dec_last.hip): one workgroup per image, i.e. ONE weight-gradient partial per image (strips = 1)

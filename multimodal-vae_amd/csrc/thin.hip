@@ -469,6 +469,7 @@ int launch_dec_last_fused(const DecLastFusedArgs& a, hipStream_t s) {
     MMVAE_REQUIRE(a.bwd_groups == 0 || (a.target && a.db && a.red && a.wslab), "dec last fused: backward outputs missing");
     MMVAE_REQUIRE(!a.fin.training || a.fin.count > 1.f, "Expected more than 1 value per channel when training");
     if (dec_last_mfma_applies(a)) return launch_dec_last_mfma(a, s);
+    MMVAE_REQUIRE(!a.loglik, "dec last fused: the importance-weighted form needs the matrix-core kernel (G*B = %d images)", a.G * a.B);
     const int strips = dec_last_fused_strips(a.IH);
     const int TW = a.IW + 2, DLW = 2 * a.IW + 2;
     const size_t lds = (size_t)16 * 32 * sizeof(bf16) + (size_t)32 * 16 * sizeof(float) + 2 * 32 * sizeof(float2) +

@@ -8,6 +8,8 @@ of the 4 target characters -- is what is computed here (``recon_text.view(-1, 12
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -144,6 +146,166 @@ test_celeba.__test__ = False              # not a pytest test
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Importance-sampled marginal log-likelihood (the paper's evaluation: log p(x) and log p(y) with K particles per example,
+# once for each posterior) on the HIP kernels of include/mmvae_hip.h: mmvae_iw_particles -> mmvae_mm_iw_score ->
+# mmvae_iw_accumulate per particle chunk, mmvae_iw_finalize per batch.
+
+IW_ROWS = 4096          # particle rows (examples x particles) per scoring call: the plan and workspace of one chunk
+POSTERIORS = ("joint", "image", "text")
+
+
+def iw_chunks(B, K, capacity):
+    """Splits the B x K (example, particle) pairs of one batch into scoring calls of at most ``capacity`` rows:
+    -> [(first_row, n_rows, first_particle, n_particles)], every pair covered exactly once.  All B rows go into one call
+    when they fit (then the K particles are split into near-equal chunks); otherwise the rows are split into near-equal
+    blocks too."""
+    B, K, capacity = int(B), int(K), int(capacity)
+    if B < 1 or K < 1 or capacity < 1:
+        raise ValueError("iw_chunks: need B, K, capacity >= 1 (got %d, %d, %d)" % (B, K, capacity))
+    nrb = -(-B // min(B, capacity))
+    rb = -(-B // nrb)
+    nkc = -(-K // (capacity // rb))
+    kc = -(-K // nkc)
+    return [(r0, min(rb, B - r0), k0, min(kc, K - k0)) for r0 in range(0, B, rb) for k0 in range(0, K, kc)]
+
+
+def _iw_call(name, *args):
+    from ._lib import call
+    return call(name, *args)
+
+
+@torch.no_grad()
+def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0, particles_per_call=None, eps=None,
+                return_z=False, return_log_w=False):
+    """Importance-sampled log p(x), log p(y), log p(x, y) of one batch under the proposal q = N(mu, exp(logvar)).
+
+    ``model``: a multimnist ``MultimodalVAE`` (its decoders run in eval mode); ``image`` (B,1,50,50) float, ``text`` (B,4)
+    int64, ``mu`` / ``logvar`` (B, n_latents), all on the GPU.  Particles z_k = mu + exp(logvar/2) eps_k, k = 1..K, with
+    eps keyed by (seed, first_row + example, particle, dimension) only, so a particle does not depend on the batch it comes
+    in or on how the K particles are split into calls.  With
+        log w_k^x = log p(x|z_k) + log p(z_k) - log q(z_k)       (y, xy alike)
+    the estimate is log p^ = logsumexp_k(log w_k) - log K, a stochastic lower bound (K = 1: the one-sample ELBO), with the
+    effective sample size (sum w)^2 / sum w^2.
+      * log p(x|z) = sum over the 2500 pixels of x*l - softplus(l) in fp32 from the decoder's pre-sigmoid logit l; it is NOT
+        clamped at -100 like ``binary_cross_entropy`` (the two differ only where the decoder is confidently wrong).
+      * log p(y|z) = sum over the 4 positions of the text decoder's eval-mode log-softmax output at the target character,
+        with the greedy feedback of its own argmax (the term ``loss_function`` trains, FILL positions included; not a
+        teacher-forced likelihood).
+    The reference's multimnist/loglikelihood.py (and ``compute_nll``) averages the reconstruction NLL over the particles
+    instead: no prior / proposal ratio, no log-sum-exp, so it is not a bound on log p(x).  Its quantity is reported here as
+    the by-product ``nll`` (mean over the particles of -log p(x|z), -log p(y|z); without the clamp).
+
+    ``particles_per_call``: particles of one scoring call (default: as many as IW_ROWS rows allow).  Test hooks: ``eps``
+    (B, K, n_latents) replaces the generator's draws; ``return_z`` adds z (B, K, n_latents), ``return_log_w`` log w
+    (B, K, 3) (columns x, y, xy).
+    -> dict of device tensors: ``log_p`` (B, 3) and ``ess`` (B, 3) (columns x, y, xy), ``nll`` (B, 2) (image, text)."""
+    from ._lib import ptr
+    dev = mu.device
+    st = model._core.sync(dev)
+    B, D, K = int(mu.shape[0]), int(mu.shape[1]), int(n_particles)
+    if K < 1:
+        raise ValueError("n_particles must be >= 1")
+    capacity = IW_ROWS if particles_per_call is None else B * int(particles_per_call)
+    chunks = iw_chunks(B, K, capacity)
+    rows_max = max(nr * nk for _, nr, _, nk in chunks)
+    image = image.reshape(B, -1).contiguous().float()
+    text = text.contiguous().long()
+    mu, logvar = mu.contiguous().float(), logvar.contiguous().float()
+    if eps is not None:
+        eps = eps.to(dev, torch.float32).reshape(B, K, D)
+    f32 = dict(dtype=torch.float32, device=dev)
+    ws_bytes = max(_iw_call("mmvae_mm_iw_workspace_bytes", st.plan(nr * nk)) for _, nr, _, nk in chunks)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    zbuf, lr, lx = torch.empty(rows_max * D, **f32), torch.empty(rows_max, **f32), torch.empty(rows_max, **f32)
+    words = torch.empty(rows_max * 48, **f32)
+    state = torch.empty(B, 3, 4, **f32)
+    z_all = torch.empty(B, K, D, **f32) if return_z else None
+    lw_all = torch.empty(B, K, 3, **f32) if return_log_w else None
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _iw_call("mmvae_iw_init", ptr(state), B, stream)
+    for r0, nr, k0, nk in chunks:
+        rows = nr * nk
+        e = None if eps is None else eps[r0:r0 + nr, k0:k0 + nk].contiguous()
+        lwc = None if lw_all is None else torch.empty(nr, nk, 3, **f32)
+        _iw_call("mmvae_iw_particles", ptr(mu[r0:]), ptr(logvar[r0:]), nr, D, nk, int(first_row) + r0, k0, int(seed) & (2 ** 64 - 1),
+                 ptr(e), ptr(zbuf), ptr(lr), stream)
+        _iw_call("mmvae_mm_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(zbuf), ptr(image[r0:]), nr, nk, ptr(lx), ptr(words), stream)
+        _iw_call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(text[r0:]), 4, 12, ptr(lr), nr, nk, ptr(state[r0:]), ptr(lwc), stream)
+        if z_all is not None:
+            z_all[r0:r0 + nr, k0:k0 + nk] = zbuf[:rows * D].view(nr, nk, D)
+        if lw_all is not None:
+            lw_all[r0:r0 + nr, k0:k0 + nk] = lwc
+    out = torch.empty(B, 8, **f32)
+    _iw_call("mmvae_iw_finalize", ptr(state), B, K, ptr(out), stream)
+    res = {"log_p": out[:, 0:3], "ess": out[:, 3:6], "nll": out[:, 6:8]}
+    if return_z:
+        res["z"] = z_all
+    if return_log_w:
+        res["log_w"] = lw_all
+    return res
+
+
+def _proposal(model, image, text, posterior):
+    """(mu, logvar) of the eval-mode encoders + ProductOfExperts over the posterior's modalities (no decoder runs)."""
+    if posterior == "joint":
+        im_mu, im_lv = model.image_encoder(image)
+        tx_mu, tx_lv = model.text_encoder(text)
+        mu, lv = torch.stack((im_mu, tx_mu), dim=0), torch.stack((im_lv, tx_lv), dim=0)
+    elif posterior == "image":
+        mu, lv = model.image_encoder(image)
+        mu, lv = mu.unsqueeze(0), lv.unsqueeze(0)
+    elif posterior == "text":
+        mu, lv = model.text_encoder(text)
+        mu, lv = mu.unsqueeze(0), lv.unsqueeze(0)
+    else:
+        raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
+    return model.experts(mu, lv)
+
+
+@torch.no_grad()
+def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use_cuda=True, verbose=False):
+    """Dataset means of the importance-sampled log p^(x), log p^(y), log p^(x, y) (``iw_estimate``) with the proposal of
+    one posterior ("joint": q(z|x,y), "image": q(z|x), "text": q(z|y)), and of the two reconstruction NLLs.
+
+    The model runs in eval mode (BatchNorm running statistics, no dropout); per batch only the encoders and the experts run
+    to form the proposal, then the particle chunks.  Nothing is read back to the host until the end.  Unlike the reference's
+    multimnist/loglikelihood.py, the bounds weight each particle by p(z)/q(z) and take the log-sum-exp (see ``iw_estimate``);
+    ``image_nll`` / ``text_nll`` are the reference's quantity (mean over particles of the summed reconstruction NLL), without
+    its -100 clamp.
+    -> dict: log_px, log_py, log_pxy, image_nll, text_nll (floats), n (examples), log_p (N, 3) and ess (N, 3) per example
+    (CPU tensors, columns x, y, xy)."""
+    if not use_cuda:
+        raise ValueError("log_marginal runs on the GPU (the HIP kernels); there is no CPU path")
+    if posterior not in POSTERIORS:
+        raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
+    model.eval()
+    dev = next(model.parameters()).device
+    logp, ess, nll, n_seen = [], [], [], 0
+    for image, text in loader:
+        image = image.to(dev).float().reshape(-1, 1, 50, 50)
+        text = text.to(dev).long()
+        mu, logvar = _proposal(model, image, text, posterior)
+        r = iw_estimate(model, image, text, mu, logvar, n_particles, seed=seed, first_row=n_seen)
+        logp.append(r["log_p"]); ess.append(r["ess"]); nll.append(r["nll"])
+        n_seen += image.shape[0]
+        if verbose:
+            print('Evaluating [{}]: {} examples'.format(posterior, n_seen))
+    if n_seen == 0:
+        raise ValueError("log_marginal: empty loader")
+    logp, ess, nll = torch.cat(logp).cpu(), torch.cat(ess).cpu(), torch.cat(nll).cpu()
+    m, mn = logp.double().mean(0), nll.double().mean(0)
+    return {"log_px": m[0].item(), "log_py": m[1].item(), "log_pxy": m[2].item(), "image_nll": mn[0].item(),
+            "text_nll": mn[1].item(), "n": n_seen, "log_p": logp, "ess": ess}
+
+
+@torch.no_grad()
+def marginal_table(model, loader, n_particles=1000, seed=0):
+    """The paper's evaluation: log p^(x) and log p^(y) (plus log p^(x, y)) under each of the three posteriors, K particles
+    per example.  -> {posterior: log_marginal(...) result} for "joint", "image", "text"."""
+    return {post: log_marginal(model, loader, n_particles, post, seed=seed) for post in POSTERIORS}
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # multimnist/sample.py:59-144 as a function and a script: `python -m multimodal_vae_amd.evaluate sample model.pth.tar ...`
 
 @torch.no_grad()
@@ -173,11 +335,8 @@ def sample(vae, n_samples=64, image=None, text=None, use_cuda=True):
     return image_recon, text_recon
 
 
-def _main(argv=None):
+def _parser():
     import argparse
-    import os
-    from .train import load_checkpoint
-    from .utils import char_tensor, tensor_to_string
     parser = argparse.ArgumentParser(prog="python -m multimodal_vae_amd.evaluate")
     sub = parser.add_subparsers(dest="cmd", required=True)
     ps = sub.add_parser("sample", help="multimnist/sample.py")
@@ -186,7 +345,66 @@ def _main(argv=None):
     ps.add_argument('--condition_on_image', type=str, default=None, help='a .pt file holding a (50,50) uint8 or float image')
     ps.add_argument('--condition_on_text', type=str, default=None, help='a digit string of at most 4 characters')
     ps.add_argument('--out', type=str, default='./results')
-    args = parser.parse_args(argv)
+    # multimnist/loglikelihood.py's flags and defaults, plus the importance-sampled bounds (log_marginal / marginal_table)
+    pl = sub.add_parser("loglik", help="multimnist/loglikelihood.py + importance-sampled log p(x), log p(y)")
+    pl.add_argument('model_path', type=str, help='path to trained model file')
+    mode = pl.add_mutually_exclusive_group()
+    mode.add_argument('--image_only', action='store_true', default=False,
+                      help='compute NLL of test data using reconstructions from image only')
+    mode.add_argument('--text_only', action='store_true', default=False,
+                      help='compute NLL of test data using reconstructions from text only')
+    mode.add_argument('--all', action='store_true', default=False, help='all three posteriors (the paper\'s table)')
+    pl.add_argument('--n_samples', type=int, default=100, help='number of samples to use to estimate the ELBO')
+    pl.add_argument('--cuda', action='store_true', default=False, help='accepted for compatibility: the kernels run on the GPU')
+    pl.add_argument('--batch_size', type=int, default=64)
+    src = pl.add_mutually_exclusive_group()
+    src.add_argument('--data', type=str, default='./data', help='folder of the MultiMNIST test file')
+    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic MultiMNIST-shaped examples instead of files')
+    pl.add_argument('--seed', type=int, default=0, help='seed of the particles')
+    pl.add_argument('--json', type=str, default=None, help='write the bounds to this file')
+    return parser
+
+
+def _loglik_main(args):
+    import json
+    from . import data as D
+    from .train import load_checkpoint
+    from .utils import charlist_tensor
+    if args.synthetic > 0:
+        x, labels = D.synthetic_multimnist(args.synthetic, seed=args.seed)
+        t = torch.stack([charlist_tensor(l) for l in labels])
+    else:
+        x, t = D.load_multimnist(args.data, train=False)
+    x = x.float().div_(255.0).view(-1, 1, 50, 50)                 # transforms.ToTensor()
+    loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    vae = load_checkpoint(args.model_path, use_cuda=True)
+    posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
+    table = {}
+    for post in posts:
+        r = log_marginal(vae, loader, n_particles=args.n_samples, posterior=post, seed=args.seed)
+        table[post] = r
+        mess = r["ess"].double().mean(0)
+        print('\nTest Image NLL: {:.4f}\tTest Text NLL: {:.4f}'.format(r["image_nll"], r["text_nll"]))
+        print('[{} posterior, K = {}] log p(x) >= {:.4f}\tlog p(y) >= {:.4f}\tlog p(x,y) >= {:.4f}\t'
+              'mean ESS x / y / xy: {:.2f} / {:.2f} / {:.2f}'.format(post, args.n_samples, r["log_px"], r["log_py"], r["log_pxy"],
+                                                                    *mess.tolist()))
+    if args.json:
+        out = {"n_samples": args.n_samples, "n_examples": table[posts[0]]["n"], "seed": args.seed}
+        for post, r in table.items():
+            out[post] = {k: r[k] for k in ("log_px", "log_py", "log_pxy", "image_nll", "text_nll")}
+            out[post]["mean_ess"] = r["ess"].double().mean(0).tolist()
+        with open(args.json, 'w') as fp:
+            json.dump(out, fp, indent=1)
+    return table
+
+
+def _main(argv=None):
+    import os
+    from .train import load_checkpoint
+    from .utils import char_tensor, tensor_to_string
+    args = _parser().parse_args(argv)
+    if args.cmd == "loglik":
+        return _loglik_main(args)
     vae = load_checkpoint(args.model_path, use_cuda=True)
     image = text = None
     if args.condition_on_image:
