@@ -233,6 +233,14 @@ int mmvae_mnist_text_decoder_fwd(mmvae_mnist_t*, void* ws, size_t ws_bytes, cons
                                  void* stream);                                                 /* mnist/model.py:168-170 */
 int mmvae_mnist_text_decoder_bwd(mmvae_mnist_t*, void* ws, size_t ws_bytes, const float* d_log_probs, const float* log_probs,
                                  float* dz, void* stream);
+/* Importance-weighted evaluation, the MNIST scoring step between mmvae_iw_particles and mmvae_iw_accumulate(T = 1, V = 10): ONE
+ * kernel runs both eval-mode decoders (BatchNorm = the affine map of the running statistics) on the B*K particle rows
+ * z [B][K][n_latents] (row b*K + k: example b) and writes loglik_x [B*K] = sum over the 784 pixels of x*l - softplus(l) (l the
+ * pre-sigmoid logit, not clamped like the training BCE) against image [B][784], and words [B*K][10] = the text decoder's
+ * log-softmax.  fp32 MFMA on the bound fp32 parameters whatever the plan's precision: no pack_weights, no workspace, any B*K
+ * below 2^31 (independent of the plan's batch).  Nothing of the plan or the model is modified. */
+int mmvae_mnist_iw_score(mmvae_mnist_t*, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
+                         void* stream);
 
 /* ---------------------------------------------------------------- CelebA (celeba/model.py, celeba/train.py)
  * MultimodalVAE of celeba/model.py:14-57: conv ImageEncoder :91-128 / ImageDecoder :131-161 on 3x64x64 images,

@@ -221,6 +221,7 @@ SIGNATURES["mmvae_mnist_image_encoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P])
 SIGNATURES["mmvae_mnist_image_decoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P])
 SIGNATURES["mmvae_mnist_text_encoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P])
 SIGNATURES["mmvae_mnist_text_decoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P])
+SIGNATURES["mmvae_mnist_iw_score"] = (_I, [_P, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES.update(_plan_api("celeba"))
 SIGNATURES["mmvae_celeba_step"] = (_I, [_P, C.POINTER(CelebaStepIO), _I, _I, _P])
 SIGNATURES["mmvae_celeba_image_encoder_fwd"] = (_I, [_P, _P, _SZ, _P, _P, _I, _P, _P])

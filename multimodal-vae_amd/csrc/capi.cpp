@@ -325,6 +325,11 @@ int mmvae_mnist_text_decoder_bwd(mmvae_mnist_t* p, void* ws, size_t wsb, const f
     return mnist_text_decoder_bwd(p, ws, wsb, d_logp, logp, dz, S(st));
     API_GUARD_END
 }
+int mmvae_mnist_iw_score(mmvae_mnist_t* p, const float* z, const float* image, int B, int K, float* loglik_x, float* words, void* st) {
+    API_GUARD_BEGIN
+    return mnist_iw_score(p, z, image, B, K, loglik_x, words, S(st));
+    API_GUARD_END
+}
 
 // ---- CelebA (celeba/model.py, celeba/train.py)
 mmvae_celeba_t* mmvae_celeba_create(int n_latents, int batch) {

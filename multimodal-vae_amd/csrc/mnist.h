@@ -37,3 +37,8 @@ int mnist_text_encoder_fwd(MnistPlan*, void* ws, size_t wsb, const long long* la
 int mnist_text_encoder_bwd(MnistPlan*, void* ws, size_t wsb, const long long* label, const float* d_out, hipStream_t);
 int mnist_text_decoder_fwd(MnistPlan*, void* ws, size_t wsb, const float* z, int training, float* logp, hipStream_t);
 int mnist_text_decoder_bwd(MnistPlan*, void* ws, size_t wsb, const float* d_logp, const float* logp, float* dz, hipStream_t);
+// Importance-weighted evaluation (mnist_iw.hip): eval-mode decoders on B*K particle rows z [B][K][D] (example-major, iw.h) in ONE
+// kernel -> loglik_x [B*K] = sum over pixels of x*l - softplus(l) against image [B][784], words [B*K][10] = the text decoder's
+// log-softmax.  Reads the bound fp32 parameters and running statistics (either precision; no pack_weights, no workspace, no row
+// limit from the plan's batch); touches no plan state.
+int mnist_iw_score(MnistPlan*, const float* z, const float* image, int B, int K, float* loglik_x, float* words, hipStream_t);

@@ -60,6 +60,19 @@ def synthetic_multimnist(n: int, seed: int = 0, size: int = 50) -> Tuple[torch.T
     return images, labels
 
 
+def synthetic_mnist(n: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MNIST-shaped stand-in (no MNIST files in this environment): -> (uint8 (n,28,28), int64 (n,)), the layout of torchvision's
+    ``processed/test.pt``.  One blob per canvas whose extent encodes the label digit."""
+    g = torch.Generator().manual_seed(seed)
+    images = torch.zeros(n, 28, 28, dtype=torch.uint8)
+    labels = torch.randint(0, 10, (n,), generator=g)
+    for i in range(n):
+        w = 6 + int(labels[i])
+        y, x = (int(v) for v in torch.randint(0, 28 - w + 1, (2,), generator=g))
+        images[i, y:y + w, x:x + w] = (torch.rand(w, w, generator=g) * 255).to(torch.uint8)
+    return images, labels
+
+
 class DeviceBatcher:
     """Iterates ``(image fp32, second modality)`` device batches over a uint8 image dataset.
 

@@ -79,6 +79,66 @@ test_multimnist.__test__ = False          # not a pytest test
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# MNIST consumers (mnist/loglikelihood.py:15-65, mnist/test.py:18-36)
+
+@torch.no_grad()
+def compute_nll_mnist(model, loader, image_only=False, text_only=False, n_samples=1, use_cuda=True, verbose=False):
+    """-> (image NLL per sample, label NLL per sample), mnist/loglikelihood.py:15-65."""
+    from .mnist import _BCEMeanFn as _BCE, _NLLMeanFn as _NLL
+    assert not (image_only and text_only)
+    model.eval()
+    test_image_nll, test_text_nll, n_seen = 0.0, 0.0, 0
+    for image, text in loader:
+        if use_cuda:
+            image, text = image.cuda(), text.cuda()
+        image = image.float().reshape(-1, 784)
+        if not image_only and not text_only:
+            _, _, mu, logvar = model(image, text)
+        elif image_only:
+            _, _, mu, logvar = model(image=image)
+        else:
+            _, _, mu, logvar = model(text=text)
+        batch_size, n_latents = mu.size(0), mu.size(1)
+        sample = torch.randn(n_samples, n_latents)                # drawn on the host like the reference (:37)
+        if use_cuda:
+            sample = sample.cuda()
+        z = sample.unsqueeze(0) * logvar.mul(0.5).exp().unsqueeze(1) + mu.unsqueeze(1)      # (B, n_samples, D)
+        image_nll, text_nll = 0.0, 0.0
+        for i in range(n_samples):
+            zi = z[:, i].contiguous()
+            recon_image = model.decode_image(zi)
+            recon_text = model.decode_text(zi)
+            image_nll += float(_BCE.apply(recon_image.reshape(batch_size, -1), image)) * image.numel()
+            text_nll += float(_NLL.apply(recon_text, text.reshape(-1))) * text.numel()
+        test_image_nll += image_nll / n_samples
+        test_text_nll += text_nll / n_samples
+        n_seen += batch_size
+        if verbose:
+            print('Evaluating: [{}/{}]'.format(n_seen, len(loader) * batch_size))
+    return test_image_nll / max(n_seen, 1), test_text_nll / max(n_seen, 1)
+
+
+@torch.no_grad()
+def test_mnist(model, loader, use_cuda=True, verbose=True):
+    """-> accuracy of the label predicted from the image alone, mnist/test.py:18-36."""
+    model.eval()
+    correct, n_seen = 0, 0
+    for image, text in loader:
+        if use_cuda:
+            image, text = image.cuda(), text.cuda()
+        _, recon_text, _, _ = model(image=image.float().reshape(-1, 784))
+        pred = recon_text.max(1, keepdim=True)[1]
+        correct += int(pred.eq(text.view_as(pred)).sum())
+        n_seen += int(text.numel())
+    if verbose:
+        print('\nTest set: Accuracy: {}/{} ({:.0f}%)\n'.format(correct, n_seen, 100. * correct / max(n_seen, 1)))
+    return correct / float(max(n_seen, 1))
+
+
+test_mnist.__test__ = False               # not a pytest test
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # CelebA consumers (celeba/loglikelihood.py:18-67, celeba/test.py:44-71)
 
 @torch.no_grad()
@@ -147,10 +207,11 @@ test_celeba.__test__ = False              # not a pytest test
 
 # ------------------------------------------------------------------------------------------------------------------
 # Importance-sampled marginal log-likelihood (the paper's evaluation: log p(x) and log p(y) with K particles per example,
-# once for each posterior) on the HIP kernels of include/mmvae_hip.h: mmvae_iw_particles -> mmvae_mm_iw_score ->
-# mmvae_iw_accumulate per particle chunk, mmvae_iw_finalize per batch.
+# once for each posterior) on the HIP kernels of include/mmvae_hip.h: mmvae_iw_particles -> the model family's scoring call
+# (mmvae_mm_iw_score, mmvae_mnist_iw_score) -> mmvae_iw_accumulate per particle chunk, mmvae_iw_finalize per batch.
 
 IW_ROWS = 4096          # particle rows (examples x particles) per scoring call: the plan and workspace of one chunk
+IW_ROWS_MNIST = 65536   # ... of the fused MNIST scorer: no plan or workspace per chunk, 32 rows per workgroup (2048 workgroups a call)
 POSTERIORS = ("joint", "image", "text")
 
 
@@ -174,14 +235,48 @@ def _iw_call(name, *args):
     return call(name, *args)
 
 
+class _Family:
+    """What the evaluation needs to know about a model family: the scoring call between particles and accumulate, the text
+    decoder's steps T and classes V (words [rows][T][V]), the shape of one image, the particle rows of one scoring call and
+    the scoring workspace."""
+
+    def __init__(self, name, T, V, image_shape, rows, score, workspace_bytes):
+        self.name, self.T, self.V, self.image_shape, self.rows = name, T, V, image_shape, rows
+        self.score, self.workspace_bytes = score, workspace_bytes
+
+
+def _mm_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
+    from ._lib import ptr
+    _iw_call("mmvae_mm_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)
+
+
+def _mnist_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
+    from ._lib import ptr
+    _iw_call("mmvae_mnist_iw_score", st.plan(1), ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)   # any bound plan: no row limit
+
+
+_FAMILIES = {
+    "multimnist": _Family("multimnist", 4, 12, (1, 50, 50), IW_ROWS, _mm_score,
+                          lambda st, rows: _iw_call("mmvae_mm_iw_workspace_bytes", st.plan(rows))),
+    "mnist": _Family("mnist", 1, 10, (784,), IW_ROWS_MNIST, _mnist_score, lambda st, rows: 0),
+}
+
+
+def _family(model):
+    from .mnist import MultimodalVAE as MnistVAE
+    return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "multimnist"]
+
+
 @torch.no_grad()
 def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0, particles_per_call=None, eps=None,
                 return_z=False, return_log_w=False):
     """Importance-sampled log p(x), log p(y), log p(x, y) of one batch under the proposal q = N(mu, exp(logvar)).
 
     ``model``: a multimnist ``MultimodalVAE`` (its decoders run in eval mode); ``image`` (B,1,50,50) float, ``text`` (B,4)
-    int64, ``mu`` / ``logvar`` (B, n_latents), all on the GPU.  Particles z_k = mu + exp(logvar/2) eps_k, k = 1..K, with
-    eps keyed by (seed, first_row + example, particle, dimension) only, so a particle does not depend on the batch it comes
+    int64, ``mu`` / ``logvar`` (B, n_latents), all on the GPU.  A mnist ``MultimodalVAE`` takes ``image`` (B,784) (or anything
+    that reshapes to it) and the labels ``text`` (B,) int64: one fused fp32 kernel scores its particles (mmvae_mnist_iw_score;
+    784 pixels, one text position of 10 classes, no greedy feedback), everything else below is the same.
+    Particles z_k = mu + exp(logvar/2) eps_k, k = 1..K, with eps keyed by (seed, first_row + example, particle, dimension) only, so a particle does not depend on the batch it comes
     in or on how the K particles are split into calls.  With
         log w_k^x = log p(x|z_k) + log p(z_k) - log q(z_k)       (y, xy alike)
     the estimate is log p^ = logsumexp_k(log w_k) - log K, a stochastic lower bound (K = 1: the one-sample ELBO), with the
@@ -195,29 +290,33 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     instead: no prior / proposal ratio, no log-sum-exp, so it is not a bound on log p(x).  Its quantity is reported here as
     the by-product ``nll`` (mean over the particles of -log p(x|z), -log p(y|z); without the clamp).
 
-    ``particles_per_call``: particles of one scoring call (default: as many as IW_ROWS rows allow).  Test hooks: ``eps``
-    (B, K, n_latents) replaces the generator's draws; ``return_z`` adds z (B, K, n_latents), ``return_log_w`` log w
+    ``particles_per_call``: particles of one scoring call (default: as many as IW_ROWS rows allow; IW_ROWS_MNIST for MNIST).
+    Test hooks: ``eps`` (B, K, n_latents) replaces the generator's draws; ``return_z`` adds z (B, K, n_latents), ``return_log_w`` log w
     (B, K, 3) (columns x, y, xy).
     -> dict of device tensors: ``log_p`` (B, 3) and ``ess`` (B, 3) (columns x, y, xy), ``nll`` (B, 2) (image, text)."""
     from ._lib import ptr
+    fam = _family(model)
     dev = mu.device
     st = model._core.sync(dev)
     B, D, K = int(mu.shape[0]), int(mu.shape[1]), int(n_particles)
     if K < 1:
         raise ValueError("n_particles must be >= 1")
-    capacity = IW_ROWS if particles_per_call is None else B * int(particles_per_call)
+    capacity = fam.rows if particles_per_call is None else B * int(particles_per_call)
     chunks = iw_chunks(B, K, capacity)
     rows_max = max(nr * nk for _, nr, _, nk in chunks)
     image = image.reshape(B, -1).contiguous().float()
     text = text.contiguous().long()
+    if image.shape[1] != int(np.prod(fam.image_shape)) or text.numel() != B * fam.T:
+        raise ValueError("iw_estimate: a %s model takes images of %d pixels and %d target(s) per example (got %s, %s)" %
+                         (fam.name, int(np.prod(fam.image_shape)), fam.T, tuple(image.shape), tuple(text.shape)))
     mu, logvar = mu.contiguous().float(), logvar.contiguous().float()
     if eps is not None:
         eps = eps.to(dev, torch.float32).reshape(B, K, D)
     f32 = dict(dtype=torch.float32, device=dev)
-    ws_bytes = max(_iw_call("mmvae_mm_iw_workspace_bytes", st.plan(nr * nk)) for _, nr, _, nk in chunks)
+    ws_bytes = max(fam.workspace_bytes(st, nr * nk) for _, nr, _, nk in chunks)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     zbuf, lr, lx = torch.empty(rows_max * D, **f32), torch.empty(rows_max, **f32), torch.empty(rows_max, **f32)
-    words = torch.empty(rows_max * 48, **f32)
+    words = torch.empty(rows_max * fam.T * fam.V, **f32)
     state = torch.empty(B, 3, 4, **f32)
     z_all = torch.empty(B, K, D, **f32) if return_z else None
     lw_all = torch.empty(B, K, 3, **f32) if return_log_w else None
@@ -229,8 +328,8 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
         lwc = None if lw_all is None else torch.empty(nr, nk, 3, **f32)
         _iw_call("mmvae_iw_particles", ptr(mu[r0:]), ptr(logvar[r0:]), nr, D, nk, int(first_row) + r0, k0, int(seed) & (2 ** 64 - 1),
                  ptr(e), ptr(zbuf), ptr(lr), stream)
-        _iw_call("mmvae_mm_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(zbuf), ptr(image[r0:]), nr, nk, ptr(lx), ptr(words), stream)
-        _iw_call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(text[r0:]), 4, 12, ptr(lr), nr, nk, ptr(state[r0:]), ptr(lwc), stream)
+        fam.score(st, rows, ws, ws_bytes, zbuf, image[r0:], nr, nk, lx, words, stream)
+        _iw_call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(text[r0:]), fam.T, fam.V, ptr(lr), nr, nk, ptr(state[r0:]), ptr(lwc), stream)
         if z_all is not None:
             z_all[r0:r0 + nr, k0:k0 + nk] = zbuf[:rows * D].view(nr, nk, D)
         if lw_all is not None:
@@ -247,6 +346,7 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
 
 def _proposal(model, image, text, posterior):
     """(mu, logvar) of the eval-mode encoders + ProductOfExperts over the posterior's modalities (no decoder runs)."""
+    image = image.reshape(image.shape[0], *_family(model).image_shape)
     if posterior == "joint":
         im_mu, im_lv = model.image_encoder(image)
         tx_mu, tx_lv = model.text_encoder(text)
@@ -267,8 +367,8 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
     """Dataset means of the importance-sampled log p^(x), log p^(y), log p^(x, y) (``iw_estimate``) with the proposal of
     one posterior ("joint": q(z|x,y), "image": q(z|x), "text": q(z|y)), and of the two reconstruction NLLs.
 
-    The model runs in eval mode (BatchNorm running statistics, no dropout); per batch only the encoders and the experts run
-    to form the proposal, then the particle chunks.  Nothing is read back to the host until the end.  Unlike the reference's
+    ``model``: a multimnist or a mnist ``MultimodalVAE`` (``iw_estimate``).  It runs in eval mode (BatchNorm running
+    statistics, no dropout); per batch only the encoders and the experts run to form the proposal, then the particle chunks.  Nothing is read back to the host until the end.  Unlike the reference's
     multimnist/loglikelihood.py, the bounds weight each particle by p(z)/q(z) and take the log-sum-exp (see ``iw_estimate``);
     ``image_nll`` / ``text_nll`` are the reference's quantity (mean over particles of the summed reconstruction NLL), without
     its -100 clamp.
@@ -282,7 +382,7 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
     dev = next(model.parameters()).device
     logp, ess, nll, n_seen = [], [], [], 0
     for image, text in loader:
-        image = image.to(dev).float().reshape(-1, 1, 50, 50)
+        image = image.to(dev).float().reshape(-1, *_family(model).image_shape)
         text = text.to(dev).long()
         mu, logvar = _proposal(model, image, text, posterior)
         r = iw_estimate(model, image, text, mu, logvar, n_particles, seed=seed, first_row=n_seen)
@@ -348,6 +448,8 @@ def _parser():
     # multimnist/loglikelihood.py's flags and defaults, plus the importance-sampled bounds (log_marginal / marginal_table)
     pl = sub.add_parser("loglik", help="multimnist/loglikelihood.py + importance-sampled log p(x), log p(y)")
     pl.add_argument('model_path', type=str, help='path to trained model file')
+    pl.add_argument('--dataset', type=str, default='multimnist', choices=('multimnist', 'mnist'),
+                    help='model family of the checkpoint (mnist: --data names a .pt file of (uint8 images (N,28,28), int64 labels (N,)))')
     mode = pl.add_mutually_exclusive_group()
     mode.add_argument('--image_only', action='store_true', default=False,
                       help='compute NLL of test data using reconstructions from image only')
@@ -368,14 +470,23 @@ def _parser():
 def _loglik_main(args):
     import json
     from . import data as D
-    from .train import load_checkpoint
     from .utils import charlist_tensor
-    if args.synthetic > 0:
-        x, labels = D.synthetic_multimnist(args.synthetic, seed=args.seed)
-        t = torch.stack([charlist_tensor(l) for l in labels])
+    if args.dataset == "mnist":
+        from .mnist import load_checkpoint
+        if args.synthetic > 0:
+            x, t = D.synthetic_mnist(args.synthetic, seed=args.seed)
+        else:
+            x, t = torch.load(args.data, weights_only=False)      # torchvision's processed/test.pt
+        x = x.float().div_(255.0).view(-1, 784)                   # transforms.ToTensor() + view(-1, 784)
+        t = t.long()
     else:
-        x, t = D.load_multimnist(args.data, train=False)
-    x = x.float().div_(255.0).view(-1, 1, 50, 50)                 # transforms.ToTensor()
+        from .train import load_checkpoint
+        if args.synthetic > 0:
+            x, labels = D.synthetic_multimnist(args.synthetic, seed=args.seed)
+            t = torch.stack([charlist_tensor(l) for l in labels])
+        else:
+            x, t = D.load_multimnist(args.data, train=False)
+        x = x.float().div_(255.0).view(-1, 1, 50, 50)             # transforms.ToTensor()
     loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
     vae = load_checkpoint(args.model_path, use_cuda=True)
     posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)

@@ -211,6 +211,17 @@ def loss_function(mu, logvar, recon_image=None, image=None, recon_text=None, tex
 elbo_loss = loss_function
 
 
+def load_checkpoint(file_path, use_cuda=False):
+    """mnist/train.py:44-60: rebuilds a MultimodalVAE from the checkpoint dict (``state_dict``, ``n_latents``) of either code base."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    n_latents = checkpoint['n_latents'] if 'n_latents' in checkpoint else 20
+    vae = MultimodalVAE(n_latents=n_latents)
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
+
+
 class FusedTrainer:
     """``FusedTrainer(vae, batch_size, lr)(image, label)`` == zero_grad + 3 passes + 3 losses + backward + Adam step
     (mnist/train.py:131-147,149) on ``vae``'s own parameters."""

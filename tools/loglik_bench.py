@@ -1,6 +1,10 @@
 """Rate of the importance-sampled evaluation (evaluate.iw_estimate / marginal_table) against a compute_nll-style loop.
 
-    python tools/loglik_bench.py [--batch 64] [--particles 1000] [--loop_particles 100] [--batches 4] [--table_examples 10000]
+    python tools/loglik_bench.py [--dataset multimnist|mnist] [--batch 64] [--particles 1000] [--loop_particles 100] [--batches 4]
+                                 [--table_examples 10000]
+
+--dataset mnist (``main_mnist``): the fused fp32 scorer mmvae_mnist_iw_score against an unfused batched chain of the drop-in
+decoder modules + torch ops, see there.  The rest of this text is the MultiMNIST mode.
 
 Prints, at batch B:
   * particles/s of iw_estimate at K = --particles (whole batches, device-synchronised wall clock after a warm-up batch);
@@ -24,8 +28,156 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def main_mnist(args):
+    """MNIST: particles/s of
+      * ``iw_estimate`` on the fused scorer (mmvae_iw_particles -> mmvae_mnist_iw_score -> mmvae_iw_accumulate -> finalize);
+      * the same pipeline with the scoring call replaced by the unfused batched chain a user could write without it: the image- and
+        text-decoder module forwards called once on all rows of the chunk, then torch ops on what they return
+        (-binary_cross_entropy(p, x) per element = x log p + (1 - x) log(1 - p) in ONE elementwise kernel, summed per row; the
+        log-probabilities go to mmvae_iw_accumulate as they are).  Same particles, same chunks, same accumulator;
+      * the two scoring steps alone on one chunk of particles (device events), and the TFLOP/s of the decoder's
+        2 (D 200 + 200 400 + 400 784 + D 10 + 10 10) FLOP per particle over the fused kernel's time;
+      * the per-particle loop of ``compute_nll_mnist``;
+      * the wall time of ``marginal_table`` on --table_examples synthetic examples.
+    The two iw pipelines alternate ``--repeats`` times after a warm-up of both; their log p^ are compared on the first batch."""
+    import ctypes as C
+    import torch.nn.functional as F
+    from multimodal_vae_amd import mnist as M, data as Dd
+    from multimodal_vae_amd._lib import call, ptr
+    from multimodal_vae_amd.evaluate import (iw_estimate, marginal_table, compute_nll_mnist, _proposal, iw_chunks, IW_ROWS_MNIST)
+    from oracle import mmvae_ref as R
+    dev = torch.device("cuda:0")
+    D, B, K = 20, args.batch, args.particles
+    vae = M.MultimodalVAE(D)
+    vae.load_state_dict(R.formula_params("mnist", D), strict=True)
+    vae.cuda().eval()
+    st = vae._core.sync(dev)
+    n = max(args.table_examples, B * (args.batches + 1))
+    x, t = Dd.synthetic_mnist(n, seed=0)
+    x = x.float().div_(255.0).view(-1, 784)
+    batches = [(x[i:i + B].to(dev), t[i:i + B].to(dev)) for i in range(0, B * (args.batches + 1), B)]
+    f32 = dict(dtype=torch.float32, device=dev)
+    flops_particle = 2.0 * (D * 200 + 200 * 400 + 400 * 784 + D * 10 + 10 * 10)
+
+    def stream():
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def unfused_score(z, image, nr, nk):
+        """log p(x|z) (nr*nk,) and the log-probabilities (nr*nk, 10) from the decoder modules + torch ops."""
+        p = vae.decode_image(z)
+        words = vae.decode_text(z)
+        lx = -F.binary_cross_entropy(p.view(nr, nk, 784), image.unsqueeze(1).expand(nr, nk, 784), reduction="none").sum(2)
+        return lx.reshape(-1).contiguous(), words.contiguous()
+
+    def run_unfused(i):
+        image, label = batches[i]
+        mu, lv = props[i]
+        state = torch.empty(B, 3, 4, **f32)
+        call("mmvae_iw_init", ptr(state), B, stream())
+        for r0, nr, k0, nk in iw_chunks(B, K, IW_ROWS_MNIST):
+            rows = nr * nk
+            z, lr = torch.empty(rows, D, **f32), torch.empty(rows, **f32)
+            call("mmvae_iw_particles", ptr(mu[r0:]), ptr(lv[r0:]), nr, D, nk, i * B + r0, k0, 0, None, ptr(z), ptr(lr), stream())
+            lx, words = unfused_score(z, image[r0:r0 + nr], nr, nk)
+            call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(label[r0:]), 1, 10, ptr(lr), nr, nk, ptr(state[r0:]), None, stream())
+        out = torch.empty(B, 8, **f32)
+        call("mmvae_iw_finalize", ptr(state), B, K, ptr(out), stream())
+        return out[:, 0:3]
+
+    def run_fused(i):
+        return iw_estimate(vae, batches[i][0], batches[i][1], props[i][0], props[i][1], K, first_row=i * B)["log_p"]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(1, len(batches)):
+            fn(i)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    with torch.no_grad():
+        props = [_proposal(vae, im, lb, "joint") for im, lb in batches]
+        a, b = run_fused(0), run_unfused(0)                     # warm-up of both, and the same numbers from both
+        torch.cuda.synchronize()
+        diff = (a.double() - b.double()).abs().max(0).values.tolist()
+        tf, tu = [], []
+        for _ in range(args.repeats):
+            tf.append(timed(run_fused))
+            tu.append(timed(run_unfused))
+    per = B * K * args.batches
+    rate_f, rate_u = per / min(tf), per / min(tu)
+    print("loglik_bench --dataset mnist: B = %d, K = %d, n_latents = %d, rows per scoring call <= %d, %d batches per timing" %
+          (B, K, D, IW_ROWS_MNIST, args.batches))
+    print("fused   vs unfused log p^ (x, y, xy) of batch 0: max abs difference %s" % " / ".join("%.2e" % v for v in diff))
+    print("iw_estimate, fused scorer     %12.0f particles/s  (best of %s s)" % (rate_f, ", ".join("%.4f" % v for v in tf)))
+    print("same pipeline, unfused chain  %12.0f particles/s  (best of %s s)" % (rate_u, ", ".join("%.4f" % v for v in tu)))
+    print("ratio fused / unfused         %.2fx  %s" % (rate_f / rate_u, "" if rate_f >= rate_u else "(THE FUSED SCORER IS SLOWER)"))
+    sys.stdout.flush()
+
+    # ---- the scoring step alone on one chunk (device events, 10 calls each after a warm-up call)
+    with torch.no_grad():
+        r0, nr, k0, nk = iw_chunks(B, K, IW_ROWS_MNIST)[0]
+        rows = nr * nk
+        image = batches[1][0][r0:r0 + nr].contiguous()
+        z, lr = torch.empty(rows, D, **f32), torch.empty(rows, **f32)
+        call("mmvae_iw_particles", ptr(props[1][0]), ptr(props[1][1]), nr, D, nk, 0, 0, 0, None, ptr(z), ptr(lr), stream())
+        lx, words = torch.empty(rows, **f32), torch.empty(rows, 10, **f32)
+
+        def fused_score():
+            call("mmvae_mnist_iw_score", st.plan(1), ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream())
+
+        def ev_time(fn, reps=10):
+            fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) * 1e-3 / reps
+        t_fs = ev_time(fused_score)
+        t_us = ev_time(lambda: unfused_score(z, image, nr, nk))
+    print("scoring step alone, %d rows:  fused kernel %.3f ms (%.1f TFLOP/s of %.3f MFLOP per particle, fp32 MFMA)   "
+          "unfused chain %.3f ms   ratio %.2fx" % (rows, t_fs * 1e3, flops_particle * rows / t_fs / 1e12, flops_particle / 1e6,
+                                                    t_us * 1e3, t_us / t_fs))
+    print("achieved in iw_estimate       %.1f TFLOP/s (decoder count over the iw_estimate wall time)" % (flops_particle * rate_f / 1e12))
+    sys.stdout.flush()
+
+    # ---- the compute_nll_mnist loop (one decoder module call pair per particle index, host sums), batch 0 is the warm-up
+    Kl = args.loop_particles
+    cpu_batches = [(im.cpu(), lb.cpu()) for im, lb in batches]
+    compute_nll_mnist(vae, cpu_batches[:1], n_samples=Kl, use_cuda=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    compute_nll_mnist(vae, cpu_batches[1:], n_samples=Kl, use_cuda=True)
+    torch.cuda.synchronize()
+    t_loop = time.perf_counter() - t0
+    rate_loop = B * Kl * args.batches / t_loop
+    print("compute_nll_mnist loop  K = %4d  %d batches  %.3f s  %12.0f particles/s   (fused iw_estimate: %.0fx)" %
+          (Kl, args.batches, t_loop, rate_loop, rate_f / rate_loop))
+    sys.stdout.flush()
+
+    # ---- marginal_table on table_examples synthetic examples
+    N = args.table_examples
+    loader = [(x[i:i + B], t[i:i + B]) for i in range(0, N, B)]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    table = marginal_table(vae, loader, n_particles=K, seed=0)
+    torch.cuda.synchronize()
+    t_table = time.perf_counter() - t0
+    print("marginal_table     N = %d  K = %d  3 posteriors  %.2f s  (%.0f particles/s, %.1f TFLOP/s of the decoder count)" %
+          (N, K, t_table, 3.0 * N * K / t_table, flops_particle * 3.0 * N * K / t_table / 1e12))
+    for post, r in table.items():
+        print("  %-5s log p(x) >= %.3f  log p(y) >= %.3f  log p(x,y) >= %.3f  image NLL %.3f  text NLL %.3f  mean ESS %s" %
+              (post, r["log_px"], r["log_py"], r["log_pxy"], r["image_nll"], r["text_nll"],
+               " / ".join("%.2f" % v for v in r["ess"].double().mean(0).tolist())))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dataset", choices=("multimnist", "mnist"), default="multimnist")
+    ap.add_argument("--repeats", type=int, default=3, help="mnist: alternations of the fused and the unfused pipeline")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--particles", type=int, default=1000)
     ap.add_argument("--loop_particles", type=int, default=100)
@@ -34,6 +186,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("loglik_bench: no GPU (the rates are only measured on the device)")
+    if args.dataset == "mnist":
+        return main_mnist(args)
     from multimodal_vae_amd import multimnist as M, data as Dd
     from multimodal_vae_amd._lib import call
     from multimodal_vae_amd.evaluate import iw_estimate, marginal_table, _proposal, iw_chunks, IW_ROWS
