@@ -107,25 +107,6 @@ SIGNATURES = {
     "mmvae_allreduce_grads": (_I, [_P, _P, C.c_size_t, _P]),
     "mmvae_comm_world": (_I, [_P]),
     "mmvae_comm_destroy": (_I, [_P]),
-    "mmvae_mm_create": (_P, [_I, _I]),
-    "mmvae_mm_destroy": (None, [_P]),
-    "mmvae_mm_param_count": (_LL, [_P]),
-    "mmvae_mm_num_params": (_I, [_P]),
-    "mmvae_mm_param_info": (_I, [_P, _I, C.c_char_p, C.POINTER(_I), C.POINTER(_I), C.POINTER(_LL)]),
-    "mmvae_mm_bn_floats": (_LL, [_P]),
-    "mmvae_mm_num_bn": (_I, [_P]),
-    "mmvae_mm_bn_info": (_I, [_P, _I, C.c_char_p, C.POINTER(_I), C.POINTER(_LL)]),
-    "mmvae_mm_packed_elems": (_LL, [_P]),
-    "mmvae_mm_packed_vec_elems": (_LL, [_P]),
-    "mmvae_mm_gpk_elems": (_LL, [_P]),
-    "mmvae_mm_gpk_vec_elems": (_LL, [_P]),
-    "mmvae_mm_desc_bytes": (_SZ, [_P, _I]),
-    "mmvae_mm_desc_copy": (_I, [_P, _I, _P]),
-    "mmvae_mm_workspace_bytes": (_SZ, [_P]),
-    "mmvae_mm_module_workspace_bytes": (_SZ, [_P]),
-    "mmvae_mm_bind": (_I, [_P] * 11),
-    "mmvae_mm_pack_weights": (_I, [_P, _P]),
-    "mmvae_mm_grad_map": (_I, [_P, _P, _P]),
     "mmvae_mm_step": (_I, [_P, C.POINTER(StepIO), _I, _I, _P]),
     "mmvae_mm_wait_early_grads": (_I, [_P, _P]),
     "mmvae_mm_image_encoder_fwd": (_I, [_P, _P, _SZ, _P, _P, _P, _I, _P, _P]),
@@ -211,6 +192,7 @@ def _plan_api(pfx):
     }
 
 
+SIGNATURES.update(_plan_api("mm"))
 SIGNATURES.update(_plan_api("mnist"))
 SIGNATURES["mmvae_mnist_create_p"] = (_P, [_I, _I, _I])
 SIGNATURES["mmvae_mnist_precision"] = (_I, [_P])

@@ -1,4 +1,4 @@
-"""Device-side state of one MultiMNIST MMVAE instance and the fused ELBO-step engine.
+"""Device-side state of one MMVAE instance (MultiMNIST, MNIST, CelebA, COCO) and the fused ELBO-step engines.
 
 PyTorch is used for plumbing only: it owns the device allocations (``torch.empty``), the stream and
 (optionally) the HIP graph; every arithmetic operation of the hot path runs in libmmvae_hip.so.

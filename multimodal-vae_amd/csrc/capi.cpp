@@ -11,20 +11,24 @@
 
 const char* mmvae_error_string();
 
-#define API_GUARD_BEGIN try {
-#define API_GUARD_END                                                   \
-    } catch (const std::exception& e) {                                 \
-        mmvae_set_error("internal exception: %s", e.what());            \
-        return MMVAE_ESTATE;                                            \
-    } catch (...) {                                                     \
-        mmvae_set_error("internal exception");                          \
-        return MMVAE_ESTATE;                                            \
+// Runs `f` and maps an exception that escapes it to mmvae_set_error + MMVAE_ESTATE.
+template <class F>
+static int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const std::exception& e) {
+        mmvae_set_error("internal exception: %s", e.what());
+        return MMVAE_ESTATE;
+    } catch (...) {
+        mmvae_set_error("internal exception");
+        return MMVAE_ESTATE;
     }
+}
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 
-// ---- generic plan queries / bind / pack for the models built on PlanBase alone (mnist, celeba)
+// ---- generic plan queries / bind / pack: every model family gets them from MMVAE_PLAN_API over its PlanBase
 static long long pb_bn_floats(const PlanBase* b) { return b->bn_list.empty() ? 0 : b->bn_list.back().stat_off + 2 * b->bn_list.back().C; }
 static int pb_param_info(const PlanBase* b, int i, char* name, int* ndim, int* shape, long long* offset) {
     const auto& v = b->params;
@@ -89,20 +93,17 @@ static int pb_grad_map(PlanBase* P, int* map, hipStream_t s) {
     }                                                                                                                     \
     int mmvae_##pfx##_bind(T* p, float* params, float* grads, float* bn_stats, long long* nbt, void* packed,              \
                            float* packed_vec, float* gpk, float* gpk_vec, void* desc_dev, void* gdesc_dev) {              \
-        API_GUARD_BEGIN                                                                                                   \
-        return pb_bind(BASE(p), params, grads, bn_stats, nbt, packed, packed_vec, gpk, gpk_vec, desc_dev, gdesc_dev);     \
-        API_GUARD_END                                                                                                     \
+        return guarded([&] {                                                                                              \
+            return pb_bind(BASE(p), params, grads, bn_stats, nbt, packed, packed_vec, gpk, gpk_vec, desc_dev, gdesc_dev); \
+        });                                                                                                               \
     }                                                                                                                     \
     int mmvae_##pfx##_pack_weights(T* p, void* stream) {                                                                  \
-        API_GUARD_BEGIN                                                                                                   \
-        return pb_pack(BASE(p), S(stream));                                                                               \
-        API_GUARD_END                                                                                                     \
+        return guarded([&] { return pb_pack(BASE(p), S(stream)); });                                                      \
     }                                                                                                                     \
     int mmvae_##pfx##_grad_map(T* p, int* map, void* stream) {                                                            \
-        API_GUARD_BEGIN                                                                                                   \
-        return pb_grad_map(BASE(p), map, S(stream));                                                                      \
-        API_GUARD_END                                                                                                     \
+        return guarded([&] { return pb_grad_map(BASE(p), map, S(stream)); });                                             \
     }
+static inline PlanBase* mm_b(const mmvae_mm_t* p) { return mm_base(const_cast<mmvae_mm_t*>(p)); }
 static inline PlanBase* mnist_b(const mmvae_mnist_t* p) { return mnist_base(const_cast<mmvae_mnist_t*>(p)); }
 static inline PlanBase* celeba_b(const mmvae_celeba_t* p) { return celeba_base(const_cast<mmvae_celeba_t*>(p)); }
 static inline PlanBase* coco_b(const mmvae_coco_t* p) { return coco_base(const_cast<mmvae_coco_t*>(p)); }
@@ -113,159 +114,66 @@ const char* mmvae_last_error(void) { return mmvae_error_string(); }
 const char* mmvae_version(void) { return "mmvae-hip 0.1 (gfx950)"; }
 
 int mmvae_init(int device) {
-    API_GUARD_BEGIN
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { mmvae_set_error("no HIP device visible"); return MMVAE_EHIP; }
-    MMVAE_REQUIRE(device >= 0 && device < n, "device %d out of range (%d visible)", device, n);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { mmvae_set_error("hipGetDeviceProperties failed"); return MMVAE_EHIP; }
-    MMVAE_REQUIRE(strncmp(prop.gcnArchName, "gfx950", 6) == 0, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-    if (hipSetDevice(device) != hipSuccess) { mmvae_set_error("hipSetDevice failed"); return MMVAE_EHIP; }
-    return MMVAE_OK;
-    API_GUARD_END
+    return guarded([&]() -> int {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { mmvae_set_error("no HIP device visible"); return MMVAE_EHIP; }
+        MMVAE_REQUIRE(device >= 0 && device < n, "device %d out of range (%d visible)", device, n);
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) != hipSuccess) { mmvae_set_error("hipGetDeviceProperties failed"); return MMVAE_EHIP; }
+        MMVAE_REQUIRE(strncmp(prop.gcnArchName, "gfx950", 6) == 0, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+        if (hipSetDevice(device) != hipSuccess) { mmvae_set_error("hipSetDevice failed"); return MMVAE_EHIP; }
+        return MMVAE_OK;
+    });
 }
 
 mmvae_mm_t* mmvae_mm_create(int n_latents, int batch) {
     try { return mm_create(n_latents, batch); } catch (...) { mmvae_set_error("mm_create failed"); return nullptr; }
 }
 void mmvae_mm_destroy(mmvae_mm_t* p) { mm_destroy(p); }
-long long mmvae_mm_param_count(const mmvae_mm_t* p) { return mm_param_count(p); }
-int mmvae_mm_num_params(const mmvae_mm_t* p) { return (int)mm_params(p).size(); }
-int mmvae_mm_param_info(const mmvae_mm_t* p, int i, char* name, int* ndim, int* shape, long long* offset) {
-    const auto& v = mm_params(p);
-    MMVAE_REQUIRE(i >= 0 && i < (int)v.size(), "param index %d out of range", i);
-    strncpy(name, v[i].name.c_str(), 127); name[127] = 0;
-    *ndim = v[i].ndim;
-    for (int k = 0; k < 4; ++k) shape[k] = k < v[i].ndim ? v[i].shape[k] : 1;
-    *offset = v[i].offset;
-    return MMVAE_OK;
-}
-long long mmvae_mm_bn_floats(const mmvae_mm_t* p) { return mm_bn_floats(p); }
-int mmvae_mm_num_bn(const mmvae_mm_t* p) { return mm_num_bn(p); }
-int mmvae_mm_bn_info(const mmvae_mm_t* p, int i, char* prefix, int* channels, long long* offset) {
-    std::string s; int c; long long o;
-    MMVAE_TRY(mm_bn_info(p, i, s, c, o));
-    strncpy(prefix, s.c_str(), 127); prefix[127] = 0; *channels = c; *offset = o;
-    return MMVAE_OK;
-}
-long long mmvae_mm_packed_elems(const mmvae_mm_t* p) { return mm_packed_elems(p); }
-long long mmvae_mm_packed_vec_elems(const mmvae_mm_t* p) { return mm_packed_vec_elems(p); }
-long long mmvae_mm_gpk_elems(const mmvae_mm_t* p) { return mm_gpk_elems(p); }
-long long mmvae_mm_gpk_vec_elems(const mmvae_mm_t* p) { return mm_gpk_vec_elems(p); }
-size_t mmvae_mm_desc_bytes(const mmvae_mm_t* p, int which) {
-    return sizeof(PackDesc) * (size_t)(which == 0 ? mm_ndesc(p) : mm_ngdesc(p));
-}
-int mmvae_mm_desc_copy(const mmvae_mm_t* p, int which, void* host_out) {
-    memcpy(host_out, which == 0 ? mm_desc_host(p) : mm_gdesc_host(p), mmvae_mm_desc_bytes(p, which));
-    return MMVAE_OK;
-}
-size_t mmvae_mm_workspace_bytes(const mmvae_mm_t* p) { return mm_workspace_bytes(p); }
-size_t mmvae_mm_module_workspace_bytes(const mmvae_mm_t* p) { return mm_module_workspace_bytes(p); }
-int mmvae_mm_bind(mmvae_mm_t* p, float* params, float* grads, float* bn_stats, long long* nbt, void* packed, float* packed_vec,
-                  float* gpk, float* gpk_vec, void* desc_dev, void* gdesc_dev) {
-    API_GUARD_BEGIN
-    MMBuffers b;
-    b.params = params; b.grads = grads; b.bn_stats = bn_stats; b.bn_nbt = nbt; b.packed = (bf16*)packed; b.packed_vec = packed_vec;
-    b.gpk = gpk; b.gpk_vec = gpk_vec; b.desc_dev = (PackDesc*)desc_dev; b.gdesc_dev = (PackDesc*)gdesc_dev;
-    return mm_bind(p, b);
-    API_GUARD_END
-}
-int mmvae_mm_grad_map(mmvae_mm_t* p, int* map, void* stream) {
-    API_GUARD_BEGIN
-    MMVAE_REQUIRE(p && map, "mmvae_mm_grad_map: null argument");
-    return mm_grad_map(p, map, S(stream));
-    API_GUARD_END
-}
-int mmvae_mm_pack_weights(mmvae_mm_t* p, void* stream) {
-    API_GUARD_BEGIN
-    return mm_pack_weights(p, S(stream));
-    API_GUARD_END
-}
+MMVAE_PLAN_API(mm, mmvae_mm_t, mm_b)
 int mmvae_mm_wait_early_grads(mmvae_mm_t* p, void* stream) {
-    API_GUARD_BEGIN
-    return mm_wait_early_grads(p, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_wait_early_grads(p, S(stream)); });
 }
 int mmvae_mm_step(mmvae_mm_t* p, const mmvae_mm_step_io* io, int training, int do_backward, void* stream) {
-    API_GUARD_BEGIN
-    MMVAE_REQUIRE(p && io, "mmvae_mm_step: null argument");
-    MMStepIO s;
-    s.ws = io->ws; s.ws_bytes = io->ws_bytes; s.step_ctr = io->step_counter; s.image = io->image; s.text = io->text; s.eps = io->eps;
-    s.enc_mask1 = io->enc_mask1; s.enc_mask2 = io->enc_mask2; s.gru_keep = io->gru_keep;
-    s.enc_dropout = io->enc_dropout; s.gru_dropout = io->gru_dropout; s.force_tokens = io->force_tokens;
-    s.kl_lambda = io->kl_lambda;
-    for (int k = 0; k < 3; ++k) { s.lambda_xy[k] = io->lambda_xy[k]; s.lambda_yx[k] = io->lambda_yx[k]; }
-    s.seed = io->seed; s.sums = io->sums; s.recon_image = io->recon_image; s.recon_text = io->recon_text;
-    s.mu = io->mu; s.logvar = io->logvar; s.tokens = io->tokens;
-    for (int k = 0; k < 3; ++k) s.pass_skip[k] = io->pass_skip[k];
-    s.defer_unpack = io->defer_unpack;
-    s.pack_first = io->pack_first;
-    s.dp_split = io->dp_split;
-    if (io->early_adam) {
-        const mmvae_early_adam& e = *io->early_adam;
-        MMVAE_REQUIRE(e.m && e.v && e.state && e.gmap && e.ran, "mmvae_mm_step: early_adam with a null field");
-        s.early_adam = true;
-        s.ea_m = e.m; s.ea_v = e.v; s.ea_state = e.state; s.ea_lr = e.lr; s.ea_b1 = e.beta1; s.ea_b2 = e.beta2; s.ea_eps = e.eps;
-        s.ea_scale = e.grad_scale; s.ea_gmap = e.gmap; s.ea_ran = e.ran;
-        *e.ran = 0;
-    }
-    return mm_step_fwd_bwd(p, s, training, do_backward, S(stream));
-    API_GUARD_END
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_mm_step: null argument");
+        return mm_step_fwd_bwd(p, *io, training, do_backward, S(stream));
+    });
 }
 int mmvae_mm_image_encoder_fwd(mmvae_mm_t* p, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2,
                                int training, float* out, void* stream) {
-    API_GUARD_BEGIN
-    return mm_image_encoder_fwd(p, ws, wsb, image, m1, m2, training, out, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_image_encoder_fwd(p, ws, wsb, image, m1, m2, training, out, S(stream)); });
 }
 int mmvae_mm_image_encoder_bwd(mmvae_mm_t* p, void* ws, size_t wsb, const float* d_out, const uint8_t* m1, const uint8_t* m2, void* stream) {
-    API_GUARD_BEGIN
-    return mm_image_encoder_bwd(p, ws, wsb, d_out, m1, m2, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_image_encoder_bwd(p, ws, wsb, d_out, m1, m2, S(stream)); });
 }
 int mmvae_mm_image_decoder_fwd(mmvae_mm_t* p, void* ws, size_t wsb, const float* z, int training, float* recon, void* stream) {
-    API_GUARD_BEGIN
-    return mm_image_decoder_fwd(p, ws, wsb, z, training, recon, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_image_decoder_fwd(p, ws, wsb, z, training, recon, S(stream)); });
 }
 int mmvae_mm_image_decoder_bwd(mmvae_mm_t* p, void* ws, size_t wsb, const float* d_recon, const float* recon, float* dz, void* stream) {
-    API_GUARD_BEGIN
-    return mm_image_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_image_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(stream)); });
 }
 int mmvae_mm_text_encoder_fwd(mmvae_mm_t* p, void* ws, size_t wsb, const long long* text, float* out, void* stream) {
-    API_GUARD_BEGIN
-    return mm_text_encoder_fwd(p, ws, wsb, text, out, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_text_encoder_fwd(p, ws, wsb, text, out, S(stream)); });
 }
 int mmvae_mm_text_encoder_bwd(mmvae_mm_t* p, void* ws, size_t wsb, const long long* text, const float* d_out, void* stream) {
-    API_GUARD_BEGIN
-    return mm_text_encoder_bwd(p, ws, wsb, text, d_out, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_text_encoder_bwd(p, ws, wsb, text, d_out, S(stream)); });
 }
 int mmvae_mm_text_decoder_fwd(mmvae_mm_t* p, void* ws, size_t wsb, const float* z, int training, const uint8_t* keep,
                               const long long* force_tokens, float* words, long long* tokens, void* stream) {
-    API_GUARD_BEGIN
-    return mm_text_decoder_fwd(p, ws, wsb, z, training, keep, force_tokens, words, tokens, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_text_decoder_fwd(p, ws, wsb, z, training, keep, force_tokens, words, tokens, S(stream)); });
 }
 int mmvae_mm_text_decoder_bwd(mmvae_mm_t* p, void* ws, size_t wsb, const float* z, const uint8_t* keep, const long long* force_tokens,
                               const float* words, const long long* tokens, const float* d_words, float* dz, void* stream) {
-    API_GUARD_BEGIN
-    return mm_text_decoder_bwd(p, ws, wsb, z, keep, force_tokens, words, tokens, d_words, dz, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_text_decoder_bwd(p, ws, wsb, z, keep, force_tokens, words, tokens, d_words, dz, S(stream)); });
 }
-size_t mmvae_mm_iw_workspace_bytes(const mmvae_mm_t* p) { return mm_module_workspace_bytes(p); }
+size_t mmvae_mm_iw_workspace_bytes(const mmvae_mm_t* p) { return mm_b(p)->ws_bytes_module; }
 int mmvae_mm_iw_score(mmvae_mm_t* p, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x,
                       float* words, void* stream) {
-    API_GUARD_BEGIN
-    return mm_iw_score(p, ws, wsb, z, image, B, K, loglik_x, words, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_iw_score(p, ws, wsb, z, image, B, K, loglik_x, words, S(stream)); });
 }
 int mmvae_mm_bench_layer(mmvae_mm_t* p, void* ws, size_t wsb, const char* layer, int iters, void* stream) {
-    API_GUARD_BEGIN
-    return mm_bench_layer(p, ws, wsb, layer, iters, S(stream));
-    API_GUARD_END
+    return guarded([&] { return mm_bench_layer(p, ws, wsb, layer, iters, S(stream)); });
 }
 double mmvae_mm_layer_flops(const mmvae_mm_t* p, const char* layer) { return mm_layer_flops(p, layer); }
 double mmvae_mm_layer_algo_flops(const mmvae_mm_t* p, const char* layer) { return mm_layer_algo_flops(p, layer); }
@@ -283,52 +191,38 @@ int mmvae_mnist_precision(const mmvae_mnist_t* p) { return mnist_is_f32(p) ? 0 :
 void mmvae_mnist_destroy(mmvae_mnist_t* p) { mnist_destroy(p); }
 MMVAE_PLAN_API(mnist, mmvae_mnist_t, mnist_b)
 int mmvae_mnist_step(mmvae_mnist_t* p, const mmvae_mnist_step_io* io, int training, int do_backward, void* stream) {
-    API_GUARD_BEGIN
-    MMVAE_REQUIRE(p && io, "mmvae_mnist_step: null argument");
-    MnistStepIO s;
-    s.ws = io->ws; s.ws_bytes = io->ws_bytes; s.step_ctr = io->step_counter; s.image = io->image; s.label = io->label; s.eps = io->eps;
-    for (int k = 0; k < 3; ++k) { s.lambda_xy[k] = io->lambda_xy[k]; s.lambda_yx[k] = io->lambda_yx[k]; }
-    s.kl_coef = io->kl_coef; s.seed = io->seed; s.sums = io->sums; s.recon_image = io->recon_image; s.recon_text = io->recon_text;
-    s.mu = io->mu; s.logvar = io->logvar;
-    for (int k = 0; k < 3; ++k) s.pass_skip[k] = io->pass_skip[k];
-    return mnist_step(p, s, training, do_backward, S(stream));
-    API_GUARD_END
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_mnist_step: null argument");
+        return mnist_step(p, *io, training, do_backward, S(stream));
+    });
 }
 
-#define MNIST_FWD(name, in_t)                                                                                             \
-    int mmvae_mnist_##name##_fwd(mmvae_mnist_t* p, void* ws, size_t wsb, const in_t* in, int training, float* out, void* st) { \
-        API_GUARD_BEGIN                                                                                                   \
-        return mnist_##name##_fwd(p, ws, wsb, in, training, out, S(st));                                                  \
-        API_GUARD_END                                                                                                     \
-    }
-MNIST_FWD(image_encoder, float)
-MNIST_FWD(image_decoder, float)
-MNIST_FWD(text_encoder, long long)
-MNIST_FWD(text_decoder, float)
+int mmvae_mnist_image_encoder_fwd(mmvae_mnist_t* p, void* ws, size_t wsb, const float* in, int training, float* out, void* st) {
+    return guarded([&] { return mnist_image_encoder_fwd(p, ws, wsb, in, training, out, S(st)); });
+}
+int mmvae_mnist_image_decoder_fwd(mmvae_mnist_t* p, void* ws, size_t wsb, const float* in, int training, float* out, void* st) {
+    return guarded([&] { return mnist_image_decoder_fwd(p, ws, wsb, in, training, out, S(st)); });
+}
+int mmvae_mnist_text_encoder_fwd(mmvae_mnist_t* p, void* ws, size_t wsb, const long long* in, int training, float* out, void* st) {
+    return guarded([&] { return mnist_text_encoder_fwd(p, ws, wsb, in, training, out, S(st)); });
+}
+int mmvae_mnist_text_decoder_fwd(mmvae_mnist_t* p, void* ws, size_t wsb, const float* in, int training, float* out, void* st) {
+    return guarded([&] { return mnist_text_decoder_fwd(p, ws, wsb, in, training, out, S(st)); });
+}
 int mmvae_mnist_image_encoder_bwd(mmvae_mnist_t* p, void* ws, size_t wsb, const float* d_out, void* st) {
-    API_GUARD_BEGIN
-    return mnist_image_encoder_bwd(p, ws, wsb, d_out, S(st));
-    API_GUARD_END
+    return guarded([&] { return mnist_image_encoder_bwd(p, ws, wsb, d_out, S(st)); });
 }
 int mmvae_mnist_image_decoder_bwd(mmvae_mnist_t* p, void* ws, size_t wsb, const float* d_recon, const float* recon, float* dz, void* st) {
-    API_GUARD_BEGIN
-    return mnist_image_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st));
-    API_GUARD_END
+    return guarded([&] { return mnist_image_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st)); });
 }
 int mmvae_mnist_text_encoder_bwd(mmvae_mnist_t* p, void* ws, size_t wsb, const long long* label, const float* d_out, void* st) {
-    API_GUARD_BEGIN
-    return mnist_text_encoder_bwd(p, ws, wsb, label, d_out, S(st));
-    API_GUARD_END
+    return guarded([&] { return mnist_text_encoder_bwd(p, ws, wsb, label, d_out, S(st)); });
 }
 int mmvae_mnist_text_decoder_bwd(mmvae_mnist_t* p, void* ws, size_t wsb, const float* d_logp, const float* logp, float* dz, void* st) {
-    API_GUARD_BEGIN
-    return mnist_text_decoder_bwd(p, ws, wsb, d_logp, logp, dz, S(st));
-    API_GUARD_END
+    return guarded([&] { return mnist_text_decoder_bwd(p, ws, wsb, d_logp, logp, dz, S(st)); });
 }
 int mmvae_mnist_iw_score(mmvae_mnist_t* p, const float* z, const float* image, int B, int K, float* loglik_x, float* words, void* st) {
-    API_GUARD_BEGIN
-    return mnist_iw_score(p, z, image, B, K, loglik_x, words, S(st));
-    API_GUARD_END
+    return guarded([&] { return mnist_iw_score(p, z, image, B, K, loglik_x, words, S(st)); });
 }
 
 // ---- CelebA (celeba/model.py, celeba/train.py)
@@ -338,58 +232,34 @@ mmvae_celeba_t* mmvae_celeba_create(int n_latents, int batch) {
 void mmvae_celeba_destroy(mmvae_celeba_t* p) { celeba_destroy(p); }
 MMVAE_PLAN_API(celeba, mmvae_celeba_t, celeba_b)
 int mmvae_celeba_step(mmvae_celeba_t* p, const mmvae_celeba_step_io* io, int training, int do_backward, void* stream) {
-    API_GUARD_BEGIN
-    MMVAE_REQUIRE(p && io, "mmvae_celeba_step: null argument");
-    CelebaStepIO s;
-    s.ws = io->ws; s.ws_bytes = io->ws_bytes; s.step_ctr = io->step_counter; s.image = io->image; s.attrs = io->attrs; s.eps = io->eps;
-    s.enc_mask = io->enc_mask; s.enc_dropout = io->enc_dropout; s.kl_lambda = io->kl_lambda;
-    for (int k = 0; k < 3; ++k) { s.lambda_x[k] = io->lambda_x[k]; s.lambda_y[k] = io->lambda_y[k]; }
-    s.seed = io->seed; s.sums = io->sums; s.recon_image = io->recon_image; s.recon_attrs = io->recon_attrs;
-    s.mu = io->mu; s.logvar = io->logvar;
-    for (int k = 0; k < 3; ++k) s.pass_skip[k] = io->pass_skip[k];
-    s.defer_unpack = io->defer_unpack;
-    return celeba_step(p, s, training, do_backward, S(stream));
-    API_GUARD_END
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_celeba_step: null argument");
+        return celeba_step(p, *io, training, do_backward, S(stream));
+    });
 }
 int mmvae_celeba_image_encoder_fwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* image, const uint8_t* mask, int training, float* out, void* st) {
-    API_GUARD_BEGIN
-    return celeba_image_encoder_fwd(p, ws, wsb, image, mask, training, out, S(st));
-    API_GUARD_END
+    return guarded([&] { return celeba_image_encoder_fwd(p, ws, wsb, image, mask, training, out, S(st)); });
 }
 int mmvae_celeba_image_encoder_bwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* d_out, const uint8_t* mask, void* st) {
-    API_GUARD_BEGIN
-    return celeba_image_encoder_bwd(p, ws, wsb, d_out, mask, S(st));
-    API_GUARD_END
+    return guarded([&] { return celeba_image_encoder_bwd(p, ws, wsb, d_out, mask, S(st)); });
 }
 int mmvae_celeba_image_decoder_fwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* z, int training, float* recon, void* st) {
-    API_GUARD_BEGIN
-    return celeba_image_decoder_fwd(p, ws, wsb, z, training, recon, S(st));
-    API_GUARD_END
+    return guarded([&] { return celeba_image_decoder_fwd(p, ws, wsb, z, training, recon, S(st)); });
 }
 int mmvae_celeba_image_decoder_bwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* d_recon, const float* recon, float* dz, void* st) {
-    API_GUARD_BEGIN
-    return celeba_image_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st));
-    API_GUARD_END
+    return guarded([&] { return celeba_image_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st)); });
 }
 int mmvae_celeba_attrs_encoder_fwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* attrs, int training, float* out, void* st) {
-    API_GUARD_BEGIN
-    return celeba_attrs_encoder_fwd(p, ws, wsb, attrs, training, out, S(st));
-    API_GUARD_END
+    return guarded([&] { return celeba_attrs_encoder_fwd(p, ws, wsb, attrs, training, out, S(st)); });
 }
 int mmvae_celeba_attrs_encoder_bwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* d_out, void* st) {
-    API_GUARD_BEGIN
-    return celeba_attrs_encoder_bwd(p, ws, wsb, d_out, S(st));
-    API_GUARD_END
+    return guarded([&] { return celeba_attrs_encoder_bwd(p, ws, wsb, d_out, S(st)); });
 }
 int mmvae_celeba_attrs_decoder_fwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* z, int training, float* recon, void* st) {
-    API_GUARD_BEGIN
-    return celeba_attrs_decoder_fwd(p, ws, wsb, z, training, recon, S(st));
-    API_GUARD_END
+    return guarded([&] { return celeba_attrs_decoder_fwd(p, ws, wsb, z, training, recon, S(st)); });
 }
 int mmvae_celeba_attrs_decoder_bwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* d_recon, const float* recon, float* dz, void* st) {
-    API_GUARD_BEGIN
-    return celeba_attrs_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st));
-    API_GUARD_END
+    return guarded([&] { return celeba_attrs_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st)); });
 }
 
 // ---- COCO (coco/model.py, coco/train.py)
@@ -401,59 +271,34 @@ void mmvae_coco_destroy(mmvae_coco_t* p) { coco_destroy(p); }
 int mmvae_coco_steps(const mmvae_coco_t* p) { return p ? coco_steps(p) : 0; }
 MMVAE_PLAN_API(coco, mmvae_coco_t, coco_b)
 int mmvae_coco_step(mmvae_coco_t* p, const mmvae_coco_step_io* io, int training, int do_backward, void* stream) {
-    API_GUARD_BEGIN
-    MMVAE_REQUIRE(p && io, "mmvae_coco_step: null argument");
-    CocoStepIO s;
-    s.ws = io->ws; s.ws_bytes = io->ws_bytes; s.step_ctr = io->step_counter; s.image = io->image; s.text = io->text; s.sos = io->sos;
-    s.eps = io->eps; s.enc_mask1 = io->enc_mask1; s.enc_mask2 = io->enc_mask2; s.gru_keep = io->gru_keep;
-    s.enc_dropout = io->enc_dropout; s.gru_dropout = io->gru_dropout; s.kl_lambda = io->kl_lambda;
-    for (int k = 0; k < 3; ++k) { s.lambda_xy[k] = io->lambda_xy[k]; s.lambda_yx[k] = io->lambda_yx[k]; }
-    s.seed = io->seed; s.sums = io->sums; s.recon_image = io->recon_image; s.recon_text = io->recon_text;
-    s.mu = io->mu; s.logvar = io->logvar;
-    for (int k = 0; k < 3; ++k) s.pass_skip[k] = io->pass_skip[k];
-    s.defer_unpack = io->defer_unpack; s.pack_first = io->pack_first; s.optimizer_state = io->optimizer_state;
-    return coco_step(p, s, training, do_backward, S(stream));
-    API_GUARD_END
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_coco_step: null argument");
+        return coco_step(p, *io, training, do_backward, S(stream));
+    });
 }
 int mmvae_coco_image_encoder_fwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2, int training, float* out, void* st) {
-    API_GUARD_BEGIN
-    return coco_image_encoder_fwd(p, ws, wsb, image, m1, m2, training, out, S(st));
-    API_GUARD_END
+    return guarded([&] { return coco_image_encoder_fwd(p, ws, wsb, image, m1, m2, training, out, S(st)); });
 }
 int mmvae_coco_image_encoder_bwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* d_out, const uint8_t* m1, const uint8_t* m2, void* st) {
-    API_GUARD_BEGIN
-    return coco_image_encoder_bwd(p, ws, wsb, d_out, m1, m2, S(st));
-    API_GUARD_END
+    return guarded([&] { return coco_image_encoder_bwd(p, ws, wsb, d_out, m1, m2, S(st)); });
 }
 int mmvae_coco_image_decoder_fwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, int training, float* recon, void* st) {
-    API_GUARD_BEGIN
-    return coco_image_decoder_fwd(p, ws, wsb, z, training, recon, S(st));
-    API_GUARD_END
+    return guarded([&] { return coco_image_decoder_fwd(p, ws, wsb, z, training, recon, S(st)); });
 }
 int mmvae_coco_image_decoder_bwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* d_recon, const float* recon, float* dz, void* st) {
-    API_GUARD_BEGIN
-    return coco_image_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st));
-    API_GUARD_END
+    return guarded([&] { return coco_image_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st)); });
 }
 int mmvae_coco_text_encoder_fwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* text, float* out, void* st) {
-    API_GUARD_BEGIN
-    return coco_text_encoder_fwd(p, ws, wsb, text, out, S(st));
-    API_GUARD_END
+    return guarded([&] { return coco_text_encoder_fwd(p, ws, wsb, text, out, S(st)); });
 }
 int mmvae_coco_text_encoder_bwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* text, const float* d_out, void* st) {
-    API_GUARD_BEGIN
-    return coco_text_encoder_bwd(p, ws, wsb, text, d_out, S(st));
-    API_GUARD_END
+    return guarded([&] { return coco_text_encoder_bwd(p, ws, wsb, text, d_out, S(st)); });
 }
 int mmvae_coco_text_decoder_fwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, int training, float* sentence, void* st) {
-    API_GUARD_BEGIN
-    return coco_text_decoder_fwd(p, ws, wsb, z, sos, keep, training, sentence, S(st));
-    API_GUARD_END
+    return guarded([&] { return coco_text_decoder_fwd(p, ws, wsb, z, sos, keep, training, sentence, S(st)); });
 }
 int mmvae_coco_text_decoder_bwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, const float* sentence, const float* d_sentence, float* dz, void* st) {
-    API_GUARD_BEGIN
-    return coco_text_decoder_bwd(p, ws, wsb, z, sos, keep, sentence, d_sentence, dz, S(st));
-    API_GUARD_END
+    return guarded([&] { return coco_text_decoder_bwd(p, ws, wsb, z, sos, keep, sentence, d_sentence, dz, S(st)); });
 }
 
 

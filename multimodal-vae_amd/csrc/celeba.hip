@@ -479,25 +479,10 @@ int att_dec_bwd(CelebaPlan& P, const float* dalogit, int groups, float* dz, hipS
 }
 
 int use_ws(CelebaPlan* P, void* ws, size_t bytes, bool module = true) {
-    MMVAE_TRY(check_bound(P));
-    const size_t need = module ? P->ws_bytes_module : P->ws_bytes;
-    MMVAE_REQUIRE(ws != nullptr && bytes >= need, "workspace too small (%zu < %zu)", bytes, need);
-    P->carve_passes = module ? 1 : 3;
-    Workspace w(ws, bytes);
-    carve(*P, w);
+    MMVAE_TRY(plan_use_ws(P, ws, bytes, module, carve));
     P->wgrad_forked = false;
-    P->dec_skip_mask = 0;
-    P->slab.reset(P->w.slab, P->w.slab_floats);
-    // side work or a completion event a FAILED earlier call left behind must not run against this call's buffers
-    P->side_pending.clear(); P->batch_reduce = false;
-    (void)mmvae_take_stop_event();
     return MMVAE_OK;
 }
-int unpack(CelebaPlan& P, hipStream_t s) {
-    MMVAE_TRY(launch_wgrad_reduce(&P.slab, s));      // slab copies nobody summed yet (every side stream has joined s)
-    return launch_unpack_grads(P.buf.gdesc_dev, P.gk.d.data(), (int)P.gk.d.size(), P.buf.gpk, P.buf.gpk_vec, P.buf.grads, s);
-}
-int zero_gpk(CelebaPlan& P, hipStream_t s) { return launch_fill_zero(P.buf.gpk, (size_t)P.gk.mat_elems * sizeof(float), s); }
 
 }  // namespace
 
@@ -506,26 +491,17 @@ CelebaPlan* celeba_create(int D, int B) {
     CelebaPlan* P = new CelebaPlan();
     P->D = D; P->B = B;
     build(*P);
-    Workspace ws(nullptr, 0);
-    carve(*P, ws);
-    P->ws_bytes = ws.used();
-    P->carve_passes = 1;
-    Workspace wm(nullptr, 0);
-    carve(*P, wm);
-    P->ws_bytes_module = wm.used();
-    P->carve_passes = 3;
+    plan_size_workspaces(*P, carve);
     return P;
 }
 void celeba_destroy(CelebaPlan* P) { delete P; }
 PlanBase* celeba_base(CelebaPlan* P) { return P; }
 
-static int celeba_step_body(CelebaPlan* Pp, const CelebaStepIO& io, int training, int do_backward, hipStream_t s);
-int celeba_step(CelebaPlan* Pp, const CelebaStepIO& io, int training, int do_backward, hipStream_t s) {
-    const int rc = celeba_step_body(Pp, io, training, do_backward, s);
-    if (rc != MMVAE_OK && Pp) join_after_error(*Pp, s);
-    return rc;
+static int celeba_step_body(CelebaPlan* Pp, const mmvae_celeba_step_io& io, int training, int do_backward, hipStream_t s);
+int celeba_step(CelebaPlan* Pp, const mmvae_celeba_step_io& io, int training, int do_backward, hipStream_t s) {
+    return plan_step(Pp, io, training, do_backward, s, celeba_step_body);
 }
-static int celeba_step_body(CelebaPlan* Pp, const CelebaStepIO& io, int training, int do_backward, hipStream_t s) {
+static int celeba_step_body(CelebaPlan* Pp, const mmvae_celeba_step_io& io, int training, int do_backward, hipStream_t s) {
     MMVAE_TRY(use_ws(Pp, io.ws, io.ws_bytes, false));
     CelebaPlan& P = *Pp;
     CelebaPlan::W& w = P.w;
@@ -539,7 +515,7 @@ static int celeba_step_body(CelebaPlan* Pp, const CelebaStepIO& io, int training
         sb.zero_ptr[1] = P.buf.gpk; sb.zero_bytes[1] = (size_t)P.gk.mat_elems * sizeof(float);
         sb.zero_ptr[2] = P.buf.grads; sb.zero_bytes[2] = (size_t)(P.nparams / 4) * 16;
     }
-    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_ctr;
+    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_counter;
     if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B3 * D; eps = w.eps; }
     if (training && io.enc_dropout && !m1) { sb.mask[0] = w.m1; sb.n_mask[0] = (long long)2 * B * HID; m1 = w.m1; }
     MMVAE_TRY(launch_step_begin(sb, s));
@@ -618,7 +594,7 @@ static int celeba_step_body(CelebaPlan* Pp, const CelebaStepIO& io, int training
     MMVAE_TRY(join_sides(P, T, s));
     hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, s, w.sums, io.sums);
     MMVAE_TRY(mmvae_check_launch("sum_slots"));
-    return io.defer_unpack ? MMVAE_OK : unpack(P, s);
+    return io.defer_unpack ? MMVAE_OK : plan_unpack(P, s, true);
 }
 
 // ---------------------------------------------------------------- granular module entry points (drop-in modules)
@@ -631,11 +607,11 @@ int celeba_image_encoder_bwd(CelebaPlan* P, void* ws, size_t wsb, const float* d
     MMVAE_TRY(use_ws(P, ws, wsb));
     CelebaPlan::W& w = P->w;
     const int rows = P->B, D2 = 2 * P->D;
-    MMVAE_TRY(zero_gpk(*P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     MMVAE_TRY(launch_cast_bf16(d_out, (long long)rows * D2, w.d_encout, s));
     MMVAE_TRY(launch_colsum_f32(d_out, rows, D2, P->buf.grads + P->fc2.b_off, s));
     MMVAE_TRY(enc_bwd(*P, w.d_encout, 1, mask, mask != nullptr, s));
-    return unpack(*P, s);
+    return plan_unpack(*P, s, true);
 }
 int celeba_image_decoder_fwd(CelebaPlan* P, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
@@ -652,11 +628,11 @@ int celeba_image_decoder_bwd(CelebaPlan* P, void* ws, size_t wsb, const float* d
     MMVAE_TRY(use_ws(P, ws, wsb));
     CelebaPlan::W& w = P->w;
     const long long n = (long long)P->B * NPIX;
-    MMVAE_TRY(zero_gpk(*P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, d_recon, recon, n, w.tmp_f32);
     MMVAE_TRY(mmvae_check_launch("sigmoid_bwd"));
     MMVAE_TRY(dec_bwd(*P, w.tmp_f32, 1, dz, s));
-    return unpack(*P, s);
+    return plan_unpack(*P, s, true);
 }
 int celeba_attrs_encoder_fwd(CelebaPlan* P, void* ws, size_t wsb, const float* attrs, int training, float* out, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
@@ -667,11 +643,11 @@ int celeba_attrs_encoder_bwd(CelebaPlan* P, void* ws, size_t wsb, const float* d
     MMVAE_TRY(use_ws(P, ws, wsb));
     CelebaPlan::W& w = P->w;
     const int rows = P->B, D2 = 2 * P->D;
-    MMVAE_TRY(zero_gpk(*P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     MMVAE_TRY(launch_cast_bf16(d_out, (long long)rows * D2, w.d_attout_bf, s));
     MMVAE_TRY(launch_colsum_f32(d_out, rows, D2, P->buf.grads + P->ae[1].b_off, s));
     MMVAE_TRY(att_enc_bwd(*P, w.d_attout_bf, s));
-    return unpack(*P, s);
+    return plan_unpack(*P, s, true);
 }
 int celeba_attrs_decoder_fwd(CelebaPlan* P, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
@@ -689,9 +665,9 @@ int celeba_attrs_decoder_bwd(CelebaPlan* P, void* ws, size_t wsb, const float* d
     MMVAE_TRY(use_ws(P, ws, wsb));
     CelebaPlan::W& w = P->w;
     const long long n = (long long)P->B * NA;
-    MMVAE_TRY(zero_gpk(*P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, d_recon, recon, n, w.dalogit);
     MMVAE_TRY(mmvae_check_launch("sigmoid_bwd"));
     MMVAE_TRY(att_dec_bwd(*P, w.dalogit, 1, dz, s));
-    return unpack(*P, s);
+    return plan_unpack(*P, s, true);
 }

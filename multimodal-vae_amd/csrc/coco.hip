@@ -367,28 +367,13 @@ int dec_bwd(CocoPlan& P, const float* dlogit, int groups, float* dz, hipStream_t
 }
 
 int use_ws(CocoPlan* P, void* ws, size_t bytes, bool module = true) {
-    MMVAE_TRY(check_bound(P));
-    const size_t need = module ? P->ws_bytes_module : P->ws_bytes;
-    MMVAE_REQUIRE(ws != nullptr && bytes >= need, "workspace too small (%zu < %zu)", bytes, need);
-    P->carve_passes = module ? 1 : 3;
-    Workspace w(ws, bytes);
-    carve(*P, w);
+    MMVAE_TRY(plan_use_ws(P, ws, bytes, module, carve));
     P->wgrad_forked = false;
-    P->dec_skip_mask = 0;
-    P->slab.reset(P->w.slab, P->w.slab_floats);
-    // side work or a completion event a FAILED earlier call left behind must not run against this call's buffers
-    P->side_pending.clear(); P->batch_reduce = false;
-    (void)mmvae_take_stop_event();
     P->dec_wg_pending = false;
     P->comb_fresh = false; P->dw16_fresh = false; P->dec_wg_composed = false;
     P->cl_alarm_f = P->cl_alarm_b = nullptr;
     return MMVAE_OK;
 }
-int unpack(CocoPlan& P, hipStream_t s) {
-    MMVAE_TRY(launch_wgrad_reduce(&P.slab, s));      // slab copies nobody summed yet (every side stream has joined s)
-    return launch_unpack_grads(P.buf.gdesc_dev, P.gk.d.data(), (int)P.gk.d.size(), P.buf.gpk, P.buf.gpk_vec, P.buf.grads, s);
-}
-int zero_gpk(CocoPlan& P, hipStream_t s) { return launch_fill_zero(P.buf.gpk, (size_t)P.gk.mat_elems * sizeof(float), s); }
 int zero_ws(CocoPlan& P, hipStream_t s) { return launch_fill_zero(P.w.zero_begin, P.w.zero_bytes, s); }
 
 }  // namespace
@@ -401,27 +386,18 @@ CocoPlan* coco_create(int D, int B, int T) {
     CocoPlan* P = new CocoPlan();
     P->D = D; P->B = B; P->T = T;
     build(*P);
-    Workspace ws(nullptr, 0);
-    carve(*P, ws);
-    P->ws_bytes = ws.used();
-    P->carve_passes = 1;
-    Workspace wm(nullptr, 0);
-    carve(*P, wm);
-    P->ws_bytes_module = wm.used();
-    P->carve_passes = 3;
+    plan_size_workspaces(*P, carve);
     return P;
 }
 void coco_destroy(CocoPlan* P) { delete P; }
 PlanBase* coco_base(CocoPlan* P) { return P; }
 int coco_steps(const CocoPlan* P) { return P->T; }
 
-static int coco_step_body(CocoPlan* Pp, const CocoStepIO& io, int training, int do_backward, hipStream_t s);
-int coco_step(CocoPlan* Pp, const CocoStepIO& io, int training, int do_backward, hipStream_t s) {
-    const int rc = coco_step_body(Pp, io, training, do_backward, s);
-    if (rc != MMVAE_OK && Pp) join_after_error(*Pp, s);
-    return rc;
+static int coco_step_body(CocoPlan* Pp, const mmvae_coco_step_io& io, int training, int do_backward, hipStream_t s);
+int coco_step(CocoPlan* Pp, const mmvae_coco_step_io& io, int training, int do_backward, hipStream_t s) {
+    return plan_step(Pp, io, training, do_backward, s, coco_step_body);
 }
-static int coco_step_body(CocoPlan* Pp, const CocoStepIO& io, int training, int do_backward, hipStream_t s) {
+static int coco_step_body(CocoPlan* Pp, const mmvae_coco_step_io& io, int training, int do_backward, hipStream_t s) {
     MMVAE_TRY(use_ws(Pp, io.ws, io.ws_bytes, false));
     CocoPlan& P = *Pp;
     CocoPlan::W& w = P.w;
@@ -435,7 +411,7 @@ static int coco_step_body(CocoPlan* Pp, const CocoStepIO& io, int training, int 
         sb.zero_ptr[1] = P.buf.gpk; sb.zero_bytes[1] = (size_t)P.gk.mat_elems * sizeof(float);
         sb.zero_ptr[2] = P.buf.grads; sb.zero_bytes[2] = (size_t)(P.nparams / 4) * 16;
     }
-    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_ctr;
+    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_counter;
     if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B3 * D; eps = w.eps; }
     if (training && io.enc_dropout && !m1) { sb.mask[0] = w.m1; sb.n_mask[0] = (long long)2 * B * HID1; m1 = w.m1; }
     if (training && io.enc_dropout && !m2) { sb.mask[1] = w.m2; sb.n_mask[1] = (long long)2 * B * HID2; m2 = w.m2; }
@@ -519,7 +495,7 @@ static int coco_step_body(CocoPlan* Pp, const CocoStepIO& io, int training, int 
     MMVAE_TRY(edge(P, P.st_wgrad, s));
     if (P.st_wgrad2 != P.st_wgrad) MMVAE_TRY(edge(P, P.st_wgrad2, s));
     if (io.defer_unpack) MMVAE_TRY(launch_wgrad_reduce(&P.slab, s));  // the packed gradients are complete; Adam gathers them
-    else MMVAE_TRY(unpack(P, s));
+    else MMVAE_TRY(plan_unpack(P, s, true));
     // (timeout words of the decoder's cluster launches of THIS step: zeroed before each of them, set only when an exchange gave up;
     //  last kernel of the step, so that the mark in the gradient is not overwritten)
     hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, s, w.sums, io.sums, P.cl_alarm_f, P.cl_alarm_b, io.optimizer_state, P.buf.grads);
@@ -537,11 +513,11 @@ int coco_image_encoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* d_out
     MMVAE_TRY(use_ws(P, ws, wsb));
     CocoPlan::W& w = P->w;
     const int rows = P->B, D2 = 2 * P->D;
-    MMVAE_TRY(zero_gpk(*P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     MMVAE_TRY(launch_cast_bf16(d_out, (long long)rows * D2, w.d_encout, s));
     MMVAE_TRY(launch_colsum_f32(d_out, rows, D2, P->buf.grads + P->fc[2].b_off, s));
     MMVAE_TRY(enc_bwd(*P, w.d_encout, 1, m1, m2, m1 != nullptr && m2 != nullptr, s));
-    return unpack(*P, s);
+    return plan_unpack(*P, s, true);
 }
 int coco_image_decoder_fwd(CocoPlan* P, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
@@ -558,11 +534,11 @@ int coco_image_decoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* d_rec
     MMVAE_TRY(use_ws(P, ws, wsb));
     CocoPlan::W& w = P->w;
     const long long n = (long long)P->B * NPIX;
-    MMVAE_TRY(zero_gpk(*P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, d_recon, recon, n, w.tmp_f32);
     MMVAE_TRY(mmvae_check_launch("sigmoid_bwd"));
     MMVAE_TRY(dec_bwd(*P, w.tmp_f32, 1, dz, s));
-    return unpack(*P, s);
+    return plan_unpack(*P, s, true);
 }
 int coco_text_encoder_fwd(CocoPlan* P, void* ws, size_t wsb, const float* text, float* out, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));

@@ -122,7 +122,7 @@ void mnist_destroy(MnistPlan* P) { delete P; }
 int mnist_is_f32(const MnistPlan* P) { return P->f32 ? 1 : 0; }
 PlanBase* mnist_base(MnistPlan* P) { return P; }
 
-int mnist_step(MnistPlan* Pp, const MnistStepIO& io, int training, int do_backward, hipStream_t s) {
+int mnist_step(MnistPlan* Pp, const mmvae_mnist_step_io& io, int training, int do_backward, hipStream_t s) {
     MMVAE_TRY(check_bound(Pp));
     MnistPlan& P = *Pp;
     if (P.f32) return mnist_f32_step(P, io, training, do_backward, s);
@@ -139,7 +139,7 @@ int mnist_step(MnistPlan* Pp, const MnistStepIO& io, int training, int do_backwa
         sb.zero_ptr[1] = P.buf.gpk; sb.zero_bytes[1] = (size_t)P.gk.mat_elems * sizeof(float);
         sb.zero_ptr[2] = P.buf.grads; sb.zero_bytes[2] = (size_t)(P.nparams / 4) * 16;
     }
-    sb.seed = io.seed; sb.step = io.step_ctr;
+    sb.seed = io.seed; sb.step = io.step_counter;
     if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B3 * D; eps = w.eps; }
     MMVAE_TRY(launch_step_begin(sb, s));
     if (do_backward && P.nparams % 4 != 0)
@@ -240,7 +240,7 @@ int mnist_step(MnistPlan* Pp, const MnistStepIO& io, int training, int do_backwa
     MMVAE_TRY(rc);
     MMVAE_TRY(edge(P, P.st_wgrad, s));
     if (P.st_wgrad2 != P.st_wgrad) MMVAE_TRY(edge(P, P.st_wgrad2, s));
-    return launch_unpack_grads(P.buf.gdesc_dev, P.gk.d.data(), (int)P.gk.d.size(), P.buf.gpk, P.buf.gpk_vec, P.buf.grads, s);
+    return plan_unpack(P, s, false);
 }
 
 // ================================================================== granular modules (drop-in nn.Module forwards)
@@ -258,11 +258,8 @@ int mn_use_ws(MnistPlan* P, void* ws, size_t bytes) {
 }
 int mn_zero(MnistPlan& P, bool backward, hipStream_t s) {
     MMVAE_TRY(launch_fill_zero(P.w.zero_begin, P.w.zero_bytes, s));
-    if (backward) MMVAE_TRY(launch_fill_zero(P.buf.gpk, (size_t)P.gk.mat_elems * sizeof(float), s));
+    if (backward) MMVAE_TRY(plan_zero_gpk(P, s));
     return MMVAE_OK;
-}
-int mn_unpack(MnistPlan& P, hipStream_t s) {
-    return launch_unpack_grads(P.buf.gdesc_dev, P.gk.d.data(), (int)P.gk.d.size(), P.buf.gpk, P.buf.gpk_vec, P.buf.grads, s);
 }
 // dlogits[r][c] = d_logp[r][c] - softmax[r][c] * sum_c d_logp[r][c]   (log_softmax backward), bf16 rows of stride ld
 __global__ void logsoftmax_bwd_kernel(const float* d_logp, const float* logp, int rows, int classes, bf16* out, int ld) {
@@ -291,7 +288,7 @@ int mnist_image_encoder_bwd(MnistPlan* Pp, void* ws, size_t wsb, const float* d_
     if (Pp && Pp->f32) { MMVAE_TRY(check_bound(Pp)); return mnist_f32_image_encoder_bwd(*Pp, ws, wsb, d_out, s); }
     MMVAE_TRY(mn_use_ws(Pp, ws, wsb));
     MnistPlan& P = *Pp; MnistPlan::W& w = P.w; const int B = P.B, D2 = 2 * P.D;
-    MMVAE_TRY(launch_fill_zero(P.buf.gpk, (size_t)P.gk.mat_elems * sizeof(float), s));
+    MMVAE_TRY(plan_zero_gpk(P, s));
     MMVAE_TRY(launch_cast_bf16(d_out, (long long)B * D2, w.d_encout, s));
     MMVAE_TRY(launch_colsum_f32(d_out, B, D2, P.buf.grads + P.ie[2].b_off, s));
     MMVAE_TRY(lin_wgrad(P, P.ie[2], w.d_encout, w.a_ie[1], B, s));
@@ -301,7 +298,7 @@ int mnist_image_encoder_bwd(MnistPlan* Pp, void* ws, size_t wsb, const float* d_
     MMVAE_TRY(lin_dgrad(P, P.ie[1], w.d_ie[1], B, 1, w.d_ie[0], nullptr, 400, w.r_ie[0], 0, s));
     MMVAE_TRY(mn_bn_bwd(P, 0, w.d_ie[0], w.r_ie[0], B, 1, 400, s));
     MMVAE_TRY(lin_wgrad(P, P.ie[0], w.d_ie[0], w.x_bf, B, s));
-    return mn_unpack(P, s);
+    return plan_unpack(P, s, false);
 }
 int mnist_image_decoder_fwd(MnistPlan* Pp, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t s) {
     if (Pp && Pp->f32) { MMVAE_TRY(check_bound(Pp)); return mnist_f32_image_decoder_fwd(*Pp, ws, wsb, z, training, recon, s); }
@@ -323,7 +320,7 @@ int mnist_image_decoder_bwd(MnistPlan* Pp, void* ws, size_t wsb, const float* d_
     if (Pp && Pp->f32) { MMVAE_TRY(check_bound(Pp)); return mnist_f32_image_decoder_bwd(*Pp, ws, wsb, d_recon, recon, dz, s); }
     MMVAE_TRY(mn_use_ws(Pp, ws, wsb));
     MnistPlan& P = *Pp; MnistPlan::W& w = P.w; const int B = P.B;
-    MMVAE_TRY(launch_fill_zero(P.buf.gpk, (size_t)P.gk.mat_elems * sizeof(float), s));
+    MMVAE_TRY(plan_zero_gpk(P, s));
     const long long n = (long long)B * 784;
     hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, d_recon, recon, n, w.dlogit);
     MMVAE_TRY(mmvae_check_launch("sigmoid_bwd"));
@@ -337,7 +334,7 @@ int mnist_image_decoder_bwd(MnistPlan* Pp, void* ws, size_t wsb, const float* d_
     MMVAE_TRY(mn_bn_bwd(P, 2, w.d_id[0], w.r_id[0], B, 1, 200, s));
     MMVAE_TRY(lin_wgrad(P, P.id[0], w.d_id[0], w.z_bf, B, s));
     MMVAE_TRY(lin_dgrad(P, P.id[0], w.d_id[0], B, 1, nullptr, dz, P.D, nullptr, -1, s));
-    return mn_unpack(P, s);
+    return plan_unpack(P, s, false);
 }
 int mnist_text_encoder_fwd(MnistPlan* Pp, void* ws, size_t wsb, const long long* label, int training, float* out, hipStream_t s) {
     if (Pp && Pp->f32) { MMVAE_TRY(check_bound(Pp)); return mnist_f32_text_encoder_fwd(*Pp, ws, wsb, label, training, out, s); }
@@ -352,14 +349,14 @@ int mnist_text_encoder_bwd(MnistPlan* Pp, void* ws, size_t wsb, const long long*
     if (Pp && Pp->f32) { MMVAE_TRY(check_bound(Pp)); return mnist_f32_text_encoder_bwd(*Pp, ws, wsb, label, d_out, s); }
     MMVAE_TRY(mn_use_ws(Pp, ws, wsb));
     MnistPlan& P = *Pp; MnistPlan::W& w = P.w; const int B = P.B, D2 = 2 * P.D;
-    MMVAE_TRY(launch_fill_zero(P.buf.gpk, (size_t)P.gk.mat_elems * sizeof(float), s));
+    MMVAE_TRY(plan_zero_gpk(P, s));
     MMVAE_TRY(launch_cast_bf16(d_out, (long long)B * D2, w.d_txtout_bf, s));
     MMVAE_TRY(launch_colsum_f32(d_out, B, D2, P.buf.grads + P.te_lin.b_off, s));
     MMVAE_TRY(lin_wgrad(P, P.te_lin, w.d_txtout_bf, w.a_te, B, s));
     MMVAE_TRY(lin_dgrad(P, P.te_lin, w.d_txtout_bf, B, 1, w.d_te, nullptr, 56, w.r_te, 4, s));
     MMVAE_TRY(mn_bn_bwd(P, 4, w.d_te, w.r_te, B, 1, 56, s));
     MMVAE_TRY(launch_embed_scatter_add(w.d_te, 56, 50, label, B, P.buf.grads + P.emb_off, s));
-    return mn_unpack(P, s);
+    return plan_unpack(P, s, false);
 }
 int mnist_text_decoder_fwd(MnistPlan* Pp, void* ws, size_t wsb, const float* z, int training, float* logp, hipStream_t s) {
     if (Pp && Pp->f32) { MMVAE_TRY(check_bound(Pp)); return mnist_f32_text_decoder_fwd(*Pp, ws, wsb, z, training, logp, s); }
@@ -379,7 +376,7 @@ int mnist_text_decoder_bwd(MnistPlan* Pp, void* ws, size_t wsb, const float* d_l
     if (Pp && Pp->f32) { MMVAE_TRY(check_bound(Pp)); return mnist_f32_text_decoder_bwd(*Pp, ws, wsb, d_logp, logp, dz, s); }
     MMVAE_TRY(mn_use_ws(Pp, ws, wsb));
     MnistPlan& P = *Pp; MnistPlan::W& w = P.w; const int B = P.B;
-    MMVAE_TRY(launch_fill_zero(P.buf.gpk, (size_t)P.gk.mat_elems * sizeof(float), s));
+    MMVAE_TRY(plan_zero_gpk(P, s));
     hipLaunchKernelGGL(logsoftmax_bwd_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, s, d_logp, logp, B, 10, w.dtl, 16);
     MMVAE_TRY(mmvae_check_launch("logsoftmax_bwd"));
     MMVAE_TRY(launch_colsum_bf16(w.dtl, 16, B, 10, P.buf.grads + P.td[1].b_off, s));
@@ -388,5 +385,5 @@ int mnist_text_decoder_bwd(MnistPlan* Pp, void* ws, size_t wsb, const float* d_l
     MMVAE_TRY(mn_bn_bwd(P, 5, w.d_td, w.r_td, B, 1, 16, s));
     MMVAE_TRY(lin_wgrad(P, P.td[0], w.d_td, w.z_bf, B, s));
     MMVAE_TRY(lin_dgrad(P, P.td[0], w.d_td, B, 1, nullptr, dz, P.D, nullptr, -1, s));
-    return mn_unpack(P, s);
+    return plan_unpack(P, s, false);
 }

@@ -297,7 +297,7 @@ size_t mnist_f32_workspace_bytes(MnistPlan& P) {
     return ws.used();
 }
 
-int mnist_f32_step(MnistPlan& P, const MnistStepIO& io, int training, int do_backward, hipStream_t s) {
+int mnist_f32_step(MnistPlan& P, const mmvae_mnist_step_io& io, int training, int do_backward, hipStream_t s) {
     MMVAE_TRY(use_ws32(P, io.ws, io.ws_bytes));
     MMVAE_REQUIRE(io.image && io.label && io.sums, "mnist step: image/label/sums must be given");
     MnistPlan::W32& w = P.w32;
@@ -306,7 +306,7 @@ int mnist_f32_step(MnistPlan& P, const MnistStepIO& io, int training, int do_bac
     StepBeginArgs sb{};
     sb.zero_ptr[0] = w.zero_begin; sb.zero_bytes[0] = w.zero_bytes;
     if (do_backward) { sb.zero_ptr[1] = P.buf.grads; sb.zero_bytes[1] = (size_t)(P.nparams / 4) * 16; }
-    sb.seed = io.seed; sb.step = io.step_ctr;
+    sb.seed = io.seed; sb.step = io.step_counter;
     if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B3 * D; eps = w.eps; }
     MMVAE_TRY(launch_step_begin(sb, s));
     if (do_backward && P.nparams % 4 != 0)

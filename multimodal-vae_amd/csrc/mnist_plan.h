@@ -38,7 +38,7 @@ struct MnistPlan : PlanBase {
 
 // fp32 path entry points (mnist_f32.hip); same contracts as the public functions of mnist.h
 size_t mnist_f32_workspace_bytes(MnistPlan& P);
-int mnist_f32_step(MnistPlan& P, const MnistStepIO& io, int training, int do_backward, hipStream_t s);
+int mnist_f32_step(MnistPlan& P, const mmvae_mnist_step_io& io, int training, int do_backward, hipStream_t s);
 int mnist_f32_image_encoder_fwd(MnistPlan& P, void* ws, size_t wsb, const float* image, int training, float* out, hipStream_t s);
 int mnist_f32_image_encoder_bwd(MnistPlan& P, void* ws, size_t wsb, const float* d_out, hipStream_t s);
 int mnist_f32_image_decoder_fwd(MnistPlan& P, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t s);

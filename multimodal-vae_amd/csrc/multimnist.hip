@@ -91,6 +91,7 @@ void build_plan(MMPlan& P) {
     long long so = 0;
     for (int i = 0; i < 6; ++i) {
         P.bn[i] = BnL{off(P, std::string(bnn[i]) + ".weight"), off(P, std::string(bnn[i]) + ".bias"), bnc[i], so, i};
+        P.bn_names.push_back(bnn[i]); P.bn_list.push_back(P.bn[i]);
         so += 2 * bnc[i];
     }
     // encoder convs (multimnist/model.py:160-169)
@@ -209,7 +210,7 @@ void build_plan(MMPlan& P) {
         if (P.mlp_tail) { late(P.mt_w3t); late(P.mt_w2t); }
     }
     // gradient descriptors of the decoders (image_decoder.*, text_decoder.*): complete before the encoders' backward has run
-    // (MMStepIO::dp_split scatters them into the flat gradient buffer early)
+    // (mmvae_mm_step_io::dp_split scatters them into the flat gradient buffer early)
     for (PackDesc& d : P.gk.d)
         for (const ParamInfo& pi : P.params)
             if (d.src_off >= pi.offset && d.src_off < pi.offset + pi.numel)
@@ -868,14 +869,7 @@ MMPlan* mm_create(int D, int B) {
     // kernels on half the chip each: ONE stream again (643 -> 634 us; knob one_wgrad_stream)
     P->single_wgrad_stream = true;
     build_plan(*P);
-    Workspace ws(nullptr, 0);
-    carve(*P, ws);
-    P->ws_bytes = ws.used();
-    P->carve_passes = 1;
-    Workspace wm(nullptr, 0);
-    carve(*P, wm);
-    P->ws_bytes_module = wm.used();
-    P->carve_passes = 3;
+    plan_size_workspaces(*P, carve);
     return P;
 }
 void mm_destroy(MMPlan* P) { delete P; }
@@ -891,67 +885,20 @@ int mm_early_ranges(const MMPlan* P, long long* ranges, int cap) {
         if (ranges[2 * r] % 4 != 0 || ranges[2 * r + 1] % 4 != 0) return 0;
     return n;
 }
-int mm_D(const MMPlan* P) { return P->D; }
-int mm_B(const MMPlan* P) { return P->B; }
-const std::vector<ParamInfo>& mm_params(const MMPlan* P) { return P->params; }
-long long mm_param_count(const MMPlan* P) { return P->nparams; }
-long long mm_packed_elems(const MMPlan* P) { return P->pk.mat_elems; }
-long long mm_packed_vec_elems(const MMPlan* P) { return P->pk.vec_elems > 0 ? P->pk.vec_elems : 64; }
-long long mm_gpk_elems(const MMPlan* P) { return P->gk.mat_elems; }
-long long mm_gpk_vec_elems(const MMPlan* P) { return P->gk.vec_elems > 0 ? P->gk.vec_elems : 64; }
-int mm_ndesc(const MMPlan* P) { return (int)P->pk.d.size(); }
-const PackDesc* mm_desc_host(const MMPlan* P) { return P->pk.d.data(); }
-int mm_ngdesc(const MMPlan* P) { return (int)P->gk.d.size(); }
-const PackDesc* mm_gdesc_host(const MMPlan* P) { return P->gk.d.data(); }
-size_t mm_workspace_bytes(const MMPlan* P) { return P->ws_bytes; }
-size_t mm_module_workspace_bytes(const MMPlan* P) { return P->ws_bytes_module; }
+PlanBase* mm_base(MMPlan* P) { return P; }
 
-int mm_bind(MMPlan* P, const MMBuffers& b) {
-    MMVAE_REQUIRE(b.params && b.grads && b.bn_stats && b.bn_nbt && b.packed && b.packed_vec && b.gpk && b.gpk_vec &&
-                  b.desc_dev && b.gdesc_dev, "mm_bind: null buffer");
-    P->buf = b;
-    P->bound = true;
-    return MMVAE_OK;
-}
-static int use_ws(MMPlan* P, void* ws, size_t bytes, bool module = true) {
-    MMVAE_TRY(check_bound(P));
-    const size_t need = module ? P->ws_bytes_module : P->ws_bytes;
-    MMVAE_REQUIRE(ws != nullptr && bytes >= need, "workspace too small (%zu < %zu)", bytes, need);
-    P->carve_passes = module ? 1 : 3;
-    Workspace w(ws, bytes);
-    carve(*P, w);
-    P->dec_skip_mask = 0;
-    P->slab.reset(P->w.slab, P->w.slab_floats);
-    // side work or a completion event a FAILED earlier call left behind must not run against this call's buffers
-    P->side_pending.clear(); P->batch_reduce = false;
-    (void)mmvae_take_stop_event();
-    return MMVAE_OK;
-}
+// (no reset of its own behind the shared part: wgrad_forked is cleared where the step leaves its backward pass)
+static int use_ws(MMPlan* P, void* ws, size_t bytes, bool module = true) { return plan_use_ws(P, ws, bytes, module, carve); }
 
-int mm_pack_weights(MMPlan* P, hipStream_t s) {
-    MMVAE_TRY(check_bound(P));
-    return launch_pack(P->buf.desc_dev, P->pk.d.data(), (int)P->pk.d.size(), P->buf.params, P->buf.packed, P->buf.packed_vec, s);
+static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, int do_backward, hipStream_t s);
+int mm_step_fwd_bwd(MMPlan* Pp, const mmvae_mm_step_io& io, int training, int do_backward, hipStream_t s) {
+    if (const mmvae_early_adam* e = io.early_adam) {
+        MMVAE_REQUIRE(e->m && e->v && e->state && e->gmap && e->ran, "mmvae_mm_step: early_adam with a null field");
+        *e->ran = 0;
+    }
+    return plan_step(Pp, io, training, do_backward, s, mm_step_body);
 }
-int mm_unpack_grads(MMPlan* P, hipStream_t s) {
-    MMVAE_TRY(check_bound(P));
-    MMVAE_TRY(launch_wgrad_reduce(&P->slab, s));      // partial-tile slabs -> packed gradients (no-op when none are owed)
-    return launch_unpack_grads(P->buf.gdesc_dev, P->gk.d.data(), (int)P->gk.d.size(), P->buf.gpk, P->buf.gpk_vec, P->buf.grads, s);
-}
-int mm_grad_map(MMPlan* P, int* map, hipStream_t s) {
-    MMVAE_TRY(check_bound(P));
-    return launch_unpack_map(P->buf.gdesc_dev, P->gk.d.data(), (int)P->gk.d.size(), P->nparams, P->gk.mat_elems, map, s);
-}
-static int zero_gpk(MMPlan* P, hipStream_t s) {
-    return launch_fill_zero(P->buf.gpk, (size_t)P->gk.mat_elems * sizeof(float), s);
-}
-
-static int mm_step_body(MMPlan* Pp, const MMStepIO& io, int training, int do_backward, hipStream_t s);
-int mm_step_fwd_bwd(MMPlan* Pp, const MMStepIO& io, int training, int do_backward, hipStream_t s) {
-    const int rc = mm_step_body(Pp, io, training, do_backward, s);
-    if (rc != MMVAE_OK && Pp) join_after_error(*Pp, s);      // the message of the first error stays in mmvae_last_error
-    return rc;
-}
-static int mm_step_body(MMPlan* Pp, const MMStepIO& io, int training, int do_backward, hipStream_t s) {
+static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, int do_backward, hipStream_t s) {
     MMVAE_TRY(use_ws(Pp, io.ws, io.ws_bytes, false));
     MMPlan& P = *Pp;
     MMPlan::W& w = P.w;
@@ -977,7 +924,7 @@ static int mm_step_body(MMPlan* Pp, const MMStepIO& io, int training, int do_bac
         if (skipz & 1) sz.zero_ptr[1] = nullptr;
         if (skipz & 2) sz.zero_ptr[2] = nullptr;
     }
-    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_ctr;
+    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_counter;
     if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B3 * D; eps = w.eps; }
     if (training && io.enc_dropout && !m1) { sb.mask[0] = w.m1; sb.n_mask[0] = (long long)2 * B * 400; m1 = w.m1; }
     if (training && io.enc_dropout && !m2) { sb.mask[1] = w.m2; sb.n_mask[1] = (long long)2 * B * 200; m2 = w.m2; }
@@ -1085,7 +1032,7 @@ static int mm_step_body(MMPlan* Pp, const MMStepIO& io, int training, int do_bac
     P.deferred.clear();
     P.defer_wgrad = false;
     if (img_groups > 0) rc = dec_bwd(P, w.dlogit, img_groups, w.dz_img, s, fuse_tail, fuse, 3, training);
-    // ---- early optimizer part (MMStepIO::early_adam): every gradient of image_decoder.* is complete on the weight-gradient stream (its
+    // ---- early optimizer part (mmvae_mm_step_io::early_adam): every gradient of image_decoder.* is complete on the weight-gradient stream (its
     //      last flush forked off the first layer's data gradient, which also closed the BatchNorm parameter gradients), text_decoder.*
     //      behind ev_txtgrads on the second-modality stream.  Their Adam update runs in the gap that stream has until the encoders'
     //      weight gradients arrive, beside the encoders' backward -- the optimizer launch behind the step shrinks to the encoders' ranges.
@@ -1093,9 +1040,10 @@ static int mm_step_body(MMPlan* Pp, const MMStepIO& io, int training, int do_bac
         io.defer_unpack && P.ev_txtgrads && P.side_pending.empty() && P.st_wgrad2 == P.st_wgrad && mmvae_knob("mm_early_adam", 1)) {
         hipStream_t Wst = P.st_wgrad;
         AdamArgs ad{};
-        ad.p = P.buf.params; ad.g = P.buf.grads; ad.m = io.ea_m; ad.v = io.ea_v; ad.n = P.nparams; ad.step = io.ea_state;
-        ad.lr = io.ea_lr; ad.b1 = io.ea_b1; ad.b2 = io.ea_b2; ad.eps = io.ea_eps; ad.grad_scale = io.ea_scale;
-        ad.gmap = io.ea_gmap; ad.gpk = P.buf.gpk; ad.gpk_vec = P.buf.gpk_vec; ad.g_out = P.buf.grads;
+        const mmvae_early_adam& ea = *io.early_adam;
+        ad.p = P.buf.params; ad.g = P.buf.grads; ad.m = ea.m; ad.v = ea.v; ad.n = P.nparams; ad.step = ea.state;
+        ad.lr = ea.lr; ad.b1 = ea.beta1; ad.b2 = ea.beta2; ad.eps = ea.eps; ad.grad_scale = ea.grad_scale;
+        ad.gmap = ea.gmap; ad.gpk = P.buf.gpk; ad.gpk_vec = P.buf.gpk_vec; ad.g_out = P.buf.grads;
         long long rg[8];
         ad.nr = mm_early_ranges(&P, rg, 4);
         for (int r = 0; r < ad.nr; ++r) { ad.roff[r] = rg[2 * r]; ad.rlen[r] = rg[2 * r + 1]; }
@@ -1103,7 +1051,7 @@ static int mm_step_body(MMPlan* Pp, const MMStepIO& io, int training, int do_bac
         if (ad.nr > 0) {
             if (hipStreamWaitEvent(Wst, P.ev_txtgrads, 0) != hipSuccess) { mmvae_set_error("early optimizer part: %s", hipGetErrorString(hipGetLastError())); rc = MMVAE_EHIP; }
             if (rc == MMVAE_OK) rc = launch_adam(ad, Wst);
-            if (rc == MMVAE_OK) *io.ea_ran = 1;
+            if (rc == MMVAE_OK) *ea.ran = 1;
         }
     }
     if (rc == MMVAE_OK) {                            // dz of the text decoder
@@ -1127,7 +1075,7 @@ static int mm_step_body(MMPlan* Pp, const MMStepIO& io, int training, int do_bac
         if (rc == MMVAE_OK && P.st_wgrad2 != P.st_wgrad && P.st_wgrad2 != T) rc = edge(P, P.st_wgrad2, T);
         if (rc == MMVAE_OK) rc = launch_wgrad_reduce(&P.slab, T);
         if (rc == MMVAE_OK)
-            rc = launch_unpack_grads(P.buf.gdesc_dev, P.gk.d.data(), (int)P.gk.d.size(), P.buf.gpk, P.buf.gpk_vec, P.buf.grads, T, 1);
+            rc = plan_unpack(P, T, false, 1);
         if (rc == MMVAE_OK) {
             if (!P.ev_early) hipEventCreateWithFlags(&P.ev_early, hipEventDisableTiming);
             if (hipEventRecord(P.ev_early, T) != hipSuccess) { mmvae_set_error("early-gradient event failed"); rc = MMVAE_EHIP; }
@@ -1152,8 +1100,8 @@ static int mm_step_body(MMPlan* Pp, const MMStepIO& io, int training, int do_bac
     MMVAE_TRY(rc);
     MMVAE_TRY(join_sides(P, T, s));
     MMVAE_TRY(launch_wgrad_reduce(&P.slab, s));
-    if (dp_split) return launch_unpack_grads(P.buf.gdesc_dev, P.gk.d.data(), (int)P.gk.d.size(), P.buf.gpk, P.buf.gpk_vec, P.buf.grads, s, 0);
-    if (!io.defer_unpack) MMVAE_TRY(mm_unpack_grads(Pp, s));
+    if (dp_split) return plan_unpack(P, s, false, 0);
+    if (!io.defer_unpack) MMVAE_TRY(plan_unpack(P, s, true));
     return MMVAE_OK;
 }
 int mm_wait_early_grads(MMPlan* P, hipStream_t s) {
@@ -1178,12 +1126,12 @@ int mm_image_encoder_bwd(MMPlan* P, void* ws, size_t wsb, const float* d_out, co
     MMVAE_TRY(use_ws(P, ws, wsb));
     MMPlan::W& w = P->w;
     const int rows = P->B, D2 = 2 * P->D;
-    MMVAE_TRY(zero_gpk(P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     hipLaunchKernelGGL(cast_bf_kernel, dim3(ceil_div(rows * D2, 256)), dim3(256), 0, s, d_out, (long long)rows * D2, w.d_encout);
     hipLaunchKernelGGL(colsum_kernel, dim3(ceil_div(D2, 64)), dim3(64), 0, s, d_out, rows, D2, P->buf.grads + P->fc[2].b_off);
     MMVAE_TRY(mmvae_check_launch("image encoder bwd prologue"));
     MMVAE_TRY(enc_bwd(*P, w.d_encout, 1, m1, m2, m1 != nullptr, s));
-    return mm_unpack_grads(P, s);
+    return plan_unpack(*P, s, true);
 }
 int mm_image_decoder_fwd(MMPlan* P, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
@@ -1200,11 +1148,11 @@ int mm_image_decoder_bwd(MMPlan* P, void* ws, size_t wsb, const float* d_recon, 
     MMVAE_TRY(use_ws(P, ws, wsb));
     MMPlan::W& w = P->w;
     const int rows = P->B;
-    MMVAE_TRY(zero_gpk(P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(ceil_div(rows * NPIX, 256)), dim3(256), 0, s, d_recon, recon, (long long)rows * NPIX, w.dlogit);
     MMVAE_TRY(mmvae_check_launch("sigmoid_bwd"));
     MMVAE_TRY(dec_bwd(*P, w.dlogit, 1, dz, s));
-    return mm_unpack_grads(P, s);
+    return plan_unpack(*P, s, true);
 }
 int mm_text_encoder_fwd(MMPlan* P, void* ws, size_t wsb, const long long* text, float* out, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
@@ -1213,9 +1161,9 @@ int mm_text_encoder_fwd(MMPlan* P, void* ws, size_t wsb, const long long* text, 
 }
 int mm_text_encoder_bwd(MMPlan* P, void* ws, size_t wsb, const long long* text, const float* d_out, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
-    MMVAE_TRY(zero_gpk(P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     MMVAE_TRY(txt_enc_bwd(*P, text, d_out, s));
-    return mm_unpack_grads(P, s);
+    return plan_unpack(*P, s, true);
 }
 int mm_text_decoder_fwd(MMPlan* P, void* ws, size_t wsb, const float* z, int training, const uint8_t* keep,
                         const long long* force_tokens, float* words, long long* tokens, hipStream_t s) {
@@ -1228,12 +1176,12 @@ int mm_text_decoder_fwd(MMPlan* P, void* ws, size_t wsb, const float* z, int tra
 int mm_text_decoder_bwd(MMPlan* P, void* ws, size_t wsb, const float* z, const uint8_t* keep, const long long* force_tokens,
                         const float* words, const long long* tokens, const float* d_words, float* dz, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
-    MMVAE_TRY(zero_gpk(P, s));
+    MMVAE_TRY(plan_zero_gpk(*P, s));
     TextDecArgs a = td_args(*P, z, 1, true);
     a.keep = keep; a.keep_scale = 1.f / (1.f - DROP_P);
     a.force_tokens = force_tokens; a.words = const_cast<float*>(words); a.tokens_out = const_cast<long long*>(tokens);
     MMVAE_TRY(txt_dec_bwd(*P, a, d_words, dz, s));
-    return mm_unpack_grads(P, s);
+    return plan_unpack(*P, s, true);
 }
 
 // ---------------------------------------------------------------- importance-weighted evaluation (iw.h)
@@ -1496,16 +1444,6 @@ double mm_layer_algo_bytes(const MMPlan* Pc, const char* layer) {
     }
     return 0.0;
 }
-int mm_num_bn(const MMPlan*) { return 6; }
-int mm_bn_info(const MMPlan* P, int i, std::string& prefix, int& C, long long& offset) {
-    if (i < 0 || i >= 6) return MMVAE_EINVAL;
-    const char* bnn[6] = {"image_encoder.features.3", "image_encoder.features.6", "image_encoder.features.9",
-                          "image_decoder.hallucinate.1", "image_decoder.hallucinate.4", "image_decoder.hallucinate.7"};
-    prefix = bnn[i]; C = P->bn[i].C; offset = P->bn[i].stat_off;
-    return MMVAE_OK;
-}
-long long mm_bn_floats(const MMPlan* P) { return P->bn[5].stat_off + 2 * P->bn[5].C; }
-
 // ---------------------------------------------------------------- test aid: byte offset of a named workspace buffer
 long long mm_debug_offset(MMPlan* P, const char* name) {
     Workspace ws((void*)0x1000, (size_t)1 << 40);

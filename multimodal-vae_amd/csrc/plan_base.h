@@ -1,6 +1,7 @@
-// Shared host-side machinery of the per-dataset model plans (multimnist.hip, mnist.hip, celeba.hip): the flat
+// Shared host-side machinery of the per-dataset model plans (multimnist.hip, mnist.hip, celeba.hip, coco.hip): the flat
 // parameter table, weight-pack descriptor lists, layer descriptors, GEMM / wgrad parameter builders with their
-// split-K heuristics, the BatchNorm+activation launcher and the multi-stream fork/join helpers.
+// split-K heuristics, the BatchNorm+activation launcher, the multi-stream fork/join helpers and the plan lifecycle
+// (workspace sizing, use of a caller's workspace, the step wrapper, gradient unpack).
 // Include only from .hip translation units (it defines a few tiny __global__ helpers).
 #pragma once
 #include "layers.h"
@@ -578,8 +579,60 @@ inline void join_after_error(PlanBase& P, hipStream_t s) {
 }
 
 inline int check_bound(const PlanBase* P) {
-    MMVAE_REQUIRE(P && P->bound, "plan has no buffers bound (mmvae_mm_bind)");
+    MMVAE_REQUIRE(P && P->bound, "plan has no buffers bound (mmvae_<family>_bind)");
     return MMVAE_OK;
+}
+
+// ------------------------------------------------------------------ plan lifecycle shared by the families
+// Packed weight gradients -> the flat gradient buffer.  sum_slabs: the weight gradients' partial-tile slabs nobody summed yet
+// go into the packed gradients first (a no-op when none are owed; every side stream has joined `s`).  MNIST keeps no slabs.
+inline int plan_unpack(PlanBase& P, hipStream_t s, bool sum_slabs, int part = -1) {
+    if (sum_slabs) MMVAE_TRY(launch_wgrad_reduce(&P.slab, s));
+    return launch_unpack_grads(P.buf.gdesc_dev, P.gk.d.data(), (int)P.gk.d.size(), P.buf.gpk, P.buf.gpk_vec, P.buf.grads, s, part);
+}
+inline int plan_zero_gpk(PlanBase& P, hipStream_t s) { return launch_fill_zero(P.buf.gpk, (size_t)P.gk.mat_elems * sizeof(float), s); }
+
+// The families whose fused step batches three passes and whose module entry points run one (MultiMNIST, CelebA, COCO) carve
+// their workspace struct `w` with a function of their own, passed in as `carve`.
+// Sizes of the step workspace (three passes) and of the module workspace (one pass), at the end of <family>_create.
+template <class Plan>
+void plan_size_workspaces(Plan& P, void (*carve)(Plan&, Workspace&)) {
+    Workspace ws(nullptr, 0);
+    carve(P, ws);
+    P.ws_bytes = ws.used();
+    P.carve_passes = 1;
+    Workspace wm(nullptr, 0);
+    carve(P, wm);
+    P.ws_bytes_module = wm.used();
+    P.carve_passes = 3;
+}
+// Start of every call that works in a caller's workspace: refuses an unbound plan or a short workspace (before any GPU call),
+// carves it and resets the per-call scheduling state.  What else a family resets follows in its own use_ws, and the families
+// differ there: CelebA and COCO clear wgrad_forked, MultiMNIST (which clears it on every regular exit of its step and in
+// join_after_error) does not.
+template <class Plan>
+int plan_use_ws(Plan* P, void* ws, size_t bytes, bool module, void (*carve)(Plan&, Workspace&)) {
+    MMVAE_TRY(check_bound(P));
+    const size_t need = module ? P->ws_bytes_module : P->ws_bytes;
+    MMVAE_REQUIRE(ws != nullptr && bytes >= need, "workspace too small (%zu < %zu)", bytes, need);
+    P->carve_passes = module ? 1 : 3;
+    Workspace w(ws, bytes);
+    carve(*P, w);
+    P->dec_skip_mask = 0;
+    P->slab.reset(P->w.slab, P->w.slab_floats);
+    // side work or a completion event a FAILED earlier call left behind must not run against this call's buffers
+    P->side_pending.clear(); P->batch_reduce = false;
+    (void)mmvae_take_stop_event();
+    return MMVAE_OK;
+}
+// A fused step: its body, and on an error the join of whatever it had already forked onto the side streams
+// (the message of the first error stays in mmvae_last_error).
+template <class Plan, class IO>
+int plan_step(Plan* P, const IO& io, int training, int do_backward, hipStream_t s,
+              int (*body)(Plan*, const IO&, int, int, hipStream_t)) {
+    const int rc = body(P, io, training, do_backward, s);
+    if (rc != MMVAE_OK && P) join_after_error(*P, s);
+    return rc;
 }
 
 

@@ -53,6 +53,15 @@ def test_param_table_matches_reference_state_dict_order(lib, D):
     assert call("mmvae_mm_workspace_bytes", h) > 0
     assert call("mmvae_mm_packed_elems", h) > expect_off           # forward + backward packings
     assert call("mmvae_mm_num_bn", h) == 6 and call("mmvae_mm_bn_floats", h) == 2 * (64 + 128 + 256 + 128 + 64 + 32)
+    ch = C.c_int()
+    expect_stat = 0                                               # running_mean | running_var per layer, state_dict order
+    for i, (prefix, channels) in enumerate([("image_encoder.features.3", 64), ("image_encoder.features.6", 128),
+                                            ("image_encoder.features.9", 256), ("image_decoder.hallucinate.1", 128),
+                                            ("image_decoder.hallucinate.4", 64), ("image_decoder.hallucinate.7", 32)]):
+        call("mmvae_mm_bn_info", h, i, name, C.byref(ch), C.byref(off))
+        assert (name.value.decode(), ch.value, off.value) == (prefix, channels, expect_stat), i
+        assert prefix + ".running_mean" in R.formula_params("multimnist", D)
+        expect_stat += 2 * channels
     call("mmvae_mm_destroy", h)
 
 
@@ -64,6 +73,71 @@ def test_error_reporting_without_exceptions(lib):
     with pytest.raises(MMVAEError):                                # unbound plan
         call("mmvae_mm_pack_weights", h, None)
     call("mmvae_mm_destroy", h)
+
+
+def test_ctypes_step_io_layouts_match_the_header(tmp_path):
+    """The library reads the public step-io structs directly, so the ctypes classes of _lib.py are the only hand copy of their
+    layout: tests/host/stepio_layout.c compiles include/mmvae_hip.h as C and prints every size and offset."""
+    import shutil
+    import subprocess
+    from multimodal_vae_amd import _lib
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.skip("no host C compiler")
+    exe = str(tmp_path / "stepio_layout")
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host", "stepio_layout.c"),
+                    "-o", exe], check=True)
+    lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert [l.split()[0] for l in lines] == ["StepIO", "EarlyAdam", "MnistStepIO", "CelebaStepIO", "CocoStepIO"]
+    hdr = open(os.path.join(ROOT, "include", "mmvae_hip.h")).read()
+    for line in lines:
+        cls_name, size, *fields = line.split()
+        cls = getattr(_lib, cls_name)
+        assert C.sizeof(cls) == int(size), cls_name
+        assert [f.split(":")[0] for f in fields] == [n for n, _ in cls._fields_], cls_name
+        for f in fields:
+            n, o = f.split(":")
+            assert getattr(cls, n).offset == int(o), (cls_name, n)
+        # the C file lists every member the header declares: its struct body names exactly these identifiers before ';' or ','
+        c_name = cls.__doc__.split()[-1]
+        body = re.search(r"\{([^{}]*)\}\s*%s;" % c_name, hdr) if c_name.endswith("_io") else \
+            re.search(r"struct %s \{([^{}]*)\};" % c_name, hdr)
+        body = re.sub(r"/\*.*?\*/", "", body.group(1), flags=re.S)
+        declared = re.findall(r"(\w+)(?:\[\d+\])?\s*[;,]", body)
+        assert declared == [n for n, _ in cls._fields_], cls_name
+
+
+FAMILIES = {      # prefix: (create arguments, ctypes step-io class)
+    "mm": ((20, 8), "StepIO"), "mnist": ((20, 8), "MnistStepIO"), "celeba": ((20, 4), "CelebaStepIO"), "coco": ((20, 4), "CocoStepIO"),
+}
+
+
+@pytest.mark.parametrize("fam", sorted(FAMILIES))
+def test_workspace_refusals_before_any_gpu_call(lib, fam):
+    """An unbound plan and a short workspace are refused on the host, with the same words in every family."""
+    from multimodal_vae_amd import _lib
+    from multimodal_vae_amd._lib import call, MMVAEError
+    args, io_cls = FAMILIES[fam]
+    h = call("mmvae_%s_create" % fam, *args)
+    assert h
+    dummy = (C.c_float * 16)()
+    p = C.cast(dummy, C.c_void_p)
+
+    def module_call():
+        call("mmvae_%s_image_decoder_fwd" % fam, h, None, 0, p, 0, p, None)
+
+    with pytest.raises(MMVAEError, match="no buffers bound"):
+        module_call()
+    call("mmvae_%s_bind" % fam, h, *([p] * 10))
+    n_module = call("mmvae_%s_module_workspace_bytes" % fam, h)
+    n_step = call("mmvae_%s_workspace_bytes" % fam, h)
+    assert 0 < n_module <= n_step
+    with pytest.raises(MMVAEError, match=re.escape("workspace too small (0 < %d)" % n_module)):
+        module_call()
+    io = getattr(_lib, io_cls)()
+    with pytest.raises(MMVAEError, match=re.escape("workspace too small (0 < %d)" % n_step)):
+        call("mmvae_%s_step" % fam, h, C.byref(io), 0, 0, None)
+    call("mmvae_%s_destroy" % fam, h)
 
 
 def test_python_face_has_the_reference_state_dict():
