@@ -1463,6 +1463,8 @@ long long mm_debug_offset(MMPlan* P, const char* name) {
         {"red_e0", w.red_e[0]}, {"red_e1", w.red_e[1]}, {"red_e2", w.red_e[2]},
         {"red_d0", w.red_d[0]}, {"red_d1", w.red_d[1]}, {"red_d2", w.red_d[2]},
         {"a1", w.a1}, {"a2", w.a2}, {"a3", w.a3}, {"aq1", w.aq1}, {"aq2", w.aq2}, {"aq3", w.aq3},
+        {"a4", w.a4}, {"au", w.au}, {"ay1", w.ay1}, {"ay2", w.ay2}, {"slab", w.slab},
+        {"mr_e0", w.mr_e[0]}, {"mr_e1", w.mr_e[1]}, {"mr_e2", w.mr_e[2]}, {"mr_d0", w.mr_d[0]}, {"mr_d1", w.mr_d[1]}, {"mr_d2", w.mr_d[2]},
     };
     auto it = m.find(name);
     if (it == m.end()) return -1;

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import mmvae_ref as R
+from gradcheck import check_gradients
 
 pytestmark = pytest.mark.gpu
 
@@ -18,6 +19,12 @@ def _dev():
 def _load(st, P):
     for n, shape, off in st.table:
         st.params[off:off + P[n].numel()] = P[n].detach().reshape(-1).to(st.device)
+
+
+def _per_tensor(st, P, tensor_tol, label):
+    """every gradient tensor against the oracle's (relative L2; MMVAE_TOL_REPORT=1 prints the worst one)"""
+    g = st.grads.cpu()
+    check_gradients(((n, g[off:off + P[n].numel()], P[n].grad) for n, shape, off in st.table), tensor_tol, None, label)
 
 
 def _total(P):
@@ -47,6 +54,8 @@ def test_multimnist_ragged_batches(B):
     np.testing.assert_allclose(out.losses().cpu().numpy(), np.array([l.item() for l in losses]), rtol=2e-3)
     np.testing.assert_allclose(st.grads.double().norm().item(), _total(P), rtol=3e-2)
     assert torch.isfinite(st.grads).all()
+    # measured on MI355X against the oracle: worst tensor 1.48e-2 (B=2, features.6.bias), 1.20e-2 (B=7), 1.10e-2 (B=33); gate = twice that
+    _per_tensor(st, P, 3e-2, "multimnist ragged B=%d" % B)
 
 
 @pytest.mark.parametrize("B", [2, 5, 37])
@@ -85,6 +94,10 @@ def test_celeba_ragged_batches(B):
     np.testing.assert_allclose(out.losses().cpu().numpy(), np.array([l.item() for l in losses]), rtol=2e-3)
     np.testing.assert_allclose(st.grads.double().norm().item(), _total(P), rtol=5e-2)
     assert torch.isfinite(st.grads).all()
+    # (no per-tensor gate here.  Measured on MI355X against the oracle, bf16: worst tensor 7.49e-2 at B=3 (attrs_encoder.net.0.weight,
+    #  the Linear in front of a BatchNorm1d over 3 samples; image_encoder.features.3.weight 5.07e-2) and 4.69e-2 at B=5
+    #  (image_encoder.features.0.weight, the first conv, at the end of the longest backward chain); twice that is above the 4e-2 the
+    #  small-batch gates of this suite use, so the total-norm assert above stays the only one)
 
 
 def test_batch_of_one_raises_like_batchnorm():

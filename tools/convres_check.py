@@ -1,6 +1,8 @@
 """GPU check of the image-resident conv kernels (csrc/convres.hip) against the generic gather GEMM on the activations of a
 real B=256 step: same layer launched through mmvae_mm_bench_layer with the path off and on, outputs and column sums
-compared, both timed.  usage: python tools/convres_check.py [B]"""
+compared, both timed.  usage: python tools/convres_check.py [B]
+This tool is for timing: two engine kernels that share a wrong packed layout or tap table agree here.  Correctness against a
+float64 reference, layer by layer and exactly, is tests/test_gpu_layers.py."""
 import os, sys, ctypes, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import multimodal_vae_amd
