@@ -289,6 +289,13 @@ typedef struct {
     int defer_unpack;                       /* 1: the optimizer consumes the packed gradients itself (see the MultiMNIST step) */
 } mmvae_celeba_step_io;
 int mmvae_celeba_step(mmvae_celeba_t*, const mmvae_celeba_step_io*, int training, int do_backward, void* stream);
+/* Test / profiling aids, as mmvae_mm_bench_layer / mmvae_mm_debug_offset: one named layer launch of the step `iters` times on the
+ * workspace contents (enc_conv1..4, fc1, up, dec_convT1..3 and their _dgrad / _wgrad forms, fc2_dgrad, dec_last_dgrad_gemm,
+ * dec_last_wgrad; the staged forms of the fused step: enc_conv3_staged, dec_convT2_staged, dec_convT3_staged,
+ * enc_conv2/3_dgrad_staged, dec_convT2/3_dgrad_staged), and the byte
+ * offset of a named intermediate inside the step's workspace (-1 if unknown). */
+int mmvae_celeba_bench_layer(mmvae_celeba_t*, void* ws, size_t ws_bytes, const char* layer, int iters, void* stream);
+long long mmvae_celeba_debug_offset(mmvae_celeba_t*, const char* name);
 /* Granular modules (forward + autograd backward), workspace rules as for mmvae_mm_*_fwd/bwd */
 int mmvae_celeba_image_encoder_fwd(mmvae_celeba_t*, void* ws, size_t ws_bytes, const float* image, const uint8_t* mask,
                                    int training, float* out_mu_logvar, void* stream);            /* celeba/model.py:124-128 */

@@ -206,6 +206,8 @@ SIGNATURES["mmvae_mnist_text_decoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P])
 SIGNATURES["mmvae_mnist_iw_score"] = (_I, [_P, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES.update(_plan_api("celeba"))
 SIGNATURES["mmvae_celeba_step"] = (_I, [_P, C.POINTER(CelebaStepIO), _I, _I, _P])
+SIGNATURES["mmvae_celeba_bench_layer"] = (_I, [_P, _P, _SZ, C.c_char_p, _I, _P])
+SIGNATURES["mmvae_celeba_debug_offset"] = (_LL, [_P, C.c_char_p])
 SIGNATURES["mmvae_celeba_image_encoder_fwd"] = (_I, [_P, _P, _SZ, _P, _P, _I, _P, _P])
 SIGNATURES["mmvae_celeba_image_encoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P])
 SIGNATURES["mmvae_celeba_image_decoder_fwd"] = (_I, [_P, _P, _SZ, _P, _I, _P, _P])

@@ -237,6 +237,10 @@ int mmvae_celeba_step(mmvae_celeba_t* p, const mmvae_celeba_step_io* io, int tra
         return celeba_step(p, *io, training, do_backward, S(stream));
     });
 }
+int mmvae_celeba_bench_layer(mmvae_celeba_t* p, void* ws, size_t wsb, const char* layer, int iters, void* stream) {
+    return guarded([&] { return celeba_bench_layer(p, ws, wsb, layer, iters, S(stream)); });
+}
+long long mmvae_celeba_debug_offset(mmvae_celeba_t* p, const char* name) { return celeba_debug_offset(p, name); }
 int mmvae_celeba_image_encoder_fwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* image, const uint8_t* mask, int training, float* out, void* st) {
     return guarded([&] { return celeba_image_encoder_fwd(p, ws, wsb, image, mask, training, out, S(st)); });
 }

@@ -19,3 +19,7 @@ int celeba_attrs_encoder_fwd(CelebaPlan*, void* ws, size_t wsb, const float* att
 int celeba_attrs_encoder_bwd(CelebaPlan*, void* ws, size_t wsb, const float* d_out, hipStream_t);
 int celeba_attrs_decoder_fwd(CelebaPlan*, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t);
 int celeba_attrs_decoder_bwd(CelebaPlan*, void* ws, size_t wsb, const float* d_recon, const float* recon, float* dz, hipStream_t);
+// test / profiling aids: replay of one named layer launch of the step (celeba.hip named_gemm / named_wgrad) on the workspace's
+// contents, and the byte offset of a named workspace buffer (-1 if unknown)
+int celeba_bench_layer(CelebaPlan*, void* ws, size_t wsb, const char* layer, int iters, hipStream_t);
+long long celeba_debug_offset(CelebaPlan*, const char* name);

@@ -9,6 +9,8 @@
 #include "plan_base.h"
 #include "thin.h"
 #include <cstring>
+#include <map>
+#include <string>
 
 namespace {
 constexpr int IMG = 64, NPIX = 3 * IMG * IMG, NA = 18, NA_LD = 24, FEAT = 6400, HID = 1024;
@@ -179,6 +181,207 @@ int cast_pad(const float* x, int rows, int cols, bf16* out, int ld, hipStream_t 
     return mmvae_check_launch("cast_pad");
 }
 
+// ================================================================== one definition per launch
+// Every GemmParams / WgradParams of the image encoder and decoder is built here, for the step (enc_fwd / enc_bwd / dec_fwd /
+// dec_bwd) and for the replay of one layer on a test's own operands (celeba_bench_layer): a test cannot pass on a copy of the
+// parameters that drifted from the step.  l: layer index (conv[l] / convT[l]); n: row blocks -- dropout variants of the
+// classifier, BatchNorm groups (passes) of the decoder.
+enum CaGemm { CA_ENC_CONV1, CA_ENC_CONV, CA_ENC_CONV_DGRAD, CA_FC1, CA_FC2_DGRAD, CA_FC1_DGRAD, CA_UP, CA_UP_DGRAD, CA_DEC_CONVT,
+              CA_DEC_CONVT_DGRAD, CA_DEC_LAST_DGRAD };
+enum CaWgrad { CA_W_ENC_CONV1, CA_W_ENC_CONV, CA_W_FC1, CA_W_UP, CA_W_DEC_CONVT, CA_W_DEC_LAST };
+
+// mask: keep flags of classifier Dropout (CA_FC1, CA_FC2_DGRAD) or null; training: column statistics of the conv layers;
+// aux: CA_FC2_DGRAD the operand d_out [n*B][2D], CA_UP_DGRAD the fp32 result dz [n*B][D]
+GemmParams layer_gemm(CelebaPlan& P, CaGemm kind, int l, int n, int training = 1, const uint8_t* mask = nullptr, const void* aux = nullptr) {
+    CelebaPlan::W& w = P.w;
+    const int B = P.B, rows = n * B;
+    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
+    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
+    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
+    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
+    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
+    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
+    switch (kind) {
+    case CA_ENC_CONV1: {   // conv1 + Swish (no BatchNorm): raw and activated outputs
+        GatherPlan pl = dense_plan(B * 1024, 48, 48, 32);
+        GemmParams g = gemm_of(P, pl, P.conv[0].pk_fwd, 1, B * 1024);
+        g.c.A = w.patches1; g.out_bf = w.r1; g.ldo = 32; g.out_act_bf = w.a1; g.e_act = ACT_SWISH;
+        return g;
+    }
+    case CA_ENC_CONV: {
+        const ConvL& L = P.conv[l];
+        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, 1, B, L.pk_fwd_f);
+        g.c.A = a[l - 1];
+        g.out_bf = r[l]; g.ldo = L.g.Cout;
+        g.colstats = training ? w.st_e[l - 1] : nullptr;
+        return g;
+    }
+    case CA_ENC_CONV_DGRAD: {
+        const ConvL& L = P.conv[l];
+        GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
+        d.c.A = dr[l]; d.out_bf = dr[l - 1]; d.ldo = L.g.Cin;
+        d.d_r = r[l - 1]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
+        if (l > 1) { d.d_affine = w.aff_e[l - 2]; d.d_meanrstd = w.mr_e[l - 2]; d.d_red = w.red_e[l - 2]; }
+        return d;
+    }
+    case CA_FC1: {   // classifier.0 over the NHWC 5x5x256 map (shared by the variants) + Swish + Dropout
+        GatherPlan pl = plan_fwdform(5, 5, 1, 1, 256, 5, 5, 1, 0, HID, 1, rows);
+        GemmParams g = gemm_of(P, pl, &P.fc1.pk_fwd, 1, rows);
+        g.c.A = w.a4; g.c.a_bcast_n = B;
+        g.bias = P.buf.params + P.fc1.b_off; g.out_bf = w.y1; g.ldo = HID;
+        g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (mask) { g.e_mask = mask; g.e_mask_scale = 1.f / (1.f - DROP_P); }
+        return g;
+    }
+    case CA_FC2_DGRAD: {   // classifier.3
+        GatherPlan pd = dense_plan(rows, P.fc2.ldo, P.fc2.ldo, HID);
+        GemmParams d = gemm_of(P, pd, &P.fc2.pk_dgrad, 1, rows);
+        d.c.A = (const bf16*)aux; d.out_bf = w.dy1; d.ldo = HID;
+        d.d_r = w.y1; d.d_ld = HID; d.d_act = ACT_SWISH; if (mask) { d.d_mask = mask; d.d_mask_scale = 1.f / (1.f - DROP_P); }
+        d.d_colsum = P.buf.grads + P.fc1.b_off;
+        return d;
+    }
+    case CA_FC1_DGRAD: {   // classifier.0: the input gradient is one dense GEMM over NHWC columns
+        GatherPlan pd = dense_plan(rows, HID, HID, FEAT);
+        GemmParams d = gemm_of(P, pd, &P.fc1_dgrad, 1, rows);
+        d.c.A = w.dy1; d.out_bf = w.db4; d.ldo = FEAT;
+        d.d_r = w.r4; d.d_ld = FEAT; d.d_bcast_n = B; d.d_act = ACT_SWISH; d.d_cmod = 256;
+        d.d_affine = w.aff_e[2]; d.d_meanrstd = w.mr_e[2]; d.d_red = w.red_e[2];
+        return d;
+    }
+    case CA_UP: {
+        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
+        GemmParams g = gemm_of(P, pl, &P.up.pk_fwd, 1, rows);
+        g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = FEAT; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
+        return g;
+    }
+    case CA_UP_DGRAD: {
+        GatherPlan pd = dense_plan(rows, FEAT, FEAT, P.D);
+        GemmParams d = gemm_of(P, pd, &P.up.pk_dgrad, 1, rows);
+        d.c.A = w.du; d.out_f = (float*)aux; d.ldo = P.D;
+        return d;
+    }
+    case CA_DEC_CONVT: {
+        const ConvL& L = P.convT[l];
+        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, n, B, L.pk_fwd_f);
+        g.c.A = aq[l];
+        g.out_bf = q[l + 1]; g.ldo = L.g.Cout;
+        g.colstats = training ? w.st_d[l] : nullptr;
+        return g;
+    }
+    case CA_DEC_CONVT_DGRAD: {
+        const ConvL& L = P.convT[l];
+        GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, n, B, L.pk_dgrad_f);
+        d.c.A = dq[l + 1]; d.out_bf = dq[l]; d.ldo = L.g.Cin;
+        d.d_r = q[l]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
+        if (l > 0) { d.d_affine = w.aff_d[l - 1]; d.d_meanrstd = w.mr_d[l - 1]; d.d_red = w.red_d[l - 1]; }
+        return d;
+    }
+    case CA_DEC_LAST_DGRAD: {   // input gradient = dense GEMM patches x W with d-Swish + BatchNorm-backward sums in the epilogue
+        GatherPlan pd = dense_plan(B * 1024, 48, 48, 32);
+        GemmParams d = gemm_of(P, pd, P.convT[3].pk_dgrad, n, B * 1024);
+        d.c.A = w.patches4; d.out_bf = w.d3; d.ldo = 32;
+        d.d_r = w.q3; d.d_ld = 32; d.d_act = ACT_SWISH; d.d_affine = w.aff_d[2]; d.d_meanrstd = w.mr_d[2]; d.d_red = w.red_d[2];
+        return d;
+    }
+    }
+    return GemmParams{};
+}
+
+WgradParams layer_wgrad(CelebaPlan& P, CaWgrad kind, int l, int n) {
+    CelebaPlan::W& w = P.w;
+    const int B = P.B, rows = n * B;
+    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
+    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
+    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
+    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
+    switch (kind) {
+    case CA_W_ENC_CONV1: {   // conv1 wgrad over the im2col patches
+        GatherPlan pl = dense_plan(B * 1024, 48, 48, 32);
+        WgradParams g = wgrad_of(P, pl, P.conv[0].gk, 1, B * 1024);
+        g.c.A = w.patches1; g.P = w.d1e; g.ldp = 32;
+        return g;
+    }
+    case CA_W_ENC_CONV: {
+        const ConvL& L = P.conv[l];
+        WgradParams g = wgrad_of(P, L.fwd, L.gk, 1, B);
+        g.c.A = a[l - 1]; g.P = dr[l]; g.ldp = L.g.Cout;
+        return g;
+    }
+    case CA_W_FC1: {   // classifier.0: wgrad gathers the shared 5x5x256 map
+        GatherPlan pl = plan_fwdform(5, 5, 1, 1, 256, 5, 5, 1, 0, HID, 1, rows);
+        WgradParams g = wgrad_of(P, pl, &P.fc1.gk, 1, rows);
+        g.c.A = w.a4; g.c.a_bcast_n = B;
+        g.P = w.dy1; g.ldp = HID;
+        return g;
+    }
+    case CA_W_UP: {   // upsample Linear: weight (+ folded bias) gradient
+        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
+        WgradParams g = wgrad_of(P, pl, &P.up.gk, 1, rows);
+        g.c.A = w.z_bf; g.P = w.du; g.ldp = FEAT;
+        return g;
+    }
+    case CA_W_DEC_CONVT:
+        return convT_wgrad(P, P.convT[l], n, B, aq[l], dq[l + 1]);
+    case CA_W_DEC_LAST: {   // last transposed conv (32 -> 3) through the im2col patches of dlogit (K = 16 taps x 3)
+        GatherPlan pl = plan_fwdform(1, 1, 32, 32, 48, 1, 1, 1, 0, 32, n, B);   // rows (n, iy, ix), dense K=48
+        WgradParams g = wgrad_of(P, pl, P.convT[3].gk, n, B);
+        g.c.A = w.patches4; g.c.AH = 32; g.c.AW = 32; g.c.sy = g.c.sx = 1;
+        g.P = w.aq3; g.ldp = 32;
+        return g;
+    }
+    }
+    return WgradParams{};
+}
+
+// Staging transforms of the fused step (gemm.h GatherTransform; B % 4 == 0, image-resident kernels only): `tr` is read by the
+// launcher and must outlive the launch.
+// kind 1: forward layer l stages Swish(BatchNorm(raw output of the layer below)) itself, writes that layer's tables, updates its
+// running statistics and leaves the activated tensor behind for the weight gradient
+void stage_fwd_enc(CelebaPlan& P, int l, GemmParams& g, GatherTransform& tr, int bn_updates, int training) {
+    CelebaPlan::W& w = P.w;
+    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
+    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
+    const ConvL& Lp = P.conv[l - 1];
+    tr.kind = 1;
+    tr.fin = bn_fin_args(P, P.bn[Lp.bn], P.B * Lp.g.OH * Lp.g.OW, 1, w.st_e[l - 2], bn_updates, w.aff_e[l - 2], w.mr_e[l - 2], training);
+    tr.out = a[l - 1];
+    g.c.A = r[l - 1]; g.tr = &tr;
+}
+void stage_fwd_dec(CelebaPlan& P, int l, int groups, GemmParams& g, GatherTransform& tr, int training) {
+    CelebaPlan::W& w = P.w;
+    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
+    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
+    const ConvL& Lp = P.convT[l - 1];
+    tr.kind = 1;
+    tr.fin = bn_fin_args(P, P.bn[Lp.bn], P.B * Lp.g.OH * Lp.g.OW, groups, w.st_d[l - 1], 1, w.aff_d[l - 1], w.mr_d[l - 1], training);
+    tr.out = aq[l];
+    g.c.A = q[l]; g.tr = &tr;
+}
+// kind 2: the data gradient of layer l applies the BatchNorm backward of the layer's own BatchNorm to db while staging it and
+// writes dr back IN PLACE (a workgroup owns its images: each vector is read, then overwritten, by the same thread)
+void stage_bwd_enc(CelebaPlan& P, int l, GemmParams& d, GatherTransform& tr) {
+    CelebaPlan::W& w = P.w;
+    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
+    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
+    const ConvL& L = P.conv[l];
+    const BnL& b = P.bn[L.bn];
+    tr.kind = 2; tr.r = r[l]; tr.red = w.red_e[l - 1]; tr.mr = w.mr_e[l - 1]; tr.gamma = P.buf.params + b.w_off;
+    tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off;
+    tr.inv_cnt = 1.f / (float)(P.B * L.g.OH * L.g.OW); tr.groups = 1; tr.out = dr[l];
+    d.tr = &tr;
+}
+void stage_bwd_dec(CelebaPlan& P, int l, int groups, GemmParams& d, GatherTransform& tr) {
+    CelebaPlan::W& w = P.w;
+    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
+    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
+    const ConvL& L = P.convT[l];
+    const BnL& b = P.bn[L.bn];
+    tr.kind = 2; tr.r = q[l + 1]; tr.red = w.red_d[l]; tr.mr = w.mr_d[l]; tr.gamma = P.buf.params + b.w_off;
+    tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off;
+    tr.inv_cnt = 1.f / (float)(P.B * L.g.OH * L.g.OW); tr.groups = groups; tr.out = dq[l + 1];
+    d.tr = &tr;
+}
+
 // ================================================================== image encoder (celeba/model.py:124-128)
 // fuse (the fused step, B % 4 == 0): the layers that run on the image-resident kernels (convres.hip) stage BatchNorm + Swish /
 // the BatchNorm backward of their gathered operand themselves (GatherTransform) and leave the staged tensor behind for the
@@ -188,28 +391,14 @@ int enc_fwd(CelebaPlan& P, const float* image, int variants, const uint8_t* m1, 
     CelebaPlan::W& w = P.w;
     const int B = P.B;
     MMVAE_TRY(launch_im2col_small(image, B, 3, IMG, IMG, 4, 4, 2, 1, 32, 32, w.patches1, 48, s));
-    {   // conv1 + Swish (no BatchNorm): raw and activated outputs
-        GatherPlan pl = dense_plan(B * 1024, 48, 48, 32);
-        GemmParams g = gemm_of(P, pl, P.conv[0].pk_fwd, 1, B * 1024);
-        g.c.A = w.patches1; g.out_bf = w.r1; g.ldo = 32; g.out_act_bf = w.a1; g.e_act = ACT_SWISH;
-        MMVAE_TRY(launch_gemm_gather(g, s));
-    }
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_ENC_CONV1, 0, 1), s));
     bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
     bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
     for (int l = 1; l < 4; ++l) {
         const ConvL& L = P.conv[l];
-        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, 1, B, L.pk_fwd_f);
-        g.c.A = a[l - 1];
-        g.out_bf = r[l]; g.ldo = L.g.Cout;
-        g.colstats = training ? w.st_e[l - 1] : nullptr;
+        GemmParams g = layer_gemm(P, CA_ENC_CONV, l, 1, training);
         GatherTransform tr{};
-        if (fuse && l == 2) {          // features.5 stages a2 = Swish(BatchNorm(r2)) itself
-            const int prows = B * P.conv[1].g.OH * P.conv[1].g.OW;
-            tr.kind = 1;
-            tr.fin = bn_fin_args(P, P.bn[P.conv[1].bn], prows, 1, w.st_e[0], bn_updates, w.aff_e[0], w.mr_e[0], training);
-            tr.out = a[1];
-            g.c.A = r[1]; g.tr = &tr;
-        }
+        if (fuse && l == 2) stage_fwd_enc(P, l, g, tr, bn_updates, training);     // features.5 stages a2 = Swish(BatchNorm(r2)) itself
         MMVAE_TRY(launch_gemm_gather(g, s));
         const int rows = B * L.g.OH * L.g.OW;
         if (fuse && l == 1) continue;
@@ -217,14 +406,7 @@ int enc_fwd(CelebaPlan& P, const float* image, int variants, const uint8_t* m1, 
     }
     const int rows = variants * B;
     const bool drop = training && dropout;
-    {   // classifier.0 over the NHWC 5x5x256 map (shared by the variants) + Swish + Dropout
-        GatherPlan pl = plan_fwdform(5, 5, 1, 1, 256, 5, 5, 1, 0, HID, 1, rows);
-        GemmParams g = gemm_of(P, pl, &P.fc1.pk_fwd, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.bias = P.buf.params + P.fc1.b_off; g.out_bf = w.y1; g.ldo = HID;
-        g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (drop) { g.e_mask = m1; g.e_mask_scale = 1.f / (1.f - DROP_P); }
-        MMVAE_TRY(launch_gemm_gather(g, s));
-    }
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_FC1, 0, variants, training, drop ? m1 : nullptr), s));
     return mlp_fwd(P, P.fc2, w.ay1, rows, 1, nullptr, out, nullptr, s);
 }
 
@@ -234,28 +416,13 @@ int enc_bwd(CelebaPlan& P, const bf16* d_out, int variants, const uint8_t* m1, i
     const int B = P.B, rows = variants * B;
     {   // classifier.3
         MMVAE_TRY(mlp_wgrad(P, P.fc2, d_out, w.ay1, rows, s));
-        GatherPlan pd = dense_plan(rows, P.fc2.ldo, P.fc2.ldo, HID);
-        GemmParams d = gemm_of(P, pd, &P.fc2.pk_dgrad, 1, rows);
-        d.c.A = d_out; d.out_bf = w.dy1; d.ldo = HID;
-        d.d_r = w.y1; d.d_ld = HID; d.d_act = ACT_SWISH; if (dropout) { d.d_mask = m1; d.d_mask_scale = 1.f / (1.f - DROP_P); }
-        d.d_colsum = P.buf.grads + P.fc1.b_off;
-        MMVAE_TRY(launch_gemm_gather(d, s));
+        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_FC2_DGRAD, 0, variants, 1, dropout ? m1 : nullptr, d_out), s));
     }
     {   // classifier.0: wgrad gathers the shared 5x5x256 map; the input gradient is one dense GEMM over NHWC columns
-        GatherPlan pl = plan_fwdform(5, 5, 1, 1, 256, 5, 5, 1, 0, HID, 1, rows);
-        WgradParams g = wgrad_of(P, pl, &P.fc1.gk, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.P = w.dy1; g.ldp = HID;
-        MMVAE_TRY(wgrad_async(P, g, s));
-        GatherPlan pd = dense_plan(rows, HID, HID, FEAT);
-        GemmParams d = gemm_of(P, pd, &P.fc1_dgrad, 1, rows);
-        d.c.A = w.dy1; d.out_bf = w.db4; d.ldo = FEAT;
-        d.d_r = w.r4; d.d_ld = FEAT; d.d_bcast_n = B; d.d_act = ACT_SWISH; d.d_cmod = 256;
-        d.d_affine = w.aff_e[2]; d.d_meanrstd = w.mr_e[2]; d.d_red = w.red_e[2];
-        MMVAE_TRY(launch_gemm_gather(d, s));
+        MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CA_W_FC1, 0, variants), s));
+        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_FC1_DGRAD, 0, variants), s));
     }
     bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
     bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
     for (int l = 3; l >= 1; --l) {
         const ConvL& L = P.conv[l];
@@ -272,32 +439,17 @@ int enc_bwd(CelebaPlan& P, const bf16* d_out, int variants, const uint8_t* m1, i
         // gradient follows it
         const bool fl = fuse && l <= 2;
         if (!fl) MMVAE_TRY(launch_bn_bwd_apply(x, s));
-        WgradParams gw = wgrad_of(P, L.fwd, L.gk, 1, B);
-        gw.c.A = a[l - 1]; gw.P = dr[l]; gw.ldp = L.g.Cout;
+        WgradParams gw = layer_wgrad(P, CA_W_ENC_CONV, l, 1);
         if (!fl) MMVAE_TRY(wgrad_async(P, gw, s));
         {
-            GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
-            d.c.A = dr[l]; d.out_bf = dr[l - 1]; d.ldo = L.g.Cin;
-            d.d_r = r[l - 1]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-            if (l > 1) { d.d_affine = w.aff_e[l - 2]; d.d_meanrstd = w.mr_e[l - 2]; d.d_red = w.red_e[l - 2]; }
+            GemmParams d = layer_gemm(P, CA_ENC_CONV_DGRAD, l, 1);
             GatherTransform tr{};
-            if (fl) {
-                tr.kind = 2; tr.r = r[l]; tr.red = w.red_e[l - 1]; tr.mr = w.mr_e[l - 1]; tr.gamma = P.buf.params + b.w_off;
-                tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off;
-                tr.inv_cnt = 1.f / (float)(B * pix); tr.groups = 1; tr.out = dr[l];
-                d.tr = &tr;
-            }
+            if (fl) stage_bwd_enc(P, l, d, tr);
             MMVAE_TRY(launch_gemm_gather(d, s));
         }
         if (fl) MMVAE_TRY(wgrad_async(P, gw, s));
     }
-    {   // conv1 wgrad over the im2col patches
-        GatherPlan pl = dense_plan(B * 1024, 48, 48, 32);
-        WgradParams g = wgrad_of(P, pl, P.conv[0].gk, 1, B * 1024);
-        g.c.A = w.patches1; g.P = w.d1e; g.ldp = 32;
-        MMVAE_TRY(wgrad_async(P, g, s));
-    }
-    return MMVAE_OK;
+    return wgrad_async(P, layer_wgrad(P, CA_W_ENC_CONV1, 0, 1), s);
 }
 
 // ================================================================== image decoder (celeba/model.py:157-161)
@@ -307,29 +459,15 @@ int enc_bwd(CelebaPlan& P, const bf16* d_out, int variants, const uint8_t* m1, i
 int dec_fwd(CelebaPlan& P, int groups, int training, ConvTLastFwdArgs* last, hipStream_t s, int last_groups = -1, int fused_bwd_groups = -1,
             bool fuse = false) {
     CelebaPlan::W& w = P.w;
-    const int B = P.B, rows = groups * B;
-    {
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
-        GemmParams g = gemm_of(P, pl, &P.up.pk_fwd, 1, rows);
-        g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = FEAT; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
-        MMVAE_TRY(launch_gemm_gather(g, s));
-    }
+    const int B = P.B;
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_UP, 0, groups), s));
     bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
     bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
     for (int l = 0; l < 3; ++l) {
         const ConvL& L = P.convT[l];
-        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, groups, B, L.pk_fwd_f);
-        g.c.A = aq[l];
-        g.out_bf = q[l + 1]; g.ldo = L.g.Cout;
-        g.colstats = training ? w.st_d[l] : nullptr;
+        GemmParams g = layer_gemm(P, CA_DEC_CONVT, l, groups, training);
         GatherTransform tr{};
-        if (fuse && l >= 1) {          // hallucinate.3 / .6 stage Swish(BatchNorm(q[l])) themselves and leave aq[l] behind
-            const ConvL& Lp = P.convT[l - 1];
-            tr.kind = 1;
-            tr.fin = bn_fin_args(P, P.bn[Lp.bn], B * Lp.g.OH * Lp.g.OW, groups, w.st_d[l - 1], 1, w.aff_d[l - 1], w.mr_d[l - 1], training);
-            tr.out = aq[l];
-            g.c.A = q[l]; g.tr = &tr;
-        }
+        if (fuse && l >= 1) stage_fwd_dec(P, l, groups, g, tr, training);     // hallucinate.3 / .6 stage Swish(BatchNorm(q[l])) themselves and leave aq[l] behind
         MMVAE_TRY(launch_gemm_gather(g, s));
         const int rpg = B * L.g.OH * L.g.OW;
         if (l == 2 && fused_bwd_groups >= 0) continue;
@@ -371,7 +509,6 @@ int dec_bwd(CelebaPlan& P, const float* dlogit, int groups, float* dz, hipStream
     CelebaPlan::W& w = P.w;
     const int B = P.B, rows = groups * B;
     bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
     bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
     if (last_fused && P.wgrad_forked && !mmvae_serial()) {
         // d3, the BatchNorm-backward sums and the per-image weight-gradient partials of the last layer came out of the fused tail
@@ -381,20 +518,9 @@ int dec_bwd(CelebaPlan& P, const float* dlogit, int groups, float* dz, hipStream
     }
     if (!last_fused) {   // last transposed conv (32 -> 3): both gradients go through the im2col patches of dlogit (K = 16 taps x 3):
         // input gradient = dense GEMM patches x W with d-Swish + BatchNorm-backward sums in the epilogue
-        const ConvL& L = P.convT[3];
         MMVAE_TRY(launch_im2col_small(dlogit, rows, 3, IMG, IMG, 4, 4, 2, 1, 32, 32, w.patches4, 48, s));
-        {
-            GatherPlan pd = dense_plan(B * 1024, 48, 48, 32);
-            GemmParams d = gemm_of(P, pd, L.pk_dgrad, groups, B * 1024);
-            d.c.A = w.patches4; d.out_bf = w.d3; d.ldo = 32;
-            d.d_r = w.q3; d.d_ld = 32; d.d_act = ACT_SWISH; d.d_affine = w.aff_d[2]; d.d_meanrstd = w.mr_d[2]; d.d_red = w.red_d[2];
-            MMVAE_TRY(launch_gemm_gather(d, s));
-        }
-        GatherPlan pl = plan_fwdform(1, 1, 32, 32, 48, 1, 1, 1, 0, 32, groups, B);   // rows (n, iy, ix), dense K=48
-        WgradParams g = wgrad_of(P, pl, L.gk, groups, B);
-        g.c.A = w.patches4; g.c.AH = 32; g.c.AW = 32; g.c.sy = g.c.sx = 1;
-        g.P = w.aq3; g.ldp = 32;
-        MMVAE_TRY(wgrad_async(P, g, s));
+        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_DEC_LAST_DGRAD, 3, groups), s));
+        MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CA_W_DEC_LAST, 3, groups), s));
     }
     for (int l = 2; l >= 0; --l) {
         const ConvL& L = P.convT[l];
@@ -407,35 +533,19 @@ int dec_bwd(CelebaPlan& P, const float* dlogit, int groups, float* dz, hipStream
         x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
         const bool fl = fuse && l >= 1;       // hallucinate.6 / .3: BatchNorm backward inside the data gradient's staging, dr in place (enc_bwd)
         if (!fl) MMVAE_TRY(launch_bn_bwd_apply(x, s));
-        WgradParams gw = convT_wgrad(P, L, groups, B, aq[l], dq[l + 1]);
+        WgradParams gw = layer_wgrad(P, CA_W_DEC_CONVT, l, groups);
         if (!fl) MMVAE_TRY(wgrad_async(P, gw, s));
         {
-            GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, groups, B, L.pk_dgrad_f);
-            d.c.A = dq[l + 1]; d.out_bf = dq[l]; d.ldo = L.g.Cin;
-            d.d_r = q[l]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-            if (l > 0) { d.d_affine = w.aff_d[l - 1]; d.d_meanrstd = w.mr_d[l - 1]; d.d_red = w.red_d[l - 1]; }
+            GemmParams d = layer_gemm(P, CA_DEC_CONVT_DGRAD, l, groups);
             GatherTransform tr{};
-            if (fl) {
-                tr.kind = 2; tr.r = q[l + 1]; tr.red = w.red_d[l]; tr.mr = w.mr_d[l]; tr.gamma = P.buf.params + b.w_off;
-                tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off;
-                tr.inv_cnt = 1.f / (float)(B * pix); tr.groups = groups; tr.out = dq[l + 1];
-                d.tr = &tr;
-            }
+            if (fl) stage_bwd_dec(P, l, groups, d, tr);
             MMVAE_TRY(launch_gemm_gather(d, s));
         }
         if (fl) MMVAE_TRY(wgrad_async(P, gw, s));
     }
-    {   // upsample Linear: weight (+ folded bias) gradient and dz
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
-        WgradParams g = wgrad_of(P, pl, &P.up.gk, 1, rows);
-        g.c.A = w.z_bf; g.P = w.du; g.ldp = FEAT;
-        MMVAE_TRY(wgrad_async(P, g, s));
-        GatherPlan pd = dense_plan(rows, FEAT, FEAT, P.D);
-        GemmParams d = gemm_of(P, pd, &P.up.pk_dgrad, 1, rows);
-        d.c.A = w.du; d.out_f = dz; d.ldo = P.D;
-        MMVAE_TRY(launch_gemm_gather(d, s));
-    }
-    return MMVAE_OK;
+    // upsample Linear: weight (+ folded bias) gradient and dz
+    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CA_W_UP, 0, groups), s));
+    return launch_gemm_gather(layer_gemm(P, CA_UP_DGRAD, 0, groups, 1, nullptr, dz), s);
 }
 
 // ================================================================== attribute MLPs (celeba/model.py:164-196)
@@ -670,4 +780,96 @@ int celeba_attrs_decoder_bwd(CelebaPlan* P, void* ws, size_t wsb, const float* d
     MMVAE_TRY(mmvae_check_launch("sigmoid_bwd"));
     MMVAE_TRY(att_dec_bwd(*P, w.dalogit, 1, dz, s));
     return plan_unpack(*P, s, true);
+}
+
+// ---------------------------------------------------------------- test / profiling aid: replay one layer of the step
+// The launches of layer_gemm / layer_wgrad under names: <layer>, <layer>_dgrad, <layer>_wgrad.  The classifier runs its 2 dropout
+// variants, the decoder 3 passes forward and 3 backward (the default step: every lambda_x > 0).  Knob "celeba_layer_mask" (0): the
+// keep flags in W::m1 take part in fc1 / fc2_dgrad as in a step with classifier dropout.  fc2_dgrad reads d_encout and, as in the
+// step, adds its column sums to the bias gradient of classifier.0 in the flat gradients; up_dgrad writes dz into dz_img.
+// <layer>_staged / <layer>_dgrad_staged: the forms the default step runs at B % 4 == 0 (stage_fwd_* / stage_bwd_*; `tr` is theirs),
+// with the running-statistics updates of the default step (2 encoder variants, 1 per decoder pass)
+static bool named_gemm(CelebaPlan& P, const std::string& name, GemmParams& g, GatherTransform& tr) {
+    CelebaPlan::W& w = P.w;
+    const uint8_t* mask = mmvae_knob("celeba_layer_mask", 0) ? w.m1 : nullptr;
+    if (name == "enc_conv1") { g = layer_gemm(P, CA_ENC_CONV1, 0, 1); return true; }
+    for (int l = 1; l < 4; ++l) {
+        const std::string n = "enc_conv" + std::to_string(l + 1);
+        if (name == n) { g = layer_gemm(P, CA_ENC_CONV, l, 1); return true; }
+        if (name == n + "_dgrad") { g = layer_gemm(P, CA_ENC_CONV_DGRAD, l, 1); return true; }
+    }
+    if (name == "fc1") { g = layer_gemm(P, CA_FC1, 0, 2, 1, mask); return true; }
+    if (name == "fc1_dgrad") { g = layer_gemm(P, CA_FC1_DGRAD, 0, 2); return true; }
+    if (name == "fc2_dgrad") { g = layer_gemm(P, CA_FC2_DGRAD, 0, 2, 1, mask, w.d_encout); return true; }
+    if (name == "up") { g = layer_gemm(P, CA_UP, 0, 3); return true; }
+    if (name == "up_dgrad") { g = layer_gemm(P, CA_UP_DGRAD, 0, 3, 1, nullptr, w.dz_img); return true; }
+    for (int l = 0; l < 3; ++l) {
+        const std::string n = "dec_convT" + std::to_string(l + 1);
+        if (name == n) { g = layer_gemm(P, CA_DEC_CONVT, l, 3); return true; }
+        if (name == n + "_dgrad") { g = layer_gemm(P, CA_DEC_CONVT_DGRAD, l, 3); return true; }
+    }
+    if (name == "dec_last_dgrad_gemm") { g = layer_gemm(P, CA_DEC_LAST_DGRAD, 3, 3); return true; }
+    if (name == "enc_conv3_staged") { g = layer_gemm(P, CA_ENC_CONV, 2, 1); stage_fwd_enc(P, 2, g, tr, 2, 1); return true; }
+    for (int l = 1; l < 3; ++l) {
+        const std::string e = "enc_conv" + std::to_string(l + 1), d = "dec_convT" + std::to_string(l + 1);
+        if (name == d + "_staged") { g = layer_gemm(P, CA_DEC_CONVT, l, 3); stage_fwd_dec(P, l, 3, g, tr, 1); return true; }
+        if (name == e + "_dgrad_staged") { g = layer_gemm(P, CA_ENC_CONV_DGRAD, l, 1); stage_bwd_enc(P, l, g, tr); return true; }
+        if (name == d + "_dgrad_staged") { g = layer_gemm(P, CA_DEC_CONVT_DGRAD, l, 3); stage_bwd_dec(P, l, 3, g, tr); return true; }
+    }
+    return false;
+}
+static bool named_wgrad(CelebaPlan& P, const std::string& name, WgradParams& g) {
+    if (name == "enc_conv1_wgrad") { g = layer_wgrad(P, CA_W_ENC_CONV1, 0, 1); return true; }
+    for (int l = 1; l < 4; ++l)
+        if (name == "enc_conv" + std::to_string(l + 1) + "_wgrad") { g = layer_wgrad(P, CA_W_ENC_CONV, l, 1); return true; }
+    if (name == "fc1_wgrad") { g = layer_wgrad(P, CA_W_FC1, 0, 2); return true; }
+    if (name == "up_wgrad") { g = layer_wgrad(P, CA_W_UP, 0, 3); return true; }
+    for (int l = 0; l < 3; ++l)
+        if (name == "dec_convT" + std::to_string(l + 1) + "_wgrad") { g = layer_wgrad(P, CA_W_DEC_CONVT, l, 3); return true; }
+    if (name == "dec_last_wgrad") { g = layer_wgrad(P, CA_W_DEC_LAST, 3, 3); return true; }
+    return false;
+}
+int celeba_bench_layer(CelebaPlan* P, void* ws, size_t wsb, const char* layer, int iters, hipStream_t s) {
+    MMVAE_REQUIRE(P && layer, "mmvae_celeba_bench_layer: null argument");
+    MMVAE_TRY(use_ws(P, ws, wsb, false));
+    WgradParams wg{};
+    if (named_wgrad(*P, layer, wg)) {            // kernel + its share of the slab reduction, as in the step
+        for (int i = 0; i < iters; ++i) {
+            P->slab.reset(P->w.slab, P->w.slab_floats);
+            MMVAE_TRY(launch_wgrad(wg, s, &P->slab));
+            MMVAE_TRY(launch_wgrad_reduce(&P->slab, s));
+        }
+        return MMVAE_OK;
+    }
+    GemmParams g{};
+    GatherTransform tr{};
+    MMVAE_REQUIRE(named_gemm(*P, layer, g, tr), "mmvae_celeba_bench_layer: unknown layer '%s'", layer);
+    for (int i = 0; i < iters; ++i) MMVAE_TRY(launch_gemm_gather(g, s));
+    return MMVAE_OK;
+}
+// byte offset of a named workspace buffer of the fused step's carving (3 passes), -1 if unknown
+long long celeba_debug_offset(CelebaPlan* P, const char* name) {
+    if (!P || !name) return -1;
+    Workspace ws((void*)0x1000, (size_t)1 << 40);      // (every call that works in a workspace carves its own again: plan_use_ws)
+    P->carve_passes = 3;
+    carve(*P, ws);
+    CelebaPlan::W& w = P->w;
+    const std::map<std::string, const void*> m = {
+        {"patches1", w.patches1}, {"r1", w.r1}, {"r2", w.r2}, {"r3", w.r3}, {"r4", w.r4},
+        {"a1", w.a1}, {"a2", w.a2}, {"a3", w.a3}, {"a4", w.a4}, {"y1", w.y1}, {"ay1", w.ay1}, {"encout", w.encout}, {"m1", w.m1},
+        {"z_bf", w.z_bf}, {"z_f32", w.z_f32}, {"u", w.u}, {"au", w.au}, {"q1", w.q1}, {"q2", w.q2}, {"q3", w.q3},
+        {"aq1", w.aq1}, {"aq2", w.aq2}, {"aq3", w.aq3}, {"dlogit", w.dlogit}, {"patches4", w.patches4},
+        {"d3", w.d3}, {"d2", w.d2}, {"d1", w.d1}, {"du", w.du}, {"dz_img", w.dz_img}, {"dz_att", w.dz_att},
+        {"d_encout", w.d_encout}, {"dy1", w.dy1}, {"db4", w.db4}, {"dr4", w.dr4}, {"d3e", w.d3e}, {"d2e", w.d2e}, {"d1e", w.d1e},
+        {"tmp_f32", w.tmp_f32}, {"slab", w.slab},
+        {"st_e0", w.st_e[0]}, {"st_e1", w.st_e[1]}, {"st_e2", w.st_e[2]}, {"st_d0", w.st_d[0]}, {"st_d1", w.st_d[1]}, {"st_d2", w.st_d[2]},
+        {"red_e0", w.red_e[0]}, {"red_e1", w.red_e[1]}, {"red_e2", w.red_e[2]},
+        {"red_d0", w.red_d[0]}, {"red_d1", w.red_d[1]}, {"red_d2", w.red_d[2]},
+        {"aff_e0", w.aff_e[0]}, {"aff_e1", w.aff_e[1]}, {"aff_e2", w.aff_e[2]},
+        {"aff_d0", w.aff_d[0]}, {"aff_d1", w.aff_d[1]}, {"aff_d2", w.aff_d[2]},
+        {"mr_e0", w.mr_e[0]}, {"mr_e1", w.mr_e[1]}, {"mr_e2", w.mr_e[2]}, {"mr_d0", w.mr_d[0]}, {"mr_d1", w.mr_d[1]}, {"mr_d2", w.mr_d[2]},
+    };
+    auto it = m.find(name);
+    if (it == m.end()) return -1;
+    return (long long)((const char*)it->second - (const char*)0x1000);
 }

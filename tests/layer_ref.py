@@ -1,7 +1,7 @@
-"""Layer-level reference and GPU harness of the MultiMNIST conv / transposed-conv kernels (tests/test_gpu_layers.py,
-tests/test_cpu_layer_ref.py).
+"""Layer-level reference and GPU harness of the MultiMNIST and CelebA conv / transposed-conv kernels (tests/test_gpu_layers.py,
+tests/test_gpu_celeba_layers.py, tests/test_cpu_layer_ref.py).
 
-One layer of the step is replayed through mmvae_mm_bench_layer on operands the test wrote itself and compared with a float64
+One layer of the step is replayed through mmvae_<family>_bench_layer on operands the test wrote itself and compared with a float64
 reference made here with torch.nn.functional.conv2d / conv_transpose2d and torch.autograd -- never with another engine kernel.
 Operands are ternary {-1, 0, +1}: bf16 holds them exactly, every product is an integer and every fp32 partial sum stays below
 2^24, so the result depends neither on the accumulation order nor on the rounding of the bf16 store and the comparison is
@@ -10,6 +10,7 @@ d_r / d_affine / d_meanrstd / d_red) is restated in float64 and gated by the pre
 
 The top half of this module needs no GPU (geometry table, operand generator, references); LayerHarness needs the MI355X."""
 import ctypes
+import os
 from collections import namedtuple
 
 import torch
@@ -44,6 +45,32 @@ LAYERS = {
 W_DENSITY = 0.25
 G_DENSITY = 0.5
 
+# CelebA: celeba/model.py:101-150 as restated in csrc/celeba.hip build() -- 64x64 images, encoder 32 -> 64 (32x32 -> 16x16),
+# 64 -> 128 (16 -> 8), 128 -> 256 (k4 s1 p0, 8 -> 5); decoder 256 -> 128 (k4 s1 p0, 5 -> 8), 128 -> 64 (8 -> 16), 64 -> 32 (16 -> 32).
+# The replayed decoder layers run 3 BatchNorm groups forward and backward (the default step: every image term has a gradient).
+# Activation densities: the stride-1 transposed layer sums up to 16 taps x 256 channels into one output pixel (every other layer
+# at most 4 x 128 / 16 x 128 with stride 2 / forward form) and the 32x32 output of hallucinate.6 holds 262144 elements per channel
+# and group at B = 256: both take density 1/4 (tests/test_cpu_layer_ref.py asserts the regime for every batch and seed used).
+BATCHES_CELEBA = (3, 4, 6, 8, 256)
+LAYERS_CELEBA = {
+    "enc_conv2": Layer("image_encoder.features.2.weight", False, 32, 64, 4, 2, 1, 32, 16, 1, 1,
+                       "a1", "r2", "st_e0", "d2e", "d1e", "r1", None, None, None, 0.5),
+    "enc_conv3": Layer("image_encoder.features.5.weight", False, 64, 128, 4, 2, 1, 16, 8, 1, 1,
+                       "a2", "r3", "st_e1", "d3e", "d2e", "r2", "aff_e0", "mr_e0", "red_e0", 0.5),
+    "enc_conv4": Layer("image_encoder.features.8.weight", False, 128, 256, 4, 1, 0, 8, 5, 1, 1,
+                       "a3", "r4", "st_e2", "dr4", "d3e", "r3", "aff_e1", "mr_e1", "red_e1", 0.5),
+    "dec_convT1": Layer("image_decoder.hallucinate.0.weight", True, 256, 128, 4, 1, 0, 5, 8, 3, 3,
+                        "au", "q1", "st_d0", "d1", "du", "u", None, None, None, 0.25),
+    "dec_convT2": Layer("image_decoder.hallucinate.3.weight", True, 128, 64, 4, 2, 1, 8, 16, 3, 3,
+                        "aq1", "q2", "st_d1", "d2", "d1", "q1", "aff_d0", "mr_d0", "red_d0", 0.5),
+    "dec_convT3": Layer("image_decoder.hallucinate.6.weight", True, 64, 32, 4, 2, 1, 16, 32, 3, 3,
+                        "aq2", "q3", "st_d2", "d3", "d2", "q2", "aff_d1", "mr_d1", "red_d1", 0.25),
+}
+# every workspace name mmvae_celeba_debug_offset knows (csrc/celeba.hip)
+WS_NAMES_CELEBA = ("patches1 r1 r2 r3 r4 a1 a2 a3 a4 y1 ay1 encout m1 z_bf z_f32 u au q1 q2 q3 aq1 aq2 aq3 dlogit patches4 d3 d2 d1 du "
+                   "dz_img dz_att d_encout dy1 db4 dr4 d3e d2e d1e tmp_f32 slab st_e0 st_e1 st_e2 st_d0 st_d1 st_d2 red_e0 red_e1 red_e2 "
+                   "red_d0 red_d1 red_d2 aff_e0 aff_e1 aff_e2 aff_d0 aff_d1 aff_d2 mr_e0 mr_e1 mr_e2 mr_d0 mr_d1 mr_d2").split()
+
 # every workspace name mmvae_mm_debug_offset knows (csrc/multimnist.hip): the end of a named buffer is bounded by the next of these
 WS_NAMES = ("patches1 r1 r2 r3 r4 y1 y2 encout txtout z_bf z_f32 u q1 q2 q3 logits dlogit d3 d2 d1 du dz_img dz_txt d_encout "
             "d_txtout dy2 dy1 db4 dr4 d3e d2e d1e aff_d0 aff_d1 aff_d2 st_d0 patches4 tmp_f32 aff_e0 aff_e1 aff_e2 eps m1 m2 gkeep "
@@ -69,11 +96,12 @@ def weight_shape(L):
     return (L.cin, L.cout, L.k, L.k) if L.transposed else (L.cout, L.cin, L.k, L.k)
 
 
-def layer_operands(name, nimg, seed):
+def layer_operands(name, nimg, seed, layers=None):
     """(x [nimg][ih][ih][cin], w in the parameter's layout, dy [nimg][oh][oh][cout]) -- one draw per (layer, seed); the images of a
-    smaller batch are a prefix of a larger one's only by accident, nothing relies on it."""
-    L = LAYERS[name]
-    idx = list(LAYERS).index(name)
+    smaller batch are a prefix of a larger one's only by accident, nothing relies on it.  layers: the family's table (LAYERS)."""
+    layers = LAYERS if layers is None else layers
+    L = layers[name]
+    idx = list(layers).index(name)
     w = ternary(weight_shape(L), W_DENSITY, gen(seed, idx, 1))
     x = ternary((nimg, L.ih, L.ih, L.cin), L.x_density, gen(seed, idx, 2, nimg))
     dy = ternary((nimg, L.oh, L.oh, L.cout), G_DENSITY, gen(seed, idx, 3, nimg))
@@ -199,35 +227,43 @@ def describe_mismatch(got, ref, limit=6):
 # the library's defaults of the knobs the tests set, restored after every test: csrc/convres.hip try_launch_convres ("convres" 1,
 # "convres_alt" 0), csrc/wgrad_ring.hip try_launch_wgrad_ring ("wgrad_ring" 1), try_wr ("wr_pair" 0, "wr_atomic_kb" 256) -- a changed
 # default there must be changed here (and in tests/test_gpu_wgrad_ring.py)
-KNOB_DEFAULTS = {"convres": 1, "convres_alt": 0, "wgrad_ring": 1, "wr_atomic_kb": 256, "wr_pair": 0}
-RECORDS = []        # (B, layer, knobs, [(tag, kernel)]) of every launch a harness made in this process: what the coverage test reads
+# (celeba_layer_mask: csrc/celeba.hip named_gemm, the keep mask of the replayed classifier layers)
+KNOB_DEFAULTS = {"convres": 1, "convres_alt": 0, "wgrad_ring": 1, "wr_atomic_kb": 256, "wr_pair": 0, "celeba_layer_mask": 0}
+# (B, layer, knobs, [(tag, kernel)]) of every launch a harness of the family made in this process: what its coverage test reads
+RECORDS = []
+RECORDS_CELEBA = []
 
 
 class LayerHarness:
-    """One MultiMNIST plan at batch B with a bound workspace (one ordinary step has run), whose layers the tests replay one at a
-    time on operands of their own."""
+    """One plan of a model family at batch B with a bound workspace (one ordinary step has run: the workspace is bound and the
+    weights are packed), whose layers the tests replay one at a time on operands of their own.
+    state_cls / engine_cls: the family's classes of multimodal_vae_amd.core (default: MultiMNIST); prefix: its mmvae_<prefix>_*
+    entry points; ws_names: every name its debug_offset knows; workload: the family's synthetic batch of bench.py; records: the
+    family's list of compared launches."""
 
-    def __init__(self, B):
+    def __init__(self, B, state_cls=None, engine_cls=None, prefix="mm", ws_names=None, workload="multimnist", records=None):
         import multimodal_vae_amd  # noqa: F401
         from multimodal_vae_amd._lib import call
-        from multimodal_vae_amd.core import FusedELBOStep, MultimnistState
+        from multimodal_vae_amd import core
         from multimodal_vae_amd.init import default_init_
-        from bench import synthetic_batch
+        from bench import synthetic_batch_for
         self.call = call
         self.B = B
+        self.prefix = prefix
+        self.records = RECORDS if records is None else records
         self.dev = torch.device("cuda:0")
-        self.st = MultimnistState(100, self.dev)
+        self.st = (state_cls or core.MultimnistState)(100, self.dev)
         default_init_(self.st, 1234)
-        img, txt = synthetic_batch(B, 1234)
-        self.eng = FusedELBOStep(self.st, B)
-        self.eng(img.to(self.dev), txt.to(self.dev))
+        a, b = synthetic_batch_for(workload, B, 1234)
+        self.eng = (engine_cls or core.FusedELBOStep)(self.st, B)
+        self.eng(a.to(self.dev), b.to(self.dev))
         self.st.ensure_packed()
         torch.cuda.synchronize()
         self.sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         self.offsets = {}
-        for n in WS_NAMES:
-            off = call("mmvae_mm_debug_offset", self.eng.h, n.encode())
-            assert off >= 0, "mmvae_mm_debug_offset does not know '%s'" % n
+        for n in (WS_NAMES if ws_names is None else ws_names):
+            off = call("mmvae_%s_debug_offset" % prefix, self.eng.h, n.encode())
+            assert off >= 0, "mmvae_%s_debug_offset does not know '%s'" % (prefix, n)
             self.offsets[n] = int(off)
         self._sorted = sorted(set(self.offsets.values())) + [self.eng.ws.numel()]
         self.gmap = self.st.grad_map().long()
@@ -278,14 +314,19 @@ class LayerHarness:
         self.st.params[off:off + numel] = w.reshape(-1).float().to(self.dev)
         self.st.pack_weights()
 
-    def packed_grad(self, pname):
-        """(gradient of the parameter read through mmvae_mm_grad_map, max |gpk| over the elements the map gives to OTHER parameters)"""
+    def packed_grad(self, pname, also=()):
+        """(gradient of the parameter read through mmvae_<family>_grad_map, max |gpk| over the elements the map gives to OTHER
+        parameters).  also: parameters whose packed gradient the same launch writes too (a bias folded into the packed weights)."""
         off, numel, shape = self.param_range(pname)
         m = self.gmap[off:off + numel]
         assert bool((m >= 0).all()), pname + ": not every element has a slot in the packed matrix gradient"
         assert int(m.unique().numel()) == numel, pname + ": two elements share a slot"
         gpk = self.st.gpk
-        others = torch.cat([self.gmap[:off], self.gmap[off + numel:]])
+        mine = torch.zeros(self.gmap.numel(), dtype=torch.bool, device=self.gmap.device)
+        for n in (pname,) + tuple(also):
+            o, k, _ = self.param_range(n)
+            mine[o:o + k] = True
+        others = self.gmap[~mine]
         others = others[others >= 0]
         return gpk[m].reshape(shape).cpu(), float(gpk[others].abs().max())
 
@@ -302,7 +343,7 @@ class LayerHarness:
         self.set_knobs(**knobs)
         self.call("mmvae_debug_probe", 1)
         try:
-            self.call("mmvae_mm_bench_layer", self.eng.h, self.eng.ws.data_ptr(), self.eng.ws.numel(), layer.encode(), 1, self.sp)
+            self.call("mmvae_%s_bench_layer" % self.prefix, self.eng.h, self.eng.ws.data_ptr(), self.eng.ws.numel(), layer.encode(), 1, self.sp)
         finally:
             self.call("mmvae_debug_probe", 0)
         cap = 1 << 16
@@ -313,5 +354,205 @@ class LayerHarness:
         for line in text.value.decode().splitlines():
             f = line.split("\t")
             launches.append((f[0], f[1]))
-        RECORDS.append((self.B, layer, dict(knobs), launches))
+        self.records.append((self.B, layer, dict(knobs), launches))
         return launches
+
+
+# ------------------------------------------------------------------------------------------------ comparisons
+# The checks of tests/test_gpu_celeba_layers.py (the same tiers and gates as tests/test_gpu_layers.py, whose docstring derives
+# them), with the layer's table entry passed in.
+REPORT = os.environ.get("MMVAE_TOL_REPORT") is not None       # print the worst error / gate ratio of every gated check
+
+
+def check_forward(h, L, name, x, w, knob_sets, what):
+    """Tier A: raw output and column statistics of a forward layer, torch.equal"""
+    ref = ref_forward(L, x, w)
+    assert_exact_regime(out=ref, groups=L.gf, what=what)
+    ref_st = ref_colstats(ref, L.gf)
+    h.set_weight(L.param, w)
+    h.put(L.x, x)
+    for knobs in knob_sets:
+        h.zero(L.out, ref.numel(), torch.bfloat16)
+        h.zero(L.stats, L.gf * STAT_SLOTS * L.cout * 2, torch.float32)
+        launches = h.run(name, **knobs)
+        got = h.get(L.out, ref.shape).double().cpu()
+        assert torch.equal(got, ref), (what, knobs, launches, describe_mismatch(got, ref))
+        st = h.stats(L.stats, L.gf, L.cout)
+        assert torch.equal(st, ref_st), (what, knobs, launches, "column statistics: %d of %d differ, first [group, channel, 0 sum / 1 sum^2] %s"
+                                         % (int((st != ref_st).sum()), st.numel(), torch.nonzero(st != ref_st)[:6].tolist()))
+
+
+def check_wgrad(h, layer, pname, dw, knob_sets, what, also=()):
+    """Tier A: the packed weight gradient of one parameter, exact, and nothing written into another parameter's slots.
+    also: {parameter: its exact gradient} the same launch produces (a bias folded into the packed weights)"""
+    also = dict(also)
+    assert_exact_regime(dw=dw, what=what)
+    assert float(dw.abs().max()) > 0
+    for knobs in knob_sets:
+        h.st.gpk.zero_()
+        launches = h.run(layer, **knobs)
+        for pn, want in [(pname, dw)] + list(also.items()):
+            got, others = h.packed_grad(pn, [n for n in [pname] + list(also) if n != pn])
+            bad = got.double() != want
+            assert not bool(bad.any()), (what, pn, knobs, launches, "%d of %d elements differ, first %s: got %s want %s" % (
+                int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), want[bad][:6].tolist()))
+            assert others == 0.0, (what, knobs, "another parameter's packed gradient was written", others)
+
+
+def gate_elements(got, ref, acc, what, extra=""):
+    """Tier B: |got - ref| <= 2^-8 |ref| + 1e-5 |acc| per element"""
+    got, gate = got.double().cpu(), 2.0 ** -8 * ref.abs() + 1e-5 * acc.abs()
+    err = (got - ref).abs()
+    bad = ~(err <= gate)
+    if REPORT:
+        print("TIERB %s: worst err/gate %.3f" % (what, float((err / gate.clamp_min(1e-30)).max())))
+    assert not bool(bad.any()), (what, extra, "%d of %d outside the gate; first %s got %s want %s acc %s; rows affected %d" % (
+        int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), ref[bad][:6].tolist(), acc[bad][:6].tolist(),
+        int(bad.reshape(bad.shape[0], -1).any(1).sum())))
+
+
+def gate_sums(got, ref, mag, what, extra=""):
+    """Tier B: a sum of fp32 terms, |got - ref| <= 2^-16 sum |terms|"""
+    err, gate = (got.double().cpu() - ref).abs(), 2.0 ** -16 * mag
+    if REPORT:
+        print("TIERB %s: sums worst err/gate %.3f" % (what, float((err / gate.clamp_min(1e-30)).max())))
+    assert bool((err <= gate).all()), (what, extra, "first %s got %s want %s" % (
+        torch.nonzero(err > gate)[:6].tolist(), got.double().cpu()[err > gate][:6].tolist(), ref[err > gate][:6].tolist()))
+
+
+def check_exact(got, ref, what, limit=256):
+    """Tier A on a dense layer: integer reference of magnitude <= limit (256: exact in bf16; 2^24: in fp32)"""
+    got = got.double().cpu()
+    assert bool((ref == ref.round()).all()) and float(ref.abs().max()) <= limit, (what, float(ref.abs().max()))
+    bad = got != ref
+    assert not bool(bad.any()), (what, "%d of %d elements differ; first %s got %s want %s; rows affected %d" % (
+        int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), ref[bad][:6].tolist(),
+        int(bad.reshape(bad.shape[0], -1).any(1).sum())))
+
+
+def check_dgrad(h, L, name, dy, w, g, knob_sets, what):
+    """Tier B: data gradient of a conv layer with the Swish' / BatchNorm-backward epilogue of the layer below; g: generator of the
+    saved raw tensor and the tables"""
+    acc = ref_dgrad_acc(L, dy, w)
+    assert bool((acc == acc.round()).all()) and float(acc.abs().max()) <= 256, what
+    r = eighths(acc.shape, g)
+    aff, mr = dyadic_tables(L.gb, L.cin, g) if L.aff else (None, None)
+    v, red, red_abs = ref_dgrad_epilogue(acc, r, aff, mr, L.gb)
+    h.set_weight(L.param, w)
+    h.put(L.dy, dy)
+    h.put(L.r, r)
+    if L.aff:
+        h.put(L.aff, aff, torch.float32)
+        h.put(L.mr, mr, torch.float32)
+    for knobs in knob_sets:
+        h.zero(L.dx, acc.numel(), torch.bfloat16)
+        if L.red:
+            h.zero(L.red, L.gb * STAT_SLOTS * L.cin * 2, torch.float32)
+        launches = h.run(name + "_dgrad", **knobs)
+        gate_elements(h.get(L.dx, acc.shape), v, acc, "%s %s" % (what, knobs), launches)
+        if L.red:
+            gate_sums(h.stats(L.red, L.gb, L.cin), red, red_abs, "%s %s d_red" % (what, knobs), launches)
+
+
+# ------------------------------------------------------------------------------------------------ staged forms (fused step)
+# csrc/gemm.h GatherTransform, csrc/convres.hip: kind 1 stages Swish(BatchNorm(raw)) of the layer's operand from the column
+# statistics of the layer below; kind 2 stages the BatchNorm backward of the incoming gradient, in place.
+BN_EPS = float(torch.tensor(1e-5, dtype=torch.float32))       # csrc/plan_base.h BN_EPS as the fp32 value the kernel adds
+EPS32 = 2.0 ** -24                                            # one rounding of an fp32 operation, relative
+
+
+def slot_stats(r, groups):
+    """[groups][STAT_SLOTS][C][2] float64: (sum v, sum v^2) of r [nimg][h][w][C], the rows of a group dealt to the slots in
+    STAT_SLOTS contiguous runs.  For r in eighths of magnitude <= 4 and at most 4096 rows per slot every entry is exact in fp32."""
+    C = r.shape[-1]
+    o = r.double().reshape(groups, STAT_SLOTS, -1, C)
+    return torch.stack([o.sum(2), (o * o).sum(2)], -1)
+
+
+def ref_bn_tables(stats, count, gamma, beta):
+    """csrc/bn_dev.h bn_channel_tables in float64 from the slot table [groups][STAT_SLOTS][C][2] as written (fp32 values):
+    -> scale, shift, mean, rstd, each [groups][C]"""
+    s = stats.double().sum(1)
+    mean = s[..., 0] / count
+    var = (s[..., 1] / count - mean * mean).clamp_min(0)
+    rstd = 1.0 / torch.sqrt(var + BN_EPS)
+    scale = gamma.double()[None] * rstd
+    return scale, beta.double()[None] - mean * scale, mean, rstd
+
+
+def ref_stage_fwd(r, scale, shift, groups):
+    """kind 1 by-product: Swish(scale * r + shift) per group and channel, float64, shape of r"""
+    C = r.shape[-1]
+    y = r.double().reshape(groups, -1, C) * scale[:, None] + shift[:, None]
+    return (y * torch.sigmoid(y)).reshape(r.shape), y.reshape(r.shape)
+
+
+def gate_stage_fwd(r, scale, shift, mean, beta, ref, groups):
+    """Gate of the kind 1 by-product: one bf16 ulp of the stored value (2^-8 |ref|, either rounding) plus the fp32 error in front
+    of the store, 32 roundings each relative to a quantity bounded by T = (|r| + |mean| + 4) |scale| + |beta| + 1:
+    15 additions of the slot sums (|r| <= 4: their error reaches the mean by at most 15 eps * 4), 2 divisions by the count,
+    3 operations of the variance (mean^2 << variance for the operands used: no cancellation), rsqrt, scale, 2 of the shift,
+    2 of the affine, 5 of swish_fast (exponent scaling, exp, 1 +, reciprocal, product) = 31."""
+    C = r.shape[-1]
+    T = (r.double().abs().reshape(groups, -1, C) + mean.abs()[:, None] + 4) * scale.abs()[:, None] + beta.double().abs()[None, None] + 1
+    return 2.0 ** -8 * ref.abs() + 32 * EPS32 * T.reshape(r.shape)
+
+
+def ref_abs_terms(L, x, w):
+    """sum of |terms| of every output element of the layer: the forward of |x| with |w|"""
+    return ref_forward(L, x.double().abs(), w.double().abs())
+
+
+def gate_stage_conv(L, ref, absterms):
+    """Gate of a conv output whose operand is not integer-valued (the bf16 by-product): 2^-8 |ref| for the bf16 store plus
+    K * 2^-24 * sum |terms| for K fp32 additions, K = taps x input channels of the layer"""
+    return 2.0 ** -8 * ref.abs() + L.k * L.k * L.cin * EPS32 * absterms
+
+
+def gate_stage_colstats(L, ref, absterms, groups):
+    """Gate of the column statistics of such an output, summed from the fp32 accumulators BEFORE the store (convres_epi.h):
+    per element e = K * 2^-24 * sum |terms|; sum v: sum e + 2^-16 sum |v|; sum v^2: sum (2 |v| e + e^2) + 2^-16 sum v^2"""
+    C = ref.shape[-1]
+    e = (L.k * L.k * L.cin * EPS32 * absterms).reshape(groups, -1, C)
+    v = ref.reshape(groups, -1, C)
+    return torch.stack([e.sum(1) + 2.0 ** -16 * v.abs().sum(1), (2 * v.abs() * e + e * e).sum(1) + 2.0 ** -16 * (v * v).sum(1)], -1)
+
+
+def staged_bwd_operands(L, nimg, groups, count, g):
+    """Operands of a kind 2 launch on which every coefficient and every dr = g db + cb r + c2 (csrc/convres.hip) lies on the
+    2^-7 grid below 64: exact in fp32, so the in-place bf16 store is the only rounding of dr and the data gradient's fp32
+    accumulation of the stored values (multiples of 2^-8: rounding to 8 bits only coarsens the grid) is exact again.
+    -> db ternary, r eighths [nimg][oh][oh][cout]; red [groups][STAT_SLOTS][cout][2] with slot sums count * m1, count * m2
+    (m1, m2 multiples of 1/4, spread unevenly over the slots); mr [groups][cout][2] dyadic; gamma [cout] in {1, 2, -1}"""
+    C = L.cout
+    db = ternary((nimg, L.oh, L.oh, C), G_DENSITY, g)
+    r = eighths((nimg, L.oh, L.oh, C), g)
+    pick = lambda vals, shape: torch.tensor(vals, dtype=torch.float64)[torch.randint(0, len(vals), shape, generator=g)]
+    m = pick([-1.0, -0.5, -0.25, 0.0, 0.25, 0.5, 1.0], (groups, C, 2))
+    assert count % 64 == 0, count            # every slot value count * (multiple of 1/64) is an integer
+    delta = torch.tensor([1.0, -1.0] * (STAT_SLOTS // 2), dtype=torch.float64)[None, :, None, None] / 64
+    red = count * (m[:, None] / STAT_SLOTS + delta * torch.ones(groups, STAT_SLOTS, C, 2, dtype=torch.float64))
+    mr = torch.stack([pick([-0.25, 0.0, 0.5], (groups, C)), pick([0.5, 1.0, 2.0], (groups, C))], -1)
+    gamma = pick([1.0, 2.0, -1.0], (C,))
+    return db, r, red, mr, gamma
+
+
+def ref_bn_backward(db, r, red, mr, gamma, count, groups):
+    """float64 BatchNorm backward as csrc/convres.hip TR 2 states it:  dr = g (db - m1 - xhat m2), g = gamma rstd, m1 / m2 = the
+    group's sums of db / db xhat over the count, xhat = (r - mean) rstd;  dgamma = sum over groups of sum db xhat, dbeta = of sum db
+    -> dr (shape of db), dgamma [C], dbeta [C], their sums of |slot values| [C] (what the 2^-16 gate scales with)"""
+    C = db.shape[-1]
+    s = red.double().sum(1)
+    m1, m2 = s[..., 0] / count, s[..., 1] / count
+    mean, rstd = mr[..., 0].double(), mr[..., 1].double()
+    gg = gamma.double()[None] * rstd
+    xhat = (r.double().reshape(groups, -1, C) - mean[:, None]) * rstd[:, None]
+    dr = gg[:, None] * (db.double().reshape(groups, -1, C) - m1[:, None] - xhat * m2[:, None])
+    mag = red.double().abs().sum((0, 1))
+    return dr.reshape(db.shape), s[..., 1].sum(0), s[..., 0].sum(0), mag[..., 1], mag[..., 0]
+
+
+def celeba_harness(B):
+    """LayerHarness of the CelebA plan (csrc/celeba.hip celeba_bench_layer / celeba_debug_offset)"""
+    from multimodal_vae_amd.core import CelebaState, FusedCelebaStep
+    return LayerHarness(B, CelebaState, FusedCelebaStep, "celeba", WS_NAMES_CELEBA, "celeba", RECORDS_CELEBA)

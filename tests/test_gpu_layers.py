@@ -17,9 +17,8 @@ from the probe's records that every instantiation reachable with default knobs r
 
 The layer launches are the plain forms (GemmParams::tr kind 0).  What stays with the whole-step tests: the staged forms of the
 fused step (kinds 1 and 2), dec_last_fused, conv1.hip's in-step form, the fused classifier tail (mlp_tail.hip), the text kernels
-and the CelebA / COCO plans (no bench_layer)."""
-import os
-
+and the COCO plan (no bench_layer).  The CelebA plan has its own modules: tests/test_gpu_celeba_layers.py and
+tests/test_gpu_celeba_layers_staged.py (mmvae_celeba_bench_layer)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -28,7 +27,7 @@ import layer_ref as LR
 from layer_ref import LAYERS, SEEDS
 
 pytestmark = pytest.mark.gpu
-REPORT = os.environ.get("MMVAE_TOL_REPORT") is not None       # print the worst error / gate ratio of every Tier B check
+# MMVAE_TOL_REPORT=1 prints the worst error / gate ratio of every Tier B check (layer_ref.REPORT)
 
 BATCHES = LR.BATCHES
 _H = {}
@@ -46,21 +45,7 @@ def _harness(B):
 
 # ------------------------------------------------------------------------------------------------ Tier A: forward
 def _check_forward(h, name, x, w, knob_sets, what):
-    L = LAYERS[name]
-    ref = LR.ref_forward(L, x, w)
-    LR.assert_exact_regime(out=ref, groups=L.gf, what=what)
-    ref_st = LR.ref_colstats(ref, L.gf)
-    h.set_weight(L.param, w)
-    h.put(L.x, x)
-    for knobs in knob_sets:
-        h.zero(L.out, ref.numel(), torch.bfloat16)
-        h.zero(L.stats, L.gf * LR.STAT_SLOTS * L.cout * 2, torch.float32)
-        launches = h.run(name, **knobs)
-        got = h.get(L.out, ref.shape).double().cpu()
-        assert torch.equal(got, ref), (what, knobs, launches, LR.describe_mismatch(got, ref))
-        st = h.stats(L.stats, L.gf, L.cout)
-        assert torch.equal(st, ref_st), (what, knobs, launches, "column statistics: %d of %d differ, first [group, channel, 0 sum / 1 sum^2] %s"
-                                         % (int((st != ref_st).sum()), st.numel(), torch.nonzero(st != ref_st)[:6].tolist()))
+    LR.check_forward(h, LAYERS[name], name, x, w, knob_sets, what)
 
 
 @pytest.mark.parametrize("name", list(LAYERS))
@@ -109,17 +94,7 @@ WG_KNOBS = (dict(wgrad_ring=0, wr_atomic_kb=256, wr_pair=0),) + tuple(
     dict(wgrad_ring=1, wr_atomic_kb=kb, wr_pair=pair) for kb in (0, 4096) for pair in (1, 0))
 
 
-def _check_wgrad(h, layer, pname, dw, knob_sets, what):
-    LR.assert_exact_regime(dw=dw, what=what)
-    assert float(dw.abs().max()) > 0
-    for knobs in knob_sets:
-        h.st.gpk.zero_()
-        launches = h.run(layer, **knobs)
-        got, others = h.packed_grad(pname)
-        bad = got.double() != dw
-        assert not bool(bad.any()), (what, knobs, launches, "%d of %d elements differ, first %s: got %s want %s" % (
-            int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), dw[bad][:6].tolist()))
-        assert others == 0.0, (what, knobs, "another parameter's packed gradient was written", others)
+_check_wgrad = LR.check_wgrad
 
 
 @pytest.mark.parametrize("name", list(LAYERS))
@@ -185,41 +160,8 @@ def test_thin_layers_exact(B):
 
 # ------------------------------------------------------------------------------------------------ Tier B: data gradients
 def _check_dgrad(h, name, dy, w, seed, knob_sets, what):
-    L = LAYERS[name]
-    nimg = dy.shape[0]
-    acc = LR.ref_dgrad_acc(L, dy, w)
-    assert bool((acc == acc.round()).all()) and float(acc.abs().max()) <= 256, what
-    g = LR.gen(seed, list(LAYERS).index(name), 4, nimg)
-    r = LR.eighths(acc.shape, g)
-    aff, mr = LR.dyadic_tables(L.gb, L.cin, g) if L.aff else (None, None)
-    v, red, red_abs = LR.ref_dgrad_epilogue(acc, r, aff, mr, L.gb)
-    h.set_weight(L.param, w)
-    h.put(L.dy, dy)
-    h.put(L.r, r)
-    if L.aff:
-        h.put(L.aff, aff, torch.float32)
-        h.put(L.mr, mr, torch.float32)
-    gate = 2.0 ** -8 * v.abs() + 1e-5 * acc.abs()
-    for knobs in knob_sets:
-        h.zero(L.dx, acc.numel(), torch.bfloat16)
-        if L.red:
-            h.zero(L.red, L.gb * LR.STAT_SLOTS * L.cin * 2, torch.float32)
-        launches = h.run(name + "_dgrad", **knobs)
-        got = h.get(L.dx, acc.shape).double().cpu()
-        err = (got - v).abs()
-        bad = ~(err <= gate)
-        if REPORT:
-            print("TIERB %s %s: worst err/gate %.3f" % (what, knobs, float((err / gate.clamp_min(1e-30)).max())))
-        assert not bool(bad.any()), (what, knobs, launches, "%d of %d outside the gate; first [image, y, x, channel] %s got %s want %s acc %s; images affected %d" % (
-            int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), v[bad][:6].tolist(), acc[bad][:6].tolist(),
-            int(bad.reshape(nimg, -1).any(1).sum())))
-        if L.red:
-            rg = h.stats(L.red, L.gb, L.cin)
-            rerr, rgate = (rg - red).abs(), 2.0 ** -16 * red_abs
-            if REPORT:
-                print("TIERB %s %s: d_red worst err/gate %.3f" % (what, knobs, float((rerr / rgate.clamp_min(1e-30)).max())))
-            assert bool((rerr <= rgate).all()), (what, knobs, launches, "d_red: first [group, channel, term] %s got %s want %s" % (
-                torch.nonzero(rerr > rgate)[:6].tolist(), rg[rerr > rgate][:6].tolist(), red[rerr > rgate][:6].tolist()))
+    g = LR.gen(seed, list(LAYERS).index(name), 4, dy.shape[0])
+    LR.check_dgrad(h, LAYERS[name], name, dy, w, g, knob_sets, what)
 
 
 @pytest.mark.parametrize("name", list(LAYERS))
@@ -243,33 +185,14 @@ def _swish(x):
     return x * torch.sigmoid(x)
 
 
-def _gated(got, ref, acc, what):
-    """|got - ref| <= 2^-8 |ref| + 1e-5 |acc| per element (module docstring)"""
-    got, gate = got.double().cpu(), 2.0 ** -8 * ref.abs() + 1e-5 * acc.abs()
-    err = (got - ref).abs()
-    bad = ~(err <= gate)
-    if REPORT:
-        print("TIERB %s: worst err/gate %.3f" % (what, float((err / gate.clamp_min(1e-30)).max())))
-    assert not bool(bad.any()), (what, "%d of %d outside the gate; first %s got %s want %s acc %s" % (
-        int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), ref[bad][:6].tolist(), acc[bad][:6].tolist()))
-
-
-def _exact(got, ref, what):
-    got = got.double().cpu()
-    assert bool((ref == ref.round()).all()) and float(ref.abs().max()) <= 256, (what, float(ref.abs().max()))
-    bad = got != ref
-    assert not bool(bad.any()), (what, "%d of %d elements differ; first %s got %s want %s; rows affected %d" % (
-        int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), ref[bad][:6].tolist(),
-        int(bad.reshape(bad.shape[0], -1).any(1).sum())))
+# the comparisons are tests/layer_ref.py's, shared with the CelebA modules and shown on the CPU to see a dropped tap, image or
+# column tile (tests/test_cpu_layer_ref.py)
+_gated = LR.gate_elements
+_exact = LR.check_exact
 
 
 def _colsum_gate(h, N, v, what):
-    got = h.get("tmp_f32", (N,), torch.float32).double().cpu()
-    ref, mag = v.sum(0), v.abs().sum(0)
-    err = (got - ref).abs()
-    if REPORT:
-        print("TIERB %s: d_colsum worst err/gate %.3f" % (what, float((err / (2.0 ** -16 * mag).clamp_min(1e-30)).max())))
-    assert bool((err <= 2.0 ** -16 * mag).all()), (what, "d_colsum", torch.nonzero(err > 2.0 ** -16 * mag)[:6].tolist())
+    LR.gate_sums(h.get("tmp_f32", (N,), torch.float32), v.sum(0), v.abs().sum(0), what + " d_colsum")
 
 
 @pytest.mark.parametrize("B", BATCHES)
@@ -385,11 +308,7 @@ def test_last_layer_dgrad(B):
             h.run("dec_last_dgrad_gemm")
             what = "dec_last_dgrad_gemm B=%d seed %d" % (B, seed)
             _gated(h.get("d3", acc.shape), v, acc, what)
-            rg = h.stats("red_d2", 2, 32)
-            rerr, rgate = (rg - red).abs(), 2.0 ** -16 * red_abs
-            if REPORT:
-                print("TIERB %s: d_red worst err/gate %.3f" % (what, float((rerr / rgate.clamp_min(1e-30)).max())))
-            assert bool((rerr <= rgate).all()), (what, "d_red", torch.nonzero(rerr > rgate)[:6].tolist())
+            LR.gate_sums(h.stats("red_d2", 2, 32), red, red_abs, what + " d_red")
     finally:
         h.restore_knobs()
 
