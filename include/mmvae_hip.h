@@ -312,6 +312,27 @@ int mmvae_celeba_attrs_decoder_fwd(mmvae_celeba_t*, void* ws, size_t ws_bytes, c
                                    void* stream);                                                /* celeba/model.py:191-196 */
 int mmvae_celeba_attrs_decoder_bwd(mmvae_celeba_t*, void* ws, size_t ws_bytes, const float* d_recon, const float* recon,
                                    float* dz, void* stream);
+/* Importance-weighted evaluation, the CelebA scoring step between mmvae_iw_particles and mmvae_iw_accumulate(T = 18, V = 2) on the
+ * B*K particle rows z [B][K][n_latents] (row b*K + k: example b; B*K at most the plan's batch):
+ *   * the eval-mode image decoder body (the bf16 launches of mmvae_celeba_image_decoder_fwd up to the raw output of
+ *     hallucinate.6), then ONE forward-only kernel per row: BatchNorm (running statistics) + Swish while staging, the last
+ *     ConvTranspose2d(32, 3, 4, 2, 1) on the matrix cores, loglik_x [B*K] = sum over the 3x64x64 logits l of x*l - softplus(l)
+ *     (not clamped like the training BCE) against image [B][3][64][64], summed in a fixed order (equal inputs: bit-equal sums);
+ *   * the attribute decoder in fp32 on the bound fp32 parameters: words [B*K][18][2] = (log(1 - p_t), log p_t) of attribute t,
+ *     so that targets = the attributes as int64 0 / 1 select log p(y_t | z) in mmvae_iw_accumulate.
+ * Nothing of the plan's parameters, BatchNorm buffers or gradients is modified.  Workspace: mmvae_celeba_iw_workspace_bytes. */
+size_t mmvae_celeba_iw_workspace_bytes(const mmvae_celeba_t*);
+int mmvae_celeba_iw_score(mmvae_celeba_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K,
+                          float* loglik_x, float* words, void* stream);
+/* Test hooks of the two scoring kernels.
+ * mmvae_celeba_iw_tail needs no plan: q3_bf16 [B*K][32][32][32] (NHWC bf16, the raw output of hallucinate.6), affine [32][2]
+ * (scale, shift) per channel, act one of 0 none / 1 Swish / 2 ReLU (the scoring call passes Swish), w (32,3,4,4) fp32 (rounded to
+ * bf16 by the kernel), image [B][3][64][64]; loglik [B*K]; logits_or_null [B*K][3][64][64] fp32 receives the pre-sigmoid logits.
+ * mmvae_celeba_iw_attrs is the attribute scorer the scoring call runs: z [rows][n_latents] fp32 -> words [rows][18][2], any
+ * rows below 2^31 (independent of the plan's batch), no packed weights, no workspace. */
+int mmvae_celeba_iw_tail(const void* q3_bf16, const float* affine, int act, const float* w, const float* image, int B, int K,
+                         float* loglik, float* logits_or_null, void* stream);
+int mmvae_celeba_iw_attrs(mmvae_celeba_t*, const float* z, long long rows, float* words, void* stream);
 
 /* ---------------------------------------------------------------- COCO (coco/model.py, coco/train.py)
  * MultimodalVAE of coco/model.py:22-90: conv ImageEncoder :147-187 / ImageDecoder :190-216 on 3x32x32 images (the code's

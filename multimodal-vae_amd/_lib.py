@@ -216,6 +216,10 @@ SIGNATURES["mmvae_celeba_attrs_encoder_fwd"] = (_I, [_P, _P, _SZ, _P, _I, _P, _P
 SIGNATURES["mmvae_celeba_attrs_encoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P])
 SIGNATURES["mmvae_celeba_attrs_decoder_fwd"] = (_I, [_P, _P, _SZ, _P, _I, _P, _P])
 SIGNATURES["mmvae_celeba_attrs_decoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P])
+SIGNATURES["mmvae_celeba_iw_workspace_bytes"] = (_SZ, [_P])
+SIGNATURES["mmvae_celeba_iw_score"] = (_I, [_P, _P, _SZ, _P, _P, _I, _I, _P, _P, _P])
+SIGNATURES["mmvae_celeba_iw_tail"] = (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P])
+SIGNATURES["mmvae_celeba_iw_attrs"] = (_I, [_P, _P, _LL, _P, _P])
 SIGNATURES.update(_plan_api("coco"))
 SIGNATURES["mmvae_coco_create_t"] = (_P, [_I, _I, _I])
 SIGNATURES["mmvae_coco_steps"] = (_I, [_P])

@@ -258,6 +258,18 @@ def loss_function(mu, logvar, recon_x=None, x=None, recon_y=None, y=None, kl_lam
 elbo_loss = loss_function
 
 
+def load_checkpoint(file_path, use_cuda=False):
+    """celeba/train.py:46-58: rebuilds a MultimodalVAE from the checkpoint dict (``state_dict``, ``n_latents``) of either code base;
+    a dict without ``n_latents`` gets the default of celeba/train.py:87 (100)."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    n_latents = checkpoint['n_latents'] if 'n_latents' in checkpoint else 100
+    vae = MultimodalVAE(n_latents=n_latents)
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
+
+
 class FusedTrainer:
     """``FusedTrainer(vae, batch_size, lr)(image, attrs)`` == zero_grad + 3 passes + 3 losses + backward + Adam step
     (celeba/train.py:131-149) on ``vae``'s own parameters."""

@@ -265,6 +265,25 @@ int mmvae_celeba_attrs_decoder_fwd(mmvae_celeba_t* p, void* ws, size_t wsb, cons
 int mmvae_celeba_attrs_decoder_bwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* d_recon, const float* recon, float* dz, void* st) {
     return guarded([&] { return celeba_attrs_decoder_bwd(p, ws, wsb, d_recon, recon, dz, S(st)); });
 }
+size_t mmvae_celeba_iw_workspace_bytes(const mmvae_celeba_t* p) { return celeba_iw_workspace_bytes(p); }
+int mmvae_celeba_iw_score(mmvae_celeba_t* p, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x,
+                          float* words, void* st) {
+    return guarded([&] { return celeba_iw_score(p, ws, wsb, z, image, B, K, loglik_x, words, S(st)); });
+}
+int mmvae_celeba_iw_tail(const void* q3, const float* affine, int act, const float* w, const float* image, int B, int K, float* loglik,
+                         float* logits, void* st) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(affine != nullptr, "mmvae_celeba_iw_tail: null affine table");
+        MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= 0x3FFFFFFF, "mmvae_celeba_iw_tail: B=%d K=%d out of range", B, K);
+        CelebaIwTailArgs a{};
+        a.q3 = static_cast<const bf16*>(q3); a.affine = reinterpret_cast<const float2*>(affine); a.act = act; a.w = w; a.image = image;
+        a.rows = B * K; a.K = K; a.loglik = loglik; a.logits = logits;
+        return launch_celeba_iw_tail(a, S(st));
+    });
+}
+int mmvae_celeba_iw_attrs(mmvae_celeba_t* p, const float* z, long long rows, float* words, void* st) {
+    return guarded([&] { return celeba_iw_attrs(p, z, rows, words, S(st)); });
+}
 
 // ---- COCO (coco/model.py, coco/train.py)
 mmvae_coco_t* mmvae_coco_create_t(int n_latents, int batch, int steps) {

@@ -19,6 +19,33 @@ int celeba_attrs_encoder_fwd(CelebaPlan*, void* ws, size_t wsb, const float* att
 int celeba_attrs_encoder_bwd(CelebaPlan*, void* ws, size_t wsb, const float* d_out, hipStream_t);
 int celeba_attrs_decoder_fwd(CelebaPlan*, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t);
 int celeba_attrs_decoder_bwd(CelebaPlan*, void* ws, size_t wsb, const float* d_recon, const float* recon, float* dz, hipStream_t);
+// importance-weighted evaluation (include/mmvae_hip.h: mmvae_celeba_iw_*): celeba_iw_score (celeba.hip) runs the eval-mode
+// decoder body and the two scoring kernels of celeba_iw.hip
+int celeba_iw_score(CelebaPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
+                    hipStream_t);
+size_t celeba_iw_workspace_bytes(const CelebaPlan*);
+// forward-only scoring tail: raw bf16 NHWC [rows][32][32][32] -> BatchNorm affine + act -> ConvTranspose2d(32, 3, 4, 2, 1) -> one
+// log p(x|z) per row against image [rows / K].  The affine is either the table `affine` [32] (scale, shift) or, when that is
+// null, made from gamma / beta / running mean / running variance [32] each.
+struct CelebaIwTailArgs {
+    const bf16* q3; const float2* affine;
+    const float *gamma, *beta, *rmean, *rvar; float eps;
+    int act;
+    const float* w;                  // (32, 3, 4, 4) fp32
+    const float* image;              // [rows / K][3][64][64]
+    int rows, K;
+    float* loglik;                   // [rows]
+    float* logits;                   // [rows][3][64][64] or null
+};
+int launch_celeba_iw_tail(const CelebaIwTailArgs&, hipStream_t);
+// attribute scorer on fp32 parameters: Linear(D, 64) -> BatchNorm1d (running statistics) -> Swish -> Linear(64, 18) -> words
+struct CelebaIwAttrsArgs {
+    const float *w0, *b0, *gamma, *beta, *rmean, *rvar, *w1, *b1; float eps;
+    const float* z; long long rows; int D;
+    float* words;                    // [rows][18][2] = (log(1 - p), log p)
+};
+int launch_celeba_iw_attrs(const CelebaIwAttrsArgs&, hipStream_t);
+int celeba_iw_attrs(CelebaPlan*, const float* z, long long rows, float* words, hipStream_t);
 // test / profiling aids: replay of one named layer launch of the step (celeba.hip named_gemm / named_wgrad) on the workspace's
 // contents, and the byte offset of a named workspace buffer (-1 if unknown)
 int celeba_bench_layer(CelebaPlan*, void* ws, size_t wsb, const char* layer, int iters, hipStream_t);

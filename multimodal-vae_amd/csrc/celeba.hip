@@ -456,6 +456,8 @@ int enc_bwd(CelebaPlan& P, const bf16* d_out, int variants, const uint8_t* m1, i
 // fused_bwd_groups >= 0 (the fused step): BatchNorm + Swish of hallucinate.7, the last ConvTranspose2d, sigmoid + BCE and -- for
 // the first fused_bwd_groups passes -- its input / weight gradients in ONE kernel per image (dec_last.hip dec_last_ca_kernel);
 // last_groups: passes whose last layer is computed at all
+// last == nullptr (celeba_iw_score): the body only -- it ends with the raw output of hallucinate.6 in q3, whose BatchNorm + Swish
+// belong to the caller's own tail
 int dec_fwd(CelebaPlan& P, int groups, int training, ConvTLastFwdArgs* last, hipStream_t s, int last_groups = -1, int fused_bwd_groups = -1,
             bool fuse = false) {
     CelebaPlan::W& w = P.w;
@@ -470,10 +472,11 @@ int dec_fwd(CelebaPlan& P, int groups, int training, ConvTLastFwdArgs* last, hip
         if (fuse && l >= 1) stage_fwd_dec(P, l, groups, g, tr, training);     // hallucinate.3 / .6 stage Swish(BatchNorm(q[l])) themselves and leave aq[l] behind
         MMVAE_TRY(launch_gemm_gather(g, s));
         const int rpg = B * L.g.OH * L.g.OW;
-        if (l == 2 && fused_bwd_groups >= 0) continue;
+        if (l == 2 && (fused_bwd_groups >= 0 || !last)) continue;
         if (fuse && l <= 1) continue;
         MMVAE_TRY(bn_act(P, P.bn[L.bn], q[l + 1], aq[l + 1], groups * rpg, rpg, groups, w.st_d[l], 1, w.aff_d[l], w.mr_d[l], training, s));
     }
+    if (!last) return MMVAE_OK;
     if (fused_bwd_groups >= 0) {
         const ConvL& L = P.convT[2];
         const BnL& b = P.bn[L.bn];
@@ -780,6 +783,45 @@ int celeba_attrs_decoder_bwd(CelebaPlan* P, void* ws, size_t wsb, const float* d
     MMVAE_TRY(mmvae_check_launch("sigmoid_bwd"));
     MMVAE_TRY(att_dec_bwd(*P, w.dalogit, 1, dz, s));
     return plan_unpack(*P, s, true);
+}
+
+// ---------------------------------------------------------------- importance-weighted evaluation (iw.h, celeba_iw.hip)
+// Eval-mode decoders on the B*K particle rows z [B][K][D].  Image: the bf16 decoder body of celeba_image_decoder_fwd up to the
+// raw output of hallucinate.6 (no stand-alone BatchNorm + Swish pass over it), then the forward-only scoring tail -- one
+// log p(x|z) per row against the row's own example.  Attributes: the fp32 scorer on the bound parameters.  No backward
+// activation is kept; parameters, BatchNorm buffers and gradients are only read.
+size_t celeba_iw_workspace_bytes(const CelebaPlan* P) { return P->ws_bytes_module; }
+int celeba_iw_attrs(CelebaPlan* P, const float* z, long long rows, float* words, hipStream_t s) {
+    MMVAE_TRY(check_bound(P));
+    const BnL& b = P->bn[7];
+    const float* p = P->buf.params;
+    CelebaIwAttrsArgs a{};
+    a.w0 = p + P->ad[0].w_off; a.b0 = p + P->ad[0].b_off; a.w1 = p + P->ad[1].w_off; a.b1 = p + P->ad[1].b_off;
+    a.gamma = p + b.w_off; a.beta = p + b.b_off; a.rmean = P->buf.bn_stats + b.stat_off; a.rvar = a.rmean + b.C; a.eps = BN_EPS;
+    a.z = z; a.rows = rows; a.D = P->D; a.words = words;
+    return launch_celeba_iw_attrs(a, s);
+}
+int celeba_iw_score(CelebaPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
+                    hipStream_t s) {
+    MMVAE_REQUIRE(P && z && image && loglik_x && words, "mmvae_celeba_iw_score: null argument");
+    MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B,
+                  "mmvae_celeba_iw_score: %d examples x %d particles exceed the plan's %d rows", B, K, P->B);
+    MMVAE_TRY(use_ws(P, ws, wsb));
+    CelebaPlan::W& w = P->w;
+    const int rows = B * K;
+    MMVAE_TRY(launch_fill_zero(w.zero_begin, w.zero_bytes, s));
+    hipLaunchKernelGGL(cast_z_kernel, dim3(ceil_div(rows * P->ldz, 256)), dim3(256), 0, s, z, rows, P->D, w.z_bf, P->ldz);
+    MMVAE_TRY(mmvae_check_launch("cast_z"));
+    if (rows < P->B)      // the body runs the plan's rows: the ones past B*K are defined (zero) and never scored
+        MMVAE_TRY(launch_fill_zero(w.z_bf + (size_t)rows * P->ldz, (size_t)(P->B - rows) * P->ldz * sizeof(bf16), s));
+    MMVAE_TRY(dec_fwd(*P, 1, 0, nullptr, s));
+    const BnL& b = P->bn[P->convT[2].bn];
+    CelebaIwTailArgs t{};
+    t.q3 = w.q3; t.gamma = P->buf.params + b.w_off; t.beta = P->buf.params + b.b_off;
+    t.rmean = P->buf.bn_stats + b.stat_off; t.rvar = t.rmean + b.C; t.eps = BN_EPS;
+    t.act = ACT_SWISH; t.w = P->buf.params + P->convT[3].w_off; t.image = image; t.rows = rows; t.K = K; t.loglik = loglik_x;
+    MMVAE_TRY(launch_celeba_iw_tail(t, s));
+    return celeba_iw_attrs(P, z, rows, words, s);
 }
 
 // ---------------------------------------------------------------- test / profiling aid: replay one layer of the step

@@ -73,6 +73,22 @@ def synthetic_mnist(n: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     return images, labels
 
 
+def synthetic_celeba(n: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """CelebA-shaped stand-in (no CelebA files in this environment): -> (uint8 (n,3,64,64), float32 0/1 (n,18)), the layout of
+    the ``--data`` file of ``evaluate loglik_celeba``.  One coloured blob per canvas; its colour and size follow the first
+    attributes, so the two modalities are not independent.  Deterministic per seed, no image is empty."""
+    g = torch.Generator().manual_seed(seed)
+    images = torch.zeros(n, 3, 64, 64, dtype=torch.uint8)
+    attrs = (torch.rand(n, 18, generator=g) < 0.3).to(torch.float32)
+    for i in range(n):
+        w = 16 + 8 * int(attrs[i, 0]) + 4 * int(attrs[i, 1])
+        y, x = (int(v) for v in torch.randint(0, 64 - w + 1, (2,), generator=g))
+        blob = 64 + (torch.rand(3, w, w, generator=g) * 127).to(torch.uint8)          # >= 64: never empty
+        blob[int(attrs[i, 2])] += 64
+        images[i, :, y:y + w, x:x + w] = blob
+    return images, attrs
+
+
 class DeviceBatcher:
     """Iterates ``(image fp32, second modality)`` device batches over a uint8 image dataset.
 

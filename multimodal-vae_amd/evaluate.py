@@ -212,6 +212,7 @@ test_celeba.__test__ = False              # not a pytest test
 
 IW_ROWS = 4096          # particle rows (examples x particles) per scoring call: the plan and workspace of one chunk
 IW_ROWS_MNIST = 65536   # ... of the fused MNIST scorer: no plan or workspace per chunk, 32 rows per workgroup (2048 workgroups a call)
+IW_ROWS_CELEBA = 512    # ... of the CelebA scorer: the one-pass workspace of a 512-row plan (mmvae_celeba_iw_workspace_bytes) stays below 1 GiB
 POSTERIORS = ("joint", "image", "text")
 
 
@@ -255,16 +256,30 @@ def _mnist_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
     _iw_call("mmvae_mnist_iw_score", st.plan(1), ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)   # any bound plan: no row limit
 
 
+def _celeba_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
+    from ._lib import ptr
+    _iw_call("mmvae_celeba_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)
+
+
 _FAMILIES = {
     "multimnist": _Family("multimnist", 4, 12, (1, 50, 50), IW_ROWS, _mm_score,
                           lambda st, rows: _iw_call("mmvae_mm_iw_workspace_bytes", st.plan(rows))),
     "mnist": _Family("mnist", 1, 10, (784,), IW_ROWS_MNIST, _mnist_score, lambda st, rows: 0),
+    # the 18 attributes are 18 "text positions" of V = 2 classes: words [rows][18][2] = (log(1 - p), log p), targets 0 / 1
+    "celeba": _Family("celeba", 18, 2, (3, 64, 64), IW_ROWS_CELEBA, _celeba_score,
+                      lambda st, rows: _iw_call("mmvae_celeba_iw_workspace_bytes", st.plan(rows))),
 }
 
 
 def _family(model):
+    from .celeba import MultimodalVAE as CelebaVAE
     from .mnist import MultimodalVAE as MnistVAE
-    return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "multimnist"]
+    return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else "multimnist"]
+
+
+def _posterior(posterior):
+    """"attrs" (CelebA's name of the second modality) is a synonym of "text"."""
+    return "text" if posterior == "attrs" else posterior
 
 
 @torch.no_grad()
@@ -276,6 +291,10 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     int64, ``mu`` / ``logvar`` (B, n_latents), all on the GPU.  A mnist ``MultimodalVAE`` takes ``image`` (B,784) (or anything
     that reshapes to it) and the labels ``text`` (B,) int64: one fused fp32 kernel scores its particles (mmvae_mnist_iw_score;
     784 pixels, one text position of 10 classes, no greedy feedback), everything else below is the same.
+    A celeba ``MultimodalVAE`` takes ``image`` (B,3,64,64) and the attributes ``text`` (B,18) with values 0 / 1 (any dtype; they
+    are the int64 targets): mmvae_celeba_iw_score runs the bf16 image decoder and scores 3x64x64 logits, log p(y|z) is the sum
+    over the 18 attributes of y*a - softplus(a) on the attribute decoder's fp32 logit a.  The result keys keep their names: the
+    y / "text" columns are the attribute terms.
     Particles z_k = mu + exp(logvar/2) eps_k, k = 1..K, with eps keyed by (seed, first_row + example, particle, dimension) only, so a particle does not depend on the batch it comes
     in or on how the K particles are split into calls.  With
         log w_k^x = log p(x|z_k) + log p(z_k) - log q(z_k)       (y, xy alike)
@@ -346,16 +365,22 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
 
 def _proposal(model, image, text, posterior):
     """(mu, logvar) of the eval-mode encoders + ProductOfExperts over the posterior's modalities (no decoder runs)."""
-    image = image.reshape(image.shape[0], *_family(model).image_shape)
+    fam = _family(model)
+    image = image.reshape(image.shape[0], *fam.image_shape)
+    posterior = _posterior(posterior)
+    if fam.name == "celeba":
+        second = (lambda t: model.attrs_encoder(t.float()))        # the (B,18) attributes as float
+    else:
+        second = model.text_encoder
     if posterior == "joint":
         im_mu, im_lv = model.image_encoder(image)
-        tx_mu, tx_lv = model.text_encoder(text)
+        tx_mu, tx_lv = second(text)
         mu, lv = torch.stack((im_mu, tx_mu), dim=0), torch.stack((im_lv, tx_lv), dim=0)
     elif posterior == "image":
         mu, lv = model.image_encoder(image)
         mu, lv = mu.unsqueeze(0), lv.unsqueeze(0)
     elif posterior == "text":
-        mu, lv = model.text_encoder(text)
+        mu, lv = second(text)
         mu, lv = mu.unsqueeze(0), lv.unsqueeze(0)
     else:
         raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
@@ -367,7 +392,8 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
     """Dataset means of the importance-sampled log p^(x), log p^(y), log p^(x, y) (``iw_estimate``) with the proposal of
     one posterior ("joint": q(z|x,y), "image": q(z|x), "text": q(z|y)), and of the two reconstruction NLLs.
 
-    ``model``: a multimnist or a mnist ``MultimodalVAE`` (``iw_estimate``).  It runs in eval mode (BatchNorm running
+    ``model``: a multimnist, mnist or celeba ``MultimodalVAE`` (``iw_estimate``; a CelebA loader yields (image, (B,18) attributes),
+    ``posterior="attrs"`` is a synonym of "text", and ``log_py`` / ``text_nll`` are the attribute terms).  It runs in eval mode (BatchNorm running
     statistics, no dropout); per batch only the encoders and the experts run to form the proposal, then the particle chunks.  Nothing is read back to the host until the end.  Unlike the reference's
     multimnist/loglikelihood.py, the bounds weight each particle by p(z)/q(z) and take the log-sum-exp (see ``iw_estimate``);
     ``image_nll`` / ``text_nll`` are the reference's quantity (mean over particles of the summed reconstruction NLL), without
@@ -376,6 +402,7 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
     (CPU tensors, columns x, y, xy)."""
     if not use_cuda:
         raise ValueError("log_marginal runs on the GPU (the HIP kernels); there is no CPU path")
+    posterior = _posterior(posterior)
     if posterior not in POSTERIORS:
         raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
     model.eval()
@@ -464,11 +491,83 @@ def _parser():
     src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic MultiMNIST-shaped examples instead of files')
     pl.add_argument('--seed', type=int, default=0, help='seed of the particles')
     pl.add_argument('--json', type=str, default=None, help='write the bounds to this file')
+    # celeba/loglikelihood.py's flags and defaults, plus the ones `loglik` adds
+    pc = sub.add_parser("loglik_celeba", help="celeba/loglikelihood.py + importance-sampled log p(x), log p(y)")
+    pc.add_argument('model_path', type=str, help='path to trained model file')
+    mode = pc.add_mutually_exclusive_group()
+    mode.add_argument('--image_only', action='store_true', default=False,
+                      help='compute NLL of test data using reconstructions from image only')
+    mode.add_argument('--attrs_only', action='store_true', default=False,
+                      help='compute NLL of test data using reconstructions from attributes only')
+    mode.add_argument('--all', action='store_true', default=False, help='all three posteriors (the paper\'s table)')
+    pc.add_argument('--n_samples', type=int, default=100, help='number of samples to use to estimate the ELBO')
+    pc.add_argument('--cuda', action='store_true', default=False, help='accepted for compatibility: the kernels run on the GPU')
+    pc.add_argument('--batch_size', type=int, default=64)
+    src = pc.add_mutually_exclusive_group()
+    src.add_argument('--data', type=str, default=None, metavar='FILE.pt',
+                     help='a .pt file of (uint8 images (N,3,64,64), attributes (N,18) with values 0 / 1)')
+    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic CelebA-shaped examples instead of a file')
+    pc.add_argument('--seed', type=int, default=0, help='seed of the particles')
+    pc.add_argument('--json', type=str, default=None, help='write the bounds to this file')
     return parser
 
 
-def _loglik_main(args):
+def _report(vae, loader, posts, args, second):
+    """Runs ``log_marginal`` per posterior, prints the reference's NLL line and the bounds, writes ``--json``."""
     import json
+    table = {}
+    for post in posts:
+        r = log_marginal(vae, loader, n_particles=args.n_samples, posterior=post, seed=args.seed)
+        table[post] = r
+        mess = r["ess"].double().mean(0)
+        print('\nTest Image NLL: {:.4f}\tTest {} NLL: {:.4f}'.format(r["image_nll"], second, r["text_nll"]))
+        print('[{} posterior, K = {}] log p(x) >= {:.4f}\tlog p(y) >= {:.4f}\tlog p(x,y) >= {:.4f}\t'
+              'mean ESS x / y / xy: {:.2f} / {:.2f} / {:.2f}'.format(post, args.n_samples, r["log_px"], r["log_py"], r["log_pxy"],
+                                                                    *mess.tolist()))
+    if args.json:
+        out = {"n_samples": args.n_samples, "n_examples": table[posts[0]]["n"], "seed": args.seed}
+        for post, r in table.items():
+            out[post] = {k: r[k] for k in ("log_px", "log_py", "log_pxy", "image_nll", "text_nll")}
+            out[post]["mean_ess"] = r["ess"].double().mean(0).tolist()
+        with open(args.json, 'w') as fp:
+            json.dump(out, fp, indent=1)
+    return table
+
+
+def load_celeba_eval_file(path):
+    """The ``--data`` file of ``loglik_celeba``: (uint8 images (N,3,64,64), attributes (N,18)) -> (uint8 images, float32
+    attributes).  Attributes other than 0 / 1 are refused here, on the host: the scorer indexes (log(1 - p), log p) with them."""
+    x, a = torch.load(path, weights_only=False)
+    x, a = torch.as_tensor(x), torch.as_tensor(a)
+    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 64, 64):
+        raise ValueError("%s: images must be uint8 (N,3,64,64) (got %s %s)" % (path, x.dtype, tuple(x.shape)))
+    if a.dim() != 2 or a.shape[0] != x.shape[0] or a.shape[1] != 18:
+        raise ValueError("%s: attributes must be (N,18) for the N = %d images (got %s)" % (path, x.shape[0], tuple(a.shape)))
+    a = a.float()
+    if not bool(((a == 0) | (a == 1)).all()):
+        raise ValueError("%s: every attribute must be 0 or 1" % path)
+    return x, a
+
+
+def _loglik_celeba_main(args):
+    """`loglik_celeba`: the result keys (and the JSON layout) are those of `loglik`; ``log_py`` / ``text_nll`` are the attribute
+    terms and the attribute-only posterior is filed under "text"."""
+    from . import data as D
+    from .celeba import load_checkpoint
+    if args.synthetic > 0:
+        x, a = D.synthetic_celeba(args.synthetic, seed=args.seed)
+    elif args.data:
+        x, a = load_celeba_eval_file(args.data)
+    else:
+        raise SystemExit("loglik_celeba: give --data FILE.pt or --synthetic N")
+    x = x.float().div_(255.0)                                     # transforms.ToTensor()
+    loader = [(x[i:i + args.batch_size], a[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    vae = load_checkpoint(args.model_path, use_cuda=True)
+    posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.attrs_only else ("joint",)
+    return _report(vae, loader, posts, args, "Attrs")
+
+
+def _loglik_main(args):
     from . import data as D
     from .utils import charlist_tensor
     if args.dataset == "mnist":
@@ -490,23 +589,7 @@ def _loglik_main(args):
     loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
     vae = load_checkpoint(args.model_path, use_cuda=True)
     posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
-    table = {}
-    for post in posts:
-        r = log_marginal(vae, loader, n_particles=args.n_samples, posterior=post, seed=args.seed)
-        table[post] = r
-        mess = r["ess"].double().mean(0)
-        print('\nTest Image NLL: {:.4f}\tTest Text NLL: {:.4f}'.format(r["image_nll"], r["text_nll"]))
-        print('[{} posterior, K = {}] log p(x) >= {:.4f}\tlog p(y) >= {:.4f}\tlog p(x,y) >= {:.4f}\t'
-              'mean ESS x / y / xy: {:.2f} / {:.2f} / {:.2f}'.format(post, args.n_samples, r["log_px"], r["log_py"], r["log_pxy"],
-                                                                    *mess.tolist()))
-    if args.json:
-        out = {"n_samples": args.n_samples, "n_examples": table[posts[0]]["n"], "seed": args.seed}
-        for post, r in table.items():
-            out[post] = {k: r[k] for k in ("log_px", "log_py", "log_pxy", "image_nll", "text_nll")}
-            out[post]["mean_ess"] = r["ess"].double().mean(0).tolist()
-        with open(args.json, 'w') as fp:
-            json.dump(out, fp, indent=1)
-    return table
+    return _report(vae, loader, posts, args, "Text")
 
 
 def _main(argv=None):
@@ -516,6 +599,8 @@ def _main(argv=None):
     args = _parser().parse_args(argv)
     if args.cmd == "loglik":
         return _loglik_main(args)
+    if args.cmd == "loglik_celeba":
+        return _loglik_celeba_main(args)
     vae = load_checkpoint(args.model_path, use_cuda=True)
     image = text = None
     if args.condition_on_image:

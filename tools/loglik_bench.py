@@ -1,10 +1,12 @@
 """Rate of the importance-sampled evaluation (evaluate.iw_estimate / marginal_table) against a compute_nll-style loop.
 
-    python tools/loglik_bench.py [--dataset multimnist|mnist] [--batch 64] [--particles 1000] [--loop_particles 100] [--batches 4]
+    python tools/loglik_bench.py [--dataset multimnist|mnist|celeba] [--batch 64] [--particles 1000] [--loop_particles 100] [--batches 4]
                                  [--table_examples 10000]
 
 --dataset mnist (``main_mnist``): the fused fp32 scorer mmvae_mnist_iw_score against an unfused batched chain of the drop-in
-decoder modules + torch ops, see there.  The rest of this text is the MultiMNIST mode.
+decoder modules + torch ops, see there.  --dataset celeba (``main_celeba``): mmvae_celeba_iw_score against the unfused chain
+``vae.image_decoder`` / ``vae.attrs_decoder`` + torch ops on the same particles, see there.  The rest of this text is the
+MultiMNIST mode.
 
 Prints, at batch B:
   * particles/s of iw_estimate at K = --particles (whole batches, device-synchronised wall clock after a warm-up batch);
@@ -174,10 +176,132 @@ def main_mnist(args):
                " / ".join("%.2f" % v for v in r["ess"].double().mean(0).tolist())))
 
 
+def main_celeba(args):
+    """CelebA: particles/s of
+      * ``iw_estimate`` on mmvae_celeba_iw_score (particles -> bf16 decoder body -> scoring tail + fp32 attribute scorer ->
+        accumulate -> finalize);
+      * the same pipeline with the scoring call replaced by the unfused chain a user could write without it: ``vae.image_decoder``
+        and ``vae.attrs_decoder`` called once on all rows of the chunk, then torch ops on the probabilities they return
+        (-binary_cross_entropy per element, summed per row; (log(1 - p), log p) of the attributes as the words).  Same
+        particles, same chunks of at most IW_ROWS_CELEBA rows, same accumulator;
+      * the two scoring steps alone on one chunk (device events), and the TFLOP/s of the image decoder's algorithmic count
+        (2 x multiply-adds of upsample + the four transposed convolutions) over the scoring call's time.
+    The two pipelines alternate ``--repeats`` times after a warm-up of both; their log p^ are compared on the first batch."""
+    import ctypes as C
+    import torch.nn.functional as F
+    from multimodal_vae_amd import celeba as M, data as Dd
+    from multimodal_vae_amd._lib import call, ptr
+    from multimodal_vae_amd.evaluate import iw_estimate, _proposal, iw_chunks, IW_ROWS_CELEBA
+    from oracle import mmvae_ref as R
+    dev = torch.device("cuda:0")
+    D, B, K = 100, args.batch, args.particles
+    vae = M.MultimodalVAE(D)
+    vae.load_state_dict(R.formula_params("celeba", D), strict=True)
+    vae.cuda().eval()
+    st = vae._core.sync(dev)
+    x, t = Dd.synthetic_celeba(B * (args.batches + 1), seed=0)
+    x = x.float().div_(255.0)
+    batches = [(x[i:i + B].to(dev), t[i:i + B].to(dev)) for i in range(0, B * (args.batches + 1), B)]
+    f32 = dict(dtype=torch.float32, device=dev)
+    # multiply-adds per particle: Linear(D, 6400), ConvTranspose2d 5x5x256 -> 8x8x128 (every input pixel meets all 16 taps),
+    # 8x8x128 -> 16x16x64, 16x16x64 -> 32x32x32, 32x32x32 -> 64x64x3 (stride 2: 4 taps per output pixel)
+    flops_particle = 2.0 * (D * 6400 + 25 * 256 * 128 * 16 + 256 * 128 * 64 * 4 + 1024 * 64 * 32 * 4 + 4096 * 32 * 3 * 4)
+
+    def stream():
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def unfused_score(z, image, nr, nk):
+        """log p(x|z) (nr*nk,) and the words (nr*nk, 18, 2) from the decoder modules + torch ops."""
+        p = vae.image_decoder(z)
+        pa = vae.attrs_decoder(z)
+        lx = -F.binary_cross_entropy(p.view(nr, nk, -1), image.reshape(nr, 1, -1).expand(nr, nk, 3 * 64 * 64), reduction="none").sum(2)
+        words = torch.stack([torch.log1p(-pa), torch.log(pa)], 2)
+        return lx.reshape(-1).contiguous(), words.contiguous()
+
+    def run_unfused(i):
+        image, attrs = batches[i]
+        mu, lv = props[i]
+        tgt = attrs.long().contiguous()
+        state = torch.empty(B, 3, 4, **f32)
+        call("mmvae_iw_init", ptr(state), B, stream())
+        for r0, nr, k0, nk in iw_chunks(B, K, IW_ROWS_CELEBA):
+            rows = nr * nk
+            z, lr = torch.empty(rows, D, **f32), torch.empty(rows, **f32)
+            call("mmvae_iw_particles", ptr(mu[r0:]), ptr(lv[r0:]), nr, D, nk, i * B + r0, k0, 0, None, ptr(z), ptr(lr), stream())
+            lx, words = unfused_score(z, image[r0:r0 + nr], nr, nk)
+            call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(tgt[r0:]), 18, 2, ptr(lr), nr, nk, ptr(state[r0:]), None, stream())
+        out = torch.empty(B, 8, **f32)
+        call("mmvae_iw_finalize", ptr(state), B, K, ptr(out), stream())
+        return out[:, 0:3]
+
+    def run_fused(i):
+        return iw_estimate(vae, batches[i][0], batches[i][1], props[i][0], props[i][1], K, first_row=i * B)["log_p"]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(1, len(batches)):
+            fn(i)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    with torch.no_grad():
+        props = [_proposal(vae, im, at, "joint") for im, at in batches]
+        a, b = run_fused(0), run_unfused(0)                     # warm-up of both, and the same numbers from both
+        torch.cuda.synchronize()
+        diff = (a.double() - b.double()).abs().max(0).values.tolist()
+        tf, tu = [], []
+        for _ in range(args.repeats):
+            tf.append(timed(run_fused))
+            tu.append(timed(run_unfused))
+    per = B * K * args.batches
+    rate_f, rate_u = per / min(tf), per / min(tu)
+    chunks = iw_chunks(B, K, IW_ROWS_CELEBA)
+    print("loglik_bench --dataset celeba: B = %d, K = %d, n_latents = %d, %d scoring calls of <= %d rows per batch, %d batches per timing" %
+          (B, K, D, len(chunks), IW_ROWS_CELEBA, args.batches))
+    print("fused   vs unfused log p^ (x, y, xy) of batch 0: max abs difference %s" % " / ".join("%.2e" % v for v in diff))
+    print("iw_estimate, mmvae_celeba_iw_score  %12.0f particles/s  (best of %s s)" % (rate_f, ", ".join("%.4f" % v for v in tf)))
+    print("same pipeline, unfused chain        %12.0f particles/s  (best of %s s)" % (rate_u, ", ".join("%.4f" % v for v in tu)))
+    print("ratio fused / unfused               %.2fx  %s" % (rate_f / rate_u, "" if rate_f >= rate_u else "(THE FUSED SCORER IS SLOWER)"))
+    sys.stdout.flush()
+
+    # ---- the scoring step alone on one chunk (device events, 10 calls each after a warm-up call)
+    with torch.no_grad():
+        r0, nr, k0, nk = chunks[0]
+        rows = nr * nk
+        image = batches[1][0][r0:r0 + nr].contiguous()
+        z, lr = torch.empty(rows, D, **f32), torch.empty(rows, **f32)
+        call("mmvae_iw_particles", ptr(props[1][0]), ptr(props[1][1]), nr, D, nk, 0, 0, 0, None, ptr(z), ptr(lr), stream())
+        lx, words = torch.empty(rows, **f32), torch.empty(rows, 18, 2, **f32)
+        h = st.plan(rows)
+        wsb = call("mmvae_celeba_iw_workspace_bytes", h)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+
+        def fused_score():
+            call("mmvae_celeba_iw_score", h, ptr(ws), wsb, ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream())
+
+        def ev_time(fn, reps=10):
+            fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) * 1e-3 / reps
+        t_fs = ev_time(fused_score)
+        t_us = ev_time(lambda: unfused_score(z, image, nr, nk))
+    print("scoring step alone, %d rows (workspace %.1f MiB):  mmvae_celeba_iw_score %.3f ms (%.1f TFLOP/s of %.2f MFLOP per particle, "
+          "bf16 MFMA)   unfused chain %.3f ms   ratio %.2fx" % (rows, wsb / 2.0 ** 20, t_fs * 1e3, flops_particle * rows / t_fs / 1e12,
+                                                                flops_particle / 1e6, t_us * 1e3, t_us / t_fs))
+    print("achieved in iw_estimate             %.1f TFLOP/s (decoder count over the iw_estimate wall time)" % (flops_particle * rate_f / 1e12))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dataset", choices=("multimnist", "mnist"), default="multimnist")
-    ap.add_argument("--repeats", type=int, default=3, help="mnist: alternations of the fused and the unfused pipeline")
+    ap.add_argument("--dataset", choices=("multimnist", "mnist", "celeba"), default="multimnist")
+    ap.add_argument("--repeats", type=int, default=3, help="mnist, celeba: alternations of the fused and the unfused pipeline")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--particles", type=int, default=1000)
     ap.add_argument("--loop_particles", type=int, default=100)
@@ -188,6 +312,8 @@ def main():
         raise SystemExit("loglik_bench: no GPU (the rates are only measured on the device)")
     if args.dataset == "mnist":
         return main_mnist(args)
+    if args.dataset == "celeba":
+        return main_celeba(args)
     from multimodal_vae_amd import multimnist as M, data as Dd
     from multimodal_vae_amd._lib import call
     from multimodal_vae_amd.evaluate import iw_estimate, marginal_table, _proposal, iw_chunks, IW_ROWS
