@@ -521,6 +521,25 @@ int mmvae_adam_step_packed_ranges(float* p, float* g, float* m, float* v, long l
  * writes up to `cap` pairs to `ranges`, returns their number. */
 int mmvae_mm_early_ranges(const mmvae_mm_t*, long long* ranges, int cap);
 
+/* Nearest-word search over an embedding table (coco/glove.py: closest, closest_batch), fp32 throughout, dim = 300 only.
+ * table [n_words][300], queries [n_queries][300], both 16-byte aligned device memory.
+ * norms: sqnorm[v] = sum_k table[v][k]^2 (run once per table).
+ * nearest: index[q] (int64) = the word that minimises sqnorm[v] - 2 q.w_v -- the dot product one fixed fmaf chain per (query, word)
+ *   pair on the f32-input MFMA, equal scores resolved to the LOWEST index -- and dist[q] = sqrt(sum_k (q_k - w_k)^2) recomputed
+ *   directly for that word.  Bitwise independent of how the queries are batched.  ws: device scratch of
+ *   mmvae_nn_words_workspace_bytes(n_queries, n_words) bytes (MMVAE_ENOSPC when ws_bytes is less).
+ * dists: dist[q][v] = sqrt(sum_k (q_k - w_k)^2) for every word, n_queries <= 8 (closest(vec, n): the caller takes the n smallest).
+ * geometry: query rows per workgroup, words per vocabulary tile, the largest number of vocabulary splits.  The sweep runs on a
+ *   grid of (query blocks) x (splits); a call uses S = max(1, min(max_splits, T, 1024 / ceil(n_queries / query_tile))) splits of
+ *   the T = ceil(n_words / word_tile) tiles, split s covering the tiles [T s / S, T (s + 1) / S) (integer division) -- a
+ *   function of the shape alone.  Tests place their winners against these edges; no result depends on them. */
+long long mmvae_nn_words_workspace_bytes(int n_queries, long long n_words);
+int mmvae_nn_words_geometry(int* query_tile, int* word_tile, int* max_splits);
+int mmvae_nn_words_norms(const float* table, long long n_words, int dim, float* sqnorm, void* stream);
+int mmvae_nn_words_nearest(const float* queries, int n_queries, const float* table, const float* sqnorm, long long n_words, int dim,
+                           void* ws, long long ws_bytes, long long* index, float* dist, void* stream);
+int mmvae_nn_words_dists(const float* queries, int n_queries, const float* table, long long n_words, int dim, float* dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

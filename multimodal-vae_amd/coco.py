@@ -6,13 +6,22 @@ libmmvae_hip.so.  No CPU fallback.  ``FusedTrainer`` = the train() closure body 
 
 GloVe: the reference looks up exactly one vector at run time, ``GloVe('<s>')``, the decoder's first input
 (coco/model.py:271-272; the ``</s>`` pre-fill of :275-277 is overwritten at every position).  It is passed in as ``sos``
-(300 floats) and kept as a non-persistent buffer, so ``state_dict()`` has the reference's keys.  ``generate`` (nearest-word
-decoding over the 2 GB GloVe table) is outside this engine; ``generate_vector`` is ``forward``.
+(300 floats) and kept as a non-persistent buffer, so ``state_dict()`` has the reference's keys.  ``generate_vector`` is
+``forward``.
+
+Words: ``WordTable`` is the reference's ``coco/glove.py`` (``get_word``, ``closest``, ``closest_batch``, ``analogy``) over any
+``(V, 300)`` float32 table, with the search on the device: one fused fp32 MFMA sweep + arg-min per call (csrc/nn_words.hip),
+equal distances resolved to the LOWEST index (the reference's ``torch.sort(...)[1][0]`` leaves ties open).  A model built with
+``words=`` decodes captions to strings in ``generate``; the table is neither a parameter nor a buffer, so ``state_dict()`` is
+unchanged.  ``embed`` is ``coco/utils.py:36-47`` with ``str.split`` as the tokenizer (nltk is not a dependency: punctuation
+stays attached to its word, a deliberate difference).  The table file is one ``.pt`` holding ``(float32 (V,300), list[str])``
+(``save_word_table`` / ``load_word_table``; INTEGRATION.md shows the conversion from torchtext's GloVe cache).
 """
 from __future__ import annotations
 
+import ctypes
 import weakref
-from typing import Optional
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -26,6 +35,139 @@ MAX_WORDS = 102       # coco/utils.py:12-15
 N_EMBEDDING = 300
 N_HIDDENS = 200
 DROP_P = 0.1
+SOS, EOS = '<s>', '</s>'   # coco/utils.py:13-14
+MAX_DISTS = 8              # queries of one mmvae_nn_words_dists call
+
+
+def nn_words_geometry() -> Tuple[int, int, int]:
+    """(query rows per workgroup, words per vocabulary tile, largest number of vocabulary splits) of the search kernels."""
+    tq, tv, ms = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    call("mmvae_nn_words_geometry", ctypes.byref(tq), ctypes.byref(tv), ctypes.byref(ms))
+    return tq.value, tv.value, ms.value
+
+
+class WordTable:
+    """``coco/glove.py``'s ``GloVe`` over a caller-supplied table: ``vectors`` (V, 300) float32, ``itos`` V distinct strings.
+    Keeps the device copy of the table, its squared row norms (computed once, on the device), ``itos`` and ``stoi``.
+    ``device=None`` keeps a host-only table: lookups (``get_word``, ``embed``) work, a search raises (there is no CPU search)."""
+
+    def __init__(self, vectors: torch.Tensor, itos: Sequence[str], device=None):
+        vectors = torch.as_tensor(vectors)
+        if vectors.dim() != 2 or vectors.shape[1] != N_EMBEDDING or vectors.shape[0] < 1:
+            raise MMVAEError("WordTable: vectors must be (V, %d) with V >= 1 (got %s)" % (N_EMBEDDING, tuple(vectors.shape)))
+        if vectors.dtype != torch.float32:
+            raise MMVAEError("WordTable: vectors must be float32 (got %s)" % vectors.dtype)
+        itos = list(itos)
+        if len(itos) != vectors.shape[0]:
+            raise MMVAEError("WordTable: %d words for %d vectors" % (len(itos), vectors.shape[0]))
+        if not all(isinstance(w, str) for w in itos):
+            raise MMVAEError("WordTable: every word must be a str")
+        stoi = {w: i for i, w in enumerate(itos)}
+        if len(stoi) != len(itos):
+            raise MMVAEError("WordTable: duplicate words (%d distinct of %d)" % (len(stoi), len(itos)))
+        if not bool(torch.isfinite(vectors).all()):
+            raise MMVAEError("WordTable: non-finite vector entries")
+        self.itos, self.stoi = itos, stoi
+        self.device = None if device is None else torch.device(device)
+        self.vectors = vectors.detach().contiguous() if self.device is None else vectors.detach().to(self.device).contiguous()
+        self.sqnorm = None
+        if self.device is not None:
+            if self.device.type != "cuda":
+                raise MMVAEError("WordTable: the search runs on a gfx950 GPU only (device=None keeps a host-only table)")
+            self.sqnorm = torch.empty(len(itos), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                call("mmvae_nn_words_norms", ptr(self.vectors), len(itos), N_EMBEDDING, ptr(self.sqnorm), _stream())
+
+    def __len__(self):
+        return len(self.itos)
+
+    def get_word(self, word: str) -> Optional[torch.Tensor]:
+        """coco/glove.py:21-24: the word's vector (on the table's device), or None."""
+        i = self.stoi.get(word)
+        return None if i is None else self.vectors[i]
+
+    def _queries(self, vecs: torch.Tensor) -> torch.Tensor:
+        if self.device is None:
+            raise MMVAEError("WordTable: a host-only table cannot search (build it with device=); there is no CPU fallback")
+        vecs = torch.as_tensor(vecs)
+        if vecs.dim() != 2 or vecs.shape[1] != N_EMBEDDING or vecs.shape[0] < 1:
+            raise MMVAEError("WordTable: queries must be (N, %d) with N >= 1 (got %s)" % (N_EMBEDDING, tuple(vecs.shape)))
+        return vecs.detach().to(device=self.device, dtype=torch.float32).contiguous()
+
+    @torch.no_grad()
+    def nearest(self, vecs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(N, 300) -> (index int64 (N,), dist float32 (N,)) device tensors: per row the nearest word (lowest index among equally
+        near ones) and its Euclidean distance.  The result of a row does not depend on the rows it is batched with."""
+        q = self._queries(vecs)
+        n, v = q.shape[0], len(self.itos)
+        index = torch.empty(n, dtype=torch.int64, device=self.device)
+        dist = torch.empty(n, dtype=torch.float32, device=self.device)
+        wsb = call("mmvae_nn_words_workspace_bytes", n, v)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            call("mmvae_nn_words_nearest", ptr(q), n, ptr(self.vectors), ptr(self.sqnorm), v, N_EMBEDDING, ptr(ws), wsb,
+                 ptr(index), ptr(dist), _stream())
+        return index, dist
+
+    @torch.no_grad()
+    def dists(self, vecs: torch.Tensor) -> torch.Tensor:
+        """(n, 300), n <= 8 -> (n, V) float32: the distance of every word to every row, computed directly (sqrt sum (q - w)^2)."""
+        q = self._queries(vecs)
+        n, v = q.shape[0], len(self.itos)
+        if n > MAX_DISTS:
+            raise MMVAEError("WordTable.dists: at most %d rows per call (got %d)" % (MAX_DISTS, n))
+        out = torch.empty(n, v, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            call("mmvae_nn_words_dists", ptr(q), n, ptr(self.vectors), v, N_EMBEDDING, ptr(out), _stream())
+        return out
+
+    def closest(self, vec: torch.Tensor, n: int = 10) -> List[Tuple[str, float]]:
+        """coco/glove.py:26-39: the n nearest words of one 300-vector as [(word, distance)], nearest first."""
+        d = self.dists(torch.as_tensor(vec).reshape(1, N_EMBEDDING))[0]
+        val, idx = torch.topk(d, min(int(n), d.numel()), largest=False, sorted=True)
+        return [(self.itos[i], float(x)) for i, x in zip(idx.tolist(), val.tolist())]
+
+    def closest_batch(self, vec_batch: torch.Tensor) -> List[str]:
+        """coco/glove.py:41-70: the nearest word of every row of an (N, 300) batch."""
+        index, _ = self.nearest(vec_batch)
+        return [self.itos[i] for i in index.tolist()]
+
+    def analogy(self, w1: str, w2: str, w3: str, n: int = 5, filter_given: bool = True) -> List[Tuple[str, float]]:
+        """coco/glove.py:72-93: the words nearest to w2 - w1 + w3.  The reference's function lacks ``self`` and reads
+        ``self.filter_given``; this is its evident intent: a method whose ``filter_given`` argument drops the three given words,
+        and that looks at n + 3 candidates so that n remain after the drop."""
+        vs = [self.get_word(w) for w in (w1, w2, w3)]
+        for w, v in zip((w1, w2, w3), vs):
+            if v is None:
+                raise KeyError(w)
+        found = self.closest(vs[1] - vs[0] + vs[2], n + 3 if filter_given else n)
+        if filter_given:
+            found = [t for t in found if t[0] not in (w1, w2, w3)]
+        return found[:n]
+
+    def embed(self, sentence: str, tokenizer: Callable[[str], List[str]] = str.split) -> torch.Tensor:
+        """coco/utils.py:36-47: '<s>' + words + '</s>' as a (102, 300) float32 host tensor; at most 100 words are kept, an unknown
+        word and the padding are zero rows.  The default tokenizer is ``str.split`` (the reference's is nltk's word_tokenize)."""
+        words = list(tokenizer(sentence))[:MAX_WORDS - 2]
+        words = [SOS] + words + [EOS]
+        out = torch.zeros(MAX_WORDS, N_EMBEDDING)
+        for i, w in enumerate(words):
+            j = self.stoi.get(w)
+            if j is not None:
+                out[i] = self.vectors[j]
+        return out
+
+
+def save_word_table(path: str, vectors: torch.Tensor, itos: Sequence[str]) -> str:
+    """One ``.pt`` file holding ``(float32 (V,300), list[str])``."""
+    WordTable(torch.as_tensor(vectors), itos)                     # the refusals of the constructor, before anything is written
+    torch.save((torch.as_tensor(vectors).detach().cpu().contiguous(), list(itos)), path)
+    return path
+
+
+def load_word_table(path: str, device=None) -> WordTable:
+    vectors, itos = torch.load(path, map_location="cpu", weights_only=True)
+    return WordTable(vectors, itos, device)
 
 
 def _prep(mod: nn.Module, prefix: str, x: torch.Tensor):
@@ -172,17 +314,24 @@ class TextEncoder(nn.Module):
 class TextDecoder(nn.Module):
     """coco/model.py:248-312: 2-layer GRU regressing one 300-d vector per step, fed back as the next input."""
 
-    def __init__(self, n_latents, n_embedding=N_EMBEDDING, n_hiddens=N_HIDDENS, use_cuda=False, sos=None, steps=MAX_WORDS):
+    def __init__(self, n_latents, n_embedding=N_EMBEDDING, n_hiddens=N_HIDDENS, use_cuda=False, sos=None, steps=MAX_WORDS,
+                 words: Optional[WordTable] = None):
         super().__init__()
         if n_embedding != N_EMBEDDING or n_hiddens != N_HIDDENS:
             raise MMVAEError("the HIP TextDecoder implements n_embedding=300, n_hiddens=200")
         self.z2h = nn.Linear(n_latents, n_hiddens)
         self.gru = nn.GRU(n_embedding + n_latents, n_hiddens, 2, dropout=0.1)
         self.h2o = nn.Linear(n_hiddens + n_latents, n_embedding)
+        if sos is None and words is not None:
+            sos = words.get_word(SOS)
+            if sos is None:
+                raise MMVAEError("TextDecoder: the word table has no '%s' (coco/model.py:268) and no sos= was given" % SOS)
+            sos = sos.detach().cpu()                               # a buffer of the module: it moves with the module
         if sos is None:
             raise MMVAEError("TextDecoder needs sos= the 300-d GloVe vector of '<s>' (coco/model.py:271); the GloVe table "
                              "itself is not part of this engine")
         self.register_buffer("sos", torch.as_tensor(sos, dtype=torch.float32).reshape(n_embedding).clone(), persistent=False)
+        self.words = words                                         # a plain attribute: no parameter, no buffer
         self.use_cuda = use_cuda
         self.n_latents = n_latents
         self.n_embedding = n_embedding
@@ -224,20 +373,40 @@ class TextDecoder(nn.Module):
         """coco/model.py:308-309"""
         return self.forward(z)
 
-    def generate(self, z):
-        raise MMVAEError("TextDecoder.generate (coco/model.py:290-306) decodes vectors to words through the GloVe table, "
-                         "which is not part of this engine; use generate_vector")
+    def generate(self, z, stop_at_eos: bool = False):
+        """coco/model.py:288-304 with a word table attached (``words=``): B strings of ``steps`` nearest words joined by spaces.
+        This is the evident intent of the reference's reshape loop, which indexes ``strings`` out of range as written.
+        ``stop_at_eos=True`` (an addition) cuts every sentence in front of its first '</s>'."""
+        if self.words is None:
+            raise MMVAEError("TextDecoder.generate (coco/model.py:290-306) decodes vectors to words through the GloVe table, "
+                             "which is not part of this engine; use generate_vector")
+        with torch.no_grad():
+            vecs = self.forward(z)                                 # (B, steps, 300)
+            strings = self.words.closest_batch(vecs.reshape(-1, self.n_embedding))
+        return assemble_sentences(strings, vecs.shape[0], vecs.shape[1], stop_at_eos)
+
+
+def assemble_sentences(strings: Sequence[str], batch: int, steps: int, stop_at_eos: bool = False) -> List[str]:
+    """batch * steps words, example-major -> batch sentences (``stop_at_eos``: the words in front of the first '</s>')."""
+    assert len(strings) == batch * steps
+    out = []
+    for i in range(batch):
+        sentence = list(strings[i * steps:(i + 1) * steps])
+        if stop_at_eos and EOS in sentence:
+            sentence = sentence[:sentence.index(EOS)]
+        out.append(' '.join(sentence))
+    return out
 
 
 class MultimodalVAE(nn.Module):
     """coco/model.py:22-90"""
 
-    def __init__(self, n_latents=20, use_cuda=False, sos=None, steps=MAX_WORDS):
+    def __init__(self, n_latents=20, use_cuda=False, sos=None, steps=MAX_WORDS, words: Optional[WordTable] = None):
         super().__init__()
         self.image_encoder = ImageEncoder(n_latents, steps=steps)
         self.image_decoder = ImageDecoder(n_latents, steps=steps)
         self.text_encoder = TextEncoder(n_latents, steps=steps)
-        self.text_decoder = TextDecoder(n_latents, use_cuda=use_cuda, sos=sos, steps=steps)
+        self.text_decoder = TextDecoder(n_latents, use_cuda=use_cuda, sos=sos, steps=steps, words=words)
         self.experts = ProductOfExperts()
         self.n_latents = n_latents
         self.steps = steps
@@ -323,6 +492,19 @@ def loss_function(mu, logvar, recon_image=None, image=None, recon_text=None, tex
 
 
 elbo_loss = loss_function
+
+
+def load_checkpoint(file_path, use_cuda=False, sos=None, words: Optional[WordTable] = None):
+    """coco/train.py:47-61: rebuilds a MultimodalVAE from the checkpoint dict (``state_dict``, ``n_latents``) that
+    ``train_coco`` (or the reference) writes.  The '<s>' vector is not in the state dict (the reference reads it from GloVe
+    at every forward): give ``sos=`` or a word table that has '<s>'."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    n_latents = checkpoint['n_latents'] if 'n_latents' in checkpoint else 100
+    vae = MultimodalVAE(n_latents=n_latents, use_cuda=use_cuda, sos=sos, words=words)
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
 
 
 class FusedTrainer:

@@ -6,6 +6,7 @@
 #include "coco.h"
 #include "plan_base.h"
 #include "iw.h"
+#include "nn_words.h"
 #include <cstring>
 #include <exception>
 
@@ -468,3 +469,36 @@ int mmvae_adam_step_packed(float* p, float* g, float* m, float* v, long long n, 
 }
 
 }  // extern "C"
+
+// ---- nearest-word search over an embedding table (nn_words.h)
+long long mmvae_nn_words_workspace_bytes(int n_queries, long long n_words) {
+    if (n_queries <= 0 || n_words <= 0) return 0;
+    return (long long)nn_words_workspace_bytes(n_queries, n_words);
+}
+int mmvae_nn_words_geometry(int* query_tile, int* word_tile, int* max_splits) {
+    MMVAE_REQUIRE(query_tile && word_tile && max_splits, "nn_words_geometry: null argument");
+    *query_tile = NNW_TQ; *word_tile = NNW_TV; *max_splits = NNW_MAX_SPLITS;
+    return MMVAE_OK;
+}
+int mmvae_nn_words_norms(const float* table, long long n_words, int dim, float* sqnorm, void* s) {
+    MMVAE_REQUIRE(table && sqnorm, "nn_words_norms: null argument");
+    MMVAE_REQUIRE(n_words > 0, "nn_words_norms: n_words = %lld", n_words);
+    MMVAE_REQUIRE(dim == NNW_DIM, "nn_words_norms: dim = %d, the kernels are built for %d", dim, NNW_DIM);
+    return launch_nn_words_norms(table, n_words, sqnorm, S(s));
+}
+int mmvae_nn_words_nearest(const float* queries, int n_queries, const float* table, const float* sqnorm, long long n_words, int dim,
+                           void* ws, long long ws_bytes, long long* index, float* dist, void* s) {
+    MMVAE_REQUIRE(queries && table && sqnorm && ws && index && dist, "nn_words_nearest: null argument");
+    MMVAE_REQUIRE(n_queries > 0 && n_words > 0, "nn_words_nearest: n_queries = %d, n_words = %lld", n_queries, n_words);
+    MMVAE_REQUIRE(dim == NNW_DIM, "nn_words_nearest: dim = %d, the kernels are built for %d", dim, NNW_DIM);
+    const long long need = (long long)nn_words_workspace_bytes(n_queries, n_words);
+    if (ws_bytes < need) { mmvae_set_error("nn_words_nearest: workspace too small (%lld < %lld)", ws_bytes, need); return MMVAE_ENOSPC; }
+    return launch_nn_words_nearest(queries, n_queries, table, sqnorm, n_words, ws, index, dist, S(s));
+}
+int mmvae_nn_words_dists(const float* queries, int n_queries, const float* table, long long n_words, int dim, float* dist, void* s) {
+    MMVAE_REQUIRE(queries && table && dist, "nn_words_dists: null argument");
+    MMVAE_REQUIRE(n_queries > 0 && n_queries <= NNW_MAX_DISTS, "nn_words_dists: n_queries = %d, need 1..%d", n_queries, NNW_MAX_DISTS);
+    MMVAE_REQUIRE(n_words > 0, "nn_words_dists: n_words = %lld", n_words);
+    MMVAE_REQUIRE(dim == NNW_DIM, "nn_words_dists: dim = %d, the kernels are built for %d", dim, NNW_DIM);
+    return launch_nn_words_dists(queries, n_queries, table, n_words, dist, S(s));
+}

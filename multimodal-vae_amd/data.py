@@ -73,6 +73,17 @@ def synthetic_mnist(n: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     return images, labels
 
 
+def synthetic_word_table(n_words: int, seed: int = 0) -> Tuple[torch.Tensor, List[str]]:
+    """GloVe-scaled stand-in for a word table (no GloVe files in this environment): -> (float32 (n_words, 300) with 0.4 * randn
+    entries, n_words distinct strings: '<s>', '</s>', then 'w0', 'w1', ...), the arguments of ``coco.WordTable`` /
+    ``coco.save_word_table``.  Deterministic per seed."""
+    if n_words < 3:
+        raise ValueError("synthetic_word_table: need at least 3 words ('<s>', '</s>' and one more)")
+    g = torch.Generator().manual_seed(seed)
+    vectors = 0.4 * torch.randn(n_words, 300, generator=g)
+    return vectors, ['<s>', '</s>'] + ['w%d' % i for i in range(n_words - 2)]
+
+
 def synthetic_celeba(n: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """CelebA-shaped stand-in (no CelebA files in this environment): -> (uint8 (n,3,64,64), float32 0/1 (n,18)), the layout of
     the ``--data`` file of ``evaluate loglik_celeba``.  One coloured blob per canvas; its colour and size follow the first

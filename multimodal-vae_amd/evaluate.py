@@ -462,6 +462,33 @@ def sample(vae, n_samples=64, image=None, text=None, use_cuda=True):
     return image_recon, text_recon
 
 
+@torch.no_grad()
+def sample_coco(vae, n_samples=64, image=None, text=None, stop_at_eos=False, seed=None):
+    """multimnist/sample.py:80-130 for the COCO family: prior samples (image = text = None) or samples of the conditional
+    posterior -> (images (n,3,32,32) float on the host, n caption strings).  ``image``: (1,3,32,32) float in [0,1]; ``text``:
+    (1,102,300) caption vectors (``WordTable.embed``).  ``vae`` carries the word table (``MultimodalVAE(..., words=)``)."""
+    vae.eval()
+    dev = next(vae.parameters()).device
+    if image is None and text is None:
+        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
+    elif text is None:
+        mu, logvar = vae.encode_image(image.to(dev))
+        std = logvar.mul(0.5).exp()
+    elif image is None:
+        mu, logvar = vae.encode_text(text.to(dev))
+        std = logvar.mul(0.5).exp()
+    else:
+        image_mu, image_logvar = vae.encode_image(image.to(dev))
+        text_mu, text_logvar = vae.encode_text(text.to(dev))
+        mu, logvar = vae.experts(torch.stack((image_mu, text_mu), dim=0), torch.stack((image_logvar, text_logvar), dim=0))
+        std = logvar.mul(0.5).exp()
+    g = None if seed is None else torch.Generator().manual_seed(seed)
+    z = torch.randn(n_samples, vae.n_latents, generator=g).to(dev)
+    z = (z * std.expand_as(z) + mu.expand_as(z)).contiguous()
+    image_recon = vae.decode_image(z).cpu().view(n_samples, 3, 32, 32)
+    return image_recon, vae.text_decoder.generate(z, stop_at_eos=stop_at_eos)
+
+
 def _parser():
     import argparse
     parser = argparse.ArgumentParser(prog="python -m multimodal_vae_amd.evaluate")
@@ -509,7 +536,43 @@ def _parser():
     src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic CelebA-shaped examples instead of a file')
     pc.add_argument('--seed', type=int, default=0, help='seed of the particles')
     pc.add_argument('--json', type=str, default=None, help='write the bounds to this file')
+    # multimnist/sample.py's flags for a checkpoint of train_coco; the captions are decoded through a word table
+    pw = sub.add_parser("sample_coco", help="multimnist/sample.py for the COCO family: images + captions decoded to words")
+    pw.add_argument('model_path', type=str, help='path to a checkpoint written by train_coco')
+    tab = pw.add_mutually_exclusive_group(required=True)
+    tab.add_argument('--words', type=str, default=None, metavar='TABLE.pt', help='word table file (coco.save_word_table)')
+    tab.add_argument('--synthetic_words', type=int, default=0, metavar='V', help='a synthetic table of V words instead of a file')
+    pw.add_argument('--n_samples', type=int, default=64, help='Number of images and captions to sample.')
+    pw.add_argument('--condition_on_image', type=str, default=None, metavar='FILE.pt', help='a .pt file holding a (3,32,32) uint8 or float image')
+    pw.add_argument('--condition_on_text', type=str, default=None, help='a caption, e.g. "a man riding a wave"')
+    pw.add_argument('--stop_at_eos', action='store_true', default=False, help="cut every caption in front of its first '</s>'")
+    pw.add_argument('--out', type=str, default='./results')
+    pw.add_argument('--seed', type=int, default=0, help='seed of the latent samples (and of the synthetic table)')
     return parser
+
+
+def _sample_coco_main(args):
+    import os
+    from . import coco as K, data as D
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if args.synthetic_words > 0:
+        words = K.WordTable(*D.synthetic_word_table(args.synthetic_words, seed=args.seed), device=dev)
+    else:
+        words = K.load_word_table(args.words, dev)
+    vae = K.load_checkpoint(args.model_path, use_cuda=True, words=words)
+    image = text = None
+    if args.condition_on_image:
+        im = torch.load(args.condition_on_image)
+        image = (im.float() / 255.0 if im.dtype == torch.uint8 else im.float()).view(1, 3, 32, 32)
+    if args.condition_on_text:
+        text = words.embed(args.condition_on_text).unsqueeze(0)
+    image_recon, captions = sample_coco(vae, args.n_samples, image, text, stop_at_eos=args.stop_at_eos, seed=args.seed)
+    os.makedirs(args.out, exist_ok=True)
+    torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))
+    with open(os.path.join(args.out, 'sample_text.txt'), 'w') as fp:
+        for c in captions:
+            fp.write('%s\n' % c)
+    return captions
 
 
 def _report(vae, loader, posts, args, second):
@@ -601,6 +664,8 @@ def _main(argv=None):
         return _loglik_main(args)
     if args.cmd == "loglik_celeba":
         return _loglik_celeba_main(args)
+    if args.cmd == "sample_coco":
+        return _sample_coco_main(args)
     vae = load_checkpoint(args.model_path, use_cuda=True)
     image = text = None
     if args.condition_on_image:
