@@ -540,6 +540,29 @@ int mmvae_nn_words_nearest(const float* queries, int n_queries, const float* tab
                            void* ws, long long ws_bytes, long long* index, float* dist, void* stream);
 int mmvae_nn_words_dists(const float* queries, int n_queries, const float* table, long long n_words, int dim, float* dist, void* stream);
 
+/* Gaussian-kernel maximum mean discrepancy (coco/model.py:385-402: compute_kernel, compute_mmd), fp32 in and out.
+ * x [n_x][dim], y [n_y][dim] row-major device memory, 1 <= dim <= max_dim (256), 1 <= n_x, n_y <= 65536; x == y is allowed.
+ *   k(a, b) = exp(-(sum_k (a_k - b_k)^2 / dim) / dim), the squared distance from coordinate differences in a fixed order
+ *   MMD     = mean_ij k(x_i, x_j) + mean_ij k(y_i, y_j) - 2 mean_ij k(x_i, y_j), diagonals included
+ * mmd: ONE call gives out4 = {mean Kxx, mean Kyy, mean Kxy, MMD} and, where the pointer is not null, dx = dMMD/dx [n_x][dim] and
+ *   dy = dMMD/dy [n_y][dim] (with both null the value alone, at three quarters of the pairs).  Two launches: a sweep over the
+ *   pairs that writes per-(split, row) float64 partial sums into ws, and a fold in float64 in a fixed order, rounded to fp32
+ *   once.  No atomics: the result depends on the shape alone and two calls give identical bits.  ws: device scratch of
+ *   mmvae_mmd_workspace_bytes(n_x, n_y, dim) bytes, 8-byte aligned, every byte the fold reads is rewritten by each call
+ *   (MMVAE_ENOSPC when ws_bytes is less; workspace_bytes is 0 for sizes out of range).
+ * kernel_matrix: k [n_x][n_y] = k(x_i, y_j) with the per-pair arithmetic of mmd.
+ * geometry: rows per workgroup, rows of x or y per column tile, max_dim.  The sweep's grid is (row tiles) x (column splits):
+ *   the row tiles are the ceil(n_x / row_tile) tiles of x followed by the ceil(n_y / row_tile) tiles of y (R in all); the columns
+ *   of class c in {x, y} are its T_c = ceil(n_c / col_tile) tiles, cut into S_c = max(1, min(T_c, 64, 1024 / R)) splits (integer
+ *   division), split s covering the tiles [T_c s / S_c, T_c (s + 1) / S_c) -- a function of (n_x, n_y) alone.  Inside a tile the
+ *   columns are summed 8 at a time in fp32, everything above that in float64.  Tests place their edges against these numbers;
+ *   no result depends on them beyond the last bits of a real-valued sum. */
+int mmvae_mmd_geometry(int* row_tile, int* col_tile, int* max_dim);
+long long mmvae_mmd_workspace_bytes(int n_x, int n_y, int dim);
+int mmvae_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* ws, long long ws_bytes,
+              float* out4, float* dx_or_null, float* dy_or_null, void* stream);
+int mmvae_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, int dim, float* k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

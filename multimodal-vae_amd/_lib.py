@@ -237,6 +237,10 @@ SIGNATURES["mmvae_nn_words_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.PO
 SIGNATURES["mmvae_nn_words_norms"] = (_I, [_P, _LL, _I, _P, _P])
 SIGNATURES["mmvae_nn_words_nearest"] = (_I, [_P, _I, _P, _P, _LL, _I, _P, _LL, _P, _P, _P])
 SIGNATURES["mmvae_nn_words_dists"] = (_I, [_P, _I, _P, _LL, _I, _P, _P])
+SIGNATURES["mmvae_mmd_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)])
+SIGNATURES["mmvae_mmd_workspace_bytes"] = (_LL, [_I, _I, _I])
+SIGNATURES["mmvae_mmd"] = (_I, [_P, _I, _P, _I, _I, _P, _LL, _P, _P, _P, _P])
+SIGNATURES["mmvae_mmd_kernel_matrix"] = (_I, [_P, _I, _P, _I, _I, _P, _P])
 _STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
 
 _lib = None

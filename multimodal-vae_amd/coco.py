@@ -16,6 +16,10 @@ equal distances resolved to the LOWEST index (the reference's ``torch.sort(...)[
 unchanged.  ``embed`` is ``coco/utils.py:36-47`` with ``str.split`` as the tokenizer (nltk is not a dependency: punctuation
 stays attached to its word, a deliberate difference).  The table file is one ``.pt`` holding ``(float32 (V,300), list[str])``
 (``save_word_table`` / ``load_word_table``; INTEGRATION.md shows the conversion from torchtext's GloVe cache).
+
+InfoVAE: ``InfoVAE`` (coco/model.py:358-382) is ``ImageEncoder`` + ``ImageDecoder`` + ``reparametrize`` under the reference's
+``encoder.`` / ``decoder.`` keys; ``infovae_loss`` is ``coco/train_infovae.py:44-55`` (mean BCE + MMD against prior samples) with
+the MMD term on the fused op of ``mmd.py``; ``compute_mmd`` / ``compute_kernel`` are re-exported from there.
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
 from .core import CocoState, FusedCocoStep, StepOutputs
+from .mmd import compute_kernel, compute_mmd, mmd_terms  # noqa: F401  (coco/model.py:385-402)
 from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
                          _gscale, _seed_from_torch, _stream, swish)
 
@@ -492,6 +497,45 @@ def loss_function(mu, logvar, recon_image=None, image=None, recon_text=None, tex
 
 
 elbo_loss = loss_function
+
+
+class InfoVAE(nn.Module):
+    """coco/model.py:358-382.  ``encoder`` / ``decoder`` are the stand-alone HIP modules above, each on its own core, so
+    ``state_dict()`` has the reference's keys (``encoder.features.0.weight`` ... ``decoder.hallucinate.9.weight``) and
+    ``optim.Adam(vae.parameters())`` steps the ``nn.Parameter``s the kernels read."""
+
+    def __init__(self, n_latents=20):
+        super().__init__()
+        self.encoder = ImageEncoder(n_latents)
+        self.decoder = ImageDecoder(n_latents)
+        self.n_latents = n_latents
+
+    def encode(self, x, masks=None):
+        return self.encoder(x, masks)
+
+    reparametrize = MultimodalVAE.reparametrize                    # coco/model.py:368-374 is :38-44: sample in training, mu in eval
+
+    def decode(self, z):
+        return self.decoder(z)
+
+    def forward(self, x, eps=None, enc_masks=None):
+        mu, logvar = self.encode(x, enc_masks)
+        z = self.reparametrize(mu, logvar, eps)
+        return self.decode(z), z
+
+
+TRUE_SAMPLES_STREAM = 5    # Philox stream of infovae_loss's prior samples (1: reparametrize, 2-4: the dropout masks)
+
+
+def infovae_loss(recon_x, x, z, true_samples: Optional[torch.Tensor] = None):
+    """coco/train_infovae.py:44-55: mean BCE + MMD(true_samples, z), ``true_samples`` ~ N(0, I) of z's shape, drawn on the device
+    (seeded from torch's generator) unless given."""
+    BCE = _BCEMeanFn.apply(recon_x.reshape(recon_x.shape[0], -1), x.reshape(x.shape[0], -1))
+    if true_samples is None:
+        true_samples = torch.empty(z.shape[0], z.shape[1], dtype=torch.float32, device=z.device)
+        call("mmvae_normal", ptr(true_samples), true_samples.numel(), _seed_from_torch(), None, TRUE_SAMPLES_STREAM, _stream())
+    MMD = compute_mmd(true_samples, z)
+    return BCE + MMD
 
 
 def load_checkpoint(file_path, use_cuda=False, sos=None, words: Optional[WordTable] = None):

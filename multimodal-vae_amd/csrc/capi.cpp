@@ -7,6 +7,7 @@
 #include "plan_base.h"
 #include "iw.h"
 #include "nn_words.h"
+#include "mmd.h"
 #include <cstring>
 #include <exception>
 
@@ -501,4 +502,39 @@ int mmvae_nn_words_dists(const float* queries, int n_queries, const float* table
     MMVAE_REQUIRE(n_words > 0, "nn_words_dists: n_words = %lld", n_words);
     MMVAE_REQUIRE(dim == NNW_DIM, "nn_words_dists: dim = %d, the kernels are built for %d", dim, NNW_DIM);
     return launch_nn_words_dists(queries, n_queries, table, n_words, dist, S(s));
+}
+
+// ---- Gaussian-kernel MMD, value + both gradients (mmd.h)
+static bool mmd_sizes_ok(const char* what, int n_x, int n_y, int dim) {
+    if (n_x < 1 || n_x > MMD_MAX_N || n_y < 1 || n_y > MMD_MAX_N) {
+        mmvae_set_error("%s: n_x = %d, n_y = %d, need 1..%d", what, n_x, n_y, (int)MMD_MAX_N);
+        return false;
+    }
+    if (dim < 1 || dim > MMD_MAX_DIM) {
+        mmvae_set_error("%s: dim = %d, need 1..%d", what, dim, (int)MMD_MAX_DIM);
+        return false;
+    }
+    return true;
+}
+int mmvae_mmd_geometry(int* row_tile, int* col_tile, int* max_dim) {
+    MMVAE_REQUIRE(row_tile && col_tile && max_dim, "mmd_geometry: null argument");
+    *row_tile = MMD_RT; *col_tile = MMD_CT; *max_dim = MMD_MAX_DIM;
+    return MMVAE_OK;
+}
+long long mmvae_mmd_workspace_bytes(int n_x, int n_y, int dim) {
+    if (n_x < 1 || n_x > MMD_MAX_N || n_y < 1 || n_y > MMD_MAX_N || dim < 1 || dim > MMD_MAX_DIM) return 0;
+    return (long long)mmd_workspace_bytes(n_x, n_y, dim);
+}
+int mmvae_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* ws, long long ws_bytes, float* out4, float* dx, float* dy,
+              void* s) {
+    MMVAE_REQUIRE(x && y && ws && out4, "mmd: null argument");
+    if (!mmd_sizes_ok("mmd", n_x, n_y, dim)) return MMVAE_EINVAL;
+    const long long need = (long long)mmd_workspace_bytes(n_x, n_y, dim);
+    if (ws_bytes < need) { mmvae_set_error("mmd: workspace too small (%lld < %lld)", ws_bytes, need); return MMVAE_ENOSPC; }
+    return launch_mmd(x, n_x, y, n_y, dim, ws, out4, dx, dy, S(s));
+}
+int mmvae_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, int dim, float* k, void* s) {
+    MMVAE_REQUIRE(x && y && k, "mmd_kernel_matrix: null argument");
+    if (!mmd_sizes_ok("mmd_kernel_matrix", n_x, n_y, dim)) return MMVAE_EINVAL;
+    return launch_mmd_kernel_matrix(x, n_x, y, n_y, dim, k, S(s));
 }

@@ -489,6 +489,29 @@ def sample_coco(vae, n_samples=64, image=None, text=None, stop_at_eos=False, see
     return image_recon, vae.text_decoder.generate(z, stop_at_eos=stop_at_eos)
 
 
+@torch.no_grad()
+def latent_mmd(vae, loader, seed=0):
+    """MMD between the aggregate posterior of an ``coco.InfoVAE`` and its prior: encodes every image of ``loader`` (batches of
+    (B,3,32,32) floats in [0,1], or tuples whose first entry is one) in eval mode (z = mu), draws as many N(0, I) samples from
+    ``seed`` and compares the two sets in ONE call of the fused MMD op (``mmd.mmd_terms``; 10,000 x 10,000 pairs need no
+    (N, N, D) tensor).  Prints and returns {"n", "k_prior", "k_posterior", "k_cross", "mmd"}: the means of k(prior, prior),
+    k(z, z), k(prior, z) and MMD = k_prior + k_posterior - 2 k_cross."""
+    from .mmd import mmd_terms
+    vae.eval()
+    dev = next(vae.parameters()).device
+    zs = []
+    for batch in loader:
+        x = batch[0] if isinstance(batch, (tuple, list)) else batch
+        zs.append(vae.encode(x.to(dev).float())[0].clone())
+    z = torch.cat(zs).contiguous()
+    prior = torch.randn(z.shape[0], z.shape[1], generator=torch.Generator().manual_seed(seed)).to(dev)
+    t = mmd_terms(prior, z).cpu().tolist()
+    out = {"n": int(z.shape[0]), "k_prior": t[0], "k_posterior": t[1], "k_cross": t[2], "mmd": t[3]}
+    print('Latent MMD over {} examples: k(prior, prior) {:.6f}\tk(z, z) {:.6f}\tk(prior, z) {:.6f}\tMMD {:.6f}'.format(
+        out["n"], out["k_prior"], out["k_posterior"], out["k_cross"], out["mmd"]))
+    return out
+
+
 def _parser():
     import argparse
     parser = argparse.ArgumentParser(prog="python -m multimodal_vae_amd.evaluate")
@@ -548,7 +571,38 @@ def _parser():
     pw.add_argument('--stop_at_eos', action='store_true', default=False, help="cut every caption in front of its first '</s>'")
     pw.add_argument('--out', type=str, default='./results')
     pw.add_argument('--seed', type=int, default=0, help='seed of the latent samples (and of the synthetic table)')
+    # aggregate posterior against the prior for a checkpoint of train_infovae
+    pm = sub.add_parser("latent_mmd", help="MMD between the encoded test images and the prior, for a checkpoint of train_infovae")
+    pm.add_argument('model_path', type=str, help='path to a checkpoint written by train_infovae')
+    src = pm.add_mutually_exclusive_group()
+    src.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='a .pt file of uint8 images (N,3,32,32)')
+    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic COCO-shaped images instead of a file')
+    pm.add_argument('--batch_size', type=int, default=500)
+    pm.add_argument('--seed', type=int, default=0, help='seed of the prior samples (and of the synthetic images)')
+    pm.add_argument('--json', type=str, default=None, help='write the terms to this file')
     return parser
+
+
+def _latent_mmd_main(args):
+    import json
+    from .train_coco import synthetic_coco
+    from .train_infovae import load_checkpoint
+    if args.synthetic > 0:
+        x = synthetic_coco(args.synthetic, seed=args.seed)[0]
+    elif args.data:
+        x = torch.as_tensor(torch.load(args.data, weights_only=False))
+    else:
+        raise SystemExit("latent_mmd: give --data FILE.pt or --synthetic N")
+    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 32, 32):
+        raise ValueError("latent_mmd: images must be uint8 (N,3,32,32) (got %s %s)" % (x.dtype, tuple(x.shape)))
+    x = x.float().div_(255.0)                                     # transforms.ToTensor()
+    loader = [x[i:i + args.batch_size] for i in range(0, x.shape[0], args.batch_size)]
+    vae = load_checkpoint(args.model_path, use_cuda=True)
+    out = latent_mmd(vae, loader, seed=args.seed)
+    if args.json:
+        with open(args.json, 'w') as fp:
+            json.dump(out, fp, indent=1)
+    return out
 
 
 def _sample_coco_main(args):
@@ -666,6 +720,8 @@ def _main(argv=None):
         return _loglik_celeba_main(args)
     if args.cmd == "sample_coco":
         return _sample_coco_main(args)
+    if args.cmd == "latent_mmd":
+        return _latent_mmd_main(args)
     vae = load_checkpoint(args.model_path, use_cuda=True)
     image = text = None
     if args.condition_on_image:
