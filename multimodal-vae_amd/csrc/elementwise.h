@@ -123,7 +123,7 @@ struct Latent3BwdArgs {
     const float* dz_a;       // [3B][D] (image decoder) may be null
     const float* dz_b;       // [3B][D] (text decoder) may be null
     float kl_coef[3];        // kl_lambda / B (or the MNIST divisor) per pass
-    bf16* d_img_out_bf;      // [2][B][2D]
+    bf16* d_img_out_bf;      // [2][B][2D] (row stride ld_img_out_bf if that is set)
     float* d_img_bias;       // [2D] += column sums over both passes (classifier last bias), may be null
     float* d_txt_out;        // [B][2D] or null
     int sum_img_variants;    // 1: d_img_out_bf is [B][2D] = pass-1 + pass-2 gradient
@@ -132,6 +132,7 @@ struct Latent3BwdArgs {
     float* d_img_out_f32;    // optional fp32 [B][2D] = pass-1 + pass-2 gradient (then d_img_out_bf is not written)
     const float* loss_slots; // optional: the step's [MMVAE_LOSS_SLOTS][16] loss accumulators, summed into loss_out[16] by block 0
     float* loss_out;         // (every loss term must be final when this kernel starts: saves the separate sum_slots launch)
+    int ld_img_out_bf;       // row stride of d_img_out_bf, a multiple of 8 >= 2D whose pad columns the kernel zeroes; 0: 2D, no pad
 };
 int launch_latent3_bwd(const Latent3BwdArgs& a, hipStream_t s);
 

@@ -574,6 +574,7 @@ constexpr int L3B_ROWS = 4;     // one row per thread: B/4 x ceil(D/64) workgrou
 __global__ __launch_bounds__(TPB) void latent3_bwd_kernel(const Latent3BwdArgs a) {
     const Latent3Args& f = a.f;
     const int n = f.B * f.D, D2 = 2 * f.D;
+    const int LI = a.ld_img_out_bf ? a.ld_img_out_bf : D2;      // row stride of d_img_out_bf
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int d = blockIdx.x * 64 + tx;
     __shared__ float red[4][4][64];
@@ -623,13 +624,17 @@ __global__ __launch_bounds__(TPB) void latent3_bwd_kernel(const Latent3BwdArgs a
             a.d_img_out_f32[(size_t)b * D2 + d] = d_im0 + d_im1;
             a.d_img_out_f32[(size_t)b * D2 + f.D + d] = d_il0 + d_il1;
         } else if (a.sum_img_variants) {       // the two variants share one encoder forward: its backward needs the summed gradient
-            a.d_img_out_bf[(size_t)b * D2 + d] = (bf16)(d_im0 + d_im1);
-            a.d_img_out_bf[(size_t)b * D2 + f.D + d] = (bf16)(d_il0 + d_il1);
+            a.d_img_out_bf[(size_t)b * LI + d] = (bf16)(d_im0 + d_im1);
+            a.d_img_out_bf[(size_t)b * LI + f.D + d] = (bf16)(d_il0 + d_il1);
+            // the pad columns sit on the reduction dimension of the data-gradient GEMM: zeroed, not left to the workspace
+            if (d == 0) for (int c = D2; c < LI; ++c) a.d_img_out_bf[(size_t)b * LI + c] = (bf16)0.f;
         } else {
-            a.d_img_out_bf[(size_t)b * D2 + d] = (bf16)d_im0;
-            a.d_img_out_bf[(size_t)b * D2 + f.D + d] = (bf16)d_il0;
-            a.d_img_out_bf[(size_t)(f.B + b) * D2 + d] = (bf16)d_im1;
-            a.d_img_out_bf[(size_t)(f.B + b) * D2 + f.D + d] = (bf16)d_il1;
+            a.d_img_out_bf[(size_t)b * LI + d] = (bf16)d_im0;
+            a.d_img_out_bf[(size_t)b * LI + f.D + d] = (bf16)d_il0;
+            a.d_img_out_bf[(size_t)(f.B + b) * LI + d] = (bf16)d_im1;
+            a.d_img_out_bf[(size_t)(f.B + b) * LI + f.D + d] = (bf16)d_il1;
+            if (d == 0)
+                for (int c = D2; c < LI; ++c) { a.d_img_out_bf[(size_t)b * LI + c] = (bf16)0.f; a.d_img_out_bf[(size_t)(f.B + b) * LI + c] = (bf16)0.f; }
         }
         if (a.d_txt_out) {
             a.d_txt_out[(size_t)b * D2 + d] = d_tm;

@@ -14,6 +14,7 @@ constexpr int IMG = 50, NPIX = 2500;
 
 struct MMPlan : PlanBase {
     int ldz, kx, kz;
+    int lde;        // row stride of the bf16 gradient of the image encoder's output [rows][2D]: round_up(2D, 8), pad columns zero
     ConvL conv[4], convT[4];
     LinL fc[3], up;
     BnL bn[6];
@@ -83,6 +84,7 @@ void build_params(MMPlan& P) {
 void build_plan(MMPlan& P) {
     const int D = P.D;
     P.ldz = round_up(D + 1, 8); P.kz = round_up(D, 32); P.kx = round_up(100 + D, 32);
+    P.lde = round_up(2 * D, 8);
     build_params(P);
     // BatchNorm tables (state_dict order)
     const char* bnn[6] = {"image_encoder.features.3", "image_encoder.features.6", "image_encoder.features.9",
@@ -263,7 +265,7 @@ void carve(MMPlan& P, Workspace& ws) {
     w.patches4 = ws.take<bf16>(B3 * 625 * 16);
     w.d3 = ws.take<bf16>(B3 * 625 * 32); w.d2 = ws.take<bf16>(B3 * 144 * 64); w.d1 = ws.take<bf16>(B3 * 36 * 128);
     w.du = ws.take<bf16>(B3 * 1024);
-    w.d_encout = ws.take<bf16>(B2 * 2 * D); w.d_txtout = ws.take<float>(B * 2 * D);
+    w.d_encout = ws.take<bf16>(B2 * P.lde); w.d_txtout = ws.take<float>(B * 2 * D);
     w.te_dout_bf = ws.take<bf16>(B * round_up(2 * (int)D, 8));
     w.te_dgi_f = ws.take<bf16>(4 * B * 304); w.te_dgh_f = ws.take<bf16>(4 * B * 304); w.te_dgi_r = ws.take<bf16>(B * 304);
     w.dy2 = ws.take<bf16>(B2 * 200); w.dy1 = ws.take<bf16>(B2 * 400);
@@ -360,7 +362,8 @@ int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, cons
     return MMVAE_OK;
 }
 
-// d_out: bf16 [variants*B][2D]; the bias gradient of classifier.6 must already be accumulated by the caller
+// d_out: bf16 [variants*B][lde], columns 2D.. zero (the generic kernels read their operands in 8-column vectors; 2D is a multiple
+// of 8 only when n_latents is a multiple of 4); the bias gradient of classifier.6 must already be accumulated by the caller
 int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, hipStream_t s, bool fuse = false) {
     MMPlan::W& w = P.w;
     const int B = P.B, rows = variants * B, D2 = 2 * P.D;
@@ -372,7 +375,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
         {
             GatherPlan pl = dense_plan(rows, 200, 200, D2);
             WgradParams g = wgrad_of(P, pl, &P.fc[2].gk, 1, rows);
-            g.c.A = w.ay2; g.P = d_out; g.ldp = D2;
+            g.c.A = w.ay2; g.P = d_out; g.ldp = P.lde;
             if (fuse) cls_w->push_back(g);
             else MMVAE_TRY(wgrad_async(P, g, s));
         }
@@ -393,9 +396,9 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
     {   // fc3
         GatherPlan pl = dense_plan(rows, 200, 200, D2);
         WgradParams g = wgrad_of(P, pl, &P.fc[2].gk, 1, rows);
-        g.c.A = w.ay2; g.P = d_out; g.ldp = D2;
+        g.c.A = w.ay2; g.P = d_out; g.ldp = P.lde;
         MMVAE_TRY(wgrad_async(P, g, s));
-        GatherPlan pd = dense_plan(rows, D2, D2, 200);
+        GatherPlan pd = dense_plan(rows, P.lde, P.lde, 200);     // K = lde: the zero pad columns meet the zero pad of the packed weights
         GemmParams d = gemm_of(P, pd, &P.fc[2].pk_dgrad, 1, rows);
         d.c.A = d_out; d.out_bf = w.dy2; d.ldo = 200;
         d.d_r = w.y2; d.d_ld = 200; d.d_act = ACT_SWISH; if (dropout) { d.d_mask = m2; d.d_mask_scale = ms; }
@@ -1084,7 +1087,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     Latent3BwdArgs lb{};
     lb.f = la; lb.dz_a = w.dz_img; lb.dz_b = w.dz_txt;
     for (int k = 0; k < 3; ++k) lb.kl_coef[k] = sk[k] ? 0.f : io.kl_lambda / (float)B;
-    lb.d_img_out_bf = w.d_encout; lb.d_img_bias = P.buf.grads + P.fc[2].b_off; lb.d_txt_out = w.d_txtout;
+    lb.d_img_out_bf = w.d_encout; lb.ld_img_out_bf = P.lde; lb.d_img_bias = P.buf.grads + P.fc[2].b_off; lb.d_txt_out = w.d_txtout;
     lb.loss_slots = w.sums; lb.loss_out = io.sums;      // every loss term is final here (text-decoder NLL joined above)
     if (rc == MMVAE_OK) {
         arm_fork(P);                // the text encoder's backward and classifier.6's weight gradient fork off this kernel
@@ -1122,12 +1125,19 @@ int mm_image_encoder_fwd(MMPlan* P, void* ws, size_t wsb, const float* image, co
     MMVAE_TRY(launch_fill_zero(w.zero_begin, w.zero_bytes, s));
     return enc_fwd(*P, image, 1, m1, m2, training && m1 != nullptr, training, 1, out, s);
 }
+// bf16 copy of x [rows][cols] with row stride ld >= cols, pad columns zero
+static __global__ void cast_rows_pad_kernel(const float* x, int rows, int cols, bf16* out, int ld) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * ld) return;
+    int r = i / ld, c = i - r * ld;
+    out[i] = (bf16)(c < cols ? x[(size_t)r * cols + c] : 0.0f);
+}
 int mm_image_encoder_bwd(MMPlan* P, void* ws, size_t wsb, const float* d_out, const uint8_t* m1, const uint8_t* m2, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
     MMPlan::W& w = P->w;
     const int rows = P->B, D2 = 2 * P->D;
     MMVAE_TRY(plan_zero_gpk(*P, s));
-    hipLaunchKernelGGL(cast_bf_kernel, dim3(ceil_div(rows * D2, 256)), dim3(256), 0, s, d_out, (long long)rows * D2, w.d_encout);
+    hipLaunchKernelGGL(cast_rows_pad_kernel, dim3(ceil_div(rows * P->lde, 256)), dim3(256), 0, s, d_out, rows, D2, w.d_encout, P->lde);
     hipLaunchKernelGGL(colsum_kernel, dim3(ceil_div(D2, 64)), dim3(64), 0, s, d_out, rows, D2, P->buf.grads + P->fc[2].b_off);
     MMVAE_TRY(mmvae_check_launch("image encoder bwd prologue"));
     MMVAE_TRY(enc_bwd(*P, w.d_encout, 1, m1, m2, m1 != nullptr, s));
@@ -1265,7 +1275,7 @@ static bool layer_gemm(MMPlan& P, const std::string& name, GemmParams& g) {
             return true;
         }
         if (name == "enc_fc3_dgrad") {
-            GatherPlan pd = dense_plan(rows, 2 * P.D, 2 * P.D, 200);
+            GatherPlan pd = dense_plan(rows, P.lde, P.lde, 200);
             g = gemm_of(P, pd, &P.fc[2].pk_dgrad, 1, rows);
             g.c.A = w.d_encout; g.out_bf = w.dy2; g.ldo = 200;
             g.d_r = w.y2; g.d_ld = 200; g.d_act = ACT_SWISH; g.d_mask = w.m2; g.d_mask_scale = ms;

@@ -239,9 +239,11 @@ class LayerHarness:
     weights are packed), whose layers the tests replay one at a time on operands of their own.
     state_cls / engine_cls: the family's classes of multimodal_vae_amd.core (default: MultiMNIST); prefix: its mmvae_<prefix>_*
     entry points; ws_names: every name its debug_offset knows; workload: the family's synthetic batch of bench.py; records: the
-    family's list of compared launches."""
+    family's list of compared launches; n_latents: the latent size the plan is built at (the conv layers do not depend on it, the
+    dense layers around the latent do)."""
 
-    def __init__(self, B, state_cls=None, engine_cls=None, prefix="mm", ws_names=None, workload="multimnist", records=None):
+    def __init__(self, B, state_cls=None, engine_cls=None, prefix="mm", ws_names=None, workload="multimnist", records=None,
+                 n_latents=100):
         import multimodal_vae_amd  # noqa: F401
         from multimodal_vae_amd._lib import call
         from multimodal_vae_amd import core
@@ -249,10 +251,11 @@ class LayerHarness:
         from bench import synthetic_batch_for
         self.call = call
         self.B = B
+        self.n_latents = n_latents
         self.prefix = prefix
         self.records = RECORDS if records is None else records
         self.dev = torch.device("cuda:0")
-        self.st = (state_cls or core.MultimnistState)(100, self.dev)
+        self.st = (state_cls or core.MultimnistState)(n_latents, self.dev)
         default_init_(self.st, 1234)
         a, b = synthetic_batch_for(workload, B, 1234)
         self.eng = (engine_cls or core.FusedELBOStep)(self.st, B)

@@ -16,8 +16,8 @@ Batch sizes are read off the dispatch (csrc/convres.hip try_launch_convres, csrc
 from the probe's records that every instantiation reachable with default knobs ran in a compared launch.
 
 The layer launches are the plain forms (GemmParams::tr kind 0).  What stays with the whole-step tests: the staged forms of the
-fused step (kinds 1 and 2), dec_last_fused, conv1.hip's in-step form, the fused classifier tail (mlp_tail.hip), the text kernels
-and the COCO plan (no bench_layer).  The CelebA plan has its own modules: tests/test_gpu_celeba_layers.py and
+fused step (kinds 1 and 2), dec_last_fused, conv1.hip's in-step form, the fused classifier tail (mlp_tail.hip)
+and the COCO plan (no bench_layer); the text kernels have a module of their own, tests/test_gpu_text_modules.py.  The CelebA plan has its own modules: tests/test_gpu_celeba_layers.py and
 tests/test_gpu_celeba_layers_staged.py (mmvae_celeba_bench_layer)."""
 import pytest
 import torch
@@ -33,14 +33,14 @@ BATCHES = LR.BATCHES
 _H = {}
 
 
-def _harness(B):
+def _harness(B, D=100):
     if not torch.cuda.is_available():
         pytest.skip("needs the MI355X")
-    if B not in _H:
+    if (B, D) not in _H:
         _H.clear()
         torch.cuda.empty_cache()
-        _H[B] = LR.LayerHarness(B)
-    return _H[B]
+        _H[(B, D)] = LR.LayerHarness(B, n_latents=D)
+    return _H[(B, D)]
 
 
 # ------------------------------------------------------------------------------------------------ Tier A: forward
@@ -195,18 +195,27 @@ def _colsum_gate(h, N, v, what):
     LR.gate_sums(h.get("tmp_f32", (N,), torch.float32), v.sum(0), v.abs().sum(0), what + " d_colsum")
 
 
-@pytest.mark.parametrize("B", BATCHES)
-def test_dense_layers(B):
+# Latent sizes of the dense layers: 100 at every batch; 20 (the reference's other default: N = 40, K = 20, ldz = 24), 99 (odd: the
+# parameter offsets behind classifier.6 are no multiple of 4 floats, ldz = 104 as at 100) and 127 (the upper limit of
+# mmvae_mm_create: N = 254, K = 127 with the bias in the last column of ldz = 128) at the odd and the even small batch.  At
+# D = 100 the case keeps the id it had before the latent size became a parameter.
+DENSE_CASES = [pytest.param(B, 100, id=str(B)) for B in BATCHES] + [
+    pytest.param(B, D, id="%d-D%d" % (B, D)) for D in (20, 99, 127) for B in (7, 8)]
+
+
+@pytest.mark.parametrize("B,D", DENSE_CASES)
+def test_dense_layers(B, D):
     """The classifier (multimnist/model.py:173-179) and upsample (:195) Linears and their data gradients.  Integer weights, bias
     and operands make the pre-activation outputs (y1, y2, u, tmp_f32) exact; the Swish / keep-mask copies (ay1, ay2, au) and the
     data gradients (times Swish'(y) and the keep mask) take the per-element gate, d_colsum (the bias gradient of the Linear below)
-    the 2^-16 gate.  The keep masks are written by the test."""
-    h = _harness(B)
-    rows, D = 2 * B, 100
+    the 2^-16 gate.  The keep masks are written by the test.  The latent size D sets N = 2D of classifier.6 (enc_fc3), K = 2D of its
+    data gradient, K = D of upsample.0 (dec_up, bias in column D of the ldz-wide z rows) and N = D of its data gradient."""
+    h = _harness(B, D)
+    rows = 2 * B
     pre, up = "image_encoder.classifier.", "image_decoder.upsample.0."
     try:
         for seed in SEEDS:
-            g = LR.gen(seed, 11, B)
+            g = LR.gen(seed, 11, B) if D == 100 else LR.gen(seed, 11, B, D)
             tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
             ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
             keep = lambda shape: (torch.rand(shape, generator=g) < 0.9).to(torch.uint8)
@@ -218,7 +227,7 @@ def test_dense_layers(B):
             m1, m2 = keep((rows, 400)), keep((rows, 200))
             h.put("m1", m1, torch.uint8)
             h.put("m2", m2, torch.uint8)
-            tag = "B=%d seed %d" % (B, seed)
+            tag = "B=%d D=%d seed %d" % (B, D, seed)
 
             # classifier.0 on the NHWC 2x2x256 map shared by both dropout variants (row r reads image r % B); torch flattens NCHW
             a4 = tern((B, 2, 2, 256))
@@ -244,8 +253,11 @@ def test_dense_layers(B):
             _exact(h.get("tmp_f32", (rows, 2 * D), torch.float32), F.linear(x2, W6, b6), "enc_fc3 " + tag)
 
             # data gradients: dy2 = (d_encout W6) * Swish'(y2) * keep2 / 0.9, dy1 = (dy2 W3) * Swish'(y1) * keep1 / 0.9
+            # (d_encout rows are round_up(2D, 8) wide with zero pad columns: the stride the step's latent backward writes)
             de, r2, r1 = tern((rows, 2 * D)), LR.eighths((rows, 200), g), LR.eighths((rows, 400), g)
-            h.put("d_encout", de); h.put("y2", r2); h.put("y1", r1)
+            de_rows = torch.zeros(rows, (2 * D + 7) // 8 * 8, dtype=torch.float64)
+            de_rows[:, :2 * D] = de
+            h.put("d_encout", de_rows); h.put("y2", r2); h.put("y1", r1)
             acc = de @ W6
             v = acc * LR.dswish(r2) * m2 * DROP_SCALE
             h.zero("dy2", rows * 200, torch.bfloat16); h.zero("tmp_f32", 200, torch.float32)
