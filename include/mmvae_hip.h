@@ -563,6 +563,36 @@ int mmvae_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* w
               float* out4, float* dx_or_null, float* dy_or_null, void* stream);
 int mmvae_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, int dim, float* k, void* stream);
 
+/* Incremental sampler for PixelCNN / GatedPixelCNN (coco/model.py:405-585), fp32 storage and accumulation, ONE launch per call.
+ * A model is (gated, n_blocks 0..15, data_channels 1 or 3, hid_dims a multiple of 16 up to 128, out_dims 2..256); sides 1..64, any
+ * batch >= 1.  Everything else is refused (MMVAE_EINVAL) before anything is launched.
+ * params: the model's weights and biases as ONE flat fp32 device vector of param_elems floats, per layer weight (cout, cin, kh, kw)
+ *   then bias, in the order
+ *     PixelCNN:      conv1, blocks[0], blocks[2], ..., conv2, conv4
+ *     GatedPixelCNN: for conv1 and every blocks.blocks[k]: vertical_conv, x_to_h_conv, vertical_gate_conv, horizontal_conv,
+ *                    horizontal_gate_conv, horizontal_output; then conv2, conv4
+ * pack_weights: params -> packed (packed_elems floats, 16-byte aligned), each layer tap-major [tap][cin / 4][cout][4] with cin and
+ *   cout zero-padded to 16, ONLY the taps its mask keeps -- the masks apply whether or not a forward ever zeroed the weights.
+ * sample: uniforms (B, C, H, W) fp32; given (B, C, H, W) int32 levels (clamped to 0..out_dims - 1) or null; the first n_given pixels
+ *   in raster order take `given`, the others are drawn: the smallest v with u < CDF_v of the softmax over the pixel's out_dims
+ *   logits of that channel (logit channel v * C + c), clamped to out_dims - 1.  Writes out_levels (B, C, H, W) int32, out_image =
+ *   level / (out_dims - 1) fp32 and, where not null, out_logits (B, out_dims, C, H, W): the logits every pixel was drawn from.
+ *   n_given = H * W is a teacher-forced evaluation of `given`.  A sample's results depend on (weights, its uniforms, its given,
+ *   n_given) alone -- not on B, not on the tile it lands in; two calls give identical bits.
+ *   ws: device scratch of workspace_bytes, 16-byte aligned, needs no initialisation (MMVAE_ENOSPC when ws_bytes is less;
+ *   workspace_bytes and the elems queries are 0 for arguments out of range).
+ * geometry: samples per workgroup, the largest hid_dims, the largest side. */
+int mmvae_pixelcnn_geometry(int* sample_tile, int* max_hid, int* max_side);
+long long mmvae_pixelcnn_param_elems(int gated, int n_blocks, int data_channels, int hid_dims, int out_dims);
+long long mmvae_pixelcnn_packed_elems(int gated, int n_blocks, int data_channels, int hid_dims, int out_dims);
+int mmvae_pixelcnn_pack_weights(int gated, int n_blocks, int data_channels, int hid_dims, int out_dims, const float* params,
+                                long long n_params, float* packed, void* stream);
+long long mmvae_pixelcnn_workspace_bytes(int gated, int n_blocks, int data_channels, int hid_dims, int out_dims, int batch, int height,
+                                         int width);
+int mmvae_pixelcnn_sample(int gated, int n_blocks, int data_channels, int hid_dims, int out_dims, const float* packed, void* ws,
+                          long long ws_bytes, int batch, int height, int width, const float* uniforms, const int* given_or_null,
+                          int n_given, int* out_levels, float* out_image, float* out_logits_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,12 @@ SIGNATURES["mmvae_mmd_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER
 SIGNATURES["mmvae_mmd_workspace_bytes"] = (_LL, [_I, _I, _I])
 SIGNATURES["mmvae_mmd"] = (_I, [_P, _I, _P, _I, _I, _P, _LL, _P, _P, _P, _P])
 SIGNATURES["mmvae_mmd_kernel_matrix"] = (_I, [_P, _I, _P, _I, _I, _P, _P])
+SIGNATURES["mmvae_pixelcnn_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)])
+SIGNATURES["mmvae_pixelcnn_param_elems"] = (_LL, [_I] * 5)
+SIGNATURES["mmvae_pixelcnn_packed_elems"] = (_LL, [_I] * 5)
+SIGNATURES["mmvae_pixelcnn_pack_weights"] = (_I, [_I] * 5 + [_P, _LL, _P, _P])
+SIGNATURES["mmvae_pixelcnn_workspace_bytes"] = (_LL, [_I] * 8)
+SIGNATURES["mmvae_pixelcnn_sample"] = (_I, [_I] * 5 + [_P, _P, _LL, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P])
 _STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
 
 _lib = None

@@ -8,6 +8,7 @@
 #include "iw.h"
 #include "nn_words.h"
 #include "mmd.h"
+#include "pixelcnn.h"
 #include <cstring>
 #include <exception>
 
@@ -537,4 +538,58 @@ int mmvae_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, in
     MMVAE_REQUIRE(x && y && k, "mmd_kernel_matrix: null argument");
     if (!mmd_sizes_ok("mmd_kernel_matrix", n_x, n_y, dim)) return MMVAE_EINVAL;
     return launch_mmd_kernel_matrix(x, n_x, y, n_y, dim, k, S(s));
+}
+
+// ---- PixelCNN / GatedPixelCNN incremental sampler (pixelcnn.h)
+static bool pcnn_model_ok(const char* what, const PcnnCfg& c) {
+    if (pcnn_cfg_ok(c)) return true;
+    mmvae_set_error("%s: gated = %d, n_blocks = %d, data_channels = %d, hid_dims = %d, out_dims = %d: need n_blocks 0..%d, data_channels 1 or 3, "
+                    "hid_dims a multiple of 16 in 16..%d, out_dims 2..%d", what, c.gated, c.n_blocks, c.channels, c.hid, c.levels,
+                    (int)PCNN_MAX_BLOCKS, (int)PCNN_MAX_HID, (int)PCNN_MAX_LEVELS);
+    return false;
+}
+static bool pcnn_shape_ok(const char* what, int batch, int height, int width) {
+    if (batch >= 1 && height >= 1 && height <= PCNN_MAX_SIDE && width >= 1 && width <= PCNN_MAX_SIDE) return true;
+    mmvae_set_error("%s: batch = %d, height = %d, width = %d: need batch >= 1 and sides 1..%d", what, batch, height, width, (int)PCNN_MAX_SIDE);
+    return false;
+}
+int mmvae_pixelcnn_geometry(int* sample_tile, int* max_hid, int* max_side) {
+    MMVAE_REQUIRE(sample_tile && max_hid && max_side, "pixelcnn_geometry: null argument");
+    *sample_tile = PCNN_TILE; *max_hid = PCNN_MAX_HID; *max_side = PCNN_MAX_SIDE;
+    return MMVAE_OK;
+}
+long long mmvae_pixelcnn_param_elems(int gated, int n_blocks, int channels, int hid, int levels) {
+    const PcnnCfg c{gated, n_blocks, channels, hid, levels};
+    return pcnn_cfg_ok(c) ? pcnn_plan(c, 1)->param_floats : 0;
+}
+long long mmvae_pixelcnn_packed_elems(int gated, int n_blocks, int channels, int hid, int levels) {
+    const PcnnCfg c{gated, n_blocks, channels, hid, levels};
+    return pcnn_cfg_ok(c) ? pcnn_plan(c, 1)->packed_floats : 0;
+}
+int mmvae_pixelcnn_pack_weights(int gated, int n_blocks, int channels, int hid, int levels, const float* params, long long n_params,
+                                float* packed, void* s) {
+    const PcnnCfg c{gated, n_blocks, channels, hid, levels};
+    if (!pcnn_model_ok("pixelcnn_pack_weights", c)) return MMVAE_EINVAL;
+    MMVAE_REQUIRE(params && packed, "pixelcnn_pack_weights: null argument");
+    const long long want = pcnn_plan(c, 1)->param_floats;
+    MMVAE_REQUIRE(n_params == want, "pixelcnn_pack_weights: %lld parameters given, the model has %lld", n_params, want);
+    return guarded([&] { return launch_pcnn_pack(c, params, packed, S(s)); });
+}
+long long mmvae_pixelcnn_workspace_bytes(int gated, int n_blocks, int channels, int hid, int levels, int batch, int height, int width) {
+    const PcnnCfg c{gated, n_blocks, channels, hid, levels};
+    if (!pcnn_cfg_ok(c) || batch < 1 || height < 1 || height > PCNN_MAX_SIDE || width < 1 || width > PCNN_MAX_SIDE) return 0;
+    const long long tiles = (batch + PCNN_TILE - 1) / PCNN_TILE;
+    return (long long)pcnn_header_bytes() + tiles * pcnn_plan(c, width)->slab_floats * (long long)sizeof(float);
+}
+int mmvae_pixelcnn_sample(int gated, int n_blocks, int channels, int hid, int levels, const float* packed, void* ws, long long ws_bytes,
+                          int batch, int height, int width, const float* uniforms, const int* given, int n_given, int* out_levels,
+                          float* out_image, float* out_logits, void* s) {
+    const PcnnCfg c{gated, n_blocks, channels, hid, levels};
+    if (!pcnn_model_ok("pixelcnn_sample", c) || !pcnn_shape_ok("pixelcnn_sample", batch, height, width)) return MMVAE_EINVAL;
+    MMVAE_REQUIRE(packed && ws && uniforms && out_levels && out_image, "pixelcnn_sample: null argument");
+    MMVAE_REQUIRE(n_given >= 0 && n_given <= height * width, "pixelcnn_sample: n_given = %d, need 0..%d", n_given, height * width);
+    MMVAE_REQUIRE(n_given == 0 || given, "pixelcnn_sample: n_given = %d without given", n_given);
+    const long long need = mmvae_pixelcnn_workspace_bytes(gated, n_blocks, channels, hid, levels, batch, height, width);
+    if (ws_bytes < need) { mmvae_set_error("pixelcnn_sample: workspace too small (%lld < %lld)", ws_bytes, need); return MMVAE_ENOSPC; }
+    return guarded([&] { return launch_pcnn_sample(c, packed, ws, batch, height, width, uniforms, given, n_given, out_levels, out_image, out_logits, S(s)); });
 }

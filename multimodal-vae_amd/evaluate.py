@@ -490,6 +490,31 @@ def sample_coco(vae, n_samples=64, image=None, text=None, stop_at_eos=False, see
 
 
 @torch.no_grad()
+def sample_pixelcnn(model, n_samples=64, height=None, width=None, complete=None, rows=0, seed=0):
+    """Images from a ``pixelcnn.PixelCNN`` / ``GatedPixelCNN`` on the device, in one launch of the incremental sampler
+    (``pixelcnn.generate``) -> float32 (n_samples, C, H, W) in [0, 1].  ``complete`` (C, H, W) or (N, C, H, W) uint8: every sample
+    keeps the first ``rows`` rows of (its) image, quantised to the model's levels, and draws the rest."""
+    from . import pixelcnn as PX
+    height = height or getattr(model, "height", None) or 28
+    width = width or getattr(model, "width", None) or height
+    given, n_given = None, 0
+    if complete is not None:
+        im = torch.as_tensor(complete)
+        if im.dtype != torch.uint8 or im.dim() not in (3, 4) or tuple(im.shape[-3:]) != (model.data_channels, height, width):
+            raise ValueError("sample_pixelcnn: --complete must be uint8 (%d, %d, %d) (got %s %s)"
+                             % (model.data_channels, height, width, im.dtype, tuple(im.shape)))
+        if not 0 <= rows <= height:
+            raise ValueError("sample_pixelcnn: rows = %d, need 0..%d" % (rows, height))
+        im = im.view(-1, model.data_channels, height, width)
+        lev = torch.from_numpy(PX.quantisize(im.float().div(255.0).numpy(), model.out_dims)).long()
+        given = lev.expand(n_samples, -1, -1, -1) if lev.shape[0] == 1 else lev[:n_samples]
+        if given.shape[0] != n_samples:
+            raise ValueError("sample_pixelcnn: %d images to complete for %d samples" % (given.shape[0], n_samples))
+        given, n_given = given.contiguous().to(model.conv4.weight.device), rows * width
+    return PX.generate(model, n_samples, height, width, seed=seed, given=given, n_given=n_given).image
+
+
+@torch.no_grad()
 def latent_mmd(vae, loader, seed=0):
     """MMD between the aggregate posterior of an ``coco.InfoVAE`` and its prior: encodes every image of ``loader`` (batches of
     (B,3,32,32) floats in [0,1], or tuples whose first entry is one) in eval mode (z = mu), draws as many N(0, I) samples from
@@ -571,6 +596,16 @@ def _parser():
     pw.add_argument('--stop_at_eos', action='store_true', default=False, help="cut every caption in front of its first '</s>'")
     pw.add_argument('--out', type=str, default='./results')
     pw.add_argument('--seed', type=int, default=0, help='seed of the latent samples (and of the synthetic table)')
+    # images from a checkpoint of train_pixelcnn, in one launch of the incremental sampler
+    pp = sub.add_parser("sample_pixelcnn", help="images from a PixelCNN / GatedPixelCNN checkpoint of train_pixelcnn")
+    pp.add_argument('model_path', type=str, help='path to a checkpoint written by train_pixelcnn')
+    pp.add_argument('--n_samples', type=int, default=64, help='Number of images to sample.')
+    pp.add_argument('--height', type=int, default=None, help="(default: the checkpoint's, else 28)")
+    pp.add_argument('--width', type=int, default=None, help="(default: the checkpoint's, else the height)")
+    pp.add_argument('--complete', type=str, default=None, metavar='FILE.pt', help='a uint8 image (C,H,W) whose first --rows rows are kept')
+    pp.add_argument('--rows', type=int, default=0, metavar='R', help='rows of --complete to keep')
+    pp.add_argument('--seed', type=int, default=0, help='seed of the uniforms')
+    pp.add_argument('--out', type=str, default='./results')
     # aggregate posterior against the prior for a checkpoint of train_infovae
     pm = sub.add_parser("latent_mmd", help="MMD between the encoded test images and the prior, for a checkpoint of train_infovae")
     pm.add_argument('model_path', type=str, help='path to a checkpoint written by train_infovae')
@@ -603,6 +638,17 @@ def _latent_mmd_main(args):
         with open(args.json, 'w') as fp:
             json.dump(out, fp, indent=1)
     return out
+
+
+def _sample_pixelcnn_main(args):
+    import os
+    from .pixelcnn import load_checkpoint
+    model = load_checkpoint(args.model_path, use_cuda=True)
+    complete = torch.load(args.complete, weights_only=False) if args.complete else None
+    image = sample_pixelcnn(model, args.n_samples, args.height, args.width, complete, args.rows, args.seed)
+    os.makedirs(args.out, exist_ok=True)
+    torch.save(image.cpu(), os.path.join(args.out, 'sample_image.pt'))
+    return image
 
 
 def _sample_coco_main(args):
@@ -722,6 +768,8 @@ def _main(argv=None):
         return _sample_coco_main(args)
     if args.cmd == "latent_mmd":
         return _latent_mmd_main(args)
+    if args.cmd == "sample_pixelcnn":
+        return _sample_pixelcnn_main(args)
     vae = load_checkpoint(args.model_path, use_cuda=True)
     image = text = None
     if args.condition_on_image:
