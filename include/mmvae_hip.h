@@ -593,6 +593,30 @@ int mmvae_pixelcnn_sample(int gated, int n_blocks, int data_channels, int hid_di
                           long long ws_bytes, int batch, int height, int width, const float* uniforms, const int* given_or_null,
                           int n_given, int* out_levels, float* out_image, float* out_logits_or_null, void* stream);
 
+/* Causal tap-list convolution for PixelCNN / GatedPixelCNN training (csrc/causal_conv.h): bf16 operands (round to nearest even),
+ * fp32 accumulation, fp32 channels-last activations [batch * height * width][channels].
+ * taps: HOST array of n_taps x {r, c, dy, dx}: kernel cell (r, c) of the (cout, cin, kh, kw) fp32 weight is applied at offset
+ *   (dy, dx); a shifted position outside its own image contributes nothing.  A cell may appear in one tap at most.
+ *   forward:          y[p][co] = bias[co] + sum_t sum_ci x[p + (dy_t, dx_t)][ci] w[co][ci][r_t][c_t]          (bias may be null)
+ *   backward_data:    dx[p][ci] = sum_t sum_co g[p - (dy_t, dx_t)][co] w[co][ci][r_t][c_t]
+ *   backward_weight:  dw[co][ci][r_t][c_t] = sum_p g[p][co] x[p + (dy_t, dx_t)][ci], cells in no tap exactly 0; db[co] = sum_p
+ *                     g[p][co] from the unrounded g; each of dw, db may be null.  Partials per chunk of positions, folded in
+ *                     ascending chunk order: no atomics, two calls give identical bits.
+ *   ws: device scratch of workspace_bytes (0 for arguments out of range), 16-byte aligned, needs no initialisation; the packed
+ *   weights live there for the duration of one call only (MMVAE_ENOSPC when ws_bytes is less).
+ * geometry: positions and channels per workgroup tile, positions per weight-gradient chunk, the largest number of taps, the
+ *   largest |dy|, |dx| and the largest channel count. */
+int mmvae_causal_conv_geometry(int* pos_tile, int* channel_tile, int* wgrad_chunk, int* max_taps, int* max_offset, int* max_channels);
+long long mmvae_causal_conv_workspace_bytes(int batch, int height, int width, int cin, int cout, int kh, int kw, int n_taps);
+int mmvae_causal_conv_forward(const float* x, const float* weight, const float* bias_or_null, float* y, const int* taps, int n_taps,
+                              int batch, int height, int width, int cin, int cout, int kh, int kw, void* ws, long long ws_bytes,
+                              void* stream);
+int mmvae_causal_conv_backward_data(const float* g, const float* weight, float* dx, const int* taps, int n_taps, int batch, int height,
+                                    int width, int cin, int cout, int kh, int kw, void* ws, long long ws_bytes, void* stream);
+int mmvae_causal_conv_backward_weight(const float* g, const float* x, float* dw_or_null, float* db_or_null, const int* taps, int n_taps,
+                                      int batch, int height, int width, int cin, int cout, int kh, int kw, void* ws, long long ws_bytes,
+                                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -247,6 +247,11 @@ SIGNATURES["mmvae_pixelcnn_packed_elems"] = (_LL, [_I] * 5)
 SIGNATURES["mmvae_pixelcnn_pack_weights"] = (_I, [_I] * 5 + [_P, _LL, _P, _P])
 SIGNATURES["mmvae_pixelcnn_workspace_bytes"] = (_LL, [_I] * 8)
 SIGNATURES["mmvae_pixelcnn_sample"] = (_I, [_I] * 5 + [_P, _P, _LL, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P])
+SIGNATURES["mmvae_causal_conv_geometry"] = (_I, [C.POINTER(_I)] * 6)
+SIGNATURES["mmvae_causal_conv_workspace_bytes"] = (_LL, [_I] * 8)
+SIGNATURES["mmvae_causal_conv_forward"] = (_I, [_P, _P, _P, _P, C.POINTER(_I), _I] + [_I] * 7 + [_P, _LL, _P])
+SIGNATURES["mmvae_causal_conv_backward_data"] = (_I, [_P, _P, _P, C.POINTER(_I), _I] + [_I] * 7 + [_P, _LL, _P])
+SIGNATURES["mmvae_causal_conv_backward_weight"] = (_I, [_P, _P, _P, _P, C.POINTER(_I), _I] + [_I] * 7 + [_P, _LL, _P])
 _STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
 
 _lib = None

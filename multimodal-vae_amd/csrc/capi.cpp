@@ -9,6 +9,7 @@
 #include "nn_words.h"
 #include "mmd.h"
 #include "pixelcnn.h"
+#include "causal_conv.h"
 #include <cstring>
 #include <exception>
 
@@ -592,4 +593,50 @@ int mmvae_pixelcnn_sample(int gated, int n_blocks, int channels, int hid, int le
     const long long need = mmvae_pixelcnn_workspace_bytes(gated, n_blocks, channels, hid, levels, batch, height, width);
     if (ws_bytes < need) { mmvae_set_error("pixelcnn_sample: workspace too small (%lld < %lld)", ws_bytes, need); return MMVAE_ENOSPC; }
     return guarded([&] { return launch_pcnn_sample(c, packed, ws, batch, height, width, uniforms, given, n_given, out_levels, out_image, out_logits, S(s)); });
+}
+
+// ---- causal tap-list convolution for PixelCNN training (causal_conv.h)
+int mmvae_causal_conv_geometry(int* pos_tile, int* channel_tile, int* wgrad_chunk, int* max_taps, int* max_offset, int* max_channels) {
+    MMVAE_REQUIRE(pos_tile && channel_tile && wgrad_chunk && max_taps && max_offset && max_channels, "causal_conv_geometry: null argument");
+    *pos_tile = CC_TM; *channel_tile = CC_TN; *wgrad_chunk = CC_CHUNK; *max_taps = CC_MAX_TAPS; *max_offset = CC_MAX_OFF; *max_channels = CC_MAX_CH;
+    return MMVAE_OK;
+}
+static bool cc_sizes_ok(const CcShape& s, int n_taps) {
+    return s.B >= 1 && s.H >= 1 && s.W >= 1 && (long long)s.B * s.H * s.W <= CC_MAX_POS && s.Cin >= 1 && s.Cin <= CC_MAX_CH && s.Cout >= 1 &&
+           s.Cout <= CC_MAX_CH && s.kh >= 1 && s.kw >= 1 && s.kh * s.kw <= CC_MAX_CELLS && n_taps >= 1 && n_taps <= CC_MAX_TAPS;
+}
+long long mmvae_causal_conv_workspace_bytes(int batch, int height, int width, int cin, int cout, int kh, int kw, int n_taps) {
+    const CcShape s{batch, height, width, cin, cout, kh, kw};
+    return cc_sizes_ok(s, n_taps) ? (long long)cc_workspace_bytes(s, n_taps) : 0;
+}
+static int cc_prepare(const char* what, const CcShape& s, const int* taps, int n_taps, const void* ws, long long ws_bytes, CcTaps* t) {
+    MMVAE_TRY(cc_make_taps(what, s, taps, n_taps, t));
+    MMVAE_REQUIRE(ws, "%s: null workspace", what);
+    const long long need = (long long)cc_workspace_bytes(s, n_taps);
+    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
+    return MMVAE_OK;
+}
+int mmvae_causal_conv_forward(const float* x, const float* weight, const float* bias, float* y, const int* taps, int n_taps, int batch,
+                              int height, int width, int cin, int cout, int kh, int kw, void* ws, long long ws_bytes, void* st) {
+    const CcShape s{batch, height, width, cin, cout, kh, kw};
+    CcTaps t;
+    MMVAE_TRY(cc_prepare("causal_conv_forward", s, taps, n_taps, ws, ws_bytes, &t));
+    MMVAE_REQUIRE(x && weight && y, "causal_conv_forward: null argument");
+    return guarded([&] { return launch_cc_forward(s, t, x, weight, bias, y, ws, S(st)); });
+}
+int mmvae_causal_conv_backward_data(const float* g, const float* weight, float* dx, const int* taps, int n_taps, int batch, int height,
+                                    int width, int cin, int cout, int kh, int kw, void* ws, long long ws_bytes, void* st) {
+    const CcShape s{batch, height, width, cin, cout, kh, kw};
+    CcTaps t;
+    MMVAE_TRY(cc_prepare("causal_conv_backward_data", s, taps, n_taps, ws, ws_bytes, &t));
+    MMVAE_REQUIRE(g && weight && dx, "causal_conv_backward_data: null argument");
+    return guarded([&] { return launch_cc_backward_data(s, t, g, weight, dx, ws, S(st)); });
+}
+int mmvae_causal_conv_backward_weight(const float* g, const float* x, float* dw, float* db, const int* taps, int n_taps, int batch, int height,
+                                      int width, int cin, int cout, int kh, int kw, void* ws, long long ws_bytes, void* st) {
+    const CcShape s{batch, height, width, cin, cout, kh, kw};
+    CcTaps t;
+    MMVAE_TRY(cc_prepare("causal_conv_backward_weight", s, taps, n_taps, ws, ws_bytes, &t));
+    MMVAE_REQUIRE(g && (x || !dw), "causal_conv_backward_weight: null argument");
+    return guarded([&] { return launch_cc_backward_weight(s, t, g, x, dw, db, ws, S(st)); });
 }

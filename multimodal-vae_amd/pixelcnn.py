@@ -2,7 +2,9 @@
 sampler for them (csrc/pixelcnn.hip).
 
 The modules are plain torch: constructor signatures, attribute names and ``state_dict`` keys are those of ``coco/model.py``, so a
-reference checkpoint loads; they run wherever torch runs and train through autograd.  The forward returns
+reference checkpoint loads; they run wherever torch runs and train through autograd.  ``set_conv_backend(model, "hip")`` routes every
+convolution of a model through ``causal_conv2d`` (csrc/causal_conv.hip: bf16 operands, fp32 accumulation, only the taps that exist)
+for training on the device; the default backend stays torch.  The forward returns
 ``(B, out_dims, data_channels, H, W)``, output channel ``v * data_channels + c`` being level ``v`` of channel ``c``.
 
 ``generate`` replaces the reference's sampling loop (one full forward per pixel and channel, ``coco/train_pixelcnn.py:185-197``).
@@ -51,6 +53,8 @@ class MaskedConv2d(nn.Conv2d):
 
     def forward(self, x):
         self.weight.data.mul_(self.mask)
+        if getattr(self, "conv_backend", "torch") == "hip":
+            return causal_conv2d(x, self.weight, self.bias, taps_of(self))
         return self._conv_forward(x, self.weight, self.bias)
 
 
@@ -59,6 +63,8 @@ class CroppedConv2d(nn.Conv2d):
     (columns) of the input."""
 
     def forward(self, x):
+        if getattr(self, "conv_backend", "torch") == "hip":
+            return causal_conv2d(x, self.weight, self.bias, taps_of(self))      # (the cropped rows and columns are never computed)
         y = self._conv_forward(x, self.weight, self.bias)
         rows, cols = y.shape[2:]
         if self.padding[0] == self.kernel_size[0]:
@@ -66,6 +72,13 @@ class CroppedConv2d(nn.Conv2d):
         if self.padding[1] == self.kernel_size[1]:
             cols -= self.kernel_size[1] + 1
         return y[:, :, :rows, :cols]
+
+
+def _conv1x1(m, x):
+    """a plain 1 x 1 ``nn.Conv2d`` under the backend ``set_conv_backend`` chose for it"""
+    if getattr(m, "conv_backend", "torch") == "hip":
+        return causal_conv2d(x, m.weight, m.bias, taps_of(m))
+    return m(x)
 
 
 def _gate(t):
@@ -93,7 +106,7 @@ class GatedResidualBlock(nn.Module):
     def forward(self, x, h):
         above = self.vertical_conv(x)
         left = self.horizontal_conv(h) + self.x_to_h_conv(above)
-        return _gate(self.vertical_gate_conv(above)), self.horizontal_output(_gate(self.horizontal_gate_conv(left)))
+        return _gate(_conv1x1(self.vertical_gate_conv, above)), self.horizontal_output(_gate(_conv1x1(self.horizontal_gate_conv, left)))
 
 
 class GatedResidualBlockList(nn.Module):
@@ -220,13 +233,13 @@ def pixelcnn_geometry() -> Tuple[int, int, int]:
     return a.value, b.value, c.value
 
 
-def _config(model) -> Tuple[int, int, int, int, int]:
+def _config(model, what="generate") -> Tuple[int, int, int, int, int]:
     if isinstance(model, GatedPixelCNN):
         gated, hid = 1, model.conv2.weight.shape[0]
     elif isinstance(model, PixelCNN):
         gated, hid = 0, model.hid_dims
     else:
-        raise MMVAEError("generate: a PixelCNN or GatedPixelCNN expected (got %s)" % type(model).__name__)
+        raise MMVAEError("%s: a PixelCNN or GatedPixelCNN expected (got %s)" % (what, type(model).__name__))
     return gated, int(model.n_blocks), int(model.data_channels), int(hid), int(model.out_dims)
 
 
@@ -320,3 +333,149 @@ def generate(model, n_samples=64, height=28, width=28, *, uniforms=None, seed=0,
         call("mmvae_pixelcnn_sample", *cfg, ptr(packed), ptr(ws), need, B, H, W, ptr(uniforms), ptr(g32), int(n_given), ptr(levels),
              ptr(image), ptr(logits), _stream())
     return PixelSample(image, levels.long(), logits)
+
+
+# ------------------------------------------------------------------------------------------------------ the training convolution
+_CONV_WS: Dict[Tuple, torch.Tensor] = {}
+_TAPS_C: Dict[Tuple, ctypes.Array] = {}
+CONV_BACKENDS = ("torch", "hip")
+
+
+def causal_conv_geometry() -> Tuple[int, int, int, int, int, int]:
+    """(positions per tile, channels per tile, positions per weight-gradient chunk, most taps, largest |offset|, most channels)"""
+    v = [ctypes.c_int() for _ in range(6)]
+    call("mmvae_causal_conv_geometry", *[ctypes.byref(a) for a in v])
+    return tuple(a.value for a in v)
+
+
+def taps_of(module) -> Tuple[Tuple[int, int, int, int], ...]:
+    """The tap list ``((r, c, dy, dx), ...)`` of a ``MaskedConv2d``, a ``CroppedConv2d`` or a plain 1 x 1 ``nn.Conv2d``: kernel cell
+    (r, c) is applied at offset (dy, dx) = (r - padding[0], c - padding[1]).  A masked kh x kw window keeps its first n cells in raster
+    order (mask A 24 of 49, mask B 5 of 9); the vertical cropped convolution, padded by its whole height, reaches rows -reach .. -1,
+    the horizontal one columns -reach .. -1."""
+    if not isinstance(module, nn.Conv2d):
+        raise MMVAEError("taps_of: a convolution module expected (got %s)" % type(module).__name__)
+    (kh, kw), (ph, pw) = module.kernel_size, module.padding
+    if module.stride != (1, 1) or module.dilation != (1, 1) or module.groups != 1 or isinstance(ph, str) or module.padding_mode != "zeros":
+        raise MMVAEError("taps_of: stride 1, dilation 1, groups 1 and zero padding expected")
+    n = kh * kw
+    if isinstance(module, MaskedConv2d):
+        if (ph, pw) != (kh // 2, kw // 2) or kh % 2 == 0 or kw % 2 == 0:
+            raise MMVAEError("taps_of: a MaskedConv2d needs an odd kernel with centre padding (kernel %s, padding %s)" % ((kh, kw), (ph, pw)))
+        if min(kh, kw) > 1:
+            n = (kh // 2) * kw + kw // 2 + (1 if module.mask_type == "B" else 0)
+    elif isinstance(module, CroppedConv2d):
+        if not ((ph == kh or (ph == kh // 2 and kh % 2 == 1)) and (pw == kw or (pw == kw // 2 and kw % 2 == 1))):
+            raise MMVAEError("taps_of: a CroppedConv2d pads a side by the whole kernel size or by half an odd one (kernel %s, padding %s)"
+                             % ((kh, kw), (ph, pw)))
+    elif (kh, kw) != (1, 1) or (ph, pw) != (0, 0):
+        raise MMVAEError("taps_of: a plain nn.Conv2d must be 1 x 1 without padding (kernel %s, padding %s)" % ((kh, kw), (ph, pw)))
+    return tuple((t // kw, t % kw, t // kw - ph, t % kw - pw) for t in range(n))
+
+
+def _taps_c(taps):
+    arr = _TAPS_C.get(taps)
+    if arr is None:
+        flat = [int(v) for tap in taps for v in tap]
+        arr = _TAPS_C[taps] = (ctypes.c_int * max(1, len(flat)))(*flat)
+    return arr
+
+
+def _conv_ws(dev, need):
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+    ws = _CONV_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _CONV_WS[key] = torch.empty((max(need, 1 << 20) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _nhwc(t):
+    return t.contiguous(memory_format=torch.channels_last)
+
+
+def _empty_nhwc(B, C, H, W, dev):
+    # (not a permuted view: an in-place ReLU on the op's output has to stay legal)
+    return torch.empty((B, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+
+
+class _CausalConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, taps):
+        for name, t in (("x", x), ("weight", weight), ("bias", bias)):
+            if t is None and name == "bias":
+                continue
+            if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != torch.float32:
+                raise MMVAEError("causal_conv2d: %s must be a float32 tensor on a gfx950 GPU (got %s): there is no CPU fallback"
+                                 % (name, "%s, %s" % (t.device, t.dtype) if torch.is_tensor(t) else type(t).__name__))
+        if x.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x.shape[1] or weight.device != x.device:
+            raise MMVAEError("causal_conv2d: x %s and weight %s do not fit: (B, Cin, H, W) and (Cout, Cin, kh, kw) on one device expected"
+                             % (tuple(x.shape), tuple(weight.shape)))
+        if bias is not None and (tuple(bias.shape) != (weight.shape[0],) or bias.device != x.device):
+            raise MMVAEError("causal_conv2d: bias %s, need (%d,) on %s" % (tuple(bias.shape), weight.shape[0], x.device))
+        taps = tuple(tuple(int(v) for v in tap) for tap in taps)
+        if any(len(tap) != 4 for tap in taps):
+            raise MMVAEError("causal_conv2d: a tap is (r, c, dy, dx)")
+        (B, Cin, H, W), (Cout, _, kh, kw) = x.shape, weight.shape
+        dims = (B, H, W, Cin, Cout, kh, kw)
+        x, w = _nhwc(x.detach()), weight.detach().contiguous()
+        b = None if bias is None else bias.detach().contiguous()
+        need = call("mmvae_causal_conv_workspace_bytes", *dims, len(taps))
+        with torch.cuda.device(x.device):
+            ws = _conv_ws(x.device, need)
+            y = _empty_nhwc(B, Cout, H, W, x.device)
+            call("mmvae_causal_conv_forward", ptr(x), ptr(w), ptr(b), ptr(y), _taps_c(taps), len(taps), *dims, ptr(ws), ws.numel(), _stream())
+        ctx.save_for_backward(x, w)
+        ctx.taps, ctx.dims, ctx.has_bias = taps, dims, bias is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        taps, dims = ctx.taps, ctx.dims
+        B, H, W, Cin, Cout, kh, kw = dims
+        g = _nhwc(g)
+        dx = dw = db = None
+        with torch.cuda.device(x.device):
+            ws = _conv_ws(x.device, call("mmvae_causal_conv_workspace_bytes", *dims, len(taps)))
+            tail = (_taps_c(taps), len(taps)) + dims + (ptr(ws), ws.numel(), _stream())
+            if ctx.needs_input_grad[0]:
+                dx = _empty_nhwc(B, Cin, H, W, x.device)
+                call("mmvae_causal_conv_backward_data", ptr(g), ptr(w), ptr(dx), *tail)
+            want_w, want_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+            if want_w or want_b:
+                dw = torch.empty_like(w) if want_w else None
+                db = torch.empty(Cout, dtype=torch.float32, device=x.device) if want_b else None
+                call("mmvae_causal_conv_backward_weight", ptr(g), ptr(x), ptr(dw), ptr(db), *tail)
+        return dx, dw, db, None
+
+
+def causal_conv2d(x, weight, bias, taps):
+    """The convolution every layer of both models is, as a device op with HIP forward, data gradient and weight gradient.
+
+    ``x`` (B, Cin, H, W) float32 (consumed channels-last), ``weight`` (Cout, Cin, kh, kw), ``bias`` (Cout,) or None, ``taps`` a tuple
+    of ``(r, c, dy, dx)``: kernel cell (r, c) applied at offset (dy, dx) -> (B, Cout, H, W) float32, channels-last.  With bf16(.)
+    round-to-nearest-even and fp32 accumulation, a position outside the image contributing nothing::
+
+        y[b,co,i,j]       = bias[co] + sum_t sum_ci bf16(x[b,ci,i+dy_t,j+dx_t]) bf16(w[co,ci,r_t,c_t])
+        dx[b,ci,i,j]      = sum_t sum_co bf16(g[b,co,i-dy_t,j-dx_t]) bf16(w[co,ci,r_t,c_t])
+        dw[co,ci,r_t,c_t] = sum_{b,i,j} bf16(g[b,co,i,j]) bf16(x[b,ci,i+dy_t,j+dx_t]);   cells in no tap: exactly 0
+        db[co]            = sum_{b,i,j} g[b,co,i,j]
+
+    Once differentiable; gradients nobody asked for are not computed; two calls give identical bits.  Device-only: a CPU tensor
+    raises ``MMVAEError``.  One deliberate difference to the torch path: there autograd gives masked weight cells a non-zero gradient
+    (the next forward zeroes the cells again, but ``clip_grad_norm_`` counts it); here it is exactly 0, so a clipped norm is taken
+    over the taps that exist."""
+    return _CausalConv.apply(x, weight, bias, taps)
+
+
+def set_conv_backend(model, backend):
+    """Chooses what the convolutions of a ``PixelCNN`` / ``GatedPixelCNN`` run on: ``"torch"`` (the default) or ``"hip"``
+    (``causal_conv2d``; the model has to be on the device by the time of its forward).  A plain attribute on the modules: no buffer,
+    no parameter, the ``state_dict`` does not change.  Gates, ReLUs, residual adds and the loss stay torch ops.  -> model"""
+    if backend not in CONV_BACKENDS:
+        raise MMVAEError("set_conv_backend: %r, need one of %s" % (backend, CONV_BACKENDS))
+    _config(model, "set_conv_backend")
+    for m in _layers(model):
+        m.conv_backend = backend
+    return model

@@ -8,6 +8,12 @@ cross entropy over every (sample, channel, pixel); the best model so far trigger
 and train through autograd wherever torch runs.  ``generate`` is the one-launch incremental sampler (``pixelcnn.generate``) when the
 model is on the device; on the CPU it is skipped (there is no CPU sampler).
 
+``--conv_backend hip`` (needs ``--cuda``) trains through ``pixelcnn.causal_conv2d``: every convolution's forward, data gradient and
+weight gradient on bf16 MFMA with fp32 accumulation, only the taps that exist.  Gates, ReLUs, residual adds, the cross entropy and
+Adam stay torch ops; ``test()`` and ``generate`` work with either backend and the checkpoint has the same ``state_dict``.  The
+gradient of masked weight cells is exactly 0 there (torch gives them one that ``clip_grad_norm_`` counts), so the clipped norm is
+taken over the taps that exist.
+
 Defaults follow the dataset's reference script: ``--out_dims`` 8 and 28 x 28 for mnist (``--rgb`` triples the channel), ``--out_dims``
 256, ``--image_size`` 32, three channels and the gated model for coco (``--cifar`` only renames the output folder there).  One
 deliberate difference: the MNIST script passes ``(data_channels, out_dims)`` positionally into ``(n_blocks, data_channels)`` and
@@ -22,7 +28,7 @@ import sys
 import torch
 import torch.optim as optim
 
-from .pixelcnn import GatedPixelCNN, PixelCNN, cross_entropy_by_dim, quantisize, save_checkpoint
+from .pixelcnn import CONV_BACKENDS, GatedPixelCNN, PixelCNN, cross_entropy_by_dim, quantisize, save_checkpoint, set_conv_backend
 
 
 def build_parser():
@@ -40,6 +46,8 @@ def build_parser():
     parser.add_argument('--lr', type=float, default=1e-3, metavar='LR', help='learning rate (default: 1e-3)')
     parser.add_argument('--log_interval', type=int, default=10, metavar='N', help='batches between log lines (default: 10)')
     parser.add_argument('--cuda', action='store_true', default=False, help='enables GPU training (default: False)')
+    parser.add_argument('--conv_backend', choices=CONV_BACKENDS, default='torch',
+                        help='convolutions through torch ops or through the HIP causal convolution (hip needs --cuda; default: torch)')
     parser.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic images instead of files')
     parser.add_argument('--data', default='./data', help='folder with train.pt / test.pt, uint8 (N, C, H, W)')
     parser.add_argument('--seed', type=int, default=0)
@@ -56,6 +64,8 @@ def resolve(args):
     args.data_channels = 3 if (coco or args.rgb) else 1
     args.gated = args.gated or coco
     args.folder_name = ('pixel_cifar' if args.cifar else 'pixel_cnn') if coco else 'pixel_cnn'
+    if args.conv_backend == 'hip' and not (args.cuda and torch.cuda.is_available()):
+        raise SystemExit('--conv_backend hip runs on the GPU only: pass --cuda on a machine with a gfx950 device (there is no CPU fallback)')
     args.cuda = args.cuda and torch.cuda.is_available()
     assert 1 < args.out_dims <= 256
     return args
@@ -63,7 +73,8 @@ def resolve(args):
 
 def build_model(args):
     cls = GatedPixelCNN if args.gated else PixelCNN
-    return cls(n_blocks=args.n_blocks, data_channels=args.data_channels, hid_dims=args.hid_dims, out_dims=args.out_dims)
+    model = cls(n_blocks=args.n_blocks, data_channels=args.data_channels, hid_dims=args.hid_dims, out_dims=args.out_dims)
+    return set_conv_backend(model, getattr(args, 'conv_backend', 'torch'))
 
 
 def preprocess(u8, out_dims):
@@ -151,7 +162,7 @@ def main(argv=None):
         save_checkpoint({
             'state_dict': model.state_dict(), 'best_loss': best_loss, 'optimizer': optimizer.state_dict(), 'gated': args.gated,
             'n_blocks': args.n_blocks, 'data_channels': args.data_channels, 'hid_dims': args.hid_dims, 'out_dims': args.out_dims,
-            'height': args.image_size, 'width': args.image_size,
+            'height': args.image_size, 'width': args.image_size, 'conv_backend': args.conv_backend,
         }, is_best, folder='./trained_models/%s' % args.folder_name)
         if is_best:
             generate(epoch)
