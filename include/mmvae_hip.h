@@ -617,6 +617,27 @@ int mmvae_causal_conv_backward_weight(const float* g, const float* x, float* dw_
                                       int batch, int height, int width, int cin, int cout, int kh, int kw, void* ws, long long ws_bytes,
                                       void* stream);
 
+/* PixelCNN output head fused with its cross entropy (csrc/head_nll.h): the 1 x 1 convolution conv4 (weight (levels * channels, hid),
+ * output channel v * channels + c = level v of data channel c) and the per-element negative log-likelihood, without the logits ever
+ * existing in global memory.  h fp32 channels-last [batch * height * width][hid]; target (int64 levels), nll, lse and g are
+ * (batch, channels, height, width).  bf16 operands (round to nearest even), fp32 accumulation:
+ *   l[p,v,c] = bias[vC+c] + sum_k h[p,k] w[vC+c,k];  lse[p,c] = log sum_v exp l[p,v,c];  nll[p,c] = lse[p,c] - l[p,target[p,c],c]
+ *   (a target outside 0..levels-1 reads nothing and gives NaN for that element)
+ *   d[p,v,c] = g[p,c] (exp(l[p,v,c] - lse[p,c]) - [v == target[p,c]]);  dh[p,k] = sum_{v,c} d w;  dw[vC+c,k] = sum_p d h;
+ *   db[vC+c] = sum_p d from the unrounded d.  The backward recomputes the logits from h, the weights and the saved lse.
+ *   forward: lse may be null (evaluation).  backward: each of dh, dw, db may be null and is then not computed.
+ *   Partial dw / db per chunk of positions, folded in ascending chunk order: no atomics, two calls give identical bits.
+ *   ws: device scratch of workspace_bytes (0 for arguments out of range), 16-byte aligned, needs no initialisation.
+ * Limits: channels 1 or 3, hid a multiple of 8 up to max_hid, levels 2..max_levels, batch * height * width <= max_positions.
+ * geometry: positions per workgroup, levels per tile, positions per dw / db chunk and the three limits. */
+int mmvae_head_nll_geometry(int* pos_tile, int* level_tile, int* chunk, int* max_hid, int* max_levels, int* max_positions);
+long long mmvae_head_nll_workspace_bytes(int batch, int channels, int height, int width, int hid, int levels);
+int mmvae_head_nll_forward(const float* h, const float* weight, const float* bias, const long long* target, float* nll, float* lse_or_null,
+                           int batch, int channels, int height, int width, int hid, int levels, void* ws, long long ws_bytes, void* stream);
+int mmvae_head_nll_backward(const float* h, const float* weight, const float* bias, const long long* target, const float* lse,
+                            const float* g, float* dh_or_null, float* dw_or_null, float* db_or_null, int batch, int channels, int height,
+                            int width, int hid, int levels, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -252,6 +252,10 @@ SIGNATURES["mmvae_causal_conv_workspace_bytes"] = (_LL, [_I] * 8)
 SIGNATURES["mmvae_causal_conv_forward"] = (_I, [_P, _P, _P, _P, C.POINTER(_I), _I] + [_I] * 7 + [_P, _LL, _P])
 SIGNATURES["mmvae_causal_conv_backward_data"] = (_I, [_P, _P, _P, C.POINTER(_I), _I] + [_I] * 7 + [_P, _LL, _P])
 SIGNATURES["mmvae_causal_conv_backward_weight"] = (_I, [_P, _P, _P, _P, C.POINTER(_I), _I] + [_I] * 7 + [_P, _LL, _P])
+SIGNATURES["mmvae_head_nll_geometry"] = (_I, [C.POINTER(_I)] * 6)
+SIGNATURES["mmvae_head_nll_workspace_bytes"] = (_LL, [_I] * 6)
+SIGNATURES["mmvae_head_nll_forward"] = (_I, [_P] * 6 + [_I] * 6 + [_P, _LL, _P])
+SIGNATURES["mmvae_head_nll_backward"] = (_I, [_P] * 9 + [_I] * 6 + [_P, _LL, _P])
 _STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
 
 _lib = None

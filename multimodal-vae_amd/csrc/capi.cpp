@@ -10,6 +10,7 @@
 #include "mmd.h"
 #include "pixelcnn.h"
 #include "causal_conv.h"
+#include "head_nll.h"
 #include <cstring>
 #include <exception>
 
@@ -639,4 +640,40 @@ int mmvae_causal_conv_backward_weight(const float* g, const float* x, float* dw,
     MMVAE_TRY(cc_prepare("causal_conv_backward_weight", s, taps, n_taps, ws, ws_bytes, &t));
     MMVAE_REQUIRE(g && (x || !dw), "causal_conv_backward_weight: null argument");
     return guarded([&] { return launch_cc_backward_weight(s, t, g, x, dw, db, ws, S(st)); });
+}
+
+// ---- PixelCNN output head fused with its cross entropy (head_nll.h)
+int mmvae_head_nll_geometry(int* pos_tile, int* level_tile, int* chunk, int* max_hid, int* max_levels, int* max_positions) {
+    MMVAE_REQUIRE(pos_tile && level_tile && chunk && max_hid && max_levels && max_positions, "head_nll_geometry: null argument");
+    *pos_tile = HN_TM; *level_tile = HN_TN; *chunk = HN_CHUNK; *max_hid = HN_MAX_HID; *max_levels = HN_MAX_V; *max_positions = HN_MAX_POS;
+    return MMVAE_OK;
+}
+long long mmvae_head_nll_workspace_bytes(int batch, int channels, int height, int width, int hid, int levels) {
+    const HnShape s{batch, channels, height, width, hid, levels};
+    return hn_shape_ok(s) ? (long long)hn_workspace_bytes(s) : 0;
+}
+static int hn_prepare(const char* what, const HnShape& s, const float* h, const void* ws, long long ws_bytes) {
+    MMVAE_REQUIRE(hn_shape_ok(s), "%s: batch = %d, channels = %d, height = %d, width = %d, hid = %d, levels = %d: need batch * height * width "
+                  "in 1..%d, channels 1 or 3, hid a multiple of 8 in 8..%d, levels 2..%d", what, s.B, s.C, s.H, s.W, s.hid, s.V,
+                  (int)HN_MAX_POS, (int)HN_MAX_HID, (int)HN_MAX_V);
+    MMVAE_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", what);
+    MMVAE_REQUIRE(h && (reinterpret_cast<uintptr_t>(h) & 15) == 0, "%s: h must be a 16-byte aligned device buffer", what);
+    const long long need = (long long)hn_workspace_bytes(s);
+    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
+    return MMVAE_OK;
+}
+int mmvae_head_nll_forward(const float* h, const float* weight, const float* bias, const long long* target, float* nll, float* lse, int batch,
+                           int channels, int height, int width, int hid, int levels, void* ws, long long ws_bytes, void* st) {
+    const HnShape s{batch, channels, height, width, hid, levels};
+    MMVAE_TRY(hn_prepare("head_nll_forward", s, h, ws, ws_bytes));
+    MMVAE_REQUIRE(weight && bias && target && nll, "head_nll_forward: null argument");
+    return guarded([&] { return launch_hn_forward(s, h, weight, bias, target, nll, lse, ws, S(st)); });
+}
+int mmvae_head_nll_backward(const float* h, const float* weight, const float* bias, const long long* target, const float* lse, const float* g,
+                            float* dh, float* dw, float* db, int batch, int channels, int height, int width, int hid, int levels, void* ws,
+                            long long ws_bytes, void* st) {
+    const HnShape s{batch, channels, height, width, hid, levels};
+    MMVAE_TRY(hn_prepare("head_nll_backward", s, h, ws, ws_bytes));
+    MMVAE_REQUIRE(weight && bias && target && lse && g, "head_nll_backward: null argument");
+    return guarded([&] { return launch_hn_backward(s, h, weight, bias, target, lse, g, dh, dw, db, ws, S(st)); });
 }

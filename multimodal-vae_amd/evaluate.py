@@ -515,6 +515,42 @@ def sample_pixelcnn(model, n_samples=64, height=None, width=None, complete=None,
 
 
 @torch.no_grad()
+def nll_pixelcnn(model, images_u8, batch_size=32, head="torch"):
+    """Exact negative log-likelihood of uint8 images (N, C, H, W) under a ``pixelcnn.PixelCNN`` / ``GatedPixelCNN``, on the model's
+    device.  The images are preprocessed as ``train_pixelcnn`` does (quantised to the model's levels); ``head="hip"`` evaluates the
+    output head and the cross entropy in the fused forward kernel (``pixelcnn.head_nll``, device-only), ``"torch"`` runs anywhere.
+    Prints the reference's test line (the mean over elements) and the mean per image in nats and bits/dim with standard errors ->
+    {"per_image_nll", "nll_mean", "nll_se", "bits_per_dim", "bits_per_dim_se", "loss", "n", "head"}."""
+    from . import pixelcnn as PX
+    from .train_pixelcnn import preprocess
+    PX.check_head(model, head, "nll_pixelcnn")
+    im = torch.as_tensor(images_u8)
+    if im.dtype != torch.uint8 or im.dim() != 4 or im.shape[0] < 1 or im.shape[1] != model.data_channels:
+        raise ValueError("nll_pixelcnn: images must be uint8 (N, %d, H, W) with N >= 1 (got %s %s)"
+                         % (model.data_channels, im.dtype, tuple(im.shape)))
+    size = (getattr(model, "height", None), getattr(model, "width", None))
+    if None not in size and tuple(im.shape[2:]) != size:
+        raise ValueError("nll_pixelcnn: images are %d x %d, the checkpoint was trained on %d x %d" % (tuple(im.shape[2:]) + size))
+    model.eval()
+    dev = model.conv4.weight.device
+    x = preprocess(im.cpu(), model.out_dims)
+    per_image = []
+    for k in range(0, x.shape[0], batch_size):
+        per_image.append(PX.nll(model, x[k:k + batch_size].to(dev), head=head).double().flatten(1).sum(dim=1).cpu())
+    per_image = torch.cat(per_image)
+    n, dims = int(per_image.shape[0]), int(im.shape[1] * im.shape[2] * im.shape[3])
+    mean = float(per_image.mean())
+    se = float(per_image.std(unbiased=True) / n ** 0.5) if n > 1 else 0.0
+    ln2 = float(np.log(2.0))
+    out = {"per_image_nll": per_image.tolist(), "nll_mean": mean, "nll_se": se, "bits_per_dim": mean / (dims * ln2),
+           "bits_per_dim_se": se / (dims * ln2), "loss": mean / dims, "n": n, "head": head}
+    print('====> Test Epoch\tLoss: {:.4f}'.format(out["loss"]))
+    print('NLL per image over {} images: {:.4f} +- {:.4f} nats\t{:.5f} +- {:.5f} bits/dim'.format(
+        n, mean, se, out["bits_per_dim"], out["bits_per_dim_se"]))
+    return out
+
+
+@torch.no_grad()
 def latent_mmd(vae, loader, seed=0):
     """MMD between the aggregate posterior of an ``coco.InfoVAE`` and its prior: encodes every image of ``loader`` (batches of
     (B,3,32,32) floats in [0,1], or tuples whose first entry is one) in eval mode (z = mu), draws as many N(0, I) samples from
@@ -606,6 +642,18 @@ def _parser():
     pp.add_argument('--rows', type=int, default=0, metavar='R', help='rows of --complete to keep')
     pp.add_argument('--seed', type=int, default=0, help='seed of the uniforms')
     pp.add_argument('--out', type=str, default='./results')
+    # exact log-likelihood of images under a checkpoint of train_pixelcnn
+    pn = sub.add_parser("nll_pixelcnn", help="exact NLL per image and bits/dim for a PixelCNN / GatedPixelCNN checkpoint")
+    pn.add_argument('model_path', type=str, help='path to a checkpoint written by train_pixelcnn')
+    src = pn.add_mutually_exclusive_group()
+    src.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='a .pt file of uint8 images (N,C,H,W)')
+    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic images instead of a file')
+    pn.add_argument('--batch_size', type=int, default=32)
+    pn.add_argument('--head', choices=('torch', 'hip'), default='torch',
+                    help='conv4 + cross entropy as torch ops or as the fused HIP head (hip needs --cuda; default: torch)')
+    pn.add_argument('--cuda', action='store_true', default=False, help='evaluate on the GPU (default: False)')
+    pn.add_argument('--seed', type=int, default=0, help='seed of the synthetic images')
+    pn.add_argument('--json', type=str, default=None, help='write the result to this file')
     # aggregate posterior against the prior for a checkpoint of train_infovae
     pm = sub.add_parser("latent_mmd", help="MMD between the encoded test images and the prior, for a checkpoint of train_infovae")
     pm.add_argument('model_path', type=str, help='path to a checkpoint written by train_infovae')
@@ -634,6 +682,38 @@ def _latent_mmd_main(args):
     loader = [x[i:i + args.batch_size] for i in range(0, x.shape[0], args.batch_size)]
     vae = load_checkpoint(args.model_path, use_cuda=True)
     out = latent_mmd(vae, loader, seed=args.seed)
+    if args.json:
+        with open(args.json, 'w') as fp:
+            json.dump(out, fp, indent=1)
+    return out
+
+
+def _nll_pixelcnn_main(args):
+    import json
+    from .pixelcnn import load_checkpoint
+    from .train_pixelcnn import synthetic_images
+    if args.head == 'hip' and not (args.cuda and torch.cuda.is_available()):
+        raise SystemExit('--head hip runs on the GPU only: pass --cuda on a machine with a gfx950 device (there is no CPU fallback)')
+    use_cuda = args.cuda and torch.cuda.is_available()
+    model = load_checkpoint(args.model_path, use_cuda=False)
+    if args.synthetic > 0:
+        if model.height is None:
+            raise SystemExit("nll_pixelcnn: the checkpoint records no image size: give --data FILE.pt")
+        width = model.width or model.height                                            # (square images, cropped to the checkpoint's size)
+        x = synthetic_images(args.synthetic, model.data_channels, max(model.height, width), args.seed)[:, :, :model.height, :width].contiguous()
+    elif args.data:
+        x = torch.as_tensor(torch.load(args.data, weights_only=False))
+    else:
+        raise SystemExit("nll_pixelcnn: give --data FILE.pt or --synthetic N")
+    # (the images are checked against the checkpoint on the CPU, before anything is uploaded)
+    size = (model.height, model.width)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != model.data_channels or (
+            None not in size and tuple(x.shape[2:]) != size):
+        raise SystemExit("nll_pixelcnn: images must be uint8 (N, %d, %s, %s) (got %s %s)"
+                         % (model.data_channels, size[0] or 'H', size[1] or 'W', x.dtype, tuple(x.shape)))
+    if use_cuda:
+        model.cuda()
+    out = nll_pixelcnn(model, x, args.batch_size, args.head)
     if args.json:
         with open(args.json, 'w') as fp:
             json.dump(out, fp, indent=1)
@@ -770,6 +850,8 @@ def _main(argv=None):
         return _latent_mmd_main(args)
     if args.cmd == "sample_pixelcnn":
         return _sample_pixelcnn_main(args)
+    if args.cmd == "nll_pixelcnn":
+        return _nll_pixelcnn_main(args)
     vae = load_checkpoint(args.model_path, use_cuda=True)
     image = text = None
     if args.condition_on_image:
@@ -783,6 +865,9 @@ def _main(argv=None):
     with open(os.path.join(args.out, 'sample_text.txt'), 'w') as fp:
         for i in range(text_recon.size(0)):
             fp.write('%s\n' % tensor_to_string(text_recon[i]))
+
+
+main = _main
 
 
 if __name__ == "__main__":

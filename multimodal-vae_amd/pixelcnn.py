@@ -2,7 +2,9 @@
 sampler for them (csrc/pixelcnn.hip).
 
 The modules are plain torch: constructor signatures, attribute names and ``state_dict`` keys are those of ``coco/model.py``, so a
-reference checkpoint loads; they run wherever torch runs and train through autograd.  ``set_conv_backend(model, "hip")`` routes every
+reference checkpoint loads; they run wherever torch runs and train through autograd.  ``nll(model, x)`` is the per-element negative log-likelihood
+(``bits_per_dim`` per image); with ``head="hip"`` the output head ``conv4`` and the cross entropy run as one fused device op,
+``head_nll`` (csrc/head_nll.hip), that never writes the logits to memory.  ``set_conv_backend(model, "hip")`` routes every
 convolution of a model through ``causal_conv2d`` (csrc/causal_conv.hip: bf16 operands, fp32 accumulation, only the taps that exist)
 for training on the device; the default backend stays torch.  The forward returns
 ``(B, out_dims, data_channels, H, W)``, output channel ``v * data_channels + c`` being level ``v`` of channel ``c``.
@@ -138,11 +140,14 @@ class PixelCNN(nn.Module):
         self.out_dims = out_dims
         self.n_blocks = n_blocks
 
-    def forward(self, x):
+    def features(self, x):
+        """the activation ``conv4`` consumes (its ReLU included): (B, hid_dims, H, W)"""
         x = self.conv1(x)
         x = self.blocks(x)
-        x = F.relu(self.conv2(x))
-        x = self.conv4(x)
+        return F.relu(self.conv2(x))
+
+    def forward(self, x):
+        x = self.conv4(self.features(x))
         batch_size, _, height, width = x.size()
         return x.view(batch_size, self.out_dims, self.data_channels, height, width)
 
@@ -161,11 +166,14 @@ class GatedPixelCNN(nn.Module):
         self.out_dims = out_dims
         self.n_blocks = n_blocks
 
-    def forward(self, x):
+    def features(self, x):
+        """the activation ``conv4`` consumes (its ReLU included): (B, hid_dims, H, W)"""
         x, h = self.conv1(x, x)
         _, h = self.blocks(x, h)
-        h = self.conv2(F.relu(h))
-        h = self.conv4(F.relu(h))
+        return F.relu(self.conv2(F.relu(h)))
+
+    def forward(self, x):
+        h = self.conv4(self.features(x))
         batch_size, _, height, width = h.size()
         return h.view(batch_size, self.out_dims, self.data_channels, height, width)
 
@@ -479,3 +487,127 @@ def set_conv_backend(model, backend):
     for m in _layers(model):
         m.conv_backend = backend
     return model
+
+
+# ------------------------------------------------------------------------------------------------------ the fused head
+HEADS = ("torch", "hip")
+
+
+def head_nll_geometry() -> Tuple[int, int, int, int, int, int]:
+    """(positions per workgroup, levels per tile, positions per dw / db chunk, largest hid, most levels, most positions)"""
+    v = [ctypes.c_int() for _ in range(6)]
+    call("mmvae_head_nll_geometry", *[ctypes.byref(a) for a in v])
+    return tuple(a.value for a in v)
+
+
+def head_nll_workspace_bytes(B, C, H, W, hid, V) -> int:
+    """device scratch one ``head_nll`` call needs; 0 when the shape is outside the op's limits (a host function: needs no GPU)"""
+    return int(call("mmvae_head_nll_workspace_bytes", int(B), int(C), int(H), int(W), int(hid), int(V)))
+
+
+def _head_dims(what, h, weight, bias, target, data_channels):
+    """validates everything before anything is launched -> (B, C, H, W, hid, V)"""
+    for name, t in (("h", h), ("weight", weight), ("bias", bias)):
+        if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != torch.float32:
+            raise MMVAEError("%s: %s must be a float32 tensor on a gfx950 GPU (got %s): there is no CPU fallback"
+                             % (what, name, "%s, %s" % (t.device, t.dtype) if torch.is_tensor(t) else type(t).__name__))
+    if not torch.is_tensor(target) or target.dtype != torch.int64 or target.device != h.device:
+        raise MMVAEError("%s: target must be an int64 tensor of levels on %s" % (what, h.device))
+    C = int(data_channels)
+    if h.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[1:]) != (h.shape[1], 1, 1) or C < 1 or weight.shape[0] % C != 0:
+        raise MMVAEError("%s: h %s, weight %s, data_channels %d do not fit: (B, hid, H, W) and (V * C, hid, 1, 1) expected"
+                         % (what, tuple(h.shape), tuple(weight.shape), C))
+    (B, hid, H, W), V = h.shape, weight.shape[0] // C
+    if tuple(bias.shape) != (V * C,) or tuple(target.shape) != (B, C, H, W) or weight.device != h.device or bias.device != h.device:
+        raise MMVAEError("%s: bias %s, target %s: need (%d,) and %s on %s" % (what, tuple(bias.shape), tuple(target.shape), V * C,
+                                                                             (B, C, H, W), h.device))
+    if head_nll_workspace_bytes(B, C, H, W, hid, V) <= 0:
+        _, _, _, max_hid, max_v, max_pos = head_nll_geometry()
+        raise MMVAEError("%s: B = %d, C = %d, H = %d, W = %d, hid = %d, V = %d is outside what the kernels are built for (C 1 or 3, hid a "
+                         "multiple of 8 up to %d, V 2..%d, B * H * W <= %d)" % (what, B, C, H, W, hid, V, max_hid, max_v, max_pos))
+    return int(B), C, int(H), int(W), int(hid), int(V)
+
+
+class _HeadNLL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, weight, bias, target, data_channels):
+        dims = _head_dims("head_nll", h, weight, bias, target, data_channels)
+        B, C, H, W, hid, V = dims
+        h, w, b, t = _nhwc(h.detach()), weight.detach().contiguous(), bias.detach().contiguous(), target.contiguous()
+        keep = any(ctx.needs_input_grad[:3])
+        with torch.cuda.device(h.device):
+            ws = _conv_ws(h.device, head_nll_workspace_bytes(*dims))
+            nll = torch.empty(B, C, H, W, dtype=torch.float32, device=h.device)
+            lse = torch.empty(B, C, H, W, dtype=torch.float32, device=h.device) if keep else None
+            call("mmvae_head_nll_forward", ptr(h), ptr(w), ptr(b), ptr(t), ptr(nll), ptr(lse), *dims, ptr(ws), ws.numel(), _stream())
+        if keep:
+            ctx.save_for_backward(h, w, b, t, lse)
+        ctx.dims = dims
+        return nll
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        h, w, b, t, lse = ctx.saved_tensors
+        dims = ctx.dims
+        B, C, H, W, hid, V = dims
+        g = g.contiguous()
+        want_h, want_w, want_b = ctx.needs_input_grad[:3]
+        with torch.cuda.device(h.device):
+            ws = _conv_ws(h.device, head_nll_workspace_bytes(*dims))
+            dh = _empty_nhwc(B, hid, H, W, h.device) if want_h else None
+            dw = torch.empty_like(w) if want_w else None
+            db = torch.empty_like(b) if want_b else None
+            call("mmvae_head_nll_backward", ptr(h), ptr(w), ptr(b), ptr(t), ptr(lse), ptr(g), ptr(dh), ptr(dw), ptr(db), *dims, ptr(ws),
+                 ws.numel(), _stream())
+        return dh, dw, db, None, None
+
+
+def head_nll(h, weight, bias, target, data_channels):
+    """The output head ``conv4`` and the cross entropy as one device op: the logits never exist in memory.
+
+    ``h`` (B, hid, H, W) float32 (consumed channels-last), ``weight`` (V * C, hid, 1, 1) with output channel ``v * C + c`` = level v of
+    data channel c, ``bias`` (V * C,), ``target`` (B, C, H, W) int64 levels -> ``nll`` (B, C, H, W) float32 in nats.  With bf16(.)
+    round-to-nearest-even and fp32 accumulation, p = (b, i, j)::
+
+        l[p,v,c]   = bias[vC+c] + sum_k bf16(h[p,k]) bf16(w[vC+c,k])
+        lse[p,c]   = log sum_v exp(l[p,v,c])                                 (online, the running maximum subtracted)
+        nll[p,c]   = lse[p,c] - l[p,target[p,c],c]                           (a target outside 0..V-1: NaN for that element)
+        d[p,v,c]   = g[p,c] (exp(l[p,v,c] - lse[p,c]) - [v == target[p,c]])
+        dh[p,k]    = sum_{v,c} bf16(d[p,v,c]) bf16(w[vC+c,k])
+        dw[vC+c,k] = sum_p bf16(d[p,v,c]) bf16(h[p,k]);    db[vC+c] = sum_p d[p,v,c]
+
+    Once differentiable; the backward recomputes the logits from ``h``, the weights and the saved ``lse``; gradients nobody asked for
+    are not computed; no atomics, two calls give identical bits.  Limits: C 1 or 3, hid a multiple of 8 up to 256, V 2..256
+    (``head_nll_geometry``).  Device-only: a CPU tensor raises ``MMVAEError``."""
+    return _HeadNLL.apply(h, weight, bias, target, data_channels)
+
+
+def check_head(model, head, what="nll"):
+    """raises ``MMVAEError`` unless ``head`` can run on ``model`` (hip: the model within the op's limits)"""
+    if head not in HEADS:
+        raise MMVAEError("%s: head %r, need one of %s" % (what, head, HEADS))
+    _, _, C, hid, V = _config(model, what)
+    if head == "hip" and head_nll_workspace_bytes(1, C, 1, 1, hid, V) <= 0:
+        _, _, _, max_hid, max_v, _ = head_nll_geometry()
+        raise MMVAEError("%s: head 'hip' needs data_channels 1 or 3, hid_dims a multiple of 8 up to %d and out_dims 2..%d (got %d, %d, %d)"
+                         % (what, max_hid, max_v, C, hid, V))
+
+
+def nll(model, x, target=None, head="torch"):
+    """Per-element negative log-likelihood of ``target`` (default ``(x * (out_dims - 1)).long()``) under ``model`` given ``x``:
+    (B, C, H, W) in nats, differentiable.  ``head="torch"`` is ``log_softmax`` + gather on ``model(x)`` and runs anywhere;
+    ``head="hip"`` is ``head_nll`` on ``model.features(x)`` (device-only), independent of ``set_conv_backend``."""
+    check_head(model, head)
+    if target is None:
+        target = (x * (model.out_dims - 1)).long()
+    if head == "hip":
+        model.conv4.weight.data.mul_(model.conv4.mask)          # what a MaskedConv2d forward does
+        return head_nll(model.features(x), model.conv4.weight, model.conv4.bias, target, model.data_channels)
+    logp = F.log_softmax(model(x), dim=1)
+    return -logp.gather(1, target.unsqueeze(1)).squeeze(1)
+
+
+def bits_per_dim(nll):
+    """(B, C, H, W) nats -> (B,) bits per dimension: the mean over C * H * W divided by ln 2"""
+    return nll.flatten(1).mean(dim=1) / float(np.log(2.0))

@@ -14,6 +14,10 @@ Adam stay torch ops; ``test()`` and ``generate`` work with either backend and th
 gradient of masked weight cells is exactly 0 there (torch gives them one that ``clip_grad_norm_`` counts), so the clipped norm is
 taken over the taps that exist.
 
+``--head hip`` (needs ``--cuda``) computes the loss through ``pixelcnn.head_nll``: the output head ``conv4`` and the cross entropy
+as one fused device op, forward and backward, that never writes the logits to memory; the loss is ``nll(...).mean()`` in training
+and in ``test()``.  It is independent of ``--conv_backend``; the default stays ``torch``.
+
 Defaults follow the dataset's reference script: ``--out_dims`` 8 and 28 x 28 for mnist (``--rgb`` triples the channel), ``--out_dims``
 256, ``--image_size`` 32, three channels and the gated model for coco (``--cifar`` only renames the output folder there).  One
 deliberate difference: the MNIST script passes ``(data_channels, out_dims)`` positionally into ``(n_blocks, data_channels)`` and
@@ -28,7 +32,8 @@ import sys
 import torch
 import torch.optim as optim
 
-from .pixelcnn import CONV_BACKENDS, GatedPixelCNN, PixelCNN, cross_entropy_by_dim, quantisize, save_checkpoint, set_conv_backend
+from .pixelcnn import (CONV_BACKENDS, HEADS, GatedPixelCNN, MMVAEError, PixelCNN, check_head, cross_entropy_by_dim, nll, quantisize,
+                       save_checkpoint, set_conv_backend)
 
 
 def build_parser():
@@ -48,6 +53,8 @@ def build_parser():
     parser.add_argument('--cuda', action='store_true', default=False, help='enables GPU training (default: False)')
     parser.add_argument('--conv_backend', choices=CONV_BACKENDS, default='torch',
                         help='convolutions through torch ops or through the HIP causal convolution (hip needs --cuda; default: torch)')
+    parser.add_argument('--head', choices=HEADS, default='torch',
+                        help='conv4 + cross entropy as torch ops or as the fused HIP head (hip needs --cuda; default: torch)')
     parser.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic images instead of files')
     parser.add_argument('--data', default='./data', help='folder with train.pt / test.pt, uint8 (N, C, H, W)')
     parser.add_argument('--seed', type=int, default=0)
@@ -66,6 +73,8 @@ def resolve(args):
     args.folder_name = ('pixel_cifar' if args.cifar else 'pixel_cnn') if coco else 'pixel_cnn'
     if args.conv_backend == 'hip' and not (args.cuda and torch.cuda.is_available()):
         raise SystemExit('--conv_backend hip runs on the GPU only: pass --cuda on a machine with a gfx950 device (there is no CPU fallback)')
+    if args.head == 'hip' and not (args.cuda and torch.cuda.is_available()):
+        raise SystemExit('--head hip runs on the GPU only: pass --cuda on a machine with a gfx950 device (there is no CPU fallback)')
     args.cuda = args.cuda and torch.cuda.is_available()
     assert 1 < args.out_dims <= 256
     return args
@@ -74,6 +83,10 @@ def resolve(args):
 def build_model(args):
     cls = GatedPixelCNN if args.gated else PixelCNN
     model = cls(n_blocks=args.n_blocks, data_channels=args.data_channels, hid_dims=args.hid_dims, out_dims=args.out_dims)
+    try:
+        check_head(model, getattr(args, 'head', 'torch'), '--head')
+    except MMVAEError as e:
+        raise SystemExit(str(e))
     return set_conv_backend(model, getattr(args, 'conv_backend', 'torch'))
 
 
@@ -93,11 +106,18 @@ def synthetic_images(n, channels, size, seed=0):
     return (x * 255).round().clamp(0, 255).to(torch.uint8)
 
 
-def train_step(model, optimizer, data, out_dims):
-    """one optimisation step on a batch in [0, 1]; -> (loss, gradient norm after clipping)"""
+def batch_loss(model, data, out_dims, head="torch"):
+    """mean cross entropy over every (sample, channel, pixel) of a batch in [0, 1]"""
     target = (data * (out_dims - 1)).long()
+    if head == "hip":
+        return nll(model, data, target, head="hip").mean()
+    return cross_entropy_by_dim(model(data), target)
+
+
+def train_step(model, optimizer, data, out_dims, head="torch"):
+    """one optimisation step on a batch in [0, 1]; -> (loss, gradient norm after clipping)"""
     optimizer.zero_grad()
-    loss = cross_entropy_by_dim(model(data), target)
+    loss = batch_loss(model, data, out_dims, head)
     loss.backward()
     torch.nn.utils.clip_grad_norm_(model.parameters(), 1.)
     norm = torch.sqrt(sum(p.grad.double().pow(2).sum() for p in model.parameters() if p.grad is not None))
@@ -128,7 +148,7 @@ def main(argv=None):
         total, seen = 0.0, 0
         for batch_idx in range(0, (len(tr) + args.batch_size - 1) // args.batch_size):
             data = tr[perm[batch_idx * args.batch_size:(batch_idx + 1) * args.batch_size]].to(dev)
-            loss, _ = train_step(model, optimizer, data, args.out_dims)
+            loss, _ = train_step(model, optimizer, data, args.out_dims, args.head)
             total, seen = total + loss * len(data), seen + len(data)
             if batch_idx % args.log_interval == 0:
                 print('Train Epoch: {} [{}/{}]\tLoss: {:.6f}'.format(epoch, seen, len(tr), total / seen))
@@ -140,7 +160,7 @@ def main(argv=None):
         total = 0.0
         for k in range(0, len(te), args.batch_size):
             data = te[k:k + args.batch_size].to(dev)
-            total += float(cross_entropy_by_dim(model(data), (data * (args.out_dims - 1)).long())) * len(data)
+            total += float(batch_loss(model, data, args.out_dims, args.head)) * len(data)
         print('====> Test Epoch\tLoss: {:.4f}'.format(total / len(te)))
         return total / len(te)
 
@@ -162,7 +182,7 @@ def main(argv=None):
         save_checkpoint({
             'state_dict': model.state_dict(), 'best_loss': best_loss, 'optimizer': optimizer.state_dict(), 'gated': args.gated,
             'n_blocks': args.n_blocks, 'data_channels': args.data_channels, 'hid_dims': args.hid_dims, 'out_dims': args.out_dims,
-            'height': args.image_size, 'width': args.image_size, 'conv_backend': args.conv_backend,
+            'height': args.image_size, 'width': args.image_size, 'conv_backend': args.conv_backend, 'head': args.head,
         }, is_best, folder='./trained_models/%s' % args.folder_name)
         if is_best:
             generate(epoch)
