@@ -638,6 +638,33 @@ int mmvae_head_nll_backward(const float* h, const float* weight, const float* bi
                             const float* g, float* dh_or_null, float* dw_or_null, float* db_or_null, int batch, int channels, int height,
                             int width, int hid, int levels, void* ws, long long ws_bytes, void* stream);
 
+/* 4 x 4, stride 2, pad 1 convolution and its transpose, bias-free, with a fused activation (csrc/conv4s2.h): bf16 operands (round to
+ * nearest even), fp32 accumulation, fp32 channels-last activations.  S is the high-resolution side [batch * hs * ws][cs], L the
+ * low-resolution side [batch * hs/2 * ws/2][cl]; weight is the module's own fp32 parameter (cl, cs, 4, 4): nn.Conv2d(cs, cl, 4, 2, 1)
+ * and nn.ConvTranspose2d(cl, cs, 4, 2, 1) both have it.  A position outside the image contributes nothing.
+ *   down:  dst[b,oy,ox,l] = act_out(sum_{s,ky,kx} src[b,2oy-1+ky,2ox-1+kx,s] w[l,s,ky,kx])              src on S, dst on L
+ *   up:    dst[b,iy,ix,s] = act_out(sum_{l,ky,kx: iy+1-ky, ix+1-kx even} src[b,(iy+1-ky)/2,(ix+1-kx)/2,l] w[l,s,ky,kx])   src on L, dst on S
+ *   wgrad: dw[l,s,ky,kx]  = sum_{b,oy,ox} l_side[b,oy,ox,l] s_side[b,2oy-1+ky,2ox-1+kx,s]
+ *   act: 0 none, 1 relu, 2 leaky (pre > 0 ? pre : slope pre), 3 sigmoid (1 / (1 + expf(-pre))).
+ *   A gradient operand: with src_y (y_s, y_l) non-null the operand is an upstream gradient g and the pointer the forward's saved
+ *   output y at the same positions; the operand used is none: g, relu: y > 0 ? g : 0, leaky: y > 0 ? g : slope g, sigmoid:
+ *   (g y) (1 - y), formed in fp32 while loading (act_in / act names the activation).  So the data gradient of down is up on (g, y)
+ *   and that of up is down on (g, y), both with act_out = 0.  wgrad: one of y_s, y_l at most.
+ *   Partial dw per chunk of L positions, folded in ascending chunk order: no atomics, two calls give identical bits.
+ *   ws: device scratch of workspace_bytes (0 for arguments out of range), 16-byte aligned, needs no initialisation; the packed
+ *   weights live there for the duration of one call only (MMVAE_ENOSPC when ws_bytes is less).
+ * Limits: cs, cl 1..max_channels, hs, ws even in 2..max_side, batch >= 1 (batch * hs * ws <= 2^24).
+ * geometry: L positions and output channels per workgroup tile, the least number of L positions per weight-gradient chunk (a
+ *   shape with more than max_chunks of them uses larger chunks), max_chunks and the two limits. */
+int mmvae_conv4s2_geometry(int* pos_tile, int* channel_tile, int* wgrad_chunk, int* max_chunks, int* max_channels, int* max_side);
+long long mmvae_conv4s2_workspace_bytes(int batch, int cs, int cl, int hs, int ws);
+int mmvae_conv4s2_down(const float* src, const float* src_y_or_null, const float* weight, float* dst, int act_in, int act_out, float slope,
+                       int batch, int cs, int cl, int hs, int ws, void* workspace, long long ws_bytes, void* stream);
+int mmvae_conv4s2_up(const float* src, const float* src_y_or_null, const float* weight, float* dst, int act_in, int act_out, float slope,
+                     int batch, int cs, int cl, int hs, int ws, void* workspace, long long ws_bytes, void* stream);
+int mmvae_conv4s2_wgrad(const float* s_side, const float* l_side, const float* y_s_or_null, const float* y_l_or_null, int act, float slope,
+                        float* dw, int batch, int cs, int cl, int hs, int ws, void* workspace, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 #include "pixelcnn.h"
 #include "causal_conv.h"
 #include "head_nll.h"
+#include "conv4s2.h"
 #include <cstring>
 #include <exception>
 
@@ -676,4 +677,48 @@ int mmvae_head_nll_backward(const float* h, const float* weight, const float* bi
     MMVAE_TRY(hn_prepare("head_nll_backward", s, h, ws, ws_bytes));
     MMVAE_REQUIRE(weight && bias && target && lse && g, "head_nll_backward: null argument");
     return guarded([&] { return launch_hn_backward(s, h, weight, bias, target, lse, g, dh, dw, db, ws, S(st)); });
+}
+
+// ---- 4 x 4 stride-2 convolution / transposed convolution with a fused activation (conv4s2.h)
+int mmvae_conv4s2_geometry(int* pos_tile, int* channel_tile, int* wgrad_chunk, int* max_chunks, int* max_channels, int* max_side) {
+    MMVAE_REQUIRE(pos_tile && channel_tile && wgrad_chunk && max_chunks && max_channels && max_side, "conv4s2_geometry: null argument");
+    *pos_tile = C4_TM; *channel_tile = C4_TN; *wgrad_chunk = C4_CHUNK; *max_chunks = C4_MAX_CHUNKS; *max_channels = C4_MAX_CH; *max_side = C4_MAX_SIDE;
+    return MMVAE_OK;
+}
+long long mmvae_conv4s2_workspace_bytes(int batch, int cs, int cl, int hs, int ws) {
+    const C4Shape s{batch, cs, cl, hs, ws};
+    return c4_shape_ok(s) ? (long long)c4_workspace_bytes(s) : 0;
+}
+static bool c4_act_ok(int act) { return act >= C4_ACT_NONE && act <= C4_ACT_SIGMOID; }
+static int c4_prepare(const char* what, const C4Shape& s, const void* ws, long long ws_bytes) {
+    MMVAE_REQUIRE(c4_shape_ok(s), "%s: batch = %d, Cs = %d, Cl = %d, Hs = %d, Ws = %d: need batch >= 1, channels 1..%d, even sides 2..%d and "
+                  "batch * Hs * Ws <= %d", what, s.B, s.Cs, s.Cl, s.Hs, s.Ws, (int)C4_MAX_CH, (int)C4_MAX_SIDE, (int)C4_MAX_POS);
+    MMVAE_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", what);
+    const long long need = (long long)c4_workspace_bytes(s);
+    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
+    return MMVAE_OK;
+}
+int mmvae_conv4s2_down(const float* src, const float* src_y, const float* weight, float* dst, int act_in, int act_out, float slope, int batch,
+                       int cs, int cl, int hs, int ws_, void* ws, long long ws_bytes, void* st) {
+    const C4Shape s{batch, cs, cl, hs, ws_};
+    MMVAE_TRY(c4_prepare("conv4s2_down", s, ws, ws_bytes));
+    MMVAE_REQUIRE(src && weight && dst, "conv4s2_down: null argument");
+    MMVAE_REQUIRE(c4_act_ok(act_in) && c4_act_ok(act_out), "conv4s2_down: act_in = %d, act_out = %d, need 0..3", act_in, act_out);
+    return guarded([&] { return launch_c4_down(s, src, src_y, weight, dst, act_in, act_out, slope, ws, S(st)); });
+}
+int mmvae_conv4s2_up(const float* src, const float* src_y, const float* weight, float* dst, int act_in, int act_out, float slope, int batch,
+                     int cs, int cl, int hs, int ws_, void* ws, long long ws_bytes, void* st) {
+    const C4Shape s{batch, cs, cl, hs, ws_};
+    MMVAE_TRY(c4_prepare("conv4s2_up", s, ws, ws_bytes));
+    MMVAE_REQUIRE(src && weight && dst, "conv4s2_up: null argument");
+    MMVAE_REQUIRE(c4_act_ok(act_in) && c4_act_ok(act_out), "conv4s2_up: act_in = %d, act_out = %d, need 0..3", act_in, act_out);
+    return guarded([&] { return launch_c4_up(s, src, src_y, weight, dst, act_in, act_out, slope, ws, S(st)); });
+}
+int mmvae_conv4s2_wgrad(const float* s_side, const float* l_side, const float* y_s, const float* y_l, int act, float slope, float* dw, int batch,
+                        int cs, int cl, int hs, int ws_, void* ws, long long ws_bytes, void* st) {
+    const C4Shape s{batch, cs, cl, hs, ws_};
+    MMVAE_TRY(c4_prepare("conv4s2_wgrad", s, ws, ws_bytes));
+    MMVAE_REQUIRE(s_side && l_side && dw, "conv4s2_wgrad: null argument");
+    MMVAE_REQUIRE(c4_act_ok(act) && !(y_s && y_l), "conv4s2_wgrad: act = %d (need 0..3), and one side at most carries a gradient", act);
+    return guarded([&] { return launch_c4_wgrad(s, s_side, l_side, y_s, y_l, act, slope, dw, ws, S(st)); });
 }

@@ -556,17 +556,23 @@ def latent_mmd(vae, loader, seed=0):
     (B,3,32,32) floats in [0,1], or tuples whose first entry is one) in eval mode (z = mu), draws as many N(0, I) samples from
     ``seed`` and compares the two sets in ONE call of the fused MMD op (``mmd.mmd_terms``; 10,000 x 10,000 pairs need no
     (N, N, D) tensor).  Prints and returns {"n", "k_prior", "k_posterior", "k_cross", "mmd"}: the means of k(prior, prior),
-    k(z, z), k(prior, z) and MMD = k_prior + k_posterior - 2 k_cross."""
+    k(z, z), k(prior, z) and MMD = k_prior + k_posterior - 2 k_cross.  A model whose ``encode`` returns z itself (``mnist.InfoVAE``,
+    batches of (B,1,28,28)) is taken as it is; when such a model lives on the CPU the three means are torch ops."""
     from .mmd import mmd_terms
     vae.eval()
     dev = next(vae.parameters()).device
     zs = []
     for batch in loader:
         x = batch[0] if isinstance(batch, (tuple, list)) else batch
-        zs.append(vae.encode(x.to(dev).float())[0].clone())
+        enc = vae.encode(x.to(dev).float())
+        zs.append((enc if torch.is_tensor(enc) else enc[0]).clone())          # (mu, logvar) or z itself
     z = torch.cat(zs).contiguous()
     prior = torch.randn(z.shape[0], z.shape[1], generator=torch.Generator().manual_seed(seed)).to(dev)
-    t = mmd_terms(prior, z).cpu().tolist()
+    if dev.type == "cuda":
+        t = mmd_terms(prior, z).cpu().tolist()
+    else:
+        from .mnist import mmd_terms_torch
+        t = [float(v) for v in mmd_terms_torch(prior, z)]
     out = {"n": int(z.shape[0]), "k_prior": t[0], "k_posterior": t[1], "k_cross": t[2], "mmd": t[3]}
     print('Latent MMD over {} examples: k(prior, prior) {:.6f}\tk(z, z) {:.6f}\tk(prior, z) {:.6f}\tMMD {:.6f}'.format(
         out["n"], out["k_prior"], out["k_posterior"], out["k_cross"], out["mmd"]))
@@ -656,10 +662,13 @@ def _parser():
     pn.add_argument('--json', type=str, default=None, help='write the result to this file')
     # aggregate posterior against the prior for a checkpoint of train_infovae
     pm = sub.add_parser("latent_mmd", help="MMD between the encoded test images and the prior, for a checkpoint of train_infovae")
-    pm.add_argument('model_path', type=str, help='path to a checkpoint written by train_infovae')
+    pm.add_argument('model_path', type=str, help='path to a checkpoint written by train_infovae (mnist: train_infovae_mnist)')
+    pm.add_argument('--dataset', type=str, default='coco', choices=('coco', 'mnist'),
+                    help='model family of the checkpoint (mnist: uint8 images (N,28,28), alone or as the first entry of a tuple)')
+    pm.add_argument('--conv_backend', choices=('torch', 'hip'), default='torch', help='mnist: what the convolutions run on (default: torch)')
     src = pm.add_mutually_exclusive_group()
     src.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='a .pt file of uint8 images (N,3,32,32)')
-    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic COCO-shaped images instead of a file')
+    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic images of the family\'s shape instead of a file')
     pm.add_argument('--batch_size', type=int, default=500)
     pm.add_argument('--seed', type=int, default=0, help='seed of the prior samples (and of the synthetic images)')
     pm.add_argument('--json', type=str, default=None, help='write the terms to this file')
@@ -668,6 +677,26 @@ def _parser():
 
 def _latent_mmd_main(args):
     import json
+    if args.dataset == "mnist":
+        from . import data as D
+        from .mnist import load_infovae_checkpoint, set_infovae_backend
+        if args.synthetic > 0:
+            x = D.synthetic_mnist(args.synthetic, seed=args.seed)[0]
+        elif args.data:
+            x = torch.load(args.data, weights_only=False)
+            x = torch.as_tensor(x[0] if isinstance(x, (tuple, list)) else x)
+        else:
+            raise SystemExit("latent_mmd: give --data FILE.pt or --synthetic N")
+        if x.dtype != torch.uint8 or x.dim() != 3 or tuple(x.shape[1:]) != (28, 28):
+            raise ValueError("latent_mmd: images must be uint8 (N,28,28) (got %s %s)" % (x.dtype, tuple(x.shape)))
+        x = x.float().div_(255.0).unsqueeze(1)                        # transforms.ToTensor()
+        loader = [x[i:i + args.batch_size] for i in range(0, x.shape[0], args.batch_size)]
+        vae = set_infovae_backend(load_infovae_checkpoint(args.model_path, use_cuda=True), args.conv_backend)
+        out = latent_mmd(vae, loader, seed=args.seed)
+        if args.json:
+            with open(args.json, 'w') as fp:
+                json.dump(out, fp, indent=1)
+        return out
     from .train_coco import synthetic_coco
     from .train_infovae import load_checkpoint
     if args.synthetic > 0:

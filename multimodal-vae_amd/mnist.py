@@ -4,6 +4,10 @@ Same class names, constructor arguments, ``forward`` signatures and ``state_dict
 ``nn.Linear / nn.BatchNorm1d / nn.Embedding`` children are parameter containers only; every module forward/backward
 is a call into libmmvae_hip.so.  No CPU fallback.  ``FusedTrainer`` runs the whole train() closure body
 (mnist/train.py:131-147 + optimizer.step()) as one enqueue.
+
+``InfoVAE`` (mnist/model.py:238-279) is the exception: a plain torch module that runs wherever torch runs.
+``set_infovae_backend(vae, "hip")`` routes its four bias-free 4 x 4 stride-2 convolutions, each with its activation, through
+``conv4s2.down4s2`` / ``up4s2`` (csrc/conv4s2.hip); its four ``nn.Linear`` layers stay torch ops under both backends.
 """
 from __future__ import annotations
 
@@ -12,6 +16,7 @@ from typing import Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from ._lib import MMVAEError, call, ptr
 from .core import FusedMnistStep, MnistState, StepOutputs
@@ -239,3 +244,91 @@ class FusedTrainer:
     def evaluate(self, image, label, **kw) -> StepOutputs:
         """mnist/train.py:165-177: eval-mode forward of the 3 passes, no backward."""
         return self.engine.forward_backward(image.reshape(-1, 784), label, training=False, backward=False, **kw)
+
+
+# ------------------------------------------------------------------------------------------------------ InfoVAE
+INFOVAE_BACKENDS = ("torch", "hip")
+
+
+class InfoVAE(nn.Module):
+    """mnist/model.py:238-279: the MMD-regularised convolutional autoencoder, same ``state_dict`` keys and shapes.  A plain torch
+    module; ``conv_backend`` (``set_infovae_backend``) chooses what the four convolution + activation pairs run on."""
+
+    def __init__(self, n_latents=20):
+        super().__init__()
+        self.n_latents = n_latents
+        self.encoder_conv = nn.Sequential(
+            nn.Conv2d(1, 64, 4, 2, 1, bias=False), nn.LeakyReLU(0.1, inplace=True),
+            nn.Conv2d(64, 128, 4, 2, 1, bias=False), nn.LeakyReLU(0.1, inplace=True))
+        self.encoder_fc = nn.Sequential(nn.Linear(128 * 7 * 7, 1024), nn.LeakyReLU(0.1, inplace=True), nn.Linear(1024, n_latents))
+        self.decoder_fc = nn.Sequential(nn.Linear(n_latents, 1024), nn.ReLU(True), nn.Linear(1024, 128 * 7 * 7), nn.ReLU(True))
+        self.decoder_conv = nn.Sequential(
+            nn.ConvTranspose2d(128, 64, 4, 2, 1, bias=False), nn.ReLU(True),
+            nn.ConvTranspose2d(64, 1, 4, 2, 1, bias=False))
+        self.conv_backend = "torch"
+
+    def encode(self, x):
+        if self.conv_backend == "hip":
+            from .conv4s2 import down4s2
+            x = down4s2(x, self.encoder_conv[0].weight, "leaky", self.encoder_conv[1].negative_slope)
+            x = down4s2(x, self.encoder_conv[2].weight, "leaky", self.encoder_conv[3].negative_slope)
+        else:
+            x = self.encoder_conv(x)
+        # (the op returns channels-last storage: reshape, not view, flattens the logical (c, h, w) order encoder_fc.0 expects)
+        return self.encoder_fc(x.reshape(x.size(0), -1))
+
+    def decode(self, z):
+        z = self.decoder_fc(z).view(-1, 128, 7, 7)
+        if self.conv_backend == "hip":
+            from .conv4s2 import up4s2
+            z = up4s2(z, self.decoder_conv[0].weight, "relu")
+            return up4s2(z, self.decoder_conv[2].weight, "sigmoid")
+        return torch.sigmoid(self.decoder_conv(z))
+
+    def forward(self, x):
+        z = self.encode(x)
+        return self.decode(z), z
+
+
+def set_infovae_backend(vae, backend):
+    """Chooses what the convolutions of an ``InfoVAE`` run on: ``"torch"`` (the default) or ``"hip"`` (each convolution with its
+    activation is one ``down4s2`` / ``up4s2`` call; the model has to be on the device by the time of its forward: a CPU tensor
+    raises ``MMVAEError``).  A plain attribute: no buffer, no parameter, the ``state_dict`` does not change.  The four ``nn.Linear``
+    layers and their activations stay torch ops.  -> vae"""
+    if backend not in INFOVAE_BACKENDS:
+        raise MMVAEError("set_infovae_backend: %r, need one of %s" % (backend, INFOVAE_BACKENDS))
+    if not isinstance(vae, InfoVAE):
+        raise MMVAEError("set_infovae_backend: a mnist.InfoVAE expected (got %s)" % type(vae).__name__)
+    vae.conv_backend = backend
+    return vae
+
+
+def mmd_terms_torch(x, y):
+    """mnist/train_infovae.py:59-76 in torch ops, for a model that lives on the CPU -> (mean Kxx, mean Kyy, mean Kxy, MMD)"""
+    def kernel(a, b):
+        return torch.exp(-(a.unsqueeze(1) - b.unsqueeze(0)).pow(2).mean(dim=2) / float(a.size(1)))
+    kxx, kyy, kxy = kernel(x, x).mean(), kernel(y, y).mean(), kernel(x, y).mean()
+    return kxx, kyy, kxy, kxx + kyy - 2 * kxy
+
+
+def infovae_loss(recon_x, x, z, true_samples: Optional[torch.Tensor] = None):
+    """mnist/train_infovae.py:45-56: ``mean((recon_x - x)^2) + MMD(true_samples, z)``, ``true_samples ~ N(0, I)`` of z's shape drawn
+    on z's device when not given.  On the device the MMD term is the fused op ``mmd.compute_mmd``; for a model on the CPU it is the
+    same formula in torch ops."""
+    if true_samples is None:
+        true_samples = torch.randn(z.shape, device=z.device, dtype=z.dtype)
+    NLL = F.mse_loss(recon_x, x)
+    if z.device.type == "cuda":
+        from .mmd import compute_mmd
+        return NLL + compute_mmd(true_samples, z)
+    return NLL + mmd_terms_torch(true_samples, z)[3]
+
+
+def load_infovae_checkpoint(file_path, use_cuda=False):
+    """mnist/train_infovae.py:28-42: rebuilds an InfoVAE (torch backend) from the checkpoint dict of either code base."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    vae = InfoVAE(n_latents=checkpoint['n_latents'])
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
