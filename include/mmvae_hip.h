@@ -665,6 +665,44 @@ int mmvae_conv4s2_up(const float* src, const float* src_y_or_null, const float* 
 int mmvae_conv4s2_wgrad(const float* s_side, const float* l_side, const float* y_s_or_null, const float* y_l_or_null, int act, float slope,
                         float* dw, int batch, int cs, int cl, int hs, int ws, void* workspace, long long ws_bytes, void* stream);
 
+/* Exact t-SNE with a 2-component embedding (mnist/manifold.py: TSNE(n_components=2, perplexity=40, n_iter=300) over the test set's
+ * latents), fp32 in and out, float64 sums in a fixed order, no atomics: two calls give identical bits.  3 <= n <= 32768; P is a
+ * dense [n][n] fp32 matrix of the caller (4 GiB at the largest n); x [n][dim], 1 <= dim <= max_dim (256); 1 <= perplexity < n - 1.
+ * Everything else is refused (MMVAE_EINVAL) before anything is launched, and workspace_bytes is 0.  ws: device scratch of
+ * mmvae_tsne_workspace_bytes(n) bytes, 8-byte aligned; every byte a call reads it has written itself (MMVAE_ENOSPC when ws_bytes
+ * is less).  All launches go to the caller's stream; no call synchronises.
+ * affinities: d_ij = sum_k (x_ik - x_jk)^2 from coordinate differences (16 fmaf chains, coordinate k in chain k % 16 in ascending
+ *   order, folded by a fixed tree: the rounding of a 256-term sum stays near that of a pairwise one); beta_i by sklearn's search
+ *   (start 1, double / halve until bracketed, then halve the bracket; stops at |H_i - log perplexity| <= 1e-5 or after 100 steps)
+ *   on p_{j|i} = exp(-beta_i (d_ij - min_{j != i} d_ij)) / sum, j != i; then P_ij = (p_{j|i} + p_{i|j}) / 2n, floored at 1e-12 off
+ *   the diagonal, exactly 0 on it, and symmetric bit for bit.  beta [n]: the beta_i the row was written with.  out2 = {sum P log P,
+ *   sum P}, folded in float64.
+ * grad: with w_ij = 1 / (1 + |y_i - y_j|^2) and Z = sum_{i != j} w_ij,
+ *     grad_i = 4 (exaggeration sum_j P_ij w_ij (y_i - y_j) - sum_j w_ij^2 (y_i - y_j) / Z)              grad [n][2], y [n][2]
+ *     KL     = sum P log P - sum P log w + log Z                                                       (P itself, never exaggerated)
+ *   out3 = {KL, Z, sum P log P}.  ONE sweep over the pairs: the repulsive sums are divided by Z afterwards.  P MUST BE SYMMETRIC,
+ *   as affinities writes it: the sweep reads P_ji where the formula says P_ij, so that a wave reads consecutive addresses.
+ * run: n_iter iterations of sklearn's _gradient_descent, all enqueued on the stream: per iteration the sweep and one fold / update
+ *   kernel.  Iteration k of the call is iteration first_iter + k of the schedule: exaggeration early_exaggeration and momentum 0.5
+ *   while first_iter + k < exaggeration_iters, then 1 and 0.8.  gains + 0.2 where update * grad < 0, else * 0.8, floor 0.01;
+ *   update = momentum update - learning_rate gains grad; y += update; no recentring.  y, update, gains [n][2] are in and out, so
+ *   a + b iterations in two calls give the bits of a + b in one.  kl_trace [n_iter]: each iteration's KL, before its update.
+ * geometry: row_tile (rows per sweep workgroup), col_tile (columns per column tile of the sweep), sym_tile (side of a
+ *   symmetrisation tile; workgroup (a, b), a <= b, writes tiles (a, b) and (b, a)), row_threads (threads of an affinity workgroup,
+ *   one per row i: thread t takes the columns t, t + row_threads, ...), max_dim.  The sweep's grid is R = ceil(n / row_tile) row
+ *   tiles x S column splits, S = max(1, min(T, 64, 2048 / R)) with T = ceil(n / col_tile); split c covers the column tiles
+ *   [T c / S, T (c + 1) / S).  Within a tile a wave sums the force terms of 8 columns at a time in fp32, everything above that
+ *   and the terms of Z and of the KL in float64.  Tests place their edges against these numbers; no result depends on them
+ *   beyond the last bits of a real-valued sum. */
+int mmvae_tsne_geometry(int* row_tile, int* col_tile, int* sym_tile, int* row_threads, int* max_dim);
+long long mmvae_tsne_workspace_bytes(int n);
+int mmvae_tsne_affinities(const float* x, int n, int dim, float perplexity, float* P, float* beta, float* out2, void* workspace,
+                          long long ws_bytes, void* stream);
+int mmvae_tsne_grad(const float* P, float exaggeration, const float* y, int n, void* workspace, long long ws_bytes, float* grad, float* out3,
+                    void* stream);
+int mmvae_tsne_run(const float* P, int n, float* y, float* update, float* gains, int first_iter, int n_iter, float learning_rate,
+                   float early_exaggeration, int exaggeration_iters, float* kl_trace, void* workspace, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,11 @@ SIGNATURES["mmvae_mmd_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER
 SIGNATURES["mmvae_mmd_workspace_bytes"] = (_LL, [_I, _I, _I])
 SIGNATURES["mmvae_mmd"] = (_I, [_P, _I, _P, _I, _I, _P, _LL, _P, _P, _P, _P])
 SIGNATURES["mmvae_mmd_kernel_matrix"] = (_I, [_P, _I, _P, _I, _I, _P, _P])
+SIGNATURES["mmvae_tsne_geometry"] = (_I, [C.POINTER(_I)] * 5)
+SIGNATURES["mmvae_tsne_workspace_bytes"] = (_LL, [_I])
+SIGNATURES["mmvae_tsne_affinities"] = (_I, [_P, _I, _I, _F, _P, _P, _P, _P, _LL, _P])
+SIGNATURES["mmvae_tsne_grad"] = (_I, [_P, _F, _P, _I, _P, _LL, _P, _P, _P])
+SIGNATURES["mmvae_tsne_run"] = (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _F, _I, _P, _P, _LL, _P])
 SIGNATURES["mmvae_pixelcnn_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)])
 SIGNATURES["mmvae_pixelcnn_param_elems"] = (_LL, [_I] * 5)
 SIGNATURES["mmvae_pixelcnn_packed_elems"] = (_LL, [_I] * 5)

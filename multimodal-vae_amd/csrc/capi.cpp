@@ -8,6 +8,7 @@
 #include "iw.h"
 #include "nn_words.h"
 #include "mmd.h"
+#include "tsne.h"
 #include "pixelcnn.h"
 #include "causal_conv.h"
 #include "head_nll.h"
@@ -721,4 +722,59 @@ int mmvae_conv4s2_wgrad(const float* s_side, const float* l_side, const float* y
     MMVAE_REQUIRE(s_side && l_side && dw, "conv4s2_wgrad: null argument");
     MMVAE_REQUIRE(c4_act_ok(act) && !(y_s && y_l), "conv4s2_wgrad: act = %d (need 0..3), and one side at most carries a gradient", act);
     return guarded([&] { return launch_c4_wgrad(s, s_side, l_side, y_s, y_l, act, slope, dw, ws, S(st)); });
+}
+
+// ---- exact t-SNE with a 2-component embedding (tsne.h)
+static bool tsne_n_ok(const char* what, int n) {
+    if (n < TSNE_MIN_N || n > TSNE_MAX_N) {
+        mmvae_set_error("%s: n = %d, need %d..%d", what, n, (int)TSNE_MIN_N, (int)TSNE_MAX_N);
+        return false;
+    }
+    return true;
+}
+static int tsne_ws_ok(const char* what, int n, const void* ws, long long ws_bytes) {
+    MMVAE_REQUIRE(ws, "%s: null argument", what);
+    const long long need = (long long)tsne_workspace_bytes(n);
+    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
+    return MMVAE_OK;
+}
+int mmvae_tsne_geometry(int* row_tile, int* col_tile, int* sym_tile, int* row_threads, int* max_dim) {
+    MMVAE_REQUIRE(row_tile && col_tile && sym_tile && row_threads && max_dim, "tsne_geometry: null argument");
+    *row_tile = TSNE_RT; *col_tile = TSNE_CT; *sym_tile = TSNE_ST; *row_threads = TSNE_AT; *max_dim = TSNE_MAX_DIM;
+    return MMVAE_OK;
+}
+long long mmvae_tsne_workspace_bytes(int n) {
+    if (n < TSNE_MIN_N || n > TSNE_MAX_N) return 0;
+    return (long long)tsne_workspace_bytes(n);
+}
+int mmvae_tsne_affinities(const float* x, int n, int dim, float perplexity, float* P, float* beta, float* out2, void* ws, long long ws_bytes,
+                          void* s) {
+    MMVAE_REQUIRE(x && P && beta && out2, "tsne_affinities: null argument");
+    if (!tsne_n_ok("tsne_affinities", n)) return MMVAE_EINVAL;
+    MMVAE_REQUIRE(dim >= 1 && dim <= TSNE_MAX_DIM, "tsne_affinities: dim = %d, need 1..%d", dim, (int)TSNE_MAX_DIM);
+    MMVAE_REQUIRE(perplexity >= 1.f && perplexity < (float)(n - 1), "tsne_affinities: perplexity = %g, need 1 <= perplexity < n - 1 = %d",
+                  (double)perplexity, n - 1);
+    MMVAE_TRY(tsne_ws_ok("tsne_affinities", n, ws, ws_bytes));
+    return guarded([&] { return launch_tsne_affinities(x, n, dim, perplexity, P, beta, out2, ws, S(s)); });
+}
+int mmvae_tsne_grad(const float* P, float exaggeration, const float* y, int n, void* ws, long long ws_bytes, float* grad, float* out3, void* s) {
+    MMVAE_REQUIRE(P && y && grad && out3, "tsne_grad: null argument");
+    if (!tsne_n_ok("tsne_grad", n)) return MMVAE_EINVAL;
+    MMVAE_REQUIRE(exaggeration > 0.f && exaggeration <= 3.0e38f, "tsne_grad: exaggeration = %g, need a positive finite number", (double)exaggeration);
+    MMVAE_TRY(tsne_ws_ok("tsne_grad", n, ws, ws_bytes));
+    return guarded([&] { return launch_tsne_grad(P, exaggeration, y, n, ws, grad, out3, S(s)); });
+}
+int mmvae_tsne_run(const float* P, int n, float* y, float* update, float* gains, int first_iter, int n_iter, float learning_rate,
+                   float early_exaggeration, int exaggeration_iters, float* kl_trace, void* ws, long long ws_bytes, void* s) {
+    MMVAE_REQUIRE(P && y && update && gains && kl_trace, "tsne_run: null argument");
+    if (!tsne_n_ok("tsne_run", n)) return MMVAE_EINVAL;
+    MMVAE_REQUIRE(first_iter >= 0 && n_iter >= 1 && n_iter <= 1000000, "tsne_run: first_iter = %d, n_iter = %d, need first_iter >= 0, n_iter 1..1000000",
+                  first_iter, n_iter);
+    MMVAE_REQUIRE(learning_rate > 0.f && learning_rate <= 3.0e38f && early_exaggeration > 0.f && early_exaggeration <= 3.0e38f,
+                  "tsne_run: learning_rate = %g, early_exaggeration = %g, need positive finite numbers", (double)learning_rate,
+                  (double)early_exaggeration);
+    MMVAE_TRY(tsne_ws_ok("tsne_run", n, ws, ws_bytes));
+    return guarded([&] {
+        return launch_tsne_run(P, n, y, update, gains, first_iter, n_iter, learning_rate, early_exaggeration, exaggeration_iters, kl_trace, ws, S(s));
+    });
 }

@@ -579,6 +579,59 @@ def latent_mmd(vae, loader, seed=0):
     return out
 
 
+@torch.no_grad()
+def manifold(vae, loader, pca_only=False, perplexity=40, n_iter=300, seed=0):
+    """mnist/manifold.py: encodes every (image, label) batch of ``loader`` with ``gen_latents`` in eval mode (z = mu of the joint
+    posterior) and reduces the latents to 2-D: ``tsne.pca(., 2)`` with ``pca_only``, else ``tsne.tsne`` (exact t-SNE on the GPU,
+    perplexity 40 and 300 iterations as the reference asks of sklearn) after ``pca(., 50)`` when n_latents > 50.  Returns CPU tensors
+    {"latents" (N, n_latents), "labels" (N,), "embedding" (N, 2), "kl_trace" (n_iter,) or None with ``pca_only``}: the KL of every
+    iteration, before its update."""
+    from .tsne import pca, tsne
+    vae.eval()
+    dev = next(vae.parameters()).device
+    zs, labels = [], []
+    for image, text in loader:
+        z = vae.gen_latents(image.to(dev).float().reshape(-1, 784), text.to(dev))
+        zs.append(z.float().clone())
+        labels.append(text.cpu())
+    latents, labels = torch.cat(zs).contiguous(), torch.cat(labels)
+    kl_trace = None
+    if pca_only:
+        embedding = pca(latents, 2)[0]
+    else:
+        z = pca(latents, 50)[0] if latents.shape[1] > 50 else latents
+        embedding, kl_trace = tsne(z, perplexity=perplexity, n_iter=n_iter, seed=seed, return_trace=True)
+        kl_trace = kl_trace.cpu()
+    return {"latents": latents.cpu(), "labels": labels, "embedding": embedding.cpu(), "kl_trace": kl_trace}
+
+
+def array2d_string(A):
+    """mnist/latent_viz.py:20-21"""
+    return '\n'.join([''.join(['{:4}'.format(item) for item in row]) for row in A])
+
+
+@torch.no_grad()
+def latent_viz(vae, nx=20, ny=20, lim=3.0):
+    """mnist/latent_viz.py for a model with a 2-D latent: decodes the grid linspace(-lim, lim, nx) x linspace(-lim, lim, ny) in ONE
+    batched call of each decoder.  Returns (canvas (28 ny, 28 nx), digits (ny, nx)), both on the CPU, in the reference's
+    orientation: grid row i holds the latents (x_j, y_i); the canvas shows row i in its (ny - 1 - i)-th band of 28 pixel rows (the
+    second latent grows upwards), ``digits[i, j]`` is the arg-max label of that point.  The HIP plan has no 2-latent size: the
+    decoders run on ``mnist.with_padded_latents(vae)``, the same functions with two extra latents held at zero."""
+    from .mnist import with_padded_latents
+    if vae.n_latents != 2:
+        raise ValueError("latent_viz: the model has n_latents = %d: the grid needs a 2-D latent" % vae.n_latents)
+    dec = with_padded_latents(vae).eval()
+    dev = next(dec.parameters()).device
+    xs, ys = torch.linspace(-lim, lim, nx), torch.linspace(-lim, lim, ny)
+    z = torch.zeros(nx * ny, dec.n_latents)
+    z[:, 0], z[:, 1] = xs.repeat(ny), ys.repeat_interleave(nx)                                  # row i * nx + j = (x_j, y_i)
+    z = z.to(dev)
+    image = dec.decode_image(z).float().reshape(ny, nx, 28, 28).cpu()
+    digits = dec.decode_text(z).argmax(dim=1).reshape(ny, nx).cpu()
+    canvas = image.flip(0).permute(0, 2, 1, 3).reshape(28 * ny, 28 * nx).contiguous()
+    return canvas, digits
+
+
 def _parser():
     import argparse
     parser = argparse.ArgumentParser(prog="python -m multimodal_vae_amd.evaluate")
@@ -672,6 +725,22 @@ def _parser():
     pm.add_argument('--batch_size', type=int, default=500)
     pm.add_argument('--seed', type=int, default=0, help='seed of the prior samples (and of the synthetic images)')
     pm.add_argument('--json', type=str, default=None, help='write the terms to this file')
+    # mnist/manifold.py: the test set's latents reduced to 2-D by PCA or by exact t-SNE on the GPU
+    pf = sub.add_parser("manifold", help="mnist/manifold.py: latents of the test set, PCA or PCA + t-SNE to 2-D")
+    pf.add_argument('model_path', type=str, help='path to trained model file (mnist family)')
+    pf.add_argument('--pca_only', action='store_true', default=False)
+    pf.add_argument('--perplexity', type=float, default=40.0)
+    pf.add_argument('--n_iter', type=int, default=300)
+    src = pf.add_mutually_exclusive_group()
+    src.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='a .pt file of (uint8 images (N,28,28), int64 labels (N,))')
+    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic MNIST-shaped examples instead of a file')
+    pf.add_argument('--batch_size', type=int, default=128)
+    pf.add_argument('--seed', type=int, default=0, help='seed of the initial embedding (and of the synthetic images)')
+    pf.add_argument('--out', type=str, default='./results')
+    # mnist/latent_viz.py: the decoders over a grid of a 2-D latent
+    pv = sub.add_parser("latent_viz", help="mnist/latent_viz.py: decodes a 20 x 20 grid of a 2-D latent")
+    pv.add_argument('model_path', type=str, help='path to trained model file (mnist family, n_latents = 2)')
+    pv.add_argument('--out', type=str, default='./results')
     return parser
 
 
@@ -715,6 +784,57 @@ def _latent_mmd_main(args):
         with open(args.json, 'w') as fp:
             json.dump(out, fp, indent=1)
     return out
+
+
+def _manifold_main(args):
+    import os
+    from . import data as D
+    from .mnist import load_checkpoint
+    if args.synthetic > 0:
+        x, t = D.synthetic_mnist(args.synthetic, seed=args.seed)
+    elif args.data:
+        x, t = torch.load(args.data, weights_only=False)
+        x, t = torch.as_tensor(x), torch.as_tensor(t)
+    else:
+        raise SystemExit("manifold: give --data FILE.pt or --synthetic N")
+    if x.dtype != torch.uint8 or x.dim() != 3 or tuple(x.shape[1:]) != (28, 28) or t.shape != x.shape[:1]:
+        raise ValueError("manifold: need uint8 images (N,28,28) and N labels (got %s %s, %s)" % (x.dtype, tuple(x.shape), tuple(t.shape)))
+    x, t = x.float().div_(255.0).view(-1, 784), t.long()          # transforms.ToTensor() + view(-1, 784)
+    loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    vae = load_checkpoint(args.model_path, use_cuda=True)
+    out = manifold(vae, loader, pca_only=args.pca_only, perplexity=args.perplexity, n_iter=args.n_iter, seed=args.seed)
+    os.makedirs(args.out, exist_ok=True)
+    torch.save(out, os.path.join(args.out, 'manifold.pt'))
+    if out["kl_trace"] is not None:
+        print('t-SNE over {} latents: KL {:.4f} -> {:.4f} in {} iterations'.format(
+            out["latents"].shape[0], float(out["kl_trace"][0]), float(out["kl_trace"][-1]), out["kl_trace"].shape[0]))
+    try:                                                          # the figure is optional: matplotlib may not be installed
+        import matplotlib
+        matplotlib.use('Agg')
+        import matplotlib.cm as cm
+        import matplotlib.pyplot as plt
+    except ImportError:
+        return out
+    plt.figure()
+    emb, lab = out["embedding"].numpy(), out["labels"].numpy()
+    for i, color in enumerate(cm.rainbow(np.linspace(0, 1, 10))):
+        plt.scatter(emb[lab == i, 0], emb[lab == i, 1], color=color, label=str(i), alpha=0.3, edgecolors='none')
+    plt.legend()
+    plt.savefig(os.path.join(args.out, 'manifold.png'))
+    plt.close()
+    return out
+
+
+def _latent_viz_main(args):
+    import os
+    from .mnist import load_checkpoint
+    vae = load_checkpoint(args.model_path, use_cuda=True)
+    canvas, digits = latent_viz(vae)
+    os.makedirs(args.out, exist_ok=True)
+    torch.save(canvas, os.path.join(args.out, 'latent_viz_image.pt'))
+    with open(os.path.join(args.out, 'latent_viz_text.txt'), 'w') as fp:
+        fp.write(array2d_string(digits.tolist()))
+    return canvas, digits
 
 
 def _nll_pixelcnn_main(args):
@@ -877,6 +997,10 @@ def _main(argv=None):
         return _sample_coco_main(args)
     if args.cmd == "latent_mmd":
         return _latent_mmd_main(args)
+    if args.cmd == "manifold":
+        return _manifold_main(args)
+    if args.cmd == "latent_viz":
+        return _latent_viz_main(args)
     if args.cmd == "sample_pixelcnn":
         return _sample_pixelcnn_main(args)
     if args.cmd == "nll_pixelcnn":

@@ -227,6 +227,38 @@ def load_checkpoint(file_path, use_cuda=False):
     return vae
 
 
+def plan_latents(n_latents):
+    """The smallest latent size >= ``n_latents`` that the HIP plan accepts (a multiple of 4 from 4 to 124)."""
+    return max(4, (int(n_latents) + 3) // 4 * 4)
+
+
+def with_padded_latents(vae):
+    """A ``MultimodalVAE`` of ``plan_latents(vae.n_latents)`` latents that computes what ``vae`` computes, for a model whose own
+    latent size the HIP plan does not accept (``mnist/latent_viz.py`` wants n_latents = 2).  The extra latents get zero columns in
+    the first Linear of either decoder, and zero rows and biases in the last Linear of either encoder (mu = logvar = 0 there), so
+    ``decode_image(cat(z, 0))`` and ``decode_text(cat(z, 0))`` are ``vae``'s decoders at z, and the first n_latents entries of the
+    encoders' outputs are ``vae``'s.  Every other parameter and buffer is copied; the result lives where ``vae`` lives, in its mode."""
+    n, big_n = vae.n_latents, plan_latents(vae.n_latents)
+    if big_n == n:
+        return vae
+    big = MultimodalVAE(n_latents=big_n, precision=vae.precision)
+    small, sd = vae.state_dict(), big.state_dict()
+    for k, v in small.items():
+        if sd[k].shape == v.shape:
+            sd[k] = v.detach().clone()
+            continue
+        t = torch.zeros_like(sd[k], device=v.device)
+        if k.startswith(("image_decoder.net.0.", "text_decoder.net.0.")):          # (out, n) -> (out, big_n)
+            t[:, :n] = v
+        else:                                                                      # (2 n, ...) -> (2 big_n, ...): mu rows, logvar rows
+            t[:n] = v[:n]
+            t[big_n:big_n + n] = v[n:]
+        sd[k] = t
+    big.load_state_dict(sd)
+    big.to(next(vae.parameters()).device)
+    return big.train(vae.training)
+
+
 class FusedTrainer:
     """``FusedTrainer(vae, batch_size, lr)(image, label)`` == zero_grad + 3 passes + 3 losses + backward + Adam step
     (mnist/train.py:131-147,149) on ``vae``'s own parameters."""
