@@ -23,7 +23,6 @@ the MMD term on the fused op of ``mmd.py``; ``compute_mmd`` / ``compute_kernel``
 """
 from __future__ import annotations
 
-import ctypes
 import weakref
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -31,6 +30,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
+from ._ops import geometry
 from .core import CocoState, FusedCocoStep, StepOutputs
 from .mmd import compute_kernel, compute_mmd, mmd_terms  # noqa: F401  (coco/model.py:385-402)
 from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
@@ -46,9 +46,7 @@ MAX_DISTS = 8              # queries of one mmvae_nn_words_dists call
 
 def nn_words_geometry() -> Tuple[int, int, int]:
     """(query rows per workgroup, words per vocabulary tile, largest number of vocabulary splits) of the search kernels."""
-    tq, tv, ms = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    call("mmvae_nn_words_geometry", ctypes.byref(tq), ctypes.byref(tv), ctypes.byref(ms))
-    return tq.value, tv.value, ms.value
+    return geometry("mmvae_nn_words_geometry", 3)
 
 
 class WordTable:

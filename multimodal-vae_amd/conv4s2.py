@@ -8,13 +8,12 @@ there is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Tuple
 
 import torch
 
 from ._lib import MMVAEError, call, ptr
-from .pixelcnn import _conv_ws, _empty_nhwc, _nhwc, _stream
+from ._ops import CONV_WS, empty_nhwc, geometry, nhwc, stream
 
 ACTS = ("none", "relu", "leaky", "sigmoid")
 
@@ -22,9 +21,7 @@ ACTS = ("none", "relu", "leaky", "sigmoid")
 def conv4s2_geometry() -> Tuple[int, int, int, int, int, int]:
     """(L positions per workgroup, output channels per workgroup, least L positions per weight-gradient chunk, most chunks, largest
     channel count, largest side of the high-resolution image)"""
-    v = [ctypes.c_int() for _ in range(6)]
-    call("mmvae_conv4s2_geometry", *[ctypes.byref(a) for a in v])
-    return tuple(a.value for a in v)
+    return geometry("mmvae_conv4s2_geometry", 6)
 
 
 def conv4s2_workspace_bytes(B, Cs, Cl, Hs, Ws) -> int:
@@ -54,8 +51,8 @@ def _check(what, x, weight, act, x_channels):
 
 
 def _tail(dims, dev):
-    ws = _conv_ws(dev, conv4s2_workspace_bytes(*dims))
-    return dims + (ptr(ws), ws.numel(), _stream())
+    ws = CONV_WS.get(dev, conv4s2_workspace_bytes(*dims))
+    return dims + (ptr(ws), ws.numel(), stream())
 
 
 class _Down(torch.autograd.Function):
@@ -63,9 +60,9 @@ class _Down(torch.autograd.Function):
     def forward(ctx, x, weight, act, slope):
         code, dims = _check("down4s2", x, weight, act, 1)
         B, Cs, Cl, Hs, Ws = dims
-        x, w = _nhwc(x.detach()), weight.detach().contiguous()
+        x, w = nhwc(x.detach()), weight.detach().contiguous()
         with torch.cuda.device(x.device):
-            y = _empty_nhwc(B, Cl, Hs // 2, Ws // 2, x.device)
+            y = empty_nhwc(B, Cl, Hs // 2, Ws // 2, x.device)
             call("mmvae_conv4s2_down", ptr(x), None, ptr(w), ptr(y), 0, code, float(slope), *_tail(dims, x.device))
         ctx.save_for_backward(x, w, y)
         ctx.code, ctx.slope, ctx.dims = code, float(slope), dims
@@ -76,12 +73,12 @@ class _Down(torch.autograd.Function):
     def backward(ctx, g):
         x, w, y = ctx.saved_tensors
         B, Cs, Cl, Hs, Ws = ctx.dims
-        g = _nhwc(g)
+        g = nhwc(g)
         yp = ptr(y) if ctx.code else None                  # (no activation: the gradient operand is g itself)
         dx = dw = None
         with torch.cuda.device(x.device):
             if ctx.needs_input_grad[0]:
-                dx = _empty_nhwc(B, Cs, Hs, Ws, x.device)
+                dx = empty_nhwc(B, Cs, Hs, Ws, x.device)
                 call("mmvae_conv4s2_up", ptr(g), yp, ptr(w), ptr(dx), ctx.code, 0, ctx.slope, *_tail(ctx.dims, x.device))
             if ctx.needs_input_grad[1]:
                 dw = torch.empty_like(w)
@@ -94,9 +91,9 @@ class _Up(torch.autograd.Function):
     def forward(ctx, x, weight, act, slope):
         code, dims = _check("up4s2", x, weight, act, 0)
         B, Cs, Cl, Hs, Ws = dims
-        x, w = _nhwc(x.detach()), weight.detach().contiguous()
+        x, w = nhwc(x.detach()), weight.detach().contiguous()
         with torch.cuda.device(x.device):
-            y = _empty_nhwc(B, Cs, Hs, Ws, x.device)
+            y = empty_nhwc(B, Cs, Hs, Ws, x.device)
             call("mmvae_conv4s2_up", ptr(x), None, ptr(w), ptr(y), 0, code, float(slope), *_tail(dims, x.device))
         ctx.save_for_backward(x, w, y)
         ctx.code, ctx.slope, ctx.dims = code, float(slope), dims
@@ -107,12 +104,12 @@ class _Up(torch.autograd.Function):
     def backward(ctx, g):
         x, w, y = ctx.saved_tensors
         B, Cs, Cl, Hs, Ws = ctx.dims
-        g = _nhwc(g)
+        g = nhwc(g)
         yp = ptr(y) if ctx.code else None
         dx = dw = None
         with torch.cuda.device(x.device):
             if ctx.needs_input_grad[0]:
-                dx = _empty_nhwc(B, Cl, Hs // 2, Ws // 2, x.device)
+                dx = empty_nhwc(B, Cl, Hs // 2, Ws // 2, x.device)
                 call("mmvae_conv4s2_down", ptr(g), yp, ptr(w), ptr(dx), ctx.code, 0, ctx.slope, *_tail(ctx.dims, x.device))
             if ctx.needs_input_grad[1]:
                 dw = torch.empty_like(w)

@@ -12,10 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import MMVAEError, StepIO, call, ptr
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._ops import stream as _stream
 
 
 class PlanState:

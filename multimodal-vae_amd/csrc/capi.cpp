@@ -476,6 +476,14 @@ int mmvae_adam_step_packed(float* p, float* g, float* m, float* v, long long n, 
 
 }  // extern "C"
 
+// ---- the workspace check of every stand-alone op: a null (align16: or misaligned) buffer is MMVAE_EINVAL, one below `need` MMVAE_ENOSPC
+static int ws_fits(const char* what, const void* ws, long long ws_bytes, long long need, bool align16) {
+    if (align16) MMVAE_REQUIRE(ws && aligned16(ws), "%s: the workspace must be a 16-byte aligned device buffer", what);
+    else MMVAE_REQUIRE(ws, "%s: null workspace", what);
+    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
+    return MMVAE_OK;
+}
+
 // ---- nearest-word search over an embedding table (nn_words.h)
 long long mmvae_nn_words_workspace_bytes(int n_queries, long long n_words) {
     if (n_queries <= 0 || n_words <= 0) return 0;
@@ -497,8 +505,7 @@ int mmvae_nn_words_nearest(const float* queries, int n_queries, const float* tab
     MMVAE_REQUIRE(queries && table && sqnorm && ws && index && dist, "nn_words_nearest: null argument");
     MMVAE_REQUIRE(n_queries > 0 && n_words > 0, "nn_words_nearest: n_queries = %d, n_words = %lld", n_queries, n_words);
     MMVAE_REQUIRE(dim == NNW_DIM, "nn_words_nearest: dim = %d, the kernels are built for %d", dim, NNW_DIM);
-    const long long need = (long long)nn_words_workspace_bytes(n_queries, n_words);
-    if (ws_bytes < need) { mmvae_set_error("nn_words_nearest: workspace too small (%lld < %lld)", ws_bytes, need); return MMVAE_ENOSPC; }
+    MMVAE_TRY(ws_fits("nn_words_nearest", ws, ws_bytes, (long long)nn_words_workspace_bytes(n_queries, n_words), false));
     return launch_nn_words_nearest(queries, n_queries, table, sqnorm, n_words, ws, index, dist, S(s));
 }
 int mmvae_nn_words_dists(const float* queries, int n_queries, const float* table, long long n_words, int dim, float* dist, void* s) {
@@ -534,8 +541,7 @@ int mmvae_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* w
               void* s) {
     MMVAE_REQUIRE(x && y && ws && out4, "mmd: null argument");
     if (!mmd_sizes_ok("mmd", n_x, n_y, dim)) return MMVAE_EINVAL;
-    const long long need = (long long)mmd_workspace_bytes(n_x, n_y, dim);
-    if (ws_bytes < need) { mmvae_set_error("mmd: workspace too small (%lld < %lld)", ws_bytes, need); return MMVAE_ENOSPC; }
+    MMVAE_TRY(ws_fits("mmd", ws, ws_bytes, (long long)mmd_workspace_bytes(n_x, n_y, dim), false));
     return launch_mmd(x, n_x, y, n_y, dim, ws, out4, dx, dy, S(s));
 }
 int mmvae_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, int dim, float* k, void* s) {
@@ -593,8 +599,7 @@ int mmvae_pixelcnn_sample(int gated, int n_blocks, int channels, int hid, int le
     MMVAE_REQUIRE(packed && ws && uniforms && out_levels && out_image, "pixelcnn_sample: null argument");
     MMVAE_REQUIRE(n_given >= 0 && n_given <= height * width, "pixelcnn_sample: n_given = %d, need 0..%d", n_given, height * width);
     MMVAE_REQUIRE(n_given == 0 || given, "pixelcnn_sample: n_given = %d without given", n_given);
-    const long long need = mmvae_pixelcnn_workspace_bytes(gated, n_blocks, channels, hid, levels, batch, height, width);
-    if (ws_bytes < need) { mmvae_set_error("pixelcnn_sample: workspace too small (%lld < %lld)", ws_bytes, need); return MMVAE_ENOSPC; }
+    MMVAE_TRY(ws_fits("pixelcnn_sample", ws, ws_bytes, mmvae_pixelcnn_workspace_bytes(gated, n_blocks, channels, hid, levels, batch, height, width), false));
     return guarded([&] { return launch_pcnn_sample(c, packed, ws, batch, height, width, uniforms, given, n_given, out_levels, out_image, out_logits, S(s)); });
 }
 
@@ -614,10 +619,7 @@ long long mmvae_causal_conv_workspace_bytes(int batch, int height, int width, in
 }
 static int cc_prepare(const char* what, const CcShape& s, const int* taps, int n_taps, const void* ws, long long ws_bytes, CcTaps* t) {
     MMVAE_TRY(cc_make_taps(what, s, taps, n_taps, t));
-    MMVAE_REQUIRE(ws, "%s: null workspace", what);
-    const long long need = (long long)cc_workspace_bytes(s, n_taps);
-    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
-    return MMVAE_OK;
+    return ws_fits(what, ws, ws_bytes, (long long)cc_workspace_bytes(s, n_taps), false);
 }
 int mmvae_causal_conv_forward(const float* x, const float* weight, const float* bias, float* y, const int* taps, int n_taps, int batch,
                               int height, int width, int cin, int cout, int kh, int kw, void* ws, long long ws_bytes, void* st) {
@@ -658,11 +660,10 @@ static int hn_prepare(const char* what, const HnShape& s, const float* h, const 
     MMVAE_REQUIRE(hn_shape_ok(s), "%s: batch = %d, channels = %d, height = %d, width = %d, hid = %d, levels = %d: need batch * height * width "
                   "in 1..%d, channels 1 or 3, hid a multiple of 8 in 8..%d, levels 2..%d", what, s.B, s.C, s.H, s.W, s.hid, s.V,
                   (int)HN_MAX_POS, (int)HN_MAX_HID, (int)HN_MAX_V);
-    MMVAE_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", what);
-    MMVAE_REQUIRE(h && (reinterpret_cast<uintptr_t>(h) & 15) == 0, "%s: h must be a 16-byte aligned device buffer", what);
-    const long long need = (long long)hn_workspace_bytes(s);
-    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
-    return MMVAE_OK;
+    // (h is checked between the workspace's alignment and its size, so the alignment line stays here)
+    MMVAE_REQUIRE(ws && aligned16(ws), "%s: the workspace must be a 16-byte aligned device buffer", what);
+    MMVAE_REQUIRE(h && aligned16(h), "%s: h must be a 16-byte aligned device buffer", what);
+    return ws_fits(what, ws, ws_bytes, (long long)hn_workspace_bytes(s), false);
 }
 int mmvae_head_nll_forward(const float* h, const float* weight, const float* bias, const long long* target, float* nll, float* lse, int batch,
                            int channels, int height, int width, int hid, int levels, void* ws, long long ws_bytes, void* st) {
@@ -694,10 +695,7 @@ static bool c4_act_ok(int act) { return act >= C4_ACT_NONE && act <= C4_ACT_SIGM
 static int c4_prepare(const char* what, const C4Shape& s, const void* ws, long long ws_bytes) {
     MMVAE_REQUIRE(c4_shape_ok(s), "%s: batch = %d, Cs = %d, Cl = %d, Hs = %d, Ws = %d: need batch >= 1, channels 1..%d, even sides 2..%d and "
                   "batch * Hs * Ws <= %d", what, s.B, s.Cs, s.Cl, s.Hs, s.Ws, (int)C4_MAX_CH, (int)C4_MAX_SIDE, (int)C4_MAX_POS);
-    MMVAE_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", what);
-    const long long need = (long long)c4_workspace_bytes(s);
-    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
-    return MMVAE_OK;
+    return ws_fits(what, ws, ws_bytes, (long long)c4_workspace_bytes(s), true);
 }
 int mmvae_conv4s2_down(const float* src, const float* src_y, const float* weight, float* dst, int act_in, int act_out, float slope, int batch,
                        int cs, int cl, int hs, int ws_, void* ws, long long ws_bytes, void* st) {
@@ -733,10 +731,8 @@ static bool tsne_n_ok(const char* what, int n) {
     return true;
 }
 static int tsne_ws_ok(const char* what, int n, const void* ws, long long ws_bytes) {
-    MMVAE_REQUIRE(ws, "%s: null argument", what);
-    const long long need = (long long)tsne_workspace_bytes(n);
-    if (ws_bytes < need) { mmvae_set_error("%s: workspace too small (%lld < %lld)", what, ws_bytes, need); return MMVAE_ENOSPC; }
-    return MMVAE_OK;
+    MMVAE_REQUIRE(ws, "%s: null argument", what);      // (this op's wording for a null workspace)
+    return ws_fits(what, ws, ws_bytes, (long long)tsne_workspace_bytes(n), false);
 }
 int mmvae_tsne_geometry(int* row_tile, int* col_tile, int* sym_tile, int* row_threads, int* max_dim) {
     MMVAE_REQUIRE(row_tile && col_tile && sym_tile && row_threads && max_dim, "tsne_geometry: null argument");

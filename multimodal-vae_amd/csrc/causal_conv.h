@@ -9,9 +9,10 @@
 //
 // Forward and data gradient are ONE implicit-GEMM kernel (M = positions, N = output channels, K = taps x input channels): the
 // data gradient runs it with negated offsets on a weight image packed with Cin and Cout exchanged.  A workgroup owns
-// CC_TM positions x CC_TN channels; per tap it stages the shifted activation rows through LDS (fp32 -> bf16 on the way in, rows
-// whose shifted position leaves the image as zeros: decided per row and tap) and reads the packed bf16 weights
-// [tap][channel padded to CC_TN][K padded to 32] straight from global memory as MFMA B fragments.
+// CC_TM positions x CC_TN channels; per tap it stages the shifted activation rows (rows whose shifted position leaves the image as
+// zeros: decided per row and tap) and reads the packed bf16 weights [tap][channel padded to CC_TN][K padded to 32] straight from
+// global memory as MFMA B fragments, inside the k-loop.  The LDS tile layouts, the fp32 -> bf16 staging and the MFMA tile are described
+// in conv_tile.h, which holds the pieces shared with conv4s2.
 // The weight gradient splits the positions into chunks of CC_CHUNK; workgroup (chunk, tap, 64 x 64 channel tile) writes its
 // fp32 partial g^T x_shifted to the workspace, and a second launch folds the partials in ascending chunk order and scatters them
 // into the (Cout, Cin, kh, kw) layout (db likewise, from a per-chunk column sum of g).  No atomics: two calls give identical bits.

@@ -1,12 +1,12 @@
 // Causal tap-list convolution: forward / data gradient (one implicit-GEMM kernel) and weight gradient (partials + fold).
 // See causal_conv.h for the definition and the decomposition.
 #include "causal_conv.h"
+#include "conv_tile.h"
 
 namespace {
 
 constexpr int NTHR = 256;
-constexpr int A_LD = CC_KC + 8;          // bf16 per LDS row of the activation tile: 272 B, a multiple of 16 B off the bank period
-constexpr int T_LD = CC_KP + 8;          // bf16 per LDS row of the transposed weight-gradient tiles: 144 B
+static_assert(CC_KC == CT_KC && CC_KP == CT_KP && CC_TM == 64 && CC_TN == 64, "conv_tile.h is written for these stages and this tile");
 
 // p = q * d + r for 0 <= p < 2^22: the float product is within one of the quotient, fixed up exactly in integers
 __device__ __forceinline__ void cc_divmod(int p, int d, float rcp, int& q, int& r) {
@@ -14,27 +14,6 @@ __device__ __forceinline__ void cc_divmod(int p, int d, float rcp, int& q, int& 
     r = p - q * d;
     if (r < 0) { q -= 1; r += d; }
     if (r >= d) { q += 1; r -= d; }
-}
-
-// 4 consecutive channels of one position row; `left` = channels from src to the end of the row (<= 0: none)
-template <bool VEC>
-__device__ __forceinline__ float4 cc_load4(const float* __restrict__ src, int left) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (VEC) {
-        if (left > 0) v = *reinterpret_cast<const float4*>(src);
-    } else {
-        if (left > 0) v.x = src[0];
-        if (left > 1) v.y = src[1];
-        if (left > 2) v.z = src[2];
-        if (left > 3) v.w = src[3];
-    }
-    return v;
-}
-
-__device__ __forceinline__ bf16x4 cc_round4(const float4& v) {
-    bf16x4 o;
-    o[0] = f2bf(v.x); o[1] = f2bf(v.y); o[2] = f2bf(v.z); o[3] = f2bf(v.w);
-    return o;
 }
 
 // ---- weights -> bf16 [tap][Np][Kp], taps that exist only.  transposed == 0: row n = co, k = ci (forward);
@@ -88,7 +67,7 @@ __global__ __launch_bounds__(NTHR) void cc_gemm_kernel(const float* __restrict__
         for (int i = 0; i < 8; ++i) {
             const bool ok = (unsigned)(pi[i] + dy) < (unsigned)H && (unsigned)(pj[i] + dx) < (unsigned)W;
             const long long row = (long long)(p0 + r0 + 8 * i) + shift;
-            v[i] = ok ? cc_load4<VEC>(x + row * Cin + k, Cin - k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[i] = ok ? load4<VEC>(x + row * Cin + k, Cin - k) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
 
@@ -101,8 +80,9 @@ __global__ __launch_bounds__(NTHR) void cc_gemm_kernel(const float* __restrict__
 
     fetch(0);
     for (int s = 0; s < S; ++s) {
+        // the 8 staged rows -> bf16 LDS tile (written out, not a conv_tile.h helper: through a pointer parameter the LDS addresses come out differently and the kernel measured slower)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<bf16x4*>(&As[(r0 + 8 * i) * A_LD + 4 * c4]) = cc_round4(v[i]);
+        for (int i = 0; i < 8; ++i) *reinterpret_cast<bf16x4*>(&As[(r0 + 8 * i) * A_LD + 4 * c4]) = round4(v[i]);
         __syncthreads();
         if (s + 1 < S) fetch(s + 1);
         const int t = s / spt, kc = (s - t * spt) * CC_KC;
@@ -114,10 +94,7 @@ __global__ __launch_bounds__(NTHR) void cc_gemm_kernel(const float* __restrict__
             for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const bf16x8*>(&As[(wm * 32 + a * 16 + fr) * A_LD + ks * 32 + 8 * fq]);
 #pragma unroll
             for (int b = 0; b < 2; ++b) bfr[b] = *reinterpret_cast<const bf16x8*>(wrow + (long long)b * 16 * Kp + ks * 32);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
+            mma_2x2(af, bfr, acc);
         }
         if (kc + CC_KC >= Kp) {                  // the tap's last stage
 #pragma unroll
@@ -131,7 +108,6 @@ __global__ __launch_bounds__(NTHR) void cc_gemm_kernel(const float* __restrict__
         __syncthreads();
     }
 
-    // C fragment: column = lane & 15, row = 4 (lane >> 4) + register
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
         const int col = n0 + wn * 32 + b * 16 + fr;
@@ -179,19 +155,9 @@ __global__ __launch_bounds__(NTHR) void cc_wgrad_kernel(const float* __restrict_
                 cc_divmod(rem, W, rcpW, ii, jj);
                 const bool ok = in && (unsigned)(ii + dy) < (unsigned)H && (unsigned)(jj + dx) < (unsigned)W;
                 const int kg = co0 + 4 * cg, kx = ci0 + 4 * cg;
-                vg[it][e] = in ? cc_load4<VEC_G>(g + (long long)p * Cout + kg, Cout - kg) : make_float4(0.f, 0.f, 0.f, 0.f);
-                vx[it][e] = ok ? cc_load4<VEC_X>(x + ((long long)p + shift) * Cin + kx, Cin - kx) : make_float4(0.f, 0.f, 0.f, 0.f);
+                vg[it][e] = in ? load4<VEC_G>(g + (long long)p * Cout + kg, Cout - kg) : make_float4(0.f, 0.f, 0.f, 0.f);
+                vx[it][e] = ok ? load4<VEC_X>(x + ((long long)p + shift) * Cin + kx, Cin - kx) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
-    };
-    auto put = [&](bf16* dst, const float4& a, const float4& b, int lp) {          // positions lp, lp + 1 of channels 4 cg .. 4 cg + 3
-        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-            bf16x2 pr;
-            pr[0] = f2bf(av[j]); pr[1] = f2bf(bv[j]);
-            *reinterpret_cast<bf16x2*>(&dst[(4 * cg + j) * T_LD + lp]) = pr;
-        }
     };
 
     f32x4 acc[2][2];
@@ -205,11 +171,12 @@ __global__ __launch_bounds__(NTHR) void cc_wgrad_kernel(const float* __restrict_
     for (int s = 0; s < S; ++s) {
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
-            put(Gs, vg[it][0], vg[it][1], 2 * (it * 16 + pp));
-            put(Xs, vx[it][0], vx[it][1], 2 * (it * 16 + pp));
+            put_pair(Gs, vg[it][0], vg[it][1], cg, 2 * (it * 16 + pp));
+            put_pair(Xs, vx[it][0], vx[it][1], cg, 2 * (it * 16 + pp));
         }
         __syncthreads();
         if (s + 1 < S) fetch(s + 1);
+        // (the k-steps are written out for the same reason as the staging of cc_gemm_kernel: as a helper this kernel ran 1 % slower)
 #pragma unroll
         for (int ks = 0; ks < CC_KP / 32; ++ks) {
             bf16x8 af[2], bfr[2];
@@ -217,27 +184,12 @@ __global__ __launch_bounds__(NTHR) void cc_wgrad_kernel(const float* __restrict_
             for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const bf16x8*>(&Gs[(wm * 32 + a * 16 + fr) * T_LD + ks * 32 + 8 * fq]);
 #pragma unroll
             for (int b = 0; b < 2; ++b) bfr[b] = *reinterpret_cast<const bf16x8*>(&Xs[(wn * 32 + b * 16 + fr) * T_LD + ks * 32 + 8 * fq]);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
+            mma_2x2(af, bfr, acc);
         }
         __syncthreads();
     }
 
-    float* out = part + ((long long)chunk * taps.n + t) * Cout * Cin;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int ci = ci0 + wn * 32 + b * 16 + fr;
-        if (ci >= Cin) continue;
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co = co0 + wm * 32 + a * 16 + 4 * fq + j;
-                if (co < Cout) out[(long long)co * Cin + ci] = acc[a][b][j];
-            }
-    }
+    store_partial(part + ((long long)chunk * taps.n + t) * Cout * Cin, acc, co0, Cout, ci0, Cin, Cin, wm, wn, fr, fq);
 }
 
 // ---- bias gradient, partials: dbp[chunk][co] = sum over the chunk's positions of g[p][co], fp32, fixed order
@@ -279,7 +231,6 @@ __global__ __launch_bounds__(NTHR) void cc_fold_kernel(const float* __restrict__
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline long long positions(const CcShape& s) { return (long long)s.B * s.H * s.W; }
 inline int chunks_of(const CcShape& s) { return (int)((positions(s) + CC_CHUNK - 1) / CC_CHUNK); }
 inline size_t pack_bytes(int n_taps, int n, int k) { return (size_t)n_taps * round_up(n, CC_TN) * round_up(k, 32) * sizeof(bf16); }

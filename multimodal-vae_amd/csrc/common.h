@@ -7,6 +7,7 @@
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
@@ -152,3 +153,4 @@ static inline bool mmvae_first_use_on_device(std::atomic<unsigned>& mask) {
 
 __host__ __device__ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -17,9 +17,10 @@
 // pixel's row and column parity (py, px) selects 2 x 2 of the 16 cells, so the S side splits into four dense sub-problems
 // (blockIdx.z) of 4 taps, K = Cl per tap: tap (a, c) of class (py, px) is cell (1-py+2a, 1-px+2c) read at L position (qy+py-a, qx+px-c),
 // the output row is S position (2qy+py, 2qx+px).  A workgroup owns C4_TM rows x C4_TN output channels; per tap it stages the source
-// rows through LDS (fp32 -> bf16 on the way in) and reads the packed bf16 weights [cell][N padded to C4_TN][K padded to 32] from
-// global memory as MFMA B fragments (all k-steps of a tap, issued in front of the barrier); the source rows are fetched two taps
-// ahead.  One fp32 chain per tap, the taps summed in a second chain.
+// rows and reads the packed bf16 weights [cell][N padded to C4_TN][K padded to 32] from global memory as MFMA B fragments (all
+// k-steps of a tap, issued in front of the barrier); the source rows are fetched two taps ahead.  One fp32 chain per tap, the taps
+// summed in a second chain.  The LDS tile layouts, the fp32 -> bf16 staging and the MFMA tile are described in conv_tile.h, which holds
+// the pieces shared with causal_conv.
 // Cs == 1 (the model's outer pair) has a GEMM dimension of 1, so it runs on the vector unit instead: down as 16 multiply-adds per
 // output from the fp32 weights themselves, up as four dot products over Cl per S pixel with the weights in LDS, the weight gradient
 // as per-thread sums over position slices folded in ascending order.  Same rounding, same contract, nothing to pack.

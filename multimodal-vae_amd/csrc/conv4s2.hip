@@ -1,34 +1,13 @@
 // 4 x 4 stride-2 convolution / transposed convolution with a fused activation: down / up (one implicit-GEMM kernel) and the weight
 // gradient (partials + fold).  See conv4s2.h for the definition and the decomposition.
 #include "conv4s2.h"
+#include "conv_tile.h"
 
 namespace {
 
 constexpr int NTHR = 256;
 constexpr int KC = C4_MAX_CH;            // channels staged per tap: the whole (padded) K
-constexpr int A_LD = KC + 8;             // bf16 per LDS row of the source tile: 272 B, a multiple of 16 B off the bank period
-constexpr int T_LD = C4_KP + 8;          // bf16 per LDS row of the transposed weight-gradient tiles: 144 B
-
-// 4 consecutive channels of one position row; `left` = channels from src to the end of the row (<= 0: none)
-template <bool VEC>
-__device__ __forceinline__ float4 c4_load4(const float* __restrict__ src, int left) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (VEC) {
-        if (left > 0) v = *reinterpret_cast<const float4*>(src);
-    } else {
-        if (left > 0) v.x = src[0];
-        if (left > 1) v.y = src[1];
-        if (left > 2) v.z = src[2];
-        if (left > 3) v.w = src[3];
-    }
-    return v;
-}
-
-__device__ __forceinline__ bf16x4 c4_round4(const float4& v) {
-    bf16x4 o;
-    o[0] = f2bf(v.x); o[1] = f2bf(v.y); o[2] = f2bf(v.z); o[3] = f2bf(v.w);
-    return o;
-}
+static_assert(KC == CT_KC && C4_KP == CT_KP && C4_TM == 64 && C4_TN == 64, "conv_tile.h is written for these stages and this tile");
 
 __device__ __forceinline__ float c4_act(int act, float slope, float pre) {
     if (act == C4_ACT_RELU) return pre > 0.f ? pre : 0.f;
@@ -101,8 +80,8 @@ __global__ __launch_bounds__(NTHR) void c4_gemm_kernel(const float* __restrict__
         for (int i = 0; i < 8; ++i) {
             const bool ok = (unsigned)(by[i] + oy) < (unsigned)SH && (unsigned)(bx[i] + ox) < (unsigned)SW;
             const long long off = (long long)(rb[i] + shift) * K + k;
-            v[i] = ok ? c4_load4<VEC>(src + off, K - k) : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ysrc != nullptr && ok) v[i] = c4_gp4(act_in, slope, v[i], c4_load4<VEC>(ysrc + off, K - k));
+            v[i] = ok ? load4<VEC>(src + off, K - k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ysrc != nullptr && ok) v[i] = c4_gp4(act_in, slope, v[i], load4<VEC>(ysrc + off, K - k));
         }
     };
 
@@ -115,8 +94,9 @@ __global__ __launch_bounds__(NTHR) void c4_gemm_kernel(const float* __restrict__
 
     const int ksteps = Kp / 32;
     auto stage = [&](int t, float4 (&v)[8]) {
+        // the 8 staged rows -> bf16 LDS tile (written out, not a conv_tile.h helper: through a pointer parameter the LDS addresses come out differently and the kernel measured slower)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<bf16x4*>(&As[(r0 + 8 * i) * A_LD + 4 * c4]) = c4_round4(v[i]);
+        for (int i = 0; i < 8; ++i) *reinterpret_cast<bf16x4*>(&As[(r0 + 8 * i) * A_LD + 4 * c4]) = round4(v[i]);
         // the tap's weight fragments, all k-steps, issued before the barrier so that their latency overlaps it
         const int cell = UP ? (1 - py + 2 * (t >> 1)) * 4 + (1 - px + 2 * (t & 1)) : t;
         const bf16* wrow = wp + ((long long)cell * Np + n0 + wn * 32 + fr) * Kp + 8 * fq;
@@ -134,10 +114,7 @@ __global__ __launch_bounds__(NTHR) void c4_gemm_kernel(const float* __restrict__
                 bf16x8 af[2];
 #pragma unroll
                 for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const bf16x8*>(&As[(wm * 32 + a * 16 + fr) * A_LD + ks * 32 + 8 * fq]);
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[ks][b], acc[a][b], 0, 0, 0);
+                mma_2x2(af, bfr[ks], acc);
             }
         }
 #pragma unroll
@@ -157,7 +134,6 @@ __global__ __launch_bounds__(NTHR) void c4_gemm_kernel(const float* __restrict__
         stage(t + 1, vb);
     }
 
-    // C fragment: column = lane & 15, row = 4 (lane >> 4) + register
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -212,21 +188,11 @@ __global__ __launch_bounds__(NTHR) void c4_wgrad_kernel(const float* __restrict_
                 const bool ok = in && (unsigned)sy < (unsigned)SH && (unsigned)sx < (unsigned)SW;
                 const int kl = l0 + 4 * cg, ks = s0 + 4 * cg;
                 const long long offl = (long long)pc * Cl + kl, offs = ((long long)(b * SH + sy) * SW + sx) * Cs + ks;
-                vl[it][e] = in ? c4_load4<VEC_L>(lt + offl, Cl - kl) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (yl != nullptr && in) vl[it][e] = c4_gp4(act, slope, vl[it][e], c4_load4<VEC_L>(yl + offl, Cl - kl));
-                vs[it][e] = ok ? c4_load4<VEC_S>(st + offs, Cs - ks) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (ys != nullptr && ok) vs[it][e] = c4_gp4(act, slope, vs[it][e], c4_load4<VEC_S>(ys + offs, Cs - ks));
+                vl[it][e] = in ? load4<VEC_L>(lt + offl, Cl - kl) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (yl != nullptr && in) vl[it][e] = c4_gp4(act, slope, vl[it][e], load4<VEC_L>(yl + offl, Cl - kl));
+                vs[it][e] = ok ? load4<VEC_S>(st + offs, Cs - ks) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ys != nullptr && ok) vs[it][e] = c4_gp4(act, slope, vs[it][e], load4<VEC_S>(ys + offs, Cs - ks));
             }
-    };
-    auto put = [&](bf16* dst, const float4& a, const float4& b, int lp) {          // positions lp, lp + 1 of channels 4 cg .. 4 cg + 3
-        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-            bf16x2 pr;
-            pr[0] = f2bf(av[j]); pr[1] = f2bf(bv[j]);
-            *reinterpret_cast<bf16x2*>(&dst[(4 * cg + j) * T_LD + lp]) = pr;
-        }
     };
 
     f32x4 acc[2][2];
@@ -242,11 +208,12 @@ __global__ __launch_bounds__(NTHR) void c4_wgrad_kernel(const float* __restrict_
     for (int s = 0; s < S; ++s) {
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
-            put(Ls, vl[it][0], vl[it][1], 2 * (it * 16 + pp));
-            put(Ss, vs[it][0], vs[it][1], 2 * (it * 16 + pp));
+            put_pair(Ls, vl[it][0], vl[it][1], cg, 2 * (it * 16 + pp));
+            put_pair(Ss, vs[it][0], vs[it][1], cg, 2 * (it * 16 + pp));
         }
         __syncthreads();
         if (s + 1 < S) fetch(s + 1);
+        // (the k-steps are written out for the same reason as the staging of c4_gemm_kernel: as a helper this kernel ran 1 % slower)
 #pragma unroll
         for (int ks = 0; ks < C4_KP / 32; ++ks) {
             bf16x8 af[2], bfr[2];
@@ -254,27 +221,12 @@ __global__ __launch_bounds__(NTHR) void c4_wgrad_kernel(const float* __restrict_
             for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const bf16x8*>(&Ls[(wm * 32 + a * 16 + fr) * T_LD + ks * 32 + 8 * fq]);
 #pragma unroll
             for (int b = 0; b < 2; ++b) bfr[b] = *reinterpret_cast<const bf16x8*>(&Ss[(wn * 32 + b * 16 + fr) * T_LD + ks * 32 + 8 * fq]);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
+            mma_2x2(af, bfr, acc);
         }
         __syncthreads();
     }
 
-    float* out = part + ((long long)ch * 16 + cell) * Cl * Cs;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int s = s0 + wn * 32 + b * 16 + fr;
-        if (s >= Cs) continue;
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int l = l0 + wm * 32 + a * 16 + 4 * fq + j;
-                if (l < Cl) out[(long long)l * Cs + s] = acc[a][b][j];
-            }
-    }
+    store_partial(part + ((long long)ch * 16 + cell) * Cl * Cs, acc, l0, Cl, s0, Cs, Cs, wm, wn, fr, fq);
 }
 
 // ---- Cs == 1 on the vector unit.  With one channel on the S side the GEMM has K = 16 (down) or N = 1 (up, weight gradient): a
@@ -351,8 +303,8 @@ __global__ __launch_bounds__(NTHR) void c4_up1_kernel(const float* __restrict__ 
         const float* wc = wq + cell * Cl;
         float acc = 0.f;
         for (int l = 0; l < Cl; l += 4) {
-            float4 v = c4_load4<VEC>(x + off + l, Cl - l);
-            if (yx != nullptr) v = c4_gp4(act_in, slope, v, c4_load4<VEC>(yx + off + l, Cl - l));
+            float4 v = load4<VEC>(x + off + l, Cl - l);
+            if (yx != nullptr) v = c4_gp4(act_in, slope, v, load4<VEC>(yx + off + l, Cl - l));
             acc += c4_q(v.x) * wc[l];
             if (l + 1 < Cl) acc += c4_q(v.y) * wc[l + 1];
             if (l + 2 < Cl) acc += c4_q(v.z) * wc[l + 2];
@@ -418,7 +370,6 @@ __global__ __launch_bounds__(NTHR) void c4_fold_kernel(const float* __restrict__
     dw[(long long)idx * 16 + cell] = s;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int l_positions(const C4Shape& s) { return s.B * (s.Hs / 2) * (s.Ws / 2); }
 inline int chunks_of(const C4Shape& s) { return ceil_div(l_positions(s), c4_chunk(s)); }
 inline size_t pack_bytes(int n, int k) { return (size_t)16 * round_up(n, C4_TN) * round_up(k, 32) * sizeof(bf16); }

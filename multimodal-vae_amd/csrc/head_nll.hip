@@ -9,7 +9,6 @@ constexpr int NTHR = 256;
 constexpr int T_LD = 64 + 8;             // bf16 per LDS row of a 64-wide tile: 144 B, a multiple of 16 B off the bank period
 constexpr float NEG_BIG = -3.0e38f;      // start of the running maximum: finite, so that no inf - inf can arise
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 struct HnDims {
     int P, HW, C, hid, V;

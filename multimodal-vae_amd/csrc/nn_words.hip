@@ -222,8 +222,6 @@ __global__ __launch_bounds__(NTHR) void nn_words_merge_kernel(const float* __res
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 int nn_words_splits(int n_queries, long long n_words) {

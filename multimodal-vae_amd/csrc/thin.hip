@@ -10,7 +10,6 @@ namespace {
 
 constexpr int TPB = 256;
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 __device__ __forceinline__ float dot8(bf16x8 a, bf16x8 b, float acc) {
     // 8 bf16 MACs as 4 packed v_dot2c_f32_bf16 (fp32 accumulate)

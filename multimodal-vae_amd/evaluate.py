@@ -8,11 +8,11 @@ of the 4 target characters -- is what is computed here (``recon_text.view(-1, 12
 """
 from __future__ import annotations
 
-import ctypes as C
 
 import numpy as np
 import torch
 
+from . import _ops
 from .multimnist import _BCEMeanFn, _NLLMeanFn
 from .utils import FILL, max_length
 
@@ -339,7 +339,7 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     state = torch.empty(B, 3, 4, **f32)
     z_all = torch.empty(B, K, D, **f32) if return_z else None
     lw_all = torch.empty(B, K, 3, **f32) if return_log_w else None
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = _ops.stream()
     _iw_call("mmvae_iw_init", ptr(state), B, stream)
     for r0, nr, k0, nk in chunks:
         rows = nr * nk

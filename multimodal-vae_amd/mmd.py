@@ -12,23 +12,19 @@ shape).  Results depend on the shape alone: two calls give identical bits.
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Dict, Tuple
+from typing import Tuple
 
 import torch
 
 from ._lib import MMVAEError, call, ptr
-from .multimnist import _stream
+from ._ops import WorkspaceCache, geometry, stream
 
-_WS: Dict[Tuple[int, int, int, int, int], torch.Tensor] = {}
-_WS_MAX = 8          # cached workspaces (the oldest goes first)
+_WS = WorkspaceCache(8)          # cached workspaces (the oldest goes first)
 
 
 def mmd_geometry() -> Tuple[int, int, int]:
     """(rows per workgroup, rows per column tile, largest D) of the kernels; include/mmvae_hip.h states the split rule."""
-    rt, ct, md = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    call("mmvae_mmd_geometry", ctypes.byref(rt), ctypes.byref(ct), ctypes.byref(md))
-    return rt.value, ct.value, md.value
+    return geometry("mmvae_mmd_geometry", 3)
 
 
 def _pair(x: torch.Tensor, y: torch.Tensor, what: str):
@@ -50,13 +46,7 @@ def _workspace(dev: torch.device, n_x: int, n_y: int, dim: int) -> Tuple[torch.T
     if need <= 0:
         _, _, md = mmd_geometry()
         raise MMVAEError("mmd: n_x = %d, n_y = %d, D = %d: need 1..65536 rows and 1..%d columns" % (n_x, n_y, dim, md))
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream, n_x, n_y, dim)
-    ws = _WS.get(key)
-    if ws is None:
-        while len(_WS) >= _WS_MAX:
-            _WS.pop(next(iter(_WS)))
-        ws = _WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws, need
+    return _WS.get(dev, need, n_x, n_y, dim), need
 
 
 def _run(x: torch.Tensor, y: torch.Tensor, grad: bool):
@@ -66,7 +56,7 @@ def _run(x: torch.Tensor, y: torch.Tensor, grad: bool):
         out = torch.empty(4, dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x) if grad else None
         dy = torch.empty_like(y) if grad else None
-        call("mmvae_mmd", ptr(x), n_x, ptr(y), n_y, dim, ptr(ws), need, ptr(out), ptr(dx), ptr(dy), _stream())
+        call("mmvae_mmd", ptr(x), n_x, ptr(y), n_y, dim, ptr(ws), need, ptr(out), ptr(dx), ptr(dy), stream())
     return out, dx, dy
 
 
@@ -103,5 +93,5 @@ def compute_kernel(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     x, y, n_x, n_y, dim = _pair(x, y, "compute_kernel")
     k = torch.empty(n_x, n_y, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        call("mmvae_mmd_kernel_matrix", ptr(x), n_x, ptr(y), n_y, dim, ptr(k), _stream())
+        call("mmvae_mmd_kernel_matrix", ptr(x), n_x, ptr(y), n_y, dim, ptr(k), stream())
     return k

@@ -17,7 +17,6 @@ GPU the first forward raises ``MMVAEError``.  The whole 3-pass training step as 
 """
 from __future__ import annotations
 
-import ctypes as C
 import weakref
 from typing import List, Optional, Tuple
 
@@ -26,6 +25,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import MMVAEError, call, ptr
+from ._ops import stream as _stream
 from .core import FusedELBOStep, MultimnistState, StepOutputs
 
 # multimnist/utils.py:14-19
@@ -37,10 +37,6 @@ FILL = n_characters + 1
 n_characters += 2
 
 DROP_P = 0.1
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _seed_from_torch() -> int:

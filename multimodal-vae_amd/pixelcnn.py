@@ -31,6 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._lib import MMVAEError, call, ptr
+from ._ops import CONV_WS, WorkspaceCache, empty_nhwc, geometry, nhwc, stream
 
 PixelSample = namedtuple("PixelSample", ["image", "levels", "logits"])
 
@@ -230,15 +231,12 @@ def load_checkpoint(file_path, use_cuda=False):
 
 
 # ------------------------------------------------------------------------------------------------------ the sampler
-_WS: Dict[Tuple, torch.Tensor] = {}
-_WS_MAX = 4          # cached workspaces (the oldest goes first)
+_WS = WorkspaceCache(4)          # cached workspaces (the oldest goes first)
 
 
 def pixelcnn_geometry() -> Tuple[int, int, int]:
     """(samples per workgroup, largest hid_dims, largest side) of the kernel"""
-    a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    call("mmvae_pixelcnn_geometry", ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
-    return a.value, b.value, c.value
+    return geometry("mmvae_pixelcnn_geometry", 3)
 
 
 def _config(model, what="generate") -> Tuple[int, int, int, int, int]:
@@ -284,23 +282,13 @@ def pack_weights(model) -> torch.Tensor:
     flat = torch.cat(parts).contiguous()
     packed = torch.empty(call("mmvae_pixelcnn_packed_elems", *cfg), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        call("mmvae_pixelcnn_pack_weights", *cfg, ptr(flat), flat.numel(), ptr(packed), _stream())
+        call("mmvae_pixelcnn_pack_weights", *cfg, ptr(flat), flat.numel(), ptr(packed), stream())
     return packed
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _workspace(dev, cfg, B, H, W):
     need = call("mmvae_pixelcnn_workspace_bytes", *cfg, B, H, W)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream, cfg, B, H, W)
-    ws = _WS.get(key)
-    if ws is None:
-        while len(_WS) >= _WS_MAX:
-            _WS.pop(next(iter(_WS)))
-        ws = _WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws, need
+    return _WS.get(dev, need, cfg, B, H, W), need
 
 
 @torch.no_grad()
@@ -339,21 +327,19 @@ def generate(model, n_samples=64, height=28, width=28, *, uniforms=None, seed=0,
         image = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
         logits = torch.empty(B, V, C, H, W, dtype=torch.float32, device=dev) if return_logits else None
         call("mmvae_pixelcnn_sample", *cfg, ptr(packed), ptr(ws), need, B, H, W, ptr(uniforms), ptr(g32), int(n_given), ptr(levels),
-             ptr(image), ptr(logits), _stream())
+             ptr(image), ptr(logits), stream())
     return PixelSample(image, levels.long(), logits)
 
 
 # ------------------------------------------------------------------------------------------------------ the training convolution
-_CONV_WS: Dict[Tuple, torch.Tensor] = {}
+_conv_ws, _CONV_WS = CONV_WS.get, CONV_WS.buffers          # the shared scratch (_ops.py); the tests poison _CONV_WS between two runs
 _TAPS_C: Dict[Tuple, ctypes.Array] = {}
 CONV_BACKENDS = ("torch", "hip")
 
 
 def causal_conv_geometry() -> Tuple[int, int, int, int, int, int]:
     """(positions per tile, channels per tile, positions per weight-gradient chunk, most taps, largest |offset|, most channels)"""
-    v = [ctypes.c_int() for _ in range(6)]
-    call("mmvae_causal_conv_geometry", *[ctypes.byref(a) for a in v])
-    return tuple(a.value for a in v)
+    return geometry("mmvae_causal_conv_geometry", 6)
 
 
 def taps_of(module) -> Tuple[Tuple[int, int, int, int], ...]:
@@ -389,23 +375,6 @@ def _taps_c(taps):
     return arr
 
 
-def _conv_ws(dev, need):
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _CONV_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _CONV_WS[key] = torch.empty((max(need, 1 << 20) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _nhwc(t):
-    return t.contiguous(memory_format=torch.channels_last)
-
-
-def _empty_nhwc(B, C, H, W, dev):
-    # (not a permuted view: an in-place ReLU on the op's output has to stay legal)
-    return torch.empty((B, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-
-
 class _CausalConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, taps):
@@ -425,13 +394,13 @@ class _CausalConv(torch.autograd.Function):
             raise MMVAEError("causal_conv2d: a tap is (r, c, dy, dx)")
         (B, Cin, H, W), (Cout, _, kh, kw) = x.shape, weight.shape
         dims = (B, H, W, Cin, Cout, kh, kw)
-        x, w = _nhwc(x.detach()), weight.detach().contiguous()
+        x, w = nhwc(x.detach()), weight.detach().contiguous()
         b = None if bias is None else bias.detach().contiguous()
         need = call("mmvae_causal_conv_workspace_bytes", *dims, len(taps))
         with torch.cuda.device(x.device):
             ws = _conv_ws(x.device, need)
-            y = _empty_nhwc(B, Cout, H, W, x.device)
-            call("mmvae_causal_conv_forward", ptr(x), ptr(w), ptr(b), ptr(y), _taps_c(taps), len(taps), *dims, ptr(ws), ws.numel(), _stream())
+            y = empty_nhwc(B, Cout, H, W, x.device)
+            call("mmvae_causal_conv_forward", ptr(x), ptr(w), ptr(b), ptr(y), _taps_c(taps), len(taps), *dims, ptr(ws), ws.numel(), stream())
         ctx.save_for_backward(x, w)
         ctx.taps, ctx.dims, ctx.has_bias = taps, dims, bias is not None
         return y
@@ -442,13 +411,13 @@ class _CausalConv(torch.autograd.Function):
         x, w = ctx.saved_tensors
         taps, dims = ctx.taps, ctx.dims
         B, H, W, Cin, Cout, kh, kw = dims
-        g = _nhwc(g)
+        g = nhwc(g)
         dx = dw = db = None
         with torch.cuda.device(x.device):
             ws = _conv_ws(x.device, call("mmvae_causal_conv_workspace_bytes", *dims, len(taps)))
-            tail = (_taps_c(taps), len(taps)) + dims + (ptr(ws), ws.numel(), _stream())
+            tail = (_taps_c(taps), len(taps)) + dims + (ptr(ws), ws.numel(), stream())
             if ctx.needs_input_grad[0]:
-                dx = _empty_nhwc(B, Cin, H, W, x.device)
+                dx = empty_nhwc(B, Cin, H, W, x.device)
                 call("mmvae_causal_conv_backward_data", ptr(g), ptr(w), ptr(dx), *tail)
             want_w, want_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
             if want_w or want_b:
@@ -495,9 +464,7 @@ HEADS = ("torch", "hip")
 
 def head_nll_geometry() -> Tuple[int, int, int, int, int, int]:
     """(positions per workgroup, levels per tile, positions per dw / db chunk, largest hid, most levels, most positions)"""
-    v = [ctypes.c_int() for _ in range(6)]
-    call("mmvae_head_nll_geometry", *[ctypes.byref(a) for a in v])
-    return tuple(a.value for a in v)
+    return geometry("mmvae_head_nll_geometry", 6)
 
 
 def head_nll_workspace_bytes(B, C, H, W, hid, V) -> int:
@@ -533,13 +500,13 @@ class _HeadNLL(torch.autograd.Function):
     def forward(ctx, h, weight, bias, target, data_channels):
         dims = _head_dims("head_nll", h, weight, bias, target, data_channels)
         B, C, H, W, hid, V = dims
-        h, w, b, t = _nhwc(h.detach()), weight.detach().contiguous(), bias.detach().contiguous(), target.contiguous()
+        h, w, b, t = nhwc(h.detach()), weight.detach().contiguous(), bias.detach().contiguous(), target.contiguous()
         keep = any(ctx.needs_input_grad[:3])
         with torch.cuda.device(h.device):
             ws = _conv_ws(h.device, head_nll_workspace_bytes(*dims))
             nll = torch.empty(B, C, H, W, dtype=torch.float32, device=h.device)
             lse = torch.empty(B, C, H, W, dtype=torch.float32, device=h.device) if keep else None
-            call("mmvae_head_nll_forward", ptr(h), ptr(w), ptr(b), ptr(t), ptr(nll), ptr(lse), *dims, ptr(ws), ws.numel(), _stream())
+            call("mmvae_head_nll_forward", ptr(h), ptr(w), ptr(b), ptr(t), ptr(nll), ptr(lse), *dims, ptr(ws), ws.numel(), stream())
         if keep:
             ctx.save_for_backward(h, w, b, t, lse)
         ctx.dims = dims
@@ -555,11 +522,11 @@ class _HeadNLL(torch.autograd.Function):
         want_h, want_w, want_b = ctx.needs_input_grad[:3]
         with torch.cuda.device(h.device):
             ws = _conv_ws(h.device, head_nll_workspace_bytes(*dims))
-            dh = _empty_nhwc(B, hid, H, W, h.device) if want_h else None
+            dh = empty_nhwc(B, hid, H, W, h.device) if want_h else None
             dw = torch.empty_like(w) if want_w else None
             db = torch.empty_like(b) if want_b else None
             call("mmvae_head_nll_backward", ptr(h), ptr(w), ptr(b), ptr(t), ptr(lse), ptr(g), ptr(dh), ptr(dw), ptr(db), *dims, ptr(ws),
-                 ws.numel(), _stream())
+                 ws.numel(), stream())
         return dh, dw, db, None, None
 
 

@@ -14,24 +14,20 @@ shape alone: two calls give identical bits.  P is n * n * 4 bytes (400 MB at n =
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Dict, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 
 from ._lib import MMVAEError, call, ptr
-from .multimnist import _stream
+from ._ops import WorkspaceCache, geometry, stream
 
-_WS: Dict[Tuple[int, int, int], torch.Tensor] = {}
-_WS_MAX = 4          # cached workspaces (the oldest goes first)
+_WS = WorkspaceCache(4)          # cached workspaces (the oldest goes first)
 
 
 def tsne_geometry() -> Tuple[int, int, int, int, int]:
     """(rows per sweep workgroup, columns per column tile of the sweep, side of a symmetrisation tile, threads per affinity row,
     largest D) of the kernels; include/mmvae_hip.h states the split rule."""
-    v = [ctypes.c_int() for _ in range(5)]
-    call("mmvae_tsne_geometry", *[ctypes.byref(c) for c in v])
-    return tuple(c.value for c in v)
+    return geometry("mmvae_tsne_geometry", 5)
 
 
 def _device_f32(t, what: str, name: str, cols: Optional[int] = None) -> torch.Tensor:
@@ -49,13 +45,7 @@ def _workspace(dev: torch.device, n: int) -> Tuple[torch.Tensor, int]:
     need = call("mmvae_tsne_workspace_bytes", n)
     if need <= 0:
         raise MMVAEError("tsne: n = %d: need 3..32768 rows" % n)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream, n)
-    ws = _WS.get(key)
-    if ws is None:
-        while len(_WS) >= _WS_MAX:
-            _WS.pop(next(iter(_WS)))
-        ws = _WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws, need
+    return _WS.get(dev, need, n), need
 
 
 @torch.no_grad()
@@ -73,7 +63,7 @@ def joint_probabilities(x: torch.Tensor, perplexity: float = 40.0, return_stats:
         P = torch.empty(n, n, dtype=torch.float32, device=x.device)
         beta = torch.empty(n, dtype=torch.float32, device=x.device)
         out = torch.empty(2, dtype=torch.float32, device=x.device)
-        call("mmvae_tsne_affinities", ptr(x), n, dim, float(perplexity), ptr(P), ptr(beta), ptr(out), ptr(ws), need, _stream())
+        call("mmvae_tsne_affinities", ptr(x), n, dim, float(perplexity), ptr(P), ptr(beta), ptr(out), ptr(ws), need, stream())
     return (P, beta, out) if return_stats else (P, beta)
 
 
@@ -97,7 +87,7 @@ def kl_grad(P: torch.Tensor, y: torch.Tensor, exaggeration: float = 1.0):
         ws, need = _workspace(y.device, n)
         grad = torch.empty_like(y)
         out = torch.empty(3, dtype=torch.float32, device=y.device)
-        call("mmvae_tsne_grad", ptr(P), float(exaggeration), ptr(y), n, ptr(ws), need, ptr(grad), ptr(out), _stream())
+        call("mmvae_tsne_grad", ptr(P), float(exaggeration), ptr(y), n, ptr(ws), need, ptr(grad), ptr(out), stream())
     return out[0].clone(), grad
 
 
@@ -128,7 +118,7 @@ def tsne(x: torch.Tensor, perplexity: float = 40.0, n_iter: int = 300, learning_
         update, gains = torch.zeros_like(y), torch.ones_like(y)
         trace = torch.empty(int(n_iter), dtype=torch.float32, device=x.device)
         call("mmvae_tsne_run", ptr(P), n, ptr(y), ptr(update), ptr(gains), 0, int(n_iter), float(learning_rate), float(early_exaggeration),
-             int(exaggeration_iters), ptr(trace), ptr(ws), need, _stream())
+             int(exaggeration_iters), ptr(trace), ptr(ws), need, stream())
     return (y, trace) if return_trace else y
 
 

@@ -180,7 +180,7 @@ def main():
     y0 = T.initial_embedding(n, 0).to(dev)
 
     from multimodal_vae_amd._lib import ptr
-    from multimodal_vae_amd.multimnist import _stream
+    from multimodal_vae_amd._ops import stream as _stream
     ws = torch.empty(call("mmvae_tsne_workspace_bytes", n), dtype=torch.uint8, device=dev)
 
     def hip_run(n_iter=args.n_iter):
