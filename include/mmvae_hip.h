@@ -703,6 +703,35 @@ int mmvae_tsne_grad(const float* P, float exaggeration, const float* y, int n, v
 int mmvae_tsne_run(const float* P, int n, float* y, float* update, float* gains, int first_iter, int n_iter, float learning_rate,
                    float early_exaggeration, int exaggeration_iters, float* kl_trace, void* workspace, long long ws_bytes, void* stream);
 
+/* MultiMNIST canvases made on the device (multimnist/datasets.py; csrc/multimnist_gen.h, csrc/mmgen_core.h): 0 .. 4 MNIST digits per
+ * 50 x 50 canvas, each resized as Pillow's 8-bit bilinear resample does it (bit for bit) and added at its place; a canvas whose sum
+ * passes 255 anywhere is drawn again.  Integer arithmetic and Philox4x32-10 draws keyed by (seed, global canvas index): canvas
+ * first_canvas + i is the same whatever the call that makes it, and two calls give identical bits.  csrc/mmgen_core.h states the
+ * resize, every draw and the bounds.
+ * digits: device, uint8 [n_digits][28][28], 4-byte aligned; digit_labels: device, int64 [n_digits] (copied into the text as they are);
+ * tables: a DEVICE copy of the mmvae_mmgen_table_bytes() bytes that the host function build_tables fills (needs no GPU): per side
+ * side_min .. side_max and output index (xmin, tap count, max_taps int32 taps), then the 32-bit side thresholds.
+ * geometry: side_min, side_max (the sides the tables hold), max_taps, max_attempts, max_redraws, canvas (50).
+ * generate: flags = 1 fixed | 2 no_resize | 4 no_translate | 8 reverse | 16 scramble | 32 no_repeat (the last three need fixed);
+ *   0 <= min_digits <= max_digits <= 4.  Outputs, device: images_u8 [n][50][50] and / or images_f32 [n][50][50] = u8 / 255 (IEEE
+ *   division; 16-byte aligned), at least one of them; text int64 [n][4], FILL (11) past the digits; optional params int32 [n][4][4] =
+ *   (digit index or -1, side, top, left) per slot, attempts int32 [n] (1-based count of the accepted attempt) and fail_count int32
+ *   [1].  A canvas that used up max_attempts is REPORTED, not retried for ever: zeros, FILL text, params -1 / 0, attempts 0, and
+ *   *fail_count incremented (fail_count is only ever added to: clear it yourself).  The kernel always terminates.
+ * render: the same render path from an explicit params table [n][4][4] (device), no draws and no rejection: the sum is clamped to
+ *   255 and overflow [n] (required) is 1 where that happened, else 0.  A canvas with a slot outside (index < n_digits, side_min <=
+ *   side <= side_max, top, left >= 0, top + side <= 50, left + side <= 50) is not rendered: zeros and overflow = -1.
+ * Pointers, flags and counts are checked before anything is launched (MMVAE_EINVAL); n = 0 launches nothing. */
+int mmvae_mmgen_geometry(int* side_min, int* side_max, int* max_taps, int* max_attempts, int* max_redraws, int* canvas);
+long long mmvae_mmgen_table_bytes(void);
+int mmvae_mmgen_build_tables(void* host_buf);
+int mmvae_mmgen_generate(const unsigned char* digits, const long long* digit_labels, int n_digits, const void* tables, int flags,
+                         int min_digits, int max_digits, unsigned long long seed, unsigned long long first_canvas, int n,
+                         unsigned char* images_u8_or_null, float* images_f32_or_null, long long* text, int* params_or_null,
+                         int* attempts_or_null, int* fail_count_or_null, void* stream);
+int mmvae_mmgen_render(const unsigned char* digits, int n_digits, const void* tables, const int* params, int n,
+                       unsigned char* images_u8_or_null, float* images_f32_or_null, int* overflow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

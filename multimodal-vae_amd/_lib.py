@@ -266,6 +266,11 @@ SIGNATURES["mmvae_conv4s2_workspace_bytes"] = (_LL, [_I] * 5)
 SIGNATURES["mmvae_conv4s2_down"] = (_I, [_P] * 4 + [_I, _I, _F] + [_I] * 5 + [_P, _LL, _P])
 SIGNATURES["mmvae_conv4s2_up"] = (_I, [_P] * 4 + [_I, _I, _F] + [_I] * 5 + [_P, _LL, _P])
 SIGNATURES["mmvae_conv4s2_wgrad"] = (_I, [_P] * 4 + [_I, _F, _P] + [_I] * 5 + [_P, _LL, _P])
+SIGNATURES["mmvae_mmgen_geometry"] = (_I, [C.POINTER(_I)] * 6)
+SIGNATURES["mmvae_mmgen_table_bytes"] = (_LL, [])
+SIGNATURES["mmvae_mmgen_build_tables"] = (_I, [_P])
+SIGNATURES["mmvae_mmgen_generate"] = (_I, [_P, _P, _I, _P, _I, _I, _I, _ULL, _ULL, _I] + [_P] * 7)
+SIGNATURES["mmvae_mmgen_render"] = (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P])
 _STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
 
 _lib = None

@@ -13,6 +13,7 @@
 #include "causal_conv.h"
 #include "head_nll.h"
 #include "conv4s2.h"
+#include "multimnist_gen.h"
 #include <cstring>
 #include <exception>
 
@@ -720,6 +721,53 @@ int mmvae_conv4s2_wgrad(const float* s_side, const float* l_side, const float* y
     MMVAE_REQUIRE(s_side && l_side && dw, "conv4s2_wgrad: null argument");
     MMVAE_REQUIRE(c4_act_ok(act) && !(y_s && y_l), "conv4s2_wgrad: act = %d (need 0..3), and one side at most carries a gradient", act);
     return guarded([&] { return launch_c4_wgrad(s, s_side, l_side, y_s, y_l, act, slope, dw, ws, S(st)); });
+}
+
+// ---- MultiMNIST canvases made on the device (multimnist_gen.h, mmgen_core.h)
+int mmvae_mmgen_geometry(int* side_min, int* side_max, int* max_taps, int* max_attempts, int* max_redraws, int* canvas) {
+    MMVAE_REQUIRE(side_min && side_max && max_taps && max_attempts && max_redraws && canvas, "mmgen_geometry: null argument");
+    *side_min = mmgen::SIDE_MIN; *side_max = mmgen::SIDE_MAX; *max_taps = mmgen::MAX_TAPS; *max_attempts = mmgen::MAX_ATTEMPTS;
+    *max_redraws = mmgen::MAX_REDRAWS; *canvas = mmgen::CANVAS;
+    return MMVAE_OK;
+}
+long long mmvae_mmgen_table_bytes() { return (long long)mmgen::TABLE_WORDS * 4; }
+int mmvae_mmgen_build_tables(void* host_buf) {
+    MMVAE_REQUIRE(host_buf && (reinterpret_cast<uintptr_t>(host_buf) & 3) == 0, "mmgen_build_tables: null or unaligned buffer");
+    const int taps = mmgen::build_tables(static_cast<int32_t*>(host_buf));
+    MMVAE_REQUIRE(taps >= 1 && taps <= mmgen::MAX_TAPS, "mmgen_build_tables: a side in %d..%d needs more than %d taps", (int)mmgen::SIDE_MIN,
+                  (int)mmgen::SIDE_MAX, (int)mmgen::MAX_TAPS);
+    return MMVAE_OK;
+}
+static int mmgen_images_ok(const char* what, const void* digits, int n_digits, const void* tables, int n, const void* u8, const void* f32) {
+    MMVAE_REQUIRE(digits && tables, "%s: null argument", what);
+    MMVAE_REQUIRE(u8 || f32, "%s: neither a uint8 nor a float32 image output", what);
+    MMVAE_REQUIRE(n_digits >= 1, "%s: %d digits, need at least 1", what, n_digits);
+    MMVAE_REQUIRE(n >= 0, "%s: n = %d", what, n);
+    MMVAE_REQUIRE((reinterpret_cast<uintptr_t>(digits) & 3) == 0 && (reinterpret_cast<uintptr_t>(tables) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(u8) & 3) == 0 && aligned16(f32),
+                  "%s: digits, tables and the uint8 images must be 4-byte aligned, the float32 images 16-byte aligned", what);
+    return MMVAE_OK;
+}
+int mmvae_mmgen_generate(const unsigned char* digits, const long long* digit_labels, int n_digits, const void* tables, int flags, int min_digits,
+                         int max_digits, unsigned long long seed, unsigned long long first_canvas, int n, unsigned char* images_u8,
+                         float* images_f32, long long* text, int* params, int* attempts, int* fail_count, void* st) {
+    MMVAE_TRY(mmgen_images_ok("mmgen_generate", digits, n_digits, tables, n, images_u8, images_f32));
+    MMVAE_REQUIRE(digit_labels && text, "mmgen_generate: null argument");
+    MMVAE_REQUIRE(mmgen::flags_ok(flags, min_digits, max_digits),
+                  "mmgen_generate: flags = %d, min_digits = %d, max_digits = %d: need 0 <= min <= max <= %d, known flags, and "
+                  "reverse / scramble / no_repeat only with fixed", flags, min_digits, max_digits, (int)mmgen::MAX_DIGITS);
+    return guarded([&] {
+        return launch_mmgen_generate(digits, digit_labels, n_digits, static_cast<const int32_t*>(tables), flags, min_digits, max_digits, seed,
+                                     first_canvas, n, images_u8, images_f32, text, params, attempts, fail_count, S(st));
+    });
+}
+int mmvae_mmgen_render(const unsigned char* digits, int n_digits, const void* tables, const int* params, int n, unsigned char* images_u8,
+                       float* images_f32, int* overflow, void* st) {
+    MMVAE_TRY(mmgen_images_ok("mmgen_render", digits, n_digits, tables, n, images_u8, images_f32));
+    MMVAE_REQUIRE(params && overflow, "mmgen_render: null argument");
+    return guarded([&] {
+        return launch_mmgen_render(digits, n_digits, static_cast<const int32_t*>(tables), params, n, images_u8, images_f32, overflow, S(st));
+    });
 }
 
 // ---- exact t-SNE with a 2-component embedding (tsne.h)

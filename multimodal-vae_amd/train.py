@@ -7,6 +7,7 @@ checkpoint dict ``:243-251``), with the batch loop body replaced by ONE fused en
 
     python -m multimodal_vae_amd.train --cuda --epochs 2 --synthetic 4096          # no data files needed
     python -m multimodal_vae_amd.train --cuda --data ./data                         # the reference's processed/*.pt
+    python -m multimodal_vae_amd.train --cuda --generate --mnist_train A.pt --mnist_test B.pt   # fresh canvases made on the device
 
 Differences that are deliberate: the loader is ``data.DeviceBatcher`` (uint8 H2D + on-device ToTensor, fixed batch
 size: the ragged last batch of an epoch is dropped because a fused plan is built per batch size); loss values are read
@@ -91,6 +92,14 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--out', type=str, default='./trained_models', help='checkpoint folder (reference: ./trained_models)')
     parser.add_argument('--results', type=str, default='', help='folder for per-epoch sample dumps (off when empty)')
     parser.add_argument('--seed', type=int, default=1234)
+    # fresh canvases made on the device at every step (multimnist_gen.MultiMNISTStream) instead of a dataset file
+    parser.add_argument('--generate', action='store_true', default=False,
+                        help='train on canvases generated on the device from MNIST digits: --mnist_train / --mnist_test, or synthetic digits with --synthetic N')
+    parser.add_argument('--mnist_train', type=str, default='', help='--generate: MNIST training split, a .pt file holding (uint8 (N,28,28), int64 (N,))')
+    parser.add_argument('--mnist_test', type=str, default='', help='--generate: MNIST test split, same layout')
+    parser.add_argument('--epoch_size', type=int, default=60000, metavar='N', help='--generate: canvases per training epoch (default: 60000)')
+    parser.add_argument('--min_digits', type=int, default=0, help='--generate: minimum number of digits per canvas (datasets.py: 0)')
+    parser.add_argument('--max_digits', type=int, default=2, help='--generate: maximum number of digits per canvas (datasets.py: 2; at most 4)')
     return parser
 
 
@@ -120,7 +129,26 @@ def main(argv=None) -> dict:
         global print
         print = lambda *a, **k: None     # noqa: E731  (rank 0 reports)
     torch.manual_seed(args.seed)
-    if args.synthetic > 0:
+    gen_stream = None
+    if args.generate:
+        # training canvases are made on the device, one kernel in front of every step and never the same twice; the test set is
+        # generated once, from the test digits, and goes through the usual loader
+        from . import multimnist_gen as G
+        if args.synthetic > 0:
+            mn_tr, mn_te = D.synthetic_mnist(args.synthetic, seed=args.seed), D.synthetic_mnist(args.synthetic, seed=args.seed + 1)
+        elif args.mnist_train and args.mnist_test:
+            from .make_multimnist import load_mnist_pt
+            mn_tr, mn_te = load_mnist_pt(args.mnist_train), load_mnist_pt(args.mnist_test)
+        else:
+            raise SystemExit("--generate needs --mnist_train FILE.pt and --mnist_test FILE.pt, or --synthetic N for synthetic digits")
+        gen_stream = G.MultiMNISTStream(mn_tr[0], mn_tr[1], args.batch_size, dev, epoch_size=args.epoch_size // world,
+                                        seed=dp.rank_seed(args.seed, rank), min_digits=args.min_digits, max_digits=args.max_digits)
+        n_test = max(args.batch_size * world, min(10000, args.epoch_size // 6))
+        te_x, te_t = G.generate(mn_te[0].to(dev).contiguous(), mn_te[1].to(dev, torch.int64).contiguous(), n_test, seed=args.seed + 7,
+                                min_digits=args.min_digits, max_digits=args.max_digits)
+        te_x, te_t = te_x.cpu(), te_t.cpu()
+        tr_x, tr_t = te_x[:0], te_t[:0]          # (nothing is loaded for training)
+    elif args.synthetic > 0:
         n_test = max(args.batch_size, args.synthetic // 6)
         tr_x, tr_y = D.synthetic_multimnist(args.synthetic, seed=args.seed)
         te_x, te_y = D.synthetic_multimnist(n_test, seed=args.seed + 1)
@@ -133,7 +161,8 @@ def main(argv=None) -> dict:
         n_tr, n_te = len(tr_x) // world * world, len(te_x) // world * world
         tr_x, tr_t, te_x, te_t = (t.contiguous() for t in (tr_x[rank:n_tr:world], tr_t[rank:n_tr:world],
                                                            te_x[rank:n_te:world], te_t[rank:n_te:world]))
-    train_loader = D.DeviceBatcher(tr_x, tr_t, args.batch_size, dev, shuffle=True, seed=dp.rank_seed(args.seed, rank))
+    train_loader = gen_stream if gen_stream is not None else \
+        D.DeviceBatcher(tr_x, tr_t, args.batch_size, dev, shuffle=True, seed=dp.rank_seed(args.seed, rank))
     test_loader = D.DeviceBatcher(te_x, te_t, args.batch_size, dev, shuffle=True, seed=dp.rank_seed(args.seed + 7, rank))
 
     if len(train_loader) == 0 or len(test_loader) == 0:
