@@ -411,6 +411,28 @@ int mmvae_coco_text_decoder_fwd(mmvae_coco_t*, void* ws, size_t ws_bytes, const 
                                 const uint8_t* keep, int training, float* sentence, void* stream);  /* coco/model.py:266-288 */
 int mmvae_coco_text_decoder_bwd(mmvae_coco_t*, void* ws, size_t ws_bytes, const float* z, const float* sos,
                                 const uint8_t* keep, const float* sentence, const float* d_sentence, float* dz, void* stream);
+/* Importance-weighted evaluation, the COCO scoring step between mmvae_iw_particles and mmvae_iw_accumulate(T = 1, V = 1) on the
+ * B*K particle rows z [B][K][n_latents] (row b*K + k: example b; B*K at most the plan's batch):
+ *   * the eval-mode image decoder body (the bf16 launches of mmvae_coco_image_decoder_fwd up to the raw output of
+ *     hallucinate.6), then ONE forward-only kernel per row: BatchNorm (running statistics) + Swish in registers, the last
+ *     ConvTranspose2d(64, 3, 4, 2, 1) on the matrix cores, loglik_x [B*K] = sum over the 3x32x32 logits l of x*l - softplus(l)
+ *     (not clamped like the training BCE) against image [B][3][32][32], summed in a fixed order (equal inputs: bit-equal sums);
+ *   * the eval-mode caption decoder (the launches of mmvae_coco_text_decoder_fwd: own-output feedback, no dropout) into a sentence
+ *     buffer [B*K][steps][300] of the workspace, then sse_y [B*K] = sum over (t, e) of (sentence - text[b])^2 against text
+ *     [B][steps][300] (16-byte aligned), fp32 differences folded in a fixed order.  The caller turns it into a log-likelihood:
+ *     log p(y|z) = -sse_y / (2 sigma^2) - (steps * 300 / 2) log(2 pi sigma^2), the model under which the training MSE is the NLL.
+ * Nothing of the plan's parameters, BatchNorm buffers or gradients is modified.  Workspace: mmvae_coco_iw_workspace_bytes. */
+size_t mmvae_coco_iw_workspace_bytes(const mmvae_coco_t*);
+int mmvae_coco_iw_score(mmvae_coco_t*, void* ws, size_t ws_bytes, const float* z, const float* image, const float* text,
+                        const float* sos, int B, int K, float* loglik_x, float* sse_y, void* stream);
+/* Test hooks of the two scoring kernels; neither needs a plan.
+ * mmvae_coco_iw_tail: q3_bf16 [B*K][16][16][64] (NHWC bf16, the raw output of hallucinate.6), affine [64][2] (scale, shift) per
+ * channel, act one of 0 none / 1 Swish / 2 ReLU (the scoring call passes Swish), w (64,3,4,4) fp32 (rounded to bf16 by the
+ * kernel), image [B][3][32][32]; loglik [B*K]; logits_or_null [B*K][3][32][32] fp32 receives the pre-sigmoid logits.
+ * mmvae_coco_iw_text_sse: sentence [B*K][steps][300], text [B][steps][300] (both 16-byte aligned) -> sse [B*K]. */
+int mmvae_coco_iw_tail(const void* q3_bf16, const float* affine, int act, const float* w, const float* image, int B, int K,
+                       float* loglik, float* logits_or_null, void* stream);
+int mmvae_coco_iw_text_sse(const float* sentence, const float* text, int B, int K, int steps, float* sse, void* stream);
 
 /* ---------------------------------------------------------------- dataset-independent ops */
 /* ProductOfExperts.forward (multimnist/model.py:355-360) over M stacked experts of n scalars each */

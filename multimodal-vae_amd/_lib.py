@@ -232,6 +232,10 @@ SIGNATURES["mmvae_coco_text_encoder_fwd"] = (_I, [_P, _P, _SZ, _P, _P, _P])
 SIGNATURES["mmvae_coco_text_encoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P])
 SIGNATURES["mmvae_coco_text_decoder_fwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _I, _P, _P])
 SIGNATURES["mmvae_coco_text_decoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P])
+SIGNATURES["mmvae_coco_iw_workspace_bytes"] = (_SZ, [_P])
+SIGNATURES["mmvae_coco_iw_score"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P, _I, _I, _P, _P, _P])
+SIGNATURES["mmvae_coco_iw_tail"] = (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P])
+SIGNATURES["mmvae_coco_iw_text_sse"] = (_I, [_P, _P, _I, _I, _I, _P, _P])
 SIGNATURES["mmvae_nn_words_workspace_bytes"] = (_LL, [_I, _LL])
 SIGNATURES["mmvae_nn_words_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)])
 SIGNATURES["mmvae_nn_words_norms"] = (_I, [_P, _LL, _I, _P, _P])

@@ -331,6 +331,25 @@ int mmvae_coco_text_decoder_fwd(mmvae_coco_t* p, void* ws, size_t wsb, const flo
 int mmvae_coco_text_decoder_bwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, const float* sentence, const float* d_sentence, float* dz, void* st) {
     return guarded([&] { return coco_text_decoder_bwd(p, ws, wsb, z, sos, keep, sentence, d_sentence, dz, S(st)); });
 }
+size_t mmvae_coco_iw_workspace_bytes(const mmvae_coco_t* p) { return p ? coco_iw_workspace_bytes(p) : 0; }
+int mmvae_coco_iw_score(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* image, const float* text, const float* sos,
+                        int B, int K, float* loglik_x, float* sse_y, void* st) {
+    return guarded([&] { return coco_iw_score(p, ws, wsb, z, image, text, sos, B, K, loglik_x, sse_y, S(st)); });
+}
+int mmvae_coco_iw_tail(const void* q3, const float* affine, int act, const float* w, const float* image, int B, int K, float* loglik,
+                       float* logits, void* st) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(affine != nullptr, "mmvae_coco_iw_tail: null affine table");
+        MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= 0x3FFFFFFF, "mmvae_coco_iw_tail: B=%d K=%d out of range", B, K);
+        CocoIwTailArgs a{};
+        a.q3 = static_cast<const bf16*>(q3); a.affine = reinterpret_cast<const float2*>(affine); a.act = act; a.w = w; a.image = image;
+        a.rows = B * K; a.K = K; a.loglik = loglik; a.logits = logits;
+        return launch_coco_iw_tail(a, S(st));
+    });
+}
+int mmvae_coco_iw_text_sse(const float* sentence, const float* text, int B, int K, int steps, float* sse, void* st) {
+    return guarded([&] { return launch_coco_iw_text_sse(sentence, text, B, K, steps, sse, S(st)); });
+}
 
 
 int mmvae_poe_fwd(const float* mu, const float* lv, int M, int n, float* omu, float* olv, void* s) { return launch_poe_fwd(mu, lv, M, n, omu, olv, S(s)); }

@@ -20,3 +20,24 @@ int coco_text_encoder_fwd(CocoPlan*, void* ws, size_t wsb, const float* text, fl
 int coco_text_encoder_bwd(CocoPlan*, void* ws, size_t wsb, const float* text, const float* d_out, hipStream_t);
 int coco_text_decoder_fwd(CocoPlan*, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, int training, float* sentence, hipStream_t);
 int coco_text_decoder_bwd(CocoPlan*, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, const float* sentence, const float* d_sentence, float* dz, hipStream_t);
+// importance-weighted evaluation (include/mmvae_hip.h: mmvae_coco_iw_*): coco_iw_score (coco.hip) runs the eval-mode image
+// decoder body, the eval-mode caption decoder and the two scoring kernels of coco_iw.hip
+int coco_iw_score(CocoPlan*, void* ws, size_t wsb, const float* z, const float* image, const float* text, const float* sos, int B, int K,
+                  float* loglik_x, float* sse_y, hipStream_t);
+size_t coco_iw_workspace_bytes(const CocoPlan*);
+// forward-only scoring tail: raw bf16 NHWC [rows][16][16][64] -> BatchNorm affine + act -> ConvTranspose2d(64, 3, 4, 2, 1) -> one
+// log p(x|z) per row against image [rows / K].  The affine is either the table `affine` [64] (scale, shift) or, when that is
+// null, made from gamma / beta / running mean / running variance [64] each.
+struct CocoIwTailArgs {
+    const bf16* q3; const float2* affine;
+    const float *gamma, *beta, *rmean, *rvar; float eps;
+    int act;
+    const float* w;                  // (64, 3, 4, 4) fp32
+    const float* image;              // [rows / K][3][32][32]
+    int rows, K;
+    float* loglik;                   // [rows]
+    float* logits;                   // [rows][3][32][32] or null
+};
+int launch_coco_iw_tail(const CocoIwTailArgs&, hipStream_t);
+// sse[row] = sum over (t, e) of (sentence[row][t][e] - text[row / K][t][e])^2 for the B*K rows; both 16-byte aligned
+int launch_coco_iw_text_sse(const float* sentence, const float* text, int B, int K, int steps, float* sse, hipStream_t);

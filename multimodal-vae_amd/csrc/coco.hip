@@ -111,6 +111,10 @@ void carve(CocoPlan& P, Workspace& ws) {
     const size_t B = P.B, D = P.D, B3 = (size_t)P.carve_passes * B, B2 = (size_t)(P.carve_passes < 2 ? P.carve_passes : 2) * B, T = P.T;
     const int SS = MMVAE_STAT_SLOTS;
     const int ec[3] = {128, 256, 512}, dc[3] = {256, 128, 64};
+    // carve_iw (coco_iw_score): only what the eval-mode forward of the two decoders touches gets room; everything wrapped in
+    // bk() -- the encoders' buffers, what a backward pass reads or writes, the bf16 caption kernels' operands -- is empty
+    const bool iw = P.carve_iw;
+    auto bk = [iw](size_t n) { return iw ? (size_t)0 : n; };
     char* z0 = ws.take<char>(0);
     for (int i = 0; i < 3; ++i) { w.st_e[i] = ws.take<float2>(SS * ec[i]); w.red_e[i] = ws.take<float2>(SS * ec[i]); }
     for (int i = 0; i < 3; ++i) { w.st_d[i] = ws.take<float2>(3 * SS * dc[i]); w.red_d[i] = ws.take<float2>(3 * SS * dc[i]); }
@@ -123,29 +127,29 @@ void carve(CocoPlan& P, Workspace& ws) {
     w.dz_txt = ws.take<float>(B3 * D);
     for (int i = 0; i < 3; ++i) { w.aff_e[i] = ws.take<float2>(ec[i]); w.mr_e[i] = ws.take<float2>(ec[i]); }
     for (int i = 0; i < 3; ++i) { w.aff_d[i] = ws.take<float2>(3 * dc[i]); w.mr_d[i] = ws.take<float2>(3 * dc[i]); }
-    w.patches1 = ws.take<bf16>(B * 256 * 48);
-    w.r1 = ws.take<bf16>(B * 256 * 64); w.r2 = ws.take<bf16>(B * 64 * 128); w.r3 = ws.take<bf16>(B * 16 * 256); w.r4 = ws.take<bf16>(B * FEAT);
-    w.a1 = ws.take<bf16>(B * 256 * 64); w.a2 = ws.take<bf16>(B * 64 * 128); w.a3 = ws.take<bf16>(B * 16 * 256); w.a4 = ws.take<bf16>(B * FEAT);
-    w.y1 = ws.take<bf16>(B2 * HID1); w.ay1 = ws.take<bf16>(B2 * HID1); w.y2 = ws.take<bf16>(B2 * HID2); w.ay2 = ws.take<bf16>(B2 * HID2);
-    w.encout = ws.take<float>(B2 * 2 * D); w.m1 = ws.take<uint8_t>(B2 * HID1); w.m2 = ws.take<uint8_t>(B2 * HID2);
-    w.gkeep = ws.take<uint8_t>(T * B3 * COCO_H);
+    w.patches1 = ws.take<bf16>(bk(B * 256 * 48));
+    w.r1 = ws.take<bf16>(bk(B * 256 * 64)); w.r2 = ws.take<bf16>(bk(B * 64 * 128)); w.r3 = ws.take<bf16>(bk(B * 16 * 256)); w.r4 = ws.take<bf16>(bk(B * FEAT));
+    w.a1 = ws.take<bf16>(bk(B * 256 * 64)); w.a2 = ws.take<bf16>(bk(B * 64 * 128)); w.a3 = ws.take<bf16>(bk(B * 16 * 256)); w.a4 = ws.take<bf16>(bk(B * FEAT));
+    w.y1 = ws.take<bf16>(bk(B2 * HID1)); w.ay1 = ws.take<bf16>(bk(B2 * HID1)); w.y2 = ws.take<bf16>(bk(B2 * HID2)); w.ay2 = ws.take<bf16>(bk(B2 * HID2));
+    w.encout = ws.take<float>(bk(B2 * 2 * D)); w.m1 = ws.take<uint8_t>(bk(B2 * HID1)); w.m2 = ws.take<uint8_t>(bk(B2 * HID2));
+    w.gkeep = ws.take<uint8_t>(bk(T * B3 * COCO_H));
     w.eps = ws.take<float>(B3 * D); w.mu = ws.take<float>(B3 * D); w.logvar = ws.take<float>(B3 * D);
     w.z_f32 = ws.take<float>(B3 * D); w.z_bf = ws.take<bf16>(B3 * P.ldz);
     w.u = ws.take<bf16>(B3 * FEAT); w.au = ws.take<bf16>(B3 * FEAT);
     w.q1 = ws.take<bf16>(B3 * 16 * 256); w.q2 = ws.take<bf16>(B3 * 64 * 128); w.q3 = ws.take<bf16>(B3 * 256 * 64);
-    w.aq1 = ws.take<bf16>(B3 * 16 * 256); w.aq2 = ws.take<bf16>(B3 * 64 * 128); w.aq3 = ws.take<bf16>(B3 * 256 * 64);
-    w.dlogit = ws.take<float>(B3 * NPIX);
-    w.patches4 = ws.take<bf16>(B3 * 256 * 48);
-    w.d3 = ws.take<bf16>(B3 * 256 * 64); w.d2 = ws.take<bf16>(B3 * 64 * 128); w.d1 = ws.take<bf16>(B3 * 16 * 256);
-    w.du = ws.take<bf16>(B3 * FEAT);
-    w.d_encout = ws.take<bf16>(B2 * 2 * D); w.dy2 = ws.take<bf16>(B2 * HID2); w.dy1 = ws.take<bf16>(B2 * HID1);
-    w.db4 = ws.take<bf16>(B2 * FEAT); w.dr4 = ws.take<bf16>(B * FEAT);
-    w.d3e = ws.take<bf16>(B * 16 * 256); w.d2e = ws.take<bf16>(B * 64 * 128); w.d1e = ws.take<bf16>(B * 256 * 64);
-    w.tmp_f32 = ws.take<float>(B3 * NPIX);
+    w.aq1 = ws.take<bf16>(B3 * 16 * 256); w.aq2 = ws.take<bf16>(B3 * 64 * 128); w.aq3 = ws.take<bf16>(bk(B3 * 256 * 64));   // (the scoring tail activates q3 itself)
+    w.dlogit = ws.take<float>(bk(B3 * NPIX));
+    w.patches4 = ws.take<bf16>(bk(B3 * 256 * 48));
+    w.d3 = ws.take<bf16>(bk(B3 * 256 * 64)); w.d2 = ws.take<bf16>(bk(B3 * 64 * 128)); w.d1 = ws.take<bf16>(bk(B3 * 16 * 256));
+    w.du = ws.take<bf16>(bk(B3 * FEAT));
+    w.d_encout = ws.take<bf16>(bk(B2 * 2 * D)); w.dy2 = ws.take<bf16>(bk(B2 * HID2)); w.dy1 = ws.take<bf16>(bk(B2 * HID1));
+    w.db4 = ws.take<bf16>(bk(B2 * FEAT)); w.dr4 = ws.take<bf16>(bk(B * FEAT));
+    w.d3e = ws.take<bf16>(bk(B * 16 * 256)); w.d2e = ws.take<bf16>(bk(B * 64 * 128)); w.d1e = ws.take<bf16>(bk(B * 256 * 64));
+    w.tmp_f32 = ws.take<float>(bk(B3 * NPIX));
     P.sk_floats = (size_t)256 * 128 * 128;
     P.sk_buf = ws.take<float>(P.sk_floats);
     // weight-gradient partial-tile slabs (written and read once per step, never zeroed): gemm.h WgradSlabCtx
-    w.slab_floats = (size_t)(P.carve_passes >= 3 ? 48 : 16) << 20;
+    w.slab_floats = bk((size_t)(P.carve_passes >= 3 ? 48 : 16) << 20);
     w.slab = ws.take<float>(w.slab_floats);
     coco_text_carve(P, ws);
 }
@@ -282,6 +286,8 @@ int enc_bwd(CocoPlan& P, const bf16* d_out, int variants, const uint8_t* m1, con
 }
 
 // ================================================================== image decoder (coco/model.py:211-216)
+// last == nullptr (coco_iw_score): the body only -- it ends with the raw output of hallucinate.6 in q3, whose BatchNorm + Swish
+// belong to the caller's own tail
 int dec_fwd(CocoPlan& P, int groups, int training, ConvTLastFwdArgs* last, hipStream_t s) {
     CocoPlan::W& w = P.w;
     const int B = P.B, rows = groups * B;
@@ -301,8 +307,10 @@ int dec_fwd(CocoPlan& P, int groups, int training, ConvTLastFwdArgs* last, hipSt
         g.colstats = training ? w.st_d[l] : nullptr;
         MMVAE_TRY(launch_gemm_gather(g, s));
         const int rpg = B * L.g.OH * L.g.OW;
+        if (l == 2 && !last) continue;
         MMVAE_TRY(bn_act(P, P.bn[L.bn], q[l + 1], aq[l + 1], groups * rpg, rpg, groups, w.st_d[l], 1, w.aff_d[l], w.mr_d[l], training, s));
     }
+    if (!last) return MMVAE_OK;
     ConvTLastFwdArgs x = *last;
     x.act = w.aq3; x.w = P.buf.params + P.convT[3].w_off; x.G = groups; x.B = B; x.IH = 16; x.IW = 16; x.Cin = 64; x.Cout = 3;
     return launch_convt_last_fwd(x, s);
@@ -374,6 +382,14 @@ int use_ws(CocoPlan* P, void* ws, size_t bytes, bool module = true) {
     P->cl_alarm_f = P->cl_alarm_b = nullptr;
     return MMVAE_OK;
 }
+// coco_iw_score: its own (smaller) carve, with every check and reset of use_ws against ws_bytes_iw
+int use_ws_iw(CocoPlan* P, void* ws, size_t bytes) {
+    const size_t module_bytes = P->ws_bytes_module;
+    P->ws_bytes_module = P->ws_bytes_iw; P->carve_iw = true;
+    const int rc = use_ws(P, ws, bytes);
+    P->ws_bytes_module = module_bytes; P->carve_iw = false;
+    return rc;
+}
 int zero_ws(CocoPlan& P, hipStream_t s) { return launch_fill_zero(P.w.zero_begin, P.w.zero_bytes, s); }
 
 }  // namespace
@@ -387,6 +403,13 @@ CocoPlan* coco_create(int D, int B, int T) {
     P->D = D; P->B = B; P->T = T;
     build(*P);
     plan_size_workspaces(*P, carve);
+    {   // the scoring call's workspace: one pass, forward buffers of the two decoders only
+        P->carve_iw = true; P->carve_passes = 1;
+        Workspace wi(nullptr, 0);
+        carve(*P, wi);
+        P->ws_bytes_iw = wi.used();
+        P->carve_iw = false; P->carve_passes = 3;
+    }
     return P;
 }
 void coco_destroy(CocoPlan* P) { delete P; }
@@ -564,4 +587,41 @@ int coco_text_decoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* z, con
     MMVAE_TRY(launch_fill_zero(w.td_dh1, (size_t)P->B * COCO_H * sizeof(float), s));
     hipMemcpyAsync(w.td_dw, d_sentence, n * sizeof(float), hipMemcpyDeviceToDevice, s);
     return coco_text_dec_bwd(*P, z, 1, sos, keep, sentence, w.td_dw, dz, s, s);
+}
+
+// ---------------------------------------------------------------- importance-weighted evaluation (iw.h, coco_iw.hip)
+// Eval-mode decoders on the B*K particle rows z [B][K][D].  Image: the bf16 decoder body of coco_image_decoder_fwd up to the raw
+// output of hallucinate.6 (no stand-alone BatchNorm + Swish pass over it), then the forward-only scoring tail -- one log p(x|z)
+// per row against the row's own example.  Caption: the launches of coco_text_decoder_fwd in eval mode (own-output feedback, no
+// dropout, nothing saved for a backward pass) into the workspace's sentence buffer, then one squared-error sum per row.  No
+// backward activation is kept; parameters, BatchNorm buffers and gradients are only read.
+size_t coco_iw_workspace_bytes(const CocoPlan* P) { return P->ws_bytes_iw; }
+int coco_iw_score(CocoPlan* P, void* ws, size_t wsb, const float* z, const float* image, const float* text, const float* sos, int B, int K,
+                  float* loglik_x, float* sse_y, hipStream_t s) {
+    MMVAE_REQUIRE(P && z && image && text && sos && loglik_x && sse_y, "mmvae_coco_iw_score: null argument");
+    MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B,
+                  "mmvae_coco_iw_score: %d examples x %d particles exceed the plan's %d rows", B, K, P->B);
+    MMVAE_TRY(use_ws_iw(P, ws, wsb));
+    CocoPlan::W& w = P->w;
+    const int rows = B * K;
+    MMVAE_TRY(zero_ws(*P, s));
+    hipLaunchKernelGGL(cast_z_kernel, dim3(ceil_div(rows * P->ldz, 256)), dim3(256), 0, s, z, rows, P->D, w.z_bf, P->ldz);
+    MMVAE_TRY(mmvae_check_launch("cast_z"));
+    const float* zt = z;
+    if (rows < P->B) {    // the decoders run the plan's rows: the ones past B*K are defined (zero) and never scored
+        MMVAE_TRY(launch_fill_zero(w.z_bf + (size_t)rows * P->ldz, (size_t)(P->B - rows) * P->ldz * sizeof(bf16), s));
+        MMVAE_TRY(launch_fill_zero(w.z_f32, (size_t)P->B * P->D * sizeof(float), s));
+        MMVAE_REQUIRE(hipMemcpyAsync(w.z_f32, z, (size_t)rows * P->D * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess,
+                      "mmvae_coco_iw_score: copy of the particles failed");
+        zt = w.z_f32;
+    }
+    MMVAE_TRY(dec_fwd(*P, 1, 0, nullptr, s));
+    const BnL& b = P->bn[P->convT[2].bn];
+    CocoIwTailArgs t{};
+    t.q3 = w.q3; t.gamma = P->buf.params + b.w_off; t.beta = P->buf.params + b.b_off;
+    t.rmean = P->buf.bn_stats + b.stat_off; t.rvar = t.rmean + b.C; t.eps = BN_EPS;
+    t.act = ACT_SWISH; t.w = P->buf.params + P->convT[3].w_off; t.image = image; t.rows = rows; t.K = K; t.loglik = loglik_x;
+    MMVAE_TRY(launch_coco_iw_tail(t, s));
+    MMVAE_TRY(coco_text_dec_fwd(*P, zt, 1, sos, nullptr, 0, w.td_recon, s));
+    return launch_coco_iw_text_sse(w.td_recon, text, B, K, P->T, sse_y, s);
 }

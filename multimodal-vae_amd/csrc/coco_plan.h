@@ -101,6 +101,8 @@ struct CocoPlan : PlanBase {
     // caption half: offsets into the flat fp32 parameter buffer (the GEMMs read the weights where they are)
     CocoGru te_f, te_r, td0, td1;
     long long te_h2p_w, te_h2p_b, td_z2h_w, td_z2h_b, td_h2o_w, td_h2o_b;
+    // coco_iw_score's workspace (coco.hip carve / coco_text_carve with carve_iw): one pass, forward buffers of the decoders only
+    bool carve_iw = false; size_t ws_bytes_iw = 0;
     // bf16 persistent caption decoder: packed weights (forward and transposed forms) and packed-gradient descriptors
     bool text_bf16 = true;
     const unsigned *cl_alarm_f = nullptr, *cl_alarm_b = nullptr;   // timeout words of this step's cluster launches (null: not used)

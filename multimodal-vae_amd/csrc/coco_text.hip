@@ -367,19 +367,23 @@ void coco_text_build(CocoPlan& P) {
 void coco_text_carve(CocoPlan& P, Workspace& ws) {
     CocoPlan::W& w = P.w;
     const size_t B = P.B, R = (size_t)P.carve_passes * B, T = P.T, D = P.D;
-    w.te_gi = ws.take<float>(B * T * G); w.te_gh = ws.take<float>(B * G); w.te_h = ws.take<float>(T * B * H);
-    w.te_sav = ws.take<float>(T * B * 4 * H); w.te_gi_r = ws.take<float>(B * G); w.te_sav_r = ws.take<float>(B * 4 * H);
-    w.te_hb = ws.take<float>(B * H); w.te_sum = ws.take<float>(B * H); w.txtout = ws.take<float>(B * 2 * D);
-    w.d_txtout = ws.take<float>(B * 2 * D); w.te_dsum = ws.take<float>(B * H); w.te_dh = ws.take<float>(B * H);
-    w.te_dgi = ws.take<float>(B * T * G); w.te_dgh = ws.take<float>(T * B * G); w.te_dgi_r = ws.take<float>(B * G);
-    w.td_zi0 = ws.take<float>(R * G); w.td_zo = ws.take<float>(R * E); w.td_gi = ws.take<float>(R * G); w.td_gh = ws.take<float>(R * G);
-    w.td_h0 = ws.take<float>((T + 1) * R * H); w.td_h1 = ws.take<float>((T + 1) * R * H); w.td_mid = ws.take<float>(T * R * H);
-    w.td_sav0 = ws.take<float>(T * R * 4 * H); w.td_sav1 = ws.take<float>(T * R * 4 * H); w.td_recon = ws.take<float>(R * T * E);
-    w.td_dw = ws.take<float>(R * T * E);
-    w.td_dgi0 = ws.take<float>(T * R * G); w.td_dgh0 = ws.take<float>(T * R * G);
-    w.td_dgi1 = ws.take<float>(T * R * G); w.td_dgh1 = ws.take<float>(T * R * G);
-    w.td_dmid = ws.take<float>(R * H); w.td_dzi0 = ws.take<float>(R * G); w.td_dwsum = ws.take<float>(R * E); w.td_dhinit = ws.take<float>(R * H);
-    if (P.text_bf16) {
+    // carve_iw (coco_iw_score, coco.hip carve): only the eval-mode fp32 decoder forward gets room -- the z terms, the two hidden
+    // state histories and the sentence; the encoder's buffers, the saved gates, every gradient and the bf16 kernels' operands are empty
+    const bool iw = P.carve_iw;
+    auto bk = [iw](size_t n) { return iw ? (size_t)0 : n; };
+    w.te_gi = ws.take<float>(bk(B * T * G)); w.te_gh = ws.take<float>(bk(B * G)); w.te_h = ws.take<float>(bk(T * B * H));
+    w.te_sav = ws.take<float>(bk(T * B * 4 * H)); w.te_gi_r = ws.take<float>(bk(B * G)); w.te_sav_r = ws.take<float>(bk(B * 4 * H));
+    w.te_hb = ws.take<float>(bk(B * H)); w.te_sum = ws.take<float>(bk(B * H)); w.txtout = ws.take<float>(bk(B * 2 * D));
+    w.d_txtout = ws.take<float>(bk(B * 2 * D)); w.te_dsum = ws.take<float>(bk(B * H)); w.te_dh = ws.take<float>(bk(B * H));
+    w.te_dgi = ws.take<float>(bk(B * T * G)); w.te_dgh = ws.take<float>(bk(T * B * G)); w.te_dgi_r = ws.take<float>(bk(B * G));
+    w.td_zi0 = ws.take<float>(R * G); w.td_zo = ws.take<float>(R * E); w.td_gi = ws.take<float>(bk(R * G)); w.td_gh = ws.take<float>(bk(R * G));
+    w.td_h0 = ws.take<float>((T + 1) * R * H); w.td_h1 = ws.take<float>((T + 1) * R * H); w.td_mid = ws.take<float>(bk(T * R * H));
+    w.td_sav0 = ws.take<float>(bk(T * R * 4 * H)); w.td_sav1 = ws.take<float>(bk(T * R * 4 * H)); w.td_recon = ws.take<float>(R * T * E);
+    w.td_dw = ws.take<float>(bk(R * T * E));
+    w.td_dgi0 = ws.take<float>(bk(T * R * G)); w.td_dgh0 = ws.take<float>(bk(T * R * G));
+    w.td_dgi1 = ws.take<float>(bk(T * R * G)); w.td_dgh1 = ws.take<float>(bk(T * R * G));
+    w.td_dmid = ws.take<float>(bk(R * H)); w.td_dzi0 = ws.take<float>(bk(R * G)); w.td_dwsum = ws.take<float>(bk(R * E)); w.td_dhinit = ws.take<float>(bk(R * H));
+    if (P.text_bf16 && !iw) {
         w.tb_x = ws.take<bf16>(T * R * CTB_XP); w.tb_h0 = ws.take<bf16>((T + 1) * R * CTB_HP); w.tb_mid = ws.take<bf16>(T * R * CTB_HP);
         w.tb_h1 = ws.take<bf16>((T + 1) * R * CTB_HP); w.tb_dout = ws.take<bf16>(T * R * CTB_EP);
         w.tb_dgi0 = ws.take<bf16>(T * R * CTB_GP); w.tb_dgh0 = ws.take<bf16>(T * R * CTB_GP);
@@ -556,6 +560,10 @@ int coco_text_enc_bwd(CocoPlan& P, const float* text, const float* d_out, hipStr
 }
 
 // ================================================================== caption decoder (coco/model.py:266-312)
+// coco_iw_score calls this with keep == nullptr, save == 0, bf16_path == false on the SCORING carve (coco_text_carve with
+// carve_iw), in which only td_zi0, td_zo, td_h0, td_h1 and td_recon have room: on that path (the stepwise fp32 form below) nothing
+// else of W may be touched -- td_mid, td_sav0/1, td_gi/td_gh and every tb_* buffer are zero-sized there.  Whoever makes the
+// eval-mode fp32 path use another buffer gives it room in the carve_iw branch of coco_text_carve too.
 int coco_text_dec_fwd(CocoPlan& P, const float* z, int groups, const float* sos, const uint8_t* keep, int save, float* sentence,
                       hipStream_t s, bool bf16_path, const CocoMseFuse* mse) {
     P.mse_fused = false;

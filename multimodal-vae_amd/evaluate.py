@@ -213,6 +213,7 @@ test_celeba.__test__ = False              # not a pytest test
 IW_ROWS = 4096          # particle rows (examples x particles) per scoring call: the plan and workspace of one chunk
 IW_ROWS_MNIST = 65536   # ... of the fused MNIST scorer: no plan or workspace per chunk, 32 rows per workgroup (2048 workgroups a call)
 IW_ROWS_CELEBA = 512    # ... of the CelebA scorer: the one-pass workspace of a 512-row plan (mmvae_celeba_iw_workspace_bytes) stays below 1 GiB
+IW_ROWS_COCO = 512      # ... of the COCO scorer (a multiple of 4): mmvae_coco_iw_workspace_bytes of a 512-row, 102-step plan (n_latents 100) is 214983680 bytes (205.0 MiB)
 POSTERIORS = ("joint", "image", "text")
 
 
@@ -241,9 +242,12 @@ class _Family:
     decoder's steps T and classes V (words [rows][T][V]), the shape of one image, the particle rows of one scoring call and
     the scoring workspace."""
 
-    def __init__(self, name, T, V, image_shape, rows, score, workspace_bytes):
+    def __init__(self, name, T, V, image_shape, rows, score, workspace_bytes, float_text=False):
         self.name, self.T, self.V, self.image_shape, self.rows = name, T, V, image_shape, rows
         self.score, self.workspace_bytes = score, workspace_bytes
+        # float_text: the second modality is a float tensor (B, steps, 300) scored by a squared error (COCO captions), not int64
+        # targets; the scoring call then also gets text / sos / sse / scale (``_coco_score``) and writes words = scale * sse
+        self.float_text = float_text
 
 
 def _mm_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
@@ -261,6 +265,32 @@ def _celeba_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
     _iw_call("mmvae_celeba_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)
 
 
+def _coco_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream, text=None, sos=None, sse=None, scale=-0.5):
+    """words [rows][1][1] = -sse / (2 sigma^2): the per-particle part of log p(y|z); the constant is added after finalize."""
+    from ._lib import ptr
+    _iw_call("mmvae_coco_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), ptr(text), ptr(sos), nr, nk, ptr(lx), ptr(sse), stream)
+    torch.mul(sse[:rows], scale, out=words[:rows])
+
+
+def coco_text_constant(steps, text_sigma):
+    """-(steps * 300 / 2) log(2 pi sigma^2): the part of the Gaussian caption log-likelihood every particle shares (float64)."""
+    import math
+    text_sigma = float(text_sigma)
+    if not text_sigma > 0 or not math.isfinite(text_sigma):
+        raise ValueError("text_sigma must be a positive finite number (got %r)" % (text_sigma,))
+    return -0.5 * int(steps) * 300 * math.log(2.0 * math.pi * text_sigma * text_sigma)
+
+
+def _shift_text_terms(out, log_w, c):
+    """Adds the constant c of log p(y|z) behind mmvae_iw_finalize: to the y and xy columns of log p^ (``out`` (B, 8): columns 1,
+    2) and of log w (``log_w`` (B, K, 3) or None), and to the caption NLL (column 7, -c).  The same for every particle, so it
+    commutes with the log-sum-exp; the ESS columns do not change."""
+    out[:, 1:3] += c
+    out[:, 7] -= c
+    if log_w is not None:
+        log_w[..., 1:3] += c
+
+
 _FAMILIES = {
     "multimnist": _Family("multimnist", 4, 12, (1, 50, 50), IW_ROWS, _mm_score,
                           lambda st, rows: _iw_call("mmvae_mm_iw_workspace_bytes", st.plan(rows))),
@@ -268,13 +298,18 @@ _FAMILIES = {
     # the 18 attributes are 18 "text positions" of V = 2 classes: words [rows][18][2] = (log(1 - p), log p), targets 0 / 1
     "celeba": _Family("celeba", 18, 2, (3, 64, 64), IW_ROWS_CELEBA, _celeba_score,
                       lambda st, rows: _iw_call("mmvae_celeba_iw_workspace_bytes", st.plan(rows))),
+    # the caption term goes through the accumulator as ONE position of ONE class: words [rows][1][1] = -SSE / (2 sigma^2), targets 0
+    "coco": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_score,
+                    lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), float_text=True),
 }
 
 
 def _family(model):
     from .celeba import MultimodalVAE as CelebaVAE
+    from .coco import MultimodalVAE as CocoVAE
     from .mnist import MultimodalVAE as MnistVAE
-    return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else "multimnist"]
+    return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else
+                     "coco" if isinstance(model, CocoVAE) else "multimnist"]
 
 
 def _posterior(posterior):
@@ -284,7 +319,7 @@ def _posterior(posterior):
 
 @torch.no_grad()
 def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0, particles_per_call=None, eps=None,
-                return_z=False, return_log_w=False):
+                return_z=False, return_log_w=False, text_sigma=1.0):
     """Importance-sampled log p(x), log p(y), log p(x, y) of one batch under the proposal q = N(mu, exp(logvar)).
 
     ``model``: a multimnist ``MultimodalVAE`` (its decoders run in eval mode); ``image`` (B,1,50,50) float, ``text`` (B,4)
@@ -295,6 +330,14 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     are the int64 targets): mmvae_celeba_iw_score runs the bf16 image decoder and scores 3x64x64 logits, log p(y|z) is the sum
     over the 18 attributes of y*a - softplus(a) on the attribute decoder's fp32 logit a.  The result keys keep their names: the
     y / "text" columns are the attribute terms.
+    A coco ``MultimodalVAE`` takes ``image`` (B,3,32,32) and the captions ``text`` as floats (B, steps, 300) (``steps`` the model's):
+    mmvae_coco_iw_score runs the bf16 image decoder and scores 3x32x32 logits, and runs the caption decoder in eval mode (its own
+    output fed back, no dropout).  The reference trains captions with a mean squared error and defines no likelihood; the model under
+    which that loss is the NLL up to scale is used: log p(y|z) = -SSE / (2 sigma^2) - (steps * 300 / 2) log(2 pi sigma^2) with
+    sigma = ``text_sigma`` (the other families ignore it).  log p(y) and log p(x, y) of COCO therefore DEPEND ON sigma: compare
+    checkpoints only at the same ``text_sigma``.  The kernels accumulate -SSE / (2 sigma^2) alone; the constant (about -28,119 at
+    102 steps and sigma = 1) is added to the y / xy columns of ``log_p`` and ``log_w`` and to the caption ``nll`` afterwards, so
+    that fp32 keeps the digits of the per-particle terms.  ``return_log_w`` also returns ``sse`` (B, K) for this family.
     Particles z_k = mu + exp(logvar/2) eps_k, k = 1..K, with eps keyed by (seed, first_row + example, particle, dimension) only, so a particle does not depend on the batch it comes
     in or on how the K particles are split into calls.  With
         log w_k^x = log p(x|z_k) + log p(z_k) - log q(z_k)       (y, xy alike)
@@ -324,7 +367,18 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     chunks = iw_chunks(B, K, capacity)
     rows_max = max(nr * nk for _, nr, _, nk in chunks)
     image = image.reshape(B, -1).contiguous().float()
-    text = text.contiguous().long()
+    extra, sse_all, text_const = {}, None, 0.0
+    if fam.float_text:
+        steps = int(model.steps)
+        text_const = coco_text_constant(steps, text_sigma)
+        captions = text.contiguous().float()
+        if tuple(captions.shape) != (B, steps, 300) or image.shape[1] != int(np.prod(fam.image_shape)):
+            raise ValueError("iw_estimate: a coco model of %d steps takes images (B,3,32,32) and captions (B,%d,300) for its B = %d "
+                             "proposals (got %s, %s)" % (steps, steps, B, tuple(image.shape), tuple(text.shape)))
+        text = torch.zeros(B, 1, dtype=torch.int64, device=mu.device)          # the one "class" of the one caption position
+        extra = dict(sos=model.text_decoder.sos.to(mu.device, torch.float32).contiguous(), scale=-0.5 / float(text_sigma) ** 2)
+    else:
+        text = text.contiguous().long()
     if image.shape[1] != int(np.prod(fam.image_shape)) or text.numel() != B * fam.T:
         raise ValueError("iw_estimate: a %s model takes images of %d pixels and %d target(s) per example (got %s, %s)" %
                          (fam.name, int(np.prod(fam.image_shape)), fam.T, tuple(image.shape), tuple(text.shape)))
@@ -339,6 +393,9 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     state = torch.empty(B, 3, 4, **f32)
     z_all = torch.empty(B, K, D, **f32) if return_z else None
     lw_all = torch.empty(B, K, 3, **f32) if return_log_w else None
+    if fam.float_text:
+        extra["sse"] = torch.empty(rows_max, **f32)
+        sse_all = torch.empty(B, K, **f32) if return_log_w else None
     stream = _ops.stream()
     _iw_call("mmvae_iw_init", ptr(state), B, stream)
     for r0, nr, k0, nk in chunks:
@@ -347,19 +404,27 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
         lwc = None if lw_all is None else torch.empty(nr, nk, 3, **f32)
         _iw_call("mmvae_iw_particles", ptr(mu[r0:]), ptr(logvar[r0:]), nr, D, nk, int(first_row) + r0, k0, int(seed) & (2 ** 64 - 1),
                  ptr(e), ptr(zbuf), ptr(lr), stream)
-        fam.score(st, rows, ws, ws_bytes, zbuf, image[r0:], nr, nk, lx, words, stream)
+        if fam.float_text:
+            extra["text"] = captions[r0:]
+        fam.score(st, rows, ws, ws_bytes, zbuf, image[r0:], nr, nk, lx, words, stream, **extra)
         _iw_call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(text[r0:]), fam.T, fam.V, ptr(lr), nr, nk, ptr(state[r0:]), ptr(lwc), stream)
         if z_all is not None:
             z_all[r0:r0 + nr, k0:k0 + nk] = zbuf[:rows * D].view(nr, nk, D)
         if lw_all is not None:
             lw_all[r0:r0 + nr, k0:k0 + nk] = lwc
+        if sse_all is not None:
+            sse_all[r0:r0 + nr, k0:k0 + nk] = extra["sse"][:rows].view(nr, nk)
     out = torch.empty(B, 8, **f32)
     _iw_call("mmvae_iw_finalize", ptr(state), B, K, ptr(out), stream)
+    if fam.float_text:
+        _shift_text_terms(out, lw_all, text_const)
     res = {"log_p": out[:, 0:3], "ess": out[:, 3:6], "nll": out[:, 6:8]}
     if return_z:
         res["z"] = z_all
     if return_log_w:
         res["log_w"] = lw_all
+        if sse_all is not None:
+            res["sse"] = sse_all
     return res
 
 
@@ -388,12 +453,13 @@ def _proposal(model, image, text, posterior):
 
 
 @torch.no_grad()
-def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use_cuda=True, verbose=False):
+def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use_cuda=True, verbose=False, text_sigma=1.0):
     """Dataset means of the importance-sampled log p^(x), log p^(y), log p^(x, y) (``iw_estimate``) with the proposal of
     one posterior ("joint": q(z|x,y), "image": q(z|x), "text": q(z|y)), and of the two reconstruction NLLs.
 
     ``model``: a multimnist, mnist or celeba ``MultimodalVAE`` (``iw_estimate``; a CelebA loader yields (image, (B,18) attributes),
-    ``posterior="attrs"`` is a synonym of "text", and ``log_py`` / ``text_nll`` are the attribute terms).  It runs in eval mode (BatchNorm running
+    ``posterior="attrs"`` is a synonym of "text", and ``log_py`` / ``text_nll`` are the attribute terms; a COCO loader yields
+    (image, (B, steps, 300) float captions), and ``text_sigma`` is the sigma of its Gaussian caption likelihood, see ``iw_estimate``).  It runs in eval mode (BatchNorm running
     statistics, no dropout); per batch only the encoders and the experts run to form the proposal, then the particle chunks.  Nothing is read back to the host until the end.  Unlike the reference's
     multimnist/loglikelihood.py, the bounds weight each particle by p(z)/q(z) and take the log-sum-exp (see ``iw_estimate``);
     ``image_nll`` / ``text_nll`` are the reference's quantity (mean over particles of the summed reconstruction NLL), without
@@ -409,10 +475,11 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
     dev = next(model.parameters()).device
     logp, ess, nll, n_seen = [], [], [], 0
     for image, text in loader:
-        image = image.to(dev).float().reshape(-1, *_family(model).image_shape)
-        text = text.to(dev).long()
+        fam = _family(model)
+        image = image.to(dev).float().reshape(-1, *fam.image_shape)
+        text = text.to(dev).float() if fam.float_text else text.to(dev).long()
         mu, logvar = _proposal(model, image, text, posterior)
-        r = iw_estimate(model, image, text, mu, logvar, n_particles, seed=seed, first_row=n_seen)
+        r = iw_estimate(model, image, text, mu, logvar, n_particles, seed=seed, first_row=n_seen, text_sigma=text_sigma)
         logp.append(r["log_p"]); ess.append(r["ess"]); nll.append(r["nll"])
         n_seen += image.shape[0]
         if verbose:
@@ -426,10 +493,10 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
 
 
 @torch.no_grad()
-def marginal_table(model, loader, n_particles=1000, seed=0):
+def marginal_table(model, loader, n_particles=1000, seed=0, text_sigma=1.0):
     """The paper's evaluation: log p^(x) and log p^(y) (plus log p^(x, y)) under each of the three posteriors, K particles
-    per example.  -> {posterior: log_marginal(...) result} for "joint", "image", "text"."""
-    return {post: log_marginal(model, loader, n_particles, post, seed=seed) for post in POSTERIORS}
+    per example.  -> {posterior: log_marginal(...) result} for "joint", "image", "text".  ``text_sigma``: COCO only."""
+    return {post: log_marginal(model, loader, n_particles, post, seed=seed, text_sigma=text_sigma) for post in POSTERIORS}
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -679,6 +746,25 @@ def _parser():
     src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic CelebA-shaped examples instead of a file')
     pc.add_argument('--seed', type=int, default=0, help='seed of the particles')
     pc.add_argument('--json', type=str, default=None, help='write the bounds to this file')
+    # the flags of `loglik` for a checkpoint of train_coco; the '<s>' vector is not in the checkpoint
+    pk = sub.add_parser("loglik_coco", help="importance-sampled log p(x), log p(y) for a checkpoint of train_coco")
+    pk.add_argument('model_path', type=str, help='path to a checkpoint written by train_coco')
+    tab = pk.add_mutually_exclusive_group()
+    tab.add_argument('--sos', type=str, default=None, metavar='FILE.pt', help="the 300 floats of GloVe('<s>') (default: sos.pt of --data)")
+    tab.add_argument('--words', type=str, default=None, metavar='TABLE.pt', help="word table file (coco.save_word_table) that has '<s>'")
+    mode = pk.add_mutually_exclusive_group()
+    mode.add_argument('--image_only', action='store_true', default=False, help='proposal from the image only')
+    mode.add_argument('--text_only', action='store_true', default=False, help='proposal from the caption only')
+    mode.add_argument('--all', action='store_true', default=False, help='all three posteriors (the paper\'s table)')
+    pk.add_argument('--n_samples', type=int, default=100, help='particles per example')
+    pk.add_argument('--batch_size', type=int, default=64)
+    pk.add_argument('--text_sigma', type=float, default=1.0,
+                    help='sigma of the Gaussian caption likelihood; log p(y) depends on it (default: 1.0)')
+    src = pk.add_mutually_exclusive_group()
+    src.add_argument('--data', type=str, default=None, metavar='DIR', help='folder with images_u8.pt, captions.pt (and sos.pt), as train_coco reads')
+    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic COCO-shaped examples instead of files')
+    pk.add_argument('--seed', type=int, default=0, help='seed of the particles (and of the synthetic examples)')
+    pk.add_argument('--json', type=str, default=None, help='write the bounds to this file')
     # multimnist/sample.py's flags for a checkpoint of train_coco; the captions are decoded through a word table
     pw = sub.add_parser("sample_coco", help="multimnist/sample.py for the COCO family: images + captions decoded to words")
     pw.add_argument('model_path', type=str, help='path to a checkpoint written by train_coco')
@@ -904,12 +990,14 @@ def _sample_coco_main(args):
     return captions
 
 
-def _report(vae, loader, posts, args, second):
-    """Runs ``log_marginal`` per posterior, prints the reference's NLL line and the bounds, writes ``--json``."""
+def _report(vae, loader, posts, args, second, text_sigma=None):
+    """Runs ``log_marginal`` per posterior, prints the reference's NLL line and the bounds, writes ``--json`` (``text_sigma``: the
+    COCO command's, recorded in the file)."""
     import json
     table = {}
     for post in posts:
-        r = log_marginal(vae, loader, n_particles=args.n_samples, posterior=post, seed=args.seed)
+        r = log_marginal(vae, loader, n_particles=args.n_samples, posterior=post, seed=args.seed,
+                         text_sigma=1.0 if text_sigma is None else text_sigma)
         table[post] = r
         mess = r["ess"].double().mean(0)
         print('\nTest Image NLL: {:.4f}\tTest {} NLL: {:.4f}'.format(r["image_nll"], second, r["text_nll"]))
@@ -918,6 +1006,8 @@ def _report(vae, loader, posts, args, second):
                                                                     *mess.tolist()))
     if args.json:
         out = {"n_samples": args.n_samples, "n_examples": table[posts[0]]["n"], "seed": args.seed}
+        if text_sigma is not None:
+            out["text_sigma"] = text_sigma
         for post, r in table.items():
             out[post] = {k: r[k] for k in ("log_px", "log_py", "log_pxy", "image_nll", "text_nll")}
             out[post]["mean_ess"] = r["ess"].double().mean(0).tolist()
@@ -959,6 +1049,52 @@ def _loglik_celeba_main(args):
     return _report(vae, loader, posts, args, "Attrs")
 
 
+def check_coco_eval_data(images, captions, text_sigma=1.0, where="loglik_coco"):
+    """The host-side refusals of ``loglik_coco``: images must be uint8 (N,3,32,32), captions float (N,102,300) for the same N >= 1,
+    sigma > 0.  -> (uint8 images, float32 captions)."""
+    from .coco import MAX_WORDS, N_EMBEDDING
+    coco_text_constant(MAX_WORDS, text_sigma)                     # refuses sigma <= 0 / non-finite
+    x, t = torch.as_tensor(images), torch.as_tensor(captions)
+    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 32, 32) or x.shape[0] < 1:
+        raise ValueError("%s: images must be uint8 (N,3,32,32) with N >= 1 (got %s %s)" % (where, x.dtype, tuple(x.shape)))
+    if not t.is_floating_point() or t.dim() != 3 or tuple(t.shape) != (x.shape[0], MAX_WORDS, N_EMBEDDING):
+        raise ValueError("%s: captions must be float (N,%d,%d) for the N = %d images (got %s %s)"
+                         % (where, MAX_WORDS, N_EMBEDDING, x.shape[0], t.dtype, tuple(t.shape)))
+    return x, t.float()
+
+
+def _loglik_coco_main(args):
+    """`loglik_coco`: the result keys (and the JSON layout) are those of `loglik`, plus ``text_sigma``."""
+    import os
+    from . import coco as K
+    from .train_coco import synthetic_coco
+    coco_text_constant(K.MAX_WORDS, args.text_sigma)              # before anything is loaded
+    sos = words = None
+    if args.synthetic > 0:
+        x, t, sos = synthetic_coco(args.synthetic, seed=args.seed)
+    elif args.data:
+        x = torch.load(os.path.join(args.data, "images_u8.pt"), weights_only=False)
+        t = torch.load(os.path.join(args.data, "captions.pt"), weights_only=False)
+        if not args.sos and not args.words:
+            sos = torch.load(os.path.join(args.data, "sos.pt"), weights_only=False)
+    else:
+        raise SystemExit("loglik_coco: give --data DIR or --synthetic N")
+    x, t = check_coco_eval_data(x, t, args.text_sigma)
+    if args.sos:
+        sos = torch.load(args.sos, weights_only=False)
+    elif args.words:
+        sos, words = None, K.load_word_table(args.words)
+    if sos is not None:
+        sos = torch.as_tensor(sos)
+        if sos.numel() != K.N_EMBEDDING or not sos.is_floating_point():
+            raise ValueError("loglik_coco: the '<s>' vector must be %d floats (got %s %s)" % (K.N_EMBEDDING, sos.dtype, tuple(sos.shape)))
+    x = x.float().div_(255.0)                                     # transforms.ToTensor()
+    loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    vae = K.load_checkpoint(args.model_path, use_cuda=True, sos=sos, words=words)
+    posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
+    return _report(vae, loader, posts, args, "Text", text_sigma=float(args.text_sigma))
+
+
 def _loglik_main(args):
     from . import data as D
     from .utils import charlist_tensor
@@ -993,6 +1129,8 @@ def _main(argv=None):
         return _loglik_main(args)
     if args.cmd == "loglik_celeba":
         return _loglik_celeba_main(args)
+    if args.cmd == "loglik_coco":
+        return _loglik_coco_main(args)
     if args.cmd == "sample_coco":
         return _sample_coco_main(args)
     if args.cmd == "latent_mmd":

@@ -1,6 +1,6 @@
 """Rate of the importance-sampled evaluation (evaluate.iw_estimate / marginal_table) against a compute_nll-style loop.
 
-    python tools/loglik_bench.py [--dataset multimnist|mnist|celeba] [--batch 64] [--particles 1000] [--loop_particles 100] [--batches 4]
+    python tools/loglik_bench.py [--dataset multimnist|mnist|celeba|coco] [--batch 64] [--particles 1000] [--loop_particles 100] [--batches 4]
                                  [--table_examples 10000]
 
 --dataset mnist (``main_mnist``): the fused fp32 scorer mmvae_mnist_iw_score against an unfused batched chain of the drop-in
@@ -298,9 +298,146 @@ def main_celeba(args):
     print("achieved in iw_estimate             %.1f TFLOP/s (decoder count over the iw_estimate wall time)" % (flops_particle * rate_f / 1e12))
 
 
+def main_coco(args):
+    """COCO: particles/s of
+      * ``iw_estimate`` on mmvae_coco_iw_score (particles -> bf16 image decoder body -> scoring tail, caption decoder -> squared
+        error per row -> accumulate -> finalize);
+      * the same pipeline with the scoring call replaced by the unfused chain a user could write without it: ``vae.image_decoder``
+        and ``vae.text_decoder`` called once on all rows of the chunk, then torch ops on what they return (-binary_cross_entropy per
+        element summed per row; the squared error against the captions summed per row, times -1/2).  Same particles, same chunks
+        of at most IW_ROWS_COCO rows, same accumulator;
+      * the two scoring steps alone on one chunk (device events);
+      * the scoring tail alone (mmvae_coco_iw_tail on an IW_ROWS_COCO-row raw tensor) against its byte bound: the raw tensor read
+        once, 32 KB per row, plus the row's image.
+    The 102 sequential GRU steps of the caption decoder are in both pipelines and dominate both.  The two pipelines alternate
+    ``--repeats`` times after a warm-up of both; their log p^ are compared on the first batch."""
+    import ctypes as C
+    import torch.nn.functional as F
+    from multimodal_vae_amd import coco as M
+    from multimodal_vae_amd._lib import call, ptr
+    from multimodal_vae_amd.evaluate import iw_estimate, _proposal, iw_chunks, IW_ROWS_COCO
+    from multimodal_vae_amd.train_coco import synthetic_coco
+    from oracle import mmvae_ref as R
+    dev = torch.device("cuda:0")
+    D, B, K, T = 100, args.batch, args.particles, M.MAX_WORDS
+    x, t, sos = synthetic_coco(B * (args.batches + 1), seed=0)
+    vae = M.MultimodalVAE(D, sos=sos)
+    vae.load_state_dict(R.formula_params("coco", D), strict=True)
+    vae.cuda().eval()
+    st = vae._core.sync(dev)
+    x = x.float().div_(255.0)
+    batches = [(x[i:i + B].to(dev), t[i:i + B].to(dev).contiguous()) for i in range(0, B * (args.batches + 1), B)]
+    f32 = dict(dtype=torch.float32, device=dev)
+    zeros = torch.zeros(B, 1, dtype=torch.int64, device=dev)
+
+    def stream():
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def unfused_score(z, image, text, nr, nk):
+        """log p(x|z) (nr*nk,) and -SSE / 2 (nr*nk,) from the decoder modules + torch ops."""
+        p = vae.image_decoder(z)
+        y = vae.text_decoder(z)
+        lx = -F.binary_cross_entropy(p.view(nr, nk, -1), image.reshape(nr, 1, -1).expand(nr, nk, 3 * 32 * 32), reduction="none").sum(2)
+        ly = (y.view(nr, nk, T, 300) - text.view(nr, 1, T, 300)).pow(2).sum((2, 3)).mul(-0.5)
+        return lx.reshape(-1).contiguous(), ly.reshape(-1).contiguous()
+
+    def run_unfused(i):
+        image, text = batches[i]
+        mu, lv = props[i]
+        state = torch.empty(B, 3, 4, **f32)
+        call("mmvae_iw_init", ptr(state), B, stream())
+        for r0, nr, k0, nk in iw_chunks(B, K, IW_ROWS_COCO):
+            rows = nr * nk
+            z, lr = torch.empty(rows, D, **f32), torch.empty(rows, **f32)
+            call("mmvae_iw_particles", ptr(mu[r0:]), ptr(lv[r0:]), nr, D, nk, i * B + r0, k0, 0, None, ptr(z), ptr(lr), stream())
+            lx, words = unfused_score(z, image[r0:r0 + nr], text[r0:r0 + nr], nr, nk)
+            call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(zeros[r0:]), 1, 1, ptr(lr), nr, nk, ptr(state[r0:]), None, stream())
+        out = torch.empty(B, 8, **f32)
+        call("mmvae_iw_finalize", ptr(state), B, K, ptr(out), stream())
+        return out[:, 0:3]
+
+    def run_fused(i):
+        r = iw_estimate(vae, batches[i][0], batches[i][1], props[i][0], props[i][1], K, first_row=i * B)["log_p"].clone()
+        r[:, 1:3] -= const                                      # (the unfused chain above carries no constant)
+        return r
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(1, len(batches)):
+            fn(i)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    from multimodal_vae_amd.evaluate import coco_text_constant
+    const = coco_text_constant(T, 1.0)
+    with torch.no_grad():
+        props = [_proposal(vae, im, tx, "joint") for im, tx in batches]
+        a, b = run_fused(0), run_unfused(0)                     # warm-up of both, and the same numbers from both
+        torch.cuda.synchronize()
+        diff = (a.double() - b.double()).abs().max(0).values.tolist()
+        tf, tu = [], []
+        for _ in range(args.repeats):
+            tf.append(timed(run_fused))
+            tu.append(timed(run_unfused))
+    per = B * K * args.batches
+    rate_f, rate_u = per / min(tf), per / min(tu)
+    chunks = iw_chunks(B, K, IW_ROWS_COCO)
+    print("loglik_bench --dataset coco: B = %d, K = %d, n_latents = %d, steps = %d, %d scoring calls of <= %d rows per batch, %d batches per timing" %
+          (B, K, D, T, len(chunks), IW_ROWS_COCO, args.batches))
+    print("fused   vs unfused log p^ (x, y, xy) of batch 0 (without the constant): max abs difference %s" % " / ".join("%.2e" % v for v in diff))
+    print("iw_estimate, mmvae_coco_iw_score    %12.0f particles/s  (best of %s s)" % (rate_f, ", ".join("%.4f" % v for v in tf)))
+    print("same pipeline, unfused chain        %12.0f particles/s  (best of %s s)" % (rate_u, ", ".join("%.4f" % v for v in tu)))
+    print("ratio fused / unfused               %.2fx  %s" % (rate_f / rate_u, "" if rate_f >= rate_u else "(THE FUSED SCORER IS SLOWER)"))
+    sys.stdout.flush()
+
+    def ev_time(fn, reps=10):
+        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    # ---- the scoring step alone on one chunk (device events, 10 calls each after a warm-up call)
+    with torch.no_grad():
+        r0, nr, k0, nk = chunks[0]
+        rows = nr * nk
+        image, text = batches[1][0][r0:r0 + nr].contiguous(), batches[1][1][r0:r0 + nr].contiguous()
+        z, lr = torch.empty(rows, D, **f32), torch.empty(rows, **f32)
+        call("mmvae_iw_particles", ptr(props[1][0]), ptr(props[1][1]), nr, D, nk, 0, 0, 0, None, ptr(z), ptr(lr), stream())
+        lx, sse = torch.empty(rows, **f32), torch.empty(rows, **f32)
+        h = st.plan(rows)
+        wsb = call("mmvae_coco_iw_workspace_bytes", h)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        sosd = vae.text_decoder.sos.to(dev).contiguous()
+
+        def fused_score():
+            call("mmvae_coco_iw_score", h, ptr(ws), wsb, ptr(z), ptr(image), ptr(text), ptr(sosd), nr, nk, ptr(lx), ptr(sse), stream())
+        t_fs = ev_time(fused_score)
+        t_us = ev_time(lambda: unfused_score(z, image, text, nr, nk))
+    print("scoring step alone, %d rows (workspace %.1f MiB):  mmvae_coco_iw_score %.3f ms   unfused chain %.3f ms   ratio %.2fx" %
+          (rows, wsb / 2.0 ** 20, t_fs * 1e3, t_us * 1e3, t_us / t_fs))
+    # ---- the scoring tail alone against its byte bound
+    n = IW_ROWS_COCO
+    g = torch.Generator().manual_seed(0)
+    q3 = torch.randn(n, 16, 16, 64, generator=g).to(dev).to(torch.bfloat16).contiguous()
+    aff = torch.tensor([1.0, 0.0]).repeat(64, 1).to(dev).contiguous()
+    w = (torch.randn(64, 3, 4, 4, generator=g) * 0.05).to(dev).contiguous()
+    img = torch.rand(n, 3, 32, 32, generator=g).to(dev).contiguous()
+    ll = torch.empty(n, **f32)
+    t_tail = ev_time(lambda: call("mmvae_coco_iw_tail", ptr(q3), ptr(aff), 1, ptr(w), ptr(img), n, 1, ptr(ll), None, stream()), reps=50)
+    nbytes = n * (16 * 16 * 64 * 2 + 3 * 32 * 32 * 4)
+    print("scoring tail alone, %d rows:  %.1f us, %.2f MB read once (raw tensor 32 KB + image 12 KB per row) = %.0f GB/s "
+          "(50 calls back to back between device events; the inputs fit the cache)" % (n, t_tail * 1e6, nbytes / 1e6, nbytes / t_tail / 1e9))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dataset", choices=("multimnist", "mnist", "celeba"), default="multimnist")
+    ap.add_argument("--dataset", choices=("multimnist", "mnist", "celeba", "coco"), default="multimnist")
     ap.add_argument("--repeats", type=int, default=3, help="mnist, celeba: alternations of the fused and the unfused pipeline")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--particles", type=int, default=1000)
@@ -314,6 +451,8 @@ def main():
         return main_mnist(args)
     if args.dataset == "celeba":
         return main_celeba(args)
+    if args.dataset == "coco":
+        return main_coco(args)
     from multimodal_vae_amd import multimnist as M, data as Dd
     from multimodal_vae_amd._lib import call
     from multimodal_vae_amd.evaluate import iw_estimate, marginal_table, _proposal, iw_chunks, IW_ROWS
