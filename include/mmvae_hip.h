@@ -411,6 +411,19 @@ int mmvae_coco_text_decoder_fwd(mmvae_coco_t*, void* ws, size_t ws_bytes, const 
                                 const uint8_t* keep, int training, float* sentence, void* stream);  /* coco/model.py:266-288 */
 int mmvae_coco_text_decoder_bwd(mmvae_coco_t*, void* ws, size_t ws_bytes, const float* z, const float* sos,
                                 const uint8_t* keep, const float* sentence, const float* d_sentence, float* dz, void* stream);
+/* Test / profiling aids, as mmvae_celeba_bench_layer / mmvae_celeba_debug_offset: one named launch of the step's image half
+ * `iters` times on the workspace contents, built by the same definitions the step calls (csrc/coco.hip layer_gemm / layer_wgrad and
+ * the builders of the stand-alone passes), and the byte offset of a named intermediate inside the step's workspace (-1 if
+ * unknown).  The classifier runs its 2 dropout variants, the decoder 3 passes.  Layer names:
+ *   enc_conv1, enc_conv1_wgrad; enc_conv2..4 and dec_convT1..3, each with _dgrad and _wgrad;
+ *   fc1, fc2, fc3, up, each with _wgrad and _dgrad (knob "coco_layer_mask" 1: the keep flags in m1 / m2 take part);
+ *   dec_last_dgrad_gemm, dec_last_wgrad;
+ *   the stand-alone passes enc_bn2..4, dec_bn1..3 (BatchNorm + Swish, training mode, encoder 2 / decoder 1 running-statistics
+ *   updates per group) and their _bwd forms (enc_bn4_bwd sums the two variants' gradients), im2col_dlogit (dlogit -> patches4),
+ *   dec_last_fwd (target in tmp_f32, loss weights (1, 1/2, 0) / (B * 3072), logits [3B][3][32][32] at the start of slab, recon
+ *   behind them, dlogit and the BCE sums where the step writes them). */
+int mmvae_coco_bench_layer(mmvae_coco_t*, void* ws, size_t ws_bytes, const char* layer, int iters, void* stream);
+long long mmvae_coco_debug_offset(mmvae_coco_t*, const char* name);
 /* Importance-weighted evaluation, the COCO scoring step between mmvae_iw_particles and mmvae_iw_accumulate(T = 1, V = 1) on the
  * B*K particle rows z [B][K][n_latents] (row b*K + k: example b; B*K at most the plan's batch):
  *   * the eval-mode image decoder body (the bf16 launches of mmvae_coco_image_decoder_fwd up to the raw output of

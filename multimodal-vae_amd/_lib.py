@@ -232,6 +232,8 @@ SIGNATURES["mmvae_coco_text_encoder_fwd"] = (_I, [_P, _P, _SZ, _P, _P, _P])
 SIGNATURES["mmvae_coco_text_encoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P])
 SIGNATURES["mmvae_coco_text_decoder_fwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _I, _P, _P])
 SIGNATURES["mmvae_coco_text_decoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P])
+SIGNATURES["mmvae_coco_bench_layer"] = (_I, [_P, _P, _SZ, C.c_char_p, _I, _P])
+SIGNATURES["mmvae_coco_debug_offset"] = (_LL, [_P, C.c_char_p])
 SIGNATURES["mmvae_coco_iw_workspace_bytes"] = (_SZ, [_P])
 SIGNATURES["mmvae_coco_iw_score"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES["mmvae_coco_iw_tail"] = (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P])

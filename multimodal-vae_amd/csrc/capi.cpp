@@ -331,6 +331,10 @@ int mmvae_coco_text_decoder_fwd(mmvae_coco_t* p, void* ws, size_t wsb, const flo
 int mmvae_coco_text_decoder_bwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, const float* sentence, const float* d_sentence, float* dz, void* st) {
     return guarded([&] { return coco_text_decoder_bwd(p, ws, wsb, z, sos, keep, sentence, d_sentence, dz, S(st)); });
 }
+int mmvae_coco_bench_layer(mmvae_coco_t* p, void* ws, size_t wsb, const char* layer, int iters, void* stream) {
+    return guarded([&] { return coco_bench_layer(p, ws, wsb, layer, iters, S(stream)); });
+}
+long long mmvae_coco_debug_offset(mmvae_coco_t* p, const char* name) { return coco_debug_offset(p, name); }
 size_t mmvae_coco_iw_workspace_bytes(const mmvae_coco_t* p) { return p ? coco_iw_workspace_bytes(p) : 0; }
 int mmvae_coco_iw_score(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* image, const float* text, const float* sos,
                         int B, int K, float* loglik_x, float* sse_y, void* st) {

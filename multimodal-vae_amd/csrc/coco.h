@@ -20,6 +20,9 @@ int coco_text_encoder_fwd(CocoPlan*, void* ws, size_t wsb, const float* text, fl
 int coco_text_encoder_bwd(CocoPlan*, void* ws, size_t wsb, const float* text, const float* d_out, hipStream_t);
 int coco_text_decoder_fwd(CocoPlan*, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, int training, float* sentence, hipStream_t);
 int coco_text_decoder_bwd(CocoPlan*, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, const float* sentence, const float* d_sentence, float* dz, hipStream_t);
+// test / profiling aids (include/mmvae_hip.h: mmvae_coco_bench_layer / mmvae_coco_debug_offset)
+int coco_bench_layer(CocoPlan*, void* ws, size_t wsb, const char* layer, int iters, hipStream_t);
+long long coco_debug_offset(CocoPlan*, const char* name);
 // importance-weighted evaluation (include/mmvae_hip.h: mmvae_coco_iw_*): coco_iw_score (coco.hip) runs the eval-mode image
 // decoder body, the eval-mode caption decoder and the two scoring kernels of coco_iw.hip
 int coco_iw_score(CocoPlan*, void* ws, size_t wsb, const float* z, const float* image, const float* text, const float* sos, int B, int K,

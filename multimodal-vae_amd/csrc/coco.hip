@@ -12,6 +12,8 @@
 #include "coco_plan.h"
 #include "thin.h"
 #include <cstring>
+#include <map>
+#include <string>
 
 namespace {
 constexpr int IMG = 32, NPIX = 3 * IMG * IMG, FEAT = 2048, HID1 = 1024, HID2 = 256;
@@ -154,224 +156,324 @@ void carve(CocoPlan& P, Workspace& ws) {
     coco_text_carve(P, ws);
 }
 
-// ================================================================== image encoder (coco/model.py:182-187)
-int enc_fwd(CocoPlan& P, const float* image, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, int training,
-            int bn_updates, float* out, hipStream_t s) {
+// ================================================================== one definition per launch
+// Every GemmParams / WgradParams of the image encoder and decoder and the arguments of every stand-alone pass are built here, for
+// the step (enc_fwd / enc_bwd / dec_fwd / dec_bwd) and for the replay of one launch on a test's own operands (coco_bench_layer): a
+// test cannot pass on a copy of the parameters that drifted from the step.  l: layer index (conv[l] / convT[l]); n: row blocks --
+// dropout variants of the classifier, BatchNorm groups (passes) of the decoder.
+enum CoGemm { CO_ENC_CONV1, CO_ENC_CONV, CO_ENC_CONV_DGRAD, CO_FC1, CO_FC2, CO_FC3, CO_FC3_DGRAD, CO_FC2_DGRAD, CO_FC1_DGRAD, CO_UP,
+              CO_UP_DGRAD, CO_DEC_CONVT, CO_DEC_CONVT_DGRAD, CO_DEC_LAST_DGRAD };
+enum CoWgrad { CO_W_ENC_CONV1, CO_W_ENC_CONV, CO_W_FC1, CO_W_FC2, CO_W_FC3, CO_W_UP, CO_W_DEC_CONVT, CO_W_DEC_LAST };
+
+// mask: keep flags of the classifier Dropout the layer applies (CO_FC1 / CO_FC2_DGRAD: m1, CO_FC2 / CO_FC3_DGRAD: m2) or null;
+// training: column statistics of the conv layers; aux: CO_FC3 the fp32 result [n*B][2D], CO_FC3_DGRAD the operand d_out [n*B][2D],
+// CO_UP_DGRAD the fp32 result dz [n*B][D]
+GemmParams layer_gemm(CocoPlan& P, CoGemm kind, int l, int n, int training = 1, const uint8_t* mask = nullptr, const void* aux = nullptr) {
     CocoPlan::W& w = P.w;
-    const int B = P.B;
-    MMVAE_TRY(launch_im2col_small(image, B, 3, IMG, IMG, 4, 4, 2, 1, 16, 16, w.patches1, 48, s));
-    {   // conv1 + Swish (no BatchNorm): raw and activated outputs
+    const int B = P.B, rows = n * B, D2 = 2 * P.D;
+    const float ms = 1.f / (1.f - DROP_P);
+    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
+    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
+    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
+    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
+    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
+    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
+    switch (kind) {
+    case CO_ENC_CONV1: {   // conv1 + Swish (no BatchNorm): raw and activated outputs
         GatherPlan pl = dense_plan(B * 256, 48, 48, 64);
         GemmParams g = gemm_of(P, pl, P.conv[0].pk_fwd, 1, B * 256);
         g.c.A = w.patches1; g.out_bf = w.r1; g.ldo = 64; g.out_act_bf = w.a1; g.e_act = ACT_SWISH;
-        MMVAE_TRY(launch_gemm_gather(g, s));
+        return g;
     }
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    for (int l = 1; l < 4; ++l) {
+    case CO_ENC_CONV: {
         const ConvL& L = P.conv[l];
         GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, 1, B, L.pk_fwd_f);
         g.c.A = a[l - 1];
         g.out_bf = r[l]; g.ldo = L.g.Cout;
         g.colstats = training ? w.st_e[l - 1] : nullptr;
-        MMVAE_TRY(launch_gemm_gather(g, s));
-        const int rows = B * L.g.OH * L.g.OW;
-        MMVAE_TRY(bn_act(P, P.bn[L.bn], r[l], a[l], rows, rows, 1, w.st_e[l - 1], bn_updates, w.aff_e[l - 1], w.mr_e[l - 1], training, s));
+        return g;
     }
-    const int rows = variants * B;
-    const bool drop = training && dropout;
-    const float ms = 1.f / (1.f - DROP_P);
-    {   // classifier.0 over the NHWC 2x2x512 map (shared by the variants) + Swish + Dropout
+    case CO_ENC_CONV_DGRAD: {
+        const ConvL& L = P.conv[l];
+        GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
+        d.c.A = dr[l]; d.out_bf = dr[l - 1]; d.ldo = L.g.Cin;
+        d.d_r = r[l - 1]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
+        if (l > 1) { d.d_affine = w.aff_e[l - 2]; d.d_meanrstd = w.mr_e[l - 2]; d.d_red = w.red_e[l - 2]; }
+        return d;
+    }
+    case CO_FC1: {   // classifier.0 over the NHWC 2x2x512 map (shared by the variants) + Swish + Dropout
         GatherPlan pl = plan_fwdform(2, 2, 1, 1, 512, 2, 2, 1, 0, HID1, 1, rows);
         GemmParams g = gemm_of(P, pl, &P.fc[0].pk_fwd, 1, rows);
         g.c.A = w.a4; g.c.a_bcast_n = B;
         g.bias = P.buf.params + P.fc[0].b_off; g.out_bf = w.y1; g.ldo = HID1;
-        g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (drop) { g.e_mask = m1; g.e_mask_scale = ms; }
-        MMVAE_TRY(launch_gemm_gather(g, s));
+        g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (mask) { g.e_mask = mask; g.e_mask_scale = ms; }
+        return g;
     }
-    {
+    case CO_FC2: {   // classifier.3 + Swish + Dropout
         GatherPlan pl = dense_plan(rows, HID1, HID1, HID2);
         GemmParams g = gemm_of(P, pl, &P.fc[1].pk_fwd, 1, rows);
         g.c.A = w.ay1;
         g.bias = P.buf.params + P.fc[1].b_off; g.out_bf = w.y2; g.ldo = HID2;
-        g.out_act_bf = w.ay2; g.e_act = ACT_SWISH; if (drop) { g.e_mask = m2; g.e_mask_scale = ms; }
-        MMVAE_TRY(launch_gemm_gather(g, s));
+        g.out_act_bf = w.ay2; g.e_act = ACT_SWISH; if (mask) { g.e_mask = mask; g.e_mask_scale = ms; }
+        return g;
     }
-    {
-        GatherPlan pl = dense_plan(rows, HID2, HID2, 2 * P.D);
+    case CO_FC3: {   // classifier.6
+        GatherPlan pl = dense_plan(rows, HID2, HID2, D2);
         GemmParams g = gemm_of(P, pl, &P.fc[2].pk_fwd, 1, rows);
         g.c.A = w.ay2;
-        g.bias = P.buf.params + P.fc[2].b_off; g.out_f = out; g.ldo = 2 * P.D;
-        MMVAE_TRY(launch_gemm_gather(g, s));
+        g.bias = P.buf.params + P.fc[2].b_off; g.out_f = (float*)aux; g.ldo = D2;
+        return g;
     }
-    return MMVAE_OK;
-}
-
-// d_out: bf16 [variants*B][2D]; the bias gradient of classifier.6 must already be accumulated by the caller
-int enc_bwd(CocoPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, hipStream_t s) {
-    CocoPlan::W& w = P.w;
-    const int B = P.B, rows = variants * B, D2 = 2 * P.D;
-    const float ms = 1.f / (1.f - DROP_P);
-    {   // classifier.6
-        GatherPlan pl = dense_plan(rows, HID2, HID2, D2);
-        WgradParams g = wgrad_of(P, pl, &P.fc[2].gk, 1, rows);
-        g.c.A = w.ay2; g.P = d_out; g.ldp = D2;
-        MMVAE_TRY(wgrad_async(P, g, s));
+    case CO_FC3_DGRAD: {   // classifier.6: its column sums are the bias gradient of classifier.3
         GatherPlan pd = dense_plan(rows, D2, D2, HID2);
         GemmParams d = gemm_of(P, pd, &P.fc[2].pk_dgrad, 1, rows);
-        d.c.A = d_out; d.out_bf = w.dy2; d.ldo = HID2;
-        d.d_r = w.y2; d.d_ld = HID2; d.d_act = ACT_SWISH; if (dropout) { d.d_mask = m2; d.d_mask_scale = ms; }
+        d.c.A = (const bf16*)aux; d.out_bf = w.dy2; d.ldo = HID2;
+        d.d_r = w.y2; d.d_ld = HID2; d.d_act = ACT_SWISH; if (mask) { d.d_mask = mask; d.d_mask_scale = ms; }
         d.d_colsum = P.buf.grads + P.fc[1].b_off;
-        MMVAE_TRY(launch_gemm_gather(d, s));
+        return d;
     }
-    {   // classifier.3
-        GatherPlan pl = dense_plan(rows, HID1, HID1, HID2);
-        WgradParams g = wgrad_of(P, pl, &P.fc[1].gk, 1, rows);
-        g.c.A = w.ay1; g.P = w.dy2; g.ldp = HID2;
-        MMVAE_TRY(wgrad_async(P, g, s));
+    case CO_FC2_DGRAD: {   // classifier.3: its column sums are the bias gradient of classifier.0
         GatherPlan pd = dense_plan(rows, HID2, HID2, HID1);
         GemmParams d = gemm_of(P, pd, &P.fc[1].pk_dgrad, 1, rows);
         d.c.A = w.dy2; d.out_bf = w.dy1; d.ldo = HID1;
-        d.d_r = w.y1; d.d_ld = HID1; d.d_act = ACT_SWISH; if (dropout) { d.d_mask = m1; d.d_mask_scale = ms; }
+        d.d_r = w.y1; d.d_ld = HID1; d.d_act = ACT_SWISH; if (mask) { d.d_mask = mask; d.d_mask_scale = ms; }
         d.d_colsum = P.buf.grads + P.fc[0].b_off;
-        MMVAE_TRY(launch_gemm_gather(d, s));
+        return d;
     }
-    {   // classifier.0: wgrad gathers the shared 2x2x512 map; the input gradient is one dense GEMM over NHWC columns
-        GatherPlan pl = plan_fwdform(2, 2, 1, 1, 512, 2, 2, 1, 0, HID1, 1, rows);
-        WgradParams g = wgrad_of(P, pl, &P.fc[0].gk, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.P = w.dy1; g.ldp = HID1;
-        MMVAE_TRY(wgrad_async(P, g, s));
+    case CO_FC1_DGRAD: {   // classifier.0: the input gradient is one dense GEMM over NHWC columns
         GatherPlan pd = dense_plan(rows, HID1, HID1, FEAT);
         GemmParams d = gemm_of(P, pd, &P.fc1_dgrad, 1, rows);
         d.c.A = w.dy1; d.out_bf = w.db4; d.ldo = FEAT;
         d.d_r = w.r4; d.d_ld = FEAT; d.d_bcast_n = B; d.d_act = ACT_SWISH; d.d_cmod = 512;
         d.d_affine = w.aff_e[2]; d.d_meanrstd = w.mr_e[2]; d.d_red = w.red_e[2];
-        MMVAE_TRY(launch_gemm_gather(d, s));
+        return d;
     }
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
+    case CO_UP: {
+        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
+        GemmParams g = gemm_of(P, pl, &P.up.pk_fwd, 1, rows);
+        g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = FEAT; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
+        return g;
+    }
+    case CO_UP_DGRAD: {
+        GatherPlan pd = dense_plan(rows, FEAT, FEAT, P.D);
+        GemmParams d = gemm_of(P, pd, &P.up.pk_dgrad, 1, rows);
+        d.c.A = w.du; d.out_f = (float*)aux; d.ldo = P.D;
+        return d;
+    }
+    case CO_DEC_CONVT: {
+        const ConvL& L = P.convT[l];
+        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, n, B, L.pk_fwd_f);
+        g.c.A = aq[l];
+        g.out_bf = q[l + 1]; g.ldo = L.g.Cout;
+        g.colstats = training ? w.st_d[l] : nullptr;
+        return g;
+    }
+    case CO_DEC_CONVT_DGRAD: {
+        const ConvL& L = P.convT[l];
+        GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, n, B, L.pk_dgrad_f);
+        d.c.A = dq[l + 1]; d.out_bf = dq[l]; d.ldo = L.g.Cin;
+        d.d_r = q[l]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
+        if (l > 0) { d.d_affine = w.aff_d[l - 1]; d.d_meanrstd = w.mr_d[l - 1]; d.d_red = w.red_d[l - 1]; }
+        return d;
+    }
+    case CO_DEC_LAST_DGRAD: {   // input gradient = dense GEMM patches x W with d-Swish + BatchNorm-backward sums in the epilogue
+        GatherPlan pd = dense_plan(B * 256, 48, 48, 64);
+        GemmParams d = gemm_of(P, pd, P.convT[3].pk_dgrad, n, B * 256);
+        d.c.A = w.patches4; d.out_bf = w.d3; d.ldo = 64;
+        d.d_r = w.q3; d.d_ld = 64; d.d_act = ACT_SWISH; d.d_affine = w.aff_d[2]; d.d_meanrstd = w.mr_d[2]; d.d_red = w.red_d[2];
+        return d;
+    }
+    }
+    return GemmParams{};
+}
+
+// aux: CO_W_FC3 the operand d_out [n*B][2D]
+WgradParams layer_wgrad(CocoPlan& P, CoWgrad kind, int l, int n, const bf16* aux = nullptr) {
+    CocoPlan::W& w = P.w;
+    const int B = P.B, rows = n * B;
     bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
     bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    for (int l = 3; l >= 1; --l) {
-        const ConvL& L = P.conv[l];
-        const BnL& b = P.bn[L.bn];
-        const int pix = L.g.OH * L.g.OW;
-        BnBwdApplyArgs x{};
-        x.db = (l == 3) ? w.db4 : dr[l];
-        x.db2 = (l == 3 && variants == 2) ? w.db4 + (size_t)B * FEAT : nullptr;
-        x.r = r[l]; x.dr = dr[l]; x.rows = B * pix; x.C = L.g.Cout; x.ld = L.g.Cout; x.rows_per_group = B * pix; x.G = 1;
-        x.red = w.red_e[l - 1]; x.meanrstd = w.mr_e[l - 1]; x.gamma = P.buf.params + b.w_off;
-        x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
-        MMVAE_TRY(launch_bn_bwd_apply(x, s));
-        {
-            WgradParams g = wgrad_of(P, L.fwd, L.gk, 1, B);
-            g.c.A = a[l - 1]; g.P = dr[l]; g.ldp = L.g.Cout;
-            MMVAE_TRY(wgrad_async(P, g, s));
-        }
-        {
-            GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
-            d.c.A = dr[l]; d.out_bf = dr[l - 1]; d.ldo = L.g.Cin;
-            d.d_r = r[l - 1]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-            if (l > 1) { d.d_affine = w.aff_e[l - 2]; d.d_meanrstd = w.mr_e[l - 2]; d.d_red = w.red_e[l - 2]; }
-            MMVAE_TRY(launch_gemm_gather(d, s));
-        }
-    }
-    {   // conv1 wgrad over the im2col patches
+    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
+    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
+    switch (kind) {
+    case CO_W_ENC_CONV1: {   // conv1 wgrad over the im2col patches
         GatherPlan pl = dense_plan(B * 256, 48, 48, 64);
         WgradParams g = wgrad_of(P, pl, P.conv[0].gk, 1, B * 256);
         g.c.A = w.patches1; g.P = w.d1e; g.ldp = 64;
-        MMVAE_TRY(wgrad_async(P, g, s));
+        return g;
     }
-    return MMVAE_OK;
+    case CO_W_ENC_CONV: {
+        const ConvL& L = P.conv[l];
+        WgradParams g = wgrad_of(P, L.fwd, L.gk, 1, B);
+        g.c.A = a[l - 1]; g.P = dr[l]; g.ldp = L.g.Cout;
+        return g;
+    }
+    case CO_W_FC1: {   // classifier.0: wgrad gathers the shared 2x2x512 map
+        GatherPlan pl = plan_fwdform(2, 2, 1, 1, 512, 2, 2, 1, 0, HID1, 1, rows);
+        WgradParams g = wgrad_of(P, pl, &P.fc[0].gk, 1, rows);
+        g.c.A = w.a4; g.c.a_bcast_n = B;
+        g.P = w.dy1; g.ldp = HID1;
+        return g;
+    }
+    case CO_W_FC2: {   // classifier.3
+        GatherPlan pl = dense_plan(rows, HID1, HID1, HID2);
+        WgradParams g = wgrad_of(P, pl, &P.fc[1].gk, 1, rows);
+        g.c.A = w.ay1; g.P = w.dy2; g.ldp = HID2;
+        return g;
+    }
+    case CO_W_FC3: {   // classifier.6
+        GatherPlan pl = dense_plan(rows, HID2, HID2, 2 * P.D);
+        WgradParams g = wgrad_of(P, pl, &P.fc[2].gk, 1, rows);
+        g.c.A = w.ay2; g.P = aux; g.ldp = 2 * P.D;
+        return g;
+    }
+    case CO_W_UP: {   // upsample Linear: weight (+ folded bias) gradient
+        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
+        WgradParams g = wgrad_of(P, pl, &P.up.gk, 1, rows);
+        g.c.A = w.z_bf; g.P = w.du; g.ldp = FEAT;
+        return g;
+    }
+    case CO_W_DEC_CONVT:
+        return convT_wgrad(P, P.convT[l], n, B, aq[l], dq[l + 1]);
+    case CO_W_DEC_LAST: {   // last transposed conv (64 -> 3) through the im2col patches of dlogit (K = 16 taps x 3)
+        GatherPlan pl = plan_fwdform(1, 1, 16, 16, 48, 1, 1, 1, 0, 64, n, B);   // rows (n, iy, ix), dense K=48
+        WgradParams g = wgrad_of(P, pl, P.convT[3].gk, n, B);
+        g.c.A = w.patches4; g.c.AH = 16; g.c.AW = 16; g.c.sy = g.c.sx = 1;
+        g.P = w.aq3; g.ldp = 64;
+        return g;
+    }
+    }
+    return WgradParams{};
+}
+
+// ---- the stand-alone passes
+// image [B][3][32][32] -> patches1 [B*256][48];  dlogit [groups*B][3][32][32] -> patches4 [groups*B*256][48]: the same kernel with
+// the same arguments except the row count
+int im2col_image(CocoPlan& P, const float* image, hipStream_t s) {
+    return launch_im2col_small(image, P.B, 3, IMG, IMG, 4, 4, 2, 1, 16, 16, P.w.patches1, 48, s);
+}
+int im2col_dlogit(CocoPlan& P, const float* dlogit, int groups, hipStream_t s) {
+    return launch_im2col_small(dlogit, groups * P.B, 3, IMG, IMG, 4, 4, 2, 1, 16, 16, P.w.patches4, 48, s);
+}
+// BatchNorm + Swish behind conv[l] (l = 1..3) / convT[l] (l = 0..2): tables, running statistics, activated tensor
+int enc_bn_act(CocoPlan& P, int l, int bn_updates, int training, hipStream_t s) {
+    CocoPlan::W& w = P.w;
+    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
+    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
+    const ConvL& L = P.conv[l];
+    const int rows = P.B * L.g.OH * L.g.OW;
+    return bn_act(P, P.bn[L.bn], r[l], a[l], rows, rows, 1, w.st_e[l - 1], bn_updates, w.aff_e[l - 1], w.mr_e[l - 1], training, s);
+}
+int dec_bn_act(CocoPlan& P, int l, int groups, int training, hipStream_t s) {
+    CocoPlan::W& w = P.w;
+    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
+    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
+    const ConvL& L = P.convT[l];
+    const int rpg = P.B * L.g.OH * L.g.OW;
+    return bn_act(P, P.bn[L.bn], q[l + 1], aq[l + 1], groups * rpg, rpg, groups, w.st_d[l], 1, w.aff_d[l], w.mr_d[l], training, s);
+}
+// BatchNorm backward behind conv[l] / convT[l]; features.9 (l = 3) sums the gradients of the 2 classifier variants (db2)
+BnBwdApplyArgs enc_bn_bwd_args(CocoPlan& P, int l, int variants) {
+    CocoPlan::W& w = P.w;
+    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
+    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
+    const int B = P.B;
+    const ConvL& L = P.conv[l];
+    const BnL& b = P.bn[L.bn];
+    const int pix = L.g.OH * L.g.OW;
+    BnBwdApplyArgs x{};
+    x.db = (l == 3) ? w.db4 : dr[l];
+    x.db2 = (l == 3 && variants == 2) ? w.db4 + (size_t)B * FEAT : nullptr;
+    x.r = r[l]; x.dr = dr[l]; x.rows = B * pix; x.C = L.g.Cout; x.ld = L.g.Cout; x.rows_per_group = B * pix; x.G = 1;
+    x.red = w.red_e[l - 1]; x.meanrstd = w.mr_e[l - 1]; x.gamma = P.buf.params + b.w_off;
+    x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
+    return x;
+}
+BnBwdApplyArgs dec_bn_bwd_args(CocoPlan& P, int l, int groups) {
+    CocoPlan::W& w = P.w;
+    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
+    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
+    const int B = P.B, rows = groups * B;
+    const ConvL& L = P.convT[l];
+    const BnL& b = P.bn[L.bn];
+    const int pix = L.g.OH * L.g.OW;
+    BnBwdApplyArgs x{};
+    x.db = dq[l + 1]; x.r = q[l + 1]; x.dr = dq[l + 1]; x.rows = rows * pix; x.C = L.g.Cout; x.ld = L.g.Cout;
+    x.rows_per_group = B * pix; x.G = groups;
+    x.red = w.red_d[l]; x.meanrstd = w.mr_d[l]; x.gamma = P.buf.params + b.w_off;
+    x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
+    return x;
+}
+// last transposed conv (64 -> 3) + sigmoid + BCE: `last` carries the caller's target / outputs / loss weights
+ConvTLastFwdArgs dec_last_args(CocoPlan& P, const ConvTLastFwdArgs& last, int groups) {
+    ConvTLastFwdArgs x = last;
+    x.act = P.w.aq3; x.w = P.buf.params + P.convT[3].w_off; x.G = groups; x.B = P.B; x.IH = 16; x.IW = 16; x.Cin = 64; x.Cout = 3;
+    return x;
+}
+
+// ================================================================== image encoder (coco/model.py:182-187)
+int enc_fwd(CocoPlan& P, const float* image, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, int training,
+            int bn_updates, float* out, hipStream_t s) {
+    MMVAE_TRY(im2col_image(P, image, s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_ENC_CONV1, 0, 1), s));
+    for (int l = 1; l < 4; ++l) {
+        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_ENC_CONV, l, 1, training), s));
+        MMVAE_TRY(enc_bn_act(P, l, bn_updates, training, s));
+    }
+    const bool drop = training && dropout;
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC1, 0, variants, training, drop ? m1 : nullptr), s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC2, 0, variants, training, drop ? m2 : nullptr), s));
+    return launch_gemm_gather(layer_gemm(P, CO_FC3, 0, variants, training, nullptr, out), s);
+}
+
+// d_out: bf16 [variants*B][2D]; the bias gradient of classifier.6 must already be accumulated by the caller
+int enc_bwd(CocoPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, hipStream_t s) {
+    // classifier.6
+    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_FC3, 0, variants, d_out), s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC3_DGRAD, 0, variants, 1, dropout ? m2 : nullptr, d_out), s));
+    // classifier.3
+    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_FC2, 0, variants), s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC2_DGRAD, 0, variants, 1, dropout ? m1 : nullptr), s));
+    // classifier.0: wgrad gathers the shared 2x2x512 map; the input gradient is one dense GEMM over NHWC columns
+    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_FC1, 0, variants), s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC1_DGRAD, 0, variants), s));
+    for (int l = 3; l >= 1; --l) {
+        MMVAE_TRY(launch_bn_bwd_apply(enc_bn_bwd_args(P, l, variants), s));
+        MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_ENC_CONV, l, 1), s));
+        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_ENC_CONV_DGRAD, l, 1), s));
+    }
+    // conv1 wgrad over the im2col patches
+    return wgrad_async(P, layer_wgrad(P, CO_W_ENC_CONV1, 0, 1), s);
 }
 
 // ================================================================== image decoder (coco/model.py:211-216)
 // last == nullptr (coco_iw_score): the body only -- it ends with the raw output of hallucinate.6 in q3, whose BatchNorm + Swish
 // belong to the caller's own tail
 int dec_fwd(CocoPlan& P, int groups, int training, ConvTLastFwdArgs* last, hipStream_t s) {
-    CocoPlan::W& w = P.w;
-    const int B = P.B, rows = groups * B;
-    {
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
-        GemmParams g = gemm_of(P, pl, &P.up.pk_fwd, 1, rows);
-        g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = FEAT; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
-        MMVAE_TRY(launch_gemm_gather(g, s));
-    }
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_UP, 0, groups), s));
     for (int l = 0; l < 3; ++l) {
-        const ConvL& L = P.convT[l];
-        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, groups, B, L.pk_fwd_f);
-        g.c.A = aq[l];
-        g.out_bf = q[l + 1]; g.ldo = L.g.Cout;
-        g.colstats = training ? w.st_d[l] : nullptr;
-        MMVAE_TRY(launch_gemm_gather(g, s));
-        const int rpg = B * L.g.OH * L.g.OW;
+        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_DEC_CONVT, l, groups, training), s));
         if (l == 2 && !last) continue;
-        MMVAE_TRY(bn_act(P, P.bn[L.bn], q[l + 1], aq[l + 1], groups * rpg, rpg, groups, w.st_d[l], 1, w.aff_d[l], w.mr_d[l], training, s));
+        MMVAE_TRY(dec_bn_act(P, l, groups, training, s));
     }
     if (!last) return MMVAE_OK;
-    ConvTLastFwdArgs x = *last;
-    x.act = w.aq3; x.w = P.buf.params + P.convT[3].w_off; x.G = groups; x.B = B; x.IH = 16; x.IW = 16; x.Cin = 64; x.Cout = 3;
-    return launch_convt_last_fwd(x, s);
+    return launch_convt_last_fwd(dec_last_args(P, *last, groups), s);
 }
 
 // dlogit: fp32 NCHW [groups*B][3][32][32] (grad wrt the pre-sigmoid logits). Writes dz (fp32 [groups*B][D]).
 int dec_bwd(CocoPlan& P, const float* dlogit, int groups, float* dz, hipStream_t s) {
-    CocoPlan::W& w = P.w;
-    const int B = P.B, rows = groups * B;
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    {   // last transposed conv (64 -> 3): both gradients go through the im2col patches of dlogit (K = 16 taps x 3)
-        const ConvL& L = P.convT[3];
-        MMVAE_TRY(launch_im2col_small(dlogit, rows, 3, IMG, IMG, 4, 4, 2, 1, 16, 16, w.patches4, 48, s));
-        {
-            GatherPlan pd = dense_plan(B * 256, 48, 48, 64);
-            GemmParams d = gemm_of(P, pd, L.pk_dgrad, groups, B * 256);
-            d.c.A = w.patches4; d.out_bf = w.d3; d.ldo = 64;
-            d.d_r = w.q3; d.d_ld = 64; d.d_act = ACT_SWISH; d.d_affine = w.aff_d[2]; d.d_meanrstd = w.mr_d[2]; d.d_red = w.red_d[2];
-            MMVAE_TRY(launch_gemm_gather(d, s));
-        }
-        GatherPlan pl = plan_fwdform(1, 1, 16, 16, 48, 1, 1, 1, 0, 64, groups, B);   // rows (n, iy, ix), dense K=48
-        WgradParams g = wgrad_of(P, pl, L.gk, groups, B);
-        g.c.A = w.patches4; g.c.AH = 16; g.c.AW = 16; g.c.sy = g.c.sx = 1;
-        g.P = w.aq3; g.ldp = 64;
-        MMVAE_TRY(wgrad_async(P, g, s));
-    }
+    // last transposed conv (64 -> 3): both gradients go through the im2col patches of dlogit (K = 16 taps x 3)
+    MMVAE_TRY(im2col_dlogit(P, dlogit, groups, s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_DEC_LAST_DGRAD, 3, groups), s));
+    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_DEC_LAST, 3, groups), s));
     for (int l = 2; l >= 0; --l) {
-        const ConvL& L = P.convT[l];
-        const BnL& b = P.bn[L.bn];
-        const int pix = L.g.OH * L.g.OW;
-        BnBwdApplyArgs x{};
-        x.db = dq[l + 1]; x.r = q[l + 1]; x.dr = dq[l + 1]; x.rows = rows * pix; x.C = L.g.Cout; x.ld = L.g.Cout;
-        x.rows_per_group = B * pix; x.G = groups;
-        x.red = w.red_d[l]; x.meanrstd = w.mr_d[l]; x.gamma = P.buf.params + b.w_off;
-        x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
-        MMVAE_TRY(launch_bn_bwd_apply(x, s));
-        {
-            WgradParams g = convT_wgrad(P, L, groups, B, aq[l], dq[l + 1]);
-            MMVAE_TRY(wgrad_async(P, g, s));
-        }
-        {
-            GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, groups, B, L.pk_dgrad_f);
-            d.c.A = dq[l + 1]; d.out_bf = dq[l]; d.ldo = L.g.Cin;
-            d.d_r = q[l]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-            if (l > 0) { d.d_affine = w.aff_d[l - 1]; d.d_meanrstd = w.mr_d[l - 1]; d.d_red = w.red_d[l - 1]; }
-            MMVAE_TRY(launch_gemm_gather(d, s));
-        }
+        MMVAE_TRY(launch_bn_bwd_apply(dec_bn_bwd_args(P, l, groups), s));
+        MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_DEC_CONVT, l, groups), s));
+        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_DEC_CONVT_DGRAD, l, groups), s));
     }
-    {   // upsample Linear: weight (+ folded bias) gradient and dz
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
-        WgradParams g = wgrad_of(P, pl, &P.up.gk, 1, rows);
-        g.c.A = w.z_bf; g.P = w.du; g.ldp = FEAT;
-        MMVAE_TRY(wgrad_async(P, g, s));
-        GatherPlan pd = dense_plan(rows, FEAT, FEAT, P.D);
-        GemmParams d = gemm_of(P, pd, &P.up.pk_dgrad, 1, rows);
-        d.c.A = w.du; d.out_f = dz; d.ldo = P.D;
-        MMVAE_TRY(launch_gemm_gather(d, s));
-    }
-    return MMVAE_OK;
+    // upsample Linear: weight (+ folded bias) gradient and dz
+    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_UP, 0, groups), s));
+    return launch_gemm_gather(layer_gemm(P, CO_UP_DGRAD, 0, groups, 1, nullptr, dz), s);
 }
 
 int use_ws(CocoPlan* P, void* ws, size_t bytes, bool module = true) {
@@ -624,4 +726,130 @@ int coco_iw_score(CocoPlan* P, void* ws, size_t wsb, const float* z, const float
     MMVAE_TRY(launch_coco_iw_tail(t, s));
     MMVAE_TRY(coco_text_dec_fwd(*P, zt, 1, sos, nullptr, 0, w.td_recon, s));
     return launch_coco_iw_text_sse(w.td_recon, text, B, K, P->T, sse_y, s);
+}
+
+// ---------------------------------------------------------------- test / profiling aid: replay one launch of the step
+// The launches of layer_gemm / layer_wgrad and the stand-alone passes under names: <layer>, <layer>_dgrad, <layer>_wgrad, enc_bn<l> /
+// dec_bn<l> (+ _bwd), im2col_dlogit, dec_last_fwd.  The classifier runs its 2 dropout variants, the decoder 3 passes forward and
+// backward (the default step), BatchNorm makes the running-statistics updates of the default step (encoder 2, decoder 1 per
+// group).  Knob "coco_layer_mask" (0): the keep flags in W::m1 / W::m2 take part in fc1 / fc2 / fc3_dgrad / fc2_dgrad as in a step
+// with classifier dropout.  fc3 writes encout; fc3_dgrad / fc3_wgrad read d_encout; fc3_dgrad and fc2_dgrad add, as in the step,
+// their column sums to the bias gradients of classifier.3 / classifier.0 in the flat gradients; up_dgrad writes dz into dz_img.
+// dec_last_fwd: target [B][3][32][32] in tmp_f32, loss weights (1, 1/2, 0) / (B * 3072), dlogit into dlogit, BCE sums into sums,
+// logits [3B][3][32][32] at the start of the weight-gradient slab and recon right behind them.
+static bool named_gemm(CocoPlan& P, const std::string& name, GemmParams& g) {
+    CocoPlan::W& w = P.w;
+    const bool masked = mmvae_knob("coco_layer_mask", 0) != 0;
+    const uint8_t *m1 = masked ? w.m1 : nullptr, *m2 = masked ? w.m2 : nullptr;
+    if (name == "enc_conv1") { g = layer_gemm(P, CO_ENC_CONV1, 0, 1); return true; }
+    for (int l = 1; l < 4; ++l) {
+        const std::string n = "enc_conv" + std::to_string(l + 1);
+        if (name == n) { g = layer_gemm(P, CO_ENC_CONV, l, 1); return true; }
+        if (name == n + "_dgrad") { g = layer_gemm(P, CO_ENC_CONV_DGRAD, l, 1); return true; }
+    }
+    if (name == "fc1") { g = layer_gemm(P, CO_FC1, 0, 2, 1, m1); return true; }
+    if (name == "fc2") { g = layer_gemm(P, CO_FC2, 0, 2, 1, m2); return true; }
+    if (name == "fc3") { g = layer_gemm(P, CO_FC3, 0, 2, 1, nullptr, w.encout); return true; }
+    if (name == "fc3_dgrad") { g = layer_gemm(P, CO_FC3_DGRAD, 0, 2, 1, m2, w.d_encout); return true; }
+    if (name == "fc2_dgrad") { g = layer_gemm(P, CO_FC2_DGRAD, 0, 2, 1, m1); return true; }
+    if (name == "fc1_dgrad") { g = layer_gemm(P, CO_FC1_DGRAD, 0, 2); return true; }
+    if (name == "up") { g = layer_gemm(P, CO_UP, 0, 3); return true; }
+    if (name == "up_dgrad") { g = layer_gemm(P, CO_UP_DGRAD, 0, 3, 1, nullptr, w.dz_img); return true; }
+    for (int l = 0; l < 3; ++l) {
+        const std::string n = "dec_convT" + std::to_string(l + 1);
+        if (name == n) { g = layer_gemm(P, CO_DEC_CONVT, l, 3); return true; }
+        if (name == n + "_dgrad") { g = layer_gemm(P, CO_DEC_CONVT_DGRAD, l, 3); return true; }
+    }
+    if (name == "dec_last_dgrad_gemm") { g = layer_gemm(P, CO_DEC_LAST_DGRAD, 3, 3); return true; }
+    return false;
+}
+static bool named_wgrad(CocoPlan& P, const std::string& name, WgradParams& g) {
+    if (name == "enc_conv1_wgrad") { g = layer_wgrad(P, CO_W_ENC_CONV1, 0, 1); return true; }
+    for (int l = 1; l < 4; ++l)
+        if (name == "enc_conv" + std::to_string(l + 1) + "_wgrad") { g = layer_wgrad(P, CO_W_ENC_CONV, l, 1); return true; }
+    if (name == "fc1_wgrad") { g = layer_wgrad(P, CO_W_FC1, 0, 2); return true; }
+    if (name == "fc2_wgrad") { g = layer_wgrad(P, CO_W_FC2, 0, 2); return true; }
+    if (name == "fc3_wgrad") { g = layer_wgrad(P, CO_W_FC3, 0, 2, P.w.d_encout); return true; }
+    if (name == "up_wgrad") { g = layer_wgrad(P, CO_W_UP, 0, 3); return true; }
+    for (int l = 0; l < 3; ++l)
+        if (name == "dec_convT" + std::to_string(l + 1) + "_wgrad") { g = layer_wgrad(P, CO_W_DEC_CONVT, l, 3); return true; }
+    if (name == "dec_last_wgrad") { g = layer_wgrad(P, CO_W_DEC_LAST, 3, 3); return true; }
+    return false;
+}
+// 1: launched, 0: not a stand-alone pass, < 0: error
+static int named_pass(CocoPlan& P, const std::string& name, hipStream_t s) {
+    CocoPlan::W& w = P.w;
+    for (int l = 1; l < 4; ++l) {
+        const std::string n = "enc_bn" + std::to_string(l + 1);
+        if (name == n) { const int rc = enc_bn_act(P, l, 2, 1, s); return rc == MMVAE_OK ? 1 : rc; }
+        if (name == n + "_bwd") { const int rc = launch_bn_bwd_apply(enc_bn_bwd_args(P, l, 2), s); return rc == MMVAE_OK ? 1 : rc; }
+    }
+    for (int l = 0; l < 3; ++l) {
+        const std::string n = "dec_bn" + std::to_string(l + 1);
+        if (name == n) { P.dec_skip_mask = 0; const int rc = dec_bn_act(P, l, 3, 1, s); return rc == MMVAE_OK ? 1 : rc; }
+        if (name == n + "_bwd") { const int rc = launch_bn_bwd_apply(dec_bn_bwd_args(P, l, 3), s); return rc == MMVAE_OK ? 1 : rc; }
+    }
+    if (name == "im2col_dlogit") { const int rc = im2col_dlogit(P, w.dlogit, 3, s); return rc == MMVAE_OK ? 1 : rc; }
+    if (name == "dec_last_fwd") {
+        const size_t n3 = (size_t)3 * P.B * NPIX;
+        if (w.slab_floats < 2 * n3) { mmvae_set_error("mmvae_coco_bench_layer: dec_last_fwd needs %zu floats of the slab", 2 * n3); return MMVAE_EINVAL; }
+        ConvTLastFwdArgs last{};
+        last.target = w.tmp_f32; last.logits = w.slab; last.recon = w.slab + n3; last.dlogit = w.dlogit; last.loss_sum = w.sums;
+        const float lam[3] = {1.f, 0.5f, 0.f};
+        for (int k = 0; k < 3; ++k) last.coef[k] = lam[k] / (float)(P.B * NPIX);
+        const int rc = launch_convt_last_fwd(dec_last_args(P, last, 3), s);
+        return rc == MMVAE_OK ? 1 : rc;
+    }
+    return 0;
+}
+int coco_bench_layer(CocoPlan* P, void* ws, size_t wsb, const char* layer, int iters, hipStream_t s) {
+    MMVAE_REQUIRE(P && layer, "mmvae_coco_bench_layer: null argument");
+    MMVAE_TRY(use_ws(P, ws, wsb, false));
+    WgradParams wg{};
+    if (named_wgrad(*P, layer, wg)) {            // kernel + its share of the slab reduction, as in the step
+        for (int i = 0; i < iters; ++i) {
+            P->slab.reset(P->w.slab, P->w.slab_floats);
+            MMVAE_TRY(launch_wgrad(wg, s, &P->slab));
+            MMVAE_TRY(launch_wgrad_reduce(&P->slab, s));
+        }
+        return MMVAE_OK;
+    }
+    GemmParams g{};
+    if (named_gemm(*P, layer, g)) {
+        for (int i = 0; i < iters; ++i) MMVAE_TRY(launch_gemm_gather(g, s));
+        return MMVAE_OK;
+    }
+    for (int i = 0; i < iters; ++i) {
+        const int rc = named_pass(*P, layer, s);
+        MMVAE_REQUIRE(rc != 0, "mmvae_coco_bench_layer: unknown layer '%s'", layer);
+        if (rc < 0) return rc;
+    }
+    return MMVAE_OK;
+}
+// byte offset of a named workspace buffer of the fused step's carving (3 passes), -1 if unknown
+long long coco_debug_offset(CocoPlan* P, const char* name) {
+    if (!P || !name) return -1;
+    Workspace ws((void*)0x1000, (size_t)1 << 40);      // (every call that works in a workspace carves its own again: plan_use_ws)
+    P->carve_passes = 3; P->carve_iw = false;
+    carve(*P, ws);
+    CocoPlan::W& w = P->w;
+    const std::map<std::string, const void*> m = {
+        {"patches1", w.patches1}, {"r1", w.r1}, {"r2", w.r2}, {"r3", w.r3}, {"r4", w.r4},
+        {"a1", w.a1}, {"a2", w.a2}, {"a3", w.a3}, {"a4", w.a4}, {"y1", w.y1}, {"ay1", w.ay1}, {"y2", w.y2}, {"ay2", w.ay2},
+        {"encout", w.encout}, {"m1", w.m1}, {"m2", w.m2},
+        {"z_bf", w.z_bf}, {"z_f32", w.z_f32}, {"u", w.u}, {"au", w.au}, {"q1", w.q1}, {"q2", w.q2}, {"q3", w.q3},
+        {"aq1", w.aq1}, {"aq2", w.aq2}, {"aq3", w.aq3}, {"dlogit", w.dlogit}, {"patches4", w.patches4},
+        {"d3", w.d3}, {"d2", w.d2}, {"d1", w.d1}, {"du", w.du}, {"dz_img", w.dz_img},
+        {"d_encout", w.d_encout}, {"dy2", w.dy2}, {"dy1", w.dy1}, {"db4", w.db4}, {"dr4", w.dr4},
+        {"d3e", w.d3e}, {"d2e", w.d2e}, {"d1e", w.d1e}, {"tmp_f32", w.tmp_f32}, {"slab", w.slab}, {"sums", w.sums},
+        {"st_e0", w.st_e[0]}, {"st_e1", w.st_e[1]}, {"st_e2", w.st_e[2]}, {"st_d0", w.st_d[0]}, {"st_d1", w.st_d[1]}, {"st_d2", w.st_d[2]},
+        {"red_e0", w.red_e[0]}, {"red_e1", w.red_e[1]}, {"red_e2", w.red_e[2]},
+        {"red_d0", w.red_d[0]}, {"red_d1", w.red_d[1]}, {"red_d2", w.red_d[2]},
+        {"aff_e0", w.aff_e[0]}, {"aff_e1", w.aff_e[1]}, {"aff_e2", w.aff_e[2]},
+        {"aff_d0", w.aff_d[0]}, {"aff_d1", w.aff_d[1]}, {"aff_d2", w.aff_d[2]},
+        {"mr_e0", w.mr_e[0]}, {"mr_e1", w.mr_e[1]}, {"mr_e2", w.mr_e[2]}, {"mr_d0", w.mr_d[0]}, {"mr_d1", w.mr_d[1]}, {"mr_d2", w.mr_d[2]},
+    };
+    auto it = m.find(name);
+    if (it == m.end()) return -1;
+    return (long long)((const char*)it->second - (const char*)0x1000);
 }

@@ -76,6 +76,8 @@ bool mmvae_serial();
 int mmvae_cu_count();
 bool mmvae_probe_on();
 void mmvae_probe_tag(const char* tag, double algo_flops);
+// appends " <note>" to the tag of the next probed launch: which template instantiation a launcher picked (no-op when the probe is off)
+void mmvae_probe_note(const char* note);
 void mmvae_probe_events(const char* kernel, hipEvent_t* start, hipEvent_t* stop);
 #define MMVAE_LAUNCH(kernel, grid, block, lds, stream, ...)                                              \
     do {                                                                                                 \

@@ -541,6 +541,11 @@ int launch_wgrad_v(const WgradParams& p, dim3 grid, size_t lds, hipStream_t stre
         hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<NWT, KWT, WN, WK>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     }
+    if (mmvae_probe_on()) {
+        char note[48];
+        snprintf(note, sizeof(note), "wgrad<%d,%d,%d,%d> %s", NWT, KWT, WN, WK, p.slab ? "slab" : "atomic");
+        mmvae_probe_note(note);
+    }
     MMVAE_LAUNCH((wgrad_kernel<NWT, KWT, WN, WK>), grid, dim3(256), lds, stream, p);
     return mmvae_check_launch("wgrad");
 }
@@ -768,6 +773,11 @@ int launch_rowtile(const GemmParams& p, hipStream_t stream) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_rowtile_kernel<NTW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
     }
     dim3 grid(max_tiles * p.c.groups, 1, p.c.nclasses);
+    if (mmvae_probe_on()) {
+        char note[40];
+        snprintf(note, sizeof(note), "rowtile<%d>", NTW);
+        mmvae_probe_note(note);
+    }
     MMVAE_LAUNCH(gemm_rowtile_kernel<NTW>, grid, dim3(256), lds, stream, p);
     return mmvae_check_launch("gemm_rowtile");
 }
@@ -788,6 +798,11 @@ int launch_gemm_nt(const GemmParams& p, hipStream_t stream) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     }
     hipEvent_t held = ksplit > 1 ? mmvae_take_stop_event() : nullptr;    // a completion event belongs to the LAST kernel of the launch
+    if (mmvae_probe_on()) {
+        char note[40];
+        snprintf(note, sizeof(note), "gather<%d> ksplit%d", NT, ksplit);
+        mmvae_probe_note(note);
+    }
     MMVAE_LAUNCH(gemm_gather_kernel<NT>, grid, dim3(256), lds, stream, p);
     MMVAE_TRY(mmvae_check_launch("gemm_gather"));
     if (ksplit > 1) {

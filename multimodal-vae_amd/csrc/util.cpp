@@ -123,6 +123,11 @@ void mmvae_probe_tag(const char* tag, double algo_flops) {
     snprintf(g_probe_tag, sizeof(g_probe_tag), "%s", tag);
     g_probe_flops = algo_flops;
 }
+void mmvae_probe_note(const char* note) {
+    if (!mmvae_probe_on()) return;
+    const size_t n = strlen(g_probe_tag);
+    if (n + 2 < sizeof(g_probe_tag)) snprintf(g_probe_tag + n, sizeof(g_probe_tag) - n, " %s", note);
+}
 void mmvae_probe_events(const char* kernel, hipEvent_t* start, hipEvent_t* stop) {
     std::lock_guard<std::mutex> g(g_probe_mu);
     hipEvent_t e[2];

@@ -1,5 +1,5 @@
-"""Layer-level reference and GPU harness of the MultiMNIST and CelebA conv / transposed-conv kernels (tests/test_gpu_layers.py,
-tests/test_gpu_celeba_layers.py, tests/test_cpu_layer_ref.py).
+"""Layer-level reference and GPU harness of the MultiMNIST, CelebA and COCO conv / transposed-conv kernels (tests/test_gpu_layers.py,
+tests/test_gpu_celeba_layers.py, tests/test_gpu_coco_layers.py, tests/test_cpu_layer_ref.py).
 
 One layer of the step is replayed through mmvae_<family>_bench_layer on operands the test wrote itself and compared with a float64
 reference made here with torch.nn.functional.conv2d / conv_transpose2d and torch.autograd -- never with another engine kernel.
@@ -70,6 +70,35 @@ LAYERS_CELEBA = {
 WS_NAMES_CELEBA = ("patches1 r1 r2 r3 r4 a1 a2 a3 a4 y1 ay1 encout m1 z_bf z_f32 u au q1 q2 q3 aq1 aq2 aq3 dlogit patches4 d3 d2 d1 du "
                    "dz_img dz_att d_encout dy1 db4 dr4 d3e d2e d1e tmp_f32 slab st_e0 st_e1 st_e2 st_d0 st_d1 st_d2 red_e0 red_e1 red_e2 "
                    "red_d0 red_d1 red_d2 aff_e0 aff_e1 aff_e2 aff_d0 aff_d1 aff_d2 mr_e0 mr_e1 mr_e2 mr_d0 mr_d1 mr_d2").split()
+
+# COCO: coco/model.py:157-208 as restated in csrc/coco.hip build() -- 32x32 images, every conv k4 s2 p1: encoder 64 -> 128 (16x16 -> 8x8),
+# 128 -> 256 (8 -> 4), 256 -> 512 (4 -> 2); decoder 512 -> 256 (2 -> 4), 256 -> 128 (4 -> 8), 128 -> 64 (8 -> 16).  Buffer names: csrc/coco.hip
+# layer_gemm / layer_wgrad.  The encoder runs 1 BatchNorm group, the replayed decoder 3 forward and backward (the default step).
+# Activation density 1/2 everywhere: the longest sum is 9 valid taps x 256 channels (features.8 on the 4x4 map, and the data
+# gradient of hallucinate.0) with variance 2304 / 8 = 288, and the largest sum of squares of a channel and group is that of
+# hallucinate.6 at B = 256, 65536 elements of variance 64 = 4.2e6 < 2^24 (tests/test_cpu_layer_ref.py asserts the regime for every
+# batch and seed used).
+# Batches: derived in the docstring of tests/test_gpu_coco_layers.py.
+BATCHES_COCO = (3, 4, 6, 8, 128, 256)
+LAYERS_COCO = {
+    "enc_conv2": Layer("image_encoder.features.2.weight", False, 64, 128, 4, 2, 1, 16, 8, 1, 1,
+                       "a1", "r2", "st_e0", "d2e", "d1e", "r1", None, None, None, 0.5),
+    "enc_conv3": Layer("image_encoder.features.5.weight", False, 128, 256, 4, 2, 1, 8, 4, 1, 1,
+                       "a2", "r3", "st_e1", "d3e", "d2e", "r2", "aff_e0", "mr_e0", "red_e0", 0.5),
+    "enc_conv4": Layer("image_encoder.features.8.weight", False, 256, 512, 4, 2, 1, 4, 2, 1, 1,
+                       "a3", "r4", "st_e2", "dr4", "d3e", "r3", "aff_e1", "mr_e1", "red_e1", 0.5),
+    "dec_convT1": Layer("image_decoder.hallucinate.0.weight", True, 512, 256, 4, 2, 1, 2, 4, 3, 3,
+                        "au", "q1", "st_d0", "d1", "du", "u", None, None, None, 0.5),
+    "dec_convT2": Layer("image_decoder.hallucinate.3.weight", True, 256, 128, 4, 2, 1, 4, 8, 3, 3,
+                        "aq1", "q2", "st_d1", "d2", "d1", "q1", "aff_d0", "mr_d0", "red_d0", 0.5),
+    "dec_convT3": Layer("image_decoder.hallucinate.6.weight", True, 128, 64, 4, 2, 1, 8, 16, 3, 3,
+                        "aq2", "q3", "st_d2", "d3", "d2", "q2", "aff_d1", "mr_d1", "red_d1", 0.5),
+}
+# every workspace name mmvae_coco_debug_offset knows (csrc/coco.hip)
+WS_NAMES_COCO = ("patches1 r1 r2 r3 r4 a1 a2 a3 a4 y1 ay1 y2 ay2 encout m1 m2 z_bf z_f32 u au q1 q2 q3 aq1 aq2 aq3 dlogit patches4 d3 d2 d1 "
+                 "du dz_img d_encout dy2 dy1 db4 dr4 d3e d2e d1e tmp_f32 slab sums st_e0 st_e1 st_e2 st_d0 st_d1 st_d2 red_e0 red_e1 red_e2 "
+                 "red_d0 red_d1 red_d2 aff_e0 aff_e1 aff_e2 aff_d0 aff_d1 aff_d2 mr_e0 mr_e1 mr_e2 mr_d0 mr_d1 mr_d2").split()
+LOSS_SLOTS = 32                 # MMVAE_LOSS_SLOTS (csrc/common.h): the loss sums are [LOSS_SLOTS][16] floats, column g of every slot row
 
 # every workspace name mmvae_mm_debug_offset knows (csrc/multimnist.hip): the end of a named buffer is bounded by the next of these
 WS_NAMES = ("patches1 r1 r2 r3 r4 y1 y2 encout txtout z_bf z_f32 u q1 q2 q3 logits dlogit d3 d2 d1 du dz_img dz_txt d_encout "
@@ -227,11 +256,13 @@ def describe_mismatch(got, ref, limit=6):
 # the library's defaults of the knobs the tests set, restored after every test: csrc/convres.hip try_launch_convres ("convres" 1,
 # "convres_alt" 0), csrc/wgrad_ring.hip try_launch_wgrad_ring ("wgrad_ring" 1), try_wr ("wr_pair" 0, "wr_atomic_kb" 256) -- a changed
 # default there must be changed here (and in tests/test_gpu_wgrad_ring.py)
-# (celeba_layer_mask: csrc/celeba.hip named_gemm, the keep mask of the replayed classifier layers)
-KNOB_DEFAULTS = {"convres": 1, "convres_alt": 0, "wgrad_ring": 1, "wr_atomic_kb": 256, "wr_pair": 0, "celeba_layer_mask": 0}
+# (celeba_layer_mask / coco_layer_mask: csrc/celeba.hip / csrc/coco.hip named_gemm, the keep masks of the replayed classifier layers)
+KNOB_DEFAULTS = {"convres": 1, "convres_alt": 0, "wgrad_ring": 1, "wr_atomic_kb": 256, "wr_pair": 0, "celeba_layer_mask": 0,
+                 "coco_layer_mask": 0}
 # (B, layer, knobs, [(tag, kernel)]) of every launch a harness of the family made in this process: what its coverage test reads
 RECORDS = []
 RECORDS_CELEBA = []
+RECORDS_COCO = []
 
 
 class LayerHarness:
@@ -240,10 +271,10 @@ class LayerHarness:
     state_cls / engine_cls: the family's classes of multimodal_vae_amd.core (default: MultiMNIST); prefix: its mmvae_<prefix>_*
     entry points; ws_names: every name its debug_offset knows; workload: the family's synthetic batch of bench.py; records: the
     family's list of compared launches; n_latents: the latent size the plan is built at (the conv layers do not depend on it, the
-    dense layers around the latent do)."""
+    dense layers around the latent do); engine_args: what the engine's constructor takes behind (state, batch) -- COCO's sos."""
 
     def __init__(self, B, state_cls=None, engine_cls=None, prefix="mm", ws_names=None, workload="multimnist", records=None,
-                 n_latents=100):
+                 n_latents=100, engine_args=()):
         import multimodal_vae_amd  # noqa: F401
         from multimodal_vae_amd._lib import call
         from multimodal_vae_amd import core
@@ -258,7 +289,7 @@ class LayerHarness:
         self.st = (state_cls or core.MultimnistState)(n_latents, self.dev)
         default_init_(self.st, 1234)
         a, b = synthetic_batch_for(workload, B, 1234)
-        self.eng = (engine_cls or core.FusedELBOStep)(self.st, B)
+        self.eng = (engine_cls or core.FusedELBOStep)(self.st, B, *engine_args)
         self.eng(a.to(self.dev), b.to(self.dev))
         self.st.ensure_packed()
         torch.cuda.synchronize()
@@ -521,18 +552,20 @@ def gate_stage_colstats(L, ref, absterms, groups):
     return torch.stack([e.sum(1) + 2.0 ** -16 * v.abs().sum(1), (2 * v.abs() * e + e * e).sum(1) + 2.0 ** -16 * (v * v).sum(1)], -1)
 
 
-def staged_bwd_operands(L, nimg, groups, count, g):
+def staged_bwd_operands(L, nimg, groups, count, g, integer_slots=True):
     """Operands of a kind 2 launch on which every coefficient and every dr = g db + cb r + c2 (csrc/convres.hip) lies on the
     2^-7 grid below 64: exact in fp32, so the in-place bf16 store is the only rounding of dr and the data gradient's fp32
     accumulation of the stored values (multiples of 2^-8: rounding to 8 bits only coarsens the grid) is exact again.
     -> db ternary, r eighths [nimg][oh][oh][cout]; red [groups][STAT_SLOTS][cout][2] with slot sums count * m1, count * m2
-    (m1, m2 multiples of 1/4, spread unevenly over the slots); mr [groups][cout][2] dyadic; gamma [cout] in {1, 2, -1}"""
+    (m1, m2 multiples of 1/4, spread unevenly over the slots); mr [groups][cout][2] dyadic; gamma [cout] in {1, 2, -1}
+    integer_slots=False (the small COCO maps, count = 12 .. 48): the slot values are multiples of count / 64 instead of integers --
+    dyadic and of magnitude <= count, so still exact in fp32 (the caller asserts it)"""
     C = L.cout
     db = ternary((nimg, L.oh, L.oh, C), G_DENSITY, g)
     r = eighths((nimg, L.oh, L.oh, C), g)
     pick = lambda vals, shape: torch.tensor(vals, dtype=torch.float64)[torch.randint(0, len(vals), shape, generator=g)]
     m = pick([-1.0, -0.5, -0.25, 0.0, 0.25, 0.5, 1.0], (groups, C, 2))
-    assert count % 64 == 0, count            # every slot value count * (multiple of 1/64) is an integer
+    assert count % 64 == 0 or not integer_slots, count            # every slot value count * (multiple of 1/64) is an integer
     delta = torch.tensor([1.0, -1.0] * (STAT_SLOTS // 2), dtype=torch.float64)[None, :, None, None] / 64
     red = count * (m[:, None] / STAT_SLOTS + delta * torch.ones(groups, STAT_SLOTS, C, 2, dtype=torch.float64))
     mr = torch.stack([pick([-0.25, 0.0, 0.5], (groups, C)), pick([0.5, 1.0, 2.0], (groups, C))], -1)
@@ -559,3 +592,129 @@ def celeba_harness(B):
     """LayerHarness of the CelebA plan (csrc/celeba.hip celeba_bench_layer / celeba_debug_offset)"""
     from multimodal_vae_amd.core import CelebaState, FusedCelebaStep
     return LayerHarness(B, CelebaState, FusedCelebaStep, "celeba", WS_NAMES_CELEBA, "celeba", RECORDS_CELEBA)
+
+
+# ------------------------------------------------------------------------------------------------ COCO (tests/test_gpu_coco_layers.py)
+def coco_harness(B, n_latents=100):
+    """LayerHarness of the COCO plan (csrc/coco.hip coco_bench_layer / coco_debug_offset); default caption length: the one warm-up
+    step costs milliseconds"""
+    from multimodal_vae_amd.core import CocoState, FusedCocoStep
+    from bench import synthetic_sos
+    return LayerHarness(B, CocoState, FusedCocoStep, "coco", WS_NAMES_COCO, "coco", RECORDS_COCO, n_latents, (synthetic_sos(),))
+
+
+def patches_k4s2(img):
+    """im2col of [n][3][H][H] for a 4x4 / stride 2 / padding 1 window: [n * (H/2)^2][48], column (ky * 4 + kx) * 3 + channel
+    (csrc/elementwise.hip im2col_small_kernel; torch's unfold has the channel slowest), zeros where the window leaves the image"""
+    n, H = img.shape[0], img.shape[-1]
+    pix = (H // 2) ** 2
+    u = F.unfold(img, 4, padding=1, stride=2).reshape(n, 3, 16, pix)
+    return u.permute(0, 3, 2, 1).reshape(n * pix, 48).contiguous()
+
+
+def slot_stats_any(r, groups):
+    """slot_stats for any row count: the rows of a group dealt to the STAT_SLOTS slots in contiguous runs of near-equal length
+    (empty slots hold zeros).  Exact in fp32 under the same condition (eighths, at most 4096 rows per slot)."""
+    C = r.shape[-1]
+    o = r.double().reshape(groups, -1, C)
+    out = torch.zeros(groups, STAT_SLOTS, C, 2, dtype=torch.float64)
+    for q, part in enumerate(torch.tensor_split(o, STAT_SLOTS, dim=1)):
+        out[:, q, :, 0], out[:, q, :, 1] = part.sum(1), (part * part).sum(1)
+    return out
+
+
+BN_MOM32 = torch.tensor(0.1, dtype=torch.float32)           # csrc/plan_base.h BN_MOM as the fp32 value the kernel multiplies with
+BN_KEEP32 = torch.tensor(1.0, dtype=torch.float32) - BN_MOM32  # ... and its (1.f - momentum), rounded once in fp32
+
+
+def ref_bn_running(stats, count, rm0, rv0, updates):
+    """csrc/bn_dev.h bn_running_update in float64: groups in pass order, `updates` momentum steps per group towards the group's
+    mean and unbiased variance.  -> running_mean [C], running_var [C], max over groups of the unbiased variance [C]"""
+    s = stats.double().sum(1)
+    mean = s[..., 0] / count
+    var = (s[..., 1] / count - mean * mean).clamp_min(0)
+    unb = var * count / (count - 1.0)
+    rm, rv = rm0.double().clone(), rv0.double().clone()
+    keep, mom = float(BN_KEEP32), float(BN_MOM32)
+    for g in range(stats.shape[0]):
+        for _ in range(updates):
+            rm = keep * rm + mom * mean[g]
+            rv = keep * rv + mom * unb[g]
+    return rm, rv, unb.max(0).values
+
+
+def gate_bn_backward(db, r, red, mr, gamma, count, groups, ref):
+    """Gate of the stand-alone BatchNorm backward's dr.  When the count is a power of two 1 / count is exact and, on the operands
+    of staged_bwd_operands, so is every fp32 operation: one bf16 ulp, 2^-8 |ref| (the gate of the staged form).  Otherwise 1 / count
+    is rounded and 8 fp32 roundings (the reciprocal, the two means, the two of xhat, its product with m2, the two subtractions; the
+    products with gamma rstd are exact, both powers of two) each relative to at most T = |g| (|db| + |m1| + |xhat m2|) come on top."""
+    gate = 2.0 ** -8 * ref.abs()
+    if count & (count - 1):
+        C = db.shape[-1]
+        s = red.double().sum(1)
+        m1, m2 = s[..., 0] / count, s[..., 1] / count
+        xhat = (r.double().reshape(groups, -1, C) - mr[:, None, :, 0].double()) * mr[:, None, :, 1].double()
+        T = (gamma.double()[None] * mr[..., 1].double()).abs()[:, None] * (db.double().abs().reshape(groups, -1, C) + m1.abs()[:, None] + (xhat * m2[:, None]).abs())
+        gate = gate + 8 * EPS32 * T.reshape(ref.shape)
+    return gate
+
+
+# Last decoder layer (csrc/thin.hip convt_last_fwd_kernel): ConvTranspose2d(64, 3, 4, 2, 1) on bf16 operands with fp32 accumulation
+# (exact on ternary operands), then per logit l:  p = rcp(1 + exp(-l)) on the hardware transcendentals,  dlogit = coef[g] (p - t),
+# BCE term -(t max(log p, -100) + (1 - t) max(log(1 - p), -100)).  The gates below are multiples of one fp32 rounding (EPS32 = 2^-24)
+# of the result's magnitude, and of 2^-16 sum |terms| for the sums; the multiples are at most 4 times the worst error / unit ratio
+# measured against this float64 reference (docstring of tests/test_gpu_coco_layers.py): the reference defines the centre.
+LAST_RECON_MULT = 24           # measured 7.65
+LAST_DLOGIT_MULT = 24          # measured 6.81
+LAST_SUM_MULT = 1.0 / 64       # measured 0.0049
+LAST_X_DENSITY, LAST_W_DENSITY = 0.125, 0.125      # logit variance 4 taps x 64 channels / 64 = 4: |l| <= 8 is 4 sigma
+LAST_TARGETS = (0.3125, 0.375, 0.625, 0.6875)      # exact in fp32; sigmoid(integer) stays >= 0.04 away from each: p - t does not cancel
+
+
+def last_layer_coef(B):
+    """the fp32 loss weights of the replay: (1, 1/2, 0) / (B * 3072), one fp32 division each"""
+    lam = torch.tensor([1.0, 0.5, 0.0], dtype=torch.float32)
+    return (lam / torch.tensor(float(B * 3072), dtype=torch.float32)).double()
+
+
+def ref_dec_last(a3, w9, target, coef):
+    """a3 [3B][16][16][64] NHWC, w9 (64, 3, 4, 4), target [B][3][32][32], coef [3] -> float64 logits, recon, dlogit (NCHW
+    [3B][3][32][32]), BCE sums [3] and their sums of |terms| [3]"""
+    G = 3
+    logits = F.conv_transpose2d(_nchw(a3.double()), w9.double(), None, 2, 1)
+    p = torch.sigmoid(logits)
+    t = target.double().repeat(G, 1, 1, 1)
+    dlogit = coef.double().repeat_interleave(logits.shape[0] // G)[:, None, None, None] * (p - t)
+    lp = F.logsigmoid(logits).clamp_min(-100.0)
+    lq = F.logsigmoid(-logits).clamp_min(-100.0)
+    terms = -(t * lp + (1 - t) * lq)
+    tg = terms.reshape(G, -1)
+    return logits, p, dlogit, tg.sum(1), tg.abs().sum(1)
+
+
+def assert_last_layer_regime(logits):
+    """integer logits, at least 90 % of them in |l| <= 8 (where a logit off by 1 moves the sigmoid by more than 3e-4) and none
+    beyond 14: there fp32 still resolves 1 - p = 8e-7 to 3 bits and neither BCE log reaches its clamp"""
+    assert bool((logits == logits.round()).all())
+    assert float((logits.abs() <= 8).double().mean()) >= 0.9, float((logits.abs() <= 8).double().mean())
+    assert float(logits.abs().max()) <= 14, float(logits.abs().max())
+
+
+def gate_last_layer(got, ref, mult, what, extra=""):
+    """|got - ref| <= mult * 2^-24 * |ref| per element"""
+    got = got.double().cpu()
+    err, unit = (got - ref).abs(), EPS32 * ref.abs()
+    if REPORT:
+        nz = unit > 0
+        print("LAST %s: worst err/(2^-24 |ref|) %.3f (gate %g)" % (what, float((err[nz] / unit[nz]).max()) if bool(nz.any()) else 0.0, mult))
+    bad = ~(err <= mult * unit)
+    assert not bool(bad.any()), (what, extra, "%d of %d outside the gate; first %s got %s want %s" % (
+        int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), ref[bad][:6].tolist()))
+
+
+def gate_last_sums(got, ref, mag, what, extra=""):
+    """|got - ref| <= LAST_SUM_MULT * 2^-16 sum |terms|"""
+    err, unit = (got.double().cpu() - ref).abs(), 2.0 ** -16 * mag
+    if REPORT:
+        print("LAST %s: sums worst err/(2^-16 sum|terms|) %.4f (gate %g)" % (what, float((err / unit.clamp_min(1e-30)).max()), LAST_SUM_MULT))
+    assert bool((err <= LAST_SUM_MULT * unit).all()), (what, extra, got.tolist(), ref.tolist())

@@ -1,4 +1,4 @@
-"""CPU companion of tests/test_gpu_layers.py and tests/test_gpu_celeba_layers.py: the float64 layer reference (tests/layer_ref.py) the GPU test trusts is tied to the
+"""CPU companion of tests/test_gpu_layers.py, tests/test_gpu_celeba_layers.py and tests/test_gpu_coco_layers.py: the float64 layer reference (tests/layer_ref.py) the GPU test trusts is tied to the
 model definition in oracle/mmvae_ref.py, and its operand generator stays inside the regime where bf16 operands with fp32
 accumulation reproduce float64 bit for bit."""
 import pytest
@@ -34,7 +34,8 @@ class _Recorder:
     """stands in for torch.nn.functional inside the oracle module: records every conv / transposed conv call"""
 
     def __init__(self):
-        self.calls = []
+        self.calls = []             # conv / transposed conv calls
+        self.order = []             # ... and the Linear calls, in call order
 
     def __getattr__(self, name):
         return getattr(F, name)
@@ -44,6 +45,7 @@ class _Recorder:
         out = fn(x, w, b, stride, pad)
         out.retain_grad()
         self.calls.append(dict(transposed=transposed, x=x, w=w, out=out, stride=stride, pad=pad))
+        self.order.append(self.calls[-1])
         return out
 
     def conv2d(self, x, w, b, stride, pad):
@@ -51,6 +53,14 @@ class _Recorder:
 
     def conv_transpose2d(self, x, w, b, stride, pad):
         return self._rec(F.conv_transpose2d, True, x, w, b, stride, pad)
+
+    def linear(self, x, w, b=None):
+        if x.requires_grad:
+            x.retain_grad()
+        out = F.linear(x, w, b)
+        out.retain_grad()
+        self.order.append(dict(linear=True, x=x, w=w, out=out))
+        return out
 
 
 def test_reference_agrees_with_autograd_on_the_oracle_modules(monkeypatch):
@@ -182,6 +192,8 @@ class _SimHarness:
       "tap"   : the engine ignores tap (ky, kx) = (1, 2) of the weights
       "image" : the engine drops the middle image of the launch (its operand reads as zero)
       "tile"  : 16 result columns (channels 16..31) land shifted by one channel
+      "border": the border mask is wrong at one pixel: the top right pixel of the last image's operand reads as zero
+      "slice" : the first two channel slices of the weights (dimension 0 of the parameter) sit in each other's place
     LR.check_forward / check_wgrad / check_dgrad run against it unchanged: they must pass without a fault and fail with each."""
 
     class _Gpk:
@@ -256,11 +268,16 @@ class _SimHarness:
         if w is not None and self.fault == "tap":
             w = w.clone()
             w[:, :, 1, 2] = 0
-        drop = self.fault == "image"
+        if w is not None and self.fault == "slice":
+            w = w.clone()
+            w[[0, 1]] = w[[1, 0]]
+        drop, border = self.fault == "image", self.fault == "border"
         if layer == base:
             x = self._operand(L.x, L, L.ih, L.cin).clone()
             if drop:
                 x[x.shape[0] // 2] = 0
+            if border:
+                x[-1, 0, -1] = 0
             out = self._shift(LR.ref_forward(L, x, w), 3)
             self.bufs[L.out] = out.to(torch.bfloat16).reshape(-1)
             self._table(L.stats, LR.ref_colstats(out, L.gf))
@@ -268,14 +285,20 @@ class _SimHarness:
             x, dy = self._operand(L.x, L, L.ih, L.cin).clone(), self._operand(L.dy, L, L.oh, L.cout)
             if drop:
                 x[x.shape[0] // 2] = 0
+            if border:
+                x[-1, 0, -1] = 0
             dw = LR.ref_wgrad(L, x, dy)
             if self.fault == "tap":
                 dw[:, :, 1, 2] = 0
+            if self.fault == "slice":
+                dw[[0, 1]] = dw[[1, 0]]
             self.grads[L.param] = self._shift(dw, 1 if L.transposed else 0)
         else:
             dy = self._operand(L.dy, L, L.oh, L.cout).clone()
             if drop:
                 dy[dy.shape[0] // 2] = 0
+            if border:
+                dy[-1, 0, -1] = 0
             acc = self._shift(LR.ref_dgrad_acc(L, dy, w), 3)
             r = self._operand(L.r, L, L.ih, L.cin)
             aff = self.bufs[L.aff].double().reshape(L.gb, L.cin, 2) if L.aff else None
@@ -288,7 +311,9 @@ class _SimHarness:
 
 
 FAULTS = ("tap", "image", "tile")
-_FAMILIES = {"multimnist": LR.LAYERS, "celeba": LR.LAYERS_CELEBA}
+FAULTS_COCO = FAULTS + ("border", "slice")
+_FAMILIES = {"multimnist": LR.LAYERS, "celeba": LR.LAYERS_CELEBA, "coco": LR.LAYERS_COCO}
+_FAMILY_FAULTS = {"multimnist": FAULTS, "celeba": FAULTS, "coco": FAULTS_COCO}
 
 
 def _run_checks(h, layers, name, B, seed=0):
@@ -322,7 +347,7 @@ def test_checks_pass_on_the_reference_and_see_every_fault(family):
     layers = _FAMILIES[family]
     for name in layers:
         assert _run_checks(_SimHarness(layers), layers, name, 4) == set(), name
-        for fault in FAULTS:
+        for fault in _FAMILY_FAULTS[family]:
             assert _run_checks(_SimHarness(layers, fault), layers, name, 4) == {"forward", "wgrad", "dgrad"}, (name, fault)
 
 
@@ -331,7 +356,16 @@ def test_sum_gates_see_every_fault(fault):
     """The 2^-16 gate of the BatchNorm-backward sums alone (check_dgrad stops at the per-element gate first), on the data gradient of
     every CelebA layer geometry (with tables, whether or not the step's layer has a BatchNorm below it): the sums of a faulty
     launch fall outside, those of the reference inside."""
-    layers = LR.LAYERS_CELEBA
+    _sum_gates(LR.LAYERS_CELEBA, fault)
+
+
+@pytest.mark.parametrize("fault", FAULTS_COCO)
+def test_coco_sum_gates_see_every_fault(fault):
+    """the same on every COCO layer geometry, with the two faults of the small maps (border pixel, channel slice) on top"""
+    _sum_gates(LR.LAYERS_COCO, fault)
+
+
+def _sum_gates(layers, fault):
     for name, L in layers.items():
         _, w, dy = LR.layer_operands(name, L.gb * 4, 0, layers)
         g = LR.gen(0, 4, 4)
@@ -525,3 +559,256 @@ def test_dense_gates_see_every_fault(fault):
         LR.gate_elements(vf.to(torch.bfloat16), v, acc, "fc2_dgrad")
     with pytest.raises(AssertionError):
         LR.gate_sums(vf.sum(0), v.sum(0), v.abs().sum(0), "fc2_dgrad")
+
+
+# ------------------------------------------------------------------------------------------------ COCO
+def _coco_cases():
+    """every (batch, seed) tests/test_gpu_coco_layers.py uses: both seeds at the small batches, the first at the large ones"""
+    return [(B, seed) for B in LR.BATCHES_COCO for seed in (LR.SEEDS if B <= 8 else LR.SEEDS[:1])]
+
+
+@pytest.mark.parametrize("name", list(LR.LAYERS_COCO))
+def test_coco_operands_stay_in_the_exact_regime(name):
+    """forward on gf * B images, both gradients on gb * B images, for every (batch, seed) of the GPU module"""
+    L = LR.LAYERS_COCO[name]
+    assert L.gf == L.gb
+    for B, seed in _coco_cases():
+        x, w, dy = LR.layer_operands(name, L.gf * B, seed, LR.LAYERS_COCO)
+        out = LR.ref_forward(L, x, w)
+        LR.assert_exact_regime(out=out, groups=L.gf, what="%s forward B=%d seed %d" % (name, B, seed))
+        assert float(out.abs().max()) > 0
+        LR.assert_exact_regime(dw=LR.ref_wgrad(L, x, dy), what="%s wgrad B=%d seed %d" % (name, B, seed))
+        acc = LR.ref_dgrad_acc(L, dy, w)
+        assert bool((acc == acc.round()).all()) and float(acc.abs().max()) <= 256, (name, B, seed, float(acc.abs().max()))
+    ws, xs = zip(*[LR.layer_operands(name, L.gf * 8, seed, LR.LAYERS_COCO)[1::-1] for seed in LR.SEEDS])
+    LR.assert_operand_coverage(list(ws), list(xs))
+
+
+def test_coco_pass_operands_stay_in_their_regimes():
+    """the operands of the stand-alone passes and of the last layer at the smallest and the largest batch of the GPU module: the
+    written statistics are exact in fp32, and the last layer's logits are integers with at least 90 % in |l| <= 8, none beyond 14"""
+    for B in (min(LR.BATCHES_COCO), max(LR.BATCHES_COCO)):
+        for name, L in LR.LAYERS_COCO.items():
+            g = LR.gen(0, 1, 16, L.gf * B)
+            stats = LR.slot_stats_any(LR.eighths((L.gf * B, L.oh, L.oh, 8), g), L.gf)
+            assert torch.equal(stats.float().double(), stats), (name, B)
+            red = LR.staged_bwd_operands(L._replace(cout=8), L.gb * B, L.gb, B * L.oh * L.oh, g, integer_slots=False)[2]
+            assert torch.equal(red.float().double(), red), (name, B)
+        for seed in LR.SEEDS:
+            g = LR.gen(seed, 21, B)
+            a3 = LR.ternary((3 * B, 16, 16, 64), LR.LAST_X_DENSITY, g)
+            w9 = LR.ternary((64, 3, 4, 4), LR.LAST_W_DENSITY, g)
+            LR.assert_last_layer_regime(F.conv_transpose2d(LR._nchw(a3), w9, None, 2, 1))
+    # slot_stats_any is slot_stats where the rows divide evenly
+    r = LR.eighths((3 * 4, 8, 8, 16), LR.gen(0, 2))
+    assert torch.equal(LR.slot_stats_any(r, 3), LR.slot_stats(r, 3))
+
+
+def test_coco_references_agree_with_autograd_on_the_oracle_modules(monkeypatch):
+    """oracle.mmvae_ref's COCO image encoder and decoder in float64 with autograd, every conv and Linear call recorded:
+    LAYERS_COCO's geometry reproduces each conv's output, weight gradient and input gradient; ref_bn_tables + ref_stage_fwd
+    reproduce the tensor the next module reads (for features.9 through the NCHW flatten c * 4 + y * 2 + x, for upsample.0 through
+    the NHWC map the engine writes); ref_dgrad_epilogue + ref_bn_backward reproduce the gradient at the conv's raw output and the
+    BatchNorm parameter gradients from the gradient at that next module's input; ref_dec_last reproduces the decoder's output."""
+    from test_gpu_coco_layers import BN_PASSES, _flat_nchw, _map_nhwc
+    torch.manual_seed(0)
+    B = 3
+    P = {k: (v.double().requires_grad_(True) if v.is_floating_point() and "running" not in k else v.double() if v.is_floating_point() else v)
+         for k, v in R.formula_params("coco", 100).items()}
+    rec = _Recorder()
+    monkeypatch.setattr(R, "F", rec)
+    image = torch.rand(B, 3, 32, 32, dtype=torch.float64).requires_grad_(True)
+    z = torch.randn(B, 100, dtype=torch.float64)
+    enc = R.coco_image_encoder(P, image * 1.0, True, None, drop_p=0.0)
+    dec = R.coco_image_decoder(P, z, True)
+    ((enc * torch.randn_like(enc)).sum() + (dec * torch.randn_like(dec)).sum()).backward()
+    monkeypatch.undo()
+    assert len(rec.calls) == 8 and len(rec.order) == 12
+    by_weight = {id(c["w"]): c for c in rec.order}
+    after = {id(c["w"]): rec.order[i + 1] for i, c in enumerate(rec.order[:-1])}       # the module that reads a call's result
+    # (float64 through two different formulas of the BatchNorm backward: cancellation leaves 1e-10 absolute)
+    close = lambda a, b: torch.testing.assert_close(a, b, rtol=1e-7, atol=1e-9)
+    for name, L in LR.LAYERS_COCO.items():
+        c = by_weight[id(P[L.param])]
+        assert c["transposed"] == L.transposed and c["stride"] == L.stride and c["pad"] == L.pad, name
+        assert tuple(c["w"].shape) == LR.weight_shape(L), name
+        x, dy = LR._nhwc(c["x"].detach()), LR._nhwc(c["out"].grad)
+        assert tuple(x.shape) == (B, L.ih, L.ih, L.cin) and tuple(dy.shape) == (B, L.oh, L.oh, L.cout), name
+        w = c["w"].detach()
+        torch.testing.assert_close(LR.ref_forward(L, x, w), LR._nhwc(c["out"].detach()), rtol=1e-12, atol=1e-12)
+        torch.testing.assert_close(LR.ref_wgrad(L, x, dy), c["w"].grad, rtol=1e-10, atol=1e-12)
+        torch.testing.assert_close(LR.ref_dgrad_acc(L, dy, w), LR._nhwc(c["x"].grad), rtol=1e-10, atol=1e-12)
+        # the BatchNorm + Swish behind it, forward and backward (one group: the oracle runs one pass)
+        bn = [v[1] for v in BN_PASSES.values() if v[0] == name][0]
+        gamma, beta = P[bn + ".weight"].detach(), P[bn + ".bias"].detach()
+        r, count = LR._nhwc(c["out"].detach()), B * L.oh * L.oh
+        scale, shift, mean, rstd = LR.ref_bn_tables(LR.slot_stats_any(r, 1), count, gamma, beta)
+        a, _ = LR.ref_stage_fwd(r, scale, shift, 1)
+        nxt = after[id(c["w"])]
+        if "linear" in nxt:                              # features.9 -> classifier.0: torch's flatten of (512, 2, 2)
+            close(_flat_nchw(a), nxt["x"].detach())
+            da = LR._nhwc(nxt["x"].grad.reshape(B, 512, 2, 2))
+        else:
+            close(a, LR._nhwc(nxt["x"].detach()))
+            da = LR._nhwc(nxt["x"].grad)
+        aff, mr = torch.stack([scale, shift], -1), torch.stack([mean, rstd], -1)
+        db, red, _ = LR.ref_dgrad_epilogue(da, r, aff, mr, 1)
+        table = torch.zeros(1, LR.STAT_SLOTS, L.cout, 2, dtype=torch.float64)
+        table[:, 5] = red
+        dr, dgamma, dbeta, _, _ = LR.ref_bn_backward(db, r, table, mr, gamma, count, 1)
+        close(dr, dy)
+        close(dgamma, P[bn + ".weight"].grad)
+        close(dbeta, P[bn + ".bias"].grad)
+    # upsample.0: the engine's NHWC columns s * 512 + c of Linear(D, 2048) are what hallucinate.0 reads
+    up = by_weight[id(P["image_decoder.upsample.0.weight"])]
+    u = _map_nhwc(up["out"].detach())
+    close(u * torch.sigmoid(u), LR._nhwc(after[id(up["w"])]["x"].detach()))
+    # last layer: logits -> sigmoid is the decoder's output; dlogit is autograd's gradient of sum_g coef[g] * BCE_g
+    last = by_weight[id(P["image_decoder.hallucinate.9.weight"])]
+    a3 = LR._nhwc(last["x"].detach()).repeat(3, 1, 1, 1)
+    target = torch.rand(B, 3, 32, 32, dtype=torch.float64)
+    coef = torch.tensor([0.7, 0.2, 0.0], dtype=torch.float64)
+    logits, recon, dlogit, sums, mags = LR.ref_dec_last(a3, last["w"].detach(), target, coef)
+    close(recon[:B], dec.detach())
+    lg = logits.clone().requires_grad_(True)
+    per = F.binary_cross_entropy(torch.sigmoid(lg), target.repeat(3, 1, 1, 1), reduction="none").reshape(3, -1).sum(1)
+    close(per.detach(), sums)
+    (per * coef).sum().backward()
+    close(lg.grad, dlogit)
+
+
+def test_coco_pass_gates_pass_on_the_reference_and_see_every_fault():
+    """The gates of the stand-alone passes and of the last layer, on values stored the way the engine stores them (bf16 / fp32):
+    they pass on the reference and fail on a reference with one group's table used for another, db2 ignored, one border pixel of
+    the im2col wrong, and -- last layer -- one tap dropped, one channel slice swapped, one border logit off by one, one group's
+    loss weight used for another."""
+    from test_gpu_coco_layers import _within
+    B = 4
+    # ---- BatchNorm forward (3 groups): tables of group g + 1 used for group g
+    L = LR.LAYERS_COCO["dec_convT2"]
+    G, C, count = 3, L.cout, B * L.oh * L.oh
+    g = LR.gen(0, 31)
+    r = LR.eighths((G * B, L.oh, L.oh, C), g)
+    r[B:2 * B] = (r[B:2 * B] / 2 + 1).mul(8).round() / 8          # the groups differ in mean and variance, as passes do
+    gamma = torch.tensor([1.0, 2.0, -1.0])[torch.randint(0, 3, (C,), generator=g)].double()
+    beta = torch.randint(-1, 2, (C,), generator=g).double()
+    scale, shift, mean, rstd = LR.ref_bn_tables(LR.slot_stats_any(r, G), count, gamma, beta)
+    a, _ = LR.ref_stage_fwd(r, scale, shift, G)
+    gate = LR.gate_stage_fwd(r, scale, shift, mean, beta, a, G)
+    _within(a.to(torch.bfloat16), a, gate, "bn forward")
+    wrong, _ = LR.ref_stage_fwd(r, scale.roll(1, 0), shift.roll(1, 0), G)
+    with pytest.raises(AssertionError):
+        _within(wrong.to(torch.bfloat16), a, gate, "bn forward, tables of another group")
+    rm, rv, unb = LR.ref_bn_running(LR.slot_stats_any(r, G), count, torch.zeros(C), torch.ones(C), 1)
+    rm1, rv1, _ = LR.ref_bn_running(LR.slot_stats_any(r, G)[:2], count, torch.zeros(C), torch.ones(C), 1)
+    gm, gv = (16 + 15) * LR.EPS32 * 4 * torch.ones_like(rm), (22 + 15) * LR.EPS32 * torch.maximum(unb, torch.ones(C).double())
+    _within(rm.float(), rm, gm, "running mean")
+    _within(rv.float(), rv, gv, "running variance")
+    with pytest.raises(AssertionError):
+        _within(rm1.float(), rm, gm, "running mean, one group's update missing")
+    with pytest.raises(AssertionError):
+        _within(rv1.float(), rv, gv, "running variance, one group's update missing")
+    # ---- BatchNorm backward: another group's (mean, rstd); enc_bn4_bwd with db2 ignored; at a power-of-two count and at count 12
+    for Ln, Bn in (("dec_convT2", 4), ("enc_conv4", 4), ("enc_conv4", 3)):
+        L = LR.LAYERS_COCO[Ln]
+        G, count = L.gb, Bn * L.oh * L.oh
+        db, r, red, mr, gamma = LR.staged_bwd_operands(L, G * Bn, G, count, g, integer_slots=False)
+        db2 = LR.ternary(db.shape, LR.G_DENSITY, g) if G == 1 else torch.zeros_like(db)
+        dr, dgamma, dbeta, mag_g, mag_b = LR.ref_bn_backward(db + db2, r, red, mr, gamma, count, G)
+        gate = LR.gate_bn_backward(db + db2, r, red, mr, gamma, count, G, dr)
+        _within(dr.to(torch.bfloat16), dr, gate, "bn backward")
+        if G == 1:
+            bad = LR.ref_bn_backward(db, r, red, mr, gamma, count, G)[0]
+        else:
+            bad = LR.ref_bn_backward(db, r, red.roll(1, 0), mr.roll(1, 0), gamma, count, G)[0]
+        with pytest.raises(AssertionError):
+            _within(bad.to(torch.bfloat16), dr, gate, "bn backward, db2 ignored / another group's tables")
+        LR.gate_sums(dgamma.float(), dgamma, mag_g, "dgamma")
+        with pytest.raises(AssertionError):
+            LR.gate_sums(LR.ref_bn_backward(db, r, red[:, 1:], mr, gamma, count, G)[1], dgamma, mag_g, "dgamma, one slot missing")
+    # ---- im2col: the comparison is equality; a border pixel that is not zeroed differs
+    dl = LR.eighths((2, 3, 32, 32), g)
+    dl[dl == 0] = 0.125
+    want = LR.patches_k4s2(dl)
+    assert float(want[0, 0]) == 0.0 and float(want[0, 5 * 3]) == float(dl[0, 0, 0, 0])      # row (0, 0): tap (0, 0) outside, tap (1, 1) = pixel (0, 0)
+    assert tuple(want.shape) == (2 * 256, 48)
+    # ---- last layer
+    a3 = LR.ternary((3 * B, 16, 16, 64), LR.LAST_X_DENSITY, g)
+    w9 = LR.ternary((64, 3, 4, 4), LR.LAST_W_DENSITY, g)
+    target = torch.tensor(LR.LAST_TARGETS, dtype=torch.float64)[torch.randint(0, 4, (B, 3, 32, 32), generator=g)]
+    coef = LR.last_layer_coef(B)
+    logits, recon, dlogit, sums, mags = LR.ref_dec_last(a3, w9, target, coef)
+    LR.check_exact(logits.float(), logits, "logits")
+    LR.gate_last_layer(recon.float(), recon, LR.LAST_RECON_MULT, "recon")
+    LR.gate_last_layer(dlogit.float(), dlogit, LR.LAST_DLOGIT_MULT, "dlogit")
+    LR.gate_last_sums(sums.float(), sums, mags, "BCE sums")
+    w_tap, w_slice, a_border = w9.clone(), w9.clone(), a3.clone()
+    w_tap[:, :, 1, 2] = 0
+    w_slice[[0, 1]] = w_slice[[1, 0]]
+    a_border[0, 0, -1] = 0               # (an image of the first group: the last group's loss weight is 0)
+    for what, args in (("tap", (a3, w_tap, target, coef)), ("slice", (a3, w_slice, target, coef)), ("border", (a_border, w9, target, coef)),
+                       ("coef", (a3, w9, target, coef.roll(1)))):
+        lo, re_, dl_, su, _ = LR.ref_dec_last(*args)
+        if what != "coef":
+            with pytest.raises(AssertionError):
+                LR.check_exact(lo.float(), logits, "logits " + what)
+            with pytest.raises(AssertionError):
+                LR.gate_last_layer(re_.float(), recon, LR.LAST_RECON_MULT, "recon " + what)
+        with pytest.raises(AssertionError):
+            LR.gate_last_layer(dl_.float(), dlogit, LR.LAST_DLOGIT_MULT, "dlogit " + what)
+        if what in ("tap", "slice"):
+            with pytest.raises(AssertionError):
+                LR.gate_last_sums(su.float(), sums, mags, "BCE sums " + what)
+    # one logit off by one: the elementwise gates see it, and so does the sum of its group
+    off = logits.clone()
+    off[0, 0, 0, 31] += 1
+    p_off = torch.sigmoid(off)
+    assert float((p_off - recon).abs().max()) > 3e-4 or float(logits[0, 0, 0, 31].abs()) > 8
+    with pytest.raises(AssertionError):
+        LR.gate_last_layer(p_off.float(), recon, LR.LAST_RECON_MULT, "recon, one logit off by one")
+
+
+@pytest.mark.parametrize("fault", ["column", "row", "tile"])
+def test_coco_dense_gates_see_every_fault(fault):
+    """The comparisons tests/test_gpu_coco_layers.py makes on the dense layers, at its densities and B = 4, against the float64
+    reference with one input column ignored, one row dropped or one tile of 16 output columns shifted: classifier.0 / .3 / .6 and
+    upsample.0 forward (exact pre-activation, gated Swish copy), classifier.6's and classifier.3's data gradients with their column
+    sums.  Every comparison fails on the fault and passes on the unharmed reference."""
+    B, D, HID1, HID2, FEAT = 4, 100, 1024, 256, 2048
+    g = LR.gen(0, 13, B)
+    tern = lambda shape, d: LR.ternary(shape, d, g)
+    ib = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
+
+    def linear(x, W, b=None):
+        x, W = x.clone(), W.clone()
+        if fault == "column":
+            W[:, int(torch.nonzero(x.abs().sum(0))[0])] = 0
+        if fault == "row":
+            x[x.shape[0] // 2] = 0
+        y = F.linear(x, W, b)
+        if fault == "tile":
+            y[:, 16:32] = torch.roll(y[:, 16:32], 1, 1)
+        return y
+
+    for x, W, b, limit in ((tern((2 * B, FEAT), 0.25), tern((HID1, FEAT), 0.25), ib(HID1), 256), (tern((2 * B, HID1), 0.25), tern((HID2, HID1), 0.25), ib(HID2), 256),
+                           (tern((2 * B, HID2), 0.5), tern((2 * D, HID2), 0.25), ib(2 * D), 2 ** 24), (tern((3 * B, D), 0.5), tern((FEAT, D), 0.25), ib(FEAT), 256)):
+        y = F.linear(x, W, b)
+        LR.check_exact(y.to(torch.bfloat16) if limit == 256 else y.float(), y, "dense", limit)
+        sw = y * torch.sigmoid(y)
+        LR.gate_elements(sw.to(torch.bfloat16), sw, y, "dense")
+        yf = linear(x, W, b)
+        with pytest.raises(AssertionError):
+            LR.check_exact(yf.to(torch.bfloat16) if limit == 256 else yf.float(), y, "dense", limit)
+        with pytest.raises(AssertionError):
+            LR.gate_elements((yf * torch.sigmoid(yf)).to(torch.bfloat16), sw, y, "dense")
+    for de, W, r in ((tern((2 * B, 2 * D), 0.5), tern((2 * D, HID2), 0.25), LR.eighths((2 * B, HID2), g)),
+                     (tern((2 * B, HID2), 0.5), tern((HID2, HID1), 0.25), LR.eighths((2 * B, HID1), g))):
+        acc = de @ W
+        v = acc * LR.dswish(r)
+        LR.gate_elements(v.to(torch.bfloat16), v, acc, "dgrad")
+        LR.gate_sums(v.float().sum(0), v.sum(0), v.abs().sum(0), "dgrad")
+        vf = linear(de, W.t().contiguous()) * LR.dswish(r)
+        with pytest.raises(AssertionError):
+            LR.gate_elements(vf.to(torch.bfloat16), v, acc, "dgrad")
+        with pytest.raises(AssertionError):
+            LR.gate_sums(vf.sum(0), v.sum(0), v.abs().sum(0), "dgrad")

@@ -16,9 +16,10 @@ Batch sizes are read off the dispatch (csrc/convres.hip try_launch_convres, csrc
 from the probe's records that every instantiation reachable with default knobs ran in a compared launch.
 
 The layer launches are the plain forms (GemmParams::tr kind 0).  What stays with the whole-step tests: the staged forms of the
-fused step (kinds 1 and 2), dec_last_fused, conv1.hip's in-step form, the fused classifier tail (mlp_tail.hip)
-and the COCO plan (no bench_layer); the text kernels have a module of their own, tests/test_gpu_text_modules.py.  The CelebA plan has its own modules: tests/test_gpu_celeba_layers.py and
-tests/test_gpu_celeba_layers_staged.py (mmvae_celeba_bench_layer)."""
+fused step (kinds 1 and 2), dec_last_fused, conv1.hip's in-step form and the fused classifier tail (mlp_tail.hip); the text kernels
+have a module of their own, tests/test_gpu_text_modules.py.  The CelebA plan has its own modules, tests/test_gpu_celeba_layers.py and
+tests/test_gpu_celeba_layers_staged.py (mmvae_celeba_bench_layer), and so has the COCO plan: tests/test_gpu_coco_layers.py
+(mmvae_coco_bench_layer: its conv and dense layers and its stand-alone passes)."""
 import pytest
 import torch
 import torch.nn.functional as F
