@@ -767,6 +767,30 @@ int mmvae_mmgen_generate(const unsigned char* digits, const long long* digit_lab
 int mmvae_mmgen_render(const unsigned char* digits, int n_digits, const void* tables, const int* params, int n,
                        unsigned char* images_u8_or_null, float* images_f32_or_null, int* overflow, void* stream);
 
+/* Scale(S) + CenterCrop(S) + ToTensor of a ragged batch of decoded RGB images (celeba/train.py:102-104, coco/train.py:107-112;
+ * csrc/imgprep.h, csrc/imgprep_core.h): torchvision's Scale / CenterCrop of that era over Pillow's 8-bit BILINEAR resample, bit for
+ * bit, in integer arithmetic.  csrc/imgprep_core.h states the scaled size, the coefficients (2^22 fixed point, float64 without fused
+ * multiply-add), the crop offsets and the limits.  One workgroup per image, no atomics: two calls give identical bits and an
+ * image's result does not depend on the batch it is in.
+ * geometry: the input sides the kernel takes (1 .. max_side), the output sides (1 .. max_out), and 22.
+ * layout (host): for one image the scaled size (ow, oh) and the crop offsets (x1, y1).
+ * coeffs (host, needs no GPU): for the axis n_in -> n_out and the output indices first .. first + count - 1 the first tap, the tap
+ *   count and the int32 coefficients, `stride` per index, zeros past the count; MMVAE_EINVAL when an index has more taps than stride.
+ *   The SAME functions as the kernel's, compiled for the host: what a test checks here is what the device computes.
+ * scale_crop: pixels: device, the images back to back or not, image i = 3 heights[i] widths[i] bytes (HWC) from byte offsets[i];
+ *   pixels_bytes: the bytes of `pixels` that may be read; offsets int64 [n], heights, widths int32 [n], status int32 [n]: device.
+ *   Outputs, device, planar: out_u8 [n][3][S][S] and / or out_f32 [n][3][S][S] = u8 / 255 (IEEE division), at least one of them.
+ *   The kernel itself refuses an image whose descriptor is unusable -- a side outside 1 .. max_side, offsets[i] < 0, or offsets[i] +
+ *   3 h w > pixels_bytes: nothing of it is read, its outputs are zeros and status[i] = -1; otherwise status[i] = 0.  Neighbours are
+ *   unaffected.  No byte outside [pixels, pixels + pixels_bytes) is read.
+ * Pointers, S and counts are checked before anything is launched (MMVAE_EINVAL); n = 0 launches nothing. */
+int mmvae_imgprep_geometry(int* max_side, int* max_out, int* precision_bits);
+int mmvae_imgprep_layout(int h, int w, int S, int* ow, int* oh, int* x1, int* y1);
+int mmvae_imgprep_coeffs(int n_in, int n_out, int first, int count, int stride, int* xmin, int* taps, int* coefs);
+int mmvae_imgprep_scale_crop(const unsigned char* pixels, long long pixels_bytes, const long long* offsets, const int* heights,
+                             const int* widths, int n, int S, unsigned char* out_u8_or_null, float* out_f32_or_null, int* status,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

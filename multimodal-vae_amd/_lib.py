@@ -277,6 +277,10 @@ SIGNATURES["mmvae_mmgen_table_bytes"] = (_LL, [])
 SIGNATURES["mmvae_mmgen_build_tables"] = (_I, [_P])
 SIGNATURES["mmvae_mmgen_generate"] = (_I, [_P, _P, _I, _P, _I, _I, _I, _ULL, _ULL, _I] + [_P] * 7)
 SIGNATURES["mmvae_mmgen_render"] = (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P])
+SIGNATURES["mmvae_imgprep_geometry"] = (_I, [C.POINTER(_I)] * 3)
+SIGNATURES["mmvae_imgprep_layout"] = (_I, [_I, _I, _I] + [C.POINTER(_I)] * 4)
+SIGNATURES["mmvae_imgprep_coeffs"] = (_I, [_I] * 5 + [_P] * 3)
+SIGNATURES["mmvae_imgprep_scale_crop"] = (_I, [_P, _LL, _P, _P, _P, _I, _I, _P, _P, _P, _P])
 _STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
 
 _lib = None

@@ -20,6 +20,44 @@ from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _
 N_ATTRS = 18          # celeba/datasets.py:26-28
 DROP_P = 0.1
 
+# the 40 columns of CelebA's Anno/list_attr_celeba.txt, in the file's order
+ATTR_NAMES = ('5_o_Clock_Shadow Arched_Eyebrows Attractive Bags_Under_Eyes Bald Bangs Big_Lips Big_Nose Black_Hair Blond_Hair Blurry '
+              'Brown_Hair Bushy_Eyebrows Chubby Double_Chin Eyeglasses Goatee Gray_Hair Heavy_Makeup High_Cheekbones Male '
+              'Mouth_Slightly_Open Mustache Narrow_Eyes No_Beard Oval_Face Pale_Skin Pointy_Nose Receding_Hairline Rosy_Cheeks Sideburns '
+              'Smiling Straight_Hair Wavy_Hair Wearing_Earrings Wearing_Hat Wearing_Lipstick Wearing_Necklace Wearing_Necktie '
+              'Young').split()
+ATTR_TO_IX_DICT = {name: ix for ix, name in enumerate(ATTR_NAMES)}
+IX_TO_ATTR_DICT = {ix: name for ix, name in enumerate(ATTR_NAMES)}
+# the 18 columns the model sees (celeba/datasets.py:26): Bald, Bangs, Black_Hair, Blond_Hair, Brown_Hair, Bushy_Eyebrows, Eyeglasses,
+# Gray_Hair, Heavy_Makeup, Male, Mouth_Slightly_Open, Mustache, Pale_Skin, Receding_Hairline, Smiling, Straight_Hair, Wavy_Hair,
+# Wearing_Hat
+ATTR_IX_TO_KEEP = [4, 5, 8, 9, 11, 12, 15, 17, 18, 20, 21, 22, 26, 28, 31, 32, 33, 35]
+assert len(ATTR_NAMES) == 40 and len(ATTR_IX_TO_KEEP) == N_ATTRS
+
+
+def tensor_to_attributes(tensor):
+    """celeba/datasets.py:100-113: an (18,) tensor of probabilities -> the names of the kept attributes above 0.5"""
+    tensor = torch.round(torch.as_tensor(tensor).detach().float().cpu().reshape(-1))
+    if tensor.numel() != N_ATTRS:
+        raise ValueError("tensor_to_attributes: %d values, need %d" % (tensor.numel(), N_ATTRS))
+    return [IX_TO_ATTR_DICT[ATTR_IX_TO_KEEP[i]] for i in range(N_ATTRS) if float(tensor[i]) > 0.5]
+
+
+def attrs_from_names(names):
+    """celeba/sample.py:44-48 (``fetch_celeba_attrs``) for one name, a comma-separated string or a list of names -> a (1, 18) float
+    tensor with those attributes set.  A name that is no CelebA attribute, or not one of the kept 18, is refused."""
+    if isinstance(names, str):
+        names = [v for v in names.split(',') if v]
+    attrs = torch.zeros(1, N_ATTRS)
+    for name in names:
+        if name not in ATTR_TO_IX_DICT:
+            raise ValueError("attrs_from_names: %r is not a CelebA attribute" % (name,))
+        if ATTR_TO_IX_DICT[name] not in ATTR_IX_TO_KEEP:
+            raise ValueError("attrs_from_names: %r is not one of the %d attributes the model keeps (%s)"
+                             % (name, N_ATTRS, ", ".join(IX_TO_ATTR_DICT[i] for i in ATTR_IX_TO_KEEP)))
+        attrs[0, ATTR_IX_TO_KEEP.index(ATTR_TO_IX_DICT[name])] = 1
+    return attrs
+
 
 def _prep(mod: nn.Module, prefix: str, x: torch.Tensor):
     core = _core_of(mod, prefix, CelebaState)

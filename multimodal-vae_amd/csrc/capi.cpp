@@ -14,6 +14,7 @@
 #include "head_nll.h"
 #include "conv4s2.h"
 #include "multimnist_gen.h"
+#include "imgprep.h"
 #include <cstring>
 #include <exception>
 
@@ -791,6 +792,47 @@ int mmvae_mmgen_render(const unsigned char* digits, int n_digits, const void* ta
     return guarded([&] {
         return launch_mmgen_render(digits, n_digits, static_cast<const int32_t*>(tables), params, n, images_u8, images_f32, overflow, S(st));
     });
+}
+
+// ---- Scale + CenterCrop + ToTensor of a ragged image batch (imgprep.h, imgprep_core.h)
+int mmvae_imgprep_geometry(int* max_side, int* max_out, int* precision_bits) {
+    MMVAE_REQUIRE(max_side && max_out && precision_bits, "imgprep_geometry: null argument");
+    *max_side = imgprep::MAX_SIDE; *max_out = imgprep::MAX_OUT; *precision_bits = imgprep::PRECISION_BITS;
+    return MMVAE_OK;
+}
+int mmvae_imgprep_layout(int h, int w, int S, int* ow, int* oh, int* x1, int* y1) {
+    MMVAE_REQUIRE(ow && oh && x1 && y1, "imgprep_layout: null argument");
+    MMVAE_REQUIRE(imgprep::sides_ok(h, w) && S >= 1 && S <= imgprep::MAX_OUT, "imgprep_layout: h = %d, w = %d (need 1..%d), S = %d (need 1..%d)", h, w,
+                  (int)imgprep::MAX_SIDE, S, (int)imgprep::MAX_OUT);
+    imgprep::scaled_size(w, h, S, ow, oh);
+    *x1 = imgprep::crop_offset(*ow - S); *y1 = imgprep::crop_offset(*oh - S);
+    return MMVAE_OK;
+}
+int mmvae_imgprep_coeffs(int n_in, int n_out, int first, int count, int stride, int* xmin, int* taps, int* coefs) {
+    MMVAE_REQUIRE(xmin && taps && coefs, "imgprep_coeffs: null argument");
+    MMVAE_REQUIRE(n_in >= 1 && n_in <= imgprep::MAX_SIDE && n_out >= 1 && first >= 0 && count >= 0 && first <= n_out - count && stride >= 1,
+                  "imgprep_coeffs: n_in = %d (need 1..%d), n_out = %d, indices %d .. %d + %d, stride %d", n_in, (int)imgprep::MAX_SIDE, n_out, first,
+                  first, count, stride);
+    for (int j = 0; j < count; ++j) {
+        const imgprep::Span sp = imgprep::span_of(n_in, n_out, first + j);
+        MMVAE_REQUIRE(sp.n <= stride, "imgprep_coeffs: index %d has %d taps, the rows hold %d", first + j, sp.n, stride);
+        xmin[j] = sp.xmin; taps[j] = sp.n;
+        for (int t = 0; t < stride; ++t)
+            coefs[(long long)j * stride + t] = t < sp.n ? imgprep::coef_at(n_in, n_out, first + j, sp.xmin, sp.ww, t) : 0;
+    }
+    return MMVAE_OK;
+}
+int mmvae_imgprep_scale_crop(const unsigned char* pixels, long long pixels_bytes, const long long* offsets, const int* heights, const int* widths,
+                             int n, int side, unsigned char* out_u8, float* out_f32, int* status, void* st) {
+    MMVAE_REQUIRE(pixels && offsets && heights && widths && status, "imgprep_scale_crop: null argument");
+    MMVAE_REQUIRE(out_u8 || out_f32, "imgprep_scale_crop: neither a uint8 nor a float32 image output");
+    MMVAE_REQUIRE(n >= 0 && pixels_bytes >= 0, "imgprep_scale_crop: n = %d, pixels_bytes = %lld", n, pixels_bytes);
+    MMVAE_REQUIRE(side >= 1 && side <= imgprep::MAX_OUT, "imgprep_scale_crop: S = %d, need 1..%d", side, (int)imgprep::MAX_OUT);
+    MMVAE_REQUIRE((reinterpret_cast<uintptr_t>(offsets) & 7) == 0 && (reinterpret_cast<uintptr_t>(heights) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(widths) & 3) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(out_f32) & 3) == 0,
+                  "imgprep_scale_crop: offsets must be 8-byte aligned, heights, widths, status and the float32 images 4-byte aligned");
+    return guarded([&] { return launch_imgprep_scale_crop(pixels, pixels_bytes, offsets, heights, widths, n, side, out_u8, out_f32, status, S(st)); });
 }
 
 // ---- exact t-SNE with a 2-component embedding (tsne.h)

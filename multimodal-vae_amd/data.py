@@ -100,6 +100,25 @@ def synthetic_celeba(n: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]
     return images, attrs
 
 
+def synthetic_celeba_raw(n: int, seed: int = 0):
+    """CelebA-shaped RAW stand-ins, what ``make_celeba`` decodes from ``img_align_celeba`` and reads from ``list_attr_celeba.txt``:
+    -> (a list of n uint8 (218,178,3) arrays, int64 (n,40) attribute rows of -1 / 1).  A smooth coloured gradient with a noisy
+    rectangle whose colour and size follow the first kept attributes; deterministic per seed, needs neither files nor Pillow."""
+    rng = np.random.default_rng(seed)
+    attrs = np.where(rng.random((n, 40)) < 0.3, 1, -1).astype(np.int64)
+    yy, xx = np.mgrid[0:218, 0:178]
+    images = []
+    for i in range(n):
+        base = np.stack([(yy * (1 + i % 3) + xx) % 256, (xx * 2 + 5 * i) % 256, (yy + xx * (1 + i % 2)) % 256], axis=2).astype(np.uint8)
+        hh = 60 + 40 * int(attrs[i, 4] > 0) + 20 * int(attrs[i, 5] > 0)
+        y, x = int(rng.integers(0, 218 - hh + 1)), int(rng.integers(0, 178 - hh + 1))
+        patch = rng.integers(64, 192, size=(hh, hh, 3), dtype=np.uint8)
+        patch[:, :, int(attrs[i, 8] > 0)] += 64
+        base[y:y + hh, x:x + hh] = patch
+        images.append(base)
+    return images, torch.from_numpy(attrs)
+
+
 class DeviceBatcher:
     """Iterates ``(image fp32, second modality)`` device batches over a uint8 image dataset.
 

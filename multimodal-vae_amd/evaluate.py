@@ -557,6 +557,48 @@ def sample_coco(vae, n_samples=64, image=None, text=None, stop_at_eos=False, see
 
 
 @torch.no_grad()
+def sample_celeba(vae, n_samples=64, image=None, attrs=None, seed=None):
+    """celeba/sample.py:73-137, its four modes: prior samples (image = attrs = None) or samples of the posterior given an image, given
+    attributes, or given both (product of experts) -> (images (n,3,64,64) float on the host, n lists of attribute names).
+    ``image``: (1,3,64,64) float in [0,1]; ``attrs``: (1,18) float (``celeba.attrs_from_names``)."""
+    from .celeba import tensor_to_attributes
+    vae.eval()
+    dev = next(vae.parameters()).device
+    if image is None and attrs is None:
+        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
+    elif attrs is None:
+        mu, logvar = vae.image_encoder(image.to(dev))
+        std = logvar.mul(0.5).exp()
+    elif image is None:
+        mu, logvar = vae.attrs_encoder(attrs.to(dev))
+        std = logvar.mul(0.5).exp()
+    else:
+        image_mu, image_logvar = vae.image_encoder(image.to(dev))
+        attrs_mu, attrs_logvar = vae.attrs_encoder(attrs.to(dev))
+        mu, logvar = vae.experts(torch.stack((image_mu, attrs_mu), dim=0), torch.stack((image_logvar, attrs_logvar), dim=0))
+        std = logvar.mul(0.5).exp()
+    g = None if seed is None else torch.Generator().manual_seed(seed)
+    z = torch.randn(n_samples, vae.n_latents, generator=g).to(dev)
+    z = (z * std.expand_as(z) + mu.expand_as(z)).contiguous()
+    image_recon = vae.image_decoder(z).cpu().view(n_samples, 3, 64, 64)
+    attrs_recon = vae.attrs_decoder(z).cpu()
+    return image_recon, [tensor_to_attributes(row) for row in attrs_recon]
+
+
+def fetch_celeba_image(path, attr_str, seed=0):
+    """What celeba/sample.py:18-41 means to do: a random image (seeded) among those of the dataset file ``path`` (``make_celeba``) that
+    have the attribute -> (1,3,64,64) float in [0,1]."""
+    from .celeba import attrs_from_names
+    col = int(attrs_from_names([attr_str]).view(-1).nonzero()[0])           # (one name; an unknown or not-kept one is refused)
+    x, a = load_celeba_eval_file(path)
+    rows = (a[:, col] == 1).nonzero().view(-1)
+    if len(rows) == 0:
+        raise ValueError("%s: no image has the attribute %s" % (path, attr_str))
+    pick = int(rows[int(torch.randint(len(rows), (1,), generator=torch.Generator().manual_seed(seed)))])
+    return x[pick:pick + 1].float().div(255.0)
+
+
+@torch.no_grad()
 def sample_pixelcnn(model, n_samples=64, height=None, width=None, complete=None, rows=0, seed=0):
     """Images from a ``pixelcnn.PixelCNN`` / ``GatedPixelCNN`` on the device, in one launch of the incremental sampler
     (``pixelcnn.generate``) -> float32 (n_samples, C, H, W) in [0, 1].  ``complete`` (C, H, W) or (N, C, H, W) uint8: every sample
@@ -777,6 +819,16 @@ def _parser():
     pw.add_argument('--stop_at_eos', action='store_true', default=False, help="cut every caption in front of its first '</s>'")
     pw.add_argument('--out', type=str, default='./results')
     pw.add_argument('--seed', type=int, default=0, help='seed of the latent samples (and of the synthetic table)')
+    # celeba/sample.py's flags for a checkpoint of train_celeba
+    pa = sub.add_parser("sample_celeba", help="celeba/sample.py: images + attribute names from a CelebA checkpoint")
+    pa.add_argument('model_path', type=str, help='path to a checkpoint written by train_celeba')
+    pa.add_argument('--n_samples', type=int, default=64, help='Number of images and texts to sample.')
+    pa.add_argument('--condition_on_image', type=str, default=None, metavar='ATTR',
+                    help='generate conditioned on a random image of --data that has this attribute')
+    pa.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='a dataset file of make_celeba (for --condition_on_image)')
+    pa.add_argument('--condition_on_attrs', type=str, default=None, metavar='NAME[,NAME]', help='generate conditioned on these attributes')
+    pa.add_argument('--out', type=str, default='./results')
+    pa.add_argument('--seed', type=int, default=0, help='seed of the latent samples and of the image choice')
     # images from a checkpoint of train_pixelcnn, in one launch of the incremental sampler
     pp = sub.add_parser("sample_pixelcnn", help="images from a PixelCNN / GatedPixelCNN checkpoint of train_pixelcnn")
     pp.add_argument('model_path', type=str, help='path to a checkpoint written by train_pixelcnn')
@@ -990,6 +1042,26 @@ def _sample_coco_main(args):
     return captions
 
 
+def _sample_celeba_main(args):
+    import os
+    from .celeba import attrs_from_names, load_checkpoint
+    image = attrs = None
+    if args.condition_on_attrs:
+        attrs = attrs_from_names(args.condition_on_attrs)         # (refuses an unknown name before anything is loaded)
+    if args.condition_on_image:
+        if not args.data:
+            raise SystemExit("sample_celeba: --condition_on_image ATTR needs --data FILE.pt to take the image from")
+        image = fetch_celeba_image(args.data, args.condition_on_image, seed=args.seed)
+    vae = load_checkpoint(args.model_path, use_cuda=True)
+    image_recon, names = sample_celeba(vae, args.n_samples, image, attrs, seed=args.seed)
+    os.makedirs(args.out, exist_ok=True)
+    torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))      # no torchvision here: the tensor, not a PNG grid
+    with open(os.path.join(args.out, 'sample_attrs.txt'), 'w') as fp:
+        for row in names:
+            fp.write('%s\n' % ','.join(row))
+    return image_recon, names
+
+
 def _report(vae, loader, posts, args, second, text_sigma=None):
     """Runs ``log_marginal`` per posterior, prints the reference's NLL line and the bounds, writes ``--json`` (``text_sigma``: the
     COCO command's, recorded in the file)."""
@@ -1133,6 +1205,8 @@ def _main(argv=None):
         return _loglik_coco_main(args)
     if args.cmd == "sample_coco":
         return _sample_coco_main(args)
+    if args.cmd == "sample_celeba":
+        return _sample_celeba_main(args)
     if args.cmd == "latent_mmd":
         return _latent_mmd_main(args)
     if args.cmd == "manifold":
