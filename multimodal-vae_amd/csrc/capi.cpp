@@ -284,7 +284,7 @@ int mmvae_celeba_iw_tail(const void* q3, const float* affine, int act, const flo
     return guarded([&]() -> int {
         MMVAE_REQUIRE(affine != nullptr, "mmvae_celeba_iw_tail: null affine table");
         MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= 0x3FFFFFFF, "mmvae_celeba_iw_tail: B=%d K=%d out of range", B, K);
-        CelebaIwTailArgs a{};
+        IwTailArgs a{};
         a.q3 = static_cast<const bf16*>(q3); a.affine = reinterpret_cast<const float2*>(affine); a.act = act; a.w = w; a.image = image;
         a.rows = B * K; a.K = K; a.loglik = loglik; a.logits = logits;
         return launch_celeba_iw_tail(a, S(st));
@@ -346,7 +346,7 @@ int mmvae_coco_iw_tail(const void* q3, const float* affine, int act, const float
     return guarded([&]() -> int {
         MMVAE_REQUIRE(affine != nullptr, "mmvae_coco_iw_tail: null affine table");
         MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= 0x3FFFFFFF, "mmvae_coco_iw_tail: B=%d K=%d out of range", B, K);
-        CocoIwTailArgs a{};
+        IwTailArgs a{};
         a.q3 = static_cast<const bf16*>(q3); a.affine = reinterpret_cast<const float2*>(affine); a.act = act; a.w = w; a.image = image;
         a.rows = B * K; a.K = K; a.loglik = loglik; a.logits = logits;
         return launch_coco_iw_tail(a, S(st));

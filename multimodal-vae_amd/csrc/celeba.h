@@ -1,6 +1,7 @@
 // CelebA MMVAE plan (celeba/model.py:14-57,91-196 ; celeba/train.py:60-81,131-147).
 #pragma once
 #include "layers.h"
+#include "iw.h"
 #include "../../include/mmvae_hip.h"
 
 struct PlanBase;
@@ -24,20 +25,8 @@ int celeba_attrs_decoder_bwd(CelebaPlan*, void* ws, size_t wsb, const float* d_r
 int celeba_iw_score(CelebaPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
                     hipStream_t);
 size_t celeba_iw_workspace_bytes(const CelebaPlan*);
-// forward-only scoring tail: raw bf16 NHWC [rows][32][32][32] -> BatchNorm affine + act -> ConvTranspose2d(32, 3, 4, 2, 1) -> one
-// log p(x|z) per row against image [rows / K].  The affine is either the table `affine` [32] (scale, shift) or, when that is
-// null, made from gamma / beta / running mean / running variance [32] each.
-struct CelebaIwTailArgs {
-    const bf16* q3; const float2* affine;
-    const float *gamma, *beta, *rmean, *rvar; float eps;
-    int act;
-    const float* w;                  // (32, 3, 4, 4) fp32
-    const float* image;              // [rows / K][3][64][64]
-    int rows, K;
-    float* loglik;                   // [rows]
-    float* logits;                   // [rows][3][64][64] or null
-};
-int launch_celeba_iw_tail(const CelebaIwTailArgs&, hipStream_t);
+// forward-only scoring tail (iw.h IwTailArgs): raw bf16 NHWC [rows][32][32][32], image [rows / K][3][64][64]
+int launch_celeba_iw_tail(const IwTailArgs&, hipStream_t);
 // attribute scorer on fp32 parameters: Linear(D, 64) -> BatchNorm1d (running statistics) -> Swish -> Linear(64, 18) -> words
 struct CelebaIwAttrsArgs {
     const float *w0, *b0, *gamma, *beta, *rmean, *rvar, *w1, *b1; float eps;
@@ -46,7 +35,7 @@ struct CelebaIwAttrsArgs {
 };
 int launch_celeba_iw_attrs(const CelebaIwAttrsArgs&, hipStream_t);
 int celeba_iw_attrs(CelebaPlan*, const float* z, long long rows, float* words, hipStream_t);
-// test / profiling aids: replay of one named layer launch of the step (celeba.hip named_gemm / named_wgrad) on the workspace's
+// test / profiling aids: replay of one named layer launch of the step (img_tower.h tower_named_gemm / tower_named_wgrad) on the workspace's
 // contents, and the byte offset of a named workspace buffer (-1 if unknown)
 int celeba_bench_layer(CelebaPlan*, void* ws, size_t wsb, const char* layer, int iters, hipStream_t);
 long long celeba_debug_offset(CelebaPlan*, const char* name);

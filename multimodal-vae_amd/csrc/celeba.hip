@@ -6,41 +6,30 @@
 // convolutions run once for passes 1 and 2 (classifier twice: independent Dropout masks), the attribute encoder once
 // for passes 1 and 3 (no dropout: identical), decoders on 3B rows with BatchNorm statistics per pass.
 #include "celeba.h"
-#include "plan_base.h"
-#include "thin.h"
+#include "img_tower.h"
 #include <cstring>
-#include <map>
-#include <string>
 
 namespace {
 constexpr int IMG = 64, NPIX = 3 * IMG * IMG, NA = 18, NA_LD = 24, FEAT = 6400, HID = 1024;
 }
 
-struct CelebaPlan : PlanBase {
-    int ldz;
-    ConvL conv[4], convT[4];
-    LinL fc1, up;
+struct CelebaPlan : TowerPlan {      // image half: img_tower.h
     MlpLin fc2, ae[2], ad[2];
-    int fc1_dgrad;                // dense [6400][1024] packing of classifier.0 for its input gradient
-    BnL bn[8];
-    struct W {
+    BnL abn[2];                      // attrs_encoder.net.1, attrs_decoder.net.1
+    struct W : TowerW {
         char* zero_begin; size_t zero_bytes;
-        float2 *st_e[3], *red_e[3], *st_d[3], *red_d[3], *st_a[2], *red_a[2];
+        float2 *st_a[2], *red_a[2];
         float* sums; float* dz_img; float* dz_att;
-        float2 *aff_e[3], *mr_e[3], *aff_d[3], *mr_d[3], *aff_a[2], *mr_a[2];
-        bf16 *patches1, *r1, *r2, *r3, *r4, *a1, *a2, *a3, *a4, *y1, *ay1;
+        float2 *aff_a[2], *mr_a[2];
         float* encout; uint8_t* m1;
         bf16 *att_bf, *r_ae, *a_ae; float* attout;
-        float *eps, *mu, *logvar, *z_f32; bf16* z_bf;
-        bf16 *u, *au, *q1, *q2, *q3, *aq1, *aq2, *aq3;
-        float* dlogit;
+        float *eps, *mu, *logvar, *z_f32;
         bf16 *r_ad, *a_ad; float *alogits, *arecon, *dalogit; bf16* dalogit_bf;
-        bf16 *patches4, *d3, *d2, *d1, *du, *d_ad;
+        bf16 *d_ad;
         bf16 *d_encout, *d_attout_bf, *d_ae;
-        bf16 *dy1, *db4, *dr4, *d3e, *d2e, *d1e;
         float* tmp_f32;
-        float* slab; size_t slab_floats;
     } w;
+    CelebaPlan() { tw = &w; }
 };
 
 namespace {
@@ -49,7 +38,6 @@ BnTabs atabs(CelebaPlan& P, int i) { CelebaPlan::W& w = P.w; return BnTabs{w.st_
 
 void build(CelebaPlan& P) {
     const int D = P.D;
-    P.ldz = round_up(D + 1, 8);
     auto lin = [&](const std::string& n, int o, int i) { add_param(P, n + ".weight", {o, i}); add_param(P, n + ".bias", {o}); };
     auto bnp = [&](const std::string& n, int c) { add_param(P, n + ".weight", {c}); add_param(P, n + ".bias", {c}); };
     add_param(P, "image_encoder.features.0.weight", {32, 3, 4, 4});
@@ -66,57 +54,24 @@ void build(CelebaPlan& P) {
     lin("attrs_encoder.net.0", 64, NA); bnp("attrs_encoder.net.1", 64); lin("attrs_encoder.net.3", 2 * D, 64);
     lin("attrs_decoder.net.0", 64, D); bnp("attrs_decoder.net.1", 64); lin("attrs_decoder.net.3", NA, 64);
 
-    const char* bnn[8] = {"image_encoder.features.3", "image_encoder.features.6", "image_encoder.features.9",
-                          "image_decoder.hallucinate.1", "image_decoder.hallucinate.4", "image_decoder.hallucinate.7",
-                          "attrs_encoder.net.1", "attrs_decoder.net.1"};
-    const int bnc[8] = {64, 128, 256, 128, 64, 32, 64, 64};
-    long long so = 0;
-    for (int i = 0; i < 8; ++i) {
-        P.bn[i] = BnL{off(P, std::string(bnn[i]) + ".weight"), off(P, std::string(bnn[i]) + ".bias"), bnc[i], so, i};
-        P.bn_names.push_back(bnn[i]); P.bn_list.push_back(P.bn[i]);
-        so += 2 * bnc[i];
+    // image encoder (celeba/model.py:100-112), image decoder (celeba/model.py:140-151)
+    const ConvGeom enc[4] = {ConvGeom{3, 32, 4, 4, 2, 1, 64, 64, 32, 32, false}, ConvGeom{32, 64, 4, 4, 2, 1, 32, 32, 16, 16, false},
+                             ConvGeom{64, 128, 4, 4, 2, 1, 16, 16, 8, 8, false}, ConvGeom{128, 256, 4, 4, 1, 0, 8, 8, 5, 5, false}};
+    const ConvGeom dec[4] = {ConvGeom{256, 128, 4, 4, 1, 0, 5, 5, 8, 8, true}, ConvGeom{128, 64, 4, 4, 2, 1, 8, 8, 16, 16, true},
+                             ConvGeom{64, 32, 4, 4, 2, 1, 16, 16, 32, 32, true}, ConvGeom{32, 3, 4, 4, 2, 1, 32, 32, 64, 64, true}};
+    P.geo = TowerGeom{IMG, 32, 32, 5, 256, FEAT, HID};
+    long long so = tower_build_convs(P, enc, dec);
+    const char* abnn[2] = {"attrs_encoder.net.1", "attrs_decoder.net.1"};
+    for (int i = 0; i < 2; ++i) {
+        P.abn[i] = BnL{off(P, std::string(abnn[i]) + ".weight"), off(P, std::string(abnn[i]) + ".bias"), 64, so, 6 + i};
+        P.bn_names.push_back(abnn[i]); P.bn_list.push_back(P.abn[i]);
+        so += 2 * 64;
     }
-    // image encoder (celeba/model.py:100-112)
-    build_conv(P, P.conv[0], "image_encoder.features.0.weight", ConvGeom{3, 32, 4, 4, 2, 1, 64, 64, 32, 32, false}, -1, false, true, false);
-    build_conv(P, P.conv[1], "image_encoder.features.2.weight", ConvGeom{32, 64, 4, 4, 2, 1, 32, 32, 16, 16, false}, 0, true, false, false);
-    build_conv(P, P.conv[2], "image_encoder.features.5.weight", ConvGeom{64, 128, 4, 4, 2, 1, 16, 16, 8, 8, false}, 1, true, false, false);
-    build_conv(P, P.conv[3], "image_encoder.features.8.weight", ConvGeom{128, 256, 4, 4, 1, 0, 8, 8, 5, 5, false}, 2, true, false, false);
-    // image decoder (celeba/model.py:140-151)
-    build_conv(P, P.convT[0], "image_decoder.hallucinate.0.weight", ConvGeom{256, 128, 4, 4, 1, 0, 5, 5, 8, 8, true}, 3, true, false, false);
-    build_conv(P, P.convT[1], "image_decoder.hallucinate.3.weight", ConvGeom{128, 64, 4, 4, 2, 1, 8, 8, 16, 16, true}, 4, true, false, false);
-    build_conv(P, P.convT[2], "image_decoder.hallucinate.6.weight", ConvGeom{64, 32, 4, 4, 2, 1, 16, 16, 32, 32, true}, 5, true, false, false);
-    build_conv(P, P.convT[3], "image_decoder.hallucinate.9.weight", ConvGeom{32, 3, 4, 4, 2, 1, 32, 32, 64, 64, true}, -1, true, false, true);
     add_frag_packs(P, P.conv[2]);      // 8x8 / 16x16 layers: direct-B image-resident kernels (convres.hip)
     add_frag_packs(P, P.convT[1]);
-
-    {   // classifier.0 consumes the NCHW flatten c*25 + y*5 + x of the (256,5,5) map held here as NHWC [5][5][256]
-        LinL& f = P.fc1;
-        f.w_off = off(P, "image_encoder.classifier.0.weight"); f.b_off = off(P, "image_encoder.classifier.0.bias");
-        f.N = HID; f.K = FEAT; f.pk_dgrad = -1;
-        PackDesc d = pack_dense(f.w_off, HID, FEAT, npad_for(HID), FEAT, FEAT, 0);
-        d.TW = 5; d.C = 256; d.s_ty = 5; d.s_tx = 1; d.s_c = 25;
-        f.pk_fwd = P.pk.add(d);
-        PackDesc gd = d; gd.Npad = round_up(HID, 64);
-        f.gk = P.gk.add(gd);
-        // input gradient as ONE dense GEMM: da[n][s*256+c] = sum_j dy[n][j] * W[j][c*25+s]
-        PackDesc t = pack_dense(f.w_off, FEAT, HID, npad_for(FEAT), HID, 0, FEAT);
-        t.NL = 256; t.s_nhi = 1; t.s_nlo = 25;
-        P.fc1_dgrad = P.pk.add(t);
-    }
+    tower_build_fc1(P);
     mlp_lin_init(P, P.fc2, "image_encoder.classifier.3", 2 * D, HID, -1, true);
-    {   // upsample Linear(D, 6400): output columns permuted to NHWC n' = s*256 + c  <->  row c*25 + s; bias folded
-        LinL& f = P.up;
-        f.w_off = off(P, "image_decoder.upsample.0.weight"); f.b_off = off(P, "image_decoder.upsample.0.bias");
-        f.N = FEAT; f.K = D;
-        PackDesc d = pack_dense(f.w_off, FEAT, D, npad_for(FEAT), round_up(P.ldz, 64), 0, 1);
-        d.NL = 256; d.s_nhi = D; d.s_nlo = 25 * D;
-        d.bias_off = f.b_off; d.b_nhi = 1; d.b_nlo = 25;
-        f.pk_fwd = P.pk.add(d);
-        PackDesc gd = d; f.gk = P.gk.add(gd);
-        PackDesc t = pack_dense(f.w_off, D, FEAT, npad_for(D), FEAT, 1, 0);
-        t.TW = 25; t.C = 256; t.s_ty = 0; t.s_tx = D; t.s_c = 25 * D;
-        f.pk_dgrad = P.pk.add(t);
-    }
+    tower_build_up(P);
     mlp_lin_init(P, P.ae[0], "attrs_encoder.net.0", 64, NA, 6, false);
     mlp_lin_init(P, P.ae[1], "attrs_encoder.net.3", 2 * D, 64, -1, true);
     mlp_lin_init(P, P.ad[0], "attrs_decoder.net.0", 64, D, 7, true, P.ldz);     // operand is z_bf
@@ -181,275 +136,38 @@ int cast_pad(const float* x, int rows, int cols, bf16* out, int ld, hipStream_t 
     return mmvae_check_launch("cast_pad");
 }
 
-// ================================================================== one definition per launch
-// Every GemmParams / WgradParams of the image encoder and decoder is built here, for the step (enc_fwd / enc_bwd / dec_fwd /
-// dec_bwd) and for the replay of one layer on a test's own operands (celeba_bench_layer): a test cannot pass on a copy of the
-// parameters that drifted from the step.  l: layer index (conv[l] / convT[l]); n: row blocks -- dropout variants of the
-// classifier, BatchNorm groups (passes) of the decoder.
-enum CaGemm { CA_ENC_CONV1, CA_ENC_CONV, CA_ENC_CONV_DGRAD, CA_FC1, CA_FC2_DGRAD, CA_FC1_DGRAD, CA_UP, CA_UP_DGRAD, CA_DEC_CONVT,
-              CA_DEC_CONVT_DGRAD, CA_DEC_LAST_DGRAD };
-enum CaWgrad { CA_W_ENC_CONV1, CA_W_ENC_CONV, CA_W_FC1, CA_W_UP, CA_W_DEC_CONVT, CA_W_DEC_LAST };
-
-// mask: keep flags of classifier Dropout (CA_FC1, CA_FC2_DGRAD) or null; training: column statistics of the conv layers;
-// aux: CA_FC2_DGRAD the operand d_out [n*B][2D], CA_UP_DGRAD the fp32 result dz [n*B][D]
-GemmParams layer_gemm(CelebaPlan& P, CaGemm kind, int l, int n, int training = 1, const uint8_t* mask = nullptr, const void* aux = nullptr) {
-    CelebaPlan::W& w = P.w;
-    const int B = P.B, rows = n * B;
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    switch (kind) {
-    case CA_ENC_CONV1: {   // conv1 + Swish (no BatchNorm): raw and activated outputs
-        GatherPlan pl = dense_plan(B * 1024, 48, 48, 32);
-        GemmParams g = gemm_of(P, pl, P.conv[0].pk_fwd, 1, B * 1024);
-        g.c.A = w.patches1; g.out_bf = w.r1; g.ldo = 32; g.out_act_bf = w.a1; g.e_act = ACT_SWISH;
-        return g;
-    }
-    case CA_ENC_CONV: {
-        const ConvL& L = P.conv[l];
-        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, 1, B, L.pk_fwd_f);
-        g.c.A = a[l - 1];
-        g.out_bf = r[l]; g.ldo = L.g.Cout;
-        g.colstats = training ? w.st_e[l - 1] : nullptr;
-        return g;
-    }
-    case CA_ENC_CONV_DGRAD: {
-        const ConvL& L = P.conv[l];
-        GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
-        d.c.A = dr[l]; d.out_bf = dr[l - 1]; d.ldo = L.g.Cin;
-        d.d_r = r[l - 1]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-        if (l > 1) { d.d_affine = w.aff_e[l - 2]; d.d_meanrstd = w.mr_e[l - 2]; d.d_red = w.red_e[l - 2]; }
-        return d;
-    }
-    case CA_FC1: {   // classifier.0 over the NHWC 5x5x256 map (shared by the variants) + Swish + Dropout
-        GatherPlan pl = plan_fwdform(5, 5, 1, 1, 256, 5, 5, 1, 0, HID, 1, rows);
-        GemmParams g = gemm_of(P, pl, &P.fc1.pk_fwd, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.bias = P.buf.params + P.fc1.b_off; g.out_bf = w.y1; g.ldo = HID;
-        g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (mask) { g.e_mask = mask; g.e_mask_scale = 1.f / (1.f - DROP_P); }
-        return g;
-    }
-    case CA_FC2_DGRAD: {   // classifier.3
-        GatherPlan pd = dense_plan(rows, P.fc2.ldo, P.fc2.ldo, HID);
-        GemmParams d = gemm_of(P, pd, &P.fc2.pk_dgrad, 1, rows);
-        d.c.A = (const bf16*)aux; d.out_bf = w.dy1; d.ldo = HID;
-        d.d_r = w.y1; d.d_ld = HID; d.d_act = ACT_SWISH; if (mask) { d.d_mask = mask; d.d_mask_scale = 1.f / (1.f - DROP_P); }
-        d.d_colsum = P.buf.grads + P.fc1.b_off;
-        return d;
-    }
-    case CA_FC1_DGRAD: {   // classifier.0: the input gradient is one dense GEMM over NHWC columns
-        GatherPlan pd = dense_plan(rows, HID, HID, FEAT);
-        GemmParams d = gemm_of(P, pd, &P.fc1_dgrad, 1, rows);
-        d.c.A = w.dy1; d.out_bf = w.db4; d.ldo = FEAT;
-        d.d_r = w.r4; d.d_ld = FEAT; d.d_bcast_n = B; d.d_act = ACT_SWISH; d.d_cmod = 256;
-        d.d_affine = w.aff_e[2]; d.d_meanrstd = w.mr_e[2]; d.d_red = w.red_e[2];
-        return d;
-    }
-    case CA_UP: {
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
-        GemmParams g = gemm_of(P, pl, &P.up.pk_fwd, 1, rows);
-        g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = FEAT; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
-        return g;
-    }
-    case CA_UP_DGRAD: {
-        GatherPlan pd = dense_plan(rows, FEAT, FEAT, P.D);
-        GemmParams d = gemm_of(P, pd, &P.up.pk_dgrad, 1, rows);
-        d.c.A = w.du; d.out_f = (float*)aux; d.ldo = P.D;
-        return d;
-    }
-    case CA_DEC_CONVT: {
-        const ConvL& L = P.convT[l];
-        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, n, B, L.pk_fwd_f);
-        g.c.A = aq[l];
-        g.out_bf = q[l + 1]; g.ldo = L.g.Cout;
-        g.colstats = training ? w.st_d[l] : nullptr;
-        return g;
-    }
-    case CA_DEC_CONVT_DGRAD: {
-        const ConvL& L = P.convT[l];
-        GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, n, B, L.pk_dgrad_f);
-        d.c.A = dq[l + 1]; d.out_bf = dq[l]; d.ldo = L.g.Cin;
-        d.d_r = q[l]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-        if (l > 0) { d.d_affine = w.aff_d[l - 1]; d.d_meanrstd = w.mr_d[l - 1]; d.d_red = w.red_d[l - 1]; }
-        return d;
-    }
-    case CA_DEC_LAST_DGRAD: {   // input gradient = dense GEMM patches x W with d-Swish + BatchNorm-backward sums in the epilogue
-        GatherPlan pd = dense_plan(B * 1024, 48, 48, 32);
-        GemmParams d = gemm_of(P, pd, P.convT[3].pk_dgrad, n, B * 1024);
-        d.c.A = w.patches4; d.out_bf = w.d3; d.ldo = 32;
-        d.d_r = w.q3; d.d_ld = 32; d.d_act = ACT_SWISH; d.d_affine = w.aff_d[2]; d.d_meanrstd = w.mr_d[2]; d.d_red = w.red_d[2];
-        return d;
-    }
-    }
-    return GemmParams{};
-}
-
-WgradParams layer_wgrad(CelebaPlan& P, CaWgrad kind, int l, int n) {
-    CelebaPlan::W& w = P.w;
-    const int B = P.B, rows = n * B;
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    switch (kind) {
-    case CA_W_ENC_CONV1: {   // conv1 wgrad over the im2col patches
-        GatherPlan pl = dense_plan(B * 1024, 48, 48, 32);
-        WgradParams g = wgrad_of(P, pl, P.conv[0].gk, 1, B * 1024);
-        g.c.A = w.patches1; g.P = w.d1e; g.ldp = 32;
-        return g;
-    }
-    case CA_W_ENC_CONV: {
-        const ConvL& L = P.conv[l];
-        WgradParams g = wgrad_of(P, L.fwd, L.gk, 1, B);
-        g.c.A = a[l - 1]; g.P = dr[l]; g.ldp = L.g.Cout;
-        return g;
-    }
-    case CA_W_FC1: {   // classifier.0: wgrad gathers the shared 5x5x256 map
-        GatherPlan pl = plan_fwdform(5, 5, 1, 1, 256, 5, 5, 1, 0, HID, 1, rows);
-        WgradParams g = wgrad_of(P, pl, &P.fc1.gk, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.P = w.dy1; g.ldp = HID;
-        return g;
-    }
-    case CA_W_UP: {   // upsample Linear: weight (+ folded bias) gradient
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
-        WgradParams g = wgrad_of(P, pl, &P.up.gk, 1, rows);
-        g.c.A = w.z_bf; g.P = w.du; g.ldp = FEAT;
-        return g;
-    }
-    case CA_W_DEC_CONVT:
-        return convT_wgrad(P, P.convT[l], n, B, aq[l], dq[l + 1]);
-    case CA_W_DEC_LAST: {   // last transposed conv (32 -> 3) through the im2col patches of dlogit (K = 16 taps x 3)
-        GatherPlan pl = plan_fwdform(1, 1, 32, 32, 48, 1, 1, 1, 0, 32, n, B);   // rows (n, iy, ix), dense K=48
-        WgradParams g = wgrad_of(P, pl, P.convT[3].gk, n, B);
-        g.c.A = w.patches4; g.c.AH = 32; g.c.AW = 32; g.c.sy = g.c.sx = 1;
-        g.P = w.aq3; g.ldp = 32;
-        return g;
-    }
-    }
-    return WgradParams{};
-}
-
-// Staging transforms of the fused step (gemm.h GatherTransform; B % 4 == 0, image-resident kernels only): `tr` is read by the
-// launcher and must outlive the launch.
-// kind 1: forward layer l stages Swish(BatchNorm(raw output of the layer below)) itself, writes that layer's tables, updates its
-// running statistics and leaves the activated tensor behind for the weight gradient
-void stage_fwd_enc(CelebaPlan& P, int l, GemmParams& g, GatherTransform& tr, int bn_updates, int training) {
-    CelebaPlan::W& w = P.w;
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    const ConvL& Lp = P.conv[l - 1];
-    tr.kind = 1;
-    tr.fin = bn_fin_args(P, P.bn[Lp.bn], P.B * Lp.g.OH * Lp.g.OW, 1, w.st_e[l - 2], bn_updates, w.aff_e[l - 2], w.mr_e[l - 2], training);
-    tr.out = a[l - 1];
-    g.c.A = r[l - 1]; g.tr = &tr;
-}
-void stage_fwd_dec(CelebaPlan& P, int l, int groups, GemmParams& g, GatherTransform& tr, int training) {
-    CelebaPlan::W& w = P.w;
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    const ConvL& Lp = P.convT[l - 1];
-    tr.kind = 1;
-    tr.fin = bn_fin_args(P, P.bn[Lp.bn], P.B * Lp.g.OH * Lp.g.OW, groups, w.st_d[l - 1], 1, w.aff_d[l - 1], w.mr_d[l - 1], training);
-    tr.out = aq[l];
-    g.c.A = q[l]; g.tr = &tr;
-}
-// kind 2: the data gradient of layer l applies the BatchNorm backward of the layer's own BatchNorm to db while staging it and
-// writes dr back IN PLACE (a workgroup owns its images: each vector is read, then overwritten, by the same thread)
-void stage_bwd_enc(CelebaPlan& P, int l, GemmParams& d, GatherTransform& tr) {
-    CelebaPlan::W& w = P.w;
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    const ConvL& L = P.conv[l];
-    const BnL& b = P.bn[L.bn];
-    tr.kind = 2; tr.r = r[l]; tr.red = w.red_e[l - 1]; tr.mr = w.mr_e[l - 1]; tr.gamma = P.buf.params + b.w_off;
-    tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off;
-    tr.inv_cnt = 1.f / (float)(P.B * L.g.OH * L.g.OW); tr.groups = 1; tr.out = dr[l];
-    d.tr = &tr;
-}
-void stage_bwd_dec(CelebaPlan& P, int l, int groups, GemmParams& d, GatherTransform& tr) {
-    CelebaPlan::W& w = P.w;
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    const ConvL& L = P.convT[l];
-    const BnL& b = P.bn[L.bn];
-    tr.kind = 2; tr.r = q[l + 1]; tr.red = w.red_d[l]; tr.mr = w.mr_d[l]; tr.gamma = P.buf.params + b.w_off;
-    tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off;
-    tr.inv_cnt = 1.f / (float)(P.B * L.g.OH * L.g.OW); tr.groups = groups; tr.out = dq[l + 1];
-    d.tr = &tr;
-}
-
 // ================================================================== image encoder (celeba/model.py:124-128)
-// fuse (the fused step, B % 4 == 0): the layers that run on the image-resident kernels (convres.hip) stage BatchNorm + Swish /
-// the BatchNorm backward of their gathered operand themselves (GatherTransform) and leave the staged tensor behind for the
-// weight gradients (GatherTransform::out) -- no bn_act / bn_bwd_apply launch in front of them
+// The launches of the conv chain, classifier.0 and the decoder body are the tower's (img_tower.h: tower_gemm / tower_wgrad and
+// the passes around them); `fuse` is the tower's: the fused step at B % 4 == 0.
+// classifier.3, input gradient: d_out [n*B][2D]; mask: keep flags of the classifier Dropout or null
+GemmParams fc2_dgrad_gemm(CelebaPlan& P, int n, const uint8_t* mask, const bf16* d_out) {
+    CelebaPlan::W& w = P.w;
+    const int rows = n * P.B;
+    GatherPlan pd = dense_plan(rows, P.fc2.ldo, P.fc2.ldo, HID);
+    GemmParams d = gemm_of(P, pd, &P.fc2.pk_dgrad, 1, rows);
+    d.c.A = d_out; d.out_bf = w.dy1; d.ldo = HID;
+    d.d_r = w.y1; d.d_ld = HID; d.d_act = ACT_SWISH; if (mask) { d.d_mask = mask; d.d_mask_scale = 1.f / (1.f - DROP_P); }
+    d.d_colsum = P.buf.grads + P.fc1.b_off;
+    return d;
+}
+
 int enc_fwd(CelebaPlan& P, const float* image, int variants, const uint8_t* m1, int dropout, int training, int bn_updates,
             float* out, hipStream_t s, bool fuse = false) {
-    CelebaPlan::W& w = P.w;
-    const int B = P.B;
-    MMVAE_TRY(launch_im2col_small(image, B, 3, IMG, IMG, 4, 4, 2, 1, 32, 32, w.patches1, 48, s));
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_ENC_CONV1, 0, 1), s));
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    for (int l = 1; l < 4; ++l) {
-        const ConvL& L = P.conv[l];
-        GemmParams g = layer_gemm(P, CA_ENC_CONV, l, 1, training);
-        GatherTransform tr{};
-        if (fuse && l == 2) stage_fwd_enc(P, l, g, tr, bn_updates, training);     // features.5 stages a2 = Swish(BatchNorm(r2)) itself
-        MMVAE_TRY(launch_gemm_gather(g, s));
-        const int rows = B * L.g.OH * L.g.OW;
-        if (fuse && l == 1) continue;
-        MMVAE_TRY(bn_act(P, P.bn[L.bn], r[l], a[l], rows, rows, 1, w.st_e[l - 1], bn_updates, w.aff_e[l - 1], w.mr_e[l - 1], training, s));
-    }
-    const int rows = variants * B;
+    MMVAE_TRY(tower_enc_fwd(P, image, training, bn_updates, s, fuse));
     const bool drop = training && dropout;
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_FC1, 0, variants, training, drop ? m1 : nullptr), s));
-    return mlp_fwd(P, P.fc2, w.ay1, rows, 1, nullptr, out, nullptr, s);
+    MMVAE_TRY(launch_gemm_gather(tower_gemm(P, TW_FC1, 0, variants, training, drop ? m1 : nullptr), s));
+    return mlp_fwd(P, P.fc2, P.w.ay1, variants * P.B, 1, nullptr, out, nullptr, s);
 }
 
 // d_out: bf16 [variants*B][2D]; the bias gradient of classifier.3 must already be accumulated by the caller
 int enc_bwd(CelebaPlan& P, const bf16* d_out, int variants, const uint8_t* m1, int dropout, hipStream_t s, bool fuse = false) {
-    CelebaPlan::W& w = P.w;
-    const int B = P.B, rows = variants * B;
-    {   // classifier.3
-        MMVAE_TRY(mlp_wgrad(P, P.fc2, d_out, w.ay1, rows, s));
-        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_FC2_DGRAD, 0, variants, 1, dropout ? m1 : nullptr, d_out), s));
-    }
-    {   // classifier.0: wgrad gathers the shared 5x5x256 map; the input gradient is one dense GEMM over NHWC columns
-        MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CA_W_FC1, 0, variants), s));
-        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_FC1_DGRAD, 0, variants), s));
-    }
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    for (int l = 3; l >= 1; --l) {
-        const ConvL& L = P.conv[l];
-        const BnL& b = P.bn[L.bn];
-        const int pix = L.g.OH * L.g.OW;
-        BnBwdApplyArgs x{};
-        x.db = (l == 3) ? w.db4 : dr[l];
-        x.db2 = (l == 3 && variants == 2) ? w.db4 + (size_t)B * FEAT : nullptr;
-        x.r = r[l]; x.dr = dr[l]; x.rows = B * pix; x.C = L.g.Cout; x.ld = L.g.Cout; x.rows_per_group = B * pix; x.G = 1;
-        x.red = w.red_e[l - 1]; x.meanrstd = w.mr_e[l - 1]; x.gamma = P.buf.params + b.w_off;
-        x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
-        // features.5 / features.2 (fused): their data gradient applies the BatchNorm backward to db while staging it and writes
-        // dr back IN PLACE (a workgroup owns its images: each vector is read, then overwritten, by the same thread) -- the weight
-        // gradient follows it
-        const bool fl = fuse && l <= 2;
-        if (!fl) MMVAE_TRY(launch_bn_bwd_apply(x, s));
-        WgradParams gw = layer_wgrad(P, CA_W_ENC_CONV, l, 1);
-        if (!fl) MMVAE_TRY(wgrad_async(P, gw, s));
-        {
-            GemmParams d = layer_gemm(P, CA_ENC_CONV_DGRAD, l, 1);
-            GatherTransform tr{};
-            if (fl) stage_bwd_enc(P, l, d, tr);
-            MMVAE_TRY(launch_gemm_gather(d, s));
-        }
-        if (fl) MMVAE_TRY(wgrad_async(P, gw, s));
-    }
-    return wgrad_async(P, layer_wgrad(P, CA_W_ENC_CONV1, 0, 1), s);
+    // classifier.3
+    MMVAE_TRY(mlp_wgrad(P, P.fc2, d_out, P.w.ay1, variants * P.B, s));
+    MMVAE_TRY(launch_gemm_gather(fc2_dgrad_gemm(P, variants, dropout ? m1 : nullptr, d_out), s));
+    // classifier.0: wgrad gathers the shared 5x5x256 map; the input gradient is one dense GEMM over NHWC columns
+    MMVAE_TRY(wgrad_async(P, tower_wgrad(P, TW_W_FC1, 0, variants), s));
+    MMVAE_TRY(launch_gemm_gather(tower_gemm(P, TW_FC1_DGRAD, 0, variants), s));
+    return tower_enc_bwd(P, variants, s, fuse);
 }
 
 // ================================================================== image decoder (celeba/model.py:157-161)
@@ -462,94 +180,45 @@ int dec_fwd(CelebaPlan& P, int groups, int training, ConvTLastFwdArgs* last, hip
             bool fuse = false) {
     CelebaPlan::W& w = P.w;
     const int B = P.B;
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_UP, 0, groups), s));
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    for (int l = 0; l < 3; ++l) {
-        const ConvL& L = P.convT[l];
-        GemmParams g = layer_gemm(P, CA_DEC_CONVT, l, groups, training);
-        GatherTransform tr{};
-        if (fuse && l >= 1) stage_fwd_dec(P, l, groups, g, tr, training);     // hallucinate.3 / .6 stage Swish(BatchNorm(q[l])) themselves and leave aq[l] behind
-        MMVAE_TRY(launch_gemm_gather(g, s));
-        const int rpg = B * L.g.OH * L.g.OW;
-        if (l == 2 && (fused_bwd_groups >= 0 || !last)) continue;
-        if (fuse && l <= 1) continue;
-        MMVAE_TRY(bn_act(P, P.bn[L.bn], q[l + 1], aq[l + 1], groups * rpg, rpg, groups, w.st_d[l], 1, w.aff_d[l], w.mr_d[l], training, s));
-    }
+    MMVAE_TRY(tower_dec_fwd(P, groups, training, last && fused_bwd_groups < 0, s, fuse));
     if (!last) return MMVAE_OK;
-    if (fused_bwd_groups >= 0) {
-        const ConvL& L = P.convT[2];
-        const BnL& b = P.bn[L.bn];
-        DecLastFusedArgs x{};
-        x.r = w.q3; x.act = ACT_SWISH; x.w = P.buf.params + P.convT[3].w_off;
-        x.G = last_groups > 0 ? last_groups : groups; x.B = B; x.IH = 32; x.IW = 32; x.Cin = 32; x.Cout = 3;
-        x.bwd_groups = std::min(fused_bwd_groups, x.G);
-        x.fin = bn_fin_args(P, b, B * L.g.OH * L.g.OW, groups, w.st_d[2], 1, w.aff_d[2], w.mr_d[2], training);
-        x.target = last->target; x.logits = last->logits; x.recon = last->recon; x.dlogit = nullptr;
-        for (int k = 0; k < 4; ++k) x.coef[k] = last->coef[k];
-        x.loss_sum = last->loss_sum;
-        if (x.bwd_groups > 0) {
-            const int chunks = x.bwd_groups * B;
-            x.wslab = P.slab.take((size_t)chunks * 32 * 48);
-            MMVAE_REQUIRE(x.wslab != nullptr, "fused decoder tail: the weight-gradient slab pool is exhausted");
-            x.db = w.d3; x.red = w.red_d[2];
-            WgradSlabJob j{};
-            const PackDesc& gd = P.gk.d[P.convT[3].gk[0]];
-            j.dst = P.buf.gpk + gd.dst_off; j.slab = x.wslab; j.N = 32; j.K = 48; j.Kpad = gd.Kpad; j.chunks = chunks;
-            j.chunk_stride = 32 * 48; j.src_ld = 48;
-            j.stream = s;            // (dec_bwd moves the sum behind its first weight gradient, off the main chain)
-            P.slab.jobs.push_back(j);
-        }
-        return launch_dec_last_ca(x, s);
+    if (fused_bwd_groups < 0) return launch_convt_last_fwd(dec_last_args(P, *last, groups), s);
+    const ConvL& L = P.convT[2];
+    const BnL& b = P.bn[L.bn];
+    DecLastFusedArgs x{};
+    x.r = w.q3; x.act = ACT_SWISH; x.w = P.buf.params + P.convT[3].w_off;
+    x.G = last_groups > 0 ? last_groups : groups; x.B = B; x.IH = 32; x.IW = 32; x.Cin = 32; x.Cout = 3;
+    x.bwd_groups = std::min(fused_bwd_groups, x.G);
+    x.fin = bn_fin_args(P, b, B * L.g.OH * L.g.OW, groups, w.st_d[2], 1, w.aff_d[2], w.mr_d[2], training);
+    x.target = last->target; x.logits = last->logits; x.recon = last->recon; x.dlogit = nullptr;
+    for (int k = 0; k < 4; ++k) x.coef[k] = last->coef[k];
+    x.loss_sum = last->loss_sum;
+    if (x.bwd_groups > 0) {
+        const int chunks = x.bwd_groups * B;
+        x.wslab = P.slab.take((size_t)chunks * 32 * 48);
+        MMVAE_REQUIRE(x.wslab != nullptr, "fused decoder tail: the weight-gradient slab pool is exhausted");
+        x.db = w.d3; x.red = w.red_d[2];
+        WgradSlabJob j{};
+        const PackDesc& gd = P.gk.d[P.convT[3].gk[0]];
+        j.dst = P.buf.gpk + gd.dst_off; j.slab = x.wslab; j.N = 32; j.K = 48; j.Kpad = gd.Kpad; j.chunks = chunks;
+        j.chunk_stride = 32 * 48; j.src_ld = 48;
+        j.stream = s;            // (dec_bwd moves the sum behind its first weight gradient, off the main chain)
+        P.slab.jobs.push_back(j);
     }
-    ConvTLastFwdArgs x = *last;
-    x.act = w.aq3; x.w = P.buf.params + P.convT[3].w_off; x.G = groups; x.B = B; x.IH = 32; x.IW = 32; x.Cin = 32; x.Cout = 3;
-    return launch_convt_last_fwd(x, s);
+    return launch_dec_last_ca(x, s);
 }
 
 // dlogit: fp32 NCHW [groups*B][3][64][64] (grad wrt the pre-sigmoid logits). Writes dz (fp32 [groups*B][D]).
 int dec_bwd(CelebaPlan& P, const float* dlogit, int groups, float* dz, hipStream_t s, bool last_fused = false, bool fuse = false) {
-    CelebaPlan::W& w = P.w;
-    const int B = P.B, rows = groups * B;
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
     if (last_fused && P.wgrad_forked && !mmvae_serial()) {
         // d3, the BatchNorm-backward sums and the per-image weight-gradient partials of the last layer came out of the fused tail
         // (dec_fwd); the sum of the partials goes behind the first weight gradient below, on its side stream (wgrad_async)
         hipStream_t wst = (P.wgrad_rr & 1) ? P.st_wgrad2 : P.st_wgrad;
         for (WgradSlabJob& j : P.slab.jobs) if (j.stream == s && j.src_ld == 48) j.stream = wst;
     }
-    if (!last_fused) {   // last transposed conv (32 -> 3): both gradients go through the im2col patches of dlogit (K = 16 taps x 3):
-        // input gradient = dense GEMM patches x W with d-Swish + BatchNorm-backward sums in the epilogue
-        MMVAE_TRY(launch_im2col_small(dlogit, rows, 3, IMG, IMG, 4, 4, 2, 1, 32, 32, w.patches4, 48, s));
-        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CA_DEC_LAST_DGRAD, 3, groups), s));
-        MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CA_W_DEC_LAST, 3, groups), s));
-    }
-    for (int l = 2; l >= 0; --l) {
-        const ConvL& L = P.convT[l];
-        const BnL& b = P.bn[L.bn];
-        const int pix = L.g.OH * L.g.OW;
-        BnBwdApplyArgs x{};
-        x.db = dq[l + 1]; x.r = q[l + 1]; x.dr = dq[l + 1]; x.rows = rows * pix; x.C = L.g.Cout; x.ld = L.g.Cout;
-        x.rows_per_group = B * pix; x.G = groups;
-        x.red = w.red_d[l]; x.meanrstd = w.mr_d[l]; x.gamma = P.buf.params + b.w_off;
-        x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
-        const bool fl = fuse && l >= 1;       // hallucinate.6 / .3: BatchNorm backward inside the data gradient's staging, dr in place (enc_bwd)
-        if (!fl) MMVAE_TRY(launch_bn_bwd_apply(x, s));
-        WgradParams gw = layer_wgrad(P, CA_W_DEC_CONVT, l, groups);
-        if (!fl) MMVAE_TRY(wgrad_async(P, gw, s));
-        {
-            GemmParams d = layer_gemm(P, CA_DEC_CONVT_DGRAD, l, groups);
-            GatherTransform tr{};
-            if (fl) stage_bwd_dec(P, l, groups, d, tr);
-            MMVAE_TRY(launch_gemm_gather(d, s));
-        }
-        if (fl) MMVAE_TRY(wgrad_async(P, gw, s));
-    }
-    // upsample Linear: weight (+ folded bias) gradient and dz
-    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CA_W_UP, 0, groups), s));
-    return launch_gemm_gather(layer_gemm(P, CA_UP_DGRAD, 0, groups, 1, nullptr, dz), s);
+    return tower_dec_bwd(P, dlogit, groups, dz, s, last_fused, fuse);
 }
+
 
 // ================================================================== attribute MLPs (celeba/model.py:164-196)
 int att_enc_fwd(CelebaPlan& P, const float* attrs, int training, int updates, float* out, hipStream_t s) {
@@ -557,7 +226,7 @@ int att_enc_fwd(CelebaPlan& P, const float* attrs, int training, int updates, fl
     const int B = P.B;
     MMVAE_TRY(cast_pad(attrs, B, NA, w.att_bf, NA_LD, s));
     MMVAE_TRY(mlp_fwd(P, P.ae[0], w.att_bf, B, 1, w.r_ae, nullptr, training ? w.st_a[0] : nullptr, s));
-    MMVAE_TRY(bn1d_act(P, P.bn[6], atabs(P, 0), w.r_ae, w.a_ae, B, 1, 64, updates, training, ACT_SWISH, s));
+    MMVAE_TRY(bn1d_act(P, P.abn[0], atabs(P, 0), w.r_ae, w.a_ae, B, 1, 64, updates, training, ACT_SWISH, s));
     return mlp_fwd(P, P.ae[1], w.a_ae, B, 1, nullptr, out, nullptr, s);
 }
 // d_out_bf: bf16 [B][2D]; the bias gradient of net.3 must already be accumulated by the caller
@@ -567,14 +236,14 @@ int att_enc_bwd(CelebaPlan& P, const bf16* d_out_bf, hipStream_t s) {
     BnTabs t = atabs(P, 0);
     MMVAE_TRY(mlp_wgrad(P, P.ae[1], d_out_bf, w.a_ae, B, s));
     MMVAE_TRY(mlp_dgrad(P, P.ae[1], d_out_bf, B, 1, w.d_ae, nullptr, 64, w.r_ae, &t, ACT_SWISH, s));
-    MMVAE_TRY(bn1d_bwd(P, P.bn[6], t, w.d_ae, w.r_ae, B, 1, 64, s));
+    MMVAE_TRY(bn1d_bwd(P, P.abn[0], t, w.d_ae, w.r_ae, B, 1, 64, s));
     return mlp_wgrad(P, P.ae[0], w.d_ae, w.att_bf, B, s);
 }
 int att_dec_fwd(CelebaPlan& P, int groups, int training, float* logits, hipStream_t s) {
     CelebaPlan::W& w = P.w;
     const int rows = groups * P.B;
     MMVAE_TRY(mlp_fwd(P, P.ad[0], w.z_bf, rows, groups, w.r_ad, nullptr, training ? w.st_a[1] : nullptr, s));
-    MMVAE_TRY(bn1d_act(P, P.bn[7], atabs(P, 1), w.r_ad, w.a_ad, rows, groups, 64, 1, training, ACT_SWISH, s));
+    MMVAE_TRY(bn1d_act(P, P.abn[1], atabs(P, 1), w.r_ad, w.a_ad, rows, groups, 64, 1, training, ACT_SWISH, s));
     return mlp_fwd(P, P.ad[1], w.a_ad, rows, 1, nullptr, logits, nullptr, s);
 }
 // dalogit: fp32 [groups*B][18]
@@ -586,7 +255,7 @@ int att_dec_bwd(CelebaPlan& P, const float* dalogit, int groups, float* dz, hipS
     MMVAE_TRY(launch_colsum_f32(dalogit, rows, NA, P.buf.grads + P.ad[1].b_off, s));
     MMVAE_TRY(mlp_wgrad(P, P.ad[1], w.dalogit_bf, w.a_ad, rows, s));
     MMVAE_TRY(mlp_dgrad(P, P.ad[1], w.dalogit_bf, rows, groups, w.d_ad, nullptr, 64, w.r_ad, &t, ACT_SWISH, s));
-    MMVAE_TRY(bn1d_bwd(P, P.bn[7], t, w.d_ad, w.r_ad, rows, groups, 64, s));
+    MMVAE_TRY(bn1d_bwd(P, P.abn[1], t, w.d_ad, w.r_ad, rows, groups, 64, s));
     MMVAE_TRY(mlp_wgrad(P, P.ad[0], w.d_ad, w.z_bf, rows, s));
     return mlp_dgrad(P, P.ad[0], w.d_ad, rows, 1, nullptr, dz, P.D, nullptr, nullptr, 0, s);
 }
@@ -793,7 +462,7 @@ int celeba_attrs_decoder_bwd(CelebaPlan* P, void* ws, size_t wsb, const float* d
 size_t celeba_iw_workspace_bytes(const CelebaPlan* P) { return P->ws_bytes_module; }
 int celeba_iw_attrs(CelebaPlan* P, const float* z, long long rows, float* words, hipStream_t s) {
     MMVAE_TRY(check_bound(P));
-    const BnL& b = P->bn[7];
+    const BnL& b = P->abn[1];
     const float* p = P->buf.params;
     CelebaIwAttrsArgs a{};
     a.w0 = p + P->ad[0].w_off; a.b0 = p + P->ad[0].b_off; a.w1 = p + P->ad[1].w_off; a.b1 = p + P->ad[1].b_off;
@@ -807,85 +476,31 @@ int celeba_iw_score(CelebaPlan* P, void* ws, size_t wsb, const float* z, const f
     MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B,
                   "mmvae_celeba_iw_score: %d examples x %d particles exceed the plan's %d rows", B, K, P->B);
     MMVAE_TRY(use_ws(P, ws, wsb));
-    CelebaPlan::W& w = P->w;
     const int rows = B * K;
-    MMVAE_TRY(launch_fill_zero(w.zero_begin, w.zero_bytes, s));
-    hipLaunchKernelGGL(cast_z_kernel, dim3(ceil_div(rows * P->ldz, 256)), dim3(256), 0, s, z, rows, P->D, w.z_bf, P->ldz);
-    MMVAE_TRY(mmvae_check_launch("cast_z"));
-    if (rows < P->B)      // the body runs the plan's rows: the ones past B*K are defined (zero) and never scored
-        MMVAE_TRY(launch_fill_zero(w.z_bf + (size_t)rows * P->ldz, (size_t)(P->B - rows) * P->ldz * sizeof(bf16), s));
+    MMVAE_TRY(launch_fill_zero(P->w.zero_begin, P->w.zero_bytes, s));
+    MMVAE_TRY(tower_iw_particles(*P, z, rows, s));
     MMVAE_TRY(dec_fwd(*P, 1, 0, nullptr, s));
-    const BnL& b = P->bn[P->convT[2].bn];
-    CelebaIwTailArgs t{};
-    t.q3 = w.q3; t.gamma = P->buf.params + b.w_off; t.beta = P->buf.params + b.b_off;
-    t.rmean = P->buf.bn_stats + b.stat_off; t.rvar = t.rmean + b.C; t.eps = BN_EPS;
-    t.act = ACT_SWISH; t.w = P->buf.params + P->convT[3].w_off; t.image = image; t.rows = rows; t.K = K; t.loglik = loglik_x;
-    MMVAE_TRY(launch_celeba_iw_tail(t, s));
+    MMVAE_TRY(launch_celeba_iw_tail(tower_iw_tail_args(*P, image, rows, K, loglik_x), s));
     return celeba_iw_attrs(P, z, rows, words, s);
 }
 
 // ---------------------------------------------------------------- test / profiling aid: replay one layer of the step
-// The launches of layer_gemm / layer_wgrad under names: <layer>, <layer>_dgrad, <layer>_wgrad.  The classifier runs its 2 dropout
-// variants, the decoder 3 passes forward and 3 backward (the default step: every lambda_x > 0).  Knob "celeba_layer_mask" (0): the
-// keep flags in W::m1 take part in fc1 / fc2_dgrad as in a step with classifier dropout.  fc2_dgrad reads d_encout and, as in the
-// step, adds its column sums to the bias gradient of classifier.0 in the flat gradients; up_dgrad writes dz into dz_img.
-// <layer>_staged / <layer>_dgrad_staged: the forms the default step runs at B % 4 == 0 (stage_fwd_* / stage_bwd_*; `tr` is theirs),
-// with the running-statistics updates of the default step (2 encoder variants, 1 per decoder pass)
-static bool named_gemm(CelebaPlan& P, const std::string& name, GemmParams& g, GatherTransform& tr) {
-    CelebaPlan::W& w = P.w;
-    const uint8_t* mask = mmvae_knob("celeba_layer_mask", 0) ? w.m1 : nullptr;
-    if (name == "enc_conv1") { g = layer_gemm(P, CA_ENC_CONV1, 0, 1); return true; }
-    for (int l = 1; l < 4; ++l) {
-        const std::string n = "enc_conv" + std::to_string(l + 1);
-        if (name == n) { g = layer_gemm(P, CA_ENC_CONV, l, 1); return true; }
-        if (name == n + "_dgrad") { g = layer_gemm(P, CA_ENC_CONV_DGRAD, l, 1); return true; }
-    }
-    if (name == "fc1") { g = layer_gemm(P, CA_FC1, 0, 2, 1, mask); return true; }
-    if (name == "fc1_dgrad") { g = layer_gemm(P, CA_FC1_DGRAD, 0, 2); return true; }
-    if (name == "fc2_dgrad") { g = layer_gemm(P, CA_FC2_DGRAD, 0, 2, 1, mask, w.d_encout); return true; }
-    if (name == "up") { g = layer_gemm(P, CA_UP, 0, 3); return true; }
-    if (name == "up_dgrad") { g = layer_gemm(P, CA_UP_DGRAD, 0, 3, 1, nullptr, w.dz_img); return true; }
-    for (int l = 0; l < 3; ++l) {
-        const std::string n = "dec_convT" + std::to_string(l + 1);
-        if (name == n) { g = layer_gemm(P, CA_DEC_CONVT, l, 3); return true; }
-        if (name == n + "_dgrad") { g = layer_gemm(P, CA_DEC_CONVT_DGRAD, l, 3); return true; }
-    }
-    if (name == "dec_last_dgrad_gemm") { g = layer_gemm(P, CA_DEC_LAST_DGRAD, 3, 3); return true; }
-    if (name == "enc_conv3_staged") { g = layer_gemm(P, CA_ENC_CONV, 2, 1); stage_fwd_enc(P, 2, g, tr, 2, 1); return true; }
-    for (int l = 1; l < 3; ++l) {
-        const std::string e = "enc_conv" + std::to_string(l + 1), d = "dec_convT" + std::to_string(l + 1);
-        if (name == d + "_staged") { g = layer_gemm(P, CA_DEC_CONVT, l, 3); stage_fwd_dec(P, l, 3, g, tr, 1); return true; }
-        if (name == e + "_dgrad_staged") { g = layer_gemm(P, CA_ENC_CONV_DGRAD, l, 1); stage_bwd_enc(P, l, g, tr); return true; }
-        if (name == d + "_dgrad_staged") { g = layer_gemm(P, CA_DEC_CONVT_DGRAD, l, 3); stage_bwd_dec(P, l, 3, g, tr); return true; }
-    }
-    return false;
-}
-static bool named_wgrad(CelebaPlan& P, const std::string& name, WgradParams& g) {
-    if (name == "enc_conv1_wgrad") { g = layer_wgrad(P, CA_W_ENC_CONV1, 0, 1); return true; }
-    for (int l = 1; l < 4; ++l)
-        if (name == "enc_conv" + std::to_string(l + 1) + "_wgrad") { g = layer_wgrad(P, CA_W_ENC_CONV, l, 1); return true; }
-    if (name == "fc1_wgrad") { g = layer_wgrad(P, CA_W_FC1, 0, 2); return true; }
-    if (name == "up_wgrad") { g = layer_wgrad(P, CA_W_UP, 0, 3); return true; }
-    for (int l = 0; l < 3; ++l)
-        if (name == "dec_convT" + std::to_string(l + 1) + "_wgrad") { g = layer_wgrad(P, CA_W_DEC_CONVT, l, 3); return true; }
-    if (name == "dec_last_wgrad") { g = layer_wgrad(P, CA_W_DEC_LAST, 3, 3); return true; }
-    return false;
-}
+// The tower's names (img_tower.h tower_named_gemm / tower_named_wgrad, with the _staged forms) and fc2_dgrad.  Knob
+// "celeba_layer_mask" (0): the keep flags in W::m1 take part in fc1 / fc2_dgrad as in a step with classifier dropout.  fc2_dgrad
+// reads d_encout and, as in the step, adds its column sums to the bias gradient of classifier.0 in the flat gradients; up_dgrad
+// writes dz into dz_img.
 int celeba_bench_layer(CelebaPlan* P, void* ws, size_t wsb, const char* layer, int iters, hipStream_t s) {
     MMVAE_REQUIRE(P && layer, "mmvae_celeba_bench_layer: null argument");
     MMVAE_TRY(use_ws(P, ws, wsb, false));
+    CelebaPlan::W& w = P->w;
+    const std::string name = layer;
+    const uint8_t* mask = mmvae_knob("celeba_layer_mask", 0) ? w.m1 : nullptr;
     WgradParams wg{};
-    if (named_wgrad(*P, layer, wg)) {            // kernel + its share of the slab reduction, as in the step
-        for (int i = 0; i < iters; ++i) {
-            P->slab.reset(P->w.slab, P->w.slab_floats);
-            MMVAE_TRY(launch_wgrad(wg, s, &P->slab));
-            MMVAE_TRY(launch_wgrad_reduce(&P->slab, s));
-        }
-        return MMVAE_OK;
-    }
+    if (tower_named_wgrad(*P, name, wg)) return tower_replay_wgrad(*P, wg, iters, s);
     GemmParams g{};
     GatherTransform tr{};
-    MMVAE_REQUIRE(named_gemm(*P, layer, g, tr), "mmvae_celeba_bench_layer: unknown layer '%s'", layer);
+    if (name == "fc2_dgrad") g = fc2_dgrad_gemm(*P, 2, mask, w.d_encout);
+    else { MMVAE_REQUIRE(tower_named_gemm(*P, name, mask, w.dz_img, true, g, tr), "mmvae_celeba_bench_layer: unknown layer '%s'", layer); }
     for (int i = 0; i < iters; ++i) MMVAE_TRY(launch_gemm_gather(g, s));
     return MMVAE_OK;
 }
@@ -896,22 +511,8 @@ long long celeba_debug_offset(CelebaPlan* P, const char* name) {
     P->carve_passes = 3;
     carve(*P, ws);
     CelebaPlan::W& w = P->w;
-    const std::map<std::string, const void*> m = {
-        {"patches1", w.patches1}, {"r1", w.r1}, {"r2", w.r2}, {"r3", w.r3}, {"r4", w.r4},
-        {"a1", w.a1}, {"a2", w.a2}, {"a3", w.a3}, {"a4", w.a4}, {"y1", w.y1}, {"ay1", w.ay1}, {"encout", w.encout}, {"m1", w.m1},
-        {"z_bf", w.z_bf}, {"z_f32", w.z_f32}, {"u", w.u}, {"au", w.au}, {"q1", w.q1}, {"q2", w.q2}, {"q3", w.q3},
-        {"aq1", w.aq1}, {"aq2", w.aq2}, {"aq3", w.aq3}, {"dlogit", w.dlogit}, {"patches4", w.patches4},
-        {"d3", w.d3}, {"d2", w.d2}, {"d1", w.d1}, {"du", w.du}, {"dz_img", w.dz_img}, {"dz_att", w.dz_att},
-        {"d_encout", w.d_encout}, {"dy1", w.dy1}, {"db4", w.db4}, {"dr4", w.dr4}, {"d3e", w.d3e}, {"d2e", w.d2e}, {"d1e", w.d1e},
-        {"tmp_f32", w.tmp_f32}, {"slab", w.slab},
-        {"st_e0", w.st_e[0]}, {"st_e1", w.st_e[1]}, {"st_e2", w.st_e[2]}, {"st_d0", w.st_d[0]}, {"st_d1", w.st_d[1]}, {"st_d2", w.st_d[2]},
-        {"red_e0", w.red_e[0]}, {"red_e1", w.red_e[1]}, {"red_e2", w.red_e[2]},
-        {"red_d0", w.red_d[0]}, {"red_d1", w.red_d[1]}, {"red_d2", w.red_d[2]},
-        {"aff_e0", w.aff_e[0]}, {"aff_e1", w.aff_e[1]}, {"aff_e2", w.aff_e[2]},
-        {"aff_d0", w.aff_d[0]}, {"aff_d1", w.aff_d[1]}, {"aff_d2", w.aff_d[2]},
-        {"mr_e0", w.mr_e[0]}, {"mr_e1", w.mr_e[1]}, {"mr_e2", w.mr_e[2]}, {"mr_d0", w.mr_d[0]}, {"mr_d1", w.mr_d[1]}, {"mr_d2", w.mr_d[2]},
-    };
-    auto it = m.find(name);
-    if (it == m.end()) return -1;
-    return (long long)((const char*)it->second - (const char*)0x1000);
+    std::map<std::string, const void*> m = tower_debug_names(w);
+    m.insert({{"encout", w.encout}, {"m1", w.m1}, {"z_f32", w.z_f32}, {"dz_img", w.dz_img}, {"dz_att", w.dz_att},
+              {"d_encout", w.d_encout}, {"tmp_f32", w.tmp_f32}});
+    return tower_offset_of(m, name, (const void*)0x1000);
 }

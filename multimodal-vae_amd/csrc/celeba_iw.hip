@@ -42,7 +42,7 @@ __device__ __forceinline__ float tail_act(int act, float v) {
     return v;
 }
 
-__global__ __launch_bounds__(T_NTHR) void celeba_iw_tail_kernel(const CelebaIwTailArgs a) {
+__global__ __launch_bounds__(T_NTHR) void celeba_iw_tail_kernel(const IwTailArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const A_s = smem + T_OFF_A;
     float* const P_s = reinterpret_cast<float*>(smem + T_OFF_P);
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(AT_NTHR) void celeba_iw_attrs_kernel(const CelebaIw
 
 }  // namespace
 
-int launch_celeba_iw_tail(const CelebaIwTailArgs& a, hipStream_t s) {
+int launch_celeba_iw_tail(const IwTailArgs& a, hipStream_t s) {
     MMVAE_REQUIRE(a.q3 && a.w && a.image && a.loglik, "celeba_iw_tail: null argument");
     MMVAE_REQUIRE(a.affine || (a.gamma && a.beta && a.rmean && a.rvar), "celeba_iw_tail: neither an affine table nor BatchNorm buffers");
     MMVAE_REQUIRE(a.act == ACT_NONE || a.act == ACT_SWISH || a.act == ACT_RELU, "celeba_iw_tail: unknown activation %d", a.act);

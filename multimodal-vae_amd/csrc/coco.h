@@ -1,6 +1,7 @@
 // COCO MMVAE plan (coco/model.py:22-90,147-312 ; coco/train.py:66-84,146-165).
 #pragma once
 #include "layers.h"
+#include "iw.h"
 #include "../../include/mmvae_hip.h"
 
 struct PlanBase;
@@ -28,19 +29,7 @@ long long coco_debug_offset(CocoPlan*, const char* name);
 int coco_iw_score(CocoPlan*, void* ws, size_t wsb, const float* z, const float* image, const float* text, const float* sos, int B, int K,
                   float* loglik_x, float* sse_y, hipStream_t);
 size_t coco_iw_workspace_bytes(const CocoPlan*);
-// forward-only scoring tail: raw bf16 NHWC [rows][16][16][64] -> BatchNorm affine + act -> ConvTranspose2d(64, 3, 4, 2, 1) -> one
-// log p(x|z) per row against image [rows / K].  The affine is either the table `affine` [64] (scale, shift) or, when that is
-// null, made from gamma / beta / running mean / running variance [64] each.
-struct CocoIwTailArgs {
-    const bf16* q3; const float2* affine;
-    const float *gamma, *beta, *rmean, *rvar; float eps;
-    int act;
-    const float* w;                  // (64, 3, 4, 4) fp32
-    const float* image;              // [rows / K][3][32][32]
-    int rows, K;
-    float* loglik;                   // [rows]
-    float* logits;                   // [rows][3][32][32] or null
-};
-int launch_coco_iw_tail(const CocoIwTailArgs&, hipStream_t);
+// forward-only scoring tail (iw.h IwTailArgs): raw bf16 NHWC [rows][16][16][64], image [rows / K][3][32][32]
+int launch_coco_iw_tail(const IwTailArgs&, hipStream_t);
 // sse[row] = sum over (t, e) of (sentence[row][t][e] - text[row / K][t][e])^2 for the B*K rows; both 16-byte aligned
 int launch_coco_iw_text_sse(const float* sentence, const float* text, int B, int K, int steps, float* sse, hipStream_t);

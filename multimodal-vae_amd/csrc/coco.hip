@@ -10,20 +10,13 @@
 // passes 1 and 3 (no dropout: identical), decoders on 3B rows with BatchNorm statistics per pass.  The caption half runs
 // on the side stream next to the image half.
 #include "coco_plan.h"
-#include "thin.h"
 #include <cstring>
-#include <map>
-#include <string>
 
 namespace {
 constexpr int IMG = 32, NPIX = 3 * IMG * IMG, FEAT = 2048, HID1 = 1024, HID2 = 256;
-}
-
-namespace {
 
 void build(CocoPlan& P) {
     const int D = P.D;
-    P.ldz = round_up(D + 1, 8);
     auto lin = [&](const std::string& n, int o, int i) { add_param(P, n + ".weight", {o, i}); add_param(P, n + ".bias", {o}); };
     auto bnp = [&](const std::string& n, int c) { add_param(P, n + ".weight", {c}); add_param(P, n + ".bias", {c}); };
     auto gru = [&](const std::string& n, const char* sfx, int in) {
@@ -48,62 +41,25 @@ void build(CocoPlan& P) {
     gru("text_decoder.gru", "l0", COCO_E + D); gru("text_decoder.gru", "l1", COCO_H);
     lin("text_decoder.h2o", COCO_E, COCO_H + D);
 
-    const char* bnn[6] = {"image_encoder.features.3", "image_encoder.features.6", "image_encoder.features.9",
-                          "image_decoder.hallucinate.1", "image_decoder.hallucinate.4", "image_decoder.hallucinate.7"};
-    const int bnc[6] = {128, 256, 512, 256, 128, 64};
-    long long so = 0;
-    for (int i = 0; i < 6; ++i) {
-        P.bn[i] = BnL{off(P, std::string(bnn[i]) + ".weight"), off(P, std::string(bnn[i]) + ".bias"), bnc[i], so, i};
-        P.bn_names.push_back(bnn[i]); P.bn_list.push_back(P.bn[i]);
-        so += 2 * bnc[i];
-    }
-    // image encoder (coco/model.py:157-169)
-    build_conv(P, P.conv[0], "image_encoder.features.0.weight", ConvGeom{3, 64, 4, 4, 2, 1, 32, 32, 16, 16, false}, -1, false, true, false);
-    build_conv(P, P.conv[1], "image_encoder.features.2.weight", ConvGeom{64, 128, 4, 4, 2, 1, 16, 16, 8, 8, false}, 0, true, false, false);
-    build_conv(P, P.conv[2], "image_encoder.features.5.weight", ConvGeom{128, 256, 4, 4, 2, 1, 8, 8, 4, 4, false}, 1, true, false, false);
-    build_conv(P, P.conv[3], "image_encoder.features.8.weight", ConvGeom{256, 512, 4, 4, 2, 1, 4, 4, 2, 2, false}, 2, true, false, false);
-    // image decoder (coco/model.py:197-208)
-    build_conv(P, P.convT[0], "image_decoder.hallucinate.0.weight", ConvGeom{512, 256, 4, 4, 2, 1, 2, 2, 4, 4, true}, 3, true, false, false);
-    build_conv(P, P.convT[1], "image_decoder.hallucinate.3.weight", ConvGeom{256, 128, 4, 4, 2, 1, 4, 4, 8, 8, true}, 4, true, false, false);
-    build_conv(P, P.convT[2], "image_decoder.hallucinate.6.weight", ConvGeom{128, 64, 4, 4, 2, 1, 8, 8, 16, 16, true}, 5, true, false, false);
-    build_conv(P, P.convT[3], "image_decoder.hallucinate.9.weight", ConvGeom{64, 3, 4, 4, 2, 1, 16, 16, 32, 32, true}, -1, true, false, true);
+    // image encoder (coco/model.py:157-169), image decoder (coco/model.py:197-208)
+    const ConvGeom enc[4] = {ConvGeom{3, 64, 4, 4, 2, 1, 32, 32, 16, 16, false}, ConvGeom{64, 128, 4, 4, 2, 1, 16, 16, 8, 8, false},
+                             ConvGeom{128, 256, 4, 4, 2, 1, 8, 8, 4, 4, false}, ConvGeom{256, 512, 4, 4, 2, 1, 4, 4, 2, 2, false}};
+    const ConvGeom dec[4] = {ConvGeom{512, 256, 4, 4, 2, 1, 2, 2, 4, 4, true}, ConvGeom{256, 128, 4, 4, 2, 1, 4, 4, 8, 8, true},
+                             ConvGeom{128, 64, 4, 4, 2, 1, 8, 8, 16, 16, true}, ConvGeom{64, 3, 4, 4, 2, 1, 16, 16, 32, 32, true}};
+    P.geo = TowerGeom{IMG, 16, 64, 2, 512, FEAT, HID1};
+    tower_build_convs(P, enc, dec);
     add_frag_packs(P, P.conv[1]);      // 8x8 / 16x16 layers: direct-B image-resident kernels (convres.hip)
     add_frag_packs(P, P.convT[2]);
-    {   // classifier.0 consumes the NCHW flatten c*4 + y*2 + x of the (512,2,2) map held here as NHWC [2][2][512]
-        LinL& f = P.fc[0];
-        f.w_off = off(P, "image_encoder.classifier.0.weight"); f.b_off = off(P, "image_encoder.classifier.0.bias");
-        f.N = HID1; f.K = FEAT; f.pk_dgrad = -1;
-        PackDesc d = pack_dense(f.w_off, HID1, FEAT, npad_for(HID1), FEAT, FEAT, 0);
-        d.TW = 2; d.C = 512; d.s_ty = 2; d.s_tx = 1; d.s_c = 4;
-        f.pk_fwd = P.pk.add(d);
-        PackDesc gd = d; gd.Npad = round_up(HID1, 64);
-        f.gk = P.gk.add(gd);
-        // input gradient as ONE dense GEMM: da[n][s*512+c] = sum_j dy[n][j] * W[j][c*4+s]
-        PackDesc t = pack_dense(f.w_off, FEAT, HID1, npad_for(FEAT), HID1, 0, FEAT);
-        t.NL = 512; t.s_nhi = 1; t.s_nlo = 4;
-        P.fc1_dgrad = P.pk.add(t);
-    }
+    tower_build_fc1(P);
     auto dense = [&](LinL& f, const std::string& n, int N, int K) {
         f.w_off = off(P, n + ".weight"); f.b_off = off(P, n + ".bias"); f.N = N; f.K = K;
         f.pk_fwd = P.pk.add(pack_dense(f.w_off, N, K, npad_for(N), round_up(round_up(K, 8), 64), K, 1));
         f.gk = P.gk.add(pack_dense(f.w_off, N, K, round_up(N, 64), round_up(round_up(K, 8), 64), K, 1));
         f.pk_dgrad = P.pk.add(pack_dense(f.w_off, K, N, npad_for(K), round_up(round_up(N, 8), 64), 1, K));
     };
-    dense(P.fc[1], "image_encoder.classifier.3", HID2, HID1);
-    dense(P.fc[2], "image_encoder.classifier.6", 2 * D, HID2);
-    {   // upsample Linear(D, 2048): output columns permuted to NHWC n' = s*512 + c  <->  row c*4 + s; bias folded
-        LinL& f = P.up;
-        f.w_off = off(P, "image_decoder.upsample.0.weight"); f.b_off = off(P, "image_decoder.upsample.0.bias");
-        f.N = FEAT; f.K = D;
-        PackDesc d = pack_dense(f.w_off, FEAT, D, npad_for(FEAT), round_up(P.ldz, 64), 0, 1);
-        d.NL = 512; d.s_nhi = D; d.s_nlo = 4 * D;
-        d.bias_off = f.b_off; d.b_nhi = 1; d.b_nlo = 4;
-        f.pk_fwd = P.pk.add(d);
-        PackDesc gd = d; f.gk = P.gk.add(gd);
-        PackDesc t = pack_dense(f.w_off, D, FEAT, npad_for(D), FEAT, 1, 0);
-        t.TW = 4; t.C = 512; t.s_ty = 0; t.s_tx = D; t.s_c = 4 * D;
-        f.pk_dgrad = P.pk.add(t);
-    }
+    dense(P.fc2, "image_encoder.classifier.3", HID2, HID1);
+    dense(P.fc3, "image_encoder.classifier.6", 2 * D, HID2);
+    tower_build_up(P);
     P.pk_text_begin = (int)P.pk.d.size();
     coco_text_build(P);
 }
@@ -156,131 +112,48 @@ void carve(CocoPlan& P, Workspace& ws) {
     coco_text_carve(P, ws);
 }
 
-// ================================================================== one definition per launch
-// Every GemmParams / WgradParams of the image encoder and decoder and the arguments of every stand-alone pass are built here, for
-// the step (enc_fwd / enc_bwd / dec_fwd / dec_bwd) and for the replay of one launch on a test's own operands (coco_bench_layer): a
-// test cannot pass on a copy of the parameters that drifted from the step.  l: layer index (conv[l] / convT[l]); n: row blocks --
-// dropout variants of the classifier, BatchNorm groups (passes) of the decoder.
-enum CoGemm { CO_ENC_CONV1, CO_ENC_CONV, CO_ENC_CONV_DGRAD, CO_FC1, CO_FC2, CO_FC3, CO_FC3_DGRAD, CO_FC2_DGRAD, CO_FC1_DGRAD, CO_UP,
-              CO_UP_DGRAD, CO_DEC_CONVT, CO_DEC_CONVT_DGRAD, CO_DEC_LAST_DGRAD };
-enum CoWgrad { CO_W_ENC_CONV1, CO_W_ENC_CONV, CO_W_FC1, CO_W_FC2, CO_W_FC3, CO_W_UP, CO_W_DEC_CONVT, CO_W_DEC_LAST };
+// ================================================================== the classifier behind classifier.0
+// The launches of the conv chain, classifier.0 and the decoder are the tower's (img_tower.h: tower_gemm / tower_wgrad and the
+// passes around them); classifier.3 / classifier.6 are built here, for the step and for coco_bench_layer alike.  n: dropout variants.
+enum CoGemm { CO_FC2, CO_FC3, CO_FC3_DGRAD, CO_FC2_DGRAD };
+enum CoWgrad { CO_W_FC2, CO_W_FC3 };
 
-// mask: keep flags of the classifier Dropout the layer applies (CO_FC1 / CO_FC2_DGRAD: m1, CO_FC2 / CO_FC3_DGRAD: m2) or null;
-// training: column statistics of the conv layers; aux: CO_FC3 the fp32 result [n*B][2D], CO_FC3_DGRAD the operand d_out [n*B][2D],
-// CO_UP_DGRAD the fp32 result dz [n*B][D]
-GemmParams layer_gemm(CocoPlan& P, CoGemm kind, int l, int n, int training = 1, const uint8_t* mask = nullptr, const void* aux = nullptr) {
+// mask: keep flags of the classifier Dropout the layer applies (CO_FC2_DGRAD: m1, CO_FC2 / CO_FC3_DGRAD: m2) or null;
+// aux: CO_FC3 the fp32 result [n*B][2D], CO_FC3_DGRAD the operand d_out [n*B][2D]
+GemmParams layer_gemm(CocoPlan& P, CoGemm kind, int n, const uint8_t* mask = nullptr, const void* aux = nullptr) {
     CocoPlan::W& w = P.w;
-    const int B = P.B, rows = n * B, D2 = 2 * P.D;
+    const int rows = n * P.B, D2 = 2 * P.D;
     const float ms = 1.f / (1.f - DROP_P);
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
     switch (kind) {
-    case CO_ENC_CONV1: {   // conv1 + Swish (no BatchNorm): raw and activated outputs
-        GatherPlan pl = dense_plan(B * 256, 48, 48, 64);
-        GemmParams g = gemm_of(P, pl, P.conv[0].pk_fwd, 1, B * 256);
-        g.c.A = w.patches1; g.out_bf = w.r1; g.ldo = 64; g.out_act_bf = w.a1; g.e_act = ACT_SWISH;
-        return g;
-    }
-    case CO_ENC_CONV: {
-        const ConvL& L = P.conv[l];
-        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, 1, B, L.pk_fwd_f);
-        g.c.A = a[l - 1];
-        g.out_bf = r[l]; g.ldo = L.g.Cout;
-        g.colstats = training ? w.st_e[l - 1] : nullptr;
-        return g;
-    }
-    case CO_ENC_CONV_DGRAD: {
-        const ConvL& L = P.conv[l];
-        GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
-        d.c.A = dr[l]; d.out_bf = dr[l - 1]; d.ldo = L.g.Cin;
-        d.d_r = r[l - 1]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-        if (l > 1) { d.d_affine = w.aff_e[l - 2]; d.d_meanrstd = w.mr_e[l - 2]; d.d_red = w.red_e[l - 2]; }
-        return d;
-    }
-    case CO_FC1: {   // classifier.0 over the NHWC 2x2x512 map (shared by the variants) + Swish + Dropout
-        GatherPlan pl = plan_fwdform(2, 2, 1, 1, 512, 2, 2, 1, 0, HID1, 1, rows);
-        GemmParams g = gemm_of(P, pl, &P.fc[0].pk_fwd, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.bias = P.buf.params + P.fc[0].b_off; g.out_bf = w.y1; g.ldo = HID1;
-        g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (mask) { g.e_mask = mask; g.e_mask_scale = ms; }
-        return g;
-    }
     case CO_FC2: {   // classifier.3 + Swish + Dropout
         GatherPlan pl = dense_plan(rows, HID1, HID1, HID2);
-        GemmParams g = gemm_of(P, pl, &P.fc[1].pk_fwd, 1, rows);
+        GemmParams g = gemm_of(P, pl, &P.fc2.pk_fwd, 1, rows);
         g.c.A = w.ay1;
-        g.bias = P.buf.params + P.fc[1].b_off; g.out_bf = w.y2; g.ldo = HID2;
+        g.bias = P.buf.params + P.fc2.b_off; g.out_bf = w.y2; g.ldo = HID2;
         g.out_act_bf = w.ay2; g.e_act = ACT_SWISH; if (mask) { g.e_mask = mask; g.e_mask_scale = ms; }
         return g;
     }
     case CO_FC3: {   // classifier.6
         GatherPlan pl = dense_plan(rows, HID2, HID2, D2);
-        GemmParams g = gemm_of(P, pl, &P.fc[2].pk_fwd, 1, rows);
+        GemmParams g = gemm_of(P, pl, &P.fc3.pk_fwd, 1, rows);
         g.c.A = w.ay2;
-        g.bias = P.buf.params + P.fc[2].b_off; g.out_f = (float*)aux; g.ldo = D2;
+        g.bias = P.buf.params + P.fc3.b_off; g.out_f = (float*)aux; g.ldo = D2;
         return g;
     }
     case CO_FC3_DGRAD: {   // classifier.6: its column sums are the bias gradient of classifier.3
         GatherPlan pd = dense_plan(rows, D2, D2, HID2);
-        GemmParams d = gemm_of(P, pd, &P.fc[2].pk_dgrad, 1, rows);
+        GemmParams d = gemm_of(P, pd, &P.fc3.pk_dgrad, 1, rows);
         d.c.A = (const bf16*)aux; d.out_bf = w.dy2; d.ldo = HID2;
         d.d_r = w.y2; d.d_ld = HID2; d.d_act = ACT_SWISH; if (mask) { d.d_mask = mask; d.d_mask_scale = ms; }
-        d.d_colsum = P.buf.grads + P.fc[1].b_off;
+        d.d_colsum = P.buf.grads + P.fc2.b_off;
         return d;
     }
     case CO_FC2_DGRAD: {   // classifier.3: its column sums are the bias gradient of classifier.0
         GatherPlan pd = dense_plan(rows, HID2, HID2, HID1);
-        GemmParams d = gemm_of(P, pd, &P.fc[1].pk_dgrad, 1, rows);
+        GemmParams d = gemm_of(P, pd, &P.fc2.pk_dgrad, 1, rows);
         d.c.A = w.dy2; d.out_bf = w.dy1; d.ldo = HID1;
         d.d_r = w.y1; d.d_ld = HID1; d.d_act = ACT_SWISH; if (mask) { d.d_mask = mask; d.d_mask_scale = ms; }
-        d.d_colsum = P.buf.grads + P.fc[0].b_off;
-        return d;
-    }
-    case CO_FC1_DGRAD: {   // classifier.0: the input gradient is one dense GEMM over NHWC columns
-        GatherPlan pd = dense_plan(rows, HID1, HID1, FEAT);
-        GemmParams d = gemm_of(P, pd, &P.fc1_dgrad, 1, rows);
-        d.c.A = w.dy1; d.out_bf = w.db4; d.ldo = FEAT;
-        d.d_r = w.r4; d.d_ld = FEAT; d.d_bcast_n = B; d.d_act = ACT_SWISH; d.d_cmod = 512;
-        d.d_affine = w.aff_e[2]; d.d_meanrstd = w.mr_e[2]; d.d_red = w.red_e[2];
-        return d;
-    }
-    case CO_UP: {
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
-        GemmParams g = gemm_of(P, pl, &P.up.pk_fwd, 1, rows);
-        g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = FEAT; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
-        return g;
-    }
-    case CO_UP_DGRAD: {
-        GatherPlan pd = dense_plan(rows, FEAT, FEAT, P.D);
-        GemmParams d = gemm_of(P, pd, &P.up.pk_dgrad, 1, rows);
-        d.c.A = w.du; d.out_f = (float*)aux; d.ldo = P.D;
-        return d;
-    }
-    case CO_DEC_CONVT: {
-        const ConvL& L = P.convT[l];
-        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, n, B, L.pk_fwd_f);
-        g.c.A = aq[l];
-        g.out_bf = q[l + 1]; g.ldo = L.g.Cout;
-        g.colstats = training ? w.st_d[l] : nullptr;
-        return g;
-    }
-    case CO_DEC_CONVT_DGRAD: {
-        const ConvL& L = P.convT[l];
-        GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, n, B, L.pk_dgrad_f);
-        d.c.A = dq[l + 1]; d.out_bf = dq[l]; d.ldo = L.g.Cin;
-        d.d_r = q[l]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-        if (l > 0) { d.d_affine = w.aff_d[l - 1]; d.d_meanrstd = w.mr_d[l - 1]; d.d_red = w.red_d[l - 1]; }
-        return d;
-    }
-    case CO_DEC_LAST_DGRAD: {   // input gradient = dense GEMM patches x W with d-Swish + BatchNorm-backward sums in the epilogue
-        GatherPlan pd = dense_plan(B * 256, 48, 48, 64);
-        GemmParams d = gemm_of(P, pd, P.convT[3].pk_dgrad, n, B * 256);
-        d.c.A = w.patches4; d.out_bf = w.d3; d.ldo = 64;
-        d.d_r = w.q3; d.d_ld = 64; d.d_act = ACT_SWISH; d.d_affine = w.aff_d[2]; d.d_meanrstd = w.mr_d[2]; d.d_red = w.red_d[2];
+        d.d_colsum = P.buf.grads + P.fc1.b_off;
         return d;
     }
     }
@@ -288,192 +161,52 @@ GemmParams layer_gemm(CocoPlan& P, CoGemm kind, int l, int n, int training = 1, 
 }
 
 // aux: CO_W_FC3 the operand d_out [n*B][2D]
-WgradParams layer_wgrad(CocoPlan& P, CoWgrad kind, int l, int n, const bf16* aux = nullptr) {
+WgradParams layer_wgrad(CocoPlan& P, CoWgrad kind, int n, const bf16* aux = nullptr) {
     CocoPlan::W& w = P.w;
-    const int B = P.B, rows = n * B;
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    switch (kind) {
-    case CO_W_ENC_CONV1: {   // conv1 wgrad over the im2col patches
-        GatherPlan pl = dense_plan(B * 256, 48, 48, 64);
-        WgradParams g = wgrad_of(P, pl, P.conv[0].gk, 1, B * 256);
-        g.c.A = w.patches1; g.P = w.d1e; g.ldp = 64;
-        return g;
-    }
-    case CO_W_ENC_CONV: {
-        const ConvL& L = P.conv[l];
-        WgradParams g = wgrad_of(P, L.fwd, L.gk, 1, B);
-        g.c.A = a[l - 1]; g.P = dr[l]; g.ldp = L.g.Cout;
-        return g;
-    }
-    case CO_W_FC1: {   // classifier.0: wgrad gathers the shared 2x2x512 map
-        GatherPlan pl = plan_fwdform(2, 2, 1, 1, 512, 2, 2, 1, 0, HID1, 1, rows);
-        WgradParams g = wgrad_of(P, pl, &P.fc[0].gk, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.P = w.dy1; g.ldp = HID1;
-        return g;
-    }
-    case CO_W_FC2: {   // classifier.3
+    const int rows = n * P.B;
+    if (kind == CO_W_FC2) {   // classifier.3
         GatherPlan pl = dense_plan(rows, HID1, HID1, HID2);
-        WgradParams g = wgrad_of(P, pl, &P.fc[1].gk, 1, rows);
+        WgradParams g = wgrad_of(P, pl, &P.fc2.gk, 1, rows);
         g.c.A = w.ay1; g.P = w.dy2; g.ldp = HID2;
         return g;
     }
-    case CO_W_FC3: {   // classifier.6
-        GatherPlan pl = dense_plan(rows, HID2, HID2, 2 * P.D);
-        WgradParams g = wgrad_of(P, pl, &P.fc[2].gk, 1, rows);
-        g.c.A = w.ay2; g.P = aux; g.ldp = 2 * P.D;
-        return g;
-    }
-    case CO_W_UP: {   // upsample Linear: weight (+ folded bias) gradient
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, FEAT);
-        WgradParams g = wgrad_of(P, pl, &P.up.gk, 1, rows);
-        g.c.A = w.z_bf; g.P = w.du; g.ldp = FEAT;
-        return g;
-    }
-    case CO_W_DEC_CONVT:
-        return convT_wgrad(P, P.convT[l], n, B, aq[l], dq[l + 1]);
-    case CO_W_DEC_LAST: {   // last transposed conv (64 -> 3) through the im2col patches of dlogit (K = 16 taps x 3)
-        GatherPlan pl = plan_fwdform(1, 1, 16, 16, 48, 1, 1, 1, 0, 64, n, B);   // rows (n, iy, ix), dense K=48
-        WgradParams g = wgrad_of(P, pl, P.convT[3].gk, n, B);
-        g.c.A = w.patches4; g.c.AH = 16; g.c.AW = 16; g.c.sy = g.c.sx = 1;
-        g.P = w.aq3; g.ldp = 64;
-        return g;
-    }
-    }
-    return WgradParams{};
-}
-
-// ---- the stand-alone passes
-// image [B][3][32][32] -> patches1 [B*256][48];  dlogit [groups*B][3][32][32] -> patches4 [groups*B*256][48]: the same kernel with
-// the same arguments except the row count
-int im2col_image(CocoPlan& P, const float* image, hipStream_t s) {
-    return launch_im2col_small(image, P.B, 3, IMG, IMG, 4, 4, 2, 1, 16, 16, P.w.patches1, 48, s);
-}
-int im2col_dlogit(CocoPlan& P, const float* dlogit, int groups, hipStream_t s) {
-    return launch_im2col_small(dlogit, groups * P.B, 3, IMG, IMG, 4, 4, 2, 1, 16, 16, P.w.patches4, 48, s);
-}
-// BatchNorm + Swish behind conv[l] (l = 1..3) / convT[l] (l = 0..2): tables, running statistics, activated tensor
-int enc_bn_act(CocoPlan& P, int l, int bn_updates, int training, hipStream_t s) {
-    CocoPlan::W& w = P.w;
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    const ConvL& L = P.conv[l];
-    const int rows = P.B * L.g.OH * L.g.OW;
-    return bn_act(P, P.bn[L.bn], r[l], a[l], rows, rows, 1, w.st_e[l - 1], bn_updates, w.aff_e[l - 1], w.mr_e[l - 1], training, s);
-}
-int dec_bn_act(CocoPlan& P, int l, int groups, int training, hipStream_t s) {
-    CocoPlan::W& w = P.w;
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    const ConvL& L = P.convT[l];
-    const int rpg = P.B * L.g.OH * L.g.OW;
-    return bn_act(P, P.bn[L.bn], q[l + 1], aq[l + 1], groups * rpg, rpg, groups, w.st_d[l], 1, w.aff_d[l], w.mr_d[l], training, s);
-}
-// BatchNorm backward behind conv[l] / convT[l]; features.9 (l = 3) sums the gradients of the 2 classifier variants (db2)
-BnBwdApplyArgs enc_bn_bwd_args(CocoPlan& P, int l, int variants) {
-    CocoPlan::W& w = P.w;
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    const int B = P.B;
-    const ConvL& L = P.conv[l];
-    const BnL& b = P.bn[L.bn];
-    const int pix = L.g.OH * L.g.OW;
-    BnBwdApplyArgs x{};
-    x.db = (l == 3) ? w.db4 : dr[l];
-    x.db2 = (l == 3 && variants == 2) ? w.db4 + (size_t)B * FEAT : nullptr;
-    x.r = r[l]; x.dr = dr[l]; x.rows = B * pix; x.C = L.g.Cout; x.ld = L.g.Cout; x.rows_per_group = B * pix; x.G = 1;
-    x.red = w.red_e[l - 1]; x.meanrstd = w.mr_e[l - 1]; x.gamma = P.buf.params + b.w_off;
-    x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
-    return x;
-}
-BnBwdApplyArgs dec_bn_bwd_args(CocoPlan& P, int l, int groups) {
-    CocoPlan::W& w = P.w;
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    const int B = P.B, rows = groups * B;
-    const ConvL& L = P.convT[l];
-    const BnL& b = P.bn[L.bn];
-    const int pix = L.g.OH * L.g.OW;
-    BnBwdApplyArgs x{};
-    x.db = dq[l + 1]; x.r = q[l + 1]; x.dr = dq[l + 1]; x.rows = rows * pix; x.C = L.g.Cout; x.ld = L.g.Cout;
-    x.rows_per_group = B * pix; x.G = groups;
-    x.red = w.red_d[l]; x.meanrstd = w.mr_d[l]; x.gamma = P.buf.params + b.w_off;
-    x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
-    return x;
-}
-// last transposed conv (64 -> 3) + sigmoid + BCE: `last` carries the caller's target / outputs / loss weights
-ConvTLastFwdArgs dec_last_args(CocoPlan& P, const ConvTLastFwdArgs& last, int groups) {
-    ConvTLastFwdArgs x = last;
-    x.act = P.w.aq3; x.w = P.buf.params + P.convT[3].w_off; x.G = groups; x.B = P.B; x.IH = 16; x.IW = 16; x.Cin = 64; x.Cout = 3;
-    return x;
+    GatherPlan pl = dense_plan(rows, HID2, HID2, 2 * P.D);   // classifier.6
+    WgradParams g = wgrad_of(P, pl, &P.fc3.gk, 1, rows);
+    g.c.A = w.ay2; g.P = aux; g.ldp = 2 * P.D;
+    return g;
 }
 
 // ================================================================== image encoder (coco/model.py:182-187)
 int enc_fwd(CocoPlan& P, const float* image, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, int training,
             int bn_updates, float* out, hipStream_t s) {
-    MMVAE_TRY(im2col_image(P, image, s));
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_ENC_CONV1, 0, 1), s));
-    for (int l = 1; l < 4; ++l) {
-        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_ENC_CONV, l, 1, training), s));
-        MMVAE_TRY(enc_bn_act(P, l, bn_updates, training, s));
-    }
+    MMVAE_TRY(tower_enc_fwd(P, image, training, bn_updates, s));
     const bool drop = training && dropout;
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC1, 0, variants, training, drop ? m1 : nullptr), s));
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC2, 0, variants, training, drop ? m2 : nullptr), s));
-    return launch_gemm_gather(layer_gemm(P, CO_FC3, 0, variants, training, nullptr, out), s);
+    MMVAE_TRY(launch_gemm_gather(tower_gemm(P, TW_FC1, 0, variants, training, drop ? m1 : nullptr), s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC2, variants, drop ? m2 : nullptr), s));
+    return launch_gemm_gather(layer_gemm(P, CO_FC3, variants, nullptr, out), s);
 }
 
 // d_out: bf16 [variants*B][2D]; the bias gradient of classifier.6 must already be accumulated by the caller
 int enc_bwd(CocoPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, hipStream_t s) {
     // classifier.6
-    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_FC3, 0, variants, d_out), s));
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC3_DGRAD, 0, variants, 1, dropout ? m2 : nullptr, d_out), s));
+    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_FC3, variants, d_out), s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC3_DGRAD, variants, dropout ? m2 : nullptr, d_out), s));
     // classifier.3
-    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_FC2, 0, variants), s));
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC2_DGRAD, 0, variants, 1, dropout ? m1 : nullptr), s));
+    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_FC2, variants), s));
+    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC2_DGRAD, variants, dropout ? m1 : nullptr), s));
     // classifier.0: wgrad gathers the shared 2x2x512 map; the input gradient is one dense GEMM over NHWC columns
-    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_FC1, 0, variants), s));
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_FC1_DGRAD, 0, variants), s));
-    for (int l = 3; l >= 1; --l) {
-        MMVAE_TRY(launch_bn_bwd_apply(enc_bn_bwd_args(P, l, variants), s));
-        MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_ENC_CONV, l, 1), s));
-        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_ENC_CONV_DGRAD, l, 1), s));
-    }
-    // conv1 wgrad over the im2col patches
-    return wgrad_async(P, layer_wgrad(P, CO_W_ENC_CONV1, 0, 1), s);
+    MMVAE_TRY(wgrad_async(P, tower_wgrad(P, TW_W_FC1, 0, variants), s));
+    MMVAE_TRY(launch_gemm_gather(tower_gemm(P, TW_FC1_DGRAD, 0, variants), s));
+    return tower_enc_bwd(P, variants, s);
 }
 
 // ================================================================== image decoder (coco/model.py:211-216)
 // last == nullptr (coco_iw_score): the body only -- it ends with the raw output of hallucinate.6 in q3, whose BatchNorm + Swish
 // belong to the caller's own tail
 int dec_fwd(CocoPlan& P, int groups, int training, ConvTLastFwdArgs* last, hipStream_t s) {
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_UP, 0, groups), s));
-    for (int l = 0; l < 3; ++l) {
-        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_DEC_CONVT, l, groups, training), s));
-        if (l == 2 && !last) continue;
-        MMVAE_TRY(dec_bn_act(P, l, groups, training, s));
-    }
+    MMVAE_TRY(tower_dec_fwd(P, groups, training, last != nullptr, s));
     if (!last) return MMVAE_OK;
     return launch_convt_last_fwd(dec_last_args(P, *last, groups), s);
-}
-
-// dlogit: fp32 NCHW [groups*B][3][32][32] (grad wrt the pre-sigmoid logits). Writes dz (fp32 [groups*B][D]).
-int dec_bwd(CocoPlan& P, const float* dlogit, int groups, float* dz, hipStream_t s) {
-    // last transposed conv (64 -> 3): both gradients go through the im2col patches of dlogit (K = 16 taps x 3)
-    MMVAE_TRY(im2col_dlogit(P, dlogit, groups, s));
-    MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_DEC_LAST_DGRAD, 3, groups), s));
-    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_DEC_LAST, 3, groups), s));
-    for (int l = 2; l >= 0; --l) {
-        MMVAE_TRY(launch_bn_bwd_apply(dec_bn_bwd_args(P, l, groups), s));
-        MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_DEC_CONVT, l, groups), s));
-        MMVAE_TRY(launch_gemm_gather(layer_gemm(P, CO_DEC_CONVT_DGRAD, l, groups), s));
-    }
-    // upsample Linear: weight (+ folded bias) gradient and dz
-    MMVAE_TRY(wgrad_async(P, layer_wgrad(P, CO_W_UP, 0, groups), s));
-    return launch_gemm_gather(layer_gemm(P, CO_UP_DGRAD, 0, groups, 1, nullptr, dz), s);
 }
 
 int use_ws(CocoPlan* P, void* ws, size_t bytes, bool module = true) {
@@ -602,12 +335,12 @@ static int coco_step_body(CocoPlan* Pp, const mmvae_coco_step_io& io, int traini
     int img_groups = 3;
     while (img_groups > 0 && (io.lambda_xy[img_groups - 1] == 0.f || sk[img_groups - 1])) --img_groups;
     int rc = MMVAE_OK;
-    if (img_groups > 0) rc = dec_bwd(P, w.dlogit, img_groups, w.dz_img, s);
+    if (img_groups > 0) rc = tower_dec_bwd(P, w.dlogit, img_groups, w.dz_img, s);
     if (rc == MMVAE_OK) rc = edge(P, Tx, s);          // dz of the caption decoder
     Latent3BwdArgs lb{};
     lb.f = la; lb.dz_a = w.dz_img; lb.dz_b = w.dz_txt;
     for (int k = 0; k < 3; ++k) lb.kl_coef[k] = sk[k] ? 0.f : io.kl_lambda / (float)B;
-    lb.d_img_out_bf = w.d_encout; lb.d_img_bias = P.buf.grads + P.fc[2].b_off;
+    lb.d_img_out_bf = w.d_encout; lb.d_img_bias = P.buf.grads + P.fc3.b_off;
     lb.d_txt_out = w.d_txtout;
     if (rc == MMVAE_OK) rc = launch_latent3_bwd(lb, s);
     if (rc == MMVAE_OK) rc = edge(P, s, Tx);
@@ -640,7 +373,7 @@ int coco_image_encoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* d_out
     const int rows = P->B, D2 = 2 * P->D;
     MMVAE_TRY(plan_zero_gpk(*P, s));
     MMVAE_TRY(launch_cast_bf16(d_out, (long long)rows * D2, w.d_encout, s));
-    MMVAE_TRY(launch_colsum_f32(d_out, rows, D2, P->buf.grads + P->fc[2].b_off, s));
+    MMVAE_TRY(launch_colsum_f32(d_out, rows, D2, P->buf.grads + P->fc3.b_off, s));
     MMVAE_TRY(enc_bwd(*P, w.d_encout, 1, m1, m2, m1 != nullptr && m2 != nullptr, s));
     return plan_unpack(*P, s, true);
 }
@@ -662,7 +395,7 @@ int coco_image_decoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* d_rec
     MMVAE_TRY(plan_zero_gpk(*P, s));
     hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, d_recon, recon, n, w.tmp_f32);
     MMVAE_TRY(mmvae_check_launch("sigmoid_bwd"));
-    MMVAE_TRY(dec_bwd(*P, w.tmp_f32, 1, dz, s));
+    MMVAE_TRY(tower_dec_bwd(*P, w.tmp_f32, 1, dz, s));
     return plan_unpack(*P, s, true);
 }
 int coco_text_encoder_fwd(CocoPlan* P, void* ws, size_t wsb, const float* text, float* out, hipStream_t s) {
@@ -707,29 +440,22 @@ int coco_iw_score(CocoPlan* P, void* ws, size_t wsb, const float* z, const float
     CocoPlan::W& w = P->w;
     const int rows = B * K;
     MMVAE_TRY(zero_ws(*P, s));
-    hipLaunchKernelGGL(cast_z_kernel, dim3(ceil_div(rows * P->ldz, 256)), dim3(256), 0, s, z, rows, P->D, w.z_bf, P->ldz);
-    MMVAE_TRY(mmvae_check_launch("cast_z"));
+    MMVAE_TRY(tower_iw_particles(*P, z, rows, s));
     const float* zt = z;
-    if (rows < P->B) {    // the decoders run the plan's rows: the ones past B*K are defined (zero) and never scored
-        MMVAE_TRY(launch_fill_zero(w.z_bf + (size_t)rows * P->ldz, (size_t)(P->B - rows) * P->ldz * sizeof(bf16), s));
+    if (rows < P->B) {    // the caption decoder runs the plan's rows as well: its fp32 particles get the same zero rows
         MMVAE_TRY(launch_fill_zero(w.z_f32, (size_t)P->B * P->D * sizeof(float), s));
         MMVAE_REQUIRE(hipMemcpyAsync(w.z_f32, z, (size_t)rows * P->D * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess,
                       "mmvae_coco_iw_score: copy of the particles failed");
         zt = w.z_f32;
     }
     MMVAE_TRY(dec_fwd(*P, 1, 0, nullptr, s));
-    const BnL& b = P->bn[P->convT[2].bn];
-    CocoIwTailArgs t{};
-    t.q3 = w.q3; t.gamma = P->buf.params + b.w_off; t.beta = P->buf.params + b.b_off;
-    t.rmean = P->buf.bn_stats + b.stat_off; t.rvar = t.rmean + b.C; t.eps = BN_EPS;
-    t.act = ACT_SWISH; t.w = P->buf.params + P->convT[3].w_off; t.image = image; t.rows = rows; t.K = K; t.loglik = loglik_x;
-    MMVAE_TRY(launch_coco_iw_tail(t, s));
+    MMVAE_TRY(launch_coco_iw_tail(tower_iw_tail_args(*P, image, rows, K, loglik_x), s));
     MMVAE_TRY(coco_text_dec_fwd(*P, zt, 1, sos, nullptr, 0, w.td_recon, s));
     return launch_coco_iw_text_sse(w.td_recon, text, B, K, P->T, sse_y, s);
 }
 
 // ---------------------------------------------------------------- test / profiling aid: replay one launch of the step
-// The launches of layer_gemm / layer_wgrad and the stand-alone passes under names: <layer>, <layer>_dgrad, <layer>_wgrad, enc_bn<l> /
+// The tower's names (img_tower.h tower_named_gemm / tower_named_wgrad), fc2 / fc3 (+ _dgrad, _wgrad) and the stand-alone passes: enc_bn<l> /
 // dec_bn<l> (+ _bwd), im2col_dlogit, dec_last_fwd.  The classifier runs its 2 dropout variants, the decoder 3 passes forward and
 // backward (the default step), BatchNorm makes the running-statistics updates of the default step (encoder 2, decoder 1 per
 // group).  Knob "coco_layer_mask" (0): the keep flags in W::m1 / W::m2 take part in fc1 / fc2 / fc3_dgrad / fc2_dgrad as in a step
@@ -741,40 +467,17 @@ static bool named_gemm(CocoPlan& P, const std::string& name, GemmParams& g) {
     CocoPlan::W& w = P.w;
     const bool masked = mmvae_knob("coco_layer_mask", 0) != 0;
     const uint8_t *m1 = masked ? w.m1 : nullptr, *m2 = masked ? w.m2 : nullptr;
-    if (name == "enc_conv1") { g = layer_gemm(P, CO_ENC_CONV1, 0, 1); return true; }
-    for (int l = 1; l < 4; ++l) {
-        const std::string n = "enc_conv" + std::to_string(l + 1);
-        if (name == n) { g = layer_gemm(P, CO_ENC_CONV, l, 1); return true; }
-        if (name == n + "_dgrad") { g = layer_gemm(P, CO_ENC_CONV_DGRAD, l, 1); return true; }
-    }
-    if (name == "fc1") { g = layer_gemm(P, CO_FC1, 0, 2, 1, m1); return true; }
-    if (name == "fc2") { g = layer_gemm(P, CO_FC2, 0, 2, 1, m2); return true; }
-    if (name == "fc3") { g = layer_gemm(P, CO_FC3, 0, 2, 1, nullptr, w.encout); return true; }
-    if (name == "fc3_dgrad") { g = layer_gemm(P, CO_FC3_DGRAD, 0, 2, 1, m2, w.d_encout); return true; }
-    if (name == "fc2_dgrad") { g = layer_gemm(P, CO_FC2_DGRAD, 0, 2, 1, m1); return true; }
-    if (name == "fc1_dgrad") { g = layer_gemm(P, CO_FC1_DGRAD, 0, 2); return true; }
-    if (name == "up") { g = layer_gemm(P, CO_UP, 0, 3); return true; }
-    if (name == "up_dgrad") { g = layer_gemm(P, CO_UP_DGRAD, 0, 3, 1, nullptr, w.dz_img); return true; }
-    for (int l = 0; l < 3; ++l) {
-        const std::string n = "dec_convT" + std::to_string(l + 1);
-        if (name == n) { g = layer_gemm(P, CO_DEC_CONVT, l, 3); return true; }
-        if (name == n + "_dgrad") { g = layer_gemm(P, CO_DEC_CONVT_DGRAD, l, 3); return true; }
-    }
-    if (name == "dec_last_dgrad_gemm") { g = layer_gemm(P, CO_DEC_LAST_DGRAD, 3, 3); return true; }
-    return false;
+    if (name == "fc2") { g = layer_gemm(P, CO_FC2, 2, m2); return true; }
+    if (name == "fc3") { g = layer_gemm(P, CO_FC3, 2, nullptr, w.encout); return true; }
+    if (name == "fc3_dgrad") { g = layer_gemm(P, CO_FC3_DGRAD, 2, m2, w.d_encout); return true; }
+    if (name == "fc2_dgrad") { g = layer_gemm(P, CO_FC2_DGRAD, 2, m1); return true; }
+    GatherTransform tr{};      // (no staged names here: never filled)
+    return tower_named_gemm(P, name, m1, w.dz_img, false, g, tr);
 }
 static bool named_wgrad(CocoPlan& P, const std::string& name, WgradParams& g) {
-    if (name == "enc_conv1_wgrad") { g = layer_wgrad(P, CO_W_ENC_CONV1, 0, 1); return true; }
-    for (int l = 1; l < 4; ++l)
-        if (name == "enc_conv" + std::to_string(l + 1) + "_wgrad") { g = layer_wgrad(P, CO_W_ENC_CONV, l, 1); return true; }
-    if (name == "fc1_wgrad") { g = layer_wgrad(P, CO_W_FC1, 0, 2); return true; }
-    if (name == "fc2_wgrad") { g = layer_wgrad(P, CO_W_FC2, 0, 2); return true; }
-    if (name == "fc3_wgrad") { g = layer_wgrad(P, CO_W_FC3, 0, 2, P.w.d_encout); return true; }
-    if (name == "up_wgrad") { g = layer_wgrad(P, CO_W_UP, 0, 3); return true; }
-    for (int l = 0; l < 3; ++l)
-        if (name == "dec_convT" + std::to_string(l + 1) + "_wgrad") { g = layer_wgrad(P, CO_W_DEC_CONVT, l, 3); return true; }
-    if (name == "dec_last_wgrad") { g = layer_wgrad(P, CO_W_DEC_LAST, 3, 3); return true; }
-    return false;
+    if (name == "fc2_wgrad") { g = layer_wgrad(P, CO_W_FC2, 2); return true; }
+    if (name == "fc3_wgrad") { g = layer_wgrad(P, CO_W_FC3, 2, P.w.d_encout); return true; }
+    return tower_named_wgrad(P, name, g);
 }
 // 1: launched, 0: not a stand-alone pass, < 0: error
 static int named_pass(CocoPlan& P, const std::string& name, hipStream_t s) {
@@ -806,14 +509,7 @@ int coco_bench_layer(CocoPlan* P, void* ws, size_t wsb, const char* layer, int i
     MMVAE_REQUIRE(P && layer, "mmvae_coco_bench_layer: null argument");
     MMVAE_TRY(use_ws(P, ws, wsb, false));
     WgradParams wg{};
-    if (named_wgrad(*P, layer, wg)) {            // kernel + its share of the slab reduction, as in the step
-        for (int i = 0; i < iters; ++i) {
-            P->slab.reset(P->w.slab, P->w.slab_floats);
-            MMVAE_TRY(launch_wgrad(wg, s, &P->slab));
-            MMVAE_TRY(launch_wgrad_reduce(&P->slab, s));
-        }
-        return MMVAE_OK;
-    }
+    if (named_wgrad(*P, layer, wg)) return tower_replay_wgrad(*P, wg, iters, s);
     GemmParams g{};
     if (named_gemm(*P, layer, g)) {
         for (int i = 0; i < iters; ++i) MMVAE_TRY(launch_gemm_gather(g, s));
@@ -833,23 +529,8 @@ long long coco_debug_offset(CocoPlan* P, const char* name) {
     P->carve_passes = 3; P->carve_iw = false;
     carve(*P, ws);
     CocoPlan::W& w = P->w;
-    const std::map<std::string, const void*> m = {
-        {"patches1", w.patches1}, {"r1", w.r1}, {"r2", w.r2}, {"r3", w.r3}, {"r4", w.r4},
-        {"a1", w.a1}, {"a2", w.a2}, {"a3", w.a3}, {"a4", w.a4}, {"y1", w.y1}, {"ay1", w.ay1}, {"y2", w.y2}, {"ay2", w.ay2},
-        {"encout", w.encout}, {"m1", w.m1}, {"m2", w.m2},
-        {"z_bf", w.z_bf}, {"z_f32", w.z_f32}, {"u", w.u}, {"au", w.au}, {"q1", w.q1}, {"q2", w.q2}, {"q3", w.q3},
-        {"aq1", w.aq1}, {"aq2", w.aq2}, {"aq3", w.aq3}, {"dlogit", w.dlogit}, {"patches4", w.patches4},
-        {"d3", w.d3}, {"d2", w.d2}, {"d1", w.d1}, {"du", w.du}, {"dz_img", w.dz_img},
-        {"d_encout", w.d_encout}, {"dy2", w.dy2}, {"dy1", w.dy1}, {"db4", w.db4}, {"dr4", w.dr4},
-        {"d3e", w.d3e}, {"d2e", w.d2e}, {"d1e", w.d1e}, {"tmp_f32", w.tmp_f32}, {"slab", w.slab}, {"sums", w.sums},
-        {"st_e0", w.st_e[0]}, {"st_e1", w.st_e[1]}, {"st_e2", w.st_e[2]}, {"st_d0", w.st_d[0]}, {"st_d1", w.st_d[1]}, {"st_d2", w.st_d[2]},
-        {"red_e0", w.red_e[0]}, {"red_e1", w.red_e[1]}, {"red_e2", w.red_e[2]},
-        {"red_d0", w.red_d[0]}, {"red_d1", w.red_d[1]}, {"red_d2", w.red_d[2]},
-        {"aff_e0", w.aff_e[0]}, {"aff_e1", w.aff_e[1]}, {"aff_e2", w.aff_e[2]},
-        {"aff_d0", w.aff_d[0]}, {"aff_d1", w.aff_d[1]}, {"aff_d2", w.aff_d[2]},
-        {"mr_e0", w.mr_e[0]}, {"mr_e1", w.mr_e[1]}, {"mr_e2", w.mr_e[2]}, {"mr_d0", w.mr_d[0]}, {"mr_d1", w.mr_d[1]}, {"mr_d2", w.mr_d[2]},
-    };
-    auto it = m.find(name);
-    if (it == m.end()) return -1;
-    return (long long)((const char*)it->second - (const char*)0x1000);
+    std::map<std::string, const void*> m = tower_debug_names(w);
+    m.insert({{"y2", w.y2}, {"ay2", w.ay2}, {"encout", w.encout}, {"m1", w.m1}, {"m2", w.m2}, {"z_f32", w.z_f32}, {"dz_img", w.dz_img},
+              {"d_encout", w.d_encout}, {"dy2", w.dy2}, {"tmp_f32", w.tmp_f32}, {"sums", w.sums}});
+    return tower_offset_of(m, name, (const void*)0x1000);
 }

@@ -38,7 +38,7 @@ __device__ __forceinline__ float tail_act(int act, float v) {
     return v;
 }
 
-__global__ __launch_bounds__(T_NTHR) void coco_iw_tail_kernel(const CocoIwTailArgs a) {
+__global__ __launch_bounds__(T_NTHR) void coco_iw_tail_kernel(const IwTailArgs a) {
     __shared__ float P_s[T_NPIX * T_PF];
     __shared__ float2 aff_s[T_C];
     __shared__ double part[T_WAVES];
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(S_NTHR) void coco_iw_text_sse_kernel(const float* _
 
 }  // namespace
 
-int launch_coco_iw_tail(const CocoIwTailArgs& a, hipStream_t s) {
+int launch_coco_iw_tail(const IwTailArgs& a, hipStream_t s) {
     MMVAE_REQUIRE(a.q3 && a.w && a.image && a.loglik, "coco_iw_tail: null argument");
     MMVAE_REQUIRE(a.affine || (a.gamma && a.beta && a.rmean && a.rvar), "coco_iw_tail: neither an affine table nor BatchNorm buffers");
     MMVAE_REQUIRE(a.act == ACT_NONE || a.act == ACT_SWISH || a.act == ACT_RELU, "coco_iw_tail: unknown activation %d", a.act);

@@ -1,7 +1,7 @@
 // Private: the COCO plan object shared by coco.hip (image half, step, entry points) and coco_text.hip (caption GRUs, fp32).
 #pragma once
 #include "coco.h"
-#include "plan_base.h"
+#include "img_tower.h"
 
 constexpr int COCO_E = 300, COCO_H = 200, COCO_G = 3 * COCO_H;
 
@@ -92,12 +92,9 @@ int launch_coco_dout_combine(const float* dw, const float* fb, int T, int R, bf1
 // dw16[r*320 + e] = bf16(dw[r*300 + e]), pad columns zero (rows = R*T)
 int launch_coco_dw16(const float* dw, long long rows, bf16* dw16, hipStream_t s);
 
-struct CocoPlan : PlanBase {
-    int ldz, T;
-    ConvL conv[4], convT[4];
-    LinL fc[3], up;
-    int fc1_dgrad;
-    BnL bn[6];
+struct CocoPlan : TowerPlan {      // image half: img_tower.h (classifier.0 is its fc1)
+    int T;
+    LinL fc2, fc3;                 // classifier.3, classifier.6
     // caption half: offsets into the flat fp32 parameter buffer (the GEMMs read the weights where they are)
     CocoGru te_f, te_r, td0, td1;
     long long te_h2p_w, te_h2p_b, td_z2h_w, td_z2h_b, td_h2o_w, td_h2o_b;
@@ -116,20 +113,14 @@ struct CocoPlan : PlanBase {
     bool dec_wg_pending = false; const float* dec_wg_z = nullptr; int dec_wg_groups = 0;   // deferred weight gradients of the bf16 decoder
     int tb_ih0, tb_hh0, tb_ih1, tb_hh1, tb_ho, tb_hoT, tb_ih1T, tb_hh1T, tb_hh0T, tb_ih0T, tb_e_hh, tb_e_hhT, tb_e_ihA, tb_e_hhg[3], tb_g_ih0[3], tb_g_hh0[3], tb_g_ih1[3], tb_g_hh1[3];
     int tg_ih0, tg_hh0, tg_ih1, tg_hh1, tg_ho, tg_e_ih, tg_e_hh;
-    struct W {
+    struct W : TowerW {
         char* zero_begin; size_t zero_bytes;
-        float2 *st_e[3], *red_e[3], *st_d[3], *red_d[3];
         float* sums; float* dz_img; float* dz_txt; float* td_dh0; float* td_dh1; float* zeros_h;
-        float2 *aff_e[3], *mr_e[3], *aff_d[3], *mr_d[3];
-        bf16 *patches1, *r1, *r2, *r3, *r4, *a1, *a2, *a3, *a4, *y1, *ay1, *y2, *ay2;
+        bf16 *y2, *ay2;
         float* encout; uint8_t *m1, *m2, *gkeep;
-        float *eps, *mu, *logvar, *z_f32; bf16* z_bf;
-        bf16 *u, *au, *q1, *q2, *q3, *aq1, *aq2, *aq3;
-        float* dlogit;
-        bf16 *patches4, *d3, *d2, *d1, *du;
-        bf16 *d_encout, *dy2, *dy1, *db4, *dr4, *d3e, *d2e, *d1e;
+        float *eps, *mu, *logvar, *z_f32;
+        bf16 *d_encout, *dy2;
         float* tmp_f32;
-        float* slab; size_t slab_floats;
         // caption encoder (B rows)
         float *te_gi, *te_gh, *te_h, *te_sav, *te_gi_r, *te_sav_r, *te_hb, *te_sum, *txtout;
         float *d_txtout, *te_dsum, *te_dh, *te_dgi, *te_dgh, *te_dgi_r;
@@ -145,6 +136,7 @@ struct CocoPlan : PlanBase {
         float *td_wz, *td_bz;
         char* cl_xchg; size_t cl_bytes; char* clb_xchg; size_t clb_bytes;
     } w;
+    CocoPlan() { tw = &w; }
 };
 
 // coco_text.hip

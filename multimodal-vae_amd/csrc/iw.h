@@ -21,4 +21,19 @@ int launch_iw_init(float* state, int B, hipStream_t s);
 // log_w (nullable): [B][K][3] the log weights of the call.
 int launch_iw_accumulate(const float* loglik_x, const float* words, const long long* targets, int T, int V, const float* log_ratio,
                          int B, int K, float* state, float* log_w, hipStream_t s);
+
+// Forward-only image scoring tail of the conv families (celeba_iw.hip, coco_iw.hip; each has a kernel of its own): raw bf16 NHWC
+// [rows][S][S][C] output of hallucinate.6 -> BatchNorm affine + act -> ConvTranspose2d(C, 3, 4, 2, 1) -> one log p(x|z) per row
+// against image [rows / K].  CelebA: S = C = 32, COCO: S = 16, C = 64.  The affine is either the table `affine` [C] (scale,
+// shift) or, when that is null, made from gamma / beta / running mean / running variance [C] each.
+struct IwTailArgs {
+    const bf16* q3; const float2* affine;
+    const float *gamma, *beta, *rmean, *rvar; float eps;
+    int act;
+    const float* w;                  // (C, 3, 4, 4) fp32
+    const float* image;              // [rows / K][3][2S][2S]
+    int rows, K;
+    float* loglik;                   // [rows]
+    float* logits;                   // [rows][3][2S][2S] or null
+};
 int launch_iw_finalize(const float* state, int B, long long K_total, float* out, hipStream_t s);

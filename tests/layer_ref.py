@@ -256,7 +256,7 @@ def describe_mismatch(got, ref, limit=6):
 # the library's defaults of the knobs the tests set, restored after every test: csrc/convres.hip try_launch_convres ("convres" 1,
 # "convres_alt" 0), csrc/wgrad_ring.hip try_launch_wgrad_ring ("wgrad_ring" 1), try_wr ("wr_pair" 0, "wr_atomic_kb" 256) -- a changed
 # default there must be changed here (and in tests/test_gpu_wgrad_ring.py)
-# (celeba_layer_mask / coco_layer_mask: csrc/celeba.hip / csrc/coco.hip named_gemm, the keep masks of the replayed classifier layers)
+# (celeba_layer_mask / coco_layer_mask: csrc/celeba.hip celeba_bench_layer / csrc/coco.hip named_gemm, the keep masks of the replayed classifier layers)
 KNOB_DEFAULTS = {"convres": 1, "convres_alt": 0, "wgrad_ring": 1, "wr_atomic_kb": 256, "wr_pair": 0, "celeba_layer_mask": 0,
                  "coco_layer_mask": 0}
 # (B, layer, knobs, [(tag, kernel)]) of every launch a harness of the family made in this process: what its coverage test reads

@@ -1,7 +1,7 @@
 """Layer-level tests of the CelebA conv, data-gradient and weight-gradient kernels against a float64 reference (plain forms).
 
 One layer of the CelebA step is launched through mmvae_celeba_bench_layer -- which builds its launch parameters with the same
-layer_gemm / layer_wgrad of csrc/celeba.hip the step calls -- on operands this test wrote into the workspace, and compared with
+tower_gemm / tower_wgrad of csrc/img_tower.h (and fc2_dgrad_gemm of csrc/celeba.hip) the step calls -- on operands this test wrote into the workspace, and compared with
 torch.nn.functional.conv2d / conv_transpose2d / linear / torch.autograd in float64 (tests/layer_ref.py), never with another
 engine kernel.  Tiers and gates are those of tests/test_gpu_layers.py, derived there from the number formats:
 Tier A, torch.equal on ternary operands (every product and partial sum an integer below 2^24; asserted on the reference first);

@@ -1,8 +1,8 @@
 """Layer-level tests of the COCO image half -- conv, data-gradient and weight-gradient kernels, the dense layers with their
 permuted packings and the stand-alone passes -- against a float64 reference.
 
-One launch of the COCO step is replayed through mmvae_coco_bench_layer -- which builds its arguments with the same layer_gemm /
-layer_wgrad / pass builders of csrc/coco.hip the step calls -- on operands this test wrote into the workspace, and compared with
+One launch of the COCO step is replayed through mmvae_coco_bench_layer -- which builds its arguments with the same tower_gemm /
+tower_wgrad / pass builders of csrc/img_tower.h and layer_gemm / layer_wgrad of csrc/coco.hip the step calls -- on operands this test wrote into the workspace, and compared with
 torch.nn.functional.conv2d / conv_transpose2d / linear / unfold / batch_norm-style float64 formulas and torch.autograd
 (tests/layer_ref.py), never with another engine kernel.  Tiers and gates are those of tests/test_gpu_layers.py, derived there from
 the number formats:
