@@ -162,7 +162,11 @@ double mmvae_mm_layer_algo_flops(const mmvae_mm_t*, const char* layer);   /* alg
 double mmvae_mm_layer_algo_bytes(const mmvae_mm_t*, const char* layer);   /* algorithmic: each operand read once, the result written once (0: not a conv layer) */
 /* measurement aid: GEMM FLOPs enqueued by this process since the last reset (counted on the host by the launchers) */
 double mmvae_debug_flops(int reset);
-/* test / A-B aid: named integer switches read by the launchers ("convres" = 0 turns the image-resident conv kernels off) */
+/* test / A-B aid: named integer switches read by the launchers ("convres" = 0 turns the image-resident conv kernels off;
+ * "coco_module_bf16" = 1 makes mmvae_coco_text_{encoder,decoder}_{fwd,bwd} run the training step's bf16 persistent caption
+ * kernels on the module's B rows instead of the fp32 ones, 2 the forward ones without saving anything for a backward pass --
+ * the backward entries then return MMVAE_EINVAL; a cluster launch that gave up waiting puts a NaN into element 0 of
+ * sentence / dz.  DESIGN.md 4.4 lists all of them) */
 int mmvae_debug_set(const char* key, int value);
 /* test aid: byte offset of a named intermediate inside the workspace (-1 if unknown) */
 long long mmvae_mm_debug_offset(mmvae_mm_t*, const char* name);

@@ -398,19 +398,59 @@ int coco_image_decoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* d_rec
     MMVAE_TRY(tower_dec_bwd(*P, w.tmp_f32, 1, dz, s));
     return plan_unpack(*P, s, true);
 }
+// Caption modules.  Knob "coco_module_bf16" (0, test aid): 1 runs the bf16 persistent kernels of the training step
+// (coco_text_bf16.hip) on the module's one group of B rows -- packed weights of the current parameters, zeroed packed gradient
+// and its unpack around each backward, the decoder's weight gradients inline; 2 runs the forward kernels without saving
+// anything for a backward pass (the SAVE = false instantiations), and the backward entries refuse.  0: the fp32 kernels of
+// coco_text.hip, as before.
+static int module_bf16() { return mmvae_knob("coco_module_bf16", 0); }
+static int module_pack(CocoPlan& P, hipStream_t s) {
+    return launch_pack(P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec, s);
+}
+// A cluster launch that gave up waiting for a peer set its timeout word: element 0 of the result says so (the step: sum_slots_kernel)
+static __global__ void module_alarm_kernel(const unsigned* alarm, float* out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0 && *alarm) out[0] = __builtin_nanf("");
+}
+static int module_alarm(const unsigned* alarm, float* out, hipStream_t s) {
+    if (!alarm) return MMVAE_OK;
+    hipLaunchKernelGGL(module_alarm_kernel, dim3(1), dim3(64), 0, s, alarm, out);
+    return mmvae_check_launch("module_alarm");
+}
 int coco_text_encoder_fwd(CocoPlan* P, void* ws, size_t wsb, const float* text, float* out, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
     MMVAE_TRY(zero_ws(*P, s));
+    const int mb = module_bf16();
+    if (mb) {
+        MMVAE_REQUIRE(P->text_bf16 && (mb == 1 || mb == 2), "coco_module_bf16 = %d: needs the bf16 caption kernels and a value of 0, 1 or 2", mb);
+        MMVAE_TRY(module_pack(*P, s));
+        return coco_text_enc_fwd(*P, text, mb == 1, out, s, true);
+    }
     return coco_text_enc_fwd(*P, text, 1, out, s, false);
 }
 int coco_text_encoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* text, const float* d_out, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
+    const int mb = module_bf16();
+    if (mb) {
+        MMVAE_REQUIRE(P->text_bf16 && mb == 1, "coco_module_bf16 = %d: the forward pass saved nothing for a backward pass", mb);
+        MMVAE_TRY(module_pack(*P, s));
+        MMVAE_TRY(plan_zero_gpk(*P, s));
+        MMVAE_TRY(coco_text_enc_bwd(*P, text, d_out, s, s, true));
+        return plan_unpack(*P, s, true);
+    }
     return coco_text_enc_bwd(*P, text, d_out, s, s, false);
 }
 int coco_text_decoder_fwd(CocoPlan* P, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, int training,
                           float* sentence, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));
     MMVAE_TRY(zero_ws(*P, s));
+    const int mb = module_bf16();
+    if (mb) {
+        MMVAE_REQUIRE(P->text_bf16 && (mb == 1 || mb == 2), "coco_module_bf16 = %d: needs the bf16 caption kernels and a value of 0, 1 or 2", mb);
+        MMVAE_TRY(module_pack(*P, s));
+        // (use_ws reset comb_fresh: the composed form makes W_comb of the current parameters inside coco_text_dec_fwd)
+        MMVAE_TRY(coco_text_dec_fwd(*P, z, 1, sos, training ? keep : nullptr, mb == 1, sentence, s, true));
+        return module_alarm(P->cl_alarm_f, sentence, s);
+    }
     return coco_text_dec_fwd(*P, z, 1, sos, training ? keep : nullptr, 1, sentence, s);
 }
 int coco_text_decoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* z, const float* sos, const uint8_t* keep, const float* sentence,
@@ -418,6 +458,19 @@ int coco_text_decoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* z, con
     MMVAE_TRY(use_ws(P, ws, wsb));
     CocoPlan::W& w = P->w;
     const size_t n = (size_t)P->B * P->T * COCO_E;
+    const int mb = module_bf16();
+    if (mb) {
+        MMVAE_REQUIRE(P->text_bf16 && mb == 1, "coco_module_bf16 = %d: the forward pass saved nothing for a backward pass", mb);
+        MMVAE_TRY(module_pack(*P, s));
+        MMVAE_TRY(plan_zero_gpk(*P, s));
+        MMVAE_REQUIRE(hipMemcpyAsync(w.td_dw, d_sentence, n * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess,
+                      "coco_text_decoder_bwd: copy of the loss gradient failed");
+        // use_ws left dw16_fresh and comb_fresh false: the composed BPTT makes its bf16 copy of the loss gradient and W_comb^T
+        // itself; sw == s: the weight gradients are issued inline, into the packed gradient
+        MMVAE_TRY(coco_text_dec_bwd(*P, z, 1, sos, keep, sentence, w.td_dw, dz, s, s, true));
+        MMVAE_TRY(plan_unpack(*P, s, true));
+        return module_alarm(P->cl_alarm_b, dz, s);
+    }
     MMVAE_TRY(launch_fill_zero(w.td_dh0, (size_t)P->B * COCO_H * sizeof(float), s));
     MMVAE_TRY(launch_fill_zero(w.td_dh1, (size_t)P->B * COCO_H * sizeof(float), s));
     hipMemcpyAsync(w.td_dw, d_sentence, n * sizeof(float), hipMemcpyDeviceToDevice, s);

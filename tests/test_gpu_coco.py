@@ -1,8 +1,11 @@
 """GPU parity tests of the COCO MMVAE (coco/model.py, coco/train.py:66-84,138-173) through the C-ABI, against the golden
 vectors captured from the reference and the CPU oracle on the same seeded inputs.
 
-Tolerances.  Caption modules alone (fp32 MFMA path, 102 dependent GRU steps): outputs abs 2e-5, every gradient tensor
-rel-L2 2e-4.  Fused step / image modules (bf16 MFMA inputs, fp32 accumulation; B=4 fixtures, BatchNorm over 4 samples):
+Tolerances.  Caption modules alone (test_text_{encoder,decoder}_module_fp32: the module entry points with the knob
+coco_module_bf16 at its default 0, i.e. the fp32 per-step kernels of csrc/coco_text.hip -- gru_layer_fwd / gru_bwd and the fp32
+`lin` GEMMs -- which the training step never launches; 102 dependent GRU steps): outputs abs 2e-5, every gradient tensor
+rel-L2 2e-4.  The step's own caption kernels, the bf16 persistent launches of csrc/coco_text_bf16.hip, are compared with float64
+on their own in tests/test_gpu_coco_text_modules.py.  Fused step / image modules (bf16 MFMA inputs, fp32 accumulation; B=4 fixtures, BatchNorm over 4 samples):
 ELBO losses rel 1e-3 | mu/logvar abs 1e-2 | per-tensor gradient rel-L2 4.5e-2, no absolute slack (tests/gradcheck.py; measured 2.3e-2) | total gradient
 norm rel 1e-2.
 """

@@ -60,8 +60,9 @@ of 3B), and its source is the caller's image pointer, not a workspace buffer: no
 test_coverage reads the probe's records of every compared launch (launcher tag with the instantiation note, kernel text) and
 prints which kernel took which layer at which batch (-s).
 
-What stays with the whole-step tests: launch_latent3_fwd / bwd, the caption half (tests/test_gpu_text_modules.py), batches above
-256."""
+What stays with the whole-step tests: launch_latent3_fwd / bwd and batches above 256.  The caption half -- the bf16 persistent
+kernels of csrc/coco_text_bf16.hip -- has its own float64 suite, tests/test_gpu_coco_text_modules.py (tests/test_gpu_text_modules.py
+is MultiMNIST's: csrc/text.hip)."""
 import re
 
 import pytest
