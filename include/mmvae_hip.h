@@ -451,6 +451,56 @@ int mmvae_coco_iw_tail(const void* q3_bf16, const float* affine, int act, const 
                        float* loglik, float* logits_or_null, void* stream);
 int mmvae_coco_iw_text_sse(const float* sentence, const float* text, int B, int K, int steps, float* sse, void* stream);
 
+/* ---------------------------------------------------------------- image-only VAE baselines (CelebA, COCO)
+ * ImageVAE of celeba/model.py:60-88 and coco/model.py:93-117 -- the family's ImageEncoder and ImageDecoder with reparametrize between
+ * them and NO product of experts -- trained by celeba/train_imageonly.py:95-113 / coco/train_imageonly.py on
+ * loss = lambda_x * BCE(recon, image) / (B * pixels) + kl_lambda * KL / B.  The step runs on the family's existing plan and buffers under the
+ * image_encoder.* / image_decoder.* names of its parameter table; the second modality's parameters are never read, and their
+ * gradients are exactly 0 after a step with do_backward (which includes optimizer.zero_grad(), as the 3-pass steps do).
+ * ONE pass over B rows: encoder with one Dropout variant and one BatchNorm running-statistics update, the one-expert latent block
+ * (mmvae_latent1_*), decoder with one BatchNorm group, sigmoid + BCE, backward.  Workspace: the one-pass carve,
+ * mmvae_<family>_image_step_workspace_bytes (== mmvae_<family>_module_workspace_bytes). */
+typedef struct {
+    void* ws; size_t ws_bytes;
+    const long long* step_counter;          /* device int64 keying the Philox streams, or NULL */
+    const float* image;                     /* [B][3][64][64] (CelebA) / [B][3][32][32] (COCO) fp32 */
+    const float* eps;                       /* [B][D] or NULL (drawn on device) */
+    const uint8_t* enc_mask1;               /* [B][1024] keep flags of the classifier's first Dropout(0.1) or NULL (drawn) */
+    const uint8_t* enc_mask2;               /* COCO only: [B][256] keep flags of its second Dropout, given or NULL together with enc_mask1 */
+    int enc_dropout;                        /* 0: no dropout */
+    float kl_lambda;
+    float lambda_x;
+    unsigned long long seed;
+    float* sums;                            /* out [16]: [0] BCE sum, [8] KL sum, the rest 0 */
+    float* recon_image;                     /* out [B][3][side][side] or NULL */
+    float* mu; float* logvar;               /* out [B][D] or NULL */
+    int defer_unpack;                       /* 1: the optimizer consumes the packed gradients itself (see the MultiMNIST step) */
+} mmvae_image_step_io;
+int mmvae_celeba_image_step(mmvae_celeba_t*, const mmvae_image_step_io*, int training, int do_backward, void* stream);
+size_t mmvae_celeba_image_step_workspace_bytes(const mmvae_celeba_t*);
+int mmvae_coco_image_step(mmvae_coco_t*, const mmvae_image_step_io*, int training, int do_backward, void* stream);
+size_t mmvae_coco_image_step_workspace_bytes(const mmvae_coco_t*);
+/* log p(x|z) of the baseline: mmvae_<family>_iw_score with the image half alone -- the eval-mode decoder body and the scoring tail
+ * kernel write loglik_x [B*K]; the second modality's decoder does not run.  Workspace: mmvae_<family>_iw_workspace_bytes. */
+int mmvae_celeba_iw_score_image(mmvae_celeba_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K,
+                                float* loglik_x, void* stream);
+int mmvae_coco_iw_score_image(mmvae_coco_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K,
+                              float* loglik_x, void* stream);
+/* The one-expert latent block of that step, alone (D <= 128).  scratch: mmvae_latent1_scratch_floats(B, D) floats, 8-byte aligned, contents
+ * undefined on entry and exit.  Every sum is folded in a fixed order without float atomics: equal inputs give equal bits.
+ * fwd: enc_out [B][2D] -> mu, logvar [B][D] = its two halves bit for bit; z [B][D] = mu + eps * exp(logvar / 2) (training, the
+ *   expression of mmvae_reparam_fwd) or mu; z_bf16 [B][ldz] = bf16(z), column D = 1.0 (the folded bias of upsample.0), the other pad
+ *   columns 0; kl_sum[0] += -0.5 * sum(1 + logvar - mu^2 - exp(logvar)).
+ * bwd: d_enc_out_bf16 [B][ld] = bf16 of (dz + kl_coef * mu | dz * eps * exp(logvar / 2) / 2 - kl_coef * (1 - exp(logvar)) / 2), pad
+ *   columns [2D, ld) 0 (dz NULL: 0; training 0: no eps term); d_bias [2D] += column sums of the fp32 values (or NULL);
+ *   loss_slots / loss_out (both or neither): loss_out[16] = sum of the [32][16] slot rows. */
+size_t mmvae_latent1_scratch_floats(int B, int D);
+int mmvae_latent1_fwd(const float* enc_out, const float* eps_or_null, int B, int D, int training, float* mu, float* logvar, float* z,
+                      void* z_bf16, int ldz, float* kl_sum, float* scratch, void* stream);
+int mmvae_latent1_bwd(const float* mu, const float* logvar, const float* eps_or_null, const float* dz_or_null, int B, int D, int training,
+                      float kl_coef, void* d_enc_out_bf16, int ld, float* d_bias_or_null, const float* loss_slots_or_null,
+                      float* loss_out_or_null, float* scratch, void* stream);
+
 /* ---------------------------------------------------------------- dataset-independent ops */
 /* ProductOfExperts.forward (multimnist/model.py:355-360) over M stacked experts of n scalars each */
 int mmvae_poe_fwd(const float* mu, const float* logvar, int M, int n, float* out_mu, float* out_logvar, void* stream);

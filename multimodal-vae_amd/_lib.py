@@ -94,6 +94,22 @@ class CelebaStepIO(C.Structure):
     ]
 
 
+class ImageStepIO(C.Structure):
+    """mmvae_image_step_io"""
+    _fields_ = [
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+        ("step_counter", C.c_void_p),
+        ("image", C.c_void_p), ("eps", C.c_void_p),
+        ("enc_mask1", C.c_void_p), ("enc_mask2", C.c_void_p),
+        ("enc_dropout", C.c_int),
+        ("kl_lambda", C.c_float), ("lambda_x", C.c_float),
+        ("seed", C.c_ulonglong),
+        ("sums", C.c_void_p), ("recon_image", C.c_void_p),
+        ("mu", C.c_void_p), ("logvar", C.c_void_p),
+        ("defer_unpack", C.c_int),
+    ]
+
+
 _P, _I, _F, _LL, _SZ, _ULL, _U = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t, C.c_ulonglong, C.c_uint
 
 # name -> (restype, argtypes); restype int means "status code, raise on != 0"
@@ -238,6 +254,13 @@ SIGNATURES["mmvae_coco_iw_workspace_bytes"] = (_SZ, [_P])
 SIGNATURES["mmvae_coco_iw_score"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES["mmvae_coco_iw_tail"] = (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES["mmvae_coco_iw_text_sse"] = (_I, [_P, _P, _I, _I, _I, _P, _P])
+for _f in ("celeba", "coco"):
+    SIGNATURES["mmvae_%s_image_step" % _f] = (_I, [_P, C.POINTER(ImageStepIO), _I, _I, _P])
+    SIGNATURES["mmvae_%s_image_step_workspace_bytes" % _f] = (_SZ, [_P])
+    SIGNATURES["mmvae_%s_iw_score_image" % _f] = (_I, [_P, _P, _SZ, _P, _P, _I, _I, _P, _P])
+SIGNATURES["mmvae_latent1_scratch_floats"] = (_SZ, [_I, _I])
+SIGNATURES["mmvae_latent1_fwd"] = (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P])
+SIGNATURES["mmvae_latent1_bwd"] = (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P])
 SIGNATURES["mmvae_nn_words_workspace_bytes"] = (_LL, [_I, _LL])
 SIGNATURES["mmvae_nn_words_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)])
 SIGNATURES["mmvae_nn_words_norms"] = (_I, [_P, _LL, _I, _P, _P])

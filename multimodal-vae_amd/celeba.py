@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
-from .core import CelebaState, FusedCelebaStep, StepOutputs
+from .core import CelebaState, FusedCelebaStep, FusedImageStep, StepOutputs
 from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
                          _seed_from_torch, _stream, swish)
 
@@ -326,3 +326,72 @@ class FusedTrainer:
 
     def evaluate(self, image, attrs, **kw) -> StepOutputs:
         return self.engine.forward_backward(image, attrs, training=False, backward=False, **kw)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the uni-modal image baseline (celeba/model.py:60-88, celeba/train_imageonly.py)
+# ----------------------------------------------------------------------------------------------------------------
+class ImageVAE(nn.Module):
+    """celeba/model.py:60-88: ``ImageEncoder`` + ``reparametrize`` + ``ImageDecoder`` under the reference's ``encoder.`` /
+    ``decoder.`` keys, with NO product of experts.  The two children live on the MultimodalVAE's plan (``encoder.features.0.weight``
+    is its ``image_encoder.features.0.weight``); the attribute half of the flat buffers keeps its initial value and never shows
+    in ``state_dict()``.  ``ImageVAETrainer`` is the train() closure of celeba/train_imageonly.py:105-117 as one enqueue."""
+
+    def __init__(self, n_latents=20):
+        super().__init__()
+        self.encoder = ImageEncoder(n_latents)
+        self.decoder = ImageDecoder(n_latents)
+        self.n_latents = n_latents
+        self._core = _Core(self, "image_", n_latents, CelebaState)
+        for m in (self.encoder, self.decoder):
+            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+
+    def encode(self, x, mask: Optional[torch.Tensor] = None):
+        return self.encoder(x, mask)
+
+    def weight_init(self, mean, std):
+        self.encoder.weight_init(mean=mean, std=std)
+        self.decoder.weight_init(mean=mean, std=std)
+
+    reparametrize = MultimodalVAE.reparametrize
+
+    def decode(self, z):
+        return self.decoder(z)
+
+    def forward(self, x, eps: Optional[torch.Tensor] = None, enc_mask: Optional[torch.Tensor] = None):
+        mu, logvar = self.encode(x, enc_mask)
+        z = self.reparametrize(mu, logvar, eps)
+        return self.decode(z), mu, logvar
+
+
+def imageonly_loss_function(recon_x, x, mu, logvar, kl_lambda=1e-3):
+    """celeba/train_imageonly.py:42-52"""
+    return loss_function(mu, logvar, recon_x=recon_x, x=x, kl_lambda=kl_lambda)
+
+
+def load_checkpoint_imageonly(file_path, use_cuda=False):
+    """celeba/train_imageonly.py:29-39: rebuilds an ImageVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    vae = ImageVAE(n_latents=checkpoint['n_latents'])
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
+
+
+class ImageVAETrainer:
+    """``ImageVAETrainer(vae, batch_size, lr)(image)`` == zero_grad + forward + loss + backward + Adam step
+    (celeba/train_imageonly.py:108-117) on ``vae``'s own parameters: one pass over B rows (core.FusedImageStep)."""
+
+    def __init__(self, vae: ImageVAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1e-3, seed: int = 1234):
+        dev = next(vae.parameters()).device
+        self.vae = vae
+        st = vae._core.sync(dev)
+        self.engine = FusedImageStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed)
+
+    def __call__(self, image, **kw) -> StepOutputs:
+        self.engine.enc_dropout = self.vae.encoder.classifier[2].p > 0
+        return self.engine(image, **kw)
+
+    def evaluate(self, image, **kw) -> StepOutputs:
+        return self.engine.forward_backward(image, training=False, backward=False, **kw)

@@ -31,7 +31,7 @@ import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
 from ._ops import geometry
-from .core import CocoState, FusedCocoStep, StepOutputs
+from .core import CocoState, FusedCocoStep, FusedImageStep, StepOutputs
 from .mmd import compute_kernel, compute_mmd, mmd_terms  # noqa: F401  (coco/model.py:385-402)
 from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
                          _gscale, _seed_from_torch, _stream, swish)
@@ -568,3 +568,67 @@ class FusedTrainer:
 
     def evaluate(self, image, text, **kw) -> StepOutputs:
         return self.engine.forward_backward(image, text, training=False, backward=False, **kw)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the uni-modal image baseline (coco/model.py:93-117, coco/train_imageonly.py)
+# ----------------------------------------------------------------------------------------------------------------
+IMAGE_VAE_STEPS = 1       # caption length of the plan an ImageVAE lives on: no caption ever runs, so its buffers are the smallest
+
+
+class ImageVAE(nn.Module):
+    """coco/model.py:93-117: ``ImageEncoder`` + ``reparametrize`` + ``ImageDecoder`` under the reference's ``encoder.`` / ``decoder.``
+    keys, with NO product of experts.  Unlike ``InfoVAE`` (two stand-alone cores, autograd between them) the two children share ONE
+    core on the MultimodalVAE's plan (``encoder.features.0.weight`` is its ``image_encoder.features.0.weight``), which is what
+    ``ImageVAETrainer`` steps in one enqueue; the caption half of the flat buffers keeps its initial value and never shows in
+    ``state_dict()``."""
+
+    def __init__(self, n_latents=20):
+        super().__init__()
+        self.encoder = ImageEncoder(n_latents, steps=IMAGE_VAE_STEPS)
+        self.decoder = ImageDecoder(n_latents, steps=IMAGE_VAE_STEPS)
+        self.n_latents = n_latents
+        self._core = _Core(self, "image_", n_latents, lambda n, d: CocoState(n, d, IMAGE_VAE_STEPS))
+        for m in (self.encoder, self.decoder):
+            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+
+    def encode(self, x, masks=None):
+        return self.encoder(x, masks)
+
+    reparametrize = MultimodalVAE.reparametrize
+
+    def decode(self, z):
+        return self.decoder(z)
+
+    def forward(self, x, eps=None, enc_masks=None):
+        mu, logvar = self.encode(x, enc_masks)
+        z = self.reparametrize(mu, logvar, eps)
+        return self.decode(z), mu, logvar
+
+
+def load_checkpoint_imageonly(file_path, use_cuda=False):
+    """coco/train_imageonly.py:28-40: rebuilds an ImageVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    vae = ImageVAE(n_latents=checkpoint['n_latents'])
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
+
+
+class ImageVAETrainer:
+    """``ImageVAETrainer(vae, batch_size, lr)(image)`` == zero_grad + forward + loss + backward + Adam step
+    (coco/train_imageonly.py:105-116, lr default 1e-4, kl_lambda 5e-4) on ``vae``'s own parameters: one pass over B rows."""
+
+    def __init__(self, vae: ImageVAE, batch_size: int, lr: float = 1e-4, kl_lambda: float = 5e-4, seed: int = 1234):
+        dev = next(vae.parameters()).device
+        self.vae = vae
+        st = vae._core.sync(dev)
+        self.engine = FusedImageStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed)
+
+    def __call__(self, image, **kw) -> StepOutputs:
+        self.engine.enc_dropout = self.vae.encoder.classifier[2].p > 0
+        return self.engine(image, **kw)
+
+    def evaluate(self, image, **kw) -> StepOutputs:
+        return self.engine.forward_backward(image, training=False, backward=False, **kw)

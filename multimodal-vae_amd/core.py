@@ -225,7 +225,7 @@ class _FusedStepBase:
             call("mmvae_set_stream_policy", 1)
         dev = state.device
         self.h = state.plan(batch)
-        self.ws = torch.empty(state.workspace_bytes(batch), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(self._workspace_bytes(state, batch), dtype=torch.uint8, device=dev)
         self.exp_avg = torch.zeros_like(state.params)
         self.exp_avg_sq = torch.zeros_like(state.params)
         self.adam_state = torch.zeros(2, dtype=torch.int64, device=dev)      # {step, ticket}
@@ -235,6 +235,9 @@ class _FusedStepBase:
 
     def _outputs(self) -> StepOutputs:
         raise NotImplementedError
+
+    def _workspace_bytes(self, state: PlanState, batch: int) -> int:
+        return state.workspace_bytes(batch)
 
     def _pass_config(self, io, passes, la, lb, name_a, name_b):
         """Fills the lambda arrays and pass_skip flags of a step-io struct; returns (passes, lambda_a, lambda_b)."""
@@ -641,3 +644,81 @@ class FusedCocoStep(_FusedStepBase):
         call("mmvae_coco_step", self.h, C.byref(io), int(training), int(backward), _stream())
         self.state.pack_pending = False
         return self._outputs()
+
+
+class FusedImageStep(_FusedStepBase):
+    """The step of celeba/train_imageonly.py:95-113 and coco/train_imageonly.py on the family's plan: zero_grad -> ONE pass over B rows
+    (image encoder, reparametrize, image decoder; no product of experts) -> BCE + kl_lambda * KL -> backward -> Adam.  ``state`` is
+    a ``CelebaState`` or a ``CocoState``; the second modality's parameters keep their values and get a gradient of exactly 0.
+    ``StepOutputs`` slot 0 carries the pass."""
+
+    SIDE = {"celeba": 64, "coco": 32}
+    IMAGE_PREFIXES = ("image_encoder.", "image_decoder.")
+
+    def __init__(self, state: PlanState, batch: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 kl_lambda: float = 1e-3, lambda_x: float = 1.0, seed: int = 1234):
+        if state.API not in self.SIDE:
+            raise MMVAEError("FusedImageStep: no image-only step for the '%s' family (CelebA and COCO have one)" % state.API)
+        super().__init__(state, batch, lr, betas, eps, seed)
+        self.kl_lambda, self.lambda_x = kl_lambda, lambda_x
+        self.enc_dropout = True
+        self.side = self.SIDE[state.API]
+        # the image half is one run at the head of the flat buffers in both families: the optimizer visits nothing else
+        n_img = 0
+        for name, shape, off in state.table:
+            if name.startswith(self.IMAGE_PREFIXES):
+                n = 1
+                for d in shape:
+                    n *= int(d)
+                assert off == n_img, "the image parameters are expected to be contiguous at the head of the table"
+                n_img = off + n
+        self.n_image_params = n_img
+        self._ranges = (C.c_longlong * 2)(0, n_img) if n_img % 4 == 0 and 0 < n_img < state.nparams else None
+
+    def _workspace_bytes(self, state: PlanState, batch: int) -> int:
+        return state._c("image_step_workspace_bytes", state.plan(batch))
+
+    def _outputs(self) -> StepOutputs:
+        return StepOutputs(self.sums, self.B * 3 * self.side * self.side, 1.0, self.kl_lambda / self.B, (self.lambda_x, 0.0, 0.0),
+                           (0.0, 0.0, 0.0), (True, False, False))
+
+    def forward_backward(self, image, training=True, backward=True, eps=None, enc_mask1=None, enc_mask2=None, recon_image=None,
+                         mu=None, logvar=None, _defer_unpack=False) -> StepOutputs:
+        assert image.is_contiguous() and image.dtype == torch.float32
+        assert image.shape == (self.B, 3, self.side, self.side)
+        io = _lib.ImageStepIO()
+        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
+        io.step_counter = self.adam_state.data_ptr()
+        io.image = image.data_ptr()
+        for k, t in (("eps", eps), ("enc_mask1", enc_mask1), ("enc_mask2", enc_mask2), ("recon_image", recon_image),
+                     ("mu", mu), ("logvar", logvar)):
+            setattr(io, k, None if t is None else t.data_ptr())
+        io.enc_dropout = int(self.enc_dropout)
+        io.kl_lambda, io.lambda_x = self.kl_lambda, self.lambda_x
+        io.seed = self.seed
+        io.sums = self.sums.data_ptr()
+        io.defer_unpack = int(bool(_defer_unpack))
+        self.state._c("image_step", self.h, C.byref(io), int(training), int(backward), _stream())
+        return self._outputs()
+
+    def __call__(self, image, **kw) -> StepOutputs:
+        """backward + optimizer.step() in one pass over the image parameters: the packed-gradient Adam (see _call_packed)."""
+        st = self.state
+        if self.separate_unpack:
+            out = self.forward_backward(image, True, True, **kw)
+            self.optimizer_step()
+            return out
+        out = self.forward_backward(image, True, True, _defer_unpack=True, **kw)
+        if self._ranges is not None:
+            call("mmvae_adam_step_packed_ranges", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
+                 self._ranges, 1, 1, ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0,
+                 ptr(st.grad_map()), ptr(st.gpk), ptr(st.gpk_vec), _stream())
+        else:
+            call("mmvae_adam_step_packed", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
+                 ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk),
+                 ptr(st.gpk_vec), _stream())
+        self._after_update()
+        return out
+
+    def capture(self, image: torch.Tensor) -> None:
+        raise MMVAEError("FusedImageStep: HIP-graph capture is not offered for the image-only step")

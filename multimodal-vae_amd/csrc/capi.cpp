@@ -250,6 +250,16 @@ int mmvae_celeba_bench_layer(mmvae_celeba_t* p, void* ws, size_t wsb, const char
     return guarded([&] { return celeba_bench_layer(p, ws, wsb, layer, iters, S(stream)); });
 }
 long long mmvae_celeba_debug_offset(mmvae_celeba_t* p, const char* name) { return celeba_debug_offset(p, name); }
+int mmvae_celeba_image_step(mmvae_celeba_t* p, const mmvae_image_step_io* io, int training, int do_backward, void* stream) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_celeba_image_step: null argument");
+        return celeba_image_step(p, *io, training, do_backward, S(stream));
+    });
+}
+size_t mmvae_celeba_image_step_workspace_bytes(const mmvae_celeba_t* p) { return p ? celeba_image_step_workspace_bytes(p) : 0; }
+int mmvae_celeba_iw_score_image(mmvae_celeba_t* p, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, void* st) {
+    return guarded([&] { return celeba_iw_score_image(p, ws, wsb, z, image, B, K, loglik_x, S(st)); });
+}
 int mmvae_celeba_image_encoder_fwd(mmvae_celeba_t* p, void* ws, size_t wsb, const float* image, const uint8_t* mask, int training, float* out, void* st) {
     return guarded([&] { return celeba_image_encoder_fwd(p, ws, wsb, image, mask, training, out, S(st)); });
 }
@@ -308,6 +318,16 @@ int mmvae_coco_step(mmvae_coco_t* p, const mmvae_coco_step_io* io, int training,
         return coco_step(p, *io, training, do_backward, S(stream));
     });
 }
+int mmvae_coco_image_step(mmvae_coco_t* p, const mmvae_image_step_io* io, int training, int do_backward, void* stream) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_coco_image_step: null argument");
+        return coco_image_step(p, *io, training, do_backward, S(stream));
+    });
+}
+size_t mmvae_coco_image_step_workspace_bytes(const mmvae_coco_t* p) { return p ? coco_image_step_workspace_bytes(p) : 0; }
+int mmvae_coco_iw_score_image(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, void* st) {
+    return guarded([&] { return coco_iw_score_image(p, ws, wsb, z, image, B, K, loglik_x, S(st)); });
+}
 int mmvae_coco_image_encoder_fwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2, int training, float* out, void* st) {
     return guarded([&] { return coco_image_encoder_fwd(p, ws, wsb, image, m1, m2, training, out, S(st)); });
 }
@@ -364,6 +384,26 @@ int mmvae_poe_bwd(const float* mu, const float* lv, int M, int n, const float* g
 int mmvae_reparam_fwd(const float* mu, const float* lv, const float* eps, int n, float* z, void* s) { return launch_reparam_fwd(mu, lv, eps, n, z, S(s)); }
 int mmvae_reparam_bwd(const float* lv, const float* eps, const float* dz, int n, float* dmu, float* dlv, void* s) {
     return launch_reparam_bwd(lv, eps, dz, n, dmu, dlv, S(s));
+}
+size_t mmvae_latent1_scratch_floats(int B, int D) { return B >= 1 && D >= 1 ? launch_latent1_scratch_floats(B, D) : 0; }
+int mmvae_latent1_fwd(const float* enc_out, const float* eps, int B, int D, int training, float* mu, float* logvar, float* z, void* z_bf16,
+                      int ldz, float* kl_sum, float* scratch, void* st) {
+    return guarded([&] {
+        Latent1Args a{};
+        a.B = B; a.D = D; a.enc_out = enc_out; a.eps = eps; a.mu = mu; a.logvar = logvar; a.z_f32 = z; a.z_bf = (bf16*)z_bf16; a.ldz = ldz;
+        a.kl_sum = kl_sum; a.training = training; a.scratch = scratch;
+        return launch_latent1_fwd(a, S(st));
+    });
+}
+int mmvae_latent1_bwd(const float* mu, const float* logvar, const float* eps, const float* dz, int B, int D, int training, float kl_coef,
+                      void* d_enc_out_bf16, int ld, float* d_bias, const float* loss_slots, float* loss_out, float* scratch, void* st) {
+    return guarded([&] {
+        Latent1BwdArgs a{};
+        a.f.B = B; a.f.D = D; a.f.mu = const_cast<float*>(mu); a.f.logvar = const_cast<float*>(logvar); a.f.eps = eps; a.f.training = training;
+        a.f.scratch = scratch;
+        a.dz = dz; a.kl_coef = kl_coef; a.d_enc_out = (bf16*)d_enc_out_bf16; a.ld = ld; a.d_bias = d_bias; a.loss_slots = loss_slots; a.loss_out = loss_out;
+        return launch_latent1_bwd(a, S(st));
+    });
 }
 int mmvae_kl_fwd(const float* mu, const float* lv, int n, float* out, void* s) { return launch_kl_fwd(mu, lv, n, out, S(s)); }
 int mmvae_kl_bwd(const float* mu, const float* lv, int n, float coef, const float* gs, float* dmu, float* dlv, void* s) { return launch_kl_bwd(mu, lv, n, coef, gs, dmu, dlv, S(s)); }

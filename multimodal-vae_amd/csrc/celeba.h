@@ -11,6 +11,10 @@ CelebaPlan* celeba_create(int D, int B);
 void celeba_destroy(CelebaPlan*);
 PlanBase* celeba_base(CelebaPlan*);
 int celeba_step(CelebaPlan*, const mmvae_celeba_step_io&, int training, int do_backward, hipStream_t);
+// image-only VAE (celeba/model.py:60-88): one pass over B rows in the one-pass carve (img_tower.h tower_image_step), and log p(x|z) alone
+int celeba_image_step(CelebaPlan*, const mmvae_image_step_io&, int training, int do_backward, hipStream_t);
+size_t celeba_image_step_workspace_bytes(const CelebaPlan*);
+int celeba_iw_score_image(CelebaPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t);
 // granular module entry points (drop-in nn.Module forwards); B rows, every call brings its workspace
 int celeba_image_encoder_fwd(CelebaPlan*, void* ws, size_t wsb, const float* image, const uint8_t* mask, int training, float* out, hipStream_t);
 int celeba_image_encoder_bwd(CelebaPlan*, void* ws, size_t wsb, const float* d_out, const uint8_t* mask, hipStream_t);

@@ -379,6 +379,44 @@ static int celeba_step_body(CelebaPlan* Pp, const mmvae_celeba_step_io& io, int 
     return io.defer_unpack ? MMVAE_OK : plan_unpack(P, s, true);
 }
 
+// ---------------------------------------------------------------- image-only VAE (celeba/model.py:60-88, celeba/train_imageonly.py)
+// One pass on B rows in the one-pass carve (img_tower.h tower_image_step); the attribute half of the plan is not touched: its
+// gradients stay at the zero the step's prologue wrote.
+namespace {
+struct CelebaImageTail {
+    int mask_width[2] = {HID, 0};
+    uint8_t* m2(CelebaPlan&) const { return nullptr; }
+    long long last_bias(const CelebaPlan& P) const { return P.fc2.b_off; }
+    int enc_fwd(CelebaPlan& P, const float* image, const uint8_t* m1, const uint8_t*, int drop, int training, float* out, hipStream_t s) const {
+        return ::enc_fwd(P, image, 1, m1, drop, training, 1, out, s);
+    }
+    int enc_bwd(CelebaPlan& P, const bf16* d_out, const uint8_t* m1, const uint8_t*, int drop, hipStream_t s) const {
+        return ::enc_bwd(P, d_out, 1, m1, drop, s);
+    }
+};
+int celeba_image_step_body(CelebaPlan* P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
+    MMVAE_REQUIRE(io.enc_mask2 == nullptr, "mmvae_celeba_image_step: the CelebA classifier has one Dropout (enc_mask2 must be NULL)");
+    MMVAE_TRY(use_ws(P, io.ws, io.ws_bytes));
+    return tower_image_step(*P, io, training, do_backward, s, CelebaImageTail{});
+}
+}  // namespace
+size_t celeba_image_step_workspace_bytes(const CelebaPlan* P) { return P->ws_bytes_module; }
+int celeba_image_step(CelebaPlan* P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
+    return plan_step(P, io, training, do_backward, s, celeba_image_step_body);
+}
+// log p(x | z) of the particle rows alone: celeba_iw_score without the attribute scorer
+int celeba_iw_score_image(CelebaPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t s) {
+    MMVAE_REQUIRE(P && z && image && loglik_x, "mmvae_celeba_iw_score_image: null argument");
+    MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B,
+                  "mmvae_celeba_iw_score_image: %d examples x %d particles exceed the plan's %d rows", B, K, P->B);
+    MMVAE_TRY(use_ws(P, ws, wsb));
+    const int rows = B * K;
+    MMVAE_TRY(launch_fill_zero(P->w.zero_begin, P->w.zero_bytes, s));
+    MMVAE_TRY(tower_iw_particles(*P, z, rows, s));
+    MMVAE_TRY(dec_fwd(*P, 1, 0, nullptr, s));
+    return launch_celeba_iw_tail(tower_iw_tail_args(*P, image, rows, K, loglik_x), s);
+}
+
 // ---------------------------------------------------------------- granular module entry points (drop-in modules)
 int celeba_image_encoder_fwd(CelebaPlan* P, void* ws, size_t wsb, const float* image, const uint8_t* mask, int training, float* out, hipStream_t s) {
     MMVAE_TRY(use_ws(P, ws, wsb));

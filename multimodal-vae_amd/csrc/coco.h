@@ -12,6 +12,10 @@ void coco_destroy(CocoPlan*);
 PlanBase* coco_base(CocoPlan*);
 int coco_steps(const CocoPlan*);
 int coco_step(CocoPlan*, const mmvae_coco_step_io&, int training, int do_backward, hipStream_t);
+// image-only VAE (coco/model.py:93-117): one pass over B rows in the one-pass carve (img_tower.h tower_image_step), and log p(x|z) alone
+int coco_image_step(CocoPlan*, const mmvae_image_step_io&, int training, int do_backward, hipStream_t);
+size_t coco_image_step_workspace_bytes(const CocoPlan*);
+int coco_iw_score_image(CocoPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t);
 // granular module entry points (drop-in nn.Module forwards); B rows, every call brings its workspace
 int coco_image_encoder_fwd(CocoPlan*, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2, int training, float* out, hipStream_t);
 int coco_image_encoder_bwd(CocoPlan*, void* ws, size_t wsb, const float* d_out, const uint8_t* m1, const uint8_t* m2, hipStream_t);

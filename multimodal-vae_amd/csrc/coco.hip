@@ -360,6 +360,44 @@ static int coco_step_body(CocoPlan* Pp, const mmvae_coco_step_io& io, int traini
     return mmvae_check_launch("sum_slots");
 }
 
+// ---------------------------------------------------------------- image-only VAE (coco/model.py:93-117, coco/train_imageonly.py)
+// One pass on B rows in the one-pass carve (img_tower.h tower_image_step); the caption half of the plan is not touched: no GRU
+// step runs, its gradients stay at the zero the step's prologue wrote.
+namespace {
+struct CocoImageTail {
+    int mask_width[2] = {HID1, HID2};
+    uint8_t* m2(CocoPlan& P) const { return P.w.m2; }
+    long long last_bias(const CocoPlan& P) const { return P.fc3.b_off; }
+    int enc_fwd(CocoPlan& P, const float* image, const uint8_t* m1, const uint8_t* m2, int drop, int training, float* out, hipStream_t s) const {
+        return ::enc_fwd(P, image, 1, m1, m2, drop, training, 1, out, s);
+    }
+    int enc_bwd(CocoPlan& P, const bf16* d_out, const uint8_t* m1, const uint8_t* m2, int drop, hipStream_t s) const {
+        return ::enc_bwd(P, d_out, 1, m1, m2, drop, s);
+    }
+};
+int coco_image_step_body(CocoPlan* P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
+    MMVAE_REQUIRE((io.enc_mask1 == nullptr) == (io.enc_mask2 == nullptr), "mmvae_coco_image_step: enc_mask1 / enc_mask2 go together");
+    MMVAE_TRY(use_ws(P, io.ws, io.ws_bytes));
+    return tower_image_step(*P, io, training, do_backward, s, CocoImageTail{});
+}
+}  // namespace
+size_t coco_image_step_workspace_bytes(const CocoPlan* P) { return P->ws_bytes_module; }
+int coco_image_step(CocoPlan* P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
+    return plan_step(P, io, training, do_backward, s, coco_image_step_body);
+}
+// log p(x | z) of the particle rows alone: coco_iw_score without the caption decoder (the same, smaller, carve)
+int coco_iw_score_image(CocoPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t s) {
+    MMVAE_REQUIRE(P && z && image && loglik_x, "mmvae_coco_iw_score_image: null argument");
+    MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B,
+                  "mmvae_coco_iw_score_image: %d examples x %d particles exceed the plan's %d rows", B, K, P->B);
+    MMVAE_TRY(use_ws_iw(P, ws, wsb));
+    const int rows = B * K;
+    MMVAE_TRY(zero_ws(*P, s));
+    MMVAE_TRY(tower_iw_particles(*P, z, rows, s));
+    MMVAE_TRY(dec_fwd(*P, 1, 0, nullptr, s));
+    return launch_coco_iw_tail(tower_iw_tail_args(*P, image, rows, K, loglik_x), s);
+}
+
 // ---------------------------------------------------------------- granular module entry points (drop-in modules)
 int coco_image_encoder_fwd(CocoPlan* P, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2, int training,
                            float* out, hipStream_t s) {

@@ -136,6 +136,38 @@ struct Latent3BwdArgs {
 };
 int launch_latent3_bwd(const Latent3BwdArgs& a, hipStream_t s);
 
+// ---- one-expert latent block of the image-only VAE step (celeba/train_imageonly.py:101-113) ----
+// The counterpart of latent3 for a model WITHOUT a product of experts: mu / logvar are the two halves of the encoder output,
+// bit for bit (no 1e-8, no exp / log round trip).  Every sum is taken in a fixed order by a fixed thread (block partials, held as doubles, in
+// `scratch`, folded by a one-block finish launch): no float atomics, equal inputs give equal bits.
+constexpr int LATENT1_KL_PARTS = 64;     // KL partials of the forward: the element range is cut into this many fixed pieces
+constexpr int LATENT1_BWD_ROWS = 16;     // sample rows per workgroup of the backward (column-sum partials: one row per workgroup)
+struct Latent1Args {
+    int B, D;
+    const float* enc_out;    // [B][2D] (mu | logvar)
+    const float* eps;        // [B][D], read when training
+    float* mu; float* logvar;   // [B][D]
+    float* z_f32;            // [B][D]
+    bf16* z_bf;              // [B][ldz]: column D = 1.0 (multiplies the folded bias of upsample.0), the other pads zero
+    int ldz;
+    float* kl_sum;           // [1] +=
+    int training;            // 0: z = mu
+    float* scratch;          // launch_latent1_scratch_floats(B, D) floats, 8-byte aligned, contents undefined on entry and on exit
+};
+size_t launch_latent1_scratch_floats(int B, int D);      // what either direction needs at most
+int launch_latent1_fwd(const Latent1Args& a, hipStream_t s);
+struct Latent1BwdArgs {
+    Latent1Args f;           // B, D, mu, logvar, eps, training, scratch
+    const float* dz;         // [B][D] or null (no reconstruction term)
+    float kl_coef;           // kl_lambda / B
+    bf16* d_enc_out;         // [B][ld], pad columns [2D, ld) zeroed
+    int ld;                  // >= 2D
+    float* d_bias;           // [2D] += column sums of the fp32 gradient (the bias of the classifier's last Linear), or null
+    const float* loss_slots; // optional, as Latent3BwdArgs: [MMVAE_LOSS_SLOTS][16] summed into loss_out[16]
+    float* loss_out;
+};
+int launch_latent1_bwd(const Latent1BwdArgs& a, hipStream_t s);
+
 // bit pattern of the "void step" mark in element 0 of a flat gradient (plan_base.h sum_slots_kernel): a quiet NaN with a payload no
 // arithmetic produces on its own
 #define MMVAE_VOID_MARK 0x7fc0deadu

@@ -657,6 +657,102 @@ __global__ __launch_bounds__(TPB) void latent3_bwd_kernel(const Latent3BwdArgs a
     }
 }
 
+// ------------------------------------------------------------------ one-expert latent block (image-only VAE)
+// Workgroup p of LATENT1_KL_PARTS owns the elements [p*chunk, (p+1)*chunk) of [B][D], chunk = ceil(B*D / parts): the cut depends on
+// the shape only, each thread folds its elements in ascending order, the wave and the workgroup fold theirs in a fixed tree, and
+// the partial goes to scratch[p] with a plain store.  The terms are kl_fwd_kernel's fp32 expression; they are ADDED in double (the
+// partials are doubles), so the sum carries one fp32 rounding, at the very end.  The pad columns of z_bf are a second grid-stride loop.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ __launch_bounds__(TPB) void latent1_fwd_kernel(const Latent1Args a) {
+    const int n = a.B * a.D, D2 = 2 * a.D;
+    const int chunk = (n + LATENT1_KL_PARTS - 1) / LATENT1_KL_PARTS;
+    const int e0 = blockIdx.x * chunk, e1 = min(n, e0 + chunk);
+    double kl = 0.0;
+    for (int e = e0 + (int)threadIdx.x; e < e1; e += TPB) {
+        const int b = e / a.D, d = e - b * a.D;
+        const float mu = a.enc_out[(size_t)b * D2 + d], lv = a.enc_out[(size_t)b * D2 + a.D + d];
+        a.mu[e] = mu; a.logvar[e] = lv;
+        const float z = a.training ? a.eps[e] * expf(0.5f * lv) + mu : mu;
+        a.z_f32[e] = z;
+        a.z_bf[(size_t)b * a.ldz + d] = (bf16)z;
+        kl += (double)(-0.5f * (1.0f + lv - mu * mu - expf(lv)));
+    }
+    const int pads = a.ldz - a.D;
+    for (int i = blockIdx.x * TPB + threadIdx.x; i < a.B * pads; i += gridDim.x * TPB) {
+        const int b = i / pads, c = i - b * pads;
+        a.z_bf[(size_t)b * a.ldz + a.D + c] = (bf16)(c == 0 ? 1.f : 0.f);
+    }
+    __shared__ double part[TPB / 64];
+    kl = wave_sum_f64(kl);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = kl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < TPB / 64; ++w) s += part[w];
+        reinterpret_cast<double*>(a.scratch)[blockIdx.x] = s;
+    }
+}
+__global__ void latent1_fwd_finish_kernel(const double* parts, float* kl_sum) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int p = 0; p < LATENT1_KL_PARTS; ++p) s += parts[p];
+    *kl_sum += (float)s;
+}
+// Thread (tx, ty) of a 64 x 4 block: latent column d = 64*blockIdx.x + tx, rows b = LATENT1_BWD_ROWS*blockIdx.y + ty + 4*i.
+// The column sums of the workgroup's rows go to scratch[blockIdx.y][2D]; latent1_bwd_finish_kernel folds the rows in order.
+// A few thousand elements on the main chain: the two gradients are evaluated and summed in double, so that an element of
+// d_enc_out is the bf16 rounding of the exact value and a bias sum carries one fp32 rounding.
+__global__ __launch_bounds__(TPB) void latent1_bwd_kernel(const Latent1BwdArgs a) {
+    const Latent1Args& f = a.f;
+    const int D2 = 2 * f.D;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int d = blockIdx.x * 64 + tx;
+    __shared__ double red[2][4][64];
+    double s_mu = 0.0, s_lv = 0.0;
+    const int b_end = min(f.B, (int)(blockIdx.y + 1) * LATENT1_BWD_ROWS);
+    for (int b = blockIdx.y * LATENT1_BWD_ROWS + ty; b < b_end; b += 4) {
+        if (d < f.D) {
+            const int e = b * f.D + d;
+            const double dz = a.dz ? (double)a.dz[e] : 0.0;
+            const double mu = f.mu[e], lv = f.logvar[e], kc = a.kl_coef;
+            const double gmu = dz + kc * mu;
+            double glv = -0.5 * kc * (1.0 - exp(lv));
+            if (f.training) glv += dz * (double)f.eps[e] * 0.5 * exp(0.5 * lv);
+            a.d_enc_out[(size_t)b * a.ld + d] = (bf16)(float)gmu;
+            a.d_enc_out[(size_t)b * a.ld + f.D + d] = (bf16)(float)glv;
+            s_mu += gmu; s_lv += glv;
+        }
+        // the pad columns sit on the reduction dimension of the data-gradient GEMM: zeroed, not left to the workspace
+        if (blockIdx.x == 0)
+            for (int c = D2 + tx; c < a.ld; c += 64) a.d_enc_out[(size_t)b * a.ld + c] = (bf16)0.f;
+    }
+    if (!a.d_bias) return;
+    red[0][ty][tx] = s_mu; red[1][ty][tx] = s_lv;
+    __syncthreads();
+    if (ty == 0 && d < f.D) {
+        double* row = reinterpret_cast<double*>(f.scratch) + (size_t)blockIdx.y * D2;
+        row[d] = red[0][0][tx] + red[0][1][tx] + red[0][2][tx] + red[0][3][tx];
+        row[f.D + d] = red[1][0][tx] + red[1][1][tx] + red[1][2][tx] + red[1][3][tx];
+    }
+}
+__global__ __launch_bounds__(TPB) void latent1_bwd_finish_kernel(const double* parts, int nrows, int D2, float* d_bias, const float* loss_slots,
+                                                                 float* loss_out) {
+    const int c = threadIdx.x;
+    if (loss_slots && c < 16) {
+        float t = 0.f;
+        for (int q = 0; q < MMVAE_LOSS_SLOTS; ++q) t += loss_slots[q * 16 + c];
+        loss_out[c] = t;
+    }
+    if (!d_bias || c >= D2) return;
+    double s = 0.0;
+    for (int r = 0; r < nrows; ++r) s += parts[(size_t)r * D2 + c];
+    d_bias[c] += (float)s;
+}
+
 // ------------------------------------------------------------------ Adam (torch.optim.Adam defaults)
 __global__ __launch_bounds__(TPB) void adam_kernel(const AdamArgs a, unsigned* done) {
     const long long t = *a.step + 1;
@@ -1018,6 +1114,36 @@ int launch_latent3_bwd(const Latent3BwdArgs& a, hipStream_t s) {
     MMVAE_REQUIRE((a.loss_slots == nullptr) == (a.loss_out == nullptr), "latent3_bwd: loss_slots / loss_out go together");
     MMVAE_LAUNCH(latent3_bwd_kernel, dim3(ceil_div(a.f.D, 64), ceil_div(a.f.B, L3B_ROWS)), dim3(TPB), 0, s, a);
     return mmvae_check_launch("latent3_bwd");
+}
+size_t launch_latent1_scratch_floats(int B, int D) {
+    const size_t fwd = 2 * (size_t)LATENT1_KL_PARTS, bwd = 2 * (size_t)ceil_div(B, LATENT1_BWD_ROWS) * 2 * D;      // doubles
+    return bwd > fwd ? bwd : fwd;
+}
+static int latent1_check(const Latent1Args& a, const char* who) {
+    MMVAE_REQUIRE(a.B >= 1 && a.D >= 1 && a.D <= 128 && (long long)a.B * a.D <= 0x3FFFFFFF, "%s: B=%d D=%d out of range (D <= 128)", who, a.B, a.D);
+    MMVAE_REQUIRE(a.mu && a.logvar && a.scratch && (!a.training || a.eps), "%s: null argument", who);
+    MMVAE_REQUIRE(((uintptr_t)a.scratch & 7) == 0, "%s: scratch must be 8-byte aligned", who);
+    return MMVAE_OK;
+}
+int launch_latent1_fwd(const Latent1Args& a, hipStream_t s) {
+    MMVAE_TRY(latent1_check(a, "latent1_fwd"));
+    MMVAE_REQUIRE(a.enc_out && a.z_f32 && a.z_bf && a.kl_sum, "latent1_fwd: null argument");
+    MMVAE_REQUIRE(a.ldz >= a.D, "latent1_fwd: ldz=%d < D=%d", a.ldz, a.D);
+    hipLaunchKernelGGL(latent1_fwd_kernel, dim3(LATENT1_KL_PARTS), dim3(TPB), 0, s, a);
+    MMVAE_TRY(mmvae_check_launch("latent1_fwd"));
+    MMVAE_LAUNCH(latent1_fwd_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)a.scratch, a.kl_sum);
+    return mmvae_check_launch("latent1_fwd_finish");
+}
+int launch_latent1_bwd(const Latent1BwdArgs& a, hipStream_t s) {
+    MMVAE_TRY(latent1_check(a.f, "latent1_bwd"));
+    MMVAE_REQUIRE(a.d_enc_out && a.ld >= 2 * a.f.D, "latent1_bwd: d_enc_out missing or ld=%d < 2D", a.ld);
+    MMVAE_REQUIRE((a.loss_slots == nullptr) == (a.loss_out == nullptr), "latent1_bwd: loss_slots / loss_out go together");
+    const int nrows = ceil_div(a.f.B, LATENT1_BWD_ROWS);
+    hipLaunchKernelGGL(latent1_bwd_kernel, dim3(ceil_div(a.f.D, 64), nrows), dim3(TPB), 0, s, a);
+    MMVAE_TRY(mmvae_check_launch("latent1_bwd"));
+    if (!a.d_bias && !a.loss_slots) return MMVAE_OK;
+    MMVAE_LAUNCH(latent1_bwd_finish_kernel, dim3(1), dim3(TPB), 0, s, (const double*)a.f.scratch, nrows, 2 * a.f.D, a.d_bias, a.loss_slots, a.loss_out);
+    return mmvae_check_launch("latent1_bwd_finish");
 }
 int launch_adam(const AdamArgs& a_in, hipStream_t s) {
     AdamArgs a = a_in;

@@ -10,6 +10,7 @@
 #include "plan_base.h"
 #include "thin.h"
 #include "iw.h"
+#include "../../include/mmvae_hip.h"
 #include <map>
 #include <string>
 
@@ -447,6 +448,74 @@ inline IwTailArgs tower_iw_tail_args(TowerPlan& P, const float* image, int rows,
     t.rmean = P.buf.bn_stats + b.stat_off; t.rvar = t.rmean + b.C; t.eps = BN_EPS;
     t.act = ACT_SWISH; t.w = P.buf.params + P.convT[3].w_off; t.image = image; t.rows = rows; t.K = K; t.loglik = loglik;
     return t;
+}
+
+// ================================================================== the one-pass step of the image-only VAE
+// celeba/train_imageonly.py:95-113, coco/train_imageonly.py: zero_grad, ONE forward of B rows (encoder with one dropout variant and
+// one BatchNorm update, latent1 -- no product of experts --, decoder with one BatchNorm group, sigmoid + BCE) and its backward.  The
+// workspace is the family's one-pass carve (the module entry points' one); the launches are the ones the module entry points run
+// (the staged forms and CelebA's fused decoder tail are built for 3 groups / 2 variants and stay with the 3-pass step).  Weight
+// gradients go to the two side streams as in the 3-pass step; nothing else leaves the main stream: there is no second modality.
+// Fam (the family's classifier tail around the tower):
+//   mask_width[2]                   widths of the classifier's Dropout layers (0: the family has no second one)
+//   last_bias(P)                    offset of the bias of the classifier's last Linear in the flat buffers
+//   enc_fwd(P, image, m1, m2, drop, training, out, s) / enc_bwd(P, d_out, m1, m2, drop, s)      one variant
+template <class Plan, class Fam>
+int tower_image_step(Plan& P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s, const Fam& fam) {
+    typename Plan::W& w = P.w;
+    const TowerGeom& G = P.geo;
+    const int B = P.B, D = P.D, npix = 3 * G.img * G.img;
+    MMVAE_REQUIRE(io.image && io.sums, "image step: image/sums must be given");
+    MMVAE_REQUIRE(launch_latent1_scratch_floats(B, D) <= (size_t)B * npix, "image step: no room for the latent block's partial sums");
+    const float* eps = io.eps;
+    const uint8_t *m1 = io.enc_mask1, *m2 = io.enc_mask2;
+    StepBeginArgs sb{};
+    sb.zero_ptr[0] = w.zero_begin; sb.zero_bytes[0] = w.zero_bytes;
+    if (do_backward) {
+        sb.zero_ptr[1] = P.buf.gpk; sb.zero_bytes[1] = (size_t)P.gk.mat_elems * sizeof(float);
+        sb.zero_ptr[2] = P.buf.grads; sb.zero_bytes[2] = (size_t)(P.nparams / 4) * 16;
+    }
+    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_counter;
+    const int enc_drop = training && io.enc_dropout;
+    if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B * D; eps = w.eps; }
+    if (enc_drop && !m1) { sb.mask[0] = w.m1; sb.n_mask[0] = (long long)B * fam.mask_width[0]; m1 = w.m1; }
+    if (enc_drop && fam.mask_width[1] && !m2) { sb.mask[1] = fam.m2(P); sb.n_mask[1] = (long long)B * fam.mask_width[1]; m2 = fam.m2(P); }
+    MMVAE_TRY(launch_step_begin(sb, s));
+    if (do_backward && P.nparams % 4 != 0)
+        MMVAE_TRY(launch_fill_zero(P.buf.grads + (P.nparams / 4) * 4, (size_t)(P.nparams % 4) * sizeof(float), s));
+    MMVAE_TRY(ensure_streams(P));
+    MMVAE_TRY(fam.enc_fwd(P, io.image, m1, m2, enc_drop, training, w.encout, s));
+    Latent1Args la{};
+    la.B = B; la.D = D; la.enc_out = w.encout; la.eps = eps;
+    la.mu = io.mu ? io.mu : w.mu; la.logvar = io.logvar ? io.logvar : w.logvar;
+    la.z_f32 = w.z_f32; la.z_bf = w.z_bf; la.ldz = P.ldz; la.kl_sum = w.sums + 8; la.training = training;
+    la.scratch = w.tmp_f32;         // (the module decoder's sigmoid-backward buffer: nobody else's in this step)
+    MMVAE_TRY(launch_latent1_fwd(la, s));
+    ConvTLastFwdArgs last{};
+    last.target = io.image; last.recon = io.recon_image; last.dlogit = do_backward ? w.dlogit : nullptr; last.loss_sum = w.sums;
+    last.coef[0] = io.lambda_x / (float)(B * npix);
+    MMVAE_TRY(tower_dec_fwd(P, 1, training, true, s));
+    MMVAE_TRY(launch_convt_last_fwd(dec_last_args(P, last, 1), s));
+    if (!do_backward) {
+        hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, s, w.sums, io.sums);
+        return mmvae_check_launch("sum_slots");
+    }
+    // =============================== backward ===============================
+    P.wgrad_forked = true;
+    int rc = MMVAE_OK;
+    const bool img_term = io.lambda_x != 0.f;        // (a zero weight has exactly no gradient)
+    if (img_term) rc = tower_dec_bwd(P, w.dlogit, 1, w.dz_img, s);
+    Latent1BwdArgs lb{};
+    lb.f = la; lb.dz = img_term ? w.dz_img : nullptr; lb.kl_coef = io.kl_lambda / (float)B;
+    lb.d_enc_out = w.d_encout; lb.ld = 2 * D; lb.d_bias = P.buf.grads + fam.last_bias(P);
+    lb.loss_slots = w.sums; lb.loss_out = io.sums;      // (BCE and KL sums are final here)
+    if (rc == MMVAE_OK) rc = launch_latent1_bwd(lb, s);
+    if (rc == MMVAE_OK) rc = fam.enc_bwd(P, w.d_encout, m1, m2, enc_drop, s);
+    P.wgrad_forked = false;
+    MMVAE_TRY(rc);
+    MMVAE_TRY(join_sides(P, s, s));
+    if (io.defer_unpack) return launch_wgrad_reduce(&P.slab, s);      // the packed gradients are complete; Adam gathers them
+    return plan_unpack(P, s, true);
 }
 
 // ================================================================== test / profiling aids (<family>_bench_layer, <family>_debug_offset)

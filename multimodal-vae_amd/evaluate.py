@@ -242,9 +242,12 @@ class _Family:
     decoder's steps T and classes V (words [rows][T][V]), the shape of one image, the particle rows of one scoring call and
     the scoring workspace."""
 
-    def __init__(self, name, T, V, image_shape, rows, score, workspace_bytes, float_text=False):
+    def __init__(self, name, T, V, image_shape, rows, score, workspace_bytes, float_text=False, image_only=False):
         self.name, self.T, self.V, self.image_shape, self.rows = name, T, V, image_shape, rows
         self.score, self.workspace_bytes = score, workspace_bytes
+        # image_only: an ImageVAE baseline (celeba / coco): there is no second modality, the scoring call writes log p(x|z) alone
+        # and the y / xy columns of every result are NaN
+        self.image_only = image_only
         # float_text: the second modality is a float tensor (B, steps, 300) scored by a squared error (COCO captions), not int64
         # targets; the scoring call then also gets text / sos / sse / scale (``_coco_score``) and writes words = scale * sse
         self.float_text = float_text
@@ -270,6 +273,16 @@ def _coco_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream, tex
     from ._lib import ptr
     _iw_call("mmvae_coco_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), ptr(text), ptr(sos), nr, nk, ptr(lx), ptr(sse), stream)
     torch.mul(sse[:rows], scale, out=words[:rows])
+
+
+def _image_score(api):
+    """The scoring call of an ImageVAE: mmvae_<family>_iw_score_image (decoder body + scoring tail, no second decoder); the words
+    of its one dummy text position are 0."""
+    def score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
+        from ._lib import ptr
+        _iw_call("mmvae_%s_iw_score_image" % api, st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), stream)
+        words[:rows].zero_()
+    return score
 
 
 def coco_text_constant(steps, text_sigma):
@@ -301,13 +314,23 @@ _FAMILIES = {
     # the caption term goes through the accumulator as ONE position of ONE class: words [rows][1][1] = -SSE / (2 sigma^2), targets 0
     "coco": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_score,
                     lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), float_text=True),
+    # the uni-modal baselines: the family's image half alone, the same particle rows per call
+    "celeba_image": _Family("celeba", 1, 1, (3, 64, 64), IW_ROWS_CELEBA, _image_score("celeba"),
+                            lambda st, rows: _iw_call("mmvae_celeba_iw_workspace_bytes", st.plan(rows)), image_only=True),
+    "coco_image": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _image_score("coco"),
+                          lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), image_only=True),
 }
+IMAGE_ONLY_NAN_COLUMNS = (1, 2, 4, 5, 7)      # of mmvae_iw_finalize's (B, 8): everything that involves y
 
 
 def _family(model):
     from .celeba import MultimodalVAE as CelebaVAE
     from .coco import MultimodalVAE as CocoVAE
     from .mnist import MultimodalVAE as MnistVAE
+    from .celeba import ImageVAE as CelebaImageVAE
+    from .coco import ImageVAE as CocoImageVAE
+    if isinstance(model, (CelebaImageVAE, CocoImageVAE)):
+        return _FAMILIES["celeba_image" if isinstance(model, CelebaImageVAE) else "coco_image"]
     return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else
                      "coco" if isinstance(model, CocoVAE) else "multimnist"]
 
@@ -368,7 +391,9 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     rows_max = max(nr * nk for _, nr, _, nk in chunks)
     image = image.reshape(B, -1).contiguous().float()
     extra, sse_all, text_const = {}, None, 0.0
-    if fam.float_text:
+    if fam.image_only:
+        text = torch.zeros(B, 1, dtype=torch.int64, device=mu.device)          # no second modality: ``text`` is ignored
+    elif fam.float_text:
         steps = int(model.steps)
         text_const = coco_text_constant(steps, text_sigma)
         captions = text.contiguous().float()
@@ -418,6 +443,10 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     _iw_call("mmvae_iw_finalize", ptr(state), B, K, ptr(out), stream)
     if fam.float_text:
         _shift_text_terms(out, lw_all, text_const)
+    if fam.image_only:          # an ImageVAE defines p(x) alone
+        out[:, IMAGE_ONLY_NAN_COLUMNS] = float("nan")
+        if lw_all is not None:
+            lw_all[..., 1:3] = float("nan")
     res = {"log_p": out[:, 0:3], "ess": out[:, 3:6], "nll": out[:, 6:8]}
     if return_z:
         res["z"] = z_all
@@ -433,6 +462,10 @@ def _proposal(model, image, text, posterior):
     fam = _family(model)
     image = image.reshape(image.shape[0], *fam.image_shape)
     posterior = _posterior(posterior)
+    if fam.image_only:          # q(z|x) of the encoder itself: an ImageVAE has no experts
+        if posterior != "image":
+            raise ValueError("an ImageVAE has the image posterior alone: posterior must be \"image\" (got %r)" % (posterior,))
+        return model.encoder(image)
     if fam.name == "celeba":
         second = (lambda t: model.attrs_encoder(t.float()))        # the (B,18) attributes as float
     else:
@@ -471,13 +504,15 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
     posterior = _posterior(posterior)
     if posterior not in POSTERIORS:
         raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
+    if _family(model).image_only and posterior != "image":
+        raise ValueError("an ImageVAE has the image posterior alone: posterior must be \"image\" (got %r)" % (posterior,))
     model.eval()
     dev = next(model.parameters()).device
     logp, ess, nll, n_seen = [], [], [], 0
     for image, text in loader:
         fam = _family(model)
         image = image.to(dev).float().reshape(-1, *fam.image_shape)
-        text = text.to(dev).float() if fam.float_text else text.to(dev).long()
+        text = None if fam.image_only else text.to(dev).float() if fam.float_text else text.to(dev).long()
         mu, logvar = _proposal(model, image, text, posterior)
         r = iw_estimate(model, image, text, mu, logvar, n_particles, seed=seed, first_row=n_seen, text_sigma=text_sigma)
         logp.append(r["log_p"]); ess.append(r["ess"]); nll.append(r["nll"])
@@ -808,6 +843,13 @@ def _parser():
     pk.add_argument('--seed', type=int, default=0, help='seed of the particles (and of the synthetic examples)')
     pk.add_argument('--json', type=str, default=None, help='write the bounds to this file')
     # multimnist/sample.py's flags for a checkpoint of train_coco; the captions are decoded through a word table
+    pt = sub.add_parser("test_imageonly", help="celeba/test_imageonly.py: eval-mode loss (kl_lambda = 1) of a train_imageonly checkpoint")
+    pt.add_argument('model_path', type=str)
+    pt.add_argument('--dataset', choices=('celeba', 'coco'), default='celeba')
+    pt.add_argument('--data', type=str, default='', help='celeba: FILE.pt of make_celeba; coco: DIR with images_u8.pt')
+    pt.add_argument('--synthetic', type=int, default=0, metavar='N')
+    pt.add_argument('--batch_size', type=int, default=128, metavar='N')
+    pt.add_argument('--seed', type=int, default=0)
     pw = sub.add_parser("sample_coco", help="multimnist/sample.py for the COCO family: images + captions decoded to words")
     pw.add_argument('model_path', type=str, help='path to a checkpoint written by train_coco')
     tab = pw.add_mutually_exclusive_group(required=True)
@@ -1088,6 +1130,39 @@ def _report(vae, loader, posts, args, second, text_sigma=None):
     return table
 
 
+def is_imageonly_checkpoint(path):
+    """True for a checkpoint of ``train_imageonly`` (or the reference's train_imageonly.py): every key of its ``state_dict`` starts
+    with ``encoder.`` or ``decoder.``."""
+    keys = list(torch.load(path, map_location='cpu', weights_only=False)['state_dict'].keys())
+    return len(keys) > 0 and all(k.startswith(("encoder.", "decoder.")) for k in keys)
+
+
+@torch.no_grad()
+def test_imageonly(vae, loader, kl_lambda=1.0, verbose=True):
+    """celeba/test_imageonly.py: the mean over the batches of the eval-mode loss BCE + kl_lambda * KL / B of an ``ImageVAE``
+    (``kl_lambda`` = 1 there), on the one-pass step.  ``loader`` yields (image, anything) whole batches of one size."""
+    import importlib
+    vae.eval()
+    dev = next(vae.parameters()).device
+    mod = importlib.import_module(type(vae).__module__)
+    trainer, total, n = None, 0.0, 0
+    for image, _ in loader:
+        image = image.to(dev).float().contiguous()
+        if trainer is None or trainer.engine.B != image.shape[0]:
+            trainer = mod.ImageVAETrainer(vae, image.shape[0], kl_lambda=kl_lambda)
+        total += float(trainer.evaluate(image).losses()[0].item())
+        n += 1
+    if n == 0:
+        raise ValueError("test_imageonly: empty loader")
+    total /= n
+    if verbose:
+        print('====> Test set loss: {:.4f}'.format(total))
+    return total
+
+
+test_imageonly.__test__ = False           # not a pytest test
+
+
 def load_celeba_eval_file(path):
     """The ``--data`` file of ``loglik_celeba``: (uint8 images (N,3,64,64), attributes (N,18)) -> (uint8 images, float32
     attributes).  Attributes other than 0 / 1 are refused here, on the host: the scorer indexes (log(1 - p), log p) with them."""
@@ -1116,6 +1191,9 @@ def _loglik_celeba_main(args):
         raise SystemExit("loglik_celeba: give --data FILE.pt or --synthetic N")
     x = x.float().div_(255.0)                                     # transforms.ToTensor()
     loader = [(x[i:i + args.batch_size], a[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    if is_imageonly_checkpoint(args.model_path):                  # a checkpoint of train_imageonly: log p(x) alone
+        from .celeba import load_checkpoint_imageonly
+        return _report(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Attrs")
     vae = load_checkpoint(args.model_path, use_cuda=True)
     posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.attrs_only else ("joint",)
     return _report(vae, loader, posts, args, "Attrs")
@@ -1162,9 +1240,39 @@ def _loglik_coco_main(args):
             raise ValueError("loglik_coco: the '<s>' vector must be %d floats (got %s %s)" % (K.N_EMBEDDING, sos.dtype, tuple(sos.shape)))
     x = x.float().div_(255.0)                                     # transforms.ToTensor()
     loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    if is_imageonly_checkpoint(args.model_path):                  # a checkpoint of train_imageonly: log p(x) alone
+        return _report(K.load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Text",
+                       text_sigma=float(args.text_sigma))
     vae = K.load_checkpoint(args.model_path, use_cuda=True, sos=sos, words=words)
     posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
     return _report(vae, loader, posts, args, "Text", text_sigma=float(args.text_sigma))
+
+
+def _test_imageonly_main(args):
+    """`test_imageonly`: whole batches only (the plan takes a fixed batch size); a trailing partial batch is dropped."""
+    import os
+    from . import data as D
+    if args.dataset == "celeba":
+        from .celeba import load_checkpoint_imageonly
+        if args.synthetic > 0:
+            x, _ = D.synthetic_celeba(args.synthetic, seed=args.seed)
+        elif args.data:
+            x, _ = load_celeba_eval_file(args.data)
+        else:
+            raise SystemExit("test_imageonly: give --data or --synthetic N")
+    else:
+        from .coco import load_checkpoint_imageonly
+        from .train_coco import synthetic_coco
+        if args.synthetic > 0:
+            x, _, _ = synthetic_coco(args.synthetic, seed=args.seed)
+        elif args.data:
+            x = torch.as_tensor(torch.load(os.path.join(args.data, "images_u8.pt"), weights_only=False))
+        else:
+            raise SystemExit("test_imageonly: give --data or --synthetic N")
+    bs = min(args.batch_size, x.shape[0])
+    x = x.float().div_(255.0)
+    loader = [(x[i:i + bs], None) for i in range(0, x.shape[0] - bs + 1, bs)]
+    return test_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader)
 
 
 def _loglik_main(args):
@@ -1203,6 +1311,8 @@ def _main(argv=None):
         return _loglik_celeba_main(args)
     if args.cmd == "loglik_coco":
         return _loglik_coco_main(args)
+    if args.cmd == "test_imageonly":
+        return _test_imageonly_main(args)
     if args.cmd == "sample_coco":
         return _sample_coco_main(args)
     if args.cmd == "sample_celeba":

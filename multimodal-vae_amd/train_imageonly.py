@@ -1,0 +1,211 @@
+"""``celeba/train_imageonly.py`` / ``coco/train_imageonly.py``-compatible driver of the uni-modal image baselines.
+
+Per data set the reference script's command line, defaults, printed lines, KL schedule and checkpoint dict (``state_dict``,
+``best_loss``, ``n_latents``, ``optimizer``), with the batch loop body replaced by ONE fused enqueue (``ImageVAETrainer``: one pass
+over B rows, no product of experts) and the ``DataLoader`` by ``data.DeviceBatcher``:
+
+    celeba (celeba/train_imageonly.py:57-70,141-153): --n_latents 100 --lr 1e-3, kl_lambda 1e-3 throughout
+    coco   (coco/train_imageonly.py:45-60,141-162):   --n_latents 20 --lr 1e-4 [--anneal_kl], kl_lambda 5e-4, or with --anneal_kl
+                                                      1e-5, 1e-4, 1e-3 advancing every 5 epochs
+
+    python -m multimodal_vae_amd.train_imageonly --dataset celeba --cuda --data ./data
+    python -m multimodal_vae_amd.train_imageonly --dataset coco --cuda --epochs 2 --synthetic 4096   # no data files needed
+
+After each epoch 64 prior samples are written as ``sample_image_epochN.pt`` (the tensor, not a PNG grid: no torchvision here).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import torch
+
+from .train import AverageMeter, save_checkpoint
+
+DATASETS = {
+    #          n_latents  lr    kl_lambda  side
+    "celeba": (100, 1e-3, 1e-3, 64),
+    "coco": (20, 1e-4, 5e-4, 32),
+}
+COCO_KL_SCHEDULE = (1e-5, 1e-4, 1e-3)       # coco/train_imageonly.py:142
+
+
+def build_parser(dataset: str) -> argparse.ArgumentParser:
+    n_latents, lr, _, _ = DATASETS[dataset]
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--dataset', choices=sorted(DATASETS), default=dataset)
+    # the reference's flags, same names / defaults
+    parser.add_argument('--n_latents', type=int, default=n_latents, help='size of the latent embedding')
+    parser.add_argument('--batch_size', type=int, default=128, metavar='N', help='input batch size for training (default: 128)')
+    parser.add_argument('--epochs', type=int, default=10, metavar='N', help='number of epochs to train (default: 10)')
+    parser.add_argument('--lr', type=float, default=lr, metavar='LR', help='learning rate (default: %g)' % lr)
+    parser.add_argument('--log_interval', type=int, default=10, metavar='N', help='how many batches to wait before logging training status')
+    if dataset == "coco":
+        parser.add_argument('--anneal_kl', action='store_true', default=False, help='if True, use a fixed interval of doubling the KL term')
+    parser.add_argument('--cuda', action='store_true', default=False, help='enables CUDA training')
+    # additions, as train_celeba / train_coco
+    parser.add_argument('--data', type=str, default='./data', metavar='DIR',
+                        help='celeba: folder with celeba_{train,val}.pt (make_celeba); coco: folder with images_u8.pt (as train_coco)')
+    parser.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic samples instead of files')
+    parser.add_argument('--out', type=str, default='./trained_models/image_only', help='checkpoint folder (reference: ./trained_models/image_only)')
+    parser.add_argument('--results', type=str, default='./results/image_only', help='folder of the per-epoch sample dumps (off when empty)')
+    parser.add_argument('--seed', type=int, default=1234)
+    return parser
+
+
+def dataset_of(argv) -> str:
+    """The value of ``--dataset`` (it selects the other flags' defaults, so it is looked at first)."""
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument('--dataset', choices=sorted(DATASETS), default='celeba')
+    return pre.parse_known_args(argv)[0].dataset
+
+
+def kl_lambdas(dataset: str, epochs: int, anneal_kl: bool = False):
+    """kl_lambda of epochs 1..epochs.  celeba: loss_function's default throughout (celeba/train_imageonly.py:42,114); coco: 5e-4, or
+    with --anneal_kl the next value of 1e-5, 1e-4, 1e-3 every 5 epochs, the last one kept (coco/train_imageonly.py:141-149)."""
+    kl = DATASETS[dataset][2]
+    schedule = iter(COCO_KL_SCHEDULE)
+    out = []
+    for epoch in range(1, epochs + 1):
+        if dataset == "coco" and (epoch - 1) % 5 == 0 and anneal_kl:
+            kl = next(schedule, kl)
+        out.append(kl)
+    return out
+
+
+def image_adam_state_dict(vae, engine) -> dict:
+    """The engine's flat Adam moments of the ImageVAE's own parameters as a ``torch.optim.Adam.state_dict()``."""
+    st = engine.state
+    step = int(engine.adam_state[0].item())
+    own = {vae._core.prefix + n for n, _ in vae.named_parameters()}
+    state = {}
+    for name, shape, off in st.table:
+        if name not in own:
+            continue
+        numel = 1
+        for s in shape:
+            numel *= s
+        state[len(state)] = {'step': torch.tensor(float(step)),
+                             'exp_avg': engine.exp_avg[off:off + numel].view(shape).clone(),
+                             'exp_avg_sq': engine.exp_avg_sq[off:off + numel].view(shape).clone()}
+    group = {'lr': engine.lr, 'betas': tuple(engine.betas), 'eps': engine.eps, 'weight_decay': 0, 'amsgrad': False,
+             'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
+             'decoupled_weight_decay': False, 'params': list(range(len(state)))}
+    return {'state': state, 'param_groups': [group]}
+
+
+def checkpoint_dict(vae, engine, best_loss, n_latents) -> dict:
+    """celeba/train_imageonly.py:148-153"""
+    return {'state_dict': vae.state_dict(), 'best_loss': best_loss, 'n_latents': n_latents,
+            'optimizer': image_adam_state_dict(vae, engine)}
+
+
+def _load_images(args):
+    from . import data as D
+    if args.dataset == "celeba":
+        from .evaluate import load_celeba_eval_file
+        if args.synthetic > 0:
+            return (D.synthetic_celeba(args.synthetic, seed=args.seed)[0],
+                    D.synthetic_celeba(max(args.batch_size, args.synthetic // 6), seed=args.seed + 1)[0])
+        return (load_celeba_eval_file(os.path.join(args.data, "celeba_train.pt"))[0],
+                load_celeba_eval_file(os.path.join(args.data, "celeba_val.pt"))[0])
+    from .train_coco import synthetic_coco
+    if args.synthetic > 0:
+        return (synthetic_coco(args.synthetic, seed=args.seed)[0],
+                synthetic_coco(max(args.batch_size, args.synthetic // 6), seed=args.seed + 1)[0])
+    x = torch.as_tensor(torch.load(os.path.join(args.data, "images_u8.pt"), weights_only=False))      # as train_coco: the first tenth is the test split
+    n_test = max(args.batch_size, len(x) // 10)
+    return x[n_test:], x[:n_test]
+
+
+def main(argv=None) -> dict:
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = build_parser(dataset_of(argv)).parse_args(argv)
+    args.cuda = args.cuda and torch.cuda.is_available()
+    if not args.cuda:
+        raise SystemExit("this engine runs on a gfx950 GPU only: pass --cuda on a machine that has one (no CPU fallback)")
+    import importlib
+    from . import data as D
+    M = importlib.import_module("." + args.dataset, __package__)
+    side = DATASETS[args.dataset][3]
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    torch.manual_seed(args.seed)
+    tr_x, te_x = _load_images(args)
+    for name, x in (("training", tr_x), ("test (val)", te_x)):
+        if x.dtype != torch.uint8 or tuple(x.shape[1:]) != (3, side, side):
+            raise SystemExit("the %s images must be uint8 (N,3,%d,%d) (got %s %s)" % (name, side, side, x.dtype, tuple(x.shape)))
+        if len(x) < args.batch_size:
+            raise SystemExit("the %s split has %d images, fewer than one batch of %d (the fused plan takes whole batches)"
+                             % (name, len(x), args.batch_size))
+    none = lambda x: torch.zeros(len(x), dtype=torch.int64)          # the batcher carries a second tensor: nothing reads it
+    train_loader = D.DeviceBatcher(tr_x, none(tr_x), args.batch_size, dev, shuffle=True, seed=args.seed)
+    test_loader = D.DeviceBatcher(te_x, none(te_x), args.batch_size, dev, shuffle=True, seed=args.seed + 7)
+
+    vae = M.ImageVAE(n_latents=args.n_latents)
+    if args.dataset == "celeba":
+        vae.weight_init(mean=0.0, std=0.02)
+    vae.cuda()
+    trainer = M.ImageVAETrainer(vae, args.batch_size, lr=args.lr, kl_lambda=DATASETS[args.dataset][2], seed=args.seed)
+
+    def train(epoch, kl_lambda):
+        if args.dataset == "coco":
+            print('Using KL Lambda: {}'.format(kl_lambda))
+        vae.train()
+        trainer.engine.kl_lambda = kl_lambda
+        meter = AverageMeter()
+        n_total = len(train_loader) * args.batch_size
+        pending = []
+
+        def drain():
+            for l in torch.stack(pending).cpu().tolist():        # one read-back per log interval
+                meter.update(l, args.batch_size)
+            pending.clear()
+
+        for batch_idx, (image, _) in enumerate(train_loader):
+            pending.append(trainer(image).losses()[0].clone())   # device tensor, no sync
+            if batch_idx % args.log_interval == 0:
+                drain()
+                print('Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(
+                    epoch, batch_idx * args.batch_size, n_total, 100. * batch_idx / max(len(train_loader), 1), meter.avg))
+        if pending:
+            drain()
+        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, meter.avg))
+        return meter.avg
+
+    def test(kl_lambda):
+        vae.eval()
+        trainer.engine.kl_lambda = kl_lambda
+        acc = torch.zeros((), device=dev)
+        nb = 0
+        for image, _ in test_loader:
+            acc += trainer.evaluate(image).losses()[0]
+            nb += 1
+        test_loss = float((acc / max(nb, 1)).item())
+        print('====> Test set loss: {:.4f}'.format(test_loss))
+        return test_loss
+
+    best_loss = float(sys.maxsize)
+    history = {"train": [], "test": [], "kl_lambda": []}
+    schedule = kl_lambdas(args.dataset, args.epochs, bool(getattr(args, "anneal_kl", False)))
+    for epoch in range(1, args.epochs + 1):
+        kl_lambda = schedule[epoch - 1]
+        history["kl_lambda"].append(kl_lambda)
+        history["train"].append(train(epoch, kl_lambda))
+        loss = test(kl_lambda)
+        history["test"].append(loss)
+        is_best = loss < best_loss
+        best_loss = min(loss, best_loss)
+        save_checkpoint(checkpoint_dict(vae, trainer.engine, best_loss, args.n_latents), is_best, folder=args.out)
+        if args.results:
+            os.makedirs(args.results, exist_ok=True)
+            sample = torch.randn(64, args.n_latents, device=dev)
+            vae.eval()
+            with torch.no_grad():
+                torch.save(vae.decode(sample).cpu().view(64, 3, side, side), os.path.join(args.results, 'sample_image_epoch%d.pt' % epoch))
+    return history
+
+
+if __name__ == "__main__":
+    main()
