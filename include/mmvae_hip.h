@@ -500,6 +500,43 @@ int mmvae_latent1_fwd(const float* enc_out, const float* eps_or_null, int B, int
 int mmvae_latent1_bwd(const float* mu, const float* logvar, const float* eps_or_null, const float* dz_or_null, int B, int D, int training,
                       float kl_coef, void* d_enc_out_bf16, int ld, float* d_bias_or_null, const float* loss_slots_or_null,
                       float* loss_out_or_null, float* scratch, void* stream);
+/* The same gradient in fp32 [B][ld] (ld >= 2D, pad columns exact zeros), for an encoder whose backward takes fp32: every element is the
+ * fp32 rounding of the value mmvae_latent1_bwd rounds to bf16, so bf16(d_enc_out) equals its output bit for bit.  No bias sum, no
+ * scratch, nothing is added up across threads. */
+int mmvae_latent1_bwd_f32(const float* mu, const float* logvar, const float* eps_or_null, const float* dz_or_null, int B, int D,
+                          int training, float kl_coef, float* d_enc_out, int ld, void* stream);
+
+/* ---------------------------------------------------------------- text-only VAE baseline (COCO)
+ * TextVAE of coco/model.py:120-144 -- TextEncoder and TextDecoder with reparametrize between them and NO product of experts -- trained
+ * by coco/train_textonly.py:106-120 on loss = lambda_y * sum((recon - text)^2) / (B * steps * 300) + kl_lambda * KL / B.  The step runs
+ * on the COCO plan and buffers under the text_encoder.* / text_decoder.* names of its parameter table (n_latents 4..124, a multiple of
+ * 4: the operand padding of the caption kernels); the image half is never launched: its gradients are exactly 0 after a step with
+ * do_backward (which includes optimizer.zero_grad()), its parameters, BatchNorm buffers and num_batches_tracked are not written.
+ * ONE pass over B rows: the bf16 persistent caption encoder, the one-expert latent block (mmvae_latent1_fwd / mmvae_latent1_bwd_f32;
+ * mu and logvar are the encoder's halves bit for bit), the caption decoder on one row group with the squared error, backward.
+ * Workspace: the one-pass carve, mmvae_coco_text_step_workspace_bytes (== mmvae_coco_module_workspace_bytes). */
+typedef struct {
+    void* ws; size_t ws_bytes;
+    const long long* step_counter;          /* device int64 keying the Philox streams, or NULL */
+    const float* text;                      /* [B][steps][300] */
+    const float* sos;                       /* [300] */
+    const float* eps;                       /* [B][D] or NULL (drawn on device) */
+    const uint8_t* gru_keep;                /* [steps][B][200] keep flags of the decoder's inter-layer Dropout or NULL (drawn) */
+    int gru_dropout;                        /* 0: no dropout */
+    float kl_lambda; float lambda_y;
+    unsigned long long seed;
+    float* sums;                            /* out [16]: [4] squared-error sum, [8] KL sum, the rest 0 */
+    float* recon_text;                      /* out [B][steps][300] or NULL */
+    float* mu; float* logvar;               /* out [B][D] or NULL */
+    int defer_unpack; int pack_first;       /* as in mmvae_coco_step_io; pack_first refreshes the caption half's packed weights only */
+    long long* optimizer_state;             /* as in mmvae_coco_step_io: a void step marks itself */
+} mmvae_text_step_io;
+int mmvae_coco_text_step(mmvae_coco_t*, const mmvae_text_step_io*, int training, int do_backward, void* stream);
+size_t mmvae_coco_text_step_workspace_bytes(const mmvae_coco_t*);
+/* sse_y of mmvae_coco_iw_score alone: the eval-mode caption decoder on the B*K particle rows and the squared-error kernel; the image
+ * decoder does not run.  Workspace: mmvae_coco_iw_workspace_bytes. */
+int mmvae_coco_iw_score_text(mmvae_coco_t*, void* ws, size_t ws_bytes, const float* z, const float* text, const float* sos,
+                             int B, int K, float* sse_y, void* stream);
 
 /* ---------------------------------------------------------------- dataset-independent ops */
 /* ProductOfExperts.forward (multimnist/model.py:355-360) over M stacked experts of n scalars each */

@@ -110,6 +110,22 @@ class ImageStepIO(C.Structure):
     ]
 
 
+class TextStepIO(C.Structure):
+    """mmvae_text_step_io"""
+    _fields_ = [
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+        ("step_counter", C.c_void_p),
+        ("text", C.c_void_p), ("sos", C.c_void_p), ("eps", C.c_void_p), ("gru_keep", C.c_void_p),
+        ("gru_dropout", C.c_int),
+        ("kl_lambda", C.c_float), ("lambda_y", C.c_float),
+        ("seed", C.c_ulonglong),
+        ("sums", C.c_void_p), ("recon_text", C.c_void_p),
+        ("mu", C.c_void_p), ("logvar", C.c_void_p),
+        ("defer_unpack", C.c_int), ("pack_first", C.c_int),
+        ("optimizer_state", C.c_void_p),
+    ]
+
+
 _P, _I, _F, _LL, _SZ, _ULL, _U = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t, C.c_ulonglong, C.c_uint
 
 # name -> (restype, argtypes); restype int means "status code, raise on != 0"
@@ -258,6 +274,10 @@ for _f in ("celeba", "coco"):
     SIGNATURES["mmvae_%s_image_step" % _f] = (_I, [_P, C.POINTER(ImageStepIO), _I, _I, _P])
     SIGNATURES["mmvae_%s_image_step_workspace_bytes" % _f] = (_SZ, [_P])
     SIGNATURES["mmvae_%s_iw_score_image" % _f] = (_I, [_P, _P, _SZ, _P, _P, _I, _I, _P, _P])
+SIGNATURES["mmvae_coco_text_step"] = (_I, [_P, C.POINTER(TextStepIO), _I, _I, _P])
+SIGNATURES["mmvae_coco_text_step_workspace_bytes"] = (_SZ, [_P])
+SIGNATURES["mmvae_coco_iw_score_text"] = (_I, [_P, _P, _SZ, _P, _P, _P, _I, _I, _P, _P])
+SIGNATURES["mmvae_latent1_bwd_f32"] = (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _I, _P])
 SIGNATURES["mmvae_latent1_scratch_floats"] = (_SZ, [_I, _I])
 SIGNATURES["mmvae_latent1_fwd"] = (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P])
 SIGNATURES["mmvae_latent1_bwd"] = (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P])

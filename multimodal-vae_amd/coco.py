@@ -31,7 +31,7 @@ import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
 from ._ops import geometry
-from .core import CocoState, FusedCocoStep, FusedImageStep, StepOutputs
+from .core import CocoState, FusedCocoStep, FusedImageStep, FusedTextStep, StepOutputs
 from .mmd import compute_kernel, compute_mmd, mmd_terms  # noqa: F401  (coco/model.py:385-402)
 from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
                          _gscale, _seed_from_torch, _stream, swish)
@@ -632,3 +632,80 @@ class ImageVAETrainer:
 
     def evaluate(self, image, **kw) -> StepOutputs:
         return self.engine.forward_backward(image, training=False, backward=False, **kw)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the uni-modal caption baseline (coco/model.py:120-144, coco/train_textonly.py)
+# ----------------------------------------------------------------------------------------------------------------
+MIN_LATENTS, MAX_LATENTS, LATENTS_STEP = 4, 124, 4     # what mmvae_coco_create takes: the operand padding of the caption kernels
+
+
+def check_text_latents(n_latents) -> int:
+    """The latent sizes the COCO plan is built for, refused on the host with the range in the message."""
+    n = int(n_latents)
+    if n < MIN_LATENTS or n > MAX_LATENTS or n % LATENTS_STEP != 0:
+        raise MMVAEError("TextVAE: n_latents=%d does not fit the caption kernels' operand padding; the COCO plan takes n_latents in "
+                         "%d..%d, a multiple of %d (the reference script's default of 200 is outside that range: train_textonly "
+                         "defaults to 100)" % (n, MIN_LATENTS, MAX_LATENTS, LATENTS_STEP))
+    return n
+
+
+class TextVAE(nn.Module):
+    """coco/model.py:120-144: ``TextEncoder`` + ``reparametrize`` + ``TextDecoder`` under the reference's ``encoder.`` / ``decoder.``
+    keys, with NO product of experts.  The two children share ONE core on the MultimodalVAE's plan (``encoder.gru.weight_ih_l0`` is
+    its ``text_encoder.gru.weight_ih_l0``), which is what ``TextVAETrainer`` steps in one enqueue; the image half of the flat
+    buffers is never read or written and never shows in ``state_dict()``.  ``sos`` / ``words`` / ``steps`` as for ``TextDecoder``.
+    ``n_latents``: 4..124 in multiples of 4 (the reference script's 200 is refused)."""
+
+    def __init__(self, n_latents=20, use_cuda=False, words: Optional[WordTable] = None, sos=None, steps=MAX_WORDS):
+        n_latents = check_text_latents(n_latents)
+        super().__init__()
+        self.encoder = TextEncoder(n_latents, steps=steps)
+        self.decoder = TextDecoder(n_latents, use_cuda=use_cuda, sos=sos, steps=steps, words=words)
+        self.n_latents = n_latents
+        self.steps = steps
+        self._core = _Core(self, "text_", n_latents, lambda n, d: CocoState(n, d, steps))
+        for m in (self.encoder, self.decoder):
+            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+
+    def encode(self, x):
+        return self.encoder(x)
+
+    reparametrize = MultimodalVAE.reparametrize
+
+    def decode(self, z, keep: Optional[torch.Tensor] = None):
+        return self.decoder(z, keep)
+
+    def forward(self, x, eps=None, gru_keep=None):
+        mu, logvar = self.encode(x)
+        z = self.reparametrize(mu, logvar, eps)
+        return self.decode(z, gru_keep), mu, logvar
+
+
+def load_checkpoint_textonly(file_path, use_cuda=False, sos=None, words: Optional[WordTable] = None, steps=MAX_WORDS):
+    """coco/train_textonly.py:28-40: rebuilds a TextVAE from the checkpoint dict (``state_dict``, ``n_latents``).  The '<s>' vector is
+    not in the state dict: give ``sos=`` or a word table that has '<s>'."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    vae = TextVAE(n_latents=checkpoint['n_latents'], use_cuda=use_cuda, sos=sos, words=words, steps=steps)
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
+
+
+class TextVAETrainer:
+    """``TextVAETrainer(vae, batch_size, lr)(text)`` == zero_grad + forward + loss + backward + Adam step
+    (coco/train_textonly.py:106-120, lr default 1e-4, kl_lambda 1e-3) on ``vae``'s own parameters: one pass over B rows."""
+
+    def __init__(self, vae: TextVAE, batch_size: int, lr: float = 1e-4, kl_lambda: float = 1e-3, seed: int = 1234):
+        dev = next(vae.parameters()).device
+        self.vae = vae
+        st = vae._core.sync(dev)
+        self.engine = FusedTextStep(st, batch_size, vae.decoder.sos, lr=lr, kl_lambda=kl_lambda, seed=seed)
+
+    def __call__(self, text, **kw) -> StepOutputs:
+        self.engine.gru_dropout = self.vae.decoder.gru.dropout > 0
+        return self.engine(text, **kw)
+
+    def evaluate(self, text, **kw) -> StepOutputs:
+        return self.engine.forward_backward(text, training=False, backward=False, **kw)

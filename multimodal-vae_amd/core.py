@@ -111,7 +111,23 @@ class PlanState:
         self._c("pack_weights", self.plan(1), _stream())
         self.pack_pending = False
 
-    pack_pending = False        # the parameters changed and the bf16 GEMM copies were not refreshed yet
+    # the parameters changed and the bf16 GEMM copies were not refreshed yet.  Whoever sets the flag owes a refresh of every pack;
+    # defer_text_pack() narrows that to the caption half when nothing else is owed (the text-only step's own update).
+    _pack_pending = False
+    _pack_text_only = False
+
+    @property
+    def pack_pending(self) -> bool:
+        return self._pack_pending
+
+    @pack_pending.setter
+    def pack_pending(self, v) -> None:
+        self._pack_pending, self._pack_text_only = bool(v), False
+
+    def defer_text_pack(self) -> None:
+        """Only text_encoder.* / text_decoder.* changed: a step that refreshes the caption half's packs settles the debt."""
+        only = self._pack_text_only or not self._pack_pending
+        self._pack_pending, self._pack_text_only = True, only
 
     def ensure_packed(self) -> None:
         """Refresh the packed weights if an optimizer step deferred it (the MultiMNIST fused step folds the refresh into
@@ -722,3 +738,90 @@ class FusedImageStep(_FusedStepBase):
 
     def capture(self, image: torch.Tensor) -> None:
         raise MMVAEError("FusedImageStep: HIP-graph capture is not offered for the image-only step")
+
+
+class FusedTextStep(_FusedStepBase):
+    """The step of coco/train_textonly.py:106-120 on the COCO plan: zero_grad -> ONE pass over B rows (caption encoder, reparametrize,
+    caption decoder; no product of experts) -> lambda_y * MSE + kl_lambda * KL -> backward -> Adam.  ``state`` is a ``CocoState``; the
+    image half is never launched: its parameters and BatchNorm buffers keep their values and its gradient is exactly 0.
+    ``StepOutputs`` carries the pass in slot 0 of the text terms (``parts()[1][0]``, ``parts()[2][0]``)."""
+
+    EMB = 300
+    TEXT_PREFIXES = ("text_encoder.", "text_decoder.")
+    _DEFER_PACK = True          # the step refreshes the caption half's packed weights itself (pack_first)
+
+    def __init__(self, state: PlanState, batch: int, sos: torch.Tensor, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
+                 kl_lambda: float = 1e-3, lambda_y: float = 1.0, seed: int = 1234):
+        if state.API != "coco":
+            raise MMVAEError("FusedTextStep: no text-only step for the '%s' family (COCO has one)" % state.API)
+        super().__init__(state, batch, lr, betas, eps, seed)
+        self.kl_lambda, self.lambda_y = kl_lambda, lambda_y
+        self.T = state.steps
+        self.sos = sos.to(device=state.device, dtype=torch.float32).contiguous().reshape(self.EMB)
+        self.gru_dropout = True
+        # the caption half is one run at the tail of the flat buffers: the optimizer visits nothing else when the run is 4-aligned
+        first = min(off for name, _, off in state.table if name.startswith(self.TEXT_PREFIXES))
+        assert all(name.startswith(self.TEXT_PREFIXES) == (off >= first) for name, _, off in state.table), \
+            "the caption parameters are expected to be contiguous at the tail of the table"
+        self.text_param_range = (first, state.nparams - first)
+        self._ranges = (C.c_longlong * 2)(first, state.nparams - first) if first % 4 == 0 and state.nparams % 4 == 0 and first > 0 else None
+
+    def _workspace_bytes(self, state: PlanState, batch: int) -> int:
+        return state._c("text_step_workspace_bytes", state.plan(batch))
+
+    def _outputs(self) -> StepOutputs:
+        return StepOutputs(self.sums, 1.0, self.B * self.T * self.EMB, self.kl_lambda / self.B, (0.0, 0.0, 0.0),
+                           (self.lambda_y, 0.0, 0.0), (True, False, False))
+
+    def forward_backward(self, text, training=True, backward=True, eps=None, gru_keep=None, recon_text=None, mu=None, logvar=None,
+                         _defer_unpack=False) -> StepOutputs:
+        assert text.is_contiguous() and text.dtype == torch.float32
+        assert text.shape == (self.B, self.T, self.EMB)
+        st = self.state
+        if st.pack_pending and not st._pack_text_only:      # somebody else changed parameters of the image half as well
+            st.pack_weights()
+        io = _lib.TextStepIO()
+        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
+        io.step_counter = self.adam_state.data_ptr()
+        io.optimizer_state = self.adam_state.data_ptr() if backward else None     # a void step (exchange time-out) skips its Adam update
+        io.text, io.sos = text.data_ptr(), self.sos.data_ptr()
+        for k, t in (("eps", eps), ("gru_keep", gru_keep), ("recon_text", recon_text), ("mu", mu), ("logvar", logvar)):
+            setattr(io, k, None if t is None else t.data_ptr())
+        io.gru_dropout = int(self.gru_dropout)
+        io.kl_lambda, io.lambda_y = self.kl_lambda, self.lambda_y
+        io.seed = self.seed
+        io.sums = self.sums.data_ptr()
+        io.defer_unpack = int(bool(_defer_unpack))
+        io.pack_first = int(st.pack_pending)
+        call("mmvae_coco_text_step", self.h, C.byref(io), int(training), int(backward), _stream())
+        st.pack_pending = False
+        return self._outputs()
+
+    def evaluate(self, text, **kw) -> StepOutputs:
+        """Eval-mode forward (z = mu, no dropout, nothing drawn), no backward."""
+        return self.forward_backward(text, False, False, **kw)
+
+    def _after_update(self) -> None:
+        self.state.defer_text_pack()
+
+    def __call__(self, text, **kw) -> StepOutputs:
+        """backward + optimizer.step() in one pass over the caption parameters: the packed-gradient Adam (see _call_packed)."""
+        st = self.state
+        if self.separate_unpack:
+            out = self.forward_backward(text, True, True, **kw)
+            self.optimizer_step()
+            return out
+        out = self.forward_backward(text, True, True, _defer_unpack=True, **kw)
+        if self._ranges is not None:
+            call("mmvae_adam_step_packed_ranges", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
+                 self._ranges, 1, 1, ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0,
+                 ptr(st.grad_map()), ptr(st.gpk), ptr(st.gpk_vec), _stream())
+        else:
+            call("mmvae_adam_step_packed", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
+                 ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk),
+                 ptr(st.gpk_vec), _stream())
+        self._after_update()
+        return out
+
+    def capture(self, text: torch.Tensor) -> None:
+        raise MMVAEError("FusedTextStep: HIP-graph capture is not offered for the text-only step")

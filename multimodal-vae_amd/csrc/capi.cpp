@@ -328,6 +328,17 @@ size_t mmvae_coco_image_step_workspace_bytes(const mmvae_coco_t* p) { return p ?
 int mmvae_coco_iw_score_image(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, void* st) {
     return guarded([&] { return coco_iw_score_image(p, ws, wsb, z, image, B, K, loglik_x, S(st)); });
 }
+int mmvae_coco_text_step(mmvae_coco_t* p, const mmvae_text_step_io* io, int training, int do_backward, void* stream) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_coco_text_step: null argument");
+        return coco_text_step(p, *io, training, do_backward, S(stream));
+    });
+}
+size_t mmvae_coco_text_step_workspace_bytes(const mmvae_coco_t* p) { return p ? coco_text_step_workspace_bytes(p) : 0; }
+int mmvae_coco_iw_score_text(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* text, const float* sos, int B, int K,
+                             float* sse_y, void* st) {
+    return guarded([&] { return coco_iw_score_text(p, ws, wsb, z, text, sos, B, K, sse_y, S(st)); });
+}
 int mmvae_coco_image_encoder_fwd(mmvae_coco_t* p, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2, int training, float* out, void* st) {
     return guarded([&] { return coco_image_encoder_fwd(p, ws, wsb, image, m1, m2, training, out, S(st)); });
 }
@@ -403,6 +414,15 @@ int mmvae_latent1_bwd(const float* mu, const float* logvar, const float* eps, co
         a.f.scratch = scratch;
         a.dz = dz; a.kl_coef = kl_coef; a.d_enc_out = (bf16*)d_enc_out_bf16; a.ld = ld; a.d_bias = d_bias; a.loss_slots = loss_slots; a.loss_out = loss_out;
         return launch_latent1_bwd(a, S(st));
+    });
+}
+int mmvae_latent1_bwd_f32(const float* mu, const float* logvar, const float* eps, const float* dz, int B, int D, int training, float kl_coef,
+                          float* d_enc_out, int ld, void* st) {
+    return guarded([&] {
+        Latent1BwdF32Args a{};
+        a.B = B; a.D = D; a.mu = mu; a.logvar = logvar; a.eps = eps; a.dz = dz; a.training = training; a.kl_coef = kl_coef;
+        a.d_enc_out = d_enc_out; a.ld = ld;
+        return launch_latent1_bwd_f32(a, S(st));
     });
 }
 int mmvae_kl_fwd(const float* mu, const float* lv, int n, float* out, void* s) { return launch_kl_fwd(mu, lv, n, out, S(s)); }

@@ -16,6 +16,11 @@ int coco_step(CocoPlan*, const mmvae_coco_step_io&, int training, int do_backwar
 int coco_image_step(CocoPlan*, const mmvae_image_step_io&, int training, int do_backward, hipStream_t);
 size_t coco_image_step_workspace_bytes(const CocoPlan*);
 int coco_iw_score_image(CocoPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t);
+// text-only VAE (coco/model.py:120-144): one pass over B rows in the one-pass carve, caption half only, and the squared error of the
+// particle rows' sentences alone
+int coco_text_step(CocoPlan*, const mmvae_text_step_io&, int training, int do_backward, hipStream_t);
+size_t coco_text_step_workspace_bytes(const CocoPlan*);
+int coco_iw_score_text(CocoPlan*, void* ws, size_t wsb, const float* z, const float* text, const float* sos, int B, int K, float* sse_y, hipStream_t);
 // granular module entry points (drop-in nn.Module forwards); B rows, every call brings its workspace
 int coco_image_encoder_fwd(CocoPlan*, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2, int training, float* out, hipStream_t);
 int coco_image_encoder_bwd(CocoPlan*, void* ws, size_t wsb, const float* d_out, const uint8_t* m1, const uint8_t* m2, hipStream_t);

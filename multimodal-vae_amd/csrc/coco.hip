@@ -398,6 +398,101 @@ int coco_iw_score_image(CocoPlan* P, void* ws, size_t wsb, const float* z, const
     return launch_coco_iw_tail(tower_iw_tail_args(*P, image, rows, K, loglik_x), s);
 }
 
+// ---------------------------------------------------------------- text-only VAE (coco/model.py:120-144, coco/train_textonly.py:106-120)
+// One pass on B rows in the one-pass carve: caption encoder (bf16 persistent kernels), latent1 -- no product of experts --, caption
+// decoder with ONE row group and the squared error on it, and the backward chain.  The image half of the plan is not touched: no
+// conv, dense or BatchNorm launch runs, its gradients stay at the zero the step's prologue wrote, its parameters and BatchNorm
+// buffers are not written.  Everything runs on the caller's stream except what the 3-pass step also takes off the caption chain: the
+// weight gradients, which only feed the optimizer (second weight-gradient stream; MMVAE_SERIAL: in order).
+static int coco_text_step_body(CocoPlan* Pp, const mmvae_text_step_io& io, int training, int do_backward, hipStream_t s) {
+    MMVAE_TRY(use_ws(Pp, io.ws, io.ws_bytes));
+    CocoPlan& P = *Pp;
+    CocoPlan::W& w = P.w;
+    const int B = P.B, D = P.D, T = P.T;
+    MMVAE_REQUIRE(io.text && io.sos && io.sums, "coco text step: text/sos/sums must be given");
+    MMVAE_REQUIRE(launch_latent1_scratch_floats(B, D) <= (size_t)B * NPIX, "coco text step: no room for the latent block's partial sums");
+    const float* eps = io.eps;
+    const uint8_t* gk = io.gru_keep;
+    StepBeginArgs sb{};
+    sb.zero_ptr[0] = w.zero_begin; sb.zero_bytes[0] = w.zero_bytes;
+    if (do_backward) {
+        sb.zero_ptr[1] = P.buf.gpk; sb.zero_bytes[1] = (size_t)P.gk.mat_elems * sizeof(float);
+        sb.zero_ptr[2] = P.buf.grads; sb.zero_bytes[2] = (size_t)(P.nparams / 4) * 16;
+    }
+    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_counter;
+    if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B * D; eps = w.eps; }
+    if (training && io.gru_dropout && !gk) { sb.mask[2] = w.gkeep; sb.n_mask[2] = (long long)T * B * COCO_H; gk = w.gkeep; }
+    if (!(training && io.gru_dropout)) gk = nullptr;
+    MMVAE_TRY(launch_step_begin(sb, s));
+    if (do_backward && P.nparams % 4 != 0)
+        MMVAE_TRY(launch_fill_zero(P.buf.grads + (P.nparams / 4) * 4, (size_t)(P.nparams % 4) * sizeof(float), s));
+    MMVAE_TRY(ensure_streams(P));
+    const bool serial = mmvae_serial();
+    hipStream_t Sw = serial ? s : P.st_wgrad2;
+    if (io.pack_first && !P.no_pack)      // the caption half's packs only (the table's tail): the image half's are never read here
+        MMVAE_TRY(launch_pack_range(P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.pk_text_begin, (int)P.pk.d.size(), P.buf.params,
+                                    P.buf.packed, P.buf.packed_vec, s));
+    MMVAE_TRY(coco_text_enc_fwd(P, io.text, do_backward, w.txtout, s, true));
+    Latent1Args la{};
+    la.B = B; la.D = D; la.enc_out = w.txtout; la.eps = eps;
+    la.mu = io.mu ? io.mu : w.mu; la.logvar = io.logvar ? io.logvar : w.logvar;
+    la.z_f32 = w.z_f32; la.z_bf = w.z_bf; la.ldz = P.ldz; la.kl_sum = w.sums + 8; la.training = training;
+    la.scratch = w.tmp_f32;         // (the module image decoder's sigmoid-backward buffer: nobody else's in this step)
+    MMVAE_TRY(launch_latent1_fwd(la, s));
+    float* sentence = io.recon_text ? io.recon_text : w.td_recon;
+    {
+        CocoMseFuse mf{};
+        mf.coef[0] = io.lambda_y / ((float)B * (float)T * (float)COCO_E);
+        mf.target = io.text; mf.loss_sum = w.sums; mf.dw = do_backward ? w.td_dw : nullptr; mf.dw16 = P.text_bf16 ? w.tb_dw16 : nullptr;
+        MMVAE_TRY(coco_text_dec_fwd(P, w.z_f32, 1, io.sos, gk, do_backward, sentence, s, true, &mf));
+        if (!P.mse_fused)
+            MMVAE_TRY(coco_mse3(sentence, io.text, 1, (long long)B * T * COCO_E, mf.coef, w.sums, mf.dw, s));
+        P.dw16_fresh = do_backward && P.mse_fused;
+    }
+    if (!do_backward) {
+        hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, s, w.sums, io.sums, P.cl_alarm_f, (const unsigned*)nullptr);
+        return mmvae_check_launch("sum_slots");
+    }
+    // =============================== backward ===============================
+    MMVAE_TRY(coco_text_dec_bwd(P, w.z_f32, 1, io.sos, gk, sentence, w.td_dw, w.dz_txt, s, Sw, true));
+    Latent1BwdF32Args lb{};
+    lb.B = B; lb.D = D; lb.mu = la.mu; lb.logvar = la.logvar; lb.eps = eps; lb.dz = w.dz_txt; lb.training = training;
+    lb.kl_coef = io.kl_lambda / (float)B; lb.d_enc_out = w.d_txtout; lb.ld = 2 * D;
+    MMVAE_TRY(launch_latent1_bwd_f32(lb, s));
+    MMVAE_TRY(coco_text_enc_bwd(P, io.text, w.d_txtout, s, Sw, true));
+    MMVAE_TRY(coco_text_dec_wgrads(P, Sw));          // (no-op: issued behind the encoder's BPTT launch)
+    MMVAE_TRY(join_sides(P, s, s));
+    if (io.defer_unpack) MMVAE_TRY(launch_wgrad_reduce(&P.slab, s));  // the packed gradients are complete; Adam gathers them
+    else MMVAE_TRY(plan_unpack(P, s, true));
+    // (last kernel of the step, as in coco_step_body: the mark of a void step in the gradient is not overwritten)
+    hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, s, w.sums, io.sums, P.cl_alarm_f, P.cl_alarm_b, io.optimizer_state, P.buf.grads);
+    return mmvae_check_launch("sum_slots");
+}
+size_t coco_text_step_workspace_bytes(const CocoPlan* P) { return P->ws_bytes_module; }
+int coco_text_step(CocoPlan* P, const mmvae_text_step_io& io, int training, int do_backward, hipStream_t s) {
+    return plan_step(P, io, training, do_backward, s, coco_text_step_body);
+}
+// sum of squared errors of the particle rows' sentences alone: coco_iw_score without the image decoder (the same, smaller, carve)
+int coco_iw_score_text(CocoPlan* P, void* ws, size_t wsb, const float* z, const float* text, const float* sos, int B, int K, float* sse_y,
+                       hipStream_t s) {
+    MMVAE_REQUIRE(P && z && text && sos && sse_y, "mmvae_coco_iw_score_text: null argument");
+    MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B,
+                  "mmvae_coco_iw_score_text: %d examples x %d particles exceed the plan's %d rows", B, K, P->B);
+    MMVAE_TRY(use_ws_iw(P, ws, wsb));
+    CocoPlan::W& w = P->w;
+    const int rows = B * K;
+    MMVAE_TRY(zero_ws(*P, s));
+    const float* zt = z;
+    if (rows < P->B) {    // the caption decoder runs the plan's rows: the rows behind the particles are zeros, as in coco_iw_score
+        MMVAE_TRY(launch_fill_zero(w.z_f32, (size_t)P->B * P->D * sizeof(float), s));
+        MMVAE_REQUIRE(hipMemcpyAsync(w.z_f32, z, (size_t)rows * P->D * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess,
+                      "mmvae_coco_iw_score_text: copy of the particles failed");
+        zt = w.z_f32;
+    }
+    MMVAE_TRY(coco_text_dec_fwd(*P, zt, 1, sos, nullptr, 0, w.td_recon, s));
+    return launch_coco_iw_text_sse(w.td_recon, text, B, K, P->T, sse_y, s);
+}
+
 // ---------------------------------------------------------------- granular module entry points (drop-in modules)
 int coco_image_encoder_fwd(CocoPlan* P, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2, int training,
                            float* out, hipStream_t s) {

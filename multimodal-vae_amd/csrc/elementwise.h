@@ -167,6 +167,20 @@ struct Latent1BwdArgs {
     float* loss_out;
 };
 int launch_latent1_bwd(const Latent1BwdArgs& a, hipStream_t s);
+// The same gradient in fp32, for an encoder whose backward takes fp32 (the COCO caption encoder, coco_text_enc_bwd): every element is
+// the fp32 rounding of the double latent1_bwd evaluates, so bf16(d_enc_out) here equals d_enc_out there.  No bias sum (that backward
+// forms the gradient of its last bias itself), no scratch: one thread per element of [B][ld], nothing is added up.
+struct Latent1BwdF32Args {
+    int B, D;
+    const float *mu, *logvar;   // [B][D]
+    const float* eps;           // [B][D], read when training
+    const float* dz;            // [B][D] or null (no reconstruction term)
+    int training;               // 0: no eps term
+    float kl_coef;              // kl_lambda / B
+    float* d_enc_out;           // [B][ld], pad columns [2D, ld) exact zeros
+    int ld;                     // >= 2D
+};
+int launch_latent1_bwd_f32(const Latent1BwdF32Args& a, hipStream_t s);
 
 // bit pattern of the "void step" mark in element 0 of a flat gradient (plan_base.h sum_slots_kernel): a quiet NaN with a payload no
 // arithmetic produces on its own

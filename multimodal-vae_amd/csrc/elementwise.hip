@@ -752,6 +752,25 @@ __global__ __launch_bounds__(TPB) void latent1_bwd_finish_kernel(const double* p
     for (int r = 0; r < nrows; ++r) s += parts[(size_t)r * D2 + c];
     d_bias[c] += (float)s;
 }
+// fp32 form: thread i owns element (b, c) = (i / ld, i % ld) of d_enc_out.  The doubles are latent1_bwd_kernel's, term for term.
+__global__ __launch_bounds__(TPB) void latent1_bwd_f32_kernel(const Latent1BwdF32Args a) {
+    const long long n = (long long)a.B * a.ld;
+    for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
+        const int b = (int)(i / a.ld), c = (int)(i - (long long)b * a.ld);
+        float v = 0.f;
+        if (c < 2 * a.D) {
+            const bool is_mu = c < a.D;
+            const int e = b * a.D + (is_mu ? c : c - a.D);
+            const double dz = a.dz ? (double)a.dz[e] : 0.0;
+            const double mu = a.mu[e], lv = a.logvar[e], kc = a.kl_coef;
+            const double gmu = dz + kc * mu;
+            double glv = -0.5 * kc * (1.0 - exp(lv));
+            if (a.training) glv += dz * (double)a.eps[e] * 0.5 * exp(0.5 * lv);
+            v = is_mu ? (float)gmu : (float)glv;
+        }
+        a.d_enc_out[i] = v;
+    }
+}
 
 // ------------------------------------------------------------------ Adam (torch.optim.Adam defaults)
 __global__ __launch_bounds__(TPB) void adam_kernel(const AdamArgs a, unsigned* done) {
@@ -1144,6 +1163,14 @@ int launch_latent1_bwd(const Latent1BwdArgs& a, hipStream_t s) {
     if (!a.d_bias && !a.loss_slots) return MMVAE_OK;
     MMVAE_LAUNCH(latent1_bwd_finish_kernel, dim3(1), dim3(TPB), 0, s, (const double*)a.f.scratch, nrows, 2 * a.f.D, a.d_bias, a.loss_slots, a.loss_out);
     return mmvae_check_launch("latent1_bwd_finish");
+}
+int launch_latent1_bwd_f32(const Latent1BwdF32Args& a, hipStream_t s) {
+    MMVAE_REQUIRE(a.B >= 1 && a.D >= 1 && a.D <= 128 && (long long)a.B * a.D <= 0x3FFFFFFF, "latent1_bwd_f32: B=%d D=%d out of range (D <= 128)", a.B, a.D);
+    MMVAE_REQUIRE(a.mu && a.logvar && a.d_enc_out && (!a.training || a.eps), "latent1_bwd_f32: null argument");
+    MMVAE_REQUIRE(a.ld >= 2 * a.D && (long long)a.B * a.ld <= 0x3FFFFFFF, "latent1_bwd_f32: ld=%d out of range (>= 2D)", a.ld);
+    const int nb = ceil_div(a.B * a.ld, TPB);
+    hipLaunchKernelGGL(latent1_bwd_f32_kernel, dim3(nb < 1024 ? nb : 1024), dim3(TPB), 0, s, a);
+    return mmvae_check_launch("latent1_bwd_f32");
 }
 int launch_adam(const AdamArgs& a_in, hipStream_t s) {
     AdamArgs a = a_in;

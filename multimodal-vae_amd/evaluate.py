@@ -242,9 +242,12 @@ class _Family:
     decoder's steps T and classes V (words [rows][T][V]), the shape of one image, the particle rows of one scoring call and
     the scoring workspace."""
 
-    def __init__(self, name, T, V, image_shape, rows, score, workspace_bytes, float_text=False, image_only=False):
+    def __init__(self, name, T, V, image_shape, rows, score, workspace_bytes, float_text=False, image_only=False, text_only=False):
         self.name, self.T, self.V, self.image_shape, self.rows = name, T, V, image_shape, rows
         self.score, self.workspace_bytes = score, workspace_bytes
+        # text_only: a TextVAE baseline (coco): there is no image, the scoring call writes the caption term alone and the x / xy
+        # columns of every result are NaN
+        self.text_only = text_only
         # image_only: an ImageVAE baseline (celeba / coco): there is no second modality, the scoring call writes log p(x|z) alone
         # and the y / xy columns of every result are NaN
         self.image_only = image_only
@@ -272,6 +275,15 @@ def _coco_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream, tex
     """words [rows][1][1] = -sse / (2 sigma^2): the per-particle part of log p(y|z); the constant is added after finalize."""
     from ._lib import ptr
     _iw_call("mmvae_coco_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), ptr(text), ptr(sos), nr, nk, ptr(lx), ptr(sse), stream)
+    torch.mul(sse[:rows], scale, out=words[:rows])
+
+
+def _coco_text_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream, text=None, sos=None, sse=None, scale=-0.5):
+    """The scoring call of a TextVAE: mmvae_coco_iw_score_text (the caption decoder and the squared error, no image decoder); log p(x|z) of
+    the image that is not there is 0."""
+    from ._lib import ptr
+    _iw_call("mmvae_coco_iw_score_text", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(text), ptr(sos), nr, nk, ptr(sse), stream)
+    lx[:rows].zero_()
     torch.mul(sse[:rows], scale, out=words[:rows])
 
 
@@ -319,8 +331,11 @@ _FAMILIES = {
                             lambda st, rows: _iw_call("mmvae_celeba_iw_workspace_bytes", st.plan(rows)), image_only=True),
     "coco_image": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _image_score("coco"),
                           lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), image_only=True),
+    "coco_text": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_text_score,
+                         lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), float_text=True, text_only=True),
 }
 IMAGE_ONLY_NAN_COLUMNS = (1, 2, 4, 5, 7)      # of mmvae_iw_finalize's (B, 8): everything that involves y
+TEXT_ONLY_NAN_COLUMNS = (0, 2, 3, 5, 6)       # ... everything that involves x
 
 
 def _family(model):
@@ -329,6 +344,9 @@ def _family(model):
     from .mnist import MultimodalVAE as MnistVAE
     from .celeba import ImageVAE as CelebaImageVAE
     from .coco import ImageVAE as CocoImageVAE
+    from .coco import TextVAE as CocoTextVAE
+    if isinstance(model, CocoTextVAE):
+        return _FAMILIES["coco_text"]
     if isinstance(model, (CelebaImageVAE, CocoImageVAE)):
         return _FAMILIES["celeba_image" if isinstance(model, CelebaImageVAE) else "coco_image"]
     return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else
@@ -389,6 +407,8 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     capacity = fam.rows if particles_per_call is None else B * int(particles_per_call)
     chunks = iw_chunks(B, K, capacity)
     rows_max = max(nr * nk for _, nr, _, nk in chunks)
+    if fam.text_only:           # no image: ``image`` is ignored
+        image = torch.zeros(B, int(np.prod(fam.image_shape)), dtype=torch.float32, device=dev) if image is None else image
     image = image.reshape(B, -1).contiguous().float()
     extra, sse_all, text_const = {}, None, 0.0
     if fam.image_only:
@@ -401,7 +421,8 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
             raise ValueError("iw_estimate: a coco model of %d steps takes images (B,3,32,32) and captions (B,%d,300) for its B = %d "
                              "proposals (got %s, %s)" % (steps, steps, B, tuple(image.shape), tuple(text.shape)))
         text = torch.zeros(B, 1, dtype=torch.int64, device=mu.device)          # the one "class" of the one caption position
-        extra = dict(sos=model.text_decoder.sos.to(mu.device, torch.float32).contiguous(), scale=-0.5 / float(text_sigma) ** 2)
+        decoder = model.decoder if fam.text_only else model.text_decoder
+        extra = dict(sos=decoder.sos.to(mu.device, torch.float32).contiguous(), scale=-0.5 / float(text_sigma) ** 2)
     else:
         text = text.contiguous().long()
     if image.shape[1] != int(np.prod(fam.image_shape)) or text.numel() != B * fam.T:
@@ -447,6 +468,11 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
         out[:, IMAGE_ONLY_NAN_COLUMNS] = float("nan")
         if lw_all is not None:
             lw_all[..., 1:3] = float("nan")
+    if fam.text_only:           # a TextVAE defines p(y) alone
+        out[:, TEXT_ONLY_NAN_COLUMNS] = float("nan")
+        if lw_all is not None:
+            lw_all[..., 0] = float("nan")
+            lw_all[..., 2] = float("nan")
     res = {"log_p": out[:, 0:3], "ess": out[:, 3:6], "nll": out[:, 6:8]}
     if return_z:
         res["z"] = z_all
@@ -460,8 +486,12 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
 def _proposal(model, image, text, posterior):
     """(mu, logvar) of the eval-mode encoders + ProductOfExperts over the posterior's modalities (no decoder runs)."""
     fam = _family(model)
-    image = image.reshape(image.shape[0], *fam.image_shape)
     posterior = _posterior(posterior)
+    if fam.text_only:           # q(z|y) of the encoder itself: a TextVAE has no experts
+        if posterior != "text":
+            raise ValueError("a TextVAE has the text posterior alone: posterior must be \"text\" (got %r)" % (posterior,))
+        return model.encoder(text)
+    image = image.reshape(image.shape[0], *fam.image_shape)
     if fam.image_only:          # q(z|x) of the encoder itself: an ImageVAE has no experts
         if posterior != "image":
             raise ValueError("an ImageVAE has the image posterior alone: posterior must be \"image\" (got %r)" % (posterior,))
@@ -506,17 +536,19 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
         raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
     if _family(model).image_only and posterior != "image":
         raise ValueError("an ImageVAE has the image posterior alone: posterior must be \"image\" (got %r)" % (posterior,))
+    if _family(model).text_only and posterior != "text":
+        raise ValueError("a TextVAE has the text posterior alone: posterior must be \"text\" (got %r)" % (posterior,))
     model.eval()
     dev = next(model.parameters()).device
     logp, ess, nll, n_seen = [], [], [], 0
     for image, text in loader:
         fam = _family(model)
-        image = image.to(dev).float().reshape(-1, *fam.image_shape)
+        image = None if fam.text_only else image.to(dev).float().reshape(-1, *fam.image_shape)      # (a TextVAE's loader may yield None there)
         text = None if fam.image_only else text.to(dev).float() if fam.float_text else text.to(dev).long()
         mu, logvar = _proposal(model, image, text, posterior)
         r = iw_estimate(model, image, text, mu, logvar, n_particles, seed=seed, first_row=n_seen, text_sigma=text_sigma)
         logp.append(r["log_p"]); ess.append(r["ess"]); nll.append(r["nll"])
-        n_seen += image.shape[0]
+        n_seen += mu.shape[0]
         if verbose:
             print('Evaluating [{}]: {} examples'.format(posterior, n_seen))
     if n_seen == 0:
@@ -571,8 +603,14 @@ def sample_coco(vae, n_samples=64, image=None, text=None, stop_at_eos=False, see
     (1,102,300) caption vectors (``WordTable.embed``).  ``vae`` carries the word table (``MultimodalVAE(..., words=)``)."""
     vae.eval()
     dev = next(vae.parameters()).device
+    text_only = _family(vae).text_only          # a TextVAE: captions alone (the images are None), conditioned on a caption at most
+    if text_only and image is not None:
+        raise ValueError("sample_coco: a TextVAE cannot be conditioned on an image")
     if image is None and text is None:
         mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
+    elif text_only:
+        mu, logvar = vae.encode(text.to(dev))
+        std = logvar.mul(0.5).exp()
     elif text is None:
         mu, logvar = vae.encode_image(image.to(dev))
         std = logvar.mul(0.5).exp()
@@ -587,6 +625,8 @@ def sample_coco(vae, n_samples=64, image=None, text=None, stop_at_eos=False, see
     g = None if seed is None else torch.Generator().manual_seed(seed)
     z = torch.randn(n_samples, vae.n_latents, generator=g).to(dev)
     z = (z * std.expand_as(z) + mu.expand_as(z)).contiguous()
+    if text_only:
+        return None, vae.decoder.generate(z, stop_at_eos=stop_at_eos)
     image_recon = vae.decode_image(z).cpu().view(n_samples, 3, 32, 32)
     return image_recon, vae.text_decoder.generate(z, stop_at_eos=stop_at_eos)
 
@@ -850,6 +890,15 @@ def _parser():
     pt.add_argument('--synthetic', type=int, default=0, metavar='N')
     pt.add_argument('--batch_size', type=int, default=128, metavar='N')
     pt.add_argument('--seed', type=int, default=0)
+    px = sub.add_parser("test_textonly", help="eval-mode loss (kl_lambda = 1) of a train_textonly checkpoint, as test_imageonly")
+    px.add_argument('model_path', type=str)
+    px.add_argument('--data', type=str, default='', help='DIR with captions.pt (and sos.pt), as train_coco reads')
+    px.add_argument('--synthetic', type=int, default=0, metavar='N')
+    px.add_argument('--batch_size', type=int, default=64, metavar='N')
+    px.add_argument('--seed', type=int, default=0)
+    tab = px.add_mutually_exclusive_group()
+    tab.add_argument('--sos', type=str, default=None, metavar='FILE.pt', help="the 300 floats of GloVe('<s>') (default: sos.pt of --data)")
+    tab.add_argument('--words', type=str, default=None, metavar='TABLE.pt', help="word table file (coco.save_word_table) that has '<s>'")
     pw = sub.add_parser("sample_coco", help="multimnist/sample.py for the COCO family: images + captions decoded to words")
     pw.add_argument('model_path', type=str, help='path to a checkpoint written by train_coco')
     tab = pw.add_mutually_exclusive_group(required=True)
@@ -1068,7 +1117,10 @@ def _sample_coco_main(args):
         words = K.WordTable(*D.synthetic_word_table(args.synthetic_words, seed=args.seed), device=dev)
     else:
         words = K.load_word_table(args.words, dev)
-    vae = K.load_checkpoint(args.model_path, use_cuda=True, words=words)
+    textonly = is_textonly_checkpoint(args.model_path)            # a checkpoint of train_textonly: captions only
+    if textonly and args.condition_on_image:
+        raise SystemExit("sample_coco: a text-only checkpoint cannot be conditioned on an image")
+    vae = (K.load_checkpoint_textonly if textonly else K.load_checkpoint)(args.model_path, use_cuda=True, words=words)
     image = text = None
     if args.condition_on_image:
         im = torch.load(args.condition_on_image)
@@ -1077,7 +1129,8 @@ def _sample_coco_main(args):
         text = words.embed(args.condition_on_text).unsqueeze(0)
     image_recon, captions = sample_coco(vae, args.n_samples, image, text, stop_at_eos=args.stop_at_eos, seed=args.seed)
     os.makedirs(args.out, exist_ok=True)
-    torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))
+    if image_recon is not None:
+        torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))
     with open(os.path.join(args.out, 'sample_text.txt'), 'w') as fp:
         for c in captions:
             fp.write('%s\n' % c)
@@ -1135,6 +1188,37 @@ def is_imageonly_checkpoint(path):
     with ``encoder.`` or ``decoder.``."""
     keys = list(torch.load(path, map_location='cpu', weights_only=False)['state_dict'].keys())
     return len(keys) > 0 and all(k.startswith(("encoder.", "decoder.")) for k in keys)
+
+
+def is_textonly_checkpoint(path):
+    """True for a checkpoint of ``train_textonly`` (or the reference's train_textonly.py): its ``state_dict`` has the caption encoder's
+    ``encoder.gru.weight_ih_l0``.  Asked BEFORE ``is_imageonly_checkpoint``, whose prefixes a text-only checkpoint shares."""
+    return "encoder.gru.weight_ih_l0" in torch.load(path, map_location='cpu', weights_only=False)['state_dict']
+
+
+@torch.no_grad()
+def test_textonly(vae, loader, kl_lambda=1.0, verbose=True):
+    """The counterpart of ``test_imageonly`` for a ``TextVAE``: the mean over the batches of the eval-mode loss MSE + kl_lambda * KL / B
+    (``kl_lambda`` = 1), on the one-pass caption step.  ``loader`` yields (anything, captions (B, steps, 300)) whole batches of one size."""
+    from .coco import TextVAETrainer
+    vae.eval()
+    dev = next(vae.parameters()).device
+    trainer, total, n = None, 0.0, 0
+    for _, text in loader:
+        text = text.to(dev).float().contiguous()
+        if trainer is None or trainer.engine.B != text.shape[0]:
+            trainer = TextVAETrainer(vae, text.shape[0], kl_lambda=kl_lambda)
+        total += float(trainer.evaluate(text).losses()[0].item())
+        n += 1
+    if n == 0:
+        raise ValueError("test_textonly: empty loader")
+    total /= n
+    if verbose:
+        print('====> Test set loss: {:.4f}'.format(total))
+    return total
+
+
+test_textonly.__test__ = False            # not a pytest test
 
 
 @torch.no_grad()
@@ -1240,6 +1324,9 @@ def _loglik_coco_main(args):
             raise ValueError("loglik_coco: the '<s>' vector must be %d floats (got %s %s)" % (K.N_EMBEDDING, sos.dtype, tuple(sos.shape)))
     x = x.float().div_(255.0)                                     # transforms.ToTensor()
     loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    if is_textonly_checkpoint(args.model_path):                   # a checkpoint of train_textonly: log p(y) alone
+        return _report(K.load_checkpoint_textonly(args.model_path, use_cuda=True, sos=sos, words=words), loader, ("text",), args, "Text",
+                       text_sigma=float(args.text_sigma))
     if is_imageonly_checkpoint(args.model_path):                  # a checkpoint of train_imageonly: log p(x) alone
         return _report(K.load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Text",
                        text_sigma=float(args.text_sigma))
@@ -1273,6 +1360,29 @@ def _test_imageonly_main(args):
     x = x.float().div_(255.0)
     loader = [(x[i:i + bs], None) for i in range(0, x.shape[0] - bs + 1, bs)]
     return test_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader)
+
+
+def _test_textonly_main(args):
+    """`test_textonly`: whole batches only (the plan takes a fixed batch size); a trailing partial batch is dropped."""
+    import os
+    from . import coco as K
+    from .train_coco import synthetic_coco
+    sos = words = None
+    if args.synthetic > 0:
+        _, t, sos = synthetic_coco(args.synthetic, seed=args.seed)
+    elif args.data:
+        t = torch.as_tensor(torch.load(os.path.join(args.data, "captions.pt"), weights_only=False)).float()
+        if not args.sos and not args.words:
+            sos = torch.load(os.path.join(args.data, "sos.pt"), weights_only=False)
+    else:
+        raise SystemExit("test_textonly: give --data or --synthetic N")
+    if args.sos:
+        sos = torch.load(args.sos, weights_only=False)
+    elif args.words:
+        sos, words = None, K.load_word_table(args.words)
+    bs = min(args.batch_size, t.shape[0])
+    loader = [(None, t[i:i + bs]) for i in range(0, t.shape[0] - bs + 1, bs)]
+    return test_textonly(K.load_checkpoint_textonly(args.model_path, use_cuda=True, sos=sos, words=words), loader)
 
 
 def _loglik_main(args):
@@ -1313,6 +1423,8 @@ def _main(argv=None):
         return _loglik_coco_main(args)
     if args.cmd == "test_imageonly":
         return _test_imageonly_main(args)
+    if args.cmd == "test_textonly":
+        return _test_textonly_main(args)
     if args.cmd == "sample_coco":
         return _sample_coco_main(args)
     if args.cmd == "sample_celeba":
