@@ -538,6 +538,72 @@ size_t mmvae_coco_text_step_workspace_bytes(const mmvae_coco_t*);
 int mmvae_coco_iw_score_text(mmvae_coco_t*, void* ws, size_t ws_bytes, const float* z, const float* text, const float* sos,
                              int B, int K, float* sse_y, void* stream);
 
+/* ---------------------------------------------------------------- text-only VAE baseline (MultiMNIST)
+ * TextVAE of multimnist/model.py:123-147 -- TextEncoder and TextDecoder at n_hiddens = 50 with reparametrize between them and NO product
+ * of experts -- trained by multimnist/train_textonly.py:95-113 on loss = lambda_y * NLL(recon, text) / (B * 4) + kl_lambda * KL / B.
+ * A plan of its own: the parameter table is TextVAE's state_dict (encoder.embed.weight (12,H), encoder.gru.*_l0 / *_l0_reverse,
+ * encoder.h2p.*, decoder.embed.weight, decoder.z2h.*, decoder.gru.*_l0 / *_l1, decoder.h2o.*), there is no BatchNorm (num_bn == 0,
+ * bn_floats == 0: bind still wants non-null bn_stats / nbt pointers).  n_latents 1..127; n_hiddens 50 (the reference's) or 100 (the
+ * MMVAE's width: the same kernels as mmvae_mm_text_*, bit for bit); anything else returns NULL and mmvae_last_error names 50 and 100.
+ * The kernels are the MMVAE's persistent text kernels instantiated for the hidden size; at 50 the decoder's forward is the streamed
+ * form at every latent size.  The plan/query/bind/pack functions have the same meaning as their mmvae_mm_* counterparts.
+ * ONE workspace size: mmvae_mmtext_module_workspace_bytes (== mmvae_mmtext_workspace_bytes), one pass over B rows. */
+typedef struct MMTextPlan mmvae_mmtext_t;
+mmvae_mmtext_t* mmvae_mmtext_create(int n_latents, int n_hiddens, int batch);
+void mmvae_mmtext_destroy(mmvae_mmtext_t*);
+int mmvae_mmtext_hidden(const mmvae_mmtext_t*);
+long long mmvae_mmtext_param_count(const mmvae_mmtext_t*);
+int mmvae_mmtext_num_params(const mmvae_mmtext_t*);               /* 24 */
+int mmvae_mmtext_param_info(const mmvae_mmtext_t*, int i, char* name, int* ndim, int* shape, long long* offset);
+long long mmvae_mmtext_bn_floats(const mmvae_mmtext_t*);          /* 0 */
+int mmvae_mmtext_num_bn(const mmvae_mmtext_t*);                   /* 0 */
+int mmvae_mmtext_bn_info(const mmvae_mmtext_t*, int i, char* prefix, int* channels, long long* offset);
+long long mmvae_mmtext_packed_elems(const mmvae_mmtext_t*);
+long long mmvae_mmtext_packed_vec_elems(const mmvae_mmtext_t*);
+long long mmvae_mmtext_gpk_elems(const mmvae_mmtext_t*);
+long long mmvae_mmtext_gpk_vec_elems(const mmvae_mmtext_t*);
+size_t mmvae_mmtext_desc_bytes(const mmvae_mmtext_t*, int which);
+int mmvae_mmtext_desc_copy(const mmvae_mmtext_t*, int which, void* host_out);
+size_t mmvae_mmtext_workspace_bytes(const mmvae_mmtext_t*);
+size_t mmvae_mmtext_module_workspace_bytes(const mmvae_mmtext_t*);
+int mmvae_mmtext_bind(mmvae_mmtext_t*, float* params, float* grads, float* bn_stats, long long* bn_num_batches_tracked,
+                      void* packed_bf16, float* packed_vec, float* gpk, float* gpk_vec, void* desc_dev, void* gdesc_dev);
+int mmvae_mmtext_pack_weights(mmvae_mmtext_t*, void* stream);
+int mmvae_mmtext_grad_map(mmvae_mmtext_t*, int* map, void* stream);
+/* Granular modules, with the signatures and the meaning of mmvae_mm_text_* (keep: [4][B][H] flags). */
+int mmvae_mmtext_encoder_fwd(mmvae_mmtext_t*, void* ws, size_t ws_bytes, const long long* text, float* out_mu_logvar, void* stream);
+int mmvae_mmtext_encoder_bwd(mmvae_mmtext_t*, void* ws, size_t ws_bytes, const long long* text, const float* d_out, void* stream);
+int mmvae_mmtext_decoder_fwd(mmvae_mmtext_t*, void* ws, size_t ws_bytes, const float* z, int training, const uint8_t* keep,
+                             const long long* force_tokens, float* words, long long* tokens, void* stream);
+int mmvae_mmtext_decoder_bwd(mmvae_mmtext_t*, void* ws, size_t ws_bytes, const float* z, const uint8_t* keep,
+                             const long long* force_tokens, const float* words, const long long* tokens,
+                             const float* d_words, float* dz, void* stream);
+/* One step, one enqueue, everything on the caller's stream (no side stream is used): prologue (zeroing, Philox eps / keep flags,
+ * optional pack_first), encoder forward, mmvae_latent1_fwd (mu | logvar are the encoder's halves bit for bit), decoder forward on one
+ * row group with the fused NLL (coefficient lambda_y / (B * 4)), and -- if do_backward -- the decoder's backward with its grouped weight
+ * gradients, mmvae_latent1_bwd_f32 (kl_coef = kl_lambda / B, ld = 2D), the encoder's backward, reduce and unpack (or defer_unpack).
+ * The step includes optimizer.zero_grad().  training = 0: z = mu, no dropout. */
+typedef struct {
+    void* ws; size_t ws_bytes;
+    const long long* step_counter;          /* device int64 keying the Philox streams, or NULL */
+    const long long* text;                  /* [B][4] */
+    const float* eps;                       /* [B][D] or NULL (drawn on device) */
+    const uint8_t* gru_keep;                /* [4][B][H] keep flags of the decoder's inter-layer Dropout or NULL (drawn) */
+    int gru_dropout;                        /* 0: no dropout */
+    const long long* force_tokens;          /* [B][4] or NULL: overrides the greedy feedback (test hook) */
+    float kl_lambda; float lambda_y;
+    unsigned long long seed;
+    float* sums;                            /* out [16]: [4] NLL sum, [8] KL sum, the rest 0 */
+    float* recon_text;                      /* out [B][4][12] log-probabilities or NULL */
+    float* mu; float* logvar;               /* out [B][D] or NULL */
+    long long* tokens;                      /* out [B][4] greedy tokens or NULL */
+    int defer_unpack; int pack_first;       /* as in mmvae_mm_step_io */
+} mmvae_mm_text_step_io;
+int mmvae_mmtext_step(mmvae_mmtext_t*, const mmvae_mm_text_step_io*, int training, int do_backward, void* stream);
+/* The text half of mmvae_mm_iw_score alone: the eval-mode decoder on the B*K particle rows z [B][K][n_latents] of a plan created with
+ * at least B*K rows; writes words [B*K][4][12], which feed mmvae_iw_accumulate as T = 4, V = 12. */
+int mmvae_mmtext_iw_score(mmvae_mmtext_t*, void* ws, size_t ws_bytes, const float* z, int B, int K, float* words, void* stream);
+
 /* ---------------------------------------------------------------- dataset-independent ops */
 /* ProductOfExperts.forward (multimnist/model.py:355-360) over M stacked experts of n scalars each */
 int mmvae_poe_fwd(const float* mu, const float* logvar, int M, int n, float* out_mu, float* out_logvar, void* stream);

@@ -126,6 +126,22 @@ class TextStepIO(C.Structure):
     ]
 
 
+class MMTextStepIO(C.Structure):
+    """mmvae_mm_text_step_io"""
+    _fields_ = [
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+        ("step_counter", C.c_void_p),
+        ("text", C.c_void_p), ("eps", C.c_void_p), ("gru_keep", C.c_void_p),
+        ("gru_dropout", C.c_int),
+        ("force_tokens", C.c_void_p),
+        ("kl_lambda", C.c_float), ("lambda_y", C.c_float),
+        ("seed", C.c_ulonglong),
+        ("sums", C.c_void_p), ("recon_text", C.c_void_p),
+        ("mu", C.c_void_p), ("logvar", C.c_void_p), ("tokens", C.c_void_p),
+        ("defer_unpack", C.c_int), ("pack_first", C.c_int),
+    ]
+
+
 _P, _I, _F, _LL, _SZ, _ULL, _U = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t, C.c_ulonglong, C.c_uint
 
 # name -> (restype, argtypes); restype int means "status code, raise on != 0"
@@ -277,6 +293,15 @@ for _f in ("celeba", "coco"):
 SIGNATURES["mmvae_coco_text_step"] = (_I, [_P, C.POINTER(TextStepIO), _I, _I, _P])
 SIGNATURES["mmvae_coco_text_step_workspace_bytes"] = (_SZ, [_P])
 SIGNATURES["mmvae_coco_iw_score_text"] = (_I, [_P, _P, _SZ, _P, _P, _P, _I, _I, _P, _P])
+SIGNATURES.update(_plan_api("mmtext"))
+SIGNATURES["mmvae_mmtext_create"] = (_P, [_I, _I, _I])
+SIGNATURES["mmvae_mmtext_hidden"] = (_I, [_P])
+SIGNATURES["mmvae_mmtext_step"] = (_I, [_P, C.POINTER(MMTextStepIO), _I, _I, _P])
+SIGNATURES["mmvae_mmtext_encoder_fwd"] = (_I, [_P, _P, _SZ, _P, _P, _P])
+SIGNATURES["mmvae_mmtext_encoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P])
+SIGNATURES["mmvae_mmtext_decoder_fwd"] = (_I, [_P, _P, _SZ, _P, _I, _P, _P, _P, _P, _P])
+SIGNATURES["mmvae_mmtext_decoder_bwd"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P])
+SIGNATURES["mmvae_mmtext_iw_score"] = (_I, [_P, _P, _SZ, _P, _I, _I, _P, _P])
 SIGNATURES["mmvae_latent1_bwd_f32"] = (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _I, _P])
 SIGNATURES["mmvae_latent1_scratch_floats"] = (_SZ, [_I, _I])
 SIGNATURES["mmvae_latent1_fwd"] = (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P])
@@ -324,7 +349,7 @@ SIGNATURES["mmvae_imgprep_geometry"] = (_I, [C.POINTER(_I)] * 3)
 SIGNATURES["mmvae_imgprep_layout"] = (_I, [_I, _I, _I] + [C.POINTER(_I)] * 4)
 SIGNATURES["mmvae_imgprep_coeffs"] = (_I, [_I] * 5 + [_P] * 3)
 SIGNATURES["mmvae_imgprep_scale_crop"] = (_I, [_P, _LL, _P, _P, _P, _I, _I, _P, _P, _P, _P])
-_STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
+_STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_mmtext_hidden", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
 
 _lib = None
 _inited = set()

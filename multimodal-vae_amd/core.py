@@ -157,6 +157,28 @@ class MultimnistState(PlanState):
     API = "mm"
 
 
+class MultimnistTextState(PlanState):
+    """multimnist/model.py:123-147 TextVAE: a plan of its own (parameters ``encoder.*`` / ``decoder.*``), the MMVAE's text kernels
+    instantiated for ``n_hiddens`` = 50 (the reference's TextVAE) or 100 (the MMVAE's width).  No BatchNorm."""
+    API = "mmtext"
+
+    def __init__(self, n_latents: int, device: torch.device, n_hiddens: int = 50):
+        self.n_hiddens = int(n_hiddens)
+        super().__init__(n_latents, device)
+
+    def _c(self, fn, *args):
+        if fn == "create":
+            return call("mmvae_mmtext_create", args[0], self.n_hiddens, args[1])
+        return super()._c(fn, *args)
+
+    def _bind(self, h: int) -> None:
+        # the model has no BatchNorm: bind still wants two valid pointers
+        if getattr(self, "_no_bn", None) is None:
+            self._no_bn = (torch.zeros(4, dtype=torch.float32, device=self.device), torch.zeros(1, dtype=torch.int64, device=self.device))
+        self._c("bind", h, ptr(self.params), ptr(self.grads), ptr(self._no_bn[0]), ptr(self._no_bn[1]),
+                ptr(self.packed), ptr(self.packed_vec), ptr(self.gpk), ptr(self.gpk_vec), ptr(self._desc[0]), ptr(self._desc[1]))
+
+
 class MnistState(PlanState):
     """mnist/model.py MultimodalVAE.  ``precision``: "fp32" (default: the reference's own arithmetic on fp32 MFMA) or
     "bf16" (bf16 MFMA operands like the conv models)."""
@@ -825,3 +847,68 @@ class FusedTextStep(_FusedStepBase):
 
     def capture(self, text: torch.Tensor) -> None:
         raise MMVAEError("FusedTextStep: HIP-graph capture is not offered for the text-only step")
+
+
+class FusedMMTextStep(_FusedStepBase):
+    """The step of multimnist/train_textonly.py:95-113 on the text-only plan (``MultimnistTextState``): zero_grad -> ONE pass over B
+    rows (text encoder, reparametrize, text decoder; no product of experts) -> lambda_y * NLL + kl_lambda * KL -> backward -> Adam over
+    every parameter.  ``StepOutputs`` carries the pass in slot 0 of the text terms (``parts()[1][0]``, ``parts()[2][0]``)."""
+
+    _DEFER_PACK = True          # the step's prologue refreshes the packed weights itself (pack_first)
+
+    def __init__(self, state: PlanState, batch: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 kl_lambda: float = 1e-3, lambda_y: float = 1.0, seed: int = 1234):
+        if state.API != "mmtext":
+            raise MMVAEError("FusedMMTextStep: needs a MultimnistTextState (got the '%s' family)" % state.API)
+        super().__init__(state, batch, lr, betas, eps, seed)
+        self.kl_lambda, self.lambda_y = kl_lambda, lambda_y
+        self.gru_dropout = True
+
+    def _workspace_bytes(self, state: PlanState, batch: int) -> int:
+        return state.module_workspace_bytes(batch)
+
+    def _outputs(self) -> StepOutputs:
+        return StepOutputs(self.sums, 1.0, self.B * 4, self.kl_lambda / self.B, (0.0, 0.0, 0.0), (self.lambda_y, 0.0, 0.0),
+                           (True, False, False))
+
+    def forward_backward(self, text, training=True, backward=True, eps=None, gru_keep=None, force_tokens=None, recon_text=None,
+                         mu=None, logvar=None, tokens=None, _defer_unpack=False) -> StepOutputs:
+        assert text.is_contiguous() and text.dtype == torch.int64 and text.shape == (self.B, 4)
+        st = self.state
+        io = _lib.MMTextStepIO()
+        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
+        io.step_counter = self.adam_state.data_ptr()
+        io.text = text.data_ptr()
+        for k, t in (("eps", eps), ("gru_keep", gru_keep), ("force_tokens", force_tokens), ("recon_text", recon_text), ("mu", mu),
+                     ("logvar", logvar), ("tokens", tokens)):
+            setattr(io, k, None if t is None else t.data_ptr())
+        io.gru_dropout = int(self.gru_dropout)
+        io.kl_lambda, io.lambda_y = self.kl_lambda, self.lambda_y
+        io.seed = self.seed
+        io.sums = self.sums.data_ptr()
+        io.defer_unpack = int(bool(_defer_unpack))
+        io.pack_first = int(st.pack_pending)
+        call("mmvae_mmtext_step", self.h, C.byref(io), int(training), int(backward), _stream())
+        st.pack_pending = False
+        return self._outputs()
+
+    def evaluate(self, text, **kw) -> StepOutputs:
+        """Eval-mode forward (z = mu, no dropout, nothing drawn), no backward."""
+        return self.forward_backward(text, False, False, **kw)
+
+    def __call__(self, text, **kw) -> StepOutputs:
+        """backward + optimizer.step() in one pass over the parameters: the packed-gradient Adam (see _call_packed)."""
+        st = self.state
+        if self.separate_unpack:
+            out = self.forward_backward(text, True, True, **kw)
+            self.optimizer_step()
+            return out
+        out = self.forward_backward(text, True, True, _defer_unpack=True, **kw)
+        call("mmvae_adam_step_packed", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
+             ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk),
+             ptr(st.gpk_vec), _stream())
+        self._after_update()
+        return out
+
+    def capture(self, text: torch.Tensor) -> None:
+        raise MMVAEError("FusedMMTextStep: HIP-graph capture is not offered for the text-only step")

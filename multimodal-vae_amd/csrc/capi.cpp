@@ -1,6 +1,7 @@
 // extern "C" boundary of libmmvae_hip.so (see include/mmvae_hip.h).
 #include "../../include/mmvae_hip.h"
 #include "multimnist.h"
+#include "mmtext.h"
 #include "mnist.h"
 #include "celeba.h"
 #include "coco.h"
@@ -113,6 +114,7 @@ static int pb_grad_map(PlanBase* P, int* map, hipStream_t s) {
         return guarded([&] { return pb_grad_map(BASE(p), map, S(stream)); });                                             \
     }
 static inline PlanBase* mm_b(const mmvae_mm_t* p) { return mm_base(const_cast<mmvae_mm_t*>(p)); }
+static inline PlanBase* mmtext_b(const mmvae_mmtext_t* p) { return mmtext_base(const_cast<mmvae_mmtext_t*>(p)); }
 static inline PlanBase* mnist_b(const mmvae_mnist_t* p) { return mnist_base(const_cast<mmvae_mnist_t*>(p)); }
 static inline PlanBase* celeba_b(const mmvae_celeba_t* p) { return celeba_base(const_cast<mmvae_celeba_t*>(p)); }
 static inline PlanBase* coco_b(const mmvae_coco_t* p) { return coco_base(const_cast<mmvae_coco_t*>(p)); }
@@ -188,6 +190,37 @@ double mmvae_mm_layer_flops(const mmvae_mm_t* p, const char* layer) { return mm_
 double mmvae_mm_layer_algo_flops(const mmvae_mm_t* p, const char* layer) { return mm_layer_algo_flops(p, layer); }
 double mmvae_mm_layer_algo_bytes(const mmvae_mm_t* p, const char* layer) { return mm_layer_algo_bytes(p, layer); }
 long long mmvae_mm_debug_offset(mmvae_mm_t* p, const char* name) { return mm_debug_offset(p, name); }
+
+// ---- MultiMNIST text-only VAE baseline (multimnist/model.py:123-147, multimnist/train_textonly.py)
+mmvae_mmtext_t* mmvae_mmtext_create(int n_latents, int n_hiddens, int batch) {
+    try { return mmtext_create(n_latents, n_hiddens, batch); } catch (...) { mmvae_set_error("mmtext_create failed"); return nullptr; }
+}
+void mmvae_mmtext_destroy(mmvae_mmtext_t* p) { mmtext_destroy(p); }
+int mmvae_mmtext_hidden(const mmvae_mmtext_t* p) { return mmtext_hidden(p); }
+MMVAE_PLAN_API(mmtext, mmvae_mmtext_t, mmtext_b)
+int mmvae_mmtext_step(mmvae_mmtext_t* p, const mmvae_mm_text_step_io* io, int training, int do_backward, void* stream) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_mmtext_step: null argument");
+        return mmtext_step(p, *io, training, do_backward, S(stream));
+    });
+}
+int mmvae_mmtext_encoder_fwd(mmvae_mmtext_t* p, void* ws, size_t wsb, const long long* text, float* out, void* stream) {
+    return guarded([&] { return mmtext_encoder_fwd(p, ws, wsb, text, out, S(stream)); });
+}
+int mmvae_mmtext_encoder_bwd(mmvae_mmtext_t* p, void* ws, size_t wsb, const long long* text, const float* d_out, void* stream) {
+    return guarded([&] { return mmtext_encoder_bwd(p, ws, wsb, text, d_out, S(stream)); });
+}
+int mmvae_mmtext_decoder_fwd(mmvae_mmtext_t* p, void* ws, size_t wsb, const float* z, int training, const uint8_t* keep,
+                             const long long* force_tokens, float* words, long long* tokens, void* stream) {
+    return guarded([&] { return mmtext_decoder_fwd(p, ws, wsb, z, training, keep, force_tokens, words, tokens, S(stream)); });
+}
+int mmvae_mmtext_decoder_bwd(mmvae_mmtext_t* p, void* ws, size_t wsb, const float* z, const uint8_t* keep, const long long* force_tokens,
+                             const float* words, const long long* tokens, const float* d_words, float* dz, void* stream) {
+    return guarded([&] { return mmtext_decoder_bwd(p, ws, wsb, z, keep, force_tokens, words, tokens, d_words, dz, S(stream)); });
+}
+int mmvae_mmtext_iw_score(mmvae_mmtext_t* p, void* ws, size_t wsb, const float* z, int B, int K, float* words, void* stream) {
+    return guarded([&] { return mmtext_iw_score(p, ws, wsb, z, B, K, words, S(stream)); });
+}
 
 // ---- MNIST (mnist/model.py, mnist/train.py)
 mmvae_mnist_t* mmvae_mnist_create(int n_latents, int batch) {

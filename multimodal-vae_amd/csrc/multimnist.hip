@@ -6,6 +6,7 @@
 #include "mlp_tail.h"
 #include "plan_base.h"
 #include "thin.h"
+#include "text_plan.h"
 #include <cstring>
 
 namespace {
@@ -18,8 +19,10 @@ struct MMPlan : PlanBase {
     ConvL conv[4], convT[4];
     LinL fc[3], up;
     BnL bn[6];
-    // text packs
-    struct GruIdx { int wih, whh, wihT, whhT, g_wih, g_whh; long long bih, bhh; } te_f, te_r, td0, td1;
+    // text packs (text_plan.h)
+    int H = TXT_H;
+    const char *te_name = "text_encoder", *td_name = "text_decoder";
+    TextGruIdx te_f, te_r, td0, td1;
     const float* step_image = nullptr;      // the image batch of the running fused step (conv1's weight gradient rebuilds its patches)
     hipEvent_t ev_dz = nullptr;             // fused step: completion of the text decoder's backward kernel (what the main chain joins on)
     hipEvent_t ev_txtgrads = nullptr;       // fused step: every gradient of text_decoder.* is complete (recorded on the second-modality stream)
@@ -56,10 +59,6 @@ namespace {
 void build_params(MMPlan& P) {
     const int D = P.D;
     auto bn = [&](const std::string& n, int c) { add_param(P, n + ".weight", {c}); add_param(P, n + ".bias", {c}); };
-    auto gru = [&](const std::string& n, int inp, const char* sfx) {
-        add_param(P, n + ".weight_ih_" + sfx, {300, inp}); add_param(P, n + ".weight_hh_" + sfx, {300, 100});
-        add_param(P, n + ".bias_ih_" + sfx, {300}); add_param(P, n + ".bias_hh_" + sfx, {300});
-    };
     add_param(P, "image_encoder.features.0.weight", {32, 1, 4, 4});
     add_param(P, "image_encoder.features.2.weight", {64, 32, 4, 4}); bn("image_encoder.features.3", 64);
     add_param(P, "image_encoder.features.5.weight", {128, 64, 4, 4}); bn("image_encoder.features.6", 128);
@@ -72,18 +71,13 @@ void build_params(MMPlan& P) {
     add_param(P, "image_decoder.hallucinate.3.weight", {128, 64, 4, 4}); bn("image_decoder.hallucinate.4", 64);
     add_param(P, "image_decoder.hallucinate.6.weight", {64, 32, 5, 5}); bn("image_decoder.hallucinate.7", 32);
     add_param(P, "image_decoder.hallucinate.9.weight", {32, 1, 4, 4});
-    add_param(P, "text_encoder.embed.weight", {12, 100});
-    gru("text_encoder.gru", 100, "l0"); gru("text_encoder.gru", 100, "l0_reverse");
-    add_param(P, "text_encoder.h2p.weight", {2 * D, 100}); add_param(P, "text_encoder.h2p.bias", {2 * D});
-    add_param(P, "text_decoder.embed.weight", {12, 100});
-    add_param(P, "text_decoder.z2h.weight", {100, D}); add_param(P, "text_decoder.z2h.bias", {100});
-    gru("text_decoder.gru", 100 + D, "l0"); gru("text_decoder.gru", 100, "l1");
-    add_param(P, "text_decoder.h2o.weight", {12, 100 + D}); add_param(P, "text_decoder.h2o.bias", {12});
+    text_add_encoder_params(P);
+    text_add_decoder_params(P);
 }
 
 void build_plan(MMPlan& P) {
     const int D = P.D;
-    P.ldz = round_up(D + 1, 8); P.kz = round_up(D, 32); P.kx = round_up(100 + D, 32);
+    P.ldz = round_up(D + 1, 8); P.kz = round_up(D, 32); P.kx = txt_kx(P.H, D);
     P.lde = round_up(2 * D, 8);
     build_params(P);
     // BatchNorm tables (state_dict order)
@@ -158,39 +152,7 @@ void build_plan(MMPlan& P) {
         t.TW = 4; t.C = 256; t.s_ty = 0; t.s_tx = D; t.s_c = 4 * D;
         f.pk_dgrad = P.pk.add(t);
     }
-    // ---- text packs (row-tile kernels): [round16(N)][round32(K)] bf16, plus transposed copies for backward
-    auto rt = [&](long long w, int N, int K, bool transpose) {       // fragment-major: text.hip rowtile_gemm
-        PackDesc d = transpose ? pack_dense(w, K, N, round_up(K, 16), round_up(N, 32), 1, K) : pack_dense(w, N, K, round_up(N, 16), round_up(K, 32), K, 1);
-        d.frag = 1;
-        return P.pk.add(d);
-    };
-    auto gw = [&](long long w, int N, int K, int Kc) {   // wgrad target: [round64(N)][round64(Kc)] with K valid columns
-        return P.gk.add(pack_dense(w, N, K, round_up(N, 64), round_up(Kc, 64), K, 1));
-    };
-    auto grui = [&](MMPlan::GruIdx& g, const std::string& n, const char* sfx, int inp, int inp_k, bool need_hh) {
-        const long long wih = off(P, n + ".weight_ih_" + sfx), whh = off(P, n + ".weight_hh_" + sfx);
-        g.bih = off(P, n + ".bias_ih_" + sfx); g.bhh = off(P, n + ".bias_hh_" + sfx);
-        g.wih = rt(wih, 300, inp, false); g.wihT = rt(wih, 300, inp, true);
-        g.whh = rt(whh, 300, 100, false); g.whhT = rt(whh, 300, 100, true);
-        g.g_wih = gw(wih, 300, inp, inp_k);
-        g.g_whh = need_hh ? gw(whh, 300, 100, TXT_HP) : -1;
-    };
-    grui(P.te_f, "text_encoder.gru", "l0", 100, TXT_HP, true);
-    grui(P.te_r, "text_encoder.gru", "l0_reverse", 100, TXT_HP, false);
-    {
-        const long long w = off(P, "text_encoder.h2p.weight");
-        P.te_h2p = rt(w, 2 * D, 100, false); P.te_h2pT = rt(w, 2 * D, 100, true); P.g_te_h2p = gw(w, 2 * D, 100, TXT_HP);
-    }
-    {
-        const long long w = off(P, "text_decoder.z2h.weight");
-        P.td_z2h = rt(w, 100, D, false); P.td_z2hT = rt(w, 100, D, true); P.g_td_z2h = gw(w, 100, D, P.kz);
-    }
-    grui(P.td0, "text_decoder.gru", "l0", 100 + D, P.kx, true);
-    grui(P.td1, "text_decoder.gru", "l1", 100, TXT_HP, true);
-    {
-        const long long w = off(P, "text_decoder.h2o.weight");
-        P.td_h2o = rt(w, 12, 100 + D, false); P.td_h2oT = rt(w, 12, 100 + D, true); P.g_td_h2o = gw(w, 12, 100 + D, P.kx);
-    }
+    text_build_packs(P);       // the row-tile kernels' packs (text_plan.h)
     // Stage of the fused step that refreshes each bf16 copy after an optimizer step (mm_step_body; PackDesc::part of the WEIGHT table):
     //   0  the prologue on the main stream: what the image encoder's FORWARD reads (it starts right behind the prologue)
     //   1  the second-modality stream, in front of the text encoder: every text_encoder.* / text_decoder.* copy
@@ -245,29 +207,19 @@ void carve(MMPlan& P, Workspace& ws) {
     w.au = ws.take<bf16>(B3 * 1024); w.aq1 = ws.take<bf16>(B3 * 36 * 128); w.aq2 = ws.take<bf16>(B3 * 144 * 64);
     w.aq3 = ws.take<bf16>(B3 * 625 * 32);
     w.encout = ws.take<float>(B2 * 2 * D);
-    w.m1 = ws.take<uint8_t>(B2 * 400); w.m2 = ws.take<uint8_t>(B2 * 200); w.gkeep = ws.take<uint8_t>(4 * B3 * 100);
-    w.txtout = ws.take<float>(B * 2 * D);
-    w.te_gates_f = ws.take<float>(4 * 5 * B * 100); w.te_gates_r = ws.take<float>(5 * B * 100);
-    w.te_x = ws.take<bf16>(4 * B * 128); w.te_hprev = ws.take<bf16>(4 * B * 128); w.te_hsum = ws.take<bf16>(B * 128);
+    w.m1 = ws.take<uint8_t>(B2 * 400); w.m2 = ws.take<uint8_t>(B2 * 200); w.gkeep = ws.take<uint8_t>(4 * B3 * P.H);
+    carve_text_enc(w, ws, B, D, P.H);
     w.eps = ws.take<float>(B3 * D); w.mu = ws.take<float>(B3 * D); w.logvar = ws.take<float>(B3 * D);
     w.z_f32 = ws.take<float>(B3 * D); w.z_bf = ws.take<bf16>(B3 * P.ldz);
     w.u = ws.take<bf16>(B3 * 1024); w.q1 = ws.take<bf16>(B3 * 36 * 128); w.q2 = ws.take<bf16>(B3 * 144 * 64);
     w.q3 = ws.take<bf16>(B3 * 625 * 32);
     w.logits = ws.take<float>(B3 * NPIX); w.recon = ws.take<float>(B3 * NPIX); w.dlogit = ws.take<float>(B3 * NPIX);
-    w.words = ws.take<float>(B3 * 48); w.dwords = ws.take<float>(B3 * 48); w.tokens = ws.take<long long>(B3 * 4);
-    w.td_gates = ws.take<float>(4 * 2 * 5 * B3 * 100);
-    w.td_x0 = ws.take<bf16>(4 * B3 * P.kx); w.td_hz = ws.take<bf16>(4 * B3 * P.kx);
-    w.td_h0p = ws.take<bf16>(4 * B3 * 128); w.td_mid = ws.take<bf16>(4 * B3 * 128); w.td_h1p = ws.take<bf16>(4 * B3 * 128);
-    w.td_zbf = ws.take<bf16>(B3 * P.kz);
-    w.dgi0 = ws.take<bf16>(4 * B3 * 304); w.dgh0 = ws.take<bf16>(4 * B3 * 304);
-    w.dgi1 = ws.take<bf16>(4 * B3 * 304); w.dgh1 = ws.take<bf16>(4 * B3 * 304);
-    w.dlogit_bf = ws.take<bf16>(4 * B3 * 16); w.dhinit = ws.take<bf16>(B3 * 112);
+    carve_text_dec(w, ws, B3, P.H, P.kx, P.kz);
     w.patches4 = ws.take<bf16>(B3 * 625 * 16);
     w.d3 = ws.take<bf16>(B3 * 625 * 32); w.d2 = ws.take<bf16>(B3 * 144 * 64); w.d1 = ws.take<bf16>(B3 * 36 * 128);
     w.du = ws.take<bf16>(B3 * 1024);
-    w.d_encout = ws.take<bf16>(B2 * P.lde); w.d_txtout = ws.take<float>(B * 2 * D);
-    w.te_dout_bf = ws.take<bf16>(B * round_up(2 * (int)D, 8));
-    w.te_dgi_f = ws.take<bf16>(4 * B * 304); w.te_dgh_f = ws.take<bf16>(4 * B * 304); w.te_dgi_r = ws.take<bf16>(B * 304);
+    w.d_encout = ws.take<bf16>(B2 * P.lde);
+    carve_text_enc_bwd(w, ws, B, D, P.H);
     w.dy2 = ws.take<bf16>(B2 * 200); w.dy1 = ws.take<bf16>(B2 * 400);
     w.db4 = ws.take<bf16>(B2 * 1024); w.dr4 = ws.take<bf16>(B * 1024);
     w.d3e = ws.take<bf16>(B * 36 * 128); w.d2e = ws.take<bf16>(B * 144 * 64); w.d1e = ws.take<bf16>(B * 625 * 32);
@@ -738,85 +690,13 @@ int dec_bwd(MMPlan& P, const float* dlogit, int groups, float* dz, hipStream_t s
     return MMVAE_OK;
 }
 
-// ================================================================== text modules
-GruPacked gru_of(const MMPlan& P, const MMPlan::GruIdx& g) {
-    GruPacked r{};
-    r.wih = P.buf.packed + P.pk.d[g.wih].dst_off; r.kih = P.pk.d[g.wih].Kpad;
-    r.whh = P.buf.packed + P.pk.d[g.whh].dst_off;
-    r.wihT = P.buf.packed + P.pk.d[g.wihT].dst_off; r.nih = P.pk.d[g.wihT].Npad;
-    r.whhT = P.buf.packed + P.pk.d[g.whhT].dst_off;
-    r.bih = P.buf.params + g.bih; r.bhh = P.buf.params + g.bhh;
-    return r;
-}
-TextEncArgs te_args(MMPlan& P, const long long* text, float* out, bool save) {
-    MMPlan::W& w = P.w;
-    TextEncArgs a{};
-    a.B = P.B; a.D = P.D; a.tokens = text; a.embed = P.buf.params + off(P, "text_encoder.embed.weight");
-    a.fwd = gru_of(P, P.te_f); a.rev = gru_of(P, P.te_r);
-    a.h2p = P.buf.packed + P.pk.d[P.te_h2p].dst_off; a.nh2p = P.pk.d[P.te_h2p].Npad;
-    a.h2pT = P.buf.packed + P.pk.d[P.te_h2pT].dst_off;
-    a.h2p_bias = P.buf.params + off(P, "text_encoder.h2p.bias");
-    a.out = out;
-    if (save) { a.gates_f = w.te_gates_f; a.gates_r = w.te_gates_r; a.x_bf = w.te_x; a.hprev_bf = w.te_hprev; a.hsum_bf = w.te_hsum; }
-    return a;
-}
-int txt_enc_bwd(MMPlan& P, const long long* text, const float* d_out, hipStream_t s) {
-    MMPlan::W& w = P.w;
-    const int B = P.B, D2 = 2 * P.D;
-    TextEncBwdArgs a{};
-    a.f = te_args(P, text, nullptr, true);
-    a.d_out = d_out; a.d_out_bf = w.te_dout_bf;
-    a.dgi_f = w.te_dgi_f; a.dgh_f = w.te_dgh_f; a.dgi_r = w.te_dgi_r;
-    float* G = P.buf.grads;
-    a.g_embed = G + off(P, "text_encoder.embed.weight");
-    a.g_bih_f = G + P.te_f.bih; a.g_bhh_f = G + P.te_f.bhh; a.g_bih_r = G + P.te_r.bih; a.g_bhh_r = G + P.te_r.bhh;
-    a.g_h2p_bias = G + off(P, "text_encoder.h2p.bias");
-    MMVAE_TRY(launch_text_encoder_bwd(a, s));
-    // the four weight gradients of the text encoder share ONE grouped launch
-    WgradParams list[4];
-    int nl = 0;
-    auto wg = [&](int gidx, const bf16* Pm, int N, int ldp, const bf16* Gm, int C, int rows) {
-        GatherPlan pl = dense_plan(rows, C, C, N);
-        WgradParams g = wgrad_of(P, pl, &gidx, 1, rows);
-        g.c.A = Gm; g.P = Pm; g.ldp = ldp;
-        list[nl++] = g;
-    };
-    wg(P.te_f.g_wih, w.te_dgi_f, 300, 304, w.te_x, TXT_HP, 4 * B);
-    wg(P.te_f.g_whh, w.te_dgh_f, 300, 304, w.te_hprev, TXT_HP, 4 * B);
-    wg(P.te_r.g_wih, w.te_dgi_r, 300, 304, w.te_x + (size_t)3 * B * TXT_HP, TXT_HP, B);
-    wg(P.g_te_h2p, w.te_dout_bf, D2, round_up(D2, 8), w.te_hsum, TXT_HP, B);
-    MMVAE_TRY(launch_wgrad_group(list, nl, s, &P.slab));
-    return launch_wgrad_reduce(&P.slab, s, true);
-}
-TextDecArgs td_args(MMPlan& P, const float* z, int groups, bool save) {
-    MMPlan::W& w = P.w;
-    TextDecArgs a{};
-    a.R = groups * P.B; a.D = P.D; a.rows_per_pass = P.B; a.z = z;
-    a.embed = P.buf.params + off(P, "text_decoder.embed.weight");
-    a.z2h = P.buf.packed + P.pk.d[P.td_z2h].dst_off; a.kz = P.kz;
-    a.z2hT = P.buf.packed + P.pk.d[P.td_z2hT].dst_off;
-    a.z2h_bias = P.buf.params + off(P, "text_decoder.z2h.bias");
-    a.l0 = gru_of(P, P.td0); a.l1 = gru_of(P, P.td1);
-    a.h2o = P.buf.packed + P.pk.d[P.td_h2o].dst_off; a.kx = P.kx;
-    a.h2oT = P.buf.packed + P.pk.d[P.td_h2oT].dst_off;
-    a.h2o_bias = P.buf.params + off(P, "text_decoder.h2o.bias");
-    a.words = w.words; a.tokens_out = w.tokens;
-    if (save) {
-        a.gates = w.td_gates; a.x0_bf = w.td_x0; a.h0p_bf = w.td_h0p; a.mid_bf = w.td_mid; a.h1p_bf = w.td_h1p;
-        a.hz_bf = w.td_hz; a.z_bf = w.td_zbf;
-    }
-    return a;
-}
+// ================================================================== text modules (argument builders and grouped weight gradients: text_plan.h)
+TextEncArgs te_args(MMPlan& P, const long long* text, float* out, bool save) { return text_enc_args(P, text, out, save); }
+int txt_enc_bwd(MMPlan& P, const long long* text, const float* d_out, hipStream_t s) { return text_enc_bwd(P, text, d_out, s); }
+TextDecArgs td_args(MMPlan& P, const float* z, int groups, bool save) { return text_dec_args(P, z, groups, save); }
 int txt_dec_bwd(MMPlan& P, const TextDecArgs& f, const float* dwords, float* dz, hipStream_t s) {
-    MMPlan::W& w = P.w;
-    const int R = f.R, XI = 100 + P.D;
-    TextDecBwdArgs a{};
-    a.f = f; a.dwords = dwords; a.R_active = R; a.dz = dz;
-    a.dgi0 = w.dgi0; a.dgh0 = w.dgh0; a.dgi1 = w.dgi1; a.dgh1 = w.dgh1; a.dlogit_bf = w.dlogit_bf; a.dhinit_bf = w.dhinit;
-    float* G = P.buf.grads;
-    a.g_embed = G + off(P, "text_decoder.embed.weight");
-    a.g_b[0] = G + P.td0.bih; a.g_b[1] = G + P.td0.bhh; a.g_b[2] = G + P.td1.bih; a.g_b[3] = G + P.td1.bhh;
-    a.g_h2o_bias = G + off(P, "text_decoder.h2o.bias"); a.g_z2h_bias = G + off(P, "text_decoder.z2h.bias");
+    const int R = f.R;
+    const TextDecBwdArgs a = text_dec_bwd_args(P, f, dwords, dz);
     // In the fused step the main chain needs dz (and the NLL sums) of THIS kernel, not the weight gradients enqueued behind it on the
     // same stream: the join is the kernel's own completion event (a join on "everything enqueued on T so far" made the main chain wait
     // for ~45 us of weight-gradient launches; measured on the traces of round 4: the second-modality stream was co-critical)
@@ -831,24 +711,7 @@ int txt_dec_bwd(MMPlan& P, const TextDecArgs& f, const float* dwords, float* dz,
         mmvae_set_error("text decoder event failed: %s", hipGetErrorString(hipGetLastError()));
         return MMVAE_EHIP;
     }
-    // the six weight gradients of the text decoder: one grouped launch (128x128 tile class) + the thin h2o one
-    WgradParams list[6];
-    int nl = 0;
-    auto wg = [&](int gidx, const bf16* Pm, int N, int ldp, const bf16* Gm, int C, int rows) {
-        GatherPlan pl = dense_plan(rows, C, C, N);
-        WgradParams g = wgrad_of(P, pl, &gidx, 1, rows);
-        g.c.A = Gm; g.P = Pm; g.ldp = ldp;
-        list[nl++] = g;
-    };
-    (void)XI;
-    wg(P.td0.g_wih, w.dgi0, 300, 304, w.td_x0, P.kx, 4 * R);
-    wg(P.td0.g_whh, w.dgh0, 300, 304, w.td_h0p, TXT_HP, 4 * R);
-    wg(P.td1.g_wih, w.dgi1, 300, 304, w.td_mid, TXT_HP, 4 * R);
-    wg(P.td1.g_whh, w.dgh1, 300, 304, w.td_h1p, TXT_HP, 4 * R);
-    wg(P.g_td_z2h, w.dhinit, 100, 112, w.td_zbf, P.kz, R);
-    wg(P.g_td_h2o, w.dlogit_bf, 12, 16, w.td_hz, P.kx, 4 * R);
-    MMVAE_TRY(launch_wgrad_group(list, nl, s, &P.slab));
-    MMVAE_TRY(launch_wgrad_reduce(&P.slab, s, true));
+    MMVAE_TRY(text_dec_wgrads(P, R, s));
     // every gradient of text_decoder.* is complete on this stream here: the early optimizer part waits for this event
     P.ev_txtgrads = nullptr;
     if (own_ev) {
@@ -931,7 +794,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B3 * D; eps = w.eps; }
     if (training && io.enc_dropout && !m1) { sb.mask[0] = w.m1; sb.n_mask[0] = (long long)2 * B * 400; m1 = w.m1; }
     if (training && io.enc_dropout && !m2) { sb.mask[1] = w.m2; sb.n_mask[1] = (long long)2 * B * 200; m2 = w.m2; }
-    if (training && io.gru_dropout && !gk) { sb.mask[2] = w.gkeep; sb.n_mask[2] = (long long)4 * B3 * 100; gk = w.gkeep; }
+    if (training && io.gru_dropout && !gk) { sb.mask[2] = w.gkeep; sb.n_mask[2] = (long long)4 * B3 * P.H; gk = w.gkeep; }
     const int skipb = mmvae_knob("dbg_begin_skip", 0);              // measurement aid (results are garbage): 1 no pack, 2 no random draws, 4 no workspace zeroing
     if (skipb & 2) { sb.eps = nullptr; sb.mask[0] = sb.mask[1] = sb.mask[2] = nullptr; }
     if (skipb & 4) sb.zero_ptr[0] = nullptr;

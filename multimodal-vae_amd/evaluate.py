@@ -287,6 +287,14 @@ def _coco_text_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream
     torch.mul(sse[:rows], scale, out=words[:rows])
 
 
+def _mmtext_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
+    """The scoring call of a MultiMNIST TextVAE: mmvae_mmtext_iw_score (the text decoder alone, words [rows][4][12]); log p(x|z) of the
+    image that is not there is 0."""
+    from ._lib import ptr
+    _iw_call("mmvae_mmtext_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), nr, nk, ptr(words), stream)
+    lx[:rows].zero_()
+
+
 def _image_score(api):
     """The scoring call of an ImageVAE: mmvae_<family>_iw_score_image (decoder body + scoring tail, no second decoder); the words
     of its one dummy text position are 0."""
@@ -333,6 +341,9 @@ _FAMILIES = {
                           lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), image_only=True),
     "coco_text": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_text_score,
                          lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), float_text=True, text_only=True),
+    # the MultiMNIST TextVAE: the text decoder alone on a plan of its own; its "image" is one dummy pixel
+    "multimnist_text": _Family("multimnist", 4, 12, (1,), IW_ROWS, _mmtext_score,
+                               lambda st, rows: st.module_workspace_bytes(rows), text_only=True),
 }
 IMAGE_ONLY_NAN_COLUMNS = (1, 2, 4, 5, 7)      # of mmvae_iw_finalize's (B, 8): everything that involves y
 TEXT_ONLY_NAN_COLUMNS = (0, 2, 3, 5, 6)       # ... everything that involves x
@@ -345,8 +356,11 @@ def _family(model):
     from .celeba import ImageVAE as CelebaImageVAE
     from .coco import ImageVAE as CocoImageVAE
     from .coco import TextVAE as CocoTextVAE
+    from .multimnist import TextVAE as MultimnistTextVAE
     if isinstance(model, CocoTextVAE):
         return _FAMILIES["coco_text"]
+    if isinstance(model, MultimnistTextVAE):
+        return _FAMILIES["multimnist_text"]
     if isinstance(model, (CelebaImageVAE, CocoImageVAE)):
         return _FAMILIES["celeba_image" if isinstance(model, CelebaImageVAE) else "coco_image"]
     return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else
@@ -594,6 +608,21 @@ def sample(vae, n_samples=64, image=None, text=None, use_cuda=True):
     image_recon = vae.decode_image(z.contiguous()).cpu().view(n_samples, 1, 50, 50)
     text_recon = torch.max(vae.decode_text(z.contiguous()).cpu(), dim=2)[1]
     return image_recon, text_recon
+
+
+@torch.no_grad()
+def sample_textonly(vae, n_samples=64, text=None):
+    """``sample`` for a multimnist ``TextVAE``: token samples (n,4) LongTensor, from the prior or from q(z|y) of ``text`` (1,4)."""
+    vae.eval()
+    dev = next(vae.parameters()).device
+    if text is None:
+        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
+    else:
+        mu, logvar = vae.encode(text.to(dev))
+        std = logvar.mul(0.5).exp()
+    z = torch.randn(n_samples, vae.n_latents).to(dev)
+    z = z * std.expand_as(z) + mu.expand_as(z)
+    return torch.max(vae.decode(z.contiguous()).cpu(), dim=2)[1]
 
 
 @torch.no_grad()
@@ -892,6 +921,8 @@ def _parser():
     pt.add_argument('--seed', type=int, default=0)
     px = sub.add_parser("test_textonly", help="eval-mode loss (kl_lambda = 1) of a train_textonly checkpoint, as test_imageonly")
     px.add_argument('model_path', type=str)
+    px.add_argument('--dataset', choices=('coco', 'multimnist'), default='coco',
+                    help='multimnist: a checkpoint of train_textonly_multimnist; --data is then the folder of the MultiMNIST test file')
     px.add_argument('--data', type=str, default='', help='DIR with captions.pt (and sos.pt), as train_coco reads')
     px.add_argument('--synthetic', type=int, default=0, metavar='N')
     px.add_argument('--batch_size', type=int, default=64, metavar='N')
@@ -1201,11 +1232,15 @@ def test_textonly(vae, loader, kl_lambda=1.0, verbose=True):
     """The counterpart of ``test_imageonly`` for a ``TextVAE``: the mean over the batches of the eval-mode loss MSE + kl_lambda * KL / B
     (``kl_lambda`` = 1), on the one-pass caption step.  ``loader`` yields (anything, captions (B, steps, 300)) whole batches of one size."""
     from .coco import TextVAETrainer
+    from .multimnist import TextVAE as MultimnistTextVAE
+    mm = isinstance(vae, MultimnistTextVAE)       # (B, 4) int64 labels, lambda_y * NLL + kl_lambda * KL / B
+    if mm:
+        from .multimnist import TextVAETrainer
     vae.eval()
     dev = next(vae.parameters()).device
     trainer, total, n = None, 0.0, 0
     for _, text in loader:
-        text = text.to(dev).float().contiguous()
+        text = text.to(dev).long().contiguous() if mm else text.to(dev).float().contiguous()
         if trainer is None or trainer.engine.B != text.shape[0]:
             trainer = TextVAETrainer(vae, text.shape[0], kl_lambda=kl_lambda)
         total += float(trainer.evaluate(text).losses()[0].item())
@@ -1365,6 +1400,20 @@ def _test_imageonly_main(args):
 def _test_textonly_main(args):
     """`test_textonly`: whole batches only (the plan takes a fixed batch size); a trailing partial batch is dropped."""
     import os
+    if args.dataset == "multimnist":
+        from . import data as D
+        from .multimnist import load_checkpoint_textonly
+        from .utils import charlist_tensor
+        if args.synthetic > 0:
+            _, labels = D.synthetic_multimnist(args.synthetic, seed=args.seed)
+            t = torch.stack([charlist_tensor(l) for l in labels])
+        elif args.data:
+            _, t = D.load_multimnist(args.data, train=False)
+        else:
+            raise SystemExit("test_textonly: give --data or --synthetic N")
+        bs = min(args.batch_size, t.shape[0])
+        loader = [(None, t[i:i + bs]) for i in range(0, t.shape[0] - bs + 1, bs)]
+        return test_textonly(load_checkpoint_textonly(args.model_path, use_cuda=True), loader)
     from . import coco as K
     from .train_coco import synthetic_coco
     sos = words = None
@@ -1405,6 +1454,9 @@ def _loglik_main(args):
             x, t = D.load_multimnist(args.data, train=False)
         x = x.float().div_(255.0).view(-1, 1, 50, 50)             # transforms.ToTensor()
     loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    if args.dataset == "multimnist" and is_textonly_checkpoint(args.model_path):      # a checkpoint of train_textonly_multimnist: log p(y) alone
+        from .multimnist import load_checkpoint_textonly
+        return _report(load_checkpoint_textonly(args.model_path, use_cuda=True), loader, ("text",), args, "Text")
     vae = load_checkpoint(args.model_path, use_cuda=True)
     posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
     return _report(vae, loader, posts, args, "Text")
@@ -1439,6 +1491,17 @@ def _main(argv=None):
         return _sample_pixelcnn_main(args)
     if args.cmd == "nll_pixelcnn":
         return _nll_pixelcnn_main(args)
+    if is_textonly_checkpoint(args.model_path):       # a checkpoint of train_textonly_multimnist: text samples only
+        from .multimnist import load_checkpoint_textonly
+        vae = load_checkpoint_textonly(args.model_path, use_cuda=True)
+        if args.condition_on_image:
+            raise SystemExit("sample: a text-only checkpoint has no image encoder")
+        text_recon = sample_textonly(vae, args.n_samples, None if not args.condition_on_text else char_tensor(args.condition_on_text).unsqueeze(0))
+        os.makedirs(args.out, exist_ok=True)
+        with open(os.path.join(args.out, 'sample_text.txt'), 'w') as fp:
+            for i in range(text_recon.size(0)):
+                fp.write('%s\n' % tensor_to_string(text_recon[i]))
+        return None
     vae = load_checkpoint(args.model_path, use_cuda=True)
     image = text = None
     if args.condition_on_image:

@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import MMVAEError, call, ptr
 from ._ops import stream as _stream
-from .core import FusedELBOStep, MultimnistState, StepOutputs
+from .core import FusedELBOStep, FusedMMTextStep, MultimnistState, MultimnistTextState, StepOutputs
 
 # multimnist/utils.py:14-19
 max_length = 4
@@ -297,11 +297,13 @@ class ImageDecoder(nn.Module):
 class TextEncoder(nn.Module):
     """multimnist/model.py:219-247 (bidirectional=True is the only configuration MultimodalVAE uses)."""
 
-    def __init__(self, n_latents, n_characters, n_hiddens=50, bidirectional=True):
+    def __init__(self, n_latents, n_characters, n_hiddens=50, bidirectional=True, _textvae=False):
         super().__init__()
-        if n_hiddens != 100 or not bidirectional or n_characters != 12:
+        # (_textvae: built by TextVAE, whose plan runs the kernels' hidden-size-50 instantiation)
+        if n_hiddens != (50 if _textvae else 100) or not bidirectional or n_characters != 12:
             raise MMVAEError("the HIP TextEncoder implements the configuration used by MultimodalVAE: "
                              "n_characters=12, n_hiddens=100, bidirectional=True")
+        self._api, self._pfx = ("mmtext", "encoder.") if _textvae else ("mm", "text_encoder.")
         self.embed = nn.Embedding(n_characters, n_hiddens)
         self.gru = nn.GRU(n_hiddens, n_hiddens, 1, dropout=0.0, bidirectional=bidirectional)   # dropout is a no-op for 1 layer
         self.h2p = nn.Linear(n_hiddens, n_latents * 2)
@@ -312,26 +314,28 @@ class TextEncoder(nn.Module):
 
     def forward(self, x):
         n = self.n_latents
-        core = _core_of(self, "text_encoder.")
+        core = _core_of(self, self._pfx)
         st = core.sync(x.device)
         x = x.contiguous().long()
         B = x.shape[0]
         assert x.shape == (B, max_length)
         h = st.plan(B)
         wsb = st.module_workspace_bytes(B)
-        names = ["text_encoder." + k for k, _ in self.named_parameters()]
+        names = [self._pfx + k for k, _ in self.named_parameters()]
+        f_fwd, f_bwd = ("mmvae_mm_text_encoder_fwd", "mmvae_mm_text_encoder_bwd") if self._api == "mm" else \
+                       ("mmvae_mmtext_encoder_fwd", "mmvae_mmtext_encoder_bwd")
         plist = [p for _, p in self.named_parameters()]
 
         def fwd(ctx):
             ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
             out = torch.empty(B, 2 * n, dtype=torch.float32, device=x.device)
-            call("mmvae_mm_text_encoder_fwd", h, ptr(ws), wsb, ptr(x), ptr(out), _stream())
+            call(f_fwd, h, ptr(ws), wsb, ptr(x), ptr(out), _stream())
             ctx.ws = ws
             return out
 
         def bwd(ctx, d_out):
             st.grads.zero_()
-            call("mmvae_mm_text_encoder_bwd", h, ptr(ctx.ws), wsb, ptr(x), ptr(d_out.contiguous()), _stream())
+            call(f_bwd, h, ptr(ctx.ws), wsb, ptr(x), ptr(d_out.contiguous()), _stream())
             return core.grads_for(names)
 
         out = _ModuleFn.apply(fwd, bwd, 0, *plist)
@@ -341,11 +345,13 @@ class TextEncoder(nn.Module):
 class TextDecoder(nn.Module):
     """multimnist/model.py:250-307: 2-layer GRU, 4 greedy steps, log-softmax outputs (B, 4, 12)."""
 
-    def __init__(self, n_latents, n_characters, n_hiddens=50, use_cuda=False):
+    def __init__(self, n_latents, n_characters, n_hiddens=50, use_cuda=False, _textvae=False):
         super().__init__()
-        if n_hiddens != 100 or n_characters != 12:
+        if n_hiddens != (50 if _textvae else 100) or n_characters != 12:
             raise MMVAEError("the HIP TextDecoder implements the configuration used by MultimodalVAE: "
                              "n_characters=12, n_hiddens=100")
+        self._api, self._pfx = ("mmtext", "decoder.") if _textvae else ("mm", "text_decoder.")
+        self.n_hiddens = n_hiddens
         self.embed = nn.Embedding(n_characters, n_hiddens)
         self.z2h = nn.Linear(n_latents, n_hiddens)
         self.gru = nn.GRU(n_hiddens + n_latents, n_hiddens, 2, dropout=0.1)
@@ -357,7 +363,7 @@ class TextDecoder(nn.Module):
         self.last_tokens = None
 
     def forward(self, z, keep: Optional[torch.Tensor] = None, force_tokens: Optional[torch.Tensor] = None):
-        core = _core_of(self, "text_decoder.")
+        core = _core_of(self, self._pfx)
         st = core.sync(z.device)
         z = z.contiguous().float()
         B = z.shape[0]
@@ -369,21 +375,23 @@ class TextDecoder(nn.Module):
             if abs(pdrop - DROP_P) > 1e-9:
                 raise MMVAEError("the HIP text decoder supports GRU dropout in {0, 0.1} (reference: 0.1)")
             if keep is None:
-                keep = torch.empty(max_length, B, 100, dtype=torch.uint8, device=z.device)
+                keep = torch.empty(max_length, B, self.n_hiddens, dtype=torch.uint8, device=z.device)
                 call("mmvae_keep_mask", ptr(keep), keep.numel(), DROP_P, _seed_from_torch(), None, 4, _stream())
             else:
                 keep = keep.to(torch.uint8).contiguous()
         else:
             keep = None
         ft = None if force_tokens is None else force_tokens.contiguous().long()
-        names = ["text_decoder." + k for k, _ in self.named_parameters()]
+        names = [self._pfx + k for k, _ in self.named_parameters()]
+        f_fwd, f_bwd = ("mmvae_mm_text_decoder_fwd", "mmvae_mm_text_decoder_bwd") if self._api == "mm" else \
+                       ("mmvae_mmtext_decoder_fwd", "mmvae_mmtext_decoder_bwd")
         plist = [p for _, p in self.named_parameters()]
 
         def fwd(ctx):
             ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
             words = torch.empty(B, max_length, n_characters, dtype=torch.float32, device=z.device)
             tokens = torch.empty(B, max_length, dtype=torch.int64, device=z.device)
-            call("mmvae_mm_text_decoder_fwd", h, ptr(ws), wsb, ptr(z), training, ptr(keep), ptr(ft), ptr(words), ptr(tokens), _stream())
+            call(f_fwd, h, ptr(ws), wsb, ptr(z), training, ptr(keep), ptr(ft), ptr(words), ptr(tokens), _stream())
             ctx.ws, ctx.words, ctx.tokens = ws, words, tokens
             self.last_tokens = tokens
             return words
@@ -391,7 +399,7 @@ class TextDecoder(nn.Module):
         def bwd(ctx, d_words):
             st.grads.zero_()
             dz = torch.empty(B, self.n_latents, dtype=torch.float32, device=z.device)
-            call("mmvae_mm_text_decoder_bwd", h, ptr(ctx.ws), wsb, ptr(z), ptr(keep), ptr(ft), ptr(ctx.words), ptr(ctx.tokens),
+            call(f_bwd, h, ptr(ctx.ws), wsb, ptr(z), ptr(keep), ptr(ft), ptr(ctx.words), ptr(ctx.tokens),
                  ptr(d_words.contiguous()), ptr(dz), _stream())
             return [dz] + core.grads_for(names)
 
@@ -521,6 +529,47 @@ class MultimodalVAE(nn.Module):
         return image_recon, text_recon, mu, logvar
 
 
+class TextVAE(nn.Module):
+    """multimnist/model.py:123-147: ``TextEncoder`` + ``reparametrize`` + ``TextDecoder`` at n_hiddens = 50 under the reference's
+    ``encoder.`` / ``decoder.`` keys, with NO product of experts.  The two children share ONE core on a plan of their own
+    (``core.MultimnistTextState``: the text kernels' hidden-size-50 instantiation), which is what ``TextVAETrainer`` steps in one
+    enqueue."""
+
+    N_HIDDENS = 50
+
+    def __init__(self, n_latents=20, use_cuda=False):
+        super().__init__()
+        self.encoder = TextEncoder(n_latents, n_characters, _textvae=True)
+        self.decoder = TextDecoder(n_latents, n_characters, use_cuda=use_cuda, _textvae=True)
+        self.n_latents = n_latents
+        self._core = _Core(self, "", n_latents, lambda n, d: MultimnistTextState(n, d, self.N_HIDDENS))
+        for m in (self.encoder, self.decoder):
+            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+
+    def encode(self, x):
+        return self.encoder(x)
+
+    reparametrize = MultimodalVAE.reparametrize
+
+    def decode(self, z, keep: Optional[torch.Tensor] = None, force_tokens: Optional[torch.Tensor] = None):
+        return self.decoder(z, keep, force_tokens)
+
+    def forward(self, x, eps=None, gru_keep=None, force_tokens=None):
+        mu, logvar = self.encode(x)
+        z = self.reparametrize(mu, logvar, eps)
+        return self.decode(z, gru_keep, force_tokens), mu, logvar
+
+
+def load_checkpoint_textonly(file_path, use_cuda=False):
+    """multimnist/train_textonly.py:31-42: rebuilds a TextVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    vae = TextVAE(checkpoint['n_latents'], use_cuda=use_cuda)
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # loss_function (multimnist/train.py:69-87)
 # ----------------------------------------------------------------------------------------------------------------
@@ -599,6 +648,11 @@ def loss_function(mu, logvar, recon_image=None, image=None, recon_text=None, tex
 elbo_loss = loss_function          # the name BASELINE.json uses
 
 
+def textonly_loss_function(mu, logvar, recon_text, text, kl_lambda=1e-3):
+    """The loss of multimnist/train_textonly.py:105-106: loss_function with the text term alone, lambda_yx = 1."""
+    return loss_function(mu, logvar, recon_text=recon_text, text=text, kl_lambda=kl_lambda, lambda_yx=1.)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # fused trainer: the train() closure body of multimnist/train.py:146-173 as one enqueue
 # ----------------------------------------------------------------------------------------------------------------
@@ -624,3 +678,24 @@ class FusedTrainer:
     def evaluate(self, image, text, **kw) -> StepOutputs:
         """The test() closure body (multimnist/train.py:197-209): eval-mode forward of the 3 passes, no backward."""
         return self.engine.forward_backward(image, text, training=False, backward=False, **kw)
+
+
+class TextVAETrainer:
+    """``TextVAETrainer(vae, batch_size, lr)(text)`` == zero_grad + forward + loss + backward + Adam step
+    (multimnist/train_textonly.py:95-113, lr default 1e-3, kl_lambda 1e-3) on ``vae``'s own parameters: one pass over B rows."""
+
+    def __init__(self, vae: TextVAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1e-3, seed: int = 1234):
+        dev = next(vae.parameters()).device
+        self.vae = vae
+        st = vae._core.sync(dev)
+        self.engine = FusedMMTextStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed)
+
+    def __call__(self, text, **kw) -> StepOutputs:
+        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
+        self.engine.gru_dropout = self.vae.decoder.gru.dropout > 0
+        return self.engine(text, **kw)
+
+    def evaluate(self, text, **kw) -> StepOutputs:
+        """The test() closure body (multimnist/train_textonly.py:118-131): eval-mode forward, no backward."""
+        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
+        return self.engine.forward_backward(text, training=False, backward=False, **kw)
