@@ -155,7 +155,10 @@ int mmvae_mm_text_decoder_bwd(mmvae_mm_t*, void* ws, size_t ws_bytes, const floa
 size_t mmvae_mm_iw_workspace_bytes(const mmvae_mm_t*);
 int mmvae_mm_iw_score(mmvae_mm_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K, float* loglik_x,
                       float* words, void* stream);
-/* Runs one named GEMM of the step `iters` times on the workspace contents of the last step (profiling aid). */
+/* Runs one named GEMM of the step `iters` times on the workspace contents of the last step (profiling aid).
+ * "image_step:waist_fwd" | "image_step:chain_fwd" | "image_step:waist_bwd" | "image_step:chain_bwd" (test aid): the middle of
+ * mmvae_mm_image_step again -- classifier.3 to z, or dz back to classifier.0's output gradient -- fused or unfused, in training mode
+ * with dropout at kl_lambda = 1e-3, on the one-pass workspace of a step that drew its own eps and masks. */
 int mmvae_mm_bench_layer(mmvae_mm_t*, void* ws, size_t ws_bytes, const char* layer, int iters, void* stream);
 double mmvae_mm_layer_flops(const mmvae_mm_t*, const char* layer);        /* executed: 2*rows*N*K, zero-padded taps included */
 double mmvae_mm_layer_algo_flops(const mmvae_mm_t*, const char* layer);   /* algorithmic: the FlopCounterMode count of the reference layer */
@@ -168,7 +171,8 @@ double mmvae_debug_flops(int reset);
  * the backward entries then return MMVAE_EINVAL; a cluster launch that gave up waiting puts a NaN into element 0 of
  * sentence / dz.  DESIGN.md 4.4 lists all of them) */
 int mmvae_debug_set(const char* key, int value);
-/* test aid: byte offset of a named intermediate inside the workspace (-1 if unknown) */
+/* test aid: byte offset of a named intermediate inside the workspace (-1 if unknown); "image_step:<name>": inside the one-pass
+ * workspace of mmvae_mm_image_step and of the module entry points */
 long long mmvae_mm_debug_offset(mmvae_mm_t*, const char* name);
 
 /* ---------------------------------------------------------------- MNIST (mnist/model.py, mnist/train.py)
@@ -486,6 +490,20 @@ int mmvae_celeba_iw_score_image(mmvae_celeba_t*, void* ws, size_t ws_bytes, cons
                                 float* loglik_x, void* stream);
 int mmvae_coco_iw_score_image(mmvae_coco_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K,
                               float* loglik_x, void* stream);
+/* MultiMNIST's ImageVAE (multimnist/model.py, trained by multimnist/train_imageonly.py) on the same struct: image [B][1][50][50],
+ * enc_mask1 [B][400] and enc_mask2 [B][200] keep flags (each given or drawn on its own), coef = lambda_x / (B * 2500).  The plan is an
+ * mmvae_mm_t at any n_latents 1..127; nothing of text_encoder.* / text_decoder.* is launched.  Workspace: the one-pass carve,
+ * mmvae_mm_image_step_workspace_bytes (== mmvae_mm_module_workspace_bytes).  This family has a tower of its own, so the step runs
+ * the launch forms of the mmvae_mm_image_* module entry points.  At n_latents = 20 and 100, with the switch "mm_image_waist" (mmvae_debug_set)
+ * on, classifier.3 + classifier.6 + the latent block are ONE row-block launch per direction (csrc/mlp_tail.hip: 16 rows per workgroup from
+ * classifier.0's output to z, and from dz back to classifier.0's output gradient) and one single-workgroup fold of their partial sums
+ * beside the main chain; every other n_latents, or the switch at 0, runs classifier.3 / classifier.6, mmvae_latent1_fwd / _bwd and the
+ * two data gradients as separate launches.  Both ways fold every sum of the latent block in a fixed order without float atomics.
+ * mmvae_mm_iw_score_image: the image half of mmvae_mm_iw_score alone, loglik_x [B*K]; workspace mmvae_mm_iw_workspace_bytes. */
+int mmvae_mm_image_step(mmvae_mm_t*, const mmvae_image_step_io*, int training, int do_backward, void* stream);
+size_t mmvae_mm_image_step_workspace_bytes(const mmvae_mm_t*);
+int mmvae_mm_iw_score_image(mmvae_mm_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K, float* loglik_x,
+                            void* stream);
 /* The one-expert latent block of that step, alone (D <= 128).  scratch: mmvae_latent1_scratch_floats(B, D) floats, 8-byte aligned, contents
  * undefined on entry and exit.  Every sum is folded in a fixed order without float atomics: equal inputs give equal bits.
  * fwd: enc_out [B][2D] -> mu, logvar [B][D] = its two halves bit for bit; z [B][D] = mu + eps * exp(logvar / 2) (training, the

@@ -286,7 +286,7 @@ SIGNATURES["mmvae_coco_iw_workspace_bytes"] = (_SZ, [_P])
 SIGNATURES["mmvae_coco_iw_score"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES["mmvae_coco_iw_tail"] = (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES["mmvae_coco_iw_text_sse"] = (_I, [_P, _P, _I, _I, _I, _P, _P])
-for _f in ("celeba", "coco"):
+for _f in ("celeba", "coco", "mm"):
     SIGNATURES["mmvae_%s_image_step" % _f] = (_I, [_P, C.POINTER(ImageStepIO), _I, _I, _P])
     SIGNATURES["mmvae_%s_image_step_workspace_bytes" % _f] = (_SZ, [_P])
     SIGNATURES["mmvae_%s_iw_score_image" % _f] = (_I, [_P, _P, _SZ, _P, _P, _I, _I, _P, _P])

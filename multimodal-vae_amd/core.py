@@ -685,22 +685,25 @@ class FusedCocoStep(_FusedStepBase):
 
 
 class FusedImageStep(_FusedStepBase):
-    """The step of celeba/train_imageonly.py:95-113 and coco/train_imageonly.py on the family's plan: zero_grad -> ONE pass over B rows
-    (image encoder, reparametrize, image decoder; no product of experts) -> BCE + kl_lambda * KL -> backward -> Adam.  ``state`` is
-    a ``CelebaState`` or a ``CocoState``; the second modality's parameters keep their values and get a gradient of exactly 0.
-    ``StepOutputs`` slot 0 carries the pass."""
+    """The step of celeba/train_imageonly.py:95-113, coco/train_imageonly.py and multimnist/train_imageonly.py:91-106 on the family's
+    plan: zero_grad -> ONE pass over B rows (image encoder, reparametrize, image decoder; no product of experts) -> BCE +
+    kl_lambda * KL -> backward -> Adam.  ``state`` is a ``CelebaState``, a ``CocoState`` or a ``MultimnistState``; the second
+    modality's parameters keep their values and get a gradient of exactly 0.  ``StepOutputs`` slot 0 carries the pass."""
 
-    SIDE = {"celeba": 64, "coco": 32}
+    SIDE = {"celeba": 64, "coco": 32, "mm": 50}
+    CHANNELS = {"celeba": 3, "coco": 3, "mm": 1}
+    FAMILIES = "CelebA, COCO and MultiMNIST"
     IMAGE_PREFIXES = ("image_encoder.", "image_decoder.")
 
     def __init__(self, state: PlanState, batch: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  kl_lambda: float = 1e-3, lambda_x: float = 1.0, seed: int = 1234):
         if state.API not in self.SIDE:
-            raise MMVAEError("FusedImageStep: no image-only step for the '%s' family (CelebA and COCO have one)" % state.API)
+            raise MMVAEError("FusedImageStep: no image-only step for the '%s' family (%s have one)" % (state.API, self.FAMILIES))
         super().__init__(state, batch, lr, betas, eps, seed)
         self.kl_lambda, self.lambda_x = kl_lambda, lambda_x
         self.enc_dropout = True
-        self.side = self.SIDE[state.API]
+        self.side, self.channels = self.SIDE[state.API], self.CHANNELS[state.API]
+        self.pixels = self.channels * self.side * self.side      # per image: the BCE is a mean over B * pixels
         # the image half is one run at the head of the flat buffers in both families: the optimizer visits nothing else
         n_img = 0
         for name, shape, off in state.table:
@@ -717,13 +720,15 @@ class FusedImageStep(_FusedStepBase):
         return state._c("image_step_workspace_bytes", state.plan(batch))
 
     def _outputs(self) -> StepOutputs:
-        return StepOutputs(self.sums, self.B * 3 * self.side * self.side, 1.0, self.kl_lambda / self.B, (self.lambda_x, 0.0, 0.0),
+        return StepOutputs(self.sums, self.B * self.pixels, 1.0, self.kl_lambda / self.B, (self.lambda_x, 0.0, 0.0),
                            (0.0, 0.0, 0.0), (True, False, False))
 
     def forward_backward(self, image, training=True, backward=True, eps=None, enc_mask1=None, enc_mask2=None, recon_image=None,
                          mu=None, logvar=None, _defer_unpack=False) -> StepOutputs:
         assert image.is_contiguous() and image.dtype == torch.float32
-        assert image.shape == (self.B, 3, self.side, self.side)
+        if tuple(image.shape) != (self.B, self.channels, self.side, self.side):
+            raise MMVAEError("FusedImageStep: expected images of shape %s (got %s)"
+                             % ((self.B, self.channels, self.side, self.side), tuple(image.shape)))
         io = _lib.ImageStepIO()
         io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
         io.step_counter = self.adam_state.data_ptr()

@@ -183,6 +183,16 @@ int mmvae_mm_iw_score(mmvae_mm_t* p, void* ws, size_t wsb, const float* z, const
                       float* words, void* stream) {
     return guarded([&] { return mm_iw_score(p, ws, wsb, z, image, B, K, loglik_x, words, S(stream)); });
 }
+int mmvae_mm_image_step(mmvae_mm_t* p, const mmvae_image_step_io* io, int training, int do_backward, void* stream) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_mm_image_step: null argument");
+        return mm_image_step(p, *io, training, do_backward, S(stream));
+    });
+}
+size_t mmvae_mm_image_step_workspace_bytes(const mmvae_mm_t* p) { return p ? mm_image_step_workspace_bytes(p) : 0; }
+int mmvae_mm_iw_score_image(mmvae_mm_t* p, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, void* st) {
+    return guarded([&] { return mm_iw_score_image(p, ws, wsb, z, image, B, K, loglik_x, S(st)); });
+}
 int mmvae_mm_bench_layer(mmvae_mm_t* p, void* ws, size_t wsb, const char* layer, int iters, void* stream) {
     return guarded([&] { return mm_bench_layer(p, ws, wsb, layer, iters, S(stream)); });
 }

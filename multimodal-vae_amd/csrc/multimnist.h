@@ -29,6 +29,10 @@ int mm_text_decoder_bwd(MMPlan*, void* ws, size_t wsb, const float* z, const uin
 // importance-weighted evaluation: z [B][K][D] (B*K <= plan rows), image [B][1][50][50] -> loglik_x [B*K], words [B*K][4][12]
 int mm_iw_score(MMPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
                 hipStream_t);
+// image-only VAE (multimnist/model.py ImageVAE): one pass over B rows in the one-pass carve, and log p(x|z) alone
+int mm_image_step(MMPlan*, const mmvae_image_step_io&, int training, int do_backward, hipStream_t);
+size_t mm_image_step_workspace_bytes(const MMPlan*);
+int mm_iw_score_image(MMPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t);
 // makes `s` wait until the early gradient part of the last dp_split step is complete in the flat gradient buffer
 int mm_wait_early_grads(MMPlan*, hipStream_t s);
 int mm_bench_layer(MMPlan*, void* ws, size_t wsb, const char* layer, int iters, hipStream_t);

@@ -30,6 +30,10 @@ struct MMPlan : PlanBase {
     // fused classifier tail (mlp_tail.hip; n_latents = 100 only): fragment-major copies of classifier.3 / classifier.6
     bool mlp_tail = false;
     int mt_w2, mt_w3, mt_w3t, mt_w2t;
+    // one-expert waist of the image-only step (mlp_tail.hip; n_latents = 20 and 100): the same four copies, classifier.6's at the
+    // widths of 2D (at n_latents = 100 they ARE the mt_ ones)
+    bool waist = false;
+    int wa_w2, wa_w3, wa_w3t, wa_w2t;
     // ---- workspace pointers
     struct W {
         char* zero_begin; size_t zero_bytes;
@@ -135,6 +139,14 @@ void build_plan(MMPlan& P) {
         P.mt_w3 = fragd(pack_dense(P.fc[2].w_off, 200, 200, 208, 224, 200, 1));
         P.mt_w3t = fragd(pack_dense(P.fc[2].w_off, 200, 200, 208, 224, 1, 200));    // [fc2 unit][fc3 output]
         P.mt_w2t = fragd(pack_dense(P.fc[1].w_off, 400, 200, 400, 224, 1, 400));    // [fc1 unit][fc2 unit]
+        P.waist = true; P.wa_w2 = P.mt_w2; P.wa_w3 = P.mt_w3; P.wa_w3t = P.mt_w3t; P.wa_w2t = P.mt_w2t;
+    } else if (mlp2_latent1_compiled(D)) {      // n_latents = 20: read by the image-only step alone (mm_image_step_body)
+        P.waist = true;
+        auto fragd = [&](PackDesc d) { d.frag = 1; return P.pk.add(d); };
+        P.wa_w2 = fragd(pack_dense(P.fc[1].w_off, 200, 400, 208, 416, 400, 1));
+        P.wa_w3 = fragd(pack_dense(P.fc[2].w_off, 2 * D, 200, round_up(2 * D, 16), 224, 200, 1));
+        P.wa_w3t = fragd(pack_dense(P.fc[2].w_off, 200, 2 * D, 208, round_up(2 * D, 32), 1, 200));      // [fc2 unit][fc3 output]
+        P.wa_w2t = fragd(pack_dense(P.fc[1].w_off, 400, 200, 400, 224, 1, 400));                        // [fc1 unit][fc2 unit]
     }
     {   // upsample Linear(D, 1024): output columns permuted to NHWC n' = s*256 + c  <->  row c*4 + s
         LinL& f = P.up;
@@ -171,7 +183,7 @@ void build_plan(MMPlan& P) {
             for (int i = 0; i < 4; ++i) { late(P.conv[l].pk_dgrad[i]); late(P.conv[l].pk_dgrad_f[i]); }
         for (int i = 0; i < 4; ++i) late(P.fc[0].pk_dgrad4[i]);
         late(P.fc[1].pk_dgrad); late(P.fc[2].pk_dgrad);
-        if (P.mlp_tail) { late(P.mt_w3t); late(P.mt_w2t); }
+        if (P.waist) { late(P.wa_w3t); late(P.wa_w2t); }
     }
     // gradient descriptors of the decoders (image_decoder.*, text_decoder.*): complete before the encoders' backward has run
     // (mmvae_mm_step_io::dp_split scatters them into the flat gradient buffer early)
@@ -240,9 +252,13 @@ void carve(MMPlan& P, Workspace& ws) {
 // `fuse`: the layers whose consumer is an image-resident kernel (convres.hip) hand it the RAW tensor and the BatchNorm
 // statistics (GatherTransform kind 1); the materialised activation is made later, off the main chain, for the weight gradient
 int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, int training,
-            int bn_updates, float* out, hipStream_t s, bool fuse = false) {
+            int bn_updates, float* out, hipStream_t s, bool fuse = false, const Mlp2Latent1FwdArgs* waist = nullptr, bool tail_only = false) {
     MMPlan::W& w = P.w;
     const int B = P.B;
+    const int rows = variants * B;
+    const bool drop = training && dropout;
+    const float ms = 1.f / (1.f - DROP_P);
+    if (!tail_only) {      // (tail_only: classifier.3 onwards, on the ay1 of an earlier call -- mm_bench_layer's replay of the image step's middle)
     if (fuse && mmvae_knob("mm_conv1_mfma", 1)) {      // one workgroup per image on the matrix cores (conv1.hip)
         const PackDesc& d = P.pk.d[P.conv[0].pk_fwd[0]];
         MMVAE_TRY(launch_conv1_fwd_mfma(image, B, P.buf.packed + d.dst_off, d.Kpad, w.r1, w.a1, s));
@@ -276,9 +292,6 @@ int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, cons
         if (fuse && l <= 2) continue;  // a2 / a3 are made in front of the next layer's weight gradient (enc_bwd)
         MMVAE_TRY(bn_act(P, P.bn[L.bn], r[l], a[l], rows, rows, 1, w.st_e[l - 1], bn_updates, w.aff_e[l - 1], w.mr_e[l - 1], training, s));
     }
-    const int rows = variants * B;
-    const bool drop = training && dropout;
-    const float ms = 1.f / (1.f - DROP_P);
     {   // fc1 over the NHWC 2x2x256 map (shared by the variants)
         GatherPlan pl = plan_fwdform(2, 2, 1, 1, 256, 2, 2, 1, 0, 400, 1, rows);
         GemmParams g = gemm_of(P, pl, &P.fc[0].pk_fwd, 1, rows);
@@ -286,6 +299,16 @@ int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, cons
         g.bias = P.buf.params + P.fc[0].b_off; g.out_bf = w.y1; g.ldo = 400;
         g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (drop) { g.e_mask = m1; g.e_mask_scale = ms; }
         MMVAE_TRY(launch_gemm_gather(g, s));
+    }
+    }
+    if (waist) {           // image-only step: the same launch goes on to (mu | logvar), z and the KL partials (the caller's fields)
+        Mlp2Latent1FwdArgs a = *waist;
+        a.rows = rows; a.x = w.ay1;
+        a.w2 = P.buf.packed + P.pk.d[P.wa_w2].dst_off; a.b2 = P.buf.params + P.fc[1].b_off;
+        a.w3 = P.buf.packed + P.pk.d[P.wa_w3].dst_off; a.b3 = P.buf.params + P.fc[2].b_off;
+        if (drop) { a.mask = m2; a.mask_scale = ms; }
+        a.y2 = w.y2; a.ay2 = w.ay2; a.out = out;
+        return launch_mlp2_latent1_fwd(a, s);
     }
     if (P.mlp_tail) {      // classifier.3 + Swish + Dropout + classifier.6 in one row-block launch
         Mlp2FwdArgs a{};
@@ -316,14 +339,40 @@ int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, cons
 
 // d_out: bf16 [variants*B][lde], columns 2D.. zero (the generic kernels read their operands in 8-column vectors; 2D is a multiple
 // of 8 only when n_latents is a multiple of 4); the bias gradient of classifier.6 must already be accumulated by the caller
-int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, hipStream_t s, bool fuse = false) {
+// `waist` (image-only step): d_out (= w.d_encout) does not exist yet -- the waist launch forms it, and its finish launch the bias gradient
+int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, hipStream_t s, bool fuse = false,
+            const Mlp2Latent1BwdArgs* waist = nullptr, float* loss_out = nullptr, bool tail_only = false) {
     MMPlan::W& w = P.w;
     const int B = P.B, rows = variants * B, D2 = 2 * P.D;
     const float ms = 1.f / (1.f - DROP_P);
     // fused step: the three classifier weight gradients (0.04-0.4 GFLOP each, every one a launch at the kernel-latency floor) go
     // out as ONE grouped launch behind conv4's data gradient
     auto cls_w = std::make_shared<std::vector<WgradParams>>();
-    if (P.mlp_tail) {      // both data gradients in one row-block launch; the weight gradients follow on the side stream
+    if (waist) {           // latent backward + both data gradients in one row-block launch
+        Mlp2Latent1BwdArgs a = *waist;
+        a.rows = rows;
+        a.w3t = P.buf.packed + P.pk.d[P.wa_w3t].dst_off; a.w2t = P.buf.packed + P.pk.d[P.wa_w2t].dst_off;
+        a.y2 = w.y2; a.y1 = w.y1;
+        if (dropout) { a.mask2 = m2; a.mask1 = m1; a.mask_scale = ms; }
+        a.dy2 = w.dy2; a.dy1 = w.dy1;
+        a.db2 = P.buf.grads + P.fc[1].b_off; a.db1 = P.buf.grads + P.fc[0].b_off;
+        a.d_enc_out = w.d_encout; a.lde = P.lde;
+        MMVAE_TRY(launch_mlp2_latent1_bwd(a, s));
+        {   // the fold of the partials (KL of the forward, classifier.6's bias gradient) and the loss sums: nobody on the main chain
+            // reads them, so the one-workgroup launch goes beside it
+            hipStream_t fs = s;
+            MMVAE_TRY(wgrad_side_stream(P, s, &fs));
+            MMVAE_TRY(launch_mlp2_latent1_finish(a.scratch, rows, P.D, P.buf.grads + P.fc[2].b_off, w.sums, loss_out, fs));
+        }
+        GatherPlan p3 = dense_plan(rows, 200, 200, D2);
+        WgradParams g3 = wgrad_of(P, p3, &P.fc[2].gk, 1, rows);
+        g3.c.A = w.ay2; g3.P = w.d_encout; g3.ldp = P.lde;
+        MMVAE_TRY(wgrad_async(P, g3, s));
+        GatherPlan p2 = dense_plan(rows, 400, 400, 200);
+        WgradParams g2 = wgrad_of(P, p2, &P.fc[1].gk, 1, rows);
+        g2.c.A = w.ay1; g2.P = w.dy2; g2.ldp = 200;
+        MMVAE_TRY(wgrad_async(P, g2, s));
+    } else if (P.mlp_tail) {      // both data gradients in one row-block launch; the weight gradients follow on the side stream
         {
             GatherPlan pl = dense_plan(rows, 200, 200, D2);
             WgradParams g = wgrad_of(P, pl, &P.fc[2].gk, 1, rows);
@@ -370,6 +419,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
         MMVAE_TRY(launch_gemm_gather(d, s));
     }
     }
+    if (tail_only) return MMVAE_OK;        // (down to classifier.0's output gradient: mm_bench_layer's replay of the image step's middle)
     {   // fc1: wgrad gathers the shared 2x2x256 map; dgrad emits NHWC gradients for `rows` samples
         GatherPlan pl = plan_fwdform(2, 2, 1, 1, 256, 2, 2, 1, 0, 400, 1, rows);
         WgradParams g = wgrad_of(P, pl, &P.fc[0].gk, 1, rows);
@@ -979,6 +1029,147 @@ int mm_wait_early_grads(MMPlan* P, hipStream_t s) {
     return MMVAE_OK;
 }
 
+// ---------------------------------------------------------------- image-only VAE (multimnist/model.py ImageVAE, multimnist/train_imageonly.py)
+// The counterpart of img_tower.h tower_image_step on this family's own tower: zero_grad, ONE forward of B rows (encoder with one
+// dropout variant and one BatchNorm update, the one-expert latent block -- no product of experts --, decoder with one BatchNorm
+// group, sigmoid + BCE) and its backward, in the one-pass carve.  The launches are the module entry points' (the staged conv
+// forms, conv1.hip's in-step form and the fused decoder tail's backward groups are built for 3 groups / 2 variants and stay
+// with the 3-pass step); weight gradients go to the side stream.  Nothing of the text half is launched: its gradients stay at
+// the zero of the prologue.
+// The middle of that chain -- classifier.3, classifier.6, latent1 (+ finish), then upsample.0; backward latent1 (+ finish), two
+// data gradients -- is launch latency on the critical path.  Where the latent size is compiled (mlp2_latent1_compiled) and the
+// knob mm_image_waist is on, the waist pair of mlp_tail.hip replaces it: one launch per direction on the main chain.
+// default of mm_image_waist per compiled size, from profiles/imageonly_mm_bench.txt: at n_latents = 20 the waist wins at B = 256 (0.541
+// against 0.565 ms, spread 0.003) and ties at B = 128; at n_latents = 100, where the chain already has mlp2_fwd / mlp2_bwd, it does
+// not win (B = 128: 0.494 against 0.485 ms, B = 256 a tie)
+static int mm_image_waist_default(int D) { return D == 20 ? 1 : 0; }
+// the encoder with its latent block, and their backward, either way; `tail_only`: classifier.3 onwards / down to classifier.0's output
+// gradient, on the buffers an earlier step left in the workspace (mm_image_middle_replay)
+struct ImageMiddle {
+    bool waist; int training, enc_drop;
+    const float* eps; const uint8_t *m1, *m2; float *mu, *logvar;
+    const float* dz; float kl_coef; float* loss_out;
+};
+static Latent1Args image_latent_args(MMPlan& P, const ImageMiddle& m) {
+    MMPlan::W& w = P.w;
+    Latent1Args la{};
+    la.B = P.B; la.D = P.D; la.enc_out = w.encout; la.eps = m.eps; la.mu = m.mu; la.logvar = m.logvar;
+    la.z_f32 = w.z_f32; la.z_bf = w.z_bf; la.ldz = P.ldz; la.kl_sum = w.sums + 8; la.training = m.training;
+    la.scratch = w.tmp_f32;         // (the module decoder's sigmoid-backward buffer: nobody else's in this step)
+    return la;
+}
+static int image_middle_fwd(MMPlan& P, const ImageMiddle& m, const float* image, hipStream_t s, bool tail_only = false) {
+    MMPlan::W& w = P.w;
+    if (m.waist) {
+        Mlp2Latent1FwdArgs wf{};
+        wf.D = P.D; wf.ldz = P.ldz; wf.training = m.training; wf.eps = m.eps; wf.mu = m.mu; wf.logvar = m.logvar;
+        wf.z_f32 = w.z_f32; wf.z_bf = w.z_bf; wf.scratch = reinterpret_cast<double*>(w.tmp_f32);
+        return enc_fwd(P, image, 1, m.m1, m.m2, m.enc_drop, m.training, 1, w.encout, s, false, &wf, tail_only);
+    }
+    MMVAE_TRY(enc_fwd(P, image, 1, m.m1, m.m2, m.enc_drop, m.training, 1, w.encout, s, false, nullptr, tail_only));
+    return launch_latent1_fwd(image_latent_args(P, m), s);
+}
+static int image_middle_bwd(MMPlan& P, const ImageMiddle& m, hipStream_t s, bool tail_only = false) {
+    MMPlan::W& w = P.w;
+    if (m.waist) {
+        Mlp2Latent1BwdArgs wb{};
+        wb.D = P.D; wb.training = m.training; wb.mu = m.mu; wb.logvar = m.logvar; wb.eps = m.eps; wb.dz = m.dz;
+        wb.kl_coef = m.kl_coef; wb.scratch = reinterpret_cast<double*>(w.tmp_f32);
+        return enc_bwd(P, w.d_encout, 1, m.m1, m.m2, m.enc_drop, s, false, &wb, m.loss_out, tail_only);
+    }
+    Latent1BwdArgs lb{};
+    lb.f = image_latent_args(P, m); lb.dz = m.dz; lb.kl_coef = m.kl_coef;
+    lb.d_enc_out = w.d_encout; lb.ld = P.lde; lb.d_bias = P.buf.grads + P.fc[2].b_off;
+    lb.loss_slots = w.sums; lb.loss_out = m.loss_out;      // (BCE and KL sums are final here)
+    MMVAE_TRY(launch_latent1_bwd(lb, s));
+    return enc_bwd(P, w.d_encout, 1, m.m1, m.m2, m.enc_drop, s, false, nullptr, nullptr, tail_only);
+}
+static int mm_image_step_body(MMPlan* Pp, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
+    MMVAE_TRY(use_ws(Pp, io.ws, io.ws_bytes));
+    MMPlan& P = *Pp;
+    MMPlan::W& w = P.w;
+    const int B = P.B, D = P.D;
+    MMVAE_REQUIRE(io.image && io.sums, "image step: image/sums must be given");
+    const int wk = mmvae_knob("mm_image_waist", -1);          // 1 / 0: on / off where compiled; -1 (not set): the size's default
+    ImageMiddle m{};
+    m.waist = P.waist && (wk < 0 ? mm_image_waist_default(D) : wk) != 0;
+    MMVAE_REQUIRE(launch_latent1_scratch_floats(B, D) <= (size_t)B * NPIX && 2 * mlp2_latent1_scratch_doubles(B, D) <= (size_t)B * NPIX,
+                  "image step: no room for the latent block's partial sums");
+    m.training = training; m.enc_drop = training && io.enc_dropout;
+    m.eps = io.eps; m.m1 = io.enc_mask1; m.m2 = io.enc_mask2;
+    StepBeginArgs sb{};
+    sb.zero_ptr[0] = w.zero_begin; sb.zero_bytes[0] = w.zero_bytes;
+    if (do_backward) {
+        sb.zero_ptr[1] = P.buf.gpk; sb.zero_bytes[1] = (size_t)P.gk.mat_elems * sizeof(float);
+        sb.zero_ptr[2] = P.buf.grads; sb.zero_bytes[2] = (size_t)(P.nparams / 4) * 16;
+    }
+    sb.p = DROP_P; sb.seed = io.seed; sb.step = io.step_counter;
+    if (training && !m.eps) { sb.eps = w.eps; sb.n_eps = (long long)B * D; m.eps = w.eps; }
+    if (m.enc_drop && !m.m1) { sb.mask[0] = w.m1; sb.n_mask[0] = (long long)B * 400; m.m1 = w.m1; }
+    if (m.enc_drop && !m.m2) { sb.mask[1] = w.m2; sb.n_mask[1] = (long long)B * 200; m.m2 = w.m2; }
+    MMVAE_TRY(launch_step_begin(sb, s));
+    if (do_backward && P.nparams % 4 != 0)
+        MMVAE_TRY(launch_fill_zero(P.buf.grads + (P.nparams / 4) * 4, (size_t)(P.nparams % 4) * sizeof(float), s));
+    MMVAE_TRY(ensure_streams(P));
+    P.in_step = true;               // (dec_bwd binds its forks to kernel completions: arm_fork / commit_fork)
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        P.capturing = hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+    }
+    m.mu = io.mu ? io.mu : w.mu;
+    m.logvar = io.logvar ? io.logvar : w.logvar;
+    MMVAE_TRY(image_middle_fwd(P, m, io.image, s));
+    ConvTLastFwdArgs last{};
+    last.target = io.image; last.recon = io.recon_image; last.dlogit = do_backward ? w.dlogit : nullptr; last.loss_sum = w.sums;
+    last.coef[0] = io.lambda_x / (float)(B * NPIX);
+    MMVAE_TRY(dec_fwd(P, 1, training, &last, s));
+    if (!do_backward) {
+        P.in_step = false;
+        if (m.waist)                // (the KL partials are folded here, behind the decoder: not between the waist and upsample.0)
+            return launch_mlp2_latent1_finish(reinterpret_cast<double*>(w.tmp_f32), B, D, nullptr, w.sums, io.sums, s);
+        hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, s, w.sums, io.sums);
+        return mmvae_check_launch("sum_slots");
+    }
+    // =============================== backward ===============================
+    P.wgrad_forked = true;
+    P.deferred.clear();
+    P.defer_wgrad = false;
+    int rc = MMVAE_OK;
+    const bool img_term = io.lambda_x != 0.f;        // (a zero weight has exactly no gradient)
+    if (img_term) rc = dec_bwd(P, w.dlogit, 1, w.dz_img, s);
+    m.dz = img_term ? w.dz_img : nullptr; m.kl_coef = io.kl_lambda / (float)B; m.loss_out = io.sums;
+    if (rc == MMVAE_OK) rc = image_middle_bwd(P, m, s);
+    P.wgrad_forked = false;
+    P.in_step = false;
+    MMVAE_TRY(rc);
+    MMVAE_TRY(join_sides(P, s, s));
+    if (io.defer_unpack) return launch_wgrad_reduce(&P.slab, s);      // the packed gradients are complete; Adam gathers them
+    return plan_unpack(P, s, true);
+}
+// Test aid (mm_bench_layer "image_step:waist_fwd" | "chain_fwd" | "waist_bwd" | "chain_bwd"): the middle of the image-only step again --
+// classifier.3 to z, or dz back to classifier.0's output gradient -- with the waist or with the unfused chain, in training mode with
+// dropout, on what a step that DREW its eps and masks (and got no mu / logvar buffers) left in its one-pass workspace, kl_lambda =
+// 1e-3.  Two steps do not hand the middle the same bits (the conv towers' BatchNorm sums are fp32 atomics), two replays do.  The
+// backward adds to the bias gradients of classifier.0 / .3 / .6 and writes `sums` (the workspace's loss slots summed) to loss_out.
+static int mm_image_middle_replay(MMPlan* Pp, void* ws, size_t wsb, const std::string& what, hipStream_t s) {
+    MMVAE_REQUIRE(what == "waist_fwd" || what == "chain_fwd" || what == "waist_bwd" || what == "chain_bwd", "bench_layer: unknown layer 'image_step:%s'", what.c_str());
+    MMVAE_TRY(use_ws(Pp, ws, wsb));
+    MMPlan& P = *Pp;
+    MMPlan::W& w = P.w;
+    ImageMiddle m{};
+    m.waist = what.compare(0, 5, "waist") == 0;
+    MMVAE_REQUIRE(!m.waist || P.waist, "bench_layer: no waist is compiled for n_latents = %d", P.D);
+    m.training = 1; m.enc_drop = 1; m.eps = w.eps; m.m1 = w.m1; m.m2 = w.m2; m.mu = w.mu; m.logvar = w.logvar;
+    m.dz = w.dz_img; m.kl_coef = 1e-3f / (float)P.B; m.loss_out = w.tmp_f32 + (size_t)P.B * NPIX - 16;
+    if (what.compare(6, 3, "fwd") == 0) return image_middle_fwd(P, m, nullptr, s, true);
+    MMVAE_TRY(image_middle_bwd(P, m, s, true));
+    return launch_wgrad_reduce(&P.slab, s);
+}
+size_t mm_image_step_workspace_bytes(const MMPlan* P) { return P->ws_bytes_module; }
+int mm_image_step(MMPlan* P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
+    return plan_step(P, io, training, do_backward, s, mm_image_step_body);
+}
+
 // ---------------------------------------------------------------- granular module entry points (drop-in modules)
 // Every call gets its own workspace (saved activations live there until the matching backward).
 int mm_image_encoder_fwd(MMPlan* P, void* ws, size_t wsb, const float* image, const uint8_t* m1, const uint8_t* m2,
@@ -1061,11 +1252,10 @@ int mm_text_decoder_bwd(MMPlan* P, void* ws, size_t wsb, const float* z, const u
 // Eval-mode decoders on the B*K particle rows z [B][K][D]: the image decoder ends in the scoring form of the fused tail (one
 // log p(x|z) per row, against the row's own example), the text decoder writes its greedy log-softmax outputs.  No backward
 // activations are kept and the BatchNorm running statistics are not touched.
-int mm_iw_score(MMPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
-                hipStream_t s) {
-    MMVAE_REQUIRE(P && z && image && loglik_x && words, "mmvae_mm_iw_score: null argument");
-    MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B,
-                  "mmvae_mm_iw_score: %d examples x %d particles exceed the plan's %d rows", B, K, P->B);
+// the image half: particles -> z_bf, eval-mode decoder, scoring tail (`who`: the entry point, for its messages)
+static int iw_image_rows(MMPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t s,
+                         const char* who) {
+    MMVAE_REQUIRE(B >= 1 && K >= 1 && (long long)B * K <= P->B, "%s: %d examples x %d particles exceed the plan's %d rows", who, B, K, P->B);
     MMVAE_TRY(use_ws(P, ws, wsb));
     MMPlan::W& w = P->w;
     const int rows = B * K;
@@ -1074,10 +1264,20 @@ int mm_iw_score(MMPlan* P, void* ws, size_t wsb, const float* z, const float* im
     MMVAE_TRY(mmvae_check_launch("cast_z"));
     ConvTLastFwdArgs last{};
     last.target = image; last.loglik = loglik_x; last.rows_per_target = K; last.rows = rows;
-    MMVAE_TRY(dec_fwd(*P, 1, 0, &last, s, -1, 0));
+    return dec_fwd(*P, 1, 0, &last, s, -1, 0);
+}
+int mm_iw_score(MMPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, float* words,
+                hipStream_t s) {
+    MMVAE_REQUIRE(P && z && image && loglik_x && words, "mmvae_mm_iw_score: null argument");
+    MMVAE_TRY(iw_image_rows(P, ws, wsb, z, image, B, K, loglik_x, s, "mmvae_mm_iw_score"));
     TextDecArgs a = td_args(*P, z, 1, false);
-    a.R = rows; a.words = words;
+    a.R = B * K; a.words = words;
     return launch_text_decoder_fwd(a, s);
+}
+// log p(x | z) of the particle rows alone: the image-only VAE has no text decoder to run
+int mm_iw_score_image(MMPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t s) {
+    MMVAE_REQUIRE(P && z && image && loglik_x, "mmvae_mm_iw_score_image: null argument");
+    return iw_image_rows(P, ws, wsb, z, image, B, K, loglik_x, s, "mmvae_mm_iw_score_image");
 }
 
 // ---------------------------------------------------------------- profiling aid: replay one GEMM of the step
@@ -1239,6 +1439,10 @@ static double gemm_flops(const GemmParams& g) {
     return f;
 }
 int mm_bench_layer(MMPlan* P, void* ws, size_t wsb, const char* layer, int iters, hipStream_t s) {
+    if (std::strncmp(layer, "image_step:", 11) == 0) {      // the middle of mm_image_step, on its one-pass workspace
+        for (int i = 0; i < iters; ++i) MMVAE_TRY(mm_image_middle_replay(P, ws, wsb, layer + 11, s));
+        return MMVAE_OK;
+    }
     MMVAE_TRY(use_ws(P, ws, wsb, false));
     if (std::string(layer) == "dec_last_fused") {        // fused decoder tail as in the training step (2 of 3 passes carry a gradient)
         ConvTLastFwdArgs last{};
@@ -1320,8 +1524,12 @@ double mm_layer_algo_bytes(const MMPlan* Pc, const char* layer) {
 // ---------------------------------------------------------------- test aid: byte offset of a named workspace buffer
 long long mm_debug_offset(MMPlan* P, const char* name) {
     Workspace ws((void*)0x1000, (size_t)1 << 40);
-    P->carve_passes = 3;
+    // "image_step:<name>": in the one-pass carve of mm_image_step (and of the module entry points)
+    const bool one_pass = std::strncmp(name, "image_step:", 11) == 0;
+    if (one_pass) name += 11;
+    P->carve_passes = one_pass ? 1 : 3;
     carve(*P, ws);
+    P->carve_passes = 3;
     MMPlan::W& w = P->w;
     std::map<std::string, const void*> m = {
         {"patches1", w.patches1}, {"r1", w.r1}, {"r2", w.r2}, {"r3", w.r3}, {"r4", w.r4}, {"y1", w.y1}, {"y2", w.y2},
@@ -1338,6 +1546,7 @@ long long mm_debug_offset(MMPlan* P, const char* name) {
         {"a1", w.a1}, {"a2", w.a2}, {"a3", w.a3}, {"aq1", w.aq1}, {"aq2", w.aq2}, {"aq3", w.aq3},
         {"a4", w.a4}, {"au", w.au}, {"ay1", w.ay1}, {"ay2", w.ay2}, {"slab", w.slab},
         {"mr_e0", w.mr_e[0]}, {"mr_e1", w.mr_e[1]}, {"mr_e2", w.mr_e[2]}, {"mr_d0", w.mr_d[0]}, {"mr_d1", w.mr_d[1]}, {"mr_d2", w.mr_d[2]},
+        {"mu", w.mu}, {"logvar", w.logvar}, {"recon", w.recon}, {"sums", w.sums},
     };
     auto it = m.find(name);
     if (it == m.end()) return -1;

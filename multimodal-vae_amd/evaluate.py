@@ -341,6 +341,8 @@ _FAMILIES = {
                           lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), image_only=True),
     "coco_text": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_text_score,
                          lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), float_text=True, text_only=True),
+    "multimnist_image": _Family("multimnist", 1, 1, (1, 50, 50), IW_ROWS, _image_score("mm"),
+                                lambda st, rows: _iw_call("mmvae_mm_iw_workspace_bytes", st.plan(rows)), image_only=True),
     # the MultiMNIST TextVAE: the text decoder alone on a plan of its own; its "image" is one dummy pixel
     "multimnist_text": _Family("multimnist", 4, 12, (1,), IW_ROWS, _mmtext_score,
                                lambda st, rows: st.module_workspace_bytes(rows), text_only=True),
@@ -361,6 +363,9 @@ def _family(model):
         return _FAMILIES["coco_text"]
     if isinstance(model, MultimnistTextVAE):
         return _FAMILIES["multimnist_text"]
+    from .multimnist import ImageVAE as MultimnistImageVAE
+    if isinstance(model, MultimnistImageVAE):
+        return _FAMILIES["multimnist_image"]
     if isinstance(model, (CelebaImageVAE, CocoImageVAE)):
         return _FAMILIES["celeba_image" if isinstance(model, CelebaImageVAE) else "coco_image"]
     return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else
@@ -623,6 +628,21 @@ def sample_textonly(vae, n_samples=64, text=None):
     z = torch.randn(n_samples, vae.n_latents).to(dev)
     z = z * std.expand_as(z) + mu.expand_as(z)
     return torch.max(vae.decode(z.contiguous()).cpu(), dim=2)[1]
+
+
+@torch.no_grad()
+def sample_imageonly(vae, n_samples=64, image=None):
+    """``sample`` for a multimnist ``ImageVAE``: image samples (n,1,50,50), from the prior or from q(z|x) of ``image`` (1,1,50,50)."""
+    vae.eval()
+    dev = next(vae.parameters()).device
+    if image is None:
+        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
+    else:
+        mu, logvar = vae.encode(image.to(dev))
+        std = logvar.mul(0.5).exp()
+    z = torch.randn(n_samples, vae.n_latents).to(dev)
+    z = z * std.expand_as(z) + mu.expand_as(z)
+    return vae.decode(z.contiguous()).cpu().view(n_samples, 1, 50, 50)
 
 
 @torch.no_grad()
@@ -914,8 +934,9 @@ def _parser():
     # multimnist/sample.py's flags for a checkpoint of train_coco; the captions are decoded through a word table
     pt = sub.add_parser("test_imageonly", help="celeba/test_imageonly.py: eval-mode loss (kl_lambda = 1) of a train_imageonly checkpoint")
     pt.add_argument('model_path', type=str)
-    pt.add_argument('--dataset', choices=('celeba', 'coco'), default='celeba')
-    pt.add_argument('--data', type=str, default='', help='celeba: FILE.pt of make_celeba; coco: DIR with images_u8.pt')
+    pt.add_argument('--dataset', choices=('celeba', 'coco', 'multimnist'), default='celeba')
+    pt.add_argument('--data', type=str, default='',
+                    help='celeba: FILE.pt of make_celeba; coco: DIR with images_u8.pt; multimnist: root of processed/test.pt')
     pt.add_argument('--synthetic', type=int, default=0, metavar='N')
     pt.add_argument('--batch_size', type=int, default=128, metavar='N')
     pt.add_argument('--seed', type=int, default=0)
@@ -1374,7 +1395,16 @@ def _test_imageonly_main(args):
     """`test_imageonly`: whole batches only (the plan takes a fixed batch size); a trailing partial batch is dropped."""
     import os
     from . import data as D
-    if args.dataset == "celeba":
+    if args.dataset == "multimnist":
+        from .multimnist import load_checkpoint_imageonly
+        if args.synthetic > 0:
+            x, _ = D.synthetic_multimnist(args.synthetic, seed=args.seed)
+        elif args.data:
+            x, _ = D.load_multimnist(args.data, train=False)
+        else:
+            raise SystemExit("test_imageonly: give --data or --synthetic N")
+        x = x.view(-1, 1, 50, 50)
+    elif args.dataset == "celeba":
         from .celeba import load_checkpoint_imageonly
         if args.synthetic > 0:
             x, _ = D.synthetic_celeba(args.synthetic, seed=args.seed)
@@ -1457,6 +1487,9 @@ def _loglik_main(args):
     if args.dataset == "multimnist" and is_textonly_checkpoint(args.model_path):      # a checkpoint of train_textonly_multimnist: log p(y) alone
         from .multimnist import load_checkpoint_textonly
         return _report(load_checkpoint_textonly(args.model_path, use_cuda=True), loader, ("text",), args, "Text")
+    if args.dataset == "multimnist" and is_imageonly_checkpoint(args.model_path):     # a checkpoint of train_imageonly: log p(x) alone
+        from .multimnist import load_checkpoint_imageonly
+        return _report(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Text")
     vae = load_checkpoint(args.model_path, use_cuda=True)
     posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
     return _report(vae, loader, posts, args, "Text")
@@ -1502,11 +1535,19 @@ def _main(argv=None):
             for i in range(text_recon.size(0)):
                 fp.write('%s\n' % tensor_to_string(text_recon[i]))
         return None
-    vae = load_checkpoint(args.model_path, use_cuda=True)
     image = text = None
     if args.condition_on_image:
         im = torch.load(args.condition_on_image)
         image = (im.float() / 255.0 if im.dtype == torch.uint8 else im.float()).view(1, 1, 50, 50)
+    if is_imageonly_checkpoint(args.model_path):      # a checkpoint of train_imageonly --dataset multimnist: image samples only
+        from .multimnist import load_checkpoint_imageonly
+        if args.condition_on_text:
+            raise SystemExit("sample: an image-only checkpoint has no text encoder")
+        image_recon = sample_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), args.n_samples, image)
+        os.makedirs(args.out, exist_ok=True)
+        torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))
+        return None
+    vae = load_checkpoint(args.model_path, use_cuda=True)
     if args.condition_on_text:
         text = char_tensor(args.condition_on_text).unsqueeze(0)
     image_recon, text_recon = sample(vae, args.n_samples, image, text)

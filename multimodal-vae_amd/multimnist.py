@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import MMVAEError, call, ptr
 from ._ops import stream as _stream
-from .core import FusedELBOStep, FusedMMTextStep, MultimnistState, MultimnistTextState, StepOutputs
+from .core import FusedELBOStep, FusedImageStep, FusedMMTextStep, MultimnistState, MultimnistTextState, StepOutputs
 
 # multimnist/utils.py:14-19
 max_length = 4
@@ -560,6 +560,46 @@ class TextVAE(nn.Module):
         return self.decode(z, gru_keep, force_tokens), mu, logvar
 
 
+class ImageVAE(nn.Module):
+    """multimnist/model.py:96-120: ``ImageEncoder`` + ``reparametrize`` + ``ImageDecoder`` under the reference's ``encoder.`` /
+    ``decoder.`` keys, with NO product of experts (no 1e-8 in a model that has no experts).  The two children live on the
+    MultimodalVAE's plan (``encoder.features.0.weight`` is its ``image_encoder.features.0.weight``); the text half of the flat
+    buffers keeps its initial value and never shows in ``state_dict()``.  ``ImageVAETrainer`` is the train() closure of
+    multimnist/train_imageonly.py:91-106 as one enqueue."""
+
+    def __init__(self, n_latents=20):
+        super().__init__()
+        self.encoder = ImageEncoder(n_latents)
+        self.decoder = ImageDecoder(n_latents)
+        self.n_latents = n_latents
+        self._core = _Core(self, "image_", n_latents)
+        for m in (self.encoder, self.decoder):
+            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+
+    def encode(self, x, masks: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        return self.encoder(x, masks)
+
+    reparametrize = MultimodalVAE.reparametrize
+
+    def decode(self, z):
+        return self.decoder(z)
+
+    def forward(self, x, eps: Optional[torch.Tensor] = None, enc_masks: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        mu, logvar = self.encode(x, enc_masks)
+        z = self.reparametrize(mu, logvar, eps)
+        return self.decode(z), mu, logvar
+
+
+def load_checkpoint_imageonly(file_path, use_cuda=False):
+    """multimnist/train_imageonly.py:29-40: rebuilds an ImageVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    vae = ImageVAE(n_latents=checkpoint['n_latents'])
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
+
+
 def load_checkpoint_textonly(file_path, use_cuda=False):
     """multimnist/train_textonly.py:31-42: rebuilds a TextVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
     checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
@@ -648,6 +688,11 @@ def loss_function(mu, logvar, recon_image=None, image=None, recon_text=None, tex
 elbo_loss = loss_function          # the name BASELINE.json uses
 
 
+def imageonly_loss_function(recon_x, x, mu, logvar, kl_lambda=1e-3):
+    """The loss of multimnist/train_imageonly.py:102-103: loss_function with the image term alone, lambda_xy = 1."""
+    return loss_function(mu, logvar, recon_image=recon_x, image=x, kl_lambda=kl_lambda, lambda_xy=1.)
+
+
 def textonly_loss_function(mu, logvar, recon_text, text, kl_lambda=1e-3):
     """The loss of multimnist/train_textonly.py:105-106: loss_function with the text term alone, lambda_yx = 1."""
     return loss_function(mu, logvar, recon_text=recon_text, text=text, kl_lambda=kl_lambda, lambda_yx=1.)
@@ -699,3 +744,24 @@ class TextVAETrainer:
         """The test() closure body (multimnist/train_textonly.py:118-131): eval-mode forward, no backward."""
         self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
         return self.engine.forward_backward(text, training=False, backward=False, **kw)
+
+
+class ImageVAETrainer:
+    """``ImageVAETrainer(vae, batch_size, lr)(image)`` == zero_grad + forward + loss + backward + Adam step
+    (multimnist/train_imageonly.py:91-106) on ``vae``'s own parameters: one pass over B rows (core.FusedImageStep)."""
+
+    def __init__(self, vae: ImageVAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1e-3, seed: int = 1234):
+        dev = next(vae.parameters()).device
+        self.vae = vae
+        st = vae._core.sync(dev)
+        self.engine = FusedImageStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed)
+
+    def __call__(self, image, **kw) -> StepOutputs:
+        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
+        self.engine.enc_dropout = self.vae.encoder.classifier[2].p > 0
+        return self.engine(image, **kw)
+
+    def evaluate(self, image, **kw) -> StepOutputs:
+        """The test() closure body (multimnist/train_imageonly.py:115-128): eval-mode forward, no backward."""
+        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
+        return self.engine.forward_backward(image, training=False, backward=False, **kw)

@@ -1,4 +1,5 @@
-"""``celeba/train_imageonly.py`` / ``coco/train_imageonly.py``-compatible driver of the uni-modal image baselines.
+"""``celeba/train_imageonly.py`` / ``coco/train_imageonly.py`` / ``multimnist/train_imageonly.py``-compatible driver of the uni-modal
+image baselines.
 
 Per data set the reference script's command line, defaults, printed lines, KL schedule and checkpoint dict (``state_dict``,
 ``best_loss``, ``n_latents``, ``optimizer``), with the batch loop body replaced by ONE fused enqueue (``ImageVAETrainer``: one pass
@@ -7,9 +8,13 @@ over B rows, no product of experts) and the ``DataLoader`` by ``data.DeviceBatch
     celeba (celeba/train_imageonly.py:57-70,141-153): --n_latents 100 --lr 1e-3, kl_lambda 1e-3 throughout
     coco   (coco/train_imageonly.py:45-60,141-162):   --n_latents 20 --lr 1e-4 [--anneal_kl], kl_lambda 5e-4, or with --anneal_kl
                                                       1e-5, 1e-4, 1e-3 advancing every 5 epochs
+    multimnist (multimnist/train_imageonly.py:46-60,131-139): --n_latents 20 --lr 1e-3 [--anneal_kl], kl_lambda 1e-3, or with
+                                                      --anneal_kl 1e-5 ... 1.0 advancing every 5 epochs; test loss = mean over batches
 
     python -m multimodal_vae_amd.train_imageonly --dataset celeba --cuda --data ./data
     python -m multimodal_vae_amd.train_imageonly --dataset coco --cuda --epochs 2 --synthetic 4096   # no data files needed
+    python -m multimodal_vae_amd.train_imageonly --dataset multimnist --cuda --data ./data           # images of processed/*.pt
+    python -m multimodal_vae_amd.train_imageonly --dataset multimnist --cuda --generate --mnist_train A.pt --mnist_test B.pt
 
 After each epoch 64 prior samples are written as ``sample_image_epochN.pt`` (the tensor, not a PNG grid: no torchvision here).
 """
@@ -21,14 +26,17 @@ import sys
 
 import torch
 
-from .train import AverageMeter, save_checkpoint
+from .train import AverageMeter, kl_schedule, save_checkpoint
 
 DATASETS = {
     #          n_latents  lr    kl_lambda  side
     "celeba": (100, 1e-3, 1e-3, 64),
     "coco": (20, 1e-4, 5e-4, 32),
+    "multimnist": (20, 1e-3, 1e-3, 50),
 }
+CHANNELS = {"celeba": 3, "coco": 3, "multimnist": 1}
 COCO_KL_SCHEDULE = (1e-5, 1e-4, 1e-3)       # coco/train_imageonly.py:142
+KL_SCHEDULES = {"coco": COCO_KL_SCHEDULE, "multimnist": tuple(kl_schedule())}      # multimnist/train_imageonly.py:132
 
 
 def build_parser(dataset: str) -> argparse.ArgumentParser:
@@ -41,16 +49,25 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     parser.add_argument('--epochs', type=int, default=10, metavar='N', help='number of epochs to train (default: 10)')
     parser.add_argument('--lr', type=float, default=lr, metavar='LR', help='learning rate (default: %g)' % lr)
     parser.add_argument('--log_interval', type=int, default=10, metavar='N', help='how many batches to wait before logging training status')
-    if dataset == "coco":
+    if dataset in KL_SCHEDULES:
         parser.add_argument('--anneal_kl', action='store_true', default=False, help='if True, use a fixed interval of doubling the KL term')
     parser.add_argument('--cuda', action='store_true', default=False, help='enables CUDA training')
     # additions, as train_celeba / train_coco
     parser.add_argument('--data', type=str, default='./data', metavar='DIR',
-                        help='celeba: folder with celeba_{train,val}.pt (make_celeba); coco: folder with images_u8.pt (as train_coco)')
+                        help='celeba: folder with celeba_{train,val}.pt (make_celeba); coco: folder with images_u8.pt (as train_coco); '
+                             "multimnist: root of the reference's processed/{training,test}.pt (images only)")
     parser.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic samples instead of files')
     parser.add_argument('--out', type=str, default='./trained_models/image_only', help='checkpoint folder (reference: ./trained_models/image_only)')
     parser.add_argument('--results', type=str, default='./results/image_only', help='folder of the per-epoch sample dumps (off when empty)')
     parser.add_argument('--seed', type=int, default=1234)
+    if dataset == "multimnist":         # as train.py / train_textonly_multimnist.py
+        parser.add_argument('--generate', action='store_true', default=False,
+                            help='canvases generated on the device: --mnist_train / --mnist_test, or synthetic digits with --synthetic N')
+        parser.add_argument('--mnist_train', type=str, default='', help='--generate: MNIST training split, a .pt file holding (uint8 (N,28,28), int64 (N,))')
+        parser.add_argument('--mnist_test', type=str, default='', help='--generate: MNIST test split, same layout')
+        parser.add_argument('--epoch_size', type=int, default=60000, metavar='N', help='--generate: canvases per training epoch (default: 60000)')
+        parser.add_argument('--min_digits', type=int, default=0, help='--generate: minimum number of digits per canvas (datasets.py: 0)')
+        parser.add_argument('--max_digits', type=int, default=2, help='--generate: maximum number of digits per canvas (datasets.py: 2; at most 4)')
     return parser
 
 
@@ -63,12 +80,13 @@ def dataset_of(argv) -> str:
 
 def kl_lambdas(dataset: str, epochs: int, anneal_kl: bool = False):
     """kl_lambda of epochs 1..epochs.  celeba: loss_function's default throughout (celeba/train_imageonly.py:42,114); coco: 5e-4, or
-    with --anneal_kl the next value of 1e-5, 1e-4, 1e-3 every 5 epochs, the last one kept (coco/train_imageonly.py:141-149)."""
+    with --anneal_kl the next value of 1e-5, 1e-4, 1e-3 every 5 epochs, the last one kept (coco/train_imageonly.py:141-149); multimnist:
+    1e-3, or with --anneal_kl the next value of 1e-5 ... 1.0 every 5 epochs (multimnist/train_imageonly.py:131-139)."""
     kl = DATASETS[dataset][2]
-    schedule = iter(COCO_KL_SCHEDULE)
+    schedule = iter(KL_SCHEDULES.get(dataset, ()))
     out = []
     for epoch in range(1, epochs + 1):
-        if dataset == "coco" and (epoch - 1) % 5 == 0 and anneal_kl:
+        if dataset in KL_SCHEDULES and (epoch - 1) % 5 == 0 and anneal_kl:
             kl = next(schedule, kl)
         out.append(kl)
     return out
@@ -101,6 +119,44 @@ def checkpoint_dict(vae, engine, best_loss, n_latents) -> dict:
             'optimizer': image_adam_state_dict(vae, engine)}
 
 
+class _StreamImages:
+    """The canvases of a ``MultiMNISTStream`` (the labels are generated and dropped)."""
+
+    def __init__(self, stream):
+        self.stream = stream
+
+    def __len__(self) -> int:
+        return len(self.stream)
+
+    def __iter__(self):
+        for image, _ in self.stream:
+            yield image, None
+
+
+def _multimnist_loaders(args, dev):
+    """(train_loader, test images) of the MultiMNIST baseline: only the images of a data set are read."""
+    from . import data as D
+    if args.generate:
+        from . import multimnist_gen as G
+        if args.synthetic > 0:
+            mn_tr, mn_te = D.synthetic_mnist(args.synthetic, seed=args.seed), D.synthetic_mnist(args.synthetic, seed=args.seed + 1)
+        elif args.mnist_train and args.mnist_test:
+            from .make_multimnist import load_mnist_pt
+            mn_tr, mn_te = load_mnist_pt(args.mnist_train), load_mnist_pt(args.mnist_test)
+        else:
+            raise SystemExit("--generate needs --mnist_train FILE.pt and --mnist_test FILE.pt, or --synthetic N for synthetic digits")
+        stream = G.MultiMNISTStream(mn_tr[0], mn_tr[1], args.batch_size, dev, epoch_size=args.epoch_size, seed=args.seed,
+                                    min_digits=args.min_digits, max_digits=args.max_digits)
+        n_test = max(args.batch_size, min(10000, args.epoch_size // 6))
+        te_x, _ = G.generate(mn_te[0].to(dev).contiguous(), mn_te[1].to(dev, torch.int64).contiguous(), n_test, seed=args.seed + 7,
+                             min_digits=args.min_digits, max_digits=args.max_digits)
+        return _StreamImages(stream), te_x.cpu()
+    if args.synthetic > 0:
+        return (D.synthetic_multimnist(args.synthetic, seed=args.seed)[0],
+                D.synthetic_multimnist(max(args.batch_size, args.synthetic // 6), seed=args.seed + 1)[0])
+    return D.load_multimnist(args.data, train=True)[0], D.load_multimnist(args.data, train=False)[0]
+
+
 def _load_images(args):
     from . import data as D
     if args.dataset == "celeba":
@@ -128,19 +184,23 @@ def main(argv=None) -> dict:
     import importlib
     from . import data as D
     M = importlib.import_module("." + args.dataset, __package__)
-    side = DATASETS[args.dataset][3]
+    side, channels = DATASETS[args.dataset][3], CHANNELS[args.dataset]
 
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(args.seed)
-    tr_x, te_x = _load_images(args)
+    tr_x, te_x = _multimnist_loaders(args, dev) if args.dataset == "multimnist" else _load_images(args)
+    stream = tr_x if isinstance(tr_x, _StreamImages) else None
+    ishape = (side, side) if channels == 1 else (channels, side, side)       # MultiMNIST files hold (N,50,50): the batcher adds the channel
     for name, x in (("training", tr_x), ("test (val)", te_x)):
-        if x.dtype != torch.uint8 or tuple(x.shape[1:]) != (3, side, side):
-            raise SystemExit("the %s images must be uint8 (N,3,%d,%d) (got %s %s)" % (name, side, side, x.dtype, tuple(x.shape)))
+        if x is stream:
+            continue
+        if x.dtype != torch.uint8 or tuple(x.shape[1:]) != ishape:
+            raise SystemExit("the %s images must be uint8 %s (got %s %s)" % (name, ("N",) + ishape, x.dtype, tuple(x.shape)))
         if len(x) < args.batch_size:
             raise SystemExit("the %s split has %d images, fewer than one batch of %d (the fused plan takes whole batches)"
                              % (name, len(x), args.batch_size))
     none = lambda x: torch.zeros(len(x), dtype=torch.int64)          # the batcher carries a second tensor: nothing reads it
-    train_loader = D.DeviceBatcher(tr_x, none(tr_x), args.batch_size, dev, shuffle=True, seed=args.seed)
+    train_loader = stream if stream is not None else D.DeviceBatcher(tr_x, none(tr_x), args.batch_size, dev, shuffle=True, seed=args.seed)
     test_loader = D.DeviceBatcher(te_x, none(te_x), args.batch_size, dev, shuffle=True, seed=args.seed + 7)
 
     vae = M.ImageVAE(n_latents=args.n_latents)
@@ -150,7 +210,7 @@ def main(argv=None) -> dict:
     trainer = M.ImageVAETrainer(vae, args.batch_size, lr=args.lr, kl_lambda=DATASETS[args.dataset][2], seed=args.seed)
 
     def train(epoch, kl_lambda):
-        if args.dataset == "coco":
+        if args.dataset in KL_SCHEDULES:
             print('Using KL Lambda: {}'.format(kl_lambda))
         vae.train()
         trainer.engine.kl_lambda = kl_lambda
@@ -203,7 +263,7 @@ def main(argv=None) -> dict:
             sample = torch.randn(64, args.n_latents, device=dev)
             vae.eval()
             with torch.no_grad():
-                torch.save(vae.decode(sample).cpu().view(64, 3, side, side), os.path.join(args.results, 'sample_image_epoch%d.pt' % epoch))
+                torch.save(vae.decode(sample).cpu().view(64, channels, side, side), os.path.join(args.results, 'sample_image_epoch%d.pt' % epoch))
     return history
 
 
