@@ -504,6 +504,44 @@ int mmvae_mm_image_step(mmvae_mm_t*, const mmvae_image_step_io*, int training, i
 size_t mmvae_mm_image_step_workspace_bytes(const mmvae_mm_t*);
 int mmvae_mm_iw_score_image(mmvae_mm_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K, float* loglik_x,
                             void* stream);
+/* MNIST's VAE (mnist/model.py:188-232, trained by mnist/imageonly/train_imageonly.py:60-71,114-127) on the same struct and an
+ * mmvae_mnist_t of fp32 precision (a bf16 plan is refused; n_latents 4..124 in multiples of 4 as the plan takes them): image [B][784],
+ * ONE pass over B rows -- image_encoder.net.0 .. 6, the one-expert latent block, image_decoder.net.0 .. 6, sigmoid + BCE, backward --
+ * on the fp32 MFMA launches of the mmvae_mnist_image_* module entry points.  The model has no Dropout: enc_mask1 / enc_mask2 must be
+ * NULL (refused otherwise) and enc_dropout is ignored; B = 1 in training is refused with BatchNorm's own message.  The reference's
+ * loss (mean BCE + KLD / 784) / B is lambda_x = 1/B, kl_lambda = 1/784: sums[0] * lambda_x / (B * 784) + sums[8] * kl_lambda / B.
+ * Nothing of text_encoder.* / text_decoder.* is launched: parameters, BatchNorm buffers and num_batches_tracked of that half keep
+ * their bits, its gradient is exactly 0; the four image BatchNorms update their running statistics once.  The fp32 plan writes
+ * every gradient straight into `grads` (defer_unpack is ignored): mmvae_adam_step over the leading image parameters is the optimizer.
+ * Workspace: mmvae_mnist_image_step_workspace_bytes (a one-pass carve of its own; 0 for a bf16 plan).
+ * mmvae_mnist_iw_score_image: mmvae_mnist_iw_score compiled without the label decoder and without the words output; loglik_x [B*K]
+ * is bit for bit what mmvae_mnist_iw_score writes.  ws / ws_bytes are ignored (the scorer needs no workspace; the parameters keep the
+ * shape of the other families' calls). */
+int mmvae_mnist_image_step(mmvae_mnist_t*, const mmvae_image_step_io*, int training, int do_backward, void* stream);
+size_t mmvae_mnist_image_step_workspace_bytes(const mmvae_mnist_t*);
+int mmvae_mnist_iw_score_image(mmvae_mnist_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K,
+                               float* loglik_x, void* stream);
+/* Column-strip fused layers (csrc/mnist_strip.hip): with the switch "mnist_strip" (mmvae_debug_set; 1 / 0, -1 or unset: the default, 1) on and a batch of at most
+ * mmvae_mnist_strip_max_rows() rows, mmvae_mnist_image_step runs each Linear -> BatchNorm1d -> ReLU of the four BatchNorm layers as ONE
+ * launch forward (a workgroup owns 16 output features and ALL rows: GEMM strip on the fp32 MFMA, two-pass batch statistics folded in a
+ * fixed order through LDS, running-statistics update, affine + ReLU) and ONE launch backward (data gradient of the next Linear, ReLU',
+ * the two BatchNorm sums, dgamma / dbeta and the raw-input gradient) -- no atomics, no grid-wide synchronisation, equal inputs give equal
+ * bits.  Above the cap, or with the switch at 0, the step runs gemm_f32 + the BatchNorm kernels.  mmvae_mnist_step is not switched.
+ * mmvae_mnist_strip_route(rows): 1 when the step takes the strip kernels at that batch, else 0.
+ * mmvae_mnist_lin_bn_act_fwd / mmvae_mnist_lin_dgrad_bn_bwd (test and measurement aid): ONE such layer on plain device pointers.
+ *   route 1: the strip kernel (more rows than the cap are refused); 0: the launches it replaces; -1: mmvae_mnist_strip_route(rows).
+ *   fwd: x [rows][ldx], w [N][K], bias / gamma / beta / running_mean / running_var [N], nbt [1] -> r, a [rows][N], mean_rstd [N][2];
+ *        training 1: batch statistics, the running statistics move once, *nbt += 1; 0: running statistics, no buffer written.
+ *        The strip kernel needs K % 4 == 0, ldx % 4 == 0 and 16-byte aligned x, w.
+ *   bwd: dy [rows][Nn] (gradient wrt the NEXT Linear's output), w_next [Nn][N], r [rows][N] and mean_rstd [N][2] of this layer ->
+ *        d_r [rows][N]; dgamma, dbeta [N] +=.  The strip kernel needs Nn % 4 == 0 and a 16-byte aligned dy. */
+int mmvae_mnist_strip_max_rows(void);
+int mmvae_mnist_strip_route(int rows);
+int mmvae_mnist_lin_bn_act_fwd(int route, const float* x, int ldx, const float* w, const float* bias, const float* gamma, const float* beta,
+                               float* running_mean, float* running_var, long long* nbt, int rows, int N, int K, int training, float* r, float* a,
+                               float* mean_rstd, void* stream);
+int mmvae_mnist_lin_dgrad_bn_bwd(int route, const float* dy, int Nn, const float* w_next, const float* r, const float* mean_rstd,
+                                 const float* gamma, const float* beta, int rows, int N, float* d_r, float* dgamma, float* dbeta, void* stream);
 /* The one-expert latent block of that step, alone (D <= 128).  scratch: mmvae_latent1_scratch_floats(B, D) floats, 8-byte aligned, contents
  * undefined on entry and exit.  Every sum is folded in a fixed order without float atomics: equal inputs give equal bits.
  * fwd: enc_out [B][2D] -> mu, logvar [B][D] = its two halves bit for bit; z [B][D] = mu + eps * exp(logvar / 2) (training, the

@@ -286,10 +286,14 @@ SIGNATURES["mmvae_coco_iw_workspace_bytes"] = (_SZ, [_P])
 SIGNATURES["mmvae_coco_iw_score"] = (_I, [_P, _P, _SZ, _P, _P, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES["mmvae_coco_iw_tail"] = (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P])
 SIGNATURES["mmvae_coco_iw_text_sse"] = (_I, [_P, _P, _I, _I, _I, _P, _P])
-for _f in ("celeba", "coco", "mm"):
+for _f in ("celeba", "coco", "mm", "mnist"):
     SIGNATURES["mmvae_%s_image_step" % _f] = (_I, [_P, C.POINTER(ImageStepIO), _I, _I, _P])
     SIGNATURES["mmvae_%s_image_step_workspace_bytes" % _f] = (_SZ, [_P])
     SIGNATURES["mmvae_%s_iw_score_image" % _f] = (_I, [_P, _P, _SZ, _P, _P, _I, _I, _P, _P])
+SIGNATURES["mmvae_mnist_strip_max_rows"] = (_I, [])
+SIGNATURES["mmvae_mnist_strip_route"] = (_I, [_I])
+SIGNATURES["mmvae_mnist_lin_bn_act_fwd"] = (_I, [_I, _P, _I] + [_P] * 7 + [_I] * 4 + [_P] * 4)
+SIGNATURES["mmvae_mnist_lin_dgrad_bn_bwd"] = (_I, [_I, _P, _I] + [_P] * 5 + [_I, _I] + [_P] * 4)
 SIGNATURES["mmvae_coco_text_step"] = (_I, [_P, C.POINTER(TextStepIO), _I, _I, _P])
 SIGNATURES["mmvae_coco_text_step_workspace_bytes"] = (_SZ, [_P])
 SIGNATURES["mmvae_coco_iw_score_text"] = (_I, [_P, _P, _SZ, _P, _P, _P, _I, _I, _P, _P])
@@ -349,7 +353,7 @@ SIGNATURES["mmvae_imgprep_geometry"] = (_I, [C.POINTER(_I)] * 3)
 SIGNATURES["mmvae_imgprep_layout"] = (_I, [_I, _I, _I] + [C.POINTER(_I)] * 4)
 SIGNATURES["mmvae_imgprep_coeffs"] = (_I, [_I] * 5 + [_P] * 3)
 SIGNATURES["mmvae_imgprep_scale_crop"] = (_I, [_P, _LL, _P, _P, _P, _I, _I, _P, _P, _P, _P])
-_STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_mmtext_hidden", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges"))}
+_STATUS = {n for n, (r, _) in SIGNATURES.items() if r is _I and not n.endswith(("_num_params", "_num_bn", "_precision", "_mmtext_hidden", "_coco_steps", "_comm_world", "_probe_read", "_early_ranges", "_strip_max_rows", "_strip_route"))}
 
 _lib = None
 _inited = set()

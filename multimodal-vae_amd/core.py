@@ -685,26 +685,32 @@ class FusedCocoStep(_FusedStepBase):
 
 
 class FusedImageStep(_FusedStepBase):
-    """The step of celeba/train_imageonly.py:95-113, coco/train_imageonly.py and multimnist/train_imageonly.py:91-106 on the family's
-    plan: zero_grad -> ONE pass over B rows (image encoder, reparametrize, image decoder; no product of experts) -> BCE +
-    kl_lambda * KL -> backward -> Adam.  ``state`` is a ``CelebaState``, a ``CocoState`` or a ``MultimnistState``; the second
-    modality's parameters keep their values and get a gradient of exactly 0.  ``StepOutputs`` slot 0 carries the pass."""
+    """The step of celeba/train_imageonly.py:95-113, coco/train_imageonly.py, multimnist/train_imageonly.py:91-106 and
+    mnist/imageonly/train_imageonly.py:114-127 on the family's plan: zero_grad -> ONE pass over B rows (image encoder, reparametrize,
+    image decoder; no product of experts) -> lambda_x * BCE + kl_lambda * KL / B -> backward -> Adam.  ``state`` is a ``CelebaState``, a
+    ``CocoState``, a ``MultimnistState`` or a fp32 ``MnistState``; the second modality's parameters keep their values and get a gradient
+    of exactly 0.  ``StepOutputs`` slot 0 carries the pass.  MNIST images may come as (B, 1, 28, 28) or flattened (B, 784); its plan
+    keeps no packed gradients, so its optimizer is the plain Adam kernel over the leading image parameters."""
 
-    SIDE = {"celeba": 64, "coco": 32, "mm": 50}
-    CHANNELS = {"celeba": 3, "coco": 3, "mm": 1}
-    FAMILIES = "CelebA, COCO and MultiMNIST"
+    SIDE = {"celeba": 64, "coco": 32, "mm": 50, "mnist": 28}
+    CHANNELS = {"celeba": 3, "coco": 3, "mm": 1, "mnist": 1}
+    FAMILIES = "CelebA, COCO and MultiMNIST have one, MNIST has one on its fp32 plan"
     IMAGE_PREFIXES = ("image_encoder.", "image_decoder.")
 
     def __init__(self, state: PlanState, batch: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  kl_lambda: float = 1e-3, lambda_x: float = 1.0, seed: int = 1234):
         if state.API not in self.SIDE:
-            raise MMVAEError("FusedImageStep: no image-only step for the '%s' family (%s have one)" % (state.API, self.FAMILIES))
+            raise MMVAEError("FusedImageStep: no image-only step for the '%s' family (%s)" % (state.API, self.FAMILIES))
+        if state.API == "mnist" and getattr(state, "precision", None) != "fp32":     # the baseline is the reference's fp32 model
+            raise MMVAEError("FusedImageStep: no image-only step for the 'mnist' family at precision %r (%s)"
+                             % (getattr(state, "precision", None), self.FAMILIES))
         super().__init__(state, batch, lr, betas, eps, seed)
         self.kl_lambda, self.lambda_x = kl_lambda, lambda_x
         self.enc_dropout = True
         self.side, self.channels = self.SIDE[state.API], self.CHANNELS[state.API]
         self.pixels = self.channels * self.side * self.side      # per image: the BCE is a mean over B * pixels
-        # the image half is one run at the head of the flat buffers in both families: the optimizer visits nothing else
+        self.flat_images = state.API == "mnist"
+        # the image half is one run at the head of the flat buffers in every family: the optimizer visits nothing else
         n_img = 0
         for name, shape, off in state.table:
             if name.startswith(self.IMAGE_PREFIXES):
@@ -726,7 +732,9 @@ class FusedImageStep(_FusedStepBase):
     def forward_backward(self, image, training=True, backward=True, eps=None, enc_mask1=None, enc_mask2=None, recon_image=None,
                          mu=None, logvar=None, _defer_unpack=False) -> StepOutputs:
         assert image.is_contiguous() and image.dtype == torch.float32
-        if tuple(image.shape) != (self.B, self.channels, self.side, self.side):
+        # (MNIST batches may come flattened, as the reference's x.view(-1, 784) takes them)
+        flat_ok = getattr(self, "flat_images", False) and tuple(image.shape) == (self.B, self.channels * self.side * self.side)
+        if tuple(image.shape) != (self.B, self.channels, self.side, self.side) and not flat_ok:
             raise MMVAEError("FusedImageStep: expected images of shape %s (got %s)"
                              % ((self.B, self.channels, self.side, self.side), tuple(image.shape)))
         io = _lib.ImageStepIO()
@@ -747,6 +755,12 @@ class FusedImageStep(_FusedStepBase):
     def __call__(self, image, **kw) -> StepOutputs:
         """backward + optimizer.step() in one pass over the image parameters: the packed-gradient Adam (see _call_packed)."""
         st = self.state
+        if st.API == "mnist":       # the fp32 plan wrote every gradient into ``grads``: plain Adam over the image half's run
+            out = self.forward_backward(image, True, True, **kw)
+            call("mmvae_adam_step", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n_image_params,
+                 ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, _stream())
+            self._after_update()
+            return out
         if self.separate_unpack:
             out = self.forward_backward(image, True, True, **kw)
             self.optimizer_step()

@@ -3,6 +3,8 @@
 #include "multimnist.h"
 #include "mmtext.h"
 #include "mnist.h"
+#include "mnist_plan.h"
+#include "mnist_strip.h"
 #include "celeba.h"
 #include "coco.h"
 #include "plan_base.h"
@@ -275,6 +277,37 @@ int mmvae_mnist_text_decoder_bwd(mmvae_mnist_t* p, void* ws, size_t wsb, const f
 }
 int mmvae_mnist_iw_score(mmvae_mnist_t* p, const float* z, const float* image, int B, int K, float* loglik_x, float* words, void* st) {
     return guarded([&] { return mnist_iw_score(p, z, image, B, K, loglik_x, words, S(st)); });
+}
+int mmvae_mnist_image_step(mmvae_mnist_t* p, const mmvae_image_step_io* io, int training, int do_backward, void* stream) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_mnist_image_step: null argument");
+        return mnist_image_step(p, *io, training, do_backward, S(stream));
+    });
+}
+int mmvae_mnist_strip_max_rows(void) { return MNIST_STRIP_MAX_ROWS; }
+int mmvae_mnist_strip_route(int rows) { return mnist_strip_route(rows); }
+int mmvae_mnist_lin_bn_act_fwd(int route, const float* x, int ldx, const float* w, const float* bias, const float* gamma, const float* beta,
+                               float* running_mean, float* running_var, long long* nbt, int rows, int N, int K, int training, float* r, float* a,
+                               float* mean_rstd, void* st) {
+    return guarded([&] {
+        StripFwdArgs f{};
+        f.x = x; f.ldx = ldx; f.w = w; f.bias = bias; f.gamma = gamma; f.beta = beta; f.running_mean = running_mean; f.running_var = running_var;
+        f.nbt = nbt; f.rows = rows; f.N = N; f.K = K; f.training = training; f.updates = 1; f.r = r; f.a = a; f.mr = reinterpret_cast<float2*>(mean_rstd);
+        return mnist_lin_bn_act_fwd(route, f, S(st));
+    });
+}
+int mmvae_mnist_lin_dgrad_bn_bwd(int route, const float* dy, int Nn, const float* w_next, const float* r, const float* mean_rstd, const float* gamma,
+                                 const float* beta, int rows, int N, float* d_r, float* dgamma, float* dbeta, void* st) {
+    return guarded([&] {
+        StripBwdArgs b{};
+        b.dy = dy; b.Nn = Nn; b.w_next = w_next; b.r = r; b.mr = reinterpret_cast<const float2*>(mean_rstd); b.gamma = gamma; b.beta = beta;
+        b.rows = rows; b.N = N; b.d_r = d_r; b.dgamma = dgamma; b.dbeta = dbeta;
+        return mnist_lin_dgrad_bn_bwd(route, b, S(st));
+    });
+}
+size_t mmvae_mnist_image_step_workspace_bytes(const mmvae_mnist_t* p) { return p ? mnist_image_step_workspace_bytes(p) : 0; }
+int mmvae_mnist_iw_score_image(mmvae_mnist_t* p, void*, size_t, const float* z, const float* image, int B, int K, float* loglik_x, void* st) {
+    return guarded([&] { return mnist_iw_score_image(p, z, image, B, K, loglik_x, S(st)); });
 }
 
 // ---- CelebA (celeba/model.py, celeba/train.py)

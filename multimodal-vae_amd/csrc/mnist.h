@@ -25,3 +25,9 @@ int mnist_text_decoder_bwd(MnistPlan*, void* ws, size_t wsb, const float* d_logp
 // log-softmax.  Reads the bound fp32 parameters and running statistics (either precision; no pack_weights, no workspace, no row
 // limit from the plan's batch); touches no plan state.
 int mnist_iw_score(MnistPlan*, const float* z, const float* image, int B, int K, float* loglik_x, float* words, hipStream_t);
+// image-only VAE (mnist/model.py:188-232, mnist/imageonly/train_imageonly.py:60-71,114-127): one pass over B rows on the fp32 plan
+// (a bf16 plan is refused), workspace mnist_image_step_workspace_bytes; and mnist_iw_score with the image decoder alone (no label
+// decoder, no words): loglik_x is bit for bit what mnist_iw_score writes there.
+int mnist_image_step(MnistPlan*, const mmvae_image_step_io&, int training, int do_backward, hipStream_t);
+size_t mnist_image_step_workspace_bytes(const MnistPlan*);
+int mnist_iw_score_image(MnistPlan*, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t);

@@ -243,6 +243,19 @@ int mnist_step(MnistPlan* Pp, const mmvae_mnist_step_io& io, int training, int d
     return plan_unpack(P, s, false);
 }
 
+// ================================================================== image-only VAE (mnist/model.py:188-232)
+// The baseline is the reference's fp32 model: only the fp32 plan carries it (mnist_f32.hip mnist_f32_image_step).
+size_t mnist_image_step_workspace_bytes(const MnistPlan* P) {
+    return P->f32 ? mnist_f32_image_step_workspace_bytes(*const_cast<MnistPlan*>(P)) : 0;
+}
+int mnist_image_step(MnistPlan* Pp, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
+    MMVAE_TRY(check_bound(Pp));
+    MMVAE_REQUIRE(Pp->f32, "mmvae_mnist_image_step: the image-only step runs on the fp32 plan only (this plan was created with bf16 precision)");
+    MMVAE_REQUIRE(io.enc_mask1 == nullptr && io.enc_mask2 == nullptr,
+                  "mmvae_mnist_image_step: the MNIST model has no Dropout (enc_mask1 / enc_mask2 must be NULL)");
+    return mnist_f32_image_step(*Pp, io, training, do_backward, s);
+}
+
 // ================================================================== granular modules (drop-in nn.Module forwards)
 // Each call works on B rows (one BatchNorm group) in the workspace it is handed; the backward must get the workspace
 // of its forward.  Parameter gradients accumulate into the bound `grads` (the caller zeroes them).

@@ -13,10 +13,18 @@
 // Losses, product of experts, reparametrisation, KL and Adam are the shared fp32 kernels of elementwise.hip.
 #include "mnist_plan.h"
 #include "gemm_f32.h"
+#include "mnist_strip.h"
 
 namespace {
 
 constexpr int TPBF = 256;
+// the switch "mnist_strip" when nobody set it (or set it to -1).  profiles/imageonly_mnist_bench.txt: the one-pass step with the strip
+// kernels 0.2255 against 0.2680 ms at B = 128 and 0.2917 against 0.3361 ms at B = 256 (spreads <= 0.0015 ms): on
+constexpr int MNIST_STRIP_DEFAULT = 1;
+inline bool strip_switch() {
+    const int k = mmvae_knob("mnist_strip", -1);              // 1 / 0: on / off; -1 (not set): the default
+    return (k < 0 ? MNIST_STRIP_DEFAULT : k) != 0;
+}
 
 // y[rows][N] = x[rows][K] W[N][K]^T + b
 int lin_fwd32(MnistPlan& P, const MlpLin& L, const float* x, int ldx, int rows, float* y, hipStream_t s) {
@@ -158,6 +166,34 @@ int bn_bwd32(MnistPlan& P, int bi, float* d, const float* x, int rows, int group
     a.dgamma = P.buf.grads + b.w_off; a.dbeta = P.buf.grads + b.b_off; a.training = 1;
     hipLaunchKernelGGL(bn1d_bwd32_kernel, dim3(ceil_div(b.C, 64)), dim3(64 * BN_RL), 0, s, a);
     return mmvae_check_launch("bn1d_bwd32");
+}
+
+// ------------------------------------------------------------------ column-strip fused layers (mnist_strip.h), one BatchNorm group
+// Linear L + BatchNorm bi + ReLU in one launch: r = x W^T + b, a = relu(bn(r)), mr = (mean, rstd)
+int strip_fwd32(MnistPlan& P, const MlpLin& L, int bi, const float* x, int ldx, int rows, int updates, int training, float* r, float* a,
+                float2* mr, hipStream_t s) {
+    const BnL& b = P.bn[bi];
+    StripFwdArgs f{};
+    f.x = x; f.ldx = ldx; f.w = P.buf.params + L.w_off; f.bias = P.buf.params + L.b_off;
+    f.gamma = P.buf.params + b.w_off; f.beta = P.buf.params + b.b_off;
+    f.running_mean = P.buf.bn_stats + b.stat_off; f.running_var = P.buf.bn_stats + b.stat_off + b.C; f.nbt = P.buf.bn_nbt + b.idx;
+    f.rows = rows; f.N = L.N; f.K = L.K; f.training = training; f.updates = updates; f.r = r; f.a = a; f.mr = mr;
+    return launch_lin_bn_act_fwd32(f, s);
+}
+// data gradient of Linear `next` + ReLU / BatchNorm bi backward in one launch: d_r, dgamma, dbeta of the layer below `next`
+int strip_bwd32(MnistPlan& P, const MlpLin& next, int bi, const float* dy, const float* r, const float2* mr, int rows, float* d_r, hipStream_t s) {
+    const BnL& b = P.bn[bi];
+    StripBwdArgs g{};
+    g.dy = dy; g.Nn = next.N; g.w_next = P.buf.params + next.w_off; g.r = r; g.mr = mr;
+    g.gamma = P.buf.params + b.w_off; g.beta = P.buf.params + b.b_off; g.rows = rows; g.N = next.K; g.d_r = d_r;
+    g.dgamma = P.buf.grads + b.w_off; g.dbeta = P.buf.grads + b.b_off;
+    return launch_lin_dgrad_bn_bwd32(g, s);
+}
+// the four fused layers need 16-byte aligned operands with rows of a multiple of 4 floats: every width of this model is one
+bool strip_fits(const MnistPlan& P, const float* image) {
+    return P.B <= MNIST_STRIP_MAX_ROWS && P.D % 4 == 0 && (reinterpret_cast<uintptr_t>(image) & 15) == 0 &&
+           (reinterpret_cast<uintptr_t>(P.buf.params) & 15) == 0 && P.ie[0].w_off % 4 == 0 && P.ie[1].w_off % 4 == 0 && P.id[0].w_off % 4 == 0 &&
+           P.id[1].w_off % 4 == 0;
 }
 
 // ------------------------------------------------------------------ label embedding (mnist/model.py:141)
@@ -348,6 +384,155 @@ int mnist_f32_step(MnistPlan& P, const mmvae_mnist_step_io& io, int training, in
     MMVAE_TRY(launch_latent3_bwd(lb, s));
     MMVAE_TRY(img_enc_bwd32(P, io.image, w.d_encout, s));
     return txt_enc_bwd32(P, io.label, w.d_txtout, s);
+}
+
+// ================================================================== the one-pass step of the image-only VAE
+// mnist/model.py:188-232 trained by mnist/imageonly/train_imageonly.py:60-71,114-127: zero_grad, ONE forward of B rows (image
+// encoder with one BatchNorm update, the one-expert latent block -- no product of experts, no 1e-8 --, image decoder with one
+// BatchNorm group, sigmoid + BCE) and its backward.  The launches are the module pieces above at groups = 1; the workspace is a
+// carve of its own with B rows of everything and nothing of the label half.  Nothing of text_encoder.* / text_decoder.* is read or
+// written: the prologue zeroes the whole flat gradient, so that half's gradient is exactly 0.
+namespace {
+void carve32_image(const MnistPlan& P, MnistPlan::W32& w, Workspace& ws) {
+    w = MnistPlan::W32{};
+    const size_t B = P.B, D = P.D;
+    const int bnc[4] = {400, 200, 200, 400};
+    char* z0 = ws.take<char>(0);
+    w.sums = ws.take<float>(16 * MMVAE_LOSS_SLOTS);
+    w.dz_img = ws.take<float>(B * D);
+    char* z1 = ws.take<char>(0);
+    w.zero_begin = z0; w.zero_bytes = (size_t)(z1 - z0);
+    for (int i = 0; i < 4; ++i) w.mr[i] = ws.take<float2>(bnc[i]);
+    w.r_ie[0] = ws.take<float>(B * 400); w.a_ie[0] = ws.take<float>(B * 400);
+    w.r_ie[1] = ws.take<float>(B * 200); w.a_ie[1] = ws.take<float>(B * 200);
+    w.encout = ws.take<float>(B * 2 * D);
+    w.eps = ws.take<float>(B * D); w.mu = ws.take<float>(B * D); w.logvar = ws.take<float>(B * D);
+    w.z = ws.take<float>(B * D); w.z_bf = ws.take<bf16>(B * P.ldz);
+    w.lat_scratch = ws.take<float>(launch_latent1_scratch_floats((int)B, (int)D));
+    w.r_id[0] = ws.take<float>(B * 200); w.a_id[0] = ws.take<float>(B * 200);
+    w.r_id[1] = ws.take<float>(B * 400); w.a_id[1] = ws.take<float>(B * 400);
+    w.logits = ws.take<float>(B * 784); w.dlogit = ws.take<float>(B * 784);
+    w.d_id[0] = ws.take<float>(B * 200); w.d_id[1] = ws.take<float>(B * 400);
+    w.d_encout = ws.take<float>(B * 2 * D);
+    w.d_ie[0] = ws.take<float>(B * 400); w.d_ie[1] = ws.take<float>(B * 200);
+}
+}  // namespace
+
+size_t mnist_f32_image_step_workspace_bytes(MnistPlan& P) {
+    MnistPlan::W32 w;
+    Workspace ws(nullptr, 0);
+    carve32_image(P, w, ws);
+    return ws.used();
+}
+
+int mnist_f32_image_step(MnistPlan& P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
+    const size_t need = mnist_f32_image_step_workspace_bytes(P);
+    MMVAE_REQUIRE(io.ws != nullptr && io.ws_bytes >= need, "mnist image step: workspace too small (%zu < %zu)", io.ws_bytes, need);
+    MMVAE_REQUIRE(io.image && io.sums, "mnist image step: image/sums must be given");
+    const int B = P.B, D = P.D;
+    MMVAE_REQUIRE(!training || B > 1, "Expected more than 1 value per channel when training");
+    Workspace wsp(io.ws, io.ws_bytes);
+    MnistPlan::W32& w = P.w32;
+    carve32_image(P, w, wsp);
+    P.dec_skip_mask = 0;
+    const float* eps = io.eps;
+    StepBeginArgs sb{};
+    sb.zero_ptr[0] = w.zero_begin; sb.zero_bytes[0] = w.zero_bytes;
+    if (do_backward) { sb.zero_ptr[1] = P.buf.grads; sb.zero_bytes[1] = (size_t)(P.nparams / 4) * 16; }
+    sb.seed = io.seed; sb.step = io.step_counter;
+    if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B * D; eps = w.eps; }
+    MMVAE_TRY(launch_step_begin(sb, s));
+    if (do_backward && P.nparams % 4 != 0)
+        MMVAE_TRY(launch_fill_zero(P.buf.grads + (P.nparams / 4) * 4, (size_t)(P.nparams % 4) * sizeof(float), s));
+    // switch "mnist_strip" (mmvae_debug_set): each Linear + BatchNorm1d + ReLU is one column-strip launch (mnist_strip.h), forward and
+    // backward, where the batch fits a workgroup (MNIST_STRIP_MAX_ROWS); above it, or at 0, gemm_f32 + the BatchNorm kernels.
+    const bool strip = strip_switch() && strip_fits(P, io.image);
+    if (strip) {
+        MMVAE_TRY(strip_fwd32(P, P.ie[0], 0, io.image, 784, B, 1, training, w.r_ie[0], w.a_ie[0], w.mr[0], s));
+        MMVAE_TRY(strip_fwd32(P, P.ie[1], 1, w.a_ie[0], 400, B, 1, training, w.r_ie[1], w.a_ie[1], w.mr[1], s));
+        MMVAE_TRY(lin_fwd32(P, P.ie[2], w.a_ie[1], 200, B, w.encout, s));
+    } else {
+        MMVAE_TRY(img_enc_fwd32(P, io.image, 1, training, w.encout, s));
+    }
+    Latent1Args la{};
+    la.B = B; la.D = D; la.enc_out = w.encout; la.eps = eps;
+    la.mu = io.mu ? io.mu : w.mu; la.logvar = io.logvar ? io.logvar : w.logvar;
+    la.z_f32 = w.z; la.z_bf = w.z_bf; la.ldz = P.ldz; la.kl_sum = w.sums + 8; la.training = training;
+    la.scratch = w.lat_scratch;
+    MMVAE_TRY(launch_latent1_fwd(la, s));
+    if (strip) {
+        MMVAE_TRY(strip_fwd32(P, P.id[0], 2, w.z, D, B, 1, training, w.r_id[0], w.a_id[0], w.mr[2], s));
+        MMVAE_TRY(strip_fwd32(P, P.id[1], 3, w.a_id[0], 200, B, 1, training, w.r_id[1], w.a_id[1], w.mr[3], s));
+        MMVAE_TRY(lin_fwd32(P, P.id[2], w.a_id[1], 400, B, w.logits, s));
+    } else {
+        MMVAE_TRY(img_dec_fwd32(P, w.z, 1, training, w.logits, s));
+    }
+    BceArgs bc{};
+    bc.logits = w.logits; bc.ldl = 1; bc.target = io.image; bc.G = 1; bc.B = B; bc.C = 1; bc.H = 28; bc.W = 28;
+    bc.recon = io.recon_image; bc.dlogit = do_backward ? w.dlogit : nullptr; bc.loss_sum = w.sums;
+    bc.coef[0] = io.lambda_x / (float)(B * 784);
+    MMVAE_TRY(launch_sigmoid_bce(bc, s));
+    hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, s, w.sums, io.sums);
+    MMVAE_TRY(mmvae_check_launch("sum_slots"));
+    if (!do_backward) return MMVAE_OK;
+    // =============================== backward ===============================
+    if (strip) {         // img_dec_bwd32 with lin_dgrad32 + bn_bwd32 of the two BatchNorm layers as one launch each
+        MMVAE_TRY(launch_colsum_f32(w.dlogit, B, 784, P.buf.grads + P.id[2].b_off, s));
+        MMVAE_TRY(lin_wgrad32(P, P.id[2], w.dlogit, w.a_id[1], 400, B, s));
+        MMVAE_TRY(strip_bwd32(P, P.id[2], 3, w.dlogit, w.r_id[1], w.mr[3], B, w.d_id[1], s));
+        MMVAE_TRY(lin_wgrad32(P, P.id[1], w.d_id[1], w.a_id[0], 200, B, s));
+        MMVAE_TRY(strip_bwd32(P, P.id[1], 2, w.d_id[1], w.r_id[0], w.mr[2], B, w.d_id[0], s));
+        MMVAE_TRY(lin_wgrad32(P, P.id[0], w.d_id[0], w.z, D, B, s));
+        MMVAE_TRY(lin_dgrad32(P, P.id[0], w.d_id[0], B, w.dz_img, s));
+    } else {
+        MMVAE_TRY(img_dec_bwd32(P, w.z, w.dlogit, 1, w.dz_img, s));
+    }
+    Latent1BwdF32Args lb{};
+    lb.B = B; lb.D = D; lb.mu = la.mu; lb.logvar = la.logvar; lb.eps = eps; lb.dz = w.dz_img; lb.training = training;
+    lb.kl_coef = io.kl_lambda / (float)B; lb.d_enc_out = w.d_encout; lb.ld = 2 * D;
+    MMVAE_TRY(launch_latent1_bwd_f32(lb, s));
+    if (!strip) return img_enc_bwd32(P, io.image, w.d_encout, s);      // (forms the gradient of net.6's bias itself)
+    MMVAE_TRY(launch_colsum_f32(w.d_encout, B, 2 * D, P.buf.grads + P.ie[2].b_off, s));
+    MMVAE_TRY(lin_wgrad32(P, P.ie[2], w.d_encout, w.a_ie[1], 200, B, s));
+    MMVAE_TRY(strip_bwd32(P, P.ie[2], 1, w.d_encout, w.r_ie[1], w.mr[1], B, w.d_ie[1], s));
+    MMVAE_TRY(lin_wgrad32(P, P.ie[1], w.d_ie[1], w.a_ie[0], 400, B, s));
+    MMVAE_TRY(strip_bwd32(P, P.ie[1], 0, w.d_ie[1], w.r_ie[0], w.mr[0], B, w.d_ie[0], s));
+    return lin_wgrad32(P, P.ie[0], w.d_ie[0], io.image, 784, B, s);
+}
+
+// ---------------------------------------------------------------- one fused layer on plain pointers (test / measurement aid)
+// route 1: the strip kernel; route 0: the launches it replaces (gemm_f32 + bn1d_fwd32_kernel, gemm_f32 + bn1d_bwd32_kernel)
+int mnist_strip_route(int rows) { return strip_switch() && rows <= MNIST_STRIP_MAX_ROWS ? 1 : 0; }
+int mnist_lin_bn_act_fwd(int route, const StripFwdArgs& f, hipStream_t s) {
+    if (route < 0) route = mnist_strip_route(f.rows);
+    if (route == 1) return launch_lin_bn_act_fwd32(f, s);
+    MMVAE_REQUIRE(f.x && f.w && f.bias && f.gamma && f.beta && f.running_mean && f.running_var && f.nbt && f.r && f.a && f.mr && f.rows >= 1,
+                  "mnist_lin_bn_act_fwd: null argument");
+    MMVAE_REQUIRE(!f.training || f.rows > 1, "Expected more than 1 value per channel when training");
+    F32Gemm g{};
+    g.A = f.x; g.a_rs = f.ldx; g.a_cs = 1; g.B = f.w; g.b_rs = 1; g.b_cs = f.K;
+    g.M = f.rows; g.N = f.N; g.K = f.K; g.C = f.r; g.ldc = f.N; g.bias = f.bias;
+    MMVAE_TRY(gemm_f32(g, s));
+    Bn32 a{};
+    a.x = f.r; a.y = f.a; a.C = f.N; a.G = 1; a.rpg = f.rows; a.gamma = f.gamma; a.beta = f.beta;
+    a.running_mean = f.running_mean; a.running_var = f.running_var; a.nbt = f.nbt; a.mr = f.mr;
+    a.updates = f.updates; a.skip_mask = 0u; a.training = f.training; a.relu = 1;
+    hipLaunchKernelGGL(bn1d_fwd32_kernel, dim3(ceil_div(f.N, 64)), dim3(64 * BN_RL), 0, s, a);
+    return mmvae_check_launch("bn1d_fwd32");
+}
+int mnist_lin_dgrad_bn_bwd(int route, const StripBwdArgs& b, hipStream_t s) {
+    if (route < 0) route = mnist_strip_route(b.rows);
+    if (route == 1) return launch_lin_dgrad_bn_bwd32(b, s);
+    MMVAE_REQUIRE(b.dy && b.w_next && b.r && b.mr && b.gamma && b.beta && b.d_r && b.dgamma && b.dbeta && b.rows >= 1, "mnist_lin_dgrad_bn_bwd: null argument");
+    F32Gemm g{};
+    g.A = b.dy; g.a_rs = b.Nn; g.a_cs = 1; g.B = b.w_next; g.b_rs = b.N; g.b_cs = 1;
+    g.M = b.rows; g.N = b.N; g.K = b.Nn; g.C = b.d_r; g.ldc = b.N;
+    MMVAE_TRY(gemm_f32(g, s));
+    BnB32 a{};
+    a.d = b.d_r; a.x = b.r; a.C = b.N; a.G = 1; a.rpg = b.rows; a.gamma = b.gamma; a.beta = b.beta; a.mr = b.mr;
+    a.dgamma = b.dgamma; a.dbeta = b.dbeta; a.training = 1;
+    hipLaunchKernelGGL(bn1d_bwd32_kernel, dim3(ceil_div(b.N, 64)), dim3(64 * BN_RL), 0, s, a);
+    return mmvae_check_launch("bn1d_bwd32");
 }
 
 // ---------------------------------------------------------------- granular modules (B rows, one BatchNorm group)

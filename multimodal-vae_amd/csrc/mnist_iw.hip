@@ -104,6 +104,9 @@ __device__ __forceinline__ void bn_relu_store(const MnistIwArgs& a, const f32x4 
         }
 }
 
+// TEXT = false (mnist_iw_score_image): the image decoder alone -- no 14th tile in layer 1, no text tail, `words` is not touched.  The image
+// half runs the same instructions on the same operands either way: loglik_x is the same bits.
+template <bool TEXT>
 __global__ __launch_bounds__(IW_TPB) void mnist_iw_score_kernel(const MnistIwArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = a.D, ZS = z_stride(D);
@@ -125,7 +128,7 @@ __global__ __launch_bounds__(IW_TPB) void mnist_iw_score_kernel(const MnistIwArg
     {
         const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.params + a.w[0]), 0, H1 * D * 4, 0x00020000);
         const __amdgpu_buffer_rsrc_t tr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.params + a.tw[0]), 0, NCLS * D * 4, 0x00020000);
-        for (int nt = wave; nt < 14; nt += IW_WAVES) {
+        for (int nt = wave; nt < (TEXT ? 14 : 13); nt += IW_WAVES) {
             f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
             if (nt < 13) {
                 tile_gemm<0>(zs, ZS, wr, H1, D, nt * 16, fr, fq, acc);
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(IW_TPB) void mnist_iw_score_kernel(const MnistIwArg
     __syncthreads();
 
     // ---- text tail (the last wave has the fewest tiles of layer 2): Linear(10,10) + log_softmax, one lane per row
-    if (wave == IW_WAVES - 1 && lane < IW_R && row0 + lane < a.rows) {
+    if (TEXT && wave == IW_WAVES - 1 && lane < IW_R && row0 + lane < a.rows) {
         const float* W = a.params + a.tw[1];
         const float* bb = a.params + a.tb[1];
         float lg[NCLS], mx = -3.0e38f;
@@ -226,10 +229,10 @@ size_t iw_lds_bytes(int D) { return sizeof(float) * (size_t)(IW_R * (z_stride(D)
 
 }  // namespace
 
-int mnist_iw_score(MnistPlan* Pp, const float* z, const float* image, int B, int K, float* loglik_x, float* words, hipStream_t s) {
+static int iw_score(MnistPlan* Pp, const float* z, const float* image, int B, int K, float* loglik_x, float* words, bool text, hipStream_t s) {
     MMVAE_TRY(check_bound(Pp));
     MnistPlan& P = *Pp;
-    MMVAE_REQUIRE(z && image && loglik_x && words, "mnist_iw_score: null argument");
+    MMVAE_REQUIRE(z && image && loglik_x && (words || !text), "mnist_iw_score: null argument");
     const long long rows = (long long)B * K;
     // row, pixel and tile indices are 32-bit in the kernel (rows + IW_R and B * 784 must fit)
     MMVAE_REQUIRE(B >= 1 && K >= 1 && rows <= 0x7FFFFFFFll - IW_R && (long long)B * NPIX <= 0x7FFFFFFFll,
@@ -246,9 +249,21 @@ int mnist_iw_score(MnistPlan* Pp, const float* z, const float* image, int B, int
     MMVAE_REQUIRE((reinterpret_cast<uintptr_t>(a.params) & 15) == 0 && a.w[0] % 4 == 0 && a.w[1] % 4 == 0 && a.w[2] % 4 == 0 &&
                   a.tw[0] % 4 == 0 && P.D % 4 == 0, "mnist_iw_score: parameter buffer is not 16-byte aligned");
     const size_t lds = iw_lds_bytes(P.D);
-    static std::atomic<unsigned> attr_set{0};
-    if (mmvae_first_use_on_device(attr_set))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mnist_iw_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)iw_lds_bytes(124));
-    MMVAE_LAUNCH(mnist_iw_score_kernel, dim3((unsigned)((rows + IW_R - 1) / IW_R)), dim3(IW_TPB), lds, s, a);
-    return mmvae_check_launch("mnist_iw_score");
+    static std::atomic<unsigned> attr_set{0}, attr_set_image{0};
+    if (text) {
+        if (mmvae_first_use_on_device(attr_set))
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mnist_iw_score_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)iw_lds_bytes(124));
+        MMVAE_LAUNCH(mnist_iw_score_kernel<true>, dim3((unsigned)((rows + IW_R - 1) / IW_R)), dim3(IW_TPB), lds, s, a);
+        return mmvae_check_launch("mnist_iw_score");
+    }
+    if (mmvae_first_use_on_device(attr_set_image))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mnist_iw_score_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)iw_lds_bytes(124));
+    MMVAE_LAUNCH(mnist_iw_score_kernel<false>, dim3((unsigned)((rows + IW_R - 1) / IW_R)), dim3(IW_TPB), lds, s, a);
+    return mmvae_check_launch("mnist_iw_score_image");
+}
+int mnist_iw_score(MnistPlan* P, const float* z, const float* image, int B, int K, float* loglik_x, float* words, hipStream_t s) {
+    return iw_score(P, z, image, B, K, loglik_x, words, true, s);
+}
+int mnist_iw_score_image(MnistPlan* P, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t s) {
+    return iw_score(P, z, image, B, K, loglik_x, nullptr, false, s);
 }

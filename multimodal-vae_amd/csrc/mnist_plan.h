@@ -32,6 +32,7 @@ struct MnistPlan : PlanBase {
         float *r_id[2], *a_id[2], *logits, *dlogit;
         float *r_td, *a_td, *tlogits, *words, *dtl;
         float *d_id[2], *d_td, *d_encout, *d_txtout, *d_ie[2], *d_te;
+        float* lat_scratch;                              // one-pass carve only: the latent1 block's partial sums
     } w32;
 };
 
@@ -39,6 +40,16 @@ struct MnistPlan : PlanBase {
 // fp32 path entry points (mnist_f32.hip); same contracts as the public functions of mnist.h
 size_t mnist_f32_workspace_bytes(MnistPlan& P);
 int mnist_f32_step(MnistPlan& P, const mmvae_mnist_step_io& io, int training, int do_backward, hipStream_t s);
+// image-only VAE (mnist/model.py:188-232): ONE pass over B rows in a carve of its own; the label half is not launched
+size_t mnist_f32_image_step_workspace_bytes(MnistPlan& P);
+int mnist_f32_image_step(MnistPlan& P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s);
+// one Linear + BatchNorm1d + ReLU layer / its backward on plain pointers (mnist_strip.h argument blocks): route 1 the column-strip kernel,
+// 0 the launches it replaces, -1 what mnist_f32_image_step runs at that row count (mnist_strip_route: the switch and the row cap)
+struct StripFwdArgs;
+struct StripBwdArgs;
+int mnist_strip_route(int rows);
+int mnist_lin_bn_act_fwd(int route, const StripFwdArgs& f, hipStream_t s);
+int mnist_lin_dgrad_bn_bwd(int route, const StripBwdArgs& b, hipStream_t s);
 int mnist_f32_image_encoder_fwd(MnistPlan& P, void* ws, size_t wsb, const float* image, int training, float* out, hipStream_t s);
 int mnist_f32_image_encoder_bwd(MnistPlan& P, void* ws, size_t wsb, const float* d_out, hipStream_t s);
 int mnist_f32_image_decoder_fwd(MnistPlan& P, void* ws, size_t wsb, const float* z, int training, float* recon, hipStream_t s);

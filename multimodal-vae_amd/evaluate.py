@@ -119,6 +119,35 @@ def compute_nll_mnist(model, loader, image_only=False, text_only=False, n_sample
 
 
 @torch.no_grad()
+def compute_nll_mnist_imageonly(model, loader, n_samples=1, use_cuda=True, verbose=False):
+    """-> image NLL per sample of a ``mnist.VAE``, mnist/imageonly/loglikelihood_imageonly.py:17-51: the eval-mode encoder's
+    (mu, logvar), ONE set of ``n_samples`` standard-normal draws shared by the rows of a batch (the reference's behaviour, kept),
+    the summed BCE of every decoded particle, averaged over the particles and divided by the number of examples."""
+    from .mnist import _BCEMeanFn as _BCE
+    model.eval()
+    test_nll, n_seen = 0.0, 0
+    for image, _ in loader:
+        if use_cuda:
+            image = image.cuda()
+        image = image.float().reshape(-1, 784)
+        _, mu, logvar = model(image)
+        batch_size, n_latents = mu.size(0), mu.size(1)
+        sample = torch.randn(n_samples, n_latents)                # drawn on the host like the reference (:29)
+        if use_cuda:
+            sample = sample.cuda()
+        z = sample.unsqueeze(0) * logvar.mul(0.5).exp().unsqueeze(1) + mu.unsqueeze(1)      # (B, n_samples, D)
+        nll = 0.0
+        for i in range(n_samples):
+            recon_image = model.decode(z[:, i].contiguous())
+            nll += float(_BCE.apply(recon_image.reshape(batch_size, -1), image)) * image.numel()
+        test_nll += nll / n_samples
+        n_seen += batch_size
+        if verbose:
+            print('Evaluating: [{}/{}]'.format(n_seen, len(loader) * batch_size))
+    return test_nll / max(n_seen, 1)
+
+
+@torch.no_grad()
 def test_mnist(model, loader, use_cuda=True, verbose=True):
     """-> accuracy of the label predicted from the image alone, mnist/test.py:18-36."""
     model.eval()
@@ -295,6 +324,14 @@ def _mmtext_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
     lx[:rows].zero_()
 
 
+def _mnist_image_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
+    """The scoring call of a ``mnist.VAE``: mmvae_mnist_iw_score_image (the fused kernel without the label decoder); the words of its
+    one dummy text position are 0."""
+    from ._lib import ptr
+    _iw_call("mmvae_mnist_iw_score_image", st.plan(1), None, 0, ptr(z), ptr(image), nr, nk, ptr(lx), stream)   # any bound plan: no row limit
+    words[:rows].zero_()
+
+
 def _image_score(api):
     """The scoring call of an ImageVAE: mmvae_<family>_iw_score_image (decoder body + scoring tail, no second decoder); the words
     of its one dummy text position are 0."""
@@ -343,6 +380,7 @@ _FAMILIES = {
                          lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), float_text=True, text_only=True),
     "multimnist_image": _Family("multimnist", 1, 1, (1, 50, 50), IW_ROWS, _image_score("mm"),
                                 lambda st, rows: _iw_call("mmvae_mm_iw_workspace_bytes", st.plan(rows)), image_only=True),
+    "mnist_image": _Family("mnist", 1, 1, (784,), IW_ROWS_MNIST, _mnist_image_score, lambda st, rows: 0, image_only=True),
     # the MultiMNIST TextVAE: the text decoder alone on a plan of its own; its "image" is one dummy pixel
     "multimnist_text": _Family("multimnist", 4, 12, (1,), IW_ROWS, _mmtext_score,
                                lambda st, rows: st.module_workspace_bytes(rows), text_only=True),
@@ -366,6 +404,9 @@ def _family(model):
     from .multimnist import ImageVAE as MultimnistImageVAE
     if isinstance(model, MultimnistImageVAE):
         return _FAMILIES["multimnist_image"]
+    from .mnist import VAE as MnistImageVAE
+    if isinstance(model, MnistImageVAE):
+        return _FAMILIES["mnist_image"]
     if isinstance(model, (CelebaImageVAE, CocoImageVAE)):
         return _FAMILIES["celeba_image" if isinstance(model, CelebaImageVAE) else "coco_image"]
     return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else
@@ -514,7 +555,7 @@ def _proposal(model, image, text, posterior):
     if fam.image_only:          # q(z|x) of the encoder itself: an ImageVAE has no experts
         if posterior != "image":
             raise ValueError("an ImageVAE has the image posterior alone: posterior must be \"image\" (got %r)" % (posterior,))
-        return model.encoder(image)
+        return model.encode(image) if fam.name == "mnist" else model.encoder(image)      # (mnist.VAE's encoder is the bare Sequential)
     if fam.name == "celeba":
         second = (lambda t: model.attrs_encoder(t.float()))        # the (B,18) attributes as float
     else:
@@ -632,9 +673,11 @@ def sample_textonly(vae, n_samples=64, text=None):
 
 @torch.no_grad()
 def sample_imageonly(vae, n_samples=64, image=None):
-    """``sample`` for a multimnist ``ImageVAE``: image samples (n,1,50,50), from the prior or from q(z|x) of ``image`` (1,1,50,50)."""
+    """``sample`` for a multimnist ``ImageVAE``: image samples (n,1,50,50), from the prior or from q(z|x) of ``image`` (1,1,50,50); for
+    a ``mnist.VAE`` (mnist/imageonly/sample_imageonly.py:58-83) samples (n,1,28,28), ``image`` (1,784)."""
     vae.eval()
     dev = next(vae.parameters()).device
+    side = 28 if _family(vae).name == "mnist" else 50
     if image is None:
         mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
     else:
@@ -642,7 +685,7 @@ def sample_imageonly(vae, n_samples=64, image=None):
         std = logvar.mul(0.5).exp()
     z = torch.randn(n_samples, vae.n_latents).to(dev)
     z = z * std.expand_as(z) + mu.expand_as(z)
-    return vae.decode(z.contiguous()).cpu().view(n_samples, 1, 50, 50)
+    return vae.decode(z.contiguous()).cpu().view(n_samples, 1, side, side)
 
 
 @torch.no_grad()
@@ -815,7 +858,7 @@ def latent_mmd(vae, loader, seed=0):
 @torch.no_grad()
 def manifold(vae, loader, pca_only=False, perplexity=40, n_iter=300, seed=0):
     """mnist/manifold.py: encodes every (image, label) batch of ``loader`` with ``gen_latents`` in eval mode (z = mu of the joint
-    posterior) and reduces the latents to 2-D: ``tsne.pca(., 2)`` with ``pca_only``, else ``tsne.tsne`` (exact t-SNE on the GPU,
+    posterior; for a ``mnist.VAE``, mnist/imageonly/manifold_imageonly.py, the encoder's ``mu`` of the image) and reduces the latents to 2-D: ``tsne.pca(., 2)`` with ``pca_only``, else ``tsne.tsne`` (exact t-SNE on the GPU,
     perplexity 40 and 300 iterations as the reference asks of sklearn) after ``pca(., 50)`` when n_latents > 50.  Returns CPU tensors
     {"latents" (N, n_latents), "labels" (N,), "embedding" (N, 2), "kl_trace" (n_iter,) or None with ``pca_only``}: the KL of every
     iteration, before its update."""
@@ -824,7 +867,8 @@ def manifold(vae, loader, pca_only=False, perplexity=40, n_iter=300, seed=0):
     dev = next(vae.parameters()).device
     zs, labels = [], []
     for image, text in loader:
-        z = vae.gen_latents(image.to(dev).float().reshape(-1, 784), text.to(dev))
+        x = image.to(dev).float().reshape(-1, 784)
+        z = vae.encode(x)[0] if _family(vae).image_only else vae.gen_latents(x, text.to(dev))
         zs.append(z.float().clone())
         labels.append(text.cpu())
     latents, labels = torch.cat(zs).contiguous(), torch.cat(labels)
@@ -872,7 +916,12 @@ def _parser():
     ps = sub.add_parser("sample", help="multimnist/sample.py")
     ps.add_argument('model_path', type=str, help='path to trained model file.')
     ps.add_argument('--n_samples', type=int, default=64, help='Number of images and texts to sample.')
-    ps.add_argument('--condition_on_image', type=str, default=None, help='a .pt file holding a (50,50) uint8 or float image')
+    ps.add_argument('--dataset', choices=('multimnist', 'mnist'), default='multimnist',
+                    help='mnist: a checkpoint of train_imageonly --dataset mnist (mnist/imageonly/sample_imageonly.py)')
+    ps.add_argument('--condition_on_image', type=str, default=None,
+                    help='a .pt file holding a (50,50) uint8 or float image; mnist: a digit LABEL, an image of which is drawn from --data')
+    ps.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='mnist: (uint8 images (N,28,28), int64 labels (N,))')
+    ps.add_argument('--seed', type=int, default=0, help='mnist: seed of the choice of the image')
     ps.add_argument('--condition_on_text', type=str, default=None, help='a digit string of at most 4 characters')
     ps.add_argument('--out', type=str, default='./results')
     # multimnist/loglikelihood.py's flags and defaults, plus the importance-sampled bounds (log_marginal / marginal_table)
@@ -934,9 +983,10 @@ def _parser():
     # multimnist/sample.py's flags for a checkpoint of train_coco; the captions are decoded through a word table
     pt = sub.add_parser("test_imageonly", help="celeba/test_imageonly.py: eval-mode loss (kl_lambda = 1) of a train_imageonly checkpoint")
     pt.add_argument('model_path', type=str)
-    pt.add_argument('--dataset', choices=('celeba', 'coco', 'multimnist'), default='celeba')
+    pt.add_argument('--dataset', choices=('celeba', 'coco', 'multimnist', 'mnist'), default='celeba')
     pt.add_argument('--data', type=str, default='',
-                    help='celeba: FILE.pt of make_celeba; coco: DIR with images_u8.pt; multimnist: root of processed/test.pt')
+                    help='celeba: FILE.pt of make_celeba; coco: DIR with images_u8.pt; multimnist: root of processed/test.pt; '
+                         'mnist: FILE.pt of (uint8 images (N,28,28), int64 labels (N,)); its loss is (BCE + KLD / 784) / B')
     pt.add_argument('--synthetic', type=int, default=0, metavar='N')
     pt.add_argument('--batch_size', type=int, default=128, metavar='N')
     pt.add_argument('--seed', type=int, default=0)
@@ -1008,7 +1058,7 @@ def _parser():
     pm.add_argument('--json', type=str, default=None, help='write the terms to this file')
     # mnist/manifold.py: the test set's latents reduced to 2-D by PCA or by exact t-SNE on the GPU
     pf = sub.add_parser("manifold", help="mnist/manifold.py: latents of the test set, PCA or PCA + t-SNE to 2-D")
-    pf.add_argument('model_path', type=str, help='path to trained model file (mnist family)')
+    pf.add_argument('model_path', type=str, help='path to trained model file (mnist family; a train_imageonly checkpoint embeds the encoder\'s mu)')
     pf.add_argument('--pca_only', action='store_true', default=False)
     pf.add_argument('--perplexity', type=float, default=40.0)
     pf.add_argument('--n_iter', type=int, default=300)
@@ -1082,6 +1132,8 @@ def _manifold_main(args):
         raise ValueError("manifold: need uint8 images (N,28,28) and N labels (got %s %s, %s)" % (x.dtype, tuple(x.shape), tuple(t.shape)))
     x, t = x.float().div_(255.0).view(-1, 784), t.long()          # transforms.ToTensor() + view(-1, 784)
     loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
+    if is_imageonly_checkpoint(args.model_path):                  # a checkpoint of train_imageonly --dataset mnist
+        from .mnist import load_checkpoint_imageonly as load_checkpoint
     vae = load_checkpoint(args.model_path, use_cuda=True)
     out = manifold(vae, loader, pca_only=args.pca_only, perplexity=args.perplexity, n_iter=args.n_iter, seed=args.seed)
     os.makedirs(args.out, exist_ok=True)
@@ -1109,6 +1161,8 @@ def _manifold_main(args):
 def _latent_viz_main(args):
     import os
     from .mnist import load_checkpoint
+    if is_imageonly_checkpoint(args.model_path):
+        raise SystemExit("latent_viz: an image-only checkpoint is not supported (the grid needs a padded-latent variant of mnist.VAE)")
     vae = load_checkpoint(args.model_path, use_cuda=True)
     canvas, digits = latent_viz(vae)
     os.makedirs(args.out, exist_ok=True)
@@ -1395,7 +1449,19 @@ def _test_imageonly_main(args):
     """`test_imageonly`: whole batches only (the plan takes a fixed batch size); a trailing partial batch is dropped."""
     import os
     from . import data as D
-    if args.dataset == "multimnist":
+    kl_lambda = 1.0
+    if args.dataset == "mnist":
+        from .mnist import load_checkpoint_imageonly
+        from .make_multimnist import load_mnist_pt
+        if args.synthetic > 0:
+            x, _ = D.synthetic_mnist(args.synthetic, seed=args.seed)
+        elif args.data:
+            x, _ = load_mnist_pt(args.data)
+        else:
+            raise SystemExit("test_imageonly: give --data or --synthetic N")
+        x = x.view(-1, 1, 28, 28)
+        kl_lambda = 1.0 / 784                                     # the reference's own loss: (BCE + KLD / 784) / B
+    elif args.dataset == "multimnist":
         from .multimnist import load_checkpoint_imageonly
         if args.synthetic > 0:
             x, _ = D.synthetic_multimnist(args.synthetic, seed=args.seed)
@@ -1424,7 +1490,7 @@ def _test_imageonly_main(args):
     bs = min(args.batch_size, x.shape[0])
     x = x.float().div_(255.0)
     loader = [(x[i:i + bs], None) for i in range(0, x.shape[0] - bs + 1, bs)]
-    return test_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader)
+    return test_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, kl_lambda=kl_lambda)
 
 
 def _test_textonly_main(args):
@@ -1473,8 +1539,8 @@ def _loglik_main(args):
             x, t = D.synthetic_mnist(args.synthetic, seed=args.seed)
         else:
             x, t = torch.load(args.data, weights_only=False)      # torchvision's processed/test.pt
-        x = x.float().div_(255.0).view(-1, 784)                   # transforms.ToTensor() + view(-1, 784)
-        t = t.long()
+        x = torch.as_tensor(x).float().div_(255.0).view(-1, 784)  # transforms.ToTensor() + view(-1, 784)
+        t = torch.as_tensor(t).long()
     else:
         from .train import load_checkpoint
         if args.synthetic > 0:
@@ -1487,12 +1553,40 @@ def _loglik_main(args):
     if args.dataset == "multimnist" and is_textonly_checkpoint(args.model_path):      # a checkpoint of train_textonly_multimnist: log p(y) alone
         from .multimnist import load_checkpoint_textonly
         return _report(load_checkpoint_textonly(args.model_path, use_cuda=True), loader, ("text",), args, "Text")
+    if args.dataset == "mnist" and is_imageonly_checkpoint(args.model_path):          # a checkpoint of train_imageonly --dataset mnist
+        from .mnist import load_checkpoint_imageonly
+        return _report(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Text")
     if args.dataset == "multimnist" and is_imageonly_checkpoint(args.model_path):     # a checkpoint of train_imageonly: log p(x) alone
         from .multimnist import load_checkpoint_imageonly
         return _report(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Text")
     vae = load_checkpoint(args.model_path, use_cuda=True)
     posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
     return _report(vae, loader, posts, args, "Text")
+
+
+def _sample_mnist_main(args):
+    """`sample --dataset mnist` (mnist/imageonly/sample_imageonly.py): 64 images from the prior, or from q(z|x) of a test image of the
+    digit ``--condition_on_image LABEL`` chosen from ``--data``.  Writes sample_image.pt (n,1,28,28)."""
+    import os
+    from .mnist import load_checkpoint_imageonly
+    if not is_imageonly_checkpoint(args.model_path):
+        raise SystemExit("sample --dataset mnist: an image-only checkpoint (train_imageonly --dataset mnist) expected")
+    image = None
+    if args.condition_on_image is not None:
+        from .make_multimnist import load_mnist_pt
+        label = int(args.condition_on_image)
+        if not args.data:
+            raise SystemExit("sample --dataset mnist: --condition_on_image LABEL needs --data FILE.pt")
+        x, t = load_mnist_pt(args.data)
+        idx = (t == label).nonzero().flatten()
+        if idx.numel() == 0:
+            raise SystemExit("sample --dataset mnist: --data has no image of the digit %d" % label)
+        pick = idx[int(torch.randint(0, idx.numel(), (1,), generator=torch.Generator().manual_seed(args.seed)))]
+        image = x[pick].float().div(255.0).view(1, 784)
+    image_recon = sample_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), args.n_samples, image)
+    os.makedirs(args.out, exist_ok=True)
+    torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))
+    return image_recon
 
 
 def _main(argv=None):
@@ -1524,6 +1618,8 @@ def _main(argv=None):
         return _sample_pixelcnn_main(args)
     if args.cmd == "nll_pixelcnn":
         return _nll_pixelcnn_main(args)
+    if args.dataset == "mnist":
+        return _sample_mnist_main(args)
     if is_textonly_checkpoint(args.model_path):       # a checkpoint of train_textonly_multimnist: text samples only
         from .multimnist import load_checkpoint_textonly
         vae = load_checkpoint_textonly(args.model_path, use_cuda=True)

@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._lib import MMVAEError, call, ptr
-from .core import FusedMnistStep, MnistState, StepOutputs
+from .core import FusedImageStep, FusedMnistStep, MnistState, StepOutputs
 from .multimnist import (ProductOfExperts, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _NLLMeanFn, _ReparamFn, _core_of,
                          _seed_from_torch, _stream)
 
@@ -276,6 +276,119 @@ class FusedTrainer:
     def evaluate(self, image, label, **kw) -> StepOutputs:
         """mnist/train.py:165-177: eval-mode forward of the 3 passes, no backward."""
         return self.engine.forward_backward(image.reshape(-1, 784), label, training=False, backward=False, **kw)
+
+
+# ------------------------------------------------------------------------------------------------------ image-only VAE
+class _ImageNet(nn.Sequential):
+    """One half of ``VAE``: the reference's ``nn.Sequential`` as a parameter container (keys ``0.weight`` ... ``6.bias``, no
+    ``.net.`` level) whose forward is the HIP image encoder / decoder module of the MMVAE plan.  The decoder half returns the
+    sigmoid of its last Linear (the module entry point ends there), so ``VAE.decode`` adds nothing."""
+
+    def __init__(self, name, n_latents, *layers):
+        super().__init__(*layers)
+        self._name, self.n_latents = name, n_latents
+
+    def forward(self, x):
+        x = x.contiguous().float()
+        if self._name == "image_encoder":
+            assert x.dim() == 2 and x.shape[1] == 784, "expected (B,784) flattened images (mnist/model.py:230)"
+            return _run_module(self, "image_encoder.net.", x, (2 * self.n_latents,), "image_encoder", False)
+        return _run_module(self, "image_decoder.net.", x, (784,), "image_decoder", True)
+
+
+class VAE(nn.Module):
+    """mnist/model.py:188-232: the image-only baseline under the reference's ``state_dict`` keys (``encoder.0.weight`` ...
+    ``decoder.6.bias``, BatchNorm buffers under ``encoder.1``, ``encoder.4``, ``decoder.1``, ``decoder.4``); a reference checkpoint
+    loads strict.  No product of experts.  The two halves live on the fp32 MMVAE plan as its ``image_encoder.net.*`` /
+    ``image_decoder.net.*``; the label half of the flat buffers keeps its initial value and never shows in ``state_dict()``.
+    ``ImageVAETrainer`` is the train() closure of mnist/imageonly/train_imageonly.py:114-127 as one enqueue."""
+
+    def __init__(self, n_latents=20):
+        super().__init__()
+        self.encoder = _ImageNet("image_encoder", n_latents,
+                                 nn.Linear(784, 400), nn.BatchNorm1d(400), nn.ReLU(),
+                                 nn.Linear(400, 200), nn.BatchNorm1d(200), nn.ReLU(),
+                                 nn.Linear(200, n_latents * 2))
+        self.decoder = _ImageNet("image_decoder", n_latents,
+                                 nn.Linear(n_latents, 200), nn.BatchNorm1d(200), nn.ReLU(),
+                                 nn.Linear(200, 400), nn.BatchNorm1d(400), nn.ReLU(),
+                                 nn.Linear(400, 784))
+        self.n_latents = n_latents
+        # the plan's names of the same modules (image_encoder.net.0.weight is encoder.0.weight): an unregistered twin tree for _Core
+        twin = nn.Module()
+        twin.image_encoder, twin.image_decoder = nn.Module(), nn.Module()
+        twin.image_encoder.net, twin.image_decoder.net = self.encoder, self.decoder
+        object.__setattr__(self, "_twin", twin)
+        self._core = _Core(twin, "", n_latents, lambda n, d: MnistState(n, d, "fp32"))
+        for m in (self.encoder, self.decoder):
+            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+
+    @staticmethod
+    def plan_name(key: str) -> str:
+        """``encoder.0.weight`` -> ``image_encoder.net.0.weight``: the plan's name of a ``state_dict`` key"""
+        half, rest = key.split(".", 1)
+        return "image_%s.net.%s" % (half, rest)
+
+    def encode(self, x):
+        n = self.n_latents
+        out = self.encoder(x)
+        return out[:, :n], out[:, n:]
+
+    def reparameterize(self, mu, logvar, eps: Optional[torch.Tensor] = None):
+        return MultimodalVAE.reparametrize(self, mu, logvar, eps)
+
+    def decode(self, z):
+        return self.decoder(z)
+
+    def forward(self, x, eps: Optional[torch.Tensor] = None):
+        mu, logvar = self.encode(x.view(-1, 784))
+        z = self.reparameterize(mu, logvar, eps)
+        return self.decode(z), mu, logvar
+
+
+ImageVAE = VAE
+
+
+def imageonly_loss(recon_x, x, mu, logvar):
+    """mnist/imageonly/train_imageonly.py:60-71: (mean BCE over B * 784 elements + KLD / 784) / B; the extra 1 / B is the reference's."""
+    batch_size = recon_x.size(0)
+    if recon_x.device.type == "cuda" and recon_x.dtype == torch.float32:
+        BCE = _BCEMeanFn.apply(recon_x.reshape(-1, 784), x.reshape(-1, 784))
+        KLD = _KLSumFn.apply(mu, logvar)
+    else:           # the same formula in torch ops, for tensors on the CPU or in another precision
+        BCE = F.binary_cross_entropy(recon_x.reshape(-1, 784), x.reshape(-1, 784).to(recon_x.dtype))
+        KLD = -0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp())
+    return (BCE + KLD / 784) / batch_size
+
+
+def load_checkpoint_imageonly(file_path, use_cuda=False):
+    """mnist/imageonly/train_imageonly.py:46-57: rebuilds a VAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    vae = VAE(n_latents=checkpoint['n_latents'])
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae
+
+
+class ImageVAETrainer:
+    """``ImageVAETrainer(vae, batch_size, lr)(image)`` == zero_grad + forward + loss + backward + Adam step
+    (mnist/imageonly/train_imageonly.py:114-127) on ``vae``'s own parameters: one pass over B rows (core.FusedImageStep with
+    lambda_x = 1 / B and kl_lambda = 1 / 784, which is the reference's (BCE + KLD / 784) / B).  ``out.losses()[0]`` is that loss."""
+
+    def __init__(self, vae: VAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1.0 / 784, seed: int = 1234):
+        dev = next(vae.parameters()).device
+        self.vae = vae
+        st = vae._core.sync(dev)
+        self.engine = FusedImageStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, lambda_x=1.0 / batch_size, seed=seed)
+        self.engine.enc_dropout = False
+
+    def __call__(self, image, **kw) -> StepOutputs:
+        return self.engine(image.reshape(-1, 784), **kw)
+
+    def evaluate(self, image, **kw) -> StepOutputs:
+        """The test() closure body (mnist/imageonly/train_imageonly.py:136-148): eval-mode forward, no backward."""
+        return self.engine.forward_backward(image.reshape(-1, 784), training=False, backward=False, **kw)
 
 
 # ------------------------------------------------------------------------------------------------------ InfoVAE

@@ -1,5 +1,5 @@
-"""``celeba/train_imageonly.py`` / ``coco/train_imageonly.py`` / ``multimnist/train_imageonly.py``-compatible driver of the uni-modal
-image baselines.
+"""``celeba/train_imageonly.py`` / ``coco/train_imageonly.py`` / ``multimnist/train_imageonly.py`` /
+``mnist/imageonly/train_imageonly.py``-compatible driver of the uni-modal image baselines.
 
 Per data set the reference script's command line, defaults, printed lines, KL schedule and checkpoint dict (``state_dict``,
 ``best_loss``, ``n_latents``, ``optimizer``), with the batch loop body replaced by ONE fused enqueue (``ImageVAETrainer``: one pass
@@ -10,11 +10,15 @@ over B rows, no product of experts) and the ``DataLoader`` by ``data.DeviceBatch
                                                       1e-5, 1e-4, 1e-3 advancing every 5 epochs
     multimnist (multimnist/train_imageonly.py:46-60,131-139): --n_latents 20 --lr 1e-3 [--anneal_kl], kl_lambda 1e-3, or with
                                                       --anneal_kl 1e-5 ... 1.0 advancing every 5 epochs; test loss = mean over batches
+    mnist  (mnist/imageonly/train_imageonly.py:60-71,77-89): --n_latents 20 --lr 1e-3 --epochs 20, loss (BCE + KLD / 784) / B throughout,
+                                                      checkpoints in ./trained_models, ``sample_image.pt`` (64 prior samples) in ./results
+                                                      whenever the test loss reaches a new best
 
     python -m multimodal_vae_amd.train_imageonly --dataset celeba --cuda --data ./data
     python -m multimodal_vae_amd.train_imageonly --dataset coco --cuda --epochs 2 --synthetic 4096   # no data files needed
     python -m multimodal_vae_amd.train_imageonly --dataset multimnist --cuda --data ./data           # images of processed/*.pt
     python -m multimodal_vae_amd.train_imageonly --dataset multimnist --cuda --generate --mnist_train A.pt --mnist_test B.pt
+    python -m multimodal_vae_amd.train_imageonly --dataset mnist --cuda --data mnist_train.pt [--test_data mnist_test.pt]
 
 After each epoch 64 prior samples are written as ``sample_image_epochN.pt`` (the tensor, not a PNG grid: no torchvision here).
 """
@@ -33,20 +37,24 @@ DATASETS = {
     "celeba": (100, 1e-3, 1e-3, 64),
     "coco": (20, 1e-4, 5e-4, 32),
     "multimnist": (20, 1e-3, 1e-3, 50),
+    "mnist": (20, 1e-3, 1.0 / 784, 28),         # (BCE + KLD / 784) / B: the 1 / B sits in the trainer's lambda_x
 }
-CHANNELS = {"celeba": 3, "coco": 3, "multimnist": 1}
+CHANNELS = {"celeba": 3, "coco": 3, "multimnist": 1, "mnist": 1}
+# epochs, checkpoint folder, results folder where the reference script's differ from the others' (mnist/imageonly/train_imageonly.py:81,92-96)
+FOLDERS = {"mnist": (20, './trained_models', './results')}
 COCO_KL_SCHEDULE = (1e-5, 1e-4, 1e-3)       # coco/train_imageonly.py:142
 KL_SCHEDULES = {"coco": COCO_KL_SCHEDULE, "multimnist": tuple(kl_schedule())}      # multimnist/train_imageonly.py:132
 
 
 def build_parser(dataset: str) -> argparse.ArgumentParser:
     n_latents, lr, _, _ = DATASETS[dataset]
+    epochs, out, results = FOLDERS.get(dataset, (10, './trained_models/image_only', './results/image_only'))
     parser = argparse.ArgumentParser()
     parser.add_argument('--dataset', choices=sorted(DATASETS), default=dataset)
     # the reference's flags, same names / defaults
     parser.add_argument('--n_latents', type=int, default=n_latents, help='size of the latent embedding')
     parser.add_argument('--batch_size', type=int, default=128, metavar='N', help='input batch size for training (default: 128)')
-    parser.add_argument('--epochs', type=int, default=10, metavar='N', help='number of epochs to train (default: 10)')
+    parser.add_argument('--epochs', type=int, default=epochs, metavar='N', help='number of epochs to train (default: %d)' % epochs)
     parser.add_argument('--lr', type=float, default=lr, metavar='LR', help='learning rate (default: %g)' % lr)
     parser.add_argument('--log_interval', type=int, default=10, metavar='N', help='how many batches to wait before logging training status')
     if dataset in KL_SCHEDULES:
@@ -55,10 +63,11 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     # additions, as train_celeba / train_coco
     parser.add_argument('--data', type=str, default='./data', metavar='DIR',
                         help='celeba: folder with celeba_{train,val}.pt (make_celeba); coco: folder with images_u8.pt (as train_coco); '
-                             "multimnist: root of the reference's processed/{training,test}.pt (images only)")
+                             "multimnist: root of the reference's processed/{training,test}.pt (images only); "
+                             'mnist: a .pt FILE holding (uint8 (N,28,28), int64 (N,)), the file `evaluate loglik --dataset mnist` reads')
     parser.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic samples instead of files')
-    parser.add_argument('--out', type=str, default='./trained_models/image_only', help='checkpoint folder (reference: ./trained_models/image_only)')
-    parser.add_argument('--results', type=str, default='./results/image_only', help='folder of the per-epoch sample dumps (off when empty)')
+    parser.add_argument('--out', type=str, default=out, help='checkpoint folder (reference: %s)' % out)
+    parser.add_argument('--results', type=str, default=results, help='folder of the sample dumps (off when empty)')
     parser.add_argument('--seed', type=int, default=1234)
     if dataset == "multimnist":         # as train.py / train_textonly_multimnist.py
         parser.add_argument('--generate', action='store_true', default=False,
@@ -68,6 +77,9 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
         parser.add_argument('--epoch_size', type=int, default=60000, metavar='N', help='--generate: canvases per training epoch (default: 60000)')
         parser.add_argument('--min_digits', type=int, default=0, help='--generate: minimum number of digits per canvas (datasets.py: 0)')
         parser.add_argument('--max_digits', type=int, default=2, help='--generate: maximum number of digits per canvas (datasets.py: 2; at most 4)')
+    if dataset == "mnist":
+        parser.add_argument('--test_data', type=str, default='', metavar='FILE',
+                            help='the test split, same layout as --data (default: the first tenth of --data is held out)')
     return parser
 
 
@@ -96,7 +108,8 @@ def image_adam_state_dict(vae, engine) -> dict:
     """The engine's flat Adam moments of the ImageVAE's own parameters as a ``torch.optim.Adam.state_dict()``."""
     st = engine.state
     step = int(engine.adam_state[0].item())
-    own = {vae._core.prefix + n for n, _ in vae.named_parameters()}
+    plan_name = getattr(vae, "plan_name", lambda n: vae._core.prefix + n)      # (mnist.VAE's keys have no .net. level)
+    own = {plan_name(n) for n, _ in vae.named_parameters()}
     state = {}
     for name, shape, off in st.table:
         if name not in own:
@@ -159,6 +172,18 @@ def _multimnist_loaders(args, dev):
 
 def _load_images(args):
     from . import data as D
+    if args.dataset == "mnist":         # only the images are read
+        if args.synthetic > 0:
+            return (D.synthetic_mnist(args.synthetic, seed=args.seed)[0],
+                    D.synthetic_mnist(max(args.batch_size, args.synthetic // 6), seed=args.seed + 1)[0])
+        from .make_multimnist import load_mnist_pt
+        if not os.path.isfile(args.data):
+            raise SystemExit("--dataset mnist: --data must name a .pt file holding (uint8 (N,28,28), int64 (N,)), or give --synthetic N")
+        x = load_mnist_pt(args.data)[0]
+        if args.test_data:
+            return x, load_mnist_pt(args.test_data)[0]
+        n_test = max(args.batch_size, len(x) // 10)
+        return x[n_test:], x[:n_test]
     if args.dataset == "celeba":
         from .evaluate import load_celeba_eval_file
         if args.synthetic > 0:
@@ -258,7 +283,14 @@ def main(argv=None) -> dict:
         is_best = loss < best_loss
         best_loss = min(loss, best_loss)
         save_checkpoint(checkpoint_dict(vae, trainer.engine, best_loss, args.n_latents), is_best, folder=args.out)
-        if args.results:
+        if args.results and args.dataset == "mnist":      # mnist/imageonly/train_imageonly.py:166-173: on a new best only; n_latents columns
+            if is_best:
+                os.makedirs(args.results, exist_ok=True)
+                vae.eval()
+                with torch.no_grad():
+                    torch.save(vae.decode(torch.randn(64, args.n_latents, device=dev)).cpu().view(64, 1, 28, 28),
+                               os.path.join(args.results, 'sample_image.pt'))
+        elif args.results:
             os.makedirs(args.results, exist_ok=True)
             sample = torch.randn(64, args.n_latents, device=dev)
             vae.eval()
