@@ -562,6 +562,70 @@ int mmvae_latent1_bwd(const float* mu, const float* logvar, const float* eps_or_
 int mmvae_latent1_bwd_f32(const float* mu, const float* logvar, const float* eps_or_null, const float* dz_or_null, int B, int D,
                           int training, float kl_coef, float* d_enc_out, int ld, void* stream);
 
+/* The streaming kernels every step runs (latent block of the three-pass models, losses, BatchNorm, embedding, column sums) on plain
+ * device pointers (test and measurement aid).  Each call is exactly the launch the steps make; a shape the kernel would index out of
+ * range is refused with a message.  bf16 tensors are passed as void*.  "slots" = the [32][16] loss accumulators of a step: a sum is
+ * the fold of a column over the 32 rows.  "stat slots" = 16 replicas: stats / red are [G][16][C][2] and are folded over the 16.
+ * latent3_fwd: img_out [2][B][2D] (mu | logvar of the image encoder, pass 0 and pass 1; img_out_b non-NULL: pass 1 is read there,
+ *   [B][2D]), txt_out [B][2D] -> mu, logvar, z [3][B][D]: pass 0 = PoE{image 0, text}, pass 1 = PoE{image 1}, pass 2 = PoE{text} with
+ *   PoE mu = sum(mu_i var_i) / sum(var_i), logvar = log(1 / sum(1 / var_i)), var_i = exp(logvar_i) + 1e-8 (so a one-expert pass is NOT
+ *   a copy of its input); z = mu + eps * exp(logvar / 2) (eps [3][B][D]; training 0: eps may be NULL, z = mu bit for bit);
+ *   z_bf16 [3B][ldz] (ldz % 8 == 0, >= D) = bf16(z), column D = 1.0, the other pad columns 0;
+ *   kl_slots [32][16]: column k (k = 0..2) of row (workgroup % 32) += that workgroup's part of -0.5 sum(1 + logvar - mu^2 - exp(logvar)).
+ * latent3_bwd: the gradient of  sum_k (<dz_a + dz_b, z_k> + kl_coef_k * KL_k)  wrt img_out / txt_out, from the mu / logvar the forward
+ *   wrote.  dz_a, dz_b [3][B][D], each may be NULL.  The image gradient takes ONE of four forms: d_img_out_f32 [B][2D] = pass 0 + pass 1
+ *   (then d_img_out_bf16 is not touched); else sum_img_variants 1: d_img_out_bf16 [B][ld] = bf16(pass 0 + pass 1); else
+ *   d_img_out_bf16 [2][B][ld] = bf16 of each; ld = ld_img_out_bf (a multiple of 8 >= 2D, pad columns zeroed) or 2D when that is 0.
+ *   d_txt_out [B][2D] fp32 and d_txt_out_bf16 [B][2D]: each optional.  d_img_bias, d_txt_bias [2D] += column sums (float atomics), each
+ *   optional.  loss_slots / loss_out (both or neither): loss_out[16] = sum of the [32][16] slot rows.
+ * sigmoid_bce: logits NHWC [G*B][H][W][ldl] (channel c at +c), target NCHW [B][C][H][W] shared by the G <= 4 groups, coef_host[G] (HOST
+ *   floats) -> recon = sigmoid NCHW [G*B][C][H][W] (or NULL), dlogit = coef[g] * (p - t) / max(p (1 - p), 1e-12) * p (1 - p) (or NULL),
+ *   loss_sum[g] += sum of -(t max(log p, -100) + (1 - t) max(log(1 - p), -100)): F.binary_cross_entropy of F.sigmoid in fp32.
+ * logsoftmax_nll: logits [rows][classes] -> words = log_softmax; target (or NULL) int64 [target_rows], row r reads target[r %
+ *   target_rows]; group g = r / rows_per_group (at most 4 groups); nll_slots [32][16] column g += sum of -words[r][target] (or NULL);
+ *   dlogits_bf16 [rows][ld_d] (pads zero) and dlogits_f32 [rows][classes], each optional = coef_host[g] * (softmax - onehot);
+ *   coef_host: one HOST float per group, ceil(rows / rows_per_group) of them are read.
+ * bn_finalize: stats [G][16][C][2] (sum, sum of squares over `count` values) -> affine [G][C][2] = (gamma rstd, beta - mean gamma rstd),
+ *   meanrstd [G][C][2]; biased variance E[x^2] - mean^2 clamped at 0; the running buffers move by torch's momentum update (unbiased
+ *   variance) updates_per_group times per group in group order, except groups whose bit is set in skip_update_mask, and *nbt grows by
+ *   updates_per_group * (groups not skipped).  running buffers / nbt may be NULL.  training 0: tables from the running buffers, nothing
+ *   else written.
+ * bn_act: the same tables (affine / meanrstd may both be NULL) and running update + a = act(r * scale + shift) on bf16 rows
+ *   [rows][ld] (ld % 8 == 0, >= C rounded up to 8; columns [C, 8 ceil(C/8)) of a are written as 0), act 0 none / 1 swish / 2 relu;
+ *   G * C <= 4096; rows <= G * rows_per_group.
+ * bn_bwd_apply: dr = gamma rstd (db [+ db2] - sum_db / n - xhat sum_db_xhat / n), n = rows_per_group, from red [G][16][C][2] = (sum db,
+ *   sum db xhat) and meanrstd; dr may alias db; dgamma[c] += sum over groups of sum_db_xhat, dbeta[c] += sum_db (each may be NULL).
+ * embed_gather_stats: x_bf16 [rows][ld] = bf16(table[idx[r % idx_rows]][:C]), pads 0; colstats [G][16][C][2] += (sum, sum of squares)
+ *   of the bf16 values per group of rows_per_group rows (or NULL).  embed_scatter_add: g_table[idx[r]][c] += d[r][c] (float atomics).
+ * colsum_f32 / colsum_bf16: out[c] += sum_r x[r][c] for c < cols; bf16 rows have stride ld >= cols. */
+int mmvae_latent3_fwd(const float* img_out, const float* img_out_b_or_null, const float* txt_out, const float* eps_or_null, int B, int D,
+                      int training, float* mu, float* logvar, float* z, void* z_bf16, int ldz, float* kl_slots, void* stream);
+int mmvae_latent3_bwd(const float* img_out, const float* img_out_b_or_null, const float* txt_out, const float* mu, const float* logvar,
+                      const float* eps_or_null, const float* dz_a_or_null, const float* dz_b_or_null, int B, int D, int training,
+                      float kl_coef0, float kl_coef1, float kl_coef2, void* d_img_out_bf16_or_null, int ld_img_out_bf, int sum_img_variants,
+                      float* d_img_out_f32_or_null, float* d_img_bias_or_null, float* d_txt_out_or_null, void* d_txt_out_bf16_or_null,
+                      float* d_txt_bias_or_null, const float* loss_slots_or_null, float* loss_out_or_null, void* stream);
+int mmvae_sigmoid_bce(const float* logits, int ldl, const float* target, int G, int B, int C, int H, int W, const float* coef_host,
+                      float* recon_or_null, float* dlogit_or_null, float* loss_sum, void* stream);
+int mmvae_logsoftmax_nll(const float* logits, int rows, int classes, float* words, const long long* target_or_null, int target_rows,
+                         int rows_per_group, float* nll_slots_or_null, void* dlogits_bf16_or_null, int ld_d, float* dlogits_f32_or_null,
+                         const float* coef_host, void* stream);
+int mmvae_bn_finalize(const float* stats, int G, int C, float count, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, long long* num_batches_tracked, int updates_per_group, unsigned skip_update_mask, float* affine,
+                      float* meanrstd, float eps, float momentum, int training, void* stream);
+int mmvae_bn_act(const void* r_bf16, void* a_bf16, int rows, int C, int ld, int rows_per_group, int G, int act, const float* stats,
+                 float count, const float* gamma, const float* beta, float* running_mean, float* running_var, long long* num_batches_tracked,
+                 int updates_per_group, unsigned skip_update_mask, float* affine_or_null, float* meanrstd_or_null, float eps, float momentum,
+                 int training, void* stream);
+int mmvae_bn_bwd_apply(const void* db_bf16, const void* db2_bf16_or_null, const void* r_bf16, void* dr_bf16, int rows, int C, int ld,
+                       int rows_per_group, int G, const float* red, const float* meanrstd, const float* gamma, float* dgamma_or_null,
+                       float* dbeta_or_null, void* stream);
+int mmvae_embed_gather_stats(const float* table, int C, const long long* idx, int rows, int idx_rows, int rows_per_group, void* x_bf16,
+                             int ld, float* colstats_or_null, void* stream);
+int mmvae_embed_scatter_add(const void* d_bf16, int ld, int C, const long long* idx, int rows, float* g_table, void* stream);
+int mmvae_colsum_f32(const float* x, int rows, int cols, float* out, void* stream);
+int mmvae_colsum_bf16(const void* x_bf16, int ld, int rows, int cols, float* out, void* stream);
+
 /* ---------------------------------------------------------------- text-only VAE baseline (COCO)
  * TextVAE of coco/model.py:120-144 -- TextEncoder and TextDecoder with reparametrize between them and NO product of experts -- trained
  * by coco/train_textonly.py:106-120 on loss = lambda_y * sum((recon - text)^2) / (B * steps * 300) + kl_lambda * KL / B.  The step runs

@@ -310,6 +310,17 @@ SIGNATURES["mmvae_latent1_bwd_f32"] = (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, 
 SIGNATURES["mmvae_latent1_scratch_floats"] = (_SZ, [_I, _I])
 SIGNATURES["mmvae_latent1_fwd"] = (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P])
 SIGNATURES["mmvae_latent1_bwd"] = (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P])
+SIGNATURES["mmvae_latent3_fwd"] = (_I, [_P] * 4 + [_I] * 3 + [_P] * 4 + [_I, _P, _P])
+SIGNATURES["mmvae_latent3_bwd"] = (_I, [_P] * 8 + [_I] * 3 + [_F] * 3 + [_P, _I, _I] + [_P] * 8)
+SIGNATURES["mmvae_sigmoid_bce"] = (_I, [_P, _I, _P] + [_I] * 5 + [C.POINTER(_F)] + [_P] * 4)
+SIGNATURES["mmvae_logsoftmax_nll"] = (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, C.POINTER(_F), _P])
+SIGNATURES["mmvae_bn_finalize"] = (_I, [_P, _I, _I, _F] + [_P] * 5 + [_I, _U, _P, _P, _F, _F, _I, _P])
+SIGNATURES["mmvae_bn_act"] = (_I, [_P, _P] + [_I] * 6 + [_P, _F] + [_P] * 5 + [_I, _U, _P, _P, _F, _F, _I, _P])
+SIGNATURES["mmvae_bn_bwd_apply"] = (_I, [_P] * 4 + [_I] * 5 + [_P] * 6)
+SIGNATURES["mmvae_embed_gather_stats"] = (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P])
+SIGNATURES["mmvae_embed_scatter_add"] = (_I, [_P, _I, _I, _P, _I, _P, _P])
+SIGNATURES["mmvae_colsum_f32"] = (_I, [_P, _I, _I, _P, _P])
+SIGNATURES["mmvae_colsum_bf16"] = (_I, [_P, _I, _I, _I, _P, _P])
 SIGNATURES["mmvae_nn_words_workspace_bytes"] = (_LL, [_I, _LL])
 SIGNATURES["mmvae_nn_words_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)])
 SIGNATURES["mmvae_nn_words_norms"] = (_I, [_P, _LL, _I, _P, _P])

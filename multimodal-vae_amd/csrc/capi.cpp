@@ -501,6 +501,110 @@ int mmvae_latent1_bwd_f32(const float* mu, const float* logvar, const float* eps
         return launch_latent1_bwd_f32(a, S(st));
     });
 }
+// ---- the streaming kernels of every step on plain device pointers (test and measurement aid): each fills the argument struct of the step's
+// own launcher, whose checks refuse what the kernel would index out of range
+int mmvae_latent3_fwd(const float* img_out, const float* img_out_b, const float* txt_out, const float* eps, int B, int D, int training,
+                      float* mu, float* logvar, float* z, void* z_bf16, int ldz, float* kl_slots, void* st) {
+    return guarded([&] {
+        Latent3Args a{};
+        a.B = B; a.D = D; a.img_out = img_out; a.img_out_b = img_out_b; a.txt_out = txt_out; a.eps = eps; a.mu = mu; a.logvar = logvar;
+        a.z_f32 = z; a.z_bf = (bf16*)z_bf16; a.ldz = ldz; a.kl_sum = kl_slots; a.training = training;
+        return launch_latent3_fwd(a, S(st));
+    });
+}
+int mmvae_latent3_bwd(const float* img_out, const float* img_out_b, const float* txt_out, const float* mu, const float* logvar,
+                      const float* eps, const float* dz_a, const float* dz_b, int B, int D, int training, float kl_coef0, float kl_coef1,
+                      float kl_coef2, void* d_img_out_bf16, int ld_img_out_bf, int sum_img_variants, float* d_img_out_f32, float* d_img_bias,
+                      float* d_txt_out, void* d_txt_out_bf16, float* d_txt_bias, const float* loss_slots, float* loss_out, void* st) {
+    return guarded([&] {
+        Latent3BwdArgs a{};
+        a.f.B = B; a.f.D = D; a.f.img_out = img_out; a.f.img_out_b = img_out_b; a.f.txt_out = txt_out; a.f.eps = eps;
+        a.f.mu = const_cast<float*>(mu); a.f.logvar = const_cast<float*>(logvar); a.f.training = training;
+        a.dz_a = dz_a; a.dz_b = dz_b; a.kl_coef[0] = kl_coef0; a.kl_coef[1] = kl_coef1; a.kl_coef[2] = kl_coef2;
+        a.d_img_out_bf = (bf16*)d_img_out_bf16; a.ld_img_out_bf = ld_img_out_bf; a.sum_img_variants = sum_img_variants;
+        a.d_img_out_f32 = d_img_out_f32; a.d_img_bias = d_img_bias; a.d_txt_out = d_txt_out; a.d_txt_out_bf = (bf16*)d_txt_out_bf16;
+        a.d_txt_bias = d_txt_bias; a.loss_slots = loss_slots; a.loss_out = loss_out;
+        return launch_latent3_bwd(a, S(st));
+    });
+}
+int mmvae_sigmoid_bce(const float* logits, int ldl, const float* target, int G, int B, int C, int H, int W, const float* coef_host,
+                      float* recon, float* dlogit, float* loss_sum, void* st) {
+    return guarded([&] {
+        MMVAE_REQUIRE(G >= 1 && G <= 4 && coef_host, "sigmoid_bce: G=%d (1..4) or coef missing", G);
+        BceArgs a{};
+        a.logits = logits; a.ldl = ldl; a.target = target; a.G = G; a.B = B; a.C = C; a.H = H; a.W = W; a.recon = recon; a.dlogit = dlogit;
+        for (int g = 0; g < G; ++g) a.coef[g] = coef_host[g];
+        a.loss_sum = loss_sum;
+        return launch_sigmoid_bce(a, S(st));
+    });
+}
+int mmvae_logsoftmax_nll(const float* logits, int rows, int classes, float* words, const long long* target, int target_rows,
+                         int rows_per_group, float* nll_slots, void* dlogits_bf16, int ld_d, float* dlogits_f32, const float* coef_host,
+                         void* st) {
+    return guarded([&] {
+        MMVAE_REQUIRE(coef_host && rows >= 1 && rows_per_group >= 1 && (rows + rows_per_group - 1) / rows_per_group <= 4,
+                      "logsoftmax_nll: coef missing, or rows=%d are not 1..4 groups of %d", rows, rows_per_group);
+        LogSoftmaxNllArgs a{};
+        a.logits = logits; a.rows = rows; a.classes = classes; a.words = words; a.target = target; a.target_rows = target_rows;
+        a.rows_per_group = rows_per_group; a.nll_sum = nll_slots; a.dlogits = (bf16*)dlogits_bf16; a.ld_d = ld_d; a.dlogits_f32 = dlogits_f32;
+        for (int g = 0; g < (rows + rows_per_group - 1) / rows_per_group; ++g) a.coef[g] = coef_host[g];
+        return launch_logsoftmax_nll(a, S(st));
+    });
+}
+static BnFinalizeArgs bn_fin_of(const float* stats, int G, int C, float count, const float* gamma, const float* beta, float* running_mean,
+                                float* running_var, long long* nbt, int updates_per_group, unsigned skip_update_mask, float* affine,
+                                float* meanrstd, float eps, float momentum, int training) {
+    BnFinalizeArgs f{};
+    f.stats = (const float2*)stats; f.G = G; f.C = C; f.count = count; f.gamma = gamma; f.beta = beta; f.running_mean = running_mean;
+    f.running_var = running_var; f.num_batches_tracked = nbt; f.updates_per_group = updates_per_group; f.skip_update_mask = skip_update_mask;
+    f.affine = (float2*)affine; f.meanrstd = (float2*)meanrstd; f.eps = eps; f.momentum = momentum; f.training = training;
+    return f;
+}
+int mmvae_bn_finalize(const float* stats, int G, int C, float count, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, long long* nbt, int updates_per_group, unsigned skip_update_mask, float* affine, float* meanrstd,
+                      float eps, float momentum, int training, void* st) {
+    return guarded([&] {
+        return launch_bn_finalize(bn_fin_of(stats, G, C, count, gamma, beta, running_mean, running_var, nbt, updates_per_group,
+                                            skip_update_mask, affine, meanrstd, eps, momentum, training), S(st));
+    });
+}
+int mmvae_bn_act(const void* r_bf16, void* a_bf16, int rows, int C, int ld, int rows_per_group, int G, int act, const float* stats,
+                 float count, const float* gamma, const float* beta, float* running_mean, float* running_var, long long* nbt,
+                 int updates_per_group, unsigned skip_update_mask, float* affine, float* meanrstd, float eps, float momentum, int training,
+                 void* st) {
+    return guarded([&] {
+        MMVAE_REQUIRE(act == ACT_NONE || act == ACT_SWISH || act == ACT_RELU, "bn_act: activation code %d", act);
+        BnActArgs a{};
+        a.r = (const bf16*)r_bf16; a.a = (bf16*)a_bf16; a.rows = rows; a.C = C; a.ld = ld; a.rows_per_group = rows_per_group; a.G = G; a.act = act;
+        a.fin = bn_fin_of(stats, G, C, count, gamma, beta, running_mean, running_var, nbt, updates_per_group, skip_update_mask, affine,
+                          meanrstd, eps, momentum, training);
+        return launch_bn_act(a, S(st));
+    });
+}
+int mmvae_bn_bwd_apply(const void* db_bf16, const void* db2_bf16, const void* r_bf16, void* dr_bf16, int rows, int C, int ld,
+                       int rows_per_group, int G, const float* red, const float* meanrstd, const float* gamma, float* dgamma, float* dbeta,
+                       void* st) {
+    return guarded([&] {
+        BnBwdApplyArgs a{};
+        a.db = (const bf16*)db_bf16; a.db2 = (const bf16*)db2_bf16; a.r = (const bf16*)r_bf16; a.dr = (bf16*)dr_bf16; a.rows = rows; a.C = C;
+        a.ld = ld; a.rows_per_group = rows_per_group; a.G = G; a.red = (const float2*)red; a.meanrstd = (const float2*)meanrstd;
+        a.gamma = gamma; a.dgamma = dgamma; a.dbeta = dbeta;
+        return launch_bn_bwd_apply(a, S(st));
+    });
+}
+int mmvae_embed_gather_stats(const float* table, int C, const long long* idx, int rows, int idx_rows, int rows_per_group, void* x_bf16,
+                             int ld, float* colstats, void* st) {
+    return guarded([&] { return launch_embed_gather_stats(table, C, idx, rows, idx_rows, rows_per_group, (bf16*)x_bf16, ld, (float2*)colstats, S(st)); });
+}
+int mmvae_embed_scatter_add(const void* d_bf16, int ld, int C, const long long* idx, int rows, float* g_table, void* st) {
+    return guarded([&] { return launch_embed_scatter_add((const bf16*)d_bf16, ld, C, idx, rows, g_table, S(st)); });
+}
+int mmvae_colsum_f32(const float* x, int rows, int cols, float* out, void* st) {
+    return guarded([&] { return launch_colsum_f32(x, rows, cols, out, S(st)); });
+}
+int mmvae_colsum_bf16(const void* x_bf16, int ld, int rows, int cols, float* out, void* st) {
+    return guarded([&] { return launch_colsum_bf16((const bf16*)x_bf16, ld, rows, cols, out, S(st)); });
+}
 int mmvae_kl_fwd(const float* mu, const float* lv, int n, float* out, void* s) { return launch_kl_fwd(mu, lv, n, out, S(s)); }
 int mmvae_kl_bwd(const float* mu, const float* lv, int n, float coef, const float* gs, float* dmu, float* dlv, void* s) { return launch_kl_bwd(mu, lv, n, coef, gs, dmu, dlv, S(s)); }
 int mmvae_bce_fwd(const float* p, const float* t, long long n, float* out, void* s) { return launch_bce_fwd(p, t, n, out, S(s)); }

@@ -75,7 +75,6 @@ struct BnBwdApplyArgs {
     const float2* meanrstd;  // [G][C]
     const float* gamma;
     float* dgamma; float* dbeta;   // flat grads, += (may be null)
-    float* dbias;            // optional: += column sums of dr (Linear bias in front of the BN), may be null
 };
 int launch_bn_bwd_apply(const BnBwdApplyArgs& a, hipStream_t s);
 
@@ -114,7 +113,7 @@ struct Latent3Args {
     float* z_f32;            // [3B][D]
     bf16* z_bf;              // [3B][ldz], pad columns zeroed
     int ldz;
-    float* kl_sum;           // [3] +=
+    float* kl_sum;           // [MMVAE_LOSS_SLOTS][16] slot rows: columns 0..2 of row (workgroup % MMVAE_LOSS_SLOTS) += the KL sum of pass 0..2
     int training;
 };
 int launch_latent3_fwd(const Latent3Args& a, hipStream_t s);
@@ -133,6 +132,8 @@ struct Latent3BwdArgs {
     const float* loss_slots; // optional: the step's [MMVAE_LOSS_SLOTS][16] loss accumulators, summed into loss_out[16] by block 0
     float* loss_out;         // (every loss term must be final when this kernel starts: saves the separate sum_slots launch)
     int ld_img_out_bf;       // row stride of d_img_out_bf, a multiple of 8 >= 2D whose pad columns the kernel zeroes; 0: 2D, no pad
+    // The four image-gradient forms and who takes them: d_img_out_f32 (MNIST fp32 step) | sum_img_variants (MNIST bf16 step) |
+    // two variants in the padded stride ld_img_out_bf (MultiMNIST) | two variants at stride 2D, neither switch set (CelebA, COCO).
 };
 int launch_latent3_bwd(const Latent3BwdArgs& a, hipStream_t s);
 

@@ -6,6 +6,24 @@
 namespace {
 
 constexpr int TPB = 256;
+
+// expf with the accuracy of its own expansion.  The library is built with -ffp-contract=fast, under which the compiler fuses the
+// x * log2(e) of expf's range reduction into the subtraction of its rounded integer part; the rounding error of the product is then
+// counted twice and the result is off by up to |x| log2(e) 2^-24 relative (11 ulp at x = -20, where the latent kernels live: the
+// product of experts at logvar -12 .. -17 missed 4x the error of the same expression in float32 on a CPU).  The asm statement emits no
+// instruction: it only keeps the product a value of its own.  Same instruction count as expf.
+__device__ __forceinline__ float exp_unfused(float x) {
+    const float c = 0x1.715476p+0f, cc = 0x1.4ae0bep-26f;      // log2(e): head and tail
+    float ph = x * c;
+    asm volatile("" : "+v"(ph));
+    float pl = fmaf(x, c, -ph);
+    pl = fmaf(x, cc, pl);
+    const float e = rintf(ph);
+    float r = ldexpf(__builtin_amdgcn_exp2f((ph - e) + pl), (int)e);
+    r = x < -0x1.9d1dap+6f ? 0.f : r;                            // below the smallest denormal
+    r = x > 0x1.62e43p+6f ? INFINITY : r;
+    return r;
+}
 inline int nblocks(long long n, int per = TPB, int cap = 4096) {
     long long b = (n + per - 1) / per;
     if (b < 1) b = 1;
@@ -331,7 +349,7 @@ __global__ __launch_bounds__(TPB) void sigmoid_bce_kernel(const BceArgs a) {
         const long long ng = (long long)g * a.B + n;
         const float l = a.logits[((ng * a.H + y) * a.W + x) * a.ldl + c];
         const float t = a.target[i];
-        const float p = 1.0f / (1.0f + expf(-l));                  // F.sigmoid
+        const float p = 1.0f / (1.0f + exp_unfused(-l));                  // F.sigmoid
         const float lp = fmaxf(logf(p), -100.f);                    // F.binary_cross_entropy clamps both logs at -100
         const float lq = fmaxf(logf(1.0f - p), -100.f);
         acc += -(t * lp + (1.0f - t) * lq);
@@ -361,7 +379,7 @@ __device__ __forceinline__ Poe2 poe_fwd_m(const float (&mu)[M], const float (&lv
     float s0 = 0.f, s1 = 0.f, t = 0.f;
 #pragma unroll
     for (int i = 0; i < M; ++i) {
-        float var = expf(lv[i]) + 1e-8f;
+        float var = exp_unfused(lv[i]) + 1e-8f;
         s0 += var; s1 += mu[i] * var; t += 1.0f / var;
     }
     Poe2 o;
@@ -376,7 +394,7 @@ __device__ __forceinline__ void poe_bwd_m(const float (&mu)[M], const float (&lv
     float var[M];
 #pragma unroll
     for (int i = 0; i < M; ++i) {
-        var[i] = expf(lv[i]) + 1e-8f;
+        var[i] = exp_unfused(lv[i]) + 1e-8f;
         s0 += var[i]; s1 += mu[i] * var[i]; t += 1.0f / var[i];
     }
     const float pm = s1 / s0;
@@ -384,7 +402,7 @@ __device__ __forceinline__ void poe_bwd_m(const float (&mu)[M], const float (&lv
     for (int i = 0; i < M; ++i) {
         dmu[i] = gmu * var[i] / s0;
         float dvar = gmu * (mu[i] - pm) / s0 + glv / (t * var[i] * var[i]);
-        dlv[i] = dvar * expf(lv[i]);
+        dlv[i] = dvar * exp_unfused(lv[i]);
     }
 }
 
@@ -393,7 +411,7 @@ __global__ __launch_bounds__(TPB) void poe_fwd_kernel(const float* mu, const flo
     if (i >= n) return;
     float s0 = 0.f, s1 = 0.f, t = 0.f;
     for (int m = 0; m < M; ++m) {
-        float var = expf(lv[(long long)m * n + i]) + 1e-8f;
+        float var = exp_unfused(lv[(long long)m * n + i]) + 1e-8f;
         s0 += var; s1 += mu[(long long)m * n + i] * var; t += 1.0f / var;
     }
     omu[i] = s1 / s0;
@@ -405,12 +423,12 @@ __global__ __launch_bounds__(TPB) void poe_bwd_kernel(const float* mu, const flo
     if (i >= n) return;
     float s0 = 0.f, s1 = 0.f, t = 0.f;
     for (int m = 0; m < M; ++m) {
-        float var = expf(lv[(long long)m * n + i]) + 1e-8f;
+        float var = exp_unfused(lv[(long long)m * n + i]) + 1e-8f;
         s0 += var; s1 += mu[(long long)m * n + i] * var; t += 1.0f / var;
     }
     const float pm = s1 / s0, a = gmu[i], b = glv[i];
     for (int m = 0; m < M; ++m) {
-        float e = expf(lv[(long long)m * n + i]);
+        float e = exp_unfused(lv[(long long)m * n + i]);
         float var = e + 1e-8f;
         dmu[(long long)m * n + i] = a * var / s0;
         dlv[(long long)m * n + i] = (a * (mu[(long long)m * n + i] - pm) / s0 + b / (t * var * var)) * e;
@@ -418,23 +436,23 @@ __global__ __launch_bounds__(TPB) void poe_bwd_kernel(const float* mu, const flo
 }
 __global__ __launch_bounds__(TPB) void reparam_fwd_kernel(const float* mu, const float* lv, const float* eps, int n, float* z) {
     int i = blockIdx.x * TPB + threadIdx.x;
-    if (i < n) z[i] = eps[i] * expf(0.5f * lv[i]) + mu[i];
+    if (i < n) z[i] = eps[i] * exp_unfused(0.5f * lv[i]) + mu[i];
 }
 __global__ __launch_bounds__(TPB) void reparam_bwd_kernel(const float* lv, const float* eps, const float* dz, int n, float* dmu, float* dlv) {
     int i = blockIdx.x * TPB + threadIdx.x;
-    if (i < n) { dmu[i] = dz[i]; dlv[i] = dz[i] * eps[i] * 0.5f * expf(0.5f * lv[i]); }
+    if (i < n) { dmu[i] = dz[i]; dlv[i] = dz[i] * eps[i] * 0.5f * exp_unfused(0.5f * lv[i]); }
 }
 __global__ __launch_bounds__(TPB) void kl_fwd_kernel(const float* mu, const float* lv, int n, float* out) {
     float acc = 0.f;
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB)
-        acc += -0.5f * (1.0f + lv[i] - mu[i] * mu[i] - expf(lv[i]));
+        acc += -0.5f * (1.0f + lv[i] - mu[i] * mu[i] - exp_unfused(lv[i]));
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) atomicAdd(out, acc);
 }
 __global__ __launch_bounds__(TPB) void kl_bwd_kernel(const float* mu, const float* lv, int n, float coef, const float* gs, float* dmu, float* dlv) {
     if (gs) coef *= *gs;                                   // upstream gradient (0-d device tensor): no host read
     int i = blockIdx.x * TPB + threadIdx.x;
-    if (i < n) { dmu[i] = coef * mu[i]; dlv[i] = -0.5f * coef * (1.0f - expf(lv[i])); }
+    if (i < n) { dmu[i] = coef * mu[i]; dlv[i] = -0.5f * coef * (1.0f - exp_unfused(lv[i])); }
 }
 
 __global__ __launch_bounds__(TPB) void normal_kernel(float* out, long long n, unsigned long long seed, const long long* step, unsigned stream_id) {
@@ -553,10 +571,10 @@ __global__ __launch_bounds__(TPB) void latent3_fwd_kernel(const Latent3Args a) {
         for (int k = 0; k < 3; ++k) {
             const size_t e = (size_t)k * n + (size_t)b * a.D + d;
             a.mu[e] = o[k].mu; a.logvar[e] = o[k].lv;
-            float z = a.training ? a.eps[e] * expf(0.5f * o[k].lv) + o[k].mu : o[k].mu;
+            float z = a.training ? a.eps[e] * exp_unfused(0.5f * o[k].lv) + o[k].mu : o[k].mu;
             a.z_f32[e] = z;
             a.z_bf[(size_t)(k * a.B + b) * a.ldz + d] = (bf16)z;
-            kl[k] += -0.5f * (1.0f + o[k].lv - o[k].mu * o[k].mu - expf(o[k].lv));
+            kl[k] += -0.5f * (1.0f + o[k].lv - o[k].mu * o[k].mu - exp_unfused(o[k].lv));
         }
     }
 #pragma unroll
@@ -601,8 +619,8 @@ __global__ __launch_bounds__(TPB) void latent3_bwd_kernel(const Latent3BwdArgs a
             if (a.dz_b) dz += a.dz_b[e];
             const float mu = f.mu[e], lv = f.logvar[e];
             gmu[k] = dz + a.kl_coef[k] * mu;
-            glv[k] = -0.5f * a.kl_coef[k] * (1.0f - expf(lv));
-            if (f.training) glv[k] += dz * f.eps[e] * 0.5f * expf(0.5f * lv);
+            glv[k] = -0.5f * a.kl_coef[k] * (1.0f - exp_unfused(lv));
+            if (f.training) glv[k] += dz * f.eps[e] * 0.5f * exp_unfused(0.5f * lv);
         }
         float d_im0, d_il0, d_im1, d_il1, d_tm = 0.f, d_tl = 0.f;
         {
@@ -676,10 +694,10 @@ __global__ __launch_bounds__(TPB) void latent1_fwd_kernel(const Latent1Args a) {
         const int b = e / a.D, d = e - b * a.D;
         const float mu = a.enc_out[(size_t)b * D2 + d], lv = a.enc_out[(size_t)b * D2 + a.D + d];
         a.mu[e] = mu; a.logvar[e] = lv;
-        const float z = a.training ? a.eps[e] * expf(0.5f * lv) + mu : mu;
+        const float z = a.training ? a.eps[e] * exp_unfused(0.5f * lv) + mu : mu;
         a.z_f32[e] = z;
         a.z_bf[(size_t)b * a.ldz + d] = (bf16)z;
-        kl += (double)(-0.5f * (1.0f + lv - mu * mu - expf(lv)));
+        kl += (double)(-0.5f * (1.0f + lv - mu * mu - exp_unfused(lv)));
     }
     const int pads = a.ldz - a.D;
     for (int i = blockIdx.x * TPB + threadIdx.x; i < a.B * pads; i += gridDim.x * TPB) {
@@ -891,15 +909,15 @@ __global__ __launch_bounds__(TPB) void logsoftmax_nll_kernel(const LogSoftmaxNll
         float mx = -INFINITY;
         for (int c = 0; c < a.classes; ++c) mx = fmaxf(mx, l[c]);
         float se = 0.f;
-        for (int c = 0; c < a.classes; ++c) se += expf(l[c] - mx);
-        const float lse = mx + logf(se);
+        for (int c = 0; c < a.classes; ++c) se += exp_unfused(l[c] - mx);
+        const float lg = logf(se);       // log_softmax = (l - max) - log(sum): adding max to the log first would round at the size of max
         const int tg = a.target ? (int)a.target[r % a.target_rows] : -1;
         for (int c = 0; c < a.classes; ++c) {
-            const float lp = l[c] - lse;
+            const float lp = (l[c] - mx) - lg;
             a.words[(size_t)r * a.classes + c] = lp;
             if (c == tg) nll = -lp;
-            if (a.dlogits) a.dlogits[(size_t)r * a.ld_d + c] = (bf16)(a.coef[g & 3] * (expf(lp) - (c == tg ? 1.f : 0.f)));
-            if (a.dlogits_f32) a.dlogits_f32[(size_t)r * a.classes + c] = a.coef[g & 3] * (expf(lp) - (c == tg ? 1.f : 0.f));
+            if (a.dlogits) a.dlogits[(size_t)r * a.ld_d + c] = (bf16)(a.coef[g & 3] * (exp_unfused(lp) - (c == tg ? 1.f : 0.f)));
+            if (a.dlogits_f32) a.dlogits_f32[(size_t)r * a.classes + c] = a.coef[g & 3] * (exp_unfused(lp) - (c == tg ? 1.f : 0.f));
         }
         if (a.dlogits)
             for (int c = a.classes; c < a.ld_d; ++c) a.dlogits[(size_t)r * a.ld_d + c] = (bf16)0.f;
@@ -1068,26 +1086,50 @@ int launch_im2col_small(const float* src, int Nimg, int Cin, int H, int W, int K
                        KH, KW, stride, pad, OH, OW, dst, ld);
     return mmvae_check_launch("im2col_small");
 }
+// what bn_finalize_kernel / bn_channel_tables / bn_running_update index with: [G][slots][C] statistics, [G][C] tables, bit g of the mask
+static int bn_finalize_check(const BnFinalizeArgs& a, const char* who) {
+    MMVAE_REQUIRE(a.C >= 1 && a.G >= 1 && a.G <= 31, "%s: C=%d G=%d out of range (1 <= G <= 31)", who, a.C, a.G);
+    MMVAE_REQUIRE(a.gamma && a.beta, "%s: gamma / beta missing", who);
+    MMVAE_REQUIRE(a.training ? a.stats != nullptr : (a.running_mean && a.running_var), "%s: %s missing", who,
+                  a.training ? "stats" : "running statistics (eval mode)");
+    MMVAE_REQUIRE((a.running_mean == nullptr) == (a.running_var == nullptr), "%s: running_mean / running_var go together", who);
+    MMVAE_REQUIRE(a.updates_per_group >= 0, "%s: updates_per_group=%d", who, a.updates_per_group);
+    return MMVAE_OK;
+}
 int launch_bn_finalize(const BnFinalizeArgs& a, hipStream_t s) {
+    MMVAE_TRY(bn_finalize_check(a, "bn_finalize"));
+    MMVAE_REQUIRE(a.affine && a.meanrstd, "bn_finalize: affine / meanrstd missing");
     MMVAE_REQUIRE(!a.training || a.count > 1.f, "Expected more than 1 value per channel when training");
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(a.C, 64)), dim3(64), 0, s, a);
     return mmvae_check_launch("bn_finalize");
 }
 int launch_bn_act(const BnActArgs& a, hipStream_t s) {
-    MMVAE_REQUIRE(a.ld % 8 == 0 && a.ld >= round_up(a.C, 8) && a.G * a.C <= 4096, "bn_act: C=%d ld=%d G=%d", a.C, a.ld, a.G);
+    MMVAE_REQUIRE(a.ld % 8 == 0 && a.ld >= round_up(a.C, 8) && (long long)a.G * a.C <= 4096, "bn_act: C=%d ld=%d G=%d", a.C, a.ld, a.G);
+    MMVAE_REQUIRE(a.fin.C == a.C && a.fin.G == a.G, "bn_act: fin.C=%d fin.G=%d differ from C=%d G=%d", a.fin.C, a.fin.G, a.C, a.G);
+    MMVAE_TRY(bn_finalize_check(a.fin, "bn_act"));
+    MMVAE_REQUIRE(a.r && a.a && (!a.fin.affine || a.fin.meanrstd), "bn_act: null argument");
+    MMVAE_REQUIRE(a.rows >= 1 && a.rows_per_group >= 1 && a.rows <= (long long)a.G * a.rows_per_group,
+                  "bn_act: rows=%d exceed G=%d groups of %d rows", a.rows, a.G, a.rows_per_group);
     MMVAE_REQUIRE(!a.fin.training || a.fin.count > 1.f, "Expected more than 1 value per channel when training");
     hipLaunchKernelGGL(bn_act_kernel, dim3(nblocks((long long)a.rows * ((a.C + 7) / 8), TPB, 2048)), dim3(TPB),
                        (size_t)a.G * a.C * sizeof(float2), s, a);
     return mmvae_check_launch("bn_act");
 }
 int launch_bn_bwd_apply(const BnBwdApplyArgs& a, hipStream_t s) {
-    MMVAE_REQUIRE(a.ld % 8 == 0 && a.ld >= round_up(a.C, 8), "bn_bwd_apply: C=%d ld=%d", a.C, a.ld);
+    // the [G][C] float4 table lives in LDS (64 KB): the same bound as bn_act
+    MMVAE_REQUIRE(a.C >= 1 && a.G >= 1 && a.ld % 8 == 0 && a.ld >= round_up(a.C, 8) && (long long)a.G * a.C <= 4096,
+                  "bn_bwd_apply: C=%d ld=%d G=%d", a.C, a.ld, a.G);
+    MMVAE_REQUIRE(a.db && a.r && a.dr && a.red && a.meanrstd && a.gamma, "bn_bwd_apply: null argument");
+    MMVAE_REQUIRE(a.rows >= 1 && a.rows_per_group >= 1 && a.rows <= (long long)a.G * a.rows_per_group,
+                  "bn_bwd_apply: rows=%d exceed G=%d groups of %d rows", a.rows, a.G, a.rows_per_group);
     MMVAE_LAUNCH(bn_bwd_apply_kernel, dim3(nblocks((long long)a.rows * ((a.C + 7) / 8), TPB, 2048)), dim3(TPB),
                        (size_t)a.G * a.C * sizeof(float4), s, a);
     return mmvae_check_launch("bn_bwd_apply");
 }
 int launch_sigmoid_bce(const BceArgs& a, hipStream_t s) {
     MMVAE_REQUIRE(a.G >= 1 && a.G <= 4, "bce: G=%d", a.G);
+    MMVAE_REQUIRE(a.B >= 1 && a.C >= 1 && a.H >= 1 && a.W >= 1 && a.ldl >= a.C, "bce: B=%d C=%d H=%d W=%d ldl=%d", a.B, a.C, a.H, a.W, a.ldl);
+    MMVAE_REQUIRE(a.logits && a.target && a.loss_sum, "bce: null argument");
     long long per_group = (long long)a.B * a.C * a.H * a.W;
     hipLaunchKernelGGL(sigmoid_bce_kernel, dim3(nblocks(per_group, TPB * 4, 1024), a.G), dim3(TPB), 0, s, a);
     return mmvae_check_launch("sigmoid_bce");
@@ -1125,12 +1167,20 @@ int launch_keep_mask(uint8_t* out, long long n, float p, unsigned long long seed
     return mmvae_check_launch("keep_mask");
 }
 int launch_latent3_fwd(const Latent3Args& a, hipStream_t s) {
-    MMVAE_REQUIRE(a.ldz >= a.D && a.ldz % 8 == 0, "latent3: ldz=%d", a.ldz);
+    MMVAE_REQUIRE(a.B >= 1 && a.D >= 1 && a.ldz >= a.D && a.ldz % 8 == 0 && (long long)a.B * a.ldz <= 0x3FFFFFFF,
+                  "latent3: B=%d D=%d ldz=%d", a.B, a.D, a.ldz);
+    MMVAE_REQUIRE(a.img_out && a.txt_out && a.mu && a.logvar && a.z_f32 && a.z_bf && a.kl_sum && (!a.training || a.eps), "latent3: null argument");
     MMVAE_LAUNCH(latent3_fwd_kernel, dim3(nblocks((long long)a.B * a.ldz, TPB, 256)), dim3(TPB), 0, s, a);
     return mmvae_check_launch("latent3_fwd");
 }
 int launch_latent3_bwd(const Latent3BwdArgs& a, hipStream_t s) {
     MMVAE_REQUIRE((a.loss_slots == nullptr) == (a.loss_out == nullptr), "latent3_bwd: loss_slots / loss_out go together");
+    MMVAE_REQUIRE(a.f.B >= 1 && a.f.D >= 1 && (long long)a.f.B * a.f.D <= 0x3FFFFFFF && ceil_div(a.f.B, L3B_ROWS) <= 65535,
+                  "latent3_bwd: B=%d D=%d out of range", a.f.B, a.f.D);
+    MMVAE_REQUIRE(a.f.img_out && a.f.txt_out && a.f.mu && a.f.logvar && (!a.f.training || a.f.eps), "latent3_bwd: null argument");
+    MMVAE_REQUIRE(a.d_img_out_f32 || a.d_img_out_bf, "latent3_bwd: no image gradient output (d_img_out_f32 or d_img_out_bf)");
+    MMVAE_REQUIRE(a.ld_img_out_bf == 0 || (a.ld_img_out_bf >= 2 * a.f.D && a.ld_img_out_bf % 8 == 0),
+                  "latent3_bwd: ld_img_out_bf=%d is no multiple of 8 >= 2D", a.ld_img_out_bf);
     MMVAE_LAUNCH(latent3_bwd_kernel, dim3(ceil_div(a.f.D, 64), ceil_div(a.f.B, L3B_ROWS)), dim3(TPB), 0, s, a);
     return mmvae_check_launch("latent3_bwd");
 }
@@ -1290,15 +1340,24 @@ int step_begin_with_pack(StepBeginArgs& a, const PackDesc* table_dev, const Pack
 
 int launch_embed_gather_stats(const float* table, int C, const long long* idx, int rows, int idx_rows, int rows_per_group,
                               bf16* x, int ld, float2* colstats, hipStream_t s) {
-    MMVAE_REQUIRE(ld >= C && ld % 8 == 0, "embed_gather: C=%d ld=%d", C, ld);
+    MMVAE_REQUIRE(C >= 1 && ld >= C && ld % 8 == 0, "embed_gather: C=%d ld=%d", C, ld);
+    MMVAE_REQUIRE(rows >= 1 && idx_rows >= 1 && rows_per_group >= 1 && table && idx && x, "embed_gather: rows=%d idx_rows=%d rows_per_group=%d or a null argument",
+                  rows, idx_rows, rows_per_group);
     hipLaunchKernelGGL(embed_gather_stats_kernel, dim3(ceil_div(rows, 64)), dim3(TPB), 0, s, table, C, idx, rows, idx_rows, rows_per_group, x, ld, colstats);
     return mmvae_check_launch("embed_gather_stats");
 }
 int launch_embed_scatter_add(const bf16* d, int ld, int C, const long long* idx, int rows, float* g_table, hipStream_t s) {
+    MMVAE_REQUIRE(rows >= 1 && C >= 1 && ld >= C && (long long)rows * C <= 0x3FFFFFFF && d && idx && g_table, "embed_scatter: rows=%d C=%d ld=%d or a null argument",
+                  rows, C, ld);
     hipLaunchKernelGGL(embed_scatter_add_kernel, dim3(ceil_div(rows * C, TPB)), dim3(TPB), 0, s, d, ld, C, idx, rows, g_table);
     return mmvae_check_launch("embed_scatter_add");
 }
 int launch_logsoftmax_nll(const LogSoftmaxNllArgs& a, hipStream_t s) {
+    MMVAE_REQUIRE(a.rows >= 1 && a.classes >= 1 && a.rows_per_group >= 1 && a.logits && a.words, "logsoftmax_nll: rows=%d classes=%d rows_per_group=%d or a null argument",
+                  a.rows, a.classes, a.rows_per_group);
+    MMVAE_REQUIRE(ceil_div(a.rows, a.rows_per_group) <= 4, "logsoftmax_nll: %d rows are more than 4 groups of %d", a.rows, a.rows_per_group);
+    MMVAE_REQUIRE(!a.target || a.target_rows >= 1, "logsoftmax_nll: target_rows=%d", a.target_rows);
+    MMVAE_REQUIRE(!a.dlogits || a.ld_d >= a.classes, "logsoftmax_nll: ld_d=%d < classes=%d", a.ld_d, a.classes);
     hipLaunchKernelGGL(logsoftmax_nll_kernel, dim3(ceil_div(a.rows, TPB)), dim3(TPB), 0, s, a);
     return mmvae_check_launch("logsoftmax_nll");
 }
@@ -1307,10 +1366,13 @@ int launch_cast_bf16(const float* x, long long n, bf16* out, hipStream_t s) {
     return mmvae_check_launch("cast_bf16");
 }
 int launch_colsum_f32(const float* x, int rows, int cols, float* out, hipStream_t s) {
+    MMVAE_REQUIRE(rows >= 1 && cols >= 1 && x && out, "colsum_f32: rows=%d cols=%d or a null argument", rows, cols);
     hipLaunchKernelGGL(colsum_kernel_t<float>, dim3(ceil_div(cols, 64), min(64, ceil_div(rows, 16))), dim3(TPB), 0, s, x, cols, rows, cols, out);
     return mmvae_check_launch("colsum_f32");
 }
 int launch_colsum_bf16(const bf16* x, int ld, int rows, int cols, float* out, hipStream_t s) {
+    MMVAE_REQUIRE(rows >= 1 && cols >= 1 && cols <= ld && x && out, "colsum_bf16: rows=%d cols=%d ld=%d or a null argument", rows, cols, ld);
+    // the vector kernel gives a thread one 8-column vector: ld % 8 == 0 and ld / 8 <= TPB, 16-byte aligned rows; else one thread per column
     if (ld % 8 == 0 && ld / 8 <= TPB && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
         const int RL = TPB / (ld / 8);
         hipLaunchKernelGGL(colsum_bf16_kernel, dim3(max(1, min(256, ceil_div(rows, RL * 8)))), dim3(TPB), 0, s, x, ld, rows, cols, out);
