@@ -158,7 +158,13 @@ int mmvae_mm_iw_score(mmvae_mm_t*, void* ws, size_t ws_bytes, const float* z, co
 /* Runs one named GEMM of the step `iters` times on the workspace contents of the last step (profiling aid).
  * "image_step:waist_fwd" | "image_step:chain_fwd" | "image_step:waist_bwd" | "image_step:chain_bwd" (test aid): the middle of
  * mmvae_mm_image_step again -- classifier.3 to z, or dz back to classifier.0's output gradient -- fused or unfused, in training mode
- * with dropout at kl_lambda = 1e-3, on the one-pass workspace of a step that drew its own eps and masks. */
+ * with dropout at kl_lambda = 1e-3, on the one-pass workspace of a step that drew its own eps and masks.
+ * "enc_conv1_mfma" | "enc_conv1_wgrad_mfma": the first conv and its weight gradient as the fused step launches them (two workgroups
+ * per image on the fp32 image batch, read from the first B * 2500 floats of tmp_f32; the gradient goes into the packed gradient
+ * with float atomics) -- "enc_conv1" / "enc_conv1_wgrad" are the generic GEMMs over patches1 of the unfused step.
+ * "dec_last_fused": the fused decoder tail of the step (3 BatchNorm groups, 2 with a last layer and a gradient; raw input q3, statistics
+ * st_d2, target in tmp_f32, loss weights 1 / (B * 2500), BCE sums into sums); "dec_last_fused_reduce": the same followed by the sum of
+ * its weight-gradient partials into the packed gradient, with logits / recon / dlogit written to the buffers of those names. */
 int mmvae_mm_bench_layer(mmvae_mm_t*, void* ws, size_t ws_bytes, const char* layer, int iters, void* stream);
 double mmvae_mm_layer_flops(const mmvae_mm_t*, const char* layer);        /* executed: 2*rows*N*K, zero-padded taps included */
 double mmvae_mm_layer_algo_flops(const mmvae_mm_t*, const char* layer);   /* algorithmic: the FlopCounterMode count of the reference layer */

@@ -28,18 +28,18 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4c;
 //     (row, channel octet) mapping, written as [row][32 channels], read back transposed into the accumulator layout.
 // `off0` / `off1`: byte offsets (row table + channel octet + image base) of this lane's two vectors; rows >= rows_valid
 // (PARTIAL tiles only) carry an out-of-range offset (dropped by the buffer range check) and are kept out of the sums.
+// cr_epilogue_tile_r: the same with the two MODE 1 vectors already in registers (r0 / r1: what the loads at off0 / off1 return,
+// zero for a dropped offset) -- a kernel that knows its tiles at entry issues them long before the accumulator exists.
 template <int MODE, bool PARTIAL>
-__device__ __forceinline__ void cr_epilogue_tile(const f32x16& acc, char* scr, int lane, int rows_valid, unsigned off0, unsigned off1,
-                                                 __amdgpu_buffer_rsrc_t orsrc, __amdgpu_buffer_rsrc_t rrsrc, float dsc, float dsh,
-                                                 float dmean, float drstd, float& s1, float& s2, bool store) {
+__device__ __forceinline__ void cr_epilogue_tile_r(const f32x16& acc, char* scr, int lane, int rows_valid, unsigned off0, unsigned off1,
+                                                   __amdgpu_buffer_rsrc_t orsrc, const i32x4c r0, const i32x4c r1, float dsc, float dsh,
+                                                   float dmean, float drstd, float& s1, float& s2, bool store) {
     constexpr int SP = 80;                                       // scratch row pitch: 32 x bf16 + 16
     const int r = lane & 31, h = lane >> 5, g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
     float v[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) v[j] = acc[j];
     if constexpr (MODE == 1) {
-        const i32x4c r0 = __builtin_bit_cast(i32x4c, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)off0, 0, 0));
-        const i32x4c r1 = __builtin_bit_cast(i32x4c, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)off1, 0, 0));
         *reinterpret_cast<i32x4c*>(scr + i * SP + g * 16) = r0;              // [row][channel]
         *reinterpret_cast<i32x4c*>(scr + (16 + i) * SP + g * 16) = r1;
         asm volatile("" ::: "memory");      // wave-private scratch: LDS order within a wave is issue order
@@ -109,6 +109,17 @@ __device__ __forceinline__ void cr_epilogue_tile(const f32x16& acc, char* scr, i
         __builtin_amdgcn_raw_buffer_store_b128(u1.v, orsrc, (int)off1, 0, 0);
     }
     asm volatile("" ::: "memory");
+}
+template <int MODE, bool PARTIAL>
+__device__ __forceinline__ void cr_epilogue_tile(const f32x16& acc, char* scr, int lane, int rows_valid, unsigned off0, unsigned off1,
+                                                 __amdgpu_buffer_rsrc_t orsrc, __amdgpu_buffer_rsrc_t rrsrc, float dsc, float dsh,
+                                                 float dmean, float drstd, float& s1, float& s2, bool store) {
+    i32x4c r0 = {0, 0, 0, 0}, r1 = {0, 0, 0, 0};
+    if constexpr (MODE == 1) {
+        r0 = __builtin_bit_cast(i32x4c, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)off0, 0, 0));
+        r1 = __builtin_bit_cast(i32x4c, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)off1, 0, 0));
+    }
+    cr_epilogue_tile_r<MODE, PARTIAL>(acc, scr, lane, rows_valid, off0, off1, orsrc, r0, r1, dsc, dsh, dmean, drstd, s1, s2, store);
 }
 
 }  // namespace

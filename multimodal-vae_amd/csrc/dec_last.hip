@@ -8,12 +8,14 @@
 //   input grad   dA[pixel][ch]   = patch[pixel][16 taps] . W^T[16 taps][32 ch]  one MFMA per 32 pixels, patch = the 4x4
 //                                  window of dlogit around the pixel
 //   weight grad  dW[ch][tap]     = sum over pixels A[pixel][ch] . patch[pixel][tap]              transposed LDS reads
-// One workgroup (8 waves) owns one image: raw input -> BatchNorm + Swish while staging (A is never written to memory),
-// P and the patches live in LDS, the input gradient leaves through the accumulator epilogue of the conv kernels
-// (d-Swish of the producer, BatchNorm-backward sums, 16-byte stores), the weight-gradient partial goes to the slab.
+// A workgroup (8 waves) owns an image (evaluation form) or half of one (training form): raw input -> BatchNorm + Swish while
+// staging (A is never written to memory), P and the patches live in LDS, the input gradient leaves through the accumulator
+// epilogue of the conv kernels (d-Swish of the producer, BatchNorm-backward sums, 16-byte stores), the weight-gradient partial
+// goes to the slab.
 #include "thin.h"
 #include "bn_dev.h"
 #include "convres_epi.h"
+#include "thin_split_geo.h"
 
 namespace {
 
@@ -40,15 +42,12 @@ __device__ __forceinline__ bf16x8 tr_pair_d(const char* a0, const char* a1) {
     return u.v;
 }
 
-// IW: the importance-weighted evaluation form (DecLastFusedArgs::loglik): forward only, one log p(x|z) per image, no other output
-template <bool IW>
+// The importance-weighted evaluation form (DecLastFusedArgs::loglik), one workgroup per image: forward only, one log p(x|z) per
+// image, no other output.  (The training form is dec_last_half_kernel below.)
 __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const A_s = smem + DL_OFF_A;
     float* const P_s = reinterpret_cast<float*>(smem + DL_OFF_P);
-    char* const pat_s = smem + DL_OFF_P;
-    float* const dl_s = reinterpret_cast<float*>(smem + DL_OFF_DL);
-    char* const scr_s = smem + DL_OFF_SCR;
     float2* const aff_s = reinterpret_cast<float2*>(smem + DL_OFF_TAB);
     float2* const mr_s = aff_s + DL_C;
     __shared__ float part[DL_WAVES];
@@ -59,7 +58,6 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
     const int n_in_g = blockIdx.x, g = blockIdx.y;
     const long long n = (long long)g * a.B + n_in_g;
     const BnFinalizeArgs& f = a.fin;
-    const bool bwd = g < a.bwd_groups;
 
     // ---- raw image: loads in flight while the tables are made and the buffers cleared
     constexpr int NV = DL_NPIX * 4, IT = (NV + DL_NTHR - 1) / DL_NTHR;          // 16-byte vectors of the image
@@ -74,29 +72,17 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
         bn_channel_tables(f, g, tid, aff, mr);
         aff_s[tid] = aff; mr_s[tid] = mr;
     }
-    if (!IW && blockIdx.x == 0 && blockIdx.y == 0) {         // the tables backward reads + running statistics: once
-        for (int i = tid; i < f.G * DL_C; i += DL_NTHR) {
-            float2 aff, mr;
-            bn_channel_tables(f, i / DL_C, i % DL_C, aff, mr);
-            f.affine[i] = aff; f.meanrstd[i] = mr;
-        }
-        bn_running_update(f, tid, DL_NTHR);
-    }
     {
         const i32x4c z = {0, 0, 0, 0};
         for (int i = tid * 16; i < (DL_ROWS - DL_NPIX) * DL_AP; i += DL_NTHR * 16)      // padding pixel rows of A
             *reinterpret_cast<i32x4c*>(A_s + DL_NPIX * DL_AP + i) = z;
-        if (!IW)
-            for (int i = tid; i < DL_DLW * DL_DLW; i += DL_NTHR) dl_s[i] = 0.f;
     }
-    // weight fragments (fp32 (32, 1, 4, 4) -> bf16): forward B[k = ch][j = tap] for the two k-steps, input gradient B[k = tap][j = ch]
-    bf16x8 wf[2], wd;
+    // weight fragments (fp32 (32, 1, 4, 4) -> bf16): forward B[k = ch][j = tap] for the two k-steps
+    bf16x8 wf[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int j = 0; j < 8; ++j) wf[ks][j] = r < 16 ? (bf16)a.w[(ks * 16 + 8 * h + j) * 16 + r] : (bf16)0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) wd[j] = (bf16)a.w[r * 16 + 8 * h + j];
     __syncthreads();
     // ---- stage: BatchNorm + Swish -> A tile
     {
@@ -132,7 +118,7 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
         }
     }
     __syncthreads();
-    if constexpr (IW) {
+    {
         // ---- log p(x|z) = sum over pixels of t*l - softplus(l) in fp32 from the logit l (not clamped like the BCE below);
         //      the target is the image of the example this particle row belongs to
         const float* const timg = a.target + (long long)(n / a.rows_per_target) * (DL_OH * DL_OW);
@@ -160,35 +146,197 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
             for (int w = 0; w < DL_WAVES; ++w) s += part[w];
             a.loglik[n] = s;
         }
-        return;
     }
-    // ---- logits by overlap-add, sigmoid, BCE and its gradient
-    float loss = 0.f;
-    for (int o = tid; o < DL_OH * DL_OW; o += DL_NTHR) {
-        const int oy = o / DL_OW, ox = o - oy * DL_OW;
-        const int kh0 = (oy + 1) & 1, kw0 = (ox + 1) & 1;
-        const int iy0 = (oy + 1 - kh0) >> 1, ix0 = (ox + 1 - kw0) >> 1;
-        float acc = 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Training form on half images (thin_split_geo.h, namespace dls): grid (B, G, 2), 76 KB of LDS, two workgroups resident per CU so
+// that the barriers and load round trips of one overlap the work of the other.  Workgroup z stages its 13 / 12 input rows and a
+// halo row on each side (outside the image: zero, so P = 0 there and the overlap-add needs no row test), makes P for those, the
+// logits of the output rows its pixels' gradient windows touch (loss and the optional outputs for the owned rows only), and the
+// patches, input gradient, BatchNorm-backward sums and weight-gradient partial of its own pixels.  Loads whose addresses are
+// known at entry leave the dependent chain: the targets are fetched before the first barrier and parked in the dlogit buffer
+// (dec_last_ca_kernel's fetch_targets), the saved r vectors of the epilogue are issued in front of the logits pass.
+// The BatchNorm-backward sums of the 8 waves are added in LDS and leave as ONE pair of float atomics per channel and workgroup:
+// same-address float atomics serialise at the memory side (about 11 ns each here), and 8 waves x 1024 workgroups on 16 slot rows
+// were 6 us of the launch.  (4 waves per workgroup: 2 us slower alone, 4 us in the step.)
+__global__ __launch_bounds__(dls::MAX_WAVES * 64, dls::MAX_WAVES / 2) void dec_last_half_kernel(const DecLastFusedArgs a) {
+    constexpr int WAVES = dls::MAX_WAVES, NTHR = WAVES * 64;
+    static_assert( DL_AP == dls::AP && DL_PP == dls::PP && DL_DLW == dls::DLW && DL_C == dls::C && DL_IW == dls::IW &&
+                  DL_NPIX == dls::NPIX && DL_OW == dls::OW, "thin_split_geo.h describes this layer");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* const A_s = smem + dls::OFF_A;
+    float* const P_s = reinterpret_cast<float*>(smem + dls::OFF_P);
+    char* const pat_s = smem + dls::OFF_P;
+    float* const dl_s = reinterpret_cast<float*>(smem + dls::OFF_DL);
+    char* const scr_s = smem + dls::OFF_DL;
+    float2* const aff_s = reinterpret_cast<float2*>(smem + dls::OFF_TAB);
+    float2* const mr_s = aff_s + DL_C;
+    __shared__ float part[dls::MAX_WAVES];
+    __shared__ float2 wsum[dls::MAX_WAVES][DL_C];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int n_in_g = blockIdx.x, g = blockIdx.y, z = blockIdx.z;
+    const long long n = (long long)g * a.B + n_in_g;
+    const BnFinalizeArgs& f = a.fin;
+    const bool bwd = g < a.bwd_groups;
+    const int st_pix = dls::st_pix(z), own_pix = dls::own_pix(z), own_tiles = dls::own_tiles(z);
+
+    // ---- raw rows st_lo .. st_lo + st_rows - 1 of the image (contiguous pixels; outside the image: zero), in flight while the
+    //      tables are made
+    constexpr int NV = dls::ST_ROWS_MAX * 4, IT = NV / NTHR;                     // 16-byte vectors of the A tile
+    static_assert(NV % NTHR == 0, "whole trips");
+    i32x4c rv[IT];
+    const int gp0 = dls::st_lo(z) * DL_IW;                   // image pixel of staged pixel 0
 #pragma unroll
-        for (int ty = 0; ty < 2; ++ty)
+    for (int it = 0; it < IT; ++it) {
+        const int v = tid + it * NTHR, gp = gp0 + (v >> 2);
+        rv[it] = i32x4c{0, 0, 0, 0};
+        if ((v >> 2) < st_pix && (unsigned)gp < (unsigned)DL_NPIX)
+            rv[it] = *reinterpret_cast<const i32x4c*>(a.r + ((size_t)n * DL_NPIX + gp) * DL_C + (size_t)(v & 3) * 8);
+    }
+    // targets of the dlogit buffer's rows (halo columns, rows outside the image: zero)
+    constexpr int ND = dls::LO_ROWS_MAX * DL_DLW, DT = (ND + NTHR - 1) / NTHR;
+    float tv[DT];
+    {
+        const float* const timg = a.target ? a.target + (long long)n_in_g * (DL_OH * DL_OW) : nullptr;
+        const int lo_lo = dls::lo_lo(z), lo_rows = dls::lo_rows(z);
 #pragma unroll
-            for (int tx = 0; tx < 2; ++tx) {
-                const int iy = iy0 - ty, ix = ix0 - tx;
-                if ((unsigned)iy < (unsigned)DL_IH && (unsigned)ix < (unsigned)DL_IW)
-                    acc += P_s[(iy * DL_IW + ix) * 16 + (kh0 + 2 * ty) * 4 + kw0 + 2 * tx];
+        for (int k = 0; k < DT; ++k) {
+            const int i = tid + k * NTHR;
+            const int l = i / DL_DLW, c = i - l * DL_DLW, oy = lo_lo + l;
+            tv[k] = 0.f;
+            if (timg && l < lo_rows && c >= 1 && c <= DL_OW && (unsigned)oy < (unsigned)DL_OH) tv[k] = timg[oy * DL_OW + c - 1];
+        }
+    }
+    if (tid < DL_C) {
+        float2 aff, mr;
+        bn_channel_tables(f, g, tid, aff, mr);
+        aff_s[tid] = aff; mr_s[tid] = mr;
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {      // the tables backward reads + running statistics: once
+        for (int i = tid; i < f.G * DL_C; i += NTHR) {
+            float2 aff, mr;
+            bn_channel_tables(f, i / DL_C, i % DL_C, aff, mr);
+            f.affine[i] = aff; f.meanrstd[i] = mr;
+        }
+        bn_running_update(f, tid, NTHR);
+    }
+    // weight fragments (fp32 (32, 1, 4, 4) -> bf16): forward B[k = ch][j = tap] for the two k-steps, input gradient B[k = tap][j = ch]
+    bf16x8 wf[2], wd;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wf[ks][j] = r < 16 ? (bf16)a.w[(ks * 16 + 8 * h + j) * 16 + r] : (bf16)0.f;
+    {
+        const f32x4 w0 = *reinterpret_cast<const f32x4*>(a.w + r * 16 + 8 * h), w1 = *reinterpret_cast<const f32x4*>(a.w + r * 16 + 8 * h + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { wd[j] = (bf16)w0[j]; wd[4 + j] = (bf16)w1[j]; }
+    }
+#pragma unroll
+    for (int k = 0; k < DT; ++k) {
+        const int i = tid + k * NTHR;
+        if (i < ND) dl_s[i] = tv[k];
+    }
+    __syncthreads();
+    // ---- stage: BatchNorm + Swish -> A tile (rows outside the image and the padding pixel rows: zero)
+    {
+        const int cv = tid & 3;                              // NTHR % 4 == 0: a thread keeps its channel octet
+        float sc[8], sh[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float2 t = aff_s[cv * 8 + j]; sc[j] = t.x; sh[j] = t.y; }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int v = tid + it * NTHR, gp = gp0 + (v >> 2);
+            bf16x8 o;
+            if ((v >> 2) < st_pix && (unsigned)gp < (unsigned)DL_NPIX) {
+                const bf16x8 x = __builtin_bit_cast(bf16x8, rv[it]);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = (bf16)swish_fast((float)x[j] * sc[j] + sh[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = (bf16)0.f;
             }
-        const long long oidx = n * (DL_OH * DL_OW) + o;      // NCHW, one channel
-        const float p = __builtin_amdgcn_rcpf(1.0f + __expf(-acc));
-        if (a.logits) a.logits[oidx] = acc;
-        if (a.recon) a.recon[oidx] = p;
-        if (a.target) {
-            const float t = a.target[(long long)n_in_g * (DL_OH * DL_OW) + o];
-            const float lp = fmaxf(__logf(p), -100.f), lq = fmaxf(__logf(1.0f - p), -100.f);       // BCE log clamp
-            loss += -(t * lp + (1.0f - t) * lq);
-            const float pq = p * (1.0f - p);
-            const float dl = a.coef[g] * (p - t) / fmaxf(pq, 1e-12f) * pq;
-            if (a.dlogit) a.dlogit[oidx] = dl;
-            dl_s[(oy + 1) * DL_DLW + ox + 1] = dl;
+            *reinterpret_cast<bf16x8*>(A_s + (v >> 2) * DL_AP + cv * 16) = o;
+        }
+    }
+    __syncthreads();
+    // ---- forward: P[staged pixel][tap]
+    for (int t = wave; t < dls::st_tiles(z); t += WAVES) {
+        f32x16 acc;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+        const char* ap = A_s + (t * 32 + r) * DL_AP + h * 16;
+        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(ap), a1 = *reinterpret_cast<const bf16x8*>(ap + 32);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wf[1], acc, 0, 0, 0);
+        if (r < 16) {                                        // lane = tap, register j = pixel (j&3) + 8*(j>>2) + 4h of the tile
+#pragma unroll
+            for (int j = 0; j < 16; ++j) P_s[(t * 32 + (j & 3) + 8 * (j >> 2) + 4 * h) * 16 + r] = acc[j];
+        }
+    }
+    // the saved r vectors of this wave's input-gradient tiles (this lane: pixels (lane&15) and 16 + (lane&15), channel octet lane>>4)
+    constexpr int NT = (dls::OWN_ROWS_MAX / 32 + WAVES - 1) / WAVES;
+    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
+        a.db, 0, (int)((size_t)a.bwd_groups * a.B * DL_NPIX * DL_C * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<bf16*>(a.r), 0, (int)((size_t)a.bwd_groups * a.B * DL_NPIX * DL_C * 2), 0x00020000);
+    unsigned off0[NT], off1[NT];
+    i32x4c rr0[NT], rr1[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+        const int t = wave + k * WAVES;
+        const unsigned base = (unsigned)((n * DL_NPIX + dls::own_lo(z) * DL_IW + t * 32) * (DL_C * 2)) + (unsigned)((lane >> 4) * 16);
+        const int p0 = t * 32 + (lane & 15), p1 = p0 + 16;
+        off0[k] = p0 < own_pix ? base + (unsigned)((lane & 15) * (DL_C * 2)) : 0x40000000u;
+        off1[k] = p1 < own_pix ? base + (unsigned)((16 + (lane & 15)) * (DL_C * 2)) : 0x40000000u;
+        rr0[k] = i32x4c{0, 0, 0, 0}; rr1[k] = i32x4c{0, 0, 0, 0};
+        if (bwd) {
+            rr0[k] = __builtin_bit_cast(i32x4c, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)off0[k], 0, 0));
+            rr1[k] = __builtin_bit_cast(i32x4c, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)off1[k], 0, 0));
+        }
+    }
+    __syncthreads();
+    // ---- logits of output rows lo_lo .. lo_lo + lo_rows - 1 by overlap-add, sigmoid, BCE and its gradient
+    float loss = 0.f;
+    {
+        const int lo_lo = dls::lo_lo(z), st_lo = dls::st_lo(z), out_lo = dls::out_lo(z), out_hi = dls::out_hi(z);
+        const float coef = a.coef[g];
+        for (int o = tid; o < dls::lo_rows(z) * DL_OW; o += NTHR) {
+            const int l = o / DL_OW, ox = o - l * DL_OW, oy = lo_lo + l;
+            if ((unsigned)oy >= (unsigned)DL_OH) continue;
+            const int kh0 = (oy + 1) & 1, kw0 = (ox + 1) & 1;
+            const int iy0 = (oy + 1 - kh0) >> 1, ix0 = (ox + 1 - kw0) >> 1;
+            float acc = 0.f;
+#pragma unroll
+            for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+                for (int tx = 0; tx < 2; ++tx) {
+                    // (rows outside the image are staged as zeros, i.e. P = 0 there; a column outside is masked, not branched on)
+                    const int iy = iy0 - ty, ix = ix0 - tx, ixc = min(max(ix, 0), DL_IW - 1);
+                    const float pv = P_s[((iy - st_lo) * DL_IW + ixc) * 16 + (kh0 + 2 * ty) * 4 + kw0 + 2 * tx];
+                    acc += ix == ixc ? pv : 0.f;
+                }
+            const bool owned = oy >= out_lo && oy < out_hi;
+            const long long oidx = n * (DL_OH * DL_OW) + oy * DL_OW + ox;       // NCHW, one channel
+            const float p = __builtin_amdgcn_rcpf(1.0f + __expf(-acc));
+            if (owned) {
+                if (a.logits) a.logits[oidx] = acc;
+                if (a.recon) a.recon[oidx] = p;
+            }
+            if (a.target) {
+                const float t = dl_s[l * DL_DLW + ox + 1];
+                const float pq = p * (1.0f - p);
+                const float dl = coef * (p - t) / fmaxf(pq, 1e-12f) * pq;
+                if (owned) {
+                    const float lp = fmaxf(__logf(p), -100.f), lq = fmaxf(__logf(1.0f - p), -100.f);       // BCE log clamp
+                    loss += -(t * lp + (1.0f - t) * lq);
+                    if (a.dlogit) a.dlogit[oidx] = dl;
+                }
+                dl_s[l * DL_DLW + ox + 1] = dl;
+            }
         }
     }
     if (a.loss_sum) {
@@ -198,71 +346,66 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
     __syncthreads();
     if (a.loss_sum && tid == 0) {
         float s = 0.f;
-        for (int w = 0; w < DL_WAVES; ++w) s += part[w];
+        for (int w = 0; w < WAVES; ++w) s += part[w];
         atomicAdd(a.loss_sum + (blockIdx.x % MMVAE_LOSS_SLOTS) * 16 + g, s);
     }
     if (!bwd) return;
-    // ---- patches[pixel][tap] = dlogit(2iy-1+kh, 2ix-1+kw) as bf16 (P is dead: same buffer); padding rows zero
-    for (int px = tid; px < DL_ROWS; px += DL_NTHR) {
-        bf16x8 lo, hi;
-        if (px < DL_NPIX) {
-            const int iy = px / DL_IW, ix = px - iy * DL_IW;
-            const float* d0 = dl_s + (2 * iy) * DL_DLW + 2 * ix;         // (2iy-1+kh) + 1 halo row, (2ix-1+kw) + 1 halo column
+    // ---- patches[owned pixel][tap] = dlogit(2iy-1+kh, 2ix-1+kw) as bf16 (P is dead: same buffer); two threads per pixel
+    //      (kernel rows 0-1 / 2-3); padding rows zero
+    for (int i = tid; i < 2 * own_tiles * 32; i += NTHR) {
+        const int j = i >> 1, half = i & 1;
+        bf16x8 o;
+        if (j < own_pix) {
+            const float* d0 = dl_s + dls::dl_window(z, j, half);
 #pragma unroll
-            for (int kw = 0; kw < 4; ++kw) {
-                lo[kw] = (bf16)d0[kw]; lo[4 + kw] = (bf16)d0[DL_DLW + kw];
-                hi[kw] = (bf16)d0[2 * DL_DLW + kw]; hi[4 + kw] = (bf16)d0[3 * DL_DLW + kw];
-            }
+            for (int kw = 0; kw < 4; ++kw) { o[kw] = (bf16)d0[kw]; o[4 + kw] = (bf16)d0[DL_DLW + kw]; }
         } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { lo[j] = (bf16)0.f; hi[j] = (bf16)0.f; }
+            for (int e = 0; e < 8; ++e) o[e] = (bf16)0.f;
         }
-        *reinterpret_cast<bf16x8*>(pat_s + px * DL_PP) = lo;
-        *reinterpret_cast<bf16x8*>(pat_s + px * DL_PP + 16) = hi;
+        *reinterpret_cast<bf16x8*>(pat_s + j * DL_PP + half * 16) = o;
     }
-    __syncthreads();
-    // ---- input gradient: one MFMA per 32 pixels, then the conv kernels' accumulator epilogue (lane = channel)
+    __syncthreads();                                         // the dlogit buffer is dead: the waves' epilogue scratch takes its place
+    // ---- input gradient: one MFMA per 32 owned pixels, then the conv kernels' accumulator epilogue (lane = channel)
     {
-        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
-            a.db, 0, (int)((size_t)a.bwd_groups * a.B * DL_NPIX * DL_C * 2), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<bf16*>(a.r), 0, (int)((size_t)a.bwd_groups * a.B * DL_NPIX * DL_C * 2), 0x00020000);
         const float2 af = aff_s[r], mr = mr_s[r];
         float s1 = 0.f, s2 = 0.f;
-        char* const scr = scr_s + wave * 2560;
-        for (int t = wave; t < DL_TILES; t += DL_WAVES) {
-            f32x16 acc;
+        char* const scr = scr_s + wave * dls::SCR;
 #pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-            const bf16x8 pa = *reinterpret_cast<const bf16x8*>(pat_s + (t * 32 + r) * DL_PP + h * 16);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, wd, acc, 0, 0, 0);
-            // this lane's two output vectors: pixels (lane&15) and 16 + (lane&15) of the tile, channel octet lane>>4
-            const unsigned base = (unsigned)((n * DL_NPIX + t * 32) * (DL_C * 2)) + (unsigned)((lane >> 4) * 16);
-            const int p0 = t * 32 + (lane & 15), p1 = p0 + 16;
-            const unsigned off0 = p0 < DL_NPIX ? base + (unsigned)((lane & 15) * (DL_C * 2)) : 0x40000000u;
-            const unsigned off1 = p1 < DL_NPIX ? base + (unsigned)((16 + (lane & 15)) * (DL_C * 2)) : 0x40000000u;
-            const int left = DL_NPIX - t * 32;
-            if (left >= 32) cr_epilogue_tile<1, false>(acc, scr, lane, 32, off0, off1, orsrc, rrsrc, af.x, af.y, mr.x, mr.y, s1, s2, true);
-            else cr_epilogue_tile<1, true>(acc, scr, lane, left, off0, off1, orsrc, rrsrc, af.x, af.y, mr.x, mr.y, s1, s2, true);
+        for (int k = 0; k < NT; ++k) {
+            const int t = wave + k * WAVES;
+            if (t < own_tiles) {
+                f32x16 acc;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+                const bf16x8 pa = *reinterpret_cast<const bf16x8*>(pat_s + (t * 32 + r) * DL_PP + h * 16);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, wd, acc, 0, 0, 0);
+                const int left = own_pix - t * 32;
+                if (left >= 32) cr_epilogue_tile_r<1, false>(acc, scr, lane, 32, off0[k], off1[k], orsrc, rr0[k], rr1[k], af.x, af.y, mr.x, mr.y, s1, s2, true);
+                else cr_epilogue_tile_r<1, true>(acc, scr, lane, left, off0[k], off1[k], orsrc, rr0[k], rr1[k], af.x, af.y, mr.x, mr.y, s1, s2, true);
+            }
         }
         const float t1 = s1 + __shfl_xor(s1, 32, 64), t2 = s2 + __shfl_xor(s2, 32, 64);
-        if (h == 0) {
-            const int slot = (int)(blockIdx.x + wave) % MMVAE_STAT_SLOTS;
-            float2* d = a.red + ((size_t)g * MMVAE_STAT_SLOTS + slot) * DL_C + r;
-            atomicAdd(&d->x, t1);
-            atomicAdd(&d->y, t2);
-        }
+        if (h == 0) wsum[wave][r] = float2{t1, t2};
     }
     __syncthreads();                                         // the epilogue scratch becomes the waves' dW partials
-    // ---- weight gradient dW[ch][tap] = A^T . patches over the 640 pixel rows: 40 k-steps of 16 rows shared by the waves
+    if (tid < DL_C) {
+        float2 t = wsum[0][tid];
+        for (int w = 1; w < WAVES; ++w) { t.x += wsum[w][tid].x; t.y += wsum[w][tid].y; }
+        const int slot = (int)(blockIdx.x + 8 * z) % MMVAE_STAT_SLOTS;
+        float2* d = a.red + ((size_t)g * MMVAE_STAT_SLOTS + slot) * DL_C + tid;
+        atomicAdd(&d->x, t.x);
+        atomicAdd(&d->y, t.y);
+    }
+    // ---- weight gradient dW[ch][tap] = A^T . patches over the owned pixel rows (owned pixel j is staged pixel j + 25)
     {
         const int g4 = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
         f32x16 acc;
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-        for (int ks = wave; ks < DL_ROWS / 16; ks += DL_WAVES) {
+        for (int ks = wave; ks < own_tiles * 2; ks += WAVES) {
             const int row = ks * 16 + 8 * h + q;
-            const char* a0 = A_s + row * DL_AP + (16 * (g4 & 1) + 4 * p) * 2;
+            const char* a0 = A_s + (row + DL_IW) * DL_AP + (16 * (g4 & 1) + 4 * p) * 2;
             const char* b0 = pat_s + row * DL_PP + (4 * p) * 2;          // taps 0..15 for both column halves (16..31 unused)
             const bf16x8 af2 = tr_pair_d(a0, a0 + 4 * DL_AP);
             const bf16x8 bf2 = tr_pair_d(b0, b0 + 4 * DL_PP);
@@ -277,11 +420,11 @@ __global__ __launch_bounds__(DL_NTHR) void dec_last_mfma_kernel(const DecLastFus
     __syncthreads();
     {
         const float* wred = reinterpret_cast<const float*>(scr_s);
-        float* dst = a.wslab + ((size_t)g * gridDim.x + blockIdx.x) * DL_C * 16;
-        for (int i = tid; i < DL_C * 16; i += DL_NTHR) {
+        float* dst = a.wslab + (((size_t)g * gridDim.x + blockIdx.x) * dls::HALVES + z) * DL_C * 16;
+        for (int i = tid; i < DL_C * 16; i += NTHR) {
             float s = 0.f;
 #pragma unroll
-            for (int w = 0; w < DL_WAVES; ++w) s += wred[w * DL_C * 16 + i];
+            for (int w = 0; w < WAVES; ++w) s += wred[w * DL_C * 16 + i];
             dst[i] = s;
         }
     }
@@ -619,7 +762,6 @@ int launch_dec_last_ca(const DecLastFusedArgs& a, hipStream_t s) {
     return mmvae_check_launch("dec_last_ca");
 }
 
-// strips = 1: one workgroup per image
 bool dec_last_mfma_applies(const DecLastFusedArgs& a) {
     return a.Cin == 32 && a.Cout == 1 && a.IH == DL_IH && a.IW == DL_IW && a.act == ACT_SWISH && mmvae_knob("dec_last_mfma", 1) != 0 &&
            (size_t)a.G * a.B * DL_NPIX * DL_C * 2 < 0x40000000ull;
@@ -627,14 +769,17 @@ bool dec_last_mfma_applies(const DecLastFusedArgs& a) {
 int launch_dec_last_mfma(const DecLastFusedArgs& a, hipStream_t s) {
     static std::atomic<unsigned> attr_set{0};
     if (mmvae_first_use_on_device(attr_set)) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_last_mfma_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS);   // (+ 32 B static)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_last_mfma_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_last_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS);   // (+ 32 B static)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_last_half_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dls::LDS);
     }
     if (a.loglik) {
         MMVAE_REQUIRE(a.target && a.rows_per_target >= 1 && a.bwd_groups == 0 && !a.fin.training, "dec_last_mfma: importance-weighted form arguments");
-        MMVAE_LAUNCH(dec_last_mfma_kernel<true>, dim3(a.B, a.G), dim3(DL_NTHR), DL_LDS, s, a);
+        MMVAE_LAUNCH(dec_last_mfma_kernel, dim3(a.B, a.G), dim3(DL_NTHR), DL_LDS, s, a);
         return mmvae_check_launch("dec_last_mfma_iw");
     }
-    MMVAE_LAUNCH(dec_last_mfma_kernel<false>, dim3(a.B, a.G), dim3(DL_NTHR), DL_LDS, s, a);
-    return mmvae_check_launch("dec_last_mfma");
+    MMVAE_LAUNCH(dec_last_half_kernel, dim3(a.B, a.G, dls::HALVES), dim3(dls::MAX_WAVES * 64), dls::LDS, s, a);
+    return mmvae_check_launch("dec_last_half");
 }
+// weight-gradient partials [32][16] an image leaves in wslab: what the kernels index by and what the host sizes the slab, the
+// chunk count and the reduce job from
+int dec_last_wgrad_partials(const DecLastFusedArgs& a) { return dec_last_mfma_applies(a) ? dls::HALVES : dec_last_fused_strips(a.IH); }

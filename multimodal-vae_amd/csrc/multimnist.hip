@@ -544,7 +544,8 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
 // z_bf: [groups*B][ldz] with column D == 1.0 (folded bias).  The last layer is the fused direct kernel
 // ConvTranspose2d(32,1) + sigmoid (+ BCE and its gradient when `bce` is given).
 // BatchNorm finalize of hallucinate.7 + the thin last layer + (for the first bwd_groups groups) its gradients: thin.h
-int fused_tail(MMPlan& P, int groups, int training, const ConvTLastFwdArgs* last, int last_groups, int fused_bwd_groups, hipStream_t s) {
+int fused_tail(MMPlan& P, int groups, int training, const ConvTLastFwdArgs* last, int last_groups, int fused_bwd_groups, hipStream_t s,
+               float* dlogit_dump = nullptr) {
     MMPlan::W& w = P.w;
     const int B = P.B;
     const ConvL& L = P.convT[2];
@@ -560,12 +561,12 @@ int fused_tail(MMPlan& P, int groups, int training, const ConvTLastFwdArgs* last
     f.num_batches_tracked = P.buf.bn_nbt + b.idx;
     f.updates_per_group = 1; f.affine = w.aff_d[2]; f.meanrstd = w.mr_d[2]; f.eps = BN_EPS; f.momentum = BN_MOM; f.training = training;
     f.skip_update_mask = groups > 1 ? P.dec_skip_mask : 0u;
-    x.target = last->target; x.logits = last->logits; x.recon = last->recon; x.dlogit = nullptr;
+    x.target = last->target; x.logits = last->logits; x.recon = last->recon; x.dlogit = dlogit_dump;      // (the step keeps dlogit in LDS)
     for (int k = 0; k < 4; ++k) x.coef[k] = last->coef[k];
     x.loss_sum = last->loss_sum;
     if (last->loglik) { x.loglik = last->loglik; x.rows_per_target = last->rows_per_target; x.B = last->rows; }
     if (x.bwd_groups > 0) {
-        const int chunks = x.bwd_groups * B * (dec_last_mfma_applies(x) ? 1 : dec_last_fused_strips(25));
+        const int chunks = x.bwd_groups * B * dec_last_wgrad_partials(x);
         x.wslab = P.slab.take((size_t)chunks * 32 * 16);
         MMVAE_REQUIRE(x.wslab != nullptr, "fused decoder tail: the weight-gradient slab pool is exhausted");
         x.db = w.d3; x.red = w.red_d[2];
@@ -1444,15 +1445,34 @@ int mm_bench_layer(MMPlan* P, void* ws, size_t wsb, const char* layer, int iters
         return MMVAE_OK;
     }
     MMVAE_TRY(use_ws(P, ws, wsb, false));
-    if (std::string(layer) == "dec_last_fused") {        // fused decoder tail as in the training step (2 of 3 passes carry a gradient)
+    // fused decoder tail as in the training step (2 of 3 passes carry a gradient).  "dec_last_fused_reduce": followed by the sum of
+    // its weight-gradient partials into the packed gradient (the step makes it on a side stream), and with the optional outputs
+    // logits / recon / dlogit written to the workspace buffers of those names
+    if (std::string(layer) == "dec_last_fused" || std::string(layer) == "dec_last_fused_reduce") {
+        const bool reduce = std::string(layer) == "dec_last_fused_reduce";
         ConvTLastFwdArgs last{};
         last.target = (const float*)P->w.tmp_f32; last.loss_sum = P->w.sums;
         last.coef[0] = last.coef[1] = 1.f / (float)(P->B * NPIX);
+        if (reduce) { last.logits = P->w.logits; last.recon = P->w.recon; }
         for (int i = 0; i < iters; ++i) {
             P->slab.reset(P->w.slab, P->w.slab_floats);
-            MMVAE_TRY(fused_tail(*P, 3, 1, &last, 2, 2, s));
+            MMVAE_TRY(fused_tail(*P, 3, 1, &last, 2, 2, s, reduce ? P->w.dlogit : nullptr));
+            if (reduce) MMVAE_TRY(launch_wgrad_reduce(&P->slab, s));
             P->slab.jobs.clear(); P->slab.ring_jobs.clear();
         }
+        return MMVAE_OK;
+    }
+    // conv1.hip's forms as the fused step launches them; the image batch is read from the first B * 2500 floats of tmp_f32
+    if (std::string(layer) == "enc_conv1_mfma") {
+        const PackDesc& d = P->pk.d[P->conv[0].pk_fwd[0]];
+        for (int i = 0; i < iters; ++i)
+            MMVAE_TRY(launch_conv1_fwd_mfma(P->w.tmp_f32, P->B, P->buf.packed + d.dst_off, d.Kpad, P->w.r1, P->w.a1, s));
+        return MMVAE_OK;
+    }
+    if (std::string(layer) == "enc_conv1_wgrad_mfma") {       // float atomics into the packed gradient: no slab, no reduce launch
+        const PackDesc& gd = P->gk.d[P->conv[0].gk[0]];
+        for (int i = 0; i < iters; ++i)
+            MMVAE_TRY(launch_conv1_wgrad_mfma(P->w.tmp_f32, P->B, P->w.d1e, P->buf.gpk + gd.dst_off, gd.Kpad, s));
         return MMVAE_OK;
     }
     WgradParams wg{};
@@ -1473,7 +1493,9 @@ double mm_layer_flops(const MMPlan* Pc, const char* layer) {
     MMPlan& P = *const_cast<MMPlan*>(Pc);
     GemmParams g{};
     WgradParams wg{};
-    if (std::string(layer) == "dec_last_fused") return 3.0 * 2.0 * 2 * P.B * 625 * 16 * 32;      // forward + both gradients, 2 passes
+    if (std::string(layer) == "dec_last_fused" || std::string(layer) == "dec_last_fused_reduce")
+        return 3.0 * 2.0 * 2 * P.B * 625 * 16 * 32;      // forward + both gradients, 2 passes
+    if (std::string(layer) == "enc_conv1_mfma" || std::string(layer) == "enc_conv1_wgrad_mfma") return 2.0 * P.B * 640 * 16 * 32;   // 20 tiles of 32 rows
     if (P.bound && layer_wgrad(P, layer, wg)) return wgrad_flops(wg);
     if (!P.bound || !layer_gemm(P, layer, g)) return -1.0;
     return gemm_flops(g);
@@ -1497,6 +1519,8 @@ double mm_layer_algo_flops(const MMPlan* Pc, const char* layer) {
         if (name == d + "_dgrad" || name == d + "_wgrad") return conv(P.convT[l], 2 * B);
     }
     if (name == "dec_last_wgrad" || name == "dec_last_dgrad_gemm") return conv(P.convT[3], 2 * B);
+    if (name == "dec_last_fused" || name == "dec_last_fused_reduce") return 3.0 * conv(P.convT[3], 2 * B);
+    if (name == "enc_conv1_mfma" || name == "enc_conv1_wgrad_mfma") return conv(P.conv[0], B);
     return mm_layer_flops(Pc, layer);          // dense layers: no padding in the count
 }
 // Algorithmic bytes of one conv-shaped layer launch: every operand tensor read once and the result written once (bf16
@@ -1519,6 +1543,11 @@ double mm_layer_algo_bytes(const MMPlan* Pc, const char* layer) {
         if (name == d + "_dgrad") return conv(P.convT[l], 2 * B, false);
         if (name == d + "_wgrad") return conv(P.convT[l], 2 * B, true);
     }
+    // conv1.hip reads the fp32 image itself (no patch buffer) and writes the raw and the Swish copy / reads the gradient
+    if (name == "enc_conv1_mfma") return (double)B * (2500 * 4.0 + 2 * 625 * 32 * 2.0) + 32 * 16 * 2.0;
+    if (name == "enc_conv1_wgrad_mfma") return (double)B * (2500 * 4.0 + 625 * 32 * 2.0) + 32 * 16 * 4.0;
+    // fused tail, 2 passes: raw input read, input gradient written, the fp32 target image read once per pass
+    if (name == "dec_last_fused" || name == "dec_last_fused_reduce") return 2.0 * B * (2 * 625 * 32 * 2.0 + 2500 * 4.0) + 32 * 16 * 4.0;
     return 0.0;
 }
 // ---------------------------------------------------------------- test aid: byte offset of a named workspace buffer

@@ -51,15 +51,18 @@ struct DecLastFusedArgs {
     float* loss_sum;         // [MMVAE_LOSS_SLOTS][16] column g += BCE sums, or null
     bf16* db;                // out NHWC [G*B][IH][IW][Cin]
     float2* red;             // [fin.G][MMVAE_STAT_SLOTS][Cin] += (sum db, sum db*xhat)
-    float* wslab;            // [bwd_groups*B*strips][Cin][16]: per-workgroup weight-gradient partials (plain stores)
+    float* wslab;            // [bwd_groups*B*dec_last_wgrad_partials()][Cin][16]: per-workgroup weight-gradient partials (plain stores)
     // importance-weighted evaluation (dec_last_mfma only, eval mode, no backward): image n gets loglik[n] = log p(x|z) against
     // target image n / rows_per_target; nothing else is written (no logits, probabilities, BCE sums or BatchNorm tables)
     float* loglik = nullptr;
     int rows_per_target = 1;
 };
 int dec_last_fused_strips(int IH);
-// matrix-core form (dec_last.hip): one workgroup per image, i.e. ONE weight-gradient partial per image (strips = 1)
+// matrix-core form (dec_last.hip): two workgroups per image in the training form, each with a weight-gradient partial of its own
 bool dec_last_mfma_applies(const DecLastFusedArgs& a);
+// partials per image in wslab, whichever kernel launch_dec_last_fused picks for these arguments: the one number the kernels'
+// slab index and the host's slab size / reduce job come from
+int dec_last_wgrad_partials(const DecLastFusedArgs& a);
 int launch_dec_last_mfma(const DecLastFusedArgs& a, hipStream_t s);
 int launch_dec_last_fused(const DecLastFusedArgs& a, hipStream_t s);
 // CelebA tail (dec_last.hip): 32x32x32 -> 64x64x3, one workgroup per image in 4 strips; wslab [bwd_groups*B][32][48], column
