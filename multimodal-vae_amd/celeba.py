@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
-from .core import CelebaState, FusedCelebaStep, FusedImageStep, StepOutputs
+from .core import CelebaState, FusedCelebaStep, FusedImageStep, Trainer, load_vae_checkpoint
 from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
                          _seed_from_torch, _stream, swish)
 
@@ -299,33 +299,13 @@ elbo_loss = loss_function
 def load_checkpoint(file_path, use_cuda=False):
     """celeba/train.py:46-58: rebuilds a MultimodalVAE from the checkpoint dict (``state_dict``, ``n_latents``) of either code base;
     a dict without ``n_latents`` gets the default of celeba/train.py:87 (100)."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    n_latents = checkpoint['n_latents'] if 'n_latents' in checkpoint else 100
-    vae = MultimodalVAE(n_latents=n_latents)
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, MultimodalVAE, use_cuda, 100)
 
 
-class FusedTrainer:
-    """``FusedTrainer(vae, batch_size, lr)(image, attrs)`` == zero_grad + 3 passes + 3 losses + backward + Adam step
-    (celeba/train.py:131-149) on ``vae``'s own parameters."""
-
-    def __init__(self, vae: MultimodalVAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1e-3, seed: int = 1234,
-                 world_size: int = 1, all_reduce=None):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedCelebaStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed, world_size=world_size,
-                                      all_reduce=all_reduce)
-
-    def __call__(self, image, attrs, **kw) -> StepOutputs:
-        self.engine.enc_dropout = self.vae.image_encoder.classifier[2].p > 0
-        return self.engine(image, attrs, **kw)
-
-    def evaluate(self, image, attrs, **kw) -> StepOutputs:
-        return self.engine.forward_backward(image, attrs, training=False, backward=False, **kw)
+class FusedTrainer(Trainer):
+    """``FusedTrainer(vae, batch_size, lr)(image, attrs)``: celeba/train.py:131-149 (3 passes, 3 losses), lr 1e-3, kl_lambda 1e-3."""
+    ENGINE = FusedCelebaStep
+    ENC_DROPOUT = staticmethod(lambda vae: vae.image_encoder.classifier[2].p)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -371,27 +351,11 @@ def imageonly_loss_function(recon_x, x, mu, logvar, kl_lambda=1e-3):
 
 def load_checkpoint_imageonly(file_path, use_cuda=False):
     """celeba/train_imageonly.py:29-39: rebuilds an ImageVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    vae = ImageVAE(n_latents=checkpoint['n_latents'])
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, ImageVAE, use_cuda)
 
 
-class ImageVAETrainer:
-    """``ImageVAETrainer(vae, batch_size, lr)(image)`` == zero_grad + forward + loss + backward + Adam step
-    (celeba/train_imageonly.py:108-117) on ``vae``'s own parameters: one pass over B rows (core.FusedImageStep)."""
-
-    def __init__(self, vae: ImageVAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1e-3, seed: int = 1234):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedImageStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed)
-
-    def __call__(self, image, **kw) -> StepOutputs:
-        self.engine.enc_dropout = self.vae.encoder.classifier[2].p > 0
-        return self.engine(image, **kw)
-
-    def evaluate(self, image, **kw) -> StepOutputs:
-        return self.engine.forward_backward(image, training=False, backward=False, **kw)
+class ImageVAETrainer(Trainer):
+    """``ImageVAETrainer(vae, batch_size, lr)(image)``: celeba/train_imageonly.py:108-117, lr 1e-3, kl_lambda 1e-3, on an
+    ``ImageVAE``: one pass over B rows (core.FusedImageStep)."""
+    ENGINE = FusedImageStep
+    ENC_DROPOUT = staticmethod(lambda vae: vae.encoder.classifier[2].p)

@@ -31,7 +31,7 @@ import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
 from ._ops import geometry
-from .core import CocoState, FusedCocoStep, FusedImageStep, FusedTextStep, StepOutputs
+from .core import CocoState, FusedCocoStep, FusedImageStep, FusedTextStep, Trainer, load_vae_checkpoint
 from .mmd import compute_kernel, compute_mmd, mmd_terms  # noqa: F401  (coco/model.py:385-402)
 from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
                          _gscale, _seed_from_torch, _stream, swish)
@@ -540,34 +540,18 @@ def load_checkpoint(file_path, use_cuda=False, sos=None, words: Optional[WordTab
     """coco/train.py:47-61: rebuilds a MultimodalVAE from the checkpoint dict (``state_dict``, ``n_latents``) that
     ``train_coco`` (or the reference) writes.  The '<s>' vector is not in the state dict (the reference reads it from GloVe
     at every forward): give ``sos=`` or a word table that has '<s>'."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    n_latents = checkpoint['n_latents'] if 'n_latents' in checkpoint else 100
-    vae = MultimodalVAE(n_latents=n_latents, use_cuda=use_cuda, sos=sos, words=words)
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, MultimodalVAE, use_cuda, 100, use_cuda=use_cuda, sos=sos, words=words)
 
 
-class FusedTrainer:
-    """``FusedTrainer(vae, batch_size, lr)(image, text)`` == zero_grad + 3 passes + 3 losses + backward + Adam step
-    (coco/train.py:138-173, lr default 1e-4 as coco/train.py:94) on ``vae``'s own parameters."""
+class FusedTrainer(Trainer):
+    """``FusedTrainer(vae, batch_size, lr)(image, text)``: coco/train.py:138-173 (3 passes, 3 losses), lr 1e-4 (coco/train.py:94),
+    kl_lambda 1e-3."""
+    ENGINE, LR = FusedCocoStep, 1e-4
+    ENC_DROPOUT = staticmethod(lambda vae: vae.image_encoder.classifier[2].p)
+    GRU_DROPOUT = staticmethod(lambda vae: vae.text_decoder.gru.dropout)
 
-    def __init__(self, vae: MultimodalVAE, batch_size: int, lr: float = 1e-4, kl_lambda: float = 1e-3, seed: int = 1234,
-                 world_size: int = 1, all_reduce=None):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedCocoStep(st, batch_size, vae.text_decoder.sos, lr=lr, kl_lambda=kl_lambda, seed=seed,
-                                    world_size=world_size, all_reduce=all_reduce)
-
-    def __call__(self, image, text, **kw) -> StepOutputs:
-        self.engine.enc_dropout = self.vae.image_encoder.classifier[2].p > 0
-        self.engine.gru_dropout = self.vae.text_decoder.gru.dropout > 0
-        return self.engine(image, text, **kw)
-
-    def evaluate(self, image, text, **kw) -> StepOutputs:
-        return self.engine.forward_backward(image, text, training=False, backward=False, **kw)
+    def _engine_kw(self, vae, batch_size):
+        return {"sos": vae.text_decoder.sos}
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -608,30 +592,14 @@ class ImageVAE(nn.Module):
 
 def load_checkpoint_imageonly(file_path, use_cuda=False):
     """coco/train_imageonly.py:28-40: rebuilds an ImageVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    vae = ImageVAE(n_latents=checkpoint['n_latents'])
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, ImageVAE, use_cuda)
 
 
-class ImageVAETrainer:
-    """``ImageVAETrainer(vae, batch_size, lr)(image)`` == zero_grad + forward + loss + backward + Adam step
-    (coco/train_imageonly.py:105-116, lr default 1e-4, kl_lambda 5e-4) on ``vae``'s own parameters: one pass over B rows."""
-
-    def __init__(self, vae: ImageVAE, batch_size: int, lr: float = 1e-4, kl_lambda: float = 5e-4, seed: int = 1234):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedImageStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed)
-
-    def __call__(self, image, **kw) -> StepOutputs:
-        self.engine.enc_dropout = self.vae.encoder.classifier[2].p > 0
-        return self.engine(image, **kw)
-
-    def evaluate(self, image, **kw) -> StepOutputs:
-        return self.engine.forward_backward(image, training=False, backward=False, **kw)
+class ImageVAETrainer(Trainer):
+    """``ImageVAETrainer(vae, batch_size, lr)(image)``: coco/train_imageonly.py:105-116, lr 1e-4, kl_lambda 5e-4, on an
+    ``ImageVAE``: one pass over B rows."""
+    ENGINE, LR, KL_LAMBDA = FusedImageStep, 1e-4, 5e-4
+    ENC_DROPOUT = staticmethod(lambda vae: vae.encoder.classifier[2].p)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -685,27 +653,14 @@ class TextVAE(nn.Module):
 def load_checkpoint_textonly(file_path, use_cuda=False, sos=None, words: Optional[WordTable] = None, steps=MAX_WORDS):
     """coco/train_textonly.py:28-40: rebuilds a TextVAE from the checkpoint dict (``state_dict``, ``n_latents``).  The '<s>' vector is
     not in the state dict: give ``sos=`` or a word table that has '<s>'."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    vae = TextVAE(n_latents=checkpoint['n_latents'], use_cuda=use_cuda, sos=sos, words=words, steps=steps)
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, TextVAE, use_cuda, use_cuda=use_cuda, sos=sos, words=words, steps=steps)
 
 
-class TextVAETrainer:
-    """``TextVAETrainer(vae, batch_size, lr)(text)`` == zero_grad + forward + loss + backward + Adam step
-    (coco/train_textonly.py:106-120, lr default 1e-4, kl_lambda 1e-3) on ``vae``'s own parameters: one pass over B rows."""
+class TextVAETrainer(Trainer):
+    """``TextVAETrainer(vae, batch_size, lr)(text)``: coco/train_textonly.py:106-120, lr 1e-4, kl_lambda 1e-3, on a ``TextVAE``:
+    one pass over B rows."""
+    ENGINE, LR = FusedTextStep, 1e-4
+    GRU_DROPOUT = staticmethod(lambda vae: vae.decoder.gru.dropout)
 
-    def __init__(self, vae: TextVAE, batch_size: int, lr: float = 1e-4, kl_lambda: float = 1e-3, seed: int = 1234):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedTextStep(st, batch_size, vae.decoder.sos, lr=lr, kl_lambda=kl_lambda, seed=seed)
-
-    def __call__(self, text, **kw) -> StepOutputs:
-        self.engine.gru_dropout = self.vae.decoder.gru.dropout > 0
-        return self.engine(text, **kw)
-
-    def evaluate(self, text, **kw) -> StepOutputs:
-        return self.engine.forward_backward(text, training=False, backward=False, **kw)
+    def _engine_kw(self, vae, batch_size):
+        return {"sos": vae.decoder.sos}

@@ -249,15 +249,37 @@ class StepOutputs:
         return s[0:3] / self.bce_div, s[4:7] / self.nll_div, s[8:11]
 
 
+# fields that only some step-io structs have: the engine attribute of the same name / an argument of the call
+_ENGINE_FIELDS = ("enc_dropout", "gru_dropout", "kl_lambda", "lambda_x", "lambda_y", "kl_coef")
+_CALL_FIELDS = ("defer_unpack", "pack_first", "optimizer_state", "dp_split", "early_adam")
+_LAYOUTS: Dict[type, tuple] = {}
+
+
+def _io_layout(cls) -> tuple:
+    """What a step-io struct has of the optional fields, decided once per struct from ``_fields_``: (engine attributes it takes as a
+    scalar, with the conversion), (per-call fields), (names of its two per-pass lambda arrays; none for a one-pass struct)."""
+    lay = _LAYOUTS.get(cls)
+    if lay is None:
+        types = dict(cls._fields_)
+        conv = {C.c_int: int, C.c_float: float}
+        lay = _LAYOUTS[cls] = (tuple((n, conv[types[n]]) for n in _ENGINE_FIELDS if types.get(n) in conv),
+                               tuple(n for n in _CALL_FIELDS if n in types),
+                               tuple(n for n, t in cls._fields_ if t is C.c_float * 3))
+    return lay
+
+
 class _FusedStepBase:
     """zero_grad -> 3-pass forward -> 3 losses -> backward -> [grad all-reduce] -> Adam, as ONE enqueue of HIP kernels."""
+
+    _DEFER_PACK = False         # the family's step prologue can refresh the packed weights itself (pack_first)
+    separate_unpack = False     # tests: unpack the gradient + plain Adam instead of the packed-gradient Adam (same numbers)
 
     def __init__(self, state: PlanState, batch: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  seed: int = 1234, world_size: int = 1, all_reduce=None):
         self.state, self.B, self.D = state, int(batch), state.n_latents
         self.lr, self.betas, self.eps, self.seed = lr, betas, eps, seed
         self.world_size, self.all_reduce = world_size, all_reduce
-        if all_reduce is not None and (world_size > 1 or getattr(all_reduce, "force", False)):
+        if self._dp_active():
             # the collective library may enqueue on a stream of its own: mixed stream priorities then slow the whole
             # process down (include/mmvae_hip.h: mmvae_set_stream_policy)
             call("mmvae_set_stream_policy", 1)
@@ -277,6 +299,11 @@ class _FusedStepBase:
     def _workspace_bytes(self, state: PlanState, batch: int) -> int:
         return state.workspace_bytes(batch)
 
+    def _three_pass(self, lambda_a, lambda_b) -> None:
+        """The default per-pass loss weights of a 3-pass family."""
+        self._LA, self._LB = lambda_a, lambda_b
+        self._last = ((True, True, True), lambda_a, lambda_b)
+
     def _pass_config(self, io, passes, la, lb, name_a, name_b):
         """Fills the lambda arrays and pass_skip flags of a step-io struct; returns (passes, lambda_a, lambda_b)."""
         passes = (True, True, True) if passes is None else tuple(bool(x) for x in passes)
@@ -289,17 +316,66 @@ class _FusedStepBase:
         self._last = (passes, la, lb)
         return passes, la, lb
 
+    def _io(self, cls, inputs, optional, backward=True, passes=None, lambda_a=None, lambda_b=None, defer_unpack=False,
+            dp_split=False, early_adam=None):
+        """One filled step-io struct of type ``cls``: the engine's workspace, counters, seed and loss sums; the required ``inputs``
+        ((field, tensor) pairs); every ``optional`` tensor ({field: tensor or None}, NULL when absent); and whatever ``cls`` has of
+        the fields that only some families know (``_io_layout``)."""
+        scalars, per_call, lambdas = _io_layout(cls)
+        io = cls()
+        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
+        io.step_counter = self.adam_state.data_ptr()
+        io.seed = self.seed
+        io.sums = self.sums.data_ptr()
+        for k, t in inputs:
+            setattr(io, k, t.data_ptr())
+        for k, t in optional.items():
+            setattr(io, k, None if t is None else t.data_ptr())
+        for k, conv in scalars:
+            setattr(io, k, conv(getattr(self, k)))
+        if lambdas:
+            self._pass_config(io, passes, lambda_a, lambda_b, *lambdas)
+        values = {"defer_unpack": int(bool(defer_unpack)), "pack_first": int(self.state.pack_pending), "dp_split": int(bool(dp_split)),
+                  "early_adam": early_adam,
+                  # (a void step, the exchange time-out of the caption decoder, skips its Adam update)
+                  "optimizer_state": self.adam_state.data_ptr() if backward else None}
+        for k in per_call:
+            setattr(io, k, values[k])
+        return io
+
+    def _step(self, entry: str, io, training, backward) -> StepOutputs:
+        """Enqueues the family's step.  optimizer.zero_grad() happens inside its prologue kernel when backward is requested; a
+        prologue that was asked to (pack_first) has refreshed the packed weights."""
+        call(entry, self.h, C.byref(io), int(training), int(backward), _stream())
+        if self._DEFER_PACK:
+            self.state.pack_pending = False
+        return self._outputs()
+
+    # -- optimizer --------------------------------------------------------------------------------------
+    def _adam_args(self, ranges=None, packed=True, n=None, grad_scale=1.0):
+        """(entry point, its arguments up to the trailing stream) of one optimizer launch.  ``packed``: the GEMM-weight gradients are
+        still in their packed layout and the kernel gathers them (and completes ``grads``) itself, over everything or over the
+        (offset, length) pairs of the ``c_longlong`` array ``ranges``; else plain Adam over the first ``n`` elements (default: all)."""
+        st = self.state
+        bufs = (ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams if n is None else n)
+        hyper = (ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, grad_scale)
+        if not packed:
+            return "mmvae_adam_step", bufs + hyper
+        gathered = (ptr(st.grad_map()), ptr(st.gpk), ptr(st.gpk_vec))
+        if ranges is None:
+            return "mmvae_adam_step_packed", bufs + hyper + gathered
+        return "mmvae_adam_step_packed_ranges", bufs + (ranges, len(ranges) // 2, 1) + hyper + gathered       # (1: the step count advances)
+
+    def _adam(self, **kw) -> None:
+        name, args = self._adam_args(**kw)
+        call(name, *args, _stream())
+
     def optimizer_step(self) -> None:
         """torch.optim.Adam(lr) semantics on the flat buffers, then refresh the packed bf16 weights."""
-        st = self.state
         if self._dp_active():
-            self.all_reduce(st.grads)                                  # sum over ranks (RCCL), scaled inside Adam
-        call("mmvae_adam_step", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-             ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / self.world_size, _stream())
+            self.all_reduce(self.state.grads)                          # sum over ranks (RCCL), scaled inside Adam
+        self._adam(packed=False, grad_scale=1.0 / self.world_size)
         self._after_update()
-
-    _DEFER_PACK = False         # the family's step prologue can refresh the packed weights itself (pack_first)
-    separate_unpack = False     # tests: unpack the gradient + plain Adam instead of the packed-gradient Adam (same numbers)
 
     def _after_update(self) -> None:
         if self._DEFER_PACK:
@@ -323,11 +399,8 @@ class _FusedStepBase:
         data-parallel path needs the complete flat gradient BEFORE Adam (all-reduce), so it keeps the separate unpack."""
         if self._dp_active() or self.separate_unpack:
             return _FusedStepBase.__call__(self, a, b, **kw)
-        st = self.state
         out = self.forward_backward(a, b, True, True, _defer_unpack=True, **kw)
-        call("mmvae_adam_step_packed", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-             ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk),
-             ptr(st.gpk_vec), _stream())
+        self._adam()
         self._after_update()
         return out
 
@@ -364,8 +437,7 @@ class FusedELBOStep(_FusedStepBase):
         super().__init__(state, batch, lr, betas, eps, seed, world_size, all_reduce)
         self.kl_lambda = kl_lambda
         self.enc_dropout = self.gru_dropout = True
-        self._LA, self._LB = self.LAMBDA_XY, self.LAMBDA_YX
-        self._last = ((True, True, True), self.LAMBDA_XY, self.LAMBDA_YX)
+        self._three_pass(self.LAMBDA_XY, self.LAMBDA_YX)
 
     def _outputs(self) -> StepOutputs:
         passes, lxy, lyx = self._last
@@ -379,47 +451,32 @@ class FusedELBOStep(_FusedStepBase):
         weights: the weak-supervision steps of multimnist/paired_weak.py:84-117 and modal_weak.py:87-117."""
         assert image.is_contiguous() and text.is_contiguous() and image.dtype == torch.float32 and text.dtype == torch.int64
         assert image.shape[0] == self.B and text.shape == (self.B, 4)
-        io = StepIO()
-        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        io.step_counter = self.adam_state.data_ptr()
-        io.image, io.text = image.data_ptr(), text.data_ptr()
-        for k, t in (("eps", eps), ("enc_mask1", enc_mask1), ("enc_mask2", enc_mask2), ("gru_keep", gru_keep),
-                     ("force_tokens", force_tokens), ("recon_image", recon_image), ("recon_text", recon_text),
-                     ("mu", mu), ("logvar", logvar), ("tokens", tokens)):
-            setattr(io, k, None if t is None else t.data_ptr())
-        io.enc_dropout, io.gru_dropout = int(self.enc_dropout), int(self.gru_dropout)
-        io.kl_lambda = self.kl_lambda
-        self._pass_config(io, passes, lambda_xy, lambda_yx, "lambda_xy", "lambda_yx")
-        io.seed = self.seed
-        io.sums = self.sums.data_ptr()
-        io.defer_unpack = int(bool(_defer_unpack))
-        io.pack_first = int(self.state.pack_pending)
-        io.dp_split = int(bool(_dp_split))
-        io.early_adam = _early_adam
-        # optimizer.zero_grad() (train.py:150) happens inside the step's prologue kernel when backward is requested
-        call("mmvae_mm_step", self.h, C.byref(io), int(training), int(backward), _stream())
-        self.state.pack_pending = False
-        return self._outputs()
+        io = self._io(StepIO, (("image", image), ("text", text)),
+                      dict(eps=eps, enc_mask1=enc_mask1, enc_mask2=enc_mask2, gru_keep=gru_keep, force_tokens=force_tokens,
+                           recon_image=recon_image, recon_text=recon_text, mu=mu, logvar=logvar, tokens=tokens),
+                      backward, passes, lambda_xy, lambda_yx, _defer_unpack, _dp_split, _early_adam)
+        return self._step("mmvae_mm_step", io, training, backward)
 
     # -- data parallelism: the decoders' gradients are exchanged while the encoders' backward still runs -------------
     EARLY_PREFIXES = ("image_decoder.", "text_decoder.")     # what mmvae_mm_step_io.dp_split completes early
+    _dp_ranges = None
 
     def grad_ranges(self):
         """(early, late): lists of (offset, length) runs of the flat gradient buffer, early = complete at the event of
         ``mmvae_mm_wait_early_grads``.  Adjacent parameters of the same kind are merged: a few large messages."""
         runs = ([], [])
-        end = 0
-        for i, (name, shape, off) in enumerate(self.state.table):
+        end, last_kind = 0, None
+        for name, shape, off in self.state.table:
             n = 1
             for d in shape:
                 n *= int(d)
             kind = 0 if name.startswith(self.EARLY_PREFIXES) else 1
             r = runs[kind]
-            if r and r[-1][0] + r[-1][1] == off and getattr(self, "_last_kind", None) == kind:
+            if r and r[-1][0] + r[-1][1] == off and last_kind == kind:
                 r[-1] = (r[-1][0], r[-1][1] + n)
             else:
                 r.append((off, n))
-            self._last_kind = kind
+            last_kind = kind
             end = max(end, off + n)
         assert end == self.state.nparams
         return runs
@@ -434,11 +491,11 @@ class FusedELBOStep(_FusedStepBase):
         queue shared with one of the step's streams the step stalls behind it (0.91 -> 2.2 ms measured with a world-1 RCCL
         group, GPU_MAX_HW_QUEUES=8).  The plain exchange after the step is the default."""
         st = self.state
-        if getattr(self, "_ranges", None) is None:
-            self._ranges = self.grad_ranges()
+        if self._dp_ranges is None:
+            self._dp_ranges = self.grad_ranges()
             self._comm_owner = _lib.OwnedStream(st.device)      # (not torch.cuda.Stream(): see _lib.OwnedStream)
             self._comm = self._comm_owner.stream
-        early, late = self._ranges
+        early, late = self._dp_ranges
         out = self.forward_backward(image, text, True, True, _dp_split=True, **kw)
         # async collectives: the library's stream is ordered behind the stream that is current at the call (the
         # communication stream, whose only content is the wait for the early-gradient event, for the early ranges; the main
@@ -454,12 +511,12 @@ class FusedELBOStep(_FusedStepBase):
         for w in works:
             if w is not None:
                 w.wait()
-        call("mmvae_adam_step", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-             ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / self.world_size, _stream())
+        self._adam(packed=False, grad_scale=1.0 / self.world_size)
         self._after_update()
         return out
 
     early_adam = True       # the decoders' Adam update is issued inside the step, beside the encoders' backward (mmvae_early_adam)
+    _ea = _ea_ran = _fast = None
 
     def _early_setup(self):
         """ctypes block handed to mmvae_mm_step_io.early_adam + the ranges the call behind the step still has to update."""
@@ -477,35 +534,33 @@ class FusedELBOStep(_FusedStepBase):
         self._ea_ran = C.c_int(0)
         ea = _lib.EarlyAdam()
         ea.m, ea.v, ea.state = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.adam_state.data_ptr()
-        ea.lr, ea.beta1, ea.beta2, ea.eps, ea.grad_scale = self.lr, self.betas[0], self.betas[1], self.eps, 1.0
+        ea.grad_scale = 1.0
         ea.gmap = st.grad_map().data_ptr()
         ea.ran = C.pointer(self._ea_ran)
         self._ea = ea
         self._ea_late = (C.c_longlong * (2 * len(late)))(*[x for r in late for x in r])
-        self._ea_nlate = len(late)
         self._ea_ok = 0 < n and 0 < len(late) <= 4 and all(o % 4 == 0 and l % 4 == 0 for o, l in late[:-1]) and late[-1][0] % 4 == 0
+
+    def _early_hyper(self) -> None:
+        """The optimizer's hyper-parameters as the in-step part of the update reads them."""
+        ea = self._ea
+        ea.lr, ea.beta1, ea.beta2, ea.eps = self.lr, self.betas[0], self.betas[1], self.eps
 
     def _call_packed(self, image, text, **kw) -> StepOutputs:
         """backward + optimizer.step() with the decoders' part of the update inside the step (multimnist/train.py:168,173)."""
         if self._dp_active() or self.separate_unpack or not self.early_adam:
             return _FusedStepBase._call_packed(self, image, text, **kw)
-        if getattr(self, "_ea", None) is None:
+        if self._ea is None:
             self._early_setup()
         if not self._ea_ok:
             return _FusedStepBase._call_packed(self, image, text, **kw)
-        st = self.state
-        self._ea.lr = self.lr
         if not kw:
             return self._call_fast(image, text)
+        self._early_hyper()
+        self._fast = None           # (the fast path writes that block only when its key changes: make it look again)
         out = self.forward_backward(image, text, True, True, _defer_unpack=True, _early_adam=C.addressof(self._ea), **kw)
-        if self._ea_ran.value:      # the step updated image_decoder.* / text_decoder.*: the rest, and the step count
-            call("mmvae_adam_step_packed_ranges", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-                 self._ea_late, self._ea_nlate, 1, ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0,
-                 ptr(st.grad_map()), ptr(st.gpk), ptr(st.gpk_vec), _stream())
-        else:
-            call("mmvae_adam_step_packed", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-                 ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk),
-                 ptr(st.gpk_vec), _stream())
+        # the step updated image_decoder.* / text_decoder.* (then: the rest, and the step count) or declined to
+        self._adam(ranges=self._ea_late if self._ea_ran.value else None)
         self._after_update()
         return out
 
@@ -515,25 +570,14 @@ class FusedELBOStep(_FusedStepBase):
         time per step is what makes a loader-fed loop host-bound: 49 launches are 250 us of runtime calls,
         filling a 30-field ctypes structure and converting 18 arguments per call was another 60."""
         st = self.state
-        fast = getattr(self, "_fast", None)
-        key = (self.enc_dropout, self.gru_dropout, self.kl_lambda, self.seed, self.lr)
-        if fast is None or fast[0] != key:
-            io = StepIO()
-            io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-            io.step_counter = self.adam_state.data_ptr()
-            io.enc_dropout, io.gru_dropout = int(self.enc_dropout), int(self.gru_dropout)
-            io.kl_lambda = self.kl_lambda
-            self._pass_config(io, None, None, None, "lambda_xy", "lambda_yx")
-            io.seed = self.seed
-            io.sums = self.sums.data_ptr()
-            io.defer_unpack, io.dp_split = 1, 0
-            io.early_adam = C.addressof(self._ea)
+        fast = self._fast
+        key = (self.enc_dropout, self.gru_dropout, self.kl_lambda, self.seed, self.lr, tuple(self.betas), self.eps, self._LA, self._LB)
+        if fast is None or fast[0] != key:      # everything the cached blocks below hold by value
+            self._early_hyper()
+            io = self._io(StepIO, (), {}, defer_unpack=True, early_adam=C.addressof(self._ea))
             lib = _lib.load()
-            late = (ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams, self._ea_late, self._ea_nlate, 1,
-                    ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk), ptr(st.gpk_vec))
-            full = (ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams, ptr(self.adam_state), self.lr,
-                    self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk), ptr(st.gpk_vec))
-            fast = self._fast = (key, io, C.byref(io), lib.mmvae_mm_step, lib.mmvae_adam_step_packed_ranges, lib.mmvae_adam_step_packed, late, full, lib)
+            (n_late, late), (n_full, full) = self._adam_args(ranges=self._ea_late), self._adam_args()
+            fast = self._fast = (key, io, C.byref(io), lib.mmvae_mm_step, getattr(lib, n_late), getattr(lib, n_full), late, full, lib)
         _, io, io_ref, f_step, f_late, f_full, late, full, lib = fast
         assert image.is_contiguous() and text.is_contiguous() and image.dtype == torch.float32 and text.dtype == torch.int64
         assert image.shape[0] == self.B and text.shape == (self.B, 4)
@@ -565,29 +609,21 @@ class FusedMnistStep(_FusedStepBase):
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
-        self._LA, self._LB = self.LAMBDA_XY, self.LAMBDA_YX
-        self._last = ((True, True, True), self.LAMBDA_XY, self.LAMBDA_YX)
+        self.kl_coef = 1.0 / (self.B * (784 / 3))
+        self._three_pass(self.LAMBDA_XY, self.LAMBDA_YX)
 
     def _outputs(self) -> StepOutputs:
         passes, lxy, lyx = self._last
-        return StepOutputs(self.sums, self.B * 784, self.B, 1.0 / (self.B * (784 / 3)), lxy, lyx, passes)
+        return StepOutputs(self.sums, self.B * 784, self.B, self.kl_coef, lxy, lyx, passes)
 
     def forward_backward(self, image, label, training=True, backward=True, eps=None, recon_image=None, recon_text=None,
                          mu=None, logvar=None, passes=None, lambda_xy=None, lambda_yx=None) -> StepOutputs:
         assert image.is_contiguous() and label.is_contiguous() and image.dtype == torch.float32 and label.dtype == torch.int64
         assert image.numel() == self.B * 784 and label.shape == (self.B,)
-        io = _lib.MnistStepIO()
-        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        io.step_counter = self.adam_state.data_ptr()
-        io.image, io.label = image.data_ptr(), label.data_ptr()
-        for k, t in (("eps", eps), ("recon_image", recon_image), ("recon_text", recon_text), ("mu", mu), ("logvar", logvar)):
-            setattr(io, k, None if t is None else t.data_ptr())
-        self._pass_config(io, passes, lambda_xy, lambda_yx, "lambda_xy", "lambda_yx")
-        io.kl_coef = 1.0 / (self.B * (784 / 3))
-        io.seed = self.seed
-        io.sums = self.sums.data_ptr()
-        call("mmvae_mnist_step", self.h, C.byref(io), int(training), int(backward), _stream())
-        return self._outputs()
+        io = self._io(_lib.MnistStepIO, (("image", image), ("label", label)),
+                      dict(eps=eps, recon_image=recon_image, recon_text=recon_text, mu=mu, logvar=logvar),
+                      backward, passes, lambda_xy, lambda_yx)
+        return self._step("mmvae_mnist_step", io, training, backward)
 
 
 class FusedCelebaStep(_FusedStepBase):
@@ -602,8 +638,7 @@ class FusedCelebaStep(_FusedStepBase):
         super().__init__(state, batch, lr, betas, eps, seed, world_size, all_reduce)
         self.kl_lambda = kl_lambda
         self.enc_dropout = True
-        self._LA, self._LB = self.LAMBDA_X, self.LAMBDA_Y
-        self._last = ((True, True, True), self.LAMBDA_X, self.LAMBDA_Y)
+        self._three_pass(self.LAMBDA_X, self.LAMBDA_Y)
 
     def _outputs(self) -> StepOutputs:
         passes, lx, ly = self._last
@@ -617,21 +652,10 @@ class FusedCelebaStep(_FusedStepBase):
                          _defer_unpack=False) -> StepOutputs:
         assert image.is_contiguous() and attrs.is_contiguous() and image.dtype == torch.float32 and attrs.dtype == torch.float32
         assert image.shape == (self.B, 3, 64, 64) and attrs.shape == (self.B, self.N_ATTRS)
-        io = _lib.CelebaStepIO()
-        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        io.step_counter = self.adam_state.data_ptr()
-        io.image, io.attrs = image.data_ptr(), attrs.data_ptr()
-        for k, t in (("eps", eps), ("enc_mask", enc_mask), ("recon_image", recon_image), ("recon_attrs", recon_attrs),
-                     ("mu", mu), ("logvar", logvar)):
-            setattr(io, k, None if t is None else t.data_ptr())
-        io.enc_dropout = int(self.enc_dropout)
-        io.kl_lambda = self.kl_lambda
-        self._pass_config(io, passes, lambda_x, lambda_y, "lambda_x", "lambda_y")
-        io.seed = self.seed
-        io.sums = self.sums.data_ptr()
-        io.defer_unpack = int(bool(_defer_unpack))
-        call("mmvae_celeba_step", self.h, C.byref(io), int(training), int(backward), _stream())
-        return self._outputs()
+        io = self._io(_lib.CelebaStepIO, (("image", image), ("attrs", attrs)),
+                      dict(eps=eps, enc_mask=enc_mask, recon_image=recon_image, recon_attrs=recon_attrs, mu=mu, logvar=logvar),
+                      backward, passes, lambda_x, lambda_y, _defer_unpack)
+        return self._step("mmvae_celeba_step", io, training, backward)
 
 
 class FusedCocoStep(_FusedStepBase):
@@ -649,8 +673,7 @@ class FusedCocoStep(_FusedStepBase):
         self.T = state.steps
         self.sos = sos.to(device=state.device, dtype=torch.float32).contiguous().reshape(self.EMB)
         self.enc_dropout = self.gru_dropout = True
-        self._LA, self._LB = self.LAMBDA_XY, self.LAMBDA_YX
-        self._last = ((True, True, True), self.LAMBDA_XY, self.LAMBDA_YX)
+        self._three_pass(self.LAMBDA_XY, self.LAMBDA_YX)
 
     def _outputs(self) -> StepOutputs:
         passes, lxy, lyx = self._last
@@ -664,27 +687,42 @@ class FusedCocoStep(_FusedStepBase):
                          lambda_xy=None, lambda_yx=None, _defer_unpack=False) -> StepOutputs:
         assert image.is_contiguous() and text.is_contiguous() and image.dtype == torch.float32 and text.dtype == torch.float32
         assert image.shape == (self.B, 3, 32, 32) and text.shape == (self.B, self.T, self.EMB)
-        io = _lib.CocoStepIO()
-        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        io.step_counter = self.adam_state.data_ptr()
-        io.optimizer_state = self.adam_state.data_ptr() if backward else None     # a void step (exchange time-out) skips its Adam update
-        io.image, io.text, io.sos = image.data_ptr(), text.data_ptr(), self.sos.data_ptr()
-        for k, t in (("eps", eps), ("enc_mask1", enc_mask1), ("enc_mask2", enc_mask2), ("gru_keep", gru_keep),
-                     ("recon_image", recon_image), ("recon_text", recon_text), ("mu", mu), ("logvar", logvar)):
-            setattr(io, k, None if t is None else t.data_ptr())
-        io.enc_dropout, io.gru_dropout = int(self.enc_dropout), int(self.gru_dropout)
-        io.kl_lambda = self.kl_lambda
-        self._pass_config(io, passes, lambda_xy, lambda_yx, "lambda_xy", "lambda_yx")
-        io.seed = self.seed
-        io.defer_unpack = int(bool(_defer_unpack))
-        io.pack_first = int(self.state.pack_pending)
-        io.sums = self.sums.data_ptr()
-        call("mmvae_coco_step", self.h, C.byref(io), int(training), int(backward), _stream())
-        self.state.pack_pending = False
-        return self._outputs()
+        io = self._io(_lib.CocoStepIO, (("image", image), ("text", text), ("sos", self.sos)),
+                      dict(eps=eps, enc_mask1=enc_mask1, enc_mask2=enc_mask2, gru_keep=gru_keep, recon_image=recon_image,
+                           recon_text=recon_text, mu=mu, logvar=logvar),
+                      backward, passes, lambda_xy, lambda_yx, _defer_unpack)
+        return self._step("mmvae_coco_step", io, training, backward)
 
 
-class FusedImageStep(_FusedStepBase):
+class _SinglePassStep(_FusedStepBase):
+    """A uni-modal baseline's step: zero_grad -> ONE pass over B rows (one encoder, reparametrize, one decoder; no product of
+    experts) -> backward -> Adam over that modality's parameters, ``self._ranges`` ((offset, length) as a ``c_longlong`` pair) when
+    they are a 4-aligned part of the flat buffers, else over everything (the other half's gradient is exactly 0)."""
+
+    _KIND = ""              # "image-only" / "text-only", for messages
+    _ranges = None
+    _packed, _adam_n = True, None       # MNIST: plain Adam over the leading ``_adam_n`` elements
+
+    def evaluate(self, x, **kw) -> StepOutputs:
+        """Eval-mode forward (z = mu, no dropout, nothing drawn), no backward."""
+        return self.forward_backward(x, False, False, **kw)
+
+    def __call__(self, x, **kw) -> StepOutputs:
+        """backward + optimizer.step() in one pass over the modality's parameters: the packed-gradient Adam (see _call_packed)."""
+        if self.separate_unpack and self._packed:
+            out = self.forward_backward(x, True, True, **kw)
+            self.optimizer_step()
+            return out
+        out = self.forward_backward(x, True, True, _defer_unpack=self._packed, **kw)
+        self._adam(ranges=self._ranges, packed=self._packed, n=self._adam_n)
+        self._after_update()
+        return out
+
+    def capture(self, x: torch.Tensor) -> None:
+        raise MMVAEError("%s: HIP-graph capture is not offered for the %s step" % (type(self).__name__, self._KIND))
+
+
+class FusedImageStep(_SinglePassStep):
     """The step of celeba/train_imageonly.py:95-113, coco/train_imageonly.py, multimnist/train_imageonly.py:91-106 and
     mnist/imageonly/train_imageonly.py:114-127 on the family's plan: zero_grad -> ONE pass over B rows (image encoder, reparametrize,
     image decoder; no product of experts) -> lambda_x * BCE + kl_lambda * KL / B -> backward -> Adam.  ``state`` is a ``CelebaState``, a
@@ -696,6 +734,8 @@ class FusedImageStep(_FusedStepBase):
     CHANNELS = {"celeba": 3, "coco": 3, "mm": 1, "mnist": 1}
     FAMILIES = "CelebA, COCO and MultiMNIST have one, MNIST has one on its fp32 plan"
     IMAGE_PREFIXES = ("image_encoder.", "image_decoder.")
+    _KIND = "image-only"
+    flat_images = False         # MNIST: (B, 784) batches are taken too
 
     def __init__(self, state: PlanState, batch: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  kl_lambda: float = 1e-3, lambda_x: float = 1.0, seed: int = 1234):
@@ -720,7 +760,10 @@ class FusedImageStep(_FusedStepBase):
                 assert off == n_img, "the image parameters are expected to be contiguous at the head of the table"
                 n_img = off + n
         self.n_image_params = n_img
-        self._ranges = (C.c_longlong * 2)(0, n_img) if n_img % 4 == 0 and 0 < n_img < state.nparams else None
+        if state.API == "mnist":        # the fp32 plan writes every gradient into ``grads``
+            self._packed, self._adam_n = False, n_img
+        elif n_img % 4 == 0 and 0 < n_img < state.nparams:
+            self._ranges = (C.c_longlong * 2)(0, n_img)
 
     def _workspace_bytes(self, state: PlanState, batch: int) -> int:
         return state._c("image_step_workspace_bytes", state.plan(batch))
@@ -733,55 +776,17 @@ class FusedImageStep(_FusedStepBase):
                          mu=None, logvar=None, _defer_unpack=False) -> StepOutputs:
         assert image.is_contiguous() and image.dtype == torch.float32
         # (MNIST batches may come flattened, as the reference's x.view(-1, 784) takes them)
-        flat_ok = getattr(self, "flat_images", False) and tuple(image.shape) == (self.B, self.channels * self.side * self.side)
+        flat_ok = self.flat_images and tuple(image.shape) == (self.B, self.channels * self.side * self.side)
         if tuple(image.shape) != (self.B, self.channels, self.side, self.side) and not flat_ok:
             raise MMVAEError("FusedImageStep: expected images of shape %s (got %s)"
                              % ((self.B, self.channels, self.side, self.side), tuple(image.shape)))
-        io = _lib.ImageStepIO()
-        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        io.step_counter = self.adam_state.data_ptr()
-        io.image = image.data_ptr()
-        for k, t in (("eps", eps), ("enc_mask1", enc_mask1), ("enc_mask2", enc_mask2), ("recon_image", recon_image),
-                     ("mu", mu), ("logvar", logvar)):
-            setattr(io, k, None if t is None else t.data_ptr())
-        io.enc_dropout = int(self.enc_dropout)
-        io.kl_lambda, io.lambda_x = self.kl_lambda, self.lambda_x
-        io.seed = self.seed
-        io.sums = self.sums.data_ptr()
-        io.defer_unpack = int(bool(_defer_unpack))
-        self.state._c("image_step", self.h, C.byref(io), int(training), int(backward), _stream())
-        return self._outputs()
-
-    def __call__(self, image, **kw) -> StepOutputs:
-        """backward + optimizer.step() in one pass over the image parameters: the packed-gradient Adam (see _call_packed)."""
-        st = self.state
-        if st.API == "mnist":       # the fp32 plan wrote every gradient into ``grads``: plain Adam over the image half's run
-            out = self.forward_backward(image, True, True, **kw)
-            call("mmvae_adam_step", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n_image_params,
-                 ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, _stream())
-            self._after_update()
-            return out
-        if self.separate_unpack:
-            out = self.forward_backward(image, True, True, **kw)
-            self.optimizer_step()
-            return out
-        out = self.forward_backward(image, True, True, _defer_unpack=True, **kw)
-        if self._ranges is not None:
-            call("mmvae_adam_step_packed_ranges", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-                 self._ranges, 1, 1, ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0,
-                 ptr(st.grad_map()), ptr(st.gpk), ptr(st.gpk_vec), _stream())
-        else:
-            call("mmvae_adam_step_packed", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-                 ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk),
-                 ptr(st.gpk_vec), _stream())
-        self._after_update()
-        return out
-
-    def capture(self, image: torch.Tensor) -> None:
-        raise MMVAEError("FusedImageStep: HIP-graph capture is not offered for the image-only step")
+        io = self._io(_lib.ImageStepIO, (("image", image),),
+                      dict(eps=eps, enc_mask1=enc_mask1, enc_mask2=enc_mask2, recon_image=recon_image, mu=mu, logvar=logvar),
+                      backward, defer_unpack=_defer_unpack)
+        return self._step("mmvae_%s_image_step" % self.state.API, io, training, backward)
 
 
-class FusedTextStep(_FusedStepBase):
+class FusedTextStep(_SinglePassStep):
     """The step of coco/train_textonly.py:106-120 on the COCO plan: zero_grad -> ONE pass over B rows (caption encoder, reparametrize,
     caption decoder; no product of experts) -> lambda_y * MSE + kl_lambda * KL -> backward -> Adam.  ``state`` is a ``CocoState``; the
     image half is never launched: its parameters and BatchNorm buffers keep their values and its gradient is exactly 0.
@@ -790,6 +795,7 @@ class FusedTextStep(_FusedStepBase):
     EMB = 300
     TEXT_PREFIXES = ("text_encoder.", "text_decoder.")
     _DEFER_PACK = True          # the step refreshes the caption half's packed weights itself (pack_first)
+    _KIND = "text-only"
 
     def __init__(self, state: PlanState, batch: int, sos: torch.Tensor, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  kl_lambda: float = 1e-3, lambda_y: float = 1.0, seed: int = 1234):
@@ -805,7 +811,8 @@ class FusedTextStep(_FusedStepBase):
         assert all(name.startswith(self.TEXT_PREFIXES) == (off >= first) for name, _, off in state.table), \
             "the caption parameters are expected to be contiguous at the tail of the table"
         self.text_param_range = (first, state.nparams - first)
-        self._ranges = (C.c_longlong * 2)(first, state.nparams - first) if first % 4 == 0 and state.nparams % 4 == 0 and first > 0 else None
+        if first % 4 == 0 and state.nparams % 4 == 0 and first > 0:
+            self._ranges = (C.c_longlong * 2)(*self.text_param_range)
 
     def _workspace_bytes(self, state: PlanState, batch: int) -> int:
         return state._c("text_step_workspace_bytes", state.plan(batch))
@@ -821,59 +828,22 @@ class FusedTextStep(_FusedStepBase):
         st = self.state
         if st.pack_pending and not st._pack_text_only:      # somebody else changed parameters of the image half as well
             st.pack_weights()
-        io = _lib.TextStepIO()
-        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        io.step_counter = self.adam_state.data_ptr()
-        io.optimizer_state = self.adam_state.data_ptr() if backward else None     # a void step (exchange time-out) skips its Adam update
-        io.text, io.sos = text.data_ptr(), self.sos.data_ptr()
-        for k, t in (("eps", eps), ("gru_keep", gru_keep), ("recon_text", recon_text), ("mu", mu), ("logvar", logvar)):
-            setattr(io, k, None if t is None else t.data_ptr())
-        io.gru_dropout = int(self.gru_dropout)
-        io.kl_lambda, io.lambda_y = self.kl_lambda, self.lambda_y
-        io.seed = self.seed
-        io.sums = self.sums.data_ptr()
-        io.defer_unpack = int(bool(_defer_unpack))
-        io.pack_first = int(st.pack_pending)
-        call("mmvae_coco_text_step", self.h, C.byref(io), int(training), int(backward), _stream())
-        st.pack_pending = False
-        return self._outputs()
-
-    def evaluate(self, text, **kw) -> StepOutputs:
-        """Eval-mode forward (z = mu, no dropout, nothing drawn), no backward."""
-        return self.forward_backward(text, False, False, **kw)
+        io = self._io(_lib.TextStepIO, (("text", text), ("sos", self.sos)),
+                      dict(eps=eps, gru_keep=gru_keep, recon_text=recon_text, mu=mu, logvar=logvar),
+                      backward, defer_unpack=_defer_unpack)
+        return self._step("mmvae_coco_text_step", io, training, backward)
 
     def _after_update(self) -> None:
         self.state.defer_text_pack()
 
-    def __call__(self, text, **kw) -> StepOutputs:
-        """backward + optimizer.step() in one pass over the caption parameters: the packed-gradient Adam (see _call_packed)."""
-        st = self.state
-        if self.separate_unpack:
-            out = self.forward_backward(text, True, True, **kw)
-            self.optimizer_step()
-            return out
-        out = self.forward_backward(text, True, True, _defer_unpack=True, **kw)
-        if self._ranges is not None:
-            call("mmvae_adam_step_packed_ranges", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-                 self._ranges, 1, 1, ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0,
-                 ptr(st.grad_map()), ptr(st.gpk), ptr(st.gpk_vec), _stream())
-        else:
-            call("mmvae_adam_step_packed", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-                 ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk),
-                 ptr(st.gpk_vec), _stream())
-        self._after_update()
-        return out
 
-    def capture(self, text: torch.Tensor) -> None:
-        raise MMVAEError("FusedTextStep: HIP-graph capture is not offered for the text-only step")
-
-
-class FusedMMTextStep(_FusedStepBase):
+class FusedMMTextStep(_SinglePassStep):
     """The step of multimnist/train_textonly.py:95-113 on the text-only plan (``MultimnistTextState``): zero_grad -> ONE pass over B
     rows (text encoder, reparametrize, text decoder; no product of experts) -> lambda_y * NLL + kl_lambda * KL -> backward -> Adam over
     every parameter.  ``StepOutputs`` carries the pass in slot 0 of the text terms (``parts()[1][0]``, ``parts()[2][0]``)."""
 
     _DEFER_PACK = True          # the step's prologue refreshes the packed weights itself (pack_first)
+    _KIND = "text-only"
 
     def __init__(self, state: PlanState, batch: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  kl_lambda: float = 1e-3, lambda_y: float = 1.0, seed: int = 1234):
@@ -893,41 +863,67 @@ class FusedMMTextStep(_FusedStepBase):
     def forward_backward(self, text, training=True, backward=True, eps=None, gru_keep=None, force_tokens=None, recon_text=None,
                          mu=None, logvar=None, tokens=None, _defer_unpack=False) -> StepOutputs:
         assert text.is_contiguous() and text.dtype == torch.int64 and text.shape == (self.B, 4)
-        st = self.state
-        io = _lib.MMTextStepIO()
-        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        io.step_counter = self.adam_state.data_ptr()
-        io.text = text.data_ptr()
-        for k, t in (("eps", eps), ("gru_keep", gru_keep), ("force_tokens", force_tokens), ("recon_text", recon_text), ("mu", mu),
-                     ("logvar", logvar), ("tokens", tokens)):
-            setattr(io, k, None if t is None else t.data_ptr())
-        io.gru_dropout = int(self.gru_dropout)
-        io.kl_lambda, io.lambda_y = self.kl_lambda, self.lambda_y
-        io.seed = self.seed
-        io.sums = self.sums.data_ptr()
-        io.defer_unpack = int(bool(_defer_unpack))
-        io.pack_first = int(st.pack_pending)
-        call("mmvae_mmtext_step", self.h, C.byref(io), int(training), int(backward), _stream())
-        st.pack_pending = False
-        return self._outputs()
+        io = self._io(_lib.MMTextStepIO, (("text", text),),
+                      dict(eps=eps, gru_keep=gru_keep, force_tokens=force_tokens, recon_text=recon_text, mu=mu, logvar=logvar,
+                           tokens=tokens),
+                      backward, defer_unpack=_defer_unpack)
+        return self._step("mmvae_mmtext_step", io, training, backward)
 
-    def evaluate(self, text, **kw) -> StepOutputs:
-        """Eval-mode forward (z = mu, no dropout, nothing drawn), no backward."""
-        return self.forward_backward(text, False, False, **kw)
 
-    def __call__(self, text, **kw) -> StepOutputs:
-        """backward + optimizer.step() in one pass over the parameters: the packed-gradient Adam (see _call_packed)."""
-        st = self.state
-        if self.separate_unpack:
-            out = self.forward_backward(text, True, True, **kw)
-            self.optimizer_step()
-            return out
-        out = self.forward_backward(text, True, True, _defer_unpack=True, **kw)
-        call("mmvae_adam_step_packed", ptr(st.params), ptr(st.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), st.nparams,
-             ptr(self.adam_state), self.lr, self.betas[0], self.betas[1], self.eps, 1.0, ptr(st.grad_map()), ptr(st.gpk),
-             ptr(st.gpk_vec), _stream())
-        self._after_update()
-        return out
+# ----------------------------------------------------------------------------------------------------------------
+# the nn.Module side: one trainer and one checkpoint loader, declared per family in multimnist / mnist / celeba / coco
+# ----------------------------------------------------------------------------------------------------------------
+class Trainer:
+    """``Trainer(vae, batch_size, lr)(*inputs)`` == zero_grad + forward + loss(es) + backward + Adam step, the train() closure body
+    of a reference script as one enqueue, operating directly on ``vae``'s parameters (which stay ordinary nn.Parameters /
+    state_dict entries; the engine updates the flat buffer in place and refreshes the packed bf16 copies itself).  A family
+    declares its engine class, the reference script's ``lr`` / ``kl_lambda`` defaults and where its dropout probabilities live."""
 
-    def capture(self, text: torch.Tensor) -> None:
-        raise MMVAEError("FusedMMTextStep: HIP-graph capture is not offered for the text-only step")
+    ENGINE = None
+    LR, KL_LAMBDA = 1e-3, 1e-3          # (KL_LAMBDA None: the engine has none)
+    ENC_DROPOUT = GRU_DROPOUT = None    # vae -> dropout probability (None: the engine has no such flag)
+
+    def __init__(self, vae, batch_size: int, lr: Optional[float] = None, kl_lambda: Optional[float] = None, seed: int = 1234,
+                 **engine_kw):
+        """``engine_kw``: ``world_size`` / ``all_reduce`` of the three-pass engines."""
+        self.vae = vae
+        st = vae._core.sync(next(vae.parameters()).device)
+        if self.KL_LAMBDA is not None:
+            engine_kw["kl_lambda"] = self.KL_LAMBDA if kl_lambda is None else kl_lambda
+        self.engine = self.ENGINE(st, batch_size, lr=self.LR if lr is None else lr, seed=seed, **self._engine_kw(vae, batch_size),
+                                  **engine_kw)
+
+    def _engine_kw(self, vae, batch_size) -> dict:
+        """What else the family's engine is built from (COCO: the '<s>' vector)."""
+        return {}
+
+    def _flags(self, kw) -> None:
+        eng = self.engine
+        if "kl_lambda" in kw:
+            eng.kl_lambda = kw.pop("kl_lambda")
+        if self.ENC_DROPOUT is not None:
+            eng.enc_dropout = self.ENC_DROPOUT(self.vae) > 0
+        if self.GRU_DROPOUT is not None:
+            eng.gru_dropout = self.GRU_DROPOUT(self.vae) > 0
+
+    def __call__(self, *inputs, **kw) -> StepOutputs:
+        self._flags(kw)
+        return self.engine(*inputs, **kw)
+
+    def evaluate(self, *inputs, **kw) -> StepOutputs:
+        """The test() closure body: eval-mode forward, no backward."""
+        self._flags(kw)
+        return self.engine.forward_backward(*inputs, training=False, backward=False, **kw)
+
+
+def load_vae_checkpoint(file_path, build, use_cuda=False, default_n_latents=None, /, **kw):
+    """Rebuilds ``build(n_latents=..., **kw)`` from a checkpoint dict (``state_dict``, ``n_latents``) of either code base;
+    ``default_n_latents`` stands in where an old dict has no ``n_latents``.  (Positional-only: ``kw`` may carry a ``use_cuda``.)"""
+    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
+    if default_n_latents is not None:
+        checkpoint.setdefault('n_latents', default_n_latents)
+    vae = build(n_latents=checkpoint['n_latents'], **kw)
+    vae.load_state_dict(checkpoint['state_dict'])
+    if use_cuda:
+        vae.cuda()
+    return vae

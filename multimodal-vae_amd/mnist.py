@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._lib import MMVAEError, call, ptr
-from .core import FusedImageStep, FusedMnistStep, MnistState, StepOutputs
+from .core import FusedImageStep, FusedMnistStep, MnistState, StepOutputs, Trainer, load_vae_checkpoint
 from .multimnist import (ProductOfExperts, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _NLLMeanFn, _ReparamFn, _core_of,
                          _seed_from_torch, _stream)
 
@@ -218,13 +218,7 @@ elbo_loss = loss_function
 
 def load_checkpoint(file_path, use_cuda=False):
     """mnist/train.py:44-60: rebuilds a MultimodalVAE from the checkpoint dict (``state_dict``, ``n_latents``) of either code base."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    n_latents = checkpoint['n_latents'] if 'n_latents' in checkpoint else 20
-    vae = MultimodalVAE(n_latents=n_latents)
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, MultimodalVAE, use_cuda, 20)
 
 
 def plan_latents(n_latents):
@@ -259,23 +253,20 @@ def with_padded_latents(vae):
     return big.train(vae.training)
 
 
-class FusedTrainer:
-    """``FusedTrainer(vae, batch_size, lr)(image, label)`` == zero_grad + 3 passes + 3 losses + backward + Adam step
-    (mnist/train.py:131-147,149) on ``vae``'s own parameters."""
+class _FlatImageTrainer(Trainer):
+    """The first input is a batch of images, handed to the engine as (B, 784) rows (the reference's ``x.view(-1, 784)``)."""
 
-    def __init__(self, vae: MultimodalVAE, batch_size: int, lr: float = 1e-3, seed: int = 1234, world_size: int = 1,
-                 all_reduce=None):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedMnistStep(st, batch_size, lr=lr, seed=seed, world_size=world_size, all_reduce=all_reduce)
+    def __call__(self, image, *rest, **kw) -> StepOutputs:
+        return super().__call__(image.reshape(-1, 784), *rest, **kw)
 
-    def __call__(self, image, label, **kw) -> StepOutputs:
-        return self.engine(image.reshape(-1, 784), label, **kw)
+    def evaluate(self, image, *rest, **kw) -> StepOutputs:
+        return super().evaluate(image.reshape(-1, 784), *rest, **kw)
 
-    def evaluate(self, image, label, **kw) -> StepOutputs:
-        """mnist/train.py:165-177: eval-mode forward of the 3 passes, no backward."""
-        return self.engine.forward_backward(image.reshape(-1, 784), label, training=False, backward=False, **kw)
+
+class FusedTrainer(_FlatImageTrainer):
+    """``FusedTrainer(vae, batch_size, lr)(image, label)``: mnist/train.py:131-147,149 (3 passes, 3 losses; test(): :165-177), lr
+    1e-3; the KL weight is fixed by the batch size (no ``kl_lambda``)."""
+    ENGINE, KL_LAMBDA = FusedMnistStep, None
 
 
 # ------------------------------------------------------------------------------------------------------ image-only VAE
@@ -363,32 +354,18 @@ def imageonly_loss(recon_x, x, mu, logvar):
 
 def load_checkpoint_imageonly(file_path, use_cuda=False):
     """mnist/imageonly/train_imageonly.py:46-57: rebuilds a VAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    vae = VAE(n_latents=checkpoint['n_latents'])
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, VAE, use_cuda)
 
 
-class ImageVAETrainer:
-    """``ImageVAETrainer(vae, batch_size, lr)(image)`` == zero_grad + forward + loss + backward + Adam step
-    (mnist/imageonly/train_imageonly.py:114-127) on ``vae``'s own parameters: one pass over B rows (core.FusedImageStep with
-    lambda_x = 1 / B and kl_lambda = 1 / 784, which is the reference's (BCE + KLD / 784) / B).  ``out.losses()[0]`` is that loss."""
+class ImageVAETrainer(_FlatImageTrainer):
+    """``ImageVAETrainer(vae, batch_size, lr)(image)``: mnist/imageonly/train_imageonly.py:114-127 (test(): :136-148), lr 1e-3, on a
+    ``VAE``: one pass over B rows (core.FusedImageStep with lambda_x = 1 / B and kl_lambda = 1 / 784, which is the reference's
+    (BCE + KLD / 784) / B).  ``out.losses()[0]`` is that loss."""
+    ENGINE, KL_LAMBDA = FusedImageStep, 1.0 / 784
+    ENC_DROPOUT = staticmethod(lambda vae: 0.0)        # the model has no dropout
 
-    def __init__(self, vae: VAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1.0 / 784, seed: int = 1234):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedImageStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, lambda_x=1.0 / batch_size, seed=seed)
-        self.engine.enc_dropout = False
-
-    def __call__(self, image, **kw) -> StepOutputs:
-        return self.engine(image.reshape(-1, 784), **kw)
-
-    def evaluate(self, image, **kw) -> StepOutputs:
-        """The test() closure body (mnist/imageonly/train_imageonly.py:136-148): eval-mode forward, no backward."""
-        return self.engine.forward_backward(image.reshape(-1, 784), training=False, backward=False, **kw)
+    def _engine_kw(self, vae, batch_size):
+        return {"lambda_x": 1.0 / batch_size}
 
 
 # ------------------------------------------------------------------------------------------------------ InfoVAE

@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import MMVAEError, call, ptr
 from ._ops import stream as _stream
-from .core import FusedELBOStep, FusedImageStep, FusedMMTextStep, MultimnistState, MultimnistTextState, StepOutputs
+from .core import FusedELBOStep, FusedImageStep, FusedMMTextStep, MultimnistState, MultimnistTextState, Trainer, load_vae_checkpoint
 
 # multimnist/utils.py:14-19
 max_length = 4
@@ -592,22 +592,12 @@ class ImageVAE(nn.Module):
 
 def load_checkpoint_imageonly(file_path, use_cuda=False):
     """multimnist/train_imageonly.py:29-40: rebuilds an ImageVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    vae = ImageVAE(n_latents=checkpoint['n_latents'])
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, ImageVAE, use_cuda)
 
 
 def load_checkpoint_textonly(file_path, use_cuda=False):
     """multimnist/train_textonly.py:31-42: rebuilds a TextVAE from the checkpoint dict (``state_dict``, ``n_latents``)."""
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    vae = TextVAE(checkpoint['n_latents'], use_cuda=use_cuda)
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
+    return load_vae_checkpoint(file_path, TextVAE, use_cuda, use_cuda=use_cuda)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -701,67 +691,23 @@ def textonly_loss_function(mu, logvar, recon_text, text, kl_lambda=1e-3):
 # ----------------------------------------------------------------------------------------------------------------
 # fused trainer: the train() closure body of multimnist/train.py:146-173 as one enqueue
 # ----------------------------------------------------------------------------------------------------------------
-class FusedTrainer:
-    """``FusedTrainer(vae, batch_size, lr)(image, text)`` == zero_grad + 3 passes + 3 losses + backward + Adam step,
-    operating directly on ``vae``'s parameters (which stay ordinary nn.Parameters / state_dict entries)."""
-
-    def __init__(self, vae: MultimodalVAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1e-3, seed: int = 1234,
-                 world_size: int = 1, all_reduce=None):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedELBOStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed, world_size=world_size,
-                                    all_reduce=all_reduce)
-
-    def __call__(self, image, text, **kw) -> StepOutputs:
-        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
-        self.engine.enc_dropout = self.vae.image_encoder.classifier[2].p > 0
-        self.engine.gru_dropout = self.vae.text_decoder.gru.dropout > 0
-        # the engine updates the flat parameter buffer in place and refreshes the packed bf16 copies itself
-        return self.engine(image, text, **kw)
-
-    def evaluate(self, image, text, **kw) -> StepOutputs:
-        """The test() closure body (multimnist/train.py:197-209): eval-mode forward of the 3 passes, no backward."""
-        return self.engine.forward_backward(image, text, training=False, backward=False, **kw)
+class FusedTrainer(Trainer):
+    """``FusedTrainer(vae, batch_size, lr)(image, text)``: multimnist/train.py:146-173 (3 passes, 3 losses), lr 1e-3, kl_lambda 1e-3;
+    ``evaluate`` is its test() closure body (:197-209)."""
+    ENGINE = FusedELBOStep
+    ENC_DROPOUT = staticmethod(lambda vae: vae.image_encoder.classifier[2].p)
+    GRU_DROPOUT = staticmethod(lambda vae: vae.text_decoder.gru.dropout)
 
 
-class TextVAETrainer:
-    """``TextVAETrainer(vae, batch_size, lr)(text)`` == zero_grad + forward + loss + backward + Adam step
-    (multimnist/train_textonly.py:95-113, lr default 1e-3, kl_lambda 1e-3) on ``vae``'s own parameters: one pass over B rows."""
-
-    def __init__(self, vae: TextVAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1e-3, seed: int = 1234):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedMMTextStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed)
-
-    def __call__(self, text, **kw) -> StepOutputs:
-        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
-        self.engine.gru_dropout = self.vae.decoder.gru.dropout > 0
-        return self.engine(text, **kw)
-
-    def evaluate(self, text, **kw) -> StepOutputs:
-        """The test() closure body (multimnist/train_textonly.py:118-131): eval-mode forward, no backward."""
-        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
-        return self.engine.forward_backward(text, training=False, backward=False, **kw)
+class TextVAETrainer(Trainer):
+    """``TextVAETrainer(vae, batch_size, lr)(text)``: multimnist/train_textonly.py:95-113 (test(): :118-131), lr 1e-3, kl_lambda
+    1e-3, on a ``TextVAE``: one pass over B rows."""
+    ENGINE = FusedMMTextStep
+    GRU_DROPOUT = staticmethod(lambda vae: vae.decoder.gru.dropout)
 
 
-class ImageVAETrainer:
-    """``ImageVAETrainer(vae, batch_size, lr)(image)`` == zero_grad + forward + loss + backward + Adam step
-    (multimnist/train_imageonly.py:91-106) on ``vae``'s own parameters: one pass over B rows (core.FusedImageStep)."""
-
-    def __init__(self, vae: ImageVAE, batch_size: int, lr: float = 1e-3, kl_lambda: float = 1e-3, seed: int = 1234):
-        dev = next(vae.parameters()).device
-        self.vae = vae
-        st = vae._core.sync(dev)
-        self.engine = FusedImageStep(st, batch_size, lr=lr, kl_lambda=kl_lambda, seed=seed)
-
-    def __call__(self, image, **kw) -> StepOutputs:
-        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
-        self.engine.enc_dropout = self.vae.encoder.classifier[2].p > 0
-        return self.engine(image, **kw)
-
-    def evaluate(self, image, **kw) -> StepOutputs:
-        """The test() closure body (multimnist/train_imageonly.py:115-128): eval-mode forward, no backward."""
-        self.engine.kl_lambda = kw.pop("kl_lambda", self.engine.kl_lambda)
-        return self.engine.forward_backward(image, training=False, backward=False, **kw)
+class ImageVAETrainer(Trainer):
+    """``ImageVAETrainer(vae, batch_size, lr)(image)``: multimnist/train_imageonly.py:91-106 (test(): :115-128), lr 1e-3, kl_lambda
+    1e-3, on an ``ImageVAE``: one pass over B rows (core.FusedImageStep)."""
+    ENGINE = FusedImageStep
+    ENC_DROPOUT = staticmethod(lambda vae: vae.encoder.classifier[2].p)

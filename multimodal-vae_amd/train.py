@@ -18,56 +18,21 @@ from __future__ import annotations
 
 import argparse
 import os
-import shutil
 import sys
 
 import torch
 
+from .train_common import (AverageMeter, adam_state_dict, add_generate_flags, eval_epoch, kl_lambdas, kl_schedule,  # noqa: F401
+                           mnist_digit_sources, save_checkpoint, train_epoch)
+
 DEFAULT_N_LATENTS = 100
-
-
-class AverageMeter(object):
-    """multimnist/train.py:26-42"""
-
-    def __init__(self):
-        self.reset()
-
-    def reset(self):
-        self.val = 0
-        self.avg = 0
-        self.sum = 0
-        self.count = 0
-
-    def update(self, val, n=1):
-        self.val = val
-        self.sum += val * n
-        self.count += n
-        self.avg = self.sum / self.count
-
-
-def save_checkpoint(state, is_best, folder='./', filename='checkpoint.pth.tar'):
-    """multimnist/train.py:44-49 (same file names, same dict: see ``main``)."""
-    os.makedirs(folder, exist_ok=True)
-    torch.save(state, os.path.join(folder, filename))
-    if is_best:
-        shutil.copyfile(os.path.join(folder, filename), os.path.join(folder, 'model_best.pth.tar'))
 
 
 def load_checkpoint(file_path, use_cuda=False):
     """multimnist/train.py:52-66: rebuilds a MultimodalVAE from a checkpoint written by either code base."""
+    from .core import load_vae_checkpoint
     from .multimnist import MultimodalVAE
-    checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    n_latents = checkpoint['n_latents'] if 'n_latents' in checkpoint else DEFAULT_N_LATENTS
-    vae = MultimodalVAE(n_latents=n_latents, use_cuda=use_cuda)
-    vae.load_state_dict(checkpoint['state_dict'])
-    if use_cuda:
-        vae.cuda()
-    return vae
-
-
-def kl_schedule():
-    """multimnist/train.py:227: the value advances every 5 epochs when --anneal_kl is given."""
-    return iter([1e-5, 1e-4, 1e-3, 1e-2, 1e-1, 1.0])
+    return load_vae_checkpoint(file_path, MultimodalVAE, use_cuda, DEFAULT_N_LATENTS, use_cuda=use_cuda)
 
 
 def adjusted_lr(base_lr: float, epoch: int) -> float:
@@ -93,13 +58,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--results', type=str, default='', help='folder for per-epoch sample dumps (off when empty)')
     parser.add_argument('--seed', type=int, default=1234)
     # fresh canvases made on the device at every step (multimnist_gen.MultiMNISTStream) instead of a dataset file
-    parser.add_argument('--generate', action='store_true', default=False,
-                        help='train on canvases generated on the device from MNIST digits: --mnist_train / --mnist_test, or synthetic digits with --synthetic N')
-    parser.add_argument('--mnist_train', type=str, default='', help='--generate: MNIST training split, a .pt file holding (uint8 (N,28,28), int64 (N,))')
-    parser.add_argument('--mnist_test', type=str, default='', help='--generate: MNIST test split, same layout')
-    parser.add_argument('--epoch_size', type=int, default=60000, metavar='N', help='--generate: canvases per training epoch (default: 60000)')
-    parser.add_argument('--min_digits', type=int, default=0, help='--generate: minimum number of digits per canvas (datasets.py: 0)')
-    parser.add_argument('--max_digits', type=int, default=2, help='--generate: maximum number of digits per canvas (datasets.py: 2; at most 4)')
+    add_generate_flags(parser, 'train on canvases generated on the device from MNIST digits: --mnist_train / --mnist_test, or synthetic digits with --synthetic N')
     return parser
 
 
@@ -134,13 +93,7 @@ def main(argv=None) -> dict:
         # training canvases are made on the device, one kernel in front of every step and never the same twice; the test set is
         # generated once, from the test digits, and goes through the usual loader
         from . import multimnist_gen as G
-        if args.synthetic > 0:
-            mn_tr, mn_te = D.synthetic_mnist(args.synthetic, seed=args.seed), D.synthetic_mnist(args.synthetic, seed=args.seed + 1)
-        elif args.mnist_train and args.mnist_test:
-            from .make_multimnist import load_mnist_pt
-            mn_tr, mn_te = load_mnist_pt(args.mnist_train), load_mnist_pt(args.mnist_test)
-        else:
-            raise SystemExit("--generate needs --mnist_train FILE.pt and --mnist_test FILE.pt, or --synthetic N for synthetic digits")
+        mn_tr, mn_te = mnist_digit_sources(args)
         gen_stream = G.MultiMNISTStream(mn_tr[0], mn_tr[1], args.batch_size, dev, epoch_size=args.epoch_size // world,
                                         seed=dp.rank_seed(args.seed, rank), min_digits=args.min_digits, max_digits=args.max_digits)
         n_test = max(args.batch_size * world, min(10000, args.epoch_size // 6))
@@ -181,44 +134,24 @@ def main(argv=None) -> dict:
 
     def train(epoch, kl_lambda):
         vae.train()
-        joint_loss_meter, image_loss_meter, text_loss_meter = AverageMeter(), AverageMeter(), AverageMeter()
-        n_total = len(train_loader) * args.batch_size
-        pending = []
-        for batch_idx, (image, text) in enumerate(train_loader):
-            out = trainer(image, text, kl_lambda=kl_lambda)
-            pending.append(out.losses().clone())                    # device tensor, no sync
-            if batch_idx % args.log_interval == 0:
-                for l in torch.stack(pending).cpu().tolist():        # one read-back per log interval
-                    joint_loss_meter.update(l[0], args.batch_size)
-                    image_loss_meter.update(l[1], args.batch_size)
-                    text_loss_meter.update(l[2], args.batch_size)
-                pending = []
-                print('Train Epoch: {} [{}/{} ({:.0f}%)]\tJoint Loss: {:.6f}\tImage Loss: {:.6f}\tText Loss: {:.6f}'.format(
-                    epoch, batch_idx * args.batch_size, n_total, 100. * batch_idx / max(len(train_loader), 1),
-                    joint_loss_meter.avg, image_loss_meter.avg, text_loss_meter.avg))
-        if pending:
-            for l in torch.stack(pending).cpu().tolist():
-                joint_loss_meter.update(l[0], args.batch_size)
-                image_loss_meter.update(l[1], args.batch_size)
-                text_loss_meter.update(l[2], args.batch_size)
-        print('====> Epoch: {}\tJoint loss: {:.4f}\tImage loss: {:.4f}\tText loss: {:.4f}'.format(
-            epoch, joint_loss_meter.avg, image_loss_meter.avg, text_loss_meter.avg))
-        return joint_loss_meter.avg, image_loss_meter.avg, text_loss_meter.avg
+        avgs = train_epoch(
+            train_loader, lambda b: trainer(b[0], b[1], kl_lambda=kl_lambda).losses(), args.batch_size, args.log_interval,
+            lambda seen, n_total, pct, avg: 'Train Epoch: {} [{}/{} ({:.0f}%)]\tJoint Loss: {:.6f}\tImage Loss: {:.6f}\tText Loss: {:.6f}'.format(
+                epoch, seen, n_total, pct, *avg),
+            len(train_loader) * args.batch_size, 3, log=print)          # (this module's print: rank 0 reports)
+        print('====> Epoch: {}\tJoint loss: {:.4f}\tImage loss: {:.4f}\tText loss: {:.4f}'.format(epoch, *avgs))
+        return avgs
 
-    def test(kl_lambda):
-        vae.eval()
-        trainer.engine.kl_lambda = kl_lambda
-        dp.sync_bn_buffers(state.bn_stats, state.bn_nbt)     # eval (and the checkpoint below) see the ranks' average
-        acc = torch.zeros(3, device=dev)
-        nb = 0
-        for image, text in test_loader:
-            acc += trainer.evaluate(image, text).losses()
-            nb += 1
-        acc = acc / max(nb, 1)
+    def ranks_average(acc):
         if world > 1:
             torch.distributed.all_reduce(acc)
             acc = acc / world
-        j, i, t = acc.cpu().tolist()
+        return acc
+
+    def test(kl_lambda):
+        vae.eval()
+        dp.sync_bn_buffers(state.bn_stats, state.bn_nbt)     # eval (and the checkpoint below) see the ranks' average
+        j, i, t = eval_epoch(test_loader, lambda b: trainer.evaluate(b[0], b[1], kl_lambda=kl_lambda).losses(), 3, dev, ranks_average)
         print('====> Test Epoch\tJoint loss: {:.4f}\tImage loss: {:.4f}\tText loss:{:.4f}'.format(j, i, t))
         return j + i + t, (j, i, t)
 
@@ -227,13 +160,11 @@ def main(argv=None) -> dict:
     import gc
     gc.collect()
     gc.freeze()
-    kl_lambda = 1e-3
-    schedule = kl_schedule()
+    schedule = kl_lambdas(1e-3, kl_schedule(), args.epochs, args.anneal_kl)
     best_loss = float(sys.maxsize)
     history = {"train": [], "test": []}
     for epoch in range(1, args.epochs + 1):
-        if (epoch - 1) % 5 == 0 and args.anneal_kl:
-            kl_lambda = next(schedule, kl_lambda)
+        kl_lambda = schedule[epoch - 1]
         history["train"].append(train(epoch, kl_lambda))
         loss, (joint_loss, image_loss, text_loss) = test(kl_lambda)
         history["test"].append((joint_loss, image_loss, text_loss))
@@ -272,24 +203,6 @@ def main(argv=None) -> dict:
         dp.barrier(dev)
         torch.distributed.destroy_process_group()
     return history
-
-
-def adam_state_dict(vae, engine) -> dict:
-    """The fused engine's flat Adam moments as a ``torch.optim.Adam.state_dict()`` (per-parameter views, cloned)."""
-    st = engine.state
-    step = int(engine.adam_state[0].item())
-    state = {}
-    for i, (name, shape, off) in enumerate(st.table):
-        numel = 1
-        for s in shape:
-            numel *= s
-        state[i] = {'step': torch.tensor(float(step)),
-                    'exp_avg': engine.exp_avg[off:off + numel].view(shape).clone(),
-                    'exp_avg_sq': engine.exp_avg_sq[off:off + numel].view(shape).clone()}
-    group = {'lr': engine.lr, 'betas': tuple(engine.betas), 'eps': engine.eps, 'weight_decay': 0, 'amsgrad': False,
-             'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
-             'decoupled_weight_decay': False, 'params': list(range(len(st.table)))}
-    return {'state': state, 'param_groups': [group]}
 
 
 if __name__ == "__main__":

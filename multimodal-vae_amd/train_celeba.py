@@ -19,7 +19,7 @@ import sys
 
 import torch
 
-from .train import AverageMeter, adam_state_dict, kl_schedule, save_checkpoint
+from .train_common import adam_state_dict, eval_epoch, kl_lambdas, kl_schedule, save_checkpoint, train_epoch
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -72,39 +72,17 @@ def main(argv=None) -> dict:
 
     def train(epoch, kl_lambda):
         vae.train()
-        trainer.engine.kl_lambda = kl_lambda
-        meters = AverageMeter(), AverageMeter(), AverageMeter()
-        n_total = len(train_loader) * args.batch_size
-        pending = []
-
-        def drain():
-            for l in torch.stack(pending).cpu().tolist():        # one read-back per log interval
-                for m, v in zip(meters, l):
-                    m.update(v, args.batch_size)
-            pending.clear()
-
-        for batch_idx, (image, attrs) in enumerate(train_loader):
-            pending.append(trainer(image, attrs).losses().clone())   # device tensor, no sync
-            if batch_idx % args.log_interval == 0:
-                drain()
-                print('Train Epoch: {} [{}/{} ({:.0f}%)]\tJoint Loss: {:.6f}\tImage Loss: {:.6f}\tAttrs Loss: {:.6f}'.format(
-                    epoch, batch_idx * args.batch_size, n_total, 100. * batch_idx / max(len(train_loader), 1),
-                    meters[0].avg, meters[1].avg, meters[2].avg))
-        if pending:
-            drain()
-        print('====> Epoch: {}\tJoint loss: {:.4f}\tImage loss: {:.4f}\tAttrs loss: {:.4f}'.format(
-            epoch, meters[0].avg, meters[1].avg, meters[2].avg))
-        return meters[0].avg, meters[1].avg, meters[2].avg
+        avgs = train_epoch(
+            train_loader, lambda b: trainer(b[0], b[1], kl_lambda=kl_lambda).losses(), args.batch_size, args.log_interval,
+            lambda seen, n_total, pct, avg: 'Train Epoch: {} [{}/{} ({:.0f}%)]\tJoint Loss: {:.6f}\tImage Loss: {:.6f}\tAttrs Loss: {:.6f}'.format(
+                epoch, seen, n_total, pct, *avg),
+            len(train_loader) * args.batch_size, 3)
+        print('====> Epoch: {}\tJoint loss: {:.4f}\tImage loss: {:.4f}\tAttrs loss: {:.4f}'.format(epoch, *avgs))
+        return avgs
 
     def test(kl_lambda):
         vae.eval()
-        trainer.engine.kl_lambda = kl_lambda
-        acc = torch.zeros(3, device=dev)
-        nb = 0
-        for image, attrs in test_loader:
-            acc += trainer.evaluate(image, attrs).losses()
-            nb += 1
-        j, i, a = (acc / max(nb, 1)).cpu().tolist()
+        j, i, a = eval_epoch(test_loader, lambda b: trainer.evaluate(b[0], b[1], kl_lambda=kl_lambda).losses(), 3, dev)
         print('====> Test Epoch\tJoint loss: {:.4f}\tImage loss: {:.4f}\tAttrs loss:{:.4f}'.format(j, i, a))
         return j + i + a, (j, i, a)
 
@@ -112,13 +90,11 @@ def main(argv=None) -> dict:
     import gc
     gc.collect()
     gc.freeze()
-    kl_lambda = 1e-3
-    schedule = kl_schedule()
+    schedule = kl_lambdas(1e-3, kl_schedule(), args.epochs, args.anneal_kl)
     best_loss = float(sys.maxsize)
     history = {"train": [], "test": []}
     for epoch in range(1, args.epochs + 1):
-        if (epoch - 1) % 5 == 0 and args.anneal_kl:
-            kl_lambda = next(schedule, kl_lambda)
+        kl_lambda = schedule[epoch - 1]
         history["train"].append(train(epoch, kl_lambda))
         loss, (joint_loss, image_loss, attrs_loss) = test(kl_lambda)
         history["test"].append((joint_loss, image_loss, attrs_loss))

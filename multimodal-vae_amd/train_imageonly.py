@@ -30,7 +30,8 @@ import sys
 
 import torch
 
-from .train import AverageMeter, kl_schedule, save_checkpoint
+from .train_common import add_generate_flags, adam_state_dict, eval_epoch, kl_schedule, mnist_digit_sources, save_checkpoint, train_epoch
+from .train_common import kl_lambdas as _kl_lambdas
 
 DATASETS = {
     #          n_latents  lr    kl_lambda  side
@@ -70,13 +71,7 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     parser.add_argument('--results', type=str, default=results, help='folder of the sample dumps (off when empty)')
     parser.add_argument('--seed', type=int, default=1234)
     if dataset == "multimnist":         # as train.py / train_textonly_multimnist.py
-        parser.add_argument('--generate', action='store_true', default=False,
-                            help='canvases generated on the device: --mnist_train / --mnist_test, or synthetic digits with --synthetic N')
-        parser.add_argument('--mnist_train', type=str, default='', help='--generate: MNIST training split, a .pt file holding (uint8 (N,28,28), int64 (N,))')
-        parser.add_argument('--mnist_test', type=str, default='', help='--generate: MNIST test split, same layout')
-        parser.add_argument('--epoch_size', type=int, default=60000, metavar='N', help='--generate: canvases per training epoch (default: 60000)')
-        parser.add_argument('--min_digits', type=int, default=0, help='--generate: minimum number of digits per canvas (datasets.py: 0)')
-        parser.add_argument('--max_digits', type=int, default=2, help='--generate: maximum number of digits per canvas (datasets.py: 2; at most 4)')
+        add_generate_flags(parser, 'canvases generated on the device: --mnist_train / --mnist_test, or synthetic digits with --synthetic N')
     if dataset == "mnist":
         parser.add_argument('--test_data', type=str, default='', metavar='FILE',
                             help='the test split, same layout as --data (default: the first tenth of --data is held out)')
@@ -94,36 +89,12 @@ def kl_lambdas(dataset: str, epochs: int, anneal_kl: bool = False):
     """kl_lambda of epochs 1..epochs.  celeba: loss_function's default throughout (celeba/train_imageonly.py:42,114); coco: 5e-4, or
     with --anneal_kl the next value of 1e-5, 1e-4, 1e-3 every 5 epochs, the last one kept (coco/train_imageonly.py:141-149); multimnist:
     1e-3, or with --anneal_kl the next value of 1e-5 ... 1.0 every 5 epochs (multimnist/train_imageonly.py:131-139)."""
-    kl = DATASETS[dataset][2]
-    schedule = iter(KL_SCHEDULES.get(dataset, ()))
-    out = []
-    for epoch in range(1, epochs + 1):
-        if dataset in KL_SCHEDULES and (epoch - 1) % 5 == 0 and anneal_kl:
-            kl = next(schedule, kl)
-        out.append(kl)
-    return out
+    return _kl_lambdas(DATASETS[dataset][2], KL_SCHEDULES.get(dataset, ()), epochs, anneal_kl)
 
 
 def image_adam_state_dict(vae, engine) -> dict:
-    """The engine's flat Adam moments of the ImageVAE's own parameters as a ``torch.optim.Adam.state_dict()``."""
-    st = engine.state
-    step = int(engine.adam_state[0].item())
-    plan_name = getattr(vae, "plan_name", lambda n: vae._core.prefix + n)      # (mnist.VAE's keys have no .net. level)
-    own = {plan_name(n) for n, _ in vae.named_parameters()}
-    state = {}
-    for name, shape, off in st.table:
-        if name not in own:
-            continue
-        numel = 1
-        for s in shape:
-            numel *= s
-        state[len(state)] = {'step': torch.tensor(float(step)),
-                             'exp_avg': engine.exp_avg[off:off + numel].view(shape).clone(),
-                             'exp_avg_sq': engine.exp_avg_sq[off:off + numel].view(shape).clone()}
-    group = {'lr': engine.lr, 'betas': tuple(engine.betas), 'eps': engine.eps, 'weight_decay': 0, 'amsgrad': False,
-             'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
-             'decoupled_weight_decay': False, 'params': list(range(len(state)))}
-    return {'state': state, 'param_groups': [group]}
+    """The engine's flat Adam moments of the uni-modal model's own parameters as a ``torch.optim.Adam.state_dict()``."""
+    return adam_state_dict(vae, engine, own_only=True)
 
 
 def checkpoint_dict(vae, engine, best_loss, n_latents) -> dict:
@@ -151,13 +122,7 @@ def _multimnist_loaders(args, dev):
     from . import data as D
     if args.generate:
         from . import multimnist_gen as G
-        if args.synthetic > 0:
-            mn_tr, mn_te = D.synthetic_mnist(args.synthetic, seed=args.seed), D.synthetic_mnist(args.synthetic, seed=args.seed + 1)
-        elif args.mnist_train and args.mnist_test:
-            from .make_multimnist import load_mnist_pt
-            mn_tr, mn_te = load_mnist_pt(args.mnist_train), load_mnist_pt(args.mnist_test)
-        else:
-            raise SystemExit("--generate needs --mnist_train FILE.pt and --mnist_test FILE.pt, or --synthetic N for synthetic digits")
+        mn_tr, mn_te = mnist_digit_sources(args)
         stream = G.MultiMNISTStream(mn_tr[0], mn_tr[1], args.batch_size, dev, epoch_size=args.epoch_size, seed=args.seed,
                                     min_digits=args.min_digits, max_digits=args.max_digits)
         n_test = max(args.batch_size, min(10000, args.epoch_size // 6))
@@ -238,36 +203,16 @@ def main(argv=None) -> dict:
         if args.dataset in KL_SCHEDULES:
             print('Using KL Lambda: {}'.format(kl_lambda))
         vae.train()
-        trainer.engine.kl_lambda = kl_lambda
-        meter = AverageMeter()
-        n_total = len(train_loader) * args.batch_size
-        pending = []
-
-        def drain():
-            for l in torch.stack(pending).cpu().tolist():        # one read-back per log interval
-                meter.update(l, args.batch_size)
-            pending.clear()
-
-        for batch_idx, (image, _) in enumerate(train_loader):
-            pending.append(trainer(image).losses()[0].clone())   # device tensor, no sync
-            if batch_idx % args.log_interval == 0:
-                drain()
-                print('Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(
-                    epoch, batch_idx * args.batch_size, n_total, 100. * batch_idx / max(len(train_loader), 1), meter.avg))
-        if pending:
-            drain()
-        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, meter.avg))
-        return meter.avg
+        avg, = train_epoch(
+            train_loader, lambda b: trainer(b[0], kl_lambda=kl_lambda).losses()[0], args.batch_size, args.log_interval,
+            lambda seen, n_total, pct, avg: 'Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(epoch, seen, n_total, pct, *avg),
+            len(train_loader) * args.batch_size)
+        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, avg))
+        return avg
 
     def test(kl_lambda):
         vae.eval()
-        trainer.engine.kl_lambda = kl_lambda
-        acc = torch.zeros((), device=dev)
-        nb = 0
-        for image, _ in test_loader:
-            acc += trainer.evaluate(image).losses()[0]
-            nb += 1
-        test_loss = float((acc / max(nb, 1)).item())
+        test_loss, = eval_epoch(test_loader, lambda b: trainer.evaluate(b[0], kl_lambda=kl_lambda).losses()[0], 1, dev)
         print('====> Test set loss: {:.4f}'.format(test_loss))
         return test_loss
 

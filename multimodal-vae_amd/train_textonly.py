@@ -25,7 +25,8 @@ import sys
 
 import torch
 
-from .train import AverageMeter, kl_schedule, save_checkpoint
+from .train_common import eval_epoch, kl_schedule, save_checkpoint, train_epoch
+from .train_common import kl_lambdas as _kl_lambdas
 from .train_imageonly import image_adam_state_dict as own_adam_state_dict
 
 DEFAULT_N_LATENTS = 100      # reference: 200, outside the plan's 4..124
@@ -60,14 +61,7 @@ def build_parser() -> argparse.ArgumentParser:
 def kl_lambdas(epochs: int, anneal_kl: bool = False):
     """kl_lambda of epochs 1..epochs (coco/train_textonly.py:145-153): 1e-3, or with --anneal_kl the next value of
     1e-5, 1e-4, 1e-3, 1e-2, 1e-1, 1.0 every 5 epochs, the last one kept."""
-    kl = DEFAULT_KL_LAMBDA
-    schedule = kl_schedule()
-    out = []
-    for epoch in range(1, epochs + 1):
-        if (epoch - 1) % 5 == 0 and anneal_kl:
-            kl = next(schedule, kl)
-        out.append(kl)
-    return out
+    return _kl_lambdas(DEFAULT_KL_LAMBDA, kl_schedule(), epochs, anneal_kl)
 
 
 def checkpoint_dict(vae, engine, best_loss, n_latents) -> dict:
@@ -132,36 +126,16 @@ def main(argv=None) -> dict:
 
     def train(epoch, kl_lambda):
         vae.train()
-        trainer.engine.kl_lambda = kl_lambda
-        meter = AverageMeter()
-        n_total = len(train_loader) * args.batch_size
-        pending = []
-
-        def drain():
-            for l in torch.stack(pending).cpu().tolist():        # one read-back per log interval
-                meter.update(l, args.batch_size)
-            pending.clear()
-
-        for batch_idx, (_, text) in enumerate(train_loader):
-            pending.append(trainer(text).losses()[0].clone())    # device tensor, no sync
-            if batch_idx % args.log_interval == 0:
-                drain()
-                print('Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(
-                    epoch, batch_idx * args.batch_size, n_total, 100. * batch_idx / max(len(train_loader), 1), meter.avg))
-        if pending:
-            drain()
-        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, meter.avg))
-        return meter.avg
+        avg, = train_epoch(
+            train_loader, lambda b: trainer(b[1], kl_lambda=kl_lambda).losses()[0], args.batch_size, args.log_interval,
+            lambda seen, n_total, pct, avg: 'Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(epoch, seen, n_total, pct, *avg),
+            len(train_loader) * args.batch_size)
+        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, avg))
+        return avg
 
     def test(kl_lambda):
         vae.eval()
-        trainer.engine.kl_lambda = kl_lambda
-        acc = torch.zeros((), device=dev)
-        nb = 0
-        for _, text in test_loader:
-            acc += trainer.evaluate(text).losses()[0]
-            nb += 1
-        test_loss = float((acc / max(nb, 1)).item())
+        test_loss, = eval_epoch(test_loader, lambda b: trainer.evaluate(b[1], kl_lambda=kl_lambda).losses()[0], 1, dev)
         print('====> Test set loss: {:.4f}'.format(test_loss))
         return test_loss
 

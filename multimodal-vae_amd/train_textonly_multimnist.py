@@ -21,7 +21,8 @@ import sys
 
 import torch
 
-from .train import AverageMeter, adam_state_dict, kl_schedule, save_checkpoint
+from .train_common import (adam_state_dict, add_generate_flags, eval_epoch, kl_lambdas, kl_schedule, mnist_digit_sources, save_checkpoint,
+                           train_epoch)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -40,13 +41,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--out', type=str, default='./trained_models/text_only', help='checkpoint folder')
     parser.add_argument('--results', type=str, default='./results/text_only', help='folder of the per-epoch text samples')
     parser.add_argument('--seed', type=int, default=1234)
-    parser.add_argument('--generate', action='store_true', default=False,
-                        help='labels of canvases generated on the device: --mnist_train / --mnist_test, or synthetic digits with --synthetic N')
-    parser.add_argument('--mnist_train', type=str, default='', help='--generate: MNIST training split, a .pt file holding (uint8 (N,28,28), int64 (N,))')
-    parser.add_argument('--mnist_test', type=str, default='', help='--generate: MNIST test split, same layout')
-    parser.add_argument('--epoch_size', type=int, default=60000, metavar='N', help='--generate: canvases per training epoch (default: 60000)')
-    parser.add_argument('--min_digits', type=int, default=0, help='--generate: minimum number of digits per canvas (datasets.py: 0)')
-    parser.add_argument('--max_digits', type=int, default=2, help='--generate: maximum number of digits per canvas (datasets.py: 2; at most 4)')
+    add_generate_flags(parser, 'labels of canvases generated on the device: --mnist_train / --mnist_test, or synthetic digits with --synthetic N')
     return parser
 
 
@@ -101,13 +96,7 @@ def main(argv=None) -> dict:
     torch.manual_seed(args.seed)
     if args.generate:
         from . import multimnist_gen as G
-        if args.synthetic > 0:
-            mn_tr, mn_te = D.synthetic_mnist(args.synthetic, seed=args.seed), D.synthetic_mnist(args.synthetic, seed=args.seed + 1)
-        elif args.mnist_train and args.mnist_test:
-            from .make_multimnist import load_mnist_pt
-            mn_tr, mn_te = load_mnist_pt(args.mnist_train), load_mnist_pt(args.mnist_test)
-        else:
-            raise SystemExit("--generate needs --mnist_train FILE.pt and --mnist_test FILE.pt, or --synthetic N for synthetic digits")
+        mn_tr, mn_te = mnist_digit_sources(args)
         train_loader = _StreamLabels(G.MultiMNISTStream(mn_tr[0], mn_tr[1], args.batch_size, dev, epoch_size=args.epoch_size, seed=args.seed,
                                                         min_digits=args.min_digits, max_digits=args.max_digits))
         n_test = max(args.batch_size, min(10000, args.epoch_size // 6))
@@ -136,41 +125,24 @@ def main(argv=None) -> dict:
 
     def train(epoch, kl_lambda):
         vae.train()
-        loss_meter = AverageMeter()
-        pending = []
-        for batch_idx, data in enumerate(train_loader):
-            out = trainer(data, kl_lambda=kl_lambda)
-            pending.append(out.losses()[0:1].clone())                # device tensor, no sync
-            if batch_idx % args.log_interval == 0:
-                for l in torch.cat(pending).cpu().tolist():          # one read-back per log interval
-                    loss_meter.update(l, args.batch_size)
-                pending = []
-                print('Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(
-                    epoch, batch_idx * args.batch_size, n_train, 100. * batch_idx / max(len(train_loader), 1), loss_meter.avg))
-        if pending:
-            for l in torch.cat(pending).cpu().tolist():
-                loss_meter.update(l, args.batch_size)
-        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, loss_meter.avg))
-        return loss_meter.avg
+        avg, = train_epoch(
+            train_loader, lambda text: trainer(text, kl_lambda=kl_lambda).losses()[0:1], args.batch_size, args.log_interval,
+            lambda seen, n_total, pct, avg: 'Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(epoch, seen, n_total, pct, *avg),
+            n_train)            # (the reference prints the size of the data set, not batches times batch size)
+        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, avg))
+        return avg
 
     def test(kl_lambda):
         vae.eval()
-        acc = torch.zeros(1, device=dev)
-        nb = 0
-        for data in test_loader:
-            acc += trainer.evaluate(data, kl_lambda=kl_lambda).losses()[0:1]
-            nb += 1
-        test_loss = float((acc / max(nb, 1)).item())
+        test_loss, = eval_epoch(test_loader, lambda text: trainer.evaluate(text, kl_lambda=kl_lambda).losses()[0:1], 1, dev)
         print('====> Test set loss: {:.4f}'.format(test_loss))
         return test_loss
 
-    kl_lambda = 1e-3
-    schedule = kl_schedule()
+    schedule = kl_lambdas(1e-3, kl_schedule(), args.epochs, args.anneal_kl)
     best_loss = float(sys.maxsize)
     history = {"train": [], "test": []}
     for epoch in range(1, args.epochs + 1):
-        if (epoch - 1) % 5 == 0 and args.anneal_kl:
-            kl_lambda = next(schedule, kl_lambda)
+        kl_lambda = schedule[epoch - 1]
         history["train"].append(train(epoch, kl_lambda))
         loss = test(kl_lambda)
         history["test"].append(loss)

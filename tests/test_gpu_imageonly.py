@@ -275,6 +275,32 @@ def _image_vae_of(M, mm, D):
     return iv.cuda().eval()
 
 
+@pytest.mark.parametrize("family,kind", [("celeba", "FusedTrainer"), ("coco", "ImageVAETrainer")])
+def test_trainer_takes_kl_lambda_per_call(family, kind):
+    """``trainer(x, ..., kl_lambda=0.5)`` is the step of a trainer constructed with kl_lambda = 0.5: same seed, same inputs, same step
+    counter, so the same drawn noise and masks; the losses agree as two runs of one step do (test_step_draws_its_own_noise_and_masks:
+    rtol 1e-4, the order of the fp32 atomics).  ``evaluate`` takes the keyword too."""
+    dev = _dev()
+    B, D = 8, 20
+    image, second = (t.to(dev).contiguous() for t in R.formula_inputs(family, B))
+    inputs = (image, second) if kind == "FusedTrainer" else (image,)
+
+    def trainer(**kw):
+        M, vae = _mmvae(family, D)
+        if kind == "ImageVAETrainer":
+            vae = _image_vae_of(M, vae, D)
+        return getattr(M, kind)(vae, B, seed=11, **kw)
+    per_call, built = trainer(), trainer(kl_lambda=0.5)
+    out = per_call(*inputs, kl_lambda=0.5)
+    got = out.losses().cpu().numpy()
+    assert per_call.engine.kl_lambda == 0.5 and out.kl_scale == 0.5 / B
+    want = built(*inputs).losses().cpu().numpy()
+    print("%s %s: kl_lambda=0.5 per call %s, at construction %s" % (family, kind, got, want))
+    assert np.isfinite(got).all()
+    np.testing.assert_allclose(got, want, rtol=1e-4)
+    assert per_call.evaluate(*inputs, kl_lambda=0.25).kl_scale == 0.25 / B and per_call.engine.kl_lambda == 0.25
+
+
 @pytest.mark.parametrize("family", ["celeba", "coco"])
 def test_module_face_equals_the_mmvaes_image_modules(family):
     D, B = 20, 5

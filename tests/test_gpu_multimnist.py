@@ -399,3 +399,41 @@ def test_early_optimizer_part_equals_one_adam_launch():
             moved = float((want - p_before).norm())
             assert float((st.params.double() - want).norm()) < 2e-3 * moved, (early, t, float((st.params.double() - want).norm()), moved)
             m, v = eng.exp_avg.double().clone(), eng.exp_avg_sq.double().clone()      # (follow the kernel's moments: no drift over the steps)
+
+
+def test_default_call_follows_a_change_of_betas_and_eps():
+    """The call with default arguments keeps its step-io block and optimizer argument lists between steps.  ``betas`` and ``eps`` set
+    on the engine after a step reach the next one all the same, in both parts of the update: image_decoder.* (inside the step,
+    mmvae_early_adam) and image_encoder.* (the launch behind it) follow torch.optim.Adam's arithmetic with the new values, at the
+    tolerances of test_early_optimizer_part_equals_one_adam_launch."""
+    from multimodal_vae_amd.core import FusedELBOStep, MultimnistState
+    from multimodal_vae_amd.init import default_init_
+    dev = _dev()
+    B = 16
+    rng = np.random.default_rng(5)
+    img = torch.from_numpy((rng.random((B, 1, 50, 50)) < 0.2).astype(np.float32)).to(dev)
+    txt = torch.from_numpy(rng.integers(0, 10, size=(B, 4)).astype(np.int64)).to(dev)
+    st = MultimnistState(D, dev); default_init_(st, 31)
+    eng = FusedELBOStep(st, B, seed=9)
+    eng(img, txt)
+    torch.cuda.synchronize()
+    assert eng._ea_ran.value == 1 and int(eng.adam_state[0].item()) == 1
+    eng.betas, eng.eps = (0.5, 0.9), 1e-3
+    lr, (b1, b2), eps, t = eng.lr, eng.betas, eng.eps, 2
+    m, v = eng.exp_avg.double().clone(), eng.exp_avg_sq.double().clone()
+    p_before = st.params.double().clone()
+    eng(img, txt)
+    torch.cuda.synchronize()
+    assert eng._ea_ran.value == 1 and int(eng.adam_state[0].item()) == t
+    g = st.grads.double()
+    m = b1 * m + (1 - b1) * g; v = b2 * v + (1 - b2) * g * g
+    want = p_before - (lr / (1 - b1 ** t)) * m / (v.sqrt() / (1 - b2 ** t) ** 0.5 + eps)
+    for part in ("image_decoder.", "image_encoder."):
+        idx = torch.cat([torch.arange(off, off + int(np.prod(shape)), device=dev) for n, shape, off in st.table if n.startswith(part)])
+        em, ev = float((eng.exp_avg.double() - m)[idx].abs().max()), float((eng.exp_avg_sq.double() - v)[idx].abs().max())
+        moved, ep = float((want - p_before)[idx].norm()), float((st.params.double() - want)[idx].norm())
+        print("%s exp_avg off by %.3g of %.3g, exp_avg_sq by %.3g of %.3g, parameters by %.3g of a step of %.3g"
+              % (part, em, float(m[idx].abs().max()), ev, float(v[idx].abs().max()), ep, moved))
+        assert em <= 1e-4 * float(m[idx].abs().max()), part
+        assert ev <= 1e-3 * float(v[idx].abs().max()), part
+        assert ep < 2e-3 * moved, part
