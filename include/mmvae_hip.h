@@ -180,6 +180,10 @@ int mmvae_debug_set(const char* key, int value);
 /* test aid: byte offset of a named intermediate inside the workspace (-1 if unknown); "image_step:<name>": inside the one-pass
  * workspace of mmvae_mm_image_step and of the module entry points */
 long long mmvae_mm_debug_offset(mmvae_mm_t*, const char* name);
+/* test aid: the weight-refresh part of ONE prologue launch of the fused step on `stream`, nothing zeroed or drawn: stage 0 the
+ * main stream's, 1 and 2 the second-modality stream's, -1 the unstaged launch that refreshes every copy.
+ * blocks (may be NULL): the number of pack workgroups of that launch. */
+int mmvae_mm_debug_pack_stage(mmvae_mm_t*, int stage, int* blocks, void* stream);
 
 /* ---------------------------------------------------------------- MNIST (mnist/model.py, mnist/train.py)
  * MultimodalVAE of mnist/model.py:14-50: Linear -> BatchNorm1d -> ReLU stacks (ImageEncoder :99-118, ImageDecoder

@@ -202,6 +202,10 @@ double mmvae_mm_layer_flops(const mmvae_mm_t* p, const char* layer) { return mm_
 double mmvae_mm_layer_algo_flops(const mmvae_mm_t* p, const char* layer) { return mm_layer_algo_flops(p, layer); }
 double mmvae_mm_layer_algo_bytes(const mmvae_mm_t* p, const char* layer) { return mm_layer_algo_bytes(p, layer); }
 long long mmvae_mm_debug_offset(mmvae_mm_t* p, const char* name) { return mm_debug_offset(p, name); }
+int mmvae_mm_debug_pack_stage(mmvae_mm_t* p, int stage, int* blocks, void* stream) {
+    MMVAE_REQUIRE(p && stage >= -1 && stage <= 2, "debug_pack_stage: null plan or stage %d", stage);
+    return mm_debug_pack_stage(p, stage, blocks, (hipStream_t)stream);
+}
 
 // ---- MultiMNIST text-only VAE baseline (multimnist/model.py:123-147, multimnist/train_textonly.py)
 mmvae_mmtext_t* mmvae_mmtext_create(int n_latents, int n_hiddens, int batch) {

@@ -2,27 +2,11 @@
 // apply, sigmoid+BCE, product-of-experts / reparametrisation / KL, Adam, weight packing.  See elementwise.hip.
 #pragma once
 #include "common.h"
+#include "pack_geo.h"
 
 // ---- weight packing (fp32 reference-layout master  <->  bf16 GEMM-layout copies / fp32 packed grads) ----
-struct PackDesc {
-    long long dst_off;      // element offset in the packed buffer (bf16 units for matrices, float units for vectors)
-    long long src_off;      // element offset in the flat fp32 parameter buffer
-    int Npad, Kpad, N, K;   // packed matrix [Npad][Kpad]; entries outside [N][K] are zero
-    int NL;                 // row n = n_hi*NL + n_lo
-    int s_nhi, s_nlo;       // source strides of n_hi / n_lo
-    int TW, C;              // column k = (ty*TW + tx)*C + c
-    int s_ty, s_tx, s_c;    // source strides
-    int o_ty, o_tx, step_t; // kernel index = o + t*step
-    int is_f32;             // destination is fp32 (bias vectors, Kpad == 1)
-    long long bias_off;     // >= 0: column K of every row holds a bias folded into the GEMM (operand column K == 1.0)
-    int b_nhi, b_nlo;       // source strides of that bias vector
-    int first_block;        // prefix sum of 256-thread blocks over the table
-    int part;               // gradient descriptors: 1 = complete early in the step (decoders), 0 = with the encoders' backward;
-                            // weight descriptors: the stage of the step that refreshes the copy (StepBeginArgs::pack_parts), 0 = the prologue
-    int frag;               // 1: MFMA-fragment-major destination -- 16-row tile nt, 32-column k-step ks: the 64 lanes' 8-element
-                            // vectors (lane = 16*(k/8 % 4) + n % 16) are one contiguous 1 KB block at ((nt*(Kpad/32) + ks)*64 + lane)*8
-};
-
+// struct PackDesc and the index arithmetic of the pack: pack_geo.h (plain C++, shared with the host-side geometry check).
+// Knob pack_runs (default 1): lanes walk the source's contiguous direction; 0: the row-major assignment it replaced.
 int launch_pack(const PackDesc* table_dev, const PackDesc* table_host, int ndesc, const float* params,
                 bf16* packed_bf, float* packed_f32, hipStream_t s);
 // the descriptors [d0, d1) of the table only (a plan whose streams need different parts of the packed weights first)
@@ -229,10 +213,19 @@ struct StepBeginArgs {
     const PackDesc* pack_table; int pack_nd; const float* pack_params; bf16* packed_bf; float* packed_f32; int pack_blocks;
     unsigned pack_parts;                          // 0: every descriptor; else bit p: the descriptors with PackDesc::part == p (a step that
                                                   // refreshes the copies its first kernels read in the prologue and the rest on a side stream)
+    int pack_runs;                                // knob pack_runs at the time the arguments were filled (pack_geo.h)
+    // a staged launch holds only the blocks of its own descriptors: pack block b belongs to the last range with blk0 <= b and is
+    // block b - blk0 + tb0 of the whole table (pack_nr == 0: the grid is the whole table, filtered by pack_parts)
+    int pack_nr;
+    struct PackRange { int blk0, tb0; } pack_rng[48];
 };
+constexpr int STEP_BEGIN_MAX_RANGES = 48;
+// The zero / random-number part of the grid is sized from the bytes and draws of the launch (none: no such blocks; a launch with
+// neither them nor pack blocks is not issued), at most knob begin_blocks (2048).
 int launch_step_begin(const StepBeginArgs& a, hipStream_t s);
+// parts != 0: only the descriptors with PackDesc::part in that bit set (the stages of a fused step)
 int step_begin_with_pack(StepBeginArgs& a, const PackDesc* table_dev, const PackDesc* table_host, int nd, const float* params,
-                         bf16* packed_bf, float* packed_f32);
+                         bf16* packed_bf, float* packed_f32, unsigned parts = 0u);
 
 // ---- small ops of the MLP models (mnist/model.py:136-170) ----
 // x[r][:] = table[idx[r % idx_rows]][:] as bf16 rows of stride ld (pad columns zero) + BatchNorm column statistics

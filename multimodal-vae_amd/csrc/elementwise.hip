@@ -55,20 +55,52 @@ __device__ __forceinline__ int fast_divmod_ew(int r, int d, float inv, int& rem)
     else if (rem >= d) { ++q; rem -= d; }
     return q;
 }
-__device__ __forceinline__ long long pack_src(const PackDesc& d, int n, int k) {
-    int nhi = n / d.NL, nlo = n - nhi * d.NL;
-    int tap = k / d.C, c = k - tap * d.C;
-    int ty = tap / d.TW, tx = tap - ty * d.TW;
-    return d.src_off + (long long)nhi * d.s_nhi + (long long)nlo * d.s_nlo +
-           (long long)(d.o_ty + ty * d.step_t) * d.s_ty + (long long)(d.o_tx + tx * d.step_t) * d.s_tx + (long long)c * d.s_c;
+__device__ __forceinline__ void pack_store(const PackDesc& d, bf16* __restrict__ packed_bf, float* __restrict__ packed_f32, long long e,
+                                           const float (&val)[8]) {
+    if (d.is_f32) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) packed_f32[d.dst_off + e + j] = val[j];
+    } else {
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (bf16)val[j];
+        *reinterpret_cast<bf16x8*>(packed_bf + d.dst_off + e) = o;
+    }
+}
+// The run assignment of pack_geo.h: the blocks of a descriptor share its wave-sized tasks; in each the lanes walk the source's
+// contiguous direction, so every one of the 8 loads (channel j of the lane's octet) reads whole runs instead of 64 separate lines.
+__device__ __forceinline__ void pack_block_runs(const PackDesc& d, const PackRuns& g, const float* __restrict__ params,
+                                                bf16* __restrict__ packed_bf, float* __restrict__ packed_f32, int block) {
+    const int nb = pg_blocks(d), lb = block - d.first_block;
+    const int lane = threadIdx.x & (PG_WAVE - 1);
+    for (int task = pg_first_task(lb, threadIdx.x >> 6); task < g.tasks; task += pg_task_step(nb)) {
+        int n, tap, co;
+        if (!pg_runs_decode(g, task, lane, n, tap, co)) continue;
+        const long long b = pack_src(d, n, tap * d.C + co * 8);
+        float val[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) val[j] = params[b + (long long)j * d.s_c];
+        pack_store(d, packed_bf, packed_f32, pack_dst(d, n, tap * g.CO + co), val);
+    }
+    const float zero[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = lb * TPB + threadIdx.x; i < g.zeros; i += nb * TPB) {
+        int n, kv;
+        pg_zero_decode(d, g, i, n, kv);
+        pack_store(d, packed_bf, packed_f32, pack_dst(d, n, kv), zero);
+    }
 }
 
-// one thread = 8 consecutive columns of one packed row (16-byte bf16 store); Kpad is a multiple of 8
+// runs == 0, and the descriptors that are contiguous already: one thread = 8 consecutive columns of one packed row (16-byte bf16
+// store); Kpad is a multiple of 8
 __device__ __forceinline__ void pack_block(const PackDesc* __restrict__ table, int nd, const float* __restrict__ params,
-                                           bf16* __restrict__ packed_bf, float* __restrict__ packed_f32, int block, unsigned parts = 0u) {
+                                           bf16* __restrict__ packed_bf, float* __restrict__ packed_f32, int block, unsigned parts, int runs) {
     const int di = find_desc(table, nd, block);
     const PackDesc d = table[di];
     if (parts != 0u && !((parts >> (d.part & 31)) & 1u)) return;
+    if (runs) {
+        const PackRuns g = pg_runs(d);
+        if (g.ok) { pack_block_runs(d, g, params, packed_bf, packed_f32, block); return; }
+    }
     // 32-bit index math with reciprocal divisions (packed matrices have < 2^23 vectors; launch_pack checks)
     const int v = (int)(block - d.first_block) * TPB + threadIdx.x;
     const int vpr = d.Kpad / 8;
@@ -114,8 +146,8 @@ __device__ __forceinline__ void pack_block(const PackDesc* __restrict__ table, i
 // MAP = false: grads[flat] += packed value.  MAP = true: map[flat] = where that value lives (index into gmat, or
 // -(index + 2) into gvec) -- built once per plan for the optimizer kernel that consumes the packed gradients directly.
 __global__ __launch_bounds__(TPB) void pack_kernel(const PackDesc* __restrict__ table, int nd, const float* __restrict__ params,
-                                                   bf16* __restrict__ packed_bf, float* __restrict__ packed_f32, int block0) {
-    pack_block(table, nd, params, packed_bf, packed_f32, block0 + blockIdx.x);
+                                                   bf16* __restrict__ packed_bf, float* __restrict__ packed_f32, int block0, int runs) {
+    pack_block(table, nd, params, packed_bf, packed_f32, block0 + blockIdx.x, 0u, runs);
 }
 
 template <bool MAP>
@@ -483,7 +515,13 @@ __global__ __launch_bounds__(TPB) void step_begin_kernel(const StepBeginArgs a) 
     // the first pack_blocks workgroups refresh the bf16 GEMM copies of the weights (what pack_kernel does: after an
     // optimizer step); the others zero the accumulators and draw the step's random numbers -- independent work, one launch
     if ((int)blockIdx.x < a.pack_blocks) {
-        pack_block(a.pack_table, a.pack_nd, a.pack_params, a.packed_bf, a.packed_f32, blockIdx.x, a.pack_parts);
+        int tb = blockIdx.x;
+        if (a.pack_nr > 0) {        // a stage's own grid: its ranges of table blocks, back to back
+            int r = 0;
+            while (r + 1 < a.pack_nr && tb >= a.pack_rng[r + 1].blk0) ++r;
+            tb = tb - a.pack_rng[r].blk0 + a.pack_rng[r].tb0;
+        }
+        pack_block(a.pack_table, a.pack_nd, a.pack_params, a.packed_bf, a.packed_f32, tb, a.pack_parts, a.pack_runs);
         return;
     }
     const long long gtid = (long long)(blockIdx.x - a.pack_blocks) * TPB + threadIdx.x, gstride = (long long)(gridDim.x - a.pack_blocks) * TPB;
@@ -1049,7 +1087,8 @@ int launch_pack(const PackDesc* table_dev, const PackDesc* table_host, int nd, c
     MMVAE_REQUIRE(nd > 0, "pack: empty table");
     for (int i = 0; i < nd; ++i)
         MMVAE_REQUIRE((long long)table_host[i].Npad * (table_host[i].Kpad / 8) < (1 << 23), "pack: matrix %d too large for 32-bit index math", i);
-    hipLaunchKernelGGL(pack_kernel, dim3(table_blocks(table_host, nd)), dim3(TPB), 0, s, table_dev, nd, params, packed_bf, packed_f32, 0);
+    hipLaunchKernelGGL(pack_kernel, dim3(table_blocks(table_host, nd)), dim3(TPB), 0, s, table_dev, nd, params, packed_bf, packed_f32, 0,
+                       mmvae_knob("pack_runs", 1));
     return mmvae_check_launch("pack");
 }
 int launch_pack_range(const PackDesc* table_dev, const PackDesc* table_host, int nd, int d0, int d1, const float* params, bf16* packed_bf,
@@ -1057,7 +1096,7 @@ int launch_pack_range(const PackDesc* table_dev, const PackDesc* table_host, int
     MMVAE_REQUIRE(0 <= d0 && d0 <= d1 && d1 <= nd, "pack: descriptor range [%d, %d) of %d", d0, d1, nd);
     if (d0 == d1) return MMVAE_OK;
     const int b0 = (int)table_host[d0].first_block, b1 = d1 < nd ? (int)table_host[d1].first_block : table_blocks(table_host, nd);
-    hipLaunchKernelGGL(pack_kernel, dim3(b1 - b0), dim3(TPB), 0, s, table_dev, nd, params, packed_bf, packed_f32, b0);
+    hipLaunchKernelGGL(pack_kernel, dim3(b1 - b0), dim3(TPB), 0, s, table_dev, nd, params, packed_bf, packed_f32, b0, mmvae_knob("pack_runs", 1));
     return mmvae_check_launch("pack");
 }
 int launch_unpack_grads(const PackDesc* table_dev, const PackDesc* table_host, int nd, const float* gmat, const float* gvec,
@@ -1324,17 +1363,44 @@ int launch_nll_bwd(const long long* tg, int rows, int classes, float coef, const
 int launch_step_begin(const StepBeginArgs& a, hipStream_t s) {
     for (int r = 0; r < 4; ++r)
         MMVAE_REQUIRE(a.zero_ptr[r] == nullptr || (a.zero_bytes[r] % 16 == 0 && ((uintptr_t)a.zero_ptr[r] & 15) == 0), "step_begin: zero range %d is not 16-byte aligned", r);
-    MMVAE_LAUNCH(step_begin_kernel, dim3(mmvae_knob("begin_blocks", 2048) + (a.pack_blocks > 0 ? a.pack_blocks : 0)), dim3(TPB), 0, s, a);
+    // one work item = a 16-byte store or a 4-value Philox draw; 4 per thread, no block without work
+    long long items = 0;
+    for (int r = 0; r < 4; ++r)
+        if (a.zero_ptr[r]) items += (long long)(a.zero_bytes[r] / 16);
+    if (a.eps) items += (a.n_eps + 3) / 4;
+    for (int m = 0; m < 3; ++m)
+        if (a.mask[m]) items += (a.n_mask[m] + 3) / 4;
+    const int cap = mmvae_knob("begin_blocks", 2048);
+    const int begin = mmvae_knob("pack_stage_grid", 1) == 0 ? cap : items > 0 ? nblocks(items, TPB * 4, cap > 0 ? cap : 1) : 0;
+    const int pack = a.pack_blocks > 0 ? a.pack_blocks : 0;
+    if (begin + pack == 0) return MMVAE_OK;
+    MMVAE_LAUNCH(step_begin_kernel, dim3(begin + pack), dim3(TPB), 0, s, a);
     return mmvae_check_launch("step_begin");
 }
 // fills the pack part of a step prologue (StepBeginArgs::pack_*) from a descriptor table
 int step_begin_with_pack(StepBeginArgs& a, const PackDesc* table_dev, const PackDesc* table_host, int nd, const float* params,
-                         bf16* packed_bf, float* packed_f32) {
+                         bf16* packed_bf, float* packed_f32, unsigned parts) {
     MMVAE_REQUIRE(nd > 0, "pack: empty table");
     for (int i = 0; i < nd; ++i)
         MMVAE_REQUIRE((long long)table_host[i].Npad * (table_host[i].Kpad / 8) < (1 << 23), "pack: matrix %d too large for 32-bit index math", i);
     a.pack_table = table_dev; a.pack_nd = nd; a.pack_params = params; a.packed_bf = packed_bf; a.packed_f32 = packed_f32;
+    a.pack_runs = mmvae_knob("pack_runs", 1);
     a.pack_blocks = table_blocks(table_host, nd);
+    a.pack_parts = parts; a.pack_nr = 0;
+    if (parts == 0u || mmvae_knob("pack_stage_grid", 1) == 0) return MMVAE_OK;     // (0: the whole table in every stage's grid, A/B)
+    // the stage's own blocks: maximal runs of consecutive descriptors of the stage, back to back in the grid
+    int nr = 0, blocks = 0;
+    bool fits = true;
+    for (int i = 0; i < nd && fits; ++i) {
+        if (!((parts >> (table_host[i].part & 31)) & 1u)) continue;
+        const bool cont = i > 0 && ((parts >> (table_host[i - 1].part & 31)) & 1u);
+        if (!cont) {
+            if (nr == STEP_BEGIN_MAX_RANGES) { fits = false; break; }
+            a.pack_rng[nr].blk0 = blocks; a.pack_rng[nr].tb0 = table_host[i].first_block; ++nr;
+        }
+        blocks += pg_blocks(table_host[i]);
+    }
+    if (fits) { a.pack_nr = nr; a.pack_blocks = blocks; a.pack_parts = nr > 0 ? 0u : parts; }   // (more ranges than fit: the whole table, filtered)
     return MMVAE_OK;
 }
 

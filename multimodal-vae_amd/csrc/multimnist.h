@@ -40,3 +40,5 @@ double mm_layer_flops(const MMPlan*, const char* layer);
 double mm_layer_algo_flops(const MMPlan*, const char* layer);
 double mm_layer_algo_bytes(const MMPlan*, const char* layer);
 long long mm_debug_offset(MMPlan*, const char* name);
+// the weight-refresh part of one prologue launch of mm_step alone (stage 0..2; -1: the unstaged launch)
+int mm_debug_pack_stage(MMPlan*, int stage, int* blocks, hipStream_t);

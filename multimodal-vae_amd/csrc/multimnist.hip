@@ -851,8 +851,8 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     if (skipb & 4) sb.zero_ptr[0] = nullptr;
     const bool pack_now = io.pack_first && !(skipb & 1);
     if (pack_now) {
-        MMVAE_TRY(step_begin_with_pack(sb, P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec));
-        if (staged) sb.pack_parts = 1u << 0;
+        MMVAE_TRY(step_begin_with_pack(sb, P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec,
+                                       staged ? 1u << 0 : 0u));
     }
     MMVAE_TRY(ensure_streams(P));
     P.in_step = true;
@@ -877,8 +877,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     if (T != s) MMVAE_TRY(fork_to(P, T));
     if (staged && pack_now) {       // stage 1: the text copies, in front of the text encoder
         StepBeginArgs st1{};
-        MMVAE_TRY(step_begin_with_pack(st1, P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec));
-        st1.pack_parts = 1u << 1;
+        MMVAE_TRY(step_begin_with_pack(st1, P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec, 1u << 1));
         MMVAE_TRY(launch_step_begin(st1, T));
     }
     {
@@ -886,10 +885,8 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
         MMVAE_TRY(launch_text_encoder_fwd(a, T));
     }
     if (staged && (pack_now || sb2.zero_ptr[1] || sb2.zero_ptr[2])) {      // stage 2: gradient buffers + the copies of the decoders / the backward pass
-        if (pack_now) {
-            MMVAE_TRY(step_begin_with_pack(sb2, P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec));
-            sb2.pack_parts = 1u << 2;
-        }
+        if (pack_now)
+            MMVAE_TRY(step_begin_with_pack(sb2, P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec, 1u << 2));
         MMVAE_TRY(launch_step_begin(sb2, T));
     }
     P.step_image = io.image;
@@ -1551,6 +1548,14 @@ double mm_layer_algo_bytes(const MMPlan* Pc, const char* layer) {
     return 0.0;
 }
 // ---------------------------------------------------------------- test aid: byte offset of a named workspace buffer
+int mm_debug_pack_stage(MMPlan* Pp, int stage, int* blocks, hipStream_t s) {
+    MMPlan& P = *Pp;
+    StepBeginArgs sb{};
+    MMVAE_TRY(step_begin_with_pack(sb, P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec,
+                                   stage < 0 ? 0u : 1u << stage));
+    if (blocks) *blocks = sb.pack_blocks;
+    return launch_step_begin(sb, s);
+}
 long long mm_debug_offset(MMPlan* P, const char* name) {
     Workspace ws((void*)0x1000, (size_t)1 << 40);
     // "image_step:<name>": in the one-pass carve of mm_image_step (and of the module entry points)
