@@ -164,7 +164,9 @@ int mmvae_mm_iw_score(mmvae_mm_t*, void* ws, size_t ws_bytes, const float* z, co
  * with float atomics) -- "enc_conv1" / "enc_conv1_wgrad" are the generic GEMMs over patches1 of the unfused step.
  * "dec_last_fused": the fused decoder tail of the step (3 BatchNorm groups, 2 with a last layer and a gradient; raw input q3, statistics
  * st_d2, target in tmp_f32, loss weights 1 / (B * 2500), BCE sums into sums); "dec_last_fused_reduce": the same followed by the sum of
- * its weight-gradient partials into the packed gradient, with logits / recon / dlogit written to the buffers of those names. */
+ * its weight-gradient partials into the packed gradient, with logits / recon / dlogit written to the buffers of those names.
+ * "enc_fc1_dgrad": classifier.0's data gradient as the encoder backward launches it -- four pixel classes, dy1 -> db4 for both dropout
+ * variants against the saved r4 the B images share, conv4's BatchNorm tables aff_e2 / mr_e2 and its backward sums into red_e2. */
 int mmvae_mm_bench_layer(mmvae_mm_t*, void* ws, size_t ws_bytes, const char* layer, int iters, void* stream);
 double mmvae_mm_layer_flops(const mmvae_mm_t*, const char* layer);        /* executed: 2*rows*N*K, zero-padded taps included */
 double mmvae_mm_layer_algo_flops(const mmvae_mm_t*, const char* layer);   /* algorithmic: the FlopCounterMode count of the reference layer */

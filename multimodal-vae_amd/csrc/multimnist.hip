@@ -337,6 +337,25 @@ int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, cons
     return MMVAE_OK;
 }
 
+// classifier.0's data gradient: 4 classes = the 4 pixels of the 2x2 map, each with its own [256][400] matrix; the NHWC gradients
+// of `rows` samples (both dropout variants) against the map the B images share, with the BatchNorm-backward sums of conv4
+static GemmParams fc1_dgrad_gemm(MMPlan& P, int rows) {
+    MMPlan::W& w = P.w;
+    GatherPlan pd{};
+    pd.c.AH = 1; pd.c.AW = 1; pd.c.Ald = 400; pd.c.C = 400; pd.c.sy = pd.c.sx = 1; pd.c.dy = pd.c.dx = 1;
+    pd.c.OH = 2; pd.c.OW = 2; pd.c.osy = pd.c.osx = 1; pd.c.N = 256; pd.c.nclasses = 4;
+    for (int sidx = 0; sidx < 4; ++sidx) {
+        GatherClass& k = pd.cls[sidx];
+        k.OY = 1; k.OX = 1; k.TH = 1; k.TW = 1; k.offy = 0; k.offx = 0; k.ooy = sidx / 2; k.oox = sidx % 2;
+        k.K = 400; k.Kpad = round_up(400, 64);
+    }
+    GemmParams d = gemm_of(P, pd, P.fc[0].pk_dgrad4, 1, rows);
+    d.c.A = w.dy1; d.out_bf = w.db4; d.ldo = 256;
+    d.d_r = w.r4; d.d_ld = 256; d.d_bcast_n = P.B; d.d_act = ACT_SWISH;
+    d.d_affine = w.aff_e[2]; d.d_meanrstd = w.mr_e[2]; d.d_red = w.red_e[2];
+    return d;
+}
+
 // d_out: bf16 [variants*B][lde], columns 2D.. zero (the generic kernels read their operands in 8-column vectors; 2D is a multiple
 // of 8 only when n_latents is a multiple of 4); the bias gradient of classifier.6 must already be accumulated by the caller
 // `waist` (image-only step): d_out (= w.d_encout) does not exist yet -- the waist launch forms it, and its finish launch the bias gradient
@@ -435,20 +454,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
         } else {
             MMVAE_TRY(wgrad_async(P, g, s));
         }
-        // dgrad: 4 classes = the 4 pixels of the 2x2 map, each with its own [256][400] matrix
-        GatherPlan pd{};
-        pd.c.AH = 1; pd.c.AW = 1; pd.c.Ald = 400; pd.c.C = 400; pd.c.sy = pd.c.sx = 1; pd.c.dy = pd.c.dx = 1;
-        pd.c.OH = 2; pd.c.OW = 2; pd.c.osy = pd.c.osx = 1; pd.c.N = 256; pd.c.nclasses = 4;
-        for (int sidx = 0; sidx < 4; ++sidx) {
-            GatherClass& k = pd.cls[sidx];
-            k.OY = 1; k.OX = 1; k.TH = 1; k.TW = 1; k.offy = 0; k.offx = 0; k.ooy = sidx / 2; k.oox = sidx % 2;
-            k.K = 400; k.Kpad = round_up(400, 64);
-        }
-        GemmParams d = gemm_of(P, pd, P.fc[0].pk_dgrad4, 1, rows);
-        d.c.A = w.dy1; d.out_bf = w.db4; d.ldo = 256;
-        d.d_r = w.r4; d.d_ld = 256; d.d_bcast_n = B; d.d_act = ACT_SWISH;
-        d.d_affine = w.aff_e[2]; d.d_meanrstd = w.mr_e[2]; d.d_red = w.red_e[2];
-        MMVAE_TRY(launch_gemm_gather(d, s));
+        MMVAE_TRY(launch_gemm_gather(fc1_dgrad_gemm(P, rows), s));
     }
     // ---- conv stack (features shared by all variants: gradients of the variants add up)
     bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
@@ -1322,6 +1328,7 @@ static bool layer_gemm(MMPlan& P, const std::string& name, GemmParams& g) {
             g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; g.e_mask = w.m1; g.e_mask_scale = ms;
             return true;
         }
+        if (name == "enc_fc1_dgrad") { g = fc1_dgrad_gemm(P, rows); return true; }      // as enc_bwd launches it
         if (name == "enc_fc2") {
             GatherPlan pl = dense_plan(rows, 400, 400, 200);
             g = gemm_of(P, pl, &P.fc[1].pk_fwd, 1, rows);
