@@ -177,8 +177,14 @@ double mmvae_debug_flops(int reset);
  * "coco_module_bf16" = 1 makes mmvae_coco_text_{encoder,decoder}_{fwd,bwd} run the training step's bf16 persistent caption
  * kernels on the module's B rows instead of the fp32 ones, 2 the forward ones without saving anything for a backward pass --
  * the backward entries then return MMVAE_EINVAL; a cluster launch that gave up waiting puts a NaN into element 0 of
- * sentence / dz.  DESIGN.md 4.4 lists all of them) */
+ * sentence / dz.  csrc/knobs.h is the table of all of them, with their defaults).  A key the table lacks is MMVAE_EINVAL and
+ * mmvae_last_error names it.  mmvae_debug_get: the current value and the default (either pointer may be NULL).
+ * mmvae_debug_reset: one knob back to its default, NULL: all of them.  mmvae_debug_knob_name: the table's i-th name, NULL past
+ * its end. */
 int mmvae_debug_set(const char* key, int value);
+int mmvae_debug_get(const char* key, int* value, int* dflt);
+int mmvae_debug_reset(const char* key);
+const char* mmvae_debug_knob_name(int i);
 /* test aid: byte offset of a named intermediate inside the workspace (-1 if unknown); "image_step:<name>": inside the one-pass
  * workspace of mmvae_mm_image_step and of the module entry points */
 long long mmvae_mm_debug_offset(mmvae_mm_t*, const char* name);
@@ -807,7 +813,7 @@ int mmvae_event_synchronize(void* event);            /* blocks the calling host 
  * arrays of 3 floats (lambda / divisor per pass, 0 for an absent pass); `sums` and `losses` are device pointers. */
 int mmvae_step_losses(const float* sums, const float* w_bce, const float* w_nll, const float* w_kl, float* losses, void* stream);
 /* Measurement aids (not part of the reference's interface).  mmvae_debug_set: named integer A/B switches of the library
- * (DESIGN.md lists them).  mmvae_debug_probe(1): every kernel the library launches through its tagged launcher carries a start
+ * (csrc/knobs.h lists them).  mmvae_debug_probe(1): every kernel the library launches through its tagged launcher carries a start
  * and a stop event of its own until mmvae_debug_probe(0); mmvae_debug_probe_read waits for them and writes one line per launch
  * "tag\tkernel\tmicroseconds\talgorithmic FLOPs\n" into buf (returns the number of lines) -- bench.py's in-step roofline. */
 /* ONE more HIP stream (non-blocking, default priority) for host code that needs a copy / communication stream next to the

@@ -1,5 +1,6 @@
 """ctypes binding of libmmvae_hip.so (include/mmvae_hip.h).  No CPU fallback: if the library is missing or
 no gfx950 device is usable, calls raise."""
+import contextlib
 import ctypes as C
 import os
 
@@ -173,6 +174,9 @@ SIGNATURES = {
     "mmvae_mm_layer_algo_bytes": (C.c_double, [_P, C.c_char_p]),
     "mmvae_debug_flops": (C.c_double, [_I]),
     "mmvae_debug_set": (_I, [C.c_char_p, _I]),
+    "mmvae_debug_get": (_I, [C.c_char_p, C.POINTER(_I), C.POINTER(_I)]),
+    "mmvae_debug_reset": (_I, [C.c_char_p]),
+    "mmvae_debug_knob_name": (C.c_char_p, [_I]),
     "mmvae_mm_debug_offset": (_LL, [_P, C.c_char_p]),
     "mmvae_poe_fwd": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "mmvae_poe_bwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
@@ -395,6 +399,33 @@ def call(name, *args):
     if name in _STATUS and rc != 0:
         raise MMVAEError("%s failed (%d): %s" % (name, rc, lib.mmvae_last_error().decode()))
     return rc
+
+
+@contextlib.contextmanager
+def knobs(**kw):
+    """Sets the named library knobs (csrc/knobs.h) for the block; behind it, also on an exception, exactly those are back at
+    the table's defaults.  A name the table lacks raises."""
+    try:
+        for k, v in kw.items():
+            call("mmvae_debug_set", k.encode(), int(v))
+        yield
+    finally:
+        for k in kw:
+            load().mmvae_debug_reset(k.encode())
+
+
+def knob_default(name):
+    """the table's default of one knob"""
+    d = C.c_int()
+    call("mmvae_debug_get", name.encode(), None, C.byref(d))
+    return d.value
+
+
+def knob_ptr(prefix, t):
+    """{prefix_lo: .., prefix_hi: ..} for ``knobs(**...)``: the device pointer of tensor ``t`` (None: null) as the two int halves of
+    an ADDR pair (convres_ts, wr_ts, txt_ts)"""
+    p = 0 if t is None else t.data_ptr()
+    return {prefix + "_lo": C.c_int(p & 0xffffffff).value, prefix + "_hi": C.c_int(p >> 32).value}
 
 
 def init_device(index):

@@ -315,7 +315,7 @@ static int celeba_step_body(CelebaPlan* Pp, const mmvae_celeba_step_io& io, int 
     MMVAE_TRY(att_enc_fwd(P, io.attrs, training, 2 - sk[0] - sk[2], w.attout, T));
     P.no_splitk = false;
     // BatchNorm passes folded into the staging of the image-resident conv kernels (convres.hip; their tiles hold 4 / 2 images)
-    const bool fuse = mmvae_knob("ca_fuse_bn", 1) && mmvae_knob("convres", 1) && mmvae_knob("convres_celeba", 1) && B % 4 == 0;
+    const bool fuse = mmvae_knob(K_ca_fuse_bn) && mmvae_knob(K_convres) && mmvae_knob(K_convres_celeba) && B % 4 == 0;
     MMVAE_TRY(enc_fwd(P, io.image, 2, m1, enc_drop, training, 2 - sk[0] - sk[1], w.encout, s, fuse));
     MMVAE_TRY(edge(P, T, s));
     Latent3Args la{};
@@ -348,7 +348,7 @@ static int celeba_step_body(CelebaPlan* Pp, const mmvae_celeba_step_io& io, int 
     int last_groups = 3;        // passes whose reconstruction is looked at by anyone
     if (!io.recon_image)
         while (last_groups > 1 && last.coef[last_groups - 1] == 0.f) --last_groups;
-    const bool fuse_tail = P.slab.pool != nullptr && mmvae_knob("dec_last_ca", 1) != 0;
+    const bool fuse_tail = P.slab.pool != nullptr && mmvae_knob(K_dec_last_ca) != 0;
     MMVAE_TRY(dec_fwd(P, 3, training, &last, s, last_groups, fuse_tail ? (do_backward ? std::min(img_groups, last_groups) : 0) : -1, fuse));
     if (!do_backward) {
         MMVAE_TRY(edge(P, T, s));
@@ -532,7 +532,7 @@ int celeba_bench_layer(CelebaPlan* P, void* ws, size_t wsb, const char* layer, i
     MMVAE_TRY(use_ws(P, ws, wsb, false));
     CelebaPlan::W& w = P->w;
     const std::string name = layer;
-    const uint8_t* mask = mmvae_knob("celeba_layer_mask", 0) ? w.m1 : nullptr;
+    const uint8_t* mask = mmvae_knob(K_celeba_layer_mask) ? w.m1 : nullptr;
     WgradParams wg{};
     if (tower_named_wgrad(*P, name, wg)) return tower_replay_wgrad(*P, wg, iters, s);
     GemmParams g{};

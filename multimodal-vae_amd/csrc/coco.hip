@@ -536,7 +536,7 @@ int coco_image_decoder_bwd(CocoPlan* P, void* ws, size_t wsb, const float* d_rec
 // and its unpack around each backward, the decoder's weight gradients inline; 2 runs the forward kernels without saving
 // anything for a backward pass (the SAVE = false instantiations), and the backward entries refuse.  0: the fp32 kernels of
 // coco_text.hip, as before.
-static int module_bf16() { return mmvae_knob("coco_module_bf16", 0); }
+static int module_bf16() { return mmvae_knob(K_coco_module_bf16); }
 static int module_pack(CocoPlan& P, hipStream_t s) {
     return launch_pack(P.buf.desc_dev, P.pk.d.data(), (int)P.pk.d.size(), P.buf.params, P.buf.packed, P.buf.packed_vec, s);
 }
@@ -651,7 +651,7 @@ int coco_iw_score(CocoPlan* P, void* ws, size_t wsb, const float* z, const float
 // logits [3B][3][32][32] at the start of the weight-gradient slab and recon right behind them.
 static bool named_gemm(CocoPlan& P, const std::string& name, GemmParams& g) {
     CocoPlan::W& w = P.w;
-    const bool masked = mmvae_knob("coco_layer_mask", 0) != 0;
+    const bool masked = mmvae_knob(K_coco_layer_mask) != 0;
     const uint8_t *m1 = masked ? w.m1 : nullptr, *m2 = masked ? w.m2 : nullptr;
     if (name == "fc2") { g = layer_gemm(P, CO_FC2, 2, m2); return true; }
     if (name == "fc3") { g = layer_gemm(P, CO_FC3, 2, nullptr, w.encout); return true; }

@@ -562,9 +562,8 @@ int launch_cr(const GemmParams& p, hipStream_t stream) {
     }
     a.Npad = p.npad;
     a.out = p.out_bf; a.ldo = p.ldo; a.colstats = p.colstats;
-    a.dbg = mmvae_knob("convres_dbg", 0);
-    a.ts = reinterpret_cast<unsigned long long*>(((unsigned long long)(unsigned)mmvae_knob("convres_ts_hi", 0) << 32) |
-                                                 (unsigned)mmvae_knob("convres_ts_lo", 0));
+    a.dbg = mmvae_knob(K_convres_dbg);
+    a.ts = mmvae_knob_ptr(K_convres_ts_lo, K_convres_ts_hi);
     a.d_r = p.d_r; a.d_affine = p.d_affine; a.d_meanrstd = p.d_meanrstd; a.d_red = p.d_red;
     const int kind = p.tr ? p.tr->kind : 0;
     MMVAE_REQUIRE(!(p.tr && p.tr->out == c.A) || NSPLIT == 1, "convres: an in-place staging by-product needs one workgroup per image tile");
@@ -631,13 +630,13 @@ typedef Geo<1, 64, 32, 16, 16, 32, 32, 4, 4, 2, 1> G_ca_convT3;        // halluc
 
 int try_launch_convres(const GemmParams& p, hipStream_t stream) {
     const bool forced = p.tr && p.tr->kind != 0;        // a staging transform exists only here: no fallback
-    if ((!mmvae_knob("convres", 1) && !forced) || !features_ok(p)) {
+    if ((!mmvae_knob(K_convres) && !forced) || !features_ok(p)) {
         MMVAE_REQUIRE(!forced, "convres: a staging transform was requested for a launch this path does not cover");
         return 0;
     }
     int rc;
     const int nimg = p.c.groups * p.c.group_n;
-    const int alt = mmvae_knob("convres_alt", 0);       // measurement aid: alternative tile configurations
+    const int alt = mmvae_knob(K_convres_alt);       // measurement aid: alternative tile configurations
     //                          NI  CH  WAVES NG SCR_OWN
     if ((rc = try_cr<G_mm_conv2, 1, 16, 8, 2, true>(p, stream)) != 0) return rc;
     if (alt != 3) {       // CH = 0: direct-B kernels (need the fragment-major weight copy; else the LDS-chunk form below)
@@ -658,7 +657,7 @@ int try_launch_convres(const GemmParams& p, hipStream_t stream) {
         if ((rc = try_cr<G_mm_conv4, 8, 0, 8, 2, true, 4, 4>(p, stream)) != 0) return rc;
     }
     if ((rc = try_cr<G_mm_convT3d, 2, 10, 8, 2, false>(p, stream)) != 0) return rc;
-    if (mmvae_knob("convres_celeba", 1)) {
+    if (mmvae_knob(K_convres_celeba)) {
         if ((rc = try_cr<G_ca_conv2, 1, 16, 8, 2, true>(p, stream)) != 0) return rc;
         if ((rc = try_cr<G_ca_conv3, 2, 0, 8, 4, true>(p, stream)) != 0) return rc;
         if ((rc = try_cr<G_ca_convT2, 4, 0, 8, 2, true>(p, stream)) != 0) return rc;

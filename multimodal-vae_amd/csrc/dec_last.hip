@@ -746,7 +746,7 @@ __global__ __launch_bounds__(CL_NTHR) void dec_last_ca_kernel(const DecLastFused
 }  // namespace
 
 bool dec_last_ca_applies(const DecLastFusedArgs& a) {
-    return a.Cin == CL_C && a.Cout == CL_CO && a.IH == CL_IH && a.IW == CL_IW && a.act == ACT_SWISH && mmvae_knob("dec_last_ca", 1) != 0 &&
+    return a.Cin == CL_C && a.Cout == CL_CO && a.IH == CL_IH && a.IW == CL_IW && a.act == ACT_SWISH && mmvae_knob(K_dec_last_ca) != 0 &&
            (size_t)a.G * a.B * CL_NPIX * CL_C * 2 < 0x40000000ull;
 }
 int launch_dec_last_ca(const DecLastFusedArgs& a, hipStream_t s) {
@@ -757,13 +757,13 @@ int launch_dec_last_ca(const DecLastFusedArgs& a, hipStream_t s) {
     if (mmvae_first_use_on_device(attr_set))
         hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_last_ca_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CL_LDS);
     DecLastFusedArgs b = a;
-    b.dbg = mmvae_knob("dec_last_ca_dbg", 0);      // measurement aid: bit 0 no logits, 1 no patches, 2 no input gradient, 3 no weight gradient, 4 no P
+    b.dbg = mmvae_knob(K_dec_last_ca_dbg);      // measurement aid: bit 0 no logits, 1 no patches, 2 no input gradient, 3 no weight gradient, 4 no P
     MMVAE_LAUNCH(dec_last_ca_kernel, dim3(a.B, a.G), dim3(CL_NTHR), CL_LDS, s, b);
     return mmvae_check_launch("dec_last_ca");
 }
 
 bool dec_last_mfma_applies(const DecLastFusedArgs& a) {
-    return a.Cin == 32 && a.Cout == 1 && a.IH == DL_IH && a.IW == DL_IW && a.act == ACT_SWISH && mmvae_knob("dec_last_mfma", 1) != 0 &&
+    return a.Cin == 32 && a.Cout == 1 && a.IH == DL_IH && a.IW == DL_IW && a.act == ACT_SWISH && mmvae_knob(K_dec_last_mfma) != 0 &&
            (size_t)a.G * a.B * DL_NPIX * DL_C * 2 < 0x40000000ull;
 }
 int launch_dec_last_mfma(const DecLastFusedArgs& a, hipStream_t s) {

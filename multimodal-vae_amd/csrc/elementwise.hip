@@ -1088,7 +1088,7 @@ int launch_pack(const PackDesc* table_dev, const PackDesc* table_host, int nd, c
     for (int i = 0; i < nd; ++i)
         MMVAE_REQUIRE((long long)table_host[i].Npad * (table_host[i].Kpad / 8) < (1 << 23), "pack: matrix %d too large for 32-bit index math", i);
     hipLaunchKernelGGL(pack_kernel, dim3(table_blocks(table_host, nd)), dim3(TPB), 0, s, table_dev, nd, params, packed_bf, packed_f32, 0,
-                       mmvae_knob("pack_runs", 1));
+                       mmvae_knob(K_pack_runs));
     return mmvae_check_launch("pack");
 }
 int launch_pack_range(const PackDesc* table_dev, const PackDesc* table_host, int nd, int d0, int d1, const float* params, bf16* packed_bf,
@@ -1096,7 +1096,7 @@ int launch_pack_range(const PackDesc* table_dev, const PackDesc* table_host, int
     MMVAE_REQUIRE(0 <= d0 && d0 <= d1 && d1 <= nd, "pack: descriptor range [%d, %d) of %d", d0, d1, nd);
     if (d0 == d1) return MMVAE_OK;
     const int b0 = (int)table_host[d0].first_block, b1 = d1 < nd ? (int)table_host[d1].first_block : table_blocks(table_host, nd);
-    hipLaunchKernelGGL(pack_kernel, dim3(b1 - b0), dim3(TPB), 0, s, table_dev, nd, params, packed_bf, packed_f32, b0, mmvae_knob("pack_runs", 1));
+    hipLaunchKernelGGL(pack_kernel, dim3(b1 - b0), dim3(TPB), 0, s, table_dev, nd, params, packed_bf, packed_f32, b0, mmvae_knob(K_pack_runs));
     return mmvae_check_launch("pack");
 }
 int launch_unpack_grads(const PackDesc* table_dev, const PackDesc* table_host, int nd, const float* gmat, const float* gvec,
@@ -1274,7 +1274,7 @@ int launch_adam(const AdamArgs& a_in, hipStream_t s) {
     }
     // the word after the step counter is the block ticket (both live in the caller's 16-byte state block)
     unsigned* done = reinterpret_cast<unsigned*>(a.step + 1);
-    hipLaunchKernelGGL(adam_kernel, dim3(nblocks(vecs > 0 ? vecs : 1, TPB, mmvae_knob("adam_blocks", 512))), dim3(TPB), 0, s, a, done);   // few blocks: one ticket atomic each
+    hipLaunchKernelGGL(adam_kernel, dim3(nblocks(vecs > 0 ? vecs : 1, TPB, mmvae_knob(K_adam_blocks))), dim3(TPB), 0, s, a, done);   // few blocks: one ticket atomic each
     return mmvae_check_launch("adam");
 }
 static __global__ __launch_bounds__(256) void gather_rows_kernel(const char* __restrict__ src, const long long* __restrict__ idx,
@@ -1370,8 +1370,8 @@ int launch_step_begin(const StepBeginArgs& a, hipStream_t s) {
     if (a.eps) items += (a.n_eps + 3) / 4;
     for (int m = 0; m < 3; ++m)
         if (a.mask[m]) items += (a.n_mask[m] + 3) / 4;
-    const int cap = mmvae_knob("begin_blocks", 2048);
-    const int begin = mmvae_knob("pack_stage_grid", 1) == 0 ? cap : items > 0 ? nblocks(items, TPB * 4, cap > 0 ? cap : 1) : 0;
+    const int cap = mmvae_knob(K_begin_blocks);
+    const int begin = mmvae_knob(K_pack_stage_grid) == 0 ? cap : items > 0 ? nblocks(items, TPB * 4, cap > 0 ? cap : 1) : 0;
     const int pack = a.pack_blocks > 0 ? a.pack_blocks : 0;
     if (begin + pack == 0) return MMVAE_OK;
     MMVAE_LAUNCH(step_begin_kernel, dim3(begin + pack), dim3(TPB), 0, s, a);
@@ -1384,10 +1384,10 @@ int step_begin_with_pack(StepBeginArgs& a, const PackDesc* table_dev, const Pack
     for (int i = 0; i < nd; ++i)
         MMVAE_REQUIRE((long long)table_host[i].Npad * (table_host[i].Kpad / 8) < (1 << 23), "pack: matrix %d too large for 32-bit index math", i);
     a.pack_table = table_dev; a.pack_nd = nd; a.pack_params = params; a.packed_bf = packed_bf; a.packed_f32 = packed_f32;
-    a.pack_runs = mmvae_knob("pack_runs", 1);
+    a.pack_runs = mmvae_knob(K_pack_runs);
     a.pack_blocks = table_blocks(table_host, nd);
     a.pack_parts = parts; a.pack_nr = 0;
-    if (parts == 0u || mmvae_knob("pack_stage_grid", 1) == 0) return MMVAE_OK;     // (0: the whole table in every stage's grid, A/B)
+    if (parts == 0u || mmvae_knob(K_pack_stage_grid) == 0) return MMVAE_OK;     // (0: the whole table in every stage's grid, A/B)
     // the stage's own blocks: maximal runs of consecutive descriptors of the stage, back to back in the grid
     int nr = 0, blocks = 0;
     bool fits = true;

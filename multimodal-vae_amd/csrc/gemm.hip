@@ -910,7 +910,7 @@ static int wgrad_validate(const WgradParams& p) {
 }
 
 int launch_wgrad(const WgradParams& pin, hipStream_t stream, WgradSlabCtx* ctx) {
-    const int skip = mmvae_knob("dbg_skip_wgrad", 0);           // measurement aid: the step without (1: all, 2: the ring-staged, 3: the
+    const int skip = mmvae_knob(K_dbg_skip_wgrad);           // measurement aid: the step without (1: all, 2: the ring-staged, 3: the
     if (skip == 1) return MMVAE_OK;                             // streamed single-problem, 4: the grouped) weight gradients
     MMVAE_TRY(wgrad_validate(pin));
     WgradParams p = pin;
@@ -931,7 +931,7 @@ int launch_wgrad(const WgradParams& pin, hipStream_t stream, WgradSlabCtx* ctx) 
 // Several problems of the 128 x 128 tile class in one launch; anything that does not fit the grouped kernel (another tile
 // shape, more than WGRAD_MULTI_MAX problems) is launched on its own.
 int launch_wgrad_group(const WgradParams* list, int n, hipStream_t stream, WgradSlabCtx* ctx) {
-    if (mmvae_knob("dbg_skip_wgrad", 0) == 1 || mmvae_knob("dbg_skip_wgrad", 0) == 4) return MMVAE_OK;
+    if (mmvae_knob(K_dbg_skip_wgrad) == 1 || mmvae_knob(K_dbg_skip_wgrad) == 4) return MMVAE_OK;
     constexpr bool no_group = false;
     int i = 0;
     while (i < n) {

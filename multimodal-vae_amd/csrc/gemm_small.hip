@@ -682,7 +682,7 @@ int launch_small(const GemmParams& p, hipStream_t stream) {
     // knob gemm_small_prefetch: 2 .. 4: gemm_small_kernel with that many chunks of both operands in flight per wave (default 2);
     // 0: gemm_small_kernel_v0.  Depth 2 is the one the MultiMNIST step gains from: at depth 4 the launches are as
     // short, with 234 registers per lane instead of 186, and the step is not shorter than with the old form.
-    const int depth = mmvae_knob("gemm_small_prefetch", 2);
+    const int depth = mmvae_knob(K_gemm_small_prefetch);
     if (depth <= 0) {
         MMVAE_LAUNCH((gemm_small_kernel_v0<MT, NT, KS, DGRAD>), grid, dim3(KS * 64), lds, stream, p);
     } else {

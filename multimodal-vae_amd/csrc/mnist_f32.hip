@@ -22,7 +22,7 @@ constexpr int TPBF = 256;
 // kernels 0.2255 against 0.2680 ms at B = 128 and 0.2917 against 0.3361 ms at B = 256 (spreads <= 0.0015 ms): on
 constexpr int MNIST_STRIP_DEFAULT = 1;
 inline bool strip_switch() {
-    const int k = mmvae_knob("mnist_strip", -1);              // 1 / 0: on / off; -1 (not set): the default
+    const int k = mmvae_knob(K_mnist_strip);              // 1 / 0: on / off; -1 (not set): the default
     return (k < 0 ? MNIST_STRIP_DEFAULT : k) != 0;
 }
 

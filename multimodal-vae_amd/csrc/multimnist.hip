@@ -259,7 +259,7 @@ int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, cons
     const bool drop = training && dropout;
     const float ms = 1.f / (1.f - DROP_P);
     if (!tail_only) {      // (tail_only: classifier.3 onwards, on the ay1 of an earlier call -- mm_bench_layer's replay of the image step's middle)
-    if (fuse && mmvae_knob("mm_conv1_mfma", 1)) {      // one workgroup per image on the matrix cores (conv1.hip)
+    if (fuse && mmvae_knob(K_mm_conv1_mfma)) {      // one workgroup per image on the matrix cores (conv1.hip)
         const PackDesc& d = P.pk.d[P.conv[0].pk_fwd[0]];
         MMVAE_TRY(launch_conv1_fwd_mfma(image, B, P.buf.packed + d.dst_off, d.Kpad, w.r1, w.a1, s));
     } else {
@@ -285,7 +285,7 @@ int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, cons
             tr.kind = 1;
             tr.fin = bn_fin_args(P, P.bn[P.conv[l - 1].bn], prows, 1, w.st_e[l - 2], bn_updates, w.aff_e[l - 2], w.mr_e[l - 2], training);
             g.c.A = r[l - 1]; g.tr = &tr;
-            if (mmvae_knob("mm_stage_out", 1)) tr.out = a[l - 1];      // a2 / a3: operands of the weight gradients, a by-product of the staging
+            if (mmvae_knob(K_mm_stage_out)) tr.out = a[l - 1];      // a2 / a3: operands of the weight gradients, a by-product of the staging
         }
         MMVAE_TRY(launch_gemm_gather(g, s));
         const int rows = B * L.g.OH * L.g.OW;
@@ -450,7 +450,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
             side_later(P, [pp, cls_w](hipStream_t ws_) {
                 MMVAE_TRY(launch_wgrad_group(cls_w->data(), (int)cls_w->size(), ws_, &pp->slab));
                 return pp->batch_reduce ? MMVAE_OK : launch_wgrad_reduce(&pp->slab, ws_, true);
-            }, mmvae_knob("mm_cls_lane", 1));
+            }, mmvae_knob(K_mm_cls_lane));
         } else {
             MMVAE_TRY(wgrad_async(P, g, s));
         }
@@ -488,7 +488,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
             {
                 // With staging by-products the forward of conv3 / conv4 left a2 / a3 behind and conv3's data gradient below
                 // leaves its BatchNorm-backward dr behind: nothing to materialise in front of the kernel
-                const bool byp = mmvae_knob("mm_stage_out", 1) != 0;
+                const bool byp = mmvae_knob(K_mm_stage_out) != 0;
                 const bool actp = l >= 2 && !byp;      // a[l-1] = Swish(BatchNorm(r[l-1])) was never materialised (conv3, conv4)
                 const bool bnb = fl && !(byp && l == 2);
                 const int prows = B * P.conv[l >= 2 ? l - 1 : 1].g.OH * P.conv[l >= 2 ? l - 1 : 1].g.OW;
@@ -502,7 +502,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
                     if (bnb) MMVAE_TRY(launch_bn_bwd_apply(x, ws_));
                     if (actp) MMVAE_TRY(bn_act_side(*pp, bp, rin, ao, prows, prows, 1, st, 1, ws_));
                     return wgrad_on(*pp, g0, ws_);
-                }, l == 1 ? 1 : l == 2 ? mmvae_knob("mm_conv3_lane", 0) : mmvae_knob("mm_conv4_lane", 0));
+                }, l == 1 ? 1 : l == 2 ? mmvae_knob(K_mm_conv3_lane) : mmvae_knob(K_mm_conv4_lane));
             }
             if (fuse && l == 1) MMVAE_TRY(side_flush(P, s));    // conv2's: its operands came out of conv3's data gradient (current event)
         }
@@ -515,7 +515,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
             if (fl) {
                 tr.kind = 2; tr.r = r[l]; tr.red = w.red_e[l - 1]; tr.mr = w.mr_e[l - 1]; tr.gamma = P.buf.params + b.w_off;
                 tr.inv_cnt = 1.f / (float)(B * pix); tr.groups = 1;
-                if (l == 2 && mmvae_knob("mm_stage_out", 1)) {      // conv3: dr for its weight gradient + the BatchNorm parameter gradients
+                if (l == 2 && mmvae_knob(K_mm_stage_out)) {      // conv3: dr for its weight gradient + the BatchNorm parameter gradients
                     tr.out = drr[l]; tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off;
                 }
                 d.tr = &tr;
@@ -523,7 +523,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
             // forks: behind conv4's data gradient (classifier + conv4 + conv3 weight gradients) and behind conv3's (conv2's)
             // (knob mm_forks = 1: ONE fork for the whole encoder backward, behind conv3's data gradient -- a kernel that carries a
             //  completion event ends with a system-scope release, ~8 us on the main chain per fork: tools/step_parts.py)
-            const bool flush = fuse && P.wgrad_forked && (mmvae_knob("mm_forks", 0) ? l == 2 : l >= 2);
+            const bool flush = fuse && P.wgrad_forked && (mmvae_knob(K_mm_forks) ? l == 2 : l >= 2);
             if (flush) arm_fork(P);
             MMVAE_TRY(launch_gemm_gather(d, s));
             if (flush) { MMVAE_TRY(commit_fork(P, s)); MMVAE_TRY(side_flush(P, s)); }
@@ -531,7 +531,7 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
         if (!fuse) MMVAE_TRY(wgrad_async(P, gw, s));
     }
     if (fuse && !P.wgrad_forked) MMVAE_TRY(side_flush(P, s));     // unforked (serial) use: nothing to wait for
-    if (fuse && mmvae_knob("mm_conv1_mfma", 1) && P.step_image) {       // the LAST kernel of the backward chain: conv1.hip
+    if (fuse && mmvae_knob(K_mm_conv1_mfma) && P.step_image) {       // the LAST kernel of the backward chain: conv1.hip
         const PackDesc& gd = P.gk.d[P.conv[0].gk[0]];
         MMVAE_TRY(launch_conv1_wgrad_mfma(P.step_image, B, w.d1e, P.buf.gpk + gd.dst_off, gd.Kpad, s));
     } else {   // conv1 wgrad over the im2col patches: the LAST kernel of the backward chain -- it stays on the main stream (a hop
@@ -614,7 +614,7 @@ int dec_fwd(MMPlan& P, int groups, int training, ConvTLastFwdArgs* last, hipStre
                 tr.kind = 1;
                 tr.fin = bn_fin_args(P, P.bn[Lp.bn], prpg, groups, w.st_d[l - 1], 1, w.aff_d[l - 1], w.mr_d[l - 1], training);
                 g.c.A = q[l]; g.tr = &tr;
-                if (mmvae_knob("mm_stage_out", 1)) tr.out = aq[l];     // operand of this layer's weight gradient, a by-product of the staging
+                if (mmvae_knob(K_mm_stage_out)) tr.out = aq[l];     // operand of this layer's weight gradient, a by-product of the staging
             }
             MMVAE_TRY(launch_gemm_gather(g, s));
         }
@@ -698,7 +698,7 @@ int dec_bwd(MMPlan& P, const float* dlogit, int groups, float* dz, hipStream_t s
                 // first layer, the layer input aq[l] = Swish(BatchNorm(q[l])) that the forward never wrote
                 // (with staging by-products, GatherTransform::out, both come out of kernels of the main chain instead: aq[l]
                 //  out of this layer's forward, dr out of this layer's data gradient below -- the side work is the GEMM alone)
-                const bool byp = mmvae_knob("mm_stage_out", 1) != 0;
+                const bool byp = mmvae_knob(K_mm_stage_out) != 0;
                 const bool actp = l >= 1 && !byp;
                 const BnL bp = P.bn[Lp.bn];
                 const bf16* qin = q[l]; bf16* aqo = aq[l]; const float2* st = w.st_d[l >= 1 ? l - 1 : 0];
@@ -721,11 +721,11 @@ int dec_bwd(MMPlan& P, const float* dlogit, int groups, float* dz, hipStream_t s
             if (fl) {
                 tr.kind = 2; tr.r = q[l + 1]; tr.red = w.red_d[l]; tr.mr = w.mr_d[l]; tr.gamma = P.buf.params + b.w_off;
                 tr.inv_cnt = 1.f / (float)(B * pix); tr.groups = groups;
-                if (mmvae_knob("mm_stage_out", 1)) { tr.out = dqr[l + 1]; tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off; }
+                if (mmvae_knob(K_mm_stage_out)) { tr.out = dqr[l + 1]; tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off; }
                 d.tr = &tr;
             }
             // the side work collected so far forks off the completion of the first and of the last data gradient
-            const bool flush = P.wgrad_forked && ((l == 2 && !mmvae_knob("mm_forks", 0)) || l == 0);
+            const bool flush = P.wgrad_forked && ((l == 2 && !mmvae_knob(K_mm_forks)) || l == 0);
             if (flush) arm_fork(P);
             MMVAE_TRY(launch_gemm_gather(d, s));
             if (flush) { MMVAE_TRY(commit_fork(P, s)); if (l == 2) MMVAE_TRY(side_flush(P, s)); }
@@ -758,13 +758,13 @@ int txt_dec_bwd(MMPlan& P, const TextDecArgs& f, const float* dwords, float* dz,
     // same stream: the join is the kernel's own completion event (a join on "everything enqueued on T so far" made the main chain wait
     // for ~45 us of weight-gradient launches; measured on the traces of round 4: the second-modality stream was co-critical)
     P.ev_dz = nullptr;
-    const bool own_ev = P.in_step && s == P.st_text && mmvae_knob("mm_dz_event", 1) != 0;
+    const bool own_ev = P.in_step && s == P.st_text && mmvae_knob(K_mm_dz_event) != 0;
     if (own_ev) {
         P.ev_dz = next_ev(P);
-        if (!P.capturing && !mmvae_knob("no_stop_events", 0)) mmvae_arm_stop_event(P.ev_dz);
+        if (!P.capturing && !mmvae_knob(K_no_stop_events)) mmvae_arm_stop_event(P.ev_dz);
     }
     MMVAE_TRY(launch_text_decoder_bwd(a, s));
-    if (own_ev && (mmvae_take_stop_event() != nullptr || P.capturing || mmvae_knob("no_stop_events", 0)) && hipEventRecord(P.ev_dz, s) != hipSuccess) {
+    if (own_ev && (mmvae_take_stop_event() != nullptr || P.capturing || mmvae_knob(K_no_stop_events)) && hipEventRecord(P.ev_dz, s) != hipSuccess) {
         mmvae_set_error("text decoder event failed: %s", hipGetErrorString(hipGetLastError()));
         return MMVAE_EHIP;
     }
@@ -836,14 +836,14 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     // backward pass) and the other copies are done on the second-modality stream, which the main chain joins in front of the
     // product of experts anyway.  26 -> 9 us of prologue on the main chain.
     const bool serial0 = mmvae_serial();
-    const bool staged = mmvae_knob("mm_stage_begin", 1) != 0 && !serial0;
+    const bool staged = mmvae_knob(K_mm_stage_begin) != 0 && !serial0;
     StepBeginArgs sb{}, sb2{};
     sb.zero_ptr[0] = w.zero_begin; sb.zero_bytes[0] = w.zero_bytes;
     StepBeginArgs& sz = staged ? sb2 : sb;
     if (do_backward) {
         sz.zero_ptr[1] = P.buf.gpk; sz.zero_bytes[1] = (size_t)P.gk.mat_elems * sizeof(float);
         sz.zero_ptr[2] = P.buf.grads; sz.zero_bytes[2] = (size_t)(P.nparams / 4) * 16;     // tail (< 4 floats) below
-        const int skipz = mmvae_knob("dbg_begin_skip_zero", 0);      // measurement aid (results are garbage): 1 gpk, 2 grads, 3 both
+        const int skipz = mmvae_knob(K_dbg_begin_skip_zero);      // measurement aid (results are garbage): 1 gpk, 2 grads, 3 both
         if (skipz & 1) sz.zero_ptr[1] = nullptr;
         if (skipz & 2) sz.zero_ptr[2] = nullptr;
     }
@@ -852,7 +852,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     if (training && io.enc_dropout && !m1) { sb.mask[0] = w.m1; sb.n_mask[0] = (long long)2 * B * 400; m1 = w.m1; }
     if (training && io.enc_dropout && !m2) { sb.mask[1] = w.m2; sb.n_mask[1] = (long long)2 * B * 200; m2 = w.m2; }
     if (training && io.gru_dropout && !gk) { sb.mask[2] = w.gkeep; sb.n_mask[2] = (long long)4 * B3 * P.H; gk = w.gkeep; }
-    const int skipb = mmvae_knob("dbg_begin_skip", 0);              // measurement aid (results are garbage): 1 no pack, 2 no random draws, 4 no workspace zeroing
+    const int skipb = mmvae_knob(K_dbg_begin_skip);              // measurement aid (results are garbage): 1 no pack, 2 no random draws, 4 no workspace zeroing
     if (skipb & 2) { sb.eps = nullptr; sb.mask[0] = sb.mask[1] = sb.mask[2] = nullptr; }
     if (skipb & 4) sb.zero_ptr[0] = nullptr;
     const bool pack_now = io.pack_first && !(skipb & 1);
@@ -898,7 +898,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     P.step_image = io.image;
     // B % 8: the fused layers have no fallback kernel ("forced" launches) and conv4's geometry is compiled for 8 images per
     // workgroup only; other batch sizes run the unfused bn_act + gather-GEMM chain
-    const bool fuse = mmvae_knob("mm_fuse_bn", 1) != 0 && mmvae_knob("convres", 1) != 0 && B % 8 == 0;
+    const bool fuse = mmvae_knob(K_mm_fuse_bn) != 0 && mmvae_knob(K_convres) != 0 && B % 8 == 0;
     MMVAE_TRY(enc_fwd(P, io.image, 2, m1, m2, enc_drop, training, enc_updates, w.encout, s, fuse));
     MMVAE_TRY(edge(P, T, s));
     // ---- product of experts + reparametrisation + KL for the three passes
@@ -918,7 +918,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     if (io.tokens) td.tokens_out = io.tokens;
     td.target = io.text; td.nll_sum = w.sums + 4; td.dwords = do_backward ? w.dwords : nullptr;
     for (int k = 0; k < 3; ++k) td.nll_coef[k] = sk[k] ? 0.f : io.lambda_yx[k] / (float)(B * TXT_T);
-    if (const int half = mmvae_knob("dbg_text_rows_div", 0)) td.R = max(16, td.R / half);      // measurement aid (garbage results): the text decoder on a fraction of its rows
+    if (const int half = mmvae_knob(K_dbg_text_rows_div)) td.R = max(16, td.R / half);      // measurement aid (garbage results): the text decoder on a fraction of its rows
     MMVAE_TRY(launch_text_decoder_fwd(td, T));
     if (do_backward) MMVAE_TRY(txt_dec_bwd(P, td, w.dwords, w.dz_txt, T));
     // decoders on 3B rows, BatchNorm statistics per pass; last layer fused with sigmoid + BCE (+ gradient)
@@ -947,7 +947,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     // knob mm_wgrad_inline: the image path's weight gradients stay on the main stream, right behind the data gradient that made
     // their operands (no fork, no join, no contention with the main chain's kernels; 2: their partial copies summed by ONE launch
     // in front of the optimizer instead of one per layer)
-    P.wgrad_forked = mmvae_knob("mm_wgrad_inline", 0) == 0;
+    P.wgrad_forked = mmvae_knob(K_mm_wgrad_inline) == 0;
     int rc = MMVAE_OK;
     P.deferred.clear();
     P.defer_wgrad = false;
@@ -957,7 +957,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
     //      behind ev_txtgrads on the second-modality stream.  Their Adam update runs in the gap that stream has until the encoders'
     //      weight gradients arrive, beside the encoders' backward -- the optimizer launch behind the step shrinks to the encoders' ranges.
     if (io.early_adam && rc == MMVAE_OK && img_groups > 0 && fuse && fuse_tail && P.wgrad_forked && !serial && T != s && !io.dp_split &&
-        io.defer_unpack && P.ev_txtgrads && P.side_pending.empty() && P.st_wgrad2 == P.st_wgrad && mmvae_knob("mm_early_adam", 1)) {
+        io.defer_unpack && P.ev_txtgrads && P.side_pending.empty() && P.st_wgrad2 == P.st_wgrad && mmvae_knob(K_mm_early_adam)) {
         hipStream_t Wst = P.st_wgrad;
         AdamArgs ad{};
         const mmvae_early_adam& ea = *io.early_adam;
@@ -975,7 +975,7 @@ static int mm_step_body(MMPlan* Pp, const mmvae_mm_step_io& io, int training, in
         }
     }
     if (rc == MMVAE_OK) {                            // dz of the text decoder
-        const int k = mmvae_knob("dbg_skip_edges", 0);
+        const int k = mmvae_knob(K_dbg_skip_edges);
         if (P.ev_dz && T != s) {
             if (k != 1 && k != 3 && hipStreamWaitEvent(s, P.ev_dz, 0) != hipSuccess) {
                 mmvae_set_error("stream join failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1094,7 +1094,7 @@ static int mm_image_step_body(MMPlan* Pp, const mmvae_image_step_io& io, int tra
     MMPlan::W& w = P.w;
     const int B = P.B, D = P.D;
     MMVAE_REQUIRE(io.image && io.sums, "image step: image/sums must be given");
-    const int wk = mmvae_knob("mm_image_waist", -1);          // 1 / 0: on / off where compiled; -1 (not set): the size's default
+    const int wk = mmvae_knob(K_mm_image_waist);          // 1 / 0: on / off where compiled; -1 (not set): the size's default
     ImageMiddle m{};
     m.waist = P.waist && (wk < 0 ? mm_image_waist_default(D) : wk) != 0;
     MMVAE_REQUIRE(launch_latent1_scratch_floats(B, D) <= (size_t)B * NPIX && 2 * mlp2_latent1_scratch_doubles(B, D) <= (size_t)B * NPIX,

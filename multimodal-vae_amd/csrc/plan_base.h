@@ -115,11 +115,11 @@ inline int wgrad_async(PlanBase& P, const WgradParams& g, hipStream_t s) {
 inline void arm_fork(PlanBase& P) {
     if (!P.in_step) return;
     P.fork_ev = next_ev(P);
-    if (!P.capturing && !mmvae_knob("no_stop_events", 0)) mmvae_arm_stop_event(P.fork_ev);
+    if (!P.capturing && !mmvae_knob(K_no_stop_events)) mmvae_arm_stop_event(P.fork_ev);
 }
 inline int commit_fork(PlanBase& P, hipStream_t s) {
     if (!P.in_step) return MMVAE_OK;
-    const bool unclaimed = mmvae_take_stop_event() != nullptr || P.capturing || mmvae_knob("no_stop_events", 0);
+    const bool unclaimed = mmvae_take_stop_event() != nullptr || P.capturing || mmvae_knob(K_no_stop_events);
     if (unclaimed && hipEventRecord(P.fork_ev, s) != hipSuccess) {
         mmvae_set_error("stream fork failed: %s", hipGetErrorString(hipGetLastError()));
         return MMVAE_EHIP;
@@ -128,7 +128,7 @@ inline int commit_fork(PlanBase& P, hipStream_t s) {
 }
 inline int fork_to(PlanBase& P, hipStream_t to) {
     {
-        const int k = mmvae_knob("dbg_skip_edges", 0);
+        const int k = mmvae_knob(K_dbg_skip_edges);
         if (k == 1 || k == 2) return MMVAE_OK;
     }
     if (hipStreamWaitEvent(to, P.fork_ev, 0) != hipSuccess) {
@@ -154,12 +154,12 @@ inline int side_flush(PlanBase& P, hipStream_t s) {
     if (P.side_pending.empty()) return MMVAE_OK;
     const bool serial = mmvae_serial();
     int rc = MMVAE_OK;
-    P.batch_reduce = mmvae_knob("batch_reduce", 1) != 0;
+    P.batch_reduce = mmvae_knob(K_batch_reduce) != 0;
     if (!P.wgrad_forked || serial) {
         for (auto& fn : P.side_pending)
             if (rc == MMVAE_OK) rc = fn.first(s);
         P.side_pending.clear();
-        if (rc == MMVAE_OK && P.batch_reduce && !(mmvae_knob("mm_wgrad_inline", 0) == 2)) rc = launch_wgrad_reduce(&P.slab, s, true);
+        if (rc == MMVAE_OK && P.batch_reduce && !(mmvae_knob(K_mm_wgrad_inline) == 2)) rc = launch_wgrad_reduce(&P.slab, s, true);
         P.batch_reduce = false;
         return rc;
     }
@@ -167,7 +167,7 @@ inline int side_flush(PlanBase& P, hipStream_t s) {
     // latency chain on a fraction of the chip; two of them side by side finish sooner than one after the other)
     hipStream_t w[4] = {P.st_wgrad, P.st_wgrad2, P.st_text, P.st_wgrad2_own};
     bool forked[4] = {false, false, false, false};
-    const int lanes = mmvae_knob("side_lanes", 3);          // bit 0: lane 1 -> the second-modality stream, bit 1: lane 2 -> the spare weight-gradient stream
+    const int lanes = mmvae_knob(K_side_lanes);          // bit 0: lane 1 -> the second-modality stream, bit 1: lane 2 -> the spare weight-gradient stream
     for (auto& fn : P.side_pending) {
         const int i = (fn.second == 1 && P.st_text && (lanes & 1)) ? 2 : (fn.second == 2 && P.st_wgrad2_own && (lanes & 2)) ? 3 :
                       (w[0] == w[1]) ? 0 : (P.wgrad_rr++ & 1);
@@ -191,9 +191,9 @@ inline int wgrad_side_stream(PlanBase& P, hipStream_t s, hipStream_t* w) {
     return edge(P, s, *w);
 }
 inline int wgrad_on(PlanBase& P, const WgradParams& g, hipStream_t w) {
-    if (mmvae_knob("wgrad_atomic", 0)) return launch_wgrad(g, w, nullptr);      // A/B: fp32 atomics into the packed gradient, no slab / reduce
+    if (mmvae_knob(K_wgrad_atomic)) return launch_wgrad(g, w, nullptr);      // A/B: fp32 atomics into the packed gradient, no slab / reduce
     MMVAE_TRY(launch_wgrad(g, w, &P.slab));
-    if (!P.wgrad_forked && mmvae_knob("mm_wgrad_inline", 0) == 2) return MMVAE_OK;      // summed at the end of the step, one launch
+    if (!P.wgrad_forked && mmvae_knob(K_mm_wgrad_inline) == 2) return MMVAE_OK;      // summed at the end of the step, one launch
     if (P.batch_reduce) return MMVAE_OK;                                                 // summed at the end of the flush
     return launch_wgrad_reduce(&P.slab, w, true);
 }
@@ -476,7 +476,7 @@ inline hipEvent_t next_ev(PlanBase& P) {
         // other devices' benefit) only slows the kernels behind it -- 671 -> 645 us per MultiMNIST step without it.  The host reads
         // results after a stream synchronisation, the gradient exchange runs behind kernels of the caller's stream.
         // (knob ev_flags: 0 the default fence, 2 none; hipEventReleaseToDevice alone changed nothing)
-        const int ef = mmvae_knob("ev_flags", 2);
+        const int ef = mmvae_knob(K_ev_flags);
         hipEventCreateWithFlags(&e, hipEventDisableTiming | ((ef & 2) ? hipEventDisableSystemFence : 0u));
         P.events.push_back(e);
     }
@@ -485,7 +485,7 @@ inline hipEvent_t next_ev(PlanBase& P) {
 // `to` waits for everything enqueued on `from` so far
 inline int edge(PlanBase& P, hipStream_t from, hipStream_t to) {
     {   // measurement aid (only meaningful with the side work switched off): 1 all edges, 2 forks (main -> side), 3 joins
-        const int k = mmvae_knob("dbg_skip_edges", 0);
+        const int k = mmvae_knob(K_dbg_skip_edges);
         const bool to_side = to == P.st_text || to == P.st_wgrad || to == P.st_wgrad2;
         if (k == 1 || (k == 2 && to_side) || (k == 3 && !to_side)) return MMVAE_OK;
     }
@@ -530,7 +530,7 @@ inline int ensure_streams(PlanBase& P) {
         }
         P.st_text = shared[0]; P.st_wgrad = shared[1]; P.st_wgrad2 = shared[2]; P.st_wgrad2_own = shared[2];
     }
-    P.st_wgrad2 = (P.single_wgrad_stream || mmvae_knob("one_wgrad_stream", 0)) ? P.st_wgrad : P.st_wgrad2_own;
+    P.st_wgrad2 = (P.single_wgrad_stream || mmvae_knob(K_one_wgrad_stream)) ? P.st_wgrad : P.st_wgrad2_own;
     P.next_event = 0; P.wgrad_rr = 0;
     return MMVAE_OK;
 }
@@ -542,7 +542,7 @@ inline int join_sides(PlanBase& P, hipStream_t T, hipStream_t s) {
     hipStream_t hub = P.st_wgrad;
     // (with ONE weight-gradient stream there are two side streams: the main stream waiting for each of them directly measured
     //  628 against 634 us per MultiMNIST step)
-    const int oj = mmvae_knob("one_join", -1);          // (-1: not set.  A call site caches the value it looked up: the default must not vary)
+    const int oj = mmvae_knob(K_one_join);          // (-1: not set)
     if (!hub || hub == s || T == s || (oj >= 0 ? oj == 0 : P.st_wgrad2 == P.st_wgrad)) {
         if (T != s) MMVAE_TRY(edge(P, T, s));
         if (hub && hub != s) MMVAE_TRY(edge(P, hub, s));

@@ -854,21 +854,21 @@ int run_decoder_bwd(const TextDecBwdArgs& a, hipStream_t s) {
 }  // namespace
 
 int launch_text_encoder_fwd(const TextEncArgs& a, hipStream_t s) {
-    if (mmvae_knob("dbg_skip_text", 0)) return MMVAE_OK;          // measurement aid: the step without its text kernels
+    if (mmvae_knob(K_dbg_skip_text)) return MMVAE_OK;          // measurement aid: the step without its text kernels
     TXT_REQUIRE_H(a.H, "text encoder");
     MMVAE_REQUIRE(a.B >= 1 && a.D >= 1 && 2 * a.D <= 256 && a.nh2p % 16 == 0 && a.nh2p >= 2 * a.D && a.nh2p <= 256 &&
                   a.fwd.kih == txt_hp(a.H) && a.rev.kih == txt_hp(a.H), "text encoder: B=%d D=%d H=%d nh2p=%d kih=%d", a.B, a.D, a.H, a.nh2p, a.fwd.kih);
     return a.H == TXT_H ? run_encoder_fwd<TXT_H>(a, s) : run_encoder_fwd<50>(a, s);
 }
 int launch_text_encoder_bwd(const TextEncBwdArgs& a, hipStream_t s) {
-    if (mmvae_knob("dbg_skip_text", 0)) return MMVAE_OK;          // measurement aid: the step without its text kernels
+    if (mmvae_knob(K_dbg_skip_text)) return MMVAE_OK;          // measurement aid: the step without its text kernels
     TXT_REQUIRE_H(a.f.H, "text encoder bwd");
     MMVAE_REQUIRE(a.f.B >= 1 && a.f.D >= 1 && 2 * a.f.D <= 256, "text encoder bwd: B=%d D=%d", a.f.B, a.f.D);
     return a.f.H == TXT_H ? run_encoder_bwd<TXT_H>(a, s) : run_encoder_bwd<50>(a, s);
 }
 int launch_text_decoder_fwd(const TextDecArgs& a_in, hipStream_t s) {
     const TextDecArgs& a = a_in;
-    if (mmvae_knob("dbg_skip_text", 0)) return MMVAE_OK;          // measurement aid: the step without its text kernels
+    if (mmvae_knob(K_dbg_skip_text)) return MMVAE_OK;          // measurement aid: the step without its text kernels
     TXT_REQUIRE_H(a.H, "text decoder");
     MMVAE_REQUIRE(a.R >= 1 && a.D >= 1 && a.D <= 128 && a.kx == txt_kx(a.H, a.D) && a.kz == round_up(a.D, 32) && a.kx <= txt_kx(a.H, 128) &&
                   a.l0.kih == a.kx && a.l1.kih == txt_hp(a.H),
@@ -877,16 +877,16 @@ int launch_text_decoder_fwd(const TextDecArgs& a_in, hipStream_t s) {
     static std::atomic<unsigned> once{0};
     if (mmvae_first_use_on_device(once)) set_lds_attr(text_decoder_fwd2_kernel<7>, 160 * 1024);
     // the weights-resident form is compiled for kx = 224, kz = 128 (n_latents = 97..100: the reference's 100); other sizes stream
-    if (mmvae_knob("text_fwd2", 1) && a_in.kx == 224 && a_in.kz == 128 && a_in.l0.kih == 224 && a_in.l1.kih == TXT_HP) {
+    if (mmvae_knob(K_text_fwd2) && a_in.kx == 224 && a_in.kz == 128 && a_in.l0.kih == 224 && a_in.l1.kih == TXT_HP) {
         TextDecArgs a = a_in;
-        a.ts = reinterpret_cast<unsigned long long*>(((unsigned long long)(unsigned)mmvae_knob("txt_ts_hi", 0) << 32) | (unsigned)mmvae_knob("txt_ts_lo", 0));
+        a.ts = mmvae_knob_ptr(K_txt_ts_lo, K_txt_ts_hi);
         hipLaunchKernelGGL(text_decoder_fwd2_kernel<7>, dim3(ceil_div(a.R, TR)), dim3(NTHR), dec_lds_bytes<TXT_H>(224, 128) + (size_t)(TXT_G3P / 16) * 3 * 1024, s, a);
         return mmvae_check_launch("text_decoder_fwd");
     }
     return run_decoder_fwd<TXT_H>(a, s);
 }
 int launch_text_decoder_bwd(const TextDecBwdArgs& a, hipStream_t s) {
-    if (mmvae_knob("dbg_skip_text", 0)) return MMVAE_OK;          // measurement aid: the step without its text kernels
+    if (mmvae_knob(K_dbg_skip_text)) return MMVAE_OK;          // measurement aid: the step without its text kernels
     MMVAE_REQUIRE(a.f.tokens_out != nullptr || a.f.force_tokens != nullptr, "text decoder bwd needs the token path");
     TXT_REQUIRE_H(a.f.H, "text decoder bwd");
     MMVAE_REQUIRE(a.f.R >= 1 && a.f.D >= 1 && a.f.D <= 128 && a.f.kx == txt_kx(a.f.H, a.f.D), "text decoder bwd: R=%d D=%d H=%d kx=%d", a.f.R, a.f.D, a.f.H, a.f.kx);

@@ -52,33 +52,45 @@ extern "C" int mmvae_set_stream_policy(int flat) {
     return MMVAE_OK;
 }
 
-// ---- test / A-B knobs (include/mmvae_hip.h: mmvae_debug_set): a small process-wide table of named integers
+// ---- test / A-B knobs (knobs.h; include/mmvae_hip.h: mmvae_debug_set / _get / _reset / _knob_name)
 #include <mutex>
 #include <cstring>
+#define KNOB(name, dflt, kind, doc) {dflt},
+std::atomic<int> g_mmvae_knobs[K_COUNT] = {MMVAE_KNOBS(KNOB)};
+#undef KNOB
 namespace {
-struct Knob { char key[32]; int value; };
-Knob g_knobs[96];
-int g_nknobs = 0;
-std::mutex g_knob_mu;
+#define KNOB(name, dflt, kind, doc) {#name, dflt},
+const struct { const char* name; int dflt; } g_knob_table[K_COUNT] = {MMVAE_KNOBS(KNOB)};
+#undef KNOB
+// index of a name, or -1 with the error set
+int knob_index(const char* who, const char* key) {
+    for (int i = 0; key && i < K_COUNT; ++i)
+        if (strcmp(g_knob_table[i].name, key) == 0) return i;
+    mmvae_set_error("%s: no knob named \"%.64s\" (csrc/knobs.h)", who, key ? key : "(null)");
+    return -1;
 }
-std::atomic<unsigned> g_mmvae_knob_gen{0};
-int mmvae_knob_lookup(const char* key, int dflt) {
-    std::lock_guard<std::mutex> g(g_knob_mu);
-    for (int i = 0; i < g_nknobs; ++i)
-        if (strcmp(g_knobs[i].key, key) == 0) return g_knobs[i].value;
-    return dflt;
 }
 extern "C" int mmvae_debug_set(const char* key, int value) {
-    if (!key || strlen(key) >= sizeof(g_knobs[0].key)) { mmvae_set_error("debug_set: bad key"); return MMVAE_EINVAL; }
-    std::lock_guard<std::mutex> g(g_knob_mu);
-    for (int i = 0; i < g_nknobs; ++i)
-        if (strcmp(g_knobs[i].key, key) == 0) { g_knobs[i].value = value; g_mmvae_knob_gen.fetch_add(1); return MMVAE_OK; }
-    if (g_nknobs == (int)(sizeof(g_knobs) / sizeof(g_knobs[0]))) { mmvae_set_error("debug_set: table full"); return MMVAE_ENOSPC; }
-    strcpy(g_knobs[g_nknobs].key, key);
-    g_knobs[g_nknobs++].value = value;
-    g_mmvae_knob_gen.fetch_add(1);
+    const int i = knob_index("debug_set", key);
+    if (i < 0) return MMVAE_EINVAL;
+    g_mmvae_knobs[i].store(value, std::memory_order_relaxed);
     return MMVAE_OK;
 }
+extern "C" int mmvae_debug_get(const char* key, int* value, int* dflt) {
+    const int i = knob_index("debug_get", key);
+    if (i < 0) return MMVAE_EINVAL;
+    if (value) *value = g_mmvae_knobs[i].load(std::memory_order_relaxed);
+    if (dflt) *dflt = g_knob_table[i].dflt;
+    return MMVAE_OK;
+}
+extern "C" int mmvae_debug_reset(const char* key) {
+    const int i = key ? knob_index("debug_reset", key) : -1;
+    if (key && i < 0) return MMVAE_EINVAL;
+    for (int k = 0; k < K_COUNT; ++k)
+        if (!key || k == i) g_mmvae_knobs[k].store(g_knob_table[k].dflt, std::memory_order_relaxed);
+    return MMVAE_OK;
+}
+extern "C" const char* mmvae_debug_knob_name(int i) { return i >= 0 && i < K_COUNT ? g_knob_table[i].name : nullptr; }
 
 int mmvae_cu_count() {
     static std::atomic<int> cached[16];

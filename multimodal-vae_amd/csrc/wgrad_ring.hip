@@ -456,8 +456,8 @@ int try_wr(const WgradParams& p, hipStream_t stream, WgradSlabCtx* ctx) {
     // pair form: opt-in.  Measured (gpurun_out/s2, DESIGN tried-and-lost): the loop is faster (hallucinate.6 without its epilogue 16.6
     // against 23.9 us: 65 instead of 45 MFMAs per SIMD and batch in the same 1.6 us), but at equal workgroup count every class has
     // twice the partial copies -- the atomic epilogue takes 6-9 us per workgroup instead of 3-5 -- and the step is 591-612 against 589 us
-    if (G::PAIR && !mmvae_knob("wr_pair", 0)) return 0;          // (the one-class-per-workgroup geometry of the same layer follows in the list)
-    if (mmvae_knob("dbg_skip_wgrad", 0) == 2) return 1;         // measurement aid: the step without the ring-staged weight gradients
+    if (G::PAIR && !mmvae_knob(K_wr_pair)) return 0;          // (the one-class-per-workgroup geometry of the same layer follows in the list)
+    if (mmvae_knob(K_dbg_skip_wgrad) == 2) return 1;         // measurement aid: the step without the ring-staged weight gradients
     const GatherCommon& c = p.c;
     const int nimg = c.groups * c.group_n;
     if (nimg % G::IB != 0 || !p.cls[0].dWp || !ctx || !ctx->pool) return 0;
@@ -469,13 +469,13 @@ int try_wr(const WgradParams& p, hipStream_t stream, WgradSlabCtx* ctx) {
     // that takes every CU for a shorter time (MultiMNIST: 652 -> 648 us per step at half the chip, 634 with ONE weight-gradient
     // stream); the 9-17 GFLOP layers of CelebA run shorter on the whole chip (1.873 against 1.888 ms per step)
     const double macs = (double)nimg * G::OYX * G::KH * G::KW * G::C * G::N;
-    const int wq = mmvae_knob("wr_wgs", -1);            // (-1: not set.  A call site caches the value it looked up: the default must not vary)
+    const int wq = mmvae_knob(K_wr_wgs), wqb = mmvae_knob(K_wr_wgs_big);            // (-1 / 0: not set)
     // (re-tuned after the critical-path work of the round's second half -- the second-modality stream is no longer waited for and the
     //  decoders' optimizer part runs in this stream's gap: three quarters of the chip 574.8 us per step, half 579.3, all of it 579.8)
-    const int target = (G::WGQ > 0 ? mmvae_knob("wr_wgs_big", G::WGQ) : wq >= 0 ? wq : macs >= 4e9 ? 4 : 3) * mmvae_cu_count() / 4;
+    const int target = (G::WGQ > 0 ? (wqb > 0 ? wqb : G::WGQ) : wq >= 0 ? wq : macs >= 4e9 ? 4 : 3) * mmvae_cu_count() / 4;
     // (a batch costs a workgroup a fixed part -- the DMA issue -- next to its MFMAs: measured 0.66 us + 0.10 us per column tile
     //  on hallucinate.6; knob wr_bias = the fixed part in column tiles)
-    const int bias = mmvae_knob("wr_bias", 6);
+    const int bias = mmvae_knob(K_wr_bias);
     constexpr int NJ = G::PAIR ? G::NPAIR : G::NCLS;             // job classes: parity classes, or pairs of them
     auto wgt = [&](int i) {
         if (G::PAIR) return G::CPW(G::pair_a(i)) * G::WC + G::CPW(G::pair_b(i)) * G::WC + bias;
@@ -484,8 +484,8 @@ int try_wr(const WgradParams& p, hipStream_t stream, WgradSlabCtx* ctx) {
     int wsum = 0;
     for (int i = 0; i < NJ; ++i) wsum += wgt(i);
     WrArgs a{};
-    a.S = p.P; a.Bg = c.A; a.units = units; a.nimg = nimg; a.dbg = mmvae_knob("wr_dbg", 0);
-    a.ts = reinterpret_cast<unsigned long long*>(((unsigned long long)(unsigned)mmvae_knob("wr_ts_hi", 0) << 32) | (unsigned)mmvae_knob("wr_ts_lo", 0));
+    a.S = p.P; a.Bg = c.A; a.units = units; a.nimg = nimg; a.dbg = mmvae_knob(K_wr_dbg);
+    a.ts = mmvae_knob_ptr(K_wr_ts_lo, K_wr_ts_hi);
     size_t need = 0;
     int total = 0;
     int copies[WR_MAXCLS] = {};
@@ -510,18 +510,18 @@ int try_wr(const WgradParams& p, hipStream_t stream, WgradSlabCtx* ctx) {
             for (int g = 0; g < a.groups[i]; ++g)
                 for (int m = 0; m < G::MS; ++m) js.push_back(J{(int)((long long)units * g / a.groups[i]), (i << 12) | (g * G::MS + m)});
         std::stable_sort(js.begin(), js.end(), [](const J& x, const J& y) { return x.u0 < y.u0; });
-        const int run = std::max(1, mmvae_knob("wr_run", NJ * G::MS));
+        const int run = mmvae_knob(K_wr_run) > 0 ? mmvae_knob(K_wr_run) : NJ * G::MS;
         const int blk = 8 * run, full = total / blk * blk;
         for (int i = 0; i < total; ++i) {
             int b = i;
-            if (i < full && mmvae_knob("wr_xcd", 1)) b = i / blk * blk + (i % run) * 8 + (i / run) % 8;
+            if (i < full && mmvae_knob(K_wr_xcd)) b = i / blk * blk + (i % run) * 8 + (i / run) % 8;
             a.job[b] = (unsigned short)js[i].code;
         }
     }
     // small dW (features.2: 128 KB, hallucinate.6: 200 KB): the groups' accumulators go into the packed gradient by fp32 atomics
     // (a few MB of adds in all, spread over the kernel's tail) -- no partial copies, no reduce launch behind the kernel.  Not
     // bit-reproducible from run to run (the order of the adds), like every atomically accumulated bias / BatchNorm gradient here.
-    const bool atomic = (size_t)G::N * G::KH * G::KW * G::C * 4 <= (size_t)mmvae_knob("wr_atomic_kb", 256) * 1024;
+    const bool atomic = (size_t)G::N * G::KH * G::KW * G::C * 4 <= (size_t)mmvae_knob(K_wr_atomic_kb) * 1024;
     float* slab = atomic ? p.cls[0].dWp : ctx->take(need);
     if (!slab) return 0;
     a.slab = slab;
@@ -546,7 +546,7 @@ int try_wr(const WgradParams& p, hipStream_t stream, WgradSlabCtx* ctx) {
 }  // namespace
 
 int try_launch_wgrad_ring(const WgradParams& p, hipStream_t stream, WgradSlabCtx* ctx) {
-    if (!mmvae_knob("wgrad_ring", 1)) return 0;
+    if (!mmvae_knob(K_wgrad_ring)) return 0;
     if (p.c.a_bcast_n > 0 || p.c.a_mask || p.c.a_affine || p.c.a_act != ACT_NONE || p.p_affine || p.p_act != ACT_NONE) return 0;
     int rc;
 #define X(name, ...) if ((rc = try_wr<wrgeo::Geo<__VA_ARGS__>>(p, stream, ctx)) != 0) return rc;

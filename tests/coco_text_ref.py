@@ -415,7 +415,6 @@ def single_column_violations(run, P32, D, col, inp, keep, form, cache=None):
 
 # ------------------------------------------------------------------------------------------------ the cases of the GPU table
 # decoder form -> (knobs away from their defaults, emulation form at H + D <= 320, emulation form above)
-DEC_KNOB_DEFAULTS = dict(coco_cluster=8, coco_no_comb=0, coco_no_comb_bwd=0)
 DEC_FORM_KNOBS = {
     "wg1": (dict(coco_cluster=0), "three", "three"),              # one workgroup per 16-row block
     "cl4": (dict(coco_cluster=4), "three", "three"),              # cluster of 4

@@ -253,12 +253,6 @@ def describe_mismatch(got, ref, limit=6):
 
 
 # ------------------------------------------------------------------------------------------------ GPU harness
-# the library's defaults of the knobs the tests set, restored after every test: csrc/convres.hip try_launch_convres ("convres" 1,
-# "convres_alt" 0), csrc/wgrad_ring.hip try_launch_wgrad_ring ("wgrad_ring" 1), try_wr ("wr_pair" 0, "wr_atomic_kb" 256) -- a changed
-# default there must be changed here (and in tests/test_gpu_wgrad_ring.py)
-# (celeba_layer_mask / coco_layer_mask: csrc/celeba.hip celeba_bench_layer / csrc/coco.hip named_gemm, the keep masks of the replayed classifier layers)
-KNOB_DEFAULTS = {"convres": 1, "convres_alt": 0, "wgrad_ring": 1, "wr_atomic_kb": 256, "wr_pair": 0, "celeba_layer_mask": 0,
-                 "coco_layer_mask": 0}
 # (B, layer, knobs, [(tag, kernel)]) of every launch a harness of the family made in this process: what its coverage test reads
 RECORDS = []
 RECORDS_CELEBA = []
@@ -365,19 +359,14 @@ class LayerHarness:
         return gpk[m].reshape(shape).cpu(), float(gpk[others].abs().max())
 
     # ---- launch
-    def set_knobs(self, **kn):
-        for k, v in kn.items():
-            self.call("mmvae_debug_set", k.encode(), int(v))
-
-    def restore_knobs(self):
-        self.set_knobs(**KNOB_DEFAULTS)
-
     def run(self, layer, **knobs):
-        """one launch of the layer exactly as the step makes it; the kernels it ran are recorded (mmvae_debug_probe)"""
-        self.set_knobs(**knobs)
+        """one launch of the layer exactly as the step makes it, under the given library knobs (every other knob, and these behind
+        the launch, at the default of csrc/knobs.h); the kernels it ran are recorded (mmvae_debug_probe)"""
+        from multimodal_vae_amd._lib import knobs as lib_knobs
         self.call("mmvae_debug_probe", 1)
         try:
-            self.call("mmvae_%s_bench_layer" % self.prefix, self.eng.h, self.eng.ws.data_ptr(), self.eng.ws.numel(), layer.encode(), 1, self.sp)
+            with lib_knobs(**knobs):
+                self.call("mmvae_%s_bench_layer" % self.prefix, self.eng.h, self.eng.ws.data_ptr(), self.eng.ws.numel(), layer.encode(), 1, self.sp)
         finally:
             self.call("mmvae_debug_probe", 0)
         cap = 1 << 16

@@ -237,12 +237,6 @@ class _SimHarness:
         others = [v.abs().max() for n, v in self.grads.items() if n != pname and n not in also]
         return self.grads[pname].clone(), float(max(others)) if others else 0.0
 
-    def set_knobs(self, **kn):
-        pass
-
-    def restore_knobs(self):
-        pass
-
     def _operand(self, name, L, pix, ch):
         t = self.bufs[name].double()
         return t.reshape(-1, pix, pix, ch)

@@ -71,14 +71,11 @@ def test_forward_exact(B, name):
     h = _harness(B)
     L = LAYERS[name]
     ws, xs = [], []
-    try:
-        for seed in _seeds(B):
-            x, w, _ = LR.layer_operands(name, L.gf * B, seed, LAYERS)
-            LR.check_forward(h, L, name, x, w, CR_KNOBS, "%s B=%d seed %d" % (name, B, seed))
-            ws.append(w)
-            xs.append(x)
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        x, w, _ = LR.layer_operands(name, L.gf * B, seed, LAYERS)
+        LR.check_forward(h, L, name, x, w, CR_KNOBS, "%s B=%d seed %d" % (name, B, seed))
+        ws.append(w)
+        xs.append(x)
     if len(ws) == len(LR.SEEDS):
         LR.assert_operand_coverage(ws, xs)
 
@@ -100,14 +97,11 @@ def test_weight_packing_one_hot(B, name):
     L = LAYERS[name]
     nimg, c = L.gf * B, L.ih // 2
     w = _distinct_ints(LR.weight_shape(L))
-    try:
-        for (im, y, xx, ch) in ((0, 0, 0, 0), (nimg - 1, L.ih - 1, L.ih - 1, L.cin - 1), (0, c, c, L.cin - 1), (nimg - 1, c, c, 0),
-                                (nimg // 2, 0, L.ih - 1, L.cin // 2)):
-            x = torch.zeros(nimg, L.ih, L.ih, L.cin, dtype=torch.float64)
-            x[im, y, xx, ch] = 1.0
-            LR.check_forward(h, L, name, x, w, CR_KNOBS, "%s B=%d one-hot %s" % (name, B, (im, y, xx, ch)))
-    finally:
-        h.restore_knobs()
+    for (im, y, xx, ch) in ((0, 0, 0, 0), (nimg - 1, L.ih - 1, L.ih - 1, L.cin - 1), (0, c, c, L.cin - 1), (nimg - 1, c, c, 0),
+                            (nimg // 2, 0, L.ih - 1, L.cin // 2)):
+        x = torch.zeros(nimg, L.ih, L.ih, L.cin, dtype=torch.float64)
+        x[im, y, xx, ch] = 1.0
+        LR.check_forward(h, L, name, x, w, CR_KNOBS, "%s B=%d one-hot %s" % (name, B, (im, y, xx, ch)))
 
 
 @pytest.mark.parametrize("name", list(LAYERS))
@@ -115,14 +109,11 @@ def test_weight_packing_one_hot(B, name):
 def test_wgrad_exact(B, name):
     h = _harness(B)
     L = LAYERS[name]
-    try:
-        for seed in _seeds(B):
-            x, _, dy = LR.layer_operands(name, L.gb * B, seed, LAYERS)
-            h.put(L.x, x)
-            h.put(L.dy, dy)
-            LR.check_wgrad(h, name + "_wgrad", L.param, LR.ref_wgrad(L, x, dy), WG_KNOBS, "%s_wgrad B=%d seed %d" % (name, B, seed))
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        x, _, dy = LR.layer_operands(name, L.gb * B, seed, LAYERS)
+        h.put(L.x, x)
+        h.put(L.dy, dy)
+        LR.check_wgrad(h, name + "_wgrad", L.param, LR.ref_wgrad(L, x, dy), WG_KNOBS, "%s_wgrad B=%d seed %d" % (name, B, seed))
 
 
 def _patches(img):
@@ -140,38 +131,35 @@ def test_thin_layers_exact(B):
     gradient, the references the conv2d / conv_transpose2d of celeba/model.py:101,150 on that image."""
     h = _harness(B)
     f0, f9 = "image_encoder.features.0.weight", "image_decoder.hallucinate.9.weight"
-    try:
-        for seed in _seeds(B):
-            g = LR.gen(seed, 9, B)
-            img = LR.ternary((B, 3, 64, 64), 0.5, g)
-            w0 = LR.ternary((32, 3, 4, 4), 0.5, g)
-            d1 = LR.ternary((B, 32, 32, 32), 0.5, g)
-            h.put("patches1", _patches(img))
-            ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
-            LR.assert_exact_regime(out=ref, what="enc_conv1")
-            h.set_weight(f0, w0)
-            h.zero("r1", ref.numel(), torch.bfloat16)
-            h.zero("a1", ref.numel(), torch.bfloat16)
-            launches = h.run("enc_conv1")
-            got = h.get("r1", ref.shape).double().cpu()
-            assert torch.equal(got, ref), (B, seed, launches, LR.describe_mismatch(got, ref))
-            LR.gate_elements(h.get("a1", ref.shape), ref * torch.sigmoid(ref), ref, "enc_conv1 a1 B=%d seed %d" % (B, seed))
-            wz = torch.zeros(32, 3, 4, 4, dtype=torch.float64, requires_grad=True)
-            F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
-            h.put("d1e", d1)
-            # (the K = 48 im2col ends and the two Linears below match no ring geometry -- csrc/wgrad_ring_geos.h, and a_bcast_n keeps
-            #  fc1 out of try_launch_wgrad_ring -- so the partial-copies knob set would repeat the same launch: ring off / on only)
-            LR.check_wgrad(h, "enc_conv1_wgrad", f0, wz.grad, WG_KNOBS[:2], "enc_conv1_wgrad B=%d seed %d" % (B, seed))
-            # last transposed conv (32 -> 3 channels): dW from its activated input aq3 and im2col(dlogit), 3 passes
-            dl = LR.ternary((3 * B, 3, 64, 64), 0.25, g)
-            a3 = LR.ternary((3 * B, 32, 32, 32), 0.25, g)
-            w9 = torch.zeros(32, 3, 4, 4, dtype=torch.float64, requires_grad=True)
-            F.conv_transpose2d(LR._nchw(a3), w9, None, 2, 1).backward(dl)
-            h.put("patches4", _patches(dl))
-            h.put("aq3", a3)
-            LR.check_wgrad(h, "dec_last_wgrad", f9, w9.grad, WG_KNOBS[:2], "dec_last_wgrad B=%d seed %d" % (B, seed))
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        g = LR.gen(seed, 9, B)
+        img = LR.ternary((B, 3, 64, 64), 0.5, g)
+        w0 = LR.ternary((32, 3, 4, 4), 0.5, g)
+        d1 = LR.ternary((B, 32, 32, 32), 0.5, g)
+        h.put("patches1", _patches(img))
+        ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
+        LR.assert_exact_regime(out=ref, what="enc_conv1")
+        h.set_weight(f0, w0)
+        h.zero("r1", ref.numel(), torch.bfloat16)
+        h.zero("a1", ref.numel(), torch.bfloat16)
+        launches = h.run("enc_conv1")
+        got = h.get("r1", ref.shape).double().cpu()
+        assert torch.equal(got, ref), (B, seed, launches, LR.describe_mismatch(got, ref))
+        LR.gate_elements(h.get("a1", ref.shape), ref * torch.sigmoid(ref), ref, "enc_conv1 a1 B=%d seed %d" % (B, seed))
+        wz = torch.zeros(32, 3, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
+        h.put("d1e", d1)
+        # (the K = 48 im2col ends and the two Linears below match no ring geometry -- csrc/wgrad_ring_geos.h, and a_bcast_n keeps
+        #  fc1 out of try_launch_wgrad_ring -- so the partial-copies knob set would repeat the same launch: ring off / on only)
+        LR.check_wgrad(h, "enc_conv1_wgrad", f0, wz.grad, WG_KNOBS[:2], "enc_conv1_wgrad B=%d seed %d" % (B, seed))
+        # last transposed conv (32 -> 3 channels): dW from its activated input aq3 and im2col(dlogit), 3 passes
+        dl = LR.ternary((3 * B, 3, 64, 64), 0.25, g)
+        a3 = LR.ternary((3 * B, 32, 32, 32), 0.25, g)
+        w9 = torch.zeros(32, 3, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv_transpose2d(LR._nchw(a3), w9, None, 2, 1).backward(dl)
+        h.put("patches4", _patches(dl))
+        h.put("aq3", a3)
+        LR.check_wgrad(h, "dec_last_wgrad", f9, w9.grad, WG_KNOBS[:2], "dec_last_wgrad B=%d seed %d" % (B, seed))
 
 
 # ------------------------------------------------------------------------------------------------ Tier B: data gradients
@@ -180,13 +168,10 @@ def test_thin_layers_exact(B):
 def test_dgrad_epilogue(B, name):
     h = _harness(B)
     L = LAYERS[name]
-    try:
-        for seed in _seeds(B):
-            _, w, dy = LR.layer_operands(name, L.gb * B, seed, LAYERS)
-            g = LR.gen(seed, list(LAYERS).index(name), 4, L.gb * B)
-            LR.check_dgrad(h, L, name, dy, w, g, CR_KNOBS, "%s_dgrad B=%d seed %d" % (name, B, seed))
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        _, w, dy = LR.layer_operands(name, L.gb * B, seed, LAYERS)
+        g = LR.gen(seed, list(LAYERS).index(name), 4, L.gb * B)
+        LR.check_dgrad(h, L, name, dy, w, g, CR_KNOBS, "%s_dgrad B=%d seed %d" % (name, B, seed))
 
 
 @pytest.mark.parametrize("B", BATCHES)
@@ -194,30 +179,27 @@ def test_last_layer_dgrad(B):
     """dec_last_dgrad_gemm: the input gradient of the 32 -> 3 channel transposed conv (celeba/model.py:150) as a dense K = 48 GEMM
     over im2col(dlogit), with the Swish' / BatchNorm-backward epilogue of hallucinate.7, 3 passes."""
     h = _harness(B)
-    try:
-        for seed in _seeds(B):
-            g = LR.gen(seed, 12, B)
-            dl = LR.ternary((3 * B, 3, 64, 64), 0.5, g)
-            w9 = LR.ternary((32, 3, 4, 4), 0.5, g)
-            x = torch.zeros(3 * B, 32, 32, 32, dtype=torch.float64, requires_grad=True)
-            F.conv_transpose2d(x, w9, None, 2, 1).backward(dl)
-            acc = LR._nhwc(x.grad)
-            r = LR.eighths(acc.shape, g)
-            aff, mr = LR.dyadic_tables(3, 32, g)
-            v, red, red_abs = LR.ref_dgrad_epilogue(acc, r, aff, mr, 3)
-            h.set_weight("image_decoder.hallucinate.9.weight", w9)
-            h.put("patches4", _patches(dl))
-            h.put("q3", r)
-            h.put("aff_d2", aff, torch.float32)
-            h.put("mr_d2", mr, torch.float32)
-            h.zero("d3", acc.numel(), torch.bfloat16)
-            h.zero("red_d2", 3 * LR.STAT_SLOTS * 32 * 2, torch.float32)
-            launches = h.run("dec_last_dgrad_gemm")
-            what = "dec_last_dgrad_gemm B=%d seed %d" % (B, seed)
-            LR.gate_elements(h.get("d3", acc.shape), v, acc, what, launches)
-            LR.gate_sums(h.stats("red_d2", 3, 32), red, red_abs, what + " d_red", launches)
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        g = LR.gen(seed, 12, B)
+        dl = LR.ternary((3 * B, 3, 64, 64), 0.5, g)
+        w9 = LR.ternary((32, 3, 4, 4), 0.5, g)
+        x = torch.zeros(3 * B, 32, 32, 32, dtype=torch.float64, requires_grad=True)
+        F.conv_transpose2d(x, w9, None, 2, 1).backward(dl)
+        acc = LR._nhwc(x.grad)
+        r = LR.eighths(acc.shape, g)
+        aff, mr = LR.dyadic_tables(3, 32, g)
+        v, red, red_abs = LR.ref_dgrad_epilogue(acc, r, aff, mr, 3)
+        h.set_weight("image_decoder.hallucinate.9.weight", w9)
+        h.put("patches4", _patches(dl))
+        h.put("q3", r)
+        h.put("aff_d2", aff, torch.float32)
+        h.put("mr_d2", mr, torch.float32)
+        h.zero("d3", acc.numel(), torch.bfloat16)
+        h.zero("red_d2", 3 * LR.STAT_SLOTS * 32 * 2, torch.float32)
+        launches = h.run("dec_last_dgrad_gemm")
+        what = "dec_last_dgrad_gemm B=%d seed %d" % (B, seed)
+        LR.gate_elements(h.get("d3", acc.shape), v, acc, what, launches)
+        LR.gate_sums(h.stats("red_d2", 3, 32), red, red_abs, what + " d_red", launches)
 
 
 # ------------------------------------------------------------------------------------------------ the two permuted Linears
@@ -256,89 +238,84 @@ def test_dense_layers(B):
     through Swish' take the per-element gate, the BatchNorm-backward / bias sums the 2^-16 gate.  The keep mask is the test's."""
     h = _harness(B)
     rows = 2 * B
-    try:
-        for seed in _seeds(B):
-            g = LR.gen(seed, 11, B)
-            tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
-            ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
-            W1, W3, Wu = tern((HID, FEAT), 0.25), tern((2 * D, HID), 0.25), tern((FEAT, D), 0.25)
-            b1, bu = ibias(HID), ibias(FEAT)
-            for n, t in ((C0 + "weight", W1), (C0 + "bias", b1), (C3 + "weight", W3), (UP + "weight", Wu), (UP + "bias", bu)):
-                h.set_weight(n, t)
-            m1 = (torch.rand((rows, HID), generator=g) < 0.9).to(torch.uint8)
-            h.put("m1", m1, torch.uint8)
-            tag = "B=%d seed %d" % (B, seed)
+    for seed in _seeds(B):
+        g = LR.gen(seed, 11, B)
+        tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
+        ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
+        W1, W3, Wu = tern((HID, FEAT), 0.25), tern((2 * D, HID), 0.25), tern((FEAT, D), 0.25)
+        b1, bu = ibias(HID), ibias(FEAT)
+        for n, t in ((C0 + "weight", W1), (C0 + "bias", b1), (C3 + "weight", W3), (UP + "weight", Wu), (UP + "bias", bu)):
+            h.set_weight(n, t)
+        m1 = (torch.rand((rows, HID), generator=g) < 0.9).to(torch.uint8)
+        h.put("m1", m1, torch.uint8)
+        tag = "B=%d seed %d" % (B, seed)
 
-            # ---- classifier.0 forward: row r of the 2B rows reads image r % B
-            a4 = tern((B, 5, 5, 256), 0.25)
-            h.put("a4", a4)
-            x1 = _flat_nchw(a4).repeat(2, 1)
-            y1 = F.linear(x1, W1, b1)
-            for mask in (0, 1):
-                h.zero("y1", rows * HID, torch.bfloat16)
-                h.zero("ay1", rows * HID, torch.bfloat16)
-                h.run("fc1", celeba_layer_mask=mask)
-                LR.check_exact(h.get("y1", (rows, HID)), y1, "fc1 y1 mask %d %s" % (mask, tag))
-                LR.gate_elements(h.get("ay1", (rows, HID)), _swish(y1) * (m1 * DROP_SCALE if mask else 1.0), y1, "fc1 ay1 mask %d %s" % (mask, tag))
-            h.set_knobs(celeba_layer_mask=0)
+        # ---- classifier.0 forward: row r of the 2B rows reads image r % B
+        a4 = tern((B, 5, 5, 256), 0.25)
+        h.put("a4", a4)
+        x1 = _flat_nchw(a4).repeat(2, 1)
+        y1 = F.linear(x1, W1, b1)
+        for mask in (0, 1):
+            h.zero("y1", rows * HID, torch.bfloat16)
+            h.zero("ay1", rows * HID, torch.bfloat16)
+            h.run("fc1", celeba_layer_mask=mask)
+            LR.check_exact(h.get("y1", (rows, HID)), y1, "fc1 y1 mask %d %s" % (mask, tag))
+            LR.gate_elements(h.get("ay1", (rows, HID)), _swish(y1) * (m1 * DROP_SCALE if mask else 1.0), y1, "fc1 ay1 mask %d %s" % (mask, tag))
 
-            # ---- classifier.3 data gradient: dy1 = (d_encout W3) * Swish'(y1) [* keep / 0.9], column sums = classifier.0's bias gradient
-            de, r1 = tern((rows, 2 * D)), LR.eighths((rows, HID), g)
-            h.put("d_encout", de)
-            h.put("y1", r1)
-            acc = de @ W3
-            for mask in (0, 1):
-                v = acc * LR.dswish(r1) * (m1 * DROP_SCALE if mask else 1.0)
-                h.zero("dy1", rows * HID, torch.bfloat16)
-                h.st.grads.zero_()              # d_colsum adds into the flat gradients at classifier.0.bias, as in the step
-                h.run("fc2_dgrad", celeba_layer_mask=mask)
-                LR.gate_elements(h.get("dy1", (rows, HID)), v, acc, "fc2_dgrad mask %d %s" % (mask, tag))
-                boff, _, _ = h.param_range(C0 + "bias")
-                LR.gate_sums(h.st.grads[boff:boff + HID], v.sum(0), v.abs().sum(0), "fc2_dgrad d_colsum mask %d %s" % (mask, tag))
-                others = h.st.grads.clone()
-                others[boff:boff + HID] = 0
-                assert float(others.abs().max()) == 0.0, "fc2_dgrad wrote a gradient other than classifier.0.bias"
-            h.set_knobs(celeba_layer_mask=0)
+        # ---- classifier.3 data gradient: dy1 = (d_encout W3) * Swish'(y1) [* keep / 0.9], column sums = classifier.0's bias gradient
+        de, r1 = tern((rows, 2 * D)), LR.eighths((rows, HID), g)
+        h.put("d_encout", de)
+        h.put("y1", r1)
+        acc = de @ W3
+        for mask in (0, 1):
+            v = acc * LR.dswish(r1) * (m1 * DROP_SCALE if mask else 1.0)
+            h.zero("dy1", rows * HID, torch.bfloat16)
+            h.st.grads.zero_()              # d_colsum adds into the flat gradients at classifier.0.bias, as in the step
+            h.run("fc2_dgrad", celeba_layer_mask=mask)
+            LR.gate_elements(h.get("dy1", (rows, HID)), v, acc, "fc2_dgrad mask %d %s" % (mask, tag))
+            boff, _, _ = h.param_range(C0 + "bias")
+            LR.gate_sums(h.st.grads[boff:boff + HID], v.sum(0), v.abs().sum(0), "fc2_dgrad d_colsum mask %d %s" % (mask, tag))
+            others = h.st.grads.clone()
+            others[boff:boff + HID] = 0
+            assert float(others.abs().max()) == 0.0, "fc2_dgrad wrote a gradient other than classifier.0.bias"
 
-            # ---- classifier.0 gradients.  dy1 dense, and with the zeros a keep mask upstream leaves in it (the step with dropout)
-            for masked in (0, 1):
-                dy1 = tern((rows, HID)) * (m1.double() if masked else 1.0)
-                h.put("dy1", dy1)
-                wz = torch.zeros(HID, FEAT, dtype=torch.float64, requires_grad=True)
-                F.linear(x1, wz).backward(dy1)
-                LR.check_wgrad(h, "fc1_wgrad", C0 + "weight", wz.grad, WG_KNOBS[:1], "fc1_wgrad masked %d %s" % (masked, tag))
-                # db4[n][s * 256 + c] = (dy1 W1)[n][c * 25 + s] * Swish'(scale_c * r4[n % B] + shift_c); sums per channel c = column % 256
-                acc = _map_nhwc(dy1 @ W1)
-                r4 = LR.eighths((B, 5, 5, 256), g)
-                aff, mr = LR.dyadic_tables(1, 256, g)
-                v, red, red_abs = LR.ref_dgrad_epilogue(acc, r4.repeat(2, 1, 1, 1), aff, mr, 1)
-                h.put("r4", r4)
-                h.put("aff_e2", aff, torch.float32)
-                h.put("mr_e2", mr, torch.float32)
-                h.zero("db4", rows * FEAT, torch.bfloat16)
-                h.zero("red_e2", LR.STAT_SLOTS * 256 * 2, torch.float32)
-                launches = h.run("fc1_dgrad")
-                LR.gate_elements(h.get("db4", acc.shape), v, acc, "fc1_dgrad masked %d %s" % (masked, tag), launches)
-                LR.gate_sums(h.stats("red_e2", 1, 256), red, red_abs, "fc1_dgrad d_red masked %d %s" % (masked, tag), launches)
+        # ---- classifier.0 gradients.  dy1 dense, and with the zeros a keep mask upstream leaves in it (the step with dropout)
+        for masked in (0, 1):
+            dy1 = tern((rows, HID)) * (m1.double() if masked else 1.0)
+            h.put("dy1", dy1)
+            wz = torch.zeros(HID, FEAT, dtype=torch.float64, requires_grad=True)
+            F.linear(x1, wz).backward(dy1)
+            LR.check_wgrad(h, "fc1_wgrad", C0 + "weight", wz.grad, WG_KNOBS[:1], "fc1_wgrad masked %d %s" % (masked, tag))
+            # db4[n][s * 256 + c] = (dy1 W1)[n][c * 25 + s] * Swish'(scale_c * r4[n % B] + shift_c); sums per channel c = column % 256
+            acc = _map_nhwc(dy1 @ W1)
+            r4 = LR.eighths((B, 5, 5, 256), g)
+            aff, mr = LR.dyadic_tables(1, 256, g)
+            v, red, red_abs = LR.ref_dgrad_epilogue(acc, r4.repeat(2, 1, 1, 1), aff, mr, 1)
+            h.put("r4", r4)
+            h.put("aff_e2", aff, torch.float32)
+            h.put("mr_e2", mr, torch.float32)
+            h.zero("db4", rows * FEAT, torch.bfloat16)
+            h.zero("red_e2", LR.STAT_SLOTS * 256 * 2, torch.float32)
+            launches = h.run("fc1_dgrad")
+            LR.gate_elements(h.get("db4", acc.shape), v, acc, "fc1_dgrad masked %d %s" % (masked, tag), launches)
+            LR.gate_sums(h.stats("red_e2", 1, 256), red, red_abs, "fc1_dgrad d_red masked %d %s" % (masked, tag), launches)
 
-            # ---- upsample.0: forward, weight + folded bias gradient, dz
-            z = tern((3 * B, D))
-            h.put("z_bf", _z_rows(z))
-            u = _map_nhwc(F.linear(z, Wu, bu)).reshape(3 * B, FEAT)
-            h.zero("u", 3 * B * FEAT, torch.bfloat16)
-            h.zero("au", 3 * B * FEAT, torch.bfloat16)
-            h.run("up")
-            LR.check_exact(h.get("u", (3 * B, FEAT)), u, "up u " + tag)
-            LR.gate_elements(h.get("au", (3 * B, FEAT)), _swish(u), u, "up au " + tag)
-            du = tern((3 * B, 5, 5, 256), 0.25)
-            h.put("du", du)
-            duf = _flat_nchw(du)
-            LR.check_wgrad(h, "up_wgrad", UP + "weight", duf.t() @ z, WG_KNOBS[:1], "up_wgrad " + tag, also={UP + "bias": duf.sum(0)})
-            h.zero("dz_img", 3 * B * D, torch.float32)
-            h.run("up_dgrad")
-            LR.check_exact(h.get("dz_img", (3 * B, D), torch.float32), duf @ Wu, "up_dgrad " + tag, limit=2 ** 24)
-    finally:
-        h.restore_knobs()
+        # ---- upsample.0: forward, weight + folded bias gradient, dz
+        z = tern((3 * B, D))
+        h.put("z_bf", _z_rows(z))
+        u = _map_nhwc(F.linear(z, Wu, bu)).reshape(3 * B, FEAT)
+        h.zero("u", 3 * B * FEAT, torch.bfloat16)
+        h.zero("au", 3 * B * FEAT, torch.bfloat16)
+        h.run("up")
+        LR.check_exact(h.get("u", (3 * B, FEAT)), u, "up u " + tag)
+        LR.gate_elements(h.get("au", (3 * B, FEAT)), _swish(u), u, "up au " + tag)
+        du = tern((3 * B, 5, 5, 256), 0.25)
+        h.put("du", du)
+        duf = _flat_nchw(du)
+        LR.check_wgrad(h, "up_wgrad", UP + "weight", duf.t() @ z, WG_KNOBS[:1], "up_wgrad " + tag, also={UP + "bias": duf.sum(0)})
+        h.zero("dz_img", 3 * B * D, torch.float32)
+        h.run("up_dgrad")
+        LR.check_exact(h.get("dz_img", (3 * B, D), torch.float32), duf @ Wu, "up_dgrad " + tag, limit=2 ** 24)
 
 
 @pytest.mark.parametrize("B", [3, 8])
@@ -353,35 +330,32 @@ def test_dense_packing_one_hot(B):
     W1, Wu = _distinct_ints((HID, FEAT)), _distinct_ints((FEAT, D))
     b1 = (torch.arange(HID) % 5 - 2).double()
     bu = (torch.arange(FEAT) % 7 - 3).double()
-    try:
-        for n, t in ((C0 + "weight", W1), (C0 + "bias", b1), (UP + "weight", Wu), (UP + "bias", bu)):
-            h.set_weight(n, t)
-        for (n, y, x, c) in ((0, 0, 0, 0), (B - 1, 4, 4, 255), (B // 2, 1, 3, 128), (0, 4, 0, 7), (B - 1, 2, 2, 1)):
-            a4 = torch.zeros(B, 5, 5, 256, dtype=torch.float64)
-            a4[n, y, x, c] = 1.0
-            want = b1.repeat(rows, 1)
-            want[n] += W1[:, c * 25 + y * 5 + x]
-            want[n + B] += W1[:, c * 25 + y * 5 + x]
-            assert torch.equal(want, F.linear(_flat_nchw(a4).repeat(2, 1), W1, b1))
-            h.put("a4", a4)
-            h.zero("y1", rows * HID, torch.bfloat16)
-            h.run("fc1")
-            LR.check_exact(h.get("y1", (rows, HID)), want, "fc1 one-hot %s B=%d" % ((n, y, x, c), B))
-        for (row, k) in ((0, 0), (3 * B - 1, D - 1), (B, 37), (2 * B - 1, 64)):
-            z = torch.zeros(3 * B, D, dtype=torch.float64)
-            z[row, k] = 1.0
-            want = bu.repeat(3 * B, 1)
-            want[row] += Wu[:, k]
-            assert torch.equal(want, F.linear(z, Wu, bu))
-            want = _map_nhwc(want).reshape(3 * B, FEAT)
-            s, c = 13, 200
-            assert float(want[row, s * 256 + c]) == float(Wu[c * 25 + s, k] + bu[c * 25 + s])
-            h.put("z_bf", _z_rows(z))
-            h.zero("u", 3 * B * FEAT, torch.bfloat16)
-            h.run("up")
-            LR.check_exact(h.get("u", (3 * B, FEAT)), want, "up one-hot %s B=%d" % ((row, k), B))
-    finally:
-        h.restore_knobs()
+    for n, t in ((C0 + "weight", W1), (C0 + "bias", b1), (UP + "weight", Wu), (UP + "bias", bu)):
+        h.set_weight(n, t)
+    for (n, y, x, c) in ((0, 0, 0, 0), (B - 1, 4, 4, 255), (B // 2, 1, 3, 128), (0, 4, 0, 7), (B - 1, 2, 2, 1)):
+        a4 = torch.zeros(B, 5, 5, 256, dtype=torch.float64)
+        a4[n, y, x, c] = 1.0
+        want = b1.repeat(rows, 1)
+        want[n] += W1[:, c * 25 + y * 5 + x]
+        want[n + B] += W1[:, c * 25 + y * 5 + x]
+        assert torch.equal(want, F.linear(_flat_nchw(a4).repeat(2, 1), W1, b1))
+        h.put("a4", a4)
+        h.zero("y1", rows * HID, torch.bfloat16)
+        h.run("fc1")
+        LR.check_exact(h.get("y1", (rows, HID)), want, "fc1 one-hot %s B=%d" % ((n, y, x, c), B))
+    for (row, k) in ((0, 0), (3 * B - 1, D - 1), (B, 37), (2 * B - 1, 64)):
+        z = torch.zeros(3 * B, D, dtype=torch.float64)
+        z[row, k] = 1.0
+        want = bu.repeat(3 * B, 1)
+        want[row] += Wu[:, k]
+        assert torch.equal(want, F.linear(z, Wu, bu))
+        want = _map_nhwc(want).reshape(3 * B, FEAT)
+        s, c = 13, 200
+        assert float(want[row, s * 256 + c]) == float(Wu[c * 25 + s, k] + bu[c * 25 + s])
+        h.put("z_bf", _z_rows(z))
+        h.zero("u", 3 * B * FEAT, torch.bfloat16)
+        h.run("up")
+        LR.check_exact(h.get("u", (3 * B, FEAT)), want, "up one-hot %s B=%d" % ((row, k), B))
 
 
 # ------------------------------------------------------------------------------------------------ which kernels ran

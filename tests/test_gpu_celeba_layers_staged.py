@@ -79,44 +79,41 @@ def test_staged_forward(B, name):
     stats = LR.slot_stats(r, G)
     st_name = L.red.replace("red", "st")
     what = "%s_staged B=%d" % (name, B)
-    try:
-        h.set_weight(L.param, w)
-        h.set_weight(bn + ".weight", gamma)
-        h.set_weight(bn + ".bias", beta)
-        h.put(L.r, r)
-        h.put(st_name, stats, torch.float32)
-        for nm, n, dt in ((L.x, r.numel(), torch.bfloat16), (L.aff, G * L.cin * 2, torch.float32), (L.mr, G * L.cin * 2, torch.float32),
-                          (L.out, nimg * L.oh * L.oh * L.cout, torch.bfloat16), (L.stats, G * LR.STAT_SLOTS * L.cout * 2, torch.float32)):
-            h.zero(nm, n, dt)
-        launches = h.run(name + "_staged")
-        _tagged(launches, 1, False)
-        # (a) tables and by-product
-        scale, shift, mean, rstd = LR.ref_bn_tables(stats, count, gamma, beta)
-        aff = h.get(L.aff, (G, L.cin, 2), torch.float32)
-        mr = h.get(L.mr, (G, L.cin, 2), torch.float32)
-        # fp32 roundings of csrc/bn_dev.h bn_channel_tables, each relative to the magnitude it is gated with:
-        #   mean  : 15 additions of the 16 slot sums (partial sums bounded by count * max |r| = 4 count) + the division = 16, of 4
-        #   rstd  : 15 additions (all terms positive) + division of the sum of squares, mean^2, the subtraction (mean^2 << variance
-        #           for these operands: no cancellation), + eps, rsqrt = 20 roundings of the variance, halved by the -1/2 power = 10,
-        #           and rsqrt's own = 11 of rstd
-        #   scale : rstd's 11 + the product with gamma = 12 of |scale|
-        #   shift : mean's 16 (of 4 |scale|) + scale's 12 + the product (of |mean scale|) + the subtraction (of |shift| <= |beta| +
-        #           |mean scale|): at most 16 of (4 + |mean|) |scale| + |beta|
-        e = LR.EPS32
-        _within(aff[..., 0], scale, 12 * e * scale.abs(), what + " scale", launches)
-        _within(aff[..., 1], shift, 16 * e * ((mean.abs() + 4) * scale.abs() + beta.abs()[None]), what + " shift", launches)
-        _within(mr[..., 0], mean, 16 * e * 4 * torch.ones_like(mean), what + " mean", launches)
-        _within(mr[..., 1], rstd, 11 * e * rstd, what + " rstd", launches)
-        a_ref, _ = LR.ref_stage_fwd(r, scale, shift, G)
-        a_got = h.get(L.x, r.shape)
-        _within(a_got, a_ref, LR.gate_stage_fwd(r, scale, shift, mean, beta, a_ref, G), what + " by-product", launches)
-        # (b) the conv of what was staged
-        a_rb = a_got.double().cpu()
-        ref, absterms = LR.ref_forward(L, a_rb, w), LR.ref_abs_terms(L, a_rb, w)
-        _within(h.get(L.out, ref.shape), ref, LR.gate_stage_conv(L, ref, absterms), what + " output", launches)
-        _within(h.stats(L.stats, G, L.cout), LR.ref_colstats(ref, G), LR.gate_stage_colstats(L, ref, absterms, G), what + " colstats", launches)
-    finally:
-        h.restore_knobs()
+    h.set_weight(L.param, w)
+    h.set_weight(bn + ".weight", gamma)
+    h.set_weight(bn + ".bias", beta)
+    h.put(L.r, r)
+    h.put(st_name, stats, torch.float32)
+    for nm, n, dt in ((L.x, r.numel(), torch.bfloat16), (L.aff, G * L.cin * 2, torch.float32), (L.mr, G * L.cin * 2, torch.float32),
+                      (L.out, nimg * L.oh * L.oh * L.cout, torch.bfloat16), (L.stats, G * LR.STAT_SLOTS * L.cout * 2, torch.float32)):
+        h.zero(nm, n, dt)
+    launches = h.run(name + "_staged")
+    _tagged(launches, 1, False)
+    # (a) tables and by-product
+    scale, shift, mean, rstd = LR.ref_bn_tables(stats, count, gamma, beta)
+    aff = h.get(L.aff, (G, L.cin, 2), torch.float32)
+    mr = h.get(L.mr, (G, L.cin, 2), torch.float32)
+    # fp32 roundings of csrc/bn_dev.h bn_channel_tables, each relative to the magnitude it is gated with:
+    #   mean  : 15 additions of the 16 slot sums (partial sums bounded by count * max |r| = 4 count) + the division = 16, of 4
+    #   rstd  : 15 additions (all terms positive) + division of the sum of squares, mean^2, the subtraction (mean^2 << variance
+    #           for these operands: no cancellation), + eps, rsqrt = 20 roundings of the variance, halved by the -1/2 power = 10,
+    #           and rsqrt's own = 11 of rstd
+    #   scale : rstd's 11 + the product with gamma = 12 of |scale|
+    #   shift : mean's 16 (of 4 |scale|) + scale's 12 + the product (of |mean scale|) + the subtraction (of |shift| <= |beta| +
+    #           |mean scale|): at most 16 of (4 + |mean|) |scale| + |beta|
+    e = LR.EPS32
+    _within(aff[..., 0], scale, 12 * e * scale.abs(), what + " scale", launches)
+    _within(aff[..., 1], shift, 16 * e * ((mean.abs() + 4) * scale.abs() + beta.abs()[None]), what + " shift", launches)
+    _within(mr[..., 0], mean, 16 * e * 4 * torch.ones_like(mean), what + " mean", launches)
+    _within(mr[..., 1], rstd, 11 * e * rstd, what + " rstd", launches)
+    a_ref, _ = LR.ref_stage_fwd(r, scale, shift, G)
+    a_got = h.get(L.x, r.shape)
+    _within(a_got, a_ref, LR.gate_stage_fwd(r, scale, shift, mean, beta, a_ref, G), what + " by-product", launches)
+    # (b) the conv of what was staged
+    a_rb = a_got.double().cpu()
+    ref, absterms = LR.ref_forward(L, a_rb, w), LR.ref_abs_terms(L, a_rb, w)
+    _within(h.get(L.out, ref.shape), ref, LR.gate_stage_conv(L, ref, absterms), what + " output", launches)
+    _within(h.stats(L.stats, G, L.cout), LR.ref_colstats(ref, G), LR.gate_stage_colstats(L, ref, absterms, G), what + " colstats", launches)
 
 
 @pytest.mark.parametrize("name", ["enc_conv3", "enc_conv2", "dec_convT3", "dec_convT2"])
@@ -135,39 +132,36 @@ def test_staged_dgrad(B, name):
     what = "%s_dgrad_staged B=%d" % (name, B)
     goff, _, _ = h.param_range(bn + ".weight")
     boff, _, _ = h.param_range(bn + ".bias")
-    try:
-        h.set_weight(L.param, w)
-        h.set_weight(bn + ".weight", gamma)
-        h.put(L.dy, db)
-        h.put(L.out, r)                 # the layer's own raw output: the tensor its BatchNorm normalised (stage_bwd_*: tr.r)
-        h.put(own_red, red, torch.float32)
-        h.put(own_mr, mr, torch.float32)
-        # epilogue of the layer below (Swish' and its BatchNorm-backward sums), as in the plain data-gradient test
-        r_in = LR.eighths((nimg, L.ih, L.ih, L.cin), g)
-        aff_in, mr_in = LR.dyadic_tables(G, L.cin, g) if L.aff else (None, None)
-        h.put(L.r, r_in)
-        if L.aff:
-            h.put(L.aff, aff_in, torch.float32)
-            h.put(L.mr, mr_in, torch.float32)
-            h.zero(L.red, G * LR.STAT_SLOTS * L.cin * 2, torch.float32)
-        h.zero(L.dx, nimg * L.ih * L.ih * L.cin, torch.bfloat16)
-        h.st.grads.zero_()
-        launches = h.run(name + "_dgrad_staged")
-        _tagged(launches, 2, True)
-        # in-place dr, dgamma / dbeta
-        dr_got = h.get(L.dy, dr.shape)
-        _within(dr_got, dr, 2.0 ** -8 * dr.abs(), what + " dr", launches)
-        C = L.cout
-        LR.gate_sums(h.st.grads[goff:goff + C], dgamma, mag_g, what + " dgamma", launches)
-        LR.gate_sums(h.st.grads[boff:boff + C], dbeta, mag_b, what + " dbeta", launches)
-        # data gradient of what was stored
-        dr_rb = dr_got.double().cpu()
-        acc = LR.ref_dgrad_acc(L, dr_rb, w)
-        assert bool((acc * 256 == (acc * 256).round()).all()) and float(acc.abs().max()) * 256 < 2 ** 24, what
-        v, red_in, red_abs = LR.ref_dgrad_epilogue(acc, r_in, aff_in, mr_in, G)
-        LR.gate_elements(h.get(L.dx, acc.shape), v, acc, what + " data gradient", launches)
-        if L.red:
-            LR.gate_sums(h.stats(L.red, G, L.cin), red_in, red_abs, what + " d_red", launches)
-    finally:
-        h.restore_knobs()
+    h.set_weight(L.param, w)
+    h.set_weight(bn + ".weight", gamma)
+    h.put(L.dy, db)
+    h.put(L.out, r)                 # the layer's own raw output: the tensor its BatchNorm normalised (stage_bwd_*: tr.r)
+    h.put(own_red, red, torch.float32)
+    h.put(own_mr, mr, torch.float32)
+    # epilogue of the layer below (Swish' and its BatchNorm-backward sums), as in the plain data-gradient test
+    r_in = LR.eighths((nimg, L.ih, L.ih, L.cin), g)
+    aff_in, mr_in = LR.dyadic_tables(G, L.cin, g) if L.aff else (None, None)
+    h.put(L.r, r_in)
+    if L.aff:
+        h.put(L.aff, aff_in, torch.float32)
+        h.put(L.mr, mr_in, torch.float32)
+        h.zero(L.red, G * LR.STAT_SLOTS * L.cin * 2, torch.float32)
+    h.zero(L.dx, nimg * L.ih * L.ih * L.cin, torch.bfloat16)
+    h.st.grads.zero_()
+    launches = h.run(name + "_dgrad_staged")
+    _tagged(launches, 2, True)
+    # in-place dr, dgamma / dbeta
+    dr_got = h.get(L.dy, dr.shape)
+    _within(dr_got, dr, 2.0 ** -8 * dr.abs(), what + " dr", launches)
+    C = L.cout
+    LR.gate_sums(h.st.grads[goff:goff + C], dgamma, mag_g, what + " dgamma", launches)
+    LR.gate_sums(h.st.grads[boff:boff + C], dbeta, mag_b, what + " dbeta", launches)
+    # data gradient of what was stored
+    dr_rb = dr_got.double().cpu()
+    acc = LR.ref_dgrad_acc(L, dr_rb, w)
+    assert bool((acc * 256 == (acc * 256).round()).all()) and float(acc.abs().max()) * 256 < 2 ** 24, what
+    v, red_in, red_abs = LR.ref_dgrad_epilogue(acc, r_in, aff_in, mr_in, G)
+    LR.gate_elements(h.get(L.dx, acc.shape), v, acc, what + " data gradient", launches)
+    if L.red:
+        LR.gate_sums(h.stats(L.red, G, L.cin), red_in, red_abs, what + " d_red", launches)
 

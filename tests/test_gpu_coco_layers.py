@@ -107,14 +107,11 @@ def test_forward_exact(B, name):
     h = _harness(B)
     L = LAYERS[name]
     ws, xs = [], []
-    try:
-        for seed in _seeds(B):
-            x, w, _ = LR.layer_operands(name, L.gf * B, seed, LAYERS)
-            LR.check_forward(h, L, name, x, w, CR_KNOBS, "%s B=%d seed %d" % (name, B, seed))
-            ws.append(w)
-            xs.append(x)
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        x, w, _ = LR.layer_operands(name, L.gf * B, seed, LAYERS)
+        LR.check_forward(h, L, name, x, w, CR_KNOBS, "%s B=%d seed %d" % (name, B, seed))
+        ws.append(w)
+        xs.append(x)
     if len(ws) == len(LR.SEEDS):
         LR.assert_operand_coverage(ws, xs)
 
@@ -137,14 +134,11 @@ def test_weight_packing_one_hot(B, name):
     L = LAYERS[name]
     nimg, e, c = L.gf * B, L.ih - 1, L.ih // 2
     w = _distinct_ints(LR.weight_shape(L))
-    try:
-        for (im, y, xx, ch) in ((0, 0, 0, 0), (nimg - 1, e, e, L.cin - 1), (0, 0, e, L.cin - 1), (nimg - 1, e, 0, 0),
-                                (nimg // 2, 0, c, L.cin // 2), (nimg - 1, c, c, 0), (0, c, c, L.cin - 1)):
-            x = torch.zeros(nimg, L.ih, L.ih, L.cin, dtype=torch.float64)
-            x[im, y, xx, ch] = 1.0
-            LR.check_forward(h, L, name, x, w, CR_KNOBS, "%s B=%d one-hot %s" % (name, B, (im, y, xx, ch)))
-    finally:
-        h.restore_knobs()
+    for (im, y, xx, ch) in ((0, 0, 0, 0), (nimg - 1, e, e, L.cin - 1), (0, 0, e, L.cin - 1), (nimg - 1, e, 0, 0),
+                            (nimg // 2, 0, c, L.cin // 2), (nimg - 1, c, c, 0), (0, c, c, L.cin - 1)):
+        x = torch.zeros(nimg, L.ih, L.ih, L.cin, dtype=torch.float64)
+        x[im, y, xx, ch] = 1.0
+        LR.check_forward(h, L, name, x, w, CR_KNOBS, "%s B=%d one-hot %s" % (name, B, (im, y, xx, ch)))
 
 
 @pytest.mark.parametrize("name", list(LAYERS))
@@ -152,14 +146,11 @@ def test_weight_packing_one_hot(B, name):
 def test_wgrad_exact(B, name):
     h = _harness(B)
     L = LAYERS[name]
-    try:
-        for seed in _seeds(B):
-            x, _, dy = LR.layer_operands(name, L.gb * B, seed, LAYERS)
-            h.put(L.x, x)
-            h.put(L.dy, dy)
-            LR.check_wgrad(h, name + "_wgrad", L.param, LR.ref_wgrad(L, x, dy), WG_KNOBS, "%s_wgrad B=%d seed %d" % (name, B, seed))
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        x, _, dy = LR.layer_operands(name, L.gb * B, seed, LAYERS)
+        h.put(L.x, x)
+        h.put(L.dy, dy)
+        LR.check_wgrad(h, name + "_wgrad", L.param, LR.ref_wgrad(L, x, dy), WG_KNOBS, "%s_wgrad B=%d seed %d" % (name, B, seed))
 
 
 # ------------------------------------------------------------------------------------------------ Tier B: data gradients
@@ -183,17 +174,14 @@ def test_dgrad_epilogue(B, name):
     a table (the poisoned ones are NaN: the result would not pass its gate) nor write a sum (compared bit for bit afterwards)."""
     h = _harness(B)
     L = LAYERS[name]
-    try:
-        for seed in _seeds(B):
-            _, w, dy = LR.layer_operands(name, L.gb * B, seed, LAYERS)
-            g = LR.gen(seed, list(LAYERS).index(name), 4, L.gb * B)
-            before = _poison_tables(h, name[:3]) if L.aff is None else {}
-            LR.check_dgrad(h, L, name, dy, w, g, CR_KNOBS, "%s_dgrad B=%d seed %d" % (name, B, seed))
-            for tag, G, C in (SIDE[name[:3]] if before else ()):
-                after = h.buf("red_" + tag, G * LR.STAT_SLOTS * C * 2, torch.float32)
-                assert torch.equal(after, before["red_" + tag]), "%s_dgrad wrote BatchNorm-backward sums into red_%s" % (name, tag)
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        _, w, dy = LR.layer_operands(name, L.gb * B, seed, LAYERS)
+        g = LR.gen(seed, list(LAYERS).index(name), 4, L.gb * B)
+        before = _poison_tables(h, name[:3]) if L.aff is None else {}
+        LR.check_dgrad(h, L, name, dy, w, g, CR_KNOBS, "%s_dgrad B=%d seed %d" % (name, B, seed))
+        for tag, G, C in (SIDE[name[:3]] if before else ()):
+            after = h.buf("red_" + tag, G * LR.STAT_SLOTS * C * 2, torch.float32)
+            assert torch.equal(after, before["red_" + tag]), "%s_dgrad wrote BatchNorm-backward sums into red_%s" % (name, tag)
 
 
 # ------------------------------------------------------------------------------------------------ the 3-channel ends
@@ -205,59 +193,56 @@ def test_thin_layers_exact(B):
     column order of im2col_small_kernel, the references the conv2d / conv_transpose2d of coco/model.py:158,207 on that image."""
     h = _harness(B)
     f0, f9 = "image_encoder.features.0.weight", "image_decoder.hallucinate.9.weight"
-    try:
-        for seed in _seeds(B):
-            g = LR.gen(seed, 9, B)
-            img = LR.ternary((B, 3, 32, 32), 0.5, g)
-            w0 = LR.ternary((64, 3, 4, 4), 0.5, g)
-            d1 = LR.ternary((B, 16, 16, 64), 0.5, g)
-            h.put("patches1", LR.patches_k4s2(img))
-            ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
-            LR.assert_exact_regime(out=ref, what="enc_conv1")
-            h.set_weight(f0, w0)
-            h.zero("r1", ref.numel(), torch.bfloat16)
-            h.zero("a1", ref.numel(), torch.bfloat16)
-            launches = h.run("enc_conv1")
-            got = h.get("r1", ref.shape).double().cpu()
-            assert torch.equal(got, ref), (B, seed, launches, LR.describe_mismatch(got, ref))
-            LR.gate_elements(h.get("a1", ref.shape), ref * torch.sigmoid(ref), ref, "enc_conv1 a1 B=%d seed %d" % (B, seed))
-            wz = torch.zeros(64, 3, 4, 4, dtype=torch.float64, requires_grad=True)
-            F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
-            h.put("d1e", d1)
-            # (the K = 48 ends match no ring geometry -- csrc/wgrad_ring_geos.h -- so the partial-copies knob set would repeat the
-            #  same launch: ring off / on only)
-            LR.check_wgrad(h, "enc_conv1_wgrad", f0, wz.grad, WG_KNOBS[:2], "enc_conv1_wgrad B=%d seed %d" % (B, seed))
-            # last transposed conv (64 -> 3 channels): dW from its activated input aq3 and im2col(dlogit), 3 passes
-            dl = LR.ternary((3 * B, 3, 32, 32), 0.25, g)
-            a3 = LR.ternary((3 * B, 16, 16, 64), 0.25, g)
-            w9 = torch.zeros(64, 3, 4, 4, dtype=torch.float64, requires_grad=True)
-            F.conv_transpose2d(LR._nchw(a3), w9, None, 2, 1).backward(dl)
-            h.put("patches4", LR.patches_k4s2(dl))
-            h.put("aq3", a3)
-            LR.check_wgrad(h, "dec_last_wgrad", f9, w9.grad, WG_KNOBS[:2], "dec_last_wgrad B=%d seed %d" % (B, seed))
-            # its input gradient with the epilogue of hallucinate.7
-            dl = LR.ternary((3 * B, 3, 32, 32), 0.5, g)
-            w9 = LR.ternary((64, 3, 4, 4), 0.5, g)
-            x = torch.zeros(3 * B, 64, 16, 16, dtype=torch.float64, requires_grad=True)
-            F.conv_transpose2d(x, w9, None, 2, 1).backward(dl)
-            acc = LR._nhwc(x.grad)
-            assert bool((acc == acc.round()).all()) and float(acc.abs().max()) <= 256
-            r = LR.eighths(acc.shape, g)
-            aff, mr = LR.dyadic_tables(3, 64, g)
-            v, red, red_abs = LR.ref_dgrad_epilogue(acc, r, aff, mr, 3)
-            h.set_weight(f9, w9)
-            h.put("patches4", LR.patches_k4s2(dl))
-            h.put("q3", r)
-            h.put("aff_d2", aff, torch.float32)
-            h.put("mr_d2", mr, torch.float32)
-            h.zero("d3", acc.numel(), torch.bfloat16)
-            h.zero("red_d2", 3 * LR.STAT_SLOTS * 64 * 2, torch.float32)
-            launches = h.run("dec_last_dgrad_gemm")
-            what = "dec_last_dgrad_gemm B=%d seed %d" % (B, seed)
-            LR.gate_elements(h.get("d3", acc.shape), v, acc, what, launches)
-            LR.gate_sums(h.stats("red_d2", 3, 64), red, red_abs, what + " d_red", launches)
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        g = LR.gen(seed, 9, B)
+        img = LR.ternary((B, 3, 32, 32), 0.5, g)
+        w0 = LR.ternary((64, 3, 4, 4), 0.5, g)
+        d1 = LR.ternary((B, 16, 16, 64), 0.5, g)
+        h.put("patches1", LR.patches_k4s2(img))
+        ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
+        LR.assert_exact_regime(out=ref, what="enc_conv1")
+        h.set_weight(f0, w0)
+        h.zero("r1", ref.numel(), torch.bfloat16)
+        h.zero("a1", ref.numel(), torch.bfloat16)
+        launches = h.run("enc_conv1")
+        got = h.get("r1", ref.shape).double().cpu()
+        assert torch.equal(got, ref), (B, seed, launches, LR.describe_mismatch(got, ref))
+        LR.gate_elements(h.get("a1", ref.shape), ref * torch.sigmoid(ref), ref, "enc_conv1 a1 B=%d seed %d" % (B, seed))
+        wz = torch.zeros(64, 3, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
+        h.put("d1e", d1)
+        # (the K = 48 ends match no ring geometry -- csrc/wgrad_ring_geos.h -- so the partial-copies knob set would repeat the
+        #  same launch: ring off / on only)
+        LR.check_wgrad(h, "enc_conv1_wgrad", f0, wz.grad, WG_KNOBS[:2], "enc_conv1_wgrad B=%d seed %d" % (B, seed))
+        # last transposed conv (64 -> 3 channels): dW from its activated input aq3 and im2col(dlogit), 3 passes
+        dl = LR.ternary((3 * B, 3, 32, 32), 0.25, g)
+        a3 = LR.ternary((3 * B, 16, 16, 64), 0.25, g)
+        w9 = torch.zeros(64, 3, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv_transpose2d(LR._nchw(a3), w9, None, 2, 1).backward(dl)
+        h.put("patches4", LR.patches_k4s2(dl))
+        h.put("aq3", a3)
+        LR.check_wgrad(h, "dec_last_wgrad", f9, w9.grad, WG_KNOBS[:2], "dec_last_wgrad B=%d seed %d" % (B, seed))
+        # its input gradient with the epilogue of hallucinate.7
+        dl = LR.ternary((3 * B, 3, 32, 32), 0.5, g)
+        w9 = LR.ternary((64, 3, 4, 4), 0.5, g)
+        x = torch.zeros(3 * B, 64, 16, 16, dtype=torch.float64, requires_grad=True)
+        F.conv_transpose2d(x, w9, None, 2, 1).backward(dl)
+        acc = LR._nhwc(x.grad)
+        assert bool((acc == acc.round()).all()) and float(acc.abs().max()) <= 256
+        r = LR.eighths(acc.shape, g)
+        aff, mr = LR.dyadic_tables(3, 64, g)
+        v, red, red_abs = LR.ref_dgrad_epilogue(acc, r, aff, mr, 3)
+        h.set_weight(f9, w9)
+        h.put("patches4", LR.patches_k4s2(dl))
+        h.put("q3", r)
+        h.put("aff_d2", aff, torch.float32)
+        h.put("mr_d2", mr, torch.float32)
+        h.zero("d3", acc.numel(), torch.bfloat16)
+        h.zero("red_d2", 3 * LR.STAT_SLOTS * 64 * 2, torch.float32)
+        launches = h.run("dec_last_dgrad_gemm")
+        what = "dec_last_dgrad_gemm B=%d seed %d" % (B, seed)
+        LR.gate_elements(h.get("d3", acc.shape), v, acc, what, launches)
+        LR.gate_sums(h.stats("red_d2", 3, 64), red, red_abs, what + " d_red", launches)
 
 
 @pytest.mark.parametrize("B", BATCHES)
@@ -265,21 +250,18 @@ def test_im2col(B):
     """im2col_dlogit: dlogit [3B][3][32][32] fp32 -> patches4 [3B * 256][48] bf16 against F.unfold on values exact in bf16 -- the
     zero columns of the windows that leave the image included, and the row stride 48 (a wrong leading dimension shifts every row)."""
     h = _harness(B)
-    try:
-        g = LR.gen(0, 14, B)
-        dl = LR.eighths((3 * B, 3, 32, 32), g)
-        dl[dl == 0] = 0.125                       # no zeros inside the image: a padding column is the only way to a zero
-        want = LR.patches_k4s2(dl)
-        assert float((want == 0).double().mean()) > 0.05
-        h.put("dlogit", dl, torch.float32)
-        h.buf("patches4", want.numel(), torch.bfloat16).fill_(7.0)
-        h.run("im2col_dlogit")
-        got = h.get("patches4", want.shape).double().cpu()
-        bad = got != want
-        assert not bool(bad.any()), ("im2col_dlogit B=%d" % B, "%d of %d elements differ; first [row, column] %s got %s want %s" % (
-            int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), want[bad][:6].tolist()))
-    finally:
-        h.restore_knobs()
+    g = LR.gen(0, 14, B)
+    dl = LR.eighths((3 * B, 3, 32, 32), g)
+    dl[dl == 0] = 0.125                       # no zeros inside the image: a padding column is the only way to a zero
+    want = LR.patches_k4s2(dl)
+    assert float((want == 0).double().mean()) > 0.05
+    h.put("dlogit", dl, torch.float32)
+    h.buf("patches4", want.numel(), torch.bfloat16).fill_(7.0)
+    h.run("im2col_dlogit")
+    got = h.get("patches4", want.shape).double().cpu()
+    bad = got != want
+    assert not bool(bad.any()), ("im2col_dlogit B=%d" % B, "%d of %d elements differ; first [row, column] %s got %s want %s" % (
+        int(bad.sum()), bad.numel(), torch.nonzero(bad)[:6].tolist(), got[bad][:6].tolist(), want[bad][:6].tolist()))
 
 
 # ------------------------------------------------------------------------------------------------ dense layers
@@ -347,7 +329,6 @@ def _check_fc3(h, B, D, g, tag):
         LR.gate_elements(h.get("dy2", (rows, HID2)), v, acc, "fc3_dgrad mask %d %s" % (mask, tag))
         boff = _only_bias(h, C3 + "bias", HID2, "fc3_dgrad")
         LR.gate_sums(h.st.grads[boff:boff + HID2], v.sum(0), v.abs().sum(0), "fc3_dgrad d_colsum mask %d %s" % (mask, tag))
-    h.set_knobs(coco_layer_mask=0)
 
 
 def _check_up(h, B, D, g, tag):
@@ -383,86 +364,81 @@ def test_dense_layers(B):
     BatchNorm-backward / bias sums the 2^-16 gate.  The keep masks are the test's."""
     h = _harness(B)
     rows, D = 2 * B, 100
-    try:
-        for seed in _seeds(B):
-            g = LR.gen(seed, 11, B)
-            tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
-            ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
-            W1, W3 = tern((HID1, FEAT), 0.25), tern((HID2, HID1), 0.25)
-            b1, b3 = ibias(HID1), ibias(HID2)
-            for n, t in ((C0 + "weight", W1), (C0 + "bias", b1), (C3 + "weight", W3), (C3 + "bias", b3)):
-                h.set_weight(n, t)
-            m1 = (torch.rand((rows, HID1), generator=g) < 0.9).to(torch.uint8)
-            m2 = (torch.rand((rows, HID2), generator=g) < 0.9).to(torch.uint8)
-            h.put("m1", m1, torch.uint8)
-            h.put("m2", m2, torch.uint8)
-            tag = "B=%d seed %d" % (B, seed)
+    for seed in _seeds(B):
+        g = LR.gen(seed, 11, B)
+        tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
+        ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
+        W1, W3 = tern((HID1, FEAT), 0.25), tern((HID2, HID1), 0.25)
+        b1, b3 = ibias(HID1), ibias(HID2)
+        for n, t in ((C0 + "weight", W1), (C0 + "bias", b1), (C3 + "weight", W3), (C3 + "bias", b3)):
+            h.set_weight(n, t)
+        m1 = (torch.rand((rows, HID1), generator=g) < 0.9).to(torch.uint8)
+        m2 = (torch.rand((rows, HID2), generator=g) < 0.9).to(torch.uint8)
+        h.put("m1", m1, torch.uint8)
+        h.put("m2", m2, torch.uint8)
+        tag = "B=%d seed %d" % (B, seed)
 
-            # ---- classifier.0 / classifier.3 forward: row r of the 2B rows reads image r % B
-            a4 = tern((B, 2, 2, 512), 0.25)
-            h.put("a4", a4)
-            x1 = _flat_nchw(a4).repeat(2, 1)
-            y1 = F.linear(x1, W1, b1)
-            ay1 = tern((rows, HID1), 0.25)
-            y2 = F.linear(ay1, W3, b3)
-            for mask in (0, 1):
-                for nm, n in (("y1", HID1), ("ay1", HID1), ("y2", HID2), ("ay2", HID2)):
-                    h.zero(nm, rows * n, torch.bfloat16)
-                h.run("fc1", coco_layer_mask=mask)
-                LR.check_exact(h.get("y1", (rows, HID1)), y1, "fc1 y1 mask %d %s" % (mask, tag))
-                LR.gate_elements(h.get("ay1", (rows, HID1)), _swish(y1) * (m1 * DROP_SCALE if mask else 1.0), y1, "fc1 ay1 mask %d %s" % (mask, tag))
-                h.put("ay1", ay1)
-                h.run("fc2", coco_layer_mask=mask)
-                LR.check_exact(h.get("y2", (rows, HID2)), y2, "fc2 y2 mask %d %s" % (mask, tag))
-                LR.gate_elements(h.get("ay2", (rows, HID2)), _swish(y2) * (m2 * DROP_SCALE if mask else 1.0), y2, "fc2 ay2 mask %d %s" % (mask, tag))
-            h.set_knobs(coco_layer_mask=0)
-
-            # ---- classifier.6 and its gradients
-            _check_fc3(h, B, D, g, tag)
-            h.put("m2", m2, torch.uint8)
-
-            # ---- classifier.3 gradients: dy1 = (dy2 W3) * Swish'(y1) [* keep / 0.9], column sums = classifier.0's bias gradient
-            dy2, r1 = tern((rows, HID2)), LR.eighths((rows, HID1), g)
-            h.put("dy2", dy2)
+        # ---- classifier.0 / classifier.3 forward: row r of the 2B rows reads image r % B
+        a4 = tern((B, 2, 2, 512), 0.25)
+        h.put("a4", a4)
+        x1 = _flat_nchw(a4).repeat(2, 1)
+        y1 = F.linear(x1, W1, b1)
+        ay1 = tern((rows, HID1), 0.25)
+        y2 = F.linear(ay1, W3, b3)
+        for mask in (0, 1):
+            for nm, n in (("y1", HID1), ("ay1", HID1), ("y2", HID2), ("ay2", HID2)):
+                h.zero(nm, rows * n, torch.bfloat16)
+            h.run("fc1", coco_layer_mask=mask)
+            LR.check_exact(h.get("y1", (rows, HID1)), y1, "fc1 y1 mask %d %s" % (mask, tag))
+            LR.gate_elements(h.get("ay1", (rows, HID1)), _swish(y1) * (m1 * DROP_SCALE if mask else 1.0), y1, "fc1 ay1 mask %d %s" % (mask, tag))
             h.put("ay1", ay1)
-            LR.check_wgrad(h, "fc2_wgrad", C3 + "weight", dy2.t() @ ay1, WG_KNOBS[:1], "fc2_wgrad " + tag)
-            h.put("y1", r1)
-            acc = dy2 @ W3
-            for mask in (0, 1):
-                v = acc * LR.dswish(r1) * (m1 * DROP_SCALE if mask else 1.0)
-                h.zero("dy1", rows * HID1, torch.bfloat16)
-                h.st.grads.zero_()
-                h.run("fc2_dgrad", coco_layer_mask=mask)
-                LR.gate_elements(h.get("dy1", (rows, HID1)), v, acc, "fc2_dgrad mask %d %s" % (mask, tag))
-                boff = _only_bias(h, C0 + "bias", HID1, "fc2_dgrad")
-                LR.gate_sums(h.st.grads[boff:boff + HID1], v.sum(0), v.abs().sum(0), "fc2_dgrad d_colsum mask %d %s" % (mask, tag))
-            h.set_knobs(coco_layer_mask=0)
+            h.run("fc2", coco_layer_mask=mask)
+            LR.check_exact(h.get("y2", (rows, HID2)), y2, "fc2 y2 mask %d %s" % (mask, tag))
+            LR.gate_elements(h.get("ay2", (rows, HID2)), _swish(y2) * (m2 * DROP_SCALE if mask else 1.0), y2, "fc2 ay2 mask %d %s" % (mask, tag))
 
-            # ---- classifier.0 gradients.  dy1 dense, and with the zeros a keep mask upstream leaves in it (the step with dropout)
-            for masked in (0, 1):
-                dy1 = tern((rows, HID1)) * (m1.double() if masked else 1.0)
-                h.put("dy1", dy1)
-                wz = torch.zeros(HID1, FEAT, dtype=torch.float64, requires_grad=True)
-                F.linear(x1, wz).backward(dy1)
-                LR.check_wgrad(h, "fc1_wgrad", C0 + "weight", wz.grad, WG_KNOBS[:1], "fc1_wgrad masked %d %s" % (masked, tag))
-                # db4[n][s * 512 + c] = (dy1 W1)[n][c * 4 + s] * Swish'(scale_c * r4[n % B] + shift_c); sums per channel c = column % 512
-                acc = _map_nhwc(dy1 @ W1)
-                r4 = LR.eighths((B, 2, 2, 512), g)
-                aff, mr = LR.dyadic_tables(1, 512, g)
-                v, red, red_abs = LR.ref_dgrad_epilogue(acc, r4.repeat(2, 1, 1, 1), aff, mr, 1)
-                h.put("r4", r4)
-                h.put("aff_e2", aff, torch.float32)
-                h.put("mr_e2", mr, torch.float32)
-                h.zero("db4", rows * FEAT, torch.bfloat16)
-                h.zero("red_e2", LR.STAT_SLOTS * 512 * 2, torch.float32)
-                launches = h.run("fc1_dgrad")
-                LR.gate_elements(h.get("db4", acc.shape), v, acc, "fc1_dgrad masked %d %s" % (masked, tag), launches)
-                LR.gate_sums(h.stats("red_e2", 1, 512), red, red_abs, "fc1_dgrad d_red masked %d %s" % (masked, tag), launches)
+        # ---- classifier.6 and its gradients
+        _check_fc3(h, B, D, g, tag)
+        h.put("m2", m2, torch.uint8)
 
-            # ---- upsample.0
-            _check_up(h, B, D, g, tag)
-    finally:
-        h.restore_knobs()
+        # ---- classifier.3 gradients: dy1 = (dy2 W3) * Swish'(y1) [* keep / 0.9], column sums = classifier.0's bias gradient
+        dy2, r1 = tern((rows, HID2)), LR.eighths((rows, HID1), g)
+        h.put("dy2", dy2)
+        h.put("ay1", ay1)
+        LR.check_wgrad(h, "fc2_wgrad", C3 + "weight", dy2.t() @ ay1, WG_KNOBS[:1], "fc2_wgrad " + tag)
+        h.put("y1", r1)
+        acc = dy2 @ W3
+        for mask in (0, 1):
+            v = acc * LR.dswish(r1) * (m1 * DROP_SCALE if mask else 1.0)
+            h.zero("dy1", rows * HID1, torch.bfloat16)
+            h.st.grads.zero_()
+            h.run("fc2_dgrad", coco_layer_mask=mask)
+            LR.gate_elements(h.get("dy1", (rows, HID1)), v, acc, "fc2_dgrad mask %d %s" % (mask, tag))
+            boff = _only_bias(h, C0 + "bias", HID1, "fc2_dgrad")
+            LR.gate_sums(h.st.grads[boff:boff + HID1], v.sum(0), v.abs().sum(0), "fc2_dgrad d_colsum mask %d %s" % (mask, tag))
+
+        # ---- classifier.0 gradients.  dy1 dense, and with the zeros a keep mask upstream leaves in it (the step with dropout)
+        for masked in (0, 1):
+            dy1 = tern((rows, HID1)) * (m1.double() if masked else 1.0)
+            h.put("dy1", dy1)
+            wz = torch.zeros(HID1, FEAT, dtype=torch.float64, requires_grad=True)
+            F.linear(x1, wz).backward(dy1)
+            LR.check_wgrad(h, "fc1_wgrad", C0 + "weight", wz.grad, WG_KNOBS[:1], "fc1_wgrad masked %d %s" % (masked, tag))
+            # db4[n][s * 512 + c] = (dy1 W1)[n][c * 4 + s] * Swish'(scale_c * r4[n % B] + shift_c); sums per channel c = column % 512
+            acc = _map_nhwc(dy1 @ W1)
+            r4 = LR.eighths((B, 2, 2, 512), g)
+            aff, mr = LR.dyadic_tables(1, 512, g)
+            v, red, red_abs = LR.ref_dgrad_epilogue(acc, r4.repeat(2, 1, 1, 1), aff, mr, 1)
+            h.put("r4", r4)
+            h.put("aff_e2", aff, torch.float32)
+            h.put("mr_e2", mr, torch.float32)
+            h.zero("db4", rows * FEAT, torch.bfloat16)
+            h.zero("red_e2", LR.STAT_SLOTS * 512 * 2, torch.float32)
+            launches = h.run("fc1_dgrad")
+            LR.gate_elements(h.get("db4", acc.shape), v, acc, "fc1_dgrad masked %d %s" % (masked, tag), launches)
+            LR.gate_sums(h.stats("red_e2", 1, 512), red, red_abs, "fc1_dgrad d_red masked %d %s" % (masked, tag), launches)
+
+        # ---- upsample.0
+        _check_up(h, B, D, g, tag)
 
 
 @pytest.mark.parametrize("B", [3, 8])
@@ -471,13 +447,10 @@ def test_dense_layers_other_latent_sizes(D, B):
     """The layers whose shape depends on the latent size, at D = 20 and 64 (ldz = round_up(D + 1, 8) = 24 / 72; at D = 64, D + 1
     crosses a multiple of 64 and the packed K of upsample.0 doubles): fc3, fc3_wgrad, fc3_dgrad, up, up_wgrad, up_dgrad."""
     h = _harness(B, D)
-    try:
-        g = LR.gen(0, 15, B, D)
-        tag = "D=%d B=%d" % (D, B)
-        _check_fc3(h, B, D, g, tag)
-        _check_up(h, B, D, g, tag)
-    finally:
-        h.restore_knobs()
+    g = LR.gen(0, 15, B, D)
+    tag = "D=%d B=%d" % (D, B)
+    _check_fc3(h, B, D, g, tag)
+    _check_up(h, B, D, g, tag)
 
 
 @pytest.mark.parametrize("B", [3, 8])
@@ -493,50 +466,47 @@ def test_dense_packing_one_hot(B):
     W1, W3, W6, Wu = _distinct_ints((HID1, FEAT)), _distinct_ints((HID2, HID1)), _distinct_ints((2 * D, HID2)), _distinct_ints((FEAT, D))
     b1, b3 = (torch.arange(HID1) % 5 - 2).double(), (torch.arange(HID2) % 3 - 1).double()
     b6, bu = (torch.arange(2 * D) % 9 - 4).double(), (torch.arange(FEAT) % 7 - 3).double()
-    try:
-        for n, t in ((C0 + "weight", W1), (C0 + "bias", b1), (C3 + "weight", W3), (C3 + "bias", b3), (C6 + "weight", W6), (C6 + "bias", b6),
-                     (UP + "weight", Wu), (UP + "bias", bu)):
-            h.set_weight(n, t)
-        for (n, y, x, c) in ((0, 0, 0, 0), (B - 1, 1, 1, 511), (B // 2, 0, 1, 256), (0, 1, 0, 7), (B - 1, 1, 0, 1)):
-            a4 = torch.zeros(B, 2, 2, 512, dtype=torch.float64)
-            a4[n, y, x, c] = 1.0
-            want = b1.repeat(rows, 1)
-            want[n] += W1[:, c * 4 + y * 2 + x]
-            want[n + B] += W1[:, c * 4 + y * 2 + x]
-            assert torch.equal(want, F.linear(_flat_nchw(a4).repeat(2, 1), W1, b1))
-            h.put("a4", a4)
-            h.zero("y1", rows * HID1, torch.bfloat16)
-            h.run("fc1")
-            LR.check_exact(h.get("y1", (rows, HID1)), want, "fc1 one-hot %s B=%d" % ((n, y, x, c), B))
-        for (row, k) in ((0, 0), (rows - 1, HID1 - 1), (B, 513)):
-            x = torch.zeros(rows, HID1, dtype=torch.float64)
-            x[row, k] = 1.0
-            h.put("ay1", x)
-            h.zero("y2", rows * HID2, torch.bfloat16)
-            h.run("fc2")
-            LR.check_exact(h.get("y2", (rows, HID2)), F.linear(x, W3, b3), "fc2 one-hot %s B=%d" % ((row, k), B))
-        for (row, k) in ((0, 0), (rows - 1, HID2 - 1), (B, 129)):
-            x = torch.zeros(rows, HID2, dtype=torch.float64)
-            x[row, k] = 1.0
-            h.put("ay2", x)
-            h.zero("encout", rows * 2 * D, torch.float32)
-            h.run("fc3")
-            LR.check_exact(h.get("encout", (rows, 2 * D), torch.float32), F.linear(x, W6, b6), "fc3 one-hot %s B=%d" % ((row, k), B), limit=2 ** 24)
-        for (row, k) in ((0, 0), (3 * B - 1, D - 1), (B, 37), (2 * B - 1, 64)):
-            z = torch.zeros(3 * B, D, dtype=torch.float64)
-            z[row, k] = 1.0
-            want = bu.repeat(3 * B, 1)
-            want[row] += Wu[:, k]
-            assert torch.equal(want, F.linear(z, Wu, bu))
-            want = _map_nhwc(want).reshape(3 * B, FEAT)
-            s, c = 3, 200
-            assert float(want[row, s * 512 + c]) == float(Wu[c * 4 + s, k] + bu[c * 4 + s])
-            h.put("z_bf", _z_rows(z, D))
-            h.zero("u", 3 * B * FEAT, torch.bfloat16)
-            h.run("up")
-            LR.check_exact(h.get("u", (3 * B, FEAT)), want, "up one-hot %s B=%d" % ((row, k), B))
-    finally:
-        h.restore_knobs()
+    for n, t in ((C0 + "weight", W1), (C0 + "bias", b1), (C3 + "weight", W3), (C3 + "bias", b3), (C6 + "weight", W6), (C6 + "bias", b6),
+                 (UP + "weight", Wu), (UP + "bias", bu)):
+        h.set_weight(n, t)
+    for (n, y, x, c) in ((0, 0, 0, 0), (B - 1, 1, 1, 511), (B // 2, 0, 1, 256), (0, 1, 0, 7), (B - 1, 1, 0, 1)):
+        a4 = torch.zeros(B, 2, 2, 512, dtype=torch.float64)
+        a4[n, y, x, c] = 1.0
+        want = b1.repeat(rows, 1)
+        want[n] += W1[:, c * 4 + y * 2 + x]
+        want[n + B] += W1[:, c * 4 + y * 2 + x]
+        assert torch.equal(want, F.linear(_flat_nchw(a4).repeat(2, 1), W1, b1))
+        h.put("a4", a4)
+        h.zero("y1", rows * HID1, torch.bfloat16)
+        h.run("fc1")
+        LR.check_exact(h.get("y1", (rows, HID1)), want, "fc1 one-hot %s B=%d" % ((n, y, x, c), B))
+    for (row, k) in ((0, 0), (rows - 1, HID1 - 1), (B, 513)):
+        x = torch.zeros(rows, HID1, dtype=torch.float64)
+        x[row, k] = 1.0
+        h.put("ay1", x)
+        h.zero("y2", rows * HID2, torch.bfloat16)
+        h.run("fc2")
+        LR.check_exact(h.get("y2", (rows, HID2)), F.linear(x, W3, b3), "fc2 one-hot %s B=%d" % ((row, k), B))
+    for (row, k) in ((0, 0), (rows - 1, HID2 - 1), (B, 129)):
+        x = torch.zeros(rows, HID2, dtype=torch.float64)
+        x[row, k] = 1.0
+        h.put("ay2", x)
+        h.zero("encout", rows * 2 * D, torch.float32)
+        h.run("fc3")
+        LR.check_exact(h.get("encout", (rows, 2 * D), torch.float32), F.linear(x, W6, b6), "fc3 one-hot %s B=%d" % ((row, k), B), limit=2 ** 24)
+    for (row, k) in ((0, 0), (3 * B - 1, D - 1), (B, 37), (2 * B - 1, 64)):
+        z = torch.zeros(3 * B, D, dtype=torch.float64)
+        z[row, k] = 1.0
+        want = bu.repeat(3 * B, 1)
+        want[row] += Wu[:, k]
+        assert torch.equal(want, F.linear(z, Wu, bu))
+        want = _map_nhwc(want).reshape(3 * B, FEAT)
+        s, c = 3, 200
+        assert float(want[row, s * 512 + c]) == float(Wu[c * 4 + s, k] + bu[c * 4 + s])
+        h.put("z_bf", _z_rows(z, D))
+        h.zero("u", 3 * B * FEAT, torch.bfloat16)
+        h.run("up")
+        LR.check_exact(h.get("u", (3 * B, FEAT)), want, "up one-hot %s B=%d" % ((row, k), B))
 
 
 # ------------------------------------------------------------------------------------------------ stand-alone passes
@@ -586,39 +556,36 @@ def test_bn_forward(B, name):
     idx, Cb, soff = _bn_slot(h, bn)
     assert Cb == C
     what = "%s B=%d" % (name, B)
-    try:
-        h.set_weight(bn + ".weight", gamma)
-        h.set_weight(bn + ".bias", beta)
-        h.st.bn_stats[soff:soff + C] = rm0.float().to(h.dev)
-        h.st.bn_stats[soff + C:soff + 2 * C] = rv0.float().to(h.dev)
-        h.st.bn_nbt[idx] = 5
-        h.put(L.out, r)
-        h.put("st_" + tb, stats, torch.float32)
-        h.zero(act, r.numel(), torch.bfloat16)
-        h.zero("aff_" + tb, G * C * 2, torch.float32)
-        h.zero("mr_" + tb, G * C * 2, torch.float32)
-        h.run(name)
-        scale, shift, mean, rstd = LR.ref_bn_tables(stats, count, gamma, beta)
-        aff = h.get("aff_" + tb, (G, C, 2), torch.float32)
-        mr = h.get("mr_" + tb, (G, C, 2), torch.float32)
-        # fp32 roundings of csrc/bn_dev.h bn_channel_tables, counted in tests/test_gpu_celeba_layers_staged.py: mean 16 (of 4), rstd 11,
-        # scale 12, shift 16 of (4 + |mean|) |scale| + |beta|
-        e = LR.EPS32
-        _within(aff[..., 0], scale, 12 * e * scale.abs(), what + " scale")
-        _within(aff[..., 1], shift, 16 * e * ((mean.abs() + 4) * scale.abs() + beta.abs()[None]), what + " shift")
-        _within(mr[..., 0], mean, 16 * e * 4 * torch.ones_like(mean), what + " mean")
-        _within(mr[..., 1], rstd, 11 * e * rstd, what + " rstd")
-        a_ref, _ = LR.ref_stage_fwd(r, scale, shift, G)
-        _within(h.get(act, r.shape), a_ref, LR.gate_stage_fwd(r, scale, shift, mean, beta, a_ref, G), what + " activated")
-        # running statistics after n = G * updates momentum steps: the mean's 16 roundings (of 4), the variance's 20 and 2 more of
-        # the unbiased factor, then per step 2 products, 1 addition and the two rounded constants 0.1f / (1.f - 0.1f): 5 per step
-        n = G * updates
-        rm, rv, unb = LR.ref_bn_running(stats, count, rm0, rv0, updates)
-        _within(h.st.bn_stats[soff:soff + C], rm, (16 + 5 * n) * e * 4 * torch.ones_like(rm), what + " running_mean")
-        _within(h.st.bn_stats[soff + C:soff + 2 * C], rv, (22 + 5 * n) * e * torch.maximum(unb, rv0), what + " running_var")
-        assert int(h.st.bn_nbt[idx]) == 5 + n, (what, int(h.st.bn_nbt[idx]))
-    finally:
-        h.restore_knobs()
+    h.set_weight(bn + ".weight", gamma)
+    h.set_weight(bn + ".bias", beta)
+    h.st.bn_stats[soff:soff + C] = rm0.float().to(h.dev)
+    h.st.bn_stats[soff + C:soff + 2 * C] = rv0.float().to(h.dev)
+    h.st.bn_nbt[idx] = 5
+    h.put(L.out, r)
+    h.put("st_" + tb, stats, torch.float32)
+    h.zero(act, r.numel(), torch.bfloat16)
+    h.zero("aff_" + tb, G * C * 2, torch.float32)
+    h.zero("mr_" + tb, G * C * 2, torch.float32)
+    h.run(name)
+    scale, shift, mean, rstd = LR.ref_bn_tables(stats, count, gamma, beta)
+    aff = h.get("aff_" + tb, (G, C, 2), torch.float32)
+    mr = h.get("mr_" + tb, (G, C, 2), torch.float32)
+    # fp32 roundings of csrc/bn_dev.h bn_channel_tables, counted in tests/test_gpu_celeba_layers_staged.py: mean 16 (of 4), rstd 11,
+    # scale 12, shift 16 of (4 + |mean|) |scale| + |beta|
+    e = LR.EPS32
+    _within(aff[..., 0], scale, 12 * e * scale.abs(), what + " scale")
+    _within(aff[..., 1], shift, 16 * e * ((mean.abs() + 4) * scale.abs() + beta.abs()[None]), what + " shift")
+    _within(mr[..., 0], mean, 16 * e * 4 * torch.ones_like(mean), what + " mean")
+    _within(mr[..., 1], rstd, 11 * e * rstd, what + " rstd")
+    a_ref, _ = LR.ref_stage_fwd(r, scale, shift, G)
+    _within(h.get(act, r.shape), a_ref, LR.gate_stage_fwd(r, scale, shift, mean, beta, a_ref, G), what + " activated")
+    # running statistics after n = G * updates momentum steps: the mean's 16 roundings (of 4), the variance's 20 and 2 more of
+    # the unbiased factor, then per step 2 products, 1 addition and the two rounded constants 0.1f / (1.f - 0.1f): 5 per step
+    n = G * updates
+    rm, rv, unb = LR.ref_bn_running(stats, count, rm0, rv0, updates)
+    _within(h.st.bn_stats[soff:soff + C], rm, (16 + 5 * n) * e * 4 * torch.ones_like(rm), what + " running_mean")
+    _within(h.st.bn_stats[soff + C:soff + 2 * C], rv, (22 + 5 * n) * e * torch.maximum(unb, rv0), what + " running_var")
+    assert int(h.st.bn_nbt[idx]) == 5 + n, (what, int(h.st.bn_nbt[idx]))
 
 
 @pytest.mark.parametrize("name", list(BN_PASSES))
@@ -642,30 +609,27 @@ def test_bn_backward(B, name):
     goff, _, _ = h.param_range(bn + ".weight")
     boff, _, _ = h.param_range(bn + ".bias")
     what = "%s_bwd B=%d" % (name, B)
-    try:
-        h.set_weight(bn + ".weight", gamma)
-        if name == "enc_bn4":
-            assert bool((db != db2).any())
-            h.put("db4", torch.cat([db.reshape(B, -1), db2.reshape(B, -1)]))
-            h.zero("dr4", dr.numel(), torch.bfloat16)
-            out = "dr4"
-        else:
-            h.put(L.dy, db)
-            out = L.dy
-        h.put(L.out, r)
-        h.put("red_" + tb, red, torch.float32)
-        h.put("mr_" + tb, mr, torch.float32)
-        h.st.grads.zero_()
-        h.run(name + "_bwd")
-        _within(h.get(out, dr.shape), dr, LR.gate_bn_backward(total, r, red, mr, gamma, count, G, dr), what + " dr")
-        LR.gate_sums(h.st.grads[goff:goff + C], dgamma, mag_g, what + " dgamma")
-        LR.gate_sums(h.st.grads[boff:boff + C], dbeta, mag_b, what + " dbeta")
-        others = h.st.grads.clone()
-        others[goff:goff + C] = 0
-        others[boff:boff + C] = 0
-        assert float(others.abs().max()) == 0.0, what + " wrote another parameter's gradient"
-    finally:
-        h.restore_knobs()
+    h.set_weight(bn + ".weight", gamma)
+    if name == "enc_bn4":
+        assert bool((db != db2).any())
+        h.put("db4", torch.cat([db.reshape(B, -1), db2.reshape(B, -1)]))
+        h.zero("dr4", dr.numel(), torch.bfloat16)
+        out = "dr4"
+    else:
+        h.put(L.dy, db)
+        out = L.dy
+    h.put(L.out, r)
+    h.put("red_" + tb, red, torch.float32)
+    h.put("mr_" + tb, mr, torch.float32)
+    h.st.grads.zero_()
+    h.run(name + "_bwd")
+    _within(h.get(out, dr.shape), dr, LR.gate_bn_backward(total, r, red, mr, gamma, count, G, dr), what + " dr")
+    LR.gate_sums(h.st.grads[goff:goff + C], dgamma, mag_g, what + " dgamma")
+    LR.gate_sums(h.st.grads[boff:boff + C], dbeta, mag_b, what + " dbeta")
+    others = h.st.grads.clone()
+    others[goff:goff + C] = 0
+    others[boff:boff + C] = 0
+    assert float(others.abs().max()) == 0.0, what + " wrote another parameter's gradient"
 
 
 @pytest.mark.parametrize("B", BATCHES)
@@ -675,34 +639,31 @@ def test_dec_last_fwd(B):
     the measured gates of layer_ref (module docstring).  The target sits in tmp_f32, logits and recon in the weight-gradient slab."""
     h = _harness(B)
     n3 = 3 * B * 3072
-    try:
-        for seed in _seeds(B):
-            g = LR.gen(seed, 21, B)
-            a3 = LR.ternary((3 * B, 16, 16, 64), LR.LAST_X_DENSITY, g)
-            w9 = LR.ternary((64, 3, 4, 4), LR.LAST_W_DENSITY, g)
-            target = torch.tensor(LR.LAST_TARGETS, dtype=torch.float64)[torch.randint(0, len(LR.LAST_TARGETS), (B, 3, 32, 32), generator=g)]
-            coef = LR.last_layer_coef(B)
-            logits, recon, dlogit, sums, mags = LR.ref_dec_last(a3, w9, target, coef)
-            LR.assert_last_layer_regime(logits)
-            h.set_weight("image_decoder.hallucinate.9.weight", w9)
-            h.put("aq3", a3)
-            h.put("tmp_f32", target, torch.float32)
-            h.zero("slab", 2 * n3, torch.float32)
-            h.buf("dlogit", n3, torch.float32).fill_(7.0)
-            h.zero("sums", 16 * LR.LOSS_SLOTS, torch.float32)
-            h.run("dec_last_fwd")
-            what = "dec_last_fwd B=%d seed %d" % (B, seed)
-            both = h.get("slab", (2,) + tuple(logits.shape), torch.float32)
-            LR.check_exact(both[0], logits, what + " logits")
-            LR.gate_last_layer(both[1], recon, LR.LAST_RECON_MULT, what + " recon")
-            got_dl = h.get("dlogit", logits.shape, torch.float32)
-            assert float(got_dl[2 * B:].abs().max()) == 0.0, what + ": the pass with loss weight 0 has a gradient"
-            LR.gate_last_layer(got_dl, dlogit, LR.LAST_DLOGIT_MULT, what + " dlogit")
-            table = h.get("sums", (LR.LOSS_SLOTS, 16), torch.float32).double().cpu()
-            LR.gate_last_sums(table[:, :3].sum(0), sums, mags, what + " BCE sums")
-            assert float(table[:, 3:].abs().max()) == 0.0, what + " wrote a loss column other than its three"
-    finally:
-        h.restore_knobs()
+    for seed in _seeds(B):
+        g = LR.gen(seed, 21, B)
+        a3 = LR.ternary((3 * B, 16, 16, 64), LR.LAST_X_DENSITY, g)
+        w9 = LR.ternary((64, 3, 4, 4), LR.LAST_W_DENSITY, g)
+        target = torch.tensor(LR.LAST_TARGETS, dtype=torch.float64)[torch.randint(0, len(LR.LAST_TARGETS), (B, 3, 32, 32), generator=g)]
+        coef = LR.last_layer_coef(B)
+        logits, recon, dlogit, sums, mags = LR.ref_dec_last(a3, w9, target, coef)
+        LR.assert_last_layer_regime(logits)
+        h.set_weight("image_decoder.hallucinate.9.weight", w9)
+        h.put("aq3", a3)
+        h.put("tmp_f32", target, torch.float32)
+        h.zero("slab", 2 * n3, torch.float32)
+        h.buf("dlogit", n3, torch.float32).fill_(7.0)
+        h.zero("sums", 16 * LR.LOSS_SLOTS, torch.float32)
+        h.run("dec_last_fwd")
+        what = "dec_last_fwd B=%d seed %d" % (B, seed)
+        both = h.get("slab", (2,) + tuple(logits.shape), torch.float32)
+        LR.check_exact(both[0], logits, what + " logits")
+        LR.gate_last_layer(both[1], recon, LR.LAST_RECON_MULT, what + " recon")
+        got_dl = h.get("dlogit", logits.shape, torch.float32)
+        assert float(got_dl[2 * B:].abs().max()) == 0.0, what + ": the pass with loss weight 0 has a gradient"
+        LR.gate_last_layer(got_dl, dlogit, LR.LAST_DLOGIT_MULT, what + " dlogit")
+        table = h.get("sums", (LR.LOSS_SLOTS, 16), torch.float32).double().cpu()
+        LR.gate_last_sums(table[:, :3].sum(0), sums, mags, what + " BCE sums")
+        assert float(table[:, 3:].abs().max()) == 0.0, what + " wrote a loss column other than its three"
 
 
 # ------------------------------------------------------------------------------------------------ which kernels ran
@@ -732,6 +693,7 @@ def test_coverage():
     image-resident / ring kernel ran with its knob off."""
     if not torch.cuda.is_available():
         pytest.skip("needs the MI355X")
+    from multimodal_vae_amd._lib import knob_default
     recs = LR.RECORDS_COCO
     assert {r[0] for r in recs} >= set(BATCHES), "run the whole module: the compared launches of every batch size are the input of this test"
     hit, fallback, ring_hit, generic, table = {}, {}, {}, {}, {}
@@ -746,7 +708,7 @@ def test_coverage():
             relevant.pop("wr_atomic_kb", None)
         if CR_OF.get(layer) is None:
             relevant.pop("convres", None)
-        default = all(LR.KNOB_DEFAULTS[k] == v for k, v in relevant.items())
+        default = all(knob_default(k) == v for k, v in relevant.items())
         for t, k in launches:
             note = re.split(r" img\d+ ?", t, 1)[1] if t.startswith(("gemm ", "wgrad ")) and " img" in t else ""
             if t.startswith("convres "):

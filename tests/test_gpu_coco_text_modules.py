@@ -68,11 +68,11 @@ import torch
 
 from oracle import mmvae_ref as R
 import coco_text_ref as C
+from multimodal_vae_amd._lib import knob_default, knobs
 
 pytestmark = pytest.mark.gpu
 
 REPORT = os.environ.get("MMVAE_TOL_REPORT") is not None
-KNOB_DEFAULTS = dict(coco_module_bf16=0, coco_cluster=8, coco_no_comb=0, coco_no_comb_bwd=0, coco_enc_streamed=0)
 _REF, _COL, _MODS = {}, {}, {}
 
 
@@ -82,23 +82,9 @@ def _dev():
     return torch.device("cuda:0")
 
 
-class _knobs:
-    """the given knobs for the block, every knob of KNOB_DEFAULTS back at its default behind it"""
-
-    def __init__(self, module_bf16=1, **kw):
-        self.kw = dict(KNOB_DEFAULTS, coco_module_bf16=module_bf16, **kw)
-
-    @staticmethod
-    def _set(kw):
-        from multimodal_vae_amd._lib import call
-        for k, v in kw.items():
-            call("mmvae_debug_set", k.encode(), int(v))
-
-    def __enter__(self):
-        self._set(self.kw)
-
-    def __exit__(self, *a):
-        self._set(KNOB_DEFAULTS)
+def _knobs(module_bf16=1, **kw):
+    """the bf16 persistent kernels behind the module entry points (coco_module_bf16) and the given knobs for the block"""
+    return knobs(coco_module_bf16=module_bf16, **kw)
 
 
 # ------------------------------------------------------------------------------------------------ references, cached per case
@@ -212,21 +198,21 @@ def test_decoder_rows_bit_for_bit(case):
     form, D, B, T, keep = case
     P, inp, ref, gate, _, kind = _dec_setup(*case)
     dec = _module("dec", D, T, P, dev)
-    knobs = C.DEC_FORM_KNOBS[form][0]
-    cluster = knobs.get("coco_cluster", 8)
+    form_knobs = C.DEC_FORM_KNOBS[form][0]
+    cluster = form_knobs.get("coco_cluster", knob_default("coco_cluster"))
 
     def run(i):
         r = _dec_full(dec, i, keep, dev)
         return dict(sentence=r["sentence"], dz=r["dz"])
 
-    with _knobs(**knobs):
+    with _knobs(**form_knobs):
         full = run(inp)
         assert not C.permutation_violations(run, inp, ("sentence", "dz"), full)
         sets = [s for s in (list(range(min(16, B))), list(range(16, B))) if 0 < len(s) < B
                 and C.dec_dispatch(len(s), D, cluster) == C.dec_dispatch(B, D, cluster)]
         assert B <= 16 or len(sets) == 2, "the sub-batches of %d rows do not keep the dispatch" % B
         assert not C.sub_batch_violations(run, inp, sets, ("sentence", "dz"), full)
-    with _knobs(2, **knobs):
+    with _knobs(2, **form_knobs):
         nosave = _dec_forward(dec, inp, keep, dev)
         with pytest.raises(RuntimeError, match="saved nothing"):          # the backward entry refuses (MMVAE_EINVAL)
             _dec_full(dec, inp, keep, dev)

@@ -347,35 +347,25 @@ def test_coco_caption_kernel_forms_agree():
     keep = (torch.rand(T, 3 * B, 200, generator=g) > 0.1).to(torch.uint8).to(dev)
     st = CocoState(D, dev, steps=T); default_init_(st, 21)
     eng = FusedCocoStep(st, B, 0.4 * torch.randn(300, generator=g), seed=3)
-    from multimodal_vae_amd._lib import call
-    switches = ("coco_no_comb", "coco_no_comb_bwd", "coco_no_mse_fuse")       # A/B knobs (include/mmvae_hip.h: mmvae_debug_set)
+    from multimodal_vae_amd._lib import knobs
 
     def run(cluster, streamed, *off):
         """off: knobs that take parts of the composed cluster-of-8 form out (W_comb = W_ih0x W_ho, two exchanges per step,
         the MSE fused into the forward kernel's output pass); the default at cluster == 8 has all of them in."""
-        for k in switches:
-            call("mmvae_debug_set", k.encode(), 1 if k in off else 0)
-        call("mmvae_debug_set", b"coco_cluster", cluster)
-        call("mmvae_debug_set", b"coco_enc_streamed", 1 if streamed else 0)
         rt = torch.zeros(3, B, T, 300, device=dev)
-        out = eng.forward_backward(image, text, True, True, eps=eps, gru_keep=keep, recon_text=rt)
+        with knobs(coco_cluster=cluster, coco_enc_streamed=1 if streamed else 0, **{k: 1 for k in off}):      # (csrc/knobs.h)
+            out = eng.forward_backward(image, text, True, True, eps=eps, gru_keep=keep, recon_text=rt)
         torch.cuda.synchronize()
         return rt, st.grads.clone(), out.losses().cpu().numpy()
 
-    try:
-        r0, g0, l0 = run(0, True)
-        for cluster, streamed, *off in ((0, False), (4, False), (8, False), (8, True), (8, False, "coco_no_comb"),
-                                        (8, False, "coco_no_comb_bwd"), (8, False, "coco_no_mse_fuse")):
-            r, gg, l = run(cluster, streamed, *off)
-            np.testing.assert_allclose(l, l0, rtol=2e-4)
-            assert float((r - r0).abs().max()) < 1e-2, (cluster, streamed, off)
-            assert float((gg - g0).norm() / g0.norm()) < 1e-2, (cluster, streamed, off)
-            for n, shape, o in st.table:        # every tensor, so that a slice of units left out cannot hide in the norm
-                k = int(np.prod(shape))
-                a, b = gg[o:o + k], g0[o:o + k]
-                assert float((a - b).norm()) <= 5e-2 * float(b.norm()) + 1e-7, (cluster, streamed, off, n)
-    finally:
-        for k in switches:
-            call("mmvae_debug_set", k.encode(), 0)
-        call("mmvae_debug_set", b"coco_cluster", 8)
-        call("mmvae_debug_set", b"coco_enc_streamed", 0)
+    r0, g0, l0 = run(0, True)
+    for cluster, streamed, *off in ((0, False), (4, False), (8, False), (8, True), (8, False, "coco_no_comb"),
+                                    (8, False, "coco_no_comb_bwd"), (8, False, "coco_no_mse_fuse")):
+        r, gg, l = run(cluster, streamed, *off)
+        np.testing.assert_allclose(l, l0, rtol=2e-4)
+        assert float((r - r0).abs().max()) < 1e-2, (cluster, streamed, off)
+        assert float((gg - g0).norm() / g0.norm()) < 1e-2, (cluster, streamed, off)
+        for n, shape, o in st.table:        # every tensor, so that a slice of units left out cannot hide in the norm
+            k = int(np.prod(shape))
+            a, b = gg[o:o + k], g0[o:o + k]
+            assert float((a - b).norm()) <= 5e-2 * float(b.norm()) + 1e-7, (cluster, streamed, off, n)

@@ -24,7 +24,6 @@ pytestmark = pytest.mark.gpu
 
 BATCHES = (7, 8, 12)
 KNOB = "gemm_small_prefetch"
-KNOB_DEFAULT = 2                    # csrc/gemm_small.hip launch_small
 DEPTHS = (2, 3, 4)
 _H = {}
 
@@ -59,17 +58,13 @@ def _run_fc1_dgrad(h, B, **knobs):
 def test_fc1_dgrad_against_float64(B):
     """both forms of classifier.0's data gradient: gate_elements for db4, gate_sums for the BatchNorm-backward sums"""
     h = _harness(B)
-    try:
-        for seed in LR.SEEDS:
-            acc, v, red, red_abs = _put_fc1_dgrad(h, B, seed)
-            for knob in (0,) + DEPTHS:
-                got, sums, launches = _run_fc1_dgrad(h, B, **{KNOB: knob})
-                tag = "enc_fc1_dgrad B=%d seed %d knob %d" % (B, seed, knob)
-                LR.gate_elements(got, v, acc, tag, launches)
-                LR.gate_sums(sums, red, red_abs, tag + " d_red", launches)
-    finally:
-        h.set_knobs(**{KNOB: KNOB_DEFAULT})
-        h.restore_knobs()
+    for seed in LR.SEEDS:
+        acc, v, red, red_abs = _put_fc1_dgrad(h, B, seed)
+        for knob in (0,) + DEPTHS:
+            got, sums, launches = _run_fc1_dgrad(h, B, **{KNOB: knob})
+            tag = "enc_fc1_dgrad B=%d seed %d knob %d" % (B, seed, knob)
+            LR.gate_elements(got, v, acc, tag, launches)
+            LR.gate_sums(sums, red, red_abs, tag + " d_red", launches)
 
 
 def _bits(t):
@@ -110,49 +105,45 @@ def test_prefetch_form_equals_replaced_form_bitwise(B, D):
     bf, f32 = torch.bfloat16, torch.float32
     pre, up = "image_encoder.classifier.", "image_decoder.upsample.0."
     colsum = lambda n: (lambda: h.zero("tmp_f32", n, f32), lambda: h.get("tmp_f32", (n,), f32))
-    try:
-        for seed in LR.SEEDS:
-            tag = "B=%d seed %d" % (B, seed)
-            g = LR.gen(seed, 14, B)
-            tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
-            ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
-            keep = lambda shape: (torch.rand(shape, generator=g) < 0.9).to(torch.uint8)
-            W3, W6, Wu = tern((200, 400), 0.25), tern((2 * D, 200), 0.25), tern((1024, D), 0.25)
-            for n, t in ((pre + "0.bias", ibias(400)), (pre + "3.weight", W3), (pre + "6.weight", W6), (up + "weight", Wu), (up + "bias", ibias(1024))):
-                h.set_weight(n, t)
-            m1, m2 = keep((rows, 400)), keep((rows, 200))
-            h.put("m1", m1, torch.uint8)
-            h.put("m2", m2, torch.uint8)
+    for seed in LR.SEEDS:
+        tag = "B=%d seed %d" % (B, seed)
+        g = LR.gen(seed, 14, B)
+        tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
+        ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
+        keep = lambda shape: (torch.rand(shape, generator=g) < 0.9).to(torch.uint8)
+        W3, W6, Wu = tern((200, 400), 0.25), tern((2 * D, 200), 0.25), tern((1024, D), 0.25)
+        for n, t in ((pre + "0.bias", ibias(400)), (pre + "3.weight", W3), (pre + "6.weight", W6), (up + "weight", Wu), (up + "bias", ibias(1024))):
+            h.set_weight(n, t)
+        m1, m2 = keep((rows, 400)), keep((rows, 200))
+        h.put("m1", m1, torch.uint8)
+        h.put("m2", m2, torch.uint8)
 
-            # classifier.0's data gradient (its operands also set classifier.0's weight for the forward below)
-            acc, v, red, red_abs = _put_fc1_dgrad(h, B, seed)
-            _forms_agree(h, "enc_fc1_dgrad", [("db4", (rows, 1024), bf)],
-                         [(lambda: h.zero("red_e2", LR.STAT_SLOTS * 512, f32), lambda: h.stats("red_e2", 1, 256), red, red_abs)], "enc_fc1_dgrad " + tag)
-            h.put("a4", tern((B, 2, 2, 256)))
-            _forms_agree(h, "enc_fc1", [("y1", (rows, 400), bf), ("ay1", (rows, 400), bf)], [], "enc_fc1 " + tag)
+        # classifier.0's data gradient (its operands also set classifier.0's weight for the forward below)
+        acc, v, red, red_abs = _put_fc1_dgrad(h, B, seed)
+        _forms_agree(h, "enc_fc1_dgrad", [("db4", (rows, 1024), bf)],
+                     [(lambda: h.zero("red_e2", LR.STAT_SLOTS * 512, f32), lambda: h.stats("red_e2", 1, 256), red, red_abs)], "enc_fc1_dgrad " + tag)
+        h.put("a4", tern((B, 2, 2, 256)))
+        _forms_agree(h, "enc_fc1", [("y1", (rows, 400), bf), ("ay1", (rows, 400), bf)], [], "enc_fc1 " + tag)
 
-            de, r2, r1 = tern((rows, 2 * D)), LR.eighths((rows, 200), g), LR.eighths((rows, 400), g)
-            de_rows = torch.zeros(rows, (2 * D + 7) // 8 * 8, dtype=torch.float64)
-            de_rows[:, :2 * D] = de
-            h.put("d_encout", de_rows); h.put("y2", r2); h.put("y1", r1)
-            h.set_weight(pre + "6.bias", ibias(2 * D))
-            h.put("ay2", tern((rows, 200)))
-            _forms_agree(h, "enc_fc3", [("tmp_f32", (rows, 2 * D), f32)], [], "enc_fc3 " + tag)
-            v3 = (de @ W6) * LR.dswish(r2) * m2 * (1.0 / 0.9)
-            _forms_agree(h, "enc_fc3_dgrad", [("dy2", (rows, 200), bf)], [colsum(200) + (v3.sum(0), v3.abs().sum(0))], "enc_fc3_dgrad " + tag)
-            d2 = tern((rows, 200))
-            h.put("dy2", d2)
-            v2 = (d2 @ W3) * LR.dswish(r1) * m1 * (1.0 / 0.9)
-            _forms_agree(h, "enc_fc2_dgrad", [("dy1", (rows, 400), bf)], [colsum(400) + (v2.sum(0), v2.abs().sum(0))], "enc_fc2_dgrad " + tag)
+        de, r2, r1 = tern((rows, 2 * D)), LR.eighths((rows, 200), g), LR.eighths((rows, 400), g)
+        de_rows = torch.zeros(rows, (2 * D + 7) // 8 * 8, dtype=torch.float64)
+        de_rows[:, :2 * D] = de
+        h.put("d_encout", de_rows); h.put("y2", r2); h.put("y1", r1)
+        h.set_weight(pre + "6.bias", ibias(2 * D))
+        h.put("ay2", tern((rows, 200)))
+        _forms_agree(h, "enc_fc3", [("tmp_f32", (rows, 2 * D), f32)], [], "enc_fc3 " + tag)
+        v3 = (de @ W6) * LR.dswish(r2) * m2 * (1.0 / 0.9)
+        _forms_agree(h, "enc_fc3_dgrad", [("dy2", (rows, 200), bf)], [colsum(200) + (v3.sum(0), v3.abs().sum(0))], "enc_fc3_dgrad " + tag)
+        d2 = tern((rows, 200))
+        h.put("dy2", d2)
+        v2 = (d2 @ W3) * LR.dswish(r1) * m1 * (1.0 / 0.9)
+        _forms_agree(h, "enc_fc2_dgrad", [("dy1", (rows, 400), bf)], [colsum(400) + (v2.sum(0), v2.abs().sum(0))], "enc_fc2_dgrad " + tag)
 
-            ldz = (D + 1 + 7) // 8 * 8
-            z = torch.zeros(3 * B, ldz, dtype=torch.float64)
-            z[:, :D] = tern((3 * B, D))
-            z[:, D] = 1.0
-            h.put("z_bf", z)
-            _forms_agree(h, "dec_up", [("u", (3 * B, 1024), bf), ("au", (3 * B, 1024), bf)], [], "dec_up " + tag)
-            h.put("du", tern((rows, 2, 2, 256)))
-            _forms_agree(h, "dec_up_dgrad", [("tmp_f32", (rows, D), f32)], [], "dec_up_dgrad " + tag)
-    finally:
-        h.set_knobs(**{KNOB: KNOB_DEFAULT})
-        h.restore_knobs()
+        ldz = (D + 1 + 7) // 8 * 8
+        z = torch.zeros(3 * B, ldz, dtype=torch.float64)
+        z[:, :D] = tern((3 * B, D))
+        z[:, D] = 1.0
+        h.put("z_bf", z)
+        _forms_agree(h, "dec_up", [("u", (3 * B, 1024), bf), ("au", (3 * B, 1024), bf)], [], "dec_up " + tag)
+        h.put("du", tern((rows, 2, 2, 256)))
+        _forms_agree(h, "dec_up_dgrad", [("tmp_f32", (rows, D), f32)], [], "dec_up_dgrad " + tag)

@@ -20,7 +20,6 @@ import imageonly_mm_ref as IM
 pytestmark = pytest.mark.gpu
 
 IMG = ("image_encoder.", "image_decoder.")
-KNOB = b"mm_image_waist"
 
 
 def _dev():
@@ -47,19 +46,10 @@ def _numel(shape):
     return n
 
 
-class _knob:
-    """mm_image_waist for the length of a block: 1 / 0, and back to -1 (the size's default)"""
-
-    def __init__(self, value):
-        self.value = value
-
-    def __enter__(self):
-        from multimodal_vae_amd._lib import call
-        call("mmvae_debug_set", KNOB, self.value)
-
-    def __exit__(self, *exc):
-        from multimodal_vae_amd._lib import call
-        call("mmvae_debug_set", KNOB, -1)
+def _knob(value):
+    """mm_image_waist for the length of a block: 1 / 0, and back to the default (the size's own)"""
+    from multimodal_vae_amd._lib import knobs
+    return knobs(mm_image_waist=value)
 
 
 def _ws(eng, name, shape, dtype):

@@ -27,19 +27,10 @@ def _dev():
     return torch.device("cuda:0")
 
 
-class _strip:
+def _strip(v):
     """``with _strip(v):`` the switch "mnist_strip" at v, back at the library's default afterwards"""
-
-    def __init__(self, v):
-        self.v = v
-
-    def __enter__(self):
-        from multimodal_vae_amd._lib import call
-        call("mmvae_debug_set", b"mnist_strip", int(self.v))
-
-    def __exit__(self, *exc):
-        from multimodal_vae_amd._lib import call
-        call("mmvae_debug_set", b"mnist_strip", -1)
+    from multimodal_vae_amd._lib import knobs
+    return knobs(mnist_strip=v)
 
 
 def _numel(shape):

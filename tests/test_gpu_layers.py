@@ -55,14 +55,11 @@ def test_forward_exact(B, name):
     h = _harness(B)
     L = LAYERS[name]
     ws, xs = [], []
-    try:
-        for seed in SEEDS:
-            x, w, _ = LR.layer_operands(name, L.gf * B, seed)
-            _check_forward(h, name, x, w, (dict(convres=1), dict(convres=0)), "%s B=%d seed %d" % (name, B, seed))
-            ws.append(w)
-            xs.append(x)
-    finally:
-        h.restore_knobs()
+    for seed in SEEDS:
+        x, w, _ = LR.layer_operands(name, L.gf * B, seed)
+        _check_forward(h, name, x, w, (dict(convres=1), dict(convres=0)), "%s B=%d seed %d" % (name, B, seed))
+        ws.append(w)
+        xs.append(x)
     LR.assert_operand_coverage(ws, xs)
 
 
@@ -80,14 +77,11 @@ def test_weight_packing_one_hot(B, name):
     for s in shape:
         n *= s
     w = ((torch.arange(n, dtype=torch.int64) * 2654435761 >> 7) % 253 - 126).double().reshape(shape)
-    try:
-        for (im, y, xx, ch) in ((0, 0, 0, 0), (nimg - 1, L.ih - 1, L.ih - 1, L.cin - 1), (0, c, c, L.cin - 1), (nimg - 1, c, c, 0),
-                                (nimg // 2, 0, L.ih - 1, L.cin // 2)):
-            x = torch.zeros(nimg, L.ih, L.ih, L.cin, dtype=torch.float64)
-            x[im, y, xx, ch] = 1.0
-            _check_forward(h, name, x, w, (dict(convres=1), dict(convres=0)), "%s B=%d one-hot %s" % (name, B, (im, y, xx, ch)))
-    finally:
-        h.restore_knobs()
+    for (im, y, xx, ch) in ((0, 0, 0, 0), (nimg - 1, L.ih - 1, L.ih - 1, L.cin - 1), (0, c, c, L.cin - 1), (nimg - 1, c, c, 0),
+                            (nimg // 2, 0, L.ih - 1, L.cin // 2)):
+        x = torch.zeros(nimg, L.ih, L.ih, L.cin, dtype=torch.float64)
+        x[im, y, xx, ch] = 1.0
+        _check_forward(h, name, x, w, (dict(convres=1), dict(convres=0)), "%s B=%d one-hot %s" % (name, B, (im, y, xx, ch)))
 
 
 # ------------------------------------------------------------------------------------------------ Tier A: weight gradients
@@ -103,14 +97,11 @@ _check_wgrad = LR.check_wgrad
 def test_wgrad_exact(B, name):
     h = _harness(B)
     L = LAYERS[name]
-    try:
-        for seed in SEEDS:
-            x, _, dy = LR.layer_operands(name, L.gb * B, seed)
-            h.put(L.x, x)
-            h.put(L.dy, dy)
-            _check_wgrad(h, name + "_wgrad", L.param, LR.ref_wgrad(L, x, dy), WG_KNOBS, "%s_wgrad B=%d seed %d" % (name, B, seed))
-    finally:
-        h.restore_knobs()
+    for seed in SEEDS:
+        x, _, dy = LR.layer_operands(name, L.gb * B, seed)
+        h.put(L.x, x)
+        h.put(L.dy, dy)
+        _check_wgrad(h, name + "_wgrad", L.param, LR.ref_wgrad(L, x, dy), WG_KNOBS, "%s_wgrad B=%d seed %d" % (name, B, seed))
 
 
 def _patches(img, g):
@@ -125,38 +116,35 @@ def test_thin_layers_exact(B):
     conv2d / conv_transpose2d of multimnist/model.py:160,208 on that image."""
     h = _harness(B)
     f0, f9 = "image_encoder.features.0.weight", "image_decoder.hallucinate.9.weight"
-    try:
-        for seed in SEEDS:
-            g = LR.gen(seed, 9, B)
-            img = LR.ternary((B, 1, 50, 50), 0.5, g)
-            w0 = LR.ternary((32, 1, 4, 4), 0.5, g)
-            d1 = LR.ternary((B, 25, 25, 32), 0.5, g)
-            h.put("patches1", _patches(img, B))
-            # forward: r1 = conv2d(image, w0, stride 2, padding 1)
-            ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
-            LR.assert_exact_regime(out=ref, what="enc_conv1")
-            h.set_weight(f0, w0)
-            h.zero("r1", ref.numel(), torch.bfloat16)
-            launches = h.run("enc_conv1")
-            got = h.get("r1", ref.shape).double().cpu()
-            assert torch.equal(got, ref), (B, seed, launches, LR.describe_mismatch(got, ref))
-            # its Swish copy a1 (the epilogue's second output): Tier B
-            _gated(h.get("a1", ref.shape), ref * torch.sigmoid(ref), ref, "enc_conv1 a1 B=%d seed %d" % (B, seed))
-            # weight gradient of the same layer from d1e
-            wz = torch.zeros(32, 1, 4, 4, dtype=torch.float64, requires_grad=True)
-            F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
-            h.put("d1e", d1)
-            _check_wgrad(h, "enc_conv1_wgrad", f0, wz.grad, WG_KNOBS[:1] + WG_KNOBS[-1:], "enc_conv1_wgrad B=%d seed %d" % (B, seed))
-            # last transposed conv (32 -> 1 channel): dW from its activated input aq3 and im2col(dlogit), 2 passes
-            dl = LR.ternary((2 * B, 1, 50, 50), 0.5, g)
-            a3 = LR.ternary((2 * B, 25, 25, 32), 0.5, g)
-            w9 = torch.zeros(32, 1, 4, 4, dtype=torch.float64, requires_grad=True)
-            F.conv_transpose2d(LR._nchw(a3), w9, None, 2, 1).backward(dl)
-            h.put("patches4", _patches(dl, 2 * B))
-            h.put("aq3", a3)
-            _check_wgrad(h, "dec_last_wgrad", f9, w9.grad, WG_KNOBS[:1] + WG_KNOBS[-1:], "dec_last_wgrad B=%d seed %d" % (B, seed))
-    finally:
-        h.restore_knobs()
+    for seed in SEEDS:
+        g = LR.gen(seed, 9, B)
+        img = LR.ternary((B, 1, 50, 50), 0.5, g)
+        w0 = LR.ternary((32, 1, 4, 4), 0.5, g)
+        d1 = LR.ternary((B, 25, 25, 32), 0.5, g)
+        h.put("patches1", _patches(img, B))
+        # forward: r1 = conv2d(image, w0, stride 2, padding 1)
+        ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
+        LR.assert_exact_regime(out=ref, what="enc_conv1")
+        h.set_weight(f0, w0)
+        h.zero("r1", ref.numel(), torch.bfloat16)
+        launches = h.run("enc_conv1")
+        got = h.get("r1", ref.shape).double().cpu()
+        assert torch.equal(got, ref), (B, seed, launches, LR.describe_mismatch(got, ref))
+        # its Swish copy a1 (the epilogue's second output): Tier B
+        _gated(h.get("a1", ref.shape), ref * torch.sigmoid(ref), ref, "enc_conv1 a1 B=%d seed %d" % (B, seed))
+        # weight gradient of the same layer from d1e
+        wz = torch.zeros(32, 1, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
+        h.put("d1e", d1)
+        _check_wgrad(h, "enc_conv1_wgrad", f0, wz.grad, WG_KNOBS[:1] + WG_KNOBS[-1:], "enc_conv1_wgrad B=%d seed %d" % (B, seed))
+        # last transposed conv (32 -> 1 channel): dW from its activated input aq3 and im2col(dlogit), 2 passes
+        dl = LR.ternary((2 * B, 1, 50, 50), 0.5, g)
+        a3 = LR.ternary((2 * B, 25, 25, 32), 0.5, g)
+        w9 = torch.zeros(32, 1, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv_transpose2d(LR._nchw(a3), w9, None, 2, 1).backward(dl)
+        h.put("patches4", _patches(dl, 2 * B))
+        h.put("aq3", a3)
+        _check_wgrad(h, "dec_last_wgrad", f9, w9.grad, WG_KNOBS[:1] + WG_KNOBS[-1:], "dec_last_wgrad B=%d seed %d" % (B, seed))
 
 
 # ------------------------------------------------------------------------------------------------ Tier B: data gradients
@@ -170,12 +158,9 @@ def _check_dgrad(h, name, dy, w, seed, knob_sets, what):
 def test_dgrad_epilogue(B, name):
     h = _harness(B)
     L = LAYERS[name]
-    try:
-        for seed in SEEDS:
-            _, w, dy = LR.layer_operands(name, L.gb * B, seed)
-            _check_dgrad(h, name, dy, w, seed, (dict(convres=1), dict(convres=0)), "%s_dgrad B=%d seed %d" % (name, B, seed))
-    finally:
-        h.restore_knobs()
+    for seed in SEEDS:
+        _, w, dy = LR.layer_operands(name, L.gb * B, seed)
+        _check_dgrad(h, name, dy, w, seed, (dict(convres=1), dict(convres=0)), "%s_dgrad B=%d seed %d" % (name, B, seed))
 
 
 # ------------------------------------------------------------------------------------------------ Tier B: dense layers
@@ -214,85 +199,82 @@ def test_dense_layers(B, D):
     h = _harness(B, D)
     rows = 2 * B
     pre, up = "image_encoder.classifier.", "image_decoder.upsample.0."
-    try:
-        for seed in SEEDS:
-            g = LR.gen(seed, 11, B) if D == 100 else LR.gen(seed, 11, B, D)
-            tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
-            ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
-            keep = lambda shape: (torch.rand(shape, generator=g) < 0.9).to(torch.uint8)
-            W1, W3, W6, Wu = tern((400, 1024), 0.25), tern((200, 400), 0.25), tern((2 * D, 200), 0.25), tern((1024, D), 0.25)
-            b1, b3, b6, bu = ibias(400), ibias(200), ibias(2 * D), ibias(1024)
-            for n, t in ((pre + "0.weight", W1), (pre + "0.bias", b1), (pre + "3.weight", W3), (pre + "3.bias", b3),
-                         (pre + "6.weight", W6), (pre + "6.bias", b6), (up + "weight", Wu), (up + "bias", bu)):
-                h.set_weight(n, t)
-            m1, m2 = keep((rows, 400)), keep((rows, 200))
-            h.put("m1", m1, torch.uint8)
-            h.put("m2", m2, torch.uint8)
-            tag = "B=%d D=%d seed %d" % (B, D, seed)
+    for seed in SEEDS:
+        g = LR.gen(seed, 11, B) if D == 100 else LR.gen(seed, 11, B, D)
+        tern = lambda shape, d=0.5: LR.ternary(shape, d, g)
+        ibias = lambda n: torch.randint(-2, 3, (n,), generator=g).double()
+        keep = lambda shape: (torch.rand(shape, generator=g) < 0.9).to(torch.uint8)
+        W1, W3, W6, Wu = tern((400, 1024), 0.25), tern((200, 400), 0.25), tern((2 * D, 200), 0.25), tern((1024, D), 0.25)
+        b1, b3, b6, bu = ibias(400), ibias(200), ibias(2 * D), ibias(1024)
+        for n, t in ((pre + "0.weight", W1), (pre + "0.bias", b1), (pre + "3.weight", W3), (pre + "3.bias", b3),
+                     (pre + "6.weight", W6), (pre + "6.bias", b6), (up + "weight", Wu), (up + "bias", bu)):
+            h.set_weight(n, t)
+        m1, m2 = keep((rows, 400)), keep((rows, 200))
+        h.put("m1", m1, torch.uint8)
+        h.put("m2", m2, torch.uint8)
+        tag = "B=%d D=%d seed %d" % (B, D, seed)
 
-            # classifier.0 on the NHWC 2x2x256 map shared by both dropout variants (row r reads image r % B); torch flattens NCHW
-            a4 = tern((B, 2, 2, 256))
-            h.put("a4", a4)
-            y1 = F.linear(LR._nchw(a4).reshape(B, 1024).repeat(2, 1), W1, b1)
-            h.zero("y1", rows * 400, torch.bfloat16); h.zero("ay1", rows * 400, torch.bfloat16)
-            h.run("enc_fc1")
-            _exact(h.get("y1", (rows, 400)), y1, "enc_fc1 y1 " + tag)
-            _gated(h.get("ay1", (rows, 400)), _swish(y1) * m1 * DROP_SCALE, y1, "enc_fc1 ay1 " + tag)
+        # classifier.0 on the NHWC 2x2x256 map shared by both dropout variants (row r reads image r % B); torch flattens NCHW
+        a4 = tern((B, 2, 2, 256))
+        h.put("a4", a4)
+        y1 = F.linear(LR._nchw(a4).reshape(B, 1024).repeat(2, 1), W1, b1)
+        h.zero("y1", rows * 400, torch.bfloat16); h.zero("ay1", rows * 400, torch.bfloat16)
+        h.run("enc_fc1")
+        _exact(h.get("y1", (rows, 400)), y1, "enc_fc1 y1 " + tag)
+        _gated(h.get("ay1", (rows, 400)), _swish(y1) * m1 * DROP_SCALE, y1, "enc_fc1 ay1 " + tag)
 
-            x1 = tern((rows, 400))
-            h.put("ay1", x1)
-            y2 = F.linear(x1, W3, b3)
-            h.zero("y2", rows * 200, torch.bfloat16); h.zero("ay2", rows * 200, torch.bfloat16)
-            h.run("enc_fc2")
-            _exact(h.get("y2", (rows, 200)), y2, "enc_fc2 y2 " + tag)
-            _gated(h.get("ay2", (rows, 200)), _swish(y2) * m2 * DROP_SCALE, y2, "enc_fc2 ay2 " + tag)
+        x1 = tern((rows, 400))
+        h.put("ay1", x1)
+        y2 = F.linear(x1, W3, b3)
+        h.zero("y2", rows * 200, torch.bfloat16); h.zero("ay2", rows * 200, torch.bfloat16)
+        h.run("enc_fc2")
+        _exact(h.get("y2", (rows, 200)), y2, "enc_fc2 y2 " + tag)
+        _gated(h.get("ay2", (rows, 200)), _swish(y2) * m2 * DROP_SCALE, y2, "enc_fc2 ay2 " + tag)
 
-            x2 = tern((rows, 200))
-            h.put("ay2", x2)
-            h.zero("tmp_f32", rows * 2 * D, torch.float32)
-            h.run("enc_fc3")
-            _exact(h.get("tmp_f32", (rows, 2 * D), torch.float32), F.linear(x2, W6, b6), "enc_fc3 " + tag)
+        x2 = tern((rows, 200))
+        h.put("ay2", x2)
+        h.zero("tmp_f32", rows * 2 * D, torch.float32)
+        h.run("enc_fc3")
+        _exact(h.get("tmp_f32", (rows, 2 * D), torch.float32), F.linear(x2, W6, b6), "enc_fc3 " + tag)
 
-            # data gradients: dy2 = (d_encout W6) * Swish'(y2) * keep2 / 0.9, dy1 = (dy2 W3) * Swish'(y1) * keep1 / 0.9
-            # (d_encout rows are round_up(2D, 8) wide with zero pad columns: the stride the step's latent backward writes)
-            de, r2, r1 = tern((rows, 2 * D)), LR.eighths((rows, 200), g), LR.eighths((rows, 400), g)
-            de_rows = torch.zeros(rows, (2 * D + 7) // 8 * 8, dtype=torch.float64)
-            de_rows[:, :2 * D] = de
-            h.put("d_encout", de_rows); h.put("y2", r2); h.put("y1", r1)
-            acc = de @ W6
-            v = acc * LR.dswish(r2) * m2 * DROP_SCALE
-            h.zero("dy2", rows * 200, torch.bfloat16); h.zero("tmp_f32", 200, torch.float32)
-            h.run("enc_fc3_dgrad")
-            _gated(h.get("dy2", (rows, 200)), v, acc, "enc_fc3_dgrad " + tag)
-            _colsum_gate(h, 200, v, "enc_fc3_dgrad " + tag)
-            d2 = tern((rows, 200))
-            h.put("dy2", d2)
-            acc = d2 @ W3
-            v = acc * LR.dswish(r1) * m1 * DROP_SCALE
-            h.zero("dy1", rows * 400, torch.bfloat16); h.zero("tmp_f32", 400, torch.float32)
-            h.run("enc_fc2_dgrad")
-            _gated(h.get("dy1", (rows, 400)), v, acc, "enc_fc2_dgrad " + tag)
-            _colsum_gate(h, 400, v, "enc_fc2_dgrad " + tag)
+        # data gradients: dy2 = (d_encout W6) * Swish'(y2) * keep2 / 0.9, dy1 = (dy2 W3) * Swish'(y1) * keep1 / 0.9
+        # (d_encout rows are round_up(2D, 8) wide with zero pad columns: the stride the step's latent backward writes)
+        de, r2, r1 = tern((rows, 2 * D)), LR.eighths((rows, 200), g), LR.eighths((rows, 400), g)
+        de_rows = torch.zeros(rows, (2 * D + 7) // 8 * 8, dtype=torch.float64)
+        de_rows[:, :2 * D] = de
+        h.put("d_encout", de_rows); h.put("y2", r2); h.put("y1", r1)
+        acc = de @ W6
+        v = acc * LR.dswish(r2) * m2 * DROP_SCALE
+        h.zero("dy2", rows * 200, torch.bfloat16); h.zero("tmp_f32", 200, torch.float32)
+        h.run("enc_fc3_dgrad")
+        _gated(h.get("dy2", (rows, 200)), v, acc, "enc_fc3_dgrad " + tag)
+        _colsum_gate(h, 200, v, "enc_fc3_dgrad " + tag)
+        d2 = tern((rows, 200))
+        h.put("dy2", d2)
+        acc = d2 @ W3
+        v = acc * LR.dswish(r1) * m1 * DROP_SCALE
+        h.zero("dy1", rows * 400, torch.bfloat16); h.zero("tmp_f32", 400, torch.float32)
+        h.run("enc_fc2_dgrad")
+        _gated(h.get("dy1", (rows, 400)), v, acc, "enc_fc2_dgrad " + tag)
+        _colsum_gate(h, 400, v, "enc_fc2_dgrad " + tag)
 
-            # upsample: z rows carry a 1.0 in column D (the bias rides in the packed weights); the output is the NHWC 2x2x256 map
-            # of torch's view(-1, 256, 2, 2)
-            ldz = (D + 1 + 7) // 8 * 8
-            z = torch.zeros(3 * B, ldz, dtype=torch.float64)
-            z[:, :D] = tern((3 * B, D))
-            z[:, D] = 1.0
-            h.put("z_bf", z)
-            u = LR._nhwc(F.linear(z[:, :D], Wu, bu).reshape(3 * B, 256, 2, 2)).reshape(3 * B, 1024)
-            h.zero("u", 3 * B * 1024, torch.bfloat16); h.zero("au", 3 * B * 1024, torch.bfloat16)
-            h.run("dec_up")
-            _exact(h.get("u", (3 * B, 1024)), u, "dec_up u " + tag)
-            _gated(h.get("au", (3 * B, 1024)), _swish(u), u, "dec_up au " + tag)
-            du = tern((rows, 2, 2, 256))
-            h.put("du", du)
-            h.zero("tmp_f32", rows * D, torch.float32)
-            h.run("dec_up_dgrad")
-            _exact(h.get("tmp_f32", (rows, D), torch.float32), LR._nchw(du).reshape(rows, 1024) @ Wu, "dec_up_dgrad " + tag)
-    finally:
-        h.restore_knobs()
+        # upsample: z rows carry a 1.0 in column D (the bias rides in the packed weights); the output is the NHWC 2x2x256 map
+        # of torch's view(-1, 256, 2, 2)
+        ldz = (D + 1 + 7) // 8 * 8
+        z = torch.zeros(3 * B, ldz, dtype=torch.float64)
+        z[:, :D] = tern((3 * B, D))
+        z[:, D] = 1.0
+        h.put("z_bf", z)
+        u = LR._nhwc(F.linear(z[:, :D], Wu, bu).reshape(3 * B, 256, 2, 2)).reshape(3 * B, 1024)
+        h.zero("u", 3 * B * 1024, torch.bfloat16); h.zero("au", 3 * B * 1024, torch.bfloat16)
+        h.run("dec_up")
+        _exact(h.get("u", (3 * B, 1024)), u, "dec_up u " + tag)
+        _gated(h.get("au", (3 * B, 1024)), _swish(u), u, "dec_up au " + tag)
+        du = tern((rows, 2, 2, 256))
+        h.put("du", du)
+        h.zero("tmp_f32", rows * D, torch.float32)
+        h.run("dec_up_dgrad")
+        _exact(h.get("tmp_f32", (rows, D), torch.float32), LR._nchw(du).reshape(rows, 1024) @ Wu, "dec_up_dgrad " + tag)
 
 
 @pytest.mark.parametrize("B", BATCHES)
@@ -300,30 +282,27 @@ def test_last_layer_dgrad(B):
     """dec_last_dgrad_gemm: the input gradient of the 32 -> 1 channel transposed conv (multimnist/model.py:208) as a dense GEMM over
     im2col(dlogit), with the Swish' / BatchNorm-backward epilogue of the layer below (hallucinate.7), 2 passes."""
     h = _harness(B)
-    try:
-        for seed in SEEDS:
-            g = LR.gen(seed, 12, B)
-            dl = LR.ternary((2 * B, 1, 50, 50), 0.5, g)
-            w9 = LR.ternary((32, 1, 4, 4), 0.5, g)
-            x = torch.zeros(2 * B, 32, 25, 25, dtype=torch.float64, requires_grad=True)
-            F.conv_transpose2d(x, w9, None, 2, 1).backward(dl)
-            acc = LR._nhwc(x.grad)
-            r = LR.eighths(acc.shape, g)
-            aff, mr = LR.dyadic_tables(2, 32, g)
-            v, red, red_abs = LR.ref_dgrad_epilogue(acc, r, aff, mr, 2)
-            h.set_weight("image_decoder.hallucinate.9.weight", w9)
-            h.put("patches4", _patches(dl, 2 * B))
-            h.put("q3", r)
-            h.put("aff_d2", aff, torch.float32)
-            h.put("mr_d2", mr, torch.float32)
-            h.zero("d3", acc.numel(), torch.bfloat16)
-            h.zero("red_d2", 2 * LR.STAT_SLOTS * 32 * 2, torch.float32)
-            h.run("dec_last_dgrad_gemm")
-            what = "dec_last_dgrad_gemm B=%d seed %d" % (B, seed)
-            _gated(h.get("d3", acc.shape), v, acc, what)
-            LR.gate_sums(h.stats("red_d2", 2, 32), red, red_abs, what + " d_red")
-    finally:
-        h.restore_knobs()
+    for seed in SEEDS:
+        g = LR.gen(seed, 12, B)
+        dl = LR.ternary((2 * B, 1, 50, 50), 0.5, g)
+        w9 = LR.ternary((32, 1, 4, 4), 0.5, g)
+        x = torch.zeros(2 * B, 32, 25, 25, dtype=torch.float64, requires_grad=True)
+        F.conv_transpose2d(x, w9, None, 2, 1).backward(dl)
+        acc = LR._nhwc(x.grad)
+        r = LR.eighths(acc.shape, g)
+        aff, mr = LR.dyadic_tables(2, 32, g)
+        v, red, red_abs = LR.ref_dgrad_epilogue(acc, r, aff, mr, 2)
+        h.set_weight("image_decoder.hallucinate.9.weight", w9)
+        h.put("patches4", _patches(dl, 2 * B))
+        h.put("q3", r)
+        h.put("aff_d2", aff, torch.float32)
+        h.put("mr_d2", mr, torch.float32)
+        h.zero("d3", acc.numel(), torch.bfloat16)
+        h.zero("red_d2", 2 * LR.STAT_SLOTS * 32 * 2, torch.float32)
+        h.run("dec_last_dgrad_gemm")
+        what = "dec_last_dgrad_gemm B=%d seed %d" % (B, seed)
+        _gated(h.get("d3", acc.shape), v, acc, what)
+        LR.gate_sums(h.stats("red_d2", 2, 32), red, red_abs, what + " d_red")
 
 
 # ------------------------------------------------------------------------------------------------ measurement-aid forms
@@ -341,15 +320,12 @@ def test_convres_alt_forms(alt):
     B, seed = 256, 0
     h = _harness(B)
     fwd, dgr = ALT_FORMS[alt]
-    try:
-        for name in fwd:
-            x, w, _ = LR.layer_operands(name, LAYERS[name].gf * B, seed)
-            _check_forward(h, name, x, w, (dict(convres=1, convres_alt=alt),), "%s B=%d alt %d" % (name, B, alt))
-        for name in dgr:
-            _, w, dy = LR.layer_operands(name, LAYERS[name].gb * B, seed)
-            _check_dgrad(h, name, dy, w, seed, (dict(convres=1, convres_alt=alt),), "%s_dgrad B=%d alt %d" % (name, B, alt))
-    finally:
-        h.restore_knobs()
+    for name in fwd:
+        x, w, _ = LR.layer_operands(name, LAYERS[name].gf * B, seed)
+        _check_forward(h, name, x, w, (dict(convres=1, convres_alt=alt),), "%s B=%d alt %d" % (name, B, alt))
+    for name in dgr:
+        _, w, dy = LR.layer_operands(name, LAYERS[name].gb * B, seed)
+        _check_dgrad(h, name, dy, w, seed, (dict(convres=1, convres_alt=alt),), "%s_dgrad B=%d alt %d" % (name, B, alt))
 
 
 # ------------------------------------------------------------------------------------------------ which kernels ran

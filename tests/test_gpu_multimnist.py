@@ -336,7 +336,7 @@ def test_step_prologue_refreshes_every_weight_copy(staged):
     after a step the whole packed buffer must equal a full pack of the parameters the step started from, bit for bit."""
     from multimodal_vae_amd.core import FusedELBOStep, MultimnistState
     from multimodal_vae_amd.init import default_init_
-    from multimodal_vae_amd._lib import call
+    from multimodal_vae_amd._lib import knobs
     dev = _dev()
     B = 16
     rng = np.random.default_rng(3)
@@ -344,8 +344,7 @@ def test_step_prologue_refreshes_every_weight_copy(staged):
     txt = torch.from_numpy(rng.integers(0, 10, size=(B, 4)).astype(np.int64)).to(dev)
     st = MultimnistState(D, dev); default_init_(st, 21)
     eng = FusedELBOStep(st, B, lr=1e-2)           # a large step: every weight moves by more than a bf16 ulp
-    call("mmvae_debug_set", b"mm_stage_begin", staged)
-    try:
+    with knobs(mm_stage_begin=staged):
         eng(img, txt)
         for _ in range(2):
             assert st.pack_pending
@@ -363,8 +362,6 @@ def test_step_prologue_refreshes_every_weight_copy(staged):
             st.params.copy_(p_end); st.pack_weights(); torch.cuda.synchronize()      # and it is not the pack of the NEW parameters
             assert not torch.equal(st.packed.view(torch.int16), got.view(torch.int16))
             st.pack_pending = True
-    finally:
-        call("mmvae_debug_set", b"mm_stage_begin", 1)
 
 
 def test_early_optimizer_part_equals_one_adam_launch():

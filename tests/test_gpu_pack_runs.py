@@ -32,11 +32,6 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _knob(name, value):
-    from multimodal_vae_amd._lib import call
-    call("mmvae_debug_set", name, int(value))
-
-
 def _tricky_params(st, seed):
     """random weights; a third sit on a bf16 rounding tie (low 16 bits 0x8000), some are +0 / -0"""
     g = torch.Generator().manual_seed(seed)
@@ -56,14 +51,12 @@ def _mark(st):
 
 def _pack(st, h, runs):
     """one full pack through the family's own entry point, on the plan h, under pack_runs = runs"""
+    from multimodal_vae_amd._lib import knobs
     from multimodal_vae_amd.core import _stream
-    _knob(b"pack_runs", runs)
-    try:
+    with knobs(pack_runs=runs):
         _mark(st)
         st._c("pack_weights", h, _stream())
         torch.cuda.synchronize()
-    finally:
-        _knob(b"pack_runs", 1)
     return st.packed.view(torch.int16).clone(), st.packed_vec.view(torch.int32).clone()
 
 
@@ -107,6 +100,7 @@ def _stage_launch(st, h, stage):
 
 @pytest.mark.parametrize("runs", [1, 0])
 def test_each_stage_launch_packs_its_own_descriptors_only(runs):
+    from multimodal_vae_amd._lib import knobs
     from multimodal_vae_amd.core import MultimnistState
     dev = _dev()
     st = MultimnistState(100, dev)
@@ -121,8 +115,7 @@ def test_each_stage_launch_packs_its_own_descriptors_only(runs):
         owner[int(d["dst_off"]):int(d["dst_off"]) + int(d["Npad"]) * int(d["Kpad"])] = int(d["part"])
     assert int((owner < 0).sum()) == 0
     owner = owner.to(dev)
-    _knob(b"pack_runs", runs)
-    try:
+    with knobs(pack_runs=runs):
         for stage in (0, 1, 2, -1):
             _mark(st)
             blocks = _stage_launch(st, h, stage)
@@ -131,12 +124,11 @@ def test_each_stage_launch_packs_its_own_descriptors_only(runs):
             assert blocks == int(nblk[desc["part"] == stage].sum() if stage >= 0 else nblk.sum())     # no workgroup of another stage
             assert torch.equal(got[mine], ref[mine]), stage
             assert bool((got[~mine] == MARK).all()), stage
-    finally:
-        _knob(b"pack_runs", 1)
 
 
 @pytest.mark.parametrize("staged", [1, 0])
 def test_step_with_pack_first_refreshes_the_whole_buffer(staged):
+    from multimodal_vae_amd._lib import knobs
     from multimodal_vae_amd.core import FusedELBOStep, MultimnistState
     from multimodal_vae_amd.init import default_init_
     dev = _dev()
@@ -146,8 +138,7 @@ def test_step_with_pack_first_refreshes_the_whole_buffer(staged):
     txt = torch.from_numpy(rng.integers(0, 10, size=(B, 4)).astype(np.int64)).to(dev)
     st = MultimnistState(100, dev); default_init_(st, 21)
     eng = FusedELBOStep(st, B, lr=1e-2)
-    _knob(b"mm_stage_begin", staged)
-    try:
+    with knobs(mm_stage_begin=staged):
         eng(img, txt)
         assert st.pack_pending
         p_start = st.params.clone()
@@ -160,8 +151,6 @@ def test_step_with_pack_first_refreshes_the_whole_buffer(staged):
         ref, _ = _pack(st, st.plan(B), 0)
         st.params.copy_(p_end); st.pack_pending = True
         assert torch.equal(got, ref), int((got != ref).sum())
-    finally:
-        _knob(b"mm_stage_begin", 1)
 
 
 def test_graph_replay_matches_eager_steps():

@@ -82,17 +82,9 @@ def _full(enc, dec, inp, dev):
     return dict(words=words.detach(), tokens=toks, encout=out.detach(), dz=z.grad.detach(), grads=grads)
 
 
-class _knob:
-    def __init__(self, value):
-        self.value = value
-
-    def __enter__(self):
-        from multimodal_vae_amd._lib import call
-        call("mmvae_debug_set", b"text_fwd2", self.value)
-
-    def __exit__(self, *a):
-        from multimodal_vae_amd._lib import call
-        call("mmvae_debug_set", b"text_fwd2", 1)          # the library's default (csrc/text.hip launch_text_decoder_fwd)
+def _knob(value):
+    from multimodal_vae_amd._lib import knobs
+    return knobs(text_fwd2=value)
 
 
 @pytest.mark.parametrize("D,fwd2", CASES, ids=IDS)

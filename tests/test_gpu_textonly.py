@@ -17,12 +17,12 @@ import torch
 from oracle import mmvae_ref as R
 import coco_text_ref as CT
 import textonly_ref as TR
+from multimodal_vae_amd._lib import knobs as _knobs
 
 pytestmark = pytest.mark.gpu
 
 IMG = ("image_encoder.", "image_decoder.")
 STILL = "text_encoder.gru.weight_hh_l0_reverse"     # zero gradient in the model itself: one step from h = 0
-KNOB_DEFAULTS = dict(coco_cluster=8, coco_enc_streamed=0, coco_no_mse_fuse=0, coco_module_bf16=0)
 
 
 def _dev():
@@ -47,24 +47,6 @@ def _state(D, T, dev):
     for n, shape, off in st.table:
         st.params[off:off + P[n].numel()] = P[n].detach().reshape(-1).to(dev)
     return st
-
-
-class _knobs:
-    """sets A/B knobs (mmvae_debug_set) and puts every one of them back"""
-
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        from multimodal_vae_amd._lib import call
-        for k, v in self.kw.items():
-            assert k in KNOB_DEFAULTS, k
-            call("mmvae_debug_set", k.encode(), int(v))
-
-    def __exit__(self, *exc):
-        from multimodal_vae_amd._lib import call
-        for k in self.kw:
-            call("mmvae_debug_set", k.encode(), KNOB_DEFAULTS[k])
 
 
 # ====================================================================================================== latent1_bwd_f32 alone

@@ -74,24 +74,21 @@ def test_conv1_forward_exact(B):
     """r1 = conv2d(image, w0, stride 2, padding 1) bit for bit on a ternary image and integer weights; a1 within one bf16 ulp of
     Swish(r1).  The image batch is read as fp32 from tmp_f32."""
     h = _harness(B)
-    try:
-        for seed in SEEDS:
-            g = LR.gen(seed, 31, B)
-            img = LR.ternary((B, 1, 50, 50), 0.5, g)
-            w0 = torch.randint(-3, 4, (32, 1, 4, 4), generator=g).double()
-            ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
-            LR.assert_exact_regime(out=ref, what="enc_conv1_mfma")
-            h.set_weight(F0, w0)
-            h.put("tmp_f32", img, torch.float32)
-            h.zero("r1", ref.numel(), torch.bfloat16)
-            h.zero("a1", ref.numel(), torch.bfloat16)
-            launches = h.run("enc_conv1_mfma")
-            assert any("conv1_fwd_half_kernel" in k for _, k in launches), launches
-            got = h.get("r1", ref.shape).double().cpu()
-            assert torch.equal(got, ref), (B, seed, launches, LR.describe_mismatch(got, ref))
-            LR.gate_elements(h.get("a1", ref.shape), ref * torch.sigmoid(ref), ref, "enc_conv1_mfma a1 B=%d seed %d" % (B, seed))
-    finally:
-        h.restore_knobs()
+    for seed in SEEDS:
+        g = LR.gen(seed, 31, B)
+        img = LR.ternary((B, 1, 50, 50), 0.5, g)
+        w0 = torch.randint(-3, 4, (32, 1, 4, 4), generator=g).double()
+        ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
+        LR.assert_exact_regime(out=ref, what="enc_conv1_mfma")
+        h.set_weight(F0, w0)
+        h.put("tmp_f32", img, torch.float32)
+        h.zero("r1", ref.numel(), torch.bfloat16)
+        h.zero("a1", ref.numel(), torch.bfloat16)
+        launches = h.run("enc_conv1_mfma")
+        assert any("conv1_fwd_half_kernel" in k for _, k in launches), launches
+        got = h.get("r1", ref.shape).double().cpu()
+        assert torch.equal(got, ref), (B, seed, launches, LR.describe_mismatch(got, ref))
+        LR.gate_elements(h.get("a1", ref.shape), ref * torch.sigmoid(ref), ref, "enc_conv1_mfma a1 B=%d seed %d" % (B, seed))
 
 
 @pytest.mark.parametrize("B", BATCHES)
@@ -100,20 +97,17 @@ def test_conv1_forward_one_hot(B):
     corners, distinct integer weights: every output pixel carries the tap the geometry says"""
     h = _harness(B)
     w0 = ((torch.arange(512, dtype=torch.int64) * 2654435761 >> 7) % 253 - 126).double().reshape(32, 1, 4, 4)
-    try:
-        h.set_weight(F0, w0)
-        for (im, y, x) in ((0, 0, 0), (B - 1, 49, 49), (0, 49, 0), (B - 1, 0, 49), (0, 22, 10), (B - 1, 23, 40), (B // 2, 24, 39), (0, 25, 41),
-                           (B - 1, 26, 0), (0, 27, 49)):
-            img = torch.zeros(B, 1, 50, 50, dtype=torch.float64)
-            img[im, 0, y, x] = 1.0
-            ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
-            h.put("tmp_f32", img, torch.float32)
-            h.zero("r1", ref.numel(), torch.bfloat16)
-            h.run("enc_conv1_mfma")
-            got = h.get("r1", ref.shape).double().cpu()
-            assert torch.equal(got, ref), (B, (im, y, x), LR.describe_mismatch(got, ref))
-    finally:
-        h.restore_knobs()
+    h.set_weight(F0, w0)
+    for (im, y, x) in ((0, 0, 0), (B - 1, 49, 49), (0, 49, 0), (B - 1, 0, 49), (0, 22, 10), (B - 1, 23, 40), (B // 2, 24, 39), (0, 25, 41),
+                       (B - 1, 26, 0), (0, 27, 49)):
+        img = torch.zeros(B, 1, 50, 50, dtype=torch.float64)
+        img[im, 0, y, x] = 1.0
+        ref = LR._nhwc(F.conv2d(img, w0, None, 2, 1))
+        h.put("tmp_f32", img, torch.float32)
+        h.zero("r1", ref.numel(), torch.bfloat16)
+        h.run("enc_conv1_mfma")
+        got = h.get("r1", ref.shape).double().cpu()
+        assert torch.equal(got, ref), (B, (im, y, x), LR.describe_mismatch(got, ref))
 
 
 @pytest.mark.parametrize("B", BATCHES)
@@ -121,30 +115,27 @@ def test_conv1_wgrad_exact(B):
     """the in-step weight gradient of conv1 (float atomics into the packed gradient): ternary image and gradient, then one-hot
     gradient pixels at output rows 11, 12, 13 and the corners on a dense image of small integers"""
     h = _harness(B)
-    try:
-        for seed in SEEDS:
-            g = LR.gen(seed, 32, B)
-            img = LR.ternary((B, 1, 50, 50), 0.5, g)
-            d1 = LR.ternary((B, 25, 25, 32), 0.5, g)
-            wz = torch.zeros(32, 1, 4, 4, dtype=torch.float64, requires_grad=True)
-            F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
-            h.put("tmp_f32", img, torch.float32)
-            h.put("d1e", d1)
-            LR.check_wgrad(h, "enc_conv1_wgrad_mfma", F0, wz.grad, ({},), "enc_conv1_wgrad_mfma B=%d seed %d" % (B, seed))
-        g = LR.gen(0, 33, B)
-        img = torch.randint(-3, 4, (B, 1, 50, 50), generator=g).double()
+    for seed in SEEDS:
+        g = LR.gen(seed, 32, B)
+        img = LR.ternary((B, 1, 50, 50), 0.5, g)
+        d1 = LR.ternary((B, 25, 25, 32), 0.5, g)
+        wz = torch.zeros(32, 1, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
         h.put("tmp_f32", img, torch.float32)
-        for (im, oy, ox, ch) in ((0, 0, 0, 0), (B - 1, 24, 24, 31), (0, 11, 3, 5), (B - 1, 12, 19, 7), (0, 12, 20, 9), (B // 2, 13, 24, 30), (0, 24, 0, 16)):
-            d1 = torch.zeros(B, 25, 25, 32, dtype=torch.float64)
-            d1[im, oy, ox, ch] = 1.0
-            wz = torch.zeros(32, 1, 4, 4, dtype=torch.float64, requires_grad=True)
-            F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
-            if float(wz.grad.abs().max()) == 0:
-                continue
-            h.put("d1e", d1)
-            LR.check_wgrad(h, "enc_conv1_wgrad_mfma", F0, wz.grad, ({},), "enc_conv1_wgrad_mfma B=%d one-hot %s" % (B, (im, oy, ox, ch)))
-    finally:
-        h.restore_knobs()
+        h.put("d1e", d1)
+        LR.check_wgrad(h, "enc_conv1_wgrad_mfma", F0, wz.grad, ({},), "enc_conv1_wgrad_mfma B=%d seed %d" % (B, seed))
+    g = LR.gen(0, 33, B)
+    img = torch.randint(-3, 4, (B, 1, 50, 50), generator=g).double()
+    h.put("tmp_f32", img, torch.float32)
+    for (im, oy, ox, ch) in ((0, 0, 0, 0), (B - 1, 24, 24, 31), (0, 11, 3, 5), (B - 1, 12, 19, 7), (0, 12, 20, 9), (B // 2, 13, 24, 30), (0, 24, 0, 16)):
+        d1 = torch.zeros(B, 25, 25, 32, dtype=torch.float64)
+        d1[im, oy, ox, ch] = 1.0
+        wz = torch.zeros(32, 1, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv2d(img, wz, None, 2, 1).backward(LR._nchw(d1))
+        if float(wz.grad.abs().max()) == 0:
+            continue
+        h.put("d1e", d1)
+        LR.check_wgrad(h, "enc_conv1_wgrad_mfma", F0, wz.grad, ({},), "enc_conv1_wgrad_mfma B=%d one-hot %s" % (B, (im, oy, ox, ch)))
 
 
 # ------------------------------------------------------------------------------------------------ decoder tail
@@ -226,49 +217,46 @@ def _check_backward(B, q3, w9, out, what):
 def test_tail_against_float64(B):
     h = _harness(B)
     count, C = B * 625, 32
-    try:
-        for seed in SEEDS:
-            g = LR.gen(seed, 34, B)
-            what = "dec_last_fused_reduce B=%d seed %d" % (B, seed)
-            q3 = LR.eighths((3 * B, 25, 25, C), g)
-            gamma = torch.tensor([1.0, 2.0, -1.0])[torch.randint(0, 3, (C,), generator=g)].double()
-            beta = torch.randint(-1, 2, (C,), generator=g).double() / 2
-            rm0 = torch.randint(-4, 5, (C,), generator=g).double() / 4
-            rv0 = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=g)].double()
-            w9 = LR.ternary((C, 1, 4, 4), 0.125, g) / 16        # logits of a few tenths: max |logit| <= 3 is asserted below
-            target = torch.randint(0, 2, (B, 1, 50, 50), generator=g).double()
-            stats = LR.slot_stats_any(q3, 3)
-            assert torch.equal(stats.float().double(), stats)
-            out = _run_tail(h, B, q3, stats, gamma, beta, w9, target, rm0, rv0)
-            # tables of all 3 groups, running statistics (3 groups x 1 update), the batch counter: once per launch
-            scale, shift, mean, rstd = LR.ref_bn_tables(stats, count, gamma, beta)
-            _within(out["aff"][..., 0], scale, 12 * E * scale.abs(), what + " scale")
-            _within(out["aff"][..., 1], shift, 16 * E * ((mean.abs() + 4) * scale.abs() + beta.abs()[None]), what + " shift")
-            _within(out["mr"][..., 0], mean, 16 * E * 4 * torch.ones_like(mean), what + " mean")
-            _within(out["mr"][..., 1], rstd, 11 * E * rstd, what + " rstd")
-            rm, rv, unb = LR.ref_bn_running(stats, count, rm0, rv0, 1)
-            _within(out["rm"], rm, (16 + 5 * 3) * E * 4 * torch.ones_like(rm), what + " running_mean")
-            _within(out["rv"], rv, (22 + 5 * 3) * E * torch.maximum(unb, rv0), what + " running_var")
-            assert out["nbt"] == 5 + 3, (what, out["nbt"])
-            # logits from the gated tables
-            a64, _ = LR.ref_stage_fwd(q3[:2 * B], out["aff"][:2, :, 0], out["aff"][:2, :, 1], 2)
-            lref = F.conv_transpose2d(LR._nchw(a64), w9, None, 2, 1)
-            labs = F.conv_transpose2d(LR._nchw(a64.abs()), w9.abs(), None, 2, 1)
-            _within(out["logits"], lref, (2.0 ** -8 + 128 * E) * labs, what + " logits")
-            assert float(out["logits"].abs().max()) <= 3.0, float(out["logits"].abs().max())        # |p - t| >= 0.047 for t in {0, 1}
-            # recon, dlogit, BCE sums from the logits the launch wrote
-            coef = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(B * 2500), dtype=torch.float32)
-            lg = out["logits"]
-            p = torch.sigmoid(lg)
-            t = target.repeat(2, 1, 1, 1)
-            LR.gate_last_layer(out["recon"], p, LR.LAST_RECON_MULT, what + " recon")
-            LR.gate_last_layer(out["dlogit"], float(coef) * (p - t), LR.LAST_DLOGIT_MULT, what + " dlogit")
-            terms = -(t * F.logsigmoid(lg).clamp_min(-100.0) + (1 - t) * F.logsigmoid(-lg).clamp_min(-100.0)).reshape(2, -1)
-            LR.gate_last_sums(out["sums"][:, :2].sum(0), terms.sum(1), terms.abs().sum(1), what + " BCE sums")
-            assert float(out["sums"][:, 2:].abs().max()) == 0.0, what + " wrote a loss column other than its two"
-            _check_backward(B, q3, w9, out, what)
-    finally:
-        h.restore_knobs()
+    for seed in SEEDS:
+        g = LR.gen(seed, 34, B)
+        what = "dec_last_fused_reduce B=%d seed %d" % (B, seed)
+        q3 = LR.eighths((3 * B, 25, 25, C), g)
+        gamma = torch.tensor([1.0, 2.0, -1.0])[torch.randint(0, 3, (C,), generator=g)].double()
+        beta = torch.randint(-1, 2, (C,), generator=g).double() / 2
+        rm0 = torch.randint(-4, 5, (C,), generator=g).double() / 4
+        rv0 = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=g)].double()
+        w9 = LR.ternary((C, 1, 4, 4), 0.125, g) / 16        # logits of a few tenths: max |logit| <= 3 is asserted below
+        target = torch.randint(0, 2, (B, 1, 50, 50), generator=g).double()
+        stats = LR.slot_stats_any(q3, 3)
+        assert torch.equal(stats.float().double(), stats)
+        out = _run_tail(h, B, q3, stats, gamma, beta, w9, target, rm0, rv0)
+        # tables of all 3 groups, running statistics (3 groups x 1 update), the batch counter: once per launch
+        scale, shift, mean, rstd = LR.ref_bn_tables(stats, count, gamma, beta)
+        _within(out["aff"][..., 0], scale, 12 * E * scale.abs(), what + " scale")
+        _within(out["aff"][..., 1], shift, 16 * E * ((mean.abs() + 4) * scale.abs() + beta.abs()[None]), what + " shift")
+        _within(out["mr"][..., 0], mean, 16 * E * 4 * torch.ones_like(mean), what + " mean")
+        _within(out["mr"][..., 1], rstd, 11 * E * rstd, what + " rstd")
+        rm, rv, unb = LR.ref_bn_running(stats, count, rm0, rv0, 1)
+        _within(out["rm"], rm, (16 + 5 * 3) * E * 4 * torch.ones_like(rm), what + " running_mean")
+        _within(out["rv"], rv, (22 + 5 * 3) * E * torch.maximum(unb, rv0), what + " running_var")
+        assert out["nbt"] == 5 + 3, (what, out["nbt"])
+        # logits from the gated tables
+        a64, _ = LR.ref_stage_fwd(q3[:2 * B], out["aff"][:2, :, 0], out["aff"][:2, :, 1], 2)
+        lref = F.conv_transpose2d(LR._nchw(a64), w9, None, 2, 1)
+        labs = F.conv_transpose2d(LR._nchw(a64.abs()), w9.abs(), None, 2, 1)
+        _within(out["logits"], lref, (2.0 ** -8 + 128 * E) * labs, what + " logits")
+        assert float(out["logits"].abs().max()) <= 3.0, float(out["logits"].abs().max())        # |p - t| >= 0.047 for t in {0, 1}
+        # recon, dlogit, BCE sums from the logits the launch wrote
+        coef = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(B * 2500), dtype=torch.float32)
+        lg = out["logits"]
+        p = torch.sigmoid(lg)
+        t = target.repeat(2, 1, 1, 1)
+        LR.gate_last_layer(out["recon"], p, LR.LAST_RECON_MULT, what + " recon")
+        LR.gate_last_layer(out["dlogit"], float(coef) * (p - t), LR.LAST_DLOGIT_MULT, what + " dlogit")
+        terms = -(t * F.logsigmoid(lg).clamp_min(-100.0) + (1 - t) * F.logsigmoid(-lg).clamp_min(-100.0)).reshape(2, -1)
+        LR.gate_last_sums(out["sums"][:, :2].sum(0), terms.sum(1), terms.abs().sum(1), what + " BCE sums")
+        assert float(out["sums"][:, 2:].abs().max()) == 0.0, what + " wrote a loss column other than its two"
+        _check_backward(B, q3, w9, out, what)
 
 
 @pytest.mark.parametrize("B", BATCHES)
@@ -281,42 +269,39 @@ def test_tail_seam(B):
     gamma, beta = torch.ones(C, dtype=torch.float64), torch.zeros(C, dtype=torch.float64)
     rm0, rv0 = torch.zeros(C, dtype=torch.float64), torch.ones(C, dtype=torch.float64)
     g = LR.gen(0, 35, B)
-    try:
-        # every logit 0: each of the 2500 pixels of an image adds ln 2 exactly once, whatever its target
-        what = "dec_last_fused_reduce zero weights B=%d" % B
-        q3 = LR.eighths((3 * B, 25, 25, C), g)
-        target = torch.randint(0, 5, (B, 1, 50, 50), generator=g).double() / 4
-        out = _run_tail(h, B, q3, stats, gamma, beta, torch.zeros(C, 1, 4, 4, dtype=torch.float64), target, rm0, rv0)
-        assert float(out["logits"].abs().max()) == 0.0
-        want = torch.full((2,), B * 2500 * math.log(2.0), dtype=torch.float64)
-        LR.gate_last_sums(out["sums"][:, :2].sum(0), want, want, what + " BCE sums")
-        # one-hot activations around the seam and at the corners, at image 0 and at the last image of the last group; distinct small
-        # integer weights per channel (|logit| <= 4 * 8 * Swish(1/2) = 10: no saturated sigmoid); one-hot targets at output rows 24 - 27
-        what = "dec_last_fused_reduce one-hot B=%d" % B
-        w9 = (((torch.arange(16)[None, :] * 5 + torch.arange(C)[:, None] * 3) % 17) - 8).double().reshape(C, 1, 4, 4)
-        q3 = torch.zeros(3 * B, 25, 25, C, dtype=torch.float64)
-        spots = ((0, 0, 0), (0, 24, 1), (24, 0, 2), (24, 24, 3), (11, 7, 4), (12, 7, 5), (13, 7, 6), (12, 24, 7), (13, 0, 8), (24, 12, 9),
-                 (11, 20, 10), (12, 21, 11), (13, 22, 12))
-        for im in (0, 2 * B - 1):
-            for (iy, ix, ch) in spots:
-                q3[im, iy, ix, ch] = 0.5
-        target = torch.zeros(B, 1, 50, 50, dtype=torch.float64)
-        for im in (0, B - 1):
-            for (oy, ox) in ((24, 3), (25, 14), (26, 15), (27, 40), (25, 0), (26, 49)):
-                target[im, 0, oy, ox] = 1.0
-        out = _run_tail(h, B, q3, stats, gamma, beta, w9, target, rm0, rv0)
-        a64, _ = LR.ref_stage_fwd(q3[:2 * B], out["aff"][:2, :, 0], out["aff"][:2, :, 1], 2)
-        lref = F.conv_transpose2d(LR._nchw(a64), w9, None, 2, 1)
-        labs = F.conv_transpose2d(LR._nchw(a64.abs()), w9.abs(), None, 2, 1)
-        _within(out["logits"], lref, (2.0 ** -8 + 128 * E) * labs, what + " logits")
-        assert float(out["logits"].abs().max()) <= 14.0
-        coef = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(B * 2500), dtype=torch.float32)
-        p, t = torch.sigmoid(out["logits"]), target.repeat(2, 1, 1, 1)
-        near = (p - t).abs() >= 0.04                                     # (the margin of the gate; saturated pixels are compared below through d3)
-        dref = float(coef) * (p - t)
-        LR.gate_last_layer(torch.where(near, out["dlogit"], dref), dref, LR.LAST_DLOGIT_MULT, what + " dlogit")
-        ref, gate = _check_backward(B, q3, w9, out, what)               # d3 of every image, dW: element by element
-        # a pixel owned twice or never shows in dW at full size: the one-hot channels carry every term of their rows
-        assert bool((ref[:13].abs().amax((1, 2, 3)) > 64 * gate[:13].amax((1, 2, 3))).all())
-    finally:
-        h.restore_knobs()
+    # every logit 0: each of the 2500 pixels of an image adds ln 2 exactly once, whatever its target
+    what = "dec_last_fused_reduce zero weights B=%d" % B
+    q3 = LR.eighths((3 * B, 25, 25, C), g)
+    target = torch.randint(0, 5, (B, 1, 50, 50), generator=g).double() / 4
+    out = _run_tail(h, B, q3, stats, gamma, beta, torch.zeros(C, 1, 4, 4, dtype=torch.float64), target, rm0, rv0)
+    assert float(out["logits"].abs().max()) == 0.0
+    want = torch.full((2,), B * 2500 * math.log(2.0), dtype=torch.float64)
+    LR.gate_last_sums(out["sums"][:, :2].sum(0), want, want, what + " BCE sums")
+    # one-hot activations around the seam and at the corners, at image 0 and at the last image of the last group; distinct small
+    # integer weights per channel (|logit| <= 4 * 8 * Swish(1/2) = 10: no saturated sigmoid); one-hot targets at output rows 24 - 27
+    what = "dec_last_fused_reduce one-hot B=%d" % B
+    w9 = (((torch.arange(16)[None, :] * 5 + torch.arange(C)[:, None] * 3) % 17) - 8).double().reshape(C, 1, 4, 4)
+    q3 = torch.zeros(3 * B, 25, 25, C, dtype=torch.float64)
+    spots = ((0, 0, 0), (0, 24, 1), (24, 0, 2), (24, 24, 3), (11, 7, 4), (12, 7, 5), (13, 7, 6), (12, 24, 7), (13, 0, 8), (24, 12, 9),
+             (11, 20, 10), (12, 21, 11), (13, 22, 12))
+    for im in (0, 2 * B - 1):
+        for (iy, ix, ch) in spots:
+            q3[im, iy, ix, ch] = 0.5
+    target = torch.zeros(B, 1, 50, 50, dtype=torch.float64)
+    for im in (0, B - 1):
+        for (oy, ox) in ((24, 3), (25, 14), (26, 15), (27, 40), (25, 0), (26, 49)):
+            target[im, 0, oy, ox] = 1.0
+    out = _run_tail(h, B, q3, stats, gamma, beta, w9, target, rm0, rv0)
+    a64, _ = LR.ref_stage_fwd(q3[:2 * B], out["aff"][:2, :, 0], out["aff"][:2, :, 1], 2)
+    lref = F.conv_transpose2d(LR._nchw(a64), w9, None, 2, 1)
+    labs = F.conv_transpose2d(LR._nchw(a64.abs()), w9.abs(), None, 2, 1)
+    _within(out["logits"], lref, (2.0 ** -8 + 128 * E) * labs, what + " logits")
+    assert float(out["logits"].abs().max()) <= 14.0
+    coef = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(B * 2500), dtype=torch.float32)
+    p, t = torch.sigmoid(out["logits"]), target.repeat(2, 1, 1, 1)
+    near = (p - t).abs() >= 0.04                                     # (the margin of the gate; saturated pixels are compared below through d3)
+    dref = float(coef) * (p - t)
+    LR.gate_last_layer(torch.where(near, out["dlogit"], dref), dref, LR.LAST_DLOGIT_MULT, what + " dlogit")
+    ref, gate = _check_backward(B, q3, w9, out, what)               # d3 of every image, dW: element by element
+    # a pixel owned twice or never shows in dW at full size: the one-hot channels carry every term of their rows
+    assert bool((ref[:13].abs().amax((1, 2, 3)) > 64 * gate[:13].amax((1, 2, 3))).all())

@@ -20,7 +20,7 @@ def test_ring_kernel_equals_streamed_kernel(B):
     if not torch.cuda.is_available():
         pytest.skip("needs the MI355X")
     import multimodal_vae_amd  # noqa: F401
-    from multimodal_vae_amd._lib import call
+    from multimodal_vae_amd._lib import call, knobs
     from multimodal_vae_amd.core import FusedELBOStep, MultimnistState
     from multimodal_vae_amd.init import default_init_
     from bench import synthetic_batch
@@ -32,24 +32,17 @@ def test_ring_kernel_equals_streamed_kernel(B):
     sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def run(layer, ring, atomic_kb, pair=0):
-        call("mmvae_debug_set", b"wgrad_ring", ring)
-        call("mmvae_debug_set", b"wr_pair", pair)
-        call("mmvae_debug_set", b"wr_atomic_kb", atomic_kb)
         st.gpk.zero_()
-        call("mmvae_mm_bench_layer", eng.h, eng.ws.data_ptr(), eng.ws.numel(), layer.encode(), 1, sp)
+        with knobs(wgrad_ring=ring, wr_pair=pair, wr_atomic_kb=atomic_kb):
+            call("mmvae_mm_bench_layer", eng.h, eng.ws.data_ptr(), eng.ws.numel(), layer.encode(), 1, sp)
         torch.cuda.synchronize()
         return st.gpk.clone()
-    try:
-        for layer in LAYERS:
-            ref = run(layer, 0, 256)
-            assert int((ref != 0).sum()) > 0 and bool(torch.isfinite(ref).all()), layer
-            for atomic_kb in (0, 4096):                      # partial copies + reduce / fp32 atomics into the packed gradient
-                for pair in (1, 0):                          # two parity classes per 8-wave workgroup / one per 4-wave workgroup
-                    got = run(layer, 1, atomic_kb, pair)
-                    rel = float((ref - got).norm() / ref.norm())
-                    assert rel < 2e-5, (layer, atomic_kb, pair, rel)   # same bf16 operands, fp32 accumulation in another order
-                    assert torch.equal(got == 0, ref == 0) or rel < 2e-5
-    finally:
-        call("mmvae_debug_set", b"wgrad_ring", 1)
-        call("mmvae_debug_set", b"wr_atomic_kb", 256)
-        call("mmvae_debug_set", b"wr_pair", 0)
+    for layer in LAYERS:
+        ref = run(layer, 0, 256)
+        assert int((ref != 0).sum()) > 0 and bool(torch.isfinite(ref).all()), layer
+        for atomic_kb in (0, 4096):                      # partial copies + reduce / fp32 atomics into the packed gradient
+            for pair in (1, 0):                          # two parity classes per 8-wave workgroup / one per 4-wave workgroup
+                got = run(layer, 1, atomic_kb, pair)
+                rel = float((ref - got).norm() / ref.norm())
+                assert rel < 2e-5, (layer, atomic_kb, pair, rel)   # same bf16 operands, fp32 accumulation in another order
+                assert torch.equal(got == 0, ref == 0) or rel < 2e-5

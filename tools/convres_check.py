@@ -8,7 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import multimodal_vae_amd
 from multimodal_vae_amd.core import MultimnistState, FusedELBOStep
 from multimodal_vae_amd.init import default_init_
-from multimodal_vae_amd._lib import call
+from multimodal_vae_amd._lib import call, knobs, knob_ptr
 sys.path.insert(0, '.')
 from bench import synthetic_batch
 
@@ -17,8 +17,8 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 st = MultimnistState(100, dev); default_init_(st, 1234)
 img, txt = synthetic_batch(B, 1234)
 eng = FusedELBOStep(st, B)
-call("mmvae_debug_set", b"convres", 0)
-eng(img.to(dev), txt.to(dev)); st.ensure_packed(); torch.cuda.synchronize()
+with knobs(convres=0):
+    eng(img.to(dev), txt.to(dev)); st.ensure_packed(); torch.cuda.synchronize()
 s = torch.cuda.current_stream(); sp = ctypes.c_void_p(s.cuda_stream)
 SLOTS = 16
 
@@ -45,9 +45,9 @@ layers = {
 }
 sel = sys.argv[2:] or list(layers)
 
-def run(layer, on, iters):
-    call("mmvae_debug_set", b"convres", on)
-    call("mmvae_mm_bench_layer", eng.h, eng.ws.data_ptr(), eng.ws.numel(), layer.encode(), iters, sp)
+def run(layer, on, iters, **kn):
+    with knobs(convres=on, **kn):
+        call("mmvae_mm_bench_layer", eng.h, eng.ws.data_ptr(), eng.ws.numel(), layer.encode(), iters, sp)
 
 bad = 0
 for L in sel:
@@ -80,21 +80,16 @@ for L in sel:
     if os.environ.get("CR_ALT"):
         ts = []
         for alt in (1, 5):
-            call("mmvae_debug_set", b"convres_alt", alt)
             out.zero_()
-            run(L, 1, 3); torch.cuda.synchronize()
+            run(L, 1, 3, convres_alt=alt); torch.cuda.synchronize()
             rel2 = ((o0 - out.float()).norm() / (o0.norm() + 1e-30)).item()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s); run(L, 1, 20); e1.record(s); torch.cuda.synchronize()
+            e0.record(s); run(L, 1, 20, convres_alt=alt); e1.record(s); torch.cuda.synchronize()
             ts.append(f"alt{alt}={e0.elapsed_time(e1) * 1e3 / 20:.1f} (rel {rel2:.1e})")
-        call("mmvae_debug_set", b"convres_alt", 0)
         print("      " + "  ".join(ts), flush=True)
     if os.environ.get("CR_TS"):
         tsb = torch.zeros(4096 * 8 * 16, dtype=torch.int64, device=dev)
-        call("mmvae_debug_set", b"convres_ts_lo", ctypes.c_int(tsb.data_ptr() & 0xffffffff).value)
-        call("mmvae_debug_set", b"convres_ts_hi", ctypes.c_int(tsb.data_ptr() >> 32).value)
-        run(L, 1, 1); torch.cuda.synchronize()
-        call("mmvae_debug_set", b"convres_ts_lo", 0); call("mmvae_debug_set", b"convres_ts_hi", 0)
+        run(L, 1, 1, **knob_ptr("convres_ts", tsb)); torch.cuda.synchronize()
         t = tsb.view(-1, 16).cpu()
         t = t[t[:, 0] > 0].double()
         names = ["start", "zero+tab+issue", "barrier", "stage+w0", "barrier", "c0 mfma", "c0 epi", "c1 mfma", "c1 epi", "c2 mfma", "c2 epi",
@@ -115,12 +110,10 @@ for L in sel:
     if os.environ.get("CR_DBG"):
         ts = []
         for dbg in (1, 2, 4, 3, 7):
-            call("mmvae_debug_set", b"convres_dbg", dbg)
-            run(L, 1, 3)
+            run(L, 1, 3, convres_dbg=dbg)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s); run(L, 1, 20); e1.record(s); torch.cuda.synchronize()
+            e0.record(s); run(L, 1, 20, convres_dbg=dbg); e1.record(s); torch.cuda.synchronize()
             ts.append(f"dbg{dbg}={e0.elapsed_time(e1) * 1e3 / 20:.1f}")
-        call("mmvae_debug_set", b"convres_dbg", 0)
         print("      (1 no stores, 2 no MFMA loop, 4 no staging)  " + "  ".join(ts), flush=True)
     if not ok:
         d = (o0 - o1).abs().view(nimg, pix, ch)

@@ -100,7 +100,7 @@ def bench_step(B, D, args):
     routes = [(A, 1, lambda: one_s(image)), (B_, 0, lambda: one_u(image)), (C_, -1, lambda: three(image, label, passes=(False, True, False))),
               (D_, -1, step_modules)]
     med, spread, ms = alternate(routes, args, args.steps, knob)
-    call("mmvae_debug_set", b"mnist_strip", -1)
+    call("mmvae_debug_reset", b"mnist_strip")
     say("mnist image-only  B = %d  n_latents = %d  (%d rounds of %d steps)" % (B, D, args.repeats, args.steps))
     for n, _, _ in routes:
         say("    %-22s %8.4f ms / step   spread %.4f ms   rounds: %s" % (n, med[n], spread[n], " ".join("%.4f" % v for v in ms[n])))

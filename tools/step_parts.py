@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import multimodal_vae_amd  # noqa
 from multimodal_vae_amd.core import MultimnistState, FusedELBOStep
 from multimodal_vae_amd.init import default_init_
-from multimodal_vae_amd._lib import call
+from multimodal_vae_amd._lib import knobs
 from bench import synthetic_batch
 dev = torch.device('cuda:0'); B = 256
 st = MultimnistState(100, dev); default_init_(st, 1234)
@@ -27,8 +27,7 @@ cases = [("full step", {}), ("no weight gradients", {"dbg_skip_wgrad": 1}), ("no
          ("main chain alone, no event edges", {"dbg_skip_wgrad": 1, "dbg_skip_text": 1, "dbg_skip_edges": 1}),
          ("main chain alone, no forks (records on main)", {"dbg_skip_wgrad": 1, "dbg_skip_text": 1, "dbg_skip_edges": 2}),
          ("main chain alone, no joins (waits on main)", {"dbg_skip_wgrad": 1, "dbg_skip_text": 1, "dbg_skip_edges": 3})]
-extra = [a.split("=") for a in sys.argv[1:]]
-for name, knobs in cases:
-    for k in ("dbg_skip_wgrad", "dbg_skip_text", "dbg_skip_edges"): call("mmvae_debug_set", k.encode(), knobs.get(k, 0))
-    for k, v in extra: call("mmvae_debug_set", k.encode(), int(v))
-    print(f"{name:32s} {timeit():8.1f} us/step", flush=True)
+extra = dict(a.split("=") for a in sys.argv[1:])
+for name, kn in cases:
+    with knobs(**dict(kn, **extra)):
+        print(f"{name:32s} {timeit():8.1f} us/step", flush=True)

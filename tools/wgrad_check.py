@@ -7,26 +7,26 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import multimodal_vae_amd
 from multimodal_vae_amd.core import MultimnistState, FusedELBOStep
 from multimodal_vae_amd.init import default_init_
-from multimodal_vae_amd._lib import call
+from multimodal_vae_amd._lib import call, knobs, knob_ptr
 sys.path.insert(0, '.')
 from bench import synthetic_batch
 
 dev = torch.device('cuda:0')
 args = sys.argv[1:]
 B = int(args.pop(0)) if args and args[0].isdigit() else 256
-knobs = [a for a in args if "=" in a]
+cli_knobs = [a for a in args if "=" in a]
 sel = [a for a in args if "=" not in a] or ['dec_convT3_wgrad', 'dec_convT2_wgrad', 'enc_conv2_wgrad', 'enc_conv3_wgrad', 'dec_convT1_wgrad', 'enc_conv4_wgrad']
 st = MultimnistState(100, dev); default_init_(st, 1234)
 img, txt = synthetic_batch(B, 1234)
 eng = FusedELBOStep(st, B)
 eng(img.to(dev), txt.to(dev)); st.ensure_packed(); torch.cuda.synchronize()
-for kv in knobs:
+for kv in cli_knobs:
     k, v = kv.split("="); call("mmvae_debug_set", k.encode(), int(v))
 s = torch.cuda.current_stream(); sp = ctypes.c_void_p(s.cuda_stream)
 
-def run(layer, ring, iters):
-    call("mmvae_debug_set", b"wgrad_ring", ring)
-    call("mmvae_mm_bench_layer", eng.h, eng.ws.data_ptr(), eng.ws.numel(), layer.encode(), iters, sp)
+def run(layer, ring, iters, **kn):
+    with knobs(wgrad_ring=ring, **kn):
+        call("mmvae_mm_bench_layer", eng.h, eng.ws.data_ptr(), eng.ws.numel(), layer.encode(), iters, sp)
 
 bad = 0
 for L in sel:
@@ -56,19 +56,14 @@ for L in sel:
     if os.environ.get("WR_DBG"):
         ts = []
         for dbg in (1, 2, 4, 6, 7):
-            call("mmvae_debug_set", b"wr_dbg", dbg)
-            run(L, 1, 3)
+            run(L, 1, 3, wr_dbg=dbg)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s); run(L, 1, 20); e1.record(s); torch.cuda.synchronize()
+            e0.record(s); run(L, 1, 20, wr_dbg=dbg); e1.record(s); torch.cuda.synchronize()
             ts.append(f"dbg{dbg}={e0.elapsed_time(e1) * 1e3 / 20:.1f}")
-        call("mmvae_debug_set", b"wr_dbg", 0)
         print("      (1 no stores, 2 no MFMA loop, 4 no DMA traffic)  " + "  ".join(ts), flush=True)
     if os.environ.get("WR_TS"):
         tsb = torch.zeros(4096 * 8, dtype=torch.int64, device=dev)
-        call("mmvae_debug_set", b"wr_ts_lo", ctypes.c_int(tsb.data_ptr() & 0xffffffff).value)
-        call("mmvae_debug_set", b"wr_ts_hi", ctypes.c_int(tsb.data_ptr() >> 32).value)
-        run(L, 1, 1); torch.cuda.synchronize()
-        call("mmvae_debug_set", b"wr_ts_lo", 0); call("mmvae_debug_set", b"wr_ts_hi", 0)
+        run(L, 1, 1, **knob_ptr("wr_ts", tsb)); torch.cuda.synchronize()
         t = tsb.view(-1, 8).cpu()
         t = t[t[:, 0] > 0].double()
         base = t[:, 0].min()
@@ -86,12 +81,10 @@ for L in sel:
     if os.environ.get("WR_WGS"):
         ts = []
         for wgs in (1, 2, 3, 4, 6, 8):
-            call("mmvae_debug_set", b"wr_wgs", wgs)
-            run(L, 1, 3)
+            run(L, 1, 3, wr_wgs=wgs)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s); run(L, 1, 20); e1.record(s); torch.cuda.synchronize()
+            e0.record(s); run(L, 1, 20, wr_wgs=wgs); e1.record(s); torch.cuda.synchronize()
             ts.append(f"wgs{wgs}={e0.elapsed_time(e1) * 1e3 / 20:.1f}")
-        call("mmvae_debug_set", b"wr_wgs", 4)
         print("      workgroups per 4 CUs:  " + "  ".join(ts), flush=True)
 print("FAILED" if bad else "all layers agree")
 sys.exit(1 if bad else 0)
