@@ -245,6 +245,328 @@ void carve(MMPlan& P, Workspace& ws) {
     w.slab = ws.take<float>(w.slab_floats);
 }
 
+// ================================================================== launch arguments
+// ONE definition per launch, as in img_tower.h: every GemmParams / WgradParams and the arguments of every stand-alone pass of
+// the image half are built here, for the step (enc_fwd / enc_bwd / dec_fwd / dec_bwd / fused_tail) and for the replay of one
+// launch on a test's own operands (mm_bench_layer): a test cannot pass on a copy of the parameters that drifted from the step.
+
+// the tensors along the two conv chains, by layer: raw / activated / gradient; drr / dqr: the BatchNorm-backward outputs the fused
+// step keeps apart from db (see enc_bwd / dec_bwd)
+struct MMChains { bf16 *r[4], *a[4], *dr[4], *drr[4], *q[4], *aq[4], *dq[4], *dqr[4]; };
+MMChains mm_chains(const MMPlan::W& w) {
+    return MMChains{{w.r1, w.r2, w.r3, w.r4}, {w.a1, w.a2, w.a3, w.a4}, {w.d1e, w.d2e, w.d3e, w.dr4}, {nullptr, w.d2er, w.d3er, nullptr},
+                    {w.u, w.q1, w.q2, w.q3}, {w.au, w.aq1, w.aq2, w.aq3}, {w.du, w.d1, w.d2, w.d3}, {nullptr, w.d1r, w.d2r, w.d3r}};
+}
+
+// l: layer index (conv[l] / convT[l]); n: row blocks -- dropout variants of the classifier, BatchNorm groups (passes) of the decoder.
+enum MMGemm { MM_ENC_CONV1, MM_ENC_CONV, MM_ENC_CONV_DGRAD, MM_FC1, MM_FC1_DGRAD, MM_FC2, MM_FC3, MM_FC3_DGRAD, MM_FC2_DGRAD, MM_UP, MM_UP_DGRAD,
+              MM_DEC_CONVT, MM_DEC_CONVT_DGRAD, MM_DEC_LAST_DGRAD };
+enum MMWgrad { MM_W_ENC_CONV1, MM_W_ENC_CONV, MM_W_FC1, MM_W_FC2, MM_W_FC3, MM_W_UP, MM_W_DEC_CONVT, MM_W_DEC_LAST };
+
+// classifier.0 over the NHWC 2x2x256 feature map the variants share: a 2x2-tap gather
+GatherPlan fc1_plan(int rows) { return plan_fwdform(2, 2, 1, 1, 256, 2, 2, 1, 0, 400, 1, rows); }
+
+// training: column statistics of the conv layers; mask: keep flags of the Dropout behind the layer (MM_FC1, MM_FC2) or behind the
+// layer whose input gradient this is (MM_FC3_DGRAD: classifier.3's, MM_FC2_DGRAD: classifier.0's), or null.
+// aux: MM_FC3 the fp32 result [n*B][2D]; MM_UP_DGRAD the fp32 result dz [n*B][D]; MM_FC3_DGRAD the operand d_out, bf16 [n*B][lde]
+// with columns 2D.. zero (the generic kernels read their operands in 8-column vectors; 2D is a multiple of 8 only when n_latents
+// is a multiple of 4).  colsum (MM_FC3_DGRAD, MM_FC2_DGRAD): where the column sums of the result go; null: the bias gradient of
+// the layer below, classifier.3's / classifier.0's
+GemmParams mm_gemm(MMPlan& P, MMGemm kind, int l, int n, int training = 1, const uint8_t* mask = nullptr, const void* aux = nullptr,
+                   float* colsum = nullptr) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const int B = P.B, rows = n * B, rows1 = B * 625;
+    const float ms = 1.f / (1.f - DROP_P);
+    // a dense layer: `groups` blocks of group_n rows with K operand columns, N outputs
+    auto dense = [&](const int* pk, int groups, int group_n, int K, int N) { return gemm_of(P, dense_plan(group_n, K, K, N), pk, groups, group_n); };
+    GemmParams g{};
+    switch (kind) {
+    case MM_ENC_CONV1:   // conv1 over the im2col patches + Swish (no BatchNorm): the epilogue emits raw and activated
+        g = dense(P.conv[0].pk_fwd, 1, rows1, 16, 32);
+        g.c.A = w.patches1; g.out_bf = w.r1; g.ldo = 32; g.out_act_bf = w.a1; g.e_act = ACT_SWISH;
+        break;
+    case MM_ENC_CONV: {
+        const ConvL& L = P.conv[l];
+        g = gemm_of(P, L.fwd, L.pk_fwd, 1, B, L.pk_fwd_f);
+        g.c.A = t.a[l - 1]; g.out_bf = t.r[l]; g.ldo = L.g.Cout;
+        g.colstats = training ? w.st_e[l - 1] : nullptr;
+        break;
+    }
+    case MM_ENC_CONV_DGRAD: {   // class form, with the d-activation of the producer layer fused in the epilogue
+        const ConvL& L = P.conv[l];
+        g = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
+        g.c.A = t.dr[l]; g.out_bf = t.dr[l - 1]; g.ldo = L.g.Cin;
+        g.d_r = t.r[l - 1]; g.d_ld = L.g.Cin; g.d_act = ACT_SWISH;
+        if (l > 1) { g.d_affine = w.aff_e[l - 2]; g.d_meanrstd = w.mr_e[l - 2]; g.d_red = w.red_e[l - 2]; }
+        break;
+    }
+    case MM_FC1:
+        g = gemm_of(P, fc1_plan(rows), &P.fc[0].pk_fwd, 1, rows);
+        g.c.A = w.a4; g.c.a_bcast_n = B;
+        g.bias = P.buf.params + P.fc[0].b_off; g.out_bf = w.y1; g.ldo = 400;
+        g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (mask) { g.e_mask = mask; g.e_mask_scale = ms; }
+        break;
+    case MM_FC1_DGRAD: {
+        // 4 classes = the 4 pixels of the 2x2 map, each with its own [256][400] matrix; the NHWC gradients of `rows` samples (both
+        // dropout variants) against the map the B images share, with the BatchNorm-backward sums of conv4
+        GatherPlan pd{};
+        pd.c.AH = 1; pd.c.AW = 1; pd.c.Ald = 400; pd.c.C = 400; pd.c.sy = pd.c.sx = 1; pd.c.dy = pd.c.dx = 1;
+        pd.c.OH = 2; pd.c.OW = 2; pd.c.osy = pd.c.osx = 1; pd.c.N = 256; pd.c.nclasses = 4;
+        for (int sidx = 0; sidx < 4; ++sidx) {
+            GatherClass& k = pd.cls[sidx];
+            k.OY = 1; k.OX = 1; k.TH = 1; k.TW = 1; k.offy = 0; k.offx = 0; k.ooy = sidx / 2; k.oox = sidx % 2;
+            k.K = 400; k.Kpad = round_up(400, 64);
+        }
+        g = gemm_of(P, pd, P.fc[0].pk_dgrad4, 1, rows);
+        g.c.A = w.dy1; g.out_bf = w.db4; g.ldo = 256;
+        g.d_r = w.r4; g.d_ld = 256; g.d_bcast_n = B; g.d_act = ACT_SWISH;
+        g.d_affine = w.aff_e[2]; g.d_meanrstd = w.mr_e[2]; g.d_red = w.red_e[2];
+        break;
+    }
+    case MM_FC2:
+        g = dense(&P.fc[1].pk_fwd, 1, rows, 400, 200);
+        g.c.A = w.ay1; g.bias = P.buf.params + P.fc[1].b_off; g.out_bf = w.y2; g.ldo = 200;
+        g.out_act_bf = w.ay2; g.e_act = ACT_SWISH; if (mask) { g.e_mask = mask; g.e_mask_scale = ms; }
+        break;
+    case MM_FC3:
+        g = dense(&P.fc[2].pk_fwd, 1, rows, 200, 2 * P.D);
+        g.c.A = w.ay2; g.bias = P.buf.params + P.fc[2].b_off; g.out_f = (float*)aux; g.ldo = 2 * P.D;
+        break;
+    case MM_FC3_DGRAD:   // K = lde: the zero pad columns meet the zero pad of the packed weights
+        g = dense(&P.fc[2].pk_dgrad, 1, rows, P.lde, 200);
+        g.c.A = (const bf16*)aux; g.out_bf = w.dy2; g.ldo = 200;
+        g.d_r = w.y2; g.d_ld = 200; g.d_act = ACT_SWISH; if (mask) { g.d_mask = mask; g.d_mask_scale = ms; }
+        g.d_colsum = colsum ? colsum : P.buf.grads + P.fc[1].b_off;
+        break;
+    case MM_FC2_DGRAD:
+        g = dense(&P.fc[1].pk_dgrad, 1, rows, 200, 400);
+        g.c.A = w.dy2; g.out_bf = w.dy1; g.ldo = 400;
+        g.d_r = w.y1; g.d_ld = 400; g.d_act = ACT_SWISH; if (mask) { g.d_mask = mask; g.d_mask_scale = ms; }
+        g.d_colsum = colsum ? colsum : P.buf.grads + P.fc[0].b_off;
+        break;
+    case MM_UP:   // z_bf: [rows][ldz] with column D == 1.0 (folded bias)
+        g = dense(&P.up.pk_fwd, 1, rows, P.ldz, 1024);
+        g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = 1024; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
+        break;
+    case MM_UP_DGRAD:
+        g = dense(&P.up.pk_dgrad, 1, rows, 1024, P.D);
+        g.c.A = w.du; g.out_f = (float*)aux; g.ldo = P.D;
+        break;
+    case MM_DEC_CONVT: {
+        const ConvL& L = P.convT[l];
+        g = gemm_of(P, L.fwd, L.pk_fwd, n, B, L.pk_fwd_f);
+        g.c.A = t.aq[l]; g.out_bf = t.q[l + 1]; g.ldo = L.g.Cout;
+        g.colstats = training ? w.st_d[l] : nullptr;
+        break;
+    }
+    case MM_DEC_CONVT_DGRAD: {
+        const ConvL& L = P.convT[l];
+        g = gemm_of(P, L.dgrad, L.pk_dgrad, n, B, L.pk_dgrad_f);
+        g.c.A = t.dq[l + 1]; g.out_bf = t.dq[l]; g.ldo = L.g.Cin;
+        g.d_r = t.q[l]; g.d_ld = L.g.Cin; g.d_act = ACT_SWISH;
+        if (l > 0) { g.d_affine = w.aff_d[l - 1]; g.d_meanrstd = w.mr_d[l - 1]; g.d_red = w.red_d[l - 1]; }
+        break;
+    }
+    case MM_DEC_LAST_DGRAD:
+        // last transposed conv (32 -> 1) through the im2col patches of dlogit (K = 16 taps): input gradient = dense GEMM patches x W
+        // with d-Swish + BatchNorm-backward sums in the epilogue.  (The direct dot-product kernel convt_last_dgrad is VALU-bound:
+        // 52 us against 39 us for this GEMM at B=256.)
+        g = dense(P.convT[3].pk_dgrad, n, rows1, 16, 32);
+        g.c.A = w.patches4; g.out_bf = w.d3; g.ldo = 32;
+        g.d_r = w.q3; g.d_ld = 32; g.d_act = ACT_SWISH; g.d_affine = w.aff_d[2]; g.d_meanrstd = w.mr_d[2]; g.d_red = w.red_d[2];
+        break;
+    }
+    return g;
+}
+
+// p: MM_W_ENC_CONV / MM_W_DEC_CONVT the gradient of the layer's raw output -- dr[l] / dq[l + 1], or the buffer of its own that a fused
+// layer's BatchNorm backward writes (drr[l] / dqr[l + 1]); MM_W_FC3 the gradient of the encoder's output, bf16 [n*B][lde]
+WgradParams mm_wgrad(MMPlan& P, MMWgrad kind, int l, int n, const bf16* p = nullptr) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const int B = P.B, rows = n * B, rows1 = B * 625;
+    auto dense = [&](const int* gk, int nrows, int K, int N) { return wgrad_of(P, dense_plan(nrows, K, K, N), gk, 1, nrows); };
+    WgradParams g{};
+    switch (kind) {
+    case MM_W_ENC_CONV1:   // conv1 over the im2col patches
+        g = dense(P.conv[0].gk, rows1, 16, 32);
+        g.c.A = w.patches1; g.P = w.d1e; g.ldp = 32;
+        break;
+    case MM_W_ENC_CONV:   // rows over the output grid, the activated input gathered in forward form
+        g = wgrad_of(P, P.conv[l].fwd, P.conv[l].gk, 1, B);
+        g.c.A = t.a[l - 1]; g.P = p; g.ldp = P.conv[l].g.Cout;
+        break;
+    case MM_W_FC1:   // classifier.0: gathers the shared 2x2x256 map
+        g = wgrad_of(P, fc1_plan(rows), &P.fc[0].gk, 1, rows);
+        g.c.A = w.a4; g.c.a_bcast_n = B; g.P = w.dy1; g.ldp = 400;
+        break;
+    case MM_W_FC2:
+        g = dense(&P.fc[1].gk, rows, 400, 200);
+        g.c.A = w.ay1; g.P = w.dy2; g.ldp = 200;
+        break;
+    case MM_W_FC3:
+        g = dense(&P.fc[2].gk, rows, 200, 2 * P.D);
+        g.c.A = w.ay2; g.P = p; g.ldp = P.lde;
+        break;
+    case MM_W_UP:   // upsample Linear: weight (+ folded bias) gradient
+        g = dense(&P.up.gk, rows, P.ldz, 1024);
+        g.c.A = w.z_bf; g.P = w.du; g.ldp = 1024;
+        break;
+    case MM_W_DEC_CONVT:
+        g = convT_wgrad(P, P.convT[l], n, B, t.aq[l], p);
+        break;
+    case MM_W_DEC_LAST: {   // last transposed conv (32 -> 1): patches^T x activated input
+        GatherPlan pl = plan_fwdform(1, 1, 25, 25, 16, 1, 1, 1, 0, 32, n, B);   // rows (n, iy, ix), dense K=16
+        g = wgrad_of(P, pl, P.convT[3].gk, n, B);
+        g.c.A = w.patches4; g.c.AH = 25; g.c.AW = 25; g.c.sy = g.c.sx = 1;
+        g.P = w.aq3; g.ldp = 32;
+        break;
+    }
+    }
+    return g;
+}
+
+// ---- the stand-alone passes
+// BatchNorm backward behind conv[l] (l = 1..3) / convT[l] (l = 0..2) into `dr`: db itself, or the fused layers' buffer apart from
+// it; features.9 (l = 3) sums the gradients of the 2 classifier variants (db2)
+BnBwdApplyArgs mm_enc_bn_bwd_args(MMPlan& P, int l, int variants, bf16* dr) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const int B = P.B;
+    const ConvL& L = P.conv[l];
+    const BnL& b = P.bn[L.bn];
+    const int pix = L.g.OH * L.g.OW;
+    BnBwdApplyArgs x{};
+    x.db = (l == 3) ? w.db4 : t.dr[l];
+    x.db2 = (l == 3 && variants == 2) ? w.db4 + (size_t)B * 1024 : nullptr;
+    x.r = t.r[l]; x.dr = dr; x.rows = B * pix; x.C = L.g.Cout; x.ld = L.g.Cout; x.rows_per_group = B * pix; x.G = 1;
+    x.red = w.red_e[l - 1]; x.meanrstd = w.mr_e[l - 1]; x.gamma = P.buf.params + b.w_off;
+    x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
+    return x;
+}
+BnBwdApplyArgs mm_dec_bn_bwd_args(MMPlan& P, int l, int groups, bf16* dr) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const int B = P.B, rows = groups * B;
+    const ConvL& L = P.convT[l];
+    const BnL& b = P.bn[L.bn];
+    const int pix = L.g.OH * L.g.OW;
+    BnBwdApplyArgs x{};
+    x.db = t.dq[l + 1]; x.r = t.q[l + 1]; x.dr = dr; x.rows = rows * pix; x.C = L.g.Cout; x.ld = L.g.Cout;
+    x.rows_per_group = B * pix; x.G = groups;
+    x.red = w.red_d[l]; x.meanrstd = w.mr_d[l]; x.gamma = P.buf.params + b.w_off;
+    x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
+    return x;
+}
+// BatchNorm + Swish behind conv[l] (l = 1..3) / convT[l] (l = 0..2): tables, running statistics, activated tensor
+int mm_enc_bn_act(MMPlan& P, int l, int bn_updates, int training, hipStream_t s) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const ConvL& L = P.conv[l];
+    const int rows = P.B * L.g.OH * L.g.OW;
+    return bn_act(P, P.bn[L.bn], t.r[l], t.a[l], rows, rows, 1, w.st_e[l - 1], bn_updates, w.aff_e[l - 1], w.mr_e[l - 1], training, s);
+}
+int mm_dec_bn_act(MMPlan& P, int l, int groups, int training, hipStream_t s) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const ConvL& L = P.convT[l];
+    const int rpg = P.B * L.g.OH * L.g.OW;
+    return bn_act(P, P.bn[L.bn], t.q[l + 1], t.aq[l + 1], groups * rpg, rpg, groups, w.st_d[l], 1, w.aff_d[l], w.mr_d[l], training, s);
+}
+// The same pass for the input of conv[l] (l >= 2) / convT[l] (l >= 1) where the layer staged the raw tensor itself and left
+// nothing behind: a[l - 1] / aq[l], the operand of the layer's weight gradient, made in front of it off the main chain
+// (plan_base.h bn_act_side); `groups` row blocks
+struct MMActSide { BnL b; const bf16* r; bf16* a; int rows_per_group; const float2* st; };
+MMActSide mm_enc_act_side(MMPlan& P, int l) {
+    const MMChains t = mm_chains(P.w);
+    const ConvL& Lp = P.conv[l - 1];
+    return MMActSide{P.bn[Lp.bn], t.r[l - 1], t.a[l - 1], P.B * Lp.g.OH * Lp.g.OW, P.w.st_e[l - 2]};
+}
+MMActSide mm_dec_act_side(MMPlan& P, int l) {
+    const MMChains t = mm_chains(P.w);
+    const ConvL& Lp = P.convT[l - 1];
+    return MMActSide{P.bn[Lp.bn], t.q[l], t.aq[l], P.B * Lp.g.OH * Lp.g.OW, P.w.st_d[l - 1]};
+}
+int mm_act_side(MMPlan& P, const MMActSide& x, int groups, int training, hipStream_t s) {
+    return bn_act_side(P, x.b, x.r, x.a, groups * x.rows_per_group, x.rows_per_group, groups, x.st, training, s);
+}
+// last transposed conv (32 -> 1) + sigmoid (+ BCE and its gradient): `last` carries the caller's target / outputs / loss weights
+ConvTLastFwdArgs mm_dec_last_args(MMPlan& P, const ConvTLastFwdArgs& last, int groups) {
+    ConvTLastFwdArgs x = last;
+    x.act = P.w.aq3; x.w = P.buf.params + P.convT[3].w_off; x.G = groups; x.B = P.B; x.IH = 25; x.IW = 25; x.Cin = 32; x.Cout = 1;
+    return x;
+}
+
+// Staging transforms of the fused step (gemm.h GatherTransform; image-resident kernels only): `tr` is read by the launcher and
+// must outlive the launch.  With knob mm_stage_out (read here, when the launch is issued) the staged tensor is also left behind
+// for the weight gradient (GatherTransform::out).
+// kind 1: forward layer l stages Swish(BatchNorm(raw output of the layer below)) itself, writes that layer's tables and updates
+// its running statistics; out: a[l - 1] / aq[l], the operand of this layer's weight gradient
+void mm_stage_fwd_enc(MMPlan& P, int l, GemmParams& g, GatherTransform& tr, int bn_updates, int training) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const ConvL& Lp = P.conv[l - 1];
+    tr.kind = 1;
+    tr.fin = bn_fin_args(P, P.bn[Lp.bn], P.B * Lp.g.OH * Lp.g.OW, 1, w.st_e[l - 2], bn_updates, w.aff_e[l - 2], w.mr_e[l - 2], training);
+    if (mmvae_knob(K_mm_stage_out)) tr.out = t.a[l - 1];
+    g.c.A = t.r[l - 1]; g.tr = &tr;
+}
+void mm_stage_fwd_dec(MMPlan& P, int l, int groups, GemmParams& g, GatherTransform& tr, int training) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const ConvL& Lp = P.convT[l - 1];
+    tr.kind = 1;
+    tr.fin = bn_fin_args(P, P.bn[Lp.bn], P.B * Lp.g.OH * Lp.g.OW, groups, w.st_d[l - 1], 1, w.aff_d[l - 1], w.mr_d[l - 1], training);
+    if (mmvae_knob(K_mm_stage_out)) tr.out = t.aq[l];
+    g.c.A = t.q[l]; g.tr = &tr;
+}
+// kind 2: the data gradient of layer l applies the BatchNorm backward of the layer's own BatchNorm to db while staging it.  Not
+// in place: out is drr[l] / dqr[l + 1], a buffer apart from db, and with it go the BatchNorm parameter gradients -- in the
+// encoder for conv3 alone (conv2's dr and parameter gradients come from the bn_bwd_apply launch in front of its weight gradient)
+void mm_stage_bwd_enc(MMPlan& P, int l, GemmParams& d, GatherTransform& tr) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const ConvL& L = P.conv[l];
+    const BnL& b = P.bn[L.bn];
+    tr.kind = 2; tr.r = t.r[l]; tr.red = w.red_e[l - 1]; tr.mr = w.mr_e[l - 1]; tr.gamma = P.buf.params + b.w_off;
+    tr.inv_cnt = 1.f / (float)(P.B * L.g.OH * L.g.OW); tr.groups = 1;
+    if (l == 2 && mmvae_knob(K_mm_stage_out)) { tr.out = t.drr[l]; tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off; }
+    d.tr = &tr;
+}
+void mm_stage_bwd_dec(MMPlan& P, int l, int groups, GemmParams& d, GatherTransform& tr) {
+    MMPlan::W& w = P.w;
+    const MMChains t = mm_chains(w);
+    const ConvL& L = P.convT[l];
+    const BnL& b = P.bn[L.bn];
+    tr.kind = 2; tr.r = t.q[l + 1]; tr.red = w.red_d[l]; tr.mr = w.mr_d[l]; tr.gamma = P.buf.params + b.w_off;
+    tr.inv_cnt = 1.f / (float)(P.B * L.g.OH * L.g.OW); tr.groups = groups;
+    if (mmvae_knob(K_mm_stage_out)) { tr.out = t.dqr[l + 1]; tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off; }
+    d.tr = &tr;
+}
+
+// ---- the row-block launches of mlp_tail.hip: the block their plain and their waist (Mlp2Latent1*) forms share.  waist: the copies of
+// classifier.6 at the widths of 2D (wa_*; at n_latents = 100 they are the mt_* ones)
+// classifier.3 + Swish + Dropout + classifier.6 on ay1; mask: keep flags of the second Dropout or null
+void mm_mlp2_fwd_args(MMPlan& P, Mlp2FwdArgs& a, bool waist, int rows, const uint8_t* mask, float* out) {
+    MMPlan::W& w = P.w;
+    a.rows = rows; a.x = w.ay1;
+    a.w2 = P.buf.packed + P.pk.d[waist ? P.wa_w2 : P.mt_w2].dst_off; a.b2 = P.buf.params + P.fc[1].b_off;
+    a.w3 = P.buf.packed + P.pk.d[waist ? P.wa_w3 : P.mt_w3].dst_off; a.b3 = P.buf.params + P.fc[2].b_off;
+    if (mask) { a.mask = mask; a.mask_scale = 1.f / (1.f - DROP_P); }
+    a.y2 = w.y2; a.ay2 = w.ay2; a.out = out;
+}
+// both data gradients and the bias gradients of classifier.3 / classifier.0; m1 / m2: keep flags of the two Dropouts, or both null
+void mm_mlp2_bwd_args(MMPlan& P, Mlp2BwdArgs& a, bool waist, int rows, const uint8_t* m1, const uint8_t* m2) {
+    MMPlan::W& w = P.w;
+    a.rows = rows;
+    a.w3t = P.buf.packed + P.pk.d[waist ? P.wa_w3t : P.mt_w3t].dst_off; a.w2t = P.buf.packed + P.pk.d[waist ? P.wa_w2t : P.mt_w2t].dst_off;
+    a.y2 = w.y2; a.y1 = w.y1;
+    if (m1 || m2) { a.mask2 = m2; a.mask1 = m1; a.mask_scale = 1.f / (1.f - DROP_P); }
+    a.dy2 = w.dy2; a.dy1 = w.dy1;
+    a.db2 = P.buf.grads + P.fc[1].b_off; a.db1 = P.buf.grads + P.fc[0].b_off;
+}
+
 // ================================================================== image encoder
 // convs once on B images; classifier on variants*B rows (different dropout masks): multimnist/model.py:183-188
 // Every layer output is kept twice: raw (r*, y*: backward needs the pre-activation) and activated (a*: the next
@@ -257,103 +579,39 @@ int enc_fwd(MMPlan& P, const float* image, int variants, const uint8_t* m1, cons
     const int B = P.B;
     const int rows = variants * B;
     const bool drop = training && dropout;
-    const float ms = 1.f / (1.f - DROP_P);
+    const uint8_t *k1 = drop ? m1 : nullptr, *k2 = drop ? m2 : nullptr;
     if (!tail_only) {      // (tail_only: classifier.3 onwards, on the ay1 of an earlier call -- mm_bench_layer's replay of the image step's middle)
     if (fuse && mmvae_knob(K_mm_conv1_mfma)) {      // one workgroup per image on the matrix cores (conv1.hip)
         const PackDesc& d = P.pk.d[P.conv[0].pk_fwd[0]];
         MMVAE_TRY(launch_conv1_fwd_mfma(image, B, P.buf.packed + d.dst_off, d.Kpad, w.r1, w.a1, s));
     } else {
-    MMVAE_TRY(launch_im2col_small(image, B, 1, IMG, IMG, 4, 4, 2, 1, 25, 25, w.patches1, 16, s));
-    {   // conv1 + Swish (no BatchNorm): the epilogue emits raw and activated
-        GatherPlan pl = dense_plan(B * 625, 16, 16, 32);
-        GemmParams g = gemm_of(P, pl, P.conv[0].pk_fwd, 1, B * 625);
-        g.c.A = w.patches1; g.out_bf = w.r1; g.ldo = 32; g.out_act_bf = w.a1; g.e_act = ACT_SWISH;
-        MMVAE_TRY(launch_gemm_gather(g, s));
+        MMVAE_TRY(launch_im2col_small(image, B, 1, IMG, IMG, 4, 4, 2, 1, 25, 25, w.patches1, 16, s));
+        MMVAE_TRY(launch_gemm_gather(mm_gemm(P, MM_ENC_CONV1, 0, 1), s));
     }
-    }
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
     for (int l = 1; l < 4; ++l) {
-        const ConvL& L = P.conv[l];
-        GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, 1, B, L.pk_fwd_f);
-        g.c.A = a[l - 1];
-        g.out_bf = r[l]; g.ldo = L.g.Cout;
-        g.colstats = training ? w.st_e[l - 1] : nullptr;
+        GemmParams g = mm_gemm(P, MM_ENC_CONV, l, 1, training);
         GatherTransform tr{};
-        if (fuse && l >= 2) {          // conv3 / conv4 stage Swish(BatchNorm(raw output of the layer below)) themselves
-            const int prows = B * P.conv[l - 1].g.OH * P.conv[l - 1].g.OW;
-            tr.kind = 1;
-            tr.fin = bn_fin_args(P, P.bn[P.conv[l - 1].bn], prows, 1, w.st_e[l - 2], bn_updates, w.aff_e[l - 2], w.mr_e[l - 2], training);
-            g.c.A = r[l - 1]; g.tr = &tr;
-            if (mmvae_knob(K_mm_stage_out)) tr.out = a[l - 1];      // a2 / a3: operands of the weight gradients, a by-product of the staging
-        }
+        // conv3 / conv4 stage Swish(BatchNorm(raw output of the layer below)) themselves; a2 / a3, the operands of their weight
+        // gradients, are a by-product of the staging
+        if (fuse && l >= 2) mm_stage_fwd_enc(P, l, g, tr, bn_updates, training);
         MMVAE_TRY(launch_gemm_gather(g, s));
-        const int rows = B * L.g.OH * L.g.OW;
         if (fuse && l <= 2) continue;  // a2 / a3 are made in front of the next layer's weight gradient (enc_bwd)
-        MMVAE_TRY(bn_act(P, P.bn[L.bn], r[l], a[l], rows, rows, 1, w.st_e[l - 1], bn_updates, w.aff_e[l - 1], w.mr_e[l - 1], training, s));
+        MMVAE_TRY(mm_enc_bn_act(P, l, bn_updates, training, s));
     }
-    {   // fc1 over the NHWC 2x2x256 map (shared by the variants)
-        GatherPlan pl = plan_fwdform(2, 2, 1, 1, 256, 2, 2, 1, 0, 400, 1, rows);
-        GemmParams g = gemm_of(P, pl, &P.fc[0].pk_fwd, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.bias = P.buf.params + P.fc[0].b_off; g.out_bf = w.y1; g.ldo = 400;
-        g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; if (drop) { g.e_mask = m1; g.e_mask_scale = ms; }
-        MMVAE_TRY(launch_gemm_gather(g, s));
-    }
+    MMVAE_TRY(launch_gemm_gather(mm_gemm(P, MM_FC1, 0, variants, training, k1), s));
     }
     if (waist) {           // image-only step: the same launch goes on to (mu | logvar), z and the KL partials (the caller's fields)
         Mlp2Latent1FwdArgs a = *waist;
-        a.rows = rows; a.x = w.ay1;
-        a.w2 = P.buf.packed + P.pk.d[P.wa_w2].dst_off; a.b2 = P.buf.params + P.fc[1].b_off;
-        a.w3 = P.buf.packed + P.pk.d[P.wa_w3].dst_off; a.b3 = P.buf.params + P.fc[2].b_off;
-        if (drop) { a.mask = m2; a.mask_scale = ms; }
-        a.y2 = w.y2; a.ay2 = w.ay2; a.out = out;
+        mm_mlp2_fwd_args(P, a, true, rows, k2, out);
         return launch_mlp2_latent1_fwd(a, s);
     }
     if (P.mlp_tail) {      // classifier.3 + Swish + Dropout + classifier.6 in one row-block launch
         Mlp2FwdArgs a{};
-        a.rows = rows; a.x = w.ay1;
-        a.w2 = P.buf.packed + P.pk.d[P.mt_w2].dst_off; a.b2 = P.buf.params + P.fc[1].b_off;
-        a.w3 = P.buf.packed + P.pk.d[P.mt_w3].dst_off; a.b3 = P.buf.params + P.fc[2].b_off;
-        if (drop) { a.mask = m2; a.mask_scale = ms; }
-        a.y2 = w.y2; a.ay2 = w.ay2; a.out = out;
+        mm_mlp2_fwd_args(P, a, false, rows, k2, out);
         return launch_mlp2_fwd(a, s);
     }
-    {
-        GatherPlan pl = dense_plan(rows, 400, 400, 200);
-        GemmParams g = gemm_of(P, pl, &P.fc[1].pk_fwd, 1, rows);
-        g.c.A = w.ay1;
-        g.bias = P.buf.params + P.fc[1].b_off; g.out_bf = w.y2; g.ldo = 200;
-        g.out_act_bf = w.ay2; g.e_act = ACT_SWISH; if (drop) { g.e_mask = m2; g.e_mask_scale = ms; }
-        MMVAE_TRY(launch_gemm_gather(g, s));
-    }
-    {
-        GatherPlan pl = dense_plan(rows, 200, 200, 2 * P.D);
-        GemmParams g = gemm_of(P, pl, &P.fc[2].pk_fwd, 1, rows);
-        g.c.A = w.ay2;
-        g.bias = P.buf.params + P.fc[2].b_off; g.out_f = out; g.ldo = 2 * P.D;
-        MMVAE_TRY(launch_gemm_gather(g, s));
-    }
-    return MMVAE_OK;
-}
-
-// classifier.0's data gradient: 4 classes = the 4 pixels of the 2x2 map, each with its own [256][400] matrix; the NHWC gradients
-// of `rows` samples (both dropout variants) against the map the B images share, with the BatchNorm-backward sums of conv4
-static GemmParams fc1_dgrad_gemm(MMPlan& P, int rows) {
-    MMPlan::W& w = P.w;
-    GatherPlan pd{};
-    pd.c.AH = 1; pd.c.AW = 1; pd.c.Ald = 400; pd.c.C = 400; pd.c.sy = pd.c.sx = 1; pd.c.dy = pd.c.dx = 1;
-    pd.c.OH = 2; pd.c.OW = 2; pd.c.osy = pd.c.osx = 1; pd.c.N = 256; pd.c.nclasses = 4;
-    for (int sidx = 0; sidx < 4; ++sidx) {
-        GatherClass& k = pd.cls[sidx];
-        k.OY = 1; k.OX = 1; k.TH = 1; k.TW = 1; k.offy = 0; k.offx = 0; k.ooy = sidx / 2; k.oox = sidx % 2;
-        k.K = 400; k.Kpad = round_up(400, 64);
-    }
-    GemmParams d = gemm_of(P, pd, P.fc[0].pk_dgrad4, 1, rows);
-    d.c.A = w.dy1; d.out_bf = w.db4; d.ldo = 256;
-    d.d_r = w.r4; d.d_ld = 256; d.d_bcast_n = P.B; d.d_act = ACT_SWISH;
-    d.d_affine = w.aff_e[2]; d.d_meanrstd = w.mr_e[2]; d.d_red = w.red_e[2];
-    return d;
+    MMVAE_TRY(launch_gemm_gather(mm_gemm(P, MM_FC2, 0, variants, training, k2), s));
+    return launch_gemm_gather(mm_gemm(P, MM_FC3, 0, variants, training, nullptr, out), s);
 }
 
 // d_out: bf16 [variants*B][lde], columns 2D.. zero (the generic kernels read their operands in 8-column vectors; 2D is a multiple
@@ -362,19 +620,22 @@ static GemmParams fc1_dgrad_gemm(MMPlan& P, int rows) {
 int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const uint8_t* m2, int dropout, hipStream_t s, bool fuse = false,
             const Mlp2Latent1BwdArgs* waist = nullptr, float* loss_out = nullptr, bool tail_only = false) {
     MMPlan::W& w = P.w;
-    const int B = P.B, rows = variants * B, D2 = 2 * P.D;
-    const float ms = 1.f / (1.f - DROP_P);
+    const MMChains t = mm_chains(w);
+    const int B = P.B, rows = variants * B;
+    const uint8_t *k1 = dropout ? m1 : nullptr, *k2 = dropout ? m2 : nullptr;
     // fused step: the three classifier weight gradients (0.04-0.4 GFLOP each, every one a launch at the kernel-latency floor) go
     // out as ONE grouped launch behind conv4's data gradient
+    const bool grouped = fuse && P.mlp_tail && !waist;
     auto cls_w = std::make_shared<std::vector<WgradParams>>();
+    auto cls_wgrad = [&](const WgradParams& g) {
+        if (!grouped) return wgrad_async(P, g, s);
+        cls_w->push_back(g);
+        return (int)MMVAE_OK;
+    };
+    const WgradParams g3 = mm_wgrad(P, MM_W_FC3, 0, variants, d_out), g2 = mm_wgrad(P, MM_W_FC2, 0, variants);
     if (waist) {           // latent backward + both data gradients in one row-block launch
         Mlp2Latent1BwdArgs a = *waist;
-        a.rows = rows;
-        a.w3t = P.buf.packed + P.pk.d[P.wa_w3t].dst_off; a.w2t = P.buf.packed + P.pk.d[P.wa_w2t].dst_off;
-        a.y2 = w.y2; a.y1 = w.y1;
-        if (dropout) { a.mask2 = m2; a.mask1 = m1; a.mask_scale = ms; }
-        a.dy2 = w.dy2; a.dy1 = w.dy1;
-        a.db2 = P.buf.grads + P.fc[1].b_off; a.db1 = P.buf.grads + P.fc[0].b_off;
+        mm_mlp2_bwd_args(P, a, true, rows, k1, k2);
         a.d_enc_out = w.d_encout; a.lde = P.lde;
         MMVAE_TRY(launch_mlp2_latent1_bwd(a, s));
         {   // the fold of the partials (KL of the forward, classifier.6's bias gradient) and the loss sums: nobody on the main chain
@@ -383,143 +644,66 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
             MMVAE_TRY(wgrad_side_stream(P, s, &fs));
             MMVAE_TRY(launch_mlp2_latent1_finish(a.scratch, rows, P.D, P.buf.grads + P.fc[2].b_off, w.sums, loss_out, fs));
         }
-        GatherPlan p3 = dense_plan(rows, 200, 200, D2);
-        WgradParams g3 = wgrad_of(P, p3, &P.fc[2].gk, 1, rows);
-        g3.c.A = w.ay2; g3.P = w.d_encout; g3.ldp = P.lde;
-        MMVAE_TRY(wgrad_async(P, g3, s));
-        GatherPlan p2 = dense_plan(rows, 400, 400, 200);
-        WgradParams g2 = wgrad_of(P, p2, &P.fc[1].gk, 1, rows);
-        g2.c.A = w.ay1; g2.P = w.dy2; g2.ldp = 200;
-        MMVAE_TRY(wgrad_async(P, g2, s));
+        MMVAE_TRY(cls_wgrad(g3));
+        MMVAE_TRY(cls_wgrad(g2));
     } else if (P.mlp_tail) {      // both data gradients in one row-block launch; the weight gradients follow on the side stream
-        {
-            GatherPlan pl = dense_plan(rows, 200, 200, D2);
-            WgradParams g = wgrad_of(P, pl, &P.fc[2].gk, 1, rows);
-            g.c.A = w.ay2; g.P = d_out; g.ldp = P.lde;
-            if (fuse) cls_w->push_back(g);
-            else MMVAE_TRY(wgrad_async(P, g, s));
-        }
+        MMVAE_TRY(cls_wgrad(g3));
         Mlp2BwdArgs a{};
-        a.rows = rows; a.d_out = d_out;
-        a.w3t = P.buf.packed + P.pk.d[P.mt_w3t].dst_off; a.w2t = P.buf.packed + P.pk.d[P.mt_w2t].dst_off;
-        a.y2 = w.y2; a.y1 = w.y1;
-        if (dropout) { a.mask2 = m2; a.mask1 = m1; a.mask_scale = ms; }
-        a.dy2 = w.dy2; a.dy1 = w.dy1;
-        a.db2 = P.buf.grads + P.fc[1].b_off; a.db1 = P.buf.grads + P.fc[0].b_off;
+        mm_mlp2_bwd_args(P, a, false, rows, k1, k2);
+        a.d_out = d_out;
         MMVAE_TRY(launch_mlp2_bwd(a, s));
-        GatherPlan pl = dense_plan(rows, 400, 400, 200);
-        WgradParams g = wgrad_of(P, pl, &P.fc[1].gk, 1, rows);
-        g.c.A = w.ay1; g.P = w.dy2; g.ldp = 200;
-        if (fuse) cls_w->push_back(g);
-        else MMVAE_TRY(wgrad_async(P, g, s));
+        MMVAE_TRY(cls_wgrad(g2));
     } else {
-    {   // fc3
-        GatherPlan pl = dense_plan(rows, 200, 200, D2);
-        WgradParams g = wgrad_of(P, pl, &P.fc[2].gk, 1, rows);
-        g.c.A = w.ay2; g.P = d_out; g.ldp = P.lde;
-        MMVAE_TRY(wgrad_async(P, g, s));
-        GatherPlan pd = dense_plan(rows, P.lde, P.lde, 200);     // K = lde: the zero pad columns meet the zero pad of the packed weights
-        GemmParams d = gemm_of(P, pd, &P.fc[2].pk_dgrad, 1, rows);
-        d.c.A = d_out; d.out_bf = w.dy2; d.ldo = 200;
-        d.d_r = w.y2; d.d_ld = 200; d.d_act = ACT_SWISH; if (dropout) { d.d_mask = m2; d.d_mask_scale = ms; }
-        d.d_colsum = P.buf.grads + P.fc[1].b_off;
-        MMVAE_TRY(launch_gemm_gather(d, s));
-    }
-    {   // fc2
-        GatherPlan pl = dense_plan(rows, 400, 400, 200);
-        WgradParams g = wgrad_of(P, pl, &P.fc[1].gk, 1, rows);
-        g.c.A = w.ay1; g.P = w.dy2; g.ldp = 200;
-        MMVAE_TRY(wgrad_async(P, g, s));
-        GatherPlan pd = dense_plan(rows, 200, 200, 400);
-        GemmParams d = gemm_of(P, pd, &P.fc[1].pk_dgrad, 1, rows);
-        d.c.A = w.dy2; d.out_bf = w.dy1; d.ldo = 400;
-        d.d_r = w.y1; d.d_ld = 400; d.d_act = ACT_SWISH; if (dropout) { d.d_mask = m1; d.d_mask_scale = ms; }
-        d.d_colsum = P.buf.grads + P.fc[0].b_off;
-        MMVAE_TRY(launch_gemm_gather(d, s));
-    }
+        MMVAE_TRY(cls_wgrad(g3));
+        MMVAE_TRY(launch_gemm_gather(mm_gemm(P, MM_FC3_DGRAD, 0, variants, 1, k2, d_out), s));
+        MMVAE_TRY(cls_wgrad(g2));
+        MMVAE_TRY(launch_gemm_gather(mm_gemm(P, MM_FC2_DGRAD, 0, variants, 1, k1), s));
     }
     if (tail_only) return MMVAE_OK;        // (down to classifier.0's output gradient: mm_bench_layer's replay of the image step's middle)
-    {   // fc1: wgrad gathers the shared 2x2x256 map; dgrad emits NHWC gradients for `rows` samples
-        GatherPlan pl = plan_fwdform(2, 2, 1, 1, 256, 2, 2, 1, 0, 400, 1, rows);
-        WgradParams g = wgrad_of(P, pl, &P.fc[0].gk, 1, rows);
-        g.c.A = w.a4; g.c.a_bcast_n = B;
-        g.P = w.dy1; g.ldp = 400;
-        if (P.mlp_tail && fuse) {
-            MMPlan* pp = &P;
-            cls_w->push_back(g);
-            side_later(P, [pp, cls_w](hipStream_t ws_) {
-                MMVAE_TRY(launch_wgrad_group(cls_w->data(), (int)cls_w->size(), ws_, &pp->slab));
-                return pp->batch_reduce ? MMVAE_OK : launch_wgrad_reduce(&pp->slab, ws_, true);
-            }, mmvae_knob(K_mm_cls_lane));
-        } else {
-            MMVAE_TRY(wgrad_async(P, g, s));
-        }
-        MMVAE_TRY(launch_gemm_gather(fc1_dgrad_gemm(P, rows), s));
+    // classifier.0: the weight gradient gathers the shared 2x2x256 map; the data gradient emits NHWC gradients for `rows` samples
+    MMVAE_TRY(cls_wgrad(mm_wgrad(P, MM_W_FC1, 0, variants)));
+    if (grouped) {
+        MMPlan* pp = &P;
+        side_later(P, [pp, cls_w](hipStream_t ws_) {
+            MMVAE_TRY(launch_wgrad_group(cls_w->data(), (int)cls_w->size(), ws_, &pp->slab));
+            return pp->batch_reduce ? MMVAE_OK : launch_wgrad_reduce(&pp->slab, ws_, true);
+        }, mmvae_knob(K_mm_cls_lane));
     }
+    MMVAE_TRY(launch_gemm_gather(mm_gemm(P, MM_FC1_DGRAD, 0, variants), s));
     // ---- conv stack (features shared by all variants: gradients of the variants add up)
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    bf16* dr[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    bf16* drr[4] = {nullptr, w.d2er, w.d3er, nullptr};       // fused layers: BatchNorm-backward output apart from db
     for (int l = 3; l >= 1; --l) {
-        const ConvL& L = P.conv[l];
-        const BnL& b = P.bn[L.bn];
-        const int pix = L.g.OH * L.g.OW;
         // conv3 / conv2: the image-resident data-gradient kernel applies the BatchNorm backward to db while staging it
         // (GatherTransform kind 2); the materialised dr is only the weight gradient's operand and is made in front of it,
         // off the main chain, into a buffer of its own (db is still being read by the data gradient)
         const bool fl = fuse && l < 3;
-        BnBwdApplyArgs x{};
-        x.db = (l == 3) ? w.db4 : dr[l];
-        x.db2 = (l == 3 && variants == 2) ? w.db4 + (size_t)B * 1024 : nullptr;
-        x.r = r[l]; x.dr = fl ? drr[l] : dr[l]; x.rows = B * pix; x.C = L.g.Cout; x.ld = L.g.Cout; x.rows_per_group = B * pix; x.G = 1;
-        x.red = w.red_e[l - 1]; x.meanrstd = w.mr_e[l - 1]; x.gamma = P.buf.params + b.w_off;
-        x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
+        const BnBwdApplyArgs x = mm_enc_bn_bwd_args(P, l, variants, fl ? t.drr[l] : t.dr[l]);
         if (!fl) MMVAE_TRY(launch_bn_bwd_apply(x, s));
-        // wgrad: P = dr[l] (rows over the output grid), G = activated input gathered in forward form.  Forks are bound to a
-        // producer kernel's completion: a fused layer's operands came out of the previous data gradient (the current event);
-        // the unfused conv4 issues its weight gradient behind its own data gradient, on the event conv3's needs anyway
-        WgradParams gw = wgrad_of(P, L.fwd, L.gk, 1, B);
-        gw.c.A = a[l - 1]; gw.P = x.dr; gw.ldp = L.g.Cout;
+        // Forks are bound to a producer kernel's completion: a fused layer's operands came out of the previous data gradient (the
+        // current event); the unfused conv4 issues its weight gradient behind its own data gradient, on the event conv3's needs anyway
+        const WgradParams gw = mm_wgrad(P, MM_W_ENC_CONV, l, 1, x.dr);
         if (fuse) {
             // fused layers (conv3, conv2): the weight gradient runs on a side stream on operands that are by-products of the main
-            // chain's staging (GatherTransform::out) or are materialised right in front of it, off the main chain
+            // chain's staging (GatherTransform::out) or are materialised right in front of it, off the main chain.
+            // With staging by-products the forward of conv3 / conv4 left a2 / a3 behind and conv3's data gradient below
+            // leaves its BatchNorm-backward dr behind: nothing to materialise in front of the kernel
             MMPlan* pp = &P;
-            {
-                // With staging by-products the forward of conv3 / conv4 left a2 / a3 behind and conv3's data gradient below
-                // leaves its BatchNorm-backward dr behind: nothing to materialise in front of the kernel
-                const bool byp = mmvae_knob(K_mm_stage_out) != 0;
-                const bool actp = l >= 2 && !byp;      // a[l-1] = Swish(BatchNorm(r[l-1])) was never materialised (conv3, conv4)
-                const bool bnb = fl && !(byp && l == 2);
-                const int prows = B * P.conv[l >= 2 ? l - 1 : 1].g.OH * P.conv[l >= 2 ? l - 1 : 1].g.OW;
-                const BnL bp = P.bn[P.conv[l >= 2 ? l - 1 : 1].bn];
-                const bf16* rin = r[l >= 2 ? l - 1 : 1]; bf16* ao = a[l >= 2 ? l - 1 : 1]; const float2* st = w.st_e[l >= 2 ? l - 2 : 0];
-                WgradParams g0 = wgrad_of(P, L.fwd, L.gk, 1, B);
-                g0.c.A = a[l - 1]; g0.P = x.dr; g0.ldp = L.g.Cout;
-                // lane 1: the LAST weight gradients of the step (conv3's, conv2's) go to the second-modality stream -- it has run dry
-                // by then, and the weight-gradient stream still holds the classifier's and conv4's
-                side_later(P, [pp, x, g0, bnb, actp, bp, rin, ao, st, prows](hipStream_t ws_) {
-                    if (bnb) MMVAE_TRY(launch_bn_bwd_apply(x, ws_));
-                    if (actp) MMVAE_TRY(bn_act_side(*pp, bp, rin, ao, prows, prows, 1, st, 1, ws_));
-                    return wgrad_on(*pp, g0, ws_);
-                }, l == 1 ? 1 : l == 2 ? mmvae_knob(K_mm_conv3_lane) : mmvae_knob(K_mm_conv4_lane));
-            }
-            if (fuse && l == 1) MMVAE_TRY(side_flush(P, s));    // conv2's: its operands came out of conv3's data gradient (current event)
+            const bool byp = mmvae_knob(K_mm_stage_out) != 0;
+            const bool actp = l >= 2 && !byp;      // a[l-1] = Swish(BatchNorm(r[l-1])) was never materialised (conv3, conv4)
+            const bool bnb = fl && !(byp && l == 2);
+            const MMActSide as = actp ? mm_enc_act_side(P, l) : MMActSide{};
+            // lane 1: the LAST weight gradients of the step (conv3's, conv2's) go to the second-modality stream -- it has run dry
+            // by then, and the weight-gradient stream still holds the classifier's and conv4's
+            side_later(P, [pp, x, gw, bnb, actp, as](hipStream_t ws_) {
+                if (bnb) MMVAE_TRY(launch_bn_bwd_apply(x, ws_));
+                if (actp) MMVAE_TRY(mm_act_side(*pp, as, 1, 1, ws_));
+                return wgrad_on(*pp, gw, ws_);
+            }, l == 1 ? 1 : l == 2 ? mmvae_knob(K_mm_conv3_lane) : mmvae_knob(K_mm_conv4_lane));
+            if (l == 1) MMVAE_TRY(side_flush(P, s));    // conv2's: its operands came out of conv3's data gradient (current event)
         }
-        {   // dgrad (class form) with the d-activation of the producer layer fused in the epilogue
-            GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
-            d.c.A = dr[l]; d.out_bf = dr[l - 1]; d.ldo = L.g.Cin;
-            d.d_r = r[l - 1]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-            if (l > 1) { d.d_affine = w.aff_e[l - 2]; d.d_meanrstd = w.mr_e[l - 2]; d.d_red = w.red_e[l - 2]; }
+        {
+            GemmParams d = mm_gemm(P, MM_ENC_CONV_DGRAD, l, 1);
             GatherTransform tr{};
-            if (fl) {
-                tr.kind = 2; tr.r = r[l]; tr.red = w.red_e[l - 1]; tr.mr = w.mr_e[l - 1]; tr.gamma = P.buf.params + b.w_off;
-                tr.inv_cnt = 1.f / (float)(B * pix); tr.groups = 1;
-                if (l == 2 && mmvae_knob(K_mm_stage_out)) {      // conv3: dr for its weight gradient + the BatchNorm parameter gradients
-                    tr.out = drr[l]; tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off;
-                }
-                d.tr = &tr;
-            }
+            if (fl) mm_stage_bwd_enc(P, l, d, tr);      // conv3 also leaves dr for its weight gradient + the BatchNorm parameter gradients
             // forks: behind conv4's data gradient (classifier + conv4 + conv3 weight gradients) and behind conv3's (conv2's)
             // (knob mm_forks = 1: ONE fork for the whole encoder backward, behind conv3's data gradient -- a kernel that carries a
             //  completion event ends with a system-scope release, ~8 us on the main chain per fork: tools/step_parts.py)
@@ -533,17 +717,13 @@ int enc_bwd(MMPlan& P, const bf16* d_out, int variants, const uint8_t* m1, const
     if (fuse && !P.wgrad_forked) MMVAE_TRY(side_flush(P, s));     // unforked (serial) use: nothing to wait for
     if (fuse && mmvae_knob(K_mm_conv1_mfma) && P.step_image) {       // the LAST kernel of the backward chain: conv1.hip
         const PackDesc& gd = P.gk.d[P.conv[0].gk[0]];
-        MMVAE_TRY(launch_conv1_wgrad_mfma(P.step_image, B, w.d1e, P.buf.gpk + gd.dst_off, gd.Kpad, s));
-    } else {   // conv1 wgrad over the im2col patches: the LAST kernel of the backward chain -- it stays on the main stream (a hop
-        // to a side stream and back would put two event latencies on the critical path)
-        GatherPlan pl = dense_plan(B * 625, 16, 16, 32);
-        WgradParams g = wgrad_of(P, pl, P.conv[0].gk, 1, B * 625);
-        g.c.A = w.patches1; g.P = w.d1e; g.ldp = 32;
-        // fp32 atomics into the (zeroed) packed gradient instead of slab copies + a reduce launch: this is the last kernel in
-        // front of the optimizer, a second launch here is pure tail latency (the tile is 32 x 16)
-        MMVAE_TRY(launch_wgrad(g, s, nullptr));
+        return launch_conv1_wgrad_mfma(P.step_image, B, w.d1e, P.buf.gpk + gd.dst_off, gd.Kpad, s);
     }
-    return MMVAE_OK;
+    // conv1 wgrad over the im2col patches: the LAST kernel of the backward chain -- it stays on the main stream (a hop to a side
+    // stream and back would put two event latencies on the critical path).  fp32 atomics into the (zeroed) packed gradient instead
+    // of slab copies + a reduce launch: this is the last kernel in front of the optimizer, a second launch here is pure tail
+    // latency (the tile is 32 x 16)
+    return launch_wgrad(mm_wgrad(P, MM_W_ENC_CONV1, 0, 1), s, nullptr);
 }
 
 // ================================================================== image decoder (multimnist/model.py:211-216)
@@ -555,18 +735,11 @@ int fused_tail(MMPlan& P, int groups, int training, const ConvTLastFwdArgs* last
     MMPlan::W& w = P.w;
     const int B = P.B;
     const ConvL& L = P.convT[2];
-    const BnL& b = P.bn[L.bn];
     DecLastFusedArgs x{};
     x.r = w.q3; x.act = ACT_SWISH; x.w = P.buf.params + P.convT[3].w_off;
     x.G = last_groups > 0 ? last_groups : groups; x.B = B; x.IH = 25; x.IW = 25; x.Cin = 32;
     x.bwd_groups = std::min(fused_bwd_groups, x.G);
-    BnFinalizeArgs& f = x.fin;
-    f.stats = w.st_d[2]; f.G = groups; f.C = b.C; f.count = (float)(B * L.g.OH * L.g.OW);
-    f.gamma = P.buf.params + b.w_off; f.beta = P.buf.params + b.b_off;
-    f.running_mean = P.buf.bn_stats + b.stat_off; f.running_var = P.buf.bn_stats + b.stat_off + b.C;
-    f.num_batches_tracked = P.buf.bn_nbt + b.idx;
-    f.updates_per_group = 1; f.affine = w.aff_d[2]; f.meanrstd = w.mr_d[2]; f.eps = BN_EPS; f.momentum = BN_MOM; f.training = training;
-    f.skip_update_mask = groups > 1 ? P.dec_skip_mask : 0u;
+    x.fin = bn_fin_args(P, P.bn[L.bn], B * L.g.OH * L.g.OW, groups, w.st_d[2], 1, w.aff_d[2], w.mr_d[2], training);
     x.target = last->target; x.logits = last->logits; x.recon = last->recon; x.dlogit = dlogit_dump;      // (the step keeps dlogit in LDS)
     for (int k = 0; k < 4; ++k) x.coef[k] = last->coef[k];
     x.loss_sum = last->loss_sum;
@@ -590,54 +763,28 @@ int fused_tail(MMPlan& P, int groups, int training, const ConvTLastFwdArgs* last
 // granular modules get their upstream gradient from autograd and keep the separate kernels).
 int dec_fwd(MMPlan& P, int groups, int training, ConvTLastFwdArgs* last, hipStream_t s, int last_groups = -1, int fused_bwd_groups = -1,
             bool fuse = false) {
-    MMPlan::W& w = P.w;
-    const int B = P.B, rows = groups * B;
-    {
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, 1024);
-        GemmParams g = gemm_of(P, pl, &P.up.pk_fwd, 1, rows);
-        g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = 1024; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
-        MMVAE_TRY(launch_gemm_gather(g, s));
-    }
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
+    MMVAE_TRY(launch_gemm_gather(mm_gemm(P, MM_UP, 0, groups), s));
     for (int l = 0; l < 3; ++l) {
-        const ConvL& L = P.convT[l];
-        {
-            GemmParams g = gemm_of(P, L.fwd, L.pk_fwd, groups, B, L.pk_fwd_f);
-            g.c.A = aq[l];
-            g.out_bf = q[l + 1]; g.ldo = L.g.Cout;
-            g.colstats = training ? w.st_d[l] : nullptr;
-            GatherTransform tr{};
-            if (fuse && l >= 1) {      // convT2 / convT3 stage Swish(BatchNorm(q[l])) themselves
-                const ConvL& Lp = P.convT[l - 1];
-                const int prpg = B * Lp.g.OH * Lp.g.OW;
-                tr.kind = 1;
-                tr.fin = bn_fin_args(P, P.bn[Lp.bn], prpg, groups, w.st_d[l - 1], 1, w.aff_d[l - 1], w.mr_d[l - 1], training);
-                g.c.A = q[l]; g.tr = &tr;
-                if (mmvae_knob(K_mm_stage_out)) tr.out = aq[l];     // operand of this layer's weight gradient, a by-product of the staging
-            }
-            MMVAE_TRY(launch_gemm_gather(g, s));
-        }
-        const int rpg = B * L.g.OH * L.g.OW;
+        GemmParams g = mm_gemm(P, MM_DEC_CONVT, l, groups, training);
+        GatherTransform tr{};
+        // convT2 / convT3 stage Swish(BatchNorm(q[l])) themselves; aq[l], the operand of this layer's weight gradient, is a
+        // by-product of the staging
+        if (fuse && l >= 1) mm_stage_fwd_dec(P, l, groups, g, tr, training);
+        MMVAE_TRY(launch_gemm_gather(g, s));
         if (l == 2 && fused_bwd_groups >= 0) continue;
         if (fuse && l <= 1) continue;  // aq[l+1] is made in front of the next layer's weight gradient (dec_bwd)
-        MMVAE_TRY(bn_act(P, P.bn[L.bn], q[l + 1], aq[l + 1], groups * rpg, rpg, groups, w.st_d[l], 1, w.aff_d[l], w.mr_d[l], training, s));
+        MMVAE_TRY(mm_dec_bn_act(P, l, groups, training, s));
     }
     if (fused_bwd_groups >= 0) return fused_tail(P, groups, training, last, last_groups, fused_bwd_groups, s);
-    ConvTLastFwdArgs x = *last;
-    x.act = w.aq3; x.w = P.buf.params + P.convT[3].w_off; x.G = last_groups > 0 ? last_groups : groups; x.B = B; x.IH = 25; x.IW = 25; x.Cin = 32; x.Cout = 1;
-    return launch_convt_last_fwd(x, s);
+    return launch_convt_last_fwd(mm_dec_last_args(P, *last, last_groups > 0 ? last_groups : groups), s);
 }
 
 // dlogit: fp32 NCHW [groups*B][1][50][50] (grad wrt the pre-sigmoid logits). Writes dz (fp32 [groups*B][D]).
 int dec_bwd(MMPlan& P, const float* dlogit, int groups, float* dz, hipStream_t s, bool last_fused = false, bool fuse = false,
             int fwd_groups = 0, int training = 1) {
     MMPlan::W& w = P.w;
-    const int B = P.B, rows = groups * B;
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    bf16* dqr[4] = {nullptr, w.d1r, w.d2r, w.d3r};         // fused layers: BatchNorm-backward output apart from db
+    const MMChains t = mm_chains(w);
+    MMPlan* pp = &P;
     if (last_fused) {
         // d3, the BatchNorm-backward sums and the weight-gradient partials of the last layer came out of the fused tail
         // (dec_fwd); only the sum of the partials is left, off the main chain
@@ -648,103 +795,59 @@ int dec_bwd(MMPlan& P, const float* dlogit, int groups, float* dz, hipStream_t s
                 return launch_wgrad_reduce(&pb->slab, wst, true);
             });
         }
-    } else {   // last transposed conv (32 -> 1): both gradients go through the im2col patches of dlogit (K = 16 taps):
-        // input gradient = dense GEMM patches x W (d-Swish + BatchNorm-backward sums in the epilogue), weight
-        // gradient = patches^T x activated input.  (The direct dot-product kernel convt_last_dgrad is VALU-bound:
-        // 52 us against 39 us for this GEMM at B=256.)
-        const ConvL& L = P.convT[3];
-        MMVAE_TRY(launch_im2col_small(dlogit, rows, 1, IMG, IMG, 4, 4, 2, 1, 25, 25, w.patches4, 16, s));
-        {
-            GatherPlan pd = dense_plan(B * 625, 16, 16, 32);
-            GemmParams d = gemm_of(P, pd, L.pk_dgrad, groups, B * 625);
-            d.c.A = w.patches4; d.out_bf = w.d3; d.ldo = 32;
-            d.d_r = w.q3; d.d_ld = 32; d.d_act = ACT_SWISH; d.d_affine = w.aff_d[2]; d.d_meanrstd = w.mr_d[2]; d.d_red = w.red_d[2];
-            arm_fork(P);
-            MMVAE_TRY(launch_gemm_gather(d, s));
-            MMVAE_TRY(commit_fork(P, s));
-        }
-        GatherPlan pl = plan_fwdform(1, 1, 25, 25, 16, 1, 1, 1, 0, 32, groups, B);   // rows (n, iy, ix), dense K=16
-        WgradParams g = wgrad_of(P, pl, L.gk, groups, B);
-        g.c.A = w.patches4; g.c.AH = 25; g.c.AW = 25; g.c.sy = g.c.sx = 1;
-        g.P = w.aq3; g.ldp = 32;
-        MMVAE_TRY(wgrad_async(P, g, s));
+    } else {   // last transposed conv (32 -> 1): both gradients go through the im2col patches of dlogit (K = 16 taps)
+        MMVAE_TRY(launch_im2col_small(dlogit, groups * P.B, 1, IMG, IMG, 4, 4, 2, 1, 25, 25, w.patches4, 16, s));
+        arm_fork(P);
+        MMVAE_TRY(launch_gemm_gather(mm_gemm(P, MM_DEC_LAST_DGRAD, 3, groups), s));
+        MMVAE_TRY(commit_fork(P, s));
+        MMVAE_TRY(wgrad_async(P, mm_wgrad(P, MM_W_DEC_LAST, 3, groups), s));
     }
     for (int l = 2; l >= 0; --l) {
-        const ConvL& L = P.convT[l];
-        const BnL& b = P.bn[L.bn];
-        const int pix = L.g.OH * L.g.OW;
         // convT3 / convT2: the image-resident data-gradient kernel applies the BatchNorm backward while it stages db
         // (GatherTransform kind 2); dr and the activated layer input are only the weight gradient's operands and are made in
         // front of it on the side stream (enc_bwd has the same arrangement)
         const bool fl = fuse;          // (hallucinate.0 too: its input is the upsample Linear's activation, no BatchNorm below it)
-        BnBwdApplyArgs x{};
-        x.db = dq[l + 1]; x.r = q[l + 1]; x.dr = fl ? dqr[l + 1] : dq[l + 1]; x.rows = rows * pix; x.C = L.g.Cout; x.ld = L.g.Cout;
-        x.rows_per_group = B * pix; x.G = groups;
-        x.red = w.red_d[l]; x.meanrstd = w.mr_d[l]; x.gamma = P.buf.params + b.w_off;
-        x.dgamma = P.buf.grads + b.w_off; x.dbeta = P.buf.grads + b.b_off;
+        const BnBwdApplyArgs x = mm_dec_bn_bwd_args(P, l, groups, fl ? t.dqr[l + 1] : t.dq[l + 1]);
         if (!fl) MMVAE_TRY(launch_bn_bwd_apply(x, s));
         // Forks are bound to a producer kernel's completion (arm_fork / commit_fork).  Fused layers: the operands of the
         // weight gradient came out of the previous data gradient (or the fused tail), whose event is the current one.  The
         // unfused first layer: its weight gradient is issued behind the layer's own data gradient, on the event the upsample
         // weight gradient needs anyway (one bound event less on the main chain)
-        WgradParams gw = convT_wgrad(P, L, groups, B, aq[l], x.dr);
+        const WgradParams gw = mm_wgrad(P, MM_W_DEC_CONVT, l, groups, x.dr);
         if (fl) {
-            MMPlan* pp = &P;
-            const ConvL& Lp = P.convT[l >= 1 ? l - 1 : 0];
-            const int prpg = B * Lp.g.OH * Lp.g.OW;
-            {
-                // the streamed weight-gradient kernel on operands materialised right in front of it, on the side stream: the
-                // BatchNorm backward of db (its own buffer: the data gradient on the main chain still reads db) and, above the
-                // first layer, the layer input aq[l] = Swish(BatchNorm(q[l])) that the forward never wrote
-                // (with staging by-products, GatherTransform::out, both come out of kernels of the main chain instead: aq[l]
-                //  out of this layer's forward, dr out of this layer's data gradient below -- the side work is the GEMM alone)
-                const bool byp = mmvae_knob(K_mm_stage_out) != 0;
-                const bool actp = l >= 1 && !byp;
-                const BnL bp = P.bn[Lp.bn];
-                const bf16* qin = q[l]; bf16* aqo = aq[l]; const float2* st = w.st_d[l >= 1 ? l - 1 : 0];
-                side_later(P, [pp, x, gw, byp, actp, bp, qin, aqo, st, groups, prpg, training](hipStream_t ws_) {
-                    if (!byp) MMVAE_TRY(launch_bn_bwd_apply(x, ws_));
-                    if (actp) MMVAE_TRY(bn_act_side(*pp, bp, qin, aqo, groups * prpg, prpg, groups, st, training, ws_));
-                    return wgrad_on(*pp, gw, ws_);
-                });
-            }
-        } else if (fuse || l == 0) {
-            MMPlan* pp = &P;
+            // the streamed weight-gradient kernel on operands materialised right in front of it, on the side stream: the
+            // BatchNorm backward of db (its own buffer: the data gradient on the main chain still reads db) and, above the
+            // first layer, the layer input aq[l] = Swish(BatchNorm(q[l])) that the forward never wrote
+            // (with staging by-products, GatherTransform::out, both come out of kernels of the main chain instead: aq[l]
+            //  out of this layer's forward, dr out of this layer's data gradient below -- the side work is the GEMM alone)
+            const bool byp = mmvae_knob(K_mm_stage_out) != 0;
+            const bool actp = l >= 1 && !byp;
+            const MMActSide as = actp ? mm_dec_act_side(P, l) : MMActSide{};
+            side_later(P, [pp, x, gw, byp, actp, as, groups, training](hipStream_t ws_) {
+                if (!byp) MMVAE_TRY(launch_bn_bwd_apply(x, ws_));
+                if (actp) MMVAE_TRY(mm_act_side(*pp, as, groups, training, ws_));
+                return wgrad_on(*pp, gw, ws_);
+            });
+        } else if (l == 0) {
             side_later(P, [pp, gw](hipStream_t ws_) { return wgrad_on(*pp, gw, ws_); });
         }
         {
-            GemmParams d = gemm_of(P, L.dgrad, L.pk_dgrad, groups, B, L.pk_dgrad_f);
-            d.c.A = dq[l + 1]; d.out_bf = dq[l]; d.ldo = L.g.Cin;
-            d.d_r = q[l]; d.d_ld = L.g.Cin; d.d_act = ACT_SWISH;
-            if (l > 0) { d.d_affine = w.aff_d[l - 1]; d.d_meanrstd = w.mr_d[l - 1]; d.d_red = w.red_d[l - 1]; }
+            GemmParams d = mm_gemm(P, MM_DEC_CONVT_DGRAD, l, groups);
             GatherTransform tr{};
-            if (fl) {
-                tr.kind = 2; tr.r = q[l + 1]; tr.red = w.red_d[l]; tr.mr = w.mr_d[l]; tr.gamma = P.buf.params + b.w_off;
-                tr.inv_cnt = 1.f / (float)(B * pix); tr.groups = groups;
-                if (mmvae_knob(K_mm_stage_out)) { tr.out = dqr[l + 1]; tr.dgamma = P.buf.grads + b.w_off; tr.dbeta = P.buf.grads + b.b_off; }
-                d.tr = &tr;
-            }
+            if (fl) mm_stage_bwd_dec(P, l, groups, d, tr);
             // the side work collected so far forks off the completion of the first and of the last data gradient
             const bool flush = P.wgrad_forked && ((l == 2 && !mmvae_knob(K_mm_forks)) || l == 0);
             if (flush) arm_fork(P);
             MMVAE_TRY(launch_gemm_gather(d, s));
             if (flush) { MMVAE_TRY(commit_fork(P, s)); if (l == 2) MMVAE_TRY(side_flush(P, s)); }
         }
-        if (!fl && !(fuse || l == 0)) MMVAE_TRY(wgrad_async(P, gw, s));
+        if (!fl && l != 0) MMVAE_TRY(wgrad_async(P, gw, s));
     }
-    {   // upsample Linear: weight (+ folded bias) gradient and dz
-        GatherPlan pl = dense_plan(rows, P.ldz, P.ldz, 1024);
-        WgradParams g = wgrad_of(P, pl, &P.up.gk, 1, rows);
-        g.c.A = w.z_bf; g.P = w.du; g.ldp = 1024;
-        MMPlan* pp = &P;
-        side_later(P, [pp, g](hipStream_t ws_) { return wgrad_on(*pp, g, ws_); });
-        MMVAE_TRY(side_flush(P, s));                // forks off the last data gradient above (du is its output)
-        GatherPlan pd = dense_plan(rows, 1024, 1024, P.D);
-        GemmParams d = gemm_of(P, pd, &P.up.pk_dgrad, 1, rows);
-        d.c.A = w.du; d.out_f = dz; d.ldo = P.D;
-        MMVAE_TRY(launch_gemm_gather(d, s));
-    }
-    return MMVAE_OK;
+    // upsample Linear: weight (+ folded bias) gradient and dz
+    const WgradParams gu = mm_wgrad(P, MM_W_UP, 0, groups);
+    side_later(P, [pp, gu](hipStream_t ws_) { return wgrad_on(*pp, gu, ws_); });
+    MMVAE_TRY(side_flush(P, s));                // forks off the last data gradient above (du is its output)
+    return launch_gemm_gather(mm_gemm(P, MM_UP_DGRAD, 0, groups, 1, nullptr, dz), s);
 }
 
 // ================================================================== text modules (argument builders and grouped weight gradients: text_plan.h)
@@ -1284,161 +1387,50 @@ int mm_iw_score_image(MMPlan* P, void* ws, size_t wsb, const float* z, const flo
     return iw_image_rows(P, ws, wsb, z, image, B, K, loglik_x, s, "mmvae_mm_iw_score_image");
 }
 
-// ---------------------------------------------------------------- profiling aid: replay one GEMM of the step
+// ---------------------------------------------------------------- test / profiling aid: replay one launch of the step (mm_bench_layer)
+// The launches of mm_gemm / mm_wgrad under names, in the form the default training step runs them: training mode, the classifier on
+// its 2 dropout variants with the keep flags in w.m1 / w.m2 (as drawn by the last step), the decoder with 3 passes forward and 2
+// backward (2 of 3 passes carry an image gradient).  Statistics land in the (dead) accumulation buffers of the last step.  What the
+// step writes into the caller's buffers or the flat gradient goes to tmp_f32 instead: the result of enc_fc3 and dec_up_dgrad, the
+// column sums of enc_fc3_dgrad / enc_fc2_dgrad; enc_fc3_dgrad reads d_encout.  The weight gradients read the operands of the
+// unfused layers (dr[l] / dq[l + 1]).
 static bool layer_gemm(MMPlan& P, const std::string& name, GemmParams& g) {
-    // the GEMMs exactly as the step launches them (epilogue options included); statistics land in the (dead)
-    // accumulation buffers of the last step
     MMPlan::W& w = P.w;
-    const int B = P.B;
-    bf16* r[4] = {w.r1, w.r2, w.r3, w.r4};
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    bf16* dre[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    bf16* q[4] = {w.u, w.q1, w.q2, w.q3};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    if (name == "enc_conv1") {
-        GatherPlan pl = dense_plan(B * 625, 16, 16, 32);
-        g = gemm_of(P, pl, P.conv[0].pk_fwd, 1, B * 625);
-        g.c.A = w.patches1; g.out_bf = w.r1; g.ldo = 32; g.out_act_bf = w.a1; g.e_act = ACT_SWISH;
-        return true;
-    }
+    if (name == "enc_conv1") { g = mm_gemm(P, MM_ENC_CONV1, 0, 1); return true; }
     for (int l = 1; l < 4; ++l) {
-        const ConvL& L = P.conv[l];
-        if (name == "enc_conv" + std::to_string(l + 1)) {
-            g = gemm_of(P, L.fwd, L.pk_fwd, 1, B, L.pk_fwd_f);
-            g.c.A = a[l - 1];
-            g.out_bf = r[l]; g.ldo = L.g.Cout; g.colstats = w.st_e[l - 1];
-            return true;
-        }
-        if (name == "enc_conv" + std::to_string(l + 1) + "_dgrad") {
-            g = gemm_of(P, L.dgrad, L.pk_dgrad, 1, B, L.pk_dgrad_f);
-            g.c.A = dre[l]; g.out_bf = dre[l - 1]; g.ldo = L.g.Cin;
-            g.d_r = r[l - 1]; g.d_ld = L.g.Cin; g.d_act = ACT_SWISH;
-            if (l > 1) { g.d_affine = w.aff_e[l - 2]; g.d_meanrstd = w.mr_e[l - 2]; g.d_red = w.red_e[l - 2]; }
-            return true;
-        }
+        const std::string n = "enc_conv" + std::to_string(l + 1);
+        if (name == n) { g = mm_gemm(P, MM_ENC_CONV, l, 1); return true; }
+        if (name == n + "_dgrad") { g = mm_gemm(P, MM_ENC_CONV_DGRAD, l, 1); return true; }
     }
-    {   // classifier / upsample Linears (2 dropout variants, masks as drawn by the last step)
-        const int rows = 2 * B;
-        const float ms = 1.f / (1.f - DROP_P);
-        if (name == "enc_fc1") {
-            GatherPlan pl = plan_fwdform(2, 2, 1, 1, 256, 2, 2, 1, 0, 400, 1, rows);
-            g = gemm_of(P, pl, &P.fc[0].pk_fwd, 1, rows);
-            g.c.A = w.a4; g.c.a_bcast_n = B; g.bias = P.buf.params + P.fc[0].b_off; g.out_bf = w.y1; g.ldo = 400;
-            g.out_act_bf = w.ay1; g.e_act = ACT_SWISH; g.e_mask = w.m1; g.e_mask_scale = ms;
-            return true;
-        }
-        if (name == "enc_fc1_dgrad") { g = fc1_dgrad_gemm(P, rows); return true; }      // as enc_bwd launches it
-        if (name == "enc_fc2") {
-            GatherPlan pl = dense_plan(rows, 400, 400, 200);
-            g = gemm_of(P, pl, &P.fc[1].pk_fwd, 1, rows);
-            g.c.A = w.ay1; g.bias = P.buf.params + P.fc[1].b_off; g.out_bf = w.y2; g.ldo = 200;
-            g.out_act_bf = w.ay2; g.e_act = ACT_SWISH; g.e_mask = w.m2; g.e_mask_scale = ms;
-            return true;
-        }
-        if (name == "enc_fc3") {
-            GatherPlan pl = dense_plan(rows, 200, 200, 2 * P.D);
-            g = gemm_of(P, pl, &P.fc[2].pk_fwd, 1, rows);
-            g.c.A = w.ay2; g.bias = P.buf.params + P.fc[2].b_off; g.out_f = w.tmp_f32; g.ldo = 2 * P.D;
-            return true;
-        }
-        if (name == "enc_fc3_dgrad") {
-            GatherPlan pd = dense_plan(rows, P.lde, P.lde, 200);
-            g = gemm_of(P, pd, &P.fc[2].pk_dgrad, 1, rows);
-            g.c.A = w.d_encout; g.out_bf = w.dy2; g.ldo = 200;
-            g.d_r = w.y2; g.d_ld = 200; g.d_act = ACT_SWISH; g.d_mask = w.m2; g.d_mask_scale = ms;
-            g.d_colsum = w.tmp_f32;
-            return true;
-        }
-        if (name == "enc_fc2_dgrad") {
-            GatherPlan pd = dense_plan(rows, 200, 200, 400);
-            g = gemm_of(P, pd, &P.fc[1].pk_dgrad, 1, rows);
-            g.c.A = w.dy2; g.out_bf = w.dy1; g.ldo = 400;
-            g.d_r = w.y1; g.d_ld = 400; g.d_act = ACT_SWISH; g.d_mask = w.m1; g.d_mask_scale = ms;
-            g.d_colsum = w.tmp_f32;
-            return true;
-        }
-        if (name == "dec_up") {
-            GatherPlan pl = dense_plan(3 * B, P.ldz, P.ldz, 1024);
-            g = gemm_of(P, pl, &P.up.pk_fwd, 1, 3 * B);
-            g.c.A = w.z_bf; g.out_bf = w.u; g.ldo = 1024; g.out_act_bf = w.au; g.e_act = ACT_SWISH;
-            return true;
-        }
-        if (name == "dec_up_dgrad") {
-            GatherPlan pd = dense_plan(rows, 1024, 1024, P.D);
-            g = gemm_of(P, pd, &P.up.pk_dgrad, 1, rows);
-            g.c.A = w.du; g.out_f = w.tmp_f32; g.ldo = P.D;
-            return true;
-        }
-    }
-    if (name == "dec_last_dgrad_gemm") {       // thin last layer's input gradient as a dense GEMM over im2col(dlogit)
-        const ConvL& L = P.convT[3];
-        GatherPlan pl = dense_plan(B * 625, 16, 16, 32);
-        g = gemm_of(P, pl, L.pk_dgrad, 2, B * 625);
-        g.c.A = w.patches4; g.out_bf = w.d3; g.ldo = 32;
-        g.d_r = w.q3; g.d_ld = 32; g.d_act = ACT_SWISH; g.d_affine = w.aff_d[2]; g.d_meanrstd = w.mr_d[2]; g.d_red = w.red_d[2];
-        return true;
-    }
+    if (name == "enc_fc1") { g = mm_gemm(P, MM_FC1, 0, 2, 1, w.m1); return true; }
+    if (name == "enc_fc1_dgrad") { g = mm_gemm(P, MM_FC1_DGRAD, 0, 2); return true; }
+    if (name == "enc_fc2") { g = mm_gemm(P, MM_FC2, 0, 2, 1, w.m2); return true; }
+    if (name == "enc_fc3") { g = mm_gemm(P, MM_FC3, 0, 2, 1, nullptr, w.tmp_f32); return true; }
+    if (name == "enc_fc3_dgrad") { g = mm_gemm(P, MM_FC3_DGRAD, 0, 2, 1, w.m2, w.d_encout, w.tmp_f32); return true; }
+    if (name == "enc_fc2_dgrad") { g = mm_gemm(P, MM_FC2_DGRAD, 0, 2, 1, w.m1, nullptr, w.tmp_f32); return true; }
+    if (name == "dec_up") { g = mm_gemm(P, MM_UP, 0, 3); return true; }
+    if (name == "dec_up_dgrad") { g = mm_gemm(P, MM_UP_DGRAD, 0, 2, 1, nullptr, w.tmp_f32); return true; }
     for (int l = 0; l < 3; ++l) {
-        const ConvL& L = P.convT[l];
-        if (name == "dec_convT" + std::to_string(l + 1)) {
-            g = gemm_of(P, L.fwd, L.pk_fwd, 3, B, L.pk_fwd_f);
-            g.c.A = aq[l];
-            g.out_bf = q[l + 1]; g.ldo = L.g.Cout; g.colstats = w.st_d[l];
-            return true;
-        }
-        if (name == "dec_convT" + std::to_string(l + 1) + "_dgrad") {
-            g = gemm_of(P, L.dgrad, L.pk_dgrad, 2, B, L.pk_dgrad_f);
-            g.c.A = dq[l + 1]; g.out_bf = dq[l]; g.ldo = L.g.Cin;
-            g.d_r = q[l]; g.d_ld = L.g.Cin; g.d_act = ACT_SWISH;
-            if (l > 0) { g.d_affine = w.aff_d[l - 1]; g.d_meanrstd = w.mr_d[l - 1]; g.d_red = w.red_d[l - 1]; }
-            return true;
-        }
+        const std::string n = "dec_convT" + std::to_string(l + 1);
+        if (name == n) { g = mm_gemm(P, MM_DEC_CONVT, l, 3); return true; }
+        if (name == n + "_dgrad") { g = mm_gemm(P, MM_DEC_CONVT_DGRAD, l, 2); return true; }
     }
+    if (name == "dec_last_dgrad_gemm") { g = mm_gemm(P, MM_DEC_LAST_DGRAD, 3, 2); return true; }
     return false;
 }
-// the weight gradients exactly as the step launches them (2 decoder passes carry a gradient)
 static bool layer_wgrad(MMPlan& P, const std::string& name, WgradParams& g) {
-    MMPlan::W& w = P.w;
-    const int B = P.B;
-    bf16* a[4] = {w.a1, w.a2, w.a3, w.a4};
-    bf16* dre[4] = {w.d1e, w.d2e, w.d3e, w.dr4};
-    bf16* aq[4] = {w.au, w.aq1, w.aq2, w.aq3};
-    bf16* dq[4] = {w.du, w.d1, w.d2, w.d3};
-    for (int l = 0; l < 3; ++l)
-        if (name == "dec_convT" + std::to_string(l + 1) + "_wgrad") {
-            const ConvL& L = P.convT[l];
-            g = convT_wgrad(P, L, 2, B, aq[l], dq[l + 1]);
-            return true;
-        }
+    const MMChains t = mm_chains(P.w);
+    if (name == "enc_conv1_wgrad") { g = mm_wgrad(P, MM_W_ENC_CONV1, 0, 1); return true; }
     for (int l = 1; l < 4; ++l)
-        if (name == "enc_conv" + std::to_string(l + 1) + "_wgrad") {
-            const ConvL& L = P.conv[l];
-            g = wgrad_of(P, L.fwd, L.gk, 1, B);
-            g.c.A = a[l - 1]; g.P = dre[l]; g.ldp = L.g.Cout;
-            return true;
-        }
-    if (name == "dec_last_wgrad") {
-        GatherPlan pl = plan_fwdform(1, 1, 25, 25, 16, 1, 1, 1, 0, 32, 2, B);
-        g = wgrad_of(P, pl, P.convT[3].gk, 2, B);
-        g.c.A = w.patches4; g.c.AH = 25; g.c.AW = 25; g.c.sy = g.c.sx = 1;
-        g.P = w.aq3; g.ldp = 32;
-        return true;
-    }
-    if (name == "enc_conv1_wgrad") {
-        GatherPlan pl = dense_plan(B * 625, 16, 16, 32);
-        g = wgrad_of(P, pl, P.conv[0].gk, 1, B * 625);
-        g.c.A = w.patches1; g.P = w.d1e; g.ldp = 32;
-        return true;
-    }
+        if (name == "enc_conv" + std::to_string(l + 1) + "_wgrad") { g = mm_wgrad(P, MM_W_ENC_CONV, l, 1, t.dr[l]); return true; }
+    for (int l = 0; l < 3; ++l)
+        if (name == "dec_convT" + std::to_string(l + 1) + "_wgrad") { g = mm_wgrad(P, MM_W_DEC_CONVT, l, 2, t.dq[l + 1]); return true; }
+    if (name == "dec_last_wgrad") { g = mm_wgrad(P, MM_W_DEC_LAST, 3, 2); return true; }
     return false;
 }
-static double wgrad_flops(const WgradParams& g) {
-    double f = 0;
-    for (int i = 0; i < g.c.nclasses; ++i) f += 2.0 * g.c.groups * g.cls[i].rows_per_group * (double)g.c.N * g.cls[i].K;
-    return f;
-}
-static double gemm_flops(const GemmParams& g) {
+// FLOPs of one launch (GemmParams or WgradParams)
+template <class Params>
+static double launch_flops(const Params& g) {
     double f = 0;
     for (int i = 0; i < g.c.nclasses; ++i) f += 2.0 * g.c.groups * g.cls[i].rows_per_group * (double)g.c.N * g.cls[i].K;
     return f;
@@ -1480,7 +1472,7 @@ int mm_bench_layer(MMPlan* P, void* ws, size_t wsb, const char* layer, int iters
         return MMVAE_OK;
     }
     WgradParams wg{};
-    if (layer_wgrad(*P, layer, wg)) {            // kernel + its share of the slab reduction, as in the step
+    if (layer_wgrad(*P, layer, wg)) {         // kernel + its share of the slab reduction, as in the step
         for (int i = 0; i < iters; ++i) {
             P->slab.reset(P->w.slab, P->w.slab_floats);
             MMVAE_TRY(launch_wgrad(wg, s, &P->slab));
@@ -1500,9 +1492,9 @@ double mm_layer_flops(const MMPlan* Pc, const char* layer) {
     if (std::string(layer) == "dec_last_fused" || std::string(layer) == "dec_last_fused_reduce")
         return 3.0 * 2.0 * 2 * P.B * 625 * 16 * 32;      // forward + both gradients, 2 passes
     if (std::string(layer) == "enc_conv1_mfma" || std::string(layer) == "enc_conv1_wgrad_mfma") return 2.0 * P.B * 640 * 16 * 32;   // 20 tiles of 32 rows
-    if (P.bound && layer_wgrad(P, layer, wg)) return wgrad_flops(wg);
+    if (P.bound && layer_wgrad(P, layer, wg)) return launch_flops(wg);
     if (!P.bound || !layer_gemm(P, layer, g)) return -1.0;
-    return gemm_flops(g);
+    return launch_flops(g);
 }
 // FLOPs of a layer the way torch's FlopCounterMode counts the reference: 2 * out_pixels * taps * Cin * Cout for a
 // Conv2d, 2 * in_pixels * taps * Cin * Cout for a ConvTranspose2d, the same number again for each of the two gradients --
