@@ -5,52 +5,65 @@ modules in eval mode (BatchNorm running statistics, no dropout, z = mu).
 ``compute_nll`` quirk kept out: the reference calls ``F.nll_loss(recon_text (B,4,12), text (B,4), size_average=False)``
 directly, which modern torch rejects (class dimension mismatch); the evident intent -- the summed negative log-likelihood
 of the 4 target characters -- is what is computed here (``recon_text.view(-1, 12)`` against ``text.view(-1)``).
+
+What differs between the ten model kinds (the four ``MultimodalVAE``s and their ``ImageVAE`` / ``TextVAE`` baselines) is ONE table,
+``_FAMILIES``: the NLL loop, the posterior helper under ``_proposal`` and the samplers, ``iw_estimate`` and the command line ask it
+and hold no per-family branch of their own.
 """
 from __future__ import annotations
 
+import functools
+import importlib
 
 import numpy as np
 import torch
 
 from . import _ops
+from ._lib import call, ptr
 from .multimnist import _BCEMeanFn, _NLLMeanFn
 from .utils import FILL, max_length
 
 
 @torch.no_grad()
-def compute_nll(model, loader, image_only=False, text_only=False, n_samples=1, use_cuda=True, verbose=False):
-    """-> (image NLL per sample, text NLL per sample), multimnist/loglikelihood.py:20-69."""
-    assert not (image_only and text_only)
+def _reference_nll(model, loader, family, posterior, n_samples, use_cuda, verbose):
+    """The reference's per-particle NLL loop, shared by the ``compute_nll*`` wrappers: per batch the posterior's (mu, logvar), ONE set
+    of ``n_samples`` standard-normal draws shared by the rows of the batch (the reference's behaviour, kept), the summed loss of every
+    decoded particle -- the image term, then the second modality's -- averaged over the particles; in the end divided by the number
+    of examples.  -> [image NLL per sample, second NLL per sample] (the second stays 0.0 for an ``ImageVAE``)."""
+    fam = _FAMILIES[family]
     model.eval()
-    test_image_nll, test_text_nll, n_seen = 0.0, 0.0, 0
-    for batch_idx, (image, text) in enumerate(loader):
+    totals, n_seen = [0.0, 0.0], 0
+    for image, second in loader:
         if use_cuda:
-            image, text = image.cuda(), text.cuda()
-        if not image_only and not text_only:
-            _, _, mu, logvar = model(image, text)
-        elif image_only:
-            _, _, mu, logvar = model(image=image)
-        else:
-            _, _, mu, logvar = model(text=text)
+            image, second = image.cuda(), None if fam.image_only else second.cuda()
+        image = image.float().reshape(-1, *fam.image_shape)       # (MNIST: the reference's view(-1, 784); the others come in this shape)
+        mu, logvar = _posterior_of(model, fam, image, second, posterior)
         batch_size, n_latents = mu.size(0), mu.size(1)
-        sample = torch.randn(n_samples, n_latents)                # drawn on the host like the reference (:43)
+        sample = torch.randn(n_samples, n_latents)                # drawn on the host like the reference, after the encoders ran
         if use_cuda:
             sample = sample.cuda()
-        std = logvar.mul(0.5).exp()
-        z = sample.unsqueeze(0) * std.unsqueeze(1) + mu.unsqueeze(1)          # (B, n_samples, D)
-        image_nll, text_nll = 0.0, 0.0
+        z = sample.unsqueeze(0) * logvar.mul(0.5).exp().unsqueeze(1) + mu.unsqueeze(1)      # (B, n_samples, D)
+        nll = [0.0, 0.0]
         for i in range(n_samples):
             zi = z[:, i].contiguous()
-            recon_image = model.decode_image(zi)
-            recon_text = model.decode_text(zi)
-            image_nll += float(_BCEMeanFn.apply(recon_image.reshape(batch_size, -1), image.reshape(batch_size, -1))) * image.numel()
-            text_nll += float(_NLLMeanFn.apply(recon_text.reshape(-1, recon_text.size(2)), text.reshape(-1))) * text.numel()
-        test_image_nll += image_nll / n_samples
-        test_text_nll += text_nll / n_samples
+            nll[0] += float(_bce_rows(fam, fam.reach(model, "decode_image")(zi), image)) * image.numel()
+            if not fam.image_only:
+                nll[1] += float(fam.second_loss(fam, fam.reach(model, "decode_second")(zi), second)) * second.numel()
+        totals = [t + v / n_samples for t, v in zip(totals, nll)]
         n_seen += batch_size
         if verbose:
             print('Evaluating: [{}/{}]'.format(n_seen, len(loader) * batch_size))
-    return test_image_nll / max(n_seen, 1), test_text_nll / max(n_seen, 1)
+    return [t / max(n_seen, 1) for t in totals]
+
+
+def _mode(image_only, second_only):
+    assert not (image_only and second_only)
+    return "image" if image_only else "text" if second_only else "joint"
+
+
+def compute_nll(model, loader, image_only=False, text_only=False, n_samples=1, use_cuda=True, verbose=False):
+    """-> (image NLL per sample, text NLL per sample), multimnist/loglikelihood.py:20-69."""
+    return tuple(_reference_nll(model, loader, "multimnist", _mode(image_only, text_only), n_samples, use_cuda, verbose))
 
 
 @torch.no_grad()
@@ -81,70 +94,16 @@ test_multimnist.__test__ = False          # not a pytest test
 # ------------------------------------------------------------------------------------------------------------------
 # MNIST consumers (mnist/loglikelihood.py:15-65, mnist/test.py:18-36)
 
-@torch.no_grad()
 def compute_nll_mnist(model, loader, image_only=False, text_only=False, n_samples=1, use_cuda=True, verbose=False):
     """-> (image NLL per sample, label NLL per sample), mnist/loglikelihood.py:15-65."""
-    from .mnist import _BCEMeanFn as _BCE, _NLLMeanFn as _NLL
-    assert not (image_only and text_only)
-    model.eval()
-    test_image_nll, test_text_nll, n_seen = 0.0, 0.0, 0
-    for image, text in loader:
-        if use_cuda:
-            image, text = image.cuda(), text.cuda()
-        image = image.float().reshape(-1, 784)
-        if not image_only and not text_only:
-            _, _, mu, logvar = model(image, text)
-        elif image_only:
-            _, _, mu, logvar = model(image=image)
-        else:
-            _, _, mu, logvar = model(text=text)
-        batch_size, n_latents = mu.size(0), mu.size(1)
-        sample = torch.randn(n_samples, n_latents)                # drawn on the host like the reference (:37)
-        if use_cuda:
-            sample = sample.cuda()
-        z = sample.unsqueeze(0) * logvar.mul(0.5).exp().unsqueeze(1) + mu.unsqueeze(1)      # (B, n_samples, D)
-        image_nll, text_nll = 0.0, 0.0
-        for i in range(n_samples):
-            zi = z[:, i].contiguous()
-            recon_image = model.decode_image(zi)
-            recon_text = model.decode_text(zi)
-            image_nll += float(_BCE.apply(recon_image.reshape(batch_size, -1), image)) * image.numel()
-            text_nll += float(_NLL.apply(recon_text, text.reshape(-1))) * text.numel()
-        test_image_nll += image_nll / n_samples
-        test_text_nll += text_nll / n_samples
-        n_seen += batch_size
-        if verbose:
-            print('Evaluating: [{}/{}]'.format(n_seen, len(loader) * batch_size))
-    return test_image_nll / max(n_seen, 1), test_text_nll / max(n_seen, 1)
+    return tuple(_reference_nll(model, loader, "mnist", _mode(image_only, text_only), n_samples, use_cuda, verbose))
 
 
-@torch.no_grad()
 def compute_nll_mnist_imageonly(model, loader, n_samples=1, use_cuda=True, verbose=False):
     """-> image NLL per sample of a ``mnist.VAE``, mnist/imageonly/loglikelihood_imageonly.py:17-51: the eval-mode encoder's
     (mu, logvar), ONE set of ``n_samples`` standard-normal draws shared by the rows of a batch (the reference's behaviour, kept),
     the summed BCE of every decoded particle, averaged over the particles and divided by the number of examples."""
-    from .mnist import _BCEMeanFn as _BCE
-    model.eval()
-    test_nll, n_seen = 0.0, 0
-    for image, _ in loader:
-        if use_cuda:
-            image = image.cuda()
-        image = image.float().reshape(-1, 784)
-        _, mu, logvar = model(image)
-        batch_size, n_latents = mu.size(0), mu.size(1)
-        sample = torch.randn(n_samples, n_latents)                # drawn on the host like the reference (:29)
-        if use_cuda:
-            sample = sample.cuda()
-        z = sample.unsqueeze(0) * logvar.mul(0.5).exp().unsqueeze(1) + mu.unsqueeze(1)      # (B, n_samples, D)
-        nll = 0.0
-        for i in range(n_samples):
-            recon_image = model.decode(z[:, i].contiguous())
-            nll += float(_BCE.apply(recon_image.reshape(batch_size, -1), image)) * image.numel()
-        test_nll += nll / n_samples
-        n_seen += batch_size
-        if verbose:
-            print('Evaluating: [{}/{}]'.format(n_seen, len(loader) * batch_size))
-    return test_nll / max(n_seen, 1)
+    return _reference_nll(model, loader, "mnist_image", "image", n_samples, use_cuda, verbose)[0]
 
 
 @torch.no_grad()
@@ -170,7 +129,6 @@ test_mnist.__test__ = False               # not a pytest test
 # ------------------------------------------------------------------------------------------------------------------
 # CelebA consumers (celeba/loglikelihood.py:18-67, celeba/test.py:44-71)
 
-@torch.no_grad()
 def compute_nll_celeba(model, loader, image_only=False, attrs_only=False, n_samples=1, use_cuda=True, verbose=False):
     """-> (image NLL per sample, attribute NLL per sample), celeba/loglikelihood.py:18-67.
 
@@ -178,37 +136,7 @@ def compute_nll_celeba(model, loader, image_only=False, attrs_only=False, n_samp
     size_average=False)`` (:56), which no torch version accepts for a float target; the attribute decoder ends in a sigmoid and
     the training loss is a Bernoulli cross entropy (celeba/train.py:68-72), so the summed binary cross entropy is what is
     computed here."""
-    from .celeba import _BCEMeanFn as _BCE
-    assert not (image_only and attrs_only)
-    model.eval()
-    test_image_nll, test_attrs_nll, n_seen = 0.0, 0.0, 0
-    for image, attrs in loader:
-        if use_cuda:
-            image, attrs = image.cuda(), attrs.cuda()
-        if not image_only and not attrs_only:
-            _, _, mu, logvar = model(image, attrs)
-        elif image_only:
-            _, _, mu, logvar = model(image=image)
-        else:
-            _, _, mu, logvar = model(attrs=attrs)
-        batch_size, n_latents = mu.size(0), mu.size(1)
-        sample = torch.randn(n_samples, n_latents)                # drawn on the host like the reference (:40)
-        if use_cuda:
-            sample = sample.cuda()
-        z = sample.unsqueeze(0) * logvar.mul(0.5).exp().unsqueeze(1) + mu.unsqueeze(1)      # (B, n_samples, D)
-        image_nll, attrs_nll = 0.0, 0.0
-        for i in range(n_samples):
-            zi = z[:, i].contiguous()
-            recon_image = model.image_decoder(zi)
-            recon_attrs = model.attrs_decoder(zi)
-            image_nll += float(_BCE.apply(recon_image.reshape(batch_size, -1), image.reshape(batch_size, -1))) * image.numel()
-            attrs_nll += float(_BCE.apply(recon_attrs.reshape(batch_size, -1), attrs.reshape(batch_size, -1))) * attrs.numel()
-        test_image_nll += image_nll / n_samples
-        test_attrs_nll += attrs_nll / n_samples
-        n_seen += batch_size
-        if verbose:
-            print('Evaluating: [{}/{}]'.format(n_seen, len(loader) * batch_size))
-    return test_image_nll / max(n_seen, 1), test_attrs_nll / max(n_seen, 1)
+    return tuple(_reference_nll(model, loader, "celeba", _mode(image_only, attrs_only), n_samples, use_cuda, verbose))
 
 
 @torch.no_grad()
@@ -261,19 +189,26 @@ def iw_chunks(B, K, capacity):
     return [(r0, min(rb, B - r0), k0, min(kc, K - k0)) for r0 in range(0, B, rb) for k0 in range(0, K, kc)]
 
 
-def _iw_call(name, *args):
-    from ._lib import call
-    return call(name, *args)
-
-
 class _Family:
-    """What the evaluation needs to know about a model family: the scoring call between particles and accumulate, the text
-    decoder's steps T and classes V (words [rows][T][V]), the shape of one image, the particle rows of one scoring call and
-    the scoring workspace."""
+    """The whole description of a model kind, for everything in this file:
 
-    def __init__(self, name, T, V, image_shape, rows, score, workspace_bytes, float_text=False, image_only=False, text_only=False):
-        self.name, self.T, self.V, self.image_shape, self.rows = name, T, V, image_shape, rows
-        self.score, self.workspace_bytes = score, workspace_bytes
+    * ``cls``: the model class as "module.Class", imported on first use (``import evaluate`` stays light and acyclic);
+    * the scoring call between particles and accumulate (``score``), the text decoder's steps T and classes V (words [rows][T][V]),
+      the particle rows of one scoring call, and the scoring workspace as data: "mm" / "celeba" / "coco" ask
+      mmvae_<api>_iw_workspace_bytes of the chunk's plan, "module" the state's ``module_workspace_bytes``, None needs none;
+    * ``image_shape``: the layout of one image as the encoders and the NLL loop take it ((784,) for MNIST), ``picture``: the shape of
+      one image a sampler returns ((1,28,28) for MNIST; else the same);
+    * how to reach the encoders, decoders and experts on a model of the kind (``reach``): an attribute name, or a callable
+      (model, input); ``captions``: the attribute of COCO's caption decoder (its ``sos``; its ``generate`` when sampling);
+    * ``second_loss``: the mean-loss function (family, reconstruction, target) the reference's NLL uses for the second modality."""
+
+    def __init__(self, name, cls, T, V, image_shape, rows, score, workspace, picture=None, encode_image=None, encode_second=None,
+                 decode_image=None, decode_second=None, experts="experts", captions=None, second_loss=None, float_text=False,
+                 image_only=False, text_only=False):
+        self.name, self.cls, self.T, self.V, self.image_shape, self.rows = name, cls, T, V, image_shape, rows
+        self.score, self.workspace, self.picture = score, workspace, picture or image_shape
+        self.encode_image, self.encode_second, self.decode_image, self.decode_second = encode_image, encode_second, decode_image, decode_second
+        self.experts, self.captions, self.second_loss = experts, captions, second_loss
         # text_only: a TextVAE baseline (coco): there is no image, the scoring call writes the caption term alone and the x / xy
         # columns of every result are NaN
         self.text_only = text_only
@@ -284,34 +219,51 @@ class _Family:
         # targets; the scoring call then also gets text / sos / sse / scale (``_coco_score``) and writes words = scale * sse
         self.float_text = float_text
 
+    def module(self):
+        return importlib.import_module("." + self.cls.split(".")[0], __package__)
+
+    def model_class(self):
+        return getattr(self.module(), self.cls.split(".")[1])
+
+    def trainer(self):
+        """The one-pass Trainer of a uni-modal kind (``test_imageonly`` / ``test_textonly``)."""
+        return getattr(self.module(), "TextVAETrainer" if self.text_only else "ImageVAETrainer")
+
+    def reach(self, model, role):
+        """The callable of ``role`` ("encode_image", "encode_second", "decode_image", "decode_second", "experts", "captions")."""
+        how = getattr(self, role)
+        return getattr(model, how) if isinstance(how, str) else functools.partial(how, model)
+
+    def workspace_bytes(self, st, rows):
+        if self.workspace is None:
+            return 0
+        if self.workspace == "module":
+            return st.module_workspace_bytes(rows)
+        return call("mmvae_%s_iw_workspace_bytes" % self.workspace, st.plan(rows))
+
 
 def _mm_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
-    from ._lib import ptr
-    _iw_call("mmvae_mm_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)
+    call("mmvae_mm_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)
 
 
 def _mnist_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
-    from ._lib import ptr
-    _iw_call("mmvae_mnist_iw_score", st.plan(1), ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)   # any bound plan: no row limit
+    call("mmvae_mnist_iw_score", st.plan(1), ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)   # any bound plan: no row limit
 
 
 def _celeba_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
-    from ._lib import ptr
-    _iw_call("mmvae_celeba_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)
+    call("mmvae_celeba_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), ptr(words), stream)
 
 
 def _coco_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream, text=None, sos=None, sse=None, scale=-0.5):
     """words [rows][1][1] = -sse / (2 sigma^2): the per-particle part of log p(y|z); the constant is added after finalize."""
-    from ._lib import ptr
-    _iw_call("mmvae_coco_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), ptr(text), ptr(sos), nr, nk, ptr(lx), ptr(sse), stream)
+    call("mmvae_coco_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), ptr(text), ptr(sos), nr, nk, ptr(lx), ptr(sse), stream)
     torch.mul(sse[:rows], scale, out=words[:rows])
 
 
 def _coco_text_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream, text=None, sos=None, sse=None, scale=-0.5):
     """The scoring call of a TextVAE: mmvae_coco_iw_score_text (the caption decoder and the squared error, no image decoder); log p(x|z) of
     the image that is not there is 0."""
-    from ._lib import ptr
-    _iw_call("mmvae_coco_iw_score_text", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(text), ptr(sos), nr, nk, ptr(sse), stream)
+    call("mmvae_coco_iw_score_text", st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(text), ptr(sos), nr, nk, ptr(sse), stream)
     lx[:rows].zero_()
     torch.mul(sse[:rows], scale, out=words[:rows])
 
@@ -319,16 +271,14 @@ def _coco_text_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream
 def _mmtext_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
     """The scoring call of a MultiMNIST TextVAE: mmvae_mmtext_iw_score (the text decoder alone, words [rows][4][12]); log p(x|z) of the
     image that is not there is 0."""
-    from ._lib import ptr
-    _iw_call("mmvae_mmtext_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), nr, nk, ptr(words), stream)
+    call("mmvae_mmtext_iw_score", st.plan(rows), ptr(ws), ws_bytes, ptr(z), nr, nk, ptr(words), stream)
     lx[:rows].zero_()
 
 
 def _mnist_image_score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
     """The scoring call of a ``mnist.VAE``: mmvae_mnist_iw_score_image (the fused kernel without the label decoder); the words of its
     one dummy text position are 0."""
-    from ._lib import ptr
-    _iw_call("mmvae_mnist_iw_score_image", st.plan(1), None, 0, ptr(z), ptr(image), nr, nk, ptr(lx), stream)   # any bound plan: no row limit
+    call("mmvae_mnist_iw_score_image", st.plan(1), None, 0, ptr(z), ptr(image), nr, nk, ptr(lx), stream)   # any bound plan: no row limit
     words[:rows].zero_()
 
 
@@ -336,8 +286,7 @@ def _image_score(api):
     """The scoring call of an ImageVAE: mmvae_<family>_iw_score_image (decoder body + scoring tail, no second decoder); the words
     of its one dummy text position are 0."""
     def score(st, rows, ws, ws_bytes, z, image, nr, nk, lx, words, stream):
-        from ._lib import ptr
-        _iw_call("mmvae_%s_iw_score_image" % api, st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), stream)
+        call("mmvae_%s_iw_score_image" % api, st.plan(rows), ptr(ws), ws_bytes, ptr(z), ptr(image), nr, nk, ptr(lx), stream)
         words[:rows].zero_()
     return score
 
@@ -361,56 +310,54 @@ def _shift_text_terms(out, log_w, c):
         log_w[..., 1:3] += c
 
 
+def _bce_rows(fam, recon, target):
+    """The summed-over-a-row, averaged binary cross entropy of the reference's image (and CelebA attribute) term."""
+    return _BCEMeanFn.apply(recon.reshape(target.shape[0], -1), target.reshape(target.shape[0], -1))
+
+
+def _nll_rows(fam, recon, target):
+    """``F.nll_loss`` of the log-softmax rows (B, V) or (B, T, V) against the targets (the module docstring's quirk)."""
+    return _NLLMeanFn.apply(recon.reshape(-1, fam.V), target.reshape(-1))
+
+
+_MULTIMODAL = dict(encode_image="image_encoder", encode_second="text_encoder", decode_image="decode_image", decode_second="decode_text")
+_IMAGE_VAE = dict(encode_image="encoder", decode_image="decode", image_only=True)       # the same particle rows per call as the family
+_TEXT_VAE = dict(encode_second="encoder", decode_second="decode", text_only=True)
 _FAMILIES = {
-    "multimnist": _Family("multimnist", 4, 12, (1, 50, 50), IW_ROWS, _mm_score,
-                          lambda st, rows: _iw_call("mmvae_mm_iw_workspace_bytes", st.plan(rows))),
-    "mnist": _Family("mnist", 1, 10, (784,), IW_ROWS_MNIST, _mnist_score, lambda st, rows: 0),
+    "multimnist": _Family("multimnist", "multimnist.MultimodalVAE", 4, 12, (1, 50, 50), IW_ROWS, _mm_score, "mm",
+                          second_loss=_nll_rows, **_MULTIMODAL),
+    "mnist": _Family("mnist", "mnist.MultimodalVAE", 1, 10, (784,), IW_ROWS_MNIST, _mnist_score, None, picture=(1, 28, 28),
+                     second_loss=_nll_rows, **_MULTIMODAL),
     # the 18 attributes are 18 "text positions" of V = 2 classes: words [rows][18][2] = (log(1 - p), log p), targets 0 / 1
-    "celeba": _Family("celeba", 18, 2, (3, 64, 64), IW_ROWS_CELEBA, _celeba_score,
-                      lambda st, rows: _iw_call("mmvae_celeba_iw_workspace_bytes", st.plan(rows))),
+    "celeba": _Family("celeba", "celeba.MultimodalVAE", 18, 2, (3, 64, 64), IW_ROWS_CELEBA, _celeba_score, "celeba",
+                      encode_image="image_encoder", encode_second=lambda model, t: model.attrs_encoder(t.float()),    # the (B,18) attributes as float
+                      decode_image="image_decoder", decode_second="attrs_decoder", second_loss=_bce_rows),
     # the caption term goes through the accumulator as ONE position of ONE class: words [rows][1][1] = -SSE / (2 sigma^2), targets 0
-    "coco": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_score,
-                    lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), float_text=True),
-    # the uni-modal baselines: the family's image half alone, the same particle rows per call
-    "celeba_image": _Family("celeba", 1, 1, (3, 64, 64), IW_ROWS_CELEBA, _image_score("celeba"),
-                            lambda st, rows: _iw_call("mmvae_celeba_iw_workspace_bytes", st.plan(rows)), image_only=True),
-    "coco_image": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _image_score("coco"),
-                          lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), image_only=True),
-    "coco_text": _Family("coco", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_text_score,
-                         lambda st, rows: _iw_call("mmvae_coco_iw_workspace_bytes", st.plan(rows)), float_text=True, text_only=True),
-    "multimnist_image": _Family("multimnist", 1, 1, (1, 50, 50), IW_ROWS, _image_score("mm"),
-                                lambda st, rows: _iw_call("mmvae_mm_iw_workspace_bytes", st.plan(rows)), image_only=True),
-    "mnist_image": _Family("mnist", 1, 1, (784,), IW_ROWS_MNIST, _mnist_image_score, lambda st, rows: 0, image_only=True),
+    "coco": _Family("coco", "coco.MultimodalVAE", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_score, "coco", captions="text_decoder",
+                    float_text=True, **_MULTIMODAL),
+    # the uni-modal baselines: the family's image half (its caption half) alone
+    "celeba_image": _Family("celeba", "celeba.ImageVAE", 1, 1, (3, 64, 64), IW_ROWS_CELEBA, _image_score("celeba"), "celeba", **_IMAGE_VAE),
+    "coco_image": _Family("coco", "coco.ImageVAE", 1, 1, (3, 32, 32), IW_ROWS_COCO, _image_score("coco"), "coco", **_IMAGE_VAE),
+    "coco_text": _Family("coco", "coco.TextVAE", 1, 1, (3, 32, 32), IW_ROWS_COCO, _coco_text_score, "coco", captions="decoder",
+                         float_text=True, **_TEXT_VAE),
+    "multimnist_image": _Family("multimnist", "multimnist.ImageVAE", 1, 1, (1, 50, 50), IW_ROWS, _image_score("mm"), "mm", **_IMAGE_VAE),
+    # (mnist.VAE's ``encoder`` is the bare Sequential: ``encode`` splits its output into mu, logvar)
+    "mnist_image": _Family("mnist", "mnist.VAE", 1, 1, (784,), IW_ROWS_MNIST, _mnist_image_score, None, picture=(1, 28, 28),
+                           **dict(_IMAGE_VAE, encode_image="encode")),
     # the MultiMNIST TextVAE: the text decoder alone on a plan of its own; its "image" is one dummy pixel
-    "multimnist_text": _Family("multimnist", 4, 12, (1,), IW_ROWS, _mmtext_score,
-                               lambda st, rows: st.module_workspace_bytes(rows), text_only=True),
+    "multimnist_text": _Family("multimnist", "multimnist.TextVAE", 4, 12, (1,), IW_ROWS, _mmtext_score, "module", **_TEXT_VAE),
 }
 IMAGE_ONLY_NAN_COLUMNS = (1, 2, 4, 5, 7)      # of mmvae_iw_finalize's (B, 8): everything that involves y
 TEXT_ONLY_NAN_COLUMNS = (0, 2, 3, 5, 6)       # ... everything that involves x
 
 
 def _family(model):
-    from .celeba import MultimodalVAE as CelebaVAE
-    from .coco import MultimodalVAE as CocoVAE
-    from .mnist import MultimodalVAE as MnistVAE
-    from .celeba import ImageVAE as CelebaImageVAE
-    from .coco import ImageVAE as CocoImageVAE
-    from .coco import TextVAE as CocoTextVAE
-    from .multimnist import TextVAE as MultimnistTextVAE
-    if isinstance(model, CocoTextVAE):
-        return _FAMILIES["coco_text"]
-    if isinstance(model, MultimnistTextVAE):
-        return _FAMILIES["multimnist_text"]
-    from .multimnist import ImageVAE as MultimnistImageVAE
-    if isinstance(model, MultimnistImageVAE):
-        return _FAMILIES["multimnist_image"]
-    from .mnist import VAE as MnistImageVAE
-    if isinstance(model, MnistImageVAE):
-        return _FAMILIES["mnist_image"]
-    if isinstance(model, (CelebaImageVAE, CocoImageVAE)):
-        return _FAMILIES["celeba_image" if isinstance(model, CelebaImageVAE) else "coco_image"]
-    return _FAMILIES["mnist" if isinstance(model, MnistVAE) else "celeba" if isinstance(model, CelebaVAE) else
-                     "coco" if isinstance(model, CocoVAE) else "multimnist"]
+    """The entry of ``_FAMILIES`` whose class ``model`` is an instance of (a subclass or a padded-latent variant resolves alike);
+    anything else is taken for a MultiMNIST model."""
+    for fam in _FAMILIES.values():
+        if isinstance(model, fam.model_class()):
+            return fam
+    return _FAMILIES["multimnist"]
 
 
 def _posterior(posterior):
@@ -423,41 +370,48 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
                 return_z=False, return_log_w=False, text_sigma=1.0):
     """Importance-sampled log p(x), log p(y), log p(x, y) of one batch under the proposal q = N(mu, exp(logvar)).
 
-    ``model``: a multimnist ``MultimodalVAE`` (its decoders run in eval mode); ``image`` (B,1,50,50) float, ``text`` (B,4)
-    int64, ``mu`` / ``logvar`` (B, n_latents), all on the GPU.  A mnist ``MultimodalVAE`` takes ``image`` (B,784) (or anything
-    that reshapes to it) and the labels ``text`` (B,) int64: one fused fp32 kernel scores its particles (mmvae_mnist_iw_score;
-    784 pixels, one text position of 10 classes, no greedy feedback), everything else below is the same.
-    A celeba ``MultimodalVAE`` takes ``image`` (B,3,64,64) and the attributes ``text`` (B,18) with values 0 / 1 (any dtype; they
-    are the int64 targets): mmvae_celeba_iw_score runs the bf16 image decoder and scores 3x64x64 logits, log p(y|z) is the sum
-    over the 18 attributes of y*a - softplus(a) on the attribute decoder's fp32 logit a.  The result keys keep their names: the
-    y / "text" columns are the attribute terms.
-    A coco ``MultimodalVAE`` takes ``image`` (B,3,32,32) and the captions ``text`` as floats (B, steps, 300) (``steps`` the model's):
-    mmvae_coco_iw_score runs the bf16 image decoder and scores 3x32x32 logits, and runs the caption decoder in eval mode (its own
-    output fed back, no dropout).  The reference trains captions with a mean squared error and defines no likelihood; the model under
-    which that loss is the NLL up to scale is used: log p(y|z) = -SSE / (2 sigma^2) - (steps * 300 / 2) log(2 pi sigma^2) with
-    sigma = ``text_sigma`` (the other families ignore it).  log p(y) and log p(x, y) of COCO therefore DEPEND ON sigma: compare
-    checkpoints only at the same ``text_sigma``.  The kernels accumulate -SSE / (2 sigma^2) alone; the constant (about -28,119 at
-    102 steps and sigma = 1) is added to the y / xy columns of ``log_p`` and ``log_w`` and to the caption ``nll`` afterwards, so
-    that fp32 keeps the digits of the per-particle terms.  ``return_log_w`` also returns ``sse`` (B, K) for this family.
-    Particles z_k = mu + exp(logvar/2) eps_k, k = 1..K, with eps keyed by (seed, first_row + example, particle, dimension) only, so a particle does not depend on the batch it comes
-    in or on how the K particles are split into calls.  With
+    ``model``: a ``MultimodalVAE`` of one of the families below (its decoders run in eval mode); ``image``, ``text``, ``mu`` /
+    ``logvar`` (B, n_latents), all on the GPU.
+
+    Particles z_k = mu + exp(logvar/2) eps_k, k = 1..K, with eps keyed by (seed, first_row + example, particle, dimension) only, so
+    a particle does not depend on the batch it comes in or on how the K particles are split into calls.  With
         log w_k^x = log p(x|z_k) + log p(z_k) - log q(z_k)       (y, xy alike)
     the estimate is log p^ = logsumexp_k(log w_k) - log K, a stochastic lower bound (K = 1: the one-sample ELBO), with the
     effective sample size (sum w)^2 / sum w^2.
-      * log p(x|z) = sum over the 2500 pixels of x*l - softplus(l) in fp32 from the decoder's pre-sigmoid logit l; it is NOT
-        clamped at -100 like ``binary_cross_entropy`` (the two differ only where the decoder is confidently wrong).
-      * log p(y|z) = sum over the 4 positions of the text decoder's eval-mode log-softmax output at the target character,
-        with the greedy feedback of its own argmax (the term ``loss_function`` trains, FILL positions included; not a
-        teacher-forced likelihood).
     The reference's multimnist/loglikelihood.py (and ``compute_nll``) averages the reconstruction NLL over the particles
     instead: no prior / proposal ratio, no log-sum-exp, so it is not a bound on log p(x).  Its quantity is reported here as
     the by-product ``nll`` (mean over the particles of -log p(x|z), -log p(y|z); without the clamp).
+
+    The families:
+      * multimnist: ``image`` (B,1,50,50) float, ``text`` (B,4) int64.
+        log p(x|z) = sum over the 2500 pixels of x*l - softplus(l) in fp32 from the decoder's pre-sigmoid logit l; it is NOT
+        clamped at -100 like ``binary_cross_entropy`` (the two differ only where the decoder is confidently wrong).
+        log p(y|z) = sum over the 4 positions of the text decoder's eval-mode log-softmax output at the target character,
+        with the greedy feedback of its own argmax (the term ``loss_function`` trains, FILL positions included; not a
+        teacher-forced likelihood).
+      * mnist: ``image`` (B,784) (or anything that reshapes to it) and the labels ``text`` (B,) int64: one fused fp32 kernel scores
+        its particles (mmvae_mnist_iw_score; 784 pixels, one text position of 10 classes, no greedy feedback), everything else is
+        the same.
+      * celeba: ``image`` (B,3,64,64) and the attributes ``text`` (B,18) with values 0 / 1 (any dtype; they are the int64
+        targets): mmvae_celeba_iw_score runs the bf16 image decoder and scores 3x64x64 logits, log p(y|z) is the sum over the 18
+        attributes of y*a - softplus(a) on the attribute decoder's fp32 logit a.  The result keys keep their names: the y / "text"
+        columns are the attribute terms.
+      * coco: ``image`` (B,3,32,32) and the captions ``text`` as floats (B, steps, 300) (``steps`` the model's):
+        mmvae_coco_iw_score runs the bf16 image decoder and scores 3x32x32 logits, and runs the caption decoder in eval mode (its
+        own output fed back, no dropout).  The reference trains captions with a mean squared error and defines no likelihood; the
+        model under which that loss is the NLL up to scale is used:
+        log p(y|z) = -SSE / (2 sigma^2) - (steps * 300 / 2) log(2 pi sigma^2) with sigma = ``text_sigma`` (the other families
+        ignore it).  log p(y) and log p(x, y) of COCO therefore DEPEND ON sigma: compare checkpoints only at the same
+        ``text_sigma``.  The kernels accumulate -SSE / (2 sigma^2) alone; the constant (about -28,119 at 102 steps and sigma = 1)
+        is added to the y / xy columns of ``log_p`` and ``log_w`` and to the caption ``nll`` afterwards, so that fp32 keeps the
+        digits of the per-particle terms.  ``return_log_w`` also returns ``sse`` (B, K) for this family.
+      * an ``ImageVAE`` / ``TextVAE`` of a family: the modality it does not have is ignored (may be None), and every column that
+        involves it is NaN.
 
     ``particles_per_call``: particles of one scoring call (default: as many as IW_ROWS rows allow; IW_ROWS_MNIST for MNIST).
     Test hooks: ``eps`` (B, K, n_latents) replaces the generator's draws; ``return_z`` adds z (B, K, n_latents), ``return_log_w`` log w
     (B, K, 3) (columns x, y, xy).
     -> dict of device tensors: ``log_p`` (B, 3) and ``ess`` (B, 3) (columns x, y, xy), ``nll`` (B, 2) (image, text)."""
-    from ._lib import ptr
     fam = _family(model)
     dev = mu.device
     st = model._core.sync(dev)
@@ -481,8 +435,7 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
             raise ValueError("iw_estimate: a coco model of %d steps takes images (B,3,32,32) and captions (B,%d,300) for its B = %d "
                              "proposals (got %s, %s)" % (steps, steps, B, tuple(image.shape), tuple(text.shape)))
         text = torch.zeros(B, 1, dtype=torch.int64, device=mu.device)          # the one "class" of the one caption position
-        decoder = model.decoder if fam.text_only else model.text_decoder
-        extra = dict(sos=decoder.sos.to(mu.device, torch.float32).contiguous(), scale=-0.5 / float(text_sigma) ** 2)
+        extra = dict(sos=fam.reach(model, "captions").sos.to(mu.device, torch.float32).contiguous(), scale=-0.5 / float(text_sigma) ** 2)
     else:
         text = text.contiguous().long()
     if image.shape[1] != int(np.prod(fam.image_shape)) or text.numel() != B * fam.T:
@@ -503,17 +456,17 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
         extra["sse"] = torch.empty(rows_max, **f32)
         sse_all = torch.empty(B, K, **f32) if return_log_w else None
     stream = _ops.stream()
-    _iw_call("mmvae_iw_init", ptr(state), B, stream)
+    call("mmvae_iw_init", ptr(state), B, stream)
     for r0, nr, k0, nk in chunks:
         rows = nr * nk
         e = None if eps is None else eps[r0:r0 + nr, k0:k0 + nk].contiguous()
         lwc = None if lw_all is None else torch.empty(nr, nk, 3, **f32)
-        _iw_call("mmvae_iw_particles", ptr(mu[r0:]), ptr(logvar[r0:]), nr, D, nk, int(first_row) + r0, k0, int(seed) & (2 ** 64 - 1),
-                 ptr(e), ptr(zbuf), ptr(lr), stream)
+        call("mmvae_iw_particles", ptr(mu[r0:]), ptr(logvar[r0:]), nr, D, nk, int(first_row) + r0, k0, int(seed) & (2 ** 64 - 1),
+             ptr(e), ptr(zbuf), ptr(lr), stream)
         if fam.float_text:
             extra["text"] = captions[r0:]
         fam.score(st, rows, ws, ws_bytes, zbuf, image[r0:], nr, nk, lx, words, stream, **extra)
-        _iw_call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(text[r0:]), fam.T, fam.V, ptr(lr), nr, nk, ptr(state[r0:]), ptr(lwc), stream)
+        call("mmvae_iw_accumulate", ptr(lx), ptr(words), ptr(text[r0:]), fam.T, fam.V, ptr(lr), nr, nk, ptr(state[r0:]), ptr(lwc), stream)
         if z_all is not None:
             z_all[r0:r0 + nr, k0:k0 + nk] = zbuf[:rows * D].view(nr, nk, D)
         if lw_all is not None:
@@ -521,7 +474,7 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
         if sse_all is not None:
             sse_all[r0:r0 + nr, k0:k0 + nk] = extra["sse"][:rows].view(nr, nk)
     out = torch.empty(B, 8, **f32)
-    _iw_call("mmvae_iw_finalize", ptr(state), B, K, ptr(out), stream)
+    call("mmvae_iw_finalize", ptr(state), B, K, ptr(out), stream)
     if fam.float_text:
         _shift_text_terms(out, lw_all, text_const)
     if fam.image_only:          # an ImageVAE defines p(x) alone
@@ -543,36 +496,35 @@ def iw_estimate(model, image, text, mu, logvar, n_particles, seed=0, first_row=0
     return res
 
 
+def _posterior_of(model, fam, image, second, posterior):
+    """(mu, logvar) of ``posterior`` ("joint", "image", "text" / "attrs") on a model of the kind ``fam``: the encoder of the one
+    modality, or both encoders stacked image first, then the experts; a uni-modal model's own encoder is q itself (it has no
+    experts).  No decoder runs."""
+    posterior = _posterior(posterior)
+    if fam.text_only:
+        if posterior != "text":
+            raise ValueError("a TextVAE has the text posterior alone: posterior must be \"text\" (got %r)" % (posterior,))
+        return fam.reach(model, "encode_second")(second)
+    if fam.image_only:
+        if posterior != "image":
+            raise ValueError("an ImageVAE has the image posterior alone: posterior must be \"image\" (got %r)" % (posterior,))
+        return fam.reach(model, "encode_image")(image)
+    if posterior not in POSTERIORS:
+        raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
+    parts = []
+    if posterior != "text":
+        parts.append(fam.reach(model, "encode_image")(image))
+    if posterior != "image":
+        parts.append(fam.reach(model, "encode_second")(second))
+    return fam.reach(model, "experts")(torch.stack([p[0] for p in parts], dim=0), torch.stack([p[1] for p in parts], dim=0))
+
+
 def _proposal(model, image, text, posterior):
     """(mu, logvar) of the eval-mode encoders + ProductOfExperts over the posterior's modalities (no decoder runs)."""
     fam = _family(model)
-    posterior = _posterior(posterior)
-    if fam.text_only:           # q(z|y) of the encoder itself: a TextVAE has no experts
-        if posterior != "text":
-            raise ValueError("a TextVAE has the text posterior alone: posterior must be \"text\" (got %r)" % (posterior,))
-        return model.encoder(text)
-    image = image.reshape(image.shape[0], *fam.image_shape)
-    if fam.image_only:          # q(z|x) of the encoder itself: an ImageVAE has no experts
-        if posterior != "image":
-            raise ValueError("an ImageVAE has the image posterior alone: posterior must be \"image\" (got %r)" % (posterior,))
-        return model.encode(image) if fam.name == "mnist" else model.encoder(image)      # (mnist.VAE's encoder is the bare Sequential)
-    if fam.name == "celeba":
-        second = (lambda t: model.attrs_encoder(t.float()))        # the (B,18) attributes as float
-    else:
-        second = model.text_encoder
-    if posterior == "joint":
-        im_mu, im_lv = model.image_encoder(image)
-        tx_mu, tx_lv = second(text)
-        mu, lv = torch.stack((im_mu, tx_mu), dim=0), torch.stack((im_lv, tx_lv), dim=0)
-    elif posterior == "image":
-        mu, lv = model.image_encoder(image)
-        mu, lv = mu.unsqueeze(0), lv.unsqueeze(0)
-    elif posterior == "text":
-        mu, lv = second(text)
-        mu, lv = mu.unsqueeze(0), lv.unsqueeze(0)
-    else:
-        raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
-    return model.experts(mu, lv)
+    if not fam.text_only:
+        image = image.reshape(image.shape[0], *fam.image_shape)
+    return _posterior_of(model, fam, image, text, posterior)
 
 
 @torch.no_grad()
@@ -594,18 +546,18 @@ def log_marginal(model, loader, n_particles=1000, posterior="joint", seed=0, use
     posterior = _posterior(posterior)
     if posterior not in POSTERIORS:
         raise ValueError("posterior must be one of %s (got %r)" % (POSTERIORS, posterior))
-    if _family(model).image_only and posterior != "image":
+    fam = _family(model)
+    if fam.image_only and posterior != "image":
         raise ValueError("an ImageVAE has the image posterior alone: posterior must be \"image\" (got %r)" % (posterior,))
-    if _family(model).text_only and posterior != "text":
+    if fam.text_only and posterior != "text":
         raise ValueError("a TextVAE has the text posterior alone: posterior must be \"text\" (got %r)" % (posterior,))
     model.eval()
     dev = next(model.parameters()).device
     logp, ess, nll, n_seen = [], [], [], 0
     for image, text in loader:
-        fam = _family(model)
         image = None if fam.text_only else image.to(dev).float().reshape(-1, *fam.image_shape)      # (a TextVAE's loader may yield None there)
         text = None if fam.image_only else text.to(dev).float() if fam.float_text else text.to(dev).long()
-        mu, logvar = _proposal(model, image, text, posterior)
+        mu, logvar = _posterior_of(model, fam, image, text, posterior)
         r = iw_estimate(model, image, text, mu, logvar, n_particles, seed=seed, first_row=n_seen, text_sigma=text_sigma)
         logp.append(r["log_p"]); ess.append(r["ess"]); nll.append(r["nll"])
         n_seen += mu.shape[0]
@@ -629,63 +581,49 @@ def marginal_table(model, loader, n_particles=1000, seed=0, text_sigma=1.0):
 # ------------------------------------------------------------------------------------------------------------------
 # multimnist/sample.py:59-144 as a function and a script: `python -m multimodal_vae_amd.evaluate sample model.pth.tar ...`
 
+def _sample_latents(vae, fam, n_samples, image, second, dev, seed=None):
+    """z (n_samples, n_latents) on ``dev`` for the samplers: the prior (image = second = None: the one-element mu = 0, std = 1) or the
+    posterior of what is given (``_posterior_of``), then ONE host-side draw -- from the global generator, or from a generator of
+    its own when ``seed`` is given -- made after the encoders ran, moved to the device and combined as z * std + mu."""
+    vae.eval()
+    if image is None and second is None:
+        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
+    else:
+        posterior = "text" if image is None else "image" if second is None else "joint"
+        mu, logvar = _posterior_of(vae, fam, None if image is None else image.to(dev), None if second is None else second.to(dev), posterior)
+        std = logvar.mul(0.5).exp()
+    z = torch.randn(n_samples, vae.n_latents, generator=None if seed is None else torch.Generator().manual_seed(seed)).to(dev)
+    return (z * std.expand_as(z) + mu.expand_as(z)).contiguous()
+
+
+def _pictures(fam, vae, z):
+    """The image decoder's samples on the host, (n, *the family's picture shape)."""
+    return fam.reach(vae, "decode_image")(z).cpu().view(z.shape[0], *fam.picture)
+
+
 @torch.no_grad()
 def sample(vae, n_samples=64, image=None, text=None, use_cuda=True):
     """Unconditional (image = text = None) or conditional generation: (image samples (n,1,50,50), token samples (n,4) LongTensor).
     ``image``: (1,1,50,50) float in [0,1]; ``text``: (1,4) LongTensor (utils.char_tensor) -- multimnist/sample.py:80-130."""
-    vae.eval()
-    n_latents = vae.n_latents
-    dev = torch.device("cuda") if use_cuda else torch.device("cpu")
-    if image is None and text is None:
-        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
-    elif text is None:
-        mu, logvar = vae.encode_image(image.to(dev))
-        std = logvar.mul(0.5).exp()
-    elif image is None:
-        mu, logvar = vae.encode_text(text.to(dev))
-        std = logvar.mul(0.5).exp()
-    else:
-        image_mu, image_logvar = vae.encode_image(image.to(dev))
-        text_mu, text_logvar = vae.encode_text(text.to(dev))
-        mu, logvar = vae.experts(torch.stack((image_mu, text_mu), dim=0), torch.stack((image_logvar, text_logvar), dim=0))
-        std = logvar.mul(0.5).exp()
-    z = torch.randn(n_samples, n_latents).to(dev)
-    z = z * std.expand_as(z) + mu.expand_as(z)
-    image_recon = vae.decode_image(z.contiguous()).cpu().view(n_samples, 1, 50, 50)
-    text_recon = torch.max(vae.decode_text(z.contiguous()).cpu(), dim=2)[1]
-    return image_recon, text_recon
+    fam = _FAMILIES["multimnist"]
+    z = _sample_latents(vae, fam, n_samples, image, text, torch.device("cuda") if use_cuda else torch.device("cpu"))
+    return _pictures(fam, vae, z), torch.max(fam.reach(vae, "decode_second")(z).cpu(), dim=2)[1]
 
 
 @torch.no_grad()
 def sample_textonly(vae, n_samples=64, text=None):
     """``sample`` for a multimnist ``TextVAE``: token samples (n,4) LongTensor, from the prior or from q(z|y) of ``text`` (1,4)."""
-    vae.eval()
-    dev = next(vae.parameters()).device
-    if text is None:
-        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
-    else:
-        mu, logvar = vae.encode(text.to(dev))
-        std = logvar.mul(0.5).exp()
-    z = torch.randn(n_samples, vae.n_latents).to(dev)
-    z = z * std.expand_as(z) + mu.expand_as(z)
-    return torch.max(vae.decode(z.contiguous()).cpu(), dim=2)[1]
+    fam = _FAMILIES["multimnist_text"]
+    z = _sample_latents(vae, fam, n_samples, None, text, next(vae.parameters()).device)
+    return torch.max(fam.reach(vae, "decode_second")(z).cpu(), dim=2)[1]
 
 
 @torch.no_grad()
 def sample_imageonly(vae, n_samples=64, image=None):
     """``sample`` for a multimnist ``ImageVAE``: image samples (n,1,50,50), from the prior or from q(z|x) of ``image`` (1,1,50,50); for
     a ``mnist.VAE`` (mnist/imageonly/sample_imageonly.py:58-83) samples (n,1,28,28), ``image`` (1,784)."""
-    vae.eval()
-    dev = next(vae.parameters()).device
-    side = 28 if _family(vae).name == "mnist" else 50
-    if image is None:
-        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
-    else:
-        mu, logvar = vae.encode(image.to(dev))
-        std = logvar.mul(0.5).exp()
-    z = torch.randn(n_samples, vae.n_latents).to(dev)
-    z = z * std.expand_as(z) + mu.expand_as(z)
-    return vae.decode(z.contiguous()).cpu().view(n_samples, 1, side, side)
+    fam = _family(vae)
+    return _pictures(fam, vae, _sample_latents(vae, fam, n_samples, image, None, next(vae.parameters()).device))
 
 
 @torch.no_grad()
@@ -693,34 +631,11 @@ def sample_coco(vae, n_samples=64, image=None, text=None, stop_at_eos=False, see
     """multimnist/sample.py:80-130 for the COCO family: prior samples (image = text = None) or samples of the conditional
     posterior -> (images (n,3,32,32) float on the host, n caption strings).  ``image``: (1,3,32,32) float in [0,1]; ``text``:
     (1,102,300) caption vectors (``WordTable.embed``).  ``vae`` carries the word table (``MultimodalVAE(..., words=)``)."""
-    vae.eval()
-    dev = next(vae.parameters()).device
-    text_only = _family(vae).text_only          # a TextVAE: captions alone (the images are None), conditioned on a caption at most
-    if text_only and image is not None:
+    fam = _family(vae)                          # a TextVAE: captions alone (the images are None), conditioned on a caption at most
+    if fam.text_only and image is not None:
         raise ValueError("sample_coco: a TextVAE cannot be conditioned on an image")
-    if image is None and text is None:
-        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
-    elif text_only:
-        mu, logvar = vae.encode(text.to(dev))
-        std = logvar.mul(0.5).exp()
-    elif text is None:
-        mu, logvar = vae.encode_image(image.to(dev))
-        std = logvar.mul(0.5).exp()
-    elif image is None:
-        mu, logvar = vae.encode_text(text.to(dev))
-        std = logvar.mul(0.5).exp()
-    else:
-        image_mu, image_logvar = vae.encode_image(image.to(dev))
-        text_mu, text_logvar = vae.encode_text(text.to(dev))
-        mu, logvar = vae.experts(torch.stack((image_mu, text_mu), dim=0), torch.stack((image_logvar, text_logvar), dim=0))
-        std = logvar.mul(0.5).exp()
-    g = None if seed is None else torch.Generator().manual_seed(seed)
-    z = torch.randn(n_samples, vae.n_latents, generator=g).to(dev)
-    z = (z * std.expand_as(z) + mu.expand_as(z)).contiguous()
-    if text_only:
-        return None, vae.decoder.generate(z, stop_at_eos=stop_at_eos)
-    image_recon = vae.decode_image(z).cpu().view(n_samples, 3, 32, 32)
-    return image_recon, vae.text_decoder.generate(z, stop_at_eos=stop_at_eos)
+    z = _sample_latents(vae, fam, n_samples, image, text, next(vae.parameters()).device, seed)
+    return None if fam.text_only else _pictures(fam, vae, z), fam.reach(vae, "captions").generate(z, stop_at_eos=stop_at_eos)
 
 
 @torch.no_grad()
@@ -729,27 +644,9 @@ def sample_celeba(vae, n_samples=64, image=None, attrs=None, seed=None):
     attributes, or given both (product of experts) -> (images (n,3,64,64) float on the host, n lists of attribute names).
     ``image``: (1,3,64,64) float in [0,1]; ``attrs``: (1,18) float (``celeba.attrs_from_names``)."""
     from .celeba import tensor_to_attributes
-    vae.eval()
-    dev = next(vae.parameters()).device
-    if image is None and attrs is None:
-        mu, std = torch.zeros(1, device=dev), torch.ones(1, device=dev)
-    elif attrs is None:
-        mu, logvar = vae.image_encoder(image.to(dev))
-        std = logvar.mul(0.5).exp()
-    elif image is None:
-        mu, logvar = vae.attrs_encoder(attrs.to(dev))
-        std = logvar.mul(0.5).exp()
-    else:
-        image_mu, image_logvar = vae.image_encoder(image.to(dev))
-        attrs_mu, attrs_logvar = vae.attrs_encoder(attrs.to(dev))
-        mu, logvar = vae.experts(torch.stack((image_mu, attrs_mu), dim=0), torch.stack((image_logvar, attrs_logvar), dim=0))
-        std = logvar.mul(0.5).exp()
-    g = None if seed is None else torch.Generator().manual_seed(seed)
-    z = torch.randn(n_samples, vae.n_latents, generator=g).to(dev)
-    z = (z * std.expand_as(z) + mu.expand_as(z)).contiguous()
-    image_recon = vae.image_decoder(z).cpu().view(n_samples, 3, 64, 64)
-    attrs_recon = vae.attrs_decoder(z).cpu()
-    return image_recon, [tensor_to_attributes(row) for row in attrs_recon]
+    fam = _FAMILIES["celeba"]
+    z = _sample_latents(vae, fam, n_samples, image, attrs, next(vae.parameters()).device, seed)
+    return _pictures(fam, vae, z), [tensor_to_attributes(row) for row in fam.reach(vae, "decode_second")(z).cpu()]
 
 
 def fetch_celeba_image(path, attr_str, seed=0):
@@ -865,10 +762,11 @@ def manifold(vae, loader, pca_only=False, perplexity=40, n_iter=300, seed=0):
     from .tsne import pca, tsne
     vae.eval()
     dev = next(vae.parameters()).device
+    fam = _family(vae)
     zs, labels = [], []
     for image, text in loader:
-        x = image.to(dev).float().reshape(-1, 784)
-        z = vae.encode(x)[0] if _family(vae).image_only else vae.gen_latents(x, text.to(dev))
+        x = image.to(dev).float().reshape(-1, *fam.image_shape)
+        z = fam.reach(vae, "encode_image")(x)[0] if fam.image_only else vae.gen_latents(x, text.to(dev))
         zs.append(z.float().clone())
         labels.append(text.cpu())
     latents, labels = torch.cat(zs).contiguous(), torch.cat(labels)
@@ -909,6 +807,35 @@ def latent_viz(vae, nx=20, ny=20, lim=3.0):
     return canvas, digits
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# the command line
+
+def _add_modes(p, image_help, second, second_help):
+    """The posterior trio: --image_only | --<second>_only | --all."""
+    mode = p.add_mutually_exclusive_group()
+    mode.add_argument('--image_only', action='store_true', default=False, help=image_help)
+    mode.add_argument('--%s_only' % second, action='store_true', default=False, help=second_help)
+    mode.add_argument('--all', action='store_true', default=False, help='all three posteriors (the paper\'s table)')
+
+
+def _add_source(p, data_help, synthetic_help, default=None, metavar='FILE.pt'):
+    """--data | --synthetic N."""
+    src = p.add_mutually_exclusive_group()
+    src.add_argument('--data', type=str, default=default, metavar=metavar, help=data_help)
+    src.add_argument('--synthetic', type=int, default=0, metavar='N', help=synthetic_help)
+
+
+def _add_sos_words(p):
+    tab = p.add_mutually_exclusive_group()
+    tab.add_argument('--sos', type=str, default=None, metavar='FILE.pt', help="the 300 floats of GloVe('<s>') (default: sos.pt of --data)")
+    tab.add_argument('--words', type=str, default=None, metavar='TABLE.pt', help="word table file (coco.save_word_table) that has '<s>'")
+
+
+def _add_seed_json(p, seed_help, json_help='write the bounds to this file'):
+    p.add_argument('--seed', type=int, default=0, help=seed_help)
+    p.add_argument('--json', type=str, default=None, help=json_help)
+
+
 def _parser():
     import argparse
     parser = argparse.ArgumentParser(prog="python -m multimodal_vae_amd.evaluate")
@@ -929,58 +856,36 @@ def _parser():
     pl.add_argument('model_path', type=str, help='path to trained model file')
     pl.add_argument('--dataset', type=str, default='multimnist', choices=('multimnist', 'mnist'),
                     help='model family of the checkpoint (mnist: --data names a .pt file of (uint8 images (N,28,28), int64 labels (N,)))')
-    mode = pl.add_mutually_exclusive_group()
-    mode.add_argument('--image_only', action='store_true', default=False,
-                      help='compute NLL of test data using reconstructions from image only')
-    mode.add_argument('--text_only', action='store_true', default=False,
-                      help='compute NLL of test data using reconstructions from text only')
-    mode.add_argument('--all', action='store_true', default=False, help='all three posteriors (the paper\'s table)')
+    _add_modes(pl, 'compute NLL of test data using reconstructions from image only',
+               'text', 'compute NLL of test data using reconstructions from text only')
     pl.add_argument('--n_samples', type=int, default=100, help='number of samples to use to estimate the ELBO')
     pl.add_argument('--cuda', action='store_true', default=False, help='accepted for compatibility: the kernels run on the GPU')
     pl.add_argument('--batch_size', type=int, default=64)
-    src = pl.add_mutually_exclusive_group()
-    src.add_argument('--data', type=str, default='./data', help='folder of the MultiMNIST test file')
-    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic MultiMNIST-shaped examples instead of files')
-    pl.add_argument('--seed', type=int, default=0, help='seed of the particles')
-    pl.add_argument('--json', type=str, default=None, help='write the bounds to this file')
+    _add_source(pl, 'folder of the MultiMNIST test file', 'N synthetic MultiMNIST-shaped examples instead of files', './data', None)
+    _add_seed_json(pl, 'seed of the particles')
     # celeba/loglikelihood.py's flags and defaults, plus the ones `loglik` adds
     pc = sub.add_parser("loglik_celeba", help="celeba/loglikelihood.py + importance-sampled log p(x), log p(y)")
     pc.add_argument('model_path', type=str, help='path to trained model file')
-    mode = pc.add_mutually_exclusive_group()
-    mode.add_argument('--image_only', action='store_true', default=False,
-                      help='compute NLL of test data using reconstructions from image only')
-    mode.add_argument('--attrs_only', action='store_true', default=False,
-                      help='compute NLL of test data using reconstructions from attributes only')
-    mode.add_argument('--all', action='store_true', default=False, help='all three posteriors (the paper\'s table)')
+    _add_modes(pc, 'compute NLL of test data using reconstructions from image only',
+               'attrs', 'compute NLL of test data using reconstructions from attributes only')
     pc.add_argument('--n_samples', type=int, default=100, help='number of samples to use to estimate the ELBO')
     pc.add_argument('--cuda', action='store_true', default=False, help='accepted for compatibility: the kernels run on the GPU')
     pc.add_argument('--batch_size', type=int, default=64)
-    src = pc.add_mutually_exclusive_group()
-    src.add_argument('--data', type=str, default=None, metavar='FILE.pt',
-                     help='a .pt file of (uint8 images (N,3,64,64), attributes (N,18) with values 0 / 1)')
-    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic CelebA-shaped examples instead of a file')
-    pc.add_argument('--seed', type=int, default=0, help='seed of the particles')
-    pc.add_argument('--json', type=str, default=None, help='write the bounds to this file')
+    _add_source(pc, 'a .pt file of (uint8 images (N,3,64,64), attributes (N,18) with values 0 / 1)',
+                'N synthetic CelebA-shaped examples instead of a file')
+    _add_seed_json(pc, 'seed of the particles')
     # the flags of `loglik` for a checkpoint of train_coco; the '<s>' vector is not in the checkpoint
     pk = sub.add_parser("loglik_coco", help="importance-sampled log p(x), log p(y) for a checkpoint of train_coco")
     pk.add_argument('model_path', type=str, help='path to a checkpoint written by train_coco')
-    tab = pk.add_mutually_exclusive_group()
-    tab.add_argument('--sos', type=str, default=None, metavar='FILE.pt', help="the 300 floats of GloVe('<s>') (default: sos.pt of --data)")
-    tab.add_argument('--words', type=str, default=None, metavar='TABLE.pt', help="word table file (coco.save_word_table) that has '<s>'")
-    mode = pk.add_mutually_exclusive_group()
-    mode.add_argument('--image_only', action='store_true', default=False, help='proposal from the image only')
-    mode.add_argument('--text_only', action='store_true', default=False, help='proposal from the caption only')
-    mode.add_argument('--all', action='store_true', default=False, help='all three posteriors (the paper\'s table)')
+    _add_sos_words(pk)
+    _add_modes(pk, 'proposal from the image only', 'text', 'proposal from the caption only')
     pk.add_argument('--n_samples', type=int, default=100, help='particles per example')
     pk.add_argument('--batch_size', type=int, default=64)
     pk.add_argument('--text_sigma', type=float, default=1.0,
                     help='sigma of the Gaussian caption likelihood; log p(y) depends on it (default: 1.0)')
-    src = pk.add_mutually_exclusive_group()
-    src.add_argument('--data', type=str, default=None, metavar='DIR', help='folder with images_u8.pt, captions.pt (and sos.pt), as train_coco reads')
-    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic COCO-shaped examples instead of files')
-    pk.add_argument('--seed', type=int, default=0, help='seed of the particles (and of the synthetic examples)')
-    pk.add_argument('--json', type=str, default=None, help='write the bounds to this file')
-    # multimnist/sample.py's flags for a checkpoint of train_coco; the captions are decoded through a word table
+    _add_source(pk, 'folder with images_u8.pt, captions.pt (and sos.pt), as train_coco reads',
+                'N synthetic COCO-shaped examples instead of files', metavar='DIR')
+    _add_seed_json(pk, 'seed of the particles (and of the synthetic examples)')
     pt = sub.add_parser("test_imageonly", help="celeba/test_imageonly.py: eval-mode loss (kl_lambda = 1) of a train_imageonly checkpoint")
     pt.add_argument('model_path', type=str)
     pt.add_argument('--dataset', choices=('celeba', 'coco', 'multimnist', 'mnist'), default='celeba')
@@ -998,9 +903,8 @@ def _parser():
     px.add_argument('--synthetic', type=int, default=0, metavar='N')
     px.add_argument('--batch_size', type=int, default=64, metavar='N')
     px.add_argument('--seed', type=int, default=0)
-    tab = px.add_mutually_exclusive_group()
-    tab.add_argument('--sos', type=str, default=None, metavar='FILE.pt', help="the 300 floats of GloVe('<s>') (default: sos.pt of --data)")
-    tab.add_argument('--words', type=str, default=None, metavar='TABLE.pt', help="word table file (coco.save_word_table) that has '<s>'")
+    _add_sos_words(px)
+    # multimnist/sample.py's flags for a checkpoint of train_coco; the captions are decoded through a word table
     pw = sub.add_parser("sample_coco", help="multimnist/sample.py for the COCO family: images + captions decoded to words")
     pw.add_argument('model_path', type=str, help='path to a checkpoint written by train_coco')
     tab = pw.add_mutually_exclusive_group(required=True)
@@ -1035,36 +939,28 @@ def _parser():
     # exact log-likelihood of images under a checkpoint of train_pixelcnn
     pn = sub.add_parser("nll_pixelcnn", help="exact NLL per image and bits/dim for a PixelCNN / GatedPixelCNN checkpoint")
     pn.add_argument('model_path', type=str, help='path to a checkpoint written by train_pixelcnn')
-    src = pn.add_mutually_exclusive_group()
-    src.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='a .pt file of uint8 images (N,C,H,W)')
-    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic images instead of a file')
+    _add_source(pn, 'a .pt file of uint8 images (N,C,H,W)', 'N synthetic images instead of a file')
     pn.add_argument('--batch_size', type=int, default=32)
     pn.add_argument('--head', choices=('torch', 'hip'), default='torch',
                     help='conv4 + cross entropy as torch ops or as the fused HIP head (hip needs --cuda; default: torch)')
     pn.add_argument('--cuda', action='store_true', default=False, help='evaluate on the GPU (default: False)')
-    pn.add_argument('--seed', type=int, default=0, help='seed of the synthetic images')
-    pn.add_argument('--json', type=str, default=None, help='write the result to this file')
+    _add_seed_json(pn, 'seed of the synthetic images', 'write the result to this file')
     # aggregate posterior against the prior for a checkpoint of train_infovae
     pm = sub.add_parser("latent_mmd", help="MMD between the encoded test images and the prior, for a checkpoint of train_infovae")
     pm.add_argument('model_path', type=str, help='path to a checkpoint written by train_infovae (mnist: train_infovae_mnist)')
     pm.add_argument('--dataset', type=str, default='coco', choices=('coco', 'mnist'),
                     help='model family of the checkpoint (mnist: uint8 images (N,28,28), alone or as the first entry of a tuple)')
     pm.add_argument('--conv_backend', choices=('torch', 'hip'), default='torch', help='mnist: what the convolutions run on (default: torch)')
-    src = pm.add_mutually_exclusive_group()
-    src.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='a .pt file of uint8 images (N,3,32,32)')
-    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic images of the family\'s shape instead of a file')
+    _add_source(pm, 'a .pt file of uint8 images (N,3,32,32)', 'N synthetic images of the family\'s shape instead of a file')
     pm.add_argument('--batch_size', type=int, default=500)
-    pm.add_argument('--seed', type=int, default=0, help='seed of the prior samples (and of the synthetic images)')
-    pm.add_argument('--json', type=str, default=None, help='write the terms to this file')
+    _add_seed_json(pm, 'seed of the prior samples (and of the synthetic images)', 'write the terms to this file')
     # mnist/manifold.py: the test set's latents reduced to 2-D by PCA or by exact t-SNE on the GPU
     pf = sub.add_parser("manifold", help="mnist/manifold.py: latents of the test set, PCA or PCA + t-SNE to 2-D")
     pf.add_argument('model_path', type=str, help='path to trained model file (mnist family; a train_imageonly checkpoint embeds the encoder\'s mu)')
     pf.add_argument('--pca_only', action='store_true', default=False)
     pf.add_argument('--perplexity', type=float, default=40.0)
     pf.add_argument('--n_iter', type=int, default=300)
-    src = pf.add_mutually_exclusive_group()
-    src.add_argument('--data', type=str, default=None, metavar='FILE.pt', help='a .pt file of (uint8 images (N,28,28), int64 labels (N,))')
-    src.add_argument('--synthetic', type=int, default=0, metavar='N', help='N synthetic MNIST-shaped examples instead of a file')
+    _add_source(pf, 'a .pt file of (uint8 images (N,28,28), int64 labels (N,))', 'N synthetic MNIST-shaped examples instead of a file')
     pf.add_argument('--batch_size', type=int, default=128)
     pf.add_argument('--seed', type=int, default=0, help='seed of the initial embedding (and of the synthetic images)')
     pf.add_argument('--out', type=str, default='./results')
@@ -1075,67 +971,209 @@ def _parser():
     return parser
 
 
-def _latent_mmd_main(args):
-    import json
-    if args.dataset == "mnist":
-        from . import data as D
-        from .mnist import load_infovae_checkpoint, set_infovae_backend
-        if args.synthetic > 0:
-            x = D.synthetic_mnist(args.synthetic, seed=args.seed)[0]
-        elif args.data:
-            x = torch.load(args.data, weights_only=False)
-            x = torch.as_tensor(x[0] if isinstance(x, (tuple, list)) else x)
+def load_celeba_eval_file(path):
+    """The ``--data`` file of ``loglik_celeba``: (uint8 images (N,3,64,64), attributes (N,18)) -> (uint8 images, float32
+    attributes).  Attributes other than 0 / 1 are refused here, on the host: the scorer indexes (log(1 - p), log p) with them."""
+    x, a = torch.load(path, weights_only=False)
+    x, a = torch.as_tensor(x), torch.as_tensor(a)
+    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 64, 64):
+        raise ValueError("%s: images must be uint8 (N,3,64,64) (got %s %s)" % (path, x.dtype, tuple(x.shape)))
+    if a.dim() != 2 or a.shape[0] != x.shape[0] or a.shape[1] != 18:
+        raise ValueError("%s: attributes must be (N,18) for the N = %d images (got %s)" % (path, x.shape[0], tuple(a.shape)))
+    a = a.float()
+    if not bool(((a == 0) | (a == 1)).all()):
+        raise ValueError("%s: every attribute must be 0 or 1" % path)
+    return x, a
+
+
+def check_coco_eval_data(images, captions, text_sigma=1.0, where="loglik_coco"):
+    """The host-side refusals of ``loglik_coco``: images must be uint8 (N,3,32,32), captions float (N,102,300) for the same N >= 1,
+    sigma > 0.  -> (uint8 images, float32 captions)."""
+    from .coco import MAX_WORDS, N_EMBEDDING
+    coco_text_constant(MAX_WORDS, text_sigma)                     # refuses sigma <= 0 / non-finite
+    x, t = torch.as_tensor(images), torch.as_tensor(captions)
+    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 32, 32) or x.shape[0] < 1:
+        raise ValueError("%s: images must be uint8 (N,3,32,32) with N >= 1 (got %s %s)" % (where, x.dtype, tuple(x.shape)))
+    if not t.is_floating_point() or t.dim() != 3 or tuple(t.shape) != (x.shape[0], MAX_WORDS, N_EMBEDDING):
+        raise ValueError("%s: captions must be float (N,%d,%d) for the N = %d images (got %s %s)"
+                         % (where, MAX_WORDS, N_EMBEDDING, x.shape[0], t.dtype, tuple(t.shape)))
+    return x, t.float()
+
+
+def _eval_data(dataset, args, where, hint="--data FILE.pt", parts="xt"):
+    """The one reader of evaluation data: ``--synthetic N`` (seeded by ``--seed``) or ``--data`` of "mnist" (a .pt file of (images,
+    labels), or of the images alone), "multimnist" (the folder of the test file), "celeba" (a file of ``make_celeba``) or "coco" (a
+    folder of images_u8.pt, captions.pt, sos.pt, read for the ``parts`` "x" / "t" the command uses; or the images' own .pt file).
+    -> (uint8 images or None, second modality or None, extras: COCO's {"sos": the data's '<s>' vector}), after the shape and dtype
+    refusals the command ``where`` makes."""
+    import os
+    from . import data as D
+    load = functools.partial(torch.load, weights_only=False)
+    n, path, extras = getattr(args, "synthetic", 0), args.data, {}
+    if n <= 0 and not path:
+        raise SystemExit("%s: give %s or --synthetic N" % (where, hint))
+    if dataset == "mnist":
+        f = D.synthetic_mnist(n, seed=args.seed) if n > 0 else load(path)      # (torchvision's processed/test.pt)
+        x, t = (torch.as_tensor(v) for v in f) if isinstance(f, (tuple, list)) else (torch.as_tensor(f), None)
+    elif dataset == "multimnist":
+        if n > 0:
+            from .utils import charlist_tensor
+            x, labels = D.synthetic_multimnist(n, seed=args.seed)
+            t = torch.stack([charlist_tensor(l) for l in labels])
         else:
-            raise SystemExit("latent_mmd: give --data FILE.pt or --synthetic N")
-        if x.dtype != torch.uint8 or x.dim() != 3 or tuple(x.shape[1:]) != (28, 28):
-            raise ValueError("latent_mmd: images must be uint8 (N,28,28) (got %s %s)" % (x.dtype, tuple(x.shape)))
-        x = x.float().div_(255.0).unsqueeze(1)                        # transforms.ToTensor()
-        loader = [x[i:i + args.batch_size] for i in range(0, x.shape[0], args.batch_size)]
-        vae = set_infovae_backend(load_infovae_checkpoint(args.model_path, use_cuda=True), args.conv_backend)
-        out = latent_mmd(vae, loader, seed=args.seed)
-        if args.json:
-            with open(args.json, 'w') as fp:
-                json.dump(out, fp, indent=1)
-        return out
-    from .train_coco import synthetic_coco
-    from .train_infovae import load_checkpoint
-    if args.synthetic > 0:
-        x = synthetic_coco(args.synthetic, seed=args.seed)[0]
-    elif args.data:
-        x = torch.as_tensor(torch.load(args.data, weights_only=False))
+            x, t = D.load_multimnist(path, train=False)
+    elif dataset == "celeba":
+        x, t = D.synthetic_celeba(n, seed=args.seed) if n > 0 else load_celeba_eval_file(path)
     else:
-        raise SystemExit("latent_mmd: give --data FILE.pt or --synthetic N")
-    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 32, 32):
-        raise ValueError("latent_mmd: images must be uint8 (N,3,32,32) (got %s %s)" % (x.dtype, tuple(x.shape)))
-    x = x.float().div_(255.0)                                     # transforms.ToTensor()
-    loader = [x[i:i + args.batch_size] for i in range(0, x.shape[0], args.batch_size)]
-    vae = load_checkpoint(args.model_path, use_cuda=True)
-    out = latent_mmd(vae, loader, seed=args.seed)
-    if args.json:
-        with open(args.json, 'w') as fp:
+        x = t = None
+        if n > 0:
+            from .train_coco import synthetic_coco
+            x, t, extras["sos"] = synthetic_coco(n, seed=args.seed)
+        else:
+            if "x" in parts:
+                x = torch.as_tensor(load(os.path.join(path, "images_u8.pt") if os.path.isdir(path) else path))
+            if "t" in parts:
+                t = torch.as_tensor(load(os.path.join(path, "captions.pt")))
+                if not args.sos and not args.words:
+                    extras["sos"] = load(os.path.join(path, "sos.pt"))
+    if where == "loglik_coco":
+        x, t = check_coco_eval_data(x, t, args.text_sigma)
+    elif where == "latent_mmd":
+        shape = (28, 28) if dataset == "mnist" else (3, 32, 32)
+        if x.dtype != torch.uint8 or tuple(x.shape[1:]) != shape:
+            raise ValueError("latent_mmd: images must be uint8 (N,%s) (got %s %s)" % (",".join(map(str, shape)), x.dtype, tuple(x.shape)))
+    elif where == "manifold":
+        if x.dtype != torch.uint8 or tuple(x.shape[1:]) != (28, 28) or t is None or t.shape != x.shape[:1]:
+            raise ValueError("manifold: need uint8 images (N,28,28) and N labels (got %s %s, %s)"
+                             % (x.dtype, tuple(x.shape), None if t is None else tuple(t.shape)))
+    return (x if "x" in parts else None), (t if "t" in parts else None), extras
+
+
+def _batches(x, t, batch_size, whole_only=False):
+    """[(rows of x, rows of t)] in batches of ``batch_size`` (either tensor may be None).  ``whole_only``: batches of one size, at most
+    the whole set (the plans of ``test_imageonly`` / ``test_textonly`` take a fixed batch size); a trailing partial batch is dropped."""
+    n = (t if x is None else x).shape[0]
+    bs = min(batch_size, n) if whole_only else batch_size
+    return [(None if x is None else x[i:i + bs], None if t is None else t[i:i + bs])
+            for i in range(0, n - bs + 1 if whole_only else n, bs)]
+
+
+def _sos_words(args, sos, where):
+    """``--sos`` / ``--words`` over the '<s>' vector that came with the data -> (sos or None, word table or None)."""
+    from . import coco as K
+    words = None
+    if args.sos:
+        sos = torch.load(args.sos, weights_only=False)
+    elif args.words:
+        sos, words = None, K.load_word_table(args.words)
+    if sos is not None:
+        sos = torch.as_tensor(sos)
+        if sos.numel() != K.N_EMBEDDING or not sos.is_floating_point():
+            raise ValueError("%s: the '<s>' vector must be %d floats (got %s %s)" % (where, K.N_EMBEDDING, sos.dtype, tuple(sos.shape)))
+    return sos, words
+
+
+def _state_dict_keys(path):
+    return list(torch.load(path, map_location='cpu', weights_only=False)['state_dict'].keys())
+
+
+def _unimodal_keys(keys):
+    return len(keys) > 0 and all(k.startswith(("encoder.", "decoder.")) for k in keys)
+
+
+def _kind_of(keys):
+    """"text" / "image" / "multimodal" from the keys of a ``state_dict``.  Text-only is asked BEFORE image-only, whose prefixes a
+    text-only checkpoint shares."""
+    return "text" if "encoder.gru.weight_ih_l0" in keys else "image" if _unimodal_keys(keys) else "multimodal"
+
+
+def is_imageonly_checkpoint(path):
+    """True for a checkpoint of ``train_imageonly`` (or the reference's train_imageonly.py): every key of its ``state_dict`` starts
+    with ``encoder.`` or ``decoder.``."""
+    return _unimodal_keys(_state_dict_keys(path))
+
+
+def is_textonly_checkpoint(path):
+    """True for a checkpoint of ``train_textonly`` (or the reference's train_textonly.py): its ``state_dict`` has the caption encoder's
+    ``encoder.gru.weight_ih_l0``.  Asked BEFORE ``is_imageonly_checkpoint``, whose prefixes a text-only checkpoint shares."""
+    return _kind_of(_state_dict_keys(path)) == "text"
+
+
+_LOADERS = {          # (dataset, kind of checkpoint) -> "module.function": the combinations that exist
+    ("mnist", "multimodal"): "mnist.load_checkpoint", ("mnist", "image"): "mnist.load_checkpoint_imageonly",
+    ("multimnist", "multimodal"): "train.load_checkpoint", ("multimnist", "image"): "multimnist.load_checkpoint_imageonly",
+    ("multimnist", "text"): "multimnist.load_checkpoint_textonly",
+    ("celeba", "multimodal"): "celeba.load_checkpoint", ("celeba", "image"): "celeba.load_checkpoint_imageonly",
+    ("coco", "multimodal"): "coco.load_checkpoint", ("coco", "image"): "coco.load_checkpoint_imageonly",
+    ("coco", "text"): "coco.load_checkpoint_textonly",
+}
+
+
+def _loader(dataset, kind):
+    if (dataset, kind) not in _LOADERS:
+        raise SystemExit("there is no %s model of the %s family: the checkpoint belongs to another --dataset or command" % (
+            {"multimodal": "multimodal", "image": "image-only", "text": "text-only"}[kind], dataset))
+    module, fn = _LOADERS[dataset, kind].split(".")
+    return getattr(importlib.import_module("." + module, __package__), fn)
+
+
+def _open_checkpoint(dataset, path, use_cuda=True, **kw):
+    """-> (model, kind) of a checkpoint of ``dataset``'s drivers, kind "multimodal" / "image" / "text": the file is read once to tell
+    (``_kind_of``), then by the ``load_checkpoint*`` of that kind.  ``kw``: COCO's ``sos`` / ``words`` (an image-only model has neither)."""
+    kind = _kind_of(_state_dict_keys(path))
+    return _loader(dataset, kind)(path, use_cuda=use_cuda, **({} if kind == "image" else kw)), kind
+
+
+def _which_posteriors(args, kind="multimodal"):
+    """--all / --image_only / --text_only (--attrs_only) -> the posteriors to report; a uni-modal checkpoint has its own alone."""
+    if kind != "multimodal":
+        return (kind,)
+    if args.all:
+        return POSTERIORS
+    second_only = getattr(args, "text_only", False) or getattr(args, "attrs_only", False)
+    return ("image",) if args.image_only else ("text",) if second_only else ("joint",)
+
+
+def _write_json(path, out):
+    import json
+    if path:
+        with open(path, 'w') as fp:
             json.dump(out, fp, indent=1)
+
+
+def _write_samples(out_dir, image=None, lines=None, text_file='sample_text.txt'):
+    """sample_image.pt (no torchvision here: the tensor, not a PNG grid) and one line of text per sample, whichever there is."""
+    import os
+    os.makedirs(out_dir, exist_ok=True)                           # (the reference calls the non-existent os.mkdirs, sample.py:133)
+    if image is not None:
+        torch.save(image, os.path.join(out_dir, 'sample_image.pt'))
+    if lines is not None:
+        with open(os.path.join(out_dir, text_file), 'w') as fp:
+            for line in lines:
+                fp.write('%s\n' % line)
+
+
+def _latent_mmd_main(args):
+    x, _, _ = _eval_data(args.dataset, args, "latent_mmd", parts="x")
+    x = x.float().div_(255.0)                                     # transforms.ToTensor()
+    if args.dataset == "mnist":
+        from .mnist import load_infovae_checkpoint, set_infovae_backend
+        x = x.unsqueeze(1)
+        vae = set_infovae_backend(load_infovae_checkpoint(args.model_path, use_cuda=True), args.conv_backend)
+    else:
+        from .train_infovae import load_checkpoint
+        vae = load_checkpoint(args.model_path, use_cuda=True)
+    out = latent_mmd(vae, _batches(x, None, args.batch_size), seed=args.seed)
+    _write_json(args.json, out)
     return out
 
 
 def _manifold_main(args):
     import os
-    from . import data as D
-    from .mnist import load_checkpoint
-    if args.synthetic > 0:
-        x, t = D.synthetic_mnist(args.synthetic, seed=args.seed)
-    elif args.data:
-        x, t = torch.load(args.data, weights_only=False)
-        x, t = torch.as_tensor(x), torch.as_tensor(t)
-    else:
-        raise SystemExit("manifold: give --data FILE.pt or --synthetic N")
-    if x.dtype != torch.uint8 or x.dim() != 3 or tuple(x.shape[1:]) != (28, 28) or t.shape != x.shape[:1]:
-        raise ValueError("manifold: need uint8 images (N,28,28) and N labels (got %s %s, %s)" % (x.dtype, tuple(x.shape), tuple(t.shape)))
+    x, t, _ = _eval_data("mnist", args, "manifold")
     x, t = x.float().div_(255.0).view(-1, 784), t.long()          # transforms.ToTensor() + view(-1, 784)
-    loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
-    if is_imageonly_checkpoint(args.model_path):                  # a checkpoint of train_imageonly --dataset mnist
-        from .mnist import load_checkpoint_imageonly as load_checkpoint
-    vae = load_checkpoint(args.model_path, use_cuda=True)
-    out = manifold(vae, loader, pca_only=args.pca_only, perplexity=args.perplexity, n_iter=args.n_iter, seed=args.seed)
+    vae, _ = _open_checkpoint("mnist", args.model_path)           # (a checkpoint of train_imageonly --dataset mnist: the encoder's mu)
+    out = manifold(vae, _batches(x, t, args.batch_size), pca_only=args.pca_only, perplexity=args.perplexity, n_iter=args.n_iter, seed=args.seed)
     os.makedirs(args.out, exist_ok=True)
     torch.save(out, os.path.join(args.out, 'manifold.pt'))
     if out["kl_trace"] is not None:
@@ -1160,10 +1198,9 @@ def _manifold_main(args):
 
 def _latent_viz_main(args):
     import os
-    from .mnist import load_checkpoint
-    if is_imageonly_checkpoint(args.model_path):
+    if _kind_of(_state_dict_keys(args.model_path)) == "image":
         raise SystemExit("latent_viz: an image-only checkpoint is not supported (the grid needs a padded-latent variant of mnist.VAE)")
-    vae = load_checkpoint(args.model_path, use_cuda=True)
+    vae = _loader("mnist", "multimodal")(args.model_path, use_cuda=True)
     canvas, digits = latent_viz(vae)
     os.makedirs(args.out, exist_ok=True)
     torch.save(canvas, os.path.join(args.out, 'latent_viz_image.pt'))
@@ -1173,7 +1210,6 @@ def _latent_viz_main(args):
 
 
 def _nll_pixelcnn_main(args):
-    import json
     from .pixelcnn import load_checkpoint
     from .train_pixelcnn import synthetic_images
     if args.head == 'hip' and not (args.cuda and torch.cuda.is_available()):
@@ -1198,54 +1234,45 @@ def _nll_pixelcnn_main(args):
     if use_cuda:
         model.cuda()
     out = nll_pixelcnn(model, x, args.batch_size, args.head)
-    if args.json:
-        with open(args.json, 'w') as fp:
-            json.dump(out, fp, indent=1)
+    _write_json(args.json, out)
     return out
 
 
 def _sample_pixelcnn_main(args):
-    import os
     from .pixelcnn import load_checkpoint
     model = load_checkpoint(args.model_path, use_cuda=True)
     complete = torch.load(args.complete, weights_only=False) if args.complete else None
     image = sample_pixelcnn(model, args.n_samples, args.height, args.width, complete, args.rows, args.seed)
-    os.makedirs(args.out, exist_ok=True)
-    torch.save(image.cpu(), os.path.join(args.out, 'sample_image.pt'))
+    _write_samples(args.out, image.cpu())
     return image
 
 
+def _condition_image(path, *shape):
+    """``--condition_on_image FILE.pt``: a uint8 or float image -> (1, *shape) float in [0,1]."""
+    im = torch.load(path)
+    return (im.float() / 255.0 if im.dtype == torch.uint8 else im.float()).view(1, *shape)
+
+
 def _sample_coco_main(args):
-    import os
     from . import coco as K, data as D
     dev = torch.device("cuda", torch.cuda.current_device())
     if args.synthetic_words > 0:
         words = K.WordTable(*D.synthetic_word_table(args.synthetic_words, seed=args.seed), device=dev)
     else:
         words = K.load_word_table(args.words, dev)
-    textonly = is_textonly_checkpoint(args.model_path)            # a checkpoint of train_textonly: captions only
-    if textonly and args.condition_on_image:
+    kind = _kind_of(_state_dict_keys(args.model_path))            # "text": a checkpoint of train_textonly, captions only
+    if kind == "text" and args.condition_on_image:
         raise SystemExit("sample_coco: a text-only checkpoint cannot be conditioned on an image")
-    vae = (K.load_checkpoint_textonly if textonly else K.load_checkpoint)(args.model_path, use_cuda=True, words=words)
-    image = text = None
-    if args.condition_on_image:
-        im = torch.load(args.condition_on_image)
-        image = (im.float() / 255.0 if im.dtype == torch.uint8 else im.float()).view(1, 3, 32, 32)
-    if args.condition_on_text:
-        text = words.embed(args.condition_on_text).unsqueeze(0)
+    vae = _loader("coco", "text" if kind == "text" else "multimodal")(args.model_path, use_cuda=True, words=words)
+    image = _condition_image(args.condition_on_image, 3, 32, 32) if args.condition_on_image else None
+    text = words.embed(args.condition_on_text).unsqueeze(0) if args.condition_on_text else None
     image_recon, captions = sample_coco(vae, args.n_samples, image, text, stop_at_eos=args.stop_at_eos, seed=args.seed)
-    os.makedirs(args.out, exist_ok=True)
-    if image_recon is not None:
-        torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))
-    with open(os.path.join(args.out, 'sample_text.txt'), 'w') as fp:
-        for c in captions:
-            fp.write('%s\n' % c)
+    _write_samples(args.out, image_recon, captions)
     return captions
 
 
 def _sample_celeba_main(args):
-    import os
-    from .celeba import attrs_from_names, load_checkpoint
+    from .celeba import attrs_from_names
     image = attrs = None
     if args.condition_on_attrs:
         attrs = attrs_from_names(args.condition_on_attrs)         # (refuses an unknown name before anything is loaded)
@@ -1253,20 +1280,15 @@ def _sample_celeba_main(args):
         if not args.data:
             raise SystemExit("sample_celeba: --condition_on_image ATTR needs --data FILE.pt to take the image from")
         image = fetch_celeba_image(args.data, args.condition_on_image, seed=args.seed)
-    vae = load_checkpoint(args.model_path, use_cuda=True)
+    vae = _loader("celeba", "multimodal")(args.model_path, use_cuda=True)
     image_recon, names = sample_celeba(vae, args.n_samples, image, attrs, seed=args.seed)
-    os.makedirs(args.out, exist_ok=True)
-    torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))      # no torchvision here: the tensor, not a PNG grid
-    with open(os.path.join(args.out, 'sample_attrs.txt'), 'w') as fp:
-        for row in names:
-            fp.write('%s\n' % ','.join(row))
+    _write_samples(args.out, image_recon, [','.join(row) for row in names], 'sample_attrs.txt')
     return image_recon, names
 
 
 def _report(vae, loader, posts, args, second, text_sigma=None):
     """Runs ``log_marginal`` per posterior, prints the reference's NLL line and the bounds, writes ``--json`` (``text_sigma``: the
     COCO command's, recorded in the file)."""
-    import json
     table = {}
     for post in posts:
         r = log_marginal(vae, loader, n_particles=args.n_samples, posterior=post, seed=args.seed,
@@ -1284,374 +1306,151 @@ def _report(vae, loader, posts, args, second, text_sigma=None):
         for post, r in table.items():
             out[post] = {k: r[k] for k in ("log_px", "log_py", "log_pxy", "image_nll", "text_nll")}
             out[post]["mean_ess"] = r["ess"].double().mean(0).tolist()
-        with open(args.json, 'w') as fp:
-            json.dump(out, fp, indent=1)
+        _write_json(args.json, out)
     return table
 
 
-def is_imageonly_checkpoint(path):
-    """True for a checkpoint of ``train_imageonly`` (or the reference's train_imageonly.py): every key of its ``state_dict`` starts
-    with ``encoder.`` or ``decoder.``."""
-    keys = list(torch.load(path, map_location='cpu', weights_only=False)['state_dict'].keys())
-    return len(keys) > 0 and all(k.startswith(("encoder.", "decoder.")) for k in keys)
-
-
-def is_textonly_checkpoint(path):
-    """True for a checkpoint of ``train_textonly`` (or the reference's train_textonly.py): its ``state_dict`` has the caption encoder's
-    ``encoder.gru.weight_ih_l0``.  Asked BEFORE ``is_imageonly_checkpoint``, whose prefixes a text-only checkpoint shares."""
-    return "encoder.gru.weight_ih_l0" in torch.load(path, map_location='cpu', weights_only=False)['state_dict']
-
-
 @torch.no_grad()
-def test_textonly(vae, loader, kl_lambda=1.0, verbose=True):
-    """The counterpart of ``test_imageonly`` for a ``TextVAE``: the mean over the batches of the eval-mode loss MSE + kl_lambda * KL / B
-    (``kl_lambda`` = 1), on the one-pass caption step.  ``loader`` yields (anything, captions (B, steps, 300)) whole batches of one size."""
-    from .coco import TextVAETrainer
-    from .multimnist import TextVAE as MultimnistTextVAE
-    mm = isinstance(vae, MultimnistTextVAE)       # (B, 4) int64 labels, lambda_y * NLL + kl_lambda * KL / B
-    if mm:
-        from .multimnist import TextVAETrainer
+def _test_unimodal(vae, batches, kl_lambda, verbose, where):
+    """The mean over the batches (whole batches of one size, already on the device) of the eval-mode loss of the kind's one-pass Trainer."""
+    trainer_class = _family(vae).trainer()
     vae.eval()
-    dev = next(vae.parameters()).device
     trainer, total, n = None, 0.0, 0
-    for _, text in loader:
-        text = text.to(dev).long().contiguous() if mm else text.to(dev).float().contiguous()
-        if trainer is None or trainer.engine.B != text.shape[0]:
-            trainer = TextVAETrainer(vae, text.shape[0], kl_lambda=kl_lambda)
-        total += float(trainer.evaluate(text).losses()[0].item())
+    for batch in batches:
+        if trainer is None or trainer.engine.B != batch.shape[0]:
+            trainer = trainer_class(vae, batch.shape[0], kl_lambda=kl_lambda)
+        total += float(trainer.evaluate(batch).losses()[0].item())
         n += 1
     if n == 0:
-        raise ValueError("test_textonly: empty loader")
+        raise ValueError("%s: empty loader" % where)
     total /= n
     if verbose:
         print('====> Test set loss: {:.4f}'.format(total))
     return total
+
+
+def test_textonly(vae, loader, kl_lambda=1.0, verbose=True):
+    """The counterpart of ``test_imageonly`` for a ``TextVAE``: the mean over the batches of the eval-mode loss MSE + kl_lambda * KL / B
+    (``kl_lambda`` = 1), on the one-pass caption step (a multimnist ``TextVAE``: (B, 4) int64 labels, lambda_y * NLL + kl_lambda * KL / B).
+    ``loader`` yields (anything, captions (B, steps, 300)) whole batches of one size."""
+    dev, dtype = next(vae.parameters()).device, torch.float32 if _family(vae).float_text else torch.int64
+    return _test_unimodal(vae, (text.to(dev, dtype).contiguous() for _, text in loader), kl_lambda, verbose, "test_textonly")
 
 
 test_textonly.__test__ = False            # not a pytest test
 
 
-@torch.no_grad()
 def test_imageonly(vae, loader, kl_lambda=1.0, verbose=True):
     """celeba/test_imageonly.py: the mean over the batches of the eval-mode loss BCE + kl_lambda * KL / B of an ``ImageVAE``
     (``kl_lambda`` = 1 there), on the one-pass step.  ``loader`` yields (image, anything) whole batches of one size."""
-    import importlib
-    vae.eval()
     dev = next(vae.parameters()).device
-    mod = importlib.import_module(type(vae).__module__)
-    trainer, total, n = None, 0.0, 0
-    for image, _ in loader:
-        image = image.to(dev).float().contiguous()
-        if trainer is None or trainer.engine.B != image.shape[0]:
-            trainer = mod.ImageVAETrainer(vae, image.shape[0], kl_lambda=kl_lambda)
-        total += float(trainer.evaluate(image).losses()[0].item())
-        n += 1
-    if n == 0:
-        raise ValueError("test_imageonly: empty loader")
-    total /= n
-    if verbose:
-        print('====> Test set loss: {:.4f}'.format(total))
-    return total
+    return _test_unimodal(vae, (image.to(dev).float().contiguous() for image, _ in loader), kl_lambda, verbose, "test_imageonly")
 
 
 test_imageonly.__test__ = False           # not a pytest test
 
 
-def load_celeba_eval_file(path):
-    """The ``--data`` file of ``loglik_celeba``: (uint8 images (N,3,64,64), attributes (N,18)) -> (uint8 images, float32
-    attributes).  Attributes other than 0 / 1 are refused here, on the host: the scorer indexes (log(1 - p), log p) with them."""
-    x, a = torch.load(path, weights_only=False)
-    x, a = torch.as_tensor(x), torch.as_tensor(a)
-    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 64, 64):
-        raise ValueError("%s: images must be uint8 (N,3,64,64) (got %s %s)" % (path, x.dtype, tuple(x.shape)))
-    if a.dim() != 2 or a.shape[0] != x.shape[0] or a.shape[1] != 18:
-        raise ValueError("%s: attributes must be (N,18) for the N = %d images (got %s)" % (path, x.shape[0], tuple(a.shape)))
-    a = a.float()
-    if not bool(((a == 0) | (a == 1)).all()):
-        raise ValueError("%s: every attribute must be 0 or 1" % path)
-    return x, a
+def _loglik(args, dataset, second="Text", hint="--data FILE.pt"):
+    """The body of `loglik`, `loglik_celeba` and `loglik_coco`: the data, then the checkpoint (multimodal: the posteriors the flags
+    name; a checkpoint of train_imageonly / train_textonly: log p(x) / log p(y) alone), then ``_report``.  The result keys (and the
+    JSON layout) are the same for all three; CelebA's ``log_py`` / ``text_nll`` are the attribute terms and its attribute-only
+    posterior is filed under "text"; COCO adds ``text_sigma``."""
+    kw, text_sigma = {}, None
+    if dataset == "coco":
+        from .coco import MAX_WORDS
+        text_sigma = float(args.text_sigma)
+        coco_text_constant(MAX_WORDS, text_sigma)                 # before anything is loaded
+    x, t, extras = _eval_data(dataset, args, args.cmd, hint)
+    if dataset == "coco":
+        kw["sos"], kw["words"] = _sos_words(args, extras.get("sos"), args.cmd)
+    loader = _batches(x.float().div_(255.0), t, args.batch_size)                 # transforms.ToTensor(); log_marginal shapes the batches
+    vae, kind = _open_checkpoint(dataset, args.model_path, **kw)
+    return _report(vae, loader, _which_posteriors(args, kind), args, second, text_sigma=text_sigma)
+
+
+def _loglik_main(args):
+    return _loglik(args, args.dataset)
 
 
 def _loglik_celeba_main(args):
-    """`loglik_celeba`: the result keys (and the JSON layout) are those of `loglik`; ``log_py`` / ``text_nll`` are the attribute
-    terms and the attribute-only posterior is filed under "text"."""
-    from . import data as D
-    from .celeba import load_checkpoint
-    if args.synthetic > 0:
-        x, a = D.synthetic_celeba(args.synthetic, seed=args.seed)
-    elif args.data:
-        x, a = load_celeba_eval_file(args.data)
-    else:
-        raise SystemExit("loglik_celeba: give --data FILE.pt or --synthetic N")
-    x = x.float().div_(255.0)                                     # transforms.ToTensor()
-    loader = [(x[i:i + args.batch_size], a[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
-    if is_imageonly_checkpoint(args.model_path):                  # a checkpoint of train_imageonly: log p(x) alone
-        from .celeba import load_checkpoint_imageonly
-        return _report(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Attrs")
-    vae = load_checkpoint(args.model_path, use_cuda=True)
-    posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.attrs_only else ("joint",)
-    return _report(vae, loader, posts, args, "Attrs")
-
-
-def check_coco_eval_data(images, captions, text_sigma=1.0, where="loglik_coco"):
-    """The host-side refusals of ``loglik_coco``: images must be uint8 (N,3,32,32), captions float (N,102,300) for the same N >= 1,
-    sigma > 0.  -> (uint8 images, float32 captions)."""
-    from .coco import MAX_WORDS, N_EMBEDDING
-    coco_text_constant(MAX_WORDS, text_sigma)                     # refuses sigma <= 0 / non-finite
-    x, t = torch.as_tensor(images), torch.as_tensor(captions)
-    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 32, 32) or x.shape[0] < 1:
-        raise ValueError("%s: images must be uint8 (N,3,32,32) with N >= 1 (got %s %s)" % (where, x.dtype, tuple(x.shape)))
-    if not t.is_floating_point() or t.dim() != 3 or tuple(t.shape) != (x.shape[0], MAX_WORDS, N_EMBEDDING):
-        raise ValueError("%s: captions must be float (N,%d,%d) for the N = %d images (got %s %s)"
-                         % (where, MAX_WORDS, N_EMBEDDING, x.shape[0], t.dtype, tuple(t.shape)))
-    return x, t.float()
+    return _loglik(args, "celeba", "Attrs")
 
 
 def _loglik_coco_main(args):
-    """`loglik_coco`: the result keys (and the JSON layout) are those of `loglik`, plus ``text_sigma``."""
-    import os
-    from . import coco as K
-    from .train_coco import synthetic_coco
-    coco_text_constant(K.MAX_WORDS, args.text_sigma)              # before anything is loaded
-    sos = words = None
-    if args.synthetic > 0:
-        x, t, sos = synthetic_coco(args.synthetic, seed=args.seed)
-    elif args.data:
-        x = torch.load(os.path.join(args.data, "images_u8.pt"), weights_only=False)
-        t = torch.load(os.path.join(args.data, "captions.pt"), weights_only=False)
-        if not args.sos and not args.words:
-            sos = torch.load(os.path.join(args.data, "sos.pt"), weights_only=False)
-    else:
-        raise SystemExit("loglik_coco: give --data DIR or --synthetic N")
-    x, t = check_coco_eval_data(x, t, args.text_sigma)
-    if args.sos:
-        sos = torch.load(args.sos, weights_only=False)
-    elif args.words:
-        sos, words = None, K.load_word_table(args.words)
-    if sos is not None:
-        sos = torch.as_tensor(sos)
-        if sos.numel() != K.N_EMBEDDING or not sos.is_floating_point():
-            raise ValueError("loglik_coco: the '<s>' vector must be %d floats (got %s %s)" % (K.N_EMBEDDING, sos.dtype, tuple(sos.shape)))
-    x = x.float().div_(255.0)                                     # transforms.ToTensor()
-    loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
-    if is_textonly_checkpoint(args.model_path):                   # a checkpoint of train_textonly: log p(y) alone
-        return _report(K.load_checkpoint_textonly(args.model_path, use_cuda=True, sos=sos, words=words), loader, ("text",), args, "Text",
-                       text_sigma=float(args.text_sigma))
-    if is_imageonly_checkpoint(args.model_path):                  # a checkpoint of train_imageonly: log p(x) alone
-        return _report(K.load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Text",
-                       text_sigma=float(args.text_sigma))
-    vae = K.load_checkpoint(args.model_path, use_cuda=True, sos=sos, words=words)
-    posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
-    return _report(vae, loader, posts, args, "Text", text_sigma=float(args.text_sigma))
+    return _loglik(args, "coco", hint="--data DIR")
 
 
 def _test_imageonly_main(args):
     """`test_imageonly`: whole batches only (the plan takes a fixed batch size); a trailing partial batch is dropped."""
-    import os
-    from . import data as D
-    kl_lambda = 1.0
-    if args.dataset == "mnist":
-        from .mnist import load_checkpoint_imageonly
-        from .make_multimnist import load_mnist_pt
-        if args.synthetic > 0:
-            x, _ = D.synthetic_mnist(args.synthetic, seed=args.seed)
-        elif args.data:
-            x, _ = load_mnist_pt(args.data)
-        else:
-            raise SystemExit("test_imageonly: give --data or --synthetic N")
-        x = x.view(-1, 1, 28, 28)
-        kl_lambda = 1.0 / 784                                     # the reference's own loss: (BCE + KLD / 784) / B
-    elif args.dataset == "multimnist":
-        from .multimnist import load_checkpoint_imageonly
-        if args.synthetic > 0:
-            x, _ = D.synthetic_multimnist(args.synthetic, seed=args.seed)
-        elif args.data:
-            x, _ = D.load_multimnist(args.data, train=False)
-        else:
-            raise SystemExit("test_imageonly: give --data or --synthetic N")
-        x = x.view(-1, 1, 50, 50)
-    elif args.dataset == "celeba":
-        from .celeba import load_checkpoint_imageonly
-        if args.synthetic > 0:
-            x, _ = D.synthetic_celeba(args.synthetic, seed=args.seed)
-        elif args.data:
-            x, _ = load_celeba_eval_file(args.data)
-        else:
-            raise SystemExit("test_imageonly: give --data or --synthetic N")
-    else:
-        from .coco import load_checkpoint_imageonly
-        from .train_coco import synthetic_coco
-        if args.synthetic > 0:
-            x, _, _ = synthetic_coco(args.synthetic, seed=args.seed)
-        elif args.data:
-            x = torch.as_tensor(torch.load(os.path.join(args.data, "images_u8.pt"), weights_only=False))
-        else:
-            raise SystemExit("test_imageonly: give --data or --synthetic N")
-    bs = min(args.batch_size, x.shape[0])
-    x = x.float().div_(255.0)
-    loader = [(x[i:i + bs], None) for i in range(0, x.shape[0] - bs + 1, bs)]
-    return test_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, kl_lambda=kl_lambda)
+    x, _, _ = _eval_data(args.dataset, args, "test_imageonly", "--data", parts="x")
+    x = x.float().div_(255.0).view(-1, *_FAMILIES[args.dataset + "_image"].picture)
+    kl_lambda = 1.0 / 784 if args.dataset == "mnist" else 1.0     # mnist: the reference's own loss, (BCE + KLD / 784) / B
+    vae = _loader(args.dataset, "image")(args.model_path, use_cuda=True)
+    return test_imageonly(vae, _batches(x, None, args.batch_size, whole_only=True), kl_lambda=kl_lambda)
 
 
 def _test_textonly_main(args):
     """`test_textonly`: whole batches only (the plan takes a fixed batch size); a trailing partial batch is dropped."""
-    import os
-    if args.dataset == "multimnist":
-        from . import data as D
-        from .multimnist import load_checkpoint_textonly
-        from .utils import charlist_tensor
-        if args.synthetic > 0:
-            _, labels = D.synthetic_multimnist(args.synthetic, seed=args.seed)
-            t = torch.stack([charlist_tensor(l) for l in labels])
-        elif args.data:
-            _, t = D.load_multimnist(args.data, train=False)
-        else:
-            raise SystemExit("test_textonly: give --data or --synthetic N")
-        bs = min(args.batch_size, t.shape[0])
-        loader = [(None, t[i:i + bs]) for i in range(0, t.shape[0] - bs + 1, bs)]
-        return test_textonly(load_checkpoint_textonly(args.model_path, use_cuda=True), loader)
-    from . import coco as K
-    from .train_coco import synthetic_coco
-    sos = words = None
-    if args.synthetic > 0:
-        _, t, sos = synthetic_coco(args.synthetic, seed=args.seed)
-    elif args.data:
-        t = torch.as_tensor(torch.load(os.path.join(args.data, "captions.pt"), weights_only=False)).float()
-        if not args.sos and not args.words:
-            sos = torch.load(os.path.join(args.data, "sos.pt"), weights_only=False)
-    else:
-        raise SystemExit("test_textonly: give --data or --synthetic N")
-    if args.sos:
-        sos = torch.load(args.sos, weights_only=False)
-    elif args.words:
-        sos, words = None, K.load_word_table(args.words)
-    bs = min(args.batch_size, t.shape[0])
-    loader = [(None, t[i:i + bs]) for i in range(0, t.shape[0] - bs + 1, bs)]
-    return test_textonly(K.load_checkpoint_textonly(args.model_path, use_cuda=True, sos=sos, words=words), loader)
-
-
-def _loglik_main(args):
-    from . import data as D
-    from .utils import charlist_tensor
-    if args.dataset == "mnist":
-        from .mnist import load_checkpoint
-        if args.synthetic > 0:
-            x, t = D.synthetic_mnist(args.synthetic, seed=args.seed)
-        else:
-            x, t = torch.load(args.data, weights_only=False)      # torchvision's processed/test.pt
-        x = torch.as_tensor(x).float().div_(255.0).view(-1, 784)  # transforms.ToTensor() + view(-1, 784)
-        t = torch.as_tensor(t).long()
-    else:
-        from .train import load_checkpoint
-        if args.synthetic > 0:
-            x, labels = D.synthetic_multimnist(args.synthetic, seed=args.seed)
-            t = torch.stack([charlist_tensor(l) for l in labels])
-        else:
-            x, t = D.load_multimnist(args.data, train=False)
-        x = x.float().div_(255.0).view(-1, 1, 50, 50)             # transforms.ToTensor()
-    loader = [(x[i:i + args.batch_size], t[i:i + args.batch_size]) for i in range(0, x.shape[0], args.batch_size)]
-    if args.dataset == "multimnist" and is_textonly_checkpoint(args.model_path):      # a checkpoint of train_textonly_multimnist: log p(y) alone
-        from .multimnist import load_checkpoint_textonly
-        return _report(load_checkpoint_textonly(args.model_path, use_cuda=True), loader, ("text",), args, "Text")
-    if args.dataset == "mnist" and is_imageonly_checkpoint(args.model_path):          # a checkpoint of train_imageonly --dataset mnist
-        from .mnist import load_checkpoint_imageonly
-        return _report(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Text")
-    if args.dataset == "multimnist" and is_imageonly_checkpoint(args.model_path):     # a checkpoint of train_imageonly: log p(x) alone
-        from .multimnist import load_checkpoint_imageonly
-        return _report(load_checkpoint_imageonly(args.model_path, use_cuda=True), loader, ("image",), args, "Text")
-    vae = load_checkpoint(args.model_path, use_cuda=True)
-    posts = POSTERIORS if args.all else ("image",) if args.image_only else ("text",) if args.text_only else ("joint",)
-    return _report(vae, loader, posts, args, "Text")
+    _, t, extras = _eval_data(args.dataset, args, "test_textonly", "--data", parts="t")
+    kw = dict(zip(("sos", "words"), _sos_words(args, extras.get("sos"), "test_textonly"))) if args.dataset == "coco" else {}
+    vae = _loader(args.dataset, "text")(args.model_path, use_cuda=True, **kw)
+    return test_textonly(vae, _batches(None, t, args.batch_size, whole_only=True))
 
 
 def _sample_mnist_main(args):
     """`sample --dataset mnist` (mnist/imageonly/sample_imageonly.py): 64 images from the prior, or from q(z|x) of a test image of the
     digit ``--condition_on_image LABEL`` chosen from ``--data``.  Writes sample_image.pt (n,1,28,28)."""
-    import os
-    from .mnist import load_checkpoint_imageonly
-    if not is_imageonly_checkpoint(args.model_path):
+    if _kind_of(_state_dict_keys(args.model_path)) != "image":
         raise SystemExit("sample --dataset mnist: an image-only checkpoint (train_imageonly --dataset mnist) expected")
     image = None
     if args.condition_on_image is not None:
-        from .make_multimnist import load_mnist_pt
         label = int(args.condition_on_image)
         if not args.data:
             raise SystemExit("sample --dataset mnist: --condition_on_image LABEL needs --data FILE.pt")
-        x, t = load_mnist_pt(args.data)
+        x, t, _ = _eval_data("mnist", args, "sample --dataset mnist")
         idx = (t == label).nonzero().flatten()
         if idx.numel() == 0:
             raise SystemExit("sample --dataset mnist: --data has no image of the digit %d" % label)
         pick = idx[int(torch.randint(0, idx.numel(), (1,), generator=torch.Generator().manual_seed(args.seed)))]
         image = x[pick].float().div(255.0).view(1, 784)
-    image_recon = sample_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), args.n_samples, image)
-    os.makedirs(args.out, exist_ok=True)
-    torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))
+    image_recon = sample_imageonly(_loader("mnist", "image")(args.model_path, use_cuda=True), args.n_samples, image)
+    _write_samples(args.out, image_recon)
     return image_recon
 
 
-def _main(argv=None):
-    import os
-    from .train import load_checkpoint
+def _sample_main(args):
+    """`sample`: a multimodal checkpoint of MultiMNIST, or one of train_imageonly --dataset multimnist (image samples only) or of
+    train_textonly_multimnist (text samples only); `--dataset mnist`: ``_sample_mnist_main``."""
     from .utils import char_tensor, tensor_to_string
-    args = _parser().parse_args(argv)
-    if args.cmd == "loglik":
-        return _loglik_main(args)
-    if args.cmd == "loglik_celeba":
-        return _loglik_celeba_main(args)
-    if args.cmd == "loglik_coco":
-        return _loglik_coco_main(args)
-    if args.cmd == "test_imageonly":
-        return _test_imageonly_main(args)
-    if args.cmd == "test_textonly":
-        return _test_textonly_main(args)
-    if args.cmd == "sample_coco":
-        return _sample_coco_main(args)
-    if args.cmd == "sample_celeba":
-        return _sample_celeba_main(args)
-    if args.cmd == "latent_mmd":
-        return _latent_mmd_main(args)
-    if args.cmd == "manifold":
-        return _manifold_main(args)
-    if args.cmd == "latent_viz":
-        return _latent_viz_main(args)
-    if args.cmd == "sample_pixelcnn":
-        return _sample_pixelcnn_main(args)
-    if args.cmd == "nll_pixelcnn":
-        return _nll_pixelcnn_main(args)
     if args.dataset == "mnist":
         return _sample_mnist_main(args)
-    if is_textonly_checkpoint(args.model_path):       # a checkpoint of train_textonly_multimnist: text samples only
-        from .multimnist import load_checkpoint_textonly
-        vae = load_checkpoint_textonly(args.model_path, use_cuda=True)
-        if args.condition_on_image:
-            raise SystemExit("sample: a text-only checkpoint has no image encoder")
-        text_recon = sample_textonly(vae, args.n_samples, None if not args.condition_on_text else char_tensor(args.condition_on_text).unsqueeze(0))
-        os.makedirs(args.out, exist_ok=True)
-        with open(os.path.join(args.out, 'sample_text.txt'), 'w') as fp:
-            for i in range(text_recon.size(0)):
-                fp.write('%s\n' % tensor_to_string(text_recon[i]))
-        return None
-    image = text = None
-    if args.condition_on_image:
-        im = torch.load(args.condition_on_image)
-        image = (im.float() / 255.0 if im.dtype == torch.uint8 else im.float()).view(1, 1, 50, 50)
-    if is_imageonly_checkpoint(args.model_path):      # a checkpoint of train_imageonly --dataset multimnist: image samples only
-        from .multimnist import load_checkpoint_imageonly
-        if args.condition_on_text:
-            raise SystemExit("sample: an image-only checkpoint has no text encoder")
-        image_recon = sample_imageonly(load_checkpoint_imageonly(args.model_path, use_cuda=True), args.n_samples, image)
-        os.makedirs(args.out, exist_ok=True)
-        torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))
-        return None
-    vae = load_checkpoint(args.model_path, use_cuda=True)
-    if args.condition_on_text:
-        text = char_tensor(args.condition_on_text).unsqueeze(0)
-    image_recon, text_recon = sample(vae, args.n_samples, image, text)
-    os.makedirs(args.out, exist_ok=True)                          # (the reference calls the non-existent os.mkdirs, sample.py:133)
-    torch.save(image_recon, os.path.join(args.out, 'sample_image.pt'))      # no torchvision here: the tensor, not a PNG grid
-    with open(os.path.join(args.out, 'sample_text.txt'), 'w') as fp:
-        for i in range(text_recon.size(0)):
-            fp.write('%s\n' % tensor_to_string(text_recon[i]))
+    vae, kind = _open_checkpoint("multimnist", args.model_path)
+    if kind == "text" and args.condition_on_image:
+        raise SystemExit("sample: a text-only checkpoint has no image encoder")
+    if kind == "image" and args.condition_on_text:
+        raise SystemExit("sample: an image-only checkpoint has no text encoder")
+    image = _condition_image(args.condition_on_image, 1, 50, 50) if args.condition_on_image else None
+    text = char_tensor(args.condition_on_text).unsqueeze(0) if args.condition_on_text else None
+    if kind == "text":
+        image_recon, text_recon = None, sample_textonly(vae, args.n_samples, text)
+    elif kind == "image":
+        image_recon, text_recon = sample_imageonly(vae, args.n_samples, image), None
+    else:
+        image_recon, text_recon = sample(vae, args.n_samples, image, text)
+    _write_samples(args.out, image_recon, None if text_recon is None else [tensor_to_string(row) for row in text_recon])
+
+
+_COMMANDS = {
+    "sample": _sample_main, "loglik": _loglik_main, "loglik_celeba": _loglik_celeba_main, "loglik_coco": _loglik_coco_main,
+    "test_imageonly": _test_imageonly_main, "test_textonly": _test_textonly_main, "sample_coco": _sample_coco_main,
+    "sample_celeba": _sample_celeba_main, "sample_pixelcnn": _sample_pixelcnn_main, "nll_pixelcnn": _nll_pixelcnn_main,
+    "latent_mmd": _latent_mmd_main, "manifold": _manifold_main, "latent_viz": _latent_viz_main,
+}
+
+
+def _main(argv=None):
+    args = _parser().parse_args(argv)
+    return _COMMANDS[args.cmd](args)
 
 
 main = _main
