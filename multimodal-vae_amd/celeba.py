@@ -6,19 +6,17 @@ libmmvae_hip.so.  No CPU fallback.  ``FusedTrainer`` = the train() closure body 
 """
 from __future__ import annotations
 
-import weakref
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from ._lib import MMVAEError, call, ptr
+from ._lib import MMVAEError  # noqa: F401
 from .core import CelebaState, FusedCelebaStep, FusedImageStep, Trainer, load_vae_checkpoint
-from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
-                         _seed_from_torch, _stream, swish)
+from .modules import DECODER, Draw, ExpertsVAEBase, ProductOfExperts, Swish, VAEBase, _BCEMeanFn, _Core, _dropout_on, _KLSumFn, run_module
+from .modules import DROP_P, swish  # noqa: F401  (public names of this module, like MMVAEError)
 
 N_ATTRS = 18          # celeba/datasets.py:26-28
-DROP_P = 0.1
 
 # the 40 columns of CelebA's Anno/list_attr_celeba.txt, in the file's order
 ATTR_NAMES = ('5_o_Clock_Shadow Arched_Eyebrows Attractive Bags_Under_Eyes Bald Bangs Big_Lips Big_Nose Black_Hair Blond_Hair Blurry '
@@ -59,15 +57,6 @@ def attrs_from_names(names):
     return attrs
 
 
-def _prep(mod: nn.Module, prefix: str, x: torch.Tensor):
-    core = _core_of(mod, prefix, CelebaState)
-    st = core.sync(x.device)
-    B = x.shape[0]
-    names = [prefix + k for k, _ in mod.named_parameters()]
-    plist = [p for _, p in mod.named_parameters()]
-    return core, st, B, st.plan(B), st.module_workspace_bytes(B), names, plist
-
-
 class ImageEncoder(nn.Module):
     """celeba/model.py:91-128"""
 
@@ -91,32 +80,11 @@ class ImageEncoder(nn.Module):
         n = self.n_latents
         x = x.contiguous().float()
         assert x.shape[1:] == (3, 64, 64), "expected (B,3,64,64) images"
-        core, st, B, h, wsb, names, plist = _prep(self, "image_encoder.", x)
-        p = self.classifier[2].p
         m1 = None
-        if self.training and p > 0:
-            if abs(p - DROP_P) > 1e-9:
-                raise MMVAEError("the HIP image encoder supports Dropout p in {0, 0.1} (reference: 0.1)")
-            if mask is not None:
-                m1 = mask.to(torch.uint8).contiguous()
-            else:
-                m1 = torch.empty(B, 1024, dtype=torch.uint8, device=x.device)
-                call("mmvae_keep_mask", ptr(m1), m1.numel(), DROP_P, _seed_from_torch(), None, 2, _stream())
-        training = int(self.training)
-
-        def fwd(ctx):
-            ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-            out = torch.empty(B, 2 * n, dtype=torch.float32, device=x.device)
-            call("mmvae_celeba_image_encoder_fwd", h, ptr(ws), wsb, ptr(x), ptr(m1), training, ptr(out), _stream())
-            ctx.ws = ws
-            return out
-
-        def bwd(ctx, d_out):
-            st.grads.zero_()
-            call("mmvae_celeba_image_encoder_bwd", h, ptr(ctx.ws), wsb, ptr(d_out.contiguous()), ptr(m1), _stream())
-            return [None] + core.grads_for(names)
-
-        out = _ModuleFn.apply(fwd, bwd, 1, x, *plist)
+        if _dropout_on(self, (self.classifier[2].p,), "the HIP image encoder supports Dropout p in {0, 0.1} (reference: 0.1)"):
+            m1 = Draw((x.shape[0], 1024), 2) if mask is None else mask.to(torch.uint8).contiguous()
+        out = run_module(self, "image_encoder.", CelebaState, x, "mmvae_celeba_image_encoder", (2 * n,),
+                         ("x", m1, "training", "out"), ("d", m1))
         return out[:, :n], out[:, n:]
 
 
@@ -139,25 +107,8 @@ class ImageDecoder(nn.Module):
             normal_init(self._modules[m], mean, std)
 
     def forward(self, z):
-        z = z.contiguous().float()
-        core, st, B, h, wsb, names, plist = _prep(self, "image_decoder.", z)
-        training = int(self.training)
-        n = self.n_latents
-
-        def fwd(ctx):
-            ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
-            recon = torch.empty(B, 3, 64, 64, dtype=torch.float32, device=z.device)
-            call("mmvae_celeba_image_decoder_fwd", h, ptr(ws), wsb, ptr(z), training, ptr(recon), _stream())
-            ctx.ws, ctx.recon = ws, recon
-            return recon
-
-        def bwd(ctx, d_recon):
-            st.grads.zero_()
-            dz = torch.empty(B, n, dtype=torch.float32, device=z.device)
-            call("mmvae_celeba_image_decoder_bwd", h, ptr(ctx.ws), wsb, ptr(d_recon.contiguous()), ptr(ctx.recon), ptr(dz), _stream())
-            return [dz] + core.grads_for(names)
-
-        return _ModuleFn.apply(fwd, bwd, 1, z, *plist)
+        return run_module(self, "image_decoder.", CelebaState, z.contiguous().float(), "mmvae_celeba_image_decoder", (3, 64, 64),
+                          *DECODER)
 
 
 class AttributeEncoder(nn.Module):
@@ -173,24 +124,8 @@ class AttributeEncoder(nn.Module):
         n = self.n_latents
         x = x.contiguous().float()
         assert x.dim() == 2 and x.shape[1] == N_ATTRS
-        core, st, B, h, wsb, names, plist = _prep(self, "attrs_encoder.", x)
-        if self.training and B <= 1:
-            raise ValueError("Expected more than 1 value per channel when training")
-        training = int(self.training)
-
-        def fwd(ctx):
-            ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-            out = torch.empty(B, 2 * n, dtype=torch.float32, device=x.device)
-            call("mmvae_celeba_attrs_encoder_fwd", h, ptr(ws), wsb, ptr(x), training, ptr(out), _stream())
-            ctx.ws = ws
-            return out
-
-        def bwd(ctx, d_out):
-            st.grads.zero_()
-            call("mmvae_celeba_attrs_encoder_bwd", h, ptr(ctx.ws), wsb, ptr(d_out.contiguous()), _stream())
-            return [None] + core.grads_for(names)
-
-        out = _ModuleFn.apply(fwd, bwd, 1, x, *plist)
+        out = run_module(self, "attrs_encoder.", CelebaState, x, "mmvae_celeba_attrs_encoder", (2 * n,),
+                         ("x", "training", "out"), ("d",), bn_values=1)
         return out[:, :n], out[:, n:]
 
 
@@ -204,27 +139,8 @@ class AttributeDecoder(nn.Module):
         self._core = None
 
     def forward(self, z):
-        z = z.contiguous().float()
-        core, st, B, h, wsb, names, plist = _prep(self, "attrs_decoder.", z)
-        if self.training and B <= 1:
-            raise ValueError("Expected more than 1 value per channel when training")
-        training = int(self.training)
-        n = self.n_latents
-
-        def fwd(ctx):
-            ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
-            recon = torch.empty(B, N_ATTRS, dtype=torch.float32, device=z.device)
-            call("mmvae_celeba_attrs_decoder_fwd", h, ptr(ws), wsb, ptr(z), training, ptr(recon), _stream())
-            ctx.ws, ctx.recon = ws, recon
-            return recon
-
-        def bwd(ctx, d_recon):
-            st.grads.zero_()
-            dz = torch.empty(B, n, dtype=torch.float32, device=z.device)
-            call("mmvae_celeba_attrs_decoder_bwd", h, ptr(ctx.ws), wsb, ptr(d_recon.contiguous()), ptr(ctx.recon), ptr(dz), _stream())
-            return [dz] + core.grads_for(names)
-
-        return _ModuleFn.apply(fwd, bwd, 1, z, *plist)
+        return run_module(self, "attrs_decoder.", CelebaState, z.contiguous().float(), "mmvae_celeba_attrs_decoder", (N_ATTRS,),
+                          *DECODER, bn_values=1)
 
 
 def normal_init(m, mean, std):
@@ -234,7 +150,7 @@ def normal_init(m, mean, std):
         m.bias.data.zero_()
 
 
-class MultimodalVAE(nn.Module):
+class MultimodalVAE(ExpertsVAEBase):
     """celeba/model.py:14-57"""
 
     def __init__(self, n_latents=20, use_cuda=False):
@@ -246,35 +162,16 @@ class MultimodalVAE(nn.Module):
         self.experts = ProductOfExperts()
         self.n_latents = n_latents
         self._core = _Core(self, "", n_latents, CelebaState)
-        for m in (self.image_encoder, self.image_decoder, self.attrs_encoder, self.attrs_decoder):
-            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+        self._adopt(self.image_encoder, self.image_decoder, self.attrs_encoder, self.attrs_decoder)
 
     def weight_init(self, mean, std):
         self.image_encoder.weight_init(mean=mean, std=std)
         self.image_decoder.weight_init(mean=mean, std=std)
 
-    def reparametrize(self, mu, logvar, eps: Optional[torch.Tensor] = None):
-        if self.training:
-            if eps is None:
-                eps = torch.empty_like(mu)
-                call("mmvae_normal", ptr(eps), eps.numel(), _seed_from_torch(), None, 1, _stream())
-            return _ReparamFn.apply(mu, logvar, eps.contiguous())
-        return mu
-
     def forward(self, image=None, attrs=None, eps=None, enc_mask=None):
         assert image is not None or attrs is not None
-        if image is not None and attrs is not None:
-            image_mu, image_logvar = self.image_encoder(image, enc_mask)
-            attrs_mu, attrs_logvar = self.attrs_encoder(attrs)
-            mu = torch.stack((image_mu, attrs_mu), dim=0)
-            logvar = torch.stack((image_logvar, attrs_logvar), dim=0)
-        elif image is not None:
-            mu, logvar = self.image_encoder(image, enc_mask)
-            mu, logvar = mu.unsqueeze(0), logvar.unsqueeze(0)
-        else:
-            mu, logvar = self.attrs_encoder(attrs)
-            mu, logvar = mu.unsqueeze(0), logvar.unsqueeze(0)
-        mu, logvar = self.experts(mu, logvar)
+        mu, logvar = self._product(None if image is None else self.image_encoder(image, enc_mask),
+                                   None if attrs is None else self.attrs_encoder(attrs))
         z = self.reparametrize(mu, logvar, eps)
         return self.image_decoder(z), self.attrs_decoder(z), mu, logvar
 
@@ -311,7 +208,7 @@ class FusedTrainer(Trainer):
 # ----------------------------------------------------------------------------------------------------------------
 # the uni-modal image baseline (celeba/model.py:60-88, celeba/train_imageonly.py)
 # ----------------------------------------------------------------------------------------------------------------
-class ImageVAE(nn.Module):
+class ImageVAE(VAEBase):
     """celeba/model.py:60-88: ``ImageEncoder`` + ``reparametrize`` + ``ImageDecoder`` under the reference's ``encoder.`` /
     ``decoder.`` keys, with NO product of experts.  The two children live on the MultimodalVAE's plan (``encoder.features.0.weight``
     is its ``image_encoder.features.0.weight``); the attribute half of the flat buffers keeps its initial value and never shows
@@ -323,8 +220,7 @@ class ImageVAE(nn.Module):
         self.decoder = ImageDecoder(n_latents)
         self.n_latents = n_latents
         self._core = _Core(self, "image_", n_latents, CelebaState)
-        for m in (self.encoder, self.decoder):
-            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+        self._adopt(self.encoder, self.decoder)
 
     def encode(self, x, mask: Optional[torch.Tensor] = None):
         return self.encoder(x, mask)
@@ -332,8 +228,6 @@ class ImageVAE(nn.Module):
     def weight_init(self, mean, std):
         self.encoder.weight_init(mean=mean, std=std)
         self.decoder.weight_init(mean=mean, std=std)
-
-    reparametrize = MultimodalVAE.reparametrize
 
     def decode(self, z):
         return self.decoder(z)

@@ -23,23 +23,22 @@ the MMD term on the fused op of ``mmd.py``; ``compute_mmd`` / ``compute_kernel``
 """
 from __future__ import annotations
 
-import weakref
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
-from ._ops import geometry
+from ._ops import geometry, stream as _stream
 from .core import CocoState, FusedCocoStep, FusedImageStep, FusedTextStep, Trainer, load_vae_checkpoint
 from .mmd import compute_kernel, compute_mmd, mmd_terms  # noqa: F401  (coco/model.py:385-402)
-from .multimnist import (ProductOfExperts, Swish, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _ReparamFn, _core_of,
-                         _gscale, _seed_from_torch, _stream, swish)
+from .modules import (DECODER, Draw, ExpertsVAEBase, ProductOfExperts, Swish, VAEBase, _BCEMeanFn, _Core, _dropout_on, _KLSumFn, _MSEMeanFn,
+                      _seed_from_torch, run_module)
+from .modules import DROP_P, swish  # noqa: F401  (public names of this module)
 
 MAX_WORDS = 102       # coco/utils.py:12-15
 N_EMBEDDING = 300
 N_HIDDENS = 200
-DROP_P = 0.1
 SOS, EOS = '<s>', '</s>'   # coco/utils.py:13-14
 MAX_DISTS = 8              # queries of one mmvae_nn_words_dists call
 
@@ -173,20 +172,9 @@ def load_word_table(path: str, device=None) -> WordTable:
     return WordTable(vectors, itos, device)
 
 
-def _prep(mod: nn.Module, prefix: str, x: torch.Tensor):
-    steps = mod.steps
-    core = _core_of(mod, prefix, lambda n, d: CocoState(n, d, steps))
-    st = core.sync(x.device)
-    B = x.shape[0]
-    names = [prefix + k for k, _ in mod.named_parameters()]
-    plist = [p for _, p in mod.named_parameters()]
-    return core, st, B, st.plan(B), st.module_workspace_bytes(B), names, plist
-
-
-def _keep(shape, device, salt):
-    m = torch.empty(*shape, dtype=torch.uint8, device=device)
-    call("mmvae_keep_mask", ptr(m), m.numel(), DROP_P, _seed_from_torch(), None, salt, _stream())
-    return m
+def _plan(steps):
+    """the plan a stand-alone module builds: the family's, at the module's caption length"""
+    return lambda n, d: CocoState(n, d, steps)
 
 
 class ImageEncoder(nn.Module):
@@ -209,31 +197,15 @@ class ImageEncoder(nn.Module):
         n = self.n_latents
         x = x.contiguous().float()
         assert x.shape[1:] == (3, 32, 32), "expected (B,3,32,32) images (coco/train.py:107-112)"
-        core, st, B, h, wsb, names, plist = _prep(self, "image_encoder.", x)
-        p1, p2 = self.classifier[2].p, self.classifier[5].p
         m1 = m2 = None
-        if self.training and (p1 > 0 or p2 > 0):
-            if abs(p1 - DROP_P) > 1e-9 or abs(p2 - DROP_P) > 1e-9:
-                raise MMVAEError("the HIP image encoder supports Dropout p in {0, 0.1} on both layers (reference: 0.1)")
+        if _dropout_on(self, (self.classifier[2].p, self.classifier[5].p),
+                       "the HIP image encoder supports Dropout p in {0, 0.1} on both layers (reference: 0.1)"):
             if masks is not None:
                 m1, m2 = (m.to(torch.uint8).contiguous() for m in masks)
-            else:
-                m1, m2 = _keep((B, 1024), x.device, 2), _keep((B, 256), x.device, 3)
-        training = int(self.training)
-
-        def fwd(ctx):
-            ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-            out = torch.empty(B, 2 * n, dtype=torch.float32, device=x.device)
-            call("mmvae_coco_image_encoder_fwd", h, ptr(ws), wsb, ptr(x), ptr(m1), ptr(m2), training, ptr(out), _stream())
-            ctx.ws = ws
-            return out
-
-        def bwd(ctx, d_out):
-            st.grads.zero_()
-            call("mmvae_coco_image_encoder_bwd", h, ptr(ctx.ws), wsb, ptr(d_out.contiguous()), ptr(m1), ptr(m2), _stream())
-            return [None] + core.grads_for(names)
-
-        out = _ModuleFn.apply(fwd, bwd, 1, x, *plist)
+            else:                                                    # one seed per mask
+                m1, m2 = Draw((x.shape[0], 1024), 2), Draw((x.shape[0], 256), 3)
+        out = run_module(self, "image_encoder.", _plan(self.steps), x, "mmvae_coco_image_encoder", (2 * n,),
+                         ("x", m1, m2, "training", "out"), ("d", m1, m2))
         return out[:, :n], out[:, n:]
 
 
@@ -253,25 +225,8 @@ class ImageDecoder(nn.Module):
         self._core = None
 
     def forward(self, z):
-        z = z.contiguous().float()
-        core, st, B, h, wsb, names, plist = _prep(self, "image_decoder.", z)
-        training = int(self.training)
-        n = self.n_latents
-
-        def fwd(ctx):
-            ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
-            recon = torch.empty(B, 3, 32, 32, dtype=torch.float32, device=z.device)
-            call("mmvae_coco_image_decoder_fwd", h, ptr(ws), wsb, ptr(z), training, ptr(recon), _stream())
-            ctx.ws, ctx.recon = ws, recon
-            return recon
-
-        def bwd(ctx, d_recon):
-            st.grads.zero_()
-            dz = torch.empty(B, n, dtype=torch.float32, device=z.device)
-            call("mmvae_coco_image_decoder_bwd", h, ptr(ctx.ws), wsb, ptr(d_recon.contiguous()), ptr(ctx.recon), ptr(dz), _stream())
-            return [dz] + core.grads_for(names)
-
-        return _ModuleFn.apply(fwd, bwd, 1, z, *plist)
+        return run_module(self, "image_decoder.", _plan(self.steps), z.contiguous().float(), "mmvae_coco_image_decoder", (3, 32, 32),
+                          *DECODER)
 
 
 class TextEncoder(nn.Module):
@@ -296,21 +251,7 @@ class TextEncoder(nn.Module):
         x = x.contiguous().float()
         assert x.dim() == 3 and x.shape[1] == self.steps and x.shape[2] == N_EMBEDDING, \
             "expected (B, %d, 300) caption tensors (coco/utils.py:36-47)" % self.steps
-        core, st, B, h, wsb, names, plist = _prep(self, "text_encoder.", x)
-
-        def fwd(ctx):
-            ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-            out = torch.empty(B, 2 * n, dtype=torch.float32, device=x.device)
-            call("mmvae_coco_text_encoder_fwd", h, ptr(ws), wsb, ptr(x), ptr(out), _stream())
-            ctx.ws = ws
-            return out
-
-        def bwd(ctx, d_out):
-            st.grads.zero_()
-            call("mmvae_coco_text_encoder_bwd", h, ptr(ctx.ws), wsb, ptr(x), ptr(d_out.contiguous()), _stream())
-            return [None] + core.grads_for(names)
-
-        out = _ModuleFn.apply(fwd, bwd, 1, x, *plist)
+        out = run_module(self, "text_encoder.", _plan(self.steps), x, "mmvae_coco_text_encoder", (2 * n,), ("x", "out"), ("x", "d"))
         return out[:, :n], out[:, n:]
 
 
@@ -344,33 +285,15 @@ class TextDecoder(nn.Module):
 
     def forward(self, z, keep: Optional[torch.Tensor] = None):
         z = z.contiguous().float()
-        core, st, B, h, wsb, names, plist = _prep(self, "text_decoder.", z)
-        training = int(self.training)
-        T, n = self.steps, self.n_latents
-        pdrop = self.gru.dropout
-        if self.training and pdrop > 0:
-            if abs(pdrop - DROP_P) > 1e-9:
-                raise MMVAEError("the HIP text decoder supports GRU dropout in {0, 0.1} (reference: 0.1)")
-            keep = _keep((T, B, N_HIDDENS), z.device, 4) if keep is None else keep.to(torch.uint8).contiguous()
-        else:
+        if not _dropout_on(self, (self.gru.dropout,), "the HIP text decoder supports GRU dropout in {0, 0.1} (reference: 0.1)"):
             keep = None
+        elif keep is None:
+            keep = Draw((self.steps, z.shape[0], N_HIDDENS), 4)
+        else:
+            keep = keep.to(torch.uint8).contiguous()
         sos = self.sos.to(z.device).contiguous()
-
-        def fwd(ctx):
-            ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
-            sentence = torch.empty(B, T, N_EMBEDDING, dtype=torch.float32, device=z.device)
-            call("mmvae_coco_text_decoder_fwd", h, ptr(ws), wsb, ptr(z), ptr(sos), ptr(keep), training, ptr(sentence), _stream())
-            ctx.ws, ctx.sentence = ws, sentence
-            return sentence
-
-        def bwd(ctx, d_sentence):
-            st.grads.zero_()
-            dz = torch.empty(B, n, dtype=torch.float32, device=z.device)
-            call("mmvae_coco_text_decoder_bwd", h, ptr(ctx.ws), wsb, ptr(z), ptr(sos), ptr(keep), ptr(ctx.sentence),
-                 ptr(d_sentence.contiguous()), ptr(dz), _stream())
-            return [dz] + core.grads_for(names)
-
-        return _ModuleFn.apply(fwd, bwd, 1, z, *plist)
+        return run_module(self, "text_decoder.", _plan(self.steps), z, "mmvae_coco_text_decoder", (self.steps, N_EMBEDDING),
+                          ("x", sos, keep, "training", "out"), ("x", sos, keep, "out", "d", "dx"))
 
     def generate_vector(self, z):
         """coco/model.py:308-309"""
@@ -401,7 +324,7 @@ def assemble_sentences(strings: Sequence[str], batch: int, steps: int, stop_at_e
     return out
 
 
-class MultimodalVAE(nn.Module):
+class MultimodalVAE(ExpertsVAEBase):
     """coco/model.py:22-90"""
 
     def __init__(self, n_latents=20, use_cuda=False, sos=None, steps=MAX_WORDS, words: Optional[WordTable] = None):
@@ -414,16 +337,7 @@ class MultimodalVAE(nn.Module):
         self.n_latents = n_latents
         self.steps = steps
         self._core = _Core(self, "", n_latents, lambda n, d: CocoState(n, d, steps))
-        for m in (self.image_encoder, self.image_decoder, self.text_encoder, self.text_decoder):
-            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
-
-    def reparametrize(self, mu, logvar, eps: Optional[torch.Tensor] = None):
-        if self.training:
-            if eps is None:
-                eps = torch.empty_like(mu)
-                call("mmvae_normal", ptr(eps), eps.numel(), _seed_from_torch(), None, 1, _stream())
-            return _ReparamFn.apply(mu, logvar, eps.contiguous())
-        return mu
+        self._adopt(self.image_encoder, self.image_decoder, self.text_encoder, self.text_decoder)
 
     def encode_image(self, x):
         return self.image_encoder(x)
@@ -437,47 +351,12 @@ class MultimodalVAE(nn.Module):
     def decode_text(self, z):
         return self.text_decoder(z)
 
-    def prior(self, size, use_cuda=False):
-        """coco/model.py:50-58"""
-        mu, logvar = torch.zeros(size), torch.log(torch.ones(size))
-        if use_cuda:
-            mu, logvar = mu.cuda(), logvar.cuda()
-        return mu, logvar
-
     def forward(self, image=None, text=None, eps=None, enc_masks=None, gru_keep=None):
         assert image is not None or text is not None
-        if image is not None and text is not None:
-            image_mu, image_logvar = self.image_encoder(image, enc_masks)
-            text_mu, text_logvar = self.text_encoder(text)
-            mu = torch.stack((image_mu, text_mu), dim=0)
-            logvar = torch.stack((image_logvar, text_logvar), dim=0)
-        elif image is not None:
-            mu, logvar = self.image_encoder(image, enc_masks)
-            mu, logvar = mu.unsqueeze(0), logvar.unsqueeze(0)
-        else:
-            mu, logvar = self.text_encoder(text)
-            mu, logvar = mu.unsqueeze(0), logvar.unsqueeze(0)
-        mu, logvar = self.experts(mu, logvar)
+        mu, logvar = self._product(None if image is None else self.image_encoder(image, enc_masks),
+                                   None if text is None else self.text_encoder(text))
         z = self.reparametrize(mu, logvar, eps)
         return self.image_decoder(z), self.text_decoder(z, gru_keep), mu, logvar
-
-
-
-class _MSEMeanFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b):
-        a, b = a.contiguous().float(), b.contiguous().float()
-        out = torch.zeros(1, dtype=torch.float32, device=a.device)
-        call("mmvae_mse_fwd", ptr(a), ptr(b), a.numel(), ptr(out), _stream())
-        ctx.save_for_backward(a, b)
-        return (out / a.numel()).squeeze(0)
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b = ctx.saved_tensors
-        da = torch.empty_like(a)
-        call("mmvae_mse_bwd", ptr(a), ptr(b), a.numel(), 1.0 / a.numel(), ptr(_gscale(g)), ptr(da), _stream())
-        return da, None
 
 
 def loss_function(mu, logvar, recon_image=None, image=None, recon_text=None, text=None,
@@ -497,7 +376,7 @@ def loss_function(mu, logvar, recon_image=None, image=None, recon_text=None, tex
 elbo_loss = loss_function
 
 
-class InfoVAE(nn.Module):
+class InfoVAE(VAEBase):
     """coco/model.py:358-382.  ``encoder`` / ``decoder`` are the stand-alone HIP modules above, each on its own core, so
     ``state_dict()`` has the reference's keys (``encoder.features.0.weight`` ... ``decoder.hallucinate.9.weight``) and
     ``optim.Adam(vae.parameters())`` steps the ``nn.Parameter``s the kernels read."""
@@ -510,8 +389,6 @@ class InfoVAE(nn.Module):
 
     def encode(self, x, masks=None):
         return self.encoder(x, masks)
-
-    reparametrize = MultimodalVAE.reparametrize                    # coco/model.py:368-374 is :38-44: sample in training, mu in eval
 
     def decode(self, z):
         return self.decoder(z)
@@ -560,7 +437,7 @@ class FusedTrainer(Trainer):
 IMAGE_VAE_STEPS = 1       # caption length of the plan an ImageVAE lives on: no caption ever runs, so its buffers are the smallest
 
 
-class ImageVAE(nn.Module):
+class ImageVAE(VAEBase):
     """coco/model.py:93-117: ``ImageEncoder`` + ``reparametrize`` + ``ImageDecoder`` under the reference's ``encoder.`` / ``decoder.``
     keys, with NO product of experts.  Unlike ``InfoVAE`` (two stand-alone cores, autograd between them) the two children share ONE
     core on the MultimodalVAE's plan (``encoder.features.0.weight`` is its ``image_encoder.features.0.weight``), which is what
@@ -573,13 +450,10 @@ class ImageVAE(nn.Module):
         self.decoder = ImageDecoder(n_latents, steps=IMAGE_VAE_STEPS)
         self.n_latents = n_latents
         self._core = _Core(self, "image_", n_latents, lambda n, d: CocoState(n, d, IMAGE_VAE_STEPS))
-        for m in (self.encoder, self.decoder):
-            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+        self._adopt(self.encoder, self.decoder)
 
     def encode(self, x, masks=None):
         return self.encoder(x, masks)
-
-    reparametrize = MultimodalVAE.reparametrize
 
     def decode(self, z):
         return self.decoder(z)
@@ -618,7 +492,7 @@ def check_text_latents(n_latents) -> int:
     return n
 
 
-class TextVAE(nn.Module):
+class TextVAE(VAEBase):
     """coco/model.py:120-144: ``TextEncoder`` + ``reparametrize`` + ``TextDecoder`` under the reference's ``encoder.`` / ``decoder.``
     keys, with NO product of experts.  The two children share ONE core on the MultimodalVAE's plan (``encoder.gru.weight_ih_l0`` is
     its ``text_encoder.gru.weight_ih_l0``), which is what ``TextVAETrainer`` steps in one enqueue; the image half of the flat
@@ -633,13 +507,10 @@ class TextVAE(nn.Module):
         self.n_latents = n_latents
         self.steps = steps
         self._core = _Core(self, "text_", n_latents, lambda n, d: CocoState(n, d, steps))
-        for m in (self.encoder, self.decoder):
-            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+        self._adopt(self.encoder, self.decoder)
 
     def encode(self, x):
         return self.encoder(x)
-
-    reparametrize = MultimodalVAE.reparametrize
 
     def decode(self, z, keep: Optional[torch.Tensor] = None):
         return self.decoder(z, keep)

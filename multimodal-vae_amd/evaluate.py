@@ -20,7 +20,7 @@ import torch
 
 from . import _ops
 from ._lib import call, ptr
-from .multimnist import _BCEMeanFn, _NLLMeanFn
+from .modules import _BCEMeanFn, _NLLMeanFn
 from .utils import FILL, max_length
 
 

@@ -11,56 +11,17 @@ is a call into libmmvae_hip.so.  No CPU fallback.  ``FusedTrainer`` runs the who
 """
 from __future__ import annotations
 
-import weakref
 from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._lib import MMVAEError, call, ptr
+from ._lib import MMVAEError
 from .core import FusedImageStep, FusedMnistStep, MnistState, StepOutputs, Trainer, load_vae_checkpoint
-from .multimnist import (ProductOfExperts, _BCEMeanFn, _Core, _KLSumFn, _ModuleFn, _NLLMeanFn, _ReparamFn, _core_of,
-                         _seed_from_torch, _stream)
+from .modules import DECODER, ExpertsVAEBase, ProductOfExperts, VAEBase, _BCEMeanFn, _Core, _KLSumFn, _NLLMeanFn, run_module
 
-
-def _run_module(mod: nn.Module, prefix: str, x: torch.Tensor, out_shape, name: str, needs_input_grad: bool, extra_fwd=(),
-                bwd_args=None):
-    """Shared bridge of the four MLP modules: forward = mmvae_mnist_<name>_fwd, backward = ..._bwd."""
-    core = _core_of(mod, prefix, MnistState)
-    st = core.sync(x.device)
-    B = x.shape[0]
-    if mod.training and B <= 1:
-        raise ValueError("Expected more than 1 value per channel when training")
-    h = st.plan(B)
-    wsb = st.module_workspace_bytes(B)
-    training = int(mod.training)
-    names = [prefix + k for k, _ in mod.named_parameters()]
-    plist = [p for _, p in mod.named_parameters()]
-    n_lat = core.n_latents
-
-    def fwd(ctx):
-        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-        out = torch.empty((B,) + tuple(out_shape), dtype=torch.float32, device=x.device)
-        call("mmvae_mnist_%s_fwd" % name, h, ptr(ws), wsb, ptr(x), training, ptr(out), _stream())
-        ctx.ws, ctx.out = ws, out
-        return out
-
-    def bwd(ctx, d_out):
-        st.grads.zero_()
-        d = d_out.contiguous()
-        if name == "image_encoder":
-            call("mmvae_mnist_image_encoder_bwd", h, ptr(ctx.ws), wsb, ptr(d), _stream())
-            dx = None
-        elif name == "text_encoder":
-            call("mmvae_mnist_text_encoder_bwd", h, ptr(ctx.ws), wsb, ptr(x), ptr(d), _stream())
-            dx = None
-        else:
-            dx = torch.empty(B, n_lat, dtype=torch.float32, device=x.device)
-            call("mmvae_mnist_%s_bwd" % name, h, ptr(ctx.ws), wsb, ptr(d), ptr(ctx.out), ptr(dx), _stream())
-        return [dx] + core.grads_for(names)
-
-    return _ModuleFn.apply(fwd, bwd, 1, x, *plist)
+ENCODER_FWD = ("x", "training", "out")       # the C arguments of the two encoders' forward (modules.run_module); the decoders' are DECODER
 
 
 class ImageEncoder(nn.Module):
@@ -79,7 +40,7 @@ class ImageEncoder(nn.Module):
         n = self.n_latents
         x = x.contiguous().float()
         assert x.dim() == 2 and x.shape[1] == 784, "expected (B,784) flattened images (mnist/train.py:123)"
-        out = _run_module(self, "image_encoder.", x, (2 * n,), "image_encoder", False)
+        out = run_module(self, "image_encoder.", MnistState, x, "mmvae_mnist_image_encoder", (2 * n,), ENCODER_FWD, ("d",), bn_values=1)
         return out[:, :n], out[:, n:]
 
 
@@ -96,7 +57,7 @@ class ImageDecoder(nn.Module):
         self._core = None
 
     def forward(self, z):
-        return _run_module(self, "image_decoder.", z.contiguous().float(), (784,), "image_decoder", True)
+        return run_module(self, "image_decoder.", MnistState, z.contiguous().float(), "mmvae_mnist_image_decoder", (784,), *DECODER, bn_values=1)
 
 
 class TextEncoder(nn.Module):
@@ -112,7 +73,7 @@ class TextEncoder(nn.Module):
         n = self.n_latents
         x = x.contiguous().long()
         assert x.dim() == 1, "expected (B,) digit labels"
-        out = _run_module(self, "text_encoder.", x, (2 * n,), "text_encoder", False)
+        out = run_module(self, "text_encoder.", MnistState, x, "mmvae_mnist_text_encoder", (2 * n,), ENCODER_FWD, ("x", "d"), bn_values=1)
         return out[:, :n], out[:, n:]
 
 
@@ -126,10 +87,10 @@ class TextDecoder(nn.Module):
         self._core = None
 
     def forward(self, z):
-        return _run_module(self, "text_decoder.", z.contiguous().float(), (10,), "text_decoder", True)
+        return run_module(self, "text_decoder.", MnistState, z.contiguous().float(), "mmvae_mnist_text_decoder", (10,), *DECODER, bn_values=1)
 
 
-class MultimodalVAE(nn.Module):
+class MultimodalVAE(ExpertsVAEBase):
     """mnist/model.py:14-96"""
 
     def __init__(self, n_latents=20, precision="fp32"):
@@ -143,16 +104,7 @@ class MultimodalVAE(nn.Module):
         self.n_latents = n_latents
         self.precision = precision
         self._core = _Core(self, "", n_latents, lambda n, d: MnistState(n, d, precision))
-        for m in (self.image_encoder, self.image_decoder, self.text_encoder, self.text_decoder):
-            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
-
-    def reparametrize(self, mu, logvar, eps: Optional[torch.Tensor] = None):
-        if self.training:
-            if eps is None:
-                eps = torch.empty_like(mu)
-                call("mmvae_normal", ptr(eps), eps.numel(), _seed_from_torch(), None, 1, _stream())
-            return _ReparamFn.apply(mu, logvar, eps.contiguous())
-        return mu
+        self._adopt(self.image_encoder, self.image_decoder, self.text_encoder, self.text_decoder)
 
     def encode_image(self, x):
         return self.image_encoder(x)
@@ -166,26 +118,8 @@ class MultimodalVAE(nn.Module):
     def decode_text(self, x):
         return self.text_decoder(x)
 
-    def prior(self, size, use_cuda=False):
-        mu = torch.zeros(size)
-        logvar = torch.log(torch.ones(size))
-        if use_cuda:
-            mu, logvar = mu.cuda(), logvar.cuda()
-        return mu, logvar
-
     def _latents(self, image, text):
-        if image is not None and text is not None:
-            image_mu, image_logvar = self.encode_image(image)
-            text_mu, text_logvar = self.encode_text(text)
-            mu = torch.stack((image_mu, text_mu), dim=0)
-            logvar = torch.stack((image_logvar, text_logvar), dim=0)
-        elif image is not None:
-            mu, logvar = self.encode_image(image)
-            mu, logvar = mu.unsqueeze(0), logvar.unsqueeze(0)
-        else:
-            mu, logvar = self.encode_text(text)
-            mu, logvar = mu.unsqueeze(0), logvar.unsqueeze(0)
-        return self.experts(mu, logvar)
+        return self._product(None if image is None else self.encode_image(image), None if text is None else self.encode_text(text))
 
     def forward(self, image=None, text=None, eps=None):
         assert image is not None or text is not None
@@ -283,11 +217,11 @@ class _ImageNet(nn.Sequential):
         x = x.contiguous().float()
         if self._name == "image_encoder":
             assert x.dim() == 2 and x.shape[1] == 784, "expected (B,784) flattened images (mnist/model.py:230)"
-            return _run_module(self, "image_encoder.net.", x, (2 * self.n_latents,), "image_encoder", False)
-        return _run_module(self, "image_decoder.net.", x, (784,), "image_decoder", True)
+            return run_module(self, "image_encoder.net.", MnistState, x, "mmvae_mnist_image_encoder", (2 * self.n_latents,), ENCODER_FWD, ("d",), bn_values=1)
+        return run_module(self, "image_decoder.net.", MnistState, x, "mmvae_mnist_image_decoder", (784,), *DECODER, bn_values=1)
 
 
-class VAE(nn.Module):
+class VAE(VAEBase):
     """mnist/model.py:188-232: the image-only baseline under the reference's ``state_dict`` keys (``encoder.0.weight`` ...
     ``decoder.6.bias``, BatchNorm buffers under ``encoder.1``, ``encoder.4``, ``decoder.1``, ``decoder.4``); a reference checkpoint
     loads strict.  No product of experts.  The two halves live on the fp32 MMVAE plan as its ``image_encoder.net.*`` /
@@ -311,8 +245,7 @@ class VAE(nn.Module):
         twin.image_encoder.net, twin.image_decoder.net = self.encoder, self.decoder
         object.__setattr__(self, "_twin", twin)
         self._core = _Core(twin, "", n_latents, lambda n, d: MnistState(n, d, "fp32"))
-        for m in (self.encoder, self.decoder):
-            object.__setattr__(m, "_mmvae_root", weakref.ref(self))
+        self._adopt(self.encoder, self.decoder)
 
     @staticmethod
     def plan_name(key: str) -> str:
@@ -326,7 +259,7 @@ class VAE(nn.Module):
         return out[:, :n], out[:, n:]
 
     def reparameterize(self, mu, logvar, eps: Optional[torch.Tensor] = None):
-        return MultimodalVAE.reparametrize(self, mu, logvar, eps)
+        return self.reparametrize(mu, logvar, eps)
 
     def decode(self, z):
         return self.decoder(z)

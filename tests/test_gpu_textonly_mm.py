@@ -249,6 +249,53 @@ def _step_engine(B, D, dev, P, kl_lambda=1e-3, lambda_y=1.0):
     return core.FusedMMTextStep(st, B, lr=1e-3, kl_lambda=kl_lambda, lambda_y=lambda_y, seed=11)
 
 
+@pytest.mark.parametrize("B,D", [(2, 20), (4, 100)])
+def test_module_face_trains_like_float64(B, D):
+    """``TextVAE`` through its drop-in modules in training mode (mmvae_mmtext_encoder / decoder, fwd and bwd, with autograd between
+    them): forward, ``textonly_loss_function`` and ``.backward()`` against the float64 step, at the gates of the fused step above;
+    then once more with a keep mask the decoder draws itself."""
+    from multimodal_vae_amd import multimnist as M
+    dev = _dev()
+    P = TM.make_params(D, H)
+    c = _step_case(B, D)
+    ref = TM.run_step(P, c["text"], c["eps"], c["keep"], c["force"])
+    vae = M.TextVAE(D, use_cuda=True)
+    vae.load_state_dict(P, strict=True)
+    vae = vae.cuda().train()
+    text = c["text"].to(dev)
+    recon, mu, lv = vae(text, eps=c["eps"].to(dev), gru_keep=c["keep"].to(dev), force_tokens=c["force"].to(dev))
+    loss = M.textonly_loss_function(mu, lv, recon, text, kl_lambda=1e-3)
+    loss.backward()
+    g = {n: p.grad.detach().cpu() for n, p in vae.named_parameters()}
+    assert sorted(g) == sorted(ref["grads"])
+    rel = abs(float(loss) - ref["loss"]) / abs(ref["loss"])
+    e_mu = float((mu.double().cpu() - ref["mu"]).abs().max())
+    e_lv = float((lv.double().cpu() - ref["logvar"]).abs().max())
+    by = {n: TM.rel_l2(g[n], ref["grads"][n]) for n in g if float(ref["grads"][n].abs().max()) > 0}
+    tot = torch.sqrt(sum((g[n].double() ** 2).sum() for n in g))
+    tot_ref = torch.sqrt(sum((ref["grads"][n] ** 2).sum() for n in g))
+    e_tot = abs(float(tot) - float(tot_ref)) / float(tot_ref)
+    if REPORT:
+        print("TOL mmtext modules B=%d D=%d: loss rel %.2e, mu %.2e, logvar %.2e, worst grad %.2e (%s), total norm %.2e"
+              % (B, D, rel, e_mu, e_lv, max(by.values()), max(by, key=by.get), e_tot))
+    assert rel <= 1e-3 and e_mu <= 1e-2 and e_lv <= 1e-2
+    assert all(v <= 4e-2 for v in by.values()), {n: v for n, v in by.items() if v > 4e-2}
+    assert e_tot <= 2e-3
+    assert float(g["encoder.gru.weight_hh_l0_reverse"].abs().max()) == 0.0
+    assert torch.equal(vae.decoder.last_tokens.cpu(), ref["tokens"])
+    # a mask of its own: seeded, the same mask and so the same bits twice; another seed, another mask
+    got = []
+    for seed in (3, 3, 4):
+        vae.zero_grad()
+        torch.manual_seed(seed)
+        recon, mu, lv = vae(text, eps=c["eps"].to(dev), force_tokens=c["force"].to(dev))
+        M.textonly_loss_function(mu, lv, recon, text).backward()
+        got.append((recon.detach().clone(), vae.decoder.z2h.weight.grad.clone()))
+        assert all(bool(torch.isfinite(p.grad).all()) for p in vae.parameters())
+    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
+    assert not torch.equal(got[0][0], got[2][0])
+
+
 def _grads_of(st):
     out = {}
     for n, shape, off in st.table:

@@ -456,7 +456,7 @@ def main():
     from multimodal_vae_amd import multimnist as M, data as Dd
     from multimodal_vae_amd._lib import call
     from multimodal_vae_amd.evaluate import iw_estimate, marginal_table, _proposal, iw_chunks, IW_ROWS
-    from multimodal_vae_amd.multimnist import _BCEMeanFn, _NLLMeanFn
+    from multimodal_vae_amd.modules import _BCEMeanFn, _NLLMeanFn
     from multimodal_vae_amd.utils import charlist_tensor
     from oracle import mmvae_ref as R
     dev = torch.device("cuda:0")

@@ -154,7 +154,7 @@ def main():
         vae = K.InfoVAE(n_latents=D).cuda().train()
         opt = torch.optim.Adam(vae.parameters(), lr=1e-4)
         img = torch.rand(B, 3, 32, 32, device=dev, generator=g)
-        from multimodal_vae_amd.multimnist import _BCEMeanFn
+        from multimodal_vae_amd.modules import _BCEMeanFn
 
         def step(mmd_fn):
             def go():
