@@ -502,6 +502,47 @@ int mmvae_celeba_image_step(mmvae_celeba_t*, const mmvae_image_step_io*, int tra
 size_t mmvae_celeba_image_step_workspace_bytes(const mmvae_celeba_t*);
 int mmvae_coco_image_step(mmvae_coco_t*, const mmvae_image_step_io*, int training, int do_backward, void* stream);
 size_t mmvae_coco_image_step_workspace_bytes(const mmvae_coco_t*);
+/* COCO InfoVAE (coco/model.py:358-402, coco/train_infovae.py:44-55) as one enqueue: mmvae_coco_image_step with one more term,
+ *   loss = lambda_x * BCE / (B * 3072) + lambda_mmd * MMD(true_samples, z) + kl_lambda * KL / B
+ * (the reference's loss: lambda_x = lambda_mmd = 1, kl_lambda = 0), MMD as mmvae_mmd computes it with x = the prior samples and y = z.
+ * Everything said of mmvae_coco_image_step holds: zero_grad included, one Dropout variant, one BatchNorm update per layer, nothing of
+ * the caption half launched (its gradients exactly 0, its parameters and buffers not written), defer_unpack honoured, no host
+ * synchronisation.  The MMD term runs as the y-only form of the pair sweep (mmvae_mmd_dy) and its fold on a side stream of the plan,
+ * next to the decoder's forward and backward; the main stream waits for it once, in front of the latent block's backward, which adds
+ * lambda_mmd * dMMD/dz to the decoder's dz.  With lambda_x = 0 the decoder's backward is skipped and the MMD gradient is the only dz;
+ * with lambda_mmd = 0 the value is still reported and no gradient is formed.  true_samples NULL: drawn by the step's prologue on
+ * Philox stream MMVAE_TRUE_SAMPLES_STREAM, keyed by seed and step_counter as eps (the values of mmvae_normal for that stream).
+ * training = 0: z = mu, nothing drawn but the prior samples.  do_backward = 0: stops behind the losses, the sweep takes its
+ * value-only form.  sums [16]: [0] BCE sum, [8] KL sum, [MMVAE_SUM_MMD_KXX .. MMVAE_SUM_MMD] = {mean Kxx, mean Kyy, mean Kxy, MMD},
+ * every other slot 0.  Workspace: mmvae_coco_infovae_step_workspace_bytes = the one-pass carve + the sweep's partial sums, the MMD
+ * gradient and the drawn samples, 16-byte aligned; nothing is allocated inside the step.
+ * mmvae_coco_debug_offset "infovae_step:true_samples" | "infovae_step:dz_mmd" | "infovae_step:mmd_ws": those buffers' offsets. */
+#define MMVAE_SUM_MMD_KXX 12
+#define MMVAE_SUM_MMD_KYY 13
+#define MMVAE_SUM_MMD_KXY 14
+#define MMVAE_SUM_MMD 15
+#define MMVAE_TRUE_SAMPLES_STREAM 5
+typedef struct {
+    void* ws; size_t ws_bytes;
+    const long long* step_counter;          /* device int64 keying the Philox streams, or NULL */
+    const float* image;                     /* [B][3][32][32] fp32 */
+    const float* eps;                       /* [B][D] or NULL (drawn on device) */
+    const uint8_t* enc_mask1;               /* [B][1024] keep flags of the classifier's first Dropout(0.1) or NULL (drawn) */
+    const uint8_t* enc_mask2;               /* [B][256] keep flags of its second Dropout, given or NULL together with enc_mask1 */
+    int enc_dropout;                        /* 0: no dropout */
+    float kl_lambda;
+    float lambda_x;
+    unsigned long long seed;
+    float* sums;                            /* out [16], see above */
+    float* recon_image;                     /* out [B][3][32][32] or NULL */
+    float* mu; float* logvar;               /* out [B][D] or NULL */
+    int defer_unpack;                       /* 1: the optimizer consumes the packed gradients itself */
+    const float* true_samples;              /* [B][D] prior samples or NULL (drawn on the device) */
+    float lambda_mmd;                       /* weight of the MMD term; the reference's loss is lambda_x = lambda_mmd = 1, kl_lambda = 0 */
+    float* z;                               /* out [B][D] or NULL */
+} mmvae_infovae_step_io;
+int mmvae_coco_infovae_step(mmvae_coco_t*, const mmvae_infovae_step_io*, int training, int do_backward, void* stream);
+size_t mmvae_coco_infovae_step_workspace_bytes(const mmvae_coco_t*);
 /* log p(x|z) of the baseline: mmvae_<family>_iw_score with the image half alone -- the eval-mode decoder body and the scoring tail
  * kernel write loglik_x [B*K]; the second modality's decoder does not run.  Workspace: mmvae_<family>_iw_workspace_bytes. */
 int mmvae_celeba_iw_score_image(mmvae_celeba_t*, void* ws, size_t ws_bytes, const float* z, const float* image, int B, int K,
@@ -892,6 +933,14 @@ long long mmvae_mmd_workspace_bytes(int n_x, int n_y, int dim);
 int mmvae_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* ws, long long ws_bytes,
               float* out4, float* dx_or_null, float* dy_or_null, void* stream);
 int mmvae_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, int dim, float* k, void* stream);
+/* The form a training step takes (x: prior samples, no gradient wanted): out4 as mmvae_mmd, dy = scale * dMMD/dy (NULL: the value
+ * alone), dx never formed.  The same grid; the row tiles of x run the value form of the sweep (kernel sums only), so about half of
+ * the gradient arithmetic and of the gradient workspace goes.  Per pair, per 8 columns, per split and in the fold the arithmetic and
+ * its order are mmvae_mmd's: out4, and dy at scale = 1, are bit for bit what mmvae_mmd writes.  grad_y_only must be 1 (the one form
+ * this entry has; anything else is refused).  ws: mmvae_mmd_dy_workspace_bytes(n_x, n_y, dim) bytes, 8-byte aligned. */
+long long mmvae_mmd_dy_workspace_bytes(int n_x, int n_y, int dim);
+int mmvae_mmd_dy(const float* x, int n_x, const float* y, int n_y, int dim, void* ws, long long ws_bytes, float scale,
+                 float* out4, float* dy_or_null, int grad_y_only, void* stream);
 
 /* Incremental sampler for PixelCNN / GatedPixelCNN (coco/model.py:405-585), fp32 storage and accumulation, ONE launch per call.
  * A model is (gated, n_blocks 0..15, data_channels 1 or 3, hid_dims a multiple of 16 up to 128, out_dims 2..256); sides 1..64, any

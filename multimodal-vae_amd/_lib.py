@@ -111,6 +111,15 @@ class ImageStepIO(C.Structure):
     ]
 
 
+class InfoVAEStepIO(C.Structure):
+    """mmvae_infovae_step_io"""
+    _fields_ = ImageStepIO._fields_ + [
+        ("true_samples", C.c_void_p),
+        ("lambda_mmd", C.c_float),
+        ("z", C.c_void_p),
+    ]
+
+
 class TextStepIO(C.Structure):
     """mmvae_text_step_io"""
     _fields_ = [
@@ -294,6 +303,8 @@ for _f in ("celeba", "coco", "mm", "mnist"):
     SIGNATURES["mmvae_%s_image_step" % _f] = (_I, [_P, C.POINTER(ImageStepIO), _I, _I, _P])
     SIGNATURES["mmvae_%s_image_step_workspace_bytes" % _f] = (_SZ, [_P])
     SIGNATURES["mmvae_%s_iw_score_image" % _f] = (_I, [_P, _P, _SZ, _P, _P, _I, _I, _P, _P])
+SIGNATURES["mmvae_coco_infovae_step"] = (_I, [_P, C.POINTER(InfoVAEStepIO), _I, _I, _P])
+SIGNATURES["mmvae_coco_infovae_step_workspace_bytes"] = (_SZ, [_P])
 SIGNATURES["mmvae_mnist_strip_max_rows"] = (_I, [])
 SIGNATURES["mmvae_mnist_strip_route"] = (_I, [_I])
 SIGNATURES["mmvae_mnist_lin_bn_act_fwd"] = (_I, [_I, _P, _I] + [_P] * 7 + [_I] * 4 + [_P] * 4)
@@ -334,6 +345,8 @@ SIGNATURES["mmvae_mmd_geometry"] = (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER
 SIGNATURES["mmvae_mmd_workspace_bytes"] = (_LL, [_I, _I, _I])
 SIGNATURES["mmvae_mmd"] = (_I, [_P, _I, _P, _I, _I, _P, _LL, _P, _P, _P, _P])
 SIGNATURES["mmvae_mmd_kernel_matrix"] = (_I, [_P, _I, _P, _I, _I, _P, _P])
+SIGNATURES["mmvae_mmd_dy_workspace_bytes"] = (_LL, [_I, _I, _I])
+SIGNATURES["mmvae_mmd_dy"] = (_I, [_P, _I, _P, _I, _I, _P, _LL, _F, _P, _P, _I, _P])
 SIGNATURES["mmvae_tsne_geometry"] = (_I, [C.POINTER(_I)] * 5)
 SIGNATURES["mmvae_tsne_workspace_bytes"] = (_LL, [_I])
 SIGNATURES["mmvae_tsne_affinities"] = (_I, [_P, _I, _I, _F, _P, _P, _P, _P, _LL, _P])

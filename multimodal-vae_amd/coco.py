@@ -19,7 +19,9 @@ stays attached to its word, a deliberate difference).  The table file is one ``.
 
 InfoVAE: ``InfoVAE`` (coco/model.py:358-382) is ``ImageEncoder`` + ``ImageDecoder`` + ``reparametrize`` under the reference's
 ``encoder.`` / ``decoder.`` keys; ``infovae_loss`` is ``coco/train_infovae.py:44-55`` (mean BCE + MMD against prior samples) with
-the MMD term on the fused op of ``mmd.py``; ``compute_mmd`` / ``compute_kernel`` are re-exported from there.
+the MMD term on the fused op of ``mmd.py``; ``compute_mmd`` / ``compute_kernel`` are re-exported from there.  ``FusedInfoVAE`` is the
+same model on ONE core (the construction of ``ImageVAE``), which ``InfoVAETrainer`` steps in one enqueue with the MMD sweep beside the
+decoder (core.FusedInfoVAEStep); the two classes load each other's state dicts.
 """
 from __future__ import annotations
 
@@ -30,7 +32,7 @@ import torch.nn as nn
 
 from ._lib import MMVAEError, call, ptr
 from ._ops import geometry, stream as _stream
-from .core import CocoState, FusedCocoStep, FusedImageStep, FusedTextStep, Trainer, load_vae_checkpoint
+from .core import CocoState, FusedCocoStep, FusedImageStep, FusedInfoVAEStep, FusedTextStep, Trainer, load_vae_checkpoint
 from .mmd import compute_kernel, compute_mmd, mmd_terms  # noqa: F401  (coco/model.py:385-402)
 from .modules import (DECODER, Draw, ExpertsVAEBase, ProductOfExperts, Swish, VAEBase, _BCEMeanFn, _Core, _dropout_on, _KLSumFn, _MSEMeanFn,
                       _seed_from_torch, run_module)
@@ -473,6 +475,27 @@ class ImageVAETrainer(Trainer):
     """``ImageVAETrainer(vae, batch_size, lr)(image)``: coco/train_imageonly.py:105-116, lr 1e-4, kl_lambda 5e-4, on an
     ``ImageVAE``: one pass over B rows."""
     ENGINE, LR, KL_LAMBDA = FusedImageStep, 1e-4, 5e-4
+    ENC_DROPOUT = staticmethod(lambda vae: vae.encoder.classifier[2].p)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# InfoVAE on one core: the fused step of coco/train_infovae.py
+# ----------------------------------------------------------------------------------------------------------------
+class FusedInfoVAE(ImageVAE):
+    """coco/model.py:358-382 with ``ImageVAE``'s one-core construction: ``encoder`` / ``decoder`` share ONE core on the
+    MultimodalVAE's plan, under the reference's ``encoder.`` / ``decoder.`` keys -- ``InfoVAE``'s keys, so a state dict of either class
+    (and a reference checkpoint) loads strict into the other.  The surface is ``InfoVAE``'s: ``forward(x) -> (recon, z)``."""
+
+    def forward(self, x, eps=None, enc_masks=None):
+        mu, logvar = self.encode(x, enc_masks)
+        z = self.reparametrize(mu, logvar, eps)
+        return self.decode(z), z
+
+
+class InfoVAETrainer(Trainer):
+    """``InfoVAETrainer(vae, batch_size, lr)(image)``: coco/train_infovae.py:113-128 (mean BCE + MMD against prior samples, no KL
+    term), lr 1e-4, on a ``FusedInfoVAE``: one pass over B rows, the MMD sweep beside the decoder."""
+    ENGINE, LR, KL_LAMBDA = FusedInfoVAEStep, 1e-4, 0.0
     ENC_DROPOUT = staticmethod(lambda vae: vae.encoder.classifier[2].p)
 
 

@@ -250,7 +250,7 @@ class StepOutputs:
 
 
 # fields that only some step-io structs have: the engine attribute of the same name / an argument of the call
-_ENGINE_FIELDS = ("enc_dropout", "gru_dropout", "kl_lambda", "lambda_x", "lambda_y", "kl_coef")
+_ENGINE_FIELDS = ("enc_dropout", "gru_dropout", "kl_lambda", "lambda_x", "lambda_y", "kl_coef", "lambda_mmd")
 _CALL_FIELDS = ("defer_unpack", "pack_first", "optimizer_state", "dp_split", "early_adam")
 _LAYOUTS: Dict[type, tuple] = {}
 
@@ -703,6 +703,24 @@ class _SinglePassStep(_FusedStepBase):
     _ranges = None
     _packed, _adam_n = True, None       # MNIST: plain Adam over the leading ``_adam_n`` elements
 
+    IMAGE_PREFIXES = ("image_encoder.", "image_decoder.")
+
+    def _image_range(self, state, restrict: bool = True) -> int:
+        """The image half is one run at the head of the flat buffers in every family: its length (``n_image_params``); ``restrict``:
+        the optimizer visits nothing else (``_ranges``) when the run is 4-aligned and not the whole buffer."""
+        n_img = 0
+        for name, shape, off in state.table:
+            if name.startswith(self.IMAGE_PREFIXES):
+                n = 1
+                for d in shape:
+                    n *= int(d)
+                assert off == n_img, "the image parameters are expected to be contiguous at the head of the table"
+                n_img = off + n
+        self.n_image_params = n_img
+        if restrict and n_img % 4 == 0 and 0 < n_img < state.nparams:
+            self._ranges = (C.c_longlong * 2)(0, n_img)
+        return n_img
+
     def evaluate(self, x, **kw) -> StepOutputs:
         """Eval-mode forward (z = mu, no dropout, nothing drawn), no backward."""
         return self.forward_backward(x, False, False, **kw)
@@ -733,7 +751,6 @@ class FusedImageStep(_SinglePassStep):
     SIDE = {"celeba": 64, "coco": 32, "mm": 50, "mnist": 28}
     CHANNELS = {"celeba": 3, "coco": 3, "mm": 1, "mnist": 1}
     FAMILIES = "CelebA, COCO and MultiMNIST have one, MNIST has one on its fp32 plan"
-    IMAGE_PREFIXES = ("image_encoder.", "image_decoder.")
     _KIND = "image-only"
     flat_images = False         # MNIST: (B, 784) batches are taken too
 
@@ -750,20 +767,9 @@ class FusedImageStep(_SinglePassStep):
         self.side, self.channels = self.SIDE[state.API], self.CHANNELS[state.API]
         self.pixels = self.channels * self.side * self.side      # per image: the BCE is a mean over B * pixels
         self.flat_images = state.API == "mnist"
-        # the image half is one run at the head of the flat buffers in every family: the optimizer visits nothing else
-        n_img = 0
-        for name, shape, off in state.table:
-            if name.startswith(self.IMAGE_PREFIXES):
-                n = 1
-                for d in shape:
-                    n *= int(d)
-                assert off == n_img, "the image parameters are expected to be contiguous at the head of the table"
-                n_img = off + n
-        self.n_image_params = n_img
+        n_img = self._image_range(state, restrict=state.API != "mnist")
         if state.API == "mnist":        # the fp32 plan writes every gradient into ``grads``
             self._packed, self._adam_n = False, n_img
-        elif n_img % 4 == 0 and 0 < n_img < state.nparams:
-            self._ranges = (C.c_longlong * 2)(0, n_img)
 
     def _workspace_bytes(self, state: PlanState, batch: int) -> int:
         return state._c("image_step_workspace_bytes", state.plan(batch))
@@ -784,6 +790,77 @@ class FusedImageStep(_SinglePassStep):
                       dict(eps=eps, enc_mask1=enc_mask1, enc_mask2=enc_mask2, recon_image=recon_image, mu=mu, logvar=logvar),
                       backward, defer_unpack=_defer_unpack)
         return self._step("mmvae_%s_image_step" % self.state.API, io, training, backward)
+
+
+class InfoVAEStepOutputs(StepOutputs):
+    """``StepOutputs`` of the InfoVAE step: slot 0 carries the pass, the loss sums' slots 12..15 the MMD term
+    ({mean Kxx, mean Kyy, mean Kxy, MMD}, include/mmvae_hip.h MMVAE_SUM_MMD_*)."""
+
+    MMD_SLOTS = slice(12, 16)
+
+    def __init__(self, sums, bce_div, kl_scale, lambda_x, lambda_mmd):
+        super().__init__(sums, bce_div, 1.0, kl_scale, (lambda_x, 0.0, 0.0), (0.0, 0.0, 0.0), (True, False, False))
+        self.lambda_mmd = float(lambda_mmd)
+
+    def bce(self) -> torch.Tensor:
+        """mean BCE (0-d device tensor)"""
+        return self.sums[0] / self.bce_div
+
+    def mmd(self) -> torch.Tensor:
+        """MMD(prior samples, z) (0-d device tensor)"""
+        return self.sums[15]
+
+    def mmd_terms(self) -> torch.Tensor:
+        """{mean Kxx, mean Kyy, mean Kxy, MMD}"""
+        return self.sums[self.MMD_SLOTS]
+
+    def total(self) -> torch.Tensor:
+        """lambda_x * mean BCE + lambda_mmd * MMD + kl_lambda * KL / B: the reference's one ``Loss:`` figure at its weights (1, 1, 0)"""
+        return self.losses()[0]
+
+    def losses(self) -> torch.Tensor:
+        out = super().losses()
+        out[0] += self.lambda_mmd * self.sums[15]
+        return out
+
+
+class FusedInfoVAEStep(_SinglePassStep):
+    """The step of coco/train_infovae.py:113-128 on the COCO plan: zero_grad -> ONE pass over B rows (image encoder, reparametrize,
+    image decoder) -> lambda_x * mean BCE + lambda_mmd * MMD(prior samples, z) + kl_lambda * KL / B -> backward -> Adam over the image
+    parameters, one enqueue (mmvae_coco_infovae_step: the image-only step with the MMD sweep beside the decoder).  ``state`` is a
+    ``CocoState``; the caption half keeps its values and gets a gradient of exactly 0.  The reference's loss is the default
+    (1, 1, 0)."""
+
+    _KIND = "InfoVAE"
+
+    def __init__(self, state: PlanState, batch: int, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
+                 lambda_x: float = 1.0, lambda_mmd: float = 1.0, kl_lambda: float = 0.0, seed: int = 1234):
+        if state.API != "coco":
+            raise MMVAEError("FusedInfoVAEStep: no InfoVAE step for the '%s' family (COCO has one)" % state.API)
+        super().__init__(state, batch, lr, betas, eps, seed)
+        self.lambda_x, self.lambda_mmd, self.kl_lambda = lambda_x, lambda_mmd, kl_lambda
+        self.enc_dropout = True
+        self.pixels = 3 * 32 * 32
+        self._image_range(state)
+
+    def _workspace_bytes(self, state: PlanState, batch: int) -> int:
+        return state._c("infovae_step_workspace_bytes", state.plan(batch))
+
+    def _outputs(self) -> InfoVAEStepOutputs:
+        return InfoVAEStepOutputs(self.sums, self.B * self.pixels, self.kl_lambda / self.B, self.lambda_x, self.lambda_mmd)
+
+    def forward_backward(self, image, training=True, backward=True, eps=None, enc_mask1=None, enc_mask2=None, true_samples=None,
+                         recon_image=None, mu=None, logvar=None, z=None, _defer_unpack=False) -> InfoVAEStepOutputs:
+        assert image.is_contiguous() and image.dtype == torch.float32
+        if tuple(image.shape) != (self.B, 3, 32, 32):
+            raise MMVAEError("FusedInfoVAEStep: expected images of shape %s (got %s)" % ((self.B, 3, 32, 32), tuple(image.shape)))
+        if true_samples is not None:
+            assert true_samples.is_contiguous() and true_samples.dtype == torch.float32 and tuple(true_samples.shape) == (self.B, self.D)
+        io = self._io(_lib.InfoVAEStepIO, (("image", image),),
+                      dict(eps=eps, enc_mask1=enc_mask1, enc_mask2=enc_mask2, true_samples=true_samples, recon_image=recon_image,
+                           mu=mu, logvar=logvar, z=z),
+                      backward, defer_unpack=_defer_unpack)
+        return self._step("mmvae_coco_infovae_step", io, training, backward)
 
 
 class FusedTextStep(_SinglePassStep):

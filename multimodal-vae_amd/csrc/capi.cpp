@@ -405,6 +405,13 @@ int mmvae_coco_image_step(mmvae_coco_t* p, const mmvae_image_step_io* io, int tr
     });
 }
 size_t mmvae_coco_image_step_workspace_bytes(const mmvae_coco_t* p) { return p ? coco_image_step_workspace_bytes(p) : 0; }
+int mmvae_coco_infovae_step(mmvae_coco_t* p, const mmvae_infovae_step_io* io, int training, int do_backward, void* stream) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_coco_infovae_step: null argument");
+        return coco_infovae_step(p, *io, training, do_backward, S(stream));
+    });
+}
+size_t mmvae_coco_infovae_step_workspace_bytes(const mmvae_coco_t* p) { return p ? coco_infovae_step_workspace_bytes(p) : 0; }
 int mmvae_coco_iw_score_image(mmvae_coco_t* p, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, void* st) {
     return guarded([&] { return coco_iw_score_image(p, ws, wsb, z, image, B, K, loglik_x, S(st)); });
 }
@@ -812,6 +819,18 @@ int mmvae_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* w
     if (!mmd_sizes_ok("mmd", n_x, n_y, dim)) return MMVAE_EINVAL;
     MMVAE_TRY(ws_fits("mmd", ws, ws_bytes, (long long)mmd_workspace_bytes(n_x, n_y, dim), false));
     return launch_mmd(x, n_x, y, n_y, dim, ws, out4, dx, dy, S(s));
+}
+long long mmvae_mmd_dy_workspace_bytes(int n_x, int n_y, int dim) {
+    if (n_x < 1 || n_x > MMD_MAX_N || n_y < 1 || n_y > MMD_MAX_N || dim < 1 || dim > MMD_MAX_DIM) return 0;
+    return (long long)mmd_dy_workspace_bytes(n_x, n_y, dim);
+}
+int mmvae_mmd_dy(const float* x, int n_x, const float* y, int n_y, int dim, void* ws, long long ws_bytes, float scale, float* out4, float* dy,
+                 int grad_y_only, void* s) {
+    MMVAE_REQUIRE(x && y && ws && out4, "mmd_dy: null argument");
+    MMVAE_REQUIRE(grad_y_only == 1, "mmd_dy: grad_y_only = %d, this entry computes the gradient for y alone (mmvae_mmd has both)", grad_y_only);
+    if (!mmd_sizes_ok("mmd_dy", n_x, n_y, dim)) return MMVAE_EINVAL;
+    MMVAE_TRY(ws_fits("mmd_dy", ws, ws_bytes, (long long)mmd_dy_workspace_bytes(n_x, n_y, dim), false));
+    return launch_mmd_dy(x, n_x, y, n_y, dim, ws, scale, out4, dy, S(s));
 }
 int mmvae_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, int dim, float* k, void* s) {
     MMVAE_REQUIRE(x && y && k, "mmd_kernel_matrix: null argument");

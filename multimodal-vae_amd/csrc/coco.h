@@ -16,6 +16,9 @@ int coco_step(CocoPlan*, const mmvae_coco_step_io&, int training, int do_backwar
 int coco_image_step(CocoPlan*, const mmvae_image_step_io&, int training, int do_backward, hipStream_t);
 size_t coco_image_step_workspace_bytes(const CocoPlan*);
 int coco_iw_score_image(CocoPlan*, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t);
+// InfoVAE (coco/model.py:358-402): the image-only step + lambda_mmd * MMD(prior samples, z) beside the decoder (img_tower.h TowerLatentTerm)
+int coco_infovae_step(CocoPlan*, const mmvae_infovae_step_io&, int training, int do_backward, hipStream_t);
+size_t coco_infovae_step_workspace_bytes(const CocoPlan*);
 // text-only VAE (coco/model.py:120-144): one pass over B rows in the one-pass carve, caption half only, and the squared error of the
 // particle rows' sentences alone
 int coco_text_step(CocoPlan*, const mmvae_text_step_io&, int training, int do_backward, hipStream_t);

@@ -385,6 +385,43 @@ size_t coco_image_step_workspace_bytes(const CocoPlan* P) { return P->ws_bytes_m
 int coco_image_step(CocoPlan* P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s) {
     return plan_step(P, io, training, do_backward, s, coco_image_step_body);
 }
+// ---------------------------------------------------------------- InfoVAE (coco/model.py:358-402, coco/train_infovae.py:44-55)
+// The image-only step with one more term in z: lambda_mmd * MMD(prior samples, z) (img_tower.h TowerLatentTerm).  Its workspace is the
+// one-pass carve followed by the term's own buffers: the sweep's float64 partial sums, lambda_mmd * dMMD/dz and the drawn prior samples.
+namespace {
+struct InfoVaeCarve { size_t ws_off, dz_off, drawn_off, total; };
+InfoVaeCarve infovae_carve(const CocoPlan* P) {
+    auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    InfoVaeCarve c;
+    c.ws_off = up16(P->ws_bytes_module);
+    c.dz_off = c.ws_off + up16(mmd_dy_workspace_bytes(P->B, P->B, P->D));
+    c.drawn_off = c.dz_off + up16((size_t)P->B * P->D * sizeof(float));
+    c.total = c.drawn_off + up16((size_t)P->B * P->D * sizeof(float));
+    return c;
+}
+int coco_infovae_step_body(CocoPlan* P, const mmvae_infovae_step_io& io, int training, int do_backward, hipStream_t s) {
+    MMVAE_REQUIRE((io.enc_mask1 == nullptr) == (io.enc_mask2 == nullptr), "mmvae_coco_infovae_step: enc_mask1 / enc_mask2 go together");
+    MMVAE_TRY(check_bound(P));
+    const InfoVaeCarve c = infovae_carve(P);
+    MMVAE_REQUIRE(io.ws != nullptr && io.ws_bytes >= c.total, "mmvae_coco_infovae_step: workspace too small (%zu < %zu)", io.ws_bytes, c.total);
+    MMVAE_REQUIRE((reinterpret_cast<uintptr_t>(io.ws) & 15) == 0, "mmvae_coco_infovae_step: the workspace must be 16-byte aligned");
+    MMVAE_TRY(use_ws(P, io.ws, io.ws_bytes));
+    mmvae_image_step_io im{};
+    im.ws = io.ws; im.ws_bytes = io.ws_bytes; im.step_counter = io.step_counter; im.image = io.image; im.eps = io.eps;
+    im.enc_mask1 = io.enc_mask1; im.enc_mask2 = io.enc_mask2; im.enc_dropout = io.enc_dropout; im.kl_lambda = io.kl_lambda;
+    im.lambda_x = io.lambda_x; im.seed = io.seed; im.sums = io.sums; im.recon_image = io.recon_image; im.mu = io.mu; im.logvar = io.logvar;
+    im.defer_unpack = io.defer_unpack;
+    char* base = (char*)io.ws;
+    TowerLatentTerm lt{};
+    lt.samples = io.true_samples; lt.drawn = (float*)(base + c.drawn_off); lt.philox_stream = MMVAE_TRUE_SAMPLES_STREAM;
+    lt.lambda = io.lambda_mmd; lt.ws = base + c.ws_off; lt.dz = (float*)(base + c.dz_off); lt.z_out = io.z; lt.slot = MMVAE_SUM_MMD_KXX;
+    return tower_image_step(*P, im, training, do_backward, s, CocoImageTail{}, &lt);
+}
+}  // namespace
+size_t coco_infovae_step_workspace_bytes(const CocoPlan* P) { return infovae_carve(P).total; }
+int coco_infovae_step(CocoPlan* P, const mmvae_infovae_step_io& io, int training, int do_backward, hipStream_t s) {
+    return plan_step(P, io, training, do_backward, s, coco_infovae_step_body);
+}
 // log p(x | z) of the particle rows alone: coco_iw_score without the caption decoder (the same, smaller, carve)
 int coco_iw_score_image(CocoPlan* P, void* ws, size_t wsb, const float* z, const float* image, int B, int K, float* loglik_x, hipStream_t s) {
     MMVAE_REQUIRE(P && z && image && loglik_x, "mmvae_coco_iw_score_image: null argument");
@@ -711,6 +748,11 @@ int coco_bench_layer(CocoPlan* P, void* ws, size_t wsb, const char* layer, int i
 // byte offset of a named workspace buffer of the fused step's carving (3 passes), -1 if unknown
 long long coco_debug_offset(CocoPlan* P, const char* name) {
     if (!P || !name) return -1;
+    if (std::strncmp(name, "infovae_step:", 13) == 0) {      // the InfoVAE step's own buffers behind the one-pass carve
+        const InfoVaeCarve c = infovae_carve(P);
+        const std::string n = name + 13;
+        return n == "mmd_ws" ? (long long)c.ws_off : n == "dz_mmd" ? (long long)c.dz_off : n == "true_samples" ? (long long)c.drawn_off : -1;
+    }
     Workspace ws((void*)0x1000, (size_t)1 << 40);      // (every call that works in a workspace carves its own again: plan_use_ws)
     P->carve_passes = 3; P->carve_iw = false;
     carve(*P, ws);

@@ -150,6 +150,7 @@ struct Latent1BwdArgs {
     float* d_bias;           // [2D] += column sums of the fp32 gradient (the bias of the classifier's last Linear), or null
     const float* loss_slots; // optional, as Latent3BwdArgs: [MMVAE_LOSS_SLOTS][16] summed into loss_out[16]
     float* loss_out;
+    const float* dz2;        // [B][D] or null: the gradient of a second term in z (the InfoVAE step's MMD), added to dz in float64
 };
 int launch_latent1_bwd(const Latent1BwdArgs& a, hipStream_t s);
 // The same gradient in fp32, for an encoder whose backward takes fp32 (the COCO caption encoder, coco_text_enc_bwd): every element is
@@ -207,6 +208,8 @@ struct StepBeginArgs {
     void* zero_ptr[4]; size_t zero_bytes[4];      // multiples of 16 bytes, 16-byte aligned (unused: null/0)
     float* eps; long long n_eps;                  // null -> not drawn
     uint8_t* mask[3]; long long n_mask[3];        // null -> not drawn
+    float* normal2; long long n_normal2; unsigned normal2_stream;   // a second N(0,1) draw on a Philox stream of its own (null -> not
+                                                  // drawn): the values launch_normal gives for (seed, step, that stream)
     float p;
     unsigned long long seed; const long long* step;
     // optional: the weight pack of the previous optimizer step rides in the same launch (step_begin_with_pack)

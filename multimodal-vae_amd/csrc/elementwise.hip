@@ -487,11 +487,13 @@ __global__ __launch_bounds__(TPB) void kl_bwd_kernel(const float* mu, const floa
     if (i < n) { dmu[i] = coef * mu[i]; dlv[i] = -0.5f * coef * (1.0f - exp_unfused(lv[i])); }
 }
 
-__global__ __launch_bounds__(TPB) void normal_kernel(float* out, long long n, unsigned long long seed, const long long* step, unsigned stream_id) {
-    const unsigned long long st = step ? (unsigned long long)*step : 0ull;
-    for (long long q = (long long)blockIdx.x * TPB + threadIdx.x; q * 4 < n; q += (long long)gridDim.x * TPB) {
+// out[0 .. n) ~ N(0, 1): Philox counter q gives the 4 values of elements 4 q .. 4 q + 3 (Box-Muller), threads stride over q.  ONE
+// definition for normal_kernel and the draws of the step prologue: the same (key, stream) give the same bits in either.
+__device__ __forceinline__ void draw_normals(float* __restrict__ out, long long n, unsigned long long key, unsigned stream_id, long long first,
+                                             long long stride) {
+    for (long long q = first; q * 4 < n; q += stride) {
         uint32_t r[4];
-        Philox::gen(seed ^ (st * 0x9E3779B97F4A7C15ull), (uint64_t)q, stream_id, r);
+        Philox::gen(key, (uint64_t)q, stream_id, r);
         float u0 = u01(r[0]), u1 = u01(r[1]), u2 = u01(r[2]), u3 = u01(r[3]);
         float m0 = sqrtf(-2.0f * logf(u0)), m1 = sqrtf(-2.0f * logf(u2));
         float v[4] = {m0 * cosf(6.28318530718f * u1), m0 * sinf(6.28318530718f * u1),
@@ -499,6 +501,10 @@ __global__ __launch_bounds__(TPB) void normal_kernel(float* out, long long n, un
         for (int j = 0; j < 4; ++j)
             if (q * 4 + j < n) out[q * 4 + j] = v[j];
     }
+}
+__global__ __launch_bounds__(TPB) void normal_kernel(float* out, long long n, unsigned long long seed, const long long* step, unsigned stream_id) {
+    const unsigned long long st = step ? (unsigned long long)*step : 0ull;
+    draw_normals(out, n, seed ^ (st * 0x9E3779B97F4A7C15ull), stream_id, (long long)blockIdx.x * TPB + threadIdx.x, (long long)gridDim.x * TPB);
 }
 __global__ __launch_bounds__(TPB) void keep_mask_kernel(uint8_t* out, long long n, float p, unsigned long long seed, const long long* step, unsigned stream_id) {
     const unsigned long long st = step ? (unsigned long long)*step : 0ull;
@@ -534,18 +540,8 @@ __global__ __launch_bounds__(TPB) void step_begin_kernel(const StepBeginArgs a) 
     }
     const unsigned long long st = a.step ? (unsigned long long)*a.step : 0ull;
     const unsigned long long key = a.seed ^ (st * 0x9E3779B97F4A7C15ull);
-    if (a.eps) {
-        for (long long q = gtid; q * 4 < a.n_eps; q += gstride) {
-            uint32_t r[4];
-            Philox::gen(key, (uint64_t)q, 1, r);
-            float u0 = u01(r[0]), u1 = u01(r[1]), u2 = u01(r[2]), u3 = u01(r[3]);
-            float m0 = sqrtf(-2.0f * logf(u0)), m1 = sqrtf(-2.0f * logf(u2));
-            float v[4] = {m0 * cosf(6.28318530718f * u1), m0 * sinf(6.28318530718f * u1),
-                          m1 * cosf(6.28318530718f * u3), m1 * sinf(6.28318530718f * u3)};
-            for (int j = 0; j < 4; ++j)
-                if (q * 4 + j < a.n_eps) a.eps[q * 4 + j] = v[j];
-        }
-    }
+    if (a.eps) draw_normals(a.eps, a.n_eps, key, 1, gtid, gstride);
+    if (a.normal2) draw_normals(a.normal2, a.n_normal2, key, a.normal2_stream, gtid, gstride);
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
         if (!a.mask[m]) continue;
@@ -773,7 +769,8 @@ __global__ __launch_bounds__(TPB) void latent1_bwd_kernel(const Latent1BwdArgs a
     for (int b = blockIdx.y * LATENT1_BWD_ROWS + ty; b < b_end; b += 4) {
         if (d < f.D) {
             const int e = b * f.D + d;
-            const double dz = a.dz ? (double)a.dz[e] : 0.0;
+            double dz = a.dz ? (double)a.dz[e] : 0.0;
+            if (a.dz2) dz += (double)a.dz2[e];
             const double mu = f.mu[e], lv = f.logvar[e], kc = a.kl_coef;
             const double gmu = dz + kc * mu;
             double glv = -0.5 * kc * (1.0 - exp(lv));
@@ -1368,6 +1365,7 @@ int launch_step_begin(const StepBeginArgs& a, hipStream_t s) {
     for (int r = 0; r < 4; ++r)
         if (a.zero_ptr[r]) items += (long long)(a.zero_bytes[r] / 16);
     if (a.eps) items += (a.n_eps + 3) / 4;
+    if (a.normal2) items += (a.n_normal2 + 3) / 4;
     for (int m = 0; m < 3; ++m)
         if (a.mask[m]) items += (a.n_mask[m] + 3) / 4;
     const int cap = mmvae_knob(K_begin_blocks);

@@ -10,6 +10,7 @@
 #include "plan_base.h"
 #include "thin.h"
 #include "iw.h"
+#include "mmd.h"
 #include "../../include/mmvae_hip.h"
 #include <map>
 #include <string>
@@ -460,8 +461,26 @@ inline IwTailArgs tower_iw_tail_args(TowerPlan& P, const float* image, int rows,
 //   mask_width[2]                   widths of the classifier's Dropout layers (0: the family has no second one)
 //   last_bias(P)                    offset of the bias of the classifier's last Linear in the flat buffers
 //   enc_fwd(P, image, m1, m2, drop, training, out, s) / enc_bwd(P, d_out, m1, m2, drop, s)      one variant
+//
+// `lt` (optional): an extra loss term in the latent sample beside the reconstruction and the KL term -- the InfoVAE step's
+// lambda * MMD(prior samples, z), coco/train_infovae.py:44-55.  It needs z, which is ready right behind the latent block, and its
+// gradient is needed only by the latent block's backward; the decoder's forward and backward run in between.  So the sweep and its
+// fold (mmd.h launch_mmd_dy: gradient for z alone) go to the plan's first side stream, which this step leaves idle (there is no second
+// modality), and the main stream waits for them once, in front of the latent block's backward, which adds lt->dz to the decoder's dz
+// (Latent1BwdArgs::dz2).  MMVAE_SERIAL: in order on the caller's stream.  Without `lt` the step launches what it always launched.
+struct TowerLatentTerm {
+    const float* samples;    // [B][D] prior samples, or null: drawn into `drawn` by the step's prologue on Philox stream `philox_stream`
+    float* drawn;            // [B][D]
+    unsigned philox_stream;
+    float lambda;            // weight of the term (0: the value is still reported, no gradient)
+    void* ws;                // mmd_dy_workspace_bytes(B, B, D) bytes, 8-byte aligned
+    float* dz;               // [B][D]: lambda * dMMD/dz
+    float* z_out;            // [B][D] or null: where z goes instead of the workspace
+    int slot;                // first of the 4 loss slots {mean Kxx, mean Kyy, mean Kxy, MMD} (row 0 of the slot table, zero elsewhere)
+};
 template <class Plan, class Fam>
-int tower_image_step(Plan& P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s, const Fam& fam) {
+int tower_image_step(Plan& P, const mmvae_image_step_io& io, int training, int do_backward, hipStream_t s, const Fam& fam,
+                     const TowerLatentTerm* lt = nullptr) {
     typename Plan::W& w = P.w;
     const TowerGeom& G = P.geo;
     const int B = P.B, D = P.D, npix = 3 * G.img * G.img;
@@ -480,6 +499,12 @@ int tower_image_step(Plan& P, const mmvae_image_step_io& io, int training, int d
     if (training && !eps) { sb.eps = w.eps; sb.n_eps = (long long)B * D; eps = w.eps; }
     if (enc_drop && !m1) { sb.mask[0] = w.m1; sb.n_mask[0] = (long long)B * fam.mask_width[0]; m1 = w.m1; }
     if (enc_drop && fam.mask_width[1] && !m2) { sb.mask[1] = fam.m2(P); sb.n_mask[1] = (long long)B * fam.mask_width[1]; m2 = fam.m2(P); }
+    const float* prior = nullptr;
+    if (lt) {
+        MMVAE_REQUIRE(B <= MMD_MAX_N && lt->ws && lt->dz && lt->drawn, "image step: the latent term needs its workspace and a batch of at most %d", (int)MMD_MAX_N);
+        prior = lt->samples;
+        if (!prior) { sb.normal2 = lt->drawn; sb.n_normal2 = (long long)B * D; sb.normal2_stream = lt->philox_stream; prior = lt->drawn; }
+    }
     MMVAE_TRY(launch_step_begin(sb, s));
     if (do_backward && P.nparams % 4 != 0)
         MMVAE_TRY(launch_fill_zero(P.buf.grads + (P.nparams / 4) * 4, (size_t)(P.nparams % 4) * sizeof(float), s));
@@ -488,15 +513,22 @@ int tower_image_step(Plan& P, const mmvae_image_step_io& io, int training, int d
     Latent1Args la{};
     la.B = B; la.D = D; la.enc_out = w.encout; la.eps = eps;
     la.mu = io.mu ? io.mu : w.mu; la.logvar = io.logvar ? io.logvar : w.logvar;
-    la.z_f32 = w.z_f32; la.z_bf = w.z_bf; la.ldz = P.ldz; la.kl_sum = w.sums + 8; la.training = training;
+    la.z_f32 = (lt && lt->z_out) ? lt->z_out : w.z_f32; la.z_bf = w.z_bf; la.ldz = P.ldz; la.kl_sum = w.sums + 8; la.training = training;
     la.scratch = w.tmp_f32;         // (the module decoder's sigmoid-backward buffer: nobody else's in this step)
     MMVAE_TRY(launch_latent1_fwd(la, s));
+    hipStream_t Sm = s;             // where the latent term runs
+    const bool lt_grad = lt && do_backward && lt->lambda != 0.f;        // (a zero weight has exactly no gradient)
+    if (lt) {
+        if (!mmvae_serial()) { Sm = P.st_text; MMVAE_TRY(edge(P, s, Sm)); }
+        MMVAE_TRY(launch_mmd_dy(prior, B, la.z_f32, B, D, lt->ws, lt->lambda, w.sums + lt->slot, lt_grad ? lt->dz : nullptr, Sm));
+    }
     ConvTLastFwdArgs last{};
     last.target = io.image; last.recon = io.recon_image; last.dlogit = do_backward ? w.dlogit : nullptr; last.loss_sum = w.sums;
     last.coef[0] = io.lambda_x / (float)(B * npix);
     MMVAE_TRY(tower_dec_fwd(P, 1, training, true, s));
     MMVAE_TRY(launch_convt_last_fwd(dec_last_args(P, last, 1), s));
     if (!do_backward) {
+        if (Sm != s) MMVAE_TRY(edge(P, Sm, s));
         hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, s, w.sums, io.sums);
         return mmvae_check_launch("sum_slots");
     }
@@ -505,8 +537,9 @@ int tower_image_step(Plan& P, const mmvae_image_step_io& io, int training, int d
     int rc = MMVAE_OK;
     const bool img_term = io.lambda_x != 0.f;        // (a zero weight has exactly no gradient)
     if (img_term) rc = tower_dec_bwd(P, w.dlogit, 1, w.dz_img, s);
+    if (rc == MMVAE_OK && Sm != s) rc = edge(P, Sm, s);      // the latent term's value and gradient
     Latent1BwdArgs lb{};
-    lb.f = la; lb.dz = img_term ? w.dz_img : nullptr; lb.kl_coef = io.kl_lambda / (float)B;
+    lb.f = la; lb.dz = img_term ? w.dz_img : nullptr; lb.dz2 = lt_grad ? lt->dz : nullptr; lb.kl_coef = io.kl_lambda / (float)B;
     lb.d_enc_out = w.d_encout; lb.ld = 2 * D; lb.d_bias = P.buf.grads + fam.last_bias(P);
     lb.loss_slots = w.sums; lb.loss_out = io.sums;      // (BCE and KL sums are final here)
     if (rc == MMVAE_OK) rc = launch_latent1_bwd(lb, s);

@@ -38,5 +38,13 @@ size_t mmd_workspace_bytes(int n_x, int n_y, int dim);
 // out4 = {mean Kxx, mean Kyy, mean Kxy, MMD}; dx [n_x][dim], dy [n_y][dim], each may be null (both null: the value alone, and
 // the y-rows-by-x-columns quarter of the pairs is skipped).  x == y is allowed.
 int launch_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* ws, float* out4, float* dx, float* dy, hipStream_t s);
+// The form a training step takes, where x are prior samples and only y = z has a gradient (coco/train_infovae.py:44-55): the same
+// grid, but the row tiles of x run the value form of the sweep -- their kernel sums feed Kxx and Kxy, no k * d products, no gradient
+// partials -- so about half of the gradient arithmetic and of the gradient workspace goes.  Per pair, per 8 columns, per split and
+// in the fold the arithmetic and its order are launch_mmd's: out4 and (scale = 1) dy carry the bits launch_mmd writes.
+// dy [n_y][dim] = scale * dMMD/dy (the product in float64, rounded once), or null: the value alone.  out4 may point anywhere 4 floats
+// fit (a step's loss slots).  Workspace: [sx + sy][rpad] float64 kernel sums, then [sx + sy][rty * MMD_RT][dim] gradient sums.
+size_t mmd_dy_workspace_bytes(int n_x, int n_y, int dim);
+int launch_mmd_dy(const float* x, int n_x, const float* y, int n_y, int dim, void* ws, float scale, float* out4, float* dy, hipStream_t s);
 // k [n_x][n_y] = k(x_i, y_j), the arithmetic of launch_mmd per pair
 int launch_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, int dim, float* k, hipStream_t s);

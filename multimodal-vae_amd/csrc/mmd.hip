@@ -56,7 +56,11 @@ __device__ __forceinline__ float pair_kernel(float sq, float fD) { return expf(-
 // ---------------------------------------------------------------------------------------------- the sweep
 // grid (row tiles of x then of y, splits over x's column tiles then over y's).  Split c of a class's Sc covers its tiles
 // [T c / Sc, T (c + 1) / Sc).
-template <int M, bool GRAD>
+// GRAD: MMD_VALUE no gradient sums | MMD_GRAD_XY both classes' | MMD_GRAD_Y the y rows' alone (mmd.h launch_mmd_dy): the x row tiles run
+// the value form (kernel sums, no k * d work, nothing written to Gp), the y row tiles the gradient form into a Gp of y's rows only.
+// The branch is uniform per workgroup; per pair, per 8 columns and per split the arithmetic and its order are the same in every mode.
+enum { MMD_VALUE = 0, MMD_GRAD_XY = 1, MMD_GRAD_Y = 2 };
+template <int M, int MODE>
 __global__ __launch_bounds__(NTHR) void mmd_pairs_kernel(const float* __restrict__ X, int nx, const float* __restrict__ Y, int ny, int D,
                                                          int rtx, int tx, int ty, int sx, long long rpad,
                                                          double* __restrict__ Sp, double* __restrict__ Gp) {
@@ -65,7 +69,8 @@ __global__ __launch_bounds__(NTHR) void mmd_pairs_kernel(const float* __restrict
     const int tid = threadIdx.x, q = tid & 3, il = tid >> 2;
     const int rt = blockIdx.x, sp = blockIdx.y, S = gridDim.y;
     const bool rowy = rt >= rtx, coly = sp >= sx;
-    if (!GRAD && rowy && !coly) return;                           // k(y_j, x_i) = k(x_i, y_j): only the gradient needs this quarter
+    const bool GRAD = MODE == MMD_GRAD_XY || (MODE == MMD_GRAD_Y && rowy);
+    if (MODE == MMD_VALUE && rowy && !coly) return;                           // k(y_j, x_i) = k(x_i, y_j): only the gradient needs this quarter
     const float* R = rowy ? Y : X;
     const float* C = coly ? Y : X;
     const int nr = rowy ? ny : nx, nc = coly ? ny : nx;
@@ -122,8 +127,9 @@ __global__ __launch_bounds__(NTHR) void mmd_pairs_kernel(const float* __restrict
     }
 
     if (rok) {
-        const size_t slot = (size_t)sp * (size_t)rpad + (size_t)rt * RT + il;      // < (sx + sy) * rpad
+        size_t slot = (size_t)sp * (size_t)rpad + (size_t)rt * RT + il;            // < (sx + sy) * rpad
         if (q == 0) Sp[slot] = ss;
+        if (MODE == MMD_GRAD_Y) slot = (size_t)sp * ((size_t)rpad - (size_t)rtx * RT) + (size_t)(rt - rtx) * RT + il;   // y's rows alone
         if (GRAD) {
 #pragma unroll
             for (int m = 0; m < M; ++m)
@@ -138,54 +144,74 @@ __global__ __launch_bounds__(NTHR) void mmd_pairs_kernel(const float* __restrict
 
 // ---------------------------------------------------------------------------------------------- the fold
 // block 0: the three means and MMD; blocks 1..: one gradient element per thread.  Everything in float64, splits in ascending order.
+// the three means and MMD by one workgroup: out4 = {mean Kxx, mean Kyy, mean Kxy, MMD}
+__device__ __forceinline__ void fold_values(const double* __restrict__ Sp, int nx, int ny, int rtx, int sx, int S, long long rpad,
+                                            double (&red)[3][NTHR], float* __restrict__ out4) {
+    const int tid = threadIdx.x;
+    double axx = 0.0, axy = 0.0, ayy = 0.0;
+    for (long long i = tid; i < (long long)nx * S; i += NTHR) {
+        const int s = (int)(i / nx), row = (int)(i - (long long)s * nx);
+        const double v = Sp[(size_t)s * rpad + row];
+        if (s < sx) axx += v; else axy += v;
+    }
+    for (long long i = tid; i < (long long)ny * (S - sx); i += NTHR) {
+        const int s = (int)(i / ny), row = (int)(i - (long long)s * ny);
+        ayy += Sp[(size_t)(sx + s) * rpad + (size_t)rtx * RT + row];
+    }
+    red[0][tid] = axx; red[1][tid] = ayy; red[2][tid] = axy;
+    __syncthreads();
+    for (int o = NTHR / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) red[c][tid] += red[c][tid + o];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double kxx = red[0][0] / ((double)nx * (double)nx), kyy = red[1][0] / ((double)ny * (double)ny);
+        const double kxy = red[2][0] / ((double)nx * (double)ny);
+        out4[0] = (float)kxx; out4[1] = (float)kyy; out4[2] = (float)kxy;
+        out4[3] = (float)((kxx + kyy) - 2.0 * kxy);
+    }
+}
+// one gradient element of row `row` of class rowy: G = the [S][prows][D] partial sums, prow the row's place in a split's slab
+__device__ __forceinline__ double fold_grad(const double* __restrict__ G, size_t prows, size_t prow, int e, bool rowy, int nx, int ny, int D,
+                                            int sx, int S) {
+    double a = 0.0, b = 0.0;                                      // sums against x's columns, against y's
+    for (int s = 0; s < sx; ++s) a += G[((size_t)s * prows + prow) * D + e];
+    for (int s = sx; s < S; ++s) b += G[((size_t)s * prows + prow) * D + e];
+    const double dd = (double)D * (double)D, na = rowy ? ny : nx;
+    const double same = -4.0 / (na * na * dd), cross = 4.0 / ((double)nx * (double)ny * dd);
+    return rowy ? cross * a + same * b : same * a + cross * b;
+}
 __global__ __launch_bounds__(NTHR) void mmd_fold_kernel(const double* __restrict__ Sp, const double* __restrict__ Gp, int nx, int ny, int D,
                                                         int rtx, int sx, int S, long long rpad, bool grad, float* __restrict__ out4,
                                                         float* __restrict__ dx, float* __restrict__ dy) {
     __shared__ double red[3][NTHR];
-    const int tid = threadIdx.x;
-    if (blockIdx.x == 0) {
-        double axx = 0.0, axy = 0.0, ayy = 0.0;
-        for (long long i = tid; i < (long long)nx * S; i += NTHR) {
-            const int s = (int)(i / nx), row = (int)(i - (long long)s * nx);
-            const double v = Sp[(size_t)s * rpad + row];
-            if (s < sx) axx += v; else axy += v;
-        }
-        for (long long i = tid; i < (long long)ny * (S - sx); i += NTHR) {
-            const int s = (int)(i / ny), row = (int)(i - (long long)s * ny);
-            ayy += Sp[(size_t)(sx + s) * rpad + (size_t)rtx * RT + row];
-        }
-        red[0][tid] = axx; red[1][tid] = ayy; red[2][tid] = axy;
-        __syncthreads();
-        for (int o = NTHR / 2; o > 0; o >>= 1) {
-            if (tid < o) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) red[c][tid] += red[c][tid + o];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            const double kxx = red[0][0] / ((double)nx * (double)nx), kyy = red[1][0] / ((double)ny * (double)ny);
-            const double kxy = red[2][0] / ((double)nx * (double)ny);
-            out4[0] = (float)kxx; out4[1] = (float)kyy; out4[2] = (float)kxy;
-            out4[3] = (float)((kxx + kyy) - 2.0 * kxy);
-        }
-        return;
-    }
+    if (blockIdx.x == 0) { fold_values(Sp, nx, ny, rtx, sx, S, rpad, red, out4); return; }
     if (!grad) return;
-    const long long gid = (long long)(blockIdx.x - 1) * NTHR + tid;
+    const long long gid = (long long)(blockIdx.x - 1) * NTHR + threadIdx.x;
     if (gid >= (long long)(nx + ny) * D) return;
     const int z = (int)(gid / D), e = (int)(gid - (long long)z * D);
     const bool rowy = z >= nx;
     const int row = rowy ? z - nx : z;
     const size_t prow = (rowy ? (size_t)rtx * RT : 0) + row;
-    double a = 0.0, b = 0.0;                                      // sums against x's columns, against y's
-    for (int s = 0; s < sx; ++s) a += Gp[((size_t)s * rpad + prow) * D + e];
-    for (int s = sx; s < S; ++s) b += Gp[((size_t)s * rpad + prow) * D + e];
-    const double dd = (double)D * (double)D, na = rowy ? ny : nx;
-    const double same = -4.0 / (na * na * dd), cross = 4.0 / ((double)nx * (double)ny * dd);
-    const double g = rowy ? cross * a + same * b : same * a + cross * b;
+    const double g = fold_grad(Gp, (size_t)rpad, prow, e, rowy, nx, ny, D, sx, S);
     float* out = rowy ? dy : dx;
     if (out) out[(size_t)row * D + e] = (float)g;
+}
+// The fold behind the MMD_GRAD_Y sweep (Gy: [S][rty * RT][D], y's rows alone).  Block 0: the values, as above; blocks 1..: dy =
+// scale * dMMD/dy, the product taken in float64 and rounded once (scale = 1: the bits of mmd_fold_kernel's dy).  dy may be null.
+__global__ __launch_bounds__(NTHR) void mmd_fold_y_kernel(const double* __restrict__ Sp, const double* __restrict__ Gy, int nx, int ny, int D,
+                                                          int rtx, int sx, int S, long long rpad, float scale, float* __restrict__ out4,
+                                                          float* __restrict__ dy) {
+    __shared__ double red[3][NTHR];
+    if (blockIdx.x == 0) { fold_values(Sp, nx, ny, rtx, sx, S, rpad, red, out4); return; }
+    const long long gid = (long long)(blockIdx.x - 1) * NTHR + threadIdx.x;
+    if (!dy || gid >= (long long)ny * D) return;
+    const int row = (int)(gid / D), e = (int)(gid - (long long)row * D);
+    const double g = fold_grad(Gy, (size_t)rpad - (size_t)rtx * RT, (size_t)row, e, true, nx, ny, D, sx, S);
+    dy[gid] = (float)(g * (double)scale);
 }
 
 // ---------------------------------------------------------------------------------------------- the kernel matrix
@@ -213,7 +239,7 @@ __global__ __launch_bounds__(NTHR) void mmd_kernel_matrix_kernel(const float* __
 
 inline int steps_of(int dim) { return (ceil_div(dim, 4) + 3) / 4; }          // M: 1..16 for dim 1..256
 
-template <int M, bool GRAD>
+template <int M, int GRAD>
 void launch_pairs(const MmdShape& g, const float* x, int nx, const float* y, int ny, int D, double* Sp, double* Gp, hipStream_t s) {
     constexpr int LDS_BYTES = 2 * CT * 16 * M * (int)sizeof(float);            // at most 64 KB (M = 16)
     MMVAE_LAUNCH((mmd_pairs_kernel<M, GRAD>), dim3(g.rtx + g.rty, g.sx + g.sy), dim3(NTHR), LDS_BYTES, s, x, nx, y, ny, D, g.rtx, g.tx,
@@ -255,8 +281,8 @@ int launch_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* 
     switch (steps_of(dim)) {
 #define MMD_CASE(m)                                                                              \
     case m:                                                                                      \
-        if (grad) launch_pairs<m, true>(g, x, n_x, y, n_y, dim, Sp, Gp, s);                      \
-        else launch_pairs<m, false>(g, x, n_x, y, n_y, dim, Sp, Gp, s);                          \
+        if (grad) launch_pairs<m, MMD_GRAD_XY>(g, x, n_x, y, n_y, dim, Sp, Gp, s);               \
+        else launch_pairs<m, MMD_VALUE>(g, x, n_x, y, n_y, dim, Sp, Gp, s);                      \
         break;
         MMD_FOR_M(MMD_CASE)
 #undef MMD_CASE
@@ -267,6 +293,34 @@ int launch_mmd(const float* x, int n_x, const float* y, int n_y, int dim, void* 
     MMVAE_LAUNCH(mmd_fold_kernel, dim3((unsigned)(1 + (elems + NTHR - 1) / NTHR)), dim3(NTHR), 0, s, Sp, Gp, n_x, n_y, dim, g.rtx, g.sx, S,
                  g.rpad, grad, out4, dx, dy);
     return mmvae_check_launch("mmd_fold");
+}
+
+size_t mmd_dy_workspace_bytes(int n_x, int n_y, int dim) {
+    const MmdShape g = mmd_shape(n_x, n_y);
+    return (size_t)(g.sx + g.sy) * ((size_t)g.rpad + (size_t)g.rty * RT * (size_t)dim) * sizeof(double);
+}
+
+int launch_mmd_dy(const float* x, int n_x, const float* y, int n_y, int dim, void* ws, float scale, float* out4, float* dy, hipStream_t s) {
+    MMVAE_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "mmd_dy: the workspace must be 8-byte aligned");
+    const MmdShape g = mmd_shape(n_x, n_y);
+    const int S = g.sx + g.sy;
+    double* Sp = reinterpret_cast<double*>(ws);
+    double* Gy = Sp + (size_t)S * (size_t)g.rpad;
+    switch (steps_of(dim)) {
+#define MMD_CASE(m)                                                                              \
+    case m:                                                                                      \
+        if (dy) launch_pairs<m, MMD_GRAD_Y>(g, x, n_x, y, n_y, dim, Sp, Gy, s);                  \
+        else launch_pairs<m, MMD_VALUE>(g, x, n_x, y, n_y, dim, Sp, Gy, s);                      \
+        break;
+        MMD_FOR_M(MMD_CASE)
+#undef MMD_CASE
+        default: MMVAE_REQUIRE(false, "mmd_dy: dim = %d", dim);
+    }
+    MMVAE_TRY(mmvae_check_launch("mmd_pairs_y"));
+    const long long elems = dy ? (long long)n_y * dim : 0;
+    MMVAE_LAUNCH(mmd_fold_y_kernel, dim3((unsigned)(1 + (elems + NTHR - 1) / NTHR)), dim3(NTHR), 0, s, Sp, Gy, n_x, n_y, dim, g.rtx, g.sx, S,
+                 g.rpad, scale, out4, dy);
+    return mmvae_check_launch("mmd_fold_y");
 }
 
 int launch_mmd_kernel_matrix(const float* x, int n_x, const float* y, int n_y, int dim, float* k, hipStream_t s) {

@@ -4,9 +4,12 @@ Mirrors the command line (``coco/train_infovae.py:61-72``: ``--n_latents 100 --b
 --log_interval 10 --cuda``), the train / test loops with their printed lines (``:113-147``) and the checkpoint dict
 (``:158-163``: ``state_dict``, ``best_loss``, ``n_latents``, ``optimizer``) of the reference.  The model is ``coco.InfoVAE`` (the HIP
 image encoder and decoder), the loss ``coco.infovae_loss`` (BCE kernel + the fused MMD op), the optimizer ``torch.optim.Adam`` over
-the module's own parameters, as in the reference.
+the module's own parameters, as in the reference.  With ``--fused`` the model is ``coco.FusedInfoVAE`` and the batch loop body is ONE
+enqueue (``coco.InfoVAETrainer``: the one-pass image step with the MMD sweep beside the decoder and the packed-gradient Adam): the
+same flags, printed lines, samples and checkpoint keys; whole batches only (a short last batch is dropped, the plan has one size).
 
     python -m multimodal_vae_amd.train_infovae --cuda --epochs 2 --synthetic 4096      # no data files needed
+    python -m multimodal_vae_amd.train_infovae --cuda --fused --epochs 2 --synthetic 4096
 
 Inputs, as ``train_coco``: ``--data DIR`` with ``images_u8.pt`` ((N,3,32,32) uint8: Scale(32) + CenterCrop(32); the captions are
 not read) or ``--synthetic N``.  The images stay on the device as uint8; a batch is a gather of a device permutation + ToTensor.
@@ -22,6 +25,7 @@ import sys
 import torch
 
 from .train import AverageMeter, save_checkpoint
+from .train_common import adam_state_dict, eval_epoch, train_epoch
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -39,14 +43,17 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--out', type=str, default='./trained_models', help='checkpoints go to OUT/infovae (reference: ./trained_models/infovae)')
     parser.add_argument('--results', type=str, default='', help='folder for per-epoch sample dumps (off when empty)')
     parser.add_argument('--seed', type=int, default=1234)
+    parser.add_argument('--fused', action='store_true', default=False,
+                        help='train a FusedInfoVAE with the one-enqueue step (InfoVAETrainer) instead of modules + torch.optim.Adam')
     return parser
 
 
-def load_checkpoint(file_path, use_cuda=False):
-    """coco/train_infovae.py:30-41: rebuilds an InfoVAE from the checkpoint dict this driver (or the reference) writes."""
-    from .coco import InfoVAE
+def load_checkpoint(file_path, use_cuda=False, fused=False):
+    """coco/train_infovae.py:30-41: rebuilds an InfoVAE (``fused``: a FusedInfoVAE) from the checkpoint dict this driver writes on
+    either route, or the reference's: the two classes have the same state-dict keys."""
+    from .coco import FusedInfoVAE, InfoVAE
     checkpoint = torch.load(file_path, map_location=None if use_cuda else 'cpu', weights_only=False)
-    vae = InfoVAE(n_latents=checkpoint['n_latents'])
+    vae = (FusedInfoVAE if fused else InfoVAE)(n_latents=checkpoint['n_latents'])
     vae.load_state_dict(checkpoint['state_dict'])
     if use_cuda:
         vae.cuda()
@@ -82,7 +89,6 @@ def main(argv=None) -> dict:
     args.cuda = args.cuda and torch.cuda.is_available()
     if not args.cuda:
         raise SystemExit("this engine runs on a gfx950 GPU only: pass --cuda on a machine that has one (no CPU fallback)")
-    from .coco import InfoVAE, infovae_loss
     from .train_coco import synthetic_coco
 
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -95,6 +101,36 @@ def main(argv=None) -> dict:
         tr_x = torch.load(os.path.join(args.data, "images_u8.pt"))
         n_test = max(args.batch_size, len(tr_x) // 10)
         te_x, tr_x = tr_x[:n_test], tr_x[n_test:]
+    vae, train, test, optimizer_state = (_fused_route if args.fused else _module_route)(args, dev, tr_x, te_x)
+
+    folder = os.path.join(args.out, 'infovae')
+    best_loss = float(sys.maxsize)
+    history = {"train": [], "test": []}
+    for epoch in range(1, args.epochs + 1):
+        history["train"].append(train(epoch))
+        loss = test()
+        history["test"].append(loss)
+        is_best = loss < best_loss
+        best_loss = min(loss, best_loss)
+        save_checkpoint({
+            'state_dict': vae.state_dict(),
+            'best_loss': best_loss,
+            'n_latents': args.n_latents,
+            'optimizer': optimizer_state(),
+        }, is_best, folder=folder)
+        if args.results:
+            os.makedirs(args.results, exist_ok=True)
+            sample = torch.randn(64, args.n_latents, device=dev)
+            vae.eval()
+            with torch.no_grad():
+                torch.save(vae.decode(sample).cpu().view(64, 3, 32, 32), os.path.join(args.results, 'sample_epoch%d.pt' % epoch))
+    history["checkpoint"] = os.path.join(folder, 'checkpoint.pth.tar')
+    return history
+
+
+def _module_route(args, dev, tr_x, te_x):
+    """-> (vae, train(epoch), test(), optimizer_state()): ``InfoVAE`` + ``infovae_loss`` + ``torch.optim.Adam``, as the reference."""
+    from .coco import InfoVAE, infovae_loss
     train_loader = _DeviceImages(tr_x, args.batch_size, dev, shuffle=True, seed=args.seed)
     test_loader = _DeviceImages(te_x, args.batch_size, dev, shuffle=True, seed=args.seed + 7)
 
@@ -137,29 +173,39 @@ def main(argv=None) -> dict:
         print('====> Test set loss: {:.4f}'.format(test_loss))
         return test_loss
 
-    folder = os.path.join(args.out, 'infovae')
-    best_loss = float(sys.maxsize)
-    history = {"train": [], "test": []}
-    for epoch in range(1, args.epochs + 1):
-        history["train"].append(train(epoch))
-        loss = test()
-        history["test"].append(loss)
-        is_best = loss < best_loss
-        best_loss = min(loss, best_loss)
-        save_checkpoint({
-            'state_dict': vae.state_dict(),
-            'best_loss': best_loss,
-            'n_latents': args.n_latents,
-            'optimizer': optimizer.state_dict(),
-        }, is_best, folder=folder)
-        if args.results:
-            os.makedirs(args.results, exist_ok=True)
-            sample = torch.randn(64, args.n_latents, device=dev)
-            vae.eval()
-            with torch.no_grad():
-                torch.save(vae.decode(sample).cpu().view(64, 3, 32, 32), os.path.join(args.results, 'sample_epoch%d.pt' % epoch))
-    history["checkpoint"] = os.path.join(folder, 'checkpoint.pth.tar')
-    return history
+    return vae, train, test, optimizer.state_dict
+
+
+def _fused_route(args, dev, tr_x, te_x):
+    """-> (vae, train(epoch), test(), optimizer_state()): ``InfoVAETrainer`` on a ``FusedInfoVAE``, one enqueue per batch."""
+    from . import data as D
+    from .coco import FusedInfoVAE, InfoVAETrainer
+    for name, x in (("training", tr_x), ("test", te_x)):
+        if len(x) < args.batch_size:
+            raise SystemExit("the %s split has %d images, fewer than one batch of %d (the fused plan takes whole batches)"
+                             % (name, len(x), args.batch_size))
+    none = lambda x: torch.zeros(len(x), dtype=torch.int64)          # the batcher carries a second tensor: nothing reads it
+    train_loader = D.DeviceBatcher(tr_x, none(tr_x), args.batch_size, dev, shuffle=True, seed=args.seed)
+    test_loader = D.DeviceBatcher(te_x, none(te_x), args.batch_size, dev, shuffle=True, seed=args.seed + 7)
+    vae = FusedInfoVAE(n_latents=args.n_latents).cuda()
+    trainer = InfoVAETrainer(vae, args.batch_size, lr=args.lr, seed=args.seed)
+
+    def train(epoch):
+        vae.train()
+        avg, = train_epoch(
+            train_loader, lambda b: trainer(b[0]).total(), args.batch_size, args.log_interval,
+            lambda seen, n_total, pct, avg: 'Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(epoch, seen, n_total, pct, *avg),
+            len(train_loader) * args.batch_size)
+        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, avg))
+        return avg
+
+    def test():
+        vae.eval()
+        test_loss, = eval_epoch(test_loader, lambda b: trainer.evaluate(b[0]).total(), 1, dev)
+        print('====> Test set loss: {:.4f}'.format(test_loss))
+        return test_loss
+
+    return vae, train, test, lambda: adam_state_dict(vae, trainer.engine, own_only=True)
 
 
 if __name__ == "__main__":
