@@ -1044,6 +1044,65 @@ int mmvae_conv4s2_up(const float* src, const float* src_y_or_null, const float* 
 int mmvae_conv4s2_wgrad(const float* s_side, const float* l_side, const float* y_s_or_null, const float* y_l_or_null, int act, float slope,
                         float* dw, int batch, int cs, int cl, int hs, int ws, void* workspace, long long ws_bytes, void* stream);
 
+/* One fp32 Linear layer with a fused activation (csrc/infovae_mnist.h): y = act(x W^T + b), x [rows][K], W [N][K] (nn.Linear's
+ * layout), b [N], y [rows][N]; act 0 none, 1 relu, 2 leaky(slope).  Exact fp32 products and fp32 accumulation on
+ * v_mfma_f32_16x16x4_f32.  No atomics: two calls give identical bits, and a row's forward bits do not depend on the other rows.
+ *   fwd:    y = act(x W^T + b)
+ *   dgrad:  dx [rows][K] = gp W with gp = g (.) act'(y), formed from the upstream gradient g [rows][N] and the SAVED OUTPUT y while
+ *           the operand is loaded (relu: y > 0 ? g : 0; leaky: y > 0 ? g : slope g); y may be NULL when act = 0
+ *   wgrad:  dw [N][K] = gp^T x and db [N] = column sums of gp (NULL: not wanted), one launch, one writer per element
+ * perm = 1: the layer's 6272-wide side -- exactly one of N, K must be 6272 -- is kept channels-last, [rows][49][128], as conv4s2
+ * keeps it: feature c * 49 + p of the weight lives at p * 128 + c of x (K side) or of y, g (N side); dx of a K-side layer is
+ * written in that layout too.  The weight and its gradient stay in nn.Linear's order.
+ * rows 1..65536, N and K 1..65536, every pointer 16-byte aligned; anything else is refused (MMVAE_EINVAL) before a launch.  fwd and
+ * dgrad take device scratch of mmvae_lin_act_workspace_bytes(rows, N, K, which) bytes (which 0: fwd, 1: dgrad; 0 bytes: none needed,
+ * the pointer may be NULL); every byte a call reads of it it has written itself. */
+long long mmvae_lin_act_workspace_bytes(int rows, int n, int k, int which);
+int mmvae_lin_act_fwd(const float* x, const float* w, const float* b, float* y, int rows, int n, int k, int act, float slope, int perm,
+                      void* workspace, long long ws_bytes, void* stream);
+int mmvae_lin_act_dgrad(const float* g, const float* y_or_null, const float* w, float* dx, int rows, int n, int k, int act, float slope,
+                        int perm, void* workspace, long long ws_bytes, void* stream);
+int mmvae_lin_act_wgrad(const float* g, const float* y_or_null, const float* x, float* dw, float* db_or_null, int rows, int n, int k,
+                        int act, float slope, int perm, void* stream);
+
+/* MNIST InfoVAE (mnist/model.py:238-279, mnist/train_infovae.py:45-76) as one enqueue: zero_grad, forward, loss, backward.
+ *   loss = lambda_x * SSE / (B * 784) + lambda_mmd * MMD(true_samples, z)          (the reference: lambda_x = lambda_mmd = 1)
+ * A plan of its own, fp32, no packed weights: the 12 parameters are InfoVAE's state_dict in its order (mmvae_mnist_infovae_param_info),
+ * flat in `params`; every one of the 12 gradients is written to `grads` by each step with do_backward (no accumulation).  The
+ * optimizer is one mmvae_adam_step over the flat buffers, enqueued by the caller behind the step.  n_latents 1..256 (what mmvae_mmd
+ * takes), batch 1..65536; anything else: NULL, and mmvae_last_error names the range.
+ * The four convolutions are mmvae_conv4s2_* (bf16 operands), the four Linear layers mmvae_lin_act_* (fp32), the MMD term is the
+ * y-only sweep (mmvae_mmd_dy) with its fold on a side stream of the plan beside the decoder; weight gradients run on the shared side
+ * streams; MMVAE_SERIAL=1 puts everything in order on the caller's stream.  No host synchronisation, no allocation.
+ * sums [16]: [0] SSE = sum (recon - x)^2, [MMVAE_SUM_MMD_KXX .. MMVAE_SUM_MMD] = {mean Kxx, mean Kyy, mean Kxy, MMD}, bit for bit what
+ * mmvae_mmd returns for (true_samples, z); every other slot 0.  true_samples NULL: drawn by the step's prologue on Philox stream
+ * MMVAE_TRUE_SAMPLES_STREAM (the values of mmvae_normal for that stream, seed and step_counter).  do_backward = 0: stops behind the
+ * losses (the sweep in its value-only form), `grads` is not touched.  lambda_x = 0: the decoder's backward is skipped, its gradients
+ * are exactly 0 and the MMD gradient is the only dz.  lambda_mmd = 0: the value is reported, no gradient is formed.  The model has no
+ * BatchNorm, dropout or reparametrisation: `training` changes nothing.  An error inside the step joins the side streams and leaves
+ * the parameters untouched. */
+typedef struct MnistInfoVaePlan mmvae_mnist_infovae_t;
+typedef struct {
+    void* ws; size_t ws_bytes;              /* mmvae_mnist_infovae_step_workspace_bytes, 16-byte aligned */
+    const long long* step_counter;          /* device int64 keying the Philox stream, or NULL */
+    const float* image;                     /* [B][784] fp32 */
+    const float* true_samples;              /* [B][D] prior samples or NULL (drawn on the device) */
+    float lambda_x;
+    float lambda_mmd;
+    unsigned long long seed;
+    float* sums;                            /* out [16], see above */
+    float* recon_image;                     /* out [B][784] or NULL */
+    float* z;                               /* out [B][D] or NULL */
+} mmvae_mnist_infovae_step_io;
+mmvae_mnist_infovae_t* mmvae_mnist_infovae_create(int n_latents, int batch);
+void mmvae_mnist_infovae_destroy(mmvae_mnist_infovae_t*);
+long long mmvae_mnist_infovae_param_count(const mmvae_mnist_infovae_t*);
+int mmvae_mnist_infovae_num_params(const mmvae_mnist_infovae_t*);              /* 12 */
+int mmvae_mnist_infovae_param_info(const mmvae_mnist_infovae_t*, int i, char* name, int* ndim, int* shape, long long* offset);
+int mmvae_mnist_infovae_bind(mmvae_mnist_infovae_t*, float* params, float* grads);
+size_t mmvae_mnist_infovae_step_workspace_bytes(const mmvae_mnist_infovae_t*);
+int mmvae_mnist_infovae_step(mmvae_mnist_infovae_t*, const mmvae_mnist_infovae_step_io*, int training, int do_backward, void* stream);
+
 /* Exact t-SNE with a 2-component embedding (mnist/manifold.py: TSNE(n_components=2, perplexity=40, n_iter=300) over the test set's
  * latents), fp32 in and out, float64 sums in a fixed order, no atomics: two calls give identical bits.  3 <= n <= 32768; P is a
  * dense [n][n] fp32 matrix of the caller (4 GiB at the largest n); x [n][dim], 1 <= dim <= max_dim (256); 1 <= perplexity < n - 1.

@@ -120,6 +120,18 @@ class InfoVAEStepIO(C.Structure):
     ]
 
 
+class MnistInfoVAEStepIO(C.Structure):
+    """mmvae_mnist_infovae_step_io"""
+    _fields_ = [
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+        ("step_counter", C.c_void_p),
+        ("image", C.c_void_p), ("true_samples", C.c_void_p),
+        ("lambda_x", C.c_float), ("lambda_mmd", C.c_float),
+        ("seed", C.c_ulonglong),
+        ("sums", C.c_void_p), ("recon_image", C.c_void_p), ("z", C.c_void_p),
+    ]
+
+
 class TextStepIO(C.Structure):
     """mmvae_text_step_io"""
     _fields_ = [
@@ -373,6 +385,18 @@ SIGNATURES["mmvae_conv4s2_down"] = (_I, [_P] * 4 + [_I, _I, _F] + [_I] * 5 + [_P
 SIGNATURES["mmvae_conv4s2_up"] = (_I, [_P] * 4 + [_I, _I, _F] + [_I] * 5 + [_P, _LL, _P])
 SIGNATURES["mmvae_conv4s2_wgrad"] = (_I, [_P] * 4 + [_I, _F, _P] + [_I] * 5 + [_P, _LL, _P])
 SIGNATURES["mmvae_mmgen_geometry"] = (_I, [C.POINTER(_I)] * 6)
+SIGNATURES["mmvae_lin_act_workspace_bytes"] = (_LL, [_I] * 4)
+SIGNATURES["mmvae_lin_act_fwd"] = (_I, [_P] * 4 + [_I, _I, _I, _I, _F, _I] + [_P, _LL, _P])
+SIGNATURES["mmvae_lin_act_dgrad"] = (_I, [_P] * 4 + [_I, _I, _I, _I, _F, _I] + [_P, _LL, _P])
+SIGNATURES["mmvae_lin_act_wgrad"] = (_I, [_P] * 5 + [_I, _I, _I, _I, _F, _I] + [_P])
+SIGNATURES["mmvae_mnist_infovae_create"] = (_P, [_I, _I])
+SIGNATURES["mmvae_mnist_infovae_destroy"] = (None, [_P])
+SIGNATURES["mmvae_mnist_infovae_param_count"] = (_LL, [_P])
+SIGNATURES["mmvae_mnist_infovae_num_params"] = (_I, [_P])
+SIGNATURES["mmvae_mnist_infovae_param_info"] = (_I, [_P, _I, C.c_char_p, C.POINTER(_I), C.POINTER(_I), C.POINTER(_LL)])
+SIGNATURES["mmvae_mnist_infovae_bind"] = (_I, [_P, _P, _P])
+SIGNATURES["mmvae_mnist_infovae_step_workspace_bytes"] = (_SZ, [_P])
+SIGNATURES["mmvae_mnist_infovae_step"] = (_I, [_P, C.POINTER(MnistInfoVAEStepIO), _I, _I, _P])
 SIGNATURES["mmvae_mmgen_table_bytes"] = (_LL, [])
 SIGNATURES["mmvae_mmgen_build_tables"] = (_I, [_P])
 SIGNATURES["mmvae_mmgen_generate"] = (_I, [_P, _P, _I, _P, _I, _I, _I, _ULL, _ULL, _I] + [_P] * 7)

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmmvae_hip.so")
-SOURCES = ["gemm.hip", "convres.hip", "wgrad_ring.hip", "gemm_small.hip", "elementwise.hip", "text.hip", "thin.hip", "dec_last.hip", "conv1.hip", "multimnist.hip", "mmtext.hip", "mnist.hip", "mnist_f32.hip", "mnist_strip.hip", "mnist_iw.hip", "gemm_f32.hip", "celeba.hip", "celeba_iw.hip", "coco.hip", "coco_iw.hip", "coco_text.hip", "coco_text_bf16.hip", "mlp_tail.hip", "iw.hip", "nn_words.hip", "mmd.hip", "tsne.hip", "pixelcnn.hip", "causal_conv.hip", "head_nll.hip", "conv4s2.hip", "multimnist_gen.hip", "imgprep.hip", "capi.cpp", "comm.cpp", "util.cpp"]
+SOURCES = ["gemm.hip", "convres.hip", "wgrad_ring.hip", "gemm_small.hip", "elementwise.hip", "text.hip", "thin.hip", "dec_last.hip", "conv1.hip", "multimnist.hip", "mmtext.hip", "mnist.hip", "mnist_f32.hip", "mnist_strip.hip", "mnist_iw.hip", "gemm_f32.hip", "celeba.hip", "celeba_iw.hip", "coco.hip", "coco_iw.hip", "coco_text.hip", "coco_text_bf16.hip", "mlp_tail.hip", "iw.hip", "nn_words.hip", "mmd.hip", "tsne.hip", "pixelcnn.hip", "causal_conv.hip", "head_nll.hip", "conv4s2.hip", "infovae_mnist.hip", "multimnist_gen.hip", "imgprep.hip", "capi.cpp", "comm.cpp", "util.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", "-Wno-unused-value", "-ffp-contract=fast"]
 
 

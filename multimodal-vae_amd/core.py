@@ -214,6 +214,52 @@ class CocoState(PlanState):
         return super()._c(fn, *args)
 
 
+class MnistInfoVAEState(PlanState):
+    """mnist/model.py:238-279 InfoVAE: a small fp32 plan of its own (mmvae_mnist_infovae_*), the 12 tensors of its ``state_dict``
+    flat in ``params`` (each starts 16-byte aligned: ``table`` offsets, not a running sum), every gradient in ``grads``.  No
+    BatchNorm, no packed weight copies: ``pack_weights`` has nothing to do."""
+    API = "mnist_infovae"
+
+    def __init__(self, n_latents: int, device: torch.device):
+        if device.type != "cuda":
+            raise MMVAEError("the MMVAE HIP engine needs a gfx950 GPU (device=%s); there is no CPU fallback" % device)
+        _lib.init_device(device.index if device.index is not None else torch.cuda.current_device())
+        self.device = device
+        self.n_latents = int(n_latents)
+        self._plans: Dict[int, int] = {}
+        h = self._handle(1, bind=False)
+        self.nparams = self._c("param_count", h)
+        self.table: List[Tuple[str, Tuple[int, ...], int]] = []
+        name = C.create_string_buffer(128)
+        nd, off = C.c_int(), C.c_longlong()
+        shape = (C.c_int * 4)()
+        for i in range(self._c("num_params", h)):
+            self._c("param_info", h, i, name, C.byref(nd), shape, C.byref(off))
+            self.table.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)), off.value))
+        self.bn_table: List[Tuple[str, int, int]] = []
+        f32 = dict(dtype=torch.float32, device=device)
+        self.params = torch.zeros(self.nparams, **f32)
+        self.grads = torch.zeros(self.nparams, **f32)
+        self.bn_stats = torch.zeros(4, **f32)
+        self.bn_nbt = torch.zeros(1, dtype=torch.int64, device=device)
+        self._bind(h)
+        self.packed_version = -1
+
+    def _bind(self, h: int) -> None:
+        self._c("bind", h, ptr(self.params), ptr(self.grads))
+
+    def workspace_bytes(self, batch: int) -> int:
+        return self._c("step_workspace_bytes", self.plan(batch))
+
+    module_workspace_bytes = workspace_bytes
+
+    def grad_map(self):
+        raise MMVAEError("the MNIST InfoVAE plan keeps no packed gradients")
+
+    def pack_weights(self) -> None:
+        self.pack_pending = False
+
+
 class StepOutputs:
     """Lazy view of the loss sums of one fused step (no host sync until a value is read)."""
 
@@ -829,29 +875,52 @@ class FusedInfoVAEStep(_SinglePassStep):
     image decoder) -> lambda_x * mean BCE + lambda_mmd * MMD(prior samples, z) + kl_lambda * KL / B -> backward -> Adam over the image
     parameters, one enqueue (mmvae_coco_infovae_step: the image-only step with the MMD sweep beside the decoder).  ``state`` is a
     ``CocoState``; the caption half keeps its values and gets a gradient of exactly 0.  The reference's loss is the default
-    (1, 1, 0)."""
+    (1, 1, 0).  On a ``MnistInfoVAEState`` it is the step of mnist/train_infovae.py:123-130 (mmvae_mnist_infovae_step):
+    lambda_x * mean squared error + lambda_mmd * MMD, no KL term, plain Adam over the whole flat buffer (the reference's lr is 1e-3)."""
 
     _KIND = "InfoVAE"
 
     def __init__(self, state: PlanState, batch: int, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  lambda_x: float = 1.0, lambda_mmd: float = 1.0, kl_lambda: float = 0.0, seed: int = 1234):
-        if state.API != "coco":
-            raise MMVAEError("FusedInfoVAEStep: no InfoVAE step for the '%s' family (COCO has one)" % state.API)
+        if state.API not in ("coco", "mnist_infovae"):
+            raise MMVAEError("FusedInfoVAEStep: no InfoVAE step for the '%s' family (COCO has one on its plan, MNIST's InfoVAE a "
+                             "plan of its own: MnistInfoVAEState)" % state.API)
         super().__init__(state, batch, lr, betas, eps, seed)
         self.lambda_x, self.lambda_mmd, self.kl_lambda = lambda_x, lambda_mmd, kl_lambda
+        self.mnist = state.API == "mnist_infovae"
+        if self.mnist:
+            # mnist/train_infovae.py:45-76: mean squared error + MMD, no KL term; every gradient lands in ``grads`` and the optimizer
+            # is the plain Adam kernel over the flat buffer
+            self.kl_lambda = 0.0
+            self.pixels = 784
+            self._packed = False
+            return
         self.enc_dropout = True
         self.pixels = 3 * 32 * 32
         self._image_range(state)
 
     def _workspace_bytes(self, state: PlanState, batch: int) -> int:
+        if state.API == "mnist_infovae":
+            return state.workspace_bytes(batch)
         return state._c("infovae_step_workspace_bytes", state.plan(batch))
 
     def _outputs(self) -> InfoVAEStepOutputs:
         return InfoVAEStepOutputs(self.sums, self.B * self.pixels, self.kl_lambda / self.B, self.lambda_x, self.lambda_mmd)
 
+    def _mnist_forward_backward(self, image, training, backward, true_samples, recon_image, z) -> InfoVAEStepOutputs:
+        """mmvae_mnist_infovae_step: images (B, 1, 28, 28) or flattened (B, 784); slot 0 of the sums is the squared-error sum"""
+        if tuple(image.shape) not in ((self.B, 1, 28, 28), (self.B, 784)):
+            raise MMVAEError("FusedInfoVAEStep: expected images of shape %s (got %s)" % ((self.B, 1, 28, 28), tuple(image.shape)))
+        io = self._io(_lib.MnistInfoVAEStepIO, (("image", image),), dict(true_samples=true_samples, recon_image=recon_image, z=z), backward)
+        return self._step("mmvae_mnist_infovae_step", io, training, backward)
+
     def forward_backward(self, image, training=True, backward=True, eps=None, enc_mask1=None, enc_mask2=None, true_samples=None,
                          recon_image=None, mu=None, logvar=None, z=None, _defer_unpack=False) -> InfoVAEStepOutputs:
         assert image.is_contiguous() and image.dtype == torch.float32
+        if true_samples is not None:
+            assert true_samples.is_contiguous() and true_samples.dtype == torch.float32 and tuple(true_samples.shape) == (self.B, self.D)
+        if self.mnist:
+            return self._mnist_forward_backward(image, training, backward, true_samples, recon_image, z)
         if tuple(image.shape) != (self.B, 3, 32, 32):
             raise MMVAEError("FusedInfoVAEStep: expected images of shape %s (got %s)" % ((self.B, 3, 32, 32), tuple(image.shape)))
         if true_samples is not None:

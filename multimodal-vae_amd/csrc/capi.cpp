@@ -16,6 +16,7 @@
 #include "causal_conv.h"
 #include "head_nll.h"
 #include "conv4s2.h"
+#include "infovae_mnist.h"
 #include "multimnist_gen.h"
 #include "imgprep.h"
 #include <cstring>
@@ -1008,6 +1009,55 @@ int mmvae_conv4s2_wgrad(const float* s_side, const float* l_side, const float* y
     MMVAE_REQUIRE(s_side && l_side && dw, "conv4s2_wgrad: null argument");
     MMVAE_REQUIRE(c4_act_ok(act) && !(y_s && y_l), "conv4s2_wgrad: act = %d (need 0..3), and one side at most carries a gradient", act);
     return guarded([&] { return launch_c4_wgrad(s, s_side, l_side, y_s, y_l, act, slope, dw, ws, S(st)); });
+}
+
+// ---- fp32 Linear + activation layers and the MNIST InfoVAE step (infovae_mnist.h)
+static int lin_prepare(const char* what, const LinShape& s, int which, const void* ws, long long ws_bytes) {
+    const char* e = lin_shape_error(s);
+    MMVAE_REQUIRE(e == nullptr, "%s: rows = %d, N = %d, K = %d, act = %d, perm = %d: %s", what, s.rows, s.N, s.K, s.act, s.perm, e);
+    const long long need = (long long)(which == 0 ? lin_fwd_workspace_bytes(s) : lin_dgrad_workspace_bytes(s));
+    return need > 0 ? ws_fits(what, ws, ws_bytes, need, true) : MMVAE_OK;
+}
+long long mmvae_lin_act_workspace_bytes(int rows, int n, int k, int which) {
+    const LinShape s{rows, n, k, LIN_ACT_NONE, 0, 0.f};
+    if (lin_shape_error(s) || which < 0 || which > 1) return 0;
+    return (long long)(which == 0 ? lin_fwd_workspace_bytes(s) : lin_dgrad_workspace_bytes(s));
+}
+int mmvae_lin_act_fwd(const float* x, const float* w, const float* b, float* y, int rows, int n, int k, int act, float slope, int perm,
+                      void* ws, long long ws_bytes, void* st) {
+    const LinShape s{rows, n, k, act, perm, slope};
+    MMVAE_TRY(lin_prepare("lin_act_fwd", s, 0, ws, ws_bytes));
+    return guarded([&] { return launch_lin_fwd(s, x, w, b, y, ws, S(st)); });
+}
+int mmvae_lin_act_dgrad(const float* g, const float* y, const float* w, float* dx, int rows, int n, int k, int act, float slope, int perm,
+                        void* ws, long long ws_bytes, void* st) {
+    const LinShape s{rows, n, k, act, perm, slope};
+    MMVAE_TRY(lin_prepare("lin_act_dgrad", s, 1, ws, ws_bytes));
+    return guarded([&] { return launch_lin_dgrad(s, g, y, w, dx, ws, S(st)); });
+}
+int mmvae_lin_act_wgrad(const float* g, const float* y, const float* x, float* dw, float* db, int rows, int n, int k, int act, float slope,
+                        int perm, void* st) {
+    const LinShape s{rows, n, k, act, perm, slope};
+    return guarded([&] { return launch_lin_wgrad(s, g, y, x, dw, db, S(st)); });
+}
+mmvae_mnist_infovae_t* mmvae_mnist_infovae_create(int n_latents, int batch) {
+    try { return mnist_infovae_create(n_latents, batch); } catch (...) { mmvae_set_error("mnist_infovae_create failed"); return nullptr; }
+}
+void mmvae_mnist_infovae_destroy(mmvae_mnist_infovae_t* p) { mnist_infovae_destroy(p); }
+long long mmvae_mnist_infovae_param_count(const mmvae_mnist_infovae_t* p) { return mnist_infovae_base(const_cast<mmvae_mnist_infovae_t*>(p))->nparams; }
+int mmvae_mnist_infovae_num_params(const mmvae_mnist_infovae_t* p) { return (int)mnist_infovae_base(const_cast<mmvae_mnist_infovae_t*>(p))->params.size(); }
+int mmvae_mnist_infovae_param_info(const mmvae_mnist_infovae_t* p, int i, char* name, int* ndim, int* shape, long long* offset) {
+    return pb_param_info(mnist_infovae_base(const_cast<mmvae_mnist_infovae_t*>(p)), i, name, ndim, shape, offset);
+}
+int mmvae_mnist_infovae_bind(mmvae_mnist_infovae_t* p, float* params, float* grads) {
+    return guarded([&] { return mnist_infovae_bind(p, params, grads); });
+}
+size_t mmvae_mnist_infovae_step_workspace_bytes(const mmvae_mnist_infovae_t* p) { return mnist_infovae_step_workspace_bytes(p); }
+int mmvae_mnist_infovae_step(mmvae_mnist_infovae_t* p, const mmvae_mnist_infovae_step_io* io, int training, int do_backward, void* stream) {
+    return guarded([&]() -> int {
+        MMVAE_REQUIRE(p && io, "mmvae_mnist_infovae_step: null argument");
+        return mnist_infovae_step(p, *io, training, do_backward, S(stream));
+    });
 }
 
 // ---- MultiMNIST canvases made on the device (multimnist_gen.h, mmgen_core.h)

@@ -8,6 +8,8 @@ is a call into libmmvae_hip.so.  No CPU fallback.  ``FusedTrainer`` runs the who
 ``InfoVAE`` (mnist/model.py:238-279) is the exception: a plain torch module that runs wherever torch runs.
 ``set_infovae_backend(vae, "hip")`` routes its four bias-free 4 x 4 stride-2 convolutions, each with its activation, through
 ``conv4s2.down4s2`` / ``up4s2`` (csrc/conv4s2.hip); its four ``nn.Linear`` layers stay torch ops under both backends.
+``FusedInfoVAE`` is the same model on a plan of its own: ``InfoVAETrainer`` runs its whole training step as one enqueue
+(csrc/infovae_mnist.hip: the four Linears on the fp32 MFMA, the loss tail, the MMD sweep beside the decoder).
 """
 from __future__ import annotations
 
@@ -17,8 +19,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._lib import MMVAEError
-from .core import FusedImageStep, FusedMnistStep, MnistState, StepOutputs, Trainer, load_vae_checkpoint
+from ._lib import MMVAEError, call, ptr
+from .core import (FusedImageStep, FusedInfoVAEStep, FusedMnistStep, MnistInfoVAEState, MnistState, StepOutputs, Trainer,
+                   load_vae_checkpoint)
 from .modules import DECODER, ExpertsVAEBase, ProductOfExperts, VAEBase, _BCEMeanFn, _Core, _KLSumFn, _NLLMeanFn, run_module
 
 ENCODER_FWD = ("x", "training", "out")       # the C arguments of the two encoders' forward (modules.run_module); the decoders' are DECODER
@@ -356,6 +359,90 @@ def set_infovae_backend(vae, backend):
         raise MMVAEError("set_infovae_backend: a mnist.InfoVAE expected (got %s)" % type(vae).__name__)
     vae.conv_backend = backend
     return vae
+
+
+class FusedInfoVAE(nn.Module):
+    """``InfoVAE`` (mnist/model.py:238-279) on the plan of the one-enqueue step (``mmvae_mnist_infovae_*``): same ``state_dict`` keys
+    and shapes, so either class loads the other's checkpoint and a reference checkpoint loads strict.  On the device its parameters
+    are views of the plan's flat buffer, which ``InfoVAETrainer`` updates in place.  ``encode`` / ``decode`` / ``forward`` run the HIP
+    layers themselves (``conv4s2`` down / up, ``mmvae_lin_act_fwd`` with the (c, h, w) <-> channels-last permutation folded into the
+    two large Linears) and build no autograd graph: this class is trained by ``InfoVAETrainer``, ``InfoVAE`` through autograd.
+    Device-only: a CPU tensor raises ``MMVAEError``."""
+
+    def __init__(self, n_latents=20):
+        super().__init__()
+        self.n_latents = n_latents
+        self.encoder_conv = nn.Sequential(
+            nn.Conv2d(1, 64, 4, 2, 1, bias=False), nn.LeakyReLU(0.1, inplace=True),
+            nn.Conv2d(64, 128, 4, 2, 1, bias=False), nn.LeakyReLU(0.1, inplace=True))
+        self.encoder_fc = nn.Sequential(nn.Linear(128 * 7 * 7, 1024), nn.LeakyReLU(0.1, inplace=True), nn.Linear(1024, n_latents))
+        self.decoder_fc = nn.Sequential(nn.Linear(n_latents, 1024), nn.ReLU(True), nn.Linear(1024, 128 * 7 * 7), nn.ReLU(True))
+        self.decoder_conv = nn.Sequential(
+            nn.ConvTranspose2d(128, 64, 4, 2, 1, bias=False), nn.ReLU(True),
+            nn.ConvTranspose2d(64, 1, 4, 2, 1, bias=False))
+        self._core = _Core(self, "", n_latents, MnistInfoVAEState)
+
+    def _sync(self, x):
+        if not torch.is_tensor(x) or x.device.type != "cuda":
+            raise MMVAEError("FusedInfoVAE runs on a gfx950 GPU only (got %s); mnist.InfoVAE is the torch module of the same weights"
+                             % (x.device if torch.is_tensor(x) else type(x).__name__))
+        self._core.sync(x.device)
+
+    @staticmethod
+    def _conv(entry, src, weight, act, dims, out_elems):
+        from ._ops import CONV_WS, stream
+        out = torch.empty(out_elems, dtype=torch.float32, device=src.device)
+        ws = CONV_WS.get(src.device, int(call("mmvae_conv4s2_workspace_bytes", *dims)))
+        call(entry, ptr(src), None, ptr(weight), ptr(out), 0, act, 0.1, *dims, ptr(ws), ws.numel(), stream())
+        return out
+
+    @staticmethod
+    def _linear(x, lin, rows, act, perm):
+        from ._ops import CONV_WS, stream
+        N, K = lin.weight.shape
+        y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
+        ws = CONV_WS.get(x.device, int(call("mmvae_lin_act_workspace_bytes", rows, N, K, 0)))
+        call("mmvae_lin_act_fwd", ptr(x), ptr(lin.weight), ptr(lin.bias), ptr(y), rows, N, K, act, 0.1, perm, ptr(ws), ws.numel(), stream())
+        return y
+
+    @torch.no_grad()
+    def encode(self, x):
+        self._sync(x)
+        B = x.shape[0]
+        x = x.detach().float().contiguous().reshape(B, 784)          # (one channel: NCHW and channels-last coincide)
+        with torch.cuda.device(x.device):
+            h = self._conv("mmvae_conv4s2_down", x, self.encoder_conv[0].weight, 2, (B, 1, 64, 28, 28), B * 196 * 64)
+            h = self._conv("mmvae_conv4s2_down", h, self.encoder_conv[2].weight, 2, (B, 64, 128, 14, 14), B * 6272)
+            h = self._linear(h, self.encoder_fc[0], B, 2, 1)
+            return self._linear(h, self.encoder_fc[2], B, 0, 0)
+
+    @torch.no_grad()
+    def decode(self, z):
+        self._sync(z)
+        B = z.shape[0]
+        z = z.detach().float().contiguous()
+        with torch.cuda.device(z.device):
+            h = self._linear(z, self.decoder_fc[0], B, 1, 0)
+            h = self._linear(h, self.decoder_fc[2], B, 1, 1)
+            h = self._conv("mmvae_conv4s2_up", h, self.decoder_conv[0].weight, 1, (B, 64, 128, 14, 14), B * 196 * 64)
+            return self._conv("mmvae_conv4s2_up", h, self.decoder_conv[2].weight, 3, (B, 1, 64, 28, 28), B * 784).view(B, 1, 28, 28)
+
+    def forward(self, x):
+        z = self.encode(x)
+        return self.decode(z), z
+
+
+class InfoVAETrainer(Trainer):
+    """``InfoVAETrainer(vae, batch_size, lr=1e-3)(image)``: mnist/train_infovae.py:123-130 on a ``FusedInfoVAE`` as one enqueue
+    (core.FusedInfoVAEStep on the model's own plan, mmvae_mnist_infovae_step) + one Adam launch over the flat buffer.
+    ``out.total()`` is the reference's loss, mean squared error + MMD(prior samples, z); ``true_samples=`` supplies the prior samples
+    (default: drawn on the device).  Images come as (B, 1, 28, 28) or flattened (B, 784)."""
+    ENGINE, KL_LAMBDA = FusedInfoVAEStep, None
+
+    def __init__(self, vae, batch_size: int, lr: float = 1e-3, seed: int = 1234, **engine_kw):
+        if not isinstance(vae, FusedInfoVAE):
+            raise MMVAEError("InfoVAETrainer: a mnist.FusedInfoVAE expected (got %s)" % type(vae).__name__)
+        super().__init__(vae, batch_size, lr=lr, seed=seed, **engine_kw)
 
 
 def mmd_terms_torch(x, y):

@@ -12,6 +12,11 @@ through autograd wherever torch runs; the loss is ``mnist.infovae_loss`` (mean s
 ``nn.Linear`` layers, the loss and Adam stay torch ops (on the device the MMD term is the fused op of ``mmd.py``); the checkpoint has
 the same ``state_dict`` under either backend.
 
+``--fused`` (needs ``--cuda``) trains ``mnist.FusedInfoVAE`` with ``mnist.InfoVAETrainer``: the batch loop body is ONE enqueue
+(csrc/infovae_mnist.hip: the convolutions above, the four Linears on the fp32 MFMA, the loss tail, the MMD sweep beside the decoder,
+every gradient) plus one Adam launch.  Same printed lines, checkpoint dict and samples; the fused plan takes whole batches, so a
+trailing partial batch of an epoch is left out.  The module route stays the default.
+
 Data: ``--data FILE.pt`` is ``(uint8 (N,28,28), int64 labels (N,))``, the file ``evaluate loglik --dataset mnist`` reads (torchvision's
 ``processed/training.pt``); the last tenth (at least one batch) is held out for ``test()``.  Or ``--synthetic N``.  Checkpoints go to
 ``--out``/infovae (the reference: ./trained_models/infovae), per-epoch ``vae.decode(randn(64, n_latents))`` to ``--results`` as
@@ -41,6 +46,8 @@ def build_parser() -> argparse.ArgumentParser:
     # additions
     parser.add_argument('--conv_backend', choices=INFOVAE_BACKENDS, default='torch',
                         help='convolutions through torch ops or through the HIP 4 x 4 stride-2 op (hip needs --cuda; default: torch)')
+    parser.add_argument('--fused', action='store_true', default=False,
+                        help='the whole training step as one enqueue of HIP kernels (mnist.FusedInfoVAE + InfoVAETrainer; needs --cuda)')
     parser.add_argument('--data', type=str, default='', metavar='FILE.pt', help='(uint8 images (N,28,28), int64 labels (N,))')
     parser.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic MNIST-shaped images instead of a file')
     parser.add_argument('--out', type=str, default='./trained_models', help='checkpoints go to OUT/infovae (reference: ./trained_models/infovae)')
@@ -52,6 +59,8 @@ def build_parser() -> argparse.ArgumentParser:
 def resolve(args):
     if args.conv_backend == 'hip' and not (args.cuda and torch.cuda.is_available()):
         raise SystemExit('--conv_backend hip runs on the GPU only: pass --cuda on a machine with a gfx950 device (there is no CPU fallback)')
+    if args.fused and not (args.cuda and torch.cuda.is_available()):
+        raise SystemExit('--fused runs on the GPU only: pass --cuda on a machine with a gfx950 device (there is no CPU fallback)')
     args.cuda = args.cuda and torch.cuda.is_available()
     return args
 
@@ -92,8 +101,27 @@ def main(argv=None) -> dict:
         for i in range(0, len(images), args.batch_size):
             yield images[order[i:i + args.batch_size]].float().div_(255.0).unsqueeze(1)
 
-    vae = set_infovae_backend(InfoVAE(n_latents=args.n_latents), args.conv_backend).to(dev)
-    optimizer = torch.optim.Adam(vae.parameters(), lr=args.lr)
+    if args.fused:
+        from .mnist import FusedInfoVAE, InfoVAETrainer
+        from .train_common import adam_state_dict
+        if min(len(tr), len(te)) < args.batch_size:
+            raise SystemExit('a split has fewer images than one batch of %d (the fused plan takes whole batches)' % args.batch_size)
+        vae = FusedInfoVAE(n_latents=args.n_latents).to(dev)
+        trainer = InfoVAETrainer(vae, args.batch_size, lr=args.lr, seed=args.seed)
+        whole = lambda it: (b for b in it if len(b) == args.batch_size)
+        step = lambda data: trainer(data).total()
+        test_loss_of = lambda data: trainer.evaluate(data).total()
+        optimizer_state = lambda: adam_state_dict(vae, trainer.engine)
+    else:
+        vae = set_infovae_backend(InfoVAE(n_latents=args.n_latents), args.conv_backend).to(dev)
+        optimizer = torch.optim.Adam(vae.parameters(), lr=args.lr)
+        whole = lambda it: it
+        step = lambda data: train_step(vae, optimizer, data)
+
+        def test_loss_of(data):
+            recon_data, z = vae(data)
+            return infovae_loss(recon_data, data, z)
+        optimizer_state = optimizer.state_dict
     n_batches = (len(tr) + args.batch_size - 1) // args.batch_size
 
     def train(epoch):
@@ -106,8 +134,8 @@ def main(argv=None) -> dict:
                 loss_meter.update(float(v), n)
             pending.clear()
 
-        for batch_idx, data in enumerate(batches(tr)):
-            pending.append((train_step(vae, optimizer, data), len(data)))
+        for batch_idx, data in enumerate(whole(batches(tr))):
+            pending.append((step(data), len(data)))
             if batch_idx % args.log_interval == 0:
                 drain()
                 print('Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f}'.format(
@@ -120,9 +148,8 @@ def main(argv=None) -> dict:
     def test():
         vae.eval()
         test_loss, n = torch.zeros((), device=dev), 0
-        for data in batches(te):
-            recon_data, z = vae(data)
-            test_loss += infovae_loss(recon_data, data, z)
+        for data in whole(batches(te)):
+            test_loss += test_loss_of(data)
             n += 1
         test_loss = float(test_loss) / n
         print('====> Test Epoch\tLoss: {:.4f}'.format(test_loss))
@@ -142,7 +169,7 @@ def main(argv=None) -> dict:
             'state_dict': vae.state_dict(),
             'best_loss': best_loss,
             'n_latents': args.n_latents,
-            'optimizer': optimizer.state_dict(),
+            'optimizer': optimizer_state(),
         }, is_best, folder=folder)
         if args.results:
             os.makedirs(args.results, exist_ok=True)
