@@ -75,6 +75,9 @@ int mmvae_mm_pack_weights(mmvae_mm_t*, void* stream);    /* refresh bf16 GEMM-la
 /* map[i] (int32, param_count entries) = where flat parameter i's packed gradient lives: >= 0 index into gpk, <= -2:
  * -(index + 2) into gpk_vec, -1 none.  Built once per parameter layout; input of mmvae_adam_step_packed. */
 int mmvae_mm_grad_map(mmvae_mm_t*, int* map, void* stream);
+/* Test aid: the weight pack run over the gradient descriptor table.  src (flat, parameter layout) -> out_bf16 [gpk_elems] bf16 and
+ * out_vec [gpk_vec_elems] fp32: element i of src lands at the place mmvae_mm_grad_map names for i (the inverse, by other code). */
+int mmvae_mm_debug_pack_as_grads(mmvae_mm_t*, const float* src, void* out_bf16, float* out_vec, void* stream);
 
 /* Optimizer arguments of mmvae_mm_step_io.early_adam (torch.optim.Adam semantics, as mmvae_adam_step_packed). */
 struct mmvae_early_adam {
@@ -225,6 +228,7 @@ int mmvae_mnist_bind(mmvae_mnist_t*, float* params, float* grads, float* bn_stat
                      void* packed_bf16, float* packed_vec, float* gpk, float* gpk_vec, void* desc_dev, void* gdesc_dev);
 int mmvae_mnist_pack_weights(mmvae_mnist_t*, void* stream);
 int mmvae_mnist_grad_map(mmvae_mnist_t*, int* map, void* stream);                /* as mmvae_mm_grad_map */
+int mmvae_mnist_debug_pack_as_grads(mmvae_mnist_t*, const float* src, void* out_bf16, float* out_vec, void* stream);
 /* The train() closure body of mnist/train.py:131-147 (3 passes, 3 losses, backward): same contract as mmvae_mm_step */
 typedef struct {
     void* ws; size_t ws_bytes;
@@ -295,6 +299,7 @@ int mmvae_celeba_bind(mmvae_celeba_t*, float* params, float* grads, float* bn_st
                       void* packed_bf16, float* packed_vec, float* gpk, float* gpk_vec, void* desc_dev, void* gdesc_dev);
 int mmvae_celeba_pack_weights(mmvae_celeba_t*, void* stream);
 int mmvae_celeba_grad_map(mmvae_celeba_t*, int* map, void* stream);                /* as mmvae_mm_grad_map */
+int mmvae_celeba_debug_pack_as_grads(mmvae_celeba_t*, const float* src, void* out_bf16, float* out_vec, void* stream);
 /* The train() closure body of celeba/train.py:131-147 (3 passes, 3 losses, backward) */
 typedef struct {
     void* ws; size_t ws_bytes;
@@ -390,6 +395,7 @@ int mmvae_coco_bind(mmvae_coco_t*, float* params, float* grads, float* bn_stats,
                     void* packed, float* packed_vec, float* gpk, float* gpk_vec, void* desc_dev, void* gdesc_dev);
 int mmvae_coco_pack_weights(mmvae_coco_t*, void* stream);
 int mmvae_coco_grad_map(mmvae_coco_t*, int* map, void* stream);                /* as mmvae_mm_grad_map */
+int mmvae_coco_debug_pack_as_grads(mmvae_coco_t*, const float* src, void* out_bf16, float* out_vec, void* stream);
 /* The train() closure body of coco/train.py:138-173 (3 passes, 3 losses, backward) */
 typedef struct {
     void* ws; size_t ws_bytes;
@@ -749,6 +755,7 @@ int mmvae_mmtext_bind(mmvae_mmtext_t*, float* params, float* grads, float* bn_st
                       void* packed_bf16, float* packed_vec, float* gpk, float* gpk_vec, void* desc_dev, void* gdesc_dev);
 int mmvae_mmtext_pack_weights(mmvae_mmtext_t*, void* stream);
 int mmvae_mmtext_grad_map(mmvae_mmtext_t*, int* map, void* stream);
+int mmvae_mmtext_debug_pack_as_grads(mmvae_mmtext_t*, const float* src, void* out_bf16, float* out_vec, void* stream);
 /* Granular modules, with the signatures and the meaning of mmvae_mm_text_* (keep: [4][B][H] flags). */
 int mmvae_mmtext_encoder_fwd(mmvae_mmtext_t*, void* ws, size_t ws_bytes, const long long* text, float* out_mu_logvar, void* stream);
 int mmvae_mmtext_encoder_bwd(mmvae_mmtext_t*, void* ws, size_t ws_bytes, const long long* text, const float* d_out, void* stream);

@@ -262,6 +262,7 @@ def _plan_api(pfx):
         "mmvae_%s_bind" % pfx: (_I, [_P] * 11),
         "mmvae_%s_pack_weights" % pfx: (_I, [_P, _P]),
         "mmvae_%s_grad_map" % pfx: (_I, [_P, _P, _P]),
+        "mmvae_%s_debug_pack_as_grads" % pfx: (_I, [_P, _P, _P, _P, _P]),
     }
 
 

@@ -78,6 +78,15 @@ static int pb_grad_map(PlanBase* P, int* map, hipStream_t s) {
     MMVAE_REQUIRE(map != nullptr, "grad_map: null argument");
     return launch_unpack_map(P->buf.gdesc_dev, P->gk.d.data(), (int)P->gk.d.size(), P->nparams, P->gk.mat_elems, map, s);
 }
+// The weight pack (pack_block) run over the GRADIENT descriptor table: `src` (flat, parameter layout) lands where the packed gradient
+// of each element lives -- bf16 [gpk_elems] for the matrices, fp32 [gpk_vec_elems] for the fp32 packs.  The inverse of grad_map,
+// derived by other code: what the tests compare the map with.
+static int pb_debug_pack_as_grads(PlanBase* P, const float* src, void* out_bf16, float* out_vec, hipStream_t s) {
+    MMVAE_TRY(check_bound(P));
+    MMVAE_REQUIRE(src && out_bf16 && out_vec, "debug_pack_as_grads: null argument");
+    MMVAE_REQUIRE(!P->gk.d.empty(), "debug_pack_as_grads: the plan keeps no packed gradients");
+    return launch_pack(P->buf.gdesc_dev, P->gk.d.data(), (int)P->gk.d.size(), src, (bf16*)out_bf16, out_vec, s);
+}
 #define MMVAE_PLAN_API(pfx, T, BASE)                                                                                      \
     long long mmvae_##pfx##_param_count(const T* p) { return BASE(p)->nparams; }                                          \
     int mmvae_##pfx##_num_params(const T* p) { return (int)BASE(p)->params.size(); }                                      \
@@ -115,6 +124,9 @@ static int pb_grad_map(PlanBase* P, int* map, hipStream_t s) {
     }                                                                                                                     \
     int mmvae_##pfx##_grad_map(T* p, int* map, void* stream) {                                                            \
         return guarded([&] { return pb_grad_map(BASE(p), map, S(stream)); });                                             \
+    }                                                                                                                     \
+    int mmvae_##pfx##_debug_pack_as_grads(T* p, const float* src, void* out_bf16, float* out_vec, void* stream) {         \
+        return guarded([&] { return pb_debug_pack_as_grads(BASE(p), src, out_bf16, out_vec, S(stream)); });               \
     }
 static inline PlanBase* mm_b(const mmvae_mm_t* p) { return mm_base(const_cast<mmvae_mm_t*>(p)); }
 static inline PlanBase* mmtext_b(const mmvae_mmtext_t* p) { return mmtext_base(const_cast<mmvae_mmtext_t*>(p)); }

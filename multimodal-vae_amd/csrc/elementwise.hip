@@ -1195,10 +1195,15 @@ int launch_kl_bwd(const float* mu, const float* lv, int n, float coef, const flo
     return mmvae_check_launch("kl_bwd");
 }
 int launch_normal(float* out, long long n, unsigned long long seed, const long long* step, unsigned stream_id, hipStream_t s) {
+    MMVAE_REQUIRE(out != nullptr && n >= 0, "normal: null output or n=%lld < 0", n);
+    if (n == 0) return MMVAE_OK;
     hipLaunchKernelGGL(normal_kernel, dim3(nblocks((n + 3) / 4, TPB, 512)), dim3(TPB), 0, s, out, n, seed, step, stream_id);
     return mmvae_check_launch("normal");
 }
 int launch_keep_mask(uint8_t* out, long long n, float p, unsigned long long seed, const long long* step, unsigned stream_id, hipStream_t s) {
+    MMVAE_REQUIRE(out != nullptr && n >= 0, "keep_mask: null output or n=%lld < 0", n);
+    MMVAE_REQUIRE(p >= 0.0f && p <= 1.0f, "keep_mask: p=%g is no probability in [0, 1]", (double)p);      // (a NaN fails both comparisons)
+    if (n == 0) return MMVAE_OK;
     hipLaunchKernelGGL(keep_mask_kernel, dim3(nblocks((n + 3) / 4, TPB, 512)), dim3(TPB), 0, s, out, n, p, seed, step, stream_id);
     return mmvae_check_launch("keep_mask");
 }
@@ -1261,6 +1266,9 @@ int launch_latent1_bwd_f32(const Latent1BwdF32Args& a, hipStream_t s) {
 int launch_adam(const AdamArgs& a_in, hipStream_t s) {
     AdamArgs a = a_in;
     MMVAE_REQUIRE(a.step != nullptr, "adam: step counter is null");
+    MMVAE_REQUIRE(a.p && a.g && a.m && a.v, "adam: null parameter, gradient or moment buffer");
+    MMVAE_REQUIRE(a.n >= 1, "adam: n=%lld elements (the kernel reads g[0])", a.n);
+    MMVAE_REQUIRE(a.gmap == nullptr || (a.gpk && a.gpk_vec && a.g_out), "adam: gradient map without packed gradient buffers");
     MMVAE_REQUIRE(a.nr >= 0 && a.nr <= 4, "adam: at most 4 element ranges");
     if (a.nr == 0) { a.nr = 1; a.roff[0] = 0; a.rlen[0] = a.n; }
     long long vecs = 0;
